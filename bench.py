@@ -1,6 +1,6 @@
 """Headline benchmark: BLS12-381 Fr NTT butterflies/s (+ G1 MSM scalar-muls/s) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1 runs either under torch.distributed.run (one rank per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the
 environment) or bare: with WORLD_SIZE unset this process starts the N ranks itself as child processes (launch_ranks),
@@ -36,6 +36,28 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK = 8.0e12  # B/s, MI355X_MICROARCH.md
+WARMUP_S = 1.0             # s: the headline's shortest warm-up
+DUMP_MAX_ROWS = 1 << 16    # --dump-outputs: rows kept of each output (8 float64 words per Fr element: 4 MB per array)
+DUMP_SEED = 0x44554D50
+
+
+def dump_rows(n):
+    """--dump-outputs: the rows of an n-row output that are written -- all of them up to DUMP_MAX_ROWS, otherwise a fixed
+    seeded sample (sorted), the same in every run and every build."""
+    if n <= DUMP_MAX_ROWS:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_MAX_ROWS, replace=False))
+
+
+def write_dump(path, arrays):
+    """--dump-outputs: each uint64 array (Fr elements as [rows, 4] Montgomery limbs) goes to `path/<name>.npy` as float64
+    [rows, 8]: every limb split into its low and high 32-bit halves, low first, so the values are exact."""
+    os.makedirs(path, exist_ok=True)
+    out = {nm: np.stack([a & 0xFFFFFFFF, a >> 32], axis=-1).reshape(a.shape[0], -1).astype(np.float64)
+           for nm, a in arrays.items()}
+    assert sum(v.nbytes for v in out.values()) <= 64 << 20, "--dump-outputs: more than 64 MB"
+    for nm, v in out.items():
+        np.save(os.path.join(path, nm + ".npy"), v)
 
 
 PMC_ROUND = "r06"          # the round whose committed PMC summaries describe THIS tree's kernels
@@ -322,7 +344,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=10,
+                    help=f"untimed steps before the timed ones: at least this many and at least {WARMUP_S:g} s of them")
     ap.add_argument("--log-n", type=int, default=20)
     ap.add_argument("--msm-log-n", type=int, default=20)
     ap.add_argument("--msm-steps", type=int, default=5)
@@ -361,7 +384,13 @@ def main():
     ap.add_argument("--child-cmd", default=None,
                     help="bare `--gpus N` only: the command each rank runs instead of this script (tests drive the launcher "
                          "with a stub child)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed on rank 0 (the forward and the inverse "
+                         "transform) to DIR/<name>.npy: float64 [rows, 8], the 32-bit halves of the Montgomery limbs, low "
+                         f"first; up to {DUMP_MAX_ROWS} rows, a fixed seeded sample beyond that")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher around us: be the launcher.  Nothing above has touched the GPU (imports: numpy) and nothing in
@@ -477,36 +506,41 @@ def main():
     # dominant one's -- come from a separate, fully profiled loop of the same step right after it
     step()                                                          # first launches: tables, code load
     barrier()
-    for _ in range(max(args.warmup, 1)):
+    # warm-up: at least --warmup steps and at least WARMUP_S of them.  The first few hundred ms of steps on an idle GPU run
+    # slower than the rest (a 2000-step region right after a 5-step warm-up: +0.6 %; a 20-step one: +18 %)
+    warmup_steps, t0 = 0, time.perf_counter()
+    while warmup_steps < max(args.warmup, 1) or time.perf_counter() - t0 < WARMUP_S:
         step()
-    # The timed region: EXACTLY args.steps steps between two barrier + synchronize brackets -- measured `repeats` times,
-    # each with the host clock around the brackets AND with a hipEvent pair recorded on the launch stream right after the
-    # opening bracket / right before the closing one.  `value` is from the MEDIAN region by the device clock: the host
-    # clock also counts the closing bracket itself (ctx.sync + synchronize, ~0.3 ms here), which a 5 ms region of 20
-    # steps sees as 6 % and a 50 ms region of 200 steps as 0.6 % (the driver's 20-step run read 8.4e10
-    # where the kernels do 9.6e10).  Both clocks are in the line (`timing`).
-    repeats = 9
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(repeats)]
-    host_dts = []
-    for r_ in range(repeats):
-        barrier()
-        t0 = time.perf_counter()
-        ev[r_][0].record(tstream)
-        for _ in range(args.steps):
-            step()
-        ev[r_][1].record(tstream)
-        barrier()
-        host_dts.append(time.perf_counter() - t0)
-    dev_dts = [a_.elapsed_time(b_) * 1e-3 for a_, b_ in ev]
-    dt = max_over_ranks(float(np.median(dev_dts)))
-    dt_host = max_over_ranks(float(np.median(host_dts)))
+        warmup_steps += 1
+        if warmup_steps % 32 == 0:
+            local_sync()                                            # the host clock follows the device
+    # The timed region: EXACTLY args.steps steps, once, between two barrier + synchronize brackets, with the host clock
+    # around the brackets AND a hipEvent pair recorded on the launch stream right after the opening bracket / right before
+    # the closing one.  `value` and `ms_per_step` are by the device clock: the host clock also counts the closing bracket
+    # itself (ctx.sync + synchronize, ~0.3 ms here), which a 5 ms region of 20 steps sees as 6 % and a 50 ms region of 200
+    # steps as 0.6 % (the driver's 20-step run read 8.4e10 where the kernels do 9.6e10).  Both clocks are
+    # in the line (`timing`).
+    ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+    barrier()
+    t0 = time.perf_counter()
+    ev[0].record(tstream)
+    for _ in range(args.steps):
+        step()
+    ev[1].record(tstream)
+    barrier()
+    dt_host = max_over_ranks(time.perf_counter() - t0)
+    dt = max_over_ranks(ev[0].elapsed_time(ev[1]) * 1e-3)
     assert torch.equal(d_c, d_a), "iNTT(NTT(a)) != a"            # round trip inside the bench
+    if rank == 0 and args.dump_outputs:
+        # what the caller of the step receives from its last timed step: the forward transform and the inverse of it
+        rows = dump_rows(n)
+        write_dump(args.dump_outputs, {"ntt_forward": d_b.cpu().numpy().view(np.uint64)[rows],
+                                       "ntt_inverse": d_c.cpu().numpy().view(np.uint64)[rows]})
     butterflies_per_step = 2 * (n // 2) * k
     value = world * butterflies_per_step * args.steps / dt
     timing = {"clock": "hipEvent pair on the launch stream around exactly `steps` steps, inside the barrier + synchronize brackets",
-              "repeats": repeats, "region_ms_device_median": round(dt * 1e3, 4),
-              "region_ms_device_min_max": [round(min(dev_dts) * 1e3, 4), round(max(dev_dts) * 1e3, 4)],
-              "region_ms_host_clock_median": round(dt_host * 1e3, 4),
+              "warmup_steps_run": warmup_steps, "region_ms_device": round(dt * 1e3, 4),
+              "region_ms_host_clock": round(dt_host * 1e3, 4),
               "value_by_host_clock": world * butterflies_per_step * args.steps / dt_host}
     prof_steps = 200                                              # fixed: the kernels' mean durations must not depend on --steps
     ctx.profile(True)

@@ -4,6 +4,10 @@ import sys
 
 import numpy as np
 import pytest
+# torch before the library: torch carries its own HIP / HSA runtime, and a library loaded first brings in a second one
+# (the system ROCm's); once torch's runtime has initialised, the library's sees no device and every later Context fails with
+# PM_ERR_NO_DEVICE.  Loaded after torch, the library binds to the runtime torch loaded (as in bench.py).
+import torch  # noqa: F401
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
