@@ -223,6 +223,12 @@ int pm_g1_msm_batch_dev(pm_ctx* ctx, const pm_bases* bases, size_t offset, size_
 int pm_g1_fixed_base_mul_dev(pm_ctx* ctx, const uint64_t base_xy[12], const void* d_scalars, size_t n,
                              uint32_t scalar_form, void* d_out_xy, void* hip_stream);
 
+/* Lagrange-form commit key: out[i] = [L_i(tau)]G = n^-1 sum_{j<n} w^-ij powers[j], n = 2^log_n <= pm_g1_bases_len(powers),
+ * written to d_out_xy (n x 96 bytes, ABI affine) -- hand it to pm_g1_bases_from_dev.  Any points are accepted (it is
+ * the inverse NTT of the first n bases); identities allowed.  PM_ERR_LENGTH when n exceeds the bases,
+ * PM_ERR_DOMAIN_TOO_LARGE when log_n >= 32.  Allocates n x 320 + n x 32 bytes of scratch for the call; blocks until done. */
+int pm_g1_bases_lagrange(pm_ctx* ctx, const pm_bases* powers, uint32_t log_n, void* d_out_xy, void* hip_stream);
+
 /* out = sum of k projective points (the group-law "all-reduce" after an all-gather). Host. */
 int pm_g1_fold(const uint64_t* xyz_parts, size_t k, uint64_t out_xyz[18]);
 
@@ -386,6 +392,12 @@ void pm_plonk_key_free(pm_ctx* ctx, pm_prover_key* key);
 int pm_plonk_key_commit(pm_ctx* ctx, pm_prover_key* key, const pm_bases* commit_key, const char* transcript_label,
                         uint64_t (*verifier_key_out)[12]);
 int pm_plonk_verifier_key(const pm_prover_key* key, uint64_t (*out)[12]);
+/* Round-1 wire commitments from the witness over a Lagrange-form key (NULL detaches).  lagrange must hold exactly n
+ * points (PM_ERR_LENGTH otherwise) and is checked once against commit_key: sum_i L_i = powers[0] and
+ * sum_i w^i L_i = powers[1] (two MSMs); PM_ERR_BAD_ARG if either fails.  pm_plonk_prove on this key then requires the
+ * same commit_key (PM_ERR_BAD_ARG otherwise); pm_plonk_prove_sharded ignores the attachment.  The caller keeps
+ * ownership: lagrange must outlive the attachment.  The proof bytes are those of a key without the attachment. */
+int pm_plonk_key_set_lagrange(pm_ctx* ctx, pm_prover_key* key, const pm_bases* commit_key, const pm_bases* lagrange);
 /* d_witness: device memory, [a | b | c | d] wire values, 4n Fr.  Public inputs: n_pi (position < n, value)
  * pairs in host memory -- the dense PI vector of dusk's construct_dense_pi_vec is built on the device.
  * commit_key: at least n resident bases (pm_g1_bases_upload / pm_g1_bases_from_dev, ideally with

@@ -192,11 +192,51 @@ class CommitKey {
     return to_affine(p);
   }
   const pm_bases* bases() const { return bases_; }
+  // the Lagrange-form key [L_i(tau)]G of the 2^log_n domain (pm_g1_bases_lagrange): one inverse NTT over the first 2^log_n powers
+  class LagrangeCommitKey lagrange(uint32_t log_n) const;
 
  private:
   Context* ctx_;
   pm_bases* bases_ = nullptr;
 };
+
+// Commit key in Lagrange form: commit(evals) = the commitment to the polynomial whose values on H are evals (fewer than n
+// values are zero padded) -- the same group element CommitKey::commit gives its coefficients.
+class LagrangeCommitKey {
+ public:
+  LagrangeCommitKey(Context& ctx, pm_bases* bases) : ctx_(&ctx), bases_(bases) {}
+  ~LagrangeCommitKey() { if (bases_) pm_g1_bases_free(ctx_->get(), bases_); }
+  LagrangeCommitKey(const LagrangeCommitKey&) = delete;
+  LagrangeCommitKey& operator=(const LagrangeCommitKey&) = delete;
+  LagrangeCommitKey(LagrangeCommitKey&& o) noexcept : ctx_(o.ctx_), bases_(o.bases_) { o.bases_ = nullptr; }
+  size_t n() const { return pm_g1_bases_len(bases_); }
+  G1Affine commit(const std::vector<Fr>& evals) const {
+    if (evals.size() > n()) throw Error(PM_ERR_LENGTH, "more evaluations than the domain holds");
+    G1Projective p{};
+    const Fr zero{0, 0, 0, 0};
+    ctx_->check(pm_g1_msm(ctx_->get(), bases_, evals.size(), evals.empty() ? zero.data() : evals[0].data(),
+                          PM_SCALAR_MONTGOMERY, p.data()));
+    return to_affine(p);
+  }
+  const pm_bases* bases() const { return bases_; }
+
+ private:
+  Context* ctx_;
+  pm_bases* bases_ = nullptr;
+};
+
+inline LagrangeCommitKey CommitKey::lagrange(uint32_t log_n) const {
+  if (log_n >= 32) throw Error(PM_ERR_DOMAIN_TOO_LARGE, "log_n >= 32");
+  const size_t n = (size_t)1 << log_n;
+  void* d_xy = nullptr;
+  ctx_->check(pm_dev_alloc(ctx_->get(), n * 96, &d_xy));
+  pm_bases* out = nullptr;
+  int rc = pm_g1_bases_lagrange(ctx_->get(), bases_, log_n, d_xy, nullptr);
+  if (!rc) rc = pm_g1_bases_from_dev(ctx_->get(), d_xy, n, &out);
+  pm_dev_free(ctx_->get(), d_xy);
+  ctx_->check(rc);
+  return LagrangeCommitKey(*ctx_, out);
+}
 
 // ------------------------------------------------------------------------------------------------
 // dusk_plonk::fft::Polynomial kept in device memory between NTT and MSM calls
@@ -303,6 +343,11 @@ class ProverKey {
   ProverKey& operator=(const ProverKey&) = delete;
   size_t n() const { return n_; }
   const std::array<G1Affine, PM_PLONK_VK_POINTS>& verifier_key() const { return verifier_key_; }
+  // round 1 commits the wires from the witness over lck (checked against ck; nullptr detaches); prove() must then be
+  // given the same ck.  The proofs do not change.  lck must outlive the attachment.
+  void use_lagrange(const CommitKey& ck, const LagrangeCommitKey* lck) {
+    ctx_->check(pm_plonk_key_set_lagrange(ctx_->get(), key_, ck.bases(), lck ? lck->bases() : nullptr));
+  }
   // witness: [a | b | c | d] on the device (4n)
   Proof prove(const CommitKey& ck, const DevicePolynomial& witness, const std::vector<PublicInput>& public_inputs = {},
               bool bind_public_inputs = true) const {

@@ -8,7 +8,7 @@ runs in hand-written HIP kernels; importing works without a GPU, but creating a
 """
 from ._lib import (BackendMissing, NTT_COSET, NTT_INVERSE, NTT_TRANSPOSED, SCALAR_CANONICAL,  # noqa: F401
                    SCALAR_MONTGOMERY, load, LIB_PATH)
-from .host import (CommitKey, Context, DeviceVector, Error, EvaluationDomain, Polynomial,  # noqa: F401
+from .host import (CommitKey, Context, DeviceVector, Error, EvaluationDomain, LagrangeCommitKey, Polynomial,  # noqa: F401
                    msm_variable_base,
                    g1_fold, g1_to_affine, domain_info, ntt_plan)
 from . import field, prover, srs, synthetic, transcript  # noqa: F401,E402

@@ -86,6 +86,7 @@ SIGNATURES = {
     "pm_g1_bases_from_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "pm_g1_fixed_base_mul_dev": (C.c_int, [C.c_void_p, u64p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p,
                                            C.c_void_p]),
+    "pm_g1_bases_lagrange": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "pm_g1_bases_precompute": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "pm_g1_bases_free": (None, [C.c_void_p, C.c_void_p]),
     "pm_g1_bases_len": (C.c_size_t, [C.c_void_p]),
@@ -117,6 +118,7 @@ SIGNATURES = {
                                       C.POINTER(C.c_void_p)]),
     "pm_plonk_key_free": (None, [C.c_void_p, C.c_void_p]),
     "pm_plonk_key_commit": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p]),
+    "pm_plonk_key_set_lagrange": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pm_plonk_key_commit_sharded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                               C.c_char_p, C.c_void_p]),
     "pm_plonk_verifier_key": (C.c_int, [C.c_void_p, C.c_void_p]),

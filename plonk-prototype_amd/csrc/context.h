@@ -165,6 +165,10 @@ inline void host_mark(pm_ctx* ctx, const char* label) {
   if (ctx && ctx->marks_on)
     ctx->marks.emplace_back(label, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count());
 }
+// n XYZZ records (ec.hip.h) -> n affine points in dst (ABI form when to_abi); prefix: n x 64 bytes of scratch.  Launches
+// precompute_affine_kernel on st (msm.hip)
+hipError_t xyzz_records_to_affine(pm_ctx* ctx, const void* records, size_t n, void* prefix, void* dst, bool to_abi,
+                                  hipStream_t st);
 int fr_batch_inverse_mul(pm_ctx* ctx, void* d_inout, const void* d_mul, size_t n, void* hip_stream);   // poly.hip: mul_i / v_i in place
 int poly_evaluate_groups(pm_ctx* ctx, uint32_t groups, const uint32_t* k, const void* const* const* polys,
                          const uint64_t* const* points, uint64_t* const* outs, size_t n);   // poly.hip

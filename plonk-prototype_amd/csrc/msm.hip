@@ -113,6 +113,17 @@ __global__ void __launch_bounds__(128) precompute_affine_kernel(const u32x4* scr
   }
 }
 
+hipError_t xyzz_records_to_affine(pm_ctx* ctx, const void* records, size_t n, void* prefix, void* dst, bool to_abi,
+                                  hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  const size_t want = std::max<size_t>((n + 63) / 64, std::min<size_t>(n, (size_t)ctx->num_cus * 512));
+  const unsigned blocks = (unsigned)((want + 127) / 128);
+  const u32 per = (u32)((n + (size_t)blocks * 128 - 1) / ((size_t)blocks * 128));
+  hipLaunchKernelGGL(precompute_affine_kernel, dim3(blocks), dim3(128), 0, st, (const u32x4*)records, n, per, (u32x4*)prefix,
+                     (u32x4*)dst, to_abi ? 1u : 0u);
+  return hipGetLastError();
+}
+
 // buckets[b].ZZ <- 0 (four 16-byte stores per bucket, one per thread): the identity, see ld_xyzz
 __global__ void msm_clear_buckets_kernel(u32x4* buckets, size_t nb) {
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;

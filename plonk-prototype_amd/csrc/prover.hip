@@ -295,6 +295,9 @@ struct pm_prover_key {
   std::atomic<bool> busy{false};       // a proof is running on this key's workspace
   hipStream_t side = nullptr;         // second stream: work that does not depend on the next challenge
   hipEvent_t ev_main = nullptr, ev_side = nullptr;
+  // Lagrange-form commit key (pm_plonk_key_set_lagrange; not owned) and the commit key it was checked against
+  const pm_bases* lagrange = nullptr;
+  const pm_bases* lagrange_ck = nullptr;
 };
 
 // side stream <- everything submitted on the context's stream so far / the reverse
@@ -651,6 +654,62 @@ extern "C" int pm_plonk_key_commit_sharded(pm_ctx* ctx, pm_prover_key* key, cons
   return key_commit_impl(ctx, key, commit_key_slice, sh, transcript_label, verifier_key_out);
 }
 
+namespace {
+struct BusyGuard {   // one proof at a time per key: the key owns the per-proof workspace
+  pm_prover_key* pk;
+  bool ok;
+  explicit BusyGuard(pm_prover_key* k) : pk(k), ok(!k->busy.exchange(true)) {}
+  ~BusyGuard() {
+    if (ok) pk->busy.store(false);
+  }
+};
+}  // namespace
+
+// sum_i L_i = powers[0] and sum_i w^i L_i = powers[1]: two MSMs over the Lagrange key (scalars 1 and the key's roots of
+// unity) against the first two points of the commit key.  Together they pin the key to the commit key's tau.
+extern "C" int pm_plonk_key_set_lagrange(pm_ctx* ctx, pm_prover_key* key, const pm_bases* commit_key, const pm_bases* lagrange) {
+  if (!ctx || !key) return PM_ERR_BAD_ARG;
+  BusyGuard guard(key);
+  if (!guard.ok) return PM_ERR_BUSY;
+  if (!lagrange) {
+    key->lagrange = nullptr;
+    key->lagrange_ck = nullptr;
+    return PM_OK;
+  }
+  if (!commit_key) return PM_ERR_BAD_ARG;
+  const size_t n = key->n;
+  if (pm_g1_bases_len(lagrange) != n) return pm::set_err(ctx, PM_ERR_LENGTH, "the Lagrange key must hold exactly n points");
+  if (pm_g1_bases_len(commit_key) < std::max<size_t>(n, 2)) return pm::set_err(ctx, PM_ERR_LENGTH, "commit key shorter than n");
+  void* d_sc = nullptr;
+  PK_TRY(pm_dev_alloc(ctx, 2 * n * 32, &d_sc));
+  const HFr one = fone();
+  u64 xyz[2 * 18], got[2][12];
+  int ident[2];
+  int rc = pm_fr_powers_dev(ctx, one.l, one.l, n, d_sc, nullptr);
+  if (!rc) rc = pm_fr_powers_dev(ctx, key->omega.l, one.l, n, at(d_sc, n), nullptr);
+  if (!rc) rc = pm_g1_msm_batch_dev(ctx, lagrange, 0, n, d_sc, n, 2, PM_SCALAR_MONTGOMERY, xyz, nullptr);
+  (void)pm_dev_free(ctx, d_sc);
+  if (!rc) rc = pm_g1_to_affine_batch(xyz, 2, &got[0][0], ident);
+  // the commit key's first two points: device form (x 2^392) -> ABI Montgomery (x 2^384): one product by 2^376
+  u64 want[2][12];
+  if (!rc) rc = pm_dev_download(ctx, want, commit_key->d_xy, sizeof want);
+  if (rc) return rc;
+  const pm::host::Field<6>& F = pm::host::FP();
+  const pm::host::HFp c = pm::host::inv(pm::host::from_u64(256, F), F);
+  for (int p = 0; p < 2; ++p)
+    for (int h = 0; h < 2; ++h) {
+      pm::host::HFp v;
+      memcpy(v.l, want[p] + 6 * h, 48);
+      v = pm::host::mul(v, c, F);
+      memcpy(want[p] + 6 * h, v.l, 48);
+    }
+  if (memcmp(got, want, sizeof want) != 0)
+    return pm::set_err(ctx, PM_ERR_BAD_ARG, "the Lagrange key does not match the commit key (sum L_i != powers[0] or sum w^i L_i != powers[1])");
+  key->lagrange = lagrange;
+  key->lagrange_ck = commit_key;
+  return PM_OK;
+}
+
 // pi_evals <- 0, then the sparse public inputs (a repeated position keeps its last value).  A handful goes up
 // element by element; longer lists are staged as compact (position, value) arrays in the round-2 scratch
 // (num / den are not written before round 2, which is ordered after this on the same stream) and scattered by
@@ -731,17 +790,6 @@ extern "C" int pm_plonk_prove(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck
   return prove_impl(ctx, pk, ck, Shard(), d_witness, pi_positions, pi_values, n_pi, flags, out);
 }
 
-namespace {
-struct BusyGuard {   // one proof at a time per key: the key owns the per-proof workspace
-  pm_prover_key* pk;
-  bool ok;
-  explicit BusyGuard(pm_prover_key* k) : pk(k), ok(!k->busy.exchange(true)) {}
-  ~BusyGuard() {
-    if (ok) pk->busy.store(false);
-  }
-};
-}  // namespace
-
 static int prove_body(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, const Shard& shard, const void* d_witness,
                       const uint64_t* pi_positions, const uint64_t* pi_values, size_t n_pi, uint32_t flags,
                       pm_plonk_proof* out) {
@@ -768,21 +816,35 @@ static int prove_body(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, const 
     }
   }
   const HFr one = fone();
+  // a Lagrange-form key commits the wires from their values on H: the same group elements (no blinding), so the same proof
+  const pm_bases* lag = shard.on ? nullptr : pk->lagrange;
+  if (lag && ck != pk->lagrange_ck) return PM_ERR_BAD_ARG;   // checked against another commit key
   // ---- round 1 --------------------------------------------------------------------------------
   pm::host_mark(ctx, "round 1");
-  PK_TRY(pm_fr_ntt_dev(ctx, d_witness, n, n, pk->coeffs, n, lg, 4, PM_NTT_INVERSE, nullptr));
-  // work no challenge depends on goes to the side stream and runs under the MSMs of rounds 1 and 2:
-  // the public-input polynomial and the wire polynomials on the 4n coset (round 3 reads them)
   hipStream_t side = pk->side;
   void* pi_coeffs = at(pk->coeffs, 5 * n);
-  {
+  if (lag) {
+    // nothing waits for the wire iNTT before the MSM: it runs on the side stream ahead of the coset transforms
     PK_TRY(scatter_public_inputs(ctx, pk, pi_positions, pi_values, n_pi));
     PK_TRY(pm_fr_ntt_dev(ctx, pk->pi_evals, n, n, pi_coeffs, n, lg, 1, PM_NTT_INVERSE, nullptr));
     PK_TRY(pm_stream_fork(ctx, side, pk->ev_main));
+    PK_TRY(pm_fr_ntt_dev(ctx, d_witness, n, n, pk->coeffs, n, lg, 4, PM_NTT_INVERSE, side));
     PK_TRY(pm_fr_ntt_dev(ctx, pk->coeffs, n, n, pk->coset, 4 * n, lg + 2, 4, PM_NTT_COSET, side));
     PK_TRY(pm_fr_ntt_dev(ctx, pi_coeffs, n, n, at(pk->coset, 4 * n * 5), 4 * n, lg + 2, 1, PM_NTT_COSET, side));
+    PK_TRY(commit_batch(ctx, lag, shard, d_witness, n, n, 4, &out->commitments[0]));
+  } else {
+    PK_TRY(pm_fr_ntt_dev(ctx, d_witness, n, n, pk->coeffs, n, lg, 4, PM_NTT_INVERSE, nullptr));
+    // work no challenge depends on goes to the side stream and runs under the MSMs of rounds 1 and 2:
+    // the public-input polynomial and the wire polynomials on the 4n coset (round 3 reads them)
+    {
+      PK_TRY(scatter_public_inputs(ctx, pk, pi_positions, pi_values, n_pi));
+      PK_TRY(pm_fr_ntt_dev(ctx, pk->pi_evals, n, n, pi_coeffs, n, lg, 1, PM_NTT_INVERSE, nullptr));
+      PK_TRY(pm_stream_fork(ctx, side, pk->ev_main));
+      PK_TRY(pm_fr_ntt_dev(ctx, pk->coeffs, n, n, pk->coset, 4 * n, lg + 2, 4, PM_NTT_COSET, side));
+      PK_TRY(pm_fr_ntt_dev(ctx, pi_coeffs, n, n, at(pk->coset, 4 * n * 5), 4 * n, lg + 2, 1, PM_NTT_COSET, side));
+    }
+    PK_TRY(commit_batch(ctx, ck, shard, pk->coeffs, n, n, 4, &out->commitments[0]));
   }
-  PK_TRY(commit_batch(ctx, ck, shard, pk->coeffs, n, n, 4, &out->commitments[0]));
   for (int j = 0; j < 4; ++j) ts.append_commitment(tl::WIRES[j], out->commitments[j]);
   // ---- round 2 --------------------------------------------------------------------------------
   pm::host_mark(ctx, "round 2");

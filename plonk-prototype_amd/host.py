@@ -679,3 +679,79 @@ class CommitKey:
             raise Error(_lib.PM_ERR_LENGTH, "PolynomialDegreeTooLarge")
         xyz = self._bases.msm(c, _lib.SCALAR_MONTGOMERY)
         return g1_to_affine(xyz)[0]
+
+    def lagrange(self, log_n: int, precompute: bool = False) -> "LagrangeCommitKey":
+        """The Lagrange-form key [L_i(tau)]G of the 2^log_n domain, from the first 2^log_n powers by one inverse NTT over
+        G1 on the GPU (``pm_g1_bases_lagrange``).  A one-time conversion per domain: save ``points()`` with
+        ``srs.commit_key_to_raw_bytes`` and load it with ``LagrangeCommitKey.from_points``."""
+        ctx = self.ctx
+        if log_n >= 32:
+            raise Error(_lib.PM_ERR_DOMAIN_TOO_LARGE, "log_n >= 32")
+        n = 1 << log_n
+        if n > self._bases.n:
+            raise Error(_lib.PM_ERR_LENGTH, "2^log_n exceeds the commit key")
+        pts = DeviceVector(ctx, 3 * n)                            # n affine points of 96 bytes
+        try:
+            ctx._check(ctx._lib.pm_g1_bases_lagrange(ctx._h, self._bases._h, log_n, pts._p, None))
+            bases = Bases.from_device(ctx, pts.ptr, n)
+            host = pts.to_host().reshape(n, 12)
+        finally:
+            pts.free()
+        return LagrangeCommitKey(bases, host, precompute)
+
+
+class LagrangeCommitKey:
+    """Commit key in Lagrange form, [L_i(tau)]G for the n-point domain H: ``commit(evals)`` is the commitment to the
+    polynomial whose values on H are ``evals`` -- the same group element ``CommitKey.commit`` gives its coefficients
+    (``domain.ifft(evals)``).  Witness-shaped scalars (mostly 0 / 1 / small) make the MSM cheaper than uniform
+    coefficients do."""
+
+    def __init__(self, bases: Bases, points, precompute: bool = False):
+        self.ctx, self._bases, self.n = bases.ctx, bases, bases.n
+        self._points = points
+        if precompute:
+            self._bases.precompute()
+
+    @classmethod
+    def from_points(cls, points, ctx: Context | None = None, precompute: bool = False) -> "LagrangeCommitKey":
+        """A saved key ([n, 12] affine, e.g. from ``srs.commit_key_from_raw_bytes``); n must be a power of two."""
+        ctx = ctx or default_context()
+        p = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 12)
+        if p.shape[0] == 0 or p.shape[0] & (p.shape[0] - 1):
+            raise Error(_lib.PM_ERR_LENGTH, "a Lagrange key holds 2^k points")
+        return cls(Bases(ctx, p), p, precompute)
+
+    def points(self) -> np.ndarray:
+        """[n, 12] affine Montgomery limbs ((0, 0) = identity): what ``srs.commit_key_to_raw_bytes`` saves."""
+        return self._points
+
+    def commit(self, evals) -> np.ndarray:
+        """evals: up to n values on H (fewer are zero padded) -> affine [12]."""
+        e = _fr(evals)
+        if e.shape[0] > self.n:
+            raise Error(_lib.PM_ERR_LENGTH, "more evaluations than the domain holds")
+        return g1_to_affine(self._bases.msm(e, _lib.SCALAR_MONTGOMERY))[0]
+
+    def commit_many(self, evals) -> np.ndarray:
+        """Several evaluation vectors of one length in one pass -> [k, 12] affine."""
+        e = np.ascontiguousarray(evals, dtype=np.uint64)
+        k, m = e.shape[0], e.shape[1]
+        if m > self.n:
+            raise Error(_lib.PM_ERR_LENGTH, "more evaluations than the domain holds")
+        d = DeviceVector.from_host(self.ctx, e.reshape(-1, 4))
+        try:
+            xyz = self._bases.msm_batch_dev(d.ptr, m, k)
+        finally:
+            d.free()
+        return np.stack([g1_to_affine(x)[0] for x in xyz])
+
+    def commit_batch_dev(self, d_ptr: int, n: int, batch: int, stride: int | None = None) -> list:
+        """`batch` device-resident evaluation vectors of n elements (vector j at d_ptr + 32 j stride) -> list of
+        affine [12]."""
+        if n > self.n:
+            raise Error(_lib.PM_ERR_LENGTH, "more evaluations than the domain holds")
+        xyz = self._bases.msm_batch_dev(d_ptr, n, batch, stride=stride)
+        return [g1_to_affine(p)[0] for p in xyz]
+
+    def free(self):
+        self._bases.free()

@@ -155,6 +155,15 @@ class ProverKey:
         self.label = label
         return self.verifier_key
 
+    def use_lagrange(self, ck, lck):
+        """Commit the wires of round 1 from the witness over the Lagrange-form key ``lck`` (``CommitKey.lagrange``),
+        checked once against ``ck``; ``prove`` must then be given the same ``ck``.  The proofs do not change.
+        ``lck=None`` detaches.  The key keeps a reference to ``lck`` while it is attached."""
+        ctx = self.ctx
+        ctx._check(ctx._lib.pm_plonk_key_set_lagrange(ctx._h, self._h, ck._bases._h if ck is not None else None,
+                                                      lck._bases._h if lck is not None else None))
+        self._lagrange = lck
+
     def free(self):
         if getattr(self, "_h", None) and self.ctx._h:
             self.ctx._lib.pm_plonk_key_free(self.ctx._h, self._h)

@@ -44,20 +44,83 @@ def chain_circuit(n: int, seed: int = 1, public_rows=(0,), zero_selectors=()):
     ar = np.arange(n, dtype=np.int64)
     var = np.concatenate([ar, np.maximum(ar - 1, 0), ar + 1, np.maximum(ar - 2, 0)])   # variable of position j n + i
     witness = vl[var].reshape(4, n, 4)
-    # sigma: each variable's positions form one cycle
+    sigma = _sigma_cycles(var)
+    minus_one = fr_vec_to_limbs([R_MOD - 1])[0]
+    circuit = Circuit(q_m=fr_vec_to_limbs(qm), q_l=fr_vec_to_limbs(ql), q_r=fr_vec_to_limbs(qr),
+                      q_o=np.tile(minus_one, (n, 1)), q_4=fr_vec_to_limbs(q4), q_c=fr_vec_to_limbs(qc),
+                      q_arith=np.tile(fr_to_limbs(1), (n, 1)), sigma_index=sigma.reshape(4, n))
+    return circuit, witness, fr_vec_to_limbs(pi)
+
+
+def _sigma_cycles(var: np.ndarray) -> np.ndarray:
+    """var[j n + i] = the variable at wire j of gate i -> sigma_index (flat): each variable's positions form one cycle."""
     order = np.argsort(var, kind="stable")
     sv = var[order]
     nxt = np.roll(order, -1)
     starts = np.flatnonzero(np.r_[True, sv[1:] != sv[:-1]])
     ends = np.r_[starts[1:] - 1, var.size - 1]
     nxt[ends] = order[starts]
-    sigma = np.empty(4 * n, np.int64)
+    sigma = np.empty(var.size, np.int64)
     sigma[order] = nxt
-    minus_one = fr_vec_to_limbs([R_MOD - 1])[0]
-    circuit = Circuit(q_m=fr_vec_to_limbs(qm), q_l=fr_vec_to_limbs(ql), q_r=fr_vec_to_limbs(qr),
-                      q_o=np.tile(minus_one, (n, 1)), q_4=fr_vec_to_limbs(q4), q_c=fr_vec_to_limbs(qc),
-                      q_arith=np.tile(fr_to_limbs(1), (n, 1)), sigma_index=sigma.reshape(4, n))
-    return circuit, witness, fr_vec_to_limbs(pi)
+    return sigma
+
+
+def boolean_circuit(n: int, seed: int = 1):
+    """-> (Circuit, witness [4, n, 4], public_inputs [n, 4]) shaped like the reference's bit-decomposition and range
+    gadgets (ref:src/zk/gadgets.rs:186-225): a witness that is almost all 0 and 1.  Power-of-two n >= 8.
+
+    Rows come in blocks of B = min(n, 64).  A block's first B - R rows are bit constraints
+    (q_m = 1, q_o = -1, a = b = c = bit, d = 0: bit^2 - bit = 0); its last R = min(7, max(1, B // 9)) rows recombine
+    2R + 1 of those bits into a value, two bits per row (q_l = 4, q_r = 2, q_4 = 1, q_o = -1):
+        c_0 = 4 bit_0 + 2 bit_1 + bit_2,   c_k = 4 c_(k-1) + 2 bit_(2k+1) + bit_(2k+2)   (a = c_(k-1), b, d = bits)
+    Copy constraints tie each bit row's a, b and c together, every use of a bit to its row, each c_k to the next
+    row's a, and all the d = 0 of bit rows to one another.  At least 95 % of the wire values are 0 or 1 from
+    B = 64 on (31 of 32 at n = 8).  No public input."""
+    if n < 8 or n & (n - 1):
+        raise ValueError("boolean_circuit needs a power-of-two n >= 8")
+    rng = np.random.default_rng(seed)
+    B = min(n, 64)
+    R = min(7, max(1, B // 9))
+    nb = B - R                                             # bit rows per block
+    blocks = n // B
+    bits = rng.integers(0, 2, size=(blocks, nb), dtype=np.int64)
+    # per-row wire values and variables [4, blocks, B]; variable ids: bit (block, r) -> block nb + r, accumulators after
+    # the bits, the shared zero of the d column last
+    val = np.zeros((4, blocks, B), np.int64)
+    var = np.zeros((4, blocks, B), np.int64)
+    bit_id = np.arange(blocks * nb, dtype=np.int64).reshape(blocks, nb)
+    acc_id = blocks * nb + np.arange(blocks * R, dtype=np.int64).reshape(blocks, R)
+    zero_id = blocks * (nb + R)
+    for j in range(3):
+        val[j, :, :nb] = bits
+        var[j, :, :nb] = bit_id
+    var[3, :, :nb] = zero_id
+    acc = np.zeros(blocks, np.int64)
+    for k in range(R):
+        row = nb + k
+        if k == 0:
+            a, a_id = bits[:, 0], bit_id[:, 0]
+        else:
+            a, a_id = acc, acc_id[:, k - 1]
+        b, d = bits[:, 2 * k + 1], bits[:, 2 * k + 2]
+        acc = 4 * a + 2 * b + d
+        val[:, :, row] = np.stack([a, b, acc, d])
+        var[:, :, row] = np.stack([a_id, bit_id[:, 2 * k + 1], acc_id[:, k], bit_id[:, 2 * k + 2]])
+    val, var = val.reshape(4 * n), var.reshape(4 * n)
+    uniq, inv = np.unique(val, return_inverse=True)        # a few hundred distinct small values
+    witness = fr_vec_to_limbs([int(u) for u in uniq])[inv.reshape(-1)].reshape(4, n, 4)
+    recomb = np.zeros(B, bool)
+    recomb[nb:] = True
+    recomb = np.tile(recomb, blocks)
+
+    def sel(on_bits: int, on_recomb: int) -> np.ndarray:
+        c = fr_vec_to_limbs([on_bits, on_recomb])
+        return np.where(recomb[:, None], c[1], c[0])
+
+    circuit = Circuit(q_m=sel(1, 0), q_l=sel(0, 4), q_r=sel(0, 2), q_o=sel(-1, -1), q_4=sel(0, 1),
+                      q_c=np.zeros((n, 4), np.uint64), q_arith=np.tile(fr_to_limbs(1), (n, 1)),
+                      sigma_index=_sigma_cycles(var).reshape(4, n))
+    return circuit, witness, np.zeros((n, 4), np.uint64)
 
 
 # ------------------------------------------------------------------------------------------------
