@@ -405,6 +405,24 @@ int pm_plonk_key_set_lagrange(pm_ctx* ctx, pm_prover_key* key, const pm_bases* c
 int pm_plonk_prove(pm_ctx* ctx, pm_prover_key* key, const pm_bases* commit_key, const void* d_witness,
                    const uint64_t* pi_positions, const uint64_t* pi_values, size_t n_pi, uint32_t flags,
                    pm_plonk_proof* out);
+/* ---- Many proofs of one circuit in one call -----------------------------------------------------------------------
+ * A batch workspace holds the per-proof polynomials of up to max_batch proofs on one committed key (about 42 n x 32 bytes
+ * per proof, one device allocation; PM_ERR_OOM when it does not fit).  The key's own workspace and busy flag are not
+ * used: only its read-only data is shared, so pm_plonk_prove on the key may run beside a batch (on another context).
+ * pm_plonk_prove_batch proves `batch` witnesses together: d_witnesses is device memory, batch x [a | b | c | d] x n Fr,
+ * proof-major; proof b's public inputs are the n_pi[b] pairs (pi_positions[b][i] < n, pi_values[b] + 4 i), and n_pi
+ * (or pi_positions / pi_values) may be NULL for a batch without public inputs.  out[b] is byte-identical, challenges
+ * included, to pm_plonk_prove of witness b with the same public inputs and flags, also with a Lagrange key attached to
+ * the key.  Errors: batch 0 or above max_batch, a workspace of another key, an uncommitted key, contradicting flags:
+ * PM_ERR_BAD_ARG; a position >= n: PM_ERR_LENGTH; a workspace in use: PM_ERR_BUSY.  Single GPU only. */
+typedef struct pm_plonk_batch pm_plonk_batch;
+#define PM_PLONK_MAX_BATCH 64
+int pm_plonk_batch_create(pm_ctx* ctx, const pm_prover_key* key, uint32_t max_batch, pm_plonk_batch** out);
+void pm_plonk_batch_free(pm_ctx* ctx, pm_plonk_batch* ws);
+size_t pm_plonk_batch_bytes(const pm_plonk_batch* ws);   /* device bytes the workspace holds */
+int pm_plonk_prove_batch(pm_ctx* ctx, pm_prover_key* key, pm_plonk_batch* ws, const pm_bases* commit_key, uint32_t batch,
+                         const void* d_witnesses, const uint64_t* const* pi_positions, const uint64_t* const* pi_values,
+                         const size_t* n_pi, uint32_t flags, pm_plonk_proof* out);
 /* Proof::to_bytes: 11 x 48-byte compressed G1, then the 16 scalars of ProofEvaluations::to_bytes. */
 int pm_plonk_proof_to_bytes(const pm_plonk_proof* proof, uint8_t out[PM_PLONK_PROOF_BYTES]);
 /* ---- The prover with coefficient-range ownership end to end (SURVEY.md section 8e row 3 + 8f N5; configs[4]) ----------

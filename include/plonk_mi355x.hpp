@@ -310,6 +310,27 @@ struct PublicInput {
   Fr value;
 };
 
+class ProverKey;
+// pm_plonk_batch: the per-proof workspace of up to max_batch proofs on one key (ProverKey::batch)
+class BatchWorkspace {
+ public:
+  BatchWorkspace(Context& ctx, const pm_prover_key* key, uint32_t max_batch) : ctx_(&ctx), max_batch_(max_batch) {
+    ctx.check(pm_plonk_batch_create(ctx.get(), key, max_batch, &ws_));
+  }
+  ~BatchWorkspace() { if (ws_) pm_plonk_batch_free(ctx_->get(), ws_); }
+  BatchWorkspace(const BatchWorkspace&) = delete;
+  BatchWorkspace& operator=(const BatchWorkspace&) = delete;
+  BatchWorkspace(BatchWorkspace&& o) noexcept : ctx_(o.ctx_), ws_(o.ws_), max_batch_(o.max_batch_) { o.ws_ = nullptr; }
+  uint32_t max_batch() const { return max_batch_; }
+  size_t device_bytes() const { return pm_plonk_batch_bytes(ws_); }
+  pm_plonk_batch* get() const { return ws_; }
+
+ private:
+  Context* ctx_;
+  pm_plonk_batch* ws_ = nullptr;
+  uint32_t max_batch_;
+};
+
 class ProverKey {
  public:
   // selectors: q_m q_l q_r q_o q_c q_4 q_arith q_range q_logic q_fixed_group_add q_variable_group_add, n
@@ -360,6 +381,40 @@ class ProverKey {
     pm_plonk_proof raw;
     ctx_->check(pm_plonk_prove(ctx_->get(), key_, ck.bases(), witness.data(), pos.data(), val.data(), pos.size(),
                                bind_public_inputs ? 0u : PM_PLONK_UPSTREAM_TRANSCRIPT, &raw));
+    return from_raw(raw);
+  }
+  // A workspace for prove_batch of up to max_batch (<= PM_PLONK_MAX_BATCH) proofs: about 42 n x 32 bytes per proof
+  BatchWorkspace batch(uint32_t max_batch) const { return BatchWorkspace(*ctx_, key_, max_batch); }
+  // B proofs in one call: witnesses holds B x [a | b | c | d] (B x 4n, proof-major), public_inputs[b] the inputs of proof b
+  // (empty = none for every proof).  Proof b is byte-identical to prove(ck, witness b, public_inputs[b]).
+  std::vector<Proof> prove_batch(const CommitKey& ck, BatchWorkspace& ws, const DevicePolynomial& witnesses,
+                                 const std::vector<std::vector<PublicInput>>& public_inputs = {},
+                                 bool bind_public_inputs = true) const {
+    if (witnesses.len() == 0 || witnesses.len() % (4 * n_)) throw Error(PM_ERR_LENGTH, "the witnesses must hold B x 4n wire values");
+    const uint32_t B = (uint32_t)(witnesses.len() / (4 * n_));
+    if (!public_inputs.empty() && public_inputs.size() != B) throw Error(PM_ERR_LENGTH, "one public-input list per proof");
+    std::vector<std::vector<uint64_t>> pos(B), val(B);
+    std::vector<const uint64_t*> pp(B, nullptr), vp(B, nullptr);
+    std::vector<size_t> cnt(B, 0);
+    for (uint32_t b = 0; b < B && !public_inputs.empty(); ++b) {
+      for (const PublicInput& pi : public_inputs[b]) {
+        pos[b].push_back(pi.position);
+        val[b].insert(val[b].end(), pi.value.begin(), pi.value.end());
+      }
+      cnt[b] = pos[b].size();
+      pp[b] = pos[b].data();
+      vp[b] = val[b].data();
+    }
+    std::vector<pm_plonk_proof> raw(B);
+    ctx_->check(pm_plonk_prove_batch(ctx_->get(), key_, ws.get(), ck.bases(), B, witnesses.data(), pp.data(), vp.data(),
+                                     cnt.data(), bind_public_inputs ? 0u : PM_PLONK_UPSTREAM_TRANSCRIPT, raw.data()));
+    std::vector<Proof> out;
+    for (const pm_plonk_proof& r : raw) out.push_back(from_raw(r));
+    return out;
+  }
+
+ private:
+  Proof from_raw(const pm_plonk_proof& raw) const {
     Proof p;
     for (int i = 0; i < 11; ++i) std::copy(raw.commitments[i], raw.commitments[i] + 12, p.commitments[i].begin());
     for (int i = 0; i < PM_PLONK_EVALS; ++i) std::copy(raw.evaluations[i], raw.evaluations[i] + 4, p.evaluations[i].begin());
@@ -367,8 +422,6 @@ class ProverKey {
     ctx_->check(pm_plonk_proof_to_bytes(&raw, p.bytes.data()));
     return p;
   }
-
- private:
   Context* ctx_;
   size_t n_;
   pm_prover_key* key_ = nullptr;

@@ -54,6 +54,7 @@ VK_POINTS = (C.c_uint64 * 12) * 15
 PLONK_SELECTORS, PLONK_PROOF_BYTES, PLONK_BIND_PUBLIC_INPUTS, PLONK_UPSTREAM_TRANSCRIPT = 11, 1040, 1, 2
 COMM_ID_BYTES, COMM_MAX_POINTS = 128, 16
 LINCOMB_MAX = 16
+PLONK_MAX_BATCH = 64
 
 # name -> (restype, argtypes); must list every function the header declares
 SIGNATURES = {
@@ -135,6 +136,12 @@ SIGNATURES = {
     "pm_plonk_prove_dist": (C.c_int, [C.c_void_p, C.POINTER(Dist), C.c_void_p, C.c_void_p, C.c_void_p, u64p, u64p, C.c_size_t,
                                       C.c_uint32, C.POINTER(PlonkProof)]),
     "pm_plonk_proof_to_bytes": (C.c_int, [C.POINTER(PlonkProof), C.POINTER(C.c_uint8)]),
+    "pm_plonk_batch_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "pm_plonk_batch_free": (None, [C.c_void_p, C.c_void_p]),
+    "pm_plonk_batch_bytes": (C.c_size_t, [C.c_void_p]),
+    "pm_plonk_prove_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                       C.POINTER(u64p), C.POINTER(u64p), C.POINTER(C.c_size_t), C.c_uint32,
+                                       C.POINTER(PlonkProof)]),
     "pm_fr_poly_evaluate_many_dev": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.c_size_t, u64p, u64p,
                                                C.c_void_p]),
     "pm_comm_unique_id": (C.c_int, [C.POINTER(C.c_uint8)]),

@@ -175,6 +175,48 @@ int poly_evaluate_groups(pm_ctx* ctx, uint32_t groups, const uint32_t* k, const 
 int coset_expand(pm_ctx* ctx, const void* const* d_src, uint32_t count, const void* d_gs_pow, size_t m, void* d_out);
 int sigma_evals_from_index(pm_ctx* ctx, const int64_t* idx, size_t count, uint32_t log_n, const uint64_t omega[4],
                            const uint64_t k[3][4], void* d_out);
+// Per-proof constants of the proof-batched kernels (pm_plonk_prove_batch): a pinned host buffer and its device twin of the
+// same size.  A launcher takes one region of both, fills the host side and sends it with one async copy on its stream;
+// kernels read the device side as a table indexed by the proof.  reset() once per call, after the previous call has
+// synchronised: regions are never reused inside a call, so no copy still in flight reads a region being rewritten.
+struct ConstStage {
+  char* h = nullptr;
+  char* d = nullptr;
+  size_t cap = 0, used = 0;
+  void reset() { used = 0; }
+  bool take(size_t bytes, void** hp, void** dp) {
+    const size_t sz = (bytes + 255) / 256 * 256;
+    if (used + sz > cap) return false;
+    *hp = h + used;
+    *dp = d + used;
+    used += sz;
+    return true;
+  }
+};
+// proof-batched launchers (plonk_rounds.hip, poly.hip); `batch` proofs per launch, blockIdx.y = the proof.  Strides in elements.
+int perm_terms_batch(pm_ctx* ctx, ConstStage& stage, const pm_plonk_perm_args* args /* [batch]: pointers of proof 0 */,
+                     uint32_t batch, size_t wire_stride, size_t n, void* d_num, void* d_den, hipStream_t st);
+int quotient_batch(pm_ctx* ctx, ConstStage& stage, const pm_plonk_quotient_args* args /* [batch]: pointers of proof 0 */,
+                   uint32_t batch, size_t wire_stride, size_t one_stride, size_t n, void* d_out, hipStream_t st);
+int lincomb_batch(pm_ctx* ctx, ConstStage& stage, uint32_t k, const void* const* d_vecs, const size_t* strides,
+                  const uint64_t* coeffs /* [batch][k][4] */, uint32_t batch, size_t n, void* d_out, size_t out_stride,
+                  hipStream_t st);
+// prefix products of `batch` vectors of n at stride n in one look-back launch, when every tile is resident at once; returns
+// PM_ERR_LENGTH (having launched nothing) when they are not: the caller then takes pm_fr_prefix_product_dev per vector
+size_t prefix_product_batch_ctl_bytes(uint32_t batch, size_t n);
+int prefix_product_batch(pm_ctx* ctx, const void* d_in, size_t n, uint32_t batch, void* d_out, void* d_ctl, hipStream_t st);
+// polynomial evaluation: slot j of proof b is polys[j] + b strides[j] at point points[b][point_of[j]] (point_of[j] < 2);
+// k <= PM_EVAL_BATCH_SLOTS.  One host synchronisation; out: [batch][k][4] host
+constexpr uint32_t PM_EVAL_BATCH_SLOTS = 32;
+size_t evaluate_batch_ws_bytes(uint32_t k, uint32_t batch, size_t n);   // every k' <= k, batch' <= batch
+int evaluate_batch(pm_ctx* ctx, ConstStage& stage, uint32_t k, const void* const* polys, const size_t* strides,
+                   const uint8_t* point_of, const uint64_t* points /* [batch][2][4] */, uint32_t batch, size_t n, void* d_ws,
+                   uint64_t* out, hipStream_t st);
+// Ruffini division of `count` vectors of n coefficients (d_in + v stride, d_out + v stride) by X - z_v; falls back to
+// pm_fr_poly_ruffini_dev per vector when a z is zero or a vector has more than 2^20 coefficients
+size_t ruffini_batch_ws_bytes(uint32_t count, size_t n);
+int ruffini_batch(pm_ctx* ctx, ConstStage& stage, const void* d_in, size_t n, size_t stride, const uint64_t* zs /* [count][4] */,
+                  uint32_t count, void* d_out, void* d_ws, hipStream_t st);
 struct OrderScope {
   pm_ctx* ctx;
   StreamOrder& o;

@@ -279,6 +279,177 @@ __global__ void __launch_bounds__(256, 2) quotient_kernel(const QuotPtrs p, cons
   }
 }
 
+// ------------------------------------------------------------------ proof-batched forms (pm_plonk_prove_batch)
+// blockIdx.y is the proof.  Its constants sit in a small device table in the constant address space: the index is
+// wave-uniform, so every access is a scalar load (s_load), as from the kernel arguments of the one-proof kernels.
+#define PM_KCONST __attribute__((address_space(4)))
+template <class T>
+PM_DEV const T& kconst(const PM_KCONST T* tab, u32 i) {
+  return *(const T*)(tab + i);
+}
+__global__ void __launch_bounds__(256) perm_terms_batch_kernel(const PermPtrs p0, const PM_KCONST RoundConsts* kcs, size_t n,
+                                                               size_t wire_stride) {
+  const u32 b = blockIdx.y;
+  const RoundConsts& kc = kconst(kcs, b);
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  const Fr gamma = fr_limbs(kc.gamma), one_abi = fr_limbs(kc.one_abi);
+  const u32x4* w_[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) w_[j] = p0.w[j] + 2 * (size_t)b * wire_stride;
+  u32x4* num = p0.num + 2 * (size_t)b * n;
+  u32x4* den = p0.den + 2 * (size_t)b * n;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const Fr x = ld_canon(p0.roots, i);
+    Fr w[4], f[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) w[j] = to_dev(ld_canon(w_[j], i));
+#pragma unroll
+    for (int j = 0; j < 4; ++j) f[j] = perm_factor(w[j], x, kc.beta_k[j], gamma);
+    st_canon(num, i, fe_mul<FrP>(prod4(f[0], f[1], f[2], f[3]), one_abi));
+#pragma unroll
+    for (int j = 0; j < 4; ++j) f[j] = perm_factor(w[j], ld_canon(p0.s[j], i), kc.beta, gamma);
+    st_canon(den, i, fe_mul<FrP>(prod4(f[0], f[1], f[2], f[3]), one_abi));
+  }
+}
+// wires of proof b at w[j] + b wire_stride, z / PI / out at + b one_stride (elements); selectors, sigmas, l1, x shared
+template <bool WIDGETS>
+__global__ void __launch_bounds__(256, 2) quotient_batch_kernel(const QuotPtrs p0, const PM_KCONST RoundConsts* kcs,
+                                                             const PM_KCONST WidgetConsts* wcs, size_t n4, size_t wire_stride,
+                                                             size_t one_stride) {
+  // quotient_kernel<WIDGETS, false> row for row; only the pointers of proof b and where its constants come from differ
+  const u32 b = blockIdx.y;
+  const RoundConsts& kc = kconst(kcs, b);
+  const WidgetConsts& wc = kconst(wcs, b);
+  QuotPtrs p = p0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) p.w[j] += 2 * (size_t)b * wire_stride;
+  p.z += 2 * (size_t)b * one_stride;
+  p.pi += 2 * (size_t)b * one_stride;
+  p.out += 2 * (size_t)b * one_stride;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;   // a multiple of 4: i mod 4 is fixed per thread
+  const size_t t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const u32 r4 = (u32)(t0 & 3);
+  Fr zhi;
+#pragma unroll
+  for (int l = 0; l < 9; ++l)
+    zhi.l[l] = r4 == 0 ? kc.zh_inv[0][l] : (r4 == 1 ? kc.zh_inv[1][l] : (r4 == 2 ? kc.zh_inv[2][l] : kc.zh_inv[3][l]));
+  const Fr gamma = fr_limbs(kc.gamma);
+  for (size_t i = t0; i < n4; i += stride) {
+    const size_t inext = i + 4 < n4 ? i + 4 : i + 4 - n4;
+    Fr w[4], f[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) w[j] = to_dev(ld_canon(p.w[j], i));
+    // arithmetic identity, ABI form: five (1, <2) products and one canonical load -> (6, <11)
+    Fr g = fe_mul<FrP>(ld_canon(p.q_m, i), fe_mul<FrP>(w[0], w[1]));
+    g = fe_add<FrP>(g, fe_mul<FrP>(ld_canon(p.q_l, i), w[0]));
+    g = fe_add<FrP>(g, fe_mul<FrP>(ld_canon(p.q_r, i), w[1]));
+    g = fe_add<FrP>(g, fe_mul<FrP>(ld_canon(p.q_o, i), w[2]));
+    g = fe_add<FrP>(g, fe_mul<FrP>(ld_canon(p.q_4, i), w[3]));
+    g = fe_add<FrP>(g, ld_canon(p.q_c, i));
+    if (p.q_arith) g = fe_mul<FrP>(fe_norm<FrP>(g), to_dev(ld_canon(p.q_arith, i)));   // ABI x device -> ABI (1, <2)
+    if (WIDGETS) {
+      // the rows' other gate kinds; "next" = the same polynomial at w X = index + 4 on the 4n coset
+      const Fr a = w[0], b = w[1], c = w[2], d = w[3];
+      const Fr an = to_dev(ld_canon(p.w[0], inext)),
+               bn = to_dev(ld_canon(p.w[1], inext)),
+               dn = to_dev(ld_canon(p.w[3], inext));
+      Fr wsum = fe_zero<FrP>();
+      if (p.q_range) {
+        Fr t = wdelta(wsub(c, wmul4(d)), wc);
+        t = wadd(t, wmul(wdelta(wsub(b, wmul4(c)), wc), fr_limbs(wc.range_k[0])));
+        t = wadd(t, wmul(wdelta(wsub(a, wmul4(b)), wc), fr_limbs(wc.range_k[1])));
+        t = wadd(t, wmul(wdelta(wsub(dn, wmul4(a)), wc), fr_limbs(wc.range_k[2])));
+        t = wmul(t, fr_limbs(wc.range_sep));
+        wsum = wadd(wsum, wmul(to_dev(ld_canon(p.q_range, i)), t));
+      }
+      if (p.q_logic) {
+        const Fr qa = wsub(an, wmul4(a)), qb = wsub(bn, wmul4(b)), qd = wsub(dn, wmul4(d));
+        const Fr qc = to_dev(ld_canon(p.q_c, i));
+        Fr t = wdelta(qa, wc);
+        t = wadd(t, wmul(wdelta(qb, wc), fr_limbs(wc.logic_k[0])));
+        t = wadd(t, wmul(wdelta(qd, wc), fr_limbs(wc.logic_k[1])));
+        t = wadd(t, wmul(wsub(c, wmul(qa, qb)), fr_limbs(wc.logic_k[2])));
+        // delta_xor_and(qa, qb, w = c, qd, q_c)
+        const Fr s = wadd(qa, qb);
+        Fr in = wadd(wsub(wmul4(c), wmul2(wmul9(s))), fr_limbs(wc.c81));                         // 4w - 18(a+b) + 81
+        in = wadd(wmul(c, in), wmul2(wmul9(wadd(wsqr(qa), wsqr(qb)))));                          // w(..) + 18(a^2+b^2)
+        in = wadd(wsub(in, wmul(s, fr_limbs(wc.c81))), fr_limbs(wc.c83));                        // - 81(a+b) + 83
+        const Fr ff = wmul(c, in);
+        const Fr e = wsub(wmul3(wadd(s, qd)), wadd(ff, ff));                                    // 3(a+b+c) - 2f
+        const Fr bb = wmul(qc, wsub(wmul9(qd), wmul3(s)));                                      // q_c (9c - 3(a+b))
+        t = wadd(t, wmul(wadd(bb, e), fr_limbs(wc.logic_k[3])));
+        t = wmul(t, fr_limbs(wc.logic_sep));
+        wsum = wadd(wsum, wmul(to_dev(ld_canon(p.q_logic, i)), t));
+      }
+      if (p.q_fixed) {
+        const Fr xb = to_dev(ld_canon(p.q_l, i)), yb = to_dev(ld_canon(p.q_r, i)), xyb = to_dev(ld_canon(p.q_c, i));
+        const Fr one = fr_limbs(wc.c1);
+        const Fr bit = wsub(dn, wadd(d, d));
+        Fr t = wmul(wmul(bit, wsub(bit, one)), wadd(bit, one));                                 // bit (bit-1)(bit+1)
+        const Fr ya = wadd(wmul(wsqr(bit), wsub(yb, one)), one);
+        const Fr xa = wmul(xb, bit);
+        t = wadd(t, wmul(wsub(wmul(bit, xyb), c), fr_limbs(wc.fixed_k[0])));
+        const Fr dxy = wmul(wmul(wmul(c, a), b), fr_limbs(wc.edwards_d));
+        const Fr xacc = wsub(wadd(an, wmul(an, dxy)), wadd(wmul(a, ya), wmul(b, xa)));
+        const Fr yacc = wsub(wsub(bn, wmul(bn, dxy)), wadd(wmul(b, ya), wmul(a, xa)));
+        t = wadd(t, wmul(xacc, fr_limbs(wc.fixed_k[1])));
+        t = wadd(t, wmul(yacc, fr_limbs(wc.fixed_k[2])));
+        t = wmul(t, fr_limbs(wc.fixed_sep));
+        wsum = wadd(wsum, wmul(to_dev(ld_canon(p.q_fixed, i)), t));
+      }
+      if (p.q_var) {
+        const Fr y1x2 = wmul(b, c), y1y2 = wmul(b, d), x1x2 = wmul(a, c);
+        Fr t = wsub(wmul(a, d), dn);                                                             // x1 y2 - x1y2
+        const Fr dd = wmul(wmul(dn, y1x2), fr_limbs(wc.edwards_d));
+        const Fr x3 = wsub(wadd(dn, y1x2), wadd(an, wmul(an, dd)));
+        const Fr y3 = wsub(wadd(y1y2, x1x2), wsub(bn, wmul(bn, dd)));
+        t = wadd(t, wmul(x3, fr_limbs(wc.var_k[0])));
+        t = wadd(t, wmul(y3, fr_limbs(wc.var_k[1])));
+        t = wmul(t, fr_limbs(wc.var_sep));
+        wsum = wadd(wsum, wmul(to_dev(ld_canon(p.q_var, i)), t));
+      }
+      g = fe_add<FrP>(g, wmul(wsum, fr_limbs(kc.one_abi)));                                      // device x 2^256 -> ABI
+    }
+    g = fe_norm<FrP>(fe_add<FrP>(g, ld_canon(p.pi, i)));   // limbs back to (1)
+    // permutation identity
+    const Fr x = ld_canon(p.x, i);
+    const Fr z = ld_canon(p.z, i);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) f[j] = perm_factor(w[j], x, kc.beta_k[j], gamma);
+    const Fr idz = fe_mul<FrP>(z, prod4(f[0], f[1], f[2], f[3]));                          // ABI (1, <2)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) f[j] = perm_factor(w[j], ld_canon(p.s[j], i), kc.beta, gamma);
+    const Fr cpz = fe_mul<FrP>(ld_canon(p.z, inext), prod4(f[0], f[1], f[2], f[3]));   // ABI (1, <2)
+    // idz - cpz + 3r: (4, <5); times alpha -> ABI (1, <2)
+    g = fe_add<FrP>(g, fe_mul<FrP>(fe_sub<FrP, 3, 1>(idz, cpz), fr_limbs(kc.alpha)));
+    // (z - 1) l1 alpha^2:  z - 1 + 2r is (4, <3); product with ABI l1 is 2^251, alpha2 restores 2^256
+    const Fr zm1 = fe_sub<FrP, 2, 1>(z, fr_limbs(kc.one_abi));
+    g = fe_add<FrP>(g, fe_mul<FrP>(fe_mul<FrP>(zm1, ld_canon(p.l1, i)), fr_limbs(kc.alpha2)));
+    // g: value < 18 r, limbs < 3 * 2^29 + 16
+    st_canon(p.out, i, fe_mul<FrP>(g, zhi));
+  }
+}
+// out_b = sum_j c[b][j] v_j(b): term j of proof b at v[j] + b stride[j] (stride 0: a key polynomial all proofs share)
+struct LincombBatchArgs {
+  const u32x4* v[PM_LINCOMB_MAX];
+  size_t stride[PM_LINCOMB_MAX];
+  u32 k;
+};
+__global__ void __launch_bounds__(256) lincomb_batch_kernel(const LincombBatchArgs a, const PM_KCONST u32 (*c)[9] /* [B][k] */,
+                                                            u32x4* out, size_t out_stride, size_t n) {
+  const u32 b = blockIdx.y;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  const PM_KCONST u32(*cb)[9] = c + (size_t)b * a.k;
+  out += 2 * (size_t)b * out_stride;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    Fr acc = fe_mul<FrP>(ld_canon(a.v[0] + 2 * (size_t)b * a.stride[0], i), fr_limbs(kconst(cb, 0)));
+    for (u32 j = 1; j < a.k; ++j)
+      acc = fe_reduce_weak<FrP>(
+          fe_add<FrP>(acc, fe_mul<FrP>(ld_canon(a.v[j] + 2 * (size_t)b * a.stride[j], i), fr_limbs(kconst(cb, j)))));
+    st_canon(out, i, acc);
+  }
+}
+
 // sigma_j(w^i) = k_j' w^i' for a slice of the copy permutation given as wire positions q = j' n + i' (preprocessing; r01 - r04
 // gathered these on the host: 4 n field products or a 4 n x 32-byte round trip through host memory)
 struct SigmaConsts {
@@ -334,6 +505,30 @@ static void fill_round_consts(RoundConsts& kc, const HFr& alpha, const HFr& beta
   to_limbs29_shift(kc.one_abi, host::one(F), 0);
   if (zh_inv)
     for (int j = 0; j < 4; ++j) to_limbs29_shift(kc.zh_inv[j], load_fr(zh_inv[j]), 1);
+}
+static void fill_widget_consts(WidgetConsts& wc, const pm_plonk_quotient_args* args, bool widgets) {
+  memset(&wc, 0, sizeof wc);
+  if (!widgets) return;
+  const host::Field<4>& F = host::FR();
+  auto dev = [&](u32* dst, const HFr& v) { to_limbs29_shift(dst, v, 1); };
+  const struct { u32* dst; u64 v; } small[] = {{wc.c1, 1}, {wc.c2, 2}, {wc.c3, 3}, {wc.c4, 4}, {wc.c9, 9},
+                                               {wc.c18, 18}, {wc.c81, 81}, {wc.c83, 83}};
+  for (const auto& c : small) dev(c.dst, host::from_u64(c.v, F));
+  // JubJub d = -(10240 / 10241)
+  dev(wc.edwards_d, host::sub(host::zero<4>(), host::mul(host::from_u64(10240, F), host::inv(host::from_u64(10241, F), F), F), F));
+  auto sep_powers = [&](const uint64_t sep[4], u32* s_out, u32 (*k_out)[9], int nk) {
+    const HFr s_ = load_fr(sep), kappa = host::mul(s_, s_, F);
+    dev(s_out, s_);
+    HFr kp = kappa;
+    for (int i = 0; i < nk; ++i) {
+      dev(k_out[i], kp);
+      kp = host::mul(kp, kappa, F);
+    }
+  };
+  sep_powers(args->range_sep, wc.range_sep, wc.range_k, 3);
+  sep_powers(args->logic_sep, wc.logic_sep, wc.logic_k, 4);
+  sep_powers(args->fixed_sep, wc.fixed_sep, wc.fixed_k, 3);
+  sep_powers(args->var_sep, wc.var_sep, wc.var_k, 2);
 }
 static unsigned grid_for(const pm_ctx* ctx, size_t n) {
   return (unsigned)std::min<size_t>((n + 255) / 256, (size_t)ctx->num_cus * 16);
@@ -397,6 +592,107 @@ int sigma_evals_from_index(pm_ctx* ctx, const int64_t* idx, size_t count, uint32
   return pm_sync(ctx);   // the temporaries go away when this returns
 }
 
+// ---- launchers of the proof-batched kernels (pm_plonk_prove_batch, prover_batch.hip.h).  Each stages its per-proof
+// constants in `stage` (pinned host -> device table, one async copy) and launches once for all `batch` proofs on `st`.
+int perm_terms_batch(pm_ctx* ctx, ConstStage& stage, const pm_plonk_perm_args* args, uint32_t batch, size_t wire_stride,
+                     size_t n, void* d_num, void* d_den, hipStream_t st) {
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  PermPtrs p;
+  for (int j = 0; j < 4; ++j) {
+    p.w[j] = (const u32x4*)args[0].wires[j];
+    p.s[j] = (const u32x4*)args[0].sigmas[j];
+  }
+  p.roots = (const u32x4*)args[0].roots;
+  p.num = (u32x4*)d_num;
+  p.den = (u32x4*)d_den;
+  RoundConsts* h;
+  void* d;
+  if (!stage.take(sizeof(RoundConsts) * batch, (void**)&h, &d)) return set_err(ctx, PM_ERR_OOM, "constant table full");
+  for (uint32_t b = 0; b < batch; ++b)
+    fill_round_consts(h[b], host::zero<4>(), load_fr(args[b].beta), load_fr(args[b].gamma), args[b].k, nullptr);
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  PM_HIP(ctx, hipMemcpyAsync(d, h, sizeof(RoundConsts) * batch, hipMemcpyHostToDevice, st));
+  ProfScope prof(ctx, st, "plonk_perm_terms_batch");
+  hipLaunchKernelGGL(perm_terms_batch_kernel, dim3(grid_for(ctx, n), batch), dim3(256), 0, st, p,
+                     (const PM_KCONST RoundConsts*)d, n, wire_stride);
+  PM_HIP(ctx, hipGetLastError());
+  return PM_OK;
+}
+
+int quotient_batch(pm_ctx* ctx, ConstStage& stage, const pm_plonk_quotient_args* args, uint32_t batch, size_t wire_stride,
+                   size_t one_stride, size_t n, void* d_out, hipStream_t st) {
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  const pm_plonk_quotient_args& a0 = args[0];
+  QuotPtrs p;
+  for (int j = 0; j < 4; ++j) {
+    p.w[j] = (const u32x4*)a0.wires[j];
+    p.s[j] = (const u32x4*)a0.sigmas[j];
+  }
+  p.z = (const u32x4*)a0.z;
+  p.q_m = (const u32x4*)a0.q_m;
+  p.q_l = (const u32x4*)a0.q_l;
+  p.q_r = (const u32x4*)a0.q_r;
+  p.q_o = (const u32x4*)a0.q_o;
+  p.q_4 = (const u32x4*)a0.q_4;
+  p.q_c = (const u32x4*)a0.q_c;
+  p.q_arith = (const u32x4*)a0.q_arith;
+  p.q_range = (const u32x4*)a0.q_range;
+  p.q_logic = (const u32x4*)a0.q_logic;
+  p.q_fixed = (const u32x4*)a0.q_fixed_group_add;
+  p.q_var = (const u32x4*)a0.q_variable_group_add;
+  p.pi = (const u32x4*)a0.pi;
+  p.l1 = (const u32x4*)a0.l1;
+  p.x = (const u32x4*)a0.x;
+  p.out = (u32x4*)d_out;
+  const bool widgets = p.q_range || p.q_logic || p.q_fixed || p.q_var;
+  RoundConsts* hk;
+  WidgetConsts* hw;
+  void *dk, *dw;
+  if (!stage.take(sizeof(RoundConsts) * batch, (void**)&hk, &dk) || !stage.take(sizeof(WidgetConsts) * batch, (void**)&hw, &dw))
+    return set_err(ctx, PM_ERR_OOM, "constant table full");
+  for (uint32_t b = 0; b < batch; ++b) {
+    fill_round_consts(hk[b], load_fr(args[b].alpha), load_fr(args[b].beta), load_fr(args[b].gamma), args[b].k, args[b].zh_inv);
+    fill_widget_consts(hw[b], &args[b], widgets);
+  }
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  // the two tables are adjacent regions of the stage: one copy
+  PM_HIP(ctx, hipMemcpyAsync(dk, hk, (char*)hw - (char*)hk + sizeof(WidgetConsts) * batch, hipMemcpyHostToDevice, st));
+  ProfScope prof(ctx, st, "plonk_quotient_batch");
+  const dim3 grid(grid_for(ctx, 4 * n), batch);
+  if (widgets)
+    hipLaunchKernelGGL(quotient_batch_kernel<true>, grid, dim3(256), 0, st, p, (const PM_KCONST RoundConsts*)dk,
+                       (const PM_KCONST WidgetConsts*)dw, 4 * n, wire_stride, one_stride);
+  else
+    hipLaunchKernelGGL(quotient_batch_kernel<false>, grid, dim3(256), 0, st, p, (const PM_KCONST RoundConsts*)dk,
+                       (const PM_KCONST WidgetConsts*)dw, 4 * n, wire_stride, one_stride);
+  PM_HIP(ctx, hipGetLastError());
+  return PM_OK;
+}
+
+int lincomb_batch(pm_ctx* ctx, ConstStage& stage, uint32_t k, const void* const* d_vecs, const size_t* strides,
+                  const uint64_t* coeffs /* [batch][k][4] */, uint32_t batch, size_t n, void* d_out, size_t out_stride,
+                  hipStream_t st) {
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (k == 0 || k > PM_LINCOMB_MAX) return set_err(ctx, PM_ERR_BAD_ARG, "k must be in 1..PM_LINCOMB_MAX");
+  LincombBatchArgs a;
+  memset(&a, 0, sizeof a);
+  a.k = k;
+  for (uint32_t j = 0; j < k; ++j) {
+    a.v[j] = (const u32x4*)d_vecs[j];
+    a.stride[j] = strides[j];
+  }
+  u32(*h)[9];
+  void* d;
+  if (!stage.take(36 * (size_t)k * batch, (void**)&h, &d)) return set_err(ctx, PM_ERR_OOM, "constant table full");
+  for (size_t i = 0; i < (size_t)k * batch; ++i) to_limbs29_shift(h[i], load_fr(coeffs + 4 * i), 1);
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  PM_HIP(ctx, hipMemcpyAsync(d, h, 36 * (size_t)k * batch, hipMemcpyHostToDevice, st));
+  ProfScope prof(ctx, st, "fr_lincomb_batch");
+  hipLaunchKernelGGL(lincomb_batch_kernel, dim3(grid_for(ctx, n), batch), dim3(256), 0, st, a, (const PM_KCONST u32(*)[9])d,
+                     (u32x4*)d_out, out_stride, n);
+  PM_HIP(ctx, hipGetLastError());
+  return PM_OK;
+}
 
 }  // namespace pm
 
@@ -518,29 +814,7 @@ int pm::plonk_quotient_layout(pm_ctx* ctx, const pm_plonk_quotient_args* args, s
   fill_round_consts(kc, load_fr(args->alpha), load_fr(args->beta), load_fr(args->gamma), args->k, args->zh_inv);
   const bool widgets = p.q_range || p.q_logic || p.q_fixed || p.q_var;
   WidgetConsts wc;
-  memset(&wc, 0, sizeof wc);
-  if (widgets) {
-    const host::Field<4>& F = host::FR();
-    auto dev = [&](u32* dst, const HFr& v) { to_limbs29_shift(dst, v, 1); };
-    const struct { u32* dst; u64 v; } small[] = {{wc.c1, 1}, {wc.c2, 2}, {wc.c3, 3}, {wc.c4, 4}, {wc.c9, 9},
-                                                 {wc.c18, 18}, {wc.c81, 81}, {wc.c83, 83}};
-    for (const auto& c : small) dev(c.dst, host::from_u64(c.v, F));
-    // JubJub d = -(10240 / 10241)
-    dev(wc.edwards_d, host::sub(host::zero<4>(), host::mul(host::from_u64(10240, F), host::inv(host::from_u64(10241, F), F), F), F));
-    auto sep_powers = [&](const uint64_t sep[4], u32* s_out, u32 (*k_out)[9], int nk) {
-      const HFr s_ = load_fr(sep), kappa = host::mul(s_, s_, F);
-      dev(s_out, s_);
-      HFr kp = kappa;
-      for (int i = 0; i < nk; ++i) {
-        dev(k_out[i], kp);
-        kp = host::mul(kp, kappa, F);
-      }
-    };
-    sep_powers(args->range_sep, wc.range_sep, wc.range_k, 3);
-    sep_powers(args->logic_sep, wc.logic_sep, wc.logic_k, 4);
-    sep_powers(args->fixed_sep, wc.fixed_sep, wc.fixed_k, 3);
-    sep_powers(args->var_sep, wc.var_sep, wc.var_k, 2);
-  }
+  fill_widget_consts(wc, args, widgets);
   PM_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
   ProfScope prof(ctx, st, "plonk_quotient");

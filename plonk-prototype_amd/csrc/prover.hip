@@ -1073,4 +1073,5 @@ extern "C" int pm_plonk_verifier_key(const pm_prover_key* key, uint64_t (*out)[1
   return PM_OK;
 }
 
+#include "prover_batch.hip.h"
 #include "prover_dist.hip.h"

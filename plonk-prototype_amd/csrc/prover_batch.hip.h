@@ -1,0 +1,505 @@
+// Many proofs of one circuit in one call: pm_plonk_prove_batch (included by prover.hip: the transcript, the widgets'
+// linearisation scalars and the key are shared with prove_body, which is left as it is).
+//
+// B proofs run through every round together.  The workspace is laid out role-major -- every role (wire coefficients,
+// z, PI, the coset forms, t, r, the aggregates, the opening witnesses) holds all B proofs at one uniform stride -- so each
+// transform is ONE pm_fr_ntt_dev call over all of them, each commitment round is pm_g1_msm_batch_dev passes of at most 64
+// vectors, and the O(n) work between them is one proof-batched kernel per step (blockIdx.y = the proof, the per-proof
+// challenges in a device table).  One host synchronisation per round for the whole batch (the MSM's, and the openings'),
+// then one affine conversion for all the round's points and B challenge derivations on the host.  The launches per call
+// do not depend on B, apart from the extra MSM passes above 64 vectors.
+//
+//   coeffs [B][4][n]   wire coefficients (proof-major inside: vector 4 b + j, stride n)
+//   zc, pi_coeffs, pi_evals, num, den  [B][n]
+//   coset_w [B][4][4n]   coset_z, coset_pi, t  [B][4n]
+//   r [B][n]   agg, wit [2][B][n]  (at z, then at z w)
+struct pm_plonk_batch {
+  const pm_prover_key* key = nullptr;
+  uint32_t max_batch = 0;
+  size_t n = 0;
+  void* base = nullptr;      // the one device allocation
+  size_t bytes = 0;
+  void *coeffs = nullptr, *zc = nullptr, *pi_coeffs = nullptr, *pi_evals = nullptr, *num = nullptr, *den = nullptr,
+       *coset_w = nullptr, *coset_z = nullptr, *coset_pi = nullptr, *t = nullptr, *r = nullptr, *agg = nullptr, *wit = nullptr;
+  void *pp_ctl = nullptr, *eval_ws = nullptr, *ruf_ws = nullptr;
+  pm::ConstStage stage;      // per-proof challenge tables: pinned host + device (in `base`)
+  void* pi_h = nullptr;      // pinned staging of the public inputs, grown on demand
+  size_t pi_h_bytes = 0;
+  std::atomic<bool> busy{false};
+  hipStream_t side = nullptr;
+  hipEvent_t ev_main = nullptr, ev_side = nullptr;
+};
+
+namespace {
+constexpr uint32_t BATCH_EVAL_SLOTS = 15 + 9 + 4;   // the openings at z, the ones r(z) needs, the four at z w
+constexpr size_t BATCH_CONST_BYTES_PER_PROOF = 16384, BATCH_CONST_BYTES_FIXED = 16384;
+
+struct BatchBusy {
+  pm_plonk_batch* ws;
+  bool ok;
+  explicit BatchBusy(pm_plonk_batch* w) : ws(w), ok(!w->busy.exchange(true)) {}
+  ~BatchBusy() {
+    if (ok) ws->busy.store(false);
+  }
+};
+
+// commitments to `count` vectors of len coefficients at stride `stride`: passes of at most 64 vectors, one affine conversion
+int batch_commit(pm_ctx* ctx, const pm_bases* ck, const void* d, size_t len, size_t stride, uint32_t count, u64 (*out_xy)[12]) {
+  std::vector<u64> xyz(18 * (size_t)count);
+  for (uint32_t v0 = 0; v0 < count; v0 += 64) {
+    const uint32_t k = std::min<uint32_t>(64, count - v0);
+    PK_TRY(pm_g1_msm_batch_dev(ctx, ck, 0, len, at((void*)d, (size_t)v0 * stride), stride, k, PM_SCALAR_MONTGOMERY,
+                               &xyz[18 * (size_t)v0], nullptr));
+  }
+  return pm_g1_to_affine_batch(xyz.data(), count, &out_xy[0][0], nullptr);
+}
+
+// pi_evals <- 0, then every proof's public inputs in ONE staged scatter (pi_scatter_kernel over global positions b n + i; a
+// repeated position keeps its last value, as in scatter_public_inputs).  The compact lists go through the round-2 scratch
+// num / den, which nothing reads before round 2 (same stream).
+int batch_scatter_pi(pm_ctx* ctx, pm_plonk_batch* ws, uint32_t B, const uint64_t* const* pos, const uint64_t* const* vals,
+                     const size_t* n_pi) {
+  const size_t n = ws->n;
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  PM_HIP(ctx, hipMemsetAsync(ws->pi_evals, 0, (size_t)B * n * 32, ctx->stream));
+  if (!n_pi) return PM_OK;
+  std::vector<unsigned long long> hp;
+  std::vector<uint64_t> hv;
+  std::unordered_map<uint64_t, size_t> last;
+  for (uint32_t b = 0; b < B; ++b) {
+    const size_t k = n_pi[b];
+    if (!k) continue;
+    last.clear();
+    for (size_t i = 0; i < k; ++i) last[pos[b][i]] = i;
+    for (size_t i = 0; i < k; ++i) {
+      if (last[pos[b][i]] != i) continue;
+      hp.push_back((unsigned long long)b * n + pos[b][i]);
+      hv.insert(hv.end(), vals[b] + 4 * i, vals[b] + 4 * i + 4);
+    }
+  }
+  const size_t cnt = hp.size();   // <= B n: fits num (values) and den (positions)
+  if (!cnt) return PM_OK;
+  const size_t need = cnt * 40;
+  if (ws->pi_h_bytes < need) {
+    if (ws->pi_h) PM_HIP(ctx, hipHostFree(ws->pi_h));
+    ws->pi_h = nullptr;
+    ws->pi_h_bytes = 0;
+    PM_HIP(ctx, hipHostMalloc(&ws->pi_h, need, hipHostMallocDefault));
+    ws->pi_h_bytes = need;
+  }
+  memcpy(ws->pi_h, hv.data(), cnt * 32);
+  memcpy((char*)ws->pi_h + cnt * 32, hp.data(), cnt * 8);
+  PM_HIP(ctx, hipMemcpyAsync(ws->num, ws->pi_h, cnt * 32, hipMemcpyHostToDevice, ctx->stream));
+  PM_HIP(ctx, hipMemcpyAsync(ws->den, (char*)ws->pi_h + cnt * 32, cnt * 8, hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(pi_scatter_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, ctx->stream, (const uint4*)ws->num,
+                     (const unsigned long long*)ws->den, cnt, (uint4*)ws->pi_evals);
+  PM_HIP(ctx, hipGetLastError());
+  return PM_OK;
+}
+
+int prove_batch_body(pm_ctx* ctx, pm_prover_key* pk, pm_plonk_batch* ws, const pm_bases* ck, uint32_t B, const void* d_wit,
+                     const uint64_t* const* pi_pos, const uint64_t* const* pi_val, const size_t* n_pi, uint32_t flags,
+                     pm_plonk_proof* out) {
+  const size_t n = pk->n;
+  const uint32_t lg = pk->log_n;
+  const HFr one = fone();
+  ws->stage.reset();
+  std::vector<Transcript> ts(B, pk->base);
+  if (!(flags & PM_PLONK_UPSTREAM_TRANSCRIPT)) {
+    for (uint32_t b = 0; b < B; ++b) {
+      const size_t k = n_pi ? n_pi[b] : 0;
+      ts[b].append_u64(tl::PI_LEN, k);
+      for (size_t i = 0; i < k; ++i) {
+        ts[b].append_u64(tl::PI_POS, pi_pos[b][i]);
+        ts[b].append_scalar(tl::PI_VALUE, get(pi_val[b] + 4 * i));
+      }
+    }
+  }
+  const pm_bases* lag = pk->lagrange;
+  hipStream_t side = ws->side;
+  std::vector<u64> xy_buf(12 * 4 * (size_t)B);
+  u64(*xy)[12] = (u64(*)[12])xy_buf.data();
+  // ---- round 1 --------------------------------------------------------------------------------
+  PK_TRY(batch_scatter_pi(ctx, ws, B, pi_pos, pi_val, n_pi));
+  PK_TRY(pm_fr_ntt_dev(ctx, ws->pi_evals, n, n, ws->pi_coeffs, n, lg, B, PM_NTT_INVERSE, nullptr));
+  if (lag) {
+    // the wires are committed from their values on H: the wire iNTT goes to the side stream with the coset transforms
+    PK_TRY(pm_stream_fork(ctx, side, ws->ev_main));
+    PK_TRY(pm_fr_ntt_dev(ctx, d_wit, n, n, ws->coeffs, n, lg, 4 * B, PM_NTT_INVERSE, side));
+    PK_TRY(pm_fr_ntt_dev(ctx, ws->coeffs, n, n, ws->coset_w, 4 * n, lg + 2, 4 * B, PM_NTT_COSET, side));
+    PK_TRY(pm_fr_ntt_dev(ctx, ws->pi_coeffs, n, n, ws->coset_pi, 4 * n, lg + 2, B, PM_NTT_COSET, side));
+    PK_TRY(batch_commit(ctx, lag, d_wit, n, n, 4 * B, xy));
+  } else {
+    PK_TRY(pm_fr_ntt_dev(ctx, d_wit, n, n, ws->coeffs, n, lg, 4 * B, PM_NTT_INVERSE, nullptr));
+    PK_TRY(pm_stream_fork(ctx, side, ws->ev_main));
+    PK_TRY(pm_fr_ntt_dev(ctx, ws->coeffs, n, n, ws->coset_w, 4 * n, lg + 2, 4 * B, PM_NTT_COSET, side));
+    PK_TRY(pm_fr_ntt_dev(ctx, ws->pi_coeffs, n, n, ws->coset_pi, 4 * n, lg + 2, B, PM_NTT_COSET, side));
+    PK_TRY(batch_commit(ctx, ck, ws->coeffs, n, n, 4 * B, xy));
+  }
+  for (uint32_t b = 0; b < B; ++b)
+    for (int j = 0; j < 4; ++j) {
+      memcpy(out[b].commitments[j], xy[4 * b + j], 96);
+      ts[b].append_commitment(tl::WIRES[j], out[b].commitments[j]);
+    }
+  // ---- round 2 --------------------------------------------------------------------------------
+  std::vector<HFr> beta(B), gamma(B);
+  std::vector<pm_plonk_perm_args> pa(B);
+  for (uint32_t b = 0; b < B; ++b) {
+    beta[b] = ts[b].challenge_scalar(tl::BETA);
+    ts[b].append_scalar(tl::BETA, beta[b]);
+    gamma[b] = ts[b].challenge_scalar(tl::GAMMA);
+    memset(&pa[b], 0, sizeof pa[b]);
+    for (int j = 0; j < 4; ++j) {
+      pa[b].wires[j] = at((void*)d_wit, j * n);   // proof 0; proof b at + 4 b n
+      pa[b].sigmas[j] = at(pk->sigma_evals, j * n);
+    }
+    pa[b].roots = pk->roots;
+    put(pa[b].beta, beta[b]);
+    put(pa[b].gamma, gamma[b]);
+    for (int j = 0; j < 3; ++j) put(pa[b].k[j], pk->k[j]);
+  }
+  PK_TRY(pm::perm_terms_batch(ctx, ws->stage, pa.data(), B, 4 * n, n, ws->num, ws->den, ctx->stream));
+  PK_TRY(pm::fr_batch_inverse_mul(ctx, ws->den, ws->num, (size_t)B * n, nullptr));   // elementwise: one call for all proofs
+  int prc = pm::prefix_product_batch(ctx, ws->den, n, B, ws->num, ws->pp_ctl, ctx->stream);
+  if (prc == PM_ERR_LENGTH) {   // more tiles than are resident at once: the one-vector scan, per proof
+    prc = PM_OK;
+    for (uint32_t b = 0; b < B && !prc; ++b) prc = pm_fr_prefix_product_dev(ctx, at(ws->den, b * n), n, at(ws->num, b * n), nullptr);
+  }
+  PK_TRY(prc);
+  PK_TRY(pm_fr_ntt_dev(ctx, ws->num, n, n, ws->zc, n, lg, B, PM_NTT_INVERSE, nullptr));
+  PK_TRY(pm_stream_fork(ctx, side, ws->ev_main));
+  PK_TRY(pm_fr_ntt_dev(ctx, ws->zc, n, n, ws->coset_z, 4 * n, lg + 2, B, PM_NTT_COSET, side));
+  PK_TRY(batch_commit(ctx, ck, ws->zc, n, n, B, xy));
+  for (uint32_t b = 0; b < B; ++b) {
+    memcpy(out[b].commitments[4], xy[b], 96);
+    ts[b].append_commitment(tl::PERM, out[b].commitments[4]);
+  }
+  // ---- round 3 --------------------------------------------------------------------------------
+  std::vector<HFr> alpha(B), range_sep(B), logic_sep(B), fixed_sep(B), var_sep(B);
+  std::vector<pm_plonk_quotient_args> qa(B);
+  for (uint32_t b = 0; b < B; ++b) {
+    alpha[b] = ts[b].challenge_scalar(tl::ALPHA);
+    range_sep[b] = ts[b].challenge_scalar(tl::RANGE_SEP);
+    logic_sep[b] = ts[b].challenge_scalar(tl::LOGIC_SEP);
+    fixed_sep[b] = ts[b].challenge_scalar(tl::FIXED_SEP);
+    var_sep[b] = ts[b].challenge_scalar(tl::VAR_SEP);
+    pm_plonk_quotient_args& q = qa[b];
+    memset(&q, 0, sizeof q);
+    for (int j = 0; j < 4; ++j) {
+      q.wires[j] = at(ws->coset_w, 4 * n * j);   // proof 0; proof b at + 16 b n (z, PI, t: + 4 b n)
+      q.sigmas[j] = at(pk->sigma_coset, 4 * n * j);
+    }
+    q.z = ws->coset_z;
+    q.pi = ws->coset_pi;
+    q.q_m = pk->sel_coset[Q_M];
+    q.q_l = pk->sel_coset[Q_L];
+    q.q_r = pk->sel_coset[Q_R];
+    q.q_o = pk->sel_coset[Q_O];
+    q.q_c = pk->sel_coset[Q_C];
+    q.q_4 = pk->sel_coset[Q_4];
+    q.q_arith = pk->sel_coset[Q_ARITH];
+    q.q_range = pk->sel_coset[Q_RANGE];
+    q.q_logic = pk->sel_coset[Q_LOGIC];
+    q.q_fixed_group_add = pk->sel_coset[Q_FIXED];
+    q.q_variable_group_add = pk->sel_coset[Q_VAR];
+    q.l1 = pk->l1_coset;
+    q.x = pk->x4;
+    put(q.alpha, alpha[b]);
+    put(q.beta, beta[b]);
+    put(q.gamma, gamma[b]);
+    put(q.range_sep, range_sep[b]);
+    put(q.logic_sep, logic_sep[b]);
+    put(q.fixed_sep, fixed_sep[b]);
+    put(q.var_sep, var_sep[b]);
+    for (int j = 0; j < 3; ++j) put(q.k[j], pk->k[j]);
+    for (int j = 0; j < 4; ++j) put(q.zh_inv[j], pk->zh_inv[j]);
+  }
+  PK_TRY(pm_stream_join(ctx, side, ws->ev_side));   // the wire, PI and z coset forms are ready
+  PK_TRY(pm::quotient_batch(ctx, ws->stage, qa.data(), B, 16 * n, 4 * n, n, ws->t, ctx->stream));
+  PK_TRY(pm_fr_ntt_dev(ctx, ws->t, 4 * n, 4 * n, ws->t, 4 * n, lg + 2, B, PM_NTT_INVERSE | PM_NTT_COSET, nullptr));
+  PK_TRY(batch_commit(ctx, ck, ws->t, n, n, 4 * B, xy));   // t_i of proof b: vector 4 b + i
+  for (uint32_t b = 0; b < B; ++b)
+    for (int i = 0; i < 4; ++i) {
+      memcpy(out[b].commitments[5 + i], xy[4 * b + i], 96);
+      ts[b].append_commitment(tl::QUOTIENT[i], out[b].commitments[5 + i]);
+    }
+  // ---- round 4 --------------------------------------------------------------------------------
+  enum { E_A, E_B, E_C, E_D, E_AN, E_BN, E_DN, E_S1, E_S2, E_S3, E_QARITH, E_QC, E_QL, E_QR, E_ZN, E_T, E_R, NEV };
+  enum { X_QM, X_QO, X_Q4, X_Z, X_S4, X_RANGE, X_LOGIC, X_FIXED, X_VAR, NX };
+  std::vector<HFr> zc(B), zw(B);
+  std::vector<u64> points(8 * (size_t)B);
+  for (uint32_t b = 0; b < B; ++b) {
+    zc[b] = ts[b].challenge_scalar(tl::Z_CHALLENGE);
+    zw[b] = fmul(zc[b], pk->omega);
+    put(&points[8 * b], zc[b]);
+    put(&points[8 * b + 4], zw[b]);
+  }
+  // the openings as prove_body takes them: 15 at z, the values r(z) needs at z, 4 at z w -- one batch, one synchronisation
+  const void* sp[BATCH_EVAL_SLOTS];
+  size_t sstride[BATCH_EVAL_SLOTS];
+  uint8_t spt[BATCH_EVAL_SLOTS];
+  uint32_t K = 0;
+  auto slot = [&](const void* p, size_t stride, uint8_t pt) {
+    sp[K] = p;
+    sstride[K] = stride;
+    spt[K] = pt;
+    ++K;
+  };
+  for (int j = 0; j < 4; ++j) slot(at(ws->coeffs, j * n), 4 * n, 0);
+  for (int j = 0; j < 3; ++j) slot(at(pk->sigma_coeffs, j * n), 0, 0);
+  slot(at(pk->sel_coeffs, Q_ARITH * n), 0, 0);
+  slot(at(pk->sel_coeffs, Q_C * n), 0, 0);
+  slot(at(pk->sel_coeffs, Q_L * n), 0, 0);
+  slot(at(pk->sel_coeffs, Q_R * n), 0, 0);
+  for (int i = 0; i < 4; ++i) slot(at(ws->t, i * n), 4 * n, 0);
+  const uint32_t x0 = K;   // 15
+  slot(at(pk->sel_coeffs, Q_M * n), 0, 0);
+  slot(at(pk->sel_coeffs, Q_O * n), 0, 0);
+  slot(at(pk->sel_coeffs, Q_4 * n), 0, 0);
+  slot(ws->zc, n, 0);
+  slot(at(pk->sigma_coeffs, 3 * n), 0, 0);
+  const int wsel[4] = {Q_RANGE, Q_LOGIC, Q_FIXED, Q_VAR};
+  int xslot[4] = {-1, -1, -1, -1};
+  for (int w = 0; w < 4; ++w)
+    if (!pk->sel_zero[wsel[w]]) {
+      xslot[w] = (int)K;
+      slot(at(pk->sel_coeffs, wsel[w] * n), 0, 0);
+    }
+  const uint32_t w0 = K;
+  slot(at(ws->coeffs, 0), 4 * n, 1);
+  slot(at(ws->coeffs, n), 4 * n, 1);
+  slot(at(ws->coeffs, 3 * n), 4 * n, 1);
+  slot(ws->zc, n, 1);
+  if (K > BATCH_EVAL_SLOTS) return pm::set_err(ctx, PM_ERR_BAD_ARG, "more openings than the workspace holds");
+  std::vector<u64> ov(4 * (size_t)K * B);
+  PK_TRY(pm::evaluate_batch(ctx, ws->stage, K, sp, sstride, spt, points.data(), B, n, ws->eval_ws, ov.data(), ctx->stream));
+  const void* lin_v[12];
+  size_t lin_s[12];
+  uint32_t lk = 0;
+  std::vector<u64> lin_c;   // [B][lk][4]
+  std::vector<HFr> aw(B), aws(B);
+  for (uint32_t b = 0; b < B; ++b) {
+    auto val = [&](uint32_t s) { return get(&ov[4 * ((size_t)b * K + s)]); };
+    HFr ev[NEV], xv[NX];
+    for (int j = 0; j < 4; ++j) ev[E_A + j] = val(j);
+    for (int j = 0; j < 3; ++j) ev[E_S1 + j] = val(4 + j);
+    ev[E_QARITH] = val(7);
+    ev[E_QC] = val(8);
+    ev[E_QL] = val(9);
+    ev[E_QR] = val(10);
+    ev[E_AN] = val(w0);
+    ev[E_BN] = val(w0 + 1);
+    ev[E_DN] = val(w0 + 2);
+    ev[E_ZN] = val(w0 + 3);
+    const HFr z_ = zc[b], zn = fpow(z_, n);
+    ev[E_T] = fadd(val(11), fmul(zn, fadd(val(12), fmul(zn, fadd(val(13), fmul(zn, val(14)))))));
+    for (int j = 0; j < X_RANGE; ++j) xv[j] = val(x0 + j);
+    for (int w = 0; w < 4; ++w) xv[X_RANGE + w] = xslot[w] >= 0 ? val((uint32_t)xslot[w]) : pm::host::zero<4>();
+    // r and r(z): prove_body's linear combination, term by term
+    const HFr &a_ = ev[E_A], &b_ = ev[E_B], &c_ = ev[E_C], &d_ = ev[E_D], &s1 = ev[E_S1], &s2 = ev[E_S2], &s3 = ev[E_S3],
+              &z_next = ev[E_ZN], &qar = ev[E_QARITH];
+    const HFr l1_z = fmul(fsub(zn, one), finv(fmul(fr_u64(n), fsub(z_, one))));
+    const HFr bz = fmul(beta[b], z_);
+    HFr ident = fadd(fadd(a_, bz), gamma[b]);
+    const HFr* wv[3] = {&b_, &c_, &d_};
+    for (int j = 0; j < 3; ++j) ident = fmul(ident, fadd(fadd(*wv[j], fmul(bz, pk->k[j])), gamma[b]));
+    const HFr copy3 = fmul(fmul(fadd(fadd(a_, fmul(beta[b], s1)), gamma[b]), fadd(fadd(b_, fmul(beta[b], s2)), gamma[b])),
+                           fadd(fadd(c_, fmul(beta[b], s3)), gamma[b]));
+    const HFr alpha2 = fmul(alpha[b], alpha[b]);
+    RowEvals re{a_, b_, c_, d_, ev[E_AN], ev[E_BN], ev[E_DN], ev[E_QL], ev[E_QR], ev[E_QC]};
+    uint32_t k = 0;
+    HFr r_z = pm::host::zero<4>();
+    auto term = [&](const void* v, size_t stride, const HFr& c, const HFr& value_at_z) {
+      if (b == 0) {
+        lin_v[k] = v;
+        lin_s[k] = stride;
+      }
+      lin_c.insert(lin_c.end(), c.l, c.l + 4);
+      r_z = fadd(r_z, fmul(c, value_at_z));
+      ++k;
+    };
+    term(at(pk->sel_coeffs, Q_M * n), 0, fmul(qar, fmul(a_, b_)), xv[X_QM]);
+    term(at(pk->sel_coeffs, Q_L * n), 0, fmul(qar, a_), ev[E_QL]);
+    term(at(pk->sel_coeffs, Q_R * n), 0, fmul(qar, b_), ev[E_QR]);
+    term(at(pk->sel_coeffs, Q_O * n), 0, fmul(qar, c_), xv[X_QO]);
+    term(at(pk->sel_coeffs, Q_4 * n), 0, fmul(qar, d_), xv[X_Q4]);
+    term(at(pk->sel_coeffs, Q_C * n), 0, qar, ev[E_QC]);
+    if (!pk->sel_zero[Q_RANGE]) term(at(pk->sel_coeffs, Q_RANGE * n), 0, widget_range(range_sep[b], re), xv[X_RANGE]);
+    if (!pk->sel_zero[Q_LOGIC]) term(at(pk->sel_coeffs, Q_LOGIC * n), 0, widget_logic(logic_sep[b], re), xv[X_LOGIC]);
+    if (!pk->sel_zero[Q_FIXED]) term(at(pk->sel_coeffs, Q_FIXED * n), 0, widget_fixed(fixed_sep[b], re), xv[X_FIXED]);
+    if (!pk->sel_zero[Q_VAR]) term(at(pk->sel_coeffs, Q_VAR * n), 0, widget_var(var_sep[b], re), xv[X_VAR]);
+    term(ws->zc, n, fadd(fmul(alpha[b], ident), fmul(alpha2, l1_z)), xv[X_Z]);
+    term(at(pk->sigma_coeffs, 3 * n), 0, fneg(fmul(fmul(fmul(alpha[b], copy3), beta[b]), z_next)), xv[X_S4]);
+    lk = k;
+    ev[E_R] = r_z;
+    static_assert(NEV == 17, "tl::EVALS lists the evaluations in this enum's order");
+    for (int i = 0; i < NEV; ++i) {
+      ts[b].append_scalar(tl::EVALS[i], ev[i]);
+      put(out[b].evaluations[i], ev[i]);
+    }
+    aw[b] = ts[b].challenge_scalar(tl::AGGREGATE);
+    aws[b] = ts[b].challenge_scalar(tl::AGGREGATE);
+  }
+  PK_TRY(pm::lincomb_batch(ctx, ws->stage, lk, lin_v, lin_s, lin_c.data(), B, n, ws->r, n, ctx->stream));
+  // ---- round 5: CommitKey::compute_aggregate_witness at z and at z w ------------------------------
+  {
+    const void* agg_v[12];
+    size_t agg_s[12];
+    for (int i = 0; i < 4; ++i) {
+      agg_v[i] = at(ws->t, i * n);
+      agg_s[i] = 4 * n;
+    }
+    agg_v[4] = ws->r;
+    agg_s[4] = n;
+    for (int j = 0; j < 4; ++j) {
+      agg_v[5 + j] = at(ws->coeffs, j * n);
+      agg_s[5 + j] = 4 * n;
+    }
+    for (int j = 0; j < 3; ++j) {
+      agg_v[9 + j] = at(pk->sigma_coeffs, j * n);
+      agg_s[9 + j] = 0;
+    }
+    const void* sh_v[4] = {ws->zc, at(ws->coeffs, 0), at(ws->coeffs, n), at(ws->coeffs, 3 * n)};
+    const size_t sh_s[4] = {n, 4 * n, 4 * n, 4 * n};
+    std::vector<u64> agg_c(12 * 4 * (size_t)B), sh_c(4 * 4 * (size_t)B), zs(8 * (size_t)B);
+    for (uint32_t b = 0; b < B; ++b) {
+      const HFr zn = fpow(zc[b], n);
+      HFr ac[12];
+      ac[0] = one;
+      ac[1] = zn;
+      ac[2] = fmul(zn, zn);
+      ac[3] = fmul(ac[2], zn);
+      HFr vp = one;
+      for (int e = 0; e < 8; ++e) {
+        vp = fmul(vp, aw[b]);
+        ac[4 + e] = vp;
+      }
+      for (int i = 0; i < 12; ++i) put(&agg_c[4 * (12 * (size_t)b + i)], ac[i]);
+      vp = one;
+      for (int e = 0; e < 4; ++e) {
+        put(&sh_c[4 * (4 * (size_t)b + e)], vp);
+        vp = fmul(vp, aws[b]);
+      }
+      put(&zs[4 * (size_t)b], zc[b]);
+      put(&zs[4 * ((size_t)B + b)], zw[b]);
+    }
+    PK_TRY(pm::lincomb_batch(ctx, ws->stage, 12, agg_v, agg_s, agg_c.data(), B, n, ws->agg, n, ctx->stream));
+    PK_TRY(pm::lincomb_batch(ctx, ws->stage, 4, sh_v, sh_s, sh_c.data(), B, n, at(ws->agg, (size_t)B * n), n, ctx->stream));
+    PK_TRY(pm::ruffini_batch(ctx, ws->stage, ws->agg, n, n, zs.data(), 2 * B, ws->wit, ws->ruf_ws, ctx->stream));
+  }
+  std::vector<u64> wxy_buf(12 * 2 * (size_t)B);
+  u64(*wxy)[12] = (u64(*)[12])wxy_buf.data();
+  PK_TRY(batch_commit(ctx, ck, ws->wit, n - 1, n, 2 * B, wxy));
+  for (uint32_t b = 0; b < B; ++b) {
+    memcpy(out[b].commitments[9], wxy[b], 96);
+    memcpy(out[b].commitments[10], wxy[B + b], 96);
+    ts[b].append_commitment(tl::W_Z, out[b].commitments[9]);
+    ts[b].append_commitment(tl::W_ZW, out[b].commitments[10]);
+    const HFr chal[10] = {beta[b], gamma[b], alpha[b], range_sep[b], logic_sep[b], fixed_sep[b], var_sep[b], zc[b], aw[b], aws[b]};
+    for (int i = 0; i < 10; ++i) put(out[b].challenges[i], chal[i]);
+  }
+  return PM_OK;
+}
+}  // namespace
+
+extern "C" void pm_plonk_batch_free(pm_ctx* ctx, pm_plonk_batch* ws) {
+  if (!ws) return;
+  if (ctx) (void)pm_sync(ctx);
+  if (ws->side) {
+    (void)hipStreamSynchronize(ws->side);
+    (void)hipStreamDestroy(ws->side);
+  }
+  if (ws->ev_main) (void)hipEventDestroy(ws->ev_main);
+  if (ws->ev_side) (void)hipEventDestroy(ws->ev_side);
+  if (ws->base && ctx) (void)pm_dev_free(ctx, ws->base);
+  if (ws->stage.h) (void)hipHostFree(ws->stage.h);
+  if (ws->pi_h) (void)hipHostFree(ws->pi_h);
+  delete ws;
+}
+
+extern "C" int pm_plonk_batch_create(pm_ctx* ctx, const pm_prover_key* key, uint32_t max_batch, pm_plonk_batch** out) {
+  if (!ctx || !key || !out) return PM_ERR_BAD_ARG;
+  *out = nullptr;
+  if (max_batch == 0 || max_batch > PM_PLONK_MAX_BATCH)
+    return pm::set_err(ctx, PM_ERR_BAD_ARG, "max_batch must be in 1..PM_PLONK_MAX_BATCH");
+  const size_t n = key->n, B = max_batch;
+  pm_plonk_batch* ws = new pm_plonk_batch();
+  ws->key = key;
+  ws->max_batch = max_batch;
+  ws->n = n;
+  struct Region { void** p; size_t bytes; };
+  const size_t bn = B * n * 32;
+  const size_t const_bytes = BATCH_CONST_BYTES_FIXED + B * BATCH_CONST_BYTES_PER_PROOF;
+  void* consts_d = nullptr;
+  const Region regions[] = {{&ws->coeffs, 4 * bn},   {&ws->zc, bn},           {&ws->pi_coeffs, bn},    {&ws->pi_evals, bn},
+                            {&ws->num, bn},          {&ws->den, bn},          {&ws->coset_w, 16 * bn}, {&ws->coset_z, 4 * bn},
+                            {&ws->coset_pi, 4 * bn}, {&ws->t, 4 * bn},        {&ws->r, bn},            {&ws->agg, 2 * bn},
+                            {&ws->wit, 2 * bn},
+                            {&ws->pp_ctl, pm::prefix_product_batch_ctl_bytes(max_batch, n)},
+                            {&ws->eval_ws, pm::evaluate_batch_ws_bytes(BATCH_EVAL_SLOTS, max_batch, n)},
+                            {&ws->ruf_ws, pm::ruffini_batch_ws_bytes(2 * max_batch, n)},
+                            {&consts_d, const_bytes}};
+  size_t total = 0;
+  for (const Region& r : regions) total += (r.bytes + 255) / 256 * 256;
+  int rc = pm_dev_alloc(ctx, total, &ws->base);
+  if (rc) {
+    (void)hipGetLastError();   // a refused hipMalloc stays the thread's last error: the next launch check would report it
+    delete ws;
+    return rc == PM_ERR_OOM ? pm::set_err(ctx, PM_ERR_OOM, "the batch workspace does not fit in device memory") : rc;
+  }
+  ws->bytes = total;
+  size_t off = 0;
+  for (const Region& r : regions) {
+    *r.p = (char*)ws->base + off;
+    off += (r.bytes + 255) / 256 * 256;
+  }
+  if (hipHostMalloc(&ws->stage.h, const_bytes, hipHostMallocDefault) != hipSuccess) {
+    ws->stage.h = nullptr;
+    rc = pm::set_err(ctx, PM_ERR_OOM, "pinned host memory for the batch's constant tables");
+  }
+  ws->stage.d = (char*)consts_d;
+  ws->stage.cap = const_bytes;
+  if (!rc && hipStreamCreateWithFlags(&ws->side, hipStreamNonBlocking) != hipSuccess) rc = PM_ERR_HIP;
+  if (!rc && hipEventCreateWithFlags(&ws->ev_main, hipEventDisableTiming) != hipSuccess) rc = PM_ERR_HIP;
+  if (!rc && hipEventCreateWithFlags(&ws->ev_side, hipEventDisableTiming) != hipSuccess) rc = PM_ERR_HIP;
+  if (rc) {
+    pm_plonk_batch_free(ctx, ws);
+    return rc;
+  }
+  *out = ws;
+  return PM_OK;
+}
+
+extern "C" size_t pm_plonk_batch_bytes(const pm_plonk_batch* ws) { return ws ? ws->bytes : 0; }
+
+extern "C" int pm_plonk_prove_batch(pm_ctx* ctx, pm_prover_key* pk, pm_plonk_batch* ws, const pm_bases* ck, uint32_t batch,
+                                    const void* d_witnesses, const uint64_t* const* pi_positions, const uint64_t* const* pi_values,
+                                    const size_t* n_pi, uint32_t flags, pm_plonk_proof* out) {
+  if (!ctx) return PM_ERR_BAD_ARG;
+  if (!pk || !ws || !ck || !d_witnesses || !out) return pm::set_err(ctx, PM_ERR_BAD_ARG, "null argument");
+  if (ws->key != pk) return pm::set_err(ctx, PM_ERR_BAD_ARG, "the batch workspace was made for another key");
+  if (batch == 0 || batch > ws->max_batch) return pm::set_err(ctx, PM_ERR_BAD_ARG, "batch must be in 1..max_batch of the workspace");
+  if (flags & ~(PM_PLONK_BIND_PUBLIC_INPUTS | PM_PLONK_UPSTREAM_TRANSCRIPT)) return pm::set_err(ctx, PM_ERR_BAD_ARG, "unknown flags");
+  if (flags == (PM_PLONK_BIND_PUBLIC_INPUTS | PM_PLONK_UPSTREAM_TRANSCRIPT))
+    return pm::set_err(ctx, PM_ERR_BAD_ARG, "PM_PLONK_BIND_PUBLIC_INPUTS and PM_PLONK_UPSTREAM_TRANSCRIPT exclude each other");
+  if (!pk->committed) return pm::set_err(ctx, PM_ERR_BAD_ARG, "the key is not committed (pm_plonk_key_commit first)");
+  BatchBusy guard(ws);
+  if (!guard.ok) return pm::set_err(ctx, PM_ERR_BUSY, "the batch workspace is in use by another call");
+  const size_t n = pk->n;
+  if (pm_g1_bases_len(ck) < n) return pm::set_err(ctx, PM_ERR_LENGTH, "commit key shorter than n");
+  for (uint32_t b = 0; n_pi && b < batch; ++b) {
+    if (!n_pi[b]) continue;
+    if (!pi_positions || !pi_values || !pi_positions[b] || !pi_values[b])
+      return pm::set_err(ctx, PM_ERR_BAD_ARG, "public inputs announced without positions or values");
+    for (size_t i = 0; i < n_pi[b]; ++i)
+      if (pi_positions[b][i] >= n) return pm::set_err(ctx, PM_ERR_LENGTH, "a public-input position is not below n");
+  }
+  if (pk->lagrange && ck != pk->lagrange_ck)
+    return pm::set_err(ctx, PM_ERR_BAD_ARG, "the key's Lagrange form was checked against another commit key");
+  const int rc = prove_batch_body(ctx, pk, ws, ck, batch, d_witnesses, pi_positions, pi_values, n_pi, flags, out);
+  if (rc) {   // nothing of this call may still run on the side stream when the next one starts
+    (void)hipStreamSynchronize(ws->side);
+    (void)pm_sync(ctx);
+  }
+  return rc;
+}

@@ -164,9 +164,50 @@ class ProverKey:
                                                       lck._bases._h if lck is not None else None))
         self._lagrange = lck
 
+    def batch(self, max_batch: int) -> "BatchWorkspace":
+        """A workspace for ``prove_batch`` of up to ``max_batch`` (<= 64) proofs on this key: about 42 n x 32 bytes of
+        device memory per proof, held until ``free()``.  It is separate from the key's own workspace."""
+        return BatchWorkspace(self, max_batch)
+
     def free(self):
         if getattr(self, "_h", None) and self.ctx._h:
             self.ctx._lib.pm_plonk_key_free(self.ctx._h, self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+class BatchWorkspace:
+    """``pm_plonk_batch``: the per-proof polynomials of up to ``max_batch`` proofs on one key (``ProverKey.batch``), and the
+    staging into which ``prove_batch`` copies a list of per-proof witnesses."""
+
+    def __init__(self, pk: ProverKey, max_batch: int):
+        self.pk, self.ctx, self.max_batch = pk, pk.ctx, int(max_batch)
+        h = C.c_void_p()
+        self.ctx._check(self.ctx._lib.pm_plonk_batch_create(self.ctx._h, pk._h, self.max_batch, C.byref(h)))
+        self._h = h
+        self._staging: DeviceVector | None = None
+
+    def device_bytes(self) -> int:
+        """Device bytes the workspace holds (``pm_plonk_batch_bytes``; the witness staging not included)."""
+        return int(self.ctx._lib.pm_plonk_batch_bytes(self._h))
+
+    def staging(self) -> DeviceVector:
+        """max_batch x 4n elements of device memory for proof-major witnesses, allocated on first use."""
+        if self._staging is None:
+            self._staging = DeviceVector(self.ctx, self.max_batch * 4 * self.pk.n)
+        return self._staging
+
+    def free(self):
+        if getattr(self, "_staging", None) is not None:
+            self._staging.free()
+            self._staging = None
+        if getattr(self, "_h", None) and self.ctx._h:
+            self.ctx._lib.pm_plonk_batch_free(self.ctx._h, self._h)
         self._h = None
 
     def __del__(self):
@@ -351,6 +392,85 @@ def prove(pk: ProverKey, ck: CommitKey, witness, public_inputs=None, bind_public
         if own:
             d_wit.free()
     return _proof_from_raw(ctx, raw)
+
+
+def _pi_pairs(public_inputs) -> tuple[np.ndarray, np.ndarray]:
+    if isinstance(public_inputs, tuple):
+        pos, val = public_inputs
+        return (np.ascontiguousarray(pos, dtype=np.uint64).reshape(-1),
+                np.ascontiguousarray(val, dtype=np.uint64).reshape(-1, 4))
+    if isinstance(public_inputs, DeviceVector):
+        public_inputs = public_inputs.to_host()
+    return sparse_public_inputs(public_inputs)
+
+
+def prove_batch(pk: ProverKey, ck: CommitKey, witnesses, public_inputs=None, bind_public_inputs: bool = True,
+                workspace: BatchWorkspace | None = None) -> list[Proof]:
+    """B proofs of one circuit in one ``pm_plonk_prove_batch`` call; proof b equals ``prove(pk, ck, witness b, public
+    inputs b)`` byte for byte.
+
+    witnesses: one DeviceVector of B x 4n elements (proof-major: proof b's [a | b | c | d] at 4 n b), or a list of B
+    per-proof witnesses -- DeviceVectors of 4n elements, copied device to device into the workspace's staging (one copy
+    kernel per proof, 4n x 64 bytes of traffic each), or host arrays [4, n, 4], uploaded there.  public_inputs: None, or a
+    list of B entries in any form ``prove`` takes (None, dense [n, 4], a (positions, values) pair).  workspace: a
+    ``ProverKey.batch`` workspace with max_batch >= B; None makes one for the call."""
+    ctx, n = pk.ctx, pk.n
+    if ck.max_degree() + 1 < n:
+        raise ValueError("commit key shorter than the circuit")
+    if pk.verifier_key is None:
+        pk.commit(ck)
+    if isinstance(witnesses, DeviceVector):
+        if witnesses.n % (4 * n) or witnesses.n == 0:
+            raise ValueError("a batch of device witnesses must hold a positive multiple of 4n elements")
+        B = witnesses.n // (4 * n)
+    else:
+        witnesses = list(witnesses)
+        B = len(witnesses)
+    if B == 0:
+        raise ValueError("empty batch")
+    own_ws = workspace is None
+    ws = pk.batch(B) if own_ws else workspace
+    try:
+        if isinstance(witnesses, DeviceVector):
+            d_wit = witnesses
+        else:
+            d_wit = ws.staging()
+            if B > ws.max_batch:
+                raise ValueError("more witnesses than the workspace's max_batch")
+            one = fr_to_limbs(1).astype(np.uint64)
+            vecs = (C.c_void_p * 1)()
+            for b, w in enumerate(witnesses):
+                dst = d_wit.view(4 * n * b, 4 * n)
+                if isinstance(w, DeviceVector):
+                    if w.n != 4 * n:
+                        raise ValueError("each device witness must hold 4n elements")
+                    vecs[0] = w.ptr
+                    ctx._check(ctx._lib.pm_fr_lincomb_dev(ctx._h, 1, vecs, one.ctypes.data_as(_lib.u64p), 4 * n,
+                                                          dst._p, None))   # the copy: 1 x w
+                else:
+                    a = np.ascontiguousarray(w, dtype=np.uint64).reshape(4 * n, 4)
+                    ctx._check(ctx._lib.pm_dev_upload(ctx._h, dst._p, a.ctypes.data_as(C.c_void_p), 4 * n * 32))
+        if public_inputs is None:
+            public_inputs = [None] * B
+        if len(public_inputs) != B:
+            raise ValueError("one public-input entry per proof")
+        pairs = [_pi_pairs(p) for p in public_inputs]
+        p_pos = (_lib.u64p * B)()
+        p_val = (_lib.u64p * B)()
+        counts = (C.c_size_t * B)()
+        for b, (pos, val) in enumerate(pairs):
+            counts[b] = pos.size
+            if pos.size:
+                p_pos[b] = pos.ctypes.data_as(_lib.u64p)
+                p_val[b] = val.ctypes.data_as(_lib.u64p)
+        raws = (_lib.PlonkProof * B)()
+        flags = 0 if bind_public_inputs else _lib.PLONK_UPSTREAM_TRANSCRIPT
+        ctx._check(ctx._lib.pm_plonk_prove_batch(ctx._h, pk._h, ws._h, ck._bases._h, B, d_wit._p, p_pos, p_val, counts,
+                                                 flags, raws))
+    finally:
+        if own_ws:
+            ws.free()
+    return [_proof_from_raw(ctx, raws[b]) for b in range(B)]
 
 
 def seeded_transcript(verifier_key: dict, n: int, label: bytes | None = None) -> Transcript:

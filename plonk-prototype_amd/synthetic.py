@@ -52,6 +52,37 @@ def chain_circuit(n: int, seed: int = 1, public_rows=(0,), zero_selectors=()):
     return circuit, witness, fr_vec_to_limbs(pi)
 
 
+def chain_witnesses(n: int, seed: int = 1, count: int = 1, witness_seed: int = 1, public_rows=(0,), zero_selectors=()):
+    """-> ``count`` (witness [4, n, 4], public_inputs [n, 4]) pairs, all satisfying the one circuit that
+    ``chain_circuit(n, seed, zero_selectors=zero_selectors)`` builds (its selectors and sigma do not depend on the witness):
+    each pair has its own start value v[0] and its own public inputs.  ``public_rows`` is one tuple of rows for every pair
+    or a list of ``count`` tuples, one per pair (an empty tuple: no public input).  Deterministic in (seed, witness_seed)."""
+    rng = random.Random(seed)
+    rnd = lambda: rng.getrandbits(256) % R_MOD   # noqa: E731
+    q = {k: [rnd() for _ in range(n)] for k in ("q_m", "q_l", "q_r", "q_4", "q_c")}   # chain_circuit's draws, in its order
+    for k in zero_selectors:
+        q[k] = [0] * n
+    qm, ql, qr, q4, qc = q["q_m"], q["q_l"], q["q_r"], q["q_4"], q["q_c"]
+    rows_per = list(public_rows) if public_rows and isinstance(public_rows[0], (tuple, list, range)) else [public_rows] * count
+    if len(rows_per) != count:
+        raise ValueError("public_rows: one tuple of rows, or one per witness")
+    ar = np.arange(n, dtype=np.int64)
+    var = np.concatenate([ar, np.maximum(ar - 1, 0), ar + 1, np.maximum(ar - 2, 0)])
+    out = []
+    for w in range(count):
+        wr = random.Random(f"chain_witnesses:{seed}:{witness_seed}:{w}")
+        pi = [0] * n
+        for r_ in rows_per[w]:
+            pi[r_] = wr.getrandbits(256) % R_MOD
+        v = [0] * (n + 1)
+        v[0] = wr.getrandbits(256) % R_MOD
+        for i in range(n):
+            a, b, d = v[i], v[i - 1 if i else 0], v[i - 2 if i >= 2 else 0]
+            v[i + 1] = (qm[i] * a % R_MOD * b + ql[i] * a + qr[i] * b + q4[i] * d + qc[i] + pi[i]) % R_MOD
+        out.append((fr_vec_to_limbs(v)[var].reshape(4, n, 4), fr_vec_to_limbs(pi)))
+    return out
+
+
 def _sigma_cycles(var: np.ndarray) -> np.ndarray:
     """var[j n + i] = the variable at wire j of gate i -> sigma_index (flat): each variable's positions form one cycle."""
     order = np.argsort(var, kind="stable")
@@ -75,7 +106,10 @@ def boolean_circuit(n: int, seed: int = 1):
         c_0 = 4 bit_0 + 2 bit_1 + bit_2,   c_k = 4 c_(k-1) + 2 bit_(2k+1) + bit_(2k+2)   (a = c_(k-1), b, d = bits)
     Copy constraints tie each bit row's a, b and c together, every use of a bit to its row, each c_k to the next
     row's a, and all the d = 0 of bit rows to one another.  At least 95 % of the wire values are 0 or 1 from
-    B = 64 on (31 of 32 at n = 8).  No public input."""
+    B = 64 on (31 of 32 at n = 8).  No public input.
+
+    The seed draws only the bits: every seed gives the same circuit (selectors and sigma) with its own witness, so
+    ``boolean_circuit(n, s)`` for several s are distinct witnesses of one circuit (a batch for ``prove_batch``)."""
     if n < 8 or n & (n - 1):
         raise ValueError("boolean_circuit needs a power-of-two n >= 8")
     rng = np.random.default_rng(seed)
