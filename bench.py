@@ -1,6 +1,6 @@
 """Headline benchmark: BLS12-381 Fr NTT butterflies/s (+ G1 MSM scalar-muls/s) on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1 runs either under torch.distributed.run (one rank per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the
 environment) or bare: with WORLD_SIZE unset this process starts the N ranks itself as child processes (launch_ranks),
@@ -9,7 +9,10 @@ relays rank 0's one line and exits with the largest child code.
 A step = one pass of the hot path over one batch of synthetic input resident in HBM:
 a forward and an inverse 2^20-point NTT (BASELINE.json configs[1]).  `value` is whole-job
 butterflies/s over all ranks (weak scaling: every rank transforms its own polynomials, no
-collective on the data path).  The same JSON line carries the MSM leg (configs[2]: 2^20-point
+collective on the data path).  A plain run measures that alone: set-up, warm-up, the timed steps, the round-trip
+check of the last one, --dump-outputs and the line, whose `roofline`, `cpu_baseline` and leg fields are then null.
+
+With --full the same JSON line also carries the MSM leg (configs[2]: 2^20-point
 G1 MSM; with N > 1 the points are sharded over the ranks and the 144-byte partials are
 all-gathered over RCCL and folded), the full-prove leg (configs[3]: a 2^20-gate synthetic circuit
 through the native prover: `prover`, with `prover.all_gate_kinds` = the same size with every widget selector
@@ -388,6 +391,10 @@ def main():
                     help="after the timed steps, write what the last one computed on rank 0 (the forward and the inverse "
                          "transform) to DIR/<name>.npy: float64 [rows, 8], the 32-bit halves of the Montgomery limbs, low "
                          f"first; up to {DUMP_MAX_ROWS} rows, a fixed seeded sample beyond that")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: the roofline's profiled loop, the NTT extras, the MSM, "
+                         "next-rows and prover legs and the CPU baseline (the --no-* and leg-size options apply to these).  "
+                         "Without it the run sets up, warms up, times the steps, dumps and prints the line, nothing else")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -466,9 +473,10 @@ def main():
     oracle = CpuOracle()
     ctx = pa.Context(local_rank)
     # N > 1: the exchange step runs through the library's own RCCL communicator (pm_comm_init); if creating it
-    # fails on any rank, every rank falls back to torch.distributed for the 2.3 KB all-gathers (same fold)
+    # fails on any rank, every rank falls back to torch.distributed for the 2.3 KB all-gathers (same fold).  Only the
+    # --full legs exchange data: a plain run creates no communicator
     native_comm = False
-    if world > 1 and backend == "nccl":
+    if world > 1 and backend == "nccl" and args.full:
         native_comm = setup_native_comm(ctx, rank, world, dist, coll_dev, lambda m_: print(m_, file=sys.stderr, flush=True))
         if native_comm and args.comm_timeout_ms > 0:
             # a peer that dies inside an exchange: the library ends the blocked call with ncclCommAbort after this long and the
@@ -542,6 +550,54 @@ def main():
               "warmup_steps_run": warmup_steps, "region_ms_device": round(dt * 1e3, 4),
               "region_ms_host_clock": round(dt_host * 1e3, 4),
               "value_by_host_clock": world * butterflies_per_step * args.steps / dt_host}
+    passes = pa.ntt_plan(k)
+
+    # ------------------------------------------------------------------ the one JSON line, and a safety net for N > 1
+    # The headline above needs no data-path collective; the legs below do when N > 1 (the sharded MSM and prover through
+    # RCCL).  `roofline` and `legs` hold what has finished (a plain run leaves them empty); with N > 1 a watchdog prints the
+    # line with what there is and ends the process if the remaining legs do not finish in time (a collective that never
+    # returns has no other way out), so the driver always gets its line.
+    roofline, legs = None, {}
+
+    def emit_line(note=None):
+        out = {"metric": "bls12_381_fr_ntt_butterflies_per_s", "value": value, "unit": "butterflies/s",
+               "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
+               "timing": timing,
+               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32x9 (29-bit limbs, Fr)",
+               "data": "synthetic",
+               "config": {"workload": f"forward + inverse BLS12-381 Fr NTT, 2^{k} points, device resident, "
+                                      f"natural order in/out, bit-exact vs oracle", "log_n": k, "passes": passes,
+                          "parallelism": f"{world} independent polynomial(s), one per GPU"},
+               "exchange": (None if world == 1 or not args.full else
+                            "library RCCL communicator (pm_comm_init / pm_g1_allgather_fold)" if native_comm else
+                            f"torch.distributed ({backend})"),
+               "roofline": roofline, "cpu_baseline": legs.get("cpu"), "ntt_extra": legs.get("ntt_extra"),
+               "ntt_fourstep": legs.get("fourstep"), "msm": legs.get("msm"), "msm_large": legs.get("msm_large"),
+               "next_rows": legs.get("poly"), "prover": legs.get("prover")}
+        if note:
+            out["note"] = note
+        return emitter.emit(out)
+
+    state["emit"] = emit_line
+
+    def finish():
+        if dog:
+            # the line goes out with the watchdog still armed; close / destroy then run under a short deadline of their own, and a
+            # teardown that hangs AFTER the complete line is out ends the rank with code 0
+            dog.extend(90, "teardown (context close + process group destroy)", exit_code=0)
+        if rank == 0:
+            emit_line()
+        ctx.close()
+        if world > 1:
+            dist.destroy_process_group()
+        if dog:
+            dog.finish()
+
+    if not args.full:
+        finish()                         # a plain run: the headline is all it measures
+        return
+
+    # ------------------------------------------------------------------ roofline (--full)
     prof_steps = 200                                              # fixed: the kernels' mean durations must not depend on --steps
     ctx.profile(True)
     barrier()
@@ -556,7 +612,6 @@ def main():
     prof = pre
 
     # roofline of the dominant kernel: algorithmic bytes of one launch / its mean duration
-    passes = pa.ntt_plan(k)
     kern = dict(pre)                                               # live: the profiled loop of this run
     dom_ms = kern[dom][1] / kern[dom][0]
     s_dom = passes[0] if dom.endswith("first") or dom.endswith("single") else passes[-1]
@@ -600,32 +655,6 @@ def main():
                         "quarter of the launch is not arithmetic and an issue-ceiling fraction quoted for the pass is not a "
                         "whole-kernel efficiency"}
 
-    # ------------------------------------------------------------------ the one JSON line, and a safety net for N > 1
-    # The headline above needs no data-path collective; the legs below do when N > 1 (the sharded MSM and prover through
-    # RCCL).  `legs` collects what has finished; with N > 1 a watchdog prints the line with what there is and ends the
-    # process if the remaining legs do not finish in time (a collective that never returns has no other way out), so the
-    # driver always gets its line.
-    legs = {}
-
-    def emit_line(note=None):
-        out = {"metric": "bls12_381_fr_ntt_butterflies_per_s", "value": value, "unit": "butterflies/s",
-               "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-               "timing": timing,
-               "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32x9 (29-bit limbs, Fr)",
-               "data": "synthetic",
-               "config": {"workload": f"forward + inverse BLS12-381 Fr NTT, 2^{k} points, device resident, "
-                                      f"natural order in/out, bit-exact vs oracle", "log_n": k, "passes": passes,
-                          "parallelism": f"{world} independent polynomial(s), one per GPU"},
-               "exchange": (None if world == 1 else "library RCCL communicator (pm_comm_init / pm_g1_allgather_fold)"
-                            if native_comm else f"torch.distributed ({backend})"),
-               "roofline": roofline, "cpu_baseline": legs.get("cpu"), "ntt_extra": legs.get("ntt_extra"),
-               "ntt_fourstep": legs.get("fourstep"), "msm": legs.get("msm"), "msm_large": legs.get("msm_large"),
-               "next_rows": legs.get("poly"), "prover": legs.get("prover")}
-        if note:
-            out["note"] = note
-        return emitter.emit(out)
-
-    state["emit"] = emit_line
     if dog:
         dog.extend(args.leg_timeout, "multi-GPU legs (sharded MSM / prover)")
 
@@ -1494,17 +1523,7 @@ def main():
             cpu["msm_single_thread_sample"] = f"one 2^{s1n.bit_length() - 1}-point Pippenger MSM on 1 thread ({t1msm:.1f} s)"
 
     legs.update(cpu=cpu, ntt_extra=ntt_extra, fourstep=fourstep, msm=msm, msm_large=msm_large, poly=poly, prover=prover)
-    if dog:
-        # the line goes out with the watchdog still armed; close / destroy then run under a short deadline of their own, and a
-        # teardown that hangs AFTER the complete line is out ends the rank with code 0
-        dog.extend(90, "teardown (context close + process group destroy)", exit_code=0)
-    if rank == 0:
-        emit_line()
-    ctx.close()
-    if world > 1:
-        dist.destroy_process_group()
-    if dog:
-        dog.finish()
+    finish()
 
 
 if __name__ == "__main__":

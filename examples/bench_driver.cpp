@@ -6,7 +6,7 @@
 //   * a 2^log_n-point G1 MSM over a resident SRS stand-in P_i = g^i G generated ON the device (pm_fr_powers_dev +
 //     pm_g1_fixed_base_mul_dev + pm_g1_bases_from_dev, window table precomputed): scalar-muls/s = n / t; check: the
 //     discrete-log identity sum_i s_i P_i == (sum_i s_i g^i) G, the right side by one 1-point MSM.
-// bench.py stays the driver-facing benchmark (one JSON line with roofline and CPU baseline); this file shows the same library
+// bench.py stays the driver-facing benchmark (one JSON line; with --full also the roofline and CPU baseline); this file shows the same library
 // reaching the same rates without the Python process around it.
 //   g++ -std=c++17 -O2 examples/bench_driver.cpp -Iinclude -Lplonk-prototype_amd/lib -lplonk_mi355x
 //       -Wl,-rpath,$PWD/plonk-prototype_amd/lib -o bench_driver && ./bench_driver [log_n = 20] [steps = 50] [msm_steps = 5]

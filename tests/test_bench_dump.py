@@ -1,6 +1,7 @@
 """`bench.py --dump-outputs DIR` and `--steps`: the dump is exact (32-bit halves of the Montgomery limbs in float64), the
 row sample is fixed, the whole dump stays under 64 MB, a non-positive step count is refused, and on the GPU the files hold
-the forward transform of the bench's seeded input and its inverse (= the input), as the CPU oracle computes them."""
+the forward transform of the bench's seeded input and its inverse (= the input), as the CPU oracle computes them, from a
+plain run that measures nothing but the headline step."""
 import json
 import os
 import subprocess
@@ -49,12 +50,14 @@ def test_steps_must_be_positive(steps):
 def test_dump_outputs_on_the_gpu(tmp_path, oracle):
     k, steps = 12, 7
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "2",
-           "--log-n", str(k), "--no-msm", "--no-poly", "--no-prover", "--no-ntt-extra", "--no-cpu-baseline",
-           "--dump-outputs", str(tmp_path / "out")]
+           "--log-n", str(k), "--dump-outputs", str(tmp_path / "out")]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
     assert p.returncode == 0, p.stderr[-4000:]
     line = json.loads(p.stdout.strip().splitlines()[-1])
     assert line["steps"] == steps and line["ms_per_step"] > 0
+    # a plain run (no --full) measures the headline step alone
+    assert all(line[f] is None for f in ("roofline", "cpu_baseline", "ntt_extra", "ntt_fourstep", "msm", "msm_large",
+                                         "next_rows", "prover")), line
     assert sorted(os.listdir(tmp_path / "out")) == ["ntt_forward.npy", "ntt_inverse.npy"]
     a = oracle.fr_sample(0x504C4F4E4B, 1 << k)                    # the bench's input on rank 0
     assert np.array_equal(_from_words(np.load(tmp_path / "out" / "ntt_forward.npy")), oracle.fr_ntt(a, k, 0))

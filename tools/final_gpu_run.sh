@@ -26,7 +26,7 @@ if [ $PART != 1 ]; then
 # bench.py quotes roofline.traffic from THIS round's committed PMC summaries: on the box they are the ones just made
 # (refresh_profiles.sh copies the same files into profiles/ afterwards, so the committed line and its sources agree)
 for k in pmc_summary pmc_prover_summary pmc_big_summary; do [ -s $OUT/$k.json ] && cp $OUT/$k.json profiles/${ROUND}_$k.json; done
-( time timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err ) 2> $OUT/bench.time && \
+( time timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err ) 2> $OUT/bench.time && \
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.txt 2>&1 && \
 opt poly_rows.txt 300 python tools/poly_rows.py 22 10 && \
 opt poly_rows_2p20.txt 300 python tools/poly_rows.py 20 10 && \
@@ -37,8 +37,8 @@ opt prover24.txt 400 python tools/prover_bench.py 24 3 wide && \
 opt small_proofs.txt 200 python tools/small_proof_c_sweep.py 10,11,12,13,14,15,16,17 0 && \
 opt proof_latency_trace.txt 200 python tools/proof_latency_trace.py && \
 (cd /tmp && export TMPDIR=/tmp && \
- timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_headline -- python3 $R/bench.py --steps 200 --no-cpu-baseline --no-msm --no-poly --no-prover --no-ntt-extra > $OUT/stats_headline.json 2> $OUT/stats_headline.err && \
- timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py --steps 20 --no-cpu-baseline --msm-large-log-n 0 --prover-large-log-n 0 --no-poly --no-ntt-extra > $OUT/stats_bench.json 2> $OUT/stats.err && \
+ timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_headline -- python3 $R/bench.py --full --steps 200 --no-cpu-baseline --no-msm --no-poly --no-prover --no-ntt-extra > $OUT/stats_headline.json 2> $OUT/stats_headline.err && \
+ timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $R/bench.py --full --steps 20 --no-cpu-baseline --msm-large-log-n 0 --prover-large-log-n 0 --no-poly --no-ntt-extra > $OUT/stats_bench.json 2> $OUT/stats.err && \
  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_msm -- python3 $R/tools/msm_table_sweep.py 20 20 0 > $OUT/stats_msm.txt 2> $OUT/stats_msm.err && \
  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_msm24 -- python3 $R/tools/msm_table_sweep.py 24 22 0 > $OUT/stats_msm24.txt 2> $OUT/stats_msm24.err)
 echo "final rc=$?"
