@@ -405,6 +405,30 @@ int pm_plonk_key_set_lagrange(pm_ctx* ctx, pm_prover_key* key, const pm_bases* c
 int pm_plonk_prove(pm_ctx* ctx, pm_prover_key* key, const pm_bases* commit_key, const void* d_witness,
                    const uint64_t* pi_positions, const uint64_t* pi_values, size_t n_pi, uint32_t flags,
                    pm_plonk_proof* out);
+/* ---- Zero-knowledge proofs -----------------------------------------------------------------
+ * pm_plonk_prove_zk makes a proof in the same format, transcript and challenge derivation as pm_plonk_prove (the
+ * verifier does not change) whose wires, permutation polynomial and quotient pieces are blinded with the caller's
+ * PM_PLONK_ZK_BLINDERS scalars b[0..16] (Montgomery limbs like the witness, each below r; Z_H = X^n - 1):
+ *   a, b, d   w + (b_k + b_{k+1} X + b_{k+2} X^2) Z_H     a: k = 0, b: k = 3, d: k = 8
+ *   c         c + (b_6 + b_7 X) Z_H
+ *   z         z + (b_11 + b_12 X + b_13 X^2) Z_H
+ *   t pieces  t_1 + b_14 X^n,  t_2 - b_14 + b_15 X^n,  t_3 - b_15 + b_16 X^n,  t_4 - b_16
+ * The blinded quotient has degree up to 4n + 9, so t_4 holds n + 10 coefficients and the commit key needs at least
+ * n + PM_PLONK_ZK_EXTRA_BASES resident bases (PM_ERR_LENGTH otherwise).  Blinders must be fresh uniform scalars for every
+ * proof (fixed blinders are for tests only).
+ * pm_plonk_key_enable_zk (committed key; idempotent) builds the key's second 4n coset 7 w_8n H_4n -- selectors, sigmas
+ * and L_1 there -- and the padded per-proof workspace; added_bytes (may be NULL) receives the device bytes the zero-
+ * knowledge state holds, the same figure on every call.  pm_plonk_prove_zk takes the flags of pm_plonk_prove and uses a
+ * Lagrange key attached to the key (the proof is byte-identical without it).  With all blinders zero the proof is
+ * byte-identical to pm_plonk_prove's.  Errors: key not enabled, NULL or non-canonical blinders, bad flags:
+ * PM_ERR_BAD_ARG; a short commit key: PM_ERR_LENGTH; a key in use: PM_ERR_BUSY.  Single GPU only; pm_plonk_prove
+ * on an enabled key is unchanged. */
+#define PM_PLONK_ZK_BLINDERS 17
+#define PM_PLONK_ZK_EXTRA_BASES 10
+int pm_plonk_key_enable_zk(pm_ctx* ctx, pm_prover_key* key, size_t* added_bytes);
+int pm_plonk_prove_zk(pm_ctx* ctx, pm_prover_key* key, const pm_bases* commit_key, const void* d_witness,
+                      const uint64_t* pi_positions, const uint64_t* pi_values, size_t n_pi, uint32_t flags,
+                      const uint64_t (*blinders)[4], pm_plonk_proof* out);
 /* ---- Many proofs of one circuit in one call -----------------------------------------------------------------------
  * A batch workspace holds the per-proof polynomials of up to max_batch proofs on one committed key (about 42 n x 32 bytes
  * per proof, one device allocation; PM_ERR_OOM when it does not fit).  The key's own workspace and busy flag are not

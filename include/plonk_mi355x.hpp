@@ -383,6 +383,30 @@ class ProverKey {
                                bind_public_inputs ? 0u : PM_PLONK_UPSTREAM_TRANSCRIPT, &raw));
     return from_raw(raw);
   }
+  // Zero-knowledge proofs (pm_plonk_key_enable_zk): builds the key's second 4n coset and the padded workspace once
+  // (idempotent); returns the device bytes that state holds.
+  size_t enable_zk() {
+    size_t added = 0;
+    ctx_->check(pm_plonk_key_enable_zk(ctx_->get(), key_, &added));
+    return added;
+  }
+  // A proof that hides the witness (pm_plonk_prove_zk), same format and verifier as prove().  blinders: PM_PLONK_ZK_BLINDERS
+  // fresh uniform scalars below r for every proof; ck must hold n + PM_PLONK_ZK_EXTRA_BASES points.
+  Proof prove_zk(const CommitKey& ck, const DevicePolynomial& witness, const std::array<Fr, PM_PLONK_ZK_BLINDERS>& blinders,
+                 const std::vector<PublicInput>& public_inputs = {}, bool bind_public_inputs = true) const {
+    if (witness.len() != 4 * n_) throw Error(PM_ERR_LENGTH, "the witness must hold 4n wire values");
+    std::vector<uint64_t> pos, val;
+    for (const PublicInput& pi : public_inputs) {
+      pos.push_back(pi.position);
+      val.insert(val.end(), pi.value.begin(), pi.value.end());
+    }
+    uint64_t bl[PM_PLONK_ZK_BLINDERS][4];
+    for (int i = 0; i < PM_PLONK_ZK_BLINDERS; ++i) std::copy(blinders[i].begin(), blinders[i].end(), bl[i]);
+    pm_plonk_proof raw;
+    ctx_->check(pm_plonk_prove_zk(ctx_->get(), key_, ck.bases(), witness.data(), pos.data(), val.data(), pos.size(),
+                                  bind_public_inputs ? 0u : PM_PLONK_UPSTREAM_TRANSCRIPT, bl, &raw));
+    return from_raw(raw);
+  }
   // A workspace for prove_batch of up to max_batch (<= PM_PLONK_MAX_BATCH) proofs: about 42 n x 32 bytes per proof
   BatchWorkspace batch(uint32_t max_batch) const { return BatchWorkspace(*ctx_, key_, max_batch); }
   // B proofs in one call: witnesses holds B x [a | b | c | d] (B x 4n, proof-major), public_inputs[b] the inputs of proof b

@@ -125,6 +125,9 @@ SIGNATURES = {
     "pm_plonk_verifier_key": (C.c_int, [C.c_void_p, C.c_void_p]),
     "pm_plonk_prove": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, u64p, u64p, C.c_size_t, C.c_uint32,
                                  C.POINTER(PlonkProof)]),
+    "pm_plonk_key_enable_zk": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]),
+    "pm_plonk_prove_zk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, u64p, u64p, C.c_size_t, C.c_uint32,
+                                    u64p, C.POINTER(PlonkProof)]),
     "pm_plonk_prove_sharded": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, u64p, u64p,
                                          C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(PlonkProof)]),
     "pm_plonk_transcript_labels": (C.c_char_p, []),
@@ -174,6 +177,9 @@ PM_ERR_NO_DEVICE = -5
 PM_ERR_LENGTH = -6
 PM_ERR_EXCHANGE = -7
 PM_ERR_BUSY = -8
+
+PLONK_ZK_BLINDERS = 17        # pm_plonk_prove_zk: blinding scalars per proof
+PLONK_ZK_EXTRA_BASES = 10     # ... and commit-key points it needs beyond n
 
 NTT_INVERSE = 1
 NTT_COSET = 2

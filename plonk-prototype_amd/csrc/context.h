@@ -217,6 +217,36 @@ int evaluate_batch(pm_ctx* ctx, ConstStage& stage, uint32_t k, const void* const
 size_t ruffini_batch_ws_bytes(uint32_t count, size_t n);
 int ruffini_batch(pm_ctx* ctx, ConstStage& stage, const void* d_in, size_t n, size_t stride, const uint64_t* zs /* [count][4] */,
                   uint32_t count, void* d_out, void* d_ws, hipStream_t st);
+// zero-knowledge mode (pm_plonk_prove_zk; plonk_rounds.hip).  Coefficient vectors at a padded stride S, blinders in the
+// kernel arguments as canonical Montgomery limbs.
+constexpr uint32_t ZK_MAX_VECS = 5;      // a b c d z
+constexpr uint32_t ZK_MAX_TERMS = 3;     // blinder terms per vector
+constexpr uint32_t ZK_MAX_SHIFT = 16;    // vectors per second-coset shift launch
+constexpr size_t ZK_P1_LEN = 10;         // coefficients of t' beyond X^4n: deg t' <= 4n + 9
+struct ZkBlindArgs {
+  void* v[ZK_MAX_VECS];                  // coefficient vectors, n coefficients + a zero-filled tail up to the stride
+  uint32_t terms[ZK_MAX_VECS];           // blinder terms of each (2 or 3)
+  uint64_t beta[ZK_MAX_VECS][ZK_MAX_TERMS][4];
+};
+struct ZkShiftArgs {
+  const void* src[ZK_MAX_SHIFT];
+  void* dst[ZK_MAX_SHIFT];
+  uint32_t count;
+};
+struct ZkCombineConsts {
+  uint32_t inv2[9], inv2s[9];            // 1 / 2 and 1 / (2 * 7^4n), device form
+  uint64_t beta[3][4];                   // the quotient blinders b_14 .. b_16
+};
+// w + (beta . X^i) Z_H on `count` vectors (stride S) in one launch
+int zk_blind(pm_ctx* ctx, const ZkBlindArgs& a, uint32_t count, size_t n, size_t stride, hipStream_t st);
+// dst_j[i] = src_j[i] w_8n^i, i < len (d_w8: w_8n^i, 4n entries)
+int zk_shift(pm_ctx* ctx, const ZkShiftArgs& a, const void* d_w8, size_t len, hipStream_t st);
+// the two coset quotients (d_ab: A then B(X / w_8n), 4n coefficients each) -> t_1..t_4 with their blinders, stride S
+int zk_combine(pm_ctx* ctx, const void* d_ab, const void* d_w8, size_t n, size_t stride, const uint64_t inv2[4],
+               const uint64_t inv2s[4], const uint64_t beta[3][4], void* d_t, hipStream_t st);
+// poly_evaluate_groups with a length per group
+int poly_evaluate_groups_n(pm_ctx* ctx, uint32_t groups, const uint32_t* k, const void* const* const* polys,
+                           const uint64_t* const* points, uint64_t* const* outs, const size_t* ns);
 struct OrderScope {
   pm_ctx* ctx;
   StreamOrder& o;

@@ -694,6 +694,110 @@ int lincomb_batch(pm_ctx* ctx, ConstStage& stage, uint32_t k, const void* const*
   return PM_OK;
 }
 
+// ---- zero-knowledge mode (pm_plonk_prove_zk).  Coefficient vectors live at a padded stride
+// S = n + PM_ZK_PAD; blinders arrive as kernel arguments (canonical Montgomery limbs), never through host round trips.
+
+// w(X) + (beta_0 + ... + beta_{t-1} X^{t-1}) Z_H(X) in place: coefficient i < t loses beta_i, coefficient n + i becomes
+// beta_i, and the rest of the tail [n, S) is zeroed.  One block per vector (blockIdx.y), S - n <= 64 threads busy.
+__global__ void __launch_bounds__(64) zk_blind_kernel(const ZkBlindArgs a, size_t n, size_t tail) {
+  const u32 v = blockIdx.y, t = threadIdx.x;
+  u32x4* p = (u32x4*)a.v[v];
+  const u32 terms = a.terms[v];
+  if (t < tail) {
+    const Fr b = t < terms ? fe_unpack<FrP>((const u32*)a.beta[v][t]) : fe_zero<FrP>();
+    st_canon(p, n + t, b);
+  }
+  if (t < terms) st_canon(p, t, wsub(ld_canon(p, t), fe_unpack<FrP>((const u32*)a.beta[v][t])));
+}
+int zk_blind(pm_ctx* ctx, const ZkBlindArgs& a, uint32_t count, size_t n, size_t stride, hipStream_t st) {
+  if (count == 0 || count > ZK_MAX_VECS || stride < n || stride - n > 64 || n < ZK_MAX_TERMS) return PM_ERR_BAD_ARG;
+  for (uint32_t v = 0; v < count; ++v)
+    if (!a.v[v] || a.terms[v] > ZK_MAX_TERMS || a.terms[v] > stride - n) return PM_ERR_BAD_ARG;
+  if (!st) st = ctx->stream;   // as in every entry point: no stream = the context's own
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  ProfScope prof(ctx, st, "plonk_zk_blind");
+  hipLaunchKernelGGL(zk_blind_kernel, dim3(1, count), dim3(64), 0, st, a, n, stride - n);
+  PM_HIP(ctx, hipGetLastError());
+  return PM_OK;
+}
+
+// dst_j[i] = src_j[i] w_8n^i, i < len: p(X) -> p(w_8n X), whose 7 H_4n coset transform is p on the second coset
+// 7 w_8n H_4n.  One pass for the whole batch; w8[i] = w_8n^i in ABI form.
+__global__ void __launch_bounds__(256) zk_shift_kernel(const ZkShiftArgs a, const u32x4* w8, size_t len) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < len; i += stride) {
+    const Fr w = to_dev(ld_canon(w8, i));
+    for (u32 j = 0; j < a.count; ++j) st_canon((u32x4*)a.dst[j], i, fe_mul<FrP>(ld_canon((const u32x4*)a.src[j], i), w));   // ABI x device -> ABI
+  }
+}
+int zk_shift(pm_ctx* ctx, const ZkShiftArgs& a, const void* d_w8, size_t len, hipStream_t st) {
+  if (a.count == 0 || a.count > ZK_MAX_SHIFT || !d_w8) return PM_ERR_BAD_ARG;
+  for (uint32_t j = 0; j < a.count; ++j)
+    if (!a.src[j] || !a.dst[j]) return PM_ERR_BAD_ARG;
+  if (len == 0) return PM_OK;
+  if (!st) st = ctx->stream;
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  ProfScope prof(ctx, st, "plonk_zk_shift");
+  hipLaunchKernelGGL(zk_shift_kernel, dim3(grid_for(ctx, len)), dim3(256), 0, st, a, (const u32x4*)d_w8, len);
+  PM_HIP(ctx, hipGetLastError());
+  return PM_OK;
+}
+
+// The quotient t' (degree < 4n + ZK_P1_LEN) from A = t' mod (X^4n - s) and B = t' mod (X^4n + s), s = 7^4n: ab holds the
+// coefficients of A (4n) and then those of B(X / w_8n) (4n; the plain coset inverse of the second-coset values), so
+// B_j = ab[4n + j] w_8n^-j with w_8n^-j = -w_8n^(4n - j) for j > 0.  t' = P0 + X^4n P1, P0 = (A + B) / 2, P1 = (A - B) / 2s.
+// Writes the four pieces at stride S with the X^n blinders: t_1 + b_14 X^n, t_2 - b_14 + b_15 X^n, t_3 - b_15 + b_16 X^n,
+// t_4 - b_16 (t_4 = coefficients 3n .. 4n + ZK_P1_LEN); every element of the 4 x S output is written.
+__global__ void __launch_bounds__(256) zk_combine_kernel(const u32x4* ab, const u32x4* w8, size_t n, size_t S, const ZkCombineConsts kc,
+                                                         u32x4* t) {
+  const size_t n4 = 4 * n, tail = S - n, total = n4 + 4 * tail;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
+    size_t k, i, j;       // output piece, index in it, and the coefficient j < 4n of A and B to combine (if any)
+    bool high;            // P1_j (piece 4 beyond n) instead of P0_j
+    if (e < n4) {
+      j = e;
+      k = j / n;
+      i = j - k * n;
+      high = false;
+    } else {
+      k = (e - n4) / tail;
+      i = n + (e - n4 - k * tail);
+      j = i - n;
+      high = true;
+      if (k < 3 || j >= ZK_P1_LEN) {   // the blinder coefficient X^n of t_1..t_3, zeros elsewhere
+        const Fr b = (k < 3 && j == 0) ? fe_unpack<FrP>((const u32*)kc.beta[k]) : fe_zero<FrP>();
+        st_canon(t, k * S + i, b);
+        continue;
+      }
+    }
+    const Fr a_ = ld_canon(ab, j);
+    const Fr p = fe_mul<FrP>(ld_canon(ab, n4 + j), to_dev(ld_canon(w8, j ? n4 - j : 0)));   // B_j = p (j = 0), -p (j > 0)
+    const bool plus = (j == 0) != high;                                                      // A + B_j or A - B_j
+    const Fr s_ = plus ? wadd(a_, p) : wsub(a_, p);
+    Fr v = fe_mul<FrP>(s_, fr_limbs(high ? kc.inv2s : kc.inv2));
+    if (!high && i == 0 && k > 0) v = wsub(v, fe_unpack<FrP>((const u32*)kc.beta[k - 1]));
+    st_canon(t, k * S + i, v);
+  }
+}
+int zk_combine(pm_ctx* ctx, const void* d_ab, const void* d_w8, size_t n, size_t stride, const uint64_t inv2[4],
+               const uint64_t inv2s[4], const uint64_t beta[3][4], void* d_t, hipStream_t st) {
+  if (!d_ab || !d_w8 || !d_t || 4 * n < ZK_P1_LEN || stride < n + ZK_P1_LEN) return PM_ERR_BAD_ARG;
+  ZkCombineConsts kc;
+  memset(&kc, 0, sizeof kc);
+  to_limbs29(kc.inv2, load_fr(inv2));
+  to_limbs29(kc.inv2s, load_fr(inv2s));
+  memcpy(kc.beta, beta, sizeof kc.beta);
+  const size_t total = 4 * n + 4 * (stride - n);
+  if (!st) st = ctx->stream;
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  ProfScope prof(ctx, st, "plonk_zk_combine");
+  hipLaunchKernelGGL(zk_combine_kernel, dim3(grid_for(ctx, total)), dim3(256), 0, st, (const u32x4*)d_ab, (const u32x4*)d_w8, n,
+                     stride, kc, (u32x4*)d_t);
+  PM_HIP(ctx, hipGetLastError());
+  return PM_OK;
+}
+
 }  // namespace pm
 
 using namespace pm;

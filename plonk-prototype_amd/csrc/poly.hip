@@ -1221,9 +1221,15 @@ extern "C" int pm_fr_poly_evaluate_many_dev(pm_ctx* ctx, uint32_t k, const void*
 // synchronisation, on the context's stream.
 int pm::poly_evaluate_groups(pm_ctx* ctx, uint32_t groups, const uint32_t* k, const void* const* const* polys,
                              const uint64_t* const* points, uint64_t* const* outs, size_t n) {
-  if (!ctx || !k || !polys || !points || !outs || n == 0 || groups == 0 || groups > 3) return PM_ERR_BAD_ARG;
+  const size_t ns[3] = {n, n, n};
+  return poly_evaluate_groups_n(ctx, groups, k, polys, points, outs, ns);
+}
+// The same with its own polynomial length per group (the zero-knowledge prover opens padded and key polynomials together).
+int pm::poly_evaluate_groups_n(pm_ctx* ctx, uint32_t groups, const uint32_t* k, const void* const* const* polys,
+                               const uint64_t* const* points, uint64_t* const* outs, const size_t* ns) {
+  if (!ctx || !k || !polys || !points || !outs || !ns || groups == 0 || groups > 3) return PM_ERR_BAD_ARG;
   for (uint32_t g = 0; g < groups; ++g)
-    if (k[g] == 0 || k[g] > PM_LINCOMB_MAX || !polys[g] || !points[g] || !outs[g]) return PM_ERR_BAD_ARG;
+    if (ns[g] == 0 || k[g] == 0 || k[g] > PM_LINCOMB_MAX || !polys[g] || !points[g] || !outs[g]) return PM_ERR_BAD_ARG;
   std::lock_guard<std::mutex> lk(ctx->mu);
   PM_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
@@ -1231,14 +1237,14 @@ int pm::poly_evaluate_groups(pm_ctx* ctx, uint32_t groups, const uint32_t* k, co
   int rc = order_scope.rc;
   if (rc) return rc;
   size_t off[4] = {0, 0, 0, 0};
-  for (uint32_t g = 0; g < groups; ++g) off[g + 1] = off[g] + eval_slot_bytes(k[g], n);
+  for (uint32_t g = 0; g < groups; ++g) off[g + 1] = off[g] + eval_slot_bytes(k[g], ns[g]);
   rc = ensure_buffer(ctx, ctx->poly_ws, off[groups]);
   if (rc) return rc;
   // results through pinned memory: a copy to the caller's pageable arrays would block the host until the batch is done
   if (!ctx->poly_host_pinned) PM_HIP(ctx, hipHostMalloc(&ctx->poly_host_pinned, 3 * PM_LINCOMB_MAX * 32, hipHostMallocDefault));
   uint64_t* h = (uint64_t*)ctx->poly_host_pinned;
   for (uint32_t g = 0; g < groups && !rc; ++g)
-    rc = eval_enqueue(ctx, st, k[g], polys[g], n, points[g], h + 4 * PM_LINCOMB_MAX * g, (char*)ctx->poly_ws.ptr + off[g]);
+    rc = eval_enqueue(ctx, st, k[g], polys[g], ns[g], points[g], h + 4 * PM_LINCOMB_MAX * g, (char*)ctx->poly_ws.ptr + off[g]);
   if (rc) return rc;
   PM_HIP(ctx, hipStreamSynchronize(st));
   for (uint32_t g = 0; g < groups; ++g) memcpy(outs[g], h + 4 * PM_LINCOMB_MAX * g, 32 * (size_t)k[g]);

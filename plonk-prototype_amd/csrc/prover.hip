@@ -17,6 +17,7 @@
 #include <atomic>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -275,6 +276,20 @@ HFr widget_var(const HFr& sep, const RowEvals& e) {
 }
 }  // namespace
 
+// Zero-knowledge mode (pm_plonk_key_enable_zk): the second 4n coset 7 w_8n H_4n of the key and a
+// per-proof workspace whose coefficient vectors have the padded stride S = n + ZK_PAD (zero tails).
+constexpr size_t ZK_PAD = 16;
+struct ZkState {
+  size_t stride = 0, bytes = 0;
+  HFr zh_inv2[4], inv2, inv2s;        // 1 / Z_H on the second coset by i mod 4; 1 / 2; 1 / (2 * 7^4n)
+  void *w8 = nullptr /* w_8n^i, 4n */, *x2 = nullptr /* 7 w_8n w_4n^i, 4n */, *sigma_coset2 = nullptr /* 16n */,
+       *l1_coset2 = nullptr;
+  void* sel_coset2[NSEL] = {};        // where the key has sel_coset
+  // per proof: coeffs [a b c d z pi] 6 S | shift 6 S | coset2 [a b c d z pi] 24 n | ab 8 n | t 4 S | r S | agg S | wit 2 S
+  void *coeffs = nullptr, *shift = nullptr, *coset2 = nullptr, *ab = nullptr, *t = nullptr, *r = nullptr, *agg = nullptr,
+       *wit = nullptr;
+};
+
 struct pm_prover_key {
   size_t n = 0;
   uint32_t log_n = 0;
@@ -298,6 +313,7 @@ struct pm_prover_key {
   // Lagrange-form commit key (pm_plonk_key_set_lagrange; not owned) and the commit key it was checked against
   const pm_bases* lagrange = nullptr;
   const pm_bases* lagrange_ck = nullptr;
+  ZkState* zk = nullptr;               // pm_plonk_key_enable_zk
 };
 
 // side stream <- everything submitted on the context's stream so far / the reverse
@@ -332,6 +348,14 @@ extern "C" void pm_plonk_key_free(pm_ctx* ctx, pm_prover_key* pk) {
     if (p && ctx) (void)pm_dev_free(ctx, p);
   for (void* p : pk->sel_coset)
     if (p && ctx) (void)pm_dev_free(ctx, p);
+  if (ZkState* zs = pk->zk) {
+    for (void* p : {zs->w8, zs->x2, zs->sigma_coset2, zs->l1_coset2, zs->coeffs, zs->shift, zs->coset2, zs->ab, zs->t, zs->r,
+                    zs->agg, zs->wit})
+      if (p && ctx) (void)pm_dev_free(ctx, p);
+    for (void* p : zs->sel_coset2)
+      if (p && ctx) (void)pm_dev_free(ctx, p);
+    delete zs;
+  }
   delete pk;
 }
 
@@ -710,6 +734,89 @@ extern "C" int pm_plonk_key_set_lagrange(pm_ctx* ctx, pm_prover_key* key, const 
   return PM_OK;
 }
 
+// The key's side of the zero-knowledge mode.  A blinded quotient t' has degree up to 4n + 9, more
+// than the 4n points of the coset 7 H_4n determine; the second coset 7 w_8n H_4n (x^4n = -7^4n there, against +7^4n on the
+// first) gives t' mod (X^4n + s) beside t' mod (X^4n - s).  On it x^n = 7^n w_8 w_4^i, so 1 / Z_H still has period 4 and the
+// next row is still index + 4: pm_plonk_quotient_dev runs unchanged, given this coset's x, 1 / Z_H and the key's
+// polynomials there -- the selectors it reads, the sigmas and L_1, built here once.
+extern "C" int pm_plonk_key_enable_zk(pm_ctx* ctx, pm_prover_key* pk, size_t* added_bytes) {
+  if (!ctx || !pk) return PM_ERR_BAD_ARG;
+  if (!pk->committed) return pm::set_err(ctx, PM_ERR_BAD_ARG, "pm_plonk_key_commit first");
+  BusyGuard guard(pk);
+  if (!guard.ok) return PM_ERR_BUSY;
+  if (pk->zk) {
+    if (added_bytes) *added_bytes = pk->zk->bytes;
+    return PM_OK;
+  }
+  const size_t n = pk->n, S = n + ZK_PAD;
+  const uint32_t lg = pk->log_n;
+  u64 w8[4], w4[4], unused[4], si[4];
+  PK_TRY(pm_domain_info(lg + 3, w8, unused, unused));
+  PK_TRY(pm_domain_info(lg + 2, w4, unused, unused));
+  PK_TRY(pm_domain_info(lg, unused, unused, si));
+  ZkState* zs = new ZkState();
+  zs->stride = S;
+  struct Alloc { void** p; size_t elems; };
+  std::vector<Alloc> allocs = {{&zs->w8, 4 * n},     {&zs->x2, 4 * n},     {&zs->sigma_coset2, 16 * n}, {&zs->l1_coset2, 4 * n},
+                               {&zs->coeffs, 6 * S}, {&zs->shift, 6 * S},  {&zs->coset2, 24 * n},      {&zs->ab, 8 * n},
+                               {&zs->t, 4 * S},      {&zs->r, S},          {&zs->agg, S},              {&zs->wit, 2 * S}};
+  for (int s_ = 0; s_ < NSEL; ++s_)
+    if (pk->sel_coset[s_]) allocs.push_back({&zs->sel_coset2[s_], 4 * n});
+  int rc = PM_OK;
+  for (const Alloc& a : allocs) {
+    if ((rc = pm_dev_alloc(ctx, a.elems * 32, a.p)) != PM_OK) break;
+    zs->bytes += a.elems * 32;
+  }
+  const HFr one = fone(), g = fr_u64(7), omega8 = get(w8), omega4 = get(w4), g2 = fmul(g, omega8);
+  if (!rc) rc = pm_fr_powers_dev(ctx, omega8.l, one.l, 4 * n, zs->w8, nullptr);
+  if (!rc) rc = pm_fr_powers_dev(ctx, omega4.l, g2.l, 4 * n, zs->x2, nullptr);
+  // the padded tails start (and, for the public-input slot, stay) zero
+  if (!rc && hipMemsetAsync(zs->coeffs, 0, 6 * S * 32, ctx->stream) != hipSuccess) rc = PM_ERR_HIP;
+  // key polynomials -> the second coset: p(w_8n X) on the first coset's transform.  coset2 is scratch until the first proof.
+  pm::ZkShiftArgs sa;
+  memset(&sa, 0, sizeof sa);
+  for (int s_ = 0; s_ < NSEL; ++s_)
+    if (pk->sel_coset[s_]) {
+      sa.src[sa.count] = at(pk->sel_coeffs, s_ * n);
+      sa.dst[sa.count++] = at(zs->coset2, s_ * n);
+    }
+  for (int j = 0; j < 4; ++j) {
+    sa.src[sa.count] = at(pk->sigma_coeffs, j * n);
+    sa.dst[sa.count++] = at(zs->coset2, (NSEL + j) * n);
+  }
+  void* l1_src = at(zs->coset2, (NSEL + 5) * n);   // L_1 = (1 / n) sum X^i
+  if (!rc) rc = pm_fr_powers_dev(ctx, one.l, si, n, l1_src, nullptr);
+  sa.src[sa.count] = l1_src;
+  sa.dst[sa.count++] = at(zs->coset2, (NSEL + 4) * n);
+  if (!rc) rc = pm::zk_shift(ctx, sa, zs->w8, n, ctx->stream);
+  for (int s_ = 0; s_ < NSEL && !rc; ++s_)
+    if (pk->sel_coset[s_])
+      rc = pm_fr_ntt_dev(ctx, at(zs->coset2, s_ * n), n, n, zs->sel_coset2[s_], 4 * n, lg + 2, 1, PM_NTT_COSET, nullptr);
+  if (!rc) rc = pm_fr_ntt_dev(ctx, at(zs->coset2, NSEL * n), n, n, zs->sigma_coset2, 4 * n, lg + 2, 4, PM_NTT_COSET, nullptr);
+  if (!rc) rc = pm_fr_ntt_dev(ctx, at(zs->coset2, (NSEL + 4) * n), n, n, zs->l1_coset2, 4 * n, lg + 2, 1, PM_NTT_COSET, nullptr);
+  if (!rc) rc = pm_sync(ctx);
+  if (!rc) {
+    // Z_H(7 w_8n w_4n^i) = (7 w_8n)^n (w_4n^n)^i - 1, period 4; s = 7^4n
+    const HFr gn = fpow(g2, n), i4 = fpow(omega4, n);
+    HFr p = one;
+    for (int k = 0; k < 4; ++k) {
+      zs->zh_inv2[k] = finv(fsub(fmul(gn, p), one));
+      p = fmul(p, i4);
+    }
+    zs->inv2 = finv(fr_u64(2));
+    zs->inv2s = finv(fmul(fr_u64(2), fpow(g, 4 * n)));
+  }
+  if (rc) {
+    for (const Alloc& a : allocs)
+      if (*a.p) (void)pm_dev_free(ctx, *a.p);
+    delete zs;
+    return rc;
+  }
+  pk->zk = zs;
+  if (added_bytes) *added_bytes = zs->bytes;
+  return PM_OK;
+}
+
 // pi_evals <- 0, then the sparse public inputs (a repeated position keeps its last value).  A handful goes up
 // element by element; longer lists are staged as compact (position, value) arrays in the round-2 scratch
 // (num / den are not written before round 2, which is ordered after this on the same stream) and scattered by
@@ -752,13 +859,13 @@ static int scatter_public_inputs(pm_ctx* ctx, pm_prover_key* pk, const uint64_t*
 
 static int prove_body(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, const Shard& shard, const void* d_witness,
                       const uint64_t* pi_positions, const uint64_t* pi_values, size_t n_pi, uint32_t flags,
-                      pm_plonk_proof* out);
+                      const uint64_t (*blinders)[4], pm_plonk_proof* out);
 static int prove_impl(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, const Shard& shard, const void* d_witness,
                       const uint64_t* pi_positions, const uint64_t* pi_values, size_t n_pi, uint32_t flags,
-                      pm_plonk_proof* out) {
+                      const uint64_t (*blinders)[4], pm_plonk_proof* out) {
   if (ctx && ctx->marks_on) ctx->marks.clear();
   pm::host_mark(ctx, "prove: start");
-  const int rc = shard_leave(ctx, shard, prove_body(ctx, pk, ck, shard, d_witness, pi_positions, pi_values, n_pi, flags, out));
+  const int rc = shard_leave(ctx, shard, prove_body(ctx, pk, ck, shard, d_witness, pi_positions, pi_values, n_pi, flags, blinders, out));
   pm::host_mark(ctx, "prove: end");
   if (ctx && ctx->marks_on && !ctx->marks.empty()) {   // PM_HOST_MARKS=1: where the host's time between the kernels goes
     const double t0 = ctx->marks.front().second;
@@ -781,28 +888,98 @@ extern "C" int pm_plonk_prove_sharded(pm_ctx* ctx, pm_prover_key* pk, const pm_b
   sh.fn = exchange;
   sh.user = user;
   sh.expect = 4;
-  return prove_impl(ctx, pk, ck_slice, sh, d_witness, pi_positions, pi_values, n_pi, flags, out);
+  return prove_impl(ctx, pk, ck_slice, sh, d_witness, pi_positions, pi_values, n_pi, flags, nullptr, out);
 }
 
 extern "C" int pm_plonk_prove(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, const void* d_witness,
                               const uint64_t* pi_positions, const uint64_t* pi_values, size_t n_pi, uint32_t flags,
                               pm_plonk_proof* out) {
-  return prove_impl(ctx, pk, ck, Shard(), d_witness, pi_positions, pi_values, n_pi, flags, out);
+  return prove_impl(ctx, pk, ck, Shard(), d_witness, pi_positions, pi_values, n_pi, flags, nullptr, out);
+}
+
+extern "C" int pm_plonk_prove_zk(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, const void* d_witness,
+                                 const uint64_t* pi_positions, const uint64_t* pi_values, size_t n_pi, uint32_t flags,
+                                 const uint64_t (*blinders)[4], pm_plonk_proof* out) {
+  if (!blinders) return PM_ERR_BAD_ARG;
+  return prove_impl(ctx, pk, ck, Shard(), d_witness, pi_positions, pi_values, n_pi, flags, blinders, out);
+}
+
+// Blinded wire commitments over a Lagrange key: [w] from the witness values, plus the blinder's
+// sum_i b_i ([tau^(n+i)] - [tau^i]).  The blinded coefficients hold b_i at n + i, so two MSMs of 3 points take those same
+// scalars, over the commit key at offset n and at offset 0, and the second result is negated before the host fold.
+static int commit_lagrange_zk(pm_ctx* ctx, const pm_bases* lag, const pm_bases* ck, const void* d_witness, const void* wc,
+                              size_t n, size_t S, u64 (*out_xy)[12]) {
+  u64 xyz[3][4 * 18], sum[4][18];
+  PK_TRY(pm_g1_msm_batch_dev(ctx, lag, 0, n, d_witness, n, 4, PM_SCALAR_MONTGOMERY, xyz[0], nullptr));
+  PK_TRY(pm_g1_msm_batch_dev(ctx, ck, n, 3, at((void*)wc, n), S, 4, PM_SCALAR_MONTGOMERY, xyz[1], nullptr));
+  PK_TRY(pm_g1_msm_batch_dev(ctx, ck, 0, 3, at((void*)wc, n), S, 4, PM_SCALAR_MONTGOMERY, xyz[2], nullptr));
+  for (int w = 0; w < 4; ++w) {
+    u64 parts[3][18];
+    for (int k = 0; k < 3; ++k) memcpy(parts[k], xyz[k] + 18 * w, sizeof parts[k]);
+    HFp y;
+    memcpy(y.l, parts[2] + 6, 48);
+    y = pm::host::sub(pm::host::zero<6>(), y, pm::host::FP());   // -P = (X, -Y, Z)
+    memcpy(parts[2] + 6, y.l, 48);
+    PK_TRY(pm_g1_fold(&parts[0][0], 3, sum[w]));
+  }
+  return pm_g1_to_affine_batch(&sum[0][0], 4, &out_xy[0][0], nullptr);
 }
 
 static int prove_body(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, const Shard& shard, const void* d_witness,
                       const uint64_t* pi_positions, const uint64_t* pi_values, size_t n_pi, uint32_t flags,
-                      pm_plonk_proof* out) {
+                      const uint64_t (*blinders)[4], pm_plonk_proof* out) {
   if (!ctx || !pk || !ck || !d_witness || !out) return PM_ERR_BAD_ARG;
   if (n_pi && (!pi_positions || !pi_values)) return PM_ERR_BAD_ARG;
   if (flags & ~(PM_PLONK_BIND_PUBLIC_INPUTS | PM_PLONK_UPSTREAM_TRANSCRIPT)) return PM_ERR_BAD_ARG;
   if (flags == (PM_PLONK_BIND_PUBLIC_INPUTS | PM_PLONK_UPSTREAM_TRANSCRIPT)) return PM_ERR_BAD_ARG;   // the two modes exclude each other
   if (!pk->committed) return PM_ERR_BAD_ARG;   // pm_plonk_key_commit first: the transcript starts from the verifier key
+  if (blinders)
+    for (int i = 0; i < PM_PLONK_ZK_BLINDERS; ++i)
+      if (pm::host::geq<4>(blinders[i], FRF().m)) return pm::set_err(ctx, PM_ERR_BAD_ARG, "a blinder is not below r");
   BusyGuard guard(pk);
   if (!guard.ok) return PM_ERR_BUSY;
   const size_t n = pk->n;
   const uint32_t lg = pk->log_n;
-  if (!shard.on && pm_g1_bases_len(ck) < n) return PM_ERR_LENGTH;
+  // zero-knowledge mode (pm_plonk_prove_zk): blinded wires and z of n + 3 coefficients, quotient pieces up to n + 10, all
+  // at the padded stride S in the key's ZK workspace.  Otherwise S = n and the key's own workspace.
+  ZkState* const zs = blinders ? pk->zk : nullptr;
+  if (blinders && !zs) return pm::set_err(ctx, PM_ERR_BAD_ARG, "pm_plonk_key_enable_zk first");
+  if (!shard.on && pm_g1_bases_len(ck) < (zs ? n + PM_PLONK_ZK_EXTRA_BASES : n)) return PM_ERR_LENGTH;
+  const size_t S = zs ? zs->stride : n;
+  const size_t wlen = zs ? n + 3 : n;                // coefficients of the wires and of z
+  void* const wc = zs ? zs->coeffs : pk->coeffs;     // [a b c d z pi] at stride S
+  auto blind = [&](uint32_t first, uint32_t count, hipStream_t st) -> int {   // vectors first.. of wc with their Z_H blinders
+    static const uint32_t TERMS[5] = {3, 3, 2, 3, 3}, FIRST[5] = {0, 3, 6, 8, 11};
+    pm::ZkBlindArgs ba;
+    memset(&ba, 0, sizeof ba);
+    for (uint32_t v = 0; v < count; ++v) {
+      const uint32_t w = first + v;
+      ba.v[v] = at(wc, w * S);
+      ba.terms[v] = TERMS[w];
+      for (uint32_t i = 0; i < TERMS[w]; ++i) memcpy(ba.beta[v][i], blinders[FIRST[w] + i], 32);
+    }
+    return pm::zk_blind(ctx, ba, count, n, S, st);
+  };
+  // coefficient slots of wc -> the same slots of zs->coset2 on the second coset: one w_8n^i scaling pass for all of them,
+  // then the coset NTT per run of consecutive slots
+  auto second_coset = [&](std::initializer_list<uint32_t> slots, hipStream_t st) -> int {
+    pm::ZkShiftArgs sa;
+    memset(&sa, 0, sizeof sa);
+    for (uint32_t w : slots) {
+      sa.src[sa.count] = at(wc, w * S);
+      sa.dst[sa.count++] = at(zs->shift, w * S);
+    }
+    PK_TRY(pm::zk_shift(ctx, sa, zs->w8, wlen, st));
+    const uint32_t* p = slots.begin();
+    for (size_t i = 0; i < slots.size();) {
+      size_t j = i + 1;
+      while (j < slots.size() && p[j] == p[j - 1] + 1) ++j;
+      PK_TRY(pm_fr_ntt_dev(ctx, at(zs->shift, p[i] * S), wlen, S, at(zs->coset2, 4 * n * p[i]), 4 * n, lg + 2,
+                           (uint32_t)(j - i), PM_NTT_COSET, st));
+      i = j;
+    }
+    return PM_OK;
+  };
   for (size_t i = 0; i < n_pi; ++i)
     if (pi_positions[i] >= n) return PM_ERR_LENGTH;
   Transcript ts = pk->base;
@@ -822,28 +999,36 @@ static int prove_body(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, const 
   // ---- round 1 --------------------------------------------------------------------------------
   pm::host_mark(ctx, "round 1");
   hipStream_t side = pk->side;
-  void* pi_coeffs = at(pk->coeffs, 5 * n);
+  void* pi_coeffs = at(wc, 5 * S);
   if (lag) {
     // nothing waits for the wire iNTT before the MSM: it runs on the side stream ahead of the coset transforms
     PK_TRY(scatter_public_inputs(ctx, pk, pi_positions, pi_values, n_pi));
     PK_TRY(pm_fr_ntt_dev(ctx, pk->pi_evals, n, n, pi_coeffs, n, lg, 1, PM_NTT_INVERSE, nullptr));
     PK_TRY(pm_stream_fork(ctx, side, pk->ev_main));
-    PK_TRY(pm_fr_ntt_dev(ctx, d_witness, n, n, pk->coeffs, n, lg, 4, PM_NTT_INVERSE, side));
-    PK_TRY(pm_fr_ntt_dev(ctx, pk->coeffs, n, n, pk->coset, 4 * n, lg + 2, 4, PM_NTT_COSET, side));
-    PK_TRY(pm_fr_ntt_dev(ctx, pi_coeffs, n, n, at(pk->coset, 4 * n * 5), 4 * n, lg + 2, 1, PM_NTT_COSET, side));
-    PK_TRY(commit_batch(ctx, lag, shard, d_witness, n, n, 4, &out->commitments[0]));
+    PK_TRY(pm_fr_ntt_dev(ctx, d_witness, n, n, wc, S, lg, 4, PM_NTT_INVERSE, side));
+    if (zs) {
+      PK_TRY(blind(0, 4, side));
+      PK_TRY(pm_stream_join(ctx, side, pk->ev_side));   // the blinder MSMs below read the blinded coefficients
+    }
+    PK_TRY(pm_fr_ntt_dev(ctx, wc, wlen, S, pk->coset, 4 * n, lg + 2, 4, PM_NTT_COSET, side));
+    PK_TRY(pm_fr_ntt_dev(ctx, pi_coeffs, wlen, S, at(pk->coset, 4 * n * 5), 4 * n, lg + 2, 1, PM_NTT_COSET, side));
+    if (zs) PK_TRY(second_coset({0, 1, 2, 3, 5}, side));
+    if (zs) PK_TRY(commit_lagrange_zk(ctx, lag, ck, d_witness, wc, n, S, &out->commitments[0]));
+    else PK_TRY(commit_batch(ctx, lag, shard, d_witness, n, n, 4, &out->commitments[0]));
   } else {
-    PK_TRY(pm_fr_ntt_dev(ctx, d_witness, n, n, pk->coeffs, n, lg, 4, PM_NTT_INVERSE, nullptr));
+    PK_TRY(pm_fr_ntt_dev(ctx, d_witness, n, n, wc, S, lg, 4, PM_NTT_INVERSE, nullptr));
+    if (zs) PK_TRY(blind(0, 4, nullptr));
     // work no challenge depends on goes to the side stream and runs under the MSMs of rounds 1 and 2:
     // the public-input polynomial and the wire polynomials on the 4n coset (round 3 reads them)
     {
       PK_TRY(scatter_public_inputs(ctx, pk, pi_positions, pi_values, n_pi));
       PK_TRY(pm_fr_ntt_dev(ctx, pk->pi_evals, n, n, pi_coeffs, n, lg, 1, PM_NTT_INVERSE, nullptr));
       PK_TRY(pm_stream_fork(ctx, side, pk->ev_main));
-      PK_TRY(pm_fr_ntt_dev(ctx, pk->coeffs, n, n, pk->coset, 4 * n, lg + 2, 4, PM_NTT_COSET, side));
-      PK_TRY(pm_fr_ntt_dev(ctx, pi_coeffs, n, n, at(pk->coset, 4 * n * 5), 4 * n, lg + 2, 1, PM_NTT_COSET, side));
+      PK_TRY(pm_fr_ntt_dev(ctx, wc, wlen, S, pk->coset, 4 * n, lg + 2, 4, PM_NTT_COSET, side));
+      PK_TRY(pm_fr_ntt_dev(ctx, pi_coeffs, wlen, S, at(pk->coset, 4 * n * 5), 4 * n, lg + 2, 1, PM_NTT_COSET, side));
+      if (zs) PK_TRY(second_coset({0, 1, 2, 3, 5}, side));
     }
-    PK_TRY(commit_batch(ctx, ck, shard, pk->coeffs, n, n, 4, &out->commitments[0]));
+    PK_TRY(commit_batch(ctx, ck, shard, wc, wlen, S, 4, &out->commitments[0]));
   }
   for (int j = 0; j < 4; ++j) ts.append_commitment(tl::WIRES[j], out->commitments[j]);
   // ---- round 2 --------------------------------------------------------------------------------
@@ -864,12 +1049,14 @@ static int prove_body(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, const 
   PK_TRY(pm_plonk_perm_terms_dev(ctx, &pa, n, pk->num, pk->den, nullptr));
   PK_TRY(pm::fr_batch_inverse_mul(ctx, pk->den, pk->num, n, nullptr));       // den <- num / den (r06: one kernel, was two)
   PK_TRY(pm_fr_prefix_product_dev(ctx, pk->den, n, pk->num, nullptr));       // num <- z on H
-  void* z_coeffs = at(pk->coeffs, 4 * n);
+  void* z_coeffs = at(wc, 4 * S);
   PK_TRY(pm_fr_ntt_dev(ctx, pk->num, n, n, z_coeffs, n, lg, 1, PM_NTT_INVERSE, nullptr));
+  if (zs) PK_TRY(blind(4, 1, nullptr));
   // z on the 4n coset depends on no further challenge: side stream, under the commitment to z
   PK_TRY(pm_stream_fork(ctx, side, pk->ev_main));
-  PK_TRY(pm_fr_ntt_dev(ctx, z_coeffs, n, n, at(pk->coset, 4 * n * 4), 4 * n, lg + 2, 1, PM_NTT_COSET, side));
-  PK_TRY(commit_batch(ctx, ck, shard, z_coeffs, n, n, 1, &out->commitments[4]));
+  PK_TRY(pm_fr_ntt_dev(ctx, z_coeffs, wlen, S, at(pk->coset, 4 * n * 4), 4 * n, lg + 2, 1, PM_NTT_COSET, side));
+  if (zs) PK_TRY(second_coset({4}, side));
+  PK_TRY(commit_batch(ctx, ck, shard, z_coeffs, wlen, S, 1, &out->commitments[4]));
   ts.append_commitment(tl::PERM, out->commitments[4]);
   // ---- round 3 --------------------------------------------------------------------------------
   pm::host_mark(ctx, "round 3");
@@ -909,9 +1096,36 @@ static int prove_body(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, const 
   put(qa.var_sep, var_sep);
   for (int j = 0; j < 3; ++j) put(qa.k[j], pk->k[j]);
   for (int j = 0; j < 4; ++j) put(qa.zh_inv[j], pk->zh_inv[j]);
-  PK_TRY(pm_plonk_quotient_dev(ctx, &qa, n, pk->t, nullptr));
-  PK_TRY(pm_fr_ntt_dev(ctx, pk->t, 4 * n, 4 * n, pk->t, 4 * n, lg + 2, 1, PM_NTT_INVERSE | PM_NTT_COSET, nullptr));
-  PK_TRY(commit_batch(ctx, ck, shard, pk->t, n, n, 4, &out->commitments[5]));
+  void* const t_coeffs = zs ? zs->t : pk->t;   // t_1..t_4 at stride S
+  if (!zs) {
+    PK_TRY(pm_plonk_quotient_dev(ctx, &qa, n, pk->t, nullptr));
+    PK_TRY(pm_fr_ntt_dev(ctx, pk->t, 4 * n, 4 * n, pk->t, 4 * n, lg + 2, 1, PM_NTT_INVERSE | PM_NTT_COSET, nullptr));
+    PK_TRY(commit_batch(ctx, ck, shard, pk->t, n, n, 4, &out->commitments[5]));
+  } else {
+    // deg t' <= 4n + 9: the same kernel on the second coset 7 w_8n H_4n gives t' mod (X^4n + s) beside t' mod (X^4n - s)
+    PK_TRY(pm_plonk_quotient_dev(ctx, &qa, n, zs->ab, nullptr));
+    pm_plonk_quotient_args q2 = qa;
+    for (int j = 0; j < 4; ++j) {
+      q2.wires[j] = at(zs->coset2, 4 * n * j);
+      q2.sigmas[j] = at(zs->sigma_coset2, 4 * n * j);
+    }
+    q2.z = at(zs->coset2, 4 * n * 4);
+    q2.pi = at(zs->coset2, 4 * n * 5);
+    const void** sel2[NSEL] = {&q2.q_m, &q2.q_l, &q2.q_r, &q2.q_o, &q2.q_c, &q2.q_4, &q2.q_arith, &q2.q_range, &q2.q_logic,
+                               &q2.q_fixed_group_add, &q2.q_variable_group_add};
+    for (int s_ = 0; s_ < NSEL; ++s_) *sel2[s_] = zs->sel_coset2[s_];
+    q2.l1 = zs->l1_coset2;
+    q2.x = zs->x2;
+    for (int j = 0; j < 4; ++j) put(q2.zh_inv[j], zs->zh_inv2[j]);
+    PK_TRY(pm_plonk_quotient_dev(ctx, &q2, n, at(zs->ab, 4 * n), nullptr));
+    PK_TRY(pm_fr_ntt_dev(ctx, zs->ab, 4 * n, 4 * n, zs->ab, 4 * n, lg + 2, 2, PM_NTT_INVERSE | PM_NTT_COSET, nullptr));
+    u64 inv2[4], inv2s[4], tb[3][4];
+    put(inv2, zs->inv2);
+    put(inv2s, zs->inv2s);
+    memcpy(tb, blinders[14], sizeof tb);
+    PK_TRY(pm::zk_combine(ctx, zs->ab, zs->w8, n, S, inv2, inv2s, tb, zs->t, ctx->stream));
+    PK_TRY(commit_batch(ctx, ck, shard, zs->t, n + pm::ZK_P1_LEN, S, 4, &out->commitments[5]));
+  }
   for (int i = 0; i < 4; ++i) ts.append_commitment(tl::QUOTIENT[i], out->commitments[5 + i]);
   // ---- round 4 --------------------------------------------------------------------------------
   pm::host_mark(ctx, "round 4");
@@ -928,13 +1142,13 @@ static int prove_body(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, const 
     const void* at_z[15];
     const void* at_x[NX];
     u64 out_z[15][4], out_x[NX][4], out_zw[4][4];
-    for (int j = 0; j < 4; ++j) at_z[j] = at(pk->coeffs, j * n);
+    for (int j = 0; j < 4; ++j) at_z[j] = at(wc, j * S);
     for (int j = 0; j < 3; ++j) at_z[4 + j] = at(pk->sigma_coeffs, j * n);
     at_z[7] = at(pk->sel_coeffs, Q_ARITH * n);
     at_z[8] = at(pk->sel_coeffs, Q_C * n);
     at_z[9] = at(pk->sel_coeffs, Q_L * n);
     at_z[10] = at(pk->sel_coeffs, Q_R * n);
-    for (int i = 0; i < 4; ++i) at_z[11 + i] = at(pk->t, i * n);
+    for (int i = 0; i < 4; ++i) at_z[11 + i] = at(t_coeffs, i * S);
     at_x[X_QM] = at(pk->sel_coeffs, Q_M * n);
     at_x[X_QO] = at(pk->sel_coeffs, Q_O * n);
     at_x[X_Q4] = at(pk->sel_coeffs, Q_4 * n);
@@ -948,12 +1162,35 @@ static int prove_body(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, const 
         xslot[w] = (int)nx;
         at_x[nx++] = at(pk->sel_coeffs, wsel[w] * n);
       }
-    const void* at_zw[4] = {at(pk->coeffs, 0), at(pk->coeffs, n), at(pk->coeffs, 3 * n), z_coeffs};
-    const uint32_t gk[3] = {15, nx, 4};
-    const void* const* gp[3] = {at_z, at_x, at_zw};
-    const uint64_t* gpt[3] = {zc.l, zc.l, zw.l};
-    uint64_t* gout[3] = {&out_z[0][0], &out_x[0][0], &out_zw[0][0]};
-    PK_TRY(pm::poly_evaluate_groups(ctx, 3, gk, gp, gpt, gout, n));
+    const void* at_zw[4] = {at(wc, 0), at(wc, S), at(wc, 3 * S), z_coeffs};
+    if (!zs) {
+      const uint32_t gk[3] = {15, nx, 4};
+      const void* const* gp[3] = {at_z, at_x, at_zw};
+      const uint64_t* gpt[3] = {zc.l, zc.l, zw.l};
+      uint64_t* gout[3] = {&out_z[0][0], &out_x[0][0], &out_zw[0][0]};
+      PK_TRY(pm::poly_evaluate_groups(ctx, 3, gk, gp, gpt, gout, n));
+    } else {
+      // the same openings, grouped by length: padded polynomials (S) at z, key polynomials (n) at z, padded at z w
+      enum { P_NUM = 9, K_NUM = 7 };
+      const void* pz[P_NUM] = {at_z[0], at_z[1], at_z[2], at_z[3], at_z[11], at_z[12], at_z[13], at_z[14], z_coeffs};
+      const void* kz[PM_LINCOMB_MAX];
+      for (int j = 0; j < K_NUM; ++j) kz[j] = at_z[4 + j];
+      for (uint32_t j = 0; j < nx; ++j)
+        if (j != X_Z) kz[K_NUM + j - (j > X_Z)] = at_x[j];
+      u64 opz[P_NUM][4], okz[PM_LINCOMB_MAX][4];
+      const uint32_t gk[3] = {P_NUM, K_NUM + nx - 1, 4};
+      const void* const* gp[3] = {pz, kz, at_zw};
+      const uint64_t* gpt[3] = {zc.l, zc.l, zw.l};
+      uint64_t* gout[3] = {&opz[0][0], &okz[0][0], &out_zw[0][0]};
+      const size_t gn[3] = {S, n, S};
+      PK_TRY(pm::poly_evaluate_groups_n(ctx, 3, gk, gp, gpt, gout, gn));
+      for (int j = 0; j < 4; ++j) memcpy(out_z[j], opz[j], 32);
+      for (int i = 0; i < 4; ++i) memcpy(out_z[11 + i], opz[4 + i], 32);
+      memcpy(out_x[X_Z], opz[8], 32);
+      for (int j = 0; j < K_NUM; ++j) memcpy(out_z[4 + j], okz[j], 32);
+      for (uint32_t j = 0; j < nx; ++j)
+        if (j != X_Z) memcpy(out_x[j], okz[K_NUM + j - (j > X_Z)], 32);
+    }
     pm::host_mark(ctx, "openings at z, z w");
     for (int j = 0; j < 4; ++j) ev[E_A + j] = get(out_z[j]);
     for (int j = 0; j < 3; ++j) ev[E_S1 + j] = get(out_z[4 + j]);
@@ -982,6 +1219,9 @@ static int prove_body(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, const 
                          fadd(fadd(c_, fmul(beta, s3)), gamma));
   const HFr alpha2 = fmul(alpha, alpha);
   RowEvals re{a_, b_, c_, d_, ev[E_AN], ev[E_BN], ev[E_DN], ev[E_QL], ev[E_QR], ev[E_QC]};
+  void* const r_coeffs = zs ? zs->r : pk->r;       // S coefficients
+  void* const agg = zs ? zs->agg : pk->agg;        // S
+  void* const wit = zs ? zs->wit : pk->wit;        // 2 x S
   {
     const void* lin_v[12];
     u64 lin_c[12][4];
@@ -1004,9 +1244,14 @@ static int prove_body(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, const 
     if (!pk->sel_zero[Q_LOGIC]) term(at(pk->sel_coeffs, Q_LOGIC * n), widget_logic(logic_sep, re), xv[X_LOGIC]);
     if (!pk->sel_zero[Q_FIXED]) term(at(pk->sel_coeffs, Q_FIXED * n), widget_fixed(fixed_sep, re), xv[X_FIXED]);
     if (!pk->sel_zero[Q_VAR]) term(at(pk->sel_coeffs, Q_VAR * n), widget_var(var_sep, re), xv[X_VAR]);
-    term(z_coeffs, fadd(fmul(alpha, ident), fmul(alpha2, l1_z)), xv[X_Z]);
+    const HFr c_z = fadd(fmul(alpha, ident), fmul(alpha2, l1_z));
+    term(z_coeffs, c_z, xv[X_Z]);
     term(at(pk->sigma_coeffs, 3 * n), fneg(fmul(fmul(fmul(alpha, copy3), beta), z_next)), xv[X_S4]);
-    PK_TRY(pm_fr_lincomb_dev(ctx, k, lin_v, &lin_c[0][0], n, pk->r, nullptr));   // r itself: round 5 divides it
+    PK_TRY(pm_fr_lincomb_dev(ctx, k, lin_v, &lin_c[0][0], n, r_coeffs, nullptr));   // r itself: round 5 divides it
+    if (zs) {   // beyond n only the blinded z has coefficients
+      const void* tail_v[1] = {at(z_coeffs, n)};
+      PK_TRY(pm_fr_lincomb_dev(ctx, 1, tail_v, c_z.l, S - n, at(r_coeffs, n), nullptr));
+    }
     ev[E_R] = r_z;
   }
   static_assert(NEV == 17, "tl::EVALS lists the evaluations in this enum's order");
@@ -1029,27 +1274,33 @@ static int prove_body(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, const 
       vp = fmul(vp, aw);
       ac[4 + e] = vp;
     }
-    for (int i = 0; i < 4; ++i) agg_v[i] = at(pk->t, i * n);
-    agg_v[4] = pk->r;
-    for (int j = 0; j < 4; ++j) agg_v[5 + j] = at(pk->coeffs, j * n);
+    for (int i = 0; i < 4; ++i) agg_v[i] = at(t_coeffs, i * S);
+    agg_v[4] = r_coeffs;
+    for (int j = 0; j < 4; ++j) agg_v[5 + j] = at(wc, j * S);
     for (int j = 0; j < 3; ++j) agg_v[9 + j] = at(pk->sigma_coeffs, j * n);
     for (int i = 0; i < 12; ++i) put(agg_c[i], ac[i]);
-    PK_TRY(pm_fr_lincomb_dev(ctx, 12, agg_v, &agg_c[0][0], n, pk->agg, nullptr));
-    PK_TRY(pm_fr_poly_ruffini_dev(ctx, pk->agg, n, zc.l, pk->wit, nullptr));
+    PK_TRY(pm_fr_lincomb_dev(ctx, 12, agg_v, &agg_c[0][0], n, agg, nullptr));
+    if (zs) {   // the padded tails: t pieces, r and the wires (the sigmas end at n)
+      const void* tail_v[9];
+      for (int i = 0; i < 9; ++i) tail_v[i] = at((void*)agg_v[i], n);
+      PK_TRY(pm_fr_lincomb_dev(ctx, 9, tail_v, &agg_c[0][0], S - n, at(agg, n), nullptr));
+    }
+    PK_TRY(pm_fr_poly_ruffini_dev(ctx, agg, S, zc.l, wit, nullptr));
   }
   const HFr aws = ts.challenge_scalar(tl::AGGREGATE);
   {
-    const void* sh_v[4] = {z_coeffs, at(pk->coeffs, 0), at(pk->coeffs, n), at(pk->coeffs, 3 * n)};
+    const void* sh_v[4] = {z_coeffs, at(wc, 0), at(wc, S), at(wc, 3 * S)};
     u64 sh_c[4][4];
     HFr vp = one;
     for (int e = 0; e < 4; ++e) {
       put(sh_c[e], vp);
       vp = fmul(vp, aws);
     }
-    PK_TRY(pm_fr_lincomb_dev(ctx, 4, sh_v, &sh_c[0][0], n, pk->agg, nullptr));
-    PK_TRY(pm_fr_poly_ruffini_dev(ctx, pk->agg, n, zw.l, at(pk->wit, n), nullptr));
+    PK_TRY(pm_fr_lincomb_dev(ctx, 4, sh_v, &sh_c[0][0], S, agg, nullptr));
+    PK_TRY(pm_fr_poly_ruffini_dev(ctx, agg, S, zw.l, at(wit, S), nullptr));
   }
-  PK_TRY(commit_batch(ctx, ck, shard, pk->wit, n - 1, n, 2, &out->commitments[9]));
+  // deg W_z = deg t_4 - 1: n + 9 coefficients in zero-knowledge mode
+  PK_TRY(commit_batch(ctx, ck, shard, wit, zs ? n + pm::ZK_P1_LEN - 1 : n - 1, S, 2, &out->commitments[9]));
   ts.append_commitment(tl::W_Z, out->commitments[9]);
   ts.append_commitment(tl::W_ZW, out->commitments[10]);
   const HFr chal[10] = {beta, gamma, alpha, range_sep, logic_sep, fixed_sep, var_sep, zc, aw, aws};

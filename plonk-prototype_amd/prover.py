@@ -21,6 +21,7 @@ verifier's side of the transcript (``derive_challenges``) for the end-to-end che
 from __future__ import annotations
 
 import ctypes as C
+import secrets
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -163,6 +164,16 @@ class ProverKey:
         ctx._check(ctx._lib.pm_plonk_key_set_lagrange(ctx._h, self._h, ck._bases._h if ck is not None else None,
                                                       lck._bases._h if lck is not None else None))
         self._lagrange = lck
+
+    def enable_zk(self) -> int:
+        """Make the key ready for zero-knowledge proofs (``prove(..., zero_knowledge=True)``): the selector, sigma and L_1
+        polynomials on a second 4n coset and a padded per-proof workspace (``pm_plonk_key_enable_zk``; the key must be
+        committed).  Idempotent.  -> the device bytes the zero-knowledge state holds (the same on every call)."""
+        if self.verifier_key is None:
+            raise ValueError("commit the key first")
+        out = C.c_size_t()
+        self.ctx._check(self.ctx._lib.pm_plonk_key_enable_zk(self.ctx._h, self._h, C.byref(out)))
+        return int(out.value)
 
     def batch(self, max_batch: int) -> "BatchWorkspace":
         """A workspace for ``prove_batch`` of up to ``max_batch`` (<= 64) proofs on this key: about 42 n x 32 bytes of
@@ -346,7 +357,13 @@ def sparse_public_inputs(public_inputs) -> tuple[np.ndarray, np.ndarray]:
     return pos, np.ascontiguousarray(pi[pos.astype(np.int64)])
 
 
-def prove(pk: ProverKey, ck: CommitKey, witness, public_inputs=None, bind_public_inputs: bool = True) -> Proof:
+def random_blinders() -> np.ndarray:
+    """PM_PLONK_ZK_BLINDERS fresh uniform scalars below r (``secrets.randbelow``), [17, 4] Montgomery limbs."""
+    return np.stack([fr_to_limbs(secrets.randbelow(R_MOD)) for _ in range(_lib.PLONK_ZK_BLINDERS)])
+
+
+def prove(pk: ProverKey, ck: CommitKey, witness, public_inputs=None, bind_public_inputs: bool = True,
+          zero_knowledge: bool = False, blinders=None) -> Proof:
     """``Prover::prove_with_preprocessed``: one ``pm_plonk_prove`` call.
 
     witness: [4, n, 4] wire values (a, b, c, d rows) in Montgomery limbs, or a DeviceVector of 4n elements
@@ -356,10 +373,24 @@ def prove(pk: ProverKey, ck: CommitKey, witness, public_inputs=None, bind_public
 
     Multi-GPU: every rank calls prove() with the same inputs and a ``dist.ShardedCommitKey``; the polynomial
     work is replicated, each MSM is split by coefficient range, and the ranks exchange 144-byte partial points.
-    All ranks return the same proof."""
+    All ranks return the same proof.
+
+    zero_knowledge: one ``pm_plonk_prove_zk`` call instead (single GPU; ``pk.enable_zk()`` first): the same proof format,
+    transcript and verifier, with the wires, z and the quotient pieces blinded so that the proof hides the witness
+    (DESIGN.md section 7.2b).  The commit key needs n + 10 points.  blinders: [17, 4] Montgomery limbs, each below r;
+    None draws fresh ones with ``secrets.randbelow(r)`` -- pass fixed blinders in tests only: reusing blinders across
+    proofs of different witnesses gives the witness away."""
     ctx, n = pk.ctx, pk.n
     if ck.max_degree() + 1 < n:
         raise ValueError("commit key shorter than the circuit")
+    if blinders is not None and not zero_knowledge:
+        raise ValueError("blinders are only used with zero_knowledge=True")
+    if zero_knowledge:
+        if hasattr(ck, "lo"):
+            raise ValueError("zero-knowledge proofs are single-GPU")
+        bl = random_blinders() if blinders is None else np.ascontiguousarray(blinders, dtype=np.uint64).reshape(-1, 4)
+        if bl.shape[0] != _lib.PLONK_ZK_BLINDERS:
+            raise ValueError(f"need {_lib.PLONK_ZK_BLINDERS} blinders")
     if pk.verifier_key is None:
         pk.commit(ck)
     if isinstance(witness, DeviceVector):
@@ -385,6 +416,9 @@ def prove(pk: ProverKey, ck: CommitKey, witness, public_inputs=None, bind_public
             cb = None if ck.native else _exchange_callback(ck)      # None: the library's RCCL communicator
             ctx._check(ctx._lib.pm_plonk_prove_sharded(ctx._h, pk._h, ck._bases._h, ck.lo, d_wit._p, p_pos, p_val, pos.size,
                                                        flags, C.cast(cb, C.c_void_p) if cb else None, None, C.byref(raw)))
+        elif zero_knowledge:
+            ctx._check(ctx._lib.pm_plonk_prove_zk(ctx._h, pk._h, ck._bases._h, d_wit._p, p_pos, p_val, pos.size, flags,
+                                                  bl.ctypes.data_as(_lib.u64p), C.byref(raw)))
         else:
             ctx._check(ctx._lib.pm_plonk_prove(ctx._h, pk._h, ck._bases._h, d_wit._p, p_pos, p_val, pos.size, flags,
                                                C.byref(raw)))
