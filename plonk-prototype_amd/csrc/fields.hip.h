@@ -312,6 +312,61 @@ PM_DEV Fe<P> fe_mul(const Fe<P>& a, const Fe<P>& b) {
   fe_mont_cols<P, 1>([&](int k, u64* acc, u32& tok) { fe_col_mul<P>(k, acc[0], a, b, tok); }, out);
   return t;
 }
+// Data x split constant: a product whose second factor is known in advance, with a reduction of D digits instead
+// of N.  The data limbs are cut into groups of G (group j = limbs jG .. jG+G-1, the last one shorter) and the constant
+// w is stored as one row per group,
+//     row_j = w * 2^(W (jG + D - N)) mod m      (canonical limbs, < 2^W; w in Montgomery form),
+// so that  T = sum_j x[group j] * row_j  ==  x * w * 2^(W D) / R  (mod m), with x[group j] = sum_a x_(jG+a) 2^(W a)
+// only G limbs long.  T is still N^2 limb products in the same 64-bit columns (limb jG+a times limb b of row_j goes
+// to column a + b), but T < ceil(N/G) Bx 2^(W G) (1 + 2^(1-W)) m instead of Bx 2^(W N) m, so D = G + 1 Montgomery
+// digits bring it to (T + q m) / 2^(W D) == x w / R, the residue fe_mul returns.  N^2 + (N-1) D limb products instead of
+// 2 N^2 - N: Fr with G = 5 (two rows) 129 instead of 153, with G = 1 (N rows) 97.  wl(j, b) is limb b of row_j.
+//
+// Bounds, x limbs < Bx 2^W (normalised or not), rows canonical.  A column holds at most N data products (one per
+// data limb), at most D terms q_i m_l < 2^(2W), the carry of the column before (< 2^(64-W)) and the 2^W - 1 of the
+// digit step:  N Bx 2^(2W) + D 2^(2W) + 2^(64-W) + 2^W < 2^64  for  N Bx + D < 2^(64-2W) - 1, i.e. Bx < 6 for Fr
+// (9 * 6 + 6 = 60 < 63), the bound of fe_mul.  Result: limbs < 2^W, top limb the rest; value < T / 2^(W D) + m
+// < (1 + 2 N Bx 2^-W) m < (1 + 2^-22) m: the class (limbs normalised, value < 2m) of fe_mul.  Needs m = 1 mod 2^W (Fr): the
+// digit is q = -acc and adding 2^W - 1 stands in for q * m_0, exactly as in fe_mont_cols.  One PM_KEEP chain.
+template <class P, int G, int D, class WL>
+PM_DEV Fe<P> fe_mul_split(const Fe<P>& x, WL&& wl) {
+  constexpr int N = P::N, W = P::W;
+  constexpr u32 MASK = Consts<P>::MASK;
+  constexpr Limbs<N> M = Consts<P>::mod_limbs();
+  static_assert(M.v[0] == 1u, "fe_mul_split: the modulus must be 1 mod 2^W");
+  static_assert(G >= 1 && G <= N && D == G + 1 && D <= N, "fe_mul_split: one digit more than the longest group");
+  Fe<P> r;
+  u32 q[D];
+  u64 acc = 0;
+  u32 tok;
+  PM_KEEP_INIT(tok);
+#pragma unroll
+  for (int k = 0; k < D + N - 1; ++k) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      const int b = k - i % G;
+      if (b < 0 || b >= N) continue;
+      fe_mac(acc, x.l[i], wl(i / G, b), tok);
+    }
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+      const int l = k - i;
+      if (l < 1 || l >= N) continue;
+      fe_mac(acc, q[i], M.v[l], tok);
+    }
+    if (k < D) {
+      q[k] = (0u - (u32)acc) & MASK;
+      acc += (u64)MASK;
+    } else {
+      r.l[k - D] = (u32)acc & MASK;
+    }
+    acc >>= W;
+  }
+  r.l[N - 1] = (u32)acc;
+  asm("" : "+v"(r.l[N - 1]) : "v"(tok));  // the token chain ends in a live value
+  return r;
+}
+
 // a * b0 / R for a one-limb b0 (< 2^W): the reduction half of fe_mul only (N + N(N-1) limb products instead of
 // 2 N^2 - N).  Same bounds and result class as fe_mul.  Used for Montgomery -> integer: x 2^256 * 2^5 / 2^261.
 template <class P>

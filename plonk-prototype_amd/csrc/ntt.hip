@@ -162,9 +162,12 @@ static int get_step4_table(pm_ctx* ctx, int dir, unsigned S, void** out, hipStre
   }
   HFr wR = domain_gen(S);
   if (dir) wR = host::inv(wR, host::FR());
+  HFr w4 = domain_gen(2);   // the table starts with the split rows of this direction's w4
+  if (dir) w4 = host::inv(w4, host::FR());
   NttConsts c;
   memset(&c, 0, sizeof c);
   to_limbs(c.w8[0], wR);
+  to_limbs(c.w8[1], w4);
   to_limbs(c.one, host::one(host::FR()));
   void* d = nullptr;
   int rc = build_step4_table(ctx, &d, c, S, st);

@@ -39,8 +39,9 @@ unsigned pass4_threads(int S, int LT) { return std::max(64u, (1u << (S + LT)) / 
 
 int build_step4_table(pm_ctx* ctx, void** out, const NttConsts& c, unsigned S, hipStream_t st) {
   const u32 total = (u32)step4_tw_total((int)S);
-  PM_HIP(ctx, hipMalloc(out, (size_t)total * 48));
-  hipLaunchKernelGGL(step4_tw_kernel, dim3((total + 255) / 256), dim3(256), 0, st, (u32x4*)*out, c, S);
+  // the w4 rows in front, then 80 B per entry; at least one block, so that the head is written for every S
+  PM_HIP(ctx, hipMalloc(out, ((size_t)STEP4_HEAD + (size_t)total * STEP4_ENTRY) * sizeof(u32x4)));
+  hipLaunchKernelGGL(step4_tw_kernel, dim3((std::max(total, 9u) + 255) / 256), dim3(256), 0, st, (u32x4*)*out, c, S);
   PM_HIP(ctx, hipGetLastError());
   return PM_OK;
 }

@@ -38,7 +38,7 @@ struct NttConsts {
 struct NttPassArgs {
   const void* in;         // canonical: N x 32 B.   wide: planes (see wide_ptrs)
   void* out;
-  const u32x4* step_tw;   // in-tile step twiddles for this S, 48 B per entry
+  const u32x4* step_tw;   // in-tile step twiddles for this S: 48 B per entry (radix 8); w4 rows + 80 B entries (radix 4)
   const u32x4* tw_hi;     // w_N^(x << lh)        x < N >> lh        (48 B entries)
   const u32x4* tw_lo;     // w_N^x                x < 1 << lh
   const u32x4* cs_hi;     // coset powers g^(x << lh) (fwd) or g^-(x << lh) (inv)

@@ -2,6 +2,12 @@
 // thread keeps FOUR elements (36 VGPRs of data instead of 72) and a wave owns 9 KiB of the LDS
 // tile instead of 18, so four waves per SIMD fit where the radix-8 kernel is limited to two by
 // LDS.  Same passes, same tables for the inter-pass twiddles, its own step-twiddle tables.
+//
+// Every in-tile product has a table constant as its second factor, and the table stores it split for
+// fe_mul_split (fields.hip.h): a step twiddle as two rows (data limbs 0-4 and 5-8, six reduction digits, 129 limb
+// products instead of 153), w4 as nine rows (one per data limb, two digits, 97).  The results are of fe_mul's class,
+// so the bounds written at BFLY / dft4 hold unchanged.  Only the inter-pass twiddles (36 B per element from HBM)
+// keep the plain form.
 #pragma once
 #include "ntt_kernels.hip.h"
 
@@ -19,9 +25,52 @@ __host__ __device__ constexpr size_t pass4_lds_bytes(int S, int LT) {
   return num_steps4(S) > 1 ? ((size_t)36 << (S + LT)) : 0;
 }
 
+// ---- step table of the radix-4 kernels: [w4 rows | entries] ------------------------------------------------
+// Head, 84 words: w4 for fe_mul_split<1, 2>, transposed: word 9 b + j = limb b of row_j = w4 2^(29 (j - 7)) mod r, so
+// the nine constants of column b are neighbours.  It is read through the constant address space: wave-uniform
+// addresses there are scalar loads, the limb is the scalar operand of its v_mad_u64_u32 and no VGPR holds it.
+// Entries, 80 B each: limbs of row_0 = w 2^-87, then of row_1 = w 2^58 (fe_mul_split<5, 6>), two words of padding.
+constexpr int STEP4_HEAD = 21;   // u32x4 units in front of entry 0
+constexpr int STEP4_ENTRY = 5;   // u32x4 units per entry
+typedef const __attribute__((address_space(4))) u32* W4Rows;
+PM_DEV W4Rows w4_rows(const u32x4* step_tw) {
+  return (W4Rows)(reinterpret_cast<const u32*>(step_tw));
+}
+struct FrSplit2 {
+  u32 l[18];
+};
+PM_DEV FrSplit2 ld_tw2(const u32x4* ent, size_t idx) {
+  const u32x4* p = ent + STEP4_ENTRY * idx;
+  u32x4 a = p[0], b = p[1], c = p[2], d = p[3];
+  const uint2 e = reinterpret_cast<const uint2*>(p + 4)[0];
+  FrSplit2 r;
+  r.l[0] = a.x; r.l[1] = a.y; r.l[2] = a.z; r.l[3] = a.w;
+  r.l[4] = b.x; r.l[5] = b.y; r.l[6] = b.z; r.l[7] = b.w;
+  r.l[8] = c.x; r.l[9] = c.y; r.l[10] = c.z; r.l[11] = c.w;
+  r.l[12] = d.x; r.l[13] = d.y; r.l[14] = d.z; r.l[15] = d.w;
+  r.l[16] = e.x; r.l[17] = e.y;
+  return r;
+}
+// x * w for a table twiddle: x (B < 6, any V the limbs allow) -> (1, <2)
+PM_DEV Fr mul_tw2(const Fr& x, const FrSplit2& w) {
+  return fe_mul_split<FrP, 5, 6>(x, [&](int j, int b) { return w.l[9 * j + b]; });
+}
+// 4-point DIF as dft4 (ntt_kernels.hip.h), the product by w4 through its split rows: a3 enters it at (4, 5)
+PM_DEV void dft4s(Fr& a0, Fr& a1, Fr& a2, Fr& a3, W4Rows w4) {
+  BFLY(3, a0, a2);  // a0 (2+, <26)  a2 (4+, <27)
+  BFLY(3, a1, a3);  // a1 (2, 4)     a3 (4, 5)
+  a3 = fe_mul_split<FrP, 1, 2>(a3, [&](int j, int b) { return w4[9 * b + j]; });
+  a2 = fe_norm<FrP>(a2);
+  BFLY(5, a0, a1);  // a0 = X0, a1 = X2
+  BFLY(3, a2, a3);  // a2 = X1, a3 = X3
+  Fr t = a1;
+  a1 = a2;
+  a2 = t;
+}
+
 template <int S, int LT, int STEP, bool OUT_UFAST, bool OUT_WIDE>
 PM_DEV void ntt_step4(Fr (&x)[4], const NttPassArgs& a, const NttConsts& kc, u32x4* lds0, u32x4* lds1, u32* lds2,
-                      const Fr& w4, u32 tid, size_t j0) {
+                      W4Rows w4, u32 tid, size_t j0) {
   constexpr int R = 1 << S;
   constexpr int T = 1 << LT;
   constexpr int U = R / 4;
@@ -42,16 +91,20 @@ PM_DEV void ntt_step4(Fr (&x)[4], const NttPassArgs& a, const NttConsts& kc, u32
       x[m].l[8] = lds2[e];
     }
   }
-  const u32x4* stw = a.step_tw + 3 * step4_tw_offset(S, STEP);
+  const u32x4* stw = a.step_tw + STEP4_HEAD + STEP4_ENTRY * step4_tw_offset(S, STEP);
   if constexpr (LQ == 2) {
     const u32 kp = u & (nsp - 1);
     if (STEP > 0) {
       x[0] = fe_reduce_weak<FrP>(x[0]);
-      x[1] = fe_mul<FrP>(x[1], ld_tw(stw, 0 * nsp + kp));
-      x[2] = fe_mul<FrP>(x[2], ld_tw(stw, 1 * nsp + kp));
-      x[3] = fe_mul<FrP>(x[3], ld_tw(stw, 2 * nsp + kp));
+      x[1] = mul_tw2(x[1], ld_tw2(stw, 0 * nsp + kp));
+      x[2] = mul_tw2(x[2], ld_tw2(stw, 1 * nsp + kp));
+      x[3] = mul_tw2(x[3], ld_tw2(stw, 2 * nsp + kp));
     }
-    dft4(x[0], x[1], x[2], x[3], w4);  // X[t] in x[t]
+    // every step reads the w4 rows anew (scalar loads, a column at a time): an opaque copy of the pointer, or the
+    // rows of step 0 stay in 81 SGPRs for the whole kernel and spill
+    W4Rows w4s = w4;
+    asm volatile("" : "+s"(w4s));
+    dft4s(x[0], x[1], x[2], x[3], w4s);  // X[t] in x[t]
     if constexpr (!last) {
       __syncthreads();
       const u32 base = (u - kp) * 4 + kp;
@@ -68,8 +121,8 @@ PM_DEV void ntt_step4(Fr (&x)[4], const NttPassArgs& a, const NttConsts& kc, u32
   } else {  // radix 2, always the last step: Ns' = R/2, k' = v = u + i U, pairs (x[i], x[i+2])
     x[0] = fe_norm<FrP>(x[0]);
     x[1] = fe_norm<FrP>(x[1]);
-    x[2] = fe_mul<FrP>(x[2], ld_tw(stw, u));
-    x[3] = fe_mul<FrP>(x[3], ld_tw(stw, u + U));
+    x[2] = mul_tw2(x[2], ld_tw2(stw, u));
+    x[3] = mul_tw2(x[3], ld_tw2(stw, u + U));
     BFLY(3, x[0], x[2]);
     BFLY(3, x[1], x[3]);
   }
@@ -118,7 +171,7 @@ __global__ void __launch_bounds__((1 << (S + LT)) / 4 < 64 ? 64 : (1 << (S + LT)
   const size_t n = (size_t)1 << log_n;
   const size_t n_cols = (size_t)1 << (log_n - S);
   const size_t j0 = (size_t)xcd_tile(blockIdx.x, gridDim.x, a.flags) * T;
-  const Fr w4 = fr_limbs(kc.w8[1]);
+  const W4Rows w4 = w4_rows(a.step_tw);
 
   Fr x[4];
   {
@@ -169,9 +222,20 @@ __global__ void __launch_bounds__((1 << (S + LT)) / 4 < 64 ? 64 : (1 << (S + LT)
   if constexpr (NSTEPS > 5) ntt_step4<S, LT, 5, OUT_UFAST, OUT_WIDE>(x, a, kc, lds0, lds1, lds2, w4, tid, j0);
 }
 
-// step twiddles of the radix-4 kernel: block s, entry [(t-1)*Ns' + k'] = wR^(k' t R/(Ns' q)), Ns' = 4^s
+// step twiddles of the radix-4 kernel: block s, entry [(t-1)*Ns' + k'] = wR^(k' t R/(Ns' q)), Ns' = 4^s, both rows
+// of each (canonical limbs); the first nine threads also write the rows of w4 = c.w8[1] into the head.
+// Multiplying by 2^e in Montgomery form (fe_pow2<261 + e>) is the shift by e: 261 - 87 = 174, 261 + 58 = 319.
 static __global__ void step4_tw_kernel(u32x4* out, const NttConsts c, u32 S) {
   const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < 9) {  // row_i = w4 2^(29 (i - 7)): 2^(29 (i + 2)) in Montgomery form, walked up from 2^58
+    Fr p = fe_pow2<FrP, 58>();
+    for (u32 k = 0; k < i; ++k) p = fe_mul<FrP>(p, fe_pow2<FrP, 261 + 29>());
+    const Fr row = fr_canon(fe_mul<FrP>(fr_limbs(c.w8[1]), p));
+    u32* head = reinterpret_cast<u32*>(out);
+    for (u32 b = 0; b < 9; ++b) head[9 * b + i] = row.l[b];
+    if (i < 3) head[81 + i] = 0u;
+  }
+  u32x4* ent = out + STEP4_HEAD;
   u32 off = 0;
   for (u32 s = 0; 2 * s < S; ++s) {
     const u32 lq = (S - 2 * s) >= 2 ? 2 : 1;
@@ -180,7 +244,15 @@ static __global__ void step4_tw_kernel(u32x4* out, const NttConsts c, u32 S) {
     if (i >= off && i < off + cnt) {
       const u32 t = (i - off) / nsp + 1, kp = (i - off) % nsp;
       const u32 e = (kp * t) << (S - 2 * s - lq);
-      st_tw(out, i, fr_canon(fr_pow(fr_limbs(c.w8[0]), e, fr_limbs(c.one))));
+      const Fr w = fr_pow(fr_limbs(c.w8[0]), e, fr_limbs(c.one));
+      const Fr r0 = fr_canon(fe_mul<FrP>(w, fe_pow2<FrP, 174>()));
+      const Fr r1 = fr_canon(fe_mul<FrP>(w, fe_pow2<FrP, 319>()));
+      u32x4* p = ent + STEP4_ENTRY * (size_t)i;
+      p[0] = u32x4{r0.l[0], r0.l[1], r0.l[2], r0.l[3]};
+      p[1] = u32x4{r0.l[4], r0.l[5], r0.l[6], r0.l[7]};
+      p[2] = u32x4{r0.l[8], r1.l[0], r1.l[1], r1.l[2]};
+      p[3] = u32x4{r1.l[3], r1.l[4], r1.l[5], r1.l[6]};
+      p[4] = u32x4{r1.l[7], r1.l[8], 0u, 0u};
       return;
     }
     off += cnt;
