@@ -447,6 +447,26 @@ size_t pm_plonk_batch_bytes(const pm_plonk_batch* ws);   /* device bytes the wor
 int pm_plonk_prove_batch(pm_ctx* ctx, pm_prover_key* key, pm_plonk_batch* ws, const pm_bases* commit_key, uint32_t batch,
                          const void* d_witnesses, const uint64_t* const* pi_positions, const uint64_t* const* pi_values,
                          const size_t* n_pi, uint32_t flags, pm_plonk_proof* out);
+/* ---- Zero-knowledge proofs in a batch ------------------------------------------------------
+ * pm_plonk_batch_enable_zk adds the padded-stride, per-proof regions of zero-knowledge batches for max_batch proofs to a
+ * workspace, in one further device allocation (about 51 n x 32 bytes per proof).  The key must have had
+ * pm_plonk_key_enable_zk: it owns the second-coset forms all proofs share.  Idempotent; added_bytes (may be NULL) receives
+ * the bytes added, the same figure on every call, which pm_plonk_batch_zk_bytes reports too (0 before the call;
+ * pm_plonk_batch_bytes keeps counting the plain regions only).  PM_ERR_OOM when it does not fit: the workspace stays
+ * usable for plain batches.  An enabled workspace serves pm_plonk_prove_batch with unchanged proofs.
+ * pm_plonk_prove_batch_zk takes the arguments of pm_plonk_prove_batch and batch x PM_PLONK_ZK_BLINDERS blinders
+ * (blinders[b][i]: Montgomery limbs, below r).  out[b] is byte-identical, challenges included, to pm_plonk_prove_zk of
+ * witness b with public inputs b and blinders[b], also with a Lagrange key attached to the key.  Every proof needs its own
+ * fresh uniform blinders: one set shared by a batch, or reused across calls, gives the witnesses away.  Errors: those of
+ * pm_plonk_prove_batch; NULL blinders, a blinder not below r, a workspace without pm_plonk_batch_enable_zk:
+ * PM_ERR_BAD_ARG; a commit key with fewer than n + PM_PLONK_ZK_EXTRA_BASES bases: PM_ERR_LENGTH; a workspace in use:
+ * PM_ERR_BUSY.  Single GPU only. */
+int pm_plonk_batch_enable_zk(pm_ctx* ctx, pm_plonk_batch* ws, size_t* added_bytes);
+size_t pm_plonk_batch_zk_bytes(const pm_plonk_batch* ws);
+int pm_plonk_prove_batch_zk(pm_ctx* ctx, pm_prover_key* key, pm_plonk_batch* ws, const pm_bases* commit_key, uint32_t batch,
+                            const void* d_witnesses, const uint64_t* const* pi_positions, const uint64_t* const* pi_values,
+                            const size_t* n_pi, uint32_t flags, const uint64_t (*blinders)[PM_PLONK_ZK_BLINDERS][4],
+                            pm_plonk_proof* out);
 /* Proof::to_bytes: 11 x 48-byte compressed G1, then the 16 scalars of ProofEvaluations::to_bytes. */
 int pm_plonk_proof_to_bytes(const pm_plonk_proof* proof, uint8_t out[PM_PLONK_PROOF_BYTES]);
 /* ---- The prover with coefficient-range ownership end to end (SURVEY.md section 8e row 3 + 8f N5; configs[4]) ----------

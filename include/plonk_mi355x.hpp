@@ -323,6 +323,13 @@ class BatchWorkspace {
   BatchWorkspace(BatchWorkspace&& o) noexcept : ctx_(o.ctx_), ws_(o.ws_), max_batch_(o.max_batch_) { o.ws_ = nullptr; }
   uint32_t max_batch() const { return max_batch_; }
   size_t device_bytes() const { return pm_plonk_batch_bytes(ws_); }
+  // Zero-knowledge batches (pm_plonk_batch_enable_zk; after ProverKey::enable_zk): adds the padded per-proof regions in one
+  // allocation (idempotent) and returns the device bytes added.  Plain batches on the workspace are unchanged.
+  size_t enable_zk() {
+    size_t added = 0;
+    ctx_->check(pm_plonk_batch_enable_zk(ctx_->get(), ws_, &added));
+    return added;
+  }
   pm_plonk_batch* get() const { return ws_; }
 
  private:
@@ -432,6 +439,41 @@ class ProverKey {
     std::vector<pm_plonk_proof> raw(B);
     ctx_->check(pm_plonk_prove_batch(ctx_->get(), key_, ws.get(), ck.bases(), B, witnesses.data(), pp.data(), vp.data(),
                                      cnt.data(), bind_public_inputs ? 0u : PM_PLONK_UPSTREAM_TRANSCRIPT, raw.data()));
+    std::vector<Proof> out;
+    for (const pm_plonk_proof& r : raw) out.push_back(from_raw(r));
+    return out;
+  }
+  // B zero-knowledge proofs in one call (pm_plonk_prove_batch_zk; enable_zk() on the key and on ws first): blinders[b] are
+  // proof b's PM_PLONK_ZK_BLINDERS fresh uniform scalars below r -- one independent set per proof, never one for the batch.
+  // Proof b is byte-identical to prove_zk(ck, witness b, blinders[b], public_inputs[b]).
+  std::vector<Proof> prove_batch_zk(const CommitKey& ck, BatchWorkspace& ws, const DevicePolynomial& witnesses,
+                                    const std::vector<std::array<Fr, PM_PLONK_ZK_BLINDERS>>& blinders,
+                                    const std::vector<std::vector<PublicInput>>& public_inputs = {},
+                                    bool bind_public_inputs = true) const {
+    if (witnesses.len() == 0 || witnesses.len() % (4 * n_)) throw Error(PM_ERR_LENGTH, "the witnesses must hold B x 4n wire values");
+    const uint32_t B = (uint32_t)(witnesses.len() / (4 * n_));
+    if (blinders.size() != B) throw Error(PM_ERR_LENGTH, "one set of blinders per proof");
+    if (!public_inputs.empty() && public_inputs.size() != B) throw Error(PM_ERR_LENGTH, "one public-input list per proof");
+    std::vector<std::vector<uint64_t>> pos(B), val(B);
+    std::vector<const uint64_t*> pp(B, nullptr), vp(B, nullptr);
+    std::vector<size_t> cnt(B, 0);
+    for (uint32_t b = 0; b < B && !public_inputs.empty(); ++b) {
+      for (const PublicInput& pi : public_inputs[b]) {
+        pos[b].push_back(pi.position);
+        val[b].insert(val[b].end(), pi.value.begin(), pi.value.end());
+      }
+      cnt[b] = pos[b].size();
+      pp[b] = pos[b].data();
+      vp[b] = val[b].data();
+    }
+    std::vector<uint64_t> bl(4 * (size_t)PM_PLONK_ZK_BLINDERS * B);
+    for (uint32_t b = 0; b < B; ++b)
+      for (int i = 0; i < PM_PLONK_ZK_BLINDERS; ++i)
+        std::copy(blinders[b][i].begin(), blinders[b][i].end(), &bl[4 * ((size_t)PM_PLONK_ZK_BLINDERS * b + i)]);
+    std::vector<pm_plonk_proof> raw(B);
+    ctx_->check(pm_plonk_prove_batch_zk(ctx_->get(), key_, ws.get(), ck.bases(), B, witnesses.data(), pp.data(), vp.data(),
+                                        cnt.data(), bind_public_inputs ? 0u : PM_PLONK_UPSTREAM_TRANSCRIPT,
+                                        reinterpret_cast<const uint64_t(*)[PM_PLONK_ZK_BLINDERS][4]>(bl.data()), raw.data()));
     std::vector<Proof> out;
     for (const pm_plonk_proof& r : raw) out.push_back(from_raw(r));
     return out;

@@ -145,6 +145,11 @@ SIGNATURES = {
     "pm_plonk_prove_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
                                        C.POINTER(u64p), C.POINTER(u64p), C.POINTER(C.c_size_t), C.c_uint32,
                                        C.POINTER(PlonkProof)]),
+    "pm_plonk_batch_enable_zk": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]),
+    "pm_plonk_batch_zk_bytes": (C.c_size_t, [C.c_void_p]),
+    "pm_plonk_prove_batch_zk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                          C.POINTER(u64p), C.POINTER(u64p), C.POINTER(C.c_size_t), C.c_uint32, u64p,
+                                          C.POINTER(PlonkProof)]),
     "pm_fr_poly_evaluate_many_dev": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.c_size_t, u64p, u64p,
                                                C.c_void_p]),
     "pm_comm_unique_id": (C.c_int, [C.POINTER(C.c_uint8)]),

@@ -206,12 +206,14 @@ int lincomb_batch(pm_ctx* ctx, ConstStage& stage, uint32_t k, const void* const*
 size_t prefix_product_batch_ctl_bytes(uint32_t batch, size_t n);
 int prefix_product_batch(pm_ctx* ctx, const void* d_in, size_t n, uint32_t batch, void* d_out, void* d_ctl, hipStream_t st);
 // polynomial evaluation: slot j of proof b is polys[j] + b strides[j] at point points[b][point_of[j]] (point_of[j] < 2);
-// k <= PM_EVAL_BATCH_SLOTS.  One host synchronisation; out: [batch][k][4] host
+// k <= PM_EVAL_BATCH_SLOTS.  One host synchronisation; out: [batch][k][4] host.  lens (may be null: n everywhere): the
+// coefficients slot j has, at most n -- the zero-knowledge batch opens padded vectors (n = the padded stride) beside key
+// polynomials that end at the circuit size
 constexpr uint32_t PM_EVAL_BATCH_SLOTS = 32;
 size_t evaluate_batch_ws_bytes(uint32_t k, uint32_t batch, size_t n);   // every k' <= k, batch' <= batch
 int evaluate_batch(pm_ctx* ctx, ConstStage& stage, uint32_t k, const void* const* polys, const size_t* strides,
                    const uint8_t* point_of, const uint64_t* points /* [batch][2][4] */, uint32_t batch, size_t n, void* d_ws,
-                   uint64_t* out, hipStream_t st);
+                   uint64_t* out, hipStream_t st, const size_t* lens = nullptr);
 // Ruffini division of `count` vectors of n coefficients (d_in + v stride, d_out + v stride) by X - z_v; falls back to
 // pm_fr_poly_ruffini_dev per vector when a z is zero or a vector has more than 2^20 coefficients
 size_t ruffini_batch_ws_bytes(uint32_t count, size_t n);
@@ -244,6 +246,27 @@ int zk_shift(pm_ctx* ctx, const ZkShiftArgs& a, const void* d_w8, size_t len, hi
 // the two coset quotients (d_ab: A then B(X / w_8n), 4n coefficients each) -> t_1..t_4 with their blinders, stride S
 int zk_combine(pm_ctx* ctx, const void* d_ab, const void* d_w8, size_t n, size_t stride, const uint64_t inv2[4],
                const uint64_t inv2s[4], const uint64_t beta[3][4], void* d_t, hipStream_t st);
+// Proof-batched forms (pm_plonk_prove_batch_zk).  The blinders of all proofs do not fit the kernel
+// arguments: they sit in a device table ([batch][PM_PLONK_ZK_BLINDERS][4] canonical Montgomery limbs, staged once per call
+// in the workspace's ConstStage) that the kernels read with the wave-uniform proof index.
+// vectors_per_proof vectors per proof (vector v of proof b at d_vecs + (b vectors_per_proof + v) stride) get the Z_H
+// blinders of wire first_wire + v (0..3 = a b c d, 4 = z); the tail [n, stride) of every vector is written
+int zk_blind_batch(pm_ctx* ctx, const void* d_blinders, void* d_vecs, uint32_t vectors_per_proof, uint32_t first_wire,
+                   uint32_t batch, size_t n, size_t stride, hipStream_t st);
+// dst[i] = src[i] w_8n^i for up to two groups of vectors in one launch; group g holds vecs[g] vectors per proof of len[g]
+// coefficients, vector v of proof b at (b vecs[g] + v) stride[g], the same layout on both sides
+struct ZkShiftBatchArgs {
+  const void* src[2];
+  void* dst[2];
+  size_t stride[2], len[2];
+  uint32_t vecs[2];
+  uint32_t groups;
+};
+int zk_shift_batch(pm_ctx* ctx, const ZkShiftBatchArgs& a, const void* d_w8, uint32_t batch, hipStream_t st);
+// zk_combine for every proof: d_ab holds A of proofs 0..batch-1 and then B(X / w_8n) of proofs 0..batch-1, 4n each; the
+// pieces of proof b go to d_t + 4 b stride with its blinders b_14..b_16 from the table
+int zk_combine_batch(pm_ctx* ctx, const void* d_blinders, const void* d_ab, const void* d_w8, uint32_t batch, size_t n,
+                     size_t stride, const uint64_t inv2[4], const uint64_t inv2s[4], void* d_t, hipStream_t st);
 // poly_evaluate_groups with a length per group
 int poly_evaluate_groups_n(pm_ctx* ctx, uint32_t groups, const uint32_t* k, const void* const* const* polys,
                            const uint64_t* const* points, uint64_t* const* outs, const size_t* ns);

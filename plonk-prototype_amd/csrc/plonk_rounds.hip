@@ -798,6 +798,136 @@ int zk_combine(pm_ctx* ctx, const void* d_ab, const void* d_w8, size_t n, size_t
   return PM_OK;
 }
 
+// ---- the same three steps for every proof of a batch (pm_plonk_prove_batch_zk).  A batch's
+// blinders (64 x 17 x 32 bytes) are beyond the kernel arguments: they are a device table in the constant address space,
+// like the per-proof challenges, and every kernel fetches the few it needs with the wave-uniform proof index (scalar
+// loads) before it picks one per lane with selects.
+struct ZkBlinders {
+  u32 b[PM_PLONK_ZK_BLINDERS][8];   // canonical Montgomery limbs, as the caller passed them
+};
+PM_DEV Fr zk_pick3(const Fr& c0, const Fr& c1, const Fr& c2, u32 i) {   // one of three uniform candidates, i per lane
+  Fr r;
+#pragma unroll
+  for (int l = 0; l < 9; ++l) r.l[l] = i == 0 ? c0.l[l] : (i == 1 ? c1.l[l] : c2.l[l]);
+  return r;
+}
+// zk_blind_kernel for vector blockIdx.y = b vpp + v of all proofs: the blinders of wire first_wire + v of proof b
+__global__ void __launch_bounds__(64) zk_blind_batch_kernel(const PM_KCONST ZkBlinders* bl, u32x4* vecs, u32 vpp, u32 first_wire,
+                                                            size_t n, size_t S) {
+  const u32 vec = blockIdx.y, b = vec / vpp, wire = first_wire + (vec - b * vpp), t = threadIdx.x;
+  // a b c d z take 3 3 2 3 3 blinders from b_0, b_3, b_6, b_8, b_11 on (first + 2 <= 13: inside the table for c too)
+  const u32 terms = wire == 2 ? 2u : 3u, first = wire < 3 ? 3 * wire : (wire == 3 ? 8u : 11u);
+  const ZkBlinders& mine = kconst(bl, b);
+  const Fr c0 = fe_unpack<FrP>(mine.b[first]), c1 = fe_unpack<FrP>(mine.b[first + 1]), c2 = fe_unpack<FrP>(mine.b[first + 2]);
+  u32x4* p = vecs + 2 * (size_t)vec * S;
+  const Fr beta = t < terms ? zk_pick3(c0, c1, c2, t) : fe_zero<FrP>();
+  if (t < S - n) st_canon(p, n + t, beta);
+  if (t < terms) st_canon(p, t, wsub(ld_canon(p, t), beta));
+}
+int zk_blind_batch(pm_ctx* ctx, const void* d_blinders, void* d_vecs, uint32_t vpp, uint32_t first_wire, uint32_t batch, size_t n,
+                   size_t stride, hipStream_t st) {
+  if (!d_blinders || !d_vecs || vpp == 0 || first_wire + vpp > 5 || batch == 0 || stride < n + ZK_MAX_TERMS || stride - n > 64 ||
+      n < ZK_MAX_TERMS)
+    return PM_ERR_BAD_ARG;
+  if (!st) st = ctx->stream;
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  ProfScope prof(ctx, st, "plonk_zk_blind_batch");
+  hipLaunchKernelGGL(zk_blind_batch_kernel, dim3(1, batch * vpp), dim3(64), 0, st, (const PM_KCONST ZkBlinders*)d_blinders,
+                     (u32x4*)d_vecs, vpp, first_wire, n, stride);
+  PM_HIP(ctx, hipGetLastError());
+  return PM_OK;
+}
+
+// zk_shift_kernel with blockIdx.y = the proof: w_8n^i is fetched and moved to device form once for all the proof's vectors
+__global__ void __launch_bounds__(256) zk_shift_batch_kernel(const ZkShiftBatchArgs a, const u32x4* w8, size_t max_len) {
+  const u32 b = blockIdx.y;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < max_len; i += stride) {
+    const Fr w = to_dev(ld_canon(w8, i));
+    for (u32 g = 0; g < a.groups; ++g) {
+      if (i >= a.len[g]) continue;
+      const size_t off = 2 * (size_t)b * a.vecs[g] * a.stride[g];
+      const u32x4* src = (const u32x4*)a.src[g] + off;
+      u32x4* dst = (u32x4*)a.dst[g] + off;
+      for (u32 v = 0; v < a.vecs[g]; ++v) st_canon(dst + 2 * (size_t)v * a.stride[g], i, fe_mul<FrP>(ld_canon(src + 2 * (size_t)v * a.stride[g], i), w));
+    }
+  }
+}
+int zk_shift_batch(pm_ctx* ctx, const ZkShiftBatchArgs& a, const void* d_w8, uint32_t batch, hipStream_t st) {
+  if (a.groups == 0 || a.groups > 2 || !d_w8 || batch == 0) return PM_ERR_BAD_ARG;
+  size_t max_len = 0;
+  for (uint32_t g = 0; g < a.groups; ++g) {
+    if (!a.src[g] || !a.dst[g] || a.vecs[g] == 0 || a.len[g] > a.stride[g]) return PM_ERR_BAD_ARG;
+    max_len = std::max(max_len, a.len[g]);
+  }
+  if (max_len == 0) return PM_OK;
+  if (!st) st = ctx->stream;
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  ProfScope prof(ctx, st, "plonk_zk_shift_batch");
+  hipLaunchKernelGGL(zk_shift_batch_kernel, dim3(grid_for(ctx, max_len), batch), dim3(256), 0, st, a, (const u32x4*)d_w8, max_len);
+  PM_HIP(ctx, hipGetLastError());
+  return PM_OK;
+}
+
+// zk_combine_kernel element for element, for proof blockIdx.y: A at ab + 4n b, B(X / w_8n) at ab + 4n (batch + b), the pieces at
+// t + 4 S b.  The proof's three quotient blinders are fetched once (uniform) and picked per element.
+struct ZkCombineBatchConsts {
+  u32 inv2[9], inv2s[9];
+};
+__global__ void __launch_bounds__(256) zk_combine_batch_kernel(const PM_KCONST ZkBlinders* bl, const u32x4* ab_all, const u32x4* w8,
+                                                               size_t n, size_t S, const ZkCombineBatchConsts kc, u32x4* t_all) {
+  const u32 proof = blockIdx.y, batch = gridDim.y;
+  const size_t n4 = 4 * n, tail = S - n, total = n4 + 4 * tail;
+  const u32x4* a_vec = ab_all + 2 * (size_t)proof * n4;
+  const u32x4* b_vec = ab_all + 2 * ((size_t)batch + proof) * n4;
+  u32x4* t = t_all + 2 * (size_t)proof * 4 * S;
+  const ZkBlinders& mine = kconst(bl, proof);
+  const Fr c0 = fe_unpack<FrP>(mine.b[14]), c1 = fe_unpack<FrP>(mine.b[15]), c2 = fe_unpack<FrP>(mine.b[16]);
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
+    size_t k, i, j;       // output piece, index in it, and the coefficient j < 4n of A and B to combine (if any)
+    bool high;            // P1_j (piece 4 beyond n) instead of P0_j
+    if (e < n4) {
+      j = e;
+      k = j / n;
+      i = j - k * n;
+      high = false;
+    } else {
+      k = (e - n4) / tail;
+      i = n + (e - n4 - k * tail);
+      j = i - n;
+      high = true;
+      if (k < 3 || j >= ZK_P1_LEN) {   // the blinder coefficient X^n of t_1..t_3, zeros elsewhere
+        const Fr b = (k < 3 && j == 0) ? zk_pick3(c0, c1, c2, (u32)k) : fe_zero<FrP>();
+        st_canon(t, k * S + i, b);
+        continue;
+      }
+    }
+    const Fr a_ = ld_canon(a_vec, j);
+    const Fr p = fe_mul<FrP>(ld_canon(b_vec, j), to_dev(ld_canon(w8, j ? n4 - j : 0)));   // B_j = p (j = 0), -p (j > 0)
+    const bool plus = (j == 0) != high;                                                  // A + B_j or A - B_j
+    const Fr s_ = plus ? wadd(a_, p) : wsub(a_, p);
+    Fr v = fe_mul<FrP>(s_, fr_limbs(high ? kc.inv2s : kc.inv2));
+    if (!high && i == 0 && k > 0) v = wsub(v, zk_pick3(c0, c1, c2, (u32)k - 1));
+    st_canon(t, k * S + i, v);
+  }
+}
+int zk_combine_batch(pm_ctx* ctx, const void* d_blinders, const void* d_ab, const void* d_w8, uint32_t batch, size_t n, size_t stride,
+                     const uint64_t inv2[4], const uint64_t inv2s[4], void* d_t, hipStream_t st) {
+  if (!d_blinders || !d_ab || !d_w8 || !d_t || batch == 0 || 4 * n < ZK_P1_LEN || stride < n + ZK_P1_LEN) return PM_ERR_BAD_ARG;
+  ZkCombineBatchConsts kc;
+  to_limbs29(kc.inv2, load_fr(inv2));
+  to_limbs29(kc.inv2s, load_fr(inv2s));
+  const size_t total = 4 * n + 4 * (stride - n);
+  if (!st) st = ctx->stream;
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  ProfScope prof(ctx, st, "plonk_zk_combine_batch");
+  hipLaunchKernelGGL(zk_combine_batch_kernel, dim3(grid_for(ctx, total), batch), dim3(256), 0, st,
+                     (const PM_KCONST ZkBlinders*)d_blinders, (const u32x4*)d_ab, (const u32x4*)d_w8, n, stride, kc, (u32x4*)d_t);
+  PM_HIP(ctx, hipGetLastError());
+  return PM_OK;
+}
+
 }  // namespace pm
 
 using namespace pm;

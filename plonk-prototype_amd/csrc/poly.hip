@@ -1027,6 +1027,7 @@ __global__ void __launch_bounds__(256) ruf_sum_replay_batch_kernel(const u32x4* 
 struct EvalBatchPolys {
   const u32x4* p[PM_EVAL_BATCH_SLOTS];
   size_t stride[PM_EVAL_BATCH_SLOTS];
+  size_t len[PM_EVAL_BATCH_SLOTS];   // coefficients of slot j (<= the n the geometry was laid out for)
   u32 point[PM_EVAL_BATCH_SLOTS];
 };
 __global__ void __launch_bounds__(256) eval_tables_batch_kernel(u32x4* xpow_all, u32x4* xblk_all, const PM_KCONST EvalConsts* kcs,
@@ -1042,7 +1043,7 @@ __global__ void __launch_bounds__(256) eval_tables_batch_kernel(u32x4* xpow_all,
     st_tw(xblk, b, fr_canon(fr_pow(fr_limbs(kc.x), (unsigned long long)b * seg, fr_limbs(kc.one))));
   }
 }
-__global__ void __launch_bounds__(256) poly_eval_batch_kernel(const EvalBatchPolys polys, size_t n, u32 L,
+__global__ void __launch_bounds__(256) poly_eval_batch_kernel(const EvalBatchPolys polys, u32 L,
                                                               const PM_KCONST EvalConsts* kcs, const u32x4* xpow_all,
                                                               const u32x4* xblk_all, u32x4* partial_all) {
   __shared__ u32 sh[256 * 9];
@@ -1054,11 +1055,12 @@ __global__ void __launch_bounds__(256) poly_eval_batch_kernel(const EvalBatchPol
   u32x4* partial = partial_all + 3 * ((size_t)proof * gridDim.y + j) * gridDim.x;
   const size_t base = (size_t)b * 256 * L;
   const Fr xrow = fr_limbs(kconst(kcs, pt).xrow);
+  const size_t len = polys.len[j];
   Fr acc = fe_zero<FrP>();
   for (u32 jj = L; jj-- > 0;) {
     const size_t idx = base + (size_t)jj * 256 + t;
     acc = fe_mul<FrP>(acc, xrow);
-    if (idx < n) acc = fe_add<FrP>(acc, ld_canon(coeffs, idx));
+    if (idx < len) acc = fe_add<FrP>(acc, ld_canon(coeffs, idx));
   }
   acc = fe_mul<FrP>(acc, ld_tw(xpow, t));
   acc = block_sum_256(acc, sh);
@@ -1496,7 +1498,7 @@ size_t pm::evaluate_batch_ws_bytes(uint32_t k, uint32_t batch, size_t n) {   // 
 }
 int pm::evaluate_batch(pm_ctx* ctx, ConstStage& stage, uint32_t k, const void* const* polys, const size_t* strides,
                    const uint8_t* point_of, const uint64_t* points, uint32_t batch, size_t n, void* d_ws, uint64_t* out,
-                   hipStream_t st) {
+                   hipStream_t st, const size_t* lens) {
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (k == 0 || k > PM_EVAL_BATCH_SLOTS || batch == 0 || n == 0) return set_err(ctx, PM_ERR_BAD_ARG, "evaluate_batch: bad sizes");
   EvalBatchPolys ep;
@@ -1504,6 +1506,8 @@ int pm::evaluate_batch(pm_ctx* ctx, ConstStage& stage, uint32_t k, const void* c
   for (uint32_t j = 0; j < k; ++j) {
     ep.p[j] = (const u32x4*)polys[j];
     ep.stride[j] = strides[j];
+    ep.len[j] = lens ? lens[j] : n;
+    if (ep.len[j] > n) return set_err(ctx, PM_ERR_BAD_ARG, "evaluate_batch: a slot is longer than n");
     ep.point[j] = point_of[j] ? 1u : 0u;
   }
   const u32 L = eval_batch_len(k, batch, n);
@@ -1533,7 +1537,7 @@ int pm::evaluate_batch(pm_ctx* ctx, ConstStage& stage, uint32_t k, const void* c
     ProfScope prof(ctx, st, "fr_poly_evaluate_batch");
     hipLaunchKernelGGL(eval_tables_batch_kernel, dim3((256 + nblocks + 255) / 256, 2 * batch), dim3(256), 0, st, xpow, xblk,
                        (const PM_KCONST EvalConsts*)dk, nblocks, (u32)seg);
-    hipLaunchKernelGGL(poly_eval_batch_kernel, dim3(nblocks, k, batch), dim3(256), 0, st, ep, n, L, (const PM_KCONST EvalConsts*)dk,
+    hipLaunchKernelGGL(poly_eval_batch_kernel, dim3(nblocks, k, batch), dim3(256), 0, st, ep, L, (const PM_KCONST EvalConsts*)dk,
                        (const u32x4*)xpow, (const u32x4*)xblk, partial);
     hipLaunchKernelGGL(poly_eval_final_kernel, dim3(k * batch), dim3(256), 0, st, (const u32x4*)partial, nblocks, d_out);
   }

@@ -13,6 +13,20 @@
 //   zc, pi_coeffs, pi_evals, num, den  [B][n]
 //   coset_w [B][4][4n]   coset_z, coset_pi, t  [B][4n]
 //   r [B][n]   agg, wit [2][B][n]  (at z, then at z w)
+//
+// Zero-knowledge batches (pm_plonk_batch_enable_zk / pm_plonk_prove_batch_zk) keep every coefficient
+// vector at the padded stride S = n + ZK_PAD in a second allocation, with the second-coset forms beside it; the evaluation
+// side (pi_evals, num, den, the first-coset forms) stays where it is:
+//   coeffs [B][4][S]   zc, r [B][S]   t [B][4][S]   agg, wit [2][B][S]
+//   shift [B][4][S] (p(w_8n X) of the wires, then of z)   shift_pi [B][n]
+//   coset2_w [B][4][4n]   coset2_z, coset2_pi [B][4n]   ab [2][B][4n]  (both coset quotients: one inverse transform)
+struct BatchZk {
+  void* base = nullptr;
+  size_t bytes = 0, stride = 0;
+  void *coeffs = nullptr, *zc = nullptr, *shift = nullptr, *shift_pi = nullptr, *coset2_w = nullptr, *coset2_z = nullptr,
+       *coset2_pi = nullptr, *ab = nullptr, *t = nullptr, *r = nullptr, *agg = nullptr, *wit = nullptr, *eval_ws = nullptr,
+       *ruf_ws = nullptr;
+};
 struct pm_plonk_batch {
   const pm_prover_key* key = nullptr;
   uint32_t max_batch = 0;
@@ -28,6 +42,7 @@ struct pm_plonk_batch {
   std::atomic<bool> busy{false};
   hipStream_t side = nullptr;
   hipEvent_t ev_main = nullptr, ev_side = nullptr;
+  BatchZk* zk = nullptr;     // pm_plonk_batch_enable_zk
 };
 
 namespace {
@@ -52,6 +67,32 @@ int batch_commit(pm_ctx* ctx, const pm_bases* ck, const void* d, size_t len, siz
                                &xyz[18 * (size_t)v0], nullptr));
   }
   return pm_g1_to_affine_batch(xyz.data(), count, &out_xy[0][0], nullptr);
+}
+
+// commit_lagrange_zk for `count` blinded wire vectors: [w] from the witness values over the Lagrange key, plus
+// sum_i b_i ([tau^(n+i)] - [tau^i]) from the three tail coefficients over the commit key at offsets n and 0 (negated), in
+// passes of at most 64 vectors; one host fold per wire, one affine conversion
+int batch_commit_lagrange_zk(pm_ctx* ctx, const pm_bases* lag, const pm_bases* ck, const void* d_wit, const void* coeffs, size_t n,
+                             size_t S, uint32_t count, u64 (*out_xy)[12]) {
+  std::vector<u64> xyz(3 * 18 * (size_t)count), sum(18 * (size_t)count);
+  u64* part[3] = {xyz.data(), xyz.data() + 18 * (size_t)count, xyz.data() + 36 * (size_t)count};
+  for (uint32_t v0 = 0; v0 < count; v0 += 64) {
+    const uint32_t k = std::min<uint32_t>(64, count - v0);
+    const void* tails = at((void*)coeffs, (size_t)v0 * S + n);
+    PK_TRY(pm_g1_msm_batch_dev(ctx, lag, 0, n, at((void*)d_wit, (size_t)v0 * n), n, k, PM_SCALAR_MONTGOMERY, part[0] + 18 * (size_t)v0, nullptr));
+    PK_TRY(pm_g1_msm_batch_dev(ctx, ck, n, 3, tails, S, k, PM_SCALAR_MONTGOMERY, part[1] + 18 * (size_t)v0, nullptr));
+    PK_TRY(pm_g1_msm_batch_dev(ctx, ck, 0, 3, tails, S, k, PM_SCALAR_MONTGOMERY, part[2] + 18 * (size_t)v0, nullptr));
+  }
+  for (uint32_t v = 0; v < count; ++v) {
+    u64 parts[3][18];
+    for (int k = 0; k < 3; ++k) memcpy(parts[k], part[k] + 18 * (size_t)v, sizeof parts[k]);
+    HFp y;
+    memcpy(y.l, parts[2] + 6, 48);
+    y = pm::host::sub(pm::host::zero<6>(), y, pm::host::FP());   // -P = (X, -Y, Z)
+    memcpy(parts[2] + 6, y.l, 48);
+    PK_TRY(pm_g1_fold(&parts[0][0], 3, &sum[18 * (size_t)v]));
+  }
+  return pm_g1_to_affine_batch(sum.data(), count, &out_xy[0][0], nullptr);
 }
 
 // pi_evals <- 0, then every proof's public inputs in ONE staged scatter (pi_scatter_kernel over global positions b n + i; a
@@ -99,11 +140,51 @@ int batch_scatter_pi(pm_ctx* ctx, pm_plonk_batch* ws, uint32_t B, const uint64_t
 
 int prove_batch_body(pm_ctx* ctx, pm_prover_key* pk, pm_plonk_batch* ws, const pm_bases* ck, uint32_t B, const void* d_wit,
                      const uint64_t* const* pi_pos, const uint64_t* const* pi_val, const size_t* n_pi, uint32_t flags,
-                     pm_plonk_proof* out) {
+                     const uint64_t (*blinders)[PM_PLONK_ZK_BLINDERS][4], pm_plonk_proof* out) {
   const size_t n = pk->n;
   const uint32_t lg = pk->log_n;
   const HFr one = fone();
   ws->stage.reset();
+  // zero-knowledge mode: blinded wires and z of n + 3 coefficients, quotient pieces up to n + 10, all at the padded stride S in
+  // the workspace's ZK regions, and the second-coset forms for the quotient.  Otherwise S = n and the plain regions.
+  BatchZk* const zk = blinders ? ws->zk : nullptr;
+  const ZkState* const kz = zk ? pk->zk : nullptr;
+  const size_t S = zk ? zk->stride : n, wlen = zk ? n + 3 : n;
+  void* const W = zk ? zk->coeffs : ws->coeffs;      // [B][4][S]
+  void* const Zc = zk ? zk->zc : ws->zc;             // [B][S]
+  void* const T = zk ? zk->t : ws->t;                // [B][4][S]
+  void* const R = zk ? zk->r : ws->r;                // [B][S]
+  void* const AGG = zk ? zk->agg : ws->agg;          // [2][B][S]
+  void* const WIT = zk ? zk->wit : ws->wit;          // [2][B][S]
+  void* d_bl = nullptr;                              // the batch's blinders on the device: [B][17][4]
+  if (zk) {
+    void* h_bl;
+    const size_t bytes = sizeof(uint64_t) * 4 * PM_PLONK_ZK_BLINDERS * B;
+    if (!ws->stage.take(bytes, &h_bl, &d_bl)) return pm::set_err(ctx, PM_ERR_OOM, "constant table full");
+    memcpy(h_bl, blinders, bytes);
+    PM_HIP(ctx, hipSetDevice(ctx->device));
+    PM_HIP(ctx, hipMemcpyAsync(d_bl, h_bl, bytes, hipMemcpyHostToDevice, ctx->stream));   // ahead of every fork of this call
+  }
+  // the wires + PI (round 1) or z (round 2) on the second coset: one w_8n^i scaling pass, then the coset transforms
+  auto second_coset = [&](bool round1, hipStream_t st) -> int {
+    pm::ZkShiftBatchArgs sa;
+    memset(&sa, 0, sizeof sa);
+    sa.groups = round1 ? 2 : 1;
+    sa.src[0] = round1 ? W : Zc;
+    sa.dst[0] = zk->shift;
+    sa.vecs[0] = round1 ? 4 : 1;
+    sa.stride[0] = S;
+    sa.len[0] = wlen;
+    sa.src[1] = ws->pi_coeffs;
+    sa.dst[1] = zk->shift_pi;
+    sa.vecs[1] = 1;
+    sa.stride[1] = n;
+    sa.len[1] = n;
+    PK_TRY(pm::zk_shift_batch(ctx, sa, kz->w8, B, st));
+    if (!round1) return pm_fr_ntt_dev(ctx, zk->shift, wlen, S, zk->coset2_z, 4 * n, lg + 2, B, PM_NTT_COSET, st);
+    PK_TRY(pm_fr_ntt_dev(ctx, zk->shift, wlen, S, zk->coset2_w, 4 * n, lg + 2, 4 * B, PM_NTT_COSET, st));
+    return pm_fr_ntt_dev(ctx, zk->shift_pi, n, n, zk->coset2_pi, 4 * n, lg + 2, B, PM_NTT_COSET, st);
+  };
   std::vector<Transcript> ts(B, pk->base);
   if (!(flags & PM_PLONK_UPSTREAM_TRANSCRIPT)) {
     for (uint32_t b = 0; b < B; ++b) {
@@ -125,16 +206,27 @@ int prove_batch_body(pm_ctx* ctx, pm_prover_key* pk, pm_plonk_batch* ws, const p
   if (lag) {
     // the wires are committed from their values on H: the wire iNTT goes to the side stream with the coset transforms
     PK_TRY(pm_stream_fork(ctx, side, ws->ev_main));
-    PK_TRY(pm_fr_ntt_dev(ctx, d_wit, n, n, ws->coeffs, n, lg, 4 * B, PM_NTT_INVERSE, side));
-    PK_TRY(pm_fr_ntt_dev(ctx, ws->coeffs, n, n, ws->coset_w, 4 * n, lg + 2, 4 * B, PM_NTT_COSET, side));
+    PK_TRY(pm_fr_ntt_dev(ctx, d_wit, n, n, W, S, lg, 4 * B, PM_NTT_INVERSE, side));
+    if (zk) {
+      PK_TRY(pm::zk_blind_batch(ctx, d_bl, W, 4, 0, B, n, S, side));
+      PK_TRY(pm_stream_join(ctx, side, ws->ev_side));   // the blinder MSMs below read the blinded coefficients
+    }
+    PK_TRY(pm_fr_ntt_dev(ctx, W, wlen, S, ws->coset_w, 4 * n, lg + 2, 4 * B, PM_NTT_COSET, side));
     PK_TRY(pm_fr_ntt_dev(ctx, ws->pi_coeffs, n, n, ws->coset_pi, 4 * n, lg + 2, B, PM_NTT_COSET, side));
-    PK_TRY(batch_commit(ctx, lag, d_wit, n, n, 4 * B, xy));
+    if (zk) {
+      PK_TRY(second_coset(true, side));
+      PK_TRY(batch_commit_lagrange_zk(ctx, lag, ck, d_wit, W, n, S, 4 * B, xy));
+    } else {
+      PK_TRY(batch_commit(ctx, lag, d_wit, n, n, 4 * B, xy));
+    }
   } else {
-    PK_TRY(pm_fr_ntt_dev(ctx, d_wit, n, n, ws->coeffs, n, lg, 4 * B, PM_NTT_INVERSE, nullptr));
+    PK_TRY(pm_fr_ntt_dev(ctx, d_wit, n, n, W, S, lg, 4 * B, PM_NTT_INVERSE, nullptr));
+    if (zk) PK_TRY(pm::zk_blind_batch(ctx, d_bl, W, 4, 0, B, n, S, nullptr));
     PK_TRY(pm_stream_fork(ctx, side, ws->ev_main));
-    PK_TRY(pm_fr_ntt_dev(ctx, ws->coeffs, n, n, ws->coset_w, 4 * n, lg + 2, 4 * B, PM_NTT_COSET, side));
+    PK_TRY(pm_fr_ntt_dev(ctx, W, wlen, S, ws->coset_w, 4 * n, lg + 2, 4 * B, PM_NTT_COSET, side));
     PK_TRY(pm_fr_ntt_dev(ctx, ws->pi_coeffs, n, n, ws->coset_pi, 4 * n, lg + 2, B, PM_NTT_COSET, side));
-    PK_TRY(batch_commit(ctx, ck, ws->coeffs, n, n, 4 * B, xy));
+    if (zk) PK_TRY(second_coset(true, side));
+    PK_TRY(batch_commit(ctx, ck, W, wlen, S, 4 * B, xy));
   }
   for (uint32_t b = 0; b < B; ++b)
     for (int j = 0; j < 4; ++j) {
@@ -166,10 +258,12 @@ int prove_batch_body(pm_ctx* ctx, pm_prover_key* pk, pm_plonk_batch* ws, const p
     for (uint32_t b = 0; b < B && !prc; ++b) prc = pm_fr_prefix_product_dev(ctx, at(ws->den, b * n), n, at(ws->num, b * n), nullptr);
   }
   PK_TRY(prc);
-  PK_TRY(pm_fr_ntt_dev(ctx, ws->num, n, n, ws->zc, n, lg, B, PM_NTT_INVERSE, nullptr));
+  PK_TRY(pm_fr_ntt_dev(ctx, ws->num, n, n, Zc, S, lg, B, PM_NTT_INVERSE, nullptr));
+  if (zk) PK_TRY(pm::zk_blind_batch(ctx, d_bl, Zc, 1, 4, B, n, S, nullptr));
   PK_TRY(pm_stream_fork(ctx, side, ws->ev_main));
-  PK_TRY(pm_fr_ntt_dev(ctx, ws->zc, n, n, ws->coset_z, 4 * n, lg + 2, B, PM_NTT_COSET, side));
-  PK_TRY(batch_commit(ctx, ck, ws->zc, n, n, B, xy));
+  PK_TRY(pm_fr_ntt_dev(ctx, Zc, wlen, S, ws->coset_z, 4 * n, lg + 2, B, PM_NTT_COSET, side));
+  if (zk) PK_TRY(second_coset(false, side));
+  PK_TRY(batch_commit(ctx, ck, Zc, wlen, S, B, xy));
   for (uint32_t b = 0; b < B; ++b) {
     memcpy(out[b].commitments[4], xy[b], 96);
     ts[b].append_commitment(tl::PERM, out[b].commitments[4]);
@@ -215,9 +309,37 @@ int prove_batch_body(pm_ctx* ctx, pm_prover_key* pk, pm_plonk_batch* ws, const p
     for (int j = 0; j < 4; ++j) put(q.zh_inv[j], pk->zh_inv[j]);
   }
   PK_TRY(pm_stream_join(ctx, side, ws->ev_side));   // the wire, PI and z coset forms are ready
-  PK_TRY(pm::quotient_batch(ctx, ws->stage, qa.data(), B, 16 * n, 4 * n, n, ws->t, ctx->stream));
-  PK_TRY(pm_fr_ntt_dev(ctx, ws->t, 4 * n, 4 * n, ws->t, 4 * n, lg + 2, B, PM_NTT_INVERSE | PM_NTT_COSET, nullptr));
-  PK_TRY(batch_commit(ctx, ck, ws->t, n, n, 4 * B, xy));   // t_i of proof b: vector 4 b + i
+  if (!zk) {
+    PK_TRY(pm::quotient_batch(ctx, ws->stage, qa.data(), B, 16 * n, 4 * n, n, ws->t, ctx->stream));
+    PK_TRY(pm_fr_ntt_dev(ctx, ws->t, 4 * n, 4 * n, ws->t, 4 * n, lg + 2, B, PM_NTT_INVERSE | PM_NTT_COSET, nullptr));
+    PK_TRY(batch_commit(ctx, ck, ws->t, n, n, 4 * B, xy));   // t_i of proof b: vector 4 b + i
+  } else {
+    // deg t' <= 4n + 9: the same kernel on the second coset gives t' mod (X^4n + s) beside t' mod (X^4n - s); the 2B
+    // outputs (A of every proof, then B of every proof) share one inverse coset transform
+    PK_TRY(pm::quotient_batch(ctx, ws->stage, qa.data(), B, 16 * n, 4 * n, n, zk->ab, ctx->stream));
+    for (uint32_t b = 0; b < B; ++b) {
+      pm_plonk_quotient_args& q2 = qa[b];
+      for (int j = 0; j < 4; ++j) {
+        q2.wires[j] = at(zk->coset2_w, 4 * n * j);
+        q2.sigmas[j] = at(kz->sigma_coset2, 4 * n * j);
+      }
+      q2.z = zk->coset2_z;
+      q2.pi = zk->coset2_pi;
+      const void** sel2[NSEL] = {&q2.q_m, &q2.q_l, &q2.q_r, &q2.q_o, &q2.q_c, &q2.q_4, &q2.q_arith, &q2.q_range, &q2.q_logic,
+                                 &q2.q_fixed_group_add, &q2.q_variable_group_add};
+      for (int s_ = 0; s_ < NSEL; ++s_) *sel2[s_] = kz->sel_coset2[s_];
+      q2.l1 = kz->l1_coset2;
+      q2.x = kz->x2;
+      for (int j = 0; j < 4; ++j) put(q2.zh_inv[j], kz->zh_inv2[j]);
+    }
+    PK_TRY(pm::quotient_batch(ctx, ws->stage, qa.data(), B, 16 * n, 4 * n, n, at(zk->ab, 4 * n * (size_t)B), ctx->stream));
+    PK_TRY(pm_fr_ntt_dev(ctx, zk->ab, 4 * n, 4 * n, zk->ab, 4 * n, lg + 2, 2 * B, PM_NTT_INVERSE | PM_NTT_COSET, nullptr));
+    u64 inv2[4], inv2s[4];
+    put(inv2, kz->inv2);
+    put(inv2s, kz->inv2s);
+    PK_TRY(pm::zk_combine_batch(ctx, d_bl, zk->ab, kz->w8, B, n, S, inv2, inv2s, T, ctx->stream));
+    PK_TRY(batch_commit(ctx, ck, T, n + pm::ZK_P1_LEN, S, 4 * B, xy));
+  }
   for (uint32_t b = 0; b < B; ++b)
     for (int i = 0; i < 4; ++i) {
       memcpy(out[b].commitments[5 + i], xy[4 * b + i], 96);
@@ -235,28 +357,30 @@ int prove_batch_body(pm_ctx* ctx, pm_prover_key* pk, pm_plonk_batch* ws, const p
     put(&points[8 * b + 4], zw[b]);
   }
   // the openings as prove_body takes them: 15 at z, the values r(z) needs at z, 4 at z w -- one batch, one synchronisation
+  // (a slot with a stride is a padded vector of the batch, S coefficients; one without is a key polynomial, n)
   const void* sp[BATCH_EVAL_SLOTS];
-  size_t sstride[BATCH_EVAL_SLOTS];
+  size_t sstride[BATCH_EVAL_SLOTS], slen[BATCH_EVAL_SLOTS];
   uint8_t spt[BATCH_EVAL_SLOTS];
   uint32_t K = 0;
   auto slot = [&](const void* p, size_t stride, uint8_t pt) {
     sp[K] = p;
     sstride[K] = stride;
+    slen[K] = stride ? S : n;
     spt[K] = pt;
     ++K;
   };
-  for (int j = 0; j < 4; ++j) slot(at(ws->coeffs, j * n), 4 * n, 0);
+  for (int j = 0; j < 4; ++j) slot(at(W, j * S), 4 * S, 0);
   for (int j = 0; j < 3; ++j) slot(at(pk->sigma_coeffs, j * n), 0, 0);
   slot(at(pk->sel_coeffs, Q_ARITH * n), 0, 0);
   slot(at(pk->sel_coeffs, Q_C * n), 0, 0);
   slot(at(pk->sel_coeffs, Q_L * n), 0, 0);
   slot(at(pk->sel_coeffs, Q_R * n), 0, 0);
-  for (int i = 0; i < 4; ++i) slot(at(ws->t, i * n), 4 * n, 0);
+  for (int i = 0; i < 4; ++i) slot(at(T, i * S), 4 * S, 0);
   const uint32_t x0 = K;   // 15
   slot(at(pk->sel_coeffs, Q_M * n), 0, 0);
   slot(at(pk->sel_coeffs, Q_O * n), 0, 0);
   slot(at(pk->sel_coeffs, Q_4 * n), 0, 0);
-  slot(ws->zc, n, 0);
+  slot(Zc, S, 0);
   slot(at(pk->sigma_coeffs, 3 * n), 0, 0);
   const int wsel[4] = {Q_RANGE, Q_LOGIC, Q_FIXED, Q_VAR};
   int xslot[4] = {-1, -1, -1, -1};
@@ -266,17 +390,19 @@ int prove_batch_body(pm_ctx* ctx, pm_prover_key* pk, pm_plonk_batch* ws, const p
       slot(at(pk->sel_coeffs, wsel[w] * n), 0, 0);
     }
   const uint32_t w0 = K;
-  slot(at(ws->coeffs, 0), 4 * n, 1);
-  slot(at(ws->coeffs, n), 4 * n, 1);
-  slot(at(ws->coeffs, 3 * n), 4 * n, 1);
-  slot(ws->zc, n, 1);
+  slot(at(W, 0), 4 * S, 1);
+  slot(at(W, S), 4 * S, 1);
+  slot(at(W, 3 * S), 4 * S, 1);
+  slot(Zc, S, 1);
   if (K > BATCH_EVAL_SLOTS) return pm::set_err(ctx, PM_ERR_BAD_ARG, "more openings than the workspace holds");
   std::vector<u64> ov(4 * (size_t)K * B);
-  PK_TRY(pm::evaluate_batch(ctx, ws->stage, K, sp, sstride, spt, points.data(), B, n, ws->eval_ws, ov.data(), ctx->stream));
+  PK_TRY(pm::evaluate_batch(ctx, ws->stage, K, sp, sstride, spt, points.data(), B, S, zk ? zk->eval_ws : ws->eval_ws, ov.data(),
+                            ctx->stream, zk ? slen : nullptr));
   const void* lin_v[12];
   size_t lin_s[12];
   uint32_t lk = 0;
   std::vector<u64> lin_c;   // [B][lk][4]
+  std::vector<u64> cz_c;    // [B][4]: z's coefficient in r (zero-knowledge mode: the only term with a tail beyond n)
   std::vector<HFr> aw(B), aws(B);
   for (uint32_t b = 0; b < B; ++b) {
     auto val = [&](uint32_t s) { return get(&ov[4 * ((size_t)b * K + s)]); };
@@ -328,7 +454,9 @@ int prove_batch_body(pm_ctx* ctx, pm_prover_key* pk, pm_plonk_batch* ws, const p
     if (!pk->sel_zero[Q_LOGIC]) term(at(pk->sel_coeffs, Q_LOGIC * n), 0, widget_logic(logic_sep[b], re), xv[X_LOGIC]);
     if (!pk->sel_zero[Q_FIXED]) term(at(pk->sel_coeffs, Q_FIXED * n), 0, widget_fixed(fixed_sep[b], re), xv[X_FIXED]);
     if (!pk->sel_zero[Q_VAR]) term(at(pk->sel_coeffs, Q_VAR * n), 0, widget_var(var_sep[b], re), xv[X_VAR]);
-    term(ws->zc, n, fadd(fmul(alpha[b], ident), fmul(alpha2, l1_z)), xv[X_Z]);
+    const HFr c_z = fadd(fmul(alpha[b], ident), fmul(alpha2, l1_z));
+    term(Zc, S, c_z, xv[X_Z]);
+    cz_c.insert(cz_c.end(), c_z.l, c_z.l + 4);
     term(at(pk->sigma_coeffs, 3 * n), 0, fneg(fmul(fmul(fmul(alpha[b], copy3), beta[b]), z_next)), xv[X_S4]);
     lk = k;
     ev[E_R] = r_z;
@@ -340,27 +468,32 @@ int prove_batch_body(pm_ctx* ctx, pm_prover_key* pk, pm_plonk_batch* ws, const p
     aw[b] = ts[b].challenge_scalar(tl::AGGREGATE);
     aws[b] = ts[b].challenge_scalar(tl::AGGREGATE);
   }
-  PK_TRY(pm::lincomb_batch(ctx, ws->stage, lk, lin_v, lin_s, lin_c.data(), B, n, ws->r, n, ctx->stream));
+  PK_TRY(pm::lincomb_batch(ctx, ws->stage, lk, lin_v, lin_s, lin_c.data(), B, n, R, S, ctx->stream));
+  if (zk) {   // beyond n only the blinded z has coefficients
+    const void* tail_v[1] = {at(Zc, n)};
+    const size_t tail_s[1] = {S};
+    PK_TRY(pm::lincomb_batch(ctx, ws->stage, 1, tail_v, tail_s, cz_c.data(), B, S - n, at(R, n), S, ctx->stream));
+  }
   // ---- round 5: CommitKey::compute_aggregate_witness at z and at z w ------------------------------
   {
     const void* agg_v[12];
     size_t agg_s[12];
     for (int i = 0; i < 4; ++i) {
-      agg_v[i] = at(ws->t, i * n);
-      agg_s[i] = 4 * n;
+      agg_v[i] = at(T, i * S);
+      agg_s[i] = 4 * S;
     }
-    agg_v[4] = ws->r;
-    agg_s[4] = n;
+    agg_v[4] = R;
+    agg_s[4] = S;
     for (int j = 0; j < 4; ++j) {
-      agg_v[5 + j] = at(ws->coeffs, j * n);
-      agg_s[5 + j] = 4 * n;
+      agg_v[5 + j] = at(W, j * S);
+      agg_s[5 + j] = 4 * S;
     }
     for (int j = 0; j < 3; ++j) {
       agg_v[9 + j] = at(pk->sigma_coeffs, j * n);
       agg_s[9 + j] = 0;
     }
-    const void* sh_v[4] = {ws->zc, at(ws->coeffs, 0), at(ws->coeffs, n), at(ws->coeffs, 3 * n)};
-    const size_t sh_s[4] = {n, 4 * n, 4 * n, 4 * n};
+    const void* sh_v[4] = {Zc, at(W, 0), at(W, S), at(W, 3 * S)};
+    const size_t sh_s[4] = {S, 4 * S, 4 * S, 4 * S};
     std::vector<u64> agg_c(12 * 4 * (size_t)B), sh_c(4 * 4 * (size_t)B), zs(8 * (size_t)B);
     for (uint32_t b = 0; b < B; ++b) {
       const HFr zn = fpow(zc[b], n);
@@ -383,13 +516,21 @@ int prove_batch_body(pm_ctx* ctx, pm_prover_key* pk, pm_plonk_batch* ws, const p
       put(&zs[4 * (size_t)b], zc[b]);
       put(&zs[4 * ((size_t)B + b)], zw[b]);
     }
-    PK_TRY(pm::lincomb_batch(ctx, ws->stage, 12, agg_v, agg_s, agg_c.data(), B, n, ws->agg, n, ctx->stream));
-    PK_TRY(pm::lincomb_batch(ctx, ws->stage, 4, sh_v, sh_s, sh_c.data(), B, n, at(ws->agg, (size_t)B * n), n, ctx->stream));
-    PK_TRY(pm::ruffini_batch(ctx, ws->stage, ws->agg, n, n, zs.data(), 2 * B, ws->wit, ws->ruf_ws, ctx->stream));
+    PK_TRY(pm::lincomb_batch(ctx, ws->stage, 12, agg_v, agg_s, agg_c.data(), B, n, AGG, S, ctx->stream));
+    if (zk) {   // the padded tails: t pieces, r and the wires (the sigmas end at n)
+      const void* tail_v[9];
+      std::vector<u64> tail_c(9 * 4 * (size_t)B);
+      for (int i = 0; i < 9; ++i) tail_v[i] = at((void*)agg_v[i], n);
+      for (uint32_t b = 0; b < B; ++b) memcpy(&tail_c[9 * 4 * (size_t)b], &agg_c[12 * 4 * (size_t)b], 9 * 32);
+      PK_TRY(pm::lincomb_batch(ctx, ws->stage, 9, tail_v, agg_s, tail_c.data(), B, S - n, at(AGG, n), S, ctx->stream));
+    }
+    PK_TRY(pm::lincomb_batch(ctx, ws->stage, 4, sh_v, sh_s, sh_c.data(), B, S, at(AGG, (size_t)B * S), S, ctx->stream));
+    PK_TRY(pm::ruffini_batch(ctx, ws->stage, AGG, S, S, zs.data(), 2 * B, WIT, zk ? zk->ruf_ws : ws->ruf_ws, ctx->stream));
   }
   std::vector<u64> wxy_buf(12 * 2 * (size_t)B);
   u64(*wxy)[12] = (u64(*)[12])wxy_buf.data();
-  PK_TRY(batch_commit(ctx, ck, ws->wit, n - 1, n, 2 * B, wxy));
+  // deg W_z = deg t_4 - 1: n + 9 coefficients in zero-knowledge mode
+  PK_TRY(batch_commit(ctx, ck, WIT, zk ? n + pm::ZK_P1_LEN - 1 : n - 1, S, 2 * B, wxy));
   for (uint32_t b = 0; b < B; ++b) {
     memcpy(out[b].commitments[9], wxy[b], 96);
     memcpy(out[b].commitments[10], wxy[B + b], 96);
@@ -412,6 +553,10 @@ extern "C" void pm_plonk_batch_free(pm_ctx* ctx, pm_plonk_batch* ws) {
   if (ws->ev_main) (void)hipEventDestroy(ws->ev_main);
   if (ws->ev_side) (void)hipEventDestroy(ws->ev_side);
   if (ws->base && ctx) (void)pm_dev_free(ctx, ws->base);
+  if (ws->zk) {
+    if (ws->zk->base && ctx) (void)pm_dev_free(ctx, ws->zk->base);
+    delete ws->zk;
+  }
   if (ws->stage.h) (void)hipHostFree(ws->stage.h);
   if (ws->pi_h) (void)hipHostFree(ws->pi_h);
   delete ws;
@@ -472,9 +617,53 @@ extern "C" int pm_plonk_batch_create(pm_ctx* ctx, const pm_prover_key* key, uint
 
 extern "C" size_t pm_plonk_batch_bytes(const pm_plonk_batch* ws) { return ws ? ws->bytes : 0; }
 
-extern "C" int pm_plonk_prove_batch(pm_ctx* ctx, pm_prover_key* pk, pm_plonk_batch* ws, const pm_bases* ck, uint32_t batch,
-                                    const void* d_witnesses, const uint64_t* const* pi_positions, const uint64_t* const* pi_values,
-                                    const size_t* n_pi, uint32_t flags, pm_plonk_proof* out) {
+// The padded-stride regions of zero-knowledge batches, for max_batch proofs, in one further allocation (layout at the top).
+extern "C" int pm_plonk_batch_enable_zk(pm_ctx* ctx, pm_plonk_batch* ws, size_t* added_bytes) {
+  if (!ctx) return PM_ERR_BAD_ARG;
+  if (!ws) return pm::set_err(ctx, PM_ERR_BAD_ARG, "null argument");
+  BatchBusy guard(ws);
+  if (!guard.ok) return pm::set_err(ctx, PM_ERR_BUSY, "the batch workspace is in use by another call");
+  if (ws->zk) {
+    if (added_bytes) *added_bytes = ws->zk->bytes;
+    return PM_OK;
+  }
+  if (!ws->key->zk) return pm::set_err(ctx, PM_ERR_BAD_ARG, "the key is not ready for zero-knowledge proofs (pm_plonk_key_enable_zk first)");
+  const size_t n = ws->n, B = ws->max_batch, S = n + ZK_PAD;
+  BatchZk* zk = new BatchZk();
+  zk->stride = S;
+  struct Region { void** p; size_t bytes; };
+  const size_t bn = B * n * 32, bs = B * S * 32;
+  const Region regions[] = {{&zk->coeffs, 4 * bs},    {&zk->zc, bs},           {&zk->shift, 4 * bs},     {&zk->shift_pi, bn},
+                            {&zk->coset2_w, 16 * bn}, {&zk->coset2_z, 4 * bn}, {&zk->coset2_pi, 4 * bn}, {&zk->ab, 8 * bn},
+                            {&zk->t, 4 * bs},         {&zk->r, bs},            {&zk->agg, 2 * bs},       {&zk->wit, 2 * bs},
+                            {&zk->eval_ws, pm::evaluate_batch_ws_bytes(BATCH_EVAL_SLOTS, ws->max_batch, S)},
+                            {&zk->ruf_ws, pm::ruffini_batch_ws_bytes(2 * ws->max_batch, S)}};
+  size_t total = 0;
+  for (const Region& r : regions) total += (r.bytes + 255) / 256 * 256;
+  const int rc = pm_dev_alloc(ctx, total, &zk->base);
+  if (rc) {
+    (void)hipGetLastError();   // as in pm_plonk_batch_create: a refused hipMalloc must not stay the thread's last error
+    delete zk;
+    return rc == PM_ERR_OOM ? pm::set_err(ctx, PM_ERR_OOM, "the zero-knowledge regions of the batch workspace do not fit in device memory") : rc;
+  }
+  zk->bytes = total;
+  size_t off = 0;
+  for (const Region& r : regions) {
+    *r.p = (char*)zk->base + off;
+    off += (r.bytes + 255) / 256 * 256;
+  }
+  ws->zk = zk;
+  if (added_bytes) *added_bytes = total;
+  return PM_OK;
+}
+
+extern "C" size_t pm_plonk_batch_zk_bytes(const pm_plonk_batch* ws) { return ws && ws->zk ? ws->zk->bytes : 0; }
+
+// the argument checks and the call shared by pm_plonk_prove_batch and pm_plonk_prove_batch_zk (zero_knowledge: blinders are expected)
+static int prove_batch_entry(pm_ctx* ctx, pm_prover_key* pk, pm_plonk_batch* ws, const pm_bases* ck, uint32_t batch,
+                             const void* d_witnesses, const uint64_t* const* pi_positions, const uint64_t* const* pi_values,
+                             const size_t* n_pi, uint32_t flags, bool zero_knowledge,
+                             const uint64_t (*blinders)[PM_PLONK_ZK_BLINDERS][4], pm_plonk_proof* out) {
   if (!ctx) return PM_ERR_BAD_ARG;
   if (!pk || !ws || !ck || !d_witnesses || !out) return pm::set_err(ctx, PM_ERR_BAD_ARG, "null argument");
   if (ws->key != pk) return pm::set_err(ctx, PM_ERR_BAD_ARG, "the batch workspace was made for another key");
@@ -483,10 +672,19 @@ extern "C" int pm_plonk_prove_batch(pm_ctx* ctx, pm_prover_key* pk, pm_plonk_bat
   if (flags == (PM_PLONK_BIND_PUBLIC_INPUTS | PM_PLONK_UPSTREAM_TRANSCRIPT))
     return pm::set_err(ctx, PM_ERR_BAD_ARG, "PM_PLONK_BIND_PUBLIC_INPUTS and PM_PLONK_UPSTREAM_TRANSCRIPT exclude each other");
   if (!pk->committed) return pm::set_err(ctx, PM_ERR_BAD_ARG, "the key is not committed (pm_plonk_key_commit first)");
+  if (zero_knowledge) {
+    if (!blinders) return pm::set_err(ctx, PM_ERR_BAD_ARG, "null blinders");
+    for (uint32_t b = 0; b < batch; ++b)
+      for (int i = 0; i < PM_PLONK_ZK_BLINDERS; ++i)
+        if (pm::host::geq<4>(blinders[b][i], FRF().m)) return pm::set_err(ctx, PM_ERR_BAD_ARG, "a blinder is not below r");
+  }
   BatchBusy guard(ws);
   if (!guard.ok) return pm::set_err(ctx, PM_ERR_BUSY, "the batch workspace is in use by another call");
+  if (zero_knowledge && (!ws->zk || !pk->zk))
+    return pm::set_err(ctx, PM_ERR_BAD_ARG, "the batch workspace is not ready for zero-knowledge proofs (pm_plonk_batch_enable_zk first)");
   const size_t n = pk->n;
-  if (pm_g1_bases_len(ck) < n) return pm::set_err(ctx, PM_ERR_LENGTH, "commit key shorter than n");
+  if (pm_g1_bases_len(ck) < (zero_knowledge ? n + PM_PLONK_ZK_EXTRA_BASES : n))
+    return pm::set_err(ctx, PM_ERR_LENGTH, zero_knowledge ? "commit key shorter than n + PM_PLONK_ZK_EXTRA_BASES" : "commit key shorter than n");
   for (uint32_t b = 0; n_pi && b < batch; ++b) {
     if (!n_pi[b]) continue;
     if (!pi_positions || !pi_values || !pi_positions[b] || !pi_values[b])
@@ -496,10 +694,24 @@ extern "C" int pm_plonk_prove_batch(pm_ctx* ctx, pm_prover_key* pk, pm_plonk_bat
   }
   if (pk->lagrange && ck != pk->lagrange_ck)
     return pm::set_err(ctx, PM_ERR_BAD_ARG, "the key's Lagrange form was checked against another commit key");
-  const int rc = prove_batch_body(ctx, pk, ws, ck, batch, d_witnesses, pi_positions, pi_values, n_pi, flags, out);
+  const int rc = prove_batch_body(ctx, pk, ws, ck, batch, d_witnesses, pi_positions, pi_values, n_pi, flags,
+                                  zero_knowledge ? blinders : nullptr, out);
   if (rc) {   // nothing of this call may still run on the side stream when the next one starts
     (void)hipStreamSynchronize(ws->side);
     (void)pm_sync(ctx);
   }
   return rc;
+}
+
+extern "C" int pm_plonk_prove_batch(pm_ctx* ctx, pm_prover_key* pk, pm_plonk_batch* ws, const pm_bases* ck, uint32_t batch,
+                                    const void* d_witnesses, const uint64_t* const* pi_positions, const uint64_t* const* pi_values,
+                                    const size_t* n_pi, uint32_t flags, pm_plonk_proof* out) {
+  return prove_batch_entry(ctx, pk, ws, ck, batch, d_witnesses, pi_positions, pi_values, n_pi, flags, false, nullptr, out);
+}
+
+extern "C" int pm_plonk_prove_batch_zk(pm_ctx* ctx, pm_prover_key* pk, pm_plonk_batch* ws, const pm_bases* ck, uint32_t batch,
+                                       const void* d_witnesses, const uint64_t* const* pi_positions,
+                                       const uint64_t* const* pi_values, const size_t* n_pi, uint32_t flags,
+                                       const uint64_t (*blinders)[PM_PLONK_ZK_BLINDERS][4], pm_plonk_proof* out) {
+  return prove_batch_entry(ctx, pk, ws, ck, batch, d_witnesses, pi_positions, pi_values, n_pi, flags, true, blinders, out);
 }

@@ -175,10 +175,21 @@ class ProverKey:
         self.ctx._check(self.ctx._lib.pm_plonk_key_enable_zk(self.ctx._h, self._h, C.byref(out)))
         return int(out.value)
 
-    def batch(self, max_batch: int) -> "BatchWorkspace":
+    def batch(self, max_batch: int, zero_knowledge: bool = False) -> "BatchWorkspace":
         """A workspace for ``prove_batch`` of up to ``max_batch`` (<= 64) proofs on this key: about 42 n x 32 bytes of
-        device memory per proof, held until ``free()``.  It is separate from the key's own workspace."""
-        return BatchWorkspace(self, max_batch)
+        device memory per proof, held until ``free()``.  It is separate from the key's own workspace.
+        zero_knowledge: make the key (``enable_zk``) and the workspace (``BatchWorkspace.enable_zk``, about 51 n x 32 bytes
+        more per proof) ready for ``prove_batch(..., zero_knowledge=True)``."""
+        if zero_knowledge:
+            self.enable_zk()
+        ws = BatchWorkspace(self, max_batch)
+        if zero_knowledge:
+            try:
+                ws.enable_zk()
+            except Exception:
+                ws.free()
+                raise
+        return ws
 
     def free(self):
         if getattr(self, "_h", None) and self.ctx._h:
@@ -206,6 +217,18 @@ class BatchWorkspace:
     def device_bytes(self) -> int:
         """Device bytes the workspace holds (``pm_plonk_batch_bytes``; the witness staging not included)."""
         return int(self.ctx._lib.pm_plonk_batch_bytes(self._h))
+
+    def enable_zk(self) -> int:
+        """Add the padded-stride regions of zero-knowledge batches (``pm_plonk_batch_enable_zk``; the key must have had
+        ``ProverKey.enable_zk``).  Idempotent; plain batches on the workspace are unchanged.  -> the device bytes added (the
+        same on every call; ``device_bytes`` keeps counting the plain regions only)."""
+        out = C.c_size_t()
+        self.ctx._check(self.ctx._lib.pm_plonk_batch_enable_zk(self.ctx._h, self._h, C.byref(out)))
+        return int(out.value)
+
+    def zk_device_bytes(self) -> int:
+        """Device bytes ``enable_zk`` added (``pm_plonk_batch_zk_bytes``; 0 before it)."""
+        return int(self.ctx._lib.pm_plonk_batch_zk_bytes(self._h))
 
     def staging(self) -> DeviceVector:
         """max_batch x 4n elements of device memory for proof-major witnesses, allocated on first use."""
@@ -357,9 +380,14 @@ def sparse_public_inputs(public_inputs) -> tuple[np.ndarray, np.ndarray]:
     return pos, np.ascontiguousarray(pi[pos.astype(np.int64)])
 
 
-def random_blinders() -> np.ndarray:
-    """PM_PLONK_ZK_BLINDERS fresh uniform scalars below r (``secrets.randbelow``), [17, 4] Montgomery limbs."""
-    return np.stack([fr_to_limbs(secrets.randbelow(R_MOD)) for _ in range(_lib.PLONK_ZK_BLINDERS)])
+def random_blinders(count: int | None = None) -> np.ndarray:
+    """PM_PLONK_ZK_BLINDERS fresh uniform scalars below r (``secrets.randbelow``), [17, 4] Montgomery limbs; with a
+    ``count``, that many independent sets ([count, 17, 4]: one per proof of a batch)."""
+    if count is None:
+        return np.stack([fr_to_limbs(secrets.randbelow(R_MOD)) for _ in range(_lib.PLONK_ZK_BLINDERS)])
+    if count < 0:
+        raise ValueError("count must not be negative")
+    return np.stack([random_blinders() for _ in range(count)]) if count else np.zeros((0, _lib.PLONK_ZK_BLINDERS, 4), np.uint64)
 
 
 def prove(pk: ProverKey, ck: CommitKey, witness, public_inputs=None, bind_public_inputs: bool = True,
@@ -439,9 +467,17 @@ def _pi_pairs(public_inputs) -> tuple[np.ndarray, np.ndarray]:
 
 
 def prove_batch(pk: ProverKey, ck: CommitKey, witnesses, public_inputs=None, bind_public_inputs: bool = True,
-                workspace: BatchWorkspace | None = None) -> list[Proof]:
+                workspace: BatchWorkspace | None = None, zero_knowledge: bool = False, blinders=None) -> list[Proof]:
     """B proofs of one circuit in one ``pm_plonk_prove_batch`` call; proof b equals ``prove(pk, ck, witness b, public
     inputs b)`` byte for byte.
+
+    zero_knowledge: one ``pm_plonk_prove_batch_zk`` call instead (single GPU): every proof blinded as by
+    ``prove(..., zero_knowledge=True)``, proof b byte for byte the single zero-knowledge proof of
+    witness b, public inputs b and blinders b.  The key must be committed; it and the workspace are made ready
+    (``ProverKey.enable_zk``, ``BatchWorkspace.enable_zk``) when they are not, and the commit key needs n + 10 points.
+    blinders: [B, 17, 4] Montgomery limbs, each below r; None draws B independent sets with ``secrets.randbelow(r)``, never
+    one set for the batch -- pass fixed blinders in tests only: reusing blinders across proofs of different witnesses gives
+    the witness away.
 
     witnesses: one DeviceVector of B x 4n elements (proof-major: proof b's [a | b | c | d] at 4 n b), or a list of B
     per-proof witnesses -- DeviceVectors of 4n elements, copied device to device into the workspace's staging (one copy
@@ -451,6 +487,13 @@ def prove_batch(pk: ProverKey, ck: CommitKey, witnesses, public_inputs=None, bin
     ctx, n = pk.ctx, pk.n
     if ck.max_degree() + 1 < n:
         raise ValueError("commit key shorter than the circuit")
+    if blinders is not None and not zero_knowledge:
+        raise ValueError("blinders are only used with zero_knowledge=True")
+    if zero_knowledge:
+        if hasattr(ck, "lo"):
+            raise ValueError("zero-knowledge proofs are single-GPU")
+        if pk.verifier_key is None:
+            raise ValueError("commit the key first")
     if pk.verifier_key is None:
         pk.commit(ck)
     if isinstance(witnesses, DeviceVector):
@@ -462,9 +505,19 @@ def prove_batch(pk: ProverKey, ck: CommitKey, witnesses, public_inputs=None, bin
         B = len(witnesses)
     if B == 0:
         raise ValueError("empty batch")
+    if zero_knowledge:
+        if blinders is None:
+            bl = random_blinders(B)
+        else:
+            bl = np.ascontiguousarray(blinders, dtype=np.uint64)
+            if bl.shape != (B, _lib.PLONK_ZK_BLINDERS, 4):
+                raise ValueError(f"blinders must have the shape [{B}, {_lib.PLONK_ZK_BLINDERS}, 4]: one set per proof")
     own_ws = workspace is None
-    ws = pk.batch(B) if own_ws else workspace
+    ws = pk.batch(B, zero_knowledge=zero_knowledge) if own_ws else workspace
     try:
+        if zero_knowledge and not own_ws:
+            pk.enable_zk()
+            ws.enable_zk()
         if isinstance(witnesses, DeviceVector):
             d_wit = witnesses
         else:
@@ -499,8 +552,12 @@ def prove_batch(pk: ProverKey, ck: CommitKey, witnesses, public_inputs=None, bin
                 p_val[b] = val.ctypes.data_as(_lib.u64p)
         raws = (_lib.PlonkProof * B)()
         flags = 0 if bind_public_inputs else _lib.PLONK_UPSTREAM_TRANSCRIPT
-        ctx._check(ctx._lib.pm_plonk_prove_batch(ctx._h, pk._h, ws._h, ck._bases._h, B, d_wit._p, p_pos, p_val, counts,
-                                                 flags, raws))
+        if zero_knowledge:
+            ctx._check(ctx._lib.pm_plonk_prove_batch_zk(ctx._h, pk._h, ws._h, ck._bases._h, B, d_wit._p, p_pos, p_val, counts,
+                                                        flags, bl.ctypes.data_as(_lib.u64p), raws))
+        else:
+            ctx._check(ctx._lib.pm_plonk_prove_batch(ctx._h, pk._h, ws._h, ck._bases._h, B, d_wit._p, p_pos, p_val, counts,
+                                                     flags, raws))
     finally:
         if own_ws:
             ws.free()
