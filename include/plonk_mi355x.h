@@ -511,7 +511,7 @@ int pm_plonk_prove_dist(pm_ctx* ctx, const pm_dist* dist, pm_dist_key* key, cons
                         uint32_t flags, pm_plonk_proof* out);
 
 /* Every label string of the transcript, in message order, as "key=label" lines (a static string).  The labels are
- * restated from the published dusk-plonk 0.8 design and are PARITY-UNPINNED; they live in ONE table (csrc/prover.hip,
+ * restated from the published dusk-plonk 0.8 design and are PARITY-UNPINNED; they live in ONE table (csrc/prover_transcript.h,
  * namespace tl) that both the native prover and the Python verifier side read -- the single place to edit when
  * upstream vectors become available. */
 const char* pm_plonk_transcript_labels(void);
@@ -607,6 +607,17 @@ int pm_test_ntt_plan(uint32_t log_n, uint32_t batch, long tile_log, long max_rad
  * every partition's first bucket and log2 width.  table_window_bits 0 = bases without a window table. */
 int pm_test_msm_geometry(size_t n, long window_bits, uint32_t table_window_bits, uint32_t batch, uint32_t out[16],
                          uint32_t* part_of_bucket, uint32_t* first_bucket, uint32_t* width_bits);
+/* Pure host, no context: the scalars of the linearisation polynomial r (csrc/prover_rounds.h, the one copy all provers
+ * use) from the 17 evaluations in transcript order (pm_plonk_proof.evaluations; the last, r itself, is not read), the 9
+ * further values at z that r(z) needs (q_m, q_o, q_4, z, sigma_4, q_range, q_logic, q_fixed_group_add,
+ * q_variable_group_add) and the 10 challenges (pm_plonk_proof.challenges), all Montgomery.  Bit s of
+ * selector_present_mask: selector s (the order of pm_plonk_preprocess) is not identically zero; only the four widget
+ * selectors' bits matter.  out_count <= 12 terms in the order of the device's linear combination: out_coeffs[i] is the
+ * scalar in front of polynomial out_roles[i] = role << 8 | index -- role 2: z, 3: sigma_(index + 1), 4: selector index.
+ * out_r_z = r(z) = the sum of coefficient x value at z. */
+int pm_test_plonk_linearise(size_t n, const uint64_t (*evaluations)[4], const uint64_t (*extras)[4],
+                            const uint64_t (*challenges)[4], uint32_t selector_present_mask, uint64_t (*out_coeffs)[4],
+                            uint32_t* out_roles, uint32_t* out_count, uint64_t out_r_z[4]);
 
 #ifdef __cplusplus
 }

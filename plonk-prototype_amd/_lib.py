@@ -171,6 +171,7 @@ SIGNATURES = {
     "pm_test_msm_sizing": (C.c_int, [C.c_size_t, C.c_uint32, C.c_long, C.c_uint32, C.c_uint32, u64p]),
     "pm_test_msm_geometry": (C.c_int, [C.c_size_t, C.c_long, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32),
                                       C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "pm_test_plonk_linearise": (C.c_int, [C.c_size_t, u64p, u64p, u64p, C.c_uint32, u64p, u32p, u32p, u64p]),
 }
 
 PM_OK = 0

@@ -23,258 +23,7 @@
 #include <vector>
 
 #include "context.h"
-#include "host_field.h"
-
-namespace {
-using pm::host::HFp;
-using pm::host::HFr;
-typedef uint64_t u64;
-const pm::host::Field<4>& FRF() { return pm::host::FR(); }
-
-HFr fr_u64(u64 v) { return pm::host::from_u64(v, FRF()); }
-HFr fmul(const HFr& a, const HFr& b) { return pm::host::mul(a, b, FRF()); }
-HFr fadd(const HFr& a, const HFr& b) { return pm::host::add(a, b, FRF()); }
-HFr fsub(const HFr& a, const HFr& b) { return pm::host::sub(a, b, FRF()); }
-HFr finv(const HFr& a) { return pm::host::inv(a, FRF()); }
-HFr fpow(const HFr& a, u64 e) { return pm::host::pow(a, &e, 1, FRF()); }
-HFr fone() { return pm::host::one(FRF()); }
-HFr fneg(const HFr& a) { return fsub(pm::host::zero<4>(), a); }
-// Montgomery -> canonical limbs
-HFr fr_canonical(const HFr& a) {
-  HFr raw1 = pm::host::zero<4>();
-  raw1.l[0] = 1;
-  return fmul(a, raw1);
-}
-
-// ------------------------------------------------------------------ Merlin over STROBE-128
-struct Strobe128 {
-  static const int R = 166;
-  uint8_t st[200];
-  uint8_t pos = 0, pos_begin = 0, cur_flags = 0;
-  explicit Strobe128(const std::string& label) {
-    memset(st, 0, sizeof st);
-    const uint8_t head[6] = {1, R + 2, 1, 0, 1, 96};
-    memcpy(st, head, 6);
-    memcpy(st + 6, "STROBEv1.0.2", 12);
-    pm_keccak_f1600(st);
-    meta_ad((const uint8_t*)label.data(), label.size(), false);
-  }
-  void run_f() {
-    st[pos] ^= pos_begin;
-    st[pos + 1] ^= 0x04;
-    st[R + 1] ^= 0x80;
-    pm_keccak_f1600(st);
-    pos = 0;
-    pos_begin = 0;
-  }
-  void absorb(const uint8_t* d, size_t n) {
-    for (size_t i = 0; i < n; ++i) {
-      st[pos++] ^= d[i];
-      if (pos == R) run_f();
-    }
-  }
-  void squeeze(uint8_t* d, size_t n) {
-    for (size_t i = 0; i < n; ++i) {
-      d[i] = st[pos];
-      st[pos++] = 0;
-      if (pos == R) run_f();
-    }
-  }
-  void begin_op(uint8_t flags, bool more) {
-    if (more) return;                       // continued operation (same flags by construction here)
-    const uint8_t old_begin = pos_begin;
-    pos_begin = (uint8_t)(pos + 1);
-    cur_flags = flags;
-    const uint8_t hdr[2] = {old_begin, flags};
-    absorb(hdr, 2);
-    if ((flags & (4 | 32)) && pos != 0) run_f();   // C or K
-  }
-  void meta_ad(const uint8_t* d, size_t n, bool more) { begin_op(16 | 2, more); absorb(d, n); }
-  void ad(const uint8_t* d, size_t n, bool more) { begin_op(2, more); absorb(d, n); }
-  void prf(uint8_t* d, size_t n) { begin_op(1 | 2 | 4, false); squeeze(d, n); }
-};
-
-struct Transcript {
-  Strobe128 s;
-  explicit Transcript(const std::string& label) : s("Merlin v1.0") { append("dom-sep", (const uint8_t*)label.data(), label.size()); }
-  static void scalar_bytes(uint8_t b[32], const HFr& v) {
-    const HFr c = fr_canonical(v);
-    for (int i = 0; i < 32; ++i) b[i] = (uint8_t)(c.l[i / 8] >> (8 * (i % 8)));
-  }
-  void append(const char* label, const uint8_t* msg, size_t n) {
-    s.meta_ad((const uint8_t*)label, strlen(label), false);
-    uint8_t len[4] = {(uint8_t)n, (uint8_t)(n >> 8), (uint8_t)(n >> 16), (uint8_t)(n >> 24)};
-    s.meta_ad(len, 4, true);
-    s.ad(msg, n, false);
-  }
-  void append_u64(const char* label, u64 v) {
-    uint8_t b[8];
-    for (int i = 0; i < 8; ++i) b[i] = (uint8_t)(v >> (8 * i));
-    append(label, b, 8);
-  }
-  void append_commitment(const char* label, const u64 xy[12]) {
-    uint8_t out[48];
-    g1_compress(out, xy);
-    append(label, out, 48);
-  }
-  // 48-byte zcash compressed G1 (big-endian x; bit 7 compressed, bit 6 infinity, bit 5 = y > (p-1)/2)
-  static void g1_compress(uint8_t out[48], const u64 xy[12]) {
-    memset(out, 0, 48);
-    bool any = false;
-    for (int i = 0; i < 12; ++i) any = any || xy[i];
-    if (!any) {
-      out[0] = 0xC0;
-    } else {
-      HFp x, y, raw1 = pm::host::zero<6>();
-      memcpy(x.l, xy, 48);
-      memcpy(y.l, xy + 6, 48);
-      raw1.l[0] = 1;
-      x = pm::host::mul(x, raw1, pm::host::FP());
-      y = pm::host::mul(y, raw1, pm::host::FP());
-      for (int i = 0; i < 48; ++i) out[i] = (uint8_t)(x.l[(47 - i) / 8] >> (8 * ((47 - i) % 8)));
-      out[0] |= 0x80;
-      // y > (p - 1) / 2  <=>  2 y > p - 1  <=>  2 y >= p + 1 ... compare y with p - y
-      HFp ny = pm::host::sub(pm::host::zero<6>(), y, pm::host::FP());   // canonical limbs: p - y
-      if (pm::host::geq<6>(y.l, ny.l) && !pm::host::eq(y, ny)) out[0] |= 0x20;
-    }
-  }
-  void append_scalar(const char* label, const HFr& v) {
-    const HFr c = fr_canonical(v);
-    uint8_t b[32];
-    for (int i = 0; i < 32; ++i) b[i] = (uint8_t)(c.l[i / 8] >> (8 * (i % 8)));
-    append(label, b, 32);
-  }
-  // 64 challenge bytes as a little-endian integer mod r (BlsScalar::from_bytes_wide)
-  HFr challenge_scalar(const char* label) {
-    s.meta_ad((const uint8_t*)label, strlen(label), false);
-    uint8_t len[4] = {64, 0, 0, 0};
-    s.meta_ad(len, 4, true);
-    uint8_t b[64];
-    s.prf(b, 64);
-    const HFr k256 = fr_u64(256);
-    HFr acc = pm::host::zero<4>();
-    for (int i = 63; i >= 0; --i) acc = fadd(fmul(acc, k256), fr_u64(b[i]));
-    return acc;
-  }
-};
-
-void put(u64 dst[4], const HFr& v) { memcpy(dst, v.l, 32); }
-HFr get(const u64 src[4]) {
-  HFr r;
-  memcpy(r.l, src, 32);
-  return r;
-}
-char* at(void* base, size_t elems) { return (char*)base + 32 * elems; }
-
-// selector order of dusk's VerifierKey::seed_transcript (and of the ABI)
-enum { Q_M, Q_L, Q_R, Q_O, Q_C, Q_4, Q_ARITH, Q_RANGE, Q_LOGIC, Q_FIXED, Q_VAR, NSEL };
-const int SEL_SEED_ORDER[NSEL] = {Q_M, Q_L, Q_R, Q_O, Q_C, Q_4, Q_ARITH, Q_RANGE, Q_LOGIC, Q_VAR, Q_FIXED};
-
-// ================================================================================================================
-// THE transcript table: every label string and the order of every message of a proof's Fiat-Shamir transcript, in
-// the order they are absorbed / squeezed.  Restated from the published dusk-plonk 0.8 design (ref:Cargo.toml:19); the
-// crate is not in the reference tree and no upstream proof bytes exist here, so these strings are PARITY-UNPINNED:
-// byte-equality of a proof with dusk's stands or falls with them.  THIS IS THE SINGLE PLACE TO EDIT when upstream
-// vectors become available -- the prover below only refers to this table, and the verifier side in Python
-// (plonk-prototype_amd/prover.py: derive_challenges) reads the same table through pm_plonk_transcript_labels().
-// ================================================================================================================
-namespace tl {
-const char* const PROTOCOL = "plonk";                       // default Transcript::new(label)
-// VerifierKey::seed_transcript: the 11 selector commitments in SEL_SEED_ORDER (variable before fixed), the 4 sigmas
-const char* const SELECTORS[NSEL] = {"q_m", "q_l", "q_r", "q_o", "q_c", "q_4", "q_arith", "q_range", "q_logic",
-                                     "q_variable_group_add", "q_fixed_group_add"};
-const char* const SIGMAS[4] = {"left_sigma", "right_sigma", "out_sigma", "fourth_sigma"};
-// circuit_domain_sep(n)
-const char* const DOM_SEP = "dom-sep";
-const char* const DOM_SEP_VALUE = "circuit_size";
-const char* const CIRCUIT_SIZE = "n";
-// this library's public-input binding (flags = 0; absent with PM_PLONK_UPSTREAM_TRANSCRIPT): count, then (position, value)
-const char* const PI_LEN = "pi_len";
-const char* const PI_POS = "pi_pos";
-const char* const PI_VALUE = "pi";
-// round 1: the wire commitments
-const char* const WIRES[4] = {"w_l", "w_r", "w_o", "w_4"};
-// round 2: beta (re-absorbed under its own label), gamma, then the permutation commitment
-const char* const BETA = "beta";
-const char* const GAMMA = "gamma";
-const char* const PERM = "z";
-// round 3: the quotient's challenges, then the four quotient commitments
-const char* const ALPHA = "alpha";
-const char* const RANGE_SEP = "range separation challenge";
-const char* const LOGIC_SEP = "logic separation challenge";
-const char* const FIXED_SEP = "fixed base separation challenge";
-const char* const VAR_SEP = "variable base separation challenge";
-const char* const QUOTIENT[4] = {"t_1", "t_2", "t_3", "t_4"};
-// round 4: the evaluation challenge and the 17 evaluations in transcript order (pm_plonk_proof.evaluations)
-const char* const Z_CHALLENGE = "z";
-const char* const EVALS[17] = {"a_eval", "b_eval", "c_eval", "d_eval", "a_next_eval", "b_next_eval", "d_next_eval",
-                               "left_sig_eval", "right_sig_eval", "out_sig_eval", "q_arith_eval", "q_c_eval", "q_l_eval",
-                               "q_r_eval", "perm_eval", "t_eval", "r_eval"};
-// round 5: the two aggregation challenges (same label twice), then the opening commitments; the verifier's batch challenge
-const char* const AGGREGATE = "aggregate_witness";
-const char* const W_Z = "w_z";
-const char* const W_ZW = "w_z_w";
-const char* const BATCH = "batch";
-}  // namespace tl
-const char* const* const SEL_LABELS = tl::SELECTORS;
-const char* const* const SIGMA_LABELS = tl::SIGMAS;
-
-// ---- the widgets' linearisation scalars: the same identities as plonk_rounds.hip's quotient kernel,
-// on the opening evaluations (widget::*::ProverKey::compute_linearisation)
-HFr small(u64 v) { return fr_u64(v); }
-HFr wdelta(const HFr& f) {
-  return fmul(fmul(fmul(f, fsub(f, small(1))), fsub(f, small(2))), fsub(f, small(3)));
-}
-HFr edwards_d() { return fneg(fmul(small(10240), finv(small(10241)))); }
-struct RowEvals {
-  HFr a, b, c, d, an, bn, dn, q_l, q_r, q_c;
-};
-HFr widget_range(const HFr& sep, const RowEvals& e) {
-  const HFr k = fmul(sep, sep), k2 = fmul(k, k), k3 = fmul(k2, k), four = small(4);
-  HFr t = wdelta(fsub(e.c, fmul(four, e.d)));
-  t = fadd(t, fmul(wdelta(fsub(e.b, fmul(four, e.c))), k));
-  t = fadd(t, fmul(wdelta(fsub(e.a, fmul(four, e.b))), k2));
-  t = fadd(t, fmul(wdelta(fsub(e.dn, fmul(four, e.a))), k3));
-  return fmul(t, sep);
-}
-HFr widget_logic(const HFr& sep, const RowEvals& e) {
-  const HFr k = fmul(sep, sep), k2 = fmul(k, k), k3 = fmul(k2, k), k4 = fmul(k2, k2), four = small(4);
-  const HFr qa = fsub(e.an, fmul(four, e.a)), qb = fsub(e.bn, fmul(four, e.b)), qd = fsub(e.dn, fmul(four, e.d));
-  const HFr s = fadd(qa, qb), w = e.c;
-  HFr in = fadd(fsub(fmul(four, w), fmul(small(18), s)), small(81));
-  in = fadd(fmul(w, in), fmul(small(18), fadd(fmul(qa, qa), fmul(qb, qb))));
-  in = fadd(fsub(in, fmul(small(81), s)), small(83));
-  const HFr f = fmul(w, in);
-  const HFr ee = fsub(fmul(small(3), fadd(s, qd)), fadd(f, f));
-  const HFr bb = fmul(e.q_c, fsub(fmul(small(9), qd), fmul(small(3), s)));
-  HFr t = wdelta(qa);
-  t = fadd(t, fmul(wdelta(qb), k));
-  t = fadd(t, fmul(wdelta(qd), k2));
-  t = fadd(t, fmul(fsub(w, fmul(qa, qb)), k3));
-  t = fadd(t, fmul(fadd(bb, ee), k4));
-  return fmul(t, sep);
-}
-HFr widget_fixed(const HFr& sep, const RowEvals& e) {
-  const HFr k = fmul(sep, sep), k2 = fmul(k, k), k3 = fmul(k2, k), one = fone();
-  const HFr bit = fsub(e.dn, fadd(e.d, e.d));
-  HFr t = fmul(fmul(bit, fsub(bit, one)), fadd(bit, one));
-  const HFr ya = fadd(fmul(fmul(bit, bit), fsub(e.q_r, one)), one), xa = fmul(e.q_l, bit);
-  t = fadd(t, fmul(fsub(fmul(bit, e.q_c), e.c), k));
-  const HFr dxy = fmul(fmul(fmul(e.c, e.a), e.b), edwards_d());
-  t = fadd(t, fmul(fsub(fadd(e.an, fmul(e.an, dxy)), fadd(fmul(e.a, ya), fmul(e.b, xa))), k2));
-  t = fadd(t, fmul(fsub(fsub(e.bn, fmul(e.bn, dxy)), fadd(fmul(e.b, ya), fmul(e.a, xa))), k3));
-  return fmul(t, sep);
-}
-HFr widget_var(const HFr& sep, const RowEvals& e) {
-  const HFr k = fmul(sep, sep), k2 = fmul(k, k);
-  const HFr y1x2 = fmul(e.b, e.c), y1y2 = fmul(e.b, e.d), x1x2 = fmul(e.a, e.c);
-  HFr t = fsub(fmul(e.a, e.d), e.dn);
-  const HFr dd = fmul(fmul(e.dn, y1x2), edwards_d());
-  t = fadd(t, fmul(fsub(fadd(e.dn, y1x2), fadd(e.an, fmul(e.an, dd))), k));
-  t = fadd(t, fmul(fsub(fadd(y1y2, x1x2), fsub(e.bn, fmul(e.bn, dd))), k2));
-  return fmul(t, sep);
-}
-}  // namespace
+#include "prover_rounds.h"
 
 // Zero-knowledge mode (pm_plonk_key_enable_zk): the second 4n coset 7 w_8n H_4n of the key and a
 // per-proof workspace whose coefficient vectors have the padded stride S = n + ZK_PAD (zero tails).
@@ -333,6 +82,14 @@ static int pm_stream_join(pm_ctx* ctx, hipStream_t side, hipEvent_t ev) {
     int rc_ = (call);           \
     if (rc_ != PM_OK) return rc_; \
   } while (0)
+
+// the flags of a prove call, on every path
+static int check_flags(pm_ctx* ctx, uint32_t flags) {
+  if (flags & ~(PM_PLONK_BIND_PUBLIC_INPUTS | PM_PLONK_UPSTREAM_TRANSCRIPT)) return pm::set_err(ctx, PM_ERR_BAD_ARG, "unknown flags");
+  if (flags == (PM_PLONK_BIND_PUBLIC_INPUTS | PM_PLONK_UPSTREAM_TRANSCRIPT))
+    return pm::set_err(ctx, PM_ERR_BAD_ARG, "PM_PLONK_BIND_PUBLIC_INPUTS and PM_PLONK_UPSTREAM_TRANSCRIPT exclude each other");
+  return PM_OK;
+}
 
 extern "C" void pm_plonk_key_free(pm_ctx* ctx, pm_prover_key* pk) {
   if (!pk) return;
@@ -440,15 +197,7 @@ extern "C" int pm_plonk_preprocess(pm_ctx* ctx, const uint64_t* const selectors[
   if (!rc) rc = pm_fr_ntt_dev(ctx, tmp, n, n, pk->l1_coset, 4 * n, lg + 2, 1, PM_NTT_COSET, nullptr);
   if (!rc) rc = pm_sync(ctx);
   if (tmp) (void)pm_dev_free(ctx, tmp);
-  if (!rc) {
-    // Z_H(g w4^i) = g^n (w4^n)^i - 1, period 4
-    const HFr gn = fpow(g, n), i4 = fpow(omega4, n);
-    HFr p = one;
-    for (int k = 0; k < 4; ++k) {
-      pk->zh_inv[k] = finv(fsub(fmul(gn, p), one));
-      p = fmul(p, i4);
-    }
-  }
+  if (!rc) zh_inv_period4(g, omega4, n, pk->zh_inv);
   if (!rc && hipStreamCreateWithFlags(&pk->side, hipStreamNonBlocking) != hipSuccess) rc = PM_ERR_HIP;
   if (!rc && hipEventCreateWithFlags(&pk->ev_main, hipEventDisableTiming) != hipSuccess) rc = PM_ERR_HIP;
   if (!rc && hipEventCreateWithFlags(&pk->ev_side, hipEventDisableTiming) != hipSuccess) rc = PM_ERR_HIP;
@@ -600,12 +349,6 @@ static int check_slice_cover(pm_ctx* ctx, const pm_bases* ck, const Shard& sh, s
 }
 
 static int key_commit_body(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, const Shard& shard,
-                           const char* transcript_label, uint64_t (*vk_out)[12]);
-static int key_commit_impl(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, const Shard& shard,
-                           const char* transcript_label, uint64_t (*vk_out)[12]) {
-  return shard_leave(ctx, shard, key_commit_body(ctx, pk, ck, shard, transcript_label, vk_out));
-}
-static int key_commit_body(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, const Shard& shard,
                            const char* transcript_label, uint64_t (*vk_out)[12]) {
   if (!ctx || !pk || !ck) return PM_ERR_BAD_ARG;
   const size_t n = pk->n;
@@ -614,19 +357,17 @@ static int key_commit_body(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, c
   // the verifier key: commitments to the 11 selector and the 4 sigma polynomials
   PK_TRY(commit_batch(ctx, ck, shard, pk->sel_coeffs, n, n, NSEL, &pk->vk[0]));
   PK_TRY(commit_batch(ctx, ck, shard, pk->sigma_coeffs, n, n, 4, &pk->vk[NSEL]));
-  // Prover::preprocess: Transcript::new(label), VerifierKey::seed_transcript, circuit_domain_sep(n)
-  Transcript ts(transcript_label ? transcript_label : tl::PROTOCOL);
-  for (int i = 0; i < NSEL; ++i) ts.append_commitment(SEL_LABELS[i], pk->vk[SEL_SEED_ORDER[i]]);
-  for (int j = 0; j < 4; ++j) ts.append_commitment(SIGMA_LABELS[j], pk->vk[NSEL + j]);
-  ts.append(tl::DOM_SEP, (const uint8_t*)tl::DOM_SEP_VALUE, strlen(tl::DOM_SEP_VALUE));
-  ts.append_u64(tl::CIRCUIT_SIZE, n);
-  pk->base = ts;
+  pk->base = key_transcript(transcript_label, pk->vk, n);
   pk->committed = true;
   if (vk_out) memcpy(vk_out, pk->vk, sizeof pk->vk);
   return PM_OK;
 }
+static int key_commit_impl(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, const Shard& shard,
+                           const char* transcript_label, uint64_t (*vk_out)[12]) {
+  return shard_leave(ctx, shard, key_commit_body(ctx, pk, ck, shard, transcript_label, vk_out));
+}
 
-// The table above as text, one "key=label" line per entry in transcript order (the verifier side in Python reads it:
+// The label table of prover_transcript.h as text, one "key=label" line per entry in transcript order (the verifier side in Python reads it:
 // one table for both sides).
 extern "C" const char* pm_plonk_transcript_labels(void) {
   static const std::string text = [] {
@@ -678,22 +419,11 @@ extern "C" int pm_plonk_key_commit_sharded(pm_ctx* ctx, pm_prover_key* key, cons
   return key_commit_impl(ctx, key, commit_key_slice, sh, transcript_label, verifier_key_out);
 }
 
-namespace {
-struct BusyGuard {   // one proof at a time per key: the key owns the per-proof workspace
-  pm_prover_key* pk;
-  bool ok;
-  explicit BusyGuard(pm_prover_key* k) : pk(k), ok(!k->busy.exchange(true)) {}
-  ~BusyGuard() {
-    if (ok) pk->busy.store(false);
-  }
-};
-}  // namespace
-
 // sum_i L_i = powers[0] and sum_i w^i L_i = powers[1]: two MSMs over the Lagrange key (scalars 1 and the key's roots of
 // unity) against the first two points of the commit key.  Together they pin the key to the commit key's tau.
 extern "C" int pm_plonk_key_set_lagrange(pm_ctx* ctx, pm_prover_key* key, const pm_bases* commit_key, const pm_bases* lagrange) {
   if (!ctx || !key) return PM_ERR_BAD_ARG;
-  BusyGuard guard(key);
+  Busy guard(key->busy);
   if (!guard.ok) return PM_ERR_BUSY;
   if (!lagrange) {
     key->lagrange = nullptr;
@@ -742,7 +472,7 @@ extern "C" int pm_plonk_key_set_lagrange(pm_ctx* ctx, pm_prover_key* key, const 
 extern "C" int pm_plonk_key_enable_zk(pm_ctx* ctx, pm_prover_key* pk, size_t* added_bytes) {
   if (!ctx || !pk) return PM_ERR_BAD_ARG;
   if (!pk->committed) return pm::set_err(ctx, PM_ERR_BAD_ARG, "pm_plonk_key_commit first");
-  BusyGuard guard(pk);
+  Busy guard(pk->busy);
   if (!guard.ok) return PM_ERR_BUSY;
   if (pk->zk) {
     if (added_bytes) *added_bytes = pk->zk->bytes;
@@ -796,13 +526,7 @@ extern "C" int pm_plonk_key_enable_zk(pm_ctx* ctx, pm_prover_key* pk, size_t* ad
   if (!rc) rc = pm_fr_ntt_dev(ctx, at(zs->coset2, (NSEL + 4) * n), n, n, zs->l1_coset2, 4 * n, lg + 2, 1, PM_NTT_COSET, nullptr);
   if (!rc) rc = pm_sync(ctx);
   if (!rc) {
-    // Z_H(7 w_8n w_4n^i) = (7 w_8n)^n (w_4n^n)^i - 1, period 4; s = 7^4n
-    const HFr gn = fpow(g2, n), i4 = fpow(omega4, n);
-    HFr p = one;
-    for (int k = 0; k < 4; ++k) {
-      zs->zh_inv2[k] = finv(fsub(fmul(gn, p), one));
-      p = fmul(p, i4);
-    }
+    zh_inv_period4(g2, omega4, n, zs->zh_inv2);   // the second coset 7 w_8n <w_4n>; s = 7^4n
     zs->inv2 = finv(fr_u64(2));
     zs->inv2s = finv(fmul(fr_u64(2), fpow(g, 4 * n)));
   }
@@ -815,6 +539,20 @@ extern "C" int pm_plonk_key_enable_zk(pm_ctx* ctx, pm_prover_key* pk, size_t* ad
   pk->zk = zs;
   if (added_bytes) *added_bytes = zs->bytes;
   return PM_OK;
+}
+
+// (position, value) pairs of one statement's public inputs without repeats -- a repeated position keeps its last value --
+// appended to hp (as offset + position) and hv
+static void compact_public_inputs(const uint64_t* pos, const uint64_t* vals, size_t n_pi, uint64_t offset,
+                                  std::vector<unsigned long long>& hp, std::vector<uint64_t>& hv) {
+  std::unordered_map<uint64_t, size_t> last;
+  last.reserve(2 * n_pi);
+  for (size_t i = 0; i < n_pi; ++i) last[pos[i]] = i;
+  for (size_t i = 0; i < n_pi; ++i) {
+    if (last[pos[i]] != i) continue;
+    hp.push_back(offset + pos[i]);
+    hv.insert(hv.end(), vals + 4 * i, vals + 4 * i + 4);
+  }
 }
 
 // pi_evals <- 0, then the sparse public inputs (a repeated position keeps its last value).  A handful goes up
@@ -835,18 +573,9 @@ static int scatter_public_inputs(pm_ctx* ctx, pm_prover_key* pk, const uint64_t*
       PM_HIP(ctx, hipMemcpyAsync(at(pk->pi_evals, pos[i]), vals + 4 * i, 32, hipMemcpyHostToDevice, ctx->stream));
     return PM_OK;
   }
-  std::unordered_map<uint64_t, size_t> last;
-  last.reserve(2 * n_pi);
-  for (size_t i = 0; i < n_pi; ++i) last[pos[i]] = i;
   std::vector<unsigned long long> hp;
   std::vector<uint64_t> hv;
-  hp.reserve(last.size());
-  hv.reserve(4 * last.size());
-  for (size_t i = 0; i < n_pi; ++i) {
-    if (last[pos[i]] != i) continue;
-    hp.push_back(pos[i]);
-    hv.insert(hv.end(), vals + 4 * i, vals + 4 * i + 4);
-  }
+  compact_public_inputs(pos, vals, n_pi, 0, hp, hv);
   const size_t cnt = hp.size();   // <= n: fits the n-element scratch arrays
   PM_HIP(ctx, hipMemcpyAsync(pk->num, hv.data(), cnt * 32, hipMemcpyHostToDevice, ctx->stream));
   PM_HIP(ctx, hipMemcpyAsync(pk->den, hp.data(), cnt * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -857,72 +586,44 @@ static int scatter_public_inputs(pm_ctx* ctx, pm_prover_key* pk, const uint64_t*
   return PM_OK;
 }
 
-static int prove_body(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, const Shard& shard, const void* d_witness,
-                      const uint64_t* pi_positions, const uint64_t* pi_values, size_t n_pi, uint32_t flags,
-                      const uint64_t (*blinders)[4], pm_plonk_proof* out);
-static int prove_impl(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, const Shard& shard, const void* d_witness,
-                      const uint64_t* pi_positions, const uint64_t* pi_values, size_t n_pi, uint32_t flags,
-                      const uint64_t (*blinders)[4], pm_plonk_proof* out) {
-  if (ctx && ctx->marks_on) ctx->marks.clear();
-  pm::host_mark(ctx, "prove: start");
-  const int rc = shard_leave(ctx, shard, prove_body(ctx, pk, ck, shard, d_witness, pi_positions, pi_values, n_pi, flags, blinders, out));
-  pm::host_mark(ctx, "prove: end");
-  if (ctx && ctx->marks_on && !ctx->marks.empty()) {   // PM_HOST_MARKS=1: where the host's time between the kernels goes
-    const double t0 = ctx->marks.front().second;
-    double prev = t0;
-    for (const auto& mk : ctx->marks) {
-      fprintf(stderr, "[host] %9.1f us  +%7.1f  %s\n", mk.second - t0, mk.second - prev, mk.first);
-      prev = mk.second;
-    }
-  }
-  return rc;
-}
-
-extern "C" int pm_plonk_prove_sharded(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck_slice, size_t first_coefficient,
-                                      const void* d_witness, const uint64_t* pi_positions, const uint64_t* pi_values,
-                                      size_t n_pi, uint32_t flags, pm_exchange_fn exchange, void* user,
-                                      pm_plonk_proof* out) {
-  Shard sh;
-  sh.on = true;
-  sh.lo = first_coefficient;
-  sh.fn = exchange;
-  sh.user = user;
-  sh.expect = 4;
-  return prove_impl(ctx, pk, ck_slice, sh, d_witness, pi_positions, pi_values, n_pi, flags, nullptr, out);
-}
-
-extern "C" int pm_plonk_prove(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, const void* d_witness,
-                              const uint64_t* pi_positions, const uint64_t* pi_values, size_t n_pi, uint32_t flags,
-                              pm_plonk_proof* out) {
-  return prove_impl(ctx, pk, ck, Shard(), d_witness, pi_positions, pi_values, n_pi, flags, nullptr, out);
-}
-
-extern "C" int pm_plonk_prove_zk(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, const void* d_witness,
-                                 const uint64_t* pi_positions, const uint64_t* pi_values, size_t n_pi, uint32_t flags,
-                                 const uint64_t (*blinders)[4], pm_plonk_proof* out) {
-  if (!blinders) return PM_ERR_BAD_ARG;
-  return prove_impl(ctx, pk, ck, Shard(), d_witness, pi_positions, pi_values, n_pi, flags, blinders, out);
-}
-
-// Blinded wire commitments over a Lagrange key: [w] from the witness values, plus the blinder's
+// Blinded wire commitments over a Lagrange key, for `count` vectors: [w] from the witness values, plus the blinder's
 // sum_i b_i ([tau^(n+i)] - [tau^i]).  The blinded coefficients hold b_i at n + i, so two MSMs of 3 points take those same
-// scalars, over the commit key at offset n and at offset 0, and the second result is negated before the host fold.
-static int commit_lagrange_zk(pm_ctx* ctx, const pm_bases* lag, const pm_bases* ck, const void* d_witness, const void* wc,
-                              size_t n, size_t S, u64 (*out_xy)[12]) {
-  u64 xyz[3][4 * 18], sum[4][18];
-  PK_TRY(pm_g1_msm_batch_dev(ctx, lag, 0, n, d_witness, n, 4, PM_SCALAR_MONTGOMERY, xyz[0], nullptr));
-  PK_TRY(pm_g1_msm_batch_dev(ctx, ck, n, 3, at((void*)wc, n), S, 4, PM_SCALAR_MONTGOMERY, xyz[1], nullptr));
-  PK_TRY(pm_g1_msm_batch_dev(ctx, ck, 0, 3, at((void*)wc, n), S, 4, PM_SCALAR_MONTGOMERY, xyz[2], nullptr));
-  for (int w = 0; w < 4; ++w) {
+// scalars, over the commit key at offset n and at offset 0, and the second result is negated before the host fold.  Passes of
+// at most 64 vectors, one host fold per vector, one affine conversion.  scratch: 72 words per vector.
+static int commit_lagrange_zk(pm_ctx* ctx, const pm_bases* lag, const pm_bases* ck, const void* d_wit, const void* coeffs, size_t n,
+                              size_t S, uint32_t count, u64* scratch, u64 (*out_xy)[12]) {
+  u64* part[3] = {scratch, scratch + 18 * (size_t)count, scratch + 36 * (size_t)count};
+  u64* sum = scratch + 54 * (size_t)count;
+  for (uint32_t v0 = 0; v0 < count; v0 += 64) {
+    const uint32_t k = std::min<uint32_t>(64, count - v0);
+    const void* tails = at(coeffs, (size_t)v0 * S + n);
+    PK_TRY(pm_g1_msm_batch_dev(ctx, lag, 0, n, at(d_wit, (size_t)v0 * n), n, k, PM_SCALAR_MONTGOMERY, part[0] + 18 * (size_t)v0, nullptr));
+    PK_TRY(pm_g1_msm_batch_dev(ctx, ck, n, 3, tails, S, k, PM_SCALAR_MONTGOMERY, part[1] + 18 * (size_t)v0, nullptr));
+    PK_TRY(pm_g1_msm_batch_dev(ctx, ck, 0, 3, tails, S, k, PM_SCALAR_MONTGOMERY, part[2] + 18 * (size_t)v0, nullptr));
+  }
+  for (uint32_t v = 0; v < count; ++v) {
     u64 parts[3][18];
-    for (int k = 0; k < 3; ++k) memcpy(parts[k], xyz[k] + 18 * w, sizeof parts[k]);
+    for (int k = 0; k < 3; ++k) memcpy(parts[k], part[k] + 18 * (size_t)v, sizeof parts[k]);
     HFp y;
     memcpy(y.l, parts[2] + 6, 48);
     y = pm::host::sub(pm::host::zero<6>(), y, pm::host::FP());   // -P = (X, -Y, Z)
     memcpy(parts[2] + 6, y.l, 48);
-    PK_TRY(pm_g1_fold(&parts[0][0], 3, sum[w]));
+    PK_TRY(pm_g1_fold(&parts[0][0], 3, sum + 18 * (size_t)v));
   }
-  return pm_g1_to_affine_batch(&sum[0][0], 4, &out_xy[0][0], nullptr);
+  return pm_g1_to_affine_batch(sum, count, &out_xy[0][0], nullptr);
+}
+
+// The key on the first 4n coset 7 H_4n, and (zero-knowledge mode) on the second, 7 w_8n H_4n
+static QuotientTables key_first_coset(const pm_prover_key* pk) {
+  QuotientTables t{{}, pk->sigma_coset, 4 * pk->n, pk->l1_coset, pk->x4, pk->zh_inv};
+  for (int s = 0; s < NSEL; ++s) t.sel[s] = pk->sel_coset[s];   // q_arith: nullptr when q_arith = 1
+  return t;
+}
+static QuotientTables key_second_coset(const pm_prover_key* pk) {
+  const ZkState* zs = pk->zk;
+  QuotientTables t{{}, zs->sigma_coset2, 4 * pk->n, zs->l1_coset2, zs->x2, zs->zh_inv2};
+  for (int s = 0; s < NSEL; ++s) t.sel[s] = zs->sel_coset2[s];
+  return t;
 }
 
 static int prove_body(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, const Shard& shard, const void* d_witness,
@@ -930,13 +631,12 @@ static int prove_body(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, const 
                       const uint64_t (*blinders)[4], pm_plonk_proof* out) {
   if (!ctx || !pk || !ck || !d_witness || !out) return PM_ERR_BAD_ARG;
   if (n_pi && (!pi_positions || !pi_values)) return PM_ERR_BAD_ARG;
-  if (flags & ~(PM_PLONK_BIND_PUBLIC_INPUTS | PM_PLONK_UPSTREAM_TRANSCRIPT)) return PM_ERR_BAD_ARG;
-  if (flags == (PM_PLONK_BIND_PUBLIC_INPUTS | PM_PLONK_UPSTREAM_TRANSCRIPT)) return PM_ERR_BAD_ARG;   // the two modes exclude each other
+  PK_TRY(check_flags(ctx, flags));
   if (!pk->committed) return PM_ERR_BAD_ARG;   // pm_plonk_key_commit first: the transcript starts from the verifier key
   if (blinders)
     for (int i = 0; i < PM_PLONK_ZK_BLINDERS; ++i)
       if (pm::host::geq<4>(blinders[i], FRF().m)) return pm::set_err(ctx, PM_ERR_BAD_ARG, "a blinder is not below r");
-  BusyGuard guard(pk);
+  Busy guard(pk->busy);
   if (!guard.ok) return PM_ERR_BUSY;
   const size_t n = pk->n;
   const uint32_t lg = pk->log_n;
@@ -982,17 +682,8 @@ static int prove_body(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, const 
   };
   for (size_t i = 0; i < n_pi; ++i)
     if (pi_positions[i] >= n) return PM_ERR_LENGTH;
-  Transcript ts = pk->base;
-  if (!(flags & PM_PLONK_UPSTREAM_TRANSCRIPT)) {
-    // the default; not in dusk-plonk 0.8.2 (its transcript never sees the public inputs): binds the statement to
-    // the challenges so that it cannot be chosen after them
-    ts.append_u64(tl::PI_LEN, n_pi);
-    for (size_t i = 0; i < n_pi; ++i) {
-      ts.append_u64(tl::PI_POS, pi_positions[i]);
-      ts.append_scalar(tl::PI_VALUE, get(pi_values + 4 * i));
-    }
-  }
-  const HFr one = fone();
+  ProofRounds pr(pk->base);
+  pr.begin(flags, pi_positions, pi_values, n_pi);
   // a Lagrange-form key commits the wires from their values on H: the same group elements (no blinding), so the same proof
   const pm_bases* lag = shard.on ? nullptr : pk->lagrange;
   if (lag && ck != pk->lagrange_ck) return PM_ERR_BAD_ARG;   // checked against another commit key
@@ -1013,8 +704,12 @@ static int prove_body(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, const 
     PK_TRY(pm_fr_ntt_dev(ctx, wc, wlen, S, pk->coset, 4 * n, lg + 2, 4, PM_NTT_COSET, side));
     PK_TRY(pm_fr_ntt_dev(ctx, pi_coeffs, wlen, S, at(pk->coset, 4 * n * 5), 4 * n, lg + 2, 1, PM_NTT_COSET, side));
     if (zs) PK_TRY(second_coset({0, 1, 2, 3, 5}, side));
-    if (zs) PK_TRY(commit_lagrange_zk(ctx, lag, ck, d_witness, wc, n, S, &out->commitments[0]));
-    else PK_TRY(commit_batch(ctx, lag, shard, d_witness, n, n, 4, &out->commitments[0]));
+    if (zs) {
+      u64 scratch[72 * 4];
+      PK_TRY(commit_lagrange_zk(ctx, lag, ck, d_witness, wc, n, S, 4, scratch, &out->commitments[0]));
+    } else {
+      PK_TRY(commit_batch(ctx, lag, shard, d_witness, n, n, 4, &out->commitments[0]));
+    }
   } else {
     PK_TRY(pm_fr_ntt_dev(ctx, d_witness, n, n, wc, S, lg, 4, PM_NTT_INVERSE, nullptr));
     if (zs) PK_TRY(blind(0, 4, nullptr));
@@ -1030,22 +725,12 @@ static int prove_body(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, const 
     }
     PK_TRY(commit_batch(ctx, ck, shard, wc, wlen, S, 4, &out->commitments[0]));
   }
-  for (int j = 0; j < 4; ++j) ts.append_commitment(tl::WIRES[j], out->commitments[j]);
+  pr.absorb_wires(&out->commitments[0]);
   // ---- round 2 --------------------------------------------------------------------------------
   pm::host_mark(ctx, "round 2");
-  const HFr beta = ts.challenge_scalar(tl::BETA);
-  ts.append_scalar(tl::BETA, beta);
-  const HFr gamma = ts.challenge_scalar(tl::GAMMA);
+  pr.draw_round2();
   pm_plonk_perm_args pa;
-  memset(&pa, 0, sizeof pa);
-  for (int j = 0; j < 4; ++j) {
-    pa.wires[j] = at((void*)d_witness, j * n);
-    pa.sigmas[j] = at(pk->sigma_evals, j * n);
-  }
-  pa.roots = pk->roots;
-  put(pa.beta, beta);
-  put(pa.gamma, gamma);
-  for (int j = 0; j < 3; ++j) put(pa.k[j], pk->k[j]);
+  fill_perm_args(pa, d_witness, n, pk->sigma_evals, n, pk->roots, pk->k, pr.ch[C_BETA], pr.ch[C_GAMMA]);
   PK_TRY(pm_plonk_perm_terms_dev(ctx, &pa, n, pk->num, pk->den, nullptr));
   PK_TRY(pm::fr_batch_inverse_mul(ctx, pk->den, pk->num, n, nullptr));       // den <- num / den (r06: one kernel, was two)
   PK_TRY(pm_fr_prefix_product_dev(ctx, pk->den, n, pk->num, nullptr));       // num <- z on H
@@ -1057,45 +742,13 @@ static int prove_body(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, const 
   PK_TRY(pm_fr_ntt_dev(ctx, z_coeffs, wlen, S, at(pk->coset, 4 * n * 4), 4 * n, lg + 2, 1, PM_NTT_COSET, side));
   if (zs) PK_TRY(second_coset({4}, side));
   PK_TRY(commit_batch(ctx, ck, shard, z_coeffs, wlen, S, 1, &out->commitments[4]));
-  ts.append_commitment(tl::PERM, out->commitments[4]);
+  pr.absorb_perm(out->commitments[4]);
   // ---- round 3 --------------------------------------------------------------------------------
   pm::host_mark(ctx, "round 3");
-  const HFr alpha = ts.challenge_scalar(tl::ALPHA);
-  const HFr range_sep = ts.challenge_scalar(tl::RANGE_SEP);
-  const HFr logic_sep = ts.challenge_scalar(tl::LOGIC_SEP);
-  const HFr fixed_sep = ts.challenge_scalar(tl::FIXED_SEP);
-  const HFr var_sep = ts.challenge_scalar(tl::VAR_SEP);
+  pr.draw_round3();
   PK_TRY(pm_stream_join(ctx, side, pk->ev_side));   // the wire, PI and z coset forms are ready
   pm_plonk_quotient_args qa;
-  memset(&qa, 0, sizeof qa);
-  for (int j = 0; j < 4; ++j) {
-    qa.wires[j] = at(pk->coset, 4 * n * j);
-    qa.sigmas[j] = at(pk->sigma_coset, 4 * n * j);
-  }
-  qa.z = at(pk->coset, 4 * n * 4);
-  qa.pi = at(pk->coset, 4 * n * 5);
-  qa.q_m = pk->sel_coset[Q_M];
-  qa.q_l = pk->sel_coset[Q_L];
-  qa.q_r = pk->sel_coset[Q_R];
-  qa.q_o = pk->sel_coset[Q_O];
-  qa.q_c = pk->sel_coset[Q_C];
-  qa.q_4 = pk->sel_coset[Q_4];
-  qa.q_arith = pk->sel_coset[Q_ARITH];            // nullptr when q_arith = 1
-  qa.q_range = pk->sel_coset[Q_RANGE];
-  qa.q_logic = pk->sel_coset[Q_LOGIC];
-  qa.q_fixed_group_add = pk->sel_coset[Q_FIXED];
-  qa.q_variable_group_add = pk->sel_coset[Q_VAR];
-  qa.l1 = pk->l1_coset;
-  qa.x = pk->x4;
-  put(qa.alpha, alpha);
-  put(qa.beta, beta);
-  put(qa.gamma, gamma);
-  put(qa.range_sep, range_sep);
-  put(qa.logic_sep, logic_sep);
-  put(qa.fixed_sep, fixed_sep);
-  put(qa.var_sep, var_sep);
-  for (int j = 0; j < 3; ++j) put(qa.k[j], pk->k[j]);
-  for (int j = 0; j < 4; ++j) put(qa.zh_inv[j], pk->zh_inv[j]);
+  fill_quotient_args(qa, key_first_coset(pk), pk->coset, 4 * n, at(pk->coset, 4 * n * 4), at(pk->coset, 4 * n * 5), pk->k, pr.ch);
   void* const t_coeffs = zs ? zs->t : pk->t;   // t_1..t_4 at stride S
   if (!zs) {
     PK_TRY(pm_plonk_quotient_dev(ctx, &qa, n, pk->t, nullptr));
@@ -1104,20 +757,8 @@ static int prove_body(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, const 
   } else {
     // deg t' <= 4n + 9: the same kernel on the second coset 7 w_8n H_4n gives t' mod (X^4n + s) beside t' mod (X^4n - s)
     PK_TRY(pm_plonk_quotient_dev(ctx, &qa, n, zs->ab, nullptr));
-    pm_plonk_quotient_args q2 = qa;
-    for (int j = 0; j < 4; ++j) {
-      q2.wires[j] = at(zs->coset2, 4 * n * j);
-      q2.sigmas[j] = at(zs->sigma_coset2, 4 * n * j);
-    }
-    q2.z = at(zs->coset2, 4 * n * 4);
-    q2.pi = at(zs->coset2, 4 * n * 5);
-    const void** sel2[NSEL] = {&q2.q_m, &q2.q_l, &q2.q_r, &q2.q_o, &q2.q_c, &q2.q_4, &q2.q_arith, &q2.q_range, &q2.q_logic,
-                               &q2.q_fixed_group_add, &q2.q_variable_group_add};
-    for (int s_ = 0; s_ < NSEL; ++s_) *sel2[s_] = zs->sel_coset2[s_];
-    q2.l1 = zs->l1_coset2;
-    q2.x = zs->x2;
-    for (int j = 0; j < 4; ++j) put(q2.zh_inv[j], zs->zh_inv2[j]);
-    PK_TRY(pm_plonk_quotient_dev(ctx, &q2, n, at(zs->ab, 4 * n), nullptr));
+    fill_quotient_args(qa, key_second_coset(pk), zs->coset2, 4 * n, at(zs->coset2, 4 * n * 4), at(zs->coset2, 4 * n * 5), pk->k, pr.ch);
+    PK_TRY(pm_plonk_quotient_dev(ctx, &qa, n, at(zs->ab, 4 * n), nullptr));
     PK_TRY(pm_fr_ntt_dev(ctx, zs->ab, 4 * n, 4 * n, zs->ab, 4 * n, lg + 2, 2, PM_NTT_INVERSE | PM_NTT_COSET, nullptr));
     u64 inv2[4], inv2s[4], tb[3][4];
     put(inv2, zs->inv2);
@@ -1126,154 +767,79 @@ static int prove_body(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, const 
     PK_TRY(pm::zk_combine(ctx, zs->ab, zs->w8, n, S, inv2, inv2s, tb, zs->t, ctx->stream));
     PK_TRY(commit_batch(ctx, ck, shard, zs->t, n + pm::ZK_P1_LEN, S, 4, &out->commitments[5]));
   }
-  for (int i = 0; i < 4; ++i) ts.append_commitment(tl::QUOTIENT[i], out->commitments[5 + i]);
+  pr.absorb_quotient(&out->commitments[5]);
   // ---- round 4 --------------------------------------------------------------------------------
   pm::host_mark(ctx, "round 4");
-  const HFr zc = ts.challenge_scalar(tl::Z_CHALLENGE), zw = fmul(zc, pk->omega);
-  enum { E_A, E_B, E_C, E_D, E_AN, E_BN, E_DN, E_S1, E_S2, E_S3, E_QARITH, E_QC, E_QL, E_QR, E_ZN, E_T, E_R, NEV };
-  HFr ev[NEV];
-  // r(z) needs no pass over r: r is a linear combination of key and round polynomials, so r(z) is the same combination of
-  // their values at z -- the ones the proof does not open anyway (q_m, q_o, q_4, z, sigma_4, the widget selectors) ride along
-  // as a second group.  ONE host synchronisation for all openings (r01 - r04: three, with r's own evaluation behind the
-  // linear combination).
-  enum { X_QM, X_QO, X_Q4, X_Z, X_S4, X_RANGE, X_LOGIC, X_FIXED, X_VAR, NX };
-  HFr xv[NX];
+  pr.draw_z(pk->omega);
+  const HFr &zc = pr.ch[C_Z], &zw = pr.zw;
+  auto poly = [&](PolyRef p) -> const void* {   // the wires, t and z at stride S, the key's polynomials at n
+    switch (p.role) {
+      case R_WIRE: return at(wc, p.index * S);
+      case R_T: return at(t_coeffs, p.index * S);
+      case R_Z: return z_coeffs;
+      case R_SIGMA: return at(pk->sigma_coeffs, p.index * n);
+      default: return at(pk->sel_coeffs, p.index * n);
+    }
+  };
   {
-    const void* at_z[15];
-    const void* at_x[NX];
-    u64 out_z[15][4], out_x[NX][4], out_zw[4][4];
-    for (int j = 0; j < 4; ++j) at_z[j] = at(wc, j * S);
-    for (int j = 0; j < 3; ++j) at_z[4 + j] = at(pk->sigma_coeffs, j * n);
-    at_z[7] = at(pk->sel_coeffs, Q_ARITH * n);
-    at_z[8] = at(pk->sel_coeffs, Q_C * n);
-    at_z[9] = at(pk->sel_coeffs, Q_L * n);
-    at_z[10] = at(pk->sel_coeffs, Q_R * n);
-    for (int i = 0; i < 4; ++i) at_z[11 + i] = at(t_coeffs, i * S);
-    at_x[X_QM] = at(pk->sel_coeffs, Q_M * n);
-    at_x[X_QO] = at(pk->sel_coeffs, Q_O * n);
-    at_x[X_Q4] = at(pk->sel_coeffs, Q_4 * n);
-    at_x[X_Z] = z_coeffs;
-    at_x[X_S4] = at(pk->sigma_coeffs, 3 * n);
-    uint32_t nx = X_RANGE;
-    const int wsel[4] = {Q_RANGE, Q_LOGIC, Q_FIXED, Q_VAR};
-    int xslot[4] = {-1, -1, -1, -1};
-    for (int w = 0; w < 4; ++w)
-      if (!pk->sel_zero[wsel[w]]) {
-        xslot[w] = (int)nx;
-        at_x[nx++] = at(pk->sel_coeffs, wsel[w] * n);
-      }
-    const void* at_zw[4] = {at(wc, 0), at(wc, S), at(wc, 3 * S), z_coeffs};
+    // ONE host synchronisation for all openings (r01 - r04: three, with r's own evaluation behind the linear combination)
+    const OpeningPlan plan(pk->sel_zero);
+    const void* ptr[MAX_OPENINGS];
+    u64 val[MAX_OPENINGS][4];
+    for (uint32_t s = 0; s < plan.count; ++s) ptr[s] = poly(plan.slot[s].poly);
+    const uint32_t w0 = plan.next_row();
     if (!zs) {
-      const uint32_t gk[3] = {15, nx, 4};
-      const void* const* gp[3] = {at_z, at_x, at_zw};
+      const uint32_t gk[3] = {OPENINGS_AT_Z, plan.nx, 4};
+      const void* const* gp[3] = {ptr, ptr + OPENINGS_AT_Z, ptr + w0};
       const uint64_t* gpt[3] = {zc.l, zc.l, zw.l};
-      uint64_t* gout[3] = {&out_z[0][0], &out_x[0][0], &out_zw[0][0]};
+      uint64_t* gout[3] = {val[0], val[OPENINGS_AT_Z], val[w0]};
       PK_TRY(pm::poly_evaluate_groups(ctx, 3, gk, gp, gpt, gout, n));
     } else {
       // the same openings, grouped by length: padded polynomials (S) at z, key polynomials (n) at z, padded at z w
-      enum { P_NUM = 9, K_NUM = 7 };
-      const void* pz[P_NUM] = {at_z[0], at_z[1], at_z[2], at_z[3], at_z[11], at_z[12], at_z[13], at_z[14], z_coeffs};
-      const void* kz[PM_LINCOMB_MAX];
-      for (int j = 0; j < K_NUM; ++j) kz[j] = at_z[4 + j];
-      for (uint32_t j = 0; j < nx; ++j)
-        if (j != X_Z) kz[K_NUM + j - (j > X_Z)] = at_x[j];
-      u64 opz[P_NUM][4], okz[PM_LINCOMB_MAX][4];
-      const uint32_t gk[3] = {P_NUM, K_NUM + nx - 1, 4};
-      const void* const* gp[3] = {pz, kz, at_zw};
+      const void* gptr[2][MAX_OPENINGS];
+      u64 gval[2][MAX_OPENINGS][4];
+      uint32_t gk[3] = {0, 0, 4}, from[MAX_OPENINGS];
+      for (uint32_t s = 0; s < w0; ++s) {
+        const int g = plan.slot[s].poly.per_proof() ? 0 : 1;
+        from[s] = gk[g];
+        gptr[g][gk[g]++] = ptr[s];
+      }
+      const void* const* gp[3] = {gptr[0], gptr[1], ptr + w0};
       const uint64_t* gpt[3] = {zc.l, zc.l, zw.l};
-      uint64_t* gout[3] = {&opz[0][0], &okz[0][0], &out_zw[0][0]};
+      uint64_t* gout[3] = {gval[0][0], gval[1][0], val[w0]};
       const size_t gn[3] = {S, n, S};
       PK_TRY(pm::poly_evaluate_groups_n(ctx, 3, gk, gp, gpt, gout, gn));
-      for (int j = 0; j < 4; ++j) memcpy(out_z[j], opz[j], 32);
-      for (int i = 0; i < 4; ++i) memcpy(out_z[11 + i], opz[4 + i], 32);
-      memcpy(out_x[X_Z], opz[8], 32);
-      for (int j = 0; j < K_NUM; ++j) memcpy(out_z[4 + j], okz[j], 32);
-      for (uint32_t j = 0; j < nx; ++j)
-        if (j != X_Z) memcpy(out_x[j], okz[K_NUM + j - (j > X_Z)], 32);
+      for (uint32_t s = 0; s < w0; ++s) memcpy(val[s], gval[plan.slot[s].poly.per_proof() ? 0 : 1][from[s]], 32);
     }
     pm::host_mark(ctx, "openings at z, z w");
-    for (int j = 0; j < 4; ++j) ev[E_A + j] = get(out_z[j]);
-    for (int j = 0; j < 3; ++j) ev[E_S1 + j] = get(out_z[4 + j]);
-    ev[E_QARITH] = get(out_z[7]);
-    ev[E_QC] = get(out_z[8]);
-    ev[E_QL] = get(out_z[9]);
-    ev[E_QR] = get(out_z[10]);
-    ev[E_AN] = get(out_zw[0]);
-    ev[E_BN] = get(out_zw[1]);
-    ev[E_DN] = get(out_zw[2]);
-    ev[E_ZN] = get(out_zw[3]);
-    const HFr zn_ = fpow(zc, n);
-    ev[E_T] = fadd(get(out_z[11]), fmul(zn_, fadd(get(out_z[12]), fmul(zn_, fadd(get(out_z[13]), fmul(zn_, get(out_z[14])))))));
-    for (int j = 0; j < X_RANGE; ++j) xv[j] = get(out_x[j]);
-    for (int w = 0; w < 4; ++w) xv[X_RANGE + w] = xslot[w] >= 0 ? get(out_x[xslot[w]]) : pm::host::zero<4>();
+    pr.take_openings(plan, val[0], n);
   }
-  const HFr zn = fpow(zc, n);
-  const HFr &a_ = ev[E_A], &b_ = ev[E_B], &c_ = ev[E_C], &d_ = ev[E_D], &s1 = ev[E_S1], &s2 = ev[E_S2], &s3 = ev[E_S3],
-            &z_next = ev[E_ZN], &qar = ev[E_QARITH];
-  const HFr l1_z = fmul(fsub(zn, one), finv(fmul(fr_u64(n), fsub(zc, one))));
-  const HFr bz = fmul(beta, zc);
-  HFr ident = fadd(fadd(a_, bz), gamma);
-  const HFr* wv[3] = {&b_, &c_, &d_};
-  for (int j = 0; j < 3; ++j) ident = fmul(ident, fadd(fadd(*wv[j], fmul(bz, pk->k[j])), gamma));
-  const HFr copy3 = fmul(fmul(fadd(fadd(a_, fmul(beta, s1)), gamma), fadd(fadd(b_, fmul(beta, s2)), gamma)),
-                         fadd(fadd(c_, fmul(beta, s3)), gamma));
-  const HFr alpha2 = fmul(alpha, alpha);
-  RowEvals re{a_, b_, c_, d_, ev[E_AN], ev[E_BN], ev[E_DN], ev[E_QL], ev[E_QR], ev[E_QC]};
   void* const r_coeffs = zs ? zs->r : pk->r;       // S coefficients
   void* const agg = zs ? zs->agg : pk->agg;        // S
   void* const wit = zs ? zs->wit : pk->wit;        // 2 x S
   {
+    LinTerm terms[12];
     const void* lin_v[12];
     u64 lin_c[12][4];
-    uint32_t k = 0;
-    HFr r_z = pm::host::zero<4>();   // r(z) = sum of coefficient x value at z, term by term
-    auto term = [&](const void* v, const HFr& c, const HFr& value_at_z) {
-      lin_v[k] = v;
-      put(lin_c[k], c);
-      r_z = fadd(r_z, fmul(c, value_at_z));
-      ++k;
-    };
-    // arithmetic: q_arith(z) (a b q_m + a q_l + b q_r + c q_o + d q_4 + q_c)
-    term(at(pk->sel_coeffs, Q_M * n), fmul(qar, fmul(a_, b_)), xv[X_QM]);
-    term(at(pk->sel_coeffs, Q_L * n), fmul(qar, a_), ev[E_QL]);
-    term(at(pk->sel_coeffs, Q_R * n), fmul(qar, b_), ev[E_QR]);
-    term(at(pk->sel_coeffs, Q_O * n), fmul(qar, c_), xv[X_QO]);
-    term(at(pk->sel_coeffs, Q_4 * n), fmul(qar, d_), xv[X_Q4]);
-    term(at(pk->sel_coeffs, Q_C * n), qar, ev[E_QC]);
-    if (!pk->sel_zero[Q_RANGE]) term(at(pk->sel_coeffs, Q_RANGE * n), widget_range(range_sep, re), xv[X_RANGE]);
-    if (!pk->sel_zero[Q_LOGIC]) term(at(pk->sel_coeffs, Q_LOGIC * n), widget_logic(logic_sep, re), xv[X_LOGIC]);
-    if (!pk->sel_zero[Q_FIXED]) term(at(pk->sel_coeffs, Q_FIXED * n), widget_fixed(fixed_sep, re), xv[X_FIXED]);
-    if (!pk->sel_zero[Q_VAR]) term(at(pk->sel_coeffs, Q_VAR * n), widget_var(var_sep, re), xv[X_VAR]);
-    const HFr c_z = fadd(fmul(alpha, ident), fmul(alpha2, l1_z));
-    term(z_coeffs, c_z, xv[X_Z]);
-    term(at(pk->sigma_coeffs, 3 * n), fneg(fmul(fmul(fmul(alpha, copy3), beta), z_next)), xv[X_S4]);
+    uint32_t k;
+    linearise(pr, pk->k, n, pk->sel_zero, terms, &k);
+    for (uint32_t i = 0; i < k; ++i) {
+      lin_v[i] = poly(terms[i].poly);
+      put(lin_c[i], terms[i].coeff);
+    }
     PK_TRY(pm_fr_lincomb_dev(ctx, k, lin_v, &lin_c[0][0], n, r_coeffs, nullptr));   // r itself: round 5 divides it
     if (zs) {   // beyond n only the blinded z has coefficients
       const void* tail_v[1] = {at(z_coeffs, n)};
-      PK_TRY(pm_fr_lincomb_dev(ctx, 1, tail_v, c_z.l, S - n, at(r_coeffs, n), nullptr));
+      PK_TRY(pm_fr_lincomb_dev(ctx, 1, tail_v, pr.c_z.l, S - n, at(r_coeffs, n), nullptr));
     }
-    ev[E_R] = r_z;
   }
-  static_assert(NEV == 17, "tl::EVALS lists the evaluations in this enum's order");
-  for (int i = 0; i < NEV; ++i) {
-    ts.append_scalar(tl::EVALS[i], ev[i]);
-    put(out->evaluations[i], ev[i]);
-  }
+  pr.finish_round4(out);
   // ---- round 5: CommitKey::compute_aggregate_witness at z and at z w ------------------------------
-  const HFr aw = ts.challenge_scalar(tl::AGGREGATE);
+  HFr ac[12], sh[4];
+  aggregation_coeffs(pr, n, ac, sh);
   {
     const void* agg_v[12];
     u64 agg_c[12][4];
-    HFr ac[12];
-    ac[0] = one;                      // quot = t_1 + z^n t_2 + z^2n t_3 + z^3n t_4 comes first (power 0)
-    ac[1] = zn;
-    ac[2] = fmul(zn, zn);
-    ac[3] = fmul(ac[2], zn);
-    HFr vp = one;
-    for (int e = 0; e < 8; ++e) {     // then lin, w_l, w_r, w_o, w_4, left, right, out sigma
-      vp = fmul(vp, aw);
-      ac[4 + e] = vp;
-    }
     for (int i = 0; i < 4; ++i) agg_v[i] = at(t_coeffs, i * S);
     agg_v[4] = r_coeffs;
     for (int j = 0; j < 4; ++j) agg_v[5 + j] = at(wc, j * S);
@@ -1282,30 +848,66 @@ static int prove_body(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, const 
     PK_TRY(pm_fr_lincomb_dev(ctx, 12, agg_v, &agg_c[0][0], n, agg, nullptr));
     if (zs) {   // the padded tails: t pieces, r and the wires (the sigmas end at n)
       const void* tail_v[9];
-      for (int i = 0; i < 9; ++i) tail_v[i] = at((void*)agg_v[i], n);
+      for (int i = 0; i < 9; ++i) tail_v[i] = at(agg_v[i], n);
       PK_TRY(pm_fr_lincomb_dev(ctx, 9, tail_v, &agg_c[0][0], S - n, at(agg, n), nullptr));
     }
     PK_TRY(pm_fr_poly_ruffini_dev(ctx, agg, S, zc.l, wit, nullptr));
   }
-  const HFr aws = ts.challenge_scalar(tl::AGGREGATE);
   {
     const void* sh_v[4] = {z_coeffs, at(wc, 0), at(wc, S), at(wc, 3 * S)};
     u64 sh_c[4][4];
-    HFr vp = one;
-    for (int e = 0; e < 4; ++e) {
-      put(sh_c[e], vp);
-      vp = fmul(vp, aws);
-    }
+    for (int e = 0; e < 4; ++e) put(sh_c[e], sh[e]);
     PK_TRY(pm_fr_lincomb_dev(ctx, 4, sh_v, &sh_c[0][0], S, agg, nullptr));
     PK_TRY(pm_fr_poly_ruffini_dev(ctx, agg, S, zw.l, at(wit, S), nullptr));
   }
   // deg W_z = deg t_4 - 1: n + 9 coefficients in zero-knowledge mode
   PK_TRY(commit_batch(ctx, ck, shard, wit, zs ? n + pm::ZK_P1_LEN - 1 : n - 1, S, 2, &out->commitments[9]));
-  ts.append_commitment(tl::W_Z, out->commitments[9]);
-  ts.append_commitment(tl::W_ZW, out->commitments[10]);
-  const HFr chal[10] = {beta, gamma, alpha, range_sep, logic_sep, fixed_sep, var_sep, zc, aw, aws};
-  for (int i = 0; i < 10; ++i) put(out->challenges[i], chal[i]);
+  pr.absorb_witnesses_and_store(out);
   return PM_OK;
+}
+
+static int prove_impl(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, const Shard& shard, const void* d_witness,
+                      const uint64_t* pi_positions, const uint64_t* pi_values, size_t n_pi, uint32_t flags,
+                      const uint64_t (*blinders)[4], pm_plonk_proof* out) {
+  if (ctx && ctx->marks_on) ctx->marks.clear();
+  pm::host_mark(ctx, "prove: start");
+  const int rc = shard_leave(ctx, shard, prove_body(ctx, pk, ck, shard, d_witness, pi_positions, pi_values, n_pi, flags, blinders, out));
+  pm::host_mark(ctx, "prove: end");
+  if (ctx && ctx->marks_on && !ctx->marks.empty()) {   // PM_HOST_MARKS=1: where the host's time between the kernels goes
+    const double t0 = ctx->marks.front().second;
+    double prev = t0;
+    for (const auto& mk : ctx->marks) {
+      fprintf(stderr, "[host] %9.1f us  +%7.1f  %s\n", mk.second - t0, mk.second - prev, mk.first);
+      prev = mk.second;
+    }
+  }
+  return rc;
+}
+
+extern "C" int pm_plonk_prove_sharded(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck_slice, size_t first_coefficient,
+                                      const void* d_witness, const uint64_t* pi_positions, const uint64_t* pi_values,
+                                      size_t n_pi, uint32_t flags, pm_exchange_fn exchange, void* user,
+                                      pm_plonk_proof* out) {
+  Shard sh;
+  sh.on = true;
+  sh.lo = first_coefficient;
+  sh.fn = exchange;
+  sh.user = user;
+  sh.expect = 4;
+  return prove_impl(ctx, pk, ck_slice, sh, d_witness, pi_positions, pi_values, n_pi, flags, nullptr, out);
+}
+
+extern "C" int pm_plonk_prove(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, const void* d_witness,
+                              const uint64_t* pi_positions, const uint64_t* pi_values, size_t n_pi, uint32_t flags,
+                              pm_plonk_proof* out) {
+  return prove_impl(ctx, pk, ck, Shard(), d_witness, pi_positions, pi_values, n_pi, flags, nullptr, out);
+}
+
+extern "C" int pm_plonk_prove_zk(pm_ctx* ctx, pm_prover_key* pk, const pm_bases* ck, const void* d_witness,
+                                 const uint64_t* pi_positions, const uint64_t* pi_values, size_t n_pi, uint32_t flags,
+                                 const uint64_t (*blinders)[4], pm_plonk_proof* out) {
+  if (!blinders) return PM_ERR_BAD_ARG;
+  return prove_impl(ctx, pk, ck, Shard(), d_witness, pi_positions, pi_values, n_pi, flags, blinders, out);
 }
 
 // Proof::to_bytes of dusk-plonk 0.8: 11 compressed G1 (a b c d z t_1..t_4 w_z w_zw) then the 16 scalars of
@@ -1321,6 +923,33 @@ extern "C" int pm_plonk_proof_to_bytes(const pm_plonk_proof* proof, uint8_t out[
 extern "C" int pm_plonk_verifier_key(const pm_prover_key* key, uint64_t (*out)[12]) {
   if (!key || !out || !key->committed) return PM_ERR_BAD_ARG;
   memcpy(out, key->vk, sizeof key->vk);
+  return PM_OK;
+}
+
+// Pure host, no context: linearise of prover_rounds.h -- the one copy of the linearisation scalars -- on given openings
+// and challenges (include/plonk_mi355x.h).
+extern "C" int pm_test_plonk_linearise(size_t n, const uint64_t (*evaluations)[4], const uint64_t (*extras)[4],
+                                       const uint64_t (*challenges)[4], uint32_t selector_present_mask, uint64_t (*out_coeffs)[4],
+                                       uint32_t* out_roles, uint32_t* out_count, uint64_t out_r_z[4]) {
+  if (!evaluations || !extras || !challenges || !out_coeffs || !out_roles || !out_count || !out_r_z) return PM_ERR_BAD_ARG;
+  if (n == 0) return PM_ERR_LENGTH;
+  ProofRounds pr{Transcript(tl::PROTOCOL)};
+  struct In { HFr* dst; const uint64_t (*src)[4]; int count; };
+  for (const In& in : {In{pr.ev, evaluations, NEV}, In{pr.xv, extras, NX}, In{pr.ch, challenges, NCHAL}})
+    for (int i = 0; i < in.count; ++i) {
+      if (pm::host::geq<4>(in.src[i], FRF().m)) return PM_ERR_BAD_ARG;
+      in.dst[i] = get(in.src[i]);
+    }
+  bool sel_zero[NSEL];
+  for (int s = 0; s < NSEL; ++s) sel_zero[s] = !((selector_present_mask >> s) & 1);
+  const HFr k[3] = {fr_u64(7), fr_u64(13), fr_u64(17)};
+  LinTerm terms[12];
+  linearise(pr, k, n, sel_zero, terms, out_count);
+  for (uint32_t i = 0; i < *out_count; ++i) {
+    put(out_coeffs[i], terms[i].coeff);
+    out_roles[i] = (uint32_t)terms[i].poly.role << 8 | terms[i].poly.index;
+  }
+  put(out_r_z, pr.r_z);
   return PM_OK;
 }
 

@@ -1,5 +1,5 @@
-// Many proofs of one circuit in one call: pm_plonk_prove_batch (included by prover.hip: the transcript, the widgets'
-// linearisation scalars and the key are shared with prove_body, which is left as it is).
+// Many proofs of one circuit in one call: pm_plonk_prove_batch (included by prover.hip: the key is pm_plonk_prove's, and
+// the host side of the rounds is the same prover_rounds.h, one ProofRounds per proof).
 //
 // B proofs run through every round together.  The workspace is laid out role-major -- every role (wire coefficients,
 // z, PI, the coset forms, t, r, the aggregates, the opening witnesses) holds all B proofs at one uniform stride -- so each
@@ -46,17 +46,8 @@ struct pm_plonk_batch {
 };
 
 namespace {
-constexpr uint32_t BATCH_EVAL_SLOTS = 15 + 9 + 4;   // the openings at z, the ones r(z) needs, the four at z w
+constexpr uint32_t BATCH_EVAL_SLOTS = MAX_OPENINGS;
 constexpr size_t BATCH_CONST_BYTES_PER_PROOF = 16384, BATCH_CONST_BYTES_FIXED = 16384;
-
-struct BatchBusy {
-  pm_plonk_batch* ws;
-  bool ok;
-  explicit BatchBusy(pm_plonk_batch* w) : ws(w), ok(!w->busy.exchange(true)) {}
-  ~BatchBusy() {
-    if (ok) ws->busy.store(false);
-  }
-};
 
 // commitments to `count` vectors of len coefficients at stride `stride`: passes of at most 64 vectors, one affine conversion
 int batch_commit(pm_ctx* ctx, const pm_bases* ck, const void* d, size_t len, size_t stride, uint32_t count, u64 (*out_xy)[12]) {
@@ -67,32 +58,6 @@ int batch_commit(pm_ctx* ctx, const pm_bases* ck, const void* d, size_t len, siz
                                &xyz[18 * (size_t)v0], nullptr));
   }
   return pm_g1_to_affine_batch(xyz.data(), count, &out_xy[0][0], nullptr);
-}
-
-// commit_lagrange_zk for `count` blinded wire vectors: [w] from the witness values over the Lagrange key, plus
-// sum_i b_i ([tau^(n+i)] - [tau^i]) from the three tail coefficients over the commit key at offsets n and 0 (negated), in
-// passes of at most 64 vectors; one host fold per wire, one affine conversion
-int batch_commit_lagrange_zk(pm_ctx* ctx, const pm_bases* lag, const pm_bases* ck, const void* d_wit, const void* coeffs, size_t n,
-                             size_t S, uint32_t count, u64 (*out_xy)[12]) {
-  std::vector<u64> xyz(3 * 18 * (size_t)count), sum(18 * (size_t)count);
-  u64* part[3] = {xyz.data(), xyz.data() + 18 * (size_t)count, xyz.data() + 36 * (size_t)count};
-  for (uint32_t v0 = 0; v0 < count; v0 += 64) {
-    const uint32_t k = std::min<uint32_t>(64, count - v0);
-    const void* tails = at((void*)coeffs, (size_t)v0 * S + n);
-    PK_TRY(pm_g1_msm_batch_dev(ctx, lag, 0, n, at((void*)d_wit, (size_t)v0 * n), n, k, PM_SCALAR_MONTGOMERY, part[0] + 18 * (size_t)v0, nullptr));
-    PK_TRY(pm_g1_msm_batch_dev(ctx, ck, n, 3, tails, S, k, PM_SCALAR_MONTGOMERY, part[1] + 18 * (size_t)v0, nullptr));
-    PK_TRY(pm_g1_msm_batch_dev(ctx, ck, 0, 3, tails, S, k, PM_SCALAR_MONTGOMERY, part[2] + 18 * (size_t)v0, nullptr));
-  }
-  for (uint32_t v = 0; v < count; ++v) {
-    u64 parts[3][18];
-    for (int k = 0; k < 3; ++k) memcpy(parts[k], part[k] + 18 * (size_t)v, sizeof parts[k]);
-    HFp y;
-    memcpy(y.l, parts[2] + 6, 48);
-    y = pm::host::sub(pm::host::zero<6>(), y, pm::host::FP());   // -P = (X, -Y, Z)
-    memcpy(parts[2] + 6, y.l, 48);
-    PK_TRY(pm_g1_fold(&parts[0][0], 3, &sum[18 * (size_t)v]));
-  }
-  return pm_g1_to_affine_batch(sum.data(), count, &out_xy[0][0], nullptr);
 }
 
 // pi_evals <- 0, then every proof's public inputs in ONE staged scatter (pi_scatter_kernel over global positions b n + i; a
@@ -106,18 +71,8 @@ int batch_scatter_pi(pm_ctx* ctx, pm_plonk_batch* ws, uint32_t B, const uint64_t
   if (!n_pi) return PM_OK;
   std::vector<unsigned long long> hp;
   std::vector<uint64_t> hv;
-  std::unordered_map<uint64_t, size_t> last;
-  for (uint32_t b = 0; b < B; ++b) {
-    const size_t k = n_pi[b];
-    if (!k) continue;
-    last.clear();
-    for (size_t i = 0; i < k; ++i) last[pos[b][i]] = i;
-    for (size_t i = 0; i < k; ++i) {
-      if (last[pos[b][i]] != i) continue;
-      hp.push_back((unsigned long long)b * n + pos[b][i]);
-      hv.insert(hv.end(), vals[b] + 4 * i, vals[b] + 4 * i + 4);
-    }
-  }
+  for (uint32_t b = 0; b < B; ++b)
+    if (n_pi[b]) compact_public_inputs(pos[b], vals[b], n_pi[b], (uint64_t)b * n, hp, hv);
   const size_t cnt = hp.size();   // <= B n: fits num (values) and den (positions)
   if (!cnt) return PM_OK;
   const size_t need = cnt * 40;
@@ -138,12 +93,26 @@ int batch_scatter_pi(pm_ctx* ctx, pm_plonk_batch* ws, uint32_t B, const uint64_t
   return PM_OK;
 }
 
+// Regions of one allocation, each at a multiple of 256 bytes: the bytes they need together; with a base, their pointers
+struct Region {
+  void** p;
+  size_t bytes;
+};
+template <size_t N>
+size_t carve_regions(void* base, const Region (&regions)[N]) {
+  size_t off = 0;
+  for (const Region& r : regions) {
+    if (base) *r.p = (char*)base + off;
+    off += (r.bytes + 255) / 256 * 256;
+  }
+  return off;
+}
+
 int prove_batch_body(pm_ctx* ctx, pm_prover_key* pk, pm_plonk_batch* ws, const pm_bases* ck, uint32_t B, const void* d_wit,
                      const uint64_t* const* pi_pos, const uint64_t* const* pi_val, const size_t* n_pi, uint32_t flags,
                      const uint64_t (*blinders)[PM_PLONK_ZK_BLINDERS][4], pm_plonk_proof* out) {
   const size_t n = pk->n;
   const uint32_t lg = pk->log_n;
-  const HFr one = fone();
   ws->stage.reset();
   // zero-knowledge mode: blinded wires and z of n + 3 coefficients, quotient pieces up to n + 10, all at the padded stride S in
   // the workspace's ZK regions, and the second-coset forms for the quotient.  Otherwise S = n and the plain regions.
@@ -185,16 +154,10 @@ int prove_batch_body(pm_ctx* ctx, pm_prover_key* pk, pm_plonk_batch* ws, const p
     PK_TRY(pm_fr_ntt_dev(ctx, zk->shift, wlen, S, zk->coset2_w, 4 * n, lg + 2, 4 * B, PM_NTT_COSET, st));
     return pm_fr_ntt_dev(ctx, zk->shift_pi, n, n, zk->coset2_pi, 4 * n, lg + 2, B, PM_NTT_COSET, st);
   };
-  std::vector<Transcript> ts(B, pk->base);
-  if (!(flags & PM_PLONK_UPSTREAM_TRANSCRIPT)) {
-    for (uint32_t b = 0; b < B; ++b) {
-      const size_t k = n_pi ? n_pi[b] : 0;
-      ts[b].append_u64(tl::PI_LEN, k);
-      for (size_t i = 0; i < k; ++i) {
-        ts[b].append_u64(tl::PI_POS, pi_pos[b][i]);
-        ts[b].append_scalar(tl::PI_VALUE, get(pi_val[b] + 4 * i));
-      }
-    }
+  std::vector<ProofRounds> pr(B, ProofRounds(pk->base));
+  for (uint32_t b = 0; b < B; ++b) {
+    const size_t k = n_pi ? n_pi[b] : 0;
+    pr[b].begin(flags, k ? pi_pos[b] : nullptr, k ? pi_val[b] : nullptr, k);
   }
   const pm_bases* lag = pk->lagrange;
   hipStream_t side = ws->side;
@@ -215,7 +178,8 @@ int prove_batch_body(pm_ctx* ctx, pm_prover_key* pk, pm_plonk_batch* ws, const p
     PK_TRY(pm_fr_ntt_dev(ctx, ws->pi_coeffs, n, n, ws->coset_pi, 4 * n, lg + 2, B, PM_NTT_COSET, side));
     if (zk) {
       PK_TRY(second_coset(true, side));
-      PK_TRY(batch_commit_lagrange_zk(ctx, lag, ck, d_wit, W, n, S, 4 * B, xy));
+      std::vector<u64> scratch(72 * 4 * (size_t)B);
+      PK_TRY(commit_lagrange_zk(ctx, lag, ck, d_wit, W, n, S, 4 * B, scratch.data(), xy));
     } else {
       PK_TRY(batch_commit(ctx, lag, d_wit, n, n, 4 * B, xy));
     }
@@ -228,27 +192,16 @@ int prove_batch_body(pm_ctx* ctx, pm_prover_key* pk, pm_plonk_batch* ws, const p
     if (zk) PK_TRY(second_coset(true, side));
     PK_TRY(batch_commit(ctx, ck, W, wlen, S, 4 * B, xy));
   }
-  for (uint32_t b = 0; b < B; ++b)
-    for (int j = 0; j < 4; ++j) {
-      memcpy(out[b].commitments[j], xy[4 * b + j], 96);
-      ts[b].append_commitment(tl::WIRES[j], out[b].commitments[j]);
-    }
+  for (uint32_t b = 0; b < B; ++b) {
+    memcpy(out[b].commitments[0], xy[4 * b], 4 * 96);
+    pr[b].absorb_wires(&out[b].commitments[0]);
+  }
   // ---- round 2 --------------------------------------------------------------------------------
-  std::vector<HFr> beta(B), gamma(B);
   std::vector<pm_plonk_perm_args> pa(B);
   for (uint32_t b = 0; b < B; ++b) {
-    beta[b] = ts[b].challenge_scalar(tl::BETA);
-    ts[b].append_scalar(tl::BETA, beta[b]);
-    gamma[b] = ts[b].challenge_scalar(tl::GAMMA);
-    memset(&pa[b], 0, sizeof pa[b]);
-    for (int j = 0; j < 4; ++j) {
-      pa[b].wires[j] = at((void*)d_wit, j * n);   // proof 0; proof b at + 4 b n
-      pa[b].sigmas[j] = at(pk->sigma_evals, j * n);
-    }
-    pa[b].roots = pk->roots;
-    put(pa[b].beta, beta[b]);
-    put(pa[b].gamma, gamma[b]);
-    for (int j = 0; j < 3; ++j) put(pa[b].k[j], pk->k[j]);
+    pr[b].draw_round2();
+    // proof 0's wires; proof b's at + 4 b n
+    fill_perm_args(pa[b], d_wit, n, pk->sigma_evals, n, pk->roots, pk->k, pr[b].ch[C_BETA], pr[b].ch[C_GAMMA]);
   }
   PK_TRY(pm::perm_terms_batch(ctx, ws->stage, pa.data(), B, 4 * n, n, ws->num, ws->den, ctx->stream));
   PK_TRY(pm::fr_batch_inverse_mul(ctx, ws->den, ws->num, (size_t)B * n, nullptr));   // elementwise: one call for all proofs
@@ -266,47 +219,14 @@ int prove_batch_body(pm_ctx* ctx, pm_prover_key* pk, pm_plonk_batch* ws, const p
   PK_TRY(batch_commit(ctx, ck, Zc, wlen, S, B, xy));
   for (uint32_t b = 0; b < B; ++b) {
     memcpy(out[b].commitments[4], xy[b], 96);
-    ts[b].append_commitment(tl::PERM, out[b].commitments[4]);
+    pr[b].absorb_perm(out[b].commitments[4]);
   }
   // ---- round 3 --------------------------------------------------------------------------------
-  std::vector<HFr> alpha(B), range_sep(B), logic_sep(B), fixed_sep(B), var_sep(B);
   std::vector<pm_plonk_quotient_args> qa(B);
   for (uint32_t b = 0; b < B; ++b) {
-    alpha[b] = ts[b].challenge_scalar(tl::ALPHA);
-    range_sep[b] = ts[b].challenge_scalar(tl::RANGE_SEP);
-    logic_sep[b] = ts[b].challenge_scalar(tl::LOGIC_SEP);
-    fixed_sep[b] = ts[b].challenge_scalar(tl::FIXED_SEP);
-    var_sep[b] = ts[b].challenge_scalar(tl::VAR_SEP);
-    pm_plonk_quotient_args& q = qa[b];
-    memset(&q, 0, sizeof q);
-    for (int j = 0; j < 4; ++j) {
-      q.wires[j] = at(ws->coset_w, 4 * n * j);   // proof 0; proof b at + 16 b n (z, PI, t: + 4 b n)
-      q.sigmas[j] = at(pk->sigma_coset, 4 * n * j);
-    }
-    q.z = ws->coset_z;
-    q.pi = ws->coset_pi;
-    q.q_m = pk->sel_coset[Q_M];
-    q.q_l = pk->sel_coset[Q_L];
-    q.q_r = pk->sel_coset[Q_R];
-    q.q_o = pk->sel_coset[Q_O];
-    q.q_c = pk->sel_coset[Q_C];
-    q.q_4 = pk->sel_coset[Q_4];
-    q.q_arith = pk->sel_coset[Q_ARITH];
-    q.q_range = pk->sel_coset[Q_RANGE];
-    q.q_logic = pk->sel_coset[Q_LOGIC];
-    q.q_fixed_group_add = pk->sel_coset[Q_FIXED];
-    q.q_variable_group_add = pk->sel_coset[Q_VAR];
-    q.l1 = pk->l1_coset;
-    q.x = pk->x4;
-    put(q.alpha, alpha[b]);
-    put(q.beta, beta[b]);
-    put(q.gamma, gamma[b]);
-    put(q.range_sep, range_sep[b]);
-    put(q.logic_sep, logic_sep[b]);
-    put(q.fixed_sep, fixed_sep[b]);
-    put(q.var_sep, var_sep[b]);
-    for (int j = 0; j < 3; ++j) put(q.k[j], pk->k[j]);
-    for (int j = 0; j < 4; ++j) put(q.zh_inv[j], pk->zh_inv[j]);
+    pr[b].draw_round3();
+    // proof 0's wires, z and PI; proof b's at + 16 b n (z, PI, t: + 4 b n)
+    fill_quotient_args(qa[b], key_first_coset(pk), ws->coset_w, 4 * n, ws->coset_z, ws->coset_pi, pk->k, pr[b].ch);
   }
   PK_TRY(pm_stream_join(ctx, side, ws->ev_side));   // the wire, PI and z coset forms are ready
   if (!zk) {
@@ -317,21 +237,8 @@ int prove_batch_body(pm_ctx* ctx, pm_prover_key* pk, pm_plonk_batch* ws, const p
     // deg t' <= 4n + 9: the same kernel on the second coset gives t' mod (X^4n + s) beside t' mod (X^4n - s); the 2B
     // outputs (A of every proof, then B of every proof) share one inverse coset transform
     PK_TRY(pm::quotient_batch(ctx, ws->stage, qa.data(), B, 16 * n, 4 * n, n, zk->ab, ctx->stream));
-    for (uint32_t b = 0; b < B; ++b) {
-      pm_plonk_quotient_args& q2 = qa[b];
-      for (int j = 0; j < 4; ++j) {
-        q2.wires[j] = at(zk->coset2_w, 4 * n * j);
-        q2.sigmas[j] = at(kz->sigma_coset2, 4 * n * j);
-      }
-      q2.z = zk->coset2_z;
-      q2.pi = zk->coset2_pi;
-      const void** sel2[NSEL] = {&q2.q_m, &q2.q_l, &q2.q_r, &q2.q_o, &q2.q_c, &q2.q_4, &q2.q_arith, &q2.q_range, &q2.q_logic,
-                                 &q2.q_fixed_group_add, &q2.q_variable_group_add};
-      for (int s_ = 0; s_ < NSEL; ++s_) *sel2[s_] = kz->sel_coset2[s_];
-      q2.l1 = kz->l1_coset2;
-      q2.x = kz->x2;
-      for (int j = 0; j < 4; ++j) put(q2.zh_inv[j], kz->zh_inv2[j]);
-    }
+    for (uint32_t b = 0; b < B; ++b)
+      fill_quotient_args(qa[b], key_second_coset(pk), zk->coset2_w, 4 * n, zk->coset2_z, zk->coset2_pi, pk->k, pr[b].ch);
     PK_TRY(pm::quotient_batch(ctx, ws->stage, qa.data(), B, 16 * n, 4 * n, n, at(zk->ab, 4 * n * (size_t)B), ctx->stream));
     PK_TRY(pm_fr_ntt_dev(ctx, zk->ab, 4 * n, 4 * n, zk->ab, 4 * n, lg + 2, 2 * B, PM_NTT_INVERSE | PM_NTT_COSET, nullptr));
     u64 inv2[4], inv2s[4];
@@ -340,61 +247,45 @@ int prove_batch_body(pm_ctx* ctx, pm_prover_key* pk, pm_plonk_batch* ws, const p
     PK_TRY(pm::zk_combine_batch(ctx, d_bl, zk->ab, kz->w8, B, n, S, inv2, inv2s, T, ctx->stream));
     PK_TRY(batch_commit(ctx, ck, T, n + pm::ZK_P1_LEN, S, 4 * B, xy));
   }
-  for (uint32_t b = 0; b < B; ++b)
-    for (int i = 0; i < 4; ++i) {
-      memcpy(out[b].commitments[5 + i], xy[4 * b + i], 96);
-      ts[b].append_commitment(tl::QUOTIENT[i], out[b].commitments[5 + i]);
-    }
+  for (uint32_t b = 0; b < B; ++b) {
+    memcpy(out[b].commitments[5], xy[4 * b], 4 * 96);
+    pr[b].absorb_quotient(&out[b].commitments[5]);
+  }
   // ---- round 4 --------------------------------------------------------------------------------
-  enum { E_A, E_B, E_C, E_D, E_AN, E_BN, E_DN, E_S1, E_S2, E_S3, E_QARITH, E_QC, E_QL, E_QR, E_ZN, E_T, E_R, NEV };
-  enum { X_QM, X_QO, X_Q4, X_Z, X_S4, X_RANGE, X_LOGIC, X_FIXED, X_VAR, NX };
-  std::vector<HFr> zc(B), zw(B);
   std::vector<u64> points(8 * (size_t)B);
   for (uint32_t b = 0; b < B; ++b) {
-    zc[b] = ts[b].challenge_scalar(tl::Z_CHALLENGE);
-    zw[b] = fmul(zc[b], pk->omega);
-    put(&points[8 * b], zc[b]);
-    put(&points[8 * b + 4], zw[b]);
+    pr[b].draw_z(pk->omega);
+    put(&points[8 * b], pr[b].ch[C_Z]);
+    put(&points[8 * b + 4], pr[b].zw);
   }
-  // the openings as prove_body takes them: 15 at z, the values r(z) needs at z, 4 at z w -- one batch, one synchronisation
-  // (a slot with a stride is a padded vector of the batch, S coefficients; one without is a key polynomial, n)
-  const void* sp[BATCH_EVAL_SLOTS];
-  size_t sstride[BATCH_EVAL_SLOTS], slen[BATCH_EVAL_SLOTS];
-  uint8_t spt[BATCH_EVAL_SLOTS];
-  uint32_t K = 0;
-  auto slot = [&](const void* p, size_t stride, uint8_t pt) {
-    sp[K] = p;
-    sstride[K] = stride;
-    slen[K] = stride ? S : n;
-    spt[K] = pt;
-    ++K;
+  // proof 0's vector and the stride from proof to proof: the wires, t and z are padded vectors of the batch (S coefficients),
+  // a polynomial of the key (n) has stride 0
+  struct Vec {
+    const void* p;
+    size_t stride;
   };
-  for (int j = 0; j < 4; ++j) slot(at(W, j * S), 4 * S, 0);
-  for (int j = 0; j < 3; ++j) slot(at(pk->sigma_coeffs, j * n), 0, 0);
-  slot(at(pk->sel_coeffs, Q_ARITH * n), 0, 0);
-  slot(at(pk->sel_coeffs, Q_C * n), 0, 0);
-  slot(at(pk->sel_coeffs, Q_L * n), 0, 0);
-  slot(at(pk->sel_coeffs, Q_R * n), 0, 0);
-  for (int i = 0; i < 4; ++i) slot(at(T, i * S), 4 * S, 0);
-  const uint32_t x0 = K;   // 15
-  slot(at(pk->sel_coeffs, Q_M * n), 0, 0);
-  slot(at(pk->sel_coeffs, Q_O * n), 0, 0);
-  slot(at(pk->sel_coeffs, Q_4 * n), 0, 0);
-  slot(Zc, S, 0);
-  slot(at(pk->sigma_coeffs, 3 * n), 0, 0);
-  const int wsel[4] = {Q_RANGE, Q_LOGIC, Q_FIXED, Q_VAR};
-  int xslot[4] = {-1, -1, -1, -1};
-  for (int w = 0; w < 4; ++w)
-    if (!pk->sel_zero[wsel[w]]) {
-      xslot[w] = (int)K;
-      slot(at(pk->sel_coeffs, wsel[w] * n), 0, 0);
+  auto poly = [&](PolyRef p) -> Vec {
+    switch (p.role) {
+      case R_WIRE: return {at(W, p.index * S), 4 * S};
+      case R_T: return {at(T, p.index * S), 4 * S};
+      case R_Z: return {Zc, S};
+      case R_SIGMA: return {at(pk->sigma_coeffs, p.index * n), 0};
+      default: return {at(pk->sel_coeffs, p.index * n), 0};
     }
-  const uint32_t w0 = K;
-  slot(at(W, 0), 4 * S, 1);
-  slot(at(W, S), 4 * S, 1);
-  slot(at(W, 3 * S), 4 * S, 1);
-  slot(Zc, S, 1);
-  if (K > BATCH_EVAL_SLOTS) return pm::set_err(ctx, PM_ERR_BAD_ARG, "more openings than the workspace holds");
+  };
+  // the openings as pm_plonk_prove takes them -- one batch, one synchronisation
+  const OpeningPlan plan(pk->sel_zero);
+  const uint32_t K = plan.count;
+  const void* sp[MAX_OPENINGS];
+  size_t sstride[MAX_OPENINGS], slen[MAX_OPENINGS];
+  uint8_t spt[MAX_OPENINGS];
+  for (uint32_t s = 0; s < K; ++s) {
+    const Vec v = poly(plan.slot[s].poly);
+    sp[s] = v.p;
+    sstride[s] = v.stride;
+    slen[s] = v.stride ? S : n;
+    spt[s] = plan.slot[s].point;
+  }
   std::vector<u64> ov(4 * (size_t)K * B);
   PK_TRY(pm::evaluate_batch(ctx, ws->stage, K, sp, sstride, spt, points.data(), B, S, zk ? zk->eval_ws : ws->eval_ws, ov.data(),
                             ctx->stream, zk ? slen : nullptr));
@@ -403,70 +294,20 @@ int prove_batch_body(pm_ctx* ctx, pm_prover_key* pk, pm_plonk_batch* ws, const p
   uint32_t lk = 0;
   std::vector<u64> lin_c;   // [B][lk][4]
   std::vector<u64> cz_c;    // [B][4]: z's coefficient in r (zero-knowledge mode: the only term with a tail beyond n)
-  std::vector<HFr> aw(B), aws(B);
   for (uint32_t b = 0; b < B; ++b) {
-    auto val = [&](uint32_t s) { return get(&ov[4 * ((size_t)b * K + s)]); };
-    HFr ev[NEV], xv[NX];
-    for (int j = 0; j < 4; ++j) ev[E_A + j] = val(j);
-    for (int j = 0; j < 3; ++j) ev[E_S1 + j] = val(4 + j);
-    ev[E_QARITH] = val(7);
-    ev[E_QC] = val(8);
-    ev[E_QL] = val(9);
-    ev[E_QR] = val(10);
-    ev[E_AN] = val(w0);
-    ev[E_BN] = val(w0 + 1);
-    ev[E_DN] = val(w0 + 2);
-    ev[E_ZN] = val(w0 + 3);
-    const HFr z_ = zc[b], zn = fpow(z_, n);
-    ev[E_T] = fadd(val(11), fmul(zn, fadd(val(12), fmul(zn, fadd(val(13), fmul(zn, val(14)))))));
-    for (int j = 0; j < X_RANGE; ++j) xv[j] = val(x0 + j);
-    for (int w = 0; w < 4; ++w) xv[X_RANGE + w] = xslot[w] >= 0 ? val((uint32_t)xslot[w]) : pm::host::zero<4>();
-    // r and r(z): prove_body's linear combination, term by term
-    const HFr &a_ = ev[E_A], &b_ = ev[E_B], &c_ = ev[E_C], &d_ = ev[E_D], &s1 = ev[E_S1], &s2 = ev[E_S2], &s3 = ev[E_S3],
-              &z_next = ev[E_ZN], &qar = ev[E_QARITH];
-    const HFr l1_z = fmul(fsub(zn, one), finv(fmul(fr_u64(n), fsub(z_, one))));
-    const HFr bz = fmul(beta[b], z_);
-    HFr ident = fadd(fadd(a_, bz), gamma[b]);
-    const HFr* wv[3] = {&b_, &c_, &d_};
-    for (int j = 0; j < 3; ++j) ident = fmul(ident, fadd(fadd(*wv[j], fmul(bz, pk->k[j])), gamma[b]));
-    const HFr copy3 = fmul(fmul(fadd(fadd(a_, fmul(beta[b], s1)), gamma[b]), fadd(fadd(b_, fmul(beta[b], s2)), gamma[b])),
-                           fadd(fadd(c_, fmul(beta[b], s3)), gamma[b]));
-    const HFr alpha2 = fmul(alpha[b], alpha[b]);
-    RowEvals re{a_, b_, c_, d_, ev[E_AN], ev[E_BN], ev[E_DN], ev[E_QL], ev[E_QR], ev[E_QC]};
-    uint32_t k = 0;
-    HFr r_z = pm::host::zero<4>();
-    auto term = [&](const void* v, size_t stride, const HFr& c, const HFr& value_at_z) {
+    pr[b].take_openings(plan, &ov[4 * (size_t)b * K], n);
+    LinTerm terms[12];
+    linearise(pr[b], pk->k, n, pk->sel_zero, terms, &lk);
+    for (uint32_t i = 0; i < lk; ++i) {
       if (b == 0) {
-        lin_v[k] = v;
-        lin_s[k] = stride;
+        const Vec v = poly(terms[i].poly);
+        lin_v[i] = v.p;
+        lin_s[i] = v.stride;
       }
-      lin_c.insert(lin_c.end(), c.l, c.l + 4);
-      r_z = fadd(r_z, fmul(c, value_at_z));
-      ++k;
-    };
-    term(at(pk->sel_coeffs, Q_M * n), 0, fmul(qar, fmul(a_, b_)), xv[X_QM]);
-    term(at(pk->sel_coeffs, Q_L * n), 0, fmul(qar, a_), ev[E_QL]);
-    term(at(pk->sel_coeffs, Q_R * n), 0, fmul(qar, b_), ev[E_QR]);
-    term(at(pk->sel_coeffs, Q_O * n), 0, fmul(qar, c_), xv[X_QO]);
-    term(at(pk->sel_coeffs, Q_4 * n), 0, fmul(qar, d_), xv[X_Q4]);
-    term(at(pk->sel_coeffs, Q_C * n), 0, qar, ev[E_QC]);
-    if (!pk->sel_zero[Q_RANGE]) term(at(pk->sel_coeffs, Q_RANGE * n), 0, widget_range(range_sep[b], re), xv[X_RANGE]);
-    if (!pk->sel_zero[Q_LOGIC]) term(at(pk->sel_coeffs, Q_LOGIC * n), 0, widget_logic(logic_sep[b], re), xv[X_LOGIC]);
-    if (!pk->sel_zero[Q_FIXED]) term(at(pk->sel_coeffs, Q_FIXED * n), 0, widget_fixed(fixed_sep[b], re), xv[X_FIXED]);
-    if (!pk->sel_zero[Q_VAR]) term(at(pk->sel_coeffs, Q_VAR * n), 0, widget_var(var_sep[b], re), xv[X_VAR]);
-    const HFr c_z = fadd(fmul(alpha[b], ident), fmul(alpha2, l1_z));
-    term(Zc, S, c_z, xv[X_Z]);
-    cz_c.insert(cz_c.end(), c_z.l, c_z.l + 4);
-    term(at(pk->sigma_coeffs, 3 * n), 0, fneg(fmul(fmul(fmul(alpha[b], copy3), beta[b]), z_next)), xv[X_S4]);
-    lk = k;
-    ev[E_R] = r_z;
-    static_assert(NEV == 17, "tl::EVALS lists the evaluations in this enum's order");
-    for (int i = 0; i < NEV; ++i) {
-      ts[b].append_scalar(tl::EVALS[i], ev[i]);
-      put(out[b].evaluations[i], ev[i]);
+      lin_c.insert(lin_c.end(), terms[i].coeff.l, terms[i].coeff.l + 4);
     }
-    aw[b] = ts[b].challenge_scalar(tl::AGGREGATE);
-    aws[b] = ts[b].challenge_scalar(tl::AGGREGATE);
+    cz_c.insert(cz_c.end(), pr[b].c_z.l, pr[b].c_z.l + 4);
+    pr[b].finish_round4(&out[b]);
   }
   PK_TRY(pm::lincomb_batch(ctx, ws->stage, lk, lin_v, lin_s, lin_c.data(), B, n, R, S, ctx->stream));
   if (zk) {   // beyond n only the blinded z has coefficients
@@ -496,31 +337,18 @@ int prove_batch_body(pm_ctx* ctx, pm_prover_key* pk, pm_plonk_batch* ws, const p
     const size_t sh_s[4] = {S, 4 * S, 4 * S, 4 * S};
     std::vector<u64> agg_c(12 * 4 * (size_t)B), sh_c(4 * 4 * (size_t)B), zs(8 * (size_t)B);
     for (uint32_t b = 0; b < B; ++b) {
-      const HFr zn = fpow(zc[b], n);
-      HFr ac[12];
-      ac[0] = one;
-      ac[1] = zn;
-      ac[2] = fmul(zn, zn);
-      ac[3] = fmul(ac[2], zn);
-      HFr vp = one;
-      for (int e = 0; e < 8; ++e) {
-        vp = fmul(vp, aw[b]);
-        ac[4 + e] = vp;
-      }
+      HFr ac[12], sh[4];
+      aggregation_coeffs(pr[b], n, ac, sh);
       for (int i = 0; i < 12; ++i) put(&agg_c[4 * (12 * (size_t)b + i)], ac[i]);
-      vp = one;
-      for (int e = 0; e < 4; ++e) {
-        put(&sh_c[4 * (4 * (size_t)b + e)], vp);
-        vp = fmul(vp, aws[b]);
-      }
-      put(&zs[4 * (size_t)b], zc[b]);
-      put(&zs[4 * ((size_t)B + b)], zw[b]);
+      for (int e = 0; e < 4; ++e) put(&sh_c[4 * (4 * (size_t)b + e)], sh[e]);
+      put(&zs[4 * (size_t)b], pr[b].ch[C_Z]);
+      put(&zs[4 * ((size_t)B + b)], pr[b].zw);
     }
     PK_TRY(pm::lincomb_batch(ctx, ws->stage, 12, agg_v, agg_s, agg_c.data(), B, n, AGG, S, ctx->stream));
     if (zk) {   // the padded tails: t pieces, r and the wires (the sigmas end at n)
       const void* tail_v[9];
       std::vector<u64> tail_c(9 * 4 * (size_t)B);
-      for (int i = 0; i < 9; ++i) tail_v[i] = at((void*)agg_v[i], n);
+      for (int i = 0; i < 9; ++i) tail_v[i] = at(agg_v[i], n);
       for (uint32_t b = 0; b < B; ++b) memcpy(&tail_c[9 * 4 * (size_t)b], &agg_c[12 * 4 * (size_t)b], 9 * 32);
       PK_TRY(pm::lincomb_batch(ctx, ws->stage, 9, tail_v, agg_s, tail_c.data(), B, S - n, at(AGG, n), S, ctx->stream));
     }
@@ -534,10 +362,7 @@ int prove_batch_body(pm_ctx* ctx, pm_prover_key* pk, pm_plonk_batch* ws, const p
   for (uint32_t b = 0; b < B; ++b) {
     memcpy(out[b].commitments[9], wxy[b], 96);
     memcpy(out[b].commitments[10], wxy[B + b], 96);
-    ts[b].append_commitment(tl::W_Z, out[b].commitments[9]);
-    ts[b].append_commitment(tl::W_ZW, out[b].commitments[10]);
-    const HFr chal[10] = {beta[b], gamma[b], alpha[b], range_sep[b], logic_sep[b], fixed_sep[b], var_sep[b], zc[b], aw[b], aws[b]};
-    for (int i = 0; i < 10; ++i) put(out[b].challenges[i], chal[i]);
+    pr[b].absorb_witnesses_and_store(&out[b]);
   }
   return PM_OK;
 }
@@ -572,7 +397,6 @@ extern "C" int pm_plonk_batch_create(pm_ctx* ctx, const pm_prover_key* key, uint
   ws->key = key;
   ws->max_batch = max_batch;
   ws->n = n;
-  struct Region { void** p; size_t bytes; };
   const size_t bn = B * n * 32;
   const size_t const_bytes = BATCH_CONST_BYTES_FIXED + B * BATCH_CONST_BYTES_PER_PROOF;
   void* consts_d = nullptr;
@@ -584,8 +408,7 @@ extern "C" int pm_plonk_batch_create(pm_ctx* ctx, const pm_prover_key* key, uint
                             {&ws->eval_ws, pm::evaluate_batch_ws_bytes(BATCH_EVAL_SLOTS, max_batch, n)},
                             {&ws->ruf_ws, pm::ruffini_batch_ws_bytes(2 * max_batch, n)},
                             {&consts_d, const_bytes}};
-  size_t total = 0;
-  for (const Region& r : regions) total += (r.bytes + 255) / 256 * 256;
+  const size_t total = carve_regions(nullptr, regions);
   int rc = pm_dev_alloc(ctx, total, &ws->base);
   if (rc) {
     (void)hipGetLastError();   // a refused hipMalloc stays the thread's last error: the next launch check would report it
@@ -593,11 +416,7 @@ extern "C" int pm_plonk_batch_create(pm_ctx* ctx, const pm_prover_key* key, uint
     return rc == PM_ERR_OOM ? pm::set_err(ctx, PM_ERR_OOM, "the batch workspace does not fit in device memory") : rc;
   }
   ws->bytes = total;
-  size_t off = 0;
-  for (const Region& r : regions) {
-    *r.p = (char*)ws->base + off;
-    off += (r.bytes + 255) / 256 * 256;
-  }
+  carve_regions(ws->base, regions);
   if (hipHostMalloc(&ws->stage.h, const_bytes, hipHostMallocDefault) != hipSuccess) {
     ws->stage.h = nullptr;
     rc = pm::set_err(ctx, PM_ERR_OOM, "pinned host memory for the batch's constant tables");
@@ -621,7 +440,7 @@ extern "C" size_t pm_plonk_batch_bytes(const pm_plonk_batch* ws) { return ws ? w
 extern "C" int pm_plonk_batch_enable_zk(pm_ctx* ctx, pm_plonk_batch* ws, size_t* added_bytes) {
   if (!ctx) return PM_ERR_BAD_ARG;
   if (!ws) return pm::set_err(ctx, PM_ERR_BAD_ARG, "null argument");
-  BatchBusy guard(ws);
+  Busy guard(ws->busy);
   if (!guard.ok) return pm::set_err(ctx, PM_ERR_BUSY, "the batch workspace is in use by another call");
   if (ws->zk) {
     if (added_bytes) *added_bytes = ws->zk->bytes;
@@ -631,15 +450,13 @@ extern "C" int pm_plonk_batch_enable_zk(pm_ctx* ctx, pm_plonk_batch* ws, size_t*
   const size_t n = ws->n, B = ws->max_batch, S = n + ZK_PAD;
   BatchZk* zk = new BatchZk();
   zk->stride = S;
-  struct Region { void** p; size_t bytes; };
   const size_t bn = B * n * 32, bs = B * S * 32;
   const Region regions[] = {{&zk->coeffs, 4 * bs},    {&zk->zc, bs},           {&zk->shift, 4 * bs},     {&zk->shift_pi, bn},
                             {&zk->coset2_w, 16 * bn}, {&zk->coset2_z, 4 * bn}, {&zk->coset2_pi, 4 * bn}, {&zk->ab, 8 * bn},
                             {&zk->t, 4 * bs},         {&zk->r, bs},            {&zk->agg, 2 * bs},       {&zk->wit, 2 * bs},
                             {&zk->eval_ws, pm::evaluate_batch_ws_bytes(BATCH_EVAL_SLOTS, ws->max_batch, S)},
                             {&zk->ruf_ws, pm::ruffini_batch_ws_bytes(2 * ws->max_batch, S)}};
-  size_t total = 0;
-  for (const Region& r : regions) total += (r.bytes + 255) / 256 * 256;
+  const size_t total = carve_regions(nullptr, regions);
   const int rc = pm_dev_alloc(ctx, total, &zk->base);
   if (rc) {
     (void)hipGetLastError();   // as in pm_plonk_batch_create: a refused hipMalloc must not stay the thread's last error
@@ -647,11 +464,7 @@ extern "C" int pm_plonk_batch_enable_zk(pm_ctx* ctx, pm_plonk_batch* ws, size_t*
     return rc == PM_ERR_OOM ? pm::set_err(ctx, PM_ERR_OOM, "the zero-knowledge regions of the batch workspace do not fit in device memory") : rc;
   }
   zk->bytes = total;
-  size_t off = 0;
-  for (const Region& r : regions) {
-    *r.p = (char*)zk->base + off;
-    off += (r.bytes + 255) / 256 * 256;
-  }
+  carve_regions(zk->base, regions);
   ws->zk = zk;
   if (added_bytes) *added_bytes = total;
   return PM_OK;
@@ -668,9 +481,7 @@ static int prove_batch_entry(pm_ctx* ctx, pm_prover_key* pk, pm_plonk_batch* ws,
   if (!pk || !ws || !ck || !d_witnesses || !out) return pm::set_err(ctx, PM_ERR_BAD_ARG, "null argument");
   if (ws->key != pk) return pm::set_err(ctx, PM_ERR_BAD_ARG, "the batch workspace was made for another key");
   if (batch == 0 || batch > ws->max_batch) return pm::set_err(ctx, PM_ERR_BAD_ARG, "batch must be in 1..max_batch of the workspace");
-  if (flags & ~(PM_PLONK_BIND_PUBLIC_INPUTS | PM_PLONK_UPSTREAM_TRANSCRIPT)) return pm::set_err(ctx, PM_ERR_BAD_ARG, "unknown flags");
-  if (flags == (PM_PLONK_BIND_PUBLIC_INPUTS | PM_PLONK_UPSTREAM_TRANSCRIPT))
-    return pm::set_err(ctx, PM_ERR_BAD_ARG, "PM_PLONK_BIND_PUBLIC_INPUTS and PM_PLONK_UPSTREAM_TRANSCRIPT exclude each other");
+  PK_TRY(check_flags(ctx, flags));
   if (!pk->committed) return pm::set_err(ctx, PM_ERR_BAD_ARG, "the key is not committed (pm_plonk_key_commit first)");
   if (zero_knowledge) {
     if (!blinders) return pm::set_err(ctx, PM_ERR_BAD_ARG, "null blinders");
@@ -678,7 +489,7 @@ static int prove_batch_entry(pm_ctx* ctx, pm_prover_key* pk, pm_plonk_batch* ws,
       for (int i = 0; i < PM_PLONK_ZK_BLINDERS; ++i)
         if (pm::host::geq<4>(blinders[b][i], FRF().m)) return pm::set_err(ctx, PM_ERR_BAD_ARG, "a blinder is not below r");
   }
-  BatchBusy guard(ws);
+  Busy guard(ws->busy);
   if (!guard.ok) return pm::set_err(ctx, PM_ERR_BUSY, "the batch workspace is in use by another call");
   if (zero_knowledge && (!ws->zk || !pk->zk))
     return pm::set_err(ctx, PM_ERR_BAD_ARG, "the batch workspace is not ready for zero-knowledge proofs (pm_plonk_batch_enable_zk first)");

@@ -1,6 +1,6 @@
 // The prover with COEFFICIENT-RANGE OWNERSHIP END TO END (SURVEY.md section 8e row 3 + section 8f N5; BASELINE.json configs[4]):
-// included at the end of prover.hip (it shares the transcript, the widget scalars and the label table with the
-// single-GPU prover -- both must produce the same bytes).
+// included at the end of prover.hip (the host side of the rounds is prover_rounds.h, as for the single-GPU prover -- both
+// must produce the same bytes).
 //
 // pm_plonk_prove_sharded replicates every transform, the quotient and the openings on all ranks and only splits the MSMs;
 // at 2^24 gates that is ~70 GB of workspace per rank and an Amdahl floor of ~16 % of a proof.  Here rank r of W owns
@@ -147,14 +147,6 @@ int commit_batch_dist(pm_ctx* ctx, Dist& D, const pm_dist_key* pk, const pm_base
   PK_TRY(dist_points(ctx, D, xyz, batch));
   return pm_g1_to_affine_batch(xyz, batch, &out_xy[0][0], nullptr);
 }
-struct DistBusy {
-  pm_dist_key* pk;
-  bool ok;
-  explicit DistBusy(pm_dist_key* k) : pk(k), ok(!k->busy.exchange(true)) {}
-  ~DistBusy() {
-    if (ok) pk->busy.store(false);
-  }
-};
 int dist_check(const pm_dist* d, size_t n) {
   if (!d || d->world == 0 || (d->world & (d->world - 1)) || d->rank >= d->world) return PM_ERR_BAD_ARG;
   if (n < 4 || (n & (n - 1))) return PM_ERR_LENGTH;
@@ -345,14 +337,7 @@ static int preprocess_dist_body(pm_ctx* ctx, Dist& D, pm_dist_key* pk, const uin
     PK_TRY(dist_to_coset(ctx, D, pk, src, 2, pk->lx_coset, nullptr));
   }
   PK_TRY(pm_sync(ctx));
-  {
-    const HFr gn = fpow(g, n), i4 = fpow(omega4, n);
-    HFr p = one;
-    for (int k = 0; k < 4; ++k) {
-      pk->zh_inv[k] = finv(fsub(fmul(gn, p), one));
-      p = fmul(p, i4);
-    }
-  }
+  zh_inv_period4(g, omega4, n, pk->zh_inv);
   return PM_OK;
 }
 
@@ -394,12 +379,7 @@ extern "C" int pm_plonk_key_commit_dist(pm_ctx* ctx, const pm_dist* dist, pm_dis
     if (pm_g1_bases_len(ck_slice) < pk->m) return PM_ERR_LENGTH;   // powers [rank m, (rank + 1) m) of the commit key
     PK_TRY(commit_batch_dist(ctx, D, pk, ck_slice, pk->sel_coeffs, pk->n, NSEL, &pk->vk[0]));
     PK_TRY(commit_batch_dist(ctx, D, pk, ck_slice, pk->sigma_coeffs, pk->n, 4, &pk->vk[NSEL]));
-    Transcript ts(transcript_label ? transcript_label : tl::PROTOCOL);
-    for (int i = 0; i < NSEL; ++i) ts.append_commitment(SEL_LABELS[i], pk->vk[SEL_SEED_ORDER[i]]);
-    for (int j = 0; j < 4; ++j) ts.append_commitment(SIGMA_LABELS[j], pk->vk[NSEL + j]);
-    ts.append(tl::DOM_SEP, (const uint8_t*)tl::DOM_SEP_VALUE, strlen(tl::DOM_SEP_VALUE));
-    ts.append_u64(tl::CIRCUIT_SIZE, pk->n);
-    pk->base = ts;
+    pk->base = key_transcript(transcript_label, pk->vk, pk->n);
     pk->committed = true;
     if (vk_out) memcpy(vk_out, pk->vk, sizeof pk->vk);
     return PM_OK;
@@ -413,10 +393,9 @@ static int prove_dist_body(pm_ctx* ctx, Dist& D, pm_dist_key* pk, const pm_bases
   if (!pk || !ck || !d_witness || !out) return PM_ERR_BAD_ARG;
   if (D.d.world != pk->world || D.d.rank != pk->rank) return PM_ERR_BAD_ARG;
   if (n_pi && (!pi_positions || !pi_values)) return PM_ERR_BAD_ARG;
-  if (flags & ~(PM_PLONK_BIND_PUBLIC_INPUTS | PM_PLONK_UPSTREAM_TRANSCRIPT)) return PM_ERR_BAD_ARG;
-  if (flags == (PM_PLONK_BIND_PUBLIC_INPUTS | PM_PLONK_UPSTREAM_TRANSCRIPT)) return PM_ERR_BAD_ARG;
+  PK_TRY(check_flags(ctx, flags));
   if (!pk->committed) return PM_ERR_BAD_ARG;
-  DistBusy guard(pk);
+  Busy guard(pk->busy);
   if (!guard.ok) return PM_ERR_BUSY;
   const size_t n = pk->n, m = pk->m, lo = pk->lo;
   const uint32_t W = pk->world, rk = pk->rank;
@@ -443,14 +422,8 @@ static int prove_dist_body(pm_ctx* ctx, Dist& D, pm_dist_key* pk, const pm_bases
       if (all[r].l[0] != h || all[r].l[1] != (u64)n)
         return pm::set_err(ctx, PM_ERR_BAD_ARG, "the ranks were given different public inputs, flags or circuit sizes");
   }
-  Transcript ts = pk->base;
-  if (!(flags & PM_PLONK_UPSTREAM_TRANSCRIPT)) {
-    ts.append_u64(tl::PI_LEN, n_pi);
-    for (size_t i = 0; i < n_pi; ++i) {
-      ts.append_u64(tl::PI_POS, pi_positions[i]);
-      ts.append_scalar(tl::PI_VALUE, get(pi_values + 4 * i));
-    }
-  }
+  ProofRounds pr(pk->base);
+  pr.begin(flags, pi_positions, pi_values, n_pi);
   const HFr one = fone();
   const size_t n2 = pk->n2;
   auto coset = [&](int j) { return at(pk->coset_a, 4 * m * j); };   // planes of a, b, c, d (j < 4) and the public inputs (4)
@@ -471,21 +444,11 @@ static int prove_dist_body(pm_ctx* ctx, Dist& D, pm_dist_key* pk, const pm_bases
     PK_TRY(dist_to_coset(ctx, D, pk, src, 5, pk->coset_a, pk->halo_a));
   }
   PK_TRY(commit_batch_dist(ctx, D, pk, ck, pk->coeffs, n, 4, &out->commitments[0]));
-  for (int j = 0; j < 4; ++j) ts.append_commitment(tl::WIRES[j], out->commitments[j]);
+  pr.absorb_wires(&out->commitments[0]);
   // ---- round 2 --------------------------------------------------------------------------------
-  const HFr beta = ts.challenge_scalar(tl::BETA);
-  ts.append_scalar(tl::BETA, beta);
-  const HFr gamma = ts.challenge_scalar(tl::GAMMA);
+  pr.draw_round2();
   pm_plonk_perm_args pa;
-  memset(&pa, 0, sizeof pa);
-  for (int j = 0; j < 4; ++j) {
-    pa.wires[j] = at((void*)d_witness, j * m);
-    pa.sigmas[j] = at(pk->sigma_evals, j * m);
-  }
-  pa.roots = pk->roots;
-  put(pa.beta, beta);
-  put(pa.gamma, gamma);
-  for (int j = 0; j < 3; ++j) put(pa.k[j], pk->k[j]);
+  fill_perm_args(pa, d_witness, m, pk->sigma_evals, m, pk->roots, pk->k, pr.ch[C_BETA], pr.ch[C_GAMMA]);
   PK_TRY(pm_plonk_perm_terms_dev(ctx, &pa, m, pk->num, pk->den, nullptr));
   PK_TRY(pm::fr_batch_inverse_mul(ctx, pk->den, pk->num, m, nullptr));    // den[i] <- num[i] / den[i]
   PK_TRY(pm_fr_prefix_product_dev(ctx, pk->den, m, pk->num, nullptr));   // num[i] = product of this rank's ratios [0 .. i)
@@ -509,43 +472,15 @@ static int prove_dist_body(pm_ctx* ctx, Dist& D, pm_dist_key* pk, const pm_bases
     PK_TRY(dist_to_coset(ctx, D, pk, src, 1, pk->coset_z, pk->halo_z));
   }
   PK_TRY(commit_batch_dist(ctx, D, pk, ck, z_coeffs, n, 1, &out->commitments[4]));
-  ts.append_commitment(tl::PERM, out->commitments[4]);
+  pr.absorb_perm(out->commitments[4]);
   // ---- round 3 --------------------------------------------------------------------------------
-  const HFr alpha = ts.challenge_scalar(tl::ALPHA);
-  const HFr range_sep = ts.challenge_scalar(tl::RANGE_SEP);
-  const HFr logic_sep = ts.challenge_scalar(tl::LOGIC_SEP);
-  const HFr fixed_sep = ts.challenge_scalar(tl::FIXED_SEP);
-  const HFr var_sep = ts.challenge_scalar(tl::VAR_SEP);
+  pr.draw_round3();
   pm_plonk_quotient_args qa;
-  memset(&qa, 0, sizeof qa);
-  for (int j = 0; j < 4; ++j) {
-    qa.wires[j] = coset(j);
-    qa.sigmas[j] = at(pk->sigma_coset, 4 * m * j);
+  {
+    QuotientTables kt{{}, pk->sigma_coset, 4 * m, pk->lx_coset, at(pk->lx_coset, 4 * m), pk->zh_inv};
+    for (int s = 0; s < NSEL; ++s) kt.sel[s] = pk->sel_coset[s];
+    fill_quotient_args(qa, kt, pk->coset_a, 4 * m, pk->coset_z, coset(4), pk->k, pr.ch);
   }
-  qa.z = pk->coset_z;
-  qa.pi = coset(4);
-  qa.q_m = pk->sel_coset[Q_M];
-  qa.q_l = pk->sel_coset[Q_L];
-  qa.q_r = pk->sel_coset[Q_R];
-  qa.q_o = pk->sel_coset[Q_O];
-  qa.q_c = pk->sel_coset[Q_C];
-  qa.q_4 = pk->sel_coset[Q_4];
-  qa.q_arith = pk->sel_coset[Q_ARITH];
-  qa.q_range = pk->sel_coset[Q_RANGE];
-  qa.q_logic = pk->sel_coset[Q_LOGIC];
-  qa.q_fixed_group_add = pk->sel_coset[Q_FIXED];
-  qa.q_variable_group_add = pk->sel_coset[Q_VAR];
-  qa.l1 = pk->lx_coset;
-  qa.x = at(pk->lx_coset, 4 * m);
-  put(qa.alpha, alpha);
-  put(qa.beta, beta);
-  put(qa.gamma, gamma);
-  put(qa.range_sep, range_sep);
-  put(qa.logic_sep, logic_sep);
-  put(qa.fixed_sep, fixed_sep);
-  put(qa.var_sep, var_sep);
-  for (int j = 0; j < 3; ++j) put(qa.k[j], pk->k[j]);
-  for (int j = 0; j < 4; ++j) put(qa.zh_inv[j], pk->zh_inv[j]);
   {
     // the same kernel on the rank's 4 m points, planar layout: "one row further" is index + n2, and past the rank's last row
     // the halo rows of a, b, d and z that came with the transforms (the last rank's are rank 0's first rows, shifted by one)
@@ -578,134 +513,64 @@ static int prove_dist_body(pm_ctx* ctx, Dist& D, pm_dist_key* pk, const pm_bases
     }
   }
   PK_TRY(commit_batch_dist(ctx, D, pk, ck, pk->t, n, 4, &out->commitments[5]));
-  for (int i = 0; i < 4; ++i) ts.append_commitment(tl::QUOTIENT[i], out->commitments[5 + i]);
+  pr.absorb_quotient(&out->commitments[5]);
   // ---- round 4 --------------------------------------------------------------------------------
-  const HFr zc = ts.challenge_scalar(tl::Z_CHALLENGE), zw = fmul(zc, pk->omega);
-  enum { E_A, E_B, E_C, E_D, E_AN, E_BN, E_DN, E_S1, E_S2, E_S3, E_QARITH, E_QC, E_QL, E_QR, E_ZN, E_T, E_R, NEV };
-  HFr ev[NEV];
+  pr.draw_z(pk->omega);
+  const HFr &zc = pr.ch[C_Z], &zw = pr.zw;
   const HFr zc_lo = fpow64(zc, lo), zw_lo = fpow64(zw, lo);
-  // r(z) is the linear combination of the values at z of the polynomials r combines (prover.hip, round 4): the ones the proof
-  // does not open ride along as a second group -- one host synchronisation and ONE exchange for all openings, none for r
-  enum { X_QM, X_QO, X_Q4, X_Z, X_S4, X_RANGE, X_LOGIC, X_FIXED, X_VAR, NX };
-  HFr xv[NX];
-  {
-    // openings: every rank evaluates its coefficient slice (sum_i c_{lo + i} z^i), scales by z^lo, and the sums go round
-    const void* at_z[15];
-    const void* at_x[NX];
-    u64 out_z[15][4], out_x[NX][4], out_zw[4][4];
-    for (int j = 0; j < 4; ++j) at_z[j] = at(pk->coeffs, j * m);
-    for (int j = 0; j < 3; ++j) at_z[4 + j] = at(pk->sigma_coeffs, j * m);
-    at_z[7] = at(pk->sel_coeffs, Q_ARITH * m);
-    at_z[8] = at(pk->sel_coeffs, Q_C * m);
-    at_z[9] = at(pk->sel_coeffs, Q_L * m);
-    at_z[10] = at(pk->sel_coeffs, Q_R * m);
-    for (int i = 0; i < 4; ++i) at_z[11 + i] = at(pk->t, i * m);
-    at_x[X_QM] = at(pk->sel_coeffs, Q_M * m);
-    at_x[X_QO] = at(pk->sel_coeffs, Q_O * m);
-    at_x[X_Q4] = at(pk->sel_coeffs, Q_4 * m);
-    at_x[X_Z] = z_coeffs;
-    at_x[X_S4] = at(pk->sigma_coeffs, 3 * m);
-    uint32_t nx = X_RANGE;
-    const int wsel[4] = {Q_RANGE, Q_LOGIC, Q_FIXED, Q_VAR};
-    int xslot[4] = {-1, -1, -1, -1};
-    for (int w = 0; w < 4; ++w)
-      if (!pk->sel_zero[wsel[w]]) {
-        xslot[w] = (int)nx;
-        at_x[nx++] = at(pk->sel_coeffs, wsel[w] * m);
-      }
-    const void* at_zw[4] = {at(pk->coeffs, 0), at(pk->coeffs, m), at(pk->coeffs, 3 * m), z_coeffs};
-    const uint32_t gk[3] = {15, nx, 4};
-    const void* const* gp[3] = {at_z, at_x, at_zw};
-    const uint64_t* gpt[3] = {zc.l, zc.l, zw.l};
-    uint64_t* gout[3] = {&out_z[0][0], &out_x[0][0], &out_zw[0][0]};
-    PK_TRY(pm::poly_evaluate_groups(ctx, 3, gk, gp, gpt, gout, m));
-    constexpr uint32_t NP = 15 + 4 + NX;
-    HFr part[NP];
-    for (int j = 0; j < 15; ++j) part[j] = fmul(get(out_z[j]), zc_lo);
-    for (int j = 0; j < 4; ++j) part[15 + j] = fmul(get(out_zw[j]), zw_lo);
-    for (uint32_t j = 0; j < NX; ++j) part[19 + j] = j < nx ? fmul(get(out_x[j]), zc_lo) : pm::host::zero<4>();
-    std::vector<HFr> all;
-    PK_TRY(dist_scalars(ctx, D, part, NP, all));
-    HFr sum[NP];
-    for (uint32_t j = 0; j < NP; ++j) {
-      sum[j] = pm::host::zero<4>();
-      for (uint32_t r = 0; r < W; ++r) sum[j] = fadd(sum[j], all[(size_t)r * NP + j]);
+  auto poly = [&](PolyRef p) -> const void* {   // this rank's slice [lo, lo + m) of the polynomial's coefficients
+    switch (p.role) {
+      case R_WIRE: return at(pk->coeffs, p.index * m);
+      case R_T: return at(pk->t, p.index * m);
+      case R_Z: return z_coeffs;
+      case R_SIGMA: return at(pk->sigma_coeffs, p.index * m);
+      default: return at(pk->sel_coeffs, p.index * m);
     }
-    for (int j = 0; j < 4; ++j) ev[E_A + j] = sum[j];
-    for (int j = 0; j < 3; ++j) ev[E_S1 + j] = sum[4 + j];
-    ev[E_QARITH] = sum[7];
-    ev[E_QC] = sum[8];
-    ev[E_QL] = sum[9];
-    ev[E_QR] = sum[10];
-    ev[E_AN] = sum[15];
-    ev[E_BN] = sum[16];
-    ev[E_DN] = sum[17];
-    ev[E_ZN] = sum[18];
-    const HFr zn_ = fpow(zc, n);
-    ev[E_T] = fadd(sum[11], fmul(zn_, fadd(sum[12], fmul(zn_, fadd(sum[13], fmul(zn_, sum[14]))))));
-    for (int j = 0; j < X_RANGE; ++j) xv[j] = sum[19 + j];
-    for (int w = 0; w < 4; ++w) xv[X_RANGE + w] = xslot[w] >= 0 ? sum[19 + xslot[w]] : pm::host::zero<4>();
-  }
-  const HFr zn = fpow(zc, n);
-  const HFr &a_ = ev[E_A], &b_ = ev[E_B], &c_ = ev[E_C], &d_ = ev[E_D], &s1 = ev[E_S1], &s2 = ev[E_S2], &s3 = ev[E_S3],
-            &z_next = ev[E_ZN], &qar = ev[E_QARITH];
-  const HFr l1_z = fmul(fsub(zn, one), finv(fmul(fr_u64(n), fsub(zc, one))));
-  const HFr bz = fmul(beta, zc);
-  HFr ident = fadd(fadd(a_, bz), gamma);
-  const HFr* wv[3] = {&b_, &c_, &d_};
-  for (int j = 0; j < 3; ++j) ident = fmul(ident, fadd(fadd(*wv[j], fmul(bz, pk->k[j])), gamma));
-  const HFr copy3 = fmul(fmul(fadd(fadd(a_, fmul(beta, s1)), gamma), fadd(fadd(b_, fmul(beta, s2)), gamma)),
-                         fadd(fadd(c_, fmul(beta, s3)), gamma));
-  const HFr alpha2 = fmul(alpha, alpha);
-  RowEvals re{a_, b_, c_, d_, ev[E_AN], ev[E_BN], ev[E_DN], ev[E_QL], ev[E_QR], ev[E_QC]};
+  };
   {
+    // openings: every rank evaluates its coefficient slice (sum_i c_{lo + i} z^i), scales by z^lo, and the sums go round --
+    // one host synchronisation and ONE exchange for all openings, none for r (its value comes from theirs: prover_rounds.h)
+    const OpeningPlan plan(pk->sel_zero);
+    const void* ptr[MAX_OPENINGS];
+    u64 val[MAX_OPENINGS][4];
+    for (uint32_t s = 0; s < plan.count; ++s) ptr[s] = poly(plan.slot[s].poly);
+    const uint32_t w0 = plan.next_row();
+    const uint32_t gk[3] = {OPENINGS_AT_Z, plan.nx, 4};
+    const void* const* gp[3] = {ptr, ptr + OPENINGS_AT_Z, ptr + w0};
+    const uint64_t* gpt[3] = {zc.l, zc.l, zw.l};
+    uint64_t* gout[3] = {val[0], val[OPENINGS_AT_Z], val[w0]};
+    PK_TRY(pm::poly_evaluate_groups(ctx, 3, gk, gp, gpt, gout, m));
+    HFr part[MAX_OPENINGS], sum[MAX_OPENINGS];   // the message has MAX_OPENINGS scalars whatever the circuit opens
+    for (uint32_t s = 0; s < MAX_OPENINGS; ++s)
+      part[s] = s < plan.count ? fmul(get(val[s]), plan.slot[s].point ? zw_lo : zc_lo) : pm::host::zero<4>();
+    std::vector<HFr> all;
+    PK_TRY(dist_scalars(ctx, D, part, MAX_OPENINGS, all));
+    for (uint32_t s = 0; s < MAX_OPENINGS; ++s) {
+      sum[s] = pm::host::zero<4>();
+      for (uint32_t r = 0; r < W; ++r) sum[s] = fadd(sum[s], all[(size_t)r * MAX_OPENINGS + s]);
+    }
+    pr.take_openings(plan, sum[0].l, n);
+  }
+  {
+    LinTerm terms[12];
     const void* lin_v[12];
     u64 lin_c[12][4];
-    uint32_t k = 0;
-    HFr r_z = pm::host::zero<4>();
-    auto term = [&](const void* v, const HFr& c, const HFr& value_at_z) {
-      lin_v[k] = v;
-      put(lin_c[k], c);
-      r_z = fadd(r_z, fmul(c, value_at_z));
-      ++k;
-    };
-    term(at(pk->sel_coeffs, Q_M * m), fmul(qar, fmul(a_, b_)), xv[X_QM]);
-    term(at(pk->sel_coeffs, Q_L * m), fmul(qar, a_), ev[E_QL]);
-    term(at(pk->sel_coeffs, Q_R * m), fmul(qar, b_), ev[E_QR]);
-    term(at(pk->sel_coeffs, Q_O * m), fmul(qar, c_), xv[X_QO]);
-    term(at(pk->sel_coeffs, Q_4 * m), fmul(qar, d_), xv[X_Q4]);
-    term(at(pk->sel_coeffs, Q_C * m), qar, ev[E_QC]);
-    if (!pk->sel_zero[Q_RANGE]) term(at(pk->sel_coeffs, Q_RANGE * m), widget_range(range_sep, re), xv[X_RANGE]);
-    if (!pk->sel_zero[Q_LOGIC]) term(at(pk->sel_coeffs, Q_LOGIC * m), widget_logic(logic_sep, re), xv[X_LOGIC]);
-    if (!pk->sel_zero[Q_FIXED]) term(at(pk->sel_coeffs, Q_FIXED * m), widget_fixed(fixed_sep, re), xv[X_FIXED]);
-    if (!pk->sel_zero[Q_VAR]) term(at(pk->sel_coeffs, Q_VAR * m), widget_var(var_sep, re), xv[X_VAR]);
-    term(z_coeffs, fadd(fmul(alpha, ident), fmul(alpha2, l1_z)), xv[X_Z]);
-    term(at(pk->sigma_coeffs, 3 * m), fneg(fmul(fmul(fmul(alpha, copy3), beta), z_next)), xv[X_S4]);
+    uint32_t k;
+    linearise(pr, pk->k, n, pk->sel_zero, terms, &k);
+    for (uint32_t i = 0; i < k; ++i) {
+      lin_v[i] = poly(terms[i].poly);
+      put(lin_c[i], terms[i].coeff);
+    }
     PK_TRY(pm_fr_lincomb_dev(ctx, k, lin_v, &lin_c[0][0], m, pk->r, nullptr));
-    ev[E_R] = r_z;
   }
-  static_assert(NEV == 17, "tl::EVALS lists the evaluations in this enum's order");
-  for (int i = 0; i < NEV; ++i) {
-    ts.append_scalar(tl::EVALS[i], ev[i]);
-    put(out->evaluations[i], ev[i]);
-  }
+  pr.finish_round4(out);
   // ---- round 5 --------------------------------------------------------------------------------
-  const HFr aw = ts.challenge_scalar(tl::AGGREGATE);
-  const HFr aws = ts.challenge_scalar(tl::AGGREGATE);
   void *agg1 = pk->agg, *agg2 = at(pk->agg, m);
   {
     const void* agg_v[12];
-    u64 agg_c[12][4];
-    HFr ac[12];
-    ac[0] = one;
-    ac[1] = zn;
-    ac[2] = fmul(zn, zn);
-    ac[3] = fmul(ac[2], zn);
-    HFr vp = one;
-    for (int e = 0; e < 8; ++e) {
-      vp = fmul(vp, aw);
-      ac[4 + e] = vp;
-    }
+    u64 agg_c[12][4], sh_c[4][4];
+    HFr ac[12], sh[4];
+    aggregation_coeffs(pr, n, ac, sh);
     for (int i = 0; i < 4; ++i) agg_v[i] = at(pk->t, i * m);
     agg_v[4] = pk->r;
     for (int j = 0; j < 4; ++j) agg_v[5 + j] = at(pk->coeffs, j * m);
@@ -713,12 +578,7 @@ static int prove_dist_body(pm_ctx* ctx, Dist& D, pm_dist_key* pk, const pm_bases
     for (int i = 0; i < 12; ++i) put(agg_c[i], ac[i]);
     PK_TRY(pm_fr_lincomb_dev(ctx, 12, agg_v, &agg_c[0][0], m, agg1, nullptr));
     const void* sh_v[4] = {z_coeffs, at(pk->coeffs, 0), at(pk->coeffs, m), at(pk->coeffs, 3 * m)};
-    u64 sh_c[4][4];
-    vp = one;
-    for (int e = 0; e < 4; ++e) {
-      put(sh_c[e], vp);
-      vp = fmul(vp, aws);
-    }
+    for (int e = 0; e < 4; ++e) put(sh_c[e], sh[e]);
     PK_TRY(pm_fr_lincomb_dev(ctx, 4, sh_v, &sh_c[0][0], m, agg2, nullptr));
   }
   {
@@ -745,10 +605,7 @@ static int prove_dist_body(pm_ctx* ctx, Dist& D, pm_dist_key* pk, const pm_bases
     }
   }
   PK_TRY(commit_batch_dist(ctx, D, pk, ck, pk->wit, n - 1, 2, &out->commitments[9]));
-  ts.append_commitment(tl::W_Z, out->commitments[9]);
-  ts.append_commitment(tl::W_ZW, out->commitments[10]);
-  const HFr chal[10] = {beta, gamma, alpha, range_sep, logic_sep, fixed_sep, var_sep, zc, aw, aws};
-  for (int i = 0; i < 10; ++i) put(out->challenges[i], chal[i]);
+  pr.absorb_witnesses_and_store(out);
   return PM_OK;
 }
 

@@ -44,7 +44,7 @@ _labels_cache: dict | None = None
 
 
 def transcript_labels() -> dict:
-    """Every label string of the transcript, from the ONE table both sides use (csrc/prover.hip, namespace tl, through
+    """Every label string of the transcript, from the ONE table both sides use (csrc/prover_transcript.h, namespace tl, through
     ``pm_plonk_transcript_labels``): {key: bytes}.  The labels are restated from the published dusk-plonk 0.8 design --
     parity-unpinned -- and that table is the single place to edit when upstream vectors become available."""
     global _labels_cache

@@ -127,7 +127,7 @@ def test_commit_key_raw_bytes_roundtrip(oracle):
 
 
 def test_transcript_label_table_is_the_single_source():
-    """Both sides of Fiat-Shamir read ONE table (csrc/prover.hip, namespace tl, exported by pm_plonk_transcript_labels):
+    """Both sides of Fiat-Shamir read ONE table (csrc/prover_transcript.h, namespace tl, exported by pm_plonk_transcript_labels):
     every message of a proof has its entry, in order, and the Python verifier side holds no label strings of its own."""
     import inspect
     import plonk_prototype_amd.prover as PR

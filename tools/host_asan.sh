@@ -1,10 +1,10 @@
 #!/bin/bash
 # Host-side AddressSanitizer and UndefinedBehaviorSanitizer builds of the library (device code untouched: -Xarch_host) and the CPU tests that run its pure-host
-# entry points under it (bucket-fill geometry, MSM sizing pass, transform plan, exchange fold, Keccak / transcript, ABI surface).
+# entry points under it (bucket-fill geometry, MSM sizing pass, transform plan, exchange fold, Keccak / transcript, linearisation scalars, ABI surface).
 # CPU only -- GPU sanitizer runs are not available on this pool.   usage: bash tools/host_asan.sh
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
-TESTS="tests/test_msm_geometry.py tests/test_ntt_plan.py tests/test_abi.py tests/test_transcript.py tests/test_domain_helpers.py tests/test_comm_deadline.py"
+TESTS="tests/test_msm_geometry.py tests/test_ntt_plan.py tests/test_abi.py tests/test_transcript.py tests/test_domain_helpers.py tests/test_comm_deadline.py tests/test_linearise_host.py"
 for SAN in address undefined; do
   B=$R/build_ab/san_${SAN}
   mkdir -p $B
