@@ -237,7 +237,6 @@ struct ZkShiftArgs {
 };
 struct ZkCombineConsts {
   uint32_t inv2[9], inv2s[9];            // 1 / 2 and 1 / (2 * 7^4n), device form
-  uint64_t beta[3][4];                   // the quotient blinders b_14 .. b_16
 };
 // w + (beta . X^i) Z_H on `count` vectors (stride S) in one launch
 int zk_blind(pm_ctx* ctx, const ZkBlindArgs& a, uint32_t count, size_t n, size_t stride, hipStream_t st);

@@ -65,17 +65,33 @@ __global__ void __launch_bounds__(256) powers_kernel(u32x4* out, size_t n, const
 }
 
 // ------------------------------------------------------------------ linear combination
+// out_b = sum_j c[b][j] v_j(b): term j of proof b at v[j] + b stride[j] (stride 0: a vector all proofs share, or one proof)
 struct LincombArgs {
   const u32x4* v[PM_LINCOMB_MAX];
-  u32 c[PM_LINCOMB_MAX][9];   // device form
+  size_t stride[PM_LINCOMB_MAX];
   u32 k;
 };
-__global__ void __launch_bounds__(256) lincomb_kernel(const LincombArgs a, u32x4* out, size_t n) {
+// The coefficients (device form): k of them in the arguments, or row blockIdx.y of a [batch][k] table
+struct CoeffArgs {
+  u32 c[PM_LINCOMB_MAX][9];
+  static PM_DEV u32 slot() { return 0; }
+  PM_DEV Fr coeff(u32, u32, u32 j) const { return fr_limbs(c[j]); }
+};
+struct CoeffTable {
+  const PM_KCONST u32 (*c)[9];
+  static PM_DEV u32 slot() { return blockIdx.y; }
+  PM_DEV Fr coeff(u32 b, u32 k, u32 j) const { return fr_limbs(kconst(c + (size_t)b * k, j)); }
+};
+template <class Src>
+__global__ void __launch_bounds__(256) lincomb_kernel(const LincombArgs a, const Src src, u32x4* out, size_t out_stride, size_t n) {
+  const u32 b = Src::slot();
   const size_t stride = (size_t)gridDim.x * blockDim.x;
+  out += 2 * (size_t)b * out_stride;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    Fr acc = fe_mul<FrP>(ld_canon(a.v[0], i), fr_limbs(a.c[0]));
+    Fr acc = fe_mul<FrP>(ld_canon(a.v[0] + 2 * (size_t)b * a.stride[0], i), src.coeff(b, a.k, 0));
     for (u32 j = 1; j < a.k; ++j)
-      acc = fe_reduce_weak<FrP>(fe_add<FrP>(acc, fe_mul<FrP>(ld_canon(a.v[j], i), fr_limbs(a.c[j]))));
+      acc = fe_reduce_weak<FrP>(
+          fe_add<FrP>(acc, fe_mul<FrP>(ld_canon(a.v[j] + 2 * (size_t)b * a.stride[j], i), src.coeff(b, a.k, j))));
     st_canon(out, i, acc);
   }
 }
@@ -88,7 +104,17 @@ struct PermPtrs {
   u32x4* num;
   u32x4* den;
 };
-__global__ void __launch_bounds__(256) perm_terms_kernel(const PermPtrs p, const RoundConsts kc, size_t n) {
+// Src: FromArgs<RoundConsts> (one proof) or FromTable<RoundConsts> (blockIdx.y = proof: its wires at w[j] + b wire_stride,
+// its num / den at + b n; sigmas and roots shared)
+template <class Src>
+__global__ void __launch_bounds__(256) perm_terms_kernel(const PermPtrs p0, const Src src, size_t n, size_t wire_stride) {
+  const u32 b = Src::slot();
+  const RoundConsts& kc = src.at(b);
+  PermPtrs p = p0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) p.w[j] += 2 * (size_t)b * wire_stride;
+  p.num += 2 * (size_t)b * n;
+  p.den += 2 * (size_t)b * n;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   const Fr gamma = fr_limbs(kc.gamma), one_abi = fr_limbs(kc.one_abi);
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
@@ -163,9 +189,37 @@ struct QuotLayout {
   const u32x4* halo_w[4];   // a, b, (unused), d
   const u32x4* halo_z;
 };
-template <bool WIDGETS, bool PLANAR>
-__global__ void __launch_bounds__(256, 2) quotient_kernel(const QuotPtrs p, const RoundConsts kc, const WidgetConsts wc,
-                                                       size_t n4, size_t wrap, const QuotLayout L) {
+// Whose quotient a launch computes.  OneProof: the constants travel in the kernel arguments and the pointers are the proof's
+// own.  ProofTable: blockIdx.y is the proof, its constants are rows of two device tables (scalar loads, as from the
+// arguments), its wires sit at w[j] + b wire_stride and its z / PI / out at + b one_stride (elements); selectors, sigmas,
+// l1 and x are shared.
+struct OneProof {
+  RoundConsts kc;
+  WidgetConsts wc;
+  PM_DEV const RoundConsts& round() const { return kc; }
+  PM_DEV const WidgetConsts& widget() const { return wc; }
+  PM_DEV void select(QuotPtrs&) const {}
+};
+struct ProofTable {
+  const PM_KCONST RoundConsts* kcs;
+  const PM_KCONST WidgetConsts* wcs;
+  size_t wire_stride, one_stride;
+  PM_DEV const RoundConsts& round() const { return kconst(kcs, blockIdx.y); }
+  PM_DEV const WidgetConsts& widget() const { return kconst(wcs, blockIdx.y); }
+  PM_DEV void select(QuotPtrs& p) const {
+    const u32 b = blockIdx.y;
+    for (int j = 0; j < 4; ++j) p.w[j] += 2 * (size_t)b * wire_stride;
+    p.z += 2 * (size_t)b * one_stride;
+    p.pi += 2 * (size_t)b * one_stride;
+    p.out += 2 * (size_t)b * one_stride;
+  }
+};
+template <bool WIDGETS, bool PLANAR, class Src>
+__global__ void __launch_bounds__(256, 2) quotient_kernel(const QuotPtrs p0, const Src src, size_t n4, size_t wrap, const QuotLayout L) {
+  const RoundConsts& kc = src.round();
+  const WidgetConsts& wc = src.widget();
+  QuotPtrs p = p0;
+  src.select(p);
   const size_t stride = (size_t)gridDim.x * blockDim.x;   // a multiple of 4: i mod 4 is fixed per thread
   const size_t t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   const u32 r4 = (u32)(t0 & 3);
@@ -279,177 +333,6 @@ __global__ void __launch_bounds__(256, 2) quotient_kernel(const QuotPtrs p, cons
   }
 }
 
-// ------------------------------------------------------------------ proof-batched forms (pm_plonk_prove_batch)
-// blockIdx.y is the proof.  Its constants sit in a small device table in the constant address space: the index is
-// wave-uniform, so every access is a scalar load (s_load), as from the kernel arguments of the one-proof kernels.
-#define PM_KCONST __attribute__((address_space(4)))
-template <class T>
-PM_DEV const T& kconst(const PM_KCONST T* tab, u32 i) {
-  return *(const T*)(tab + i);
-}
-__global__ void __launch_bounds__(256) perm_terms_batch_kernel(const PermPtrs p0, const PM_KCONST RoundConsts* kcs, size_t n,
-                                                               size_t wire_stride) {
-  const u32 b = blockIdx.y;
-  const RoundConsts& kc = kconst(kcs, b);
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  const Fr gamma = fr_limbs(kc.gamma), one_abi = fr_limbs(kc.one_abi);
-  const u32x4* w_[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) w_[j] = p0.w[j] + 2 * (size_t)b * wire_stride;
-  u32x4* num = p0.num + 2 * (size_t)b * n;
-  u32x4* den = p0.den + 2 * (size_t)b * n;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const Fr x = ld_canon(p0.roots, i);
-    Fr w[4], f[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) w[j] = to_dev(ld_canon(w_[j], i));
-#pragma unroll
-    for (int j = 0; j < 4; ++j) f[j] = perm_factor(w[j], x, kc.beta_k[j], gamma);
-    st_canon(num, i, fe_mul<FrP>(prod4(f[0], f[1], f[2], f[3]), one_abi));
-#pragma unroll
-    for (int j = 0; j < 4; ++j) f[j] = perm_factor(w[j], ld_canon(p0.s[j], i), kc.beta, gamma);
-    st_canon(den, i, fe_mul<FrP>(prod4(f[0], f[1], f[2], f[3]), one_abi));
-  }
-}
-// wires of proof b at w[j] + b wire_stride, z / PI / out at + b one_stride (elements); selectors, sigmas, l1, x shared
-template <bool WIDGETS>
-__global__ void __launch_bounds__(256, 2) quotient_batch_kernel(const QuotPtrs p0, const PM_KCONST RoundConsts* kcs,
-                                                             const PM_KCONST WidgetConsts* wcs, size_t n4, size_t wire_stride,
-                                                             size_t one_stride) {
-  // quotient_kernel<WIDGETS, false> row for row; only the pointers of proof b and where its constants come from differ
-  const u32 b = blockIdx.y;
-  const RoundConsts& kc = kconst(kcs, b);
-  const WidgetConsts& wc = kconst(wcs, b);
-  QuotPtrs p = p0;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) p.w[j] += 2 * (size_t)b * wire_stride;
-  p.z += 2 * (size_t)b * one_stride;
-  p.pi += 2 * (size_t)b * one_stride;
-  p.out += 2 * (size_t)b * one_stride;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;   // a multiple of 4: i mod 4 is fixed per thread
-  const size_t t0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const u32 r4 = (u32)(t0 & 3);
-  Fr zhi;
-#pragma unroll
-  for (int l = 0; l < 9; ++l)
-    zhi.l[l] = r4 == 0 ? kc.zh_inv[0][l] : (r4 == 1 ? kc.zh_inv[1][l] : (r4 == 2 ? kc.zh_inv[2][l] : kc.zh_inv[3][l]));
-  const Fr gamma = fr_limbs(kc.gamma);
-  for (size_t i = t0; i < n4; i += stride) {
-    const size_t inext = i + 4 < n4 ? i + 4 : i + 4 - n4;
-    Fr w[4], f[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) w[j] = to_dev(ld_canon(p.w[j], i));
-    // arithmetic identity, ABI form: five (1, <2) products and one canonical load -> (6, <11)
-    Fr g = fe_mul<FrP>(ld_canon(p.q_m, i), fe_mul<FrP>(w[0], w[1]));
-    g = fe_add<FrP>(g, fe_mul<FrP>(ld_canon(p.q_l, i), w[0]));
-    g = fe_add<FrP>(g, fe_mul<FrP>(ld_canon(p.q_r, i), w[1]));
-    g = fe_add<FrP>(g, fe_mul<FrP>(ld_canon(p.q_o, i), w[2]));
-    g = fe_add<FrP>(g, fe_mul<FrP>(ld_canon(p.q_4, i), w[3]));
-    g = fe_add<FrP>(g, ld_canon(p.q_c, i));
-    if (p.q_arith) g = fe_mul<FrP>(fe_norm<FrP>(g), to_dev(ld_canon(p.q_arith, i)));   // ABI x device -> ABI (1, <2)
-    if (WIDGETS) {
-      // the rows' other gate kinds; "next" = the same polynomial at w X = index + 4 on the 4n coset
-      const Fr a = w[0], b = w[1], c = w[2], d = w[3];
-      const Fr an = to_dev(ld_canon(p.w[0], inext)),
-               bn = to_dev(ld_canon(p.w[1], inext)),
-               dn = to_dev(ld_canon(p.w[3], inext));
-      Fr wsum = fe_zero<FrP>();
-      if (p.q_range) {
-        Fr t = wdelta(wsub(c, wmul4(d)), wc);
-        t = wadd(t, wmul(wdelta(wsub(b, wmul4(c)), wc), fr_limbs(wc.range_k[0])));
-        t = wadd(t, wmul(wdelta(wsub(a, wmul4(b)), wc), fr_limbs(wc.range_k[1])));
-        t = wadd(t, wmul(wdelta(wsub(dn, wmul4(a)), wc), fr_limbs(wc.range_k[2])));
-        t = wmul(t, fr_limbs(wc.range_sep));
-        wsum = wadd(wsum, wmul(to_dev(ld_canon(p.q_range, i)), t));
-      }
-      if (p.q_logic) {
-        const Fr qa = wsub(an, wmul4(a)), qb = wsub(bn, wmul4(b)), qd = wsub(dn, wmul4(d));
-        const Fr qc = to_dev(ld_canon(p.q_c, i));
-        Fr t = wdelta(qa, wc);
-        t = wadd(t, wmul(wdelta(qb, wc), fr_limbs(wc.logic_k[0])));
-        t = wadd(t, wmul(wdelta(qd, wc), fr_limbs(wc.logic_k[1])));
-        t = wadd(t, wmul(wsub(c, wmul(qa, qb)), fr_limbs(wc.logic_k[2])));
-        // delta_xor_and(qa, qb, w = c, qd, q_c)
-        const Fr s = wadd(qa, qb);
-        Fr in = wadd(wsub(wmul4(c), wmul2(wmul9(s))), fr_limbs(wc.c81));                         // 4w - 18(a+b) + 81
-        in = wadd(wmul(c, in), wmul2(wmul9(wadd(wsqr(qa), wsqr(qb)))));                          // w(..) + 18(a^2+b^2)
-        in = wadd(wsub(in, wmul(s, fr_limbs(wc.c81))), fr_limbs(wc.c83));                        // - 81(a+b) + 83
-        const Fr ff = wmul(c, in);
-        const Fr e = wsub(wmul3(wadd(s, qd)), wadd(ff, ff));                                    // 3(a+b+c) - 2f
-        const Fr bb = wmul(qc, wsub(wmul9(qd), wmul3(s)));                                      // q_c (9c - 3(a+b))
-        t = wadd(t, wmul(wadd(bb, e), fr_limbs(wc.logic_k[3])));
-        t = wmul(t, fr_limbs(wc.logic_sep));
-        wsum = wadd(wsum, wmul(to_dev(ld_canon(p.q_logic, i)), t));
-      }
-      if (p.q_fixed) {
-        const Fr xb = to_dev(ld_canon(p.q_l, i)), yb = to_dev(ld_canon(p.q_r, i)), xyb = to_dev(ld_canon(p.q_c, i));
-        const Fr one = fr_limbs(wc.c1);
-        const Fr bit = wsub(dn, wadd(d, d));
-        Fr t = wmul(wmul(bit, wsub(bit, one)), wadd(bit, one));                                 // bit (bit-1)(bit+1)
-        const Fr ya = wadd(wmul(wsqr(bit), wsub(yb, one)), one);
-        const Fr xa = wmul(xb, bit);
-        t = wadd(t, wmul(wsub(wmul(bit, xyb), c), fr_limbs(wc.fixed_k[0])));
-        const Fr dxy = wmul(wmul(wmul(c, a), b), fr_limbs(wc.edwards_d));
-        const Fr xacc = wsub(wadd(an, wmul(an, dxy)), wadd(wmul(a, ya), wmul(b, xa)));
-        const Fr yacc = wsub(wsub(bn, wmul(bn, dxy)), wadd(wmul(b, ya), wmul(a, xa)));
-        t = wadd(t, wmul(xacc, fr_limbs(wc.fixed_k[1])));
-        t = wadd(t, wmul(yacc, fr_limbs(wc.fixed_k[2])));
-        t = wmul(t, fr_limbs(wc.fixed_sep));
-        wsum = wadd(wsum, wmul(to_dev(ld_canon(p.q_fixed, i)), t));
-      }
-      if (p.q_var) {
-        const Fr y1x2 = wmul(b, c), y1y2 = wmul(b, d), x1x2 = wmul(a, c);
-        Fr t = wsub(wmul(a, d), dn);                                                             // x1 y2 - x1y2
-        const Fr dd = wmul(wmul(dn, y1x2), fr_limbs(wc.edwards_d));
-        const Fr x3 = wsub(wadd(dn, y1x2), wadd(an, wmul(an, dd)));
-        const Fr y3 = wsub(wadd(y1y2, x1x2), wsub(bn, wmul(bn, dd)));
-        t = wadd(t, wmul(x3, fr_limbs(wc.var_k[0])));
-        t = wadd(t, wmul(y3, fr_limbs(wc.var_k[1])));
-        t = wmul(t, fr_limbs(wc.var_sep));
-        wsum = wadd(wsum, wmul(to_dev(ld_canon(p.q_var, i)), t));
-      }
-      g = fe_add<FrP>(g, wmul(wsum, fr_limbs(kc.one_abi)));                                      // device x 2^256 -> ABI
-    }
-    g = fe_norm<FrP>(fe_add<FrP>(g, ld_canon(p.pi, i)));   // limbs back to (1)
-    // permutation identity
-    const Fr x = ld_canon(p.x, i);
-    const Fr z = ld_canon(p.z, i);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) f[j] = perm_factor(w[j], x, kc.beta_k[j], gamma);
-    const Fr idz = fe_mul<FrP>(z, prod4(f[0], f[1], f[2], f[3]));                          // ABI (1, <2)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) f[j] = perm_factor(w[j], ld_canon(p.s[j], i), kc.beta, gamma);
-    const Fr cpz = fe_mul<FrP>(ld_canon(p.z, inext), prod4(f[0], f[1], f[2], f[3]));   // ABI (1, <2)
-    // idz - cpz + 3r: (4, <5); times alpha -> ABI (1, <2)
-    g = fe_add<FrP>(g, fe_mul<FrP>(fe_sub<FrP, 3, 1>(idz, cpz), fr_limbs(kc.alpha)));
-    // (z - 1) l1 alpha^2:  z - 1 + 2r is (4, <3); product with ABI l1 is 2^251, alpha2 restores 2^256
-    const Fr zm1 = fe_sub<FrP, 2, 1>(z, fr_limbs(kc.one_abi));
-    g = fe_add<FrP>(g, fe_mul<FrP>(fe_mul<FrP>(zm1, ld_canon(p.l1, i)), fr_limbs(kc.alpha2)));
-    // g: value < 18 r, limbs < 3 * 2^29 + 16
-    st_canon(p.out, i, fe_mul<FrP>(g, zhi));
-  }
-}
-// out_b = sum_j c[b][j] v_j(b): term j of proof b at v[j] + b stride[j] (stride 0: a key polynomial all proofs share)
-struct LincombBatchArgs {
-  const u32x4* v[PM_LINCOMB_MAX];
-  size_t stride[PM_LINCOMB_MAX];
-  u32 k;
-};
-__global__ void __launch_bounds__(256) lincomb_batch_kernel(const LincombBatchArgs a, const PM_KCONST u32 (*c)[9] /* [B][k] */,
-                                                            u32x4* out, size_t out_stride, size_t n) {
-  const u32 b = blockIdx.y;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  const PM_KCONST u32(*cb)[9] = c + (size_t)b * a.k;
-  out += 2 * (size_t)b * out_stride;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    Fr acc = fe_mul<FrP>(ld_canon(a.v[0] + 2 * (size_t)b * a.stride[0], i), fr_limbs(kconst(cb, 0)));
-    for (u32 j = 1; j < a.k; ++j)
-      acc = fe_reduce_weak<FrP>(
-          fe_add<FrP>(acc, fe_mul<FrP>(ld_canon(a.v[j] + 2 * (size_t)b * a.stride[j], i), fr_limbs(kconst(cb, j)))));
-    st_canon(out, i, acc);
-  }
-}
-
 // sigma_j(w^i) = k_j' w^i' for a slice of the copy permutation given as wire positions q = j' n + i' (preprocessing; r01 - r04
 // gathered these on the host: 4 n field products or a 4 n x 32-byte round trip through host memory)
 struct SigmaConsts {
@@ -534,6 +417,43 @@ static unsigned grid_for(const pm_ctx* ctx, size_t n) {
   return (unsigned)std::min<size_t>((n + 255) / 256, (size_t)ctx->num_cus * 16);
 }
 
+// the device pointers of the C ABI's argument structs, as the kernels take them
+static PermPtrs perm_ptrs(const pm_plonk_perm_args& a, void* d_num, void* d_den) {
+  PermPtrs p;
+  for (int j = 0; j < 4; ++j) {
+    p.w[j] = (const u32x4*)a.wires[j];
+    p.s[j] = (const u32x4*)a.sigmas[j];
+  }
+  p.roots = (const u32x4*)a.roots;
+  p.num = (u32x4*)d_num;
+  p.den = (u32x4*)d_den;
+  return p;
+}
+static QuotPtrs quot_ptrs(const pm_plonk_quotient_args& a, void* d_out) {
+  QuotPtrs p;
+  for (int j = 0; j < 4; ++j) {
+    p.w[j] = (const u32x4*)a.wires[j];
+    p.s[j] = (const u32x4*)a.sigmas[j];
+  }
+  p.z = (const u32x4*)a.z;
+  p.q_m = (const u32x4*)a.q_m;
+  p.q_l = (const u32x4*)a.q_l;
+  p.q_r = (const u32x4*)a.q_r;
+  p.q_o = (const u32x4*)a.q_o;
+  p.q_4 = (const u32x4*)a.q_4;
+  p.q_c = (const u32x4*)a.q_c;
+  p.q_arith = (const u32x4*)a.q_arith;
+  p.q_range = (const u32x4*)a.q_range;
+  p.q_logic = (const u32x4*)a.q_logic;
+  p.q_fixed = (const u32x4*)a.q_fixed_group_add;
+  p.q_var = (const u32x4*)a.q_variable_group_add;
+  p.pi = (const u32x4*)a.pi;
+  p.l1 = (const u32x4*)a.l1;
+  p.x = (const u32x4*)a.x;
+  p.out = (u32x4*)d_out;
+  return p;
+}
+
 int coset_expand(pm_ctx* ctx, const void* const* d_src, uint32_t count, const void* d_gs_pow, size_t m, void* d_out) {
   if (!ctx || !d_src || count == 0 || count > 8 || !d_gs_pow || !d_out) return PM_ERR_BAD_ARG;
   std::lock_guard<std::mutex> lk(ctx->mu);
@@ -592,19 +512,12 @@ int sigma_evals_from_index(pm_ctx* ctx, const int64_t* idx, size_t count, uint32
   return pm_sync(ctx);   // the temporaries go away when this returns
 }
 
-// ---- launchers of the proof-batched kernels (pm_plonk_prove_batch, prover_batch.hip.h).  Each stages its per-proof
+// ---- launchers of the proof-batched forms (pm_plonk_prove_batch, prover_batch.hip.h).  Each stages its per-proof
 // constants in `stage` (pinned host -> device table, one async copy) and launches once for all `batch` proofs on `st`.
 int perm_terms_batch(pm_ctx* ctx, ConstStage& stage, const pm_plonk_perm_args* args, uint32_t batch, size_t wire_stride,
                      size_t n, void* d_num, void* d_den, hipStream_t st) {
   std::lock_guard<std::mutex> lk(ctx->mu);
-  PermPtrs p;
-  for (int j = 0; j < 4; ++j) {
-    p.w[j] = (const u32x4*)args[0].wires[j];
-    p.s[j] = (const u32x4*)args[0].sigmas[j];
-  }
-  p.roots = (const u32x4*)args[0].roots;
-  p.num = (u32x4*)d_num;
-  p.den = (u32x4*)d_den;
+  const PermPtrs p = perm_ptrs(args[0], d_num, d_den);
   RoundConsts* h;
   void* d;
   if (!stage.take(sizeof(RoundConsts) * batch, (void**)&h, &d)) return set_err(ctx, PM_ERR_OOM, "constant table full");
@@ -613,8 +526,8 @@ int perm_terms_batch(pm_ctx* ctx, ConstStage& stage, const pm_plonk_perm_args* a
   PM_HIP(ctx, hipSetDevice(ctx->device));
   PM_HIP(ctx, hipMemcpyAsync(d, h, sizeof(RoundConsts) * batch, hipMemcpyHostToDevice, st));
   ProfScope prof(ctx, st, "plonk_perm_terms_batch");
-  hipLaunchKernelGGL(perm_terms_batch_kernel, dim3(grid_for(ctx, n), batch), dim3(256), 0, st, p,
-                     (const PM_KCONST RoundConsts*)d, n, wire_stride);
+  hipLaunchKernelGGL(perm_terms_kernel<FromTable<RoundConsts>>, dim3(grid_for(ctx, n), batch), dim3(256), 0, st, p,
+                     FromTable<RoundConsts>{(const PM_KCONST RoundConsts*)d}, n, wire_stride);
   PM_HIP(ctx, hipGetLastError());
   return PM_OK;
 }
@@ -622,28 +535,7 @@ int perm_terms_batch(pm_ctx* ctx, ConstStage& stage, const pm_plonk_perm_args* a
 int quotient_batch(pm_ctx* ctx, ConstStage& stage, const pm_plonk_quotient_args* args, uint32_t batch, size_t wire_stride,
                    size_t one_stride, size_t n, void* d_out, hipStream_t st) {
   std::lock_guard<std::mutex> lk(ctx->mu);
-  const pm_plonk_quotient_args& a0 = args[0];
-  QuotPtrs p;
-  for (int j = 0; j < 4; ++j) {
-    p.w[j] = (const u32x4*)a0.wires[j];
-    p.s[j] = (const u32x4*)a0.sigmas[j];
-  }
-  p.z = (const u32x4*)a0.z;
-  p.q_m = (const u32x4*)a0.q_m;
-  p.q_l = (const u32x4*)a0.q_l;
-  p.q_r = (const u32x4*)a0.q_r;
-  p.q_o = (const u32x4*)a0.q_o;
-  p.q_4 = (const u32x4*)a0.q_4;
-  p.q_c = (const u32x4*)a0.q_c;
-  p.q_arith = (const u32x4*)a0.q_arith;
-  p.q_range = (const u32x4*)a0.q_range;
-  p.q_logic = (const u32x4*)a0.q_logic;
-  p.q_fixed = (const u32x4*)a0.q_fixed_group_add;
-  p.q_var = (const u32x4*)a0.q_variable_group_add;
-  p.pi = (const u32x4*)a0.pi;
-  p.l1 = (const u32x4*)a0.l1;
-  p.x = (const u32x4*)a0.x;
-  p.out = (u32x4*)d_out;
+  const QuotPtrs p = quot_ptrs(args[0], d_out);
   const bool widgets = p.q_range || p.q_logic || p.q_fixed || p.q_var;
   RoundConsts* hk;
   WidgetConsts* hw;
@@ -659,12 +551,11 @@ int quotient_batch(pm_ctx* ctx, ConstStage& stage, const pm_plonk_quotient_args*
   PM_HIP(ctx, hipMemcpyAsync(dk, hk, (char*)hw - (char*)hk + sizeof(WidgetConsts) * batch, hipMemcpyHostToDevice, st));
   ProfScope prof(ctx, st, "plonk_quotient_batch");
   const dim3 grid(grid_for(ctx, 4 * n), batch);
+  const ProofTable src{(const PM_KCONST RoundConsts*)dk, (const PM_KCONST WidgetConsts*)dw, wire_stride, one_stride};
   if (widgets)
-    hipLaunchKernelGGL(quotient_batch_kernel<true>, grid, dim3(256), 0, st, p, (const PM_KCONST RoundConsts*)dk,
-                       (const PM_KCONST WidgetConsts*)dw, 4 * n, wire_stride, one_stride);
+    hipLaunchKernelGGL((quotient_kernel<true, false, ProofTable>), grid, dim3(256), 0, st, p, src, 4 * n, 4 * n, QuotLayout{});
   else
-    hipLaunchKernelGGL(quotient_batch_kernel<false>, grid, dim3(256), 0, st, p, (const PM_KCONST RoundConsts*)dk,
-                       (const PM_KCONST WidgetConsts*)dw, 4 * n, wire_stride, one_stride);
+    hipLaunchKernelGGL((quotient_kernel<false, false, ProofTable>), grid, dim3(256), 0, st, p, src, 4 * n, 4 * n, QuotLayout{});
   PM_HIP(ctx, hipGetLastError());
   return PM_OK;
 }
@@ -674,7 +565,7 @@ int lincomb_batch(pm_ctx* ctx, ConstStage& stage, uint32_t k, const void* const*
                   hipStream_t st) {
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (k == 0 || k > PM_LINCOMB_MAX) return set_err(ctx, PM_ERR_BAD_ARG, "k must be in 1..PM_LINCOMB_MAX");
-  LincombBatchArgs a;
+  LincombArgs a;
   memset(&a, 0, sizeof a);
   a.k = k;
   for (uint32_t j = 0; j < k; ++j) {
@@ -688,26 +579,64 @@ int lincomb_batch(pm_ctx* ctx, ConstStage& stage, uint32_t k, const void* const*
   PM_HIP(ctx, hipSetDevice(ctx->device));
   PM_HIP(ctx, hipMemcpyAsync(d, h, 36 * (size_t)k * batch, hipMemcpyHostToDevice, st));
   ProfScope prof(ctx, st, "fr_lincomb_batch");
-  hipLaunchKernelGGL(lincomb_batch_kernel, dim3(grid_for(ctx, n), batch), dim3(256), 0, st, a, (const PM_KCONST u32(*)[9])d,
-                     (u32x4*)d_out, out_stride, n);
+  hipLaunchKernelGGL(lincomb_kernel<CoeffTable>, dim3(grid_for(ctx, n), batch), dim3(256), 0, st, a,
+                     CoeffTable{(const PM_KCONST u32(*)[9])d}, (u32x4*)d_out, out_stride, n);
   PM_HIP(ctx, hipGetLastError());
   return PM_OK;
 }
 
-// ---- zero-knowledge mode (pm_plonk_prove_zk).  Coefficient vectors live at a padded stride
-// S = n + PM_ZK_PAD; blinders arrive as kernel arguments (canonical Montgomery limbs), never through host round trips.
+// ---- zero-knowledge mode (pm_plonk_prove_zk; the batch: pm_plonk_prove_batch_zk, section 7.2c).
+// Coefficient vectors live at a padded stride S = n + PM_ZK_PAD.  One proof's blinders arrive as kernel arguments (canonical
+// Montgomery limbs), never through host round trips.  A batch's blinders (64 x 17 x 32 bytes) are beyond the kernel
+// arguments: they are a device table in the constant address space, like the per-proof challenges, and a kernel fetches the
+// few it needs with the wave-uniform proof index (scalar loads) before it picks one per lane with selects.
+struct ZkBlinders {
+  u32 b[PM_PLONK_ZK_BLINDERS][8];   // canonical Montgomery limbs, as the caller passed them
+};
+PM_DEV Fr zk_pick3(const Fr& c0, const Fr& c1, const Fr& c2, u32 i) {   // one of three uniform candidates, i per lane
+  Fr r;
+#pragma unroll
+  for (int l = 0; l < 9; ++l) r.l[l] = i == 0 ? c0.l[l] : (i == 1 ? c1.l[l] : c2.l[l]);
+  return r;
+}
+// three consecutive blinders of proof b from `first` on, the i-th picked per lane
+PM_DEV Fr zk_blinder(const PM_KCONST ZkBlinders* bl, u32 b, u32 first, u32 i) {
+  const ZkBlinders& mine = kconst(bl, b);
+  return zk_pick3(fe_unpack<FrP>(mine.b[first]), fe_unpack<FrP>(mine.b[first + 1]), fe_unpack<FrP>(mine.b[first + 2]), i);
+}
 
+// Which vector blockIdx.y = v of a blinding launch is, how many blinder terms it takes and what they are.  BlindArgs: all
+// three in the arguments.  BlindTable: vector v = b vpp + j of all proofs, the blinders of wire first_wire + j of proof b --
+// a b c d z take 3 3 2 3 3 blinders from b_0, b_3, b_6, b_8, b_11 on (first + 2 <= 13: inside the table for c too).
+struct BlindArgs {
+  ZkBlindArgs a;
+  PM_DEV u32x4* vec(u32 v) const { return (u32x4*)a.v[v]; }
+  PM_DEV u32 terms(u32 v) const { return a.terms[v]; }
+  PM_DEV Fr blinder(u32 v, u32 t) const { return fe_unpack<FrP>((const u32*)a.beta[v][t]); }
+};
+struct BlindTable {
+  const PM_KCONST ZkBlinders* bl;
+  u32x4* vecs;
+  u32 vpp, first_wire;
+  size_t S;
+  PM_DEV u32 wire(u32 v) const { return first_wire + v % vpp; }
+  PM_DEV u32x4* vec(u32 v) const { return vecs + 2 * (size_t)v * S; }
+  PM_DEV u32 terms(u32 v) const { return wire(v) == 2 ? 2u : 3u; }
+  PM_DEV Fr blinder(u32 v, u32 t) const {
+    const u32 w = wire(v);
+    return zk_blinder(bl, v / vpp, w < 3 ? 3 * w : (w == 3 ? 8u : 11u), t);
+  }
+};
 // w(X) + (beta_0 + ... + beta_{t-1} X^{t-1}) Z_H(X) in place: coefficient i < t loses beta_i, coefficient n + i becomes
 // beta_i, and the rest of the tail [n, S) is zeroed.  One block per vector (blockIdx.y), S - n <= 64 threads busy.
-__global__ void __launch_bounds__(64) zk_blind_kernel(const ZkBlindArgs a, size_t n, size_t tail) {
+template <class Src>
+__global__ void __launch_bounds__(64) zk_blind_kernel(const Src src, size_t n, size_t tail) {
   const u32 v = blockIdx.y, t = threadIdx.x;
-  u32x4* p = (u32x4*)a.v[v];
-  const u32 terms = a.terms[v];
-  if (t < tail) {
-    const Fr b = t < terms ? fe_unpack<FrP>((const u32*)a.beta[v][t]) : fe_zero<FrP>();
-    st_canon(p, n + t, b);
-  }
-  if (t < terms) st_canon(p, t, wsub(ld_canon(p, t), fe_unpack<FrP>((const u32*)a.beta[v][t])));
+  u32x4* p = src.vec(v);
+  const u32 terms = src.terms(v);
+  const Fr beta = t < terms ? src.blinder(v, t) : fe_zero<FrP>();
+  if (t < tail) st_canon(p, n + t, beta);
+  if (t < terms) st_canon(p, t, wsub(ld_canon(p, t), beta));
 }
 int zk_blind(pm_ctx* ctx, const ZkBlindArgs& a, uint32_t count, size_t n, size_t stride, hipStream_t st) {
   if (count == 0 || count > ZK_MAX_VECS || stride < n || stride - n > 64 || n < ZK_MAX_TERMS) return PM_ERR_BAD_ARG;
@@ -716,7 +645,20 @@ int zk_blind(pm_ctx* ctx, const ZkBlindArgs& a, uint32_t count, size_t n, size_t
   if (!st) st = ctx->stream;   // as in every entry point: no stream = the context's own
   PM_HIP(ctx, hipSetDevice(ctx->device));
   ProfScope prof(ctx, st, "plonk_zk_blind");
-  hipLaunchKernelGGL(zk_blind_kernel, dim3(1, count), dim3(64), 0, st, a, n, stride - n);
+  hipLaunchKernelGGL(zk_blind_kernel<BlindArgs>, dim3(1, count), dim3(64), 0, st, BlindArgs{a}, n, stride - n);
+  PM_HIP(ctx, hipGetLastError());
+  return PM_OK;
+}
+int zk_blind_batch(pm_ctx* ctx, const void* d_blinders, void* d_vecs, uint32_t vpp, uint32_t first_wire, uint32_t batch, size_t n,
+                   size_t stride, hipStream_t st) {
+  if (!d_blinders || !d_vecs || vpp == 0 || first_wire + vpp > 5 || batch == 0 || stride < n + ZK_MAX_TERMS || stride - n > 64 ||
+      n < ZK_MAX_TERMS)
+    return PM_ERR_BAD_ARG;
+  if (!st) st = ctx->stream;
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  ProfScope prof(ctx, st, "plonk_zk_blind_batch");
+  hipLaunchKernelGGL(zk_blind_kernel<BlindTable>, dim3(1, batch * vpp), dim3(64), 0, st,
+                     BlindTable{(const PM_KCONST ZkBlinders*)d_blinders, (u32x4*)d_vecs, vpp, first_wire, stride}, n, stride - n);
   PM_HIP(ctx, hipGetLastError());
   return PM_OK;
 }
@@ -743,14 +685,40 @@ int zk_shift(pm_ctx* ctx, const ZkShiftArgs& a, const void* d_w8, size_t len, hi
   return PM_OK;
 }
 
-// The quotient t' (degree < 4n + ZK_P1_LEN) from A = t' mod (X^4n - s) and B = t' mod (X^4n + s), s = 7^4n: ab holds the
-// coefficients of A (4n) and then those of B(X / w_8n) (4n; the plain coset inverse of the second-coset values), so
-// B_j = ab[4n + j] w_8n^-j with w_8n^-j = -w_8n^(4n - j) for j > 0.  t' = P0 + X^4n P1, P0 = (A + B) / 2, P1 = (A - B) / 2s.
-// Writes the four pieces at stride S with the X^n blinders: t_1 + b_14 X^n, t_2 - b_14 + b_15 X^n, t_3 - b_15 + b_16 X^n,
-// t_4 - b_16 (t_4 = coefficients 3n .. 4n + ZK_P1_LEN); every element of the 4 x S output is written.
-__global__ void __launch_bounds__(256) zk_combine_kernel(const u32x4* ab, const u32x4* w8, size_t n, size_t S, const ZkCombineConsts kc,
-                                                         u32x4* t) {
+// The quotient blinders b_14 .. b_16 of the proof a combine launch works on, and which of how many proofs that is.  One
+// proof: the blinders sit in the arguments and are read where they are used, with the lane's index.  Proof blockIdx.y of
+// gridDim.y: a table row takes a uniform index only (scalar loads), so the kernel fetches the three once, ahead of the element
+// loop, into locals of its own and picks one per lane with zk_pick3 (FETCH_ONCE).  Held in a struct or behind a reference
+// instead of three locals they go to scratch, 112 bytes per lane.
+struct QuotBlindArgs {
+  u32 beta[3][8];
+  static constexpr bool FETCH_ONCE = false;
+  static PM_DEV u32 slot() { return 0; }
+  static PM_DEV u32 count() { return 1; }
+  PM_DEV Fr blinder(u32 k) const { return fe_unpack<FrP>(beta[k]); }
+};
+struct QuotBlindTable {
+  const PM_KCONST ZkBlinders* bl;
+  static constexpr bool FETCH_ONCE = true;
+  static PM_DEV u32 slot() { return blockIdx.y; }
+  static PM_DEV u32 count() { return gridDim.y; }
+  PM_DEV Fr blinder(u32 k) const { return fe_unpack<FrP>(kconst(bl, blockIdx.y).b[14 + k]); }
+};
+// The quotient t' (degree < 4n + ZK_P1_LEN) from A = t' mod (X^4n - s) and B = t' mod (X^4n + s), s = 7^4n: A is 4n
+// coefficients at ab + 4n b and B(X / w_8n) (the plain coset inverse of the second-coset values) 4n at ab + 4n (batch + b), so
+// B_j = B(X / w_8n)_j w_8n^-j with w_8n^-j = -w_8n^(4n - j) for j > 0.  t' = P0 + X^4n P1, P0 = (A + B) / 2, P1 = (A - B) / 2s.
+// Writes the four pieces at stride S (t + 4 S b) with the X^n blinders: t_1 + b_14 X^n, t_2 - b_14 + b_15 X^n,
+// t_3 - b_15 + b_16 X^n, t_4 - b_16 (t_4 = coefficients 3n .. 4n + ZK_P1_LEN); every element of the 4 x S output is written.
+template <class Src>
+__global__ void __launch_bounds__(256) zk_combine_kernel(const Src src, const u32x4* ab, const u32x4* w8, size_t n, size_t S,
+                                                         const ZkCombineConsts kc, u32x4* t) {
+  const u32 proof = Src::slot(), batch = Src::count();
   const size_t n4 = 4 * n, tail = S - n, total = n4 + 4 * tail;
+  const u32x4* a_vec = ab + 2 * (size_t)proof * n4;
+  const u32x4* b_vec = ab + 2 * ((size_t)batch + proof) * n4;
+  t += 2 * (size_t)proof * 4 * S;
+  constexpr bool ONCE = Src::FETCH_ONCE;
+  const Fr zero = fe_zero<FrP>(), c0 = ONCE ? src.blinder(0) : zero, c1 = ONCE ? src.blinder(1) : zero, c2 = ONCE ? src.blinder(2) : zero;
   const size_t stride = (size_t)gridDim.x * blockDim.x;
   for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
     size_t k, i, j;       // output piece, index in it, and the coefficient j < 4n of A and B to combine (if any)
@@ -766,74 +734,50 @@ __global__ void __launch_bounds__(256) zk_combine_kernel(const u32x4* ab, const 
       j = i - n;
       high = true;
       if (k < 3 || j >= ZK_P1_LEN) {   // the blinder coefficient X^n of t_1..t_3, zeros elsewhere
-        const Fr b = (k < 3 && j == 0) ? fe_unpack<FrP>((const u32*)kc.beta[k]) : fe_zero<FrP>();
+        const Fr b = (k < 3 && j == 0) ? (ONCE ? zk_pick3(c0, c1, c2, (u32)k) : src.blinder((u32)k)) : zero;
         st_canon(t, k * S + i, b);
         continue;
       }
     }
-    const Fr a_ = ld_canon(ab, j);
-    const Fr p = fe_mul<FrP>(ld_canon(ab, n4 + j), to_dev(ld_canon(w8, j ? n4 - j : 0)));   // B_j = p (j = 0), -p (j > 0)
-    const bool plus = (j == 0) != high;                                                      // A + B_j or A - B_j
+    const Fr a_ = ld_canon(a_vec, j);
+    const Fr p = fe_mul<FrP>(ld_canon(b_vec, j), to_dev(ld_canon(w8, j ? n4 - j : 0)));   // B_j = p (j = 0), -p (j > 0)
+    const bool plus = (j == 0) != high;                                                  // A + B_j or A - B_j
     const Fr s_ = plus ? wadd(a_, p) : wsub(a_, p);
     Fr v = fe_mul<FrP>(s_, fr_limbs(high ? kc.inv2s : kc.inv2));
-    if (!high && i == 0 && k > 0) v = wsub(v, fe_unpack<FrP>((const u32*)kc.beta[k - 1]));
+    if (!high && i == 0 && k > 0) v = wsub(v, ONCE ? zk_pick3(c0, c1, c2, (u32)k - 1) : src.blinder((u32)k - 1));
     st_canon(t, k * S + i, v);
   }
+}
+static ZkCombineConsts zk_combine_consts(const uint64_t inv2[4], const uint64_t inv2s[4]) {
+  ZkCombineConsts kc;
+  to_limbs29(kc.inv2, load_fr(inv2));
+  to_limbs29(kc.inv2s, load_fr(inv2s));
+  return kc;
 }
 int zk_combine(pm_ctx* ctx, const void* d_ab, const void* d_w8, size_t n, size_t stride, const uint64_t inv2[4],
                const uint64_t inv2s[4], const uint64_t beta[3][4], void* d_t, hipStream_t st) {
   if (!d_ab || !d_w8 || !d_t || 4 * n < ZK_P1_LEN || stride < n + ZK_P1_LEN) return PM_ERR_BAD_ARG;
-  ZkCombineConsts kc;
-  memset(&kc, 0, sizeof kc);
-  to_limbs29(kc.inv2, load_fr(inv2));
-  to_limbs29(kc.inv2s, load_fr(inv2s));
-  memcpy(kc.beta, beta, sizeof kc.beta);
+  QuotBlindArgs src;
+  memcpy(src.beta, beta, sizeof src.beta);
   const size_t total = 4 * n + 4 * (stride - n);
   if (!st) st = ctx->stream;
   PM_HIP(ctx, hipSetDevice(ctx->device));
   ProfScope prof(ctx, st, "plonk_zk_combine");
-  hipLaunchKernelGGL(zk_combine_kernel, dim3(grid_for(ctx, total)), dim3(256), 0, st, (const u32x4*)d_ab, (const u32x4*)d_w8, n,
-                     stride, kc, (u32x4*)d_t);
+  hipLaunchKernelGGL(zk_combine_kernel<QuotBlindArgs>, dim3(grid_for(ctx, total)), dim3(256), 0, st, src, (const u32x4*)d_ab,
+                     (const u32x4*)d_w8, n, stride, zk_combine_consts(inv2, inv2s), (u32x4*)d_t);
   PM_HIP(ctx, hipGetLastError());
   return PM_OK;
 }
-
-// ---- the same three steps for every proof of a batch (pm_plonk_prove_batch_zk).  A batch's
-// blinders (64 x 17 x 32 bytes) are beyond the kernel arguments: they are a device table in the constant address space,
-// like the per-proof challenges, and every kernel fetches the few it needs with the wave-uniform proof index (scalar
-// loads) before it picks one per lane with selects.
-struct ZkBlinders {
-  u32 b[PM_PLONK_ZK_BLINDERS][8];   // canonical Montgomery limbs, as the caller passed them
-};
-PM_DEV Fr zk_pick3(const Fr& c0, const Fr& c1, const Fr& c2, u32 i) {   // one of three uniform candidates, i per lane
-  Fr r;
-#pragma unroll
-  for (int l = 0; l < 9; ++l) r.l[l] = i == 0 ? c0.l[l] : (i == 1 ? c1.l[l] : c2.l[l]);
-  return r;
-}
-// zk_blind_kernel for vector blockIdx.y = b vpp + v of all proofs: the blinders of wire first_wire + v of proof b
-__global__ void __launch_bounds__(64) zk_blind_batch_kernel(const PM_KCONST ZkBlinders* bl, u32x4* vecs, u32 vpp, u32 first_wire,
-                                                            size_t n, size_t S) {
-  const u32 vec = blockIdx.y, b = vec / vpp, wire = first_wire + (vec - b * vpp), t = threadIdx.x;
-  // a b c d z take 3 3 2 3 3 blinders from b_0, b_3, b_6, b_8, b_11 on (first + 2 <= 13: inside the table for c too)
-  const u32 terms = wire == 2 ? 2u : 3u, first = wire < 3 ? 3 * wire : (wire == 3 ? 8u : 11u);
-  const ZkBlinders& mine = kconst(bl, b);
-  const Fr c0 = fe_unpack<FrP>(mine.b[first]), c1 = fe_unpack<FrP>(mine.b[first + 1]), c2 = fe_unpack<FrP>(mine.b[first + 2]);
-  u32x4* p = vecs + 2 * (size_t)vec * S;
-  const Fr beta = t < terms ? zk_pick3(c0, c1, c2, t) : fe_zero<FrP>();
-  if (t < S - n) st_canon(p, n + t, beta);
-  if (t < terms) st_canon(p, t, wsub(ld_canon(p, t), beta));
-}
-int zk_blind_batch(pm_ctx* ctx, const void* d_blinders, void* d_vecs, uint32_t vpp, uint32_t first_wire, uint32_t batch, size_t n,
-                   size_t stride, hipStream_t st) {
-  if (!d_blinders || !d_vecs || vpp == 0 || first_wire + vpp > 5 || batch == 0 || stride < n + ZK_MAX_TERMS || stride - n > 64 ||
-      n < ZK_MAX_TERMS)
-    return PM_ERR_BAD_ARG;
+int zk_combine_batch(pm_ctx* ctx, const void* d_blinders, const void* d_ab, const void* d_w8, uint32_t batch, size_t n, size_t stride,
+                     const uint64_t inv2[4], const uint64_t inv2s[4], void* d_t, hipStream_t st) {
+  if (!d_blinders || !d_ab || !d_w8 || !d_t || batch == 0 || 4 * n < ZK_P1_LEN || stride < n + ZK_P1_LEN) return PM_ERR_BAD_ARG;
+  const size_t total = 4 * n + 4 * (stride - n);
   if (!st) st = ctx->stream;
   PM_HIP(ctx, hipSetDevice(ctx->device));
-  ProfScope prof(ctx, st, "plonk_zk_blind_batch");
-  hipLaunchKernelGGL(zk_blind_batch_kernel, dim3(1, batch * vpp), dim3(64), 0, st, (const PM_KCONST ZkBlinders*)d_blinders,
-                     (u32x4*)d_vecs, vpp, first_wire, n, stride);
+  ProfScope prof(ctx, st, "plonk_zk_combine_batch");
+  hipLaunchKernelGGL(zk_combine_kernel<QuotBlindTable>, dim3(grid_for(ctx, total), batch), dim3(256), 0, st,
+                     QuotBlindTable{(const PM_KCONST ZkBlinders*)d_blinders}, (const u32x4*)d_ab, (const u32x4*)d_w8, n, stride,
+                     zk_combine_consts(inv2, inv2s), (u32x4*)d_t);
   PM_HIP(ctx, hipGetLastError());
   return PM_OK;
 }
@@ -865,65 +809,6 @@ int zk_shift_batch(pm_ctx* ctx, const ZkShiftBatchArgs& a, const void* d_w8, uin
   PM_HIP(ctx, hipSetDevice(ctx->device));
   ProfScope prof(ctx, st, "plonk_zk_shift_batch");
   hipLaunchKernelGGL(zk_shift_batch_kernel, dim3(grid_for(ctx, max_len), batch), dim3(256), 0, st, a, (const u32x4*)d_w8, max_len);
-  PM_HIP(ctx, hipGetLastError());
-  return PM_OK;
-}
-
-// zk_combine_kernel element for element, for proof blockIdx.y: A at ab + 4n b, B(X / w_8n) at ab + 4n (batch + b), the pieces at
-// t + 4 S b.  The proof's three quotient blinders are fetched once (uniform) and picked per element.
-struct ZkCombineBatchConsts {
-  u32 inv2[9], inv2s[9];
-};
-__global__ void __launch_bounds__(256) zk_combine_batch_kernel(const PM_KCONST ZkBlinders* bl, const u32x4* ab_all, const u32x4* w8,
-                                                               size_t n, size_t S, const ZkCombineBatchConsts kc, u32x4* t_all) {
-  const u32 proof = blockIdx.y, batch = gridDim.y;
-  const size_t n4 = 4 * n, tail = S - n, total = n4 + 4 * tail;
-  const u32x4* a_vec = ab_all + 2 * (size_t)proof * n4;
-  const u32x4* b_vec = ab_all + 2 * ((size_t)batch + proof) * n4;
-  u32x4* t = t_all + 2 * (size_t)proof * 4 * S;
-  const ZkBlinders& mine = kconst(bl, proof);
-  const Fr c0 = fe_unpack<FrP>(mine.b[14]), c1 = fe_unpack<FrP>(mine.b[15]), c2 = fe_unpack<FrP>(mine.b[16]);
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
-    size_t k, i, j;       // output piece, index in it, and the coefficient j < 4n of A and B to combine (if any)
-    bool high;            // P1_j (piece 4 beyond n) instead of P0_j
-    if (e < n4) {
-      j = e;
-      k = j / n;
-      i = j - k * n;
-      high = false;
-    } else {
-      k = (e - n4) / tail;
-      i = n + (e - n4 - k * tail);
-      j = i - n;
-      high = true;
-      if (k < 3 || j >= ZK_P1_LEN) {   // the blinder coefficient X^n of t_1..t_3, zeros elsewhere
-        const Fr b = (k < 3 && j == 0) ? zk_pick3(c0, c1, c2, (u32)k) : fe_zero<FrP>();
-        st_canon(t, k * S + i, b);
-        continue;
-      }
-    }
-    const Fr a_ = ld_canon(a_vec, j);
-    const Fr p = fe_mul<FrP>(ld_canon(b_vec, j), to_dev(ld_canon(w8, j ? n4 - j : 0)));   // B_j = p (j = 0), -p (j > 0)
-    const bool plus = (j == 0) != high;                                                  // A + B_j or A - B_j
-    const Fr s_ = plus ? wadd(a_, p) : wsub(a_, p);
-    Fr v = fe_mul<FrP>(s_, fr_limbs(high ? kc.inv2s : kc.inv2));
-    if (!high && i == 0 && k > 0) v = wsub(v, zk_pick3(c0, c1, c2, (u32)k - 1));
-    st_canon(t, k * S + i, v);
-  }
-}
-int zk_combine_batch(pm_ctx* ctx, const void* d_blinders, const void* d_ab, const void* d_w8, uint32_t batch, size_t n, size_t stride,
-                     const uint64_t inv2[4], const uint64_t inv2s[4], void* d_t, hipStream_t st) {
-  if (!d_blinders || !d_ab || !d_w8 || !d_t || batch == 0 || 4 * n < ZK_P1_LEN || stride < n + ZK_P1_LEN) return PM_ERR_BAD_ARG;
-  ZkCombineBatchConsts kc;
-  to_limbs29(kc.inv2, load_fr(inv2));
-  to_limbs29(kc.inv2s, load_fr(inv2s));
-  const size_t total = 4 * n + 4 * (stride - n);
-  if (!st) st = ctx->stream;
-  PM_HIP(ctx, hipSetDevice(ctx->device));
-  ProfScope prof(ctx, st, "plonk_zk_combine_batch");
-  hipLaunchKernelGGL(zk_combine_batch_kernel, dim3(grid_for(ctx, total), batch), dim3(256), 0, st,
-                     (const PM_KCONST ZkBlinders*)d_blinders, (const u32x4*)d_ab, (const u32x4*)d_w8, n, stride, kc, (u32x4*)d_t);
   PM_HIP(ctx, hipGetLastError());
   return PM_OK;
 }
@@ -963,17 +848,19 @@ extern "C" int pm_fr_lincomb_dev(pm_ctx* ctx, uint32_t k, const void* const* d_v
   if (n == 0) return PM_OK;
   if (!d_vecs || !coeffs || !d_out) return set_err(ctx, PM_ERR_BAD_ARG, "null pointer");
   LincombArgs a;
+  CoeffArgs c;
   memset(&a, 0, sizeof a);
+  memset(&c, 0, sizeof c);
   a.k = k;
   for (uint32_t j = 0; j < k; ++j) {
     if (!d_vecs[j]) return set_err(ctx, PM_ERR_BAD_ARG, "null device pointer");
     a.v[j] = (const u32x4*)d_vecs[j];
-    to_limbs29_shift(a.c[j], load_fr(coeffs + 4 * j), 1);
+    to_limbs29_shift(c.c[j], load_fr(coeffs + 4 * j), 1);
   }
   PM_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
   ProfScope prof(ctx, st, "fr_lincomb");
-  hipLaunchKernelGGL(lincomb_kernel, dim3(grid_for(ctx, n)), dim3(256), 0, st, a, (u32x4*)d_out, n);
+  hipLaunchKernelGGL(lincomb_kernel<CoeffArgs>, dim3(grid_for(ctx, n)), dim3(256), 0, st, a, c, (u32x4*)d_out, (size_t)0, n);
   PM_HIP(ctx, hipGetLastError());
   return PM_OK;
 }
@@ -984,22 +871,16 @@ extern "C" int pm_plonk_perm_terms_dev(pm_ctx* ctx, const pm_plonk_perm_args* ar
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (!args) return set_err(ctx, PM_ERR_BAD_ARG, "null args");
   if (n == 0) return PM_OK;
-  PermPtrs p;
-  for (int j = 0; j < 4; ++j) {
-    p.w[j] = (const u32x4*)args->wires[j];
-    p.s[j] = (const u32x4*)args->sigmas[j];
+  const PermPtrs p = perm_ptrs(*args, d_num, d_den);
+  for (int j = 0; j < 4; ++j)
     if (!p.w[j] || !p.s[j]) return set_err(ctx, PM_ERR_BAD_ARG, "null device pointer");
-  }
-  p.roots = (const u32x4*)args->roots;
-  p.num = (u32x4*)d_num;
-  p.den = (u32x4*)d_den;
   if (!p.roots || !p.num || !p.den) return set_err(ctx, PM_ERR_BAD_ARG, "null device pointer");
-  RoundConsts kc;
-  fill_round_consts(kc, host::zero<4>(), load_fr(args->beta), load_fr(args->gamma), args->k, nullptr);
+  FromArgs<RoundConsts> src;
+  fill_round_consts(src.c, host::zero<4>(), load_fr(args->beta), load_fr(args->gamma), args->k, nullptr);
   PM_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
   ProfScope prof(ctx, st, "plonk_perm_terms");
-  hipLaunchKernelGGL(perm_terms_kernel, dim3(grid_for(ctx, n)), dim3(256), 0, st, p, kc, n);
+  hipLaunchKernelGGL(perm_terms_kernel<FromArgs<RoundConsts>>, dim3(grid_for(ctx, n)), dim3(256), 0, st, p, src, n, (size_t)0);
   PM_HIP(ctx, hipGetLastError());
   return PM_OK;
 }
@@ -1019,42 +900,22 @@ int pm::plonk_quotient_layout(pm_ctx* ctx, const pm_plonk_quotient_args* args, s
   if (!args) return set_err(ctx, PM_ERR_BAD_ARG, "null args");
   if (n == 0) return PM_OK;
   if (n & (n - 1)) return set_err(ctx, PM_ERR_LENGTH, "n must be a power of two");
-  QuotPtrs p;
-  for (int j = 0; j < 4; ++j) {
-    p.w[j] = (const u32x4*)args->wires[j];
-    p.s[j] = (const u32x4*)args->sigmas[j];
-  }
-  p.z = (const u32x4*)args->z;
-  p.q_m = (const u32x4*)args->q_m;
-  p.q_l = (const u32x4*)args->q_l;
-  p.q_r = (const u32x4*)args->q_r;
-  p.q_o = (const u32x4*)args->q_o;
-  p.q_4 = (const u32x4*)args->q_4;
-  p.q_c = (const u32x4*)args->q_c;
-  p.q_arith = (const u32x4*)args->q_arith;
-  p.q_range = (const u32x4*)args->q_range;
-  p.q_logic = (const u32x4*)args->q_logic;
-  p.q_fixed = (const u32x4*)args->q_fixed_group_add;
-  p.q_var = (const u32x4*)args->q_variable_group_add;
-  p.pi = (const u32x4*)args->pi;
-  p.l1 = (const u32x4*)args->l1;
-  p.x = (const u32x4*)args->x;
-  p.out = (u32x4*)d_out;
+  const QuotPtrs p = quot_ptrs(*args, d_out);
   const void* all[] = {p.w[0], p.w[1], p.w[2], p.w[3], p.s[0], p.s[1], p.s[2], p.s[3], p.z,  p.q_m,
                        p.q_l,  p.q_r,  p.q_o,  p.q_4,  p.q_c,  p.pi,   p.l1,   p.x,    p.out};
   for (const void* q : all)
     if (!q) return set_err(ctx, PM_ERR_BAD_ARG, "null device pointer");
-  RoundConsts kc;
-  fill_round_consts(kc, load_fr(args->alpha), load_fr(args->beta), load_fr(args->gamma), args->k, args->zh_inv);
   const bool widgets = p.q_range || p.q_logic || p.q_fixed || p.q_var;
-  WidgetConsts wc;
-  fill_widget_consts(wc, args, widgets);
+  OneProof src;
+  fill_round_consts(src.kc, load_fr(args->alpha), load_fr(args->beta), load_fr(args->gamma), args->k, args->zh_inv);
+  fill_widget_consts(src.wc, args, widgets);
   PM_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
   ProfScope prof(ctx, st, "plonk_quotient");
   QuotLayout L;
   memset(&L, 0, sizeof L);
   const size_t wrap = 4 * n + (halo ? 4 : 0);
+  const dim3 grid(grid_for(ctx, 4 * n));
   if (planar) {
     while (((size_t)1 << L.log_m) < n) ++L.log_m;
     L.n2 = planar->n2;
@@ -1064,13 +925,13 @@ int pm::plonk_quotient_layout(pm_ctx* ctx, const pm_plonk_quotient_args* args, s
     if (!L.halo_z || !L.halo_w[0] || !L.halo_w[1] || !L.halo_w[3] || L.n2 == 0 || (L.n2 & (L.n2 - 1)) || L.n2 > n)
       return set_err(ctx, PM_ERR_BAD_ARG, "planar quotient layout: halo rows missing or row length not a power of two <= rows");
     if (widgets)
-      hipLaunchKernelGGL((quotient_kernel<true, true>), dim3(grid_for(ctx, 4 * n)), dim3(256), 0, st, p, kc, wc, 4 * n, wrap, L);
+      hipLaunchKernelGGL((quotient_kernel<true, true, OneProof>), grid, dim3(256), 0, st, p, src, 4 * n, wrap, L);
     else
-      hipLaunchKernelGGL((quotient_kernel<false, true>), dim3(grid_for(ctx, 4 * n)), dim3(256), 0, st, p, kc, wc, 4 * n, wrap, L);
+      hipLaunchKernelGGL((quotient_kernel<false, true, OneProof>), grid, dim3(256), 0, st, p, src, 4 * n, wrap, L);
   } else if (widgets) {
-    hipLaunchKernelGGL((quotient_kernel<true, false>), dim3(grid_for(ctx, 4 * n)), dim3(256), 0, st, p, kc, wc, 4 * n, wrap, L);
+    hipLaunchKernelGGL((quotient_kernel<true, false, OneProof>), grid, dim3(256), 0, st, p, src, 4 * n, wrap, L);
   } else {
-    hipLaunchKernelGGL((quotient_kernel<false, false>), dim3(grid_for(ctx, 4 * n)), dim3(256), 0, st, p, kc, wc, 4 * n, wrap, L);
+    hipLaunchKernelGGL((quotient_kernel<false, false, OneProof>), grid, dim3(256), 0, st, p, src, 4 * n, wrap, L);
   }
   PM_HIP(ctx, hipGetLastError());
   return PM_OK;

@@ -65,35 +65,51 @@ PM_DEV Fr block_sum_256(Fr v, u32* sh /* 256 * 9 words */) {
   }
   return v;
 }
-// the two power tables of one evaluation in ONE launch (two launches of ~12 us each were a third of a small circuit's
-// opening round): xpow[t] = x^t for t < 256 and xblk[b] = x^(b SEG)
-__global__ void __launch_bounds__(256) eval_tables_kernel(u32x4* xpow, u32x4* xblk, const NttConsts c, u32 nblocks, u32 seg) {
-  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+// the two power tables of one evaluation point in ONE launch (two launches of ~12 us each were a third of a small circuit's
+// opening round): xpow[t] = x^t for t < 256 and xblk[b] = x^(b SEG).  Src: From{Args,Table}<EvalConsts>; blockIdx.y = the
+// point, its tables at xpow + 256 y and xblk + nblocks y
+template <class Src>
+__global__ void __launch_bounds__(256) eval_tables_kernel(u32x4* xpow, u32x4* xblk, const Src src, u32 nblocks, u32 seg) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x, y = Src::slot();
+  const EvalConsts& kc = src.at(y);
+  xpow += 3 * 256 * (size_t)y;
+  xblk += 3 * (size_t)nblocks * y;
   if (i < 256u) {
-    st_tw(xpow, i, fr_canon(fr_pow(fr_limbs(c.w8[0]), i, fr_limbs(c.scale))));
+    st_tw(xpow, i, fr_canon(fr_pow(fr_limbs(kc.x), i, fr_limbs(kc.one))));
   } else if (i - 256u < nblocks) {
     const u32 b = i - 256u;
-    st_tw(xblk, b, fr_canon(fr_pow(fr_limbs(c.w8[0]), (unsigned long long)b * seg, fr_limbs(c.scale))));
+    st_tw(xblk, b, fr_canon(fr_pow(fr_limbs(kc.x), (unsigned long long)b * seg, fr_limbs(kc.one))));
   }
 }
-// partial[b] = x^(b SEG) * sum_{i in segment b} c_i x^(i - b SEG),  SEG = 256 L, strided Horner
+// partial[b] = x^(b SEG) * sum_{i in segment b} c_i x^(i - b SEG),  SEG = 256 L, strided Horner.  blockIdx.y = slot j,
+// blockIdx.z = proof: the polynomial is p[j] + proof stride[j] (len[j] coefficients) and the point is number
+// 2 proof + point[j] of the launch's points.  One proof at one point: strides and points zero, Src = FromArgs<EvalConsts>.
+static_assert(PM_LINCOMB_MAX <= PM_EVAL_BATCH_SLOTS, "the one-proof evaluation passes up to PM_LINCOMB_MAX polynomials in these slots");
 struct EvalPolys {
-  const u32x4* p[PM_LINCOMB_MAX];   // blockIdx.y selects the polynomial
+  const u32x4* p[PM_EVAL_BATCH_SLOTS];
+  size_t stride[PM_EVAL_BATCH_SLOTS];
+  size_t len[PM_EVAL_BATCH_SLOTS];   // coefficients of slot j (<= the n the geometry was laid out for)
+  u32 point[PM_EVAL_BATCH_SLOTS];
 };
-__global__ void __launch_bounds__(256) poly_eval_kernel(const EvalPolys polys, size_t n, u32 L, const EvalConsts kc,
-                                                         const u32x4* xpow /* x^t, t < 256 */,
-                                                         const u32x4* xblk /* x^(b SEG) */, u32x4* partial_all) {
+template <class Src>
+__global__ void __launch_bounds__(256) poly_eval_kernel(const EvalPolys polys, u32 L, const Src src,
+                                                         const u32x4* xpow_all /* x^t, t < 256 */,
+                                                         const u32x4* xblk_all /* x^(b SEG) */, u32x4* partial_all) {
   __shared__ u32 sh[256 * 9];
-  const u32 t = threadIdx.x, b = blockIdx.x;
-  const u32x4* coeffs = polys.p[blockIdx.y];
-  u32x4* partial = partial_all + 3 * (size_t)blockIdx.y * gridDim.x;
+  const u32 t = threadIdx.x, b = blockIdx.x, j = blockIdx.y, proof = blockIdx.z;
+  const u32 pt = proof * 2 + polys.point[j];
+  const u32x4* coeffs = polys.p[j] + 2 * (size_t)proof * polys.stride[j];
+  const u32x4* xpow = xpow_all + 3 * 256 * (size_t)pt;
+  const u32x4* xblk = xblk_all + 3 * (size_t)gridDim.x * pt;
+  u32x4* partial = partial_all + 3 * ((size_t)proof * gridDim.y + j) * gridDim.x;
   const size_t base = (size_t)b * 256 * L;
-  const Fr xrow = fr_limbs(kc.xrow);
+  const Fr xrow = fr_limbs(src.at(pt).xrow);
+  const size_t len = polys.len[j];
   Fr acc = fe_zero<FrP>();
-  for (u32 j = L; j-- > 0;) {
-    const size_t idx = base + (size_t)j * 256 + t;
+  for (u32 jj = L; jj-- > 0;) {
+    const size_t idx = base + (size_t)jj * 256 + t;
     acc = fe_mul<FrP>(acc, xrow);                       // (1, <2)
-    if (idx < n) acc = fe_add<FrP>(acc, ld_canon(coeffs, idx));   // (2, <3)
+    if (idx < len) acc = fe_add<FrP>(acc, ld_canon(coeffs, idx));   // (2, <3)
   }
   acc = fe_mul<FrP>(acc, ld_tw(xpow, t));
   acc = block_sum_256(acc, sh);
@@ -343,17 +359,35 @@ PM_DEV u32 pp_fetch(const u32* slot, Fr& v) {   // -> the tag, 0 = not there yet
 constexpr u32 PP_AHEAD = 4;   // look-back rounds whose records are requested together
 // TW: the vector holds device-form 48-byte entries (an inner level of the chunked scan: the chunk totals) instead of canonical
 // elements, read and written per thread (no LDS staging), and the exclusive products go back in device form -- in place.
-template <bool TW>
-__global__ void __launch_bounds__(256) pp_lookback_kernel(const u32x4* in, size_t n, u32x4* out, u32* ctl, u32 tiles) {
+// Src: which tile of which vector a ticket is.  OneVector: the ticket is the tile.  Segments (the proof-batched form): equal
+// vectors of n elements back to back, seg_tiles tiles and records each; ticket order is (vector, tile) order, so a tile
+// waits only on earlier tiles of its own vector, whose workgroups took their tickets before it did (the residency rule
+// above, per vector).
+struct OneVector {
+  u32 tiles;
+  PM_DEV u32 tile_of(u32 ticket, const u32x4*&, u32x4*&, u32*&, size_t) const { return ticket; }
+};
+struct Segments {
+  u32 seg_tiles, tiles;
+  PM_DEV u32 tile_of(u32 ticket, const u32x4*& in, u32x4*& out, u32*& rec, size_t n) const {
+    const u32 seg = ticket / seg_tiles;
+    in += 2 * (size_t)seg * n;
+    out += 2 * (size_t)seg * n;
+    rec += 12 * (size_t)seg * seg_tiles;
+    return ticket - seg * seg_tiles;
+  }
+};
+template <bool TW, class Src>
+__global__ void __launch_bounds__(256) pp_lookback_kernel(const u32x4* in, size_t n, u32x4* out, u32* ctl, const Src src) {
   extern __shared__ u32x4 sc_lds[];
   __shared__ u32 sh[4 * 9 + 9];
   __shared__ u32 s_tile;
   const u32 t = threadIdx.x, lane = t & 63u, wave = t >> 6;
-  u32* rec = ctl + 16;                    // 12 words per tile
+  u32* rec = ctl + 16;                    // 12 words per tile, vector-major
   if (t == 0) s_tile = atomicAdd(ctl, 1u);
   __syncthreads();
-  const u32 tile = s_tile;
-  if (tile >= tiles) return;
+  if (s_tile >= src.tiles) return;
+  const u32 tile = src.tile_of(s_tile, in, out, rec, n);
   const size_t tile0 = (size_t)tile * SC_TILE;
   u32 w[SC_K][8];
   if (!TW) tile_load(in, (long long)tile0, false, (long long)(n - tile0), sc_lds, w);
@@ -492,7 +526,14 @@ struct RufPowers {
   u32 p[4][RUF_POW_BITS][9];   // [neg_lo | pos_lo | neg_hi | pos_hi]: z^-K, z^K, z^-TILE, z^TILE
   u32 pos_lo_scale[9];         // z^-K: pos_lo[t] = z^(K (t - 1))
 };
-__global__ void __launch_bounds__(256) ruf_sum_tables_kernel(u32x4* tab, const RufPowers c, const RufSum k, u32 tiles) {
+// The three kernels take the constants of their vector from From{Args,Table}<...>: blockIdx.y = the vector, its coefficients
+// at coeffs + y in_stride, its quotient at out + y out_stride, its tables / pre / tot the y-th of equal blocks.
+template <template <class> class From>
+__global__ void __launch_bounds__(256) ruf_sum_tables_kernel(u32x4* tab, const From<RufPowers> cs, const From<RufSum> ks, u32 tiles) {
+  const u32 y = From<RufSum>::slot();
+  tab += 3 * (size_t)y * (512 + 2 * (size_t)tiles);
+  const RufPowers& c = cs.at(y);
+  const RufSum& k = ks.at(y);
   const u32 i = blockIdx.x * 256 + threadIdx.x;
   if (i >= 512 + 2 * tiles) return;
   const u32 which = i < 256 ? 0u : i < 512 ? 1u : i < 512 + tiles ? 2u : 3u;
@@ -510,8 +551,15 @@ __global__ void __launch_bounds__(256) ruf_sum_tables_kernel(u32x4* tab, const R
 PM_DEV Fr fr_wadd(const Fr& a, const Fr& b) { return fe_reduce_weak<FrP>(fe_add<FrP>(a, b)); }
 // stage 1: per thread the scaled chunk value v_g; its exclusive sum over the earlier threads of the tile -> pre[g], the
 // tile's sum -> tot[tile] (48-byte ABI-form entries)
-__global__ void __launch_bounds__(256) ruf_sum_totals_kernel(const u32x4* coeffs, size_t n_coeffs, size_t m, u32x4* pre, u32x4* tot,
-                                                              const RufSum lk, const u32x4* tab) {
+template <class Src>
+__global__ void __launch_bounds__(256) ruf_sum_totals_kernel(const u32x4* coeffs, size_t n_coeffs, size_t m, size_t in_stride,
+                                                              u32x4* pre, u32x4* tot, const Src lks, const u32x4* tab) {
+  const u32 vec = Src::slot(), tiles = gridDim.x;
+  coeffs += 2 * (size_t)vec * in_stride;
+  pre += 3 * (size_t)vec * tiles * 256;
+  tot += 3 * (size_t)vec * tiles;
+  tab += 3 * (size_t)vec * (512 + 2 * (size_t)tiles);
+  const RufSum& lk = lks.at(vec);
   extern __shared__ u32x4 sc_lds[];
   __shared__ u32 sh[4 * 9];
   const u32 t = threadIdx.x, lane = t & 63u, wave = t >> 6, tile = blockIdx.x;
@@ -602,9 +650,17 @@ __global__ void __launch_bounds__(256) ruf_sum_carry_kernel(u32x4* tot, u32 tile
 // stage 3: the carry into the thread's chunk, Y_{g-1} = z^(K (g - 1)) S_{g-1}, S_{g-1} = (sum of the tiles before) + pre[g],
 // and the replay.  SUM_TILES: stage 2 did not run (at most 512 tiles -- up to 2^20 elements: a launch costs more than the
 // sums) -- the workgroup adds up tot[0 .. tile) itself, loads in flight together, one reduction.
-template <bool SUM_TILES>
-__global__ void __launch_bounds__(256) ruf_sum_replay_kernel(const u32x4* coeffs, size_t n_coeffs, size_t m, const u32x4* pre,
-                                                              const u32x4* tot, u32x4* out, const RufSum lk, const u32x4* tab, u32 tiles) {
+template <bool SUM_TILES, class Src>
+__global__ void __launch_bounds__(256) ruf_sum_replay_kernel(const u32x4* coeffs, size_t n_coeffs, size_t m, size_t in_stride,
+                                                              const u32x4* pre, const u32x4* tot, u32x4* out, size_t out_stride,
+                                                              const Src lks, const u32x4* tab, u32 tiles) {
+  const u32 vec = Src::slot();
+  coeffs += 2 * (size_t)vec * in_stride;
+  pre += 3 * (size_t)vec * tiles * 256;
+  tot += 3 * (size_t)vec * tiles;
+  out += 2 * (size_t)vec * out_stride;
+  tab += 3 * (size_t)vec * (512 + 2 * (size_t)tiles);
+  const RufSum& lk = lks.at(vec);
   extern __shared__ u32x4 sc_lds[];
   __shared__ u32 sh[4 * 9];
   const u32 t = threadIdx.x, tile = blockIdx.x;
@@ -747,329 +803,6 @@ __global__ void __launch_bounds__(256) batch_inverse_kernel(u32x4* v, const u32x
   }
 }
 
-// ------------------------------------------------------------------ proof-batched forms (pm_plonk_prove_batch)
-// The kernels above, with blockIdx.y (or the ticket) selecting one of several vectors and its constants read from a device
-// table in the constant address space (wave-uniform index: scalar loads).  The one-vector kernels are left as they are.
-#define PM_KCONST __attribute__((address_space(4)))
-template <class T>
-PM_DEV const T& kconst(const PM_KCONST T* tab, u32 i) {
-  return *(const T*)(tab + i);
-}
-__global__ void __launch_bounds__(256) pp_lookback_batch_kernel(const u32x4* in_all, size_t n, u32x4* out_all, u32* ctl, u32 seg_tiles,
-                                                                 u32 tiles) {
-  constexpr bool TW = false;
-  extern __shared__ u32x4 sc_lds[];
-  __shared__ u32 sh[4 * 9 + 9];
-  __shared__ u32 s_tile;
-  const u32 t = threadIdx.x, lane = t & 63u, wave = t >> 6;
-  u32* rec = ctl + 16;                    // 12 words per tile, proof-major
-  if (t == 0) s_tile = atomicAdd(ctl, 1u);
-  __syncthreads();
-  const u32 ticket = s_tile;
-  if (ticket >= tiles) return;
-  // ticket order is (proof, tile) order: a tile waits only on earlier tiles of its own proof, whose workgroups took their
-  // tickets before it did (the one-proof kernel's residency rule, per proof)
-  const u32 seg = ticket / seg_tiles, tile = ticket - seg * seg_tiles;
-  const u32x4* in = in_all + 2 * (size_t)seg * n;
-  u32x4* out = out_all + 2 * (size_t)seg * n;
-  rec += 12 * (size_t)seg * seg_tiles;
-  const size_t tile0 = (size_t)tile * SC_TILE;
-  u32 w[SC_K][8];
-  if constexpr (!TW) tile_load(in, (long long)tile0, false, (long long)(n - tile0), sc_lds, w);
-  const size_t lo = tile0 + (size_t)t * SC_K;
-  const Fr one = fe_one<FrP>();
-  // 1 the thread's product, then the inclusive scan over the workgroup's threads (as pp_base_kernel)
-  Fr a[SC_K];
-  Fr tot = one;
-  if constexpr (TW) {
-#pragma unroll
-    for (int k = 0; k < SC_K; ++k) a[k] = lo + k < n ? ld_tw(in, lo + k) : one;   // all loads in flight at once
-  }
-#pragma unroll
-  for (int k = 0; k < SC_K; ++k) {
-    if constexpr (!TW) a[k] = lo + k < n ? abi_to_dev(fe_unpack<FrP>(w[k])) : one;
-    tot = k == 0 ? a[0] : fe_mul<FrP>(tot, a[k]);
-  }
-  Fr inc = tot;
-  for (int d = 1; d < 64; d <<= 1) {
-    const Fr o = fr_shfl_up(inc, d);
-    if (lane >= (u32)d) inc = fe_mul<FrP>(inc, o);
-  }
-  if (lane == 63) {
-#pragma unroll
-    for (int i = 0; i < 9; ++i) sh[wave * 9 + i] = inc.l[i];
-  }
-  Fr excl = fr_shfl_up(inc, 1);          // product of the earlier threads of this wave
-  if (lane == 0) excl = one;
-  __syncthreads();
-  Fr tile_total = one;
-#pragma unroll
-  for (u32 wv = 0; wv < 4; ++wv) {
-    Fr o;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) o.l[i] = sh[wv * 9 + i];
-    if (wv < wave) excl = fe_mul<FrP>(excl, o);
-    tile_total = wv == 0 ? o : fe_mul<FrP>(tile_total, o);
-  }
-  // 2 publish, look back (wave 0), publish the inclusive product
-  if (wave == 0) {
-    Fr carry = one;
-    if (tile > 0) {
-      if (lane == 0) pp_publish(rec + 12 * (size_t)tile, tile_total, 1u);
-      // every lane multiplies what it fetches into its OWN running product (one product per round); the product over
-      // the lanes is taken once, after the last round (the tiles in flight are all in the same phase, so the walk goes
-      // back over most of them: ~16 rounds with 1024 resident tiles)
-      Fr mine = one;
-      bool finished = false;
-      for (u32 back = 1; !finished; back += 64 * PP_AHEAD) {
-        // the records of PP_AHEAD rounds are requested together (one round trip instead of PP_AHEAD), then taken in order
-        bool valid[PP_AHEAD];
-        u32 st[PP_AHEAD];
-        Fr got[PP_AHEAD];
-#pragma unroll
-        for (u32 u = 0; u < PP_AHEAD; ++u) {
-          valid[u] = tile >= back + 64 * u + lane;    // predecessor tile - back - 64 u - lane exists
-          st[u] = valid[u] ? pp_fetch(rec + 12 * (size_t)(tile - back - 64 * u - lane), got[u]) : 2u;   // beyond tile 0: "inclusive product = one"
-          if (!valid[u]) got[u] = one;
-        }
-#pragma unroll
-        for (u32 u = 0; u < PP_AHEAD; ++u) {
-          if (finished) break;
-          while (valid[u] && st[u] == 0u) {
-            __builtin_amdgcn_s_sleep(1);
-            st[u] = pp_fetch(rec + 12 * (size_t)(tile - back - 64 * u - lane), got[u]);
-          }
-          const u64 done = __ballot(st[u] == 2u);     // lanes that hold an inclusive product (or lie beyond the start)
-          const u32 first = (u32)__ffsll((long long)done) - 1u;   // (ffs of 0 is 0: wraps to ~0 = none)
-          if (valid[u] && (done == 0 || lane <= first)) mine = fe_mul<FrP>(mine, got[u]);
-          finished = done != 0;
-        }
-      }
-      // product over the lanes (order is irrelevant in a commutative group)
-#pragma unroll
-      for (int d = 32; d > 0; d >>= 1) {
-        Fr o;
-#pragma unroll
-        for (int i = 0; i < 9; ++i) o.l[i] = __shfl_xor(mine.l[i], d);
-        mine = fe_mul<FrP>(mine, o);
-      }
-      carry = mine;
-    }
-    if (lane == 0) {
-      pp_publish(rec + 12 * (size_t)tile, fe_mul<FrP>(carry, tile_total), 2u);
-#pragma unroll
-      for (int i = 0; i < 9; ++i) sh[36 + i] = carry.l[i];
-    }
-  }
-  __syncthreads();
-  // 3 replay from the carry: out_k = (everything before element k), ABI form
-  Fr run;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) run.l[i] = sh[36 + i];
-  if constexpr (TW) {
-    run = fe_mul<FrP>(run, excl);
-#pragma unroll
-    for (int k = 0; k < SC_K; ++k) {
-      if (lo + k < n) st_tw(out, lo + k, run);
-      run = fe_mul<FrP>(run, a[k]);
-    }
-    return;
-  }
-  run = fe_mul<FrP>(fe_mul<FrP>(run, excl), fe_pow2<FrP, 256>());   // device form -> ABI form; ABI x device stays ABI
-#pragma unroll
-  for (int k = 0; k < SC_K; ++k) {
-    fe_canon_pack<FrP>(w[k], run);
-    run = fe_mul<FrP>(run, a[k]);
-  }
-  tile_store(out, (long long)tile0, false, (long long)(n - tile0), sc_lds, w);
-}
-
-__global__ void __launch_bounds__(256) ruf_sum_tables_batch_kernel(u32x4* tab_all, const PM_KCONST RufPowers* cs, const PM_KCONST RufSum* ks,
-                                                                   u32 tiles) {
-  const u32 y = blockIdx.y;
-  u32x4* tab = tab_all + 3 * (size_t)y * (512 + 2 * (size_t)tiles);
-  const RufPowers& c = kconst(cs, y);
-  const RufSum& k = kconst(ks, y);
-  const u32 i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= 512 + 2 * tiles) return;
-  const u32 which = i < 256 ? 0u : i < 512 ? 1u : i < 512 + tiles ? 2u : 3u;
-  u32 e = which == 0 ? i : which == 1 ? i - 256 : which == 2 ? i - 512 : i - 512 - tiles;
-  Fr acc = which == 1 ? fr_limbs(c.pos_lo_scale) : fr_limbs(k.one);
-  if (e >> RUF_POW_BITS) {   // beyond the precomputed squarings: finish from the top power
-    acc = fr_pow(fr_limbs(c.p[which][RUF_POW_BITS - 1]), (unsigned long long)(e >> RUF_POW_BITS) << 1, acc);
-    e &= (1u << RUF_POW_BITS) - 1u;
-  }
-#pragma unroll 1
-  for (int j = 0; j < RUF_POW_BITS; ++j)
-    if ((e >> j) & 1u) acc = fe_mul<FrP>(acc, fr_limbs(c.p[which][j]));
-  st_tw(tab, i, fr_canon(acc));
-}
-
-__global__ void __launch_bounds__(256) ruf_sum_totals_batch_kernel(const u32x4* coeffs_all, size_t n_coeffs, size_t m, size_t in_stride,
-                                                                    u32x4* pre_all, u32x4* tot_all, const PM_KCONST RufSum* lks,
-                                                                    const u32x4* tab_all) {
-  const u32 vec = blockIdx.y, tiles = gridDim.x;
-  const u32x4* coeffs = coeffs_all + 2 * (size_t)vec * in_stride;
-  u32x4* pre = pre_all + 3 * (size_t)vec * tiles * 256;
-  u32x4* tot = tot_all + 3 * (size_t)vec * tiles;
-  const u32x4* tab = tab_all + 3 * (size_t)vec * (512 + 2 * (size_t)tiles);
-  const RufSum& lk = kconst(lks, vec);
-  extern __shared__ u32x4 sc_lds[];
-  __shared__ u32 sh[4 * 9];
-  const u32 t = threadIdx.x, lane = t & 63u, wave = t >> 6, tile = blockIdx.x;
-  const u32x4 *neg_lo = tab, *neg_hi = tab + 3 * 512;
-  const size_t tile0 = (size_t)tile * SC_TILE;
-  u32 w[SC_K][8];
-  tile_load(coeffs, (long long)(n_coeffs - 1 - tile0), true, (long long)(m - tile0), sc_lds, w);
-  const Fr nlo = ld_tw(neg_lo, t), nhi = ld_tw(neg_hi, tile);   // requested before the recurrence, used after it
-  const size_t lo = tile0 + (size_t)t * SC_K;
-  const Fr z = fr_limbs(lk.z), zero = fe_zero<FrP>();
-  // the thread's chunk from a zero start (a short last chunk is padded at the end with zeros: y -> z y; nothing follows it)
-  Fr y = zero;
-#pragma unroll
-  for (int k = 0; k < SC_K; ++k) {
-    const Fr d = lo + k < m ? fe_unpack<FrP>(w[k]) : zero;
-    y = k == 0 ? d : fr_wadd(fe_mul<FrP>(y, z), d);
-  }
-  Fr inc = fe_mul<FrP>(y, fe_mul<FrP>(nhi, nlo));                // v_g = c_g z^(-K g)
-  for (int dd = 1; dd < 64; dd <<= 1) {
-    const Fr o = fr_shfl_up(inc, dd);
-    if (lane >= (u32)dd) inc = fr_wadd(inc, o);
-  }
-  if (lane == 63) {
-#pragma unroll
-    for (int i = 0; i < 9; ++i) sh[wave * 9 + i] = inc.l[i];
-  }
-  Fr excl = fr_shfl_up(inc, 1);          // sum over the earlier threads of this wave
-  if (lane == 0) excl = zero;
-  __syncthreads();
-  Fr tile_total = zero;
-#pragma unroll
-  for (u32 wv = 0; wv < 4; ++wv) {
-    Fr o;
-#pragma unroll
-    for (int i = 0; i < 9; ++i) o.l[i] = sh[wv * 9 + i];
-    if (wv < wave) excl = fr_wadd(excl, o);
-    tile_total = wv == 0 ? o : fr_wadd(tile_total, o);
-  }
-  st_tw(pre, (size_t)tile * 256 + t, excl);
-  if (t == 0) st_tw(tot, tile, tile_total);
-}
-
-__global__ void __launch_bounds__(256) ruf_sum_replay_batch_kernel(const u32x4* coeffs_all, size_t n_coeffs, size_t m, size_t in_stride,
-                                                                    const u32x4* pre_all, const u32x4* tot_all, u32x4* out_all,
-                                                                    size_t out_stride, const PM_KCONST RufSum* lks,
-                                                                    const u32x4* tab_all, u32 tiles) {
-  constexpr bool SUM_TILES = true;
-  const u32 vec = blockIdx.y;
-  const u32x4* coeffs = coeffs_all + 2 * (size_t)vec * in_stride;
-  const u32x4* pre = pre_all + 3 * (size_t)vec * tiles * 256;
-  const u32x4* tot = tot_all + 3 * (size_t)vec * tiles;
-  u32x4* out = out_all + 2 * (size_t)vec * out_stride;
-  const u32x4* tab = tab_all + 3 * (size_t)vec * (512 + 2 * (size_t)tiles);
-  const RufSum& lk = kconst(lks, vec);
-  extern __shared__ u32x4 sc_lds[];
-  __shared__ u32 sh[4 * 9];
-  const u32 t = threadIdx.x, tile = blockIdx.x;
-  const u32x4 *pos_lo = tab + 3 * 256, *pos_hi = tab + 3 * (512 + (size_t)tiles);
-  const size_t tile0 = (size_t)tile * SC_TILE;
-  const Fr zero = fe_zero<FrP>();
-  Fr before;
-  if constexpr (SUM_TILES) {
-    Fr a[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) a[k] = (u32)k * 256 + t < tile ? ld_tw(tot, (size_t)k * 256 + t) : zero;
-    Fr sum = a[0];
-#pragma unroll
-    for (int k = 1; k < 8; ++k) sum = fr_wadd(sum, a[k]);
-#pragma unroll
-    for (int dd = 32; dd > 0; dd >>= 1) {
-      Fr o;
-#pragma unroll
-      for (int i = 0; i < 9; ++i) o.l[i] = __shfl_xor(sum.l[i], dd);
-      sum = fr_wadd(sum, o);
-    }
-    if ((t & 63u) == 0) {
-#pragma unroll
-      for (int i = 0; i < 9; ++i) sh[(t >> 6) * 9 + i] = sum.l[i];
-    }
-  } else {
-    before = ld_tw(tot, tile);
-  }
-  const Fr mine = ld_tw(pre, (size_t)tile * 256 + t);
-  const Fr pw = fe_mul<FrP>(ld_tw(pos_hi, tile), ld_tw(pos_lo, t));
-  u32 w[SC_K][8];
-  tile_load(coeffs, (long long)(n_coeffs - 1 - tile0), true, (long long)(m - tile0), sc_lds, w);   // (its barriers publish sh)
-  if constexpr (SUM_TILES) {
-    before = zero;
-#pragma unroll
-    for (u32 wv = 0; wv < 4; ++wv) {
-      Fr o;
-#pragma unroll
-      for (int i = 0; i < 9; ++i) o.l[i] = sh[wv * 9 + i];
-      before = wv == 0 ? o : fr_wadd(before, o);
-    }
-  }
-  const size_t lo = tile0 + (size_t)t * SC_K;
-  const Fr z = fr_limbs(lk.z);
-  Fr y = fe_mul<FrP>(fr_wadd(before, mine), pw);
-#pragma unroll
-  for (int k = 0; k < SC_K; ++k) {
-    if (lo + k < m) {
-      y = fr_wadd(fe_mul<FrP>(y, z), fe_unpack<FrP>(w[k]));
-      fe_canon_pack<FrP>(w[k], y);
-    }
-  }
-  tile_store(out, (long long)(m - 1 - tile0), true, (long long)(m - tile0), sc_lds, w);
-}
-
-// evaluation: blockIdx.z = proof, blockIdx.y = slot; slot j of proof b is p[j] + b stride[j] at point b * 2 + point[j]
-struct EvalBatchPolys {
-  const u32x4* p[PM_EVAL_BATCH_SLOTS];
-  size_t stride[PM_EVAL_BATCH_SLOTS];
-  size_t len[PM_EVAL_BATCH_SLOTS];   // coefficients of slot j (<= the n the geometry was laid out for)
-  u32 point[PM_EVAL_BATCH_SLOTS];
-};
-__global__ void __launch_bounds__(256) eval_tables_batch_kernel(u32x4* xpow_all, u32x4* xblk_all, const PM_KCONST EvalConsts* kcs,
-                                                                u32 nblocks, u32 seg) {
-  const u32 i = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-  const EvalConsts& kc = kconst(kcs, y);
-  u32x4* xpow = xpow_all + 3 * 256 * (size_t)y;
-  u32x4* xblk = xblk_all + 3 * (size_t)nblocks * y;
-  if (i < 256u) {
-    st_tw(xpow, i, fr_canon(fr_pow(fr_limbs(kc.x), i, fr_limbs(kc.one))));
-  } else if (i - 256u < nblocks) {
-    const u32 b = i - 256u;
-    st_tw(xblk, b, fr_canon(fr_pow(fr_limbs(kc.x), (unsigned long long)b * seg, fr_limbs(kc.one))));
-  }
-}
-__global__ void __launch_bounds__(256) poly_eval_batch_kernel(const EvalBatchPolys polys, u32 L,
-                                                              const PM_KCONST EvalConsts* kcs, const u32x4* xpow_all,
-                                                              const u32x4* xblk_all, u32x4* partial_all) {
-  __shared__ u32 sh[256 * 9];
-  const u32 t = threadIdx.x, b = blockIdx.x, j = blockIdx.y, proof = blockIdx.z;
-  const u32 pt = proof * 2 + polys.point[j];
-  const u32x4* coeffs = polys.p[j] + 2 * (size_t)proof * polys.stride[j];
-  const u32x4* xpow = xpow_all + 3 * 256 * (size_t)pt;
-  const u32x4* xblk = xblk_all + 3 * (size_t)gridDim.x * pt;
-  u32x4* partial = partial_all + 3 * ((size_t)proof * gridDim.y + j) * gridDim.x;
-  const size_t base = (size_t)b * 256 * L;
-  const Fr xrow = fr_limbs(kconst(kcs, pt).xrow);
-  const size_t len = polys.len[j];
-  Fr acc = fe_zero<FrP>();
-  for (u32 jj = L; jj-- > 0;) {
-    const size_t idx = base + (size_t)jj * 256 + t;
-    acc = fe_mul<FrP>(acc, xrow);
-    if (idx < len) acc = fe_add<FrP>(acc, ld_canon(coeffs, idx));
-  }
-  acc = fe_mul<FrP>(acc, ld_tw(xpow, t));
-  acc = block_sum_256(acc, sh);
-  if (t == 0) {
-    acc = fe_mul<FrP>(acc, ld_tw(xblk, b));
-    st_tw(partial, b, acc);
-  }
-}
-
 // ------------------------------------------------------------------ host helpers
 // out[i] = base^(i * stride), `count` device-form entries of 48 bytes at `out` (caller-provided memory)
 static void build_pow(u32x4* out, const HFr& base, u32 count, u32 stride, hipStream_t st) {
@@ -1079,6 +812,30 @@ static void build_pow(u32x4* out, const HFr& base, u32 count, u32 stride, hipStr
   to_limbs29(c.scale, host::one(host::FR()));
   to_limbs29(c.one, host::one(host::FR()));
   hipLaunchKernelGGL(pow_table_kernel, dim3((count + 255) / 256), dim3(256), 0, st, out, c, count, stride);
+}
+// the constants of one evaluation point for segments of `seg` coefficients
+static void fill_eval_consts(EvalConsts& kc, const uint64_t point[4], size_t seg) {
+  HFr x;
+  memcpy(x.l, point, 32);
+  to_limbs29(kc.x, x);
+  to_limbs29(kc.xrow, hfr_pow_u64(x, 256));
+  to_limbs29(kc.xseg, hfr_pow_u64(x, seg));
+  to_limbs29(kc.one, host::one(host::FR()));
+}
+// the constants of one Ruffini division by X - z, z != 0
+static void fill_ruf_consts(RufSum& rs, RufPowers& rp, const HFr& zz) {
+  const host::Field<4>& F = host::FR();
+  const HFr z_inv = host::inv(zz, F);
+  to_limbs29(rs.z, zz);
+  to_limbs29(rs.one, host::one(F));
+  const HFr zk_inv = hfr_pow_u64(z_inv, SC_K);
+  HFr b[4] = {zk_inv, hfr_pow_u64(zz, SC_K), hfr_pow_u64(z_inv, SC_TILE), hfr_pow_u64(zz, SC_TILE)};
+  for (int w_ = 0; w_ < 4; ++w_)
+    for (int j = 0; j < RUF_POW_BITS; ++j) {
+      to_limbs29(rp.p[w_][j], b[w_]);
+      b[w_] = host::mul(b[w_], b[w_], F);
+    }
+  to_limbs29(rp.pos_lo_scale, zk_inv);
 }
 
 }  // namespace pm
@@ -1163,31 +920,22 @@ static int eval_enqueue(pm_ctx* ctx, hipStream_t st, uint32_t k, const void* con
   for (uint32_t j = 0; j < k; ++j) {
     if (!d_polys[j]) return set_err(ctx, PM_ERR_BAD_ARG, "null device pointer");
     polys.p[j] = (const u32x4*)d_polys[j];
+    polys.len[j] = n;
   }
   const u32 L = eval_len_per_thread(k, n);
   const size_t seg = (size_t)256 * L;
   const u32 nblocks = (u32)((n + seg - 1) / seg);
-  HFr x;
-  memcpy(x.l, point, 32);
-  EvalConsts kc;
-  to_limbs29(kc.x, x);
-  to_limbs29(kc.xrow, hfr_pow_u64(x, 256));
-  to_limbs29(kc.xseg, hfr_pow_u64(x, seg));
-  to_limbs29(kc.one, host::one(host::FR()));
+  FromArgs<EvalConsts> kc;
+  fill_eval_consts(kc.c, point, seg);
   u32x4* xpow = (u32x4*)ws;
   u32x4* xblk = xpow + 3 * 256;
   u32x4* partial = xblk + 3 * (size_t)nblocks;
   u32x4* d_out = partial + 3 * (size_t)nblocks * k;
-  {
-    NttConsts c;
-    memset(&c, 0, sizeof c);
-    memcpy(c.w8[0], kc.x, sizeof kc.x);
-    memcpy(c.scale, kc.one, sizeof kc.one);
-    hipLaunchKernelGGL(eval_tables_kernel, dim3((256 + nblocks + 255) / 256), dim3(256), 0, st, xpow, xblk, c, nblocks, (u32)seg);
-  }
+  hipLaunchKernelGGL(eval_tables_kernel<FromArgs<EvalConsts>>, dim3((256 + nblocks + 255) / 256), dim3(256), 0, st, xpow, xblk, kc,
+                     nblocks, (u32)seg);
   {
     ProfScope prof(ctx, st, "fr_poly_evaluate");
-    hipLaunchKernelGGL(poly_eval_kernel, dim3(nblocks, k), dim3(256), 0, st, polys, n, L, kc, (const u32x4*)xpow,
+    hipLaunchKernelGGL(poly_eval_kernel<FromArgs<EvalConsts>>, dim3(nblocks, k), dim3(256), 0, st, polys, L, kc, (const u32x4*)xpow,
                        (const u32x4*)xblk, partial);
     hipLaunchKernelGGL(poly_eval_final_kernel, dim3(k), dim3(256), 0, st, (const u32x4*)partial, nblocks, d_out);
   }
@@ -1287,40 +1035,28 @@ extern "C" int pm_fr_poly_ruffini_dev(pm_ctx* ctx, const void* d_coeffs, size_t 
   int rc = order_scope.rc;
   if (!rc) rc = ensure_buffer(ctx, ctx->poly_ws, (tab_entries + pre_entries + tiles) * 48);
   if (rc) return rc;
-  const host::Field<4>& F = host::FR();
-  const HFr z_inv = host::inv(zz, F);
-  RufSum rs;
-  to_limbs29(rs.z, zz);
-  to_limbs29(rs.one, host::one(F));
-  RufPowers rp;
-  {
-    const HFr zk_inv = hfr_pow_u64(z_inv, SC_K);
-    HFr b[4] = {zk_inv, hfr_pow_u64(zz, SC_K), hfr_pow_u64(z_inv, SC_TILE), hfr_pow_u64(zz, SC_TILE)};
-    for (int w_ = 0; w_ < 4; ++w_)
-      for (int j = 0; j < RUF_POW_BITS; ++j) {
-        to_limbs29(rp.p[w_][j], b[w_]);
-        b[w_] = host::mul(b[w_], b[w_], F);
-      }
-    to_limbs29(rp.pos_lo_scale, zk_inv);
-  }
+  using One = FromArgs<RufSum>;
+  One rs;
+  FromArgs<RufPowers> rp;
+  fill_ruf_consts(rs.c, rp.c, zz);
   const size_t lds = (size_t)SC_LDS_SLOTS * 16;
-  for (const void* fn : {(const void*)ruf_sum_totals_kernel, (const void*)ruf_sum_replay_kernel<false>,
-                         (const void*)ruf_sum_replay_kernel<true>})
+  for (const void* fn : {(const void*)ruf_sum_totals_kernel<One>, (const void*)ruf_sum_replay_kernel<false, One>,
+                         (const void*)ruf_sum_replay_kernel<true, One>})
     if (int lrc = raise_lds_limit(ctx, fn, lds)) return lrc;
   u32x4* tab = (u32x4*)ctx->poly_ws.ptr;
   u32x4* pre = tab + 3 * tab_entries;
   u32x4* tot = pre + 3 * pre_entries;
   ProfScope prof(ctx, st, "fr_poly_ruffini");
-  hipLaunchKernelGGL(ruf_sum_tables_kernel, dim3((unsigned)((tab_entries + 255) / 256)), dim3(256), 0, st, tab, rp, rs, tiles);
-  hipLaunchKernelGGL(ruf_sum_totals_kernel, dim3(tiles), dim3(256), lds, st, (const u32x4*)d_coeffs, n, m, pre, tot, rs,
-                     (const u32x4*)tab);
+  hipLaunchKernelGGL(ruf_sum_tables_kernel<FromArgs>, dim3((unsigned)((tab_entries + 255) / 256)), dim3(256), 0, st, tab, rp, rs, tiles);
+  hipLaunchKernelGGL(ruf_sum_totals_kernel<One>, dim3(tiles), dim3(256), lds, st, (const u32x4*)d_coeffs, n, m, (size_t)0, pre, tot,
+                     rs, (const u32x4*)tab);
   if (tiles > 512) {   // (the in-kernel sum of the tiles before costs ~1200 instructions per thread: worth a launch only while the tiles are few)
     hipLaunchKernelGGL(ruf_sum_carry_kernel, dim3(1), dim3(256), 0, st, tot, tiles);
-    hipLaunchKernelGGL(ruf_sum_replay_kernel<false>, dim3(tiles), dim3(256), lds, st, (const u32x4*)d_coeffs, n, m, (const u32x4*)pre,
-                       (const u32x4*)tot, (u32x4*)d_out, rs, (const u32x4*)tab, tiles);
+    hipLaunchKernelGGL((ruf_sum_replay_kernel<false, One>), dim3(tiles), dim3(256), lds, st, (const u32x4*)d_coeffs, n, m, (size_t)0,
+                       (const u32x4*)pre, (const u32x4*)tot, (u32x4*)d_out, (size_t)0, rs, (const u32x4*)tab, tiles);
   } else {
-    hipLaunchKernelGGL(ruf_sum_replay_kernel<true>, dim3(tiles), dim3(256), lds, st, (const u32x4*)d_coeffs, n, m, (const u32x4*)pre,
-                       (const u32x4*)tot, (u32x4*)d_out, rs, (const u32x4*)tab, tiles);
+    hipLaunchKernelGGL((ruf_sum_replay_kernel<true, One>), dim3(tiles), dim3(256), lds, st, (const u32x4*)d_coeffs, n, m, (size_t)0,
+                       (const u32x4*)pre, (const u32x4*)tot, (u32x4*)d_out, (size_t)0, rs, (const u32x4*)tab, tiles);
   }
   PM_HIP(ctx, hipGetLastError());
   return PM_OK;
@@ -1348,12 +1084,12 @@ extern "C" int pm_fr_prefix_product_dev(pm_ctx* ctx, const void* d_in, size_t n,
     if (!rc) rc = ensure_buffer(ctx, ctx->poly_ws, ctl_bytes);
     if (rc) return rc;
     const size_t lds = (size_t)SC_LDS_SLOTS * 16;
-    const void* fn = (const void*)pp_lookback_kernel<false>;
+    const void* fn = (const void*)pp_lookback_kernel<false, OneVector>;
     if (int lrc = raise_lds_limit(ctx, fn, lds)) return lrc;
     ProfScope prof(ctx, st, "fr_prefix_product");
     PM_HIP(ctx, hipMemsetAsync(ctx->poly_ws.ptr, 0, ctl_bytes, st));
-    hipLaunchKernelGGL(pp_lookback_kernel<false>, dim3(tiles), dim3(256), lds, st, (const u32x4*)d_in, n, (u32x4*)d_out,
-                       (u32*)ctx->poly_ws.ptr, tiles);
+    hipLaunchKernelGGL((pp_lookback_kernel<false, OneVector>), dim3(tiles), dim3(256), lds, st, (const u32x4*)d_in, n, (u32x4*)d_out,
+                       (u32*)ctx->poly_ws.ptr, OneVector{tiles});
     PM_HIP(ctx, hipGetLastError());
     return PM_OK;
   }
@@ -1407,8 +1143,8 @@ extern "C" int pm_fr_prefix_product_dev(pm_ctx* ctx, const void* d_in, size_t n,
   if (top_lookback) {
     u32* ctl = (u32*)((char*)ctx->poly_ws.ptr + lvl_bytes);
     PM_HIP(ctx, hipMemsetAsync(ctl, 0, ctl_bytes, st));
-    hipLaunchKernelGGL(pp_lookback_kernel<true>, dim3(top_tiles), dim3(256), 0, st, (const u32x4*)lvl[last], sz[last], lvl[last], ctl,
-                       top_tiles);
+    hipLaunchKernelGGL((pp_lookback_kernel<true, OneVector>), dim3(top_tiles), dim3(256), 0, st, (const u32x4*)lvl[last], sz[last],
+                       lvl[last], ctl, OneVector{top_tiles});
   } else {
     hipLaunchKernelGGL(pp_base_kernel, dim3(1), dim3(256), 0, st, lvl[last], (u32)sz[last]);
   }
@@ -1463,7 +1199,7 @@ int pm::fr_batch_inverse_mul(pm_ctx* ctx, void* d_inout, const void* d_mul, size
   return PM_OK;
 }
 
-// ---- launchers of the proof-batched kernels (pm_plonk_prove_batch)
+// ---- launchers of the proof-batched forms (pm_plonk_prove_batch)
 size_t pm::prefix_product_batch_ctl_bytes(uint32_t batch, size_t n) {
   return 64 + (size_t)batch * ((n + SC_TILE - 1) / SC_TILE) * 48;
 }
@@ -1474,12 +1210,12 @@ int pm::prefix_product_batch(pm_ctx* ctx, const void* d_in, size_t n, uint32_t b
   // takes the one-vector entry point, whose multi-level scan is the faster form at those sizes anyway
   if (tiles > (size_t)2 * ctx->num_cus) return PM_ERR_LENGTH;
   const size_t lds = (size_t)SC_LDS_SLOTS * 16;
-  if (int lrc = raise_lds_limit(ctx, (const void*)pp_lookback_batch_kernel, lds)) return lrc;
+  if (int lrc = raise_lds_limit(ctx, (const void*)pp_lookback_kernel<false, Segments>, lds)) return lrc;
   PM_HIP(ctx, hipSetDevice(ctx->device));
   ProfScope prof(ctx, st, "fr_prefix_product_batch");
   PM_HIP(ctx, hipMemsetAsync(d_ctl, 0, prefix_product_batch_ctl_bytes(batch, n), st));
-  hipLaunchKernelGGL(pp_lookback_batch_kernel, dim3((unsigned)tiles), dim3(256), lds, st, (const u32x4*)d_in, n, (u32x4*)d_out,
-                     (u32*)d_ctl, (u32)seg_tiles, (u32)tiles);
+  hipLaunchKernelGGL((pp_lookback_kernel<false, Segments>), dim3((unsigned)tiles), dim3(256), lds, st, (const u32x4*)d_in, n,
+                     (u32x4*)d_out, (u32*)d_ctl, Segments{(u32)seg_tiles, (u32)tiles});
   PM_HIP(ctx, hipGetLastError());
   return PM_OK;
 }
@@ -1501,7 +1237,7 @@ int pm::evaluate_batch(pm_ctx* ctx, ConstStage& stage, uint32_t k, const void* c
                    hipStream_t st, const size_t* lens) {
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (k == 0 || k > PM_EVAL_BATCH_SLOTS || batch == 0 || n == 0) return set_err(ctx, PM_ERR_BAD_ARG, "evaluate_batch: bad sizes");
-  EvalBatchPolys ep;
+  EvalPolys ep;
   memset(&ep, 0, sizeof ep);
   for (uint32_t j = 0; j < k; ++j) {
     ep.p[j] = (const u32x4*)polys[j];
@@ -1519,14 +1255,7 @@ int pm::evaluate_batch(pm_ctx* ctx, ConstStage& stage, uint32_t k, const void* c
   void* unused;
   if (!stage.take(sizeof(EvalConsts) * 2 * batch, (void**)&hk, &dk) || !stage.take(32 * (size_t)k * batch, (void**)&h_out, &unused))
     return set_err(ctx, PM_ERR_OOM, "constant table full");
-  for (uint32_t i = 0; i < 2 * batch; ++i) {
-    HFr x;
-    memcpy(x.l, points + 4 * i, 32);
-    to_limbs29(hk[i].x, x);
-    to_limbs29(hk[i].xrow, hfr_pow_u64(x, 256));
-    to_limbs29(hk[i].xseg, hfr_pow_u64(x, seg));
-    to_limbs29(hk[i].one, host::one(host::FR()));
-  }
+  for (uint32_t i = 0; i < 2 * batch; ++i) fill_eval_consts(hk[i], points + 4 * i, seg);
   u32x4* xpow = (u32x4*)d_ws;
   u32x4* xblk = xpow + 3 * 256 * (size_t)(2 * batch);
   u32x4* partial = xblk + 3 * (size_t)nblocks * (2 * batch);
@@ -1535,9 +1264,10 @@ int pm::evaluate_batch(pm_ctx* ctx, ConstStage& stage, uint32_t k, const void* c
   PM_HIP(ctx, hipMemcpyAsync(dk, hk, sizeof(EvalConsts) * 2 * batch, hipMemcpyHostToDevice, st));
   {
     ProfScope prof(ctx, st, "fr_poly_evaluate_batch");
-    hipLaunchKernelGGL(eval_tables_batch_kernel, dim3((256 + nblocks + 255) / 256, 2 * batch), dim3(256), 0, st, xpow, xblk,
-                       (const PM_KCONST EvalConsts*)dk, nblocks, (u32)seg);
-    hipLaunchKernelGGL(poly_eval_batch_kernel, dim3(nblocks, k, batch), dim3(256), 0, st, ep, L, (const PM_KCONST EvalConsts*)dk,
+    const FromTable<EvalConsts> kcs{(const PM_KCONST EvalConsts*)dk};
+    hipLaunchKernelGGL(eval_tables_kernel<FromTable<EvalConsts>>, dim3((256 + nblocks + 255) / 256, 2 * batch), dim3(256), 0, st, xpow,
+                       xblk, kcs, nblocks, (u32)seg);
+    hipLaunchKernelGGL(poly_eval_kernel<FromTable<EvalConsts>>, dim3(nblocks, k, batch), dim3(256), 0, st, ep, L, kcs,
                        (const u32x4*)xpow, (const u32x4*)xblk, partial);
     hipLaunchKernelGGL(poly_eval_final_kernel, dim3(k * batch), dim3(256), 0, st, (const u32x4*)partial, nblocks, d_out);
   }
@@ -1575,24 +1305,14 @@ int pm::ruffini_batch(pm_ctx* ctx, ConstStage& stage, const void* d_in, size_t n
   void *ds, *dp;
   if (!stage.take(sizeof(RufSum) * count, (void**)&hs, &ds) || !stage.take(sizeof(RufPowers) * count, (void**)&hp, &dp))
     return set_err(ctx, PM_ERR_OOM, "constant table full");
-  const host::Field<4>& F = host::FR();
-  for (uint32_t v = 0; v < count; ++v) {   // pm_fr_poly_ruffini_dev's constants, per vector
+  for (uint32_t v = 0; v < count; ++v) {
     HFr zz;
     memcpy(zz.l, zs + 4 * v, 32);
-    const HFr z_inv = host::inv(zz, F);
-    to_limbs29(hs[v].z, zz);
-    to_limbs29(hs[v].one, host::one(F));
-    const HFr zk_inv = hfr_pow_u64(z_inv, SC_K);
-    HFr b[4] = {zk_inv, hfr_pow_u64(zz, SC_K), hfr_pow_u64(z_inv, SC_TILE), hfr_pow_u64(zz, SC_TILE)};
-    for (int w_ = 0; w_ < 4; ++w_)
-      for (int j = 0; j < RUF_POW_BITS; ++j) {
-        to_limbs29(hp[v].p[w_][j], b[w_]);
-        b[w_] = host::mul(b[w_], b[w_], F);
-      }
-    to_limbs29(hp[v].pos_lo_scale, zk_inv);
+    fill_ruf_consts(hs[v], hp[v], zz);
   }
+  using Many = FromTable<RufSum>;
   const size_t lds = (size_t)SC_LDS_SLOTS * 16;
-  for (const void* fn : {(const void*)ruf_sum_totals_batch_kernel, (const void*)ruf_sum_replay_batch_kernel})
+  for (const void* fn : {(const void*)ruf_sum_totals_kernel<Many>, (const void*)ruf_sum_replay_kernel<true, Many>})
     if (int lrc = raise_lds_limit(ctx, fn, lds)) return lrc;
   const size_t tab_entries = 512 + 2 * tiles;
   u32x4* tab = (u32x4*)d_ws;
@@ -1601,13 +1321,13 @@ int pm::ruffini_batch(pm_ctx* ctx, ConstStage& stage, const void* d_in, size_t n
   PM_HIP(ctx, hipSetDevice(ctx->device));
   PM_HIP(ctx, hipMemcpyAsync(ds, hs, (char*)hp - (char*)hs + sizeof(RufPowers) * count, hipMemcpyHostToDevice, st));
   ProfScope prof(ctx, st, "fr_poly_ruffini_batch");
-  hipLaunchKernelGGL(ruf_sum_tables_batch_kernel, dim3((unsigned)((tab_entries + 255) / 256), count), dim3(256), 0, st, tab,
-                     (const PM_KCONST RufPowers*)dp, (const PM_KCONST RufSum*)ds, (u32)tiles);
-  hipLaunchKernelGGL(ruf_sum_totals_batch_kernel, dim3((unsigned)tiles, count), dim3(256), lds, st, (const u32x4*)d_in, n, m, stride,
-                     pre, tot, (const PM_KCONST RufSum*)ds, (const u32x4*)tab);
-  hipLaunchKernelGGL(ruf_sum_replay_batch_kernel, dim3((unsigned)tiles, count), dim3(256), lds, st, (const u32x4*)d_in, n, m, stride,
-                     (const u32x4*)pre, (const u32x4*)tot, (u32x4*)d_out, stride, (const PM_KCONST RufSum*)ds, (const u32x4*)tab,
-                     (u32)tiles);
+  const Many sums{(const PM_KCONST RufSum*)ds};
+  hipLaunchKernelGGL(ruf_sum_tables_kernel<FromTable>, dim3((unsigned)((tab_entries + 255) / 256), count), dim3(256), 0, st, tab,
+                     FromTable<RufPowers>{(const PM_KCONST RufPowers*)dp}, sums, (u32)tiles);
+  hipLaunchKernelGGL(ruf_sum_totals_kernel<Many>, dim3((unsigned)tiles, count), dim3(256), lds, st, (const u32x4*)d_in, n, m, stride,
+                     pre, tot, sums, (const u32x4*)tab);
+  hipLaunchKernelGGL((ruf_sum_replay_kernel<true, Many>), dim3((unsigned)tiles, count), dim3(256), lds, st, (const u32x4*)d_in, n, m,
+                     stride, (const u32x4*)pre, (const u32x4*)tot, (u32x4*)d_out, stride, sums, (const u32x4*)tab, (u32)tiles);
   PM_HIP(ctx, hipGetLastError());
   return PM_OK;
 }

@@ -28,6 +28,32 @@ PM_DEV Fr fr_abi_mul(const Fr& a, const Fr& b) { return fe_reduce_weak<FrP>(fr_s
 PM_DEV Fr ld_canon(const u32x4* p, size_t i) { return fe_load<FrP>(p + 2 * i); }
 PM_DEV void st_canon(u32x4* p, size_t i, const Fr& v) { fe_store<FrP>(p + 2 * i, v); }
 
+// ------------------------------------------------------------------ where a kernel's constants come from
+// Every kernel of poly.hip and plonk_rounds.hip that serves both one vector (or proof) per launch and a batch of them exists
+// ONCE, as a template on a small "source" type: what a launch works on and where its constants sit.
+//   FromArgs<T>   one vector per launch; T travels by value in the kernel arguments
+//   FromTable<T>  blockIdx.y (or an index the kernel derives from it) picks one of several; T sits in a device table in the
+//                 constant address space.  The index is wave-uniform, so every access is a scalar load, as from the arguments.
+// Kernels whose sources differ in more than that define their own pair beside the kernel, with the same two roles.  The body
+// stays IN the __global__ template: moved into a device function that two kernels call, the large ones spill (docs/HISTORY.md).
+#define PM_KCONST __attribute__((address_space(4)))
+template <class T>
+PM_DEV const T& kconst(const PM_KCONST T* tab, u32 i) {
+  return *(const T*)(tab + i);
+}
+template <class T>
+struct FromArgs {
+  T c;
+  static PM_DEV u32 slot() { return 0; }
+  PM_DEV const T& at(u32) const { return c; }
+};
+template <class T>
+struct FromTable {
+  const PM_KCONST T* tab;
+  static PM_DEV u32 slot() { return blockIdx.y; }
+  PM_DEV const T& at(u32 i) const { return kconst(tab, i); }
+};
+
 // ------------------------------------------------------------------ host helpers
 static inline void to_limbs29(u32* dst, HFr v) {  // ABI Montgomery -> device Montgomery limbs
   for (int i = 0; i < 5; ++i) v = host::add(v, v, host::FR());
