@@ -595,6 +595,17 @@ int pm_test_host_field_op(int op, const uint64_t* a, const uint64_t* b, uint64_t
  * workspace bytes, pinned host bytes, (digit, point) pairs at most}. */
 int pm_test_msm_sizing(size_t n, uint32_t batch, long window_bits, uint32_t table_window_bits, uint32_t num_cus,
                        uint64_t out[4]);
+/* Pure host, no device: the decisions of that plan (csrc/msm_plan.h), with the options "msm_chunk" / "msm_lb" as chunk /
+ * lb (0 = the library's choice; num_cus 0 = 256) -- out[32] = {0 the plan's return code, 1 window bits, 2 bucket sets of
+ * the piece, 3 level-1 chunk, 4 shortest chunk for sparse inputs, 5 chunk handed to the histogram kernel, 6 accumulate
+ * levels, 7 level-1 threads, 8 level-1 workgroups, 9 threads per level-1 workgroup, 10 level-1 placement request (LDS
+ * bytes: 82944, 55296 or 0), 11 buckets per lane pair in the bucket reduction (lb), 12 log2 lb, 13 level-1 waves per set
+ * (n1), 14 follow-up reduction levels (n_dev), 15-17 their groups per set, 18 items per set left for the fold, 19
+ * sequences the fold receives, 20 bit planes among them, 21 the device applies the weights (1) or the host fold does (0),
+ * 22 tiles per histogram workgroup, 23 histogram workgroups per MSM, 24 scatter workgroups, 25 partitions, 26-31 zero}.
+ * level_len (may be NULL, 8 entries): entries read by each accumulate level, saturated to 32 bits, zero past the last. */
+int pm_test_msm_plan(size_t n, uint32_t batch, long window_bits, uint32_t table_window_bits, uint32_t num_cus, long chunk,
+                     long lb, uint32_t out[32], uint32_t* level_len);
 /* Pure host, no context: the pass plan of a transform of 2^log_n points (tunables 0 = a fresh context's defaults) --
  * out[20] = {passes, 4 x {log2 radix, log2 columns per tile, threads per workgroup, LDS bytes}, mask of passes that have
  * a kernel, log2 group size of the blocked intermediate layout, 0}. */

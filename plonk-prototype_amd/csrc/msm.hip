@@ -405,10 +405,8 @@ __global__ void __launch_bounds__(128) msm_accumulate_ln_kernel(const AccArgs a)
 //       yields five more planes (the next five bits of the chunk index) and W'.  Independent waves take the jobs.
 //   The host receives  Tt,  the planes Q_0 .. Q_(5 L - 1)  (bit b of the chunk index) and at most four items of the last
 //   W, and evaluates  Tt + lb (sum_b 2^b Q_b + 32^L sum_l l W_l)  by Horner's rule: a doubling costs well under 1 us there.
-static constexpr u32 GROUP = 32;                 // items per wave in the reduction: one per lane PAIR (ec.hip.h, struct Half)
-static constexpr u32 PLANES = 5;                 // log2 GROUP: bit planes one butterfly leaves
+// (GROUP = 32 items per wave, PLANES = 5 = log2 GROUP and RED_WAVES = 4 waves per workgroup in level 1: msm_plan.h)
 static constexpr u32 RED_SLOTS = 2 * GROUP + 48; // 256-byte LDS records per wave: the butterfly's two buffers (64 + 16 x 3)
-static constexpr u32 RED_WAVES = 4;              // waves per workgroup in level 1: one per SIMD of the CU
 
 // LDS traffic of ONE wave: its DS operations execute in order, so a read sees the wave's earlier writes; the fences
 // only keep the compiler from moving them across the step boundary.
@@ -667,8 +665,6 @@ static XYZZ projective_to_xyzz(const uint64_t* xyz) {  // homogeneous (X/Z, Y/Z)
 }
 
 // ------------------------------------------------------------------ driver
-static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 // PM_MSM_DEBUG=1 in the environment: synchronise after every stage and name it on stderr (localises a device fault)
 static bool msm_debug() {
   static const bool on = getenv("PM_MSM_DEBUG") != nullptr;
@@ -683,283 +679,20 @@ static bool msm_debug() {
     }                                                                           \
   } while (0)
 
-// What the host needs to finish one piece of an MSM call (a sub-batch that went through the kernels on its own).
-struct MsmPiece {
-  u32 batch, nsets, c, n_dev, host_items, log_lb, nsets_all;
-  bool finished;        // the device applied the weights (msm_reduce_finish_kernel): ONE record per set
-  const u32* hw;        // pinned host memory: (7 + 5 n_dev) sequences x nsets_all x host_items XYZZ records
-};
-// One piece: every kernel of the pipeline plus the copy of its (7 + 5 n_dev) x nsets_all x host_items result points, enqueued on
-// `st` -- no host synchronisation.  ws == nullptr: nothing is launched, only *need_ws / *need_pinned are set (bytes of
-// device workspace and of pinned host memory a piece of this shape takes).  front_done (optional) is recorded after the
-// last accumulate level: from there on the piece only reads its own buckets (not the control block of the bucket fill).
-static int msm_piece(pm_ctx* ctx, const pm_bases* bases, size_t offset, size_t n, const void* d_scalars, size_t sc_stride,
-                     u32 batch, u32 scalar_form, hipStream_t st, hipEvent_t front_done, char* ws, size_t* need_ws,
-                     void* pinned, size_t* need_pinned, MsmPiece* piece) {
-  MsmGeom g = make_geom(n, ctx->opt_msm_window_bits, bases->table_c, bases->n, batch);
-  if (g.bins > SORT_MAX_BINS || g.rbits > SORT_MAX_RBITS || g.ts == 0)
-    return set_err(ctx, PM_ERR_BAD_ARG, "window width outside what the bucket fill is laid out for");
-  const size_t m = n * batch * g.nwin;  // (key, value) pairs at most: one per non-zero digit
-  const u32 nsets_all = g.nsets * batch;
-  // Entries per thread in the big kernel (measured, profiles/r01_msm_sweep.txt, r02_msm_sweep.txt): about
-  // four times the mean run length m / #buckets when the grid allows it (then a run is split over at
-  // most two neighbouring lanes and the in-wave join costs one addition), at least 128, and never so
-  // long that the grid drops below 2^17 threads; small inputs end up with chunks shorter than a run
-  // and pay up to six additions per wave in the segmented scan instead.
-  // The kernel holds two waves per SIMD, i.e. `slots` threads at a time, and every thread does the same work: a grid
-  // of 3.25 x slots threads (a batch of four MSMs with 128-entry chunks) runs as four rounds, the last one a quarter
-  // full.  So the grid is a whole number of rounds and the chunk follows from it (batch of four: 104 entries, as for
-  // a single MSM; measured: 2.55 -> 2.3 ms of accumulate per MSM in a batch).
-  const size_t avg_run = std::max<size_t>(1, m / ((size_t)g.nbuckets * nsets_all));
-  const size_t slots = (size_t)ctx->num_cus * 4 * 2 * 64;
-  const size_t want = std::max<size_t>(128, 4 * avg_run);
-  const size_t rounds = std::max<size_t>(1, (m + slots * want - 1) / (slots * want));
-  // Small inputs (the commit rounds of a 2^10 .. 2^14-gate circuit) fill a fraction of one round and the kernel's time is
-  // the length of one thread's chain: the chunk goes down to 12 entries, and to 4 where the runs are that short -- below
-  // ~0.6 of a run the in-wave join pays for what the chain saves (profiles/r03_small_msm.txt: batch of four at 2^14,
-  // accumulate 434 -> 365 us; at 2^10, 185 -> 108 us)
-  u32 chunk_lo = (u32)std::min<size_t>(12, std::max<size_t>(4, (6 * avg_run + 9) / 10));
-  u32 L1 = ctx->opt_msm_chunk ? (u32)ctx->opt_msm_chunk
-                              : (u32)std::max<size_t>(chunk_lo, (m + rounds * slots - 1) / (rounds * slots));
-  // r05: while the whole grid fits ONE wave per SIMD -- placed exactly, below -- a thread's time is its chain: chunk mixed
-  // additions at a lone wave's ~11.8 us each, then the in-wave join, one general addition (~16.5 us) per doubling of the lanes
-  // a run is spread over.  The chunk that minimises that sum (profiles/r05_small_msm.txt: 2^12 points, one vector: 12 -> 5
-  // entries, accumulate 174 -> 131 us)
-  const size_t lone_waves = (size_t)ctx->num_cus * 4;
-  if (!ctx->opt_msm_chunk) {
-    double best = 1e30;
-    for (u32 L = 2; L <= 16; ++L) {
-      const size_t waves = ((m + L - 1) / L + 63) / 64;
-      if (waves > lone_waves) continue;
-      const double span = (double)avg_run / L + 1.0;
-      const double cost = 11.8 * L + 16.5 * std::ceil(std::log2(span));
-      if (cost < best) {
-        best = cost;
-        L1 = L;
-        chunk_lo = std::min<u32>(chunk_lo, L);
-      }
-    }
-  }
-  // Partial lists: every level leaves two slots per WAVE; the deeper levels take one slot per lane, so
-  // the list shrinks by 32 per level and ends in a single wave (final level).
-  struct Level {
-    size_t len;   // entries read at this level
-    u32 chunk, offset;
-  };
-  std::vector<Level> lv;
-  lv.push_back({m, L1, 0});
-  {
-    size_t nthr = (m + L1 - 1) / L1;
-    while (nthr > 1) {
-      const size_t len = 2 * ((nthr + 63) / 64);
-      lv.push_back({len, 1, 1});
-      nthr = len + 1;            // one lane per slot, shifted by one
-      if (nthr <= 64) break;     // a single wave: final
-    }
-  }
-  const size_t l1_threads = (m + L1 - 1) / L1;
-  const size_t total_buckets = (size_t)g.nbuckets * nsets_all;
-  // Buckets per lane pair in level 1 of the reduction (a power of two).  A pair does 2 LB + 5 group operations and the
-  // kernel runs ONE wave per SIMD (section 4 above): waves beyond 4 per CU queue for a second round.  Every further
-  // level is a launch of ~5 dependent operations, and the host fold pays per sequence and item it receives.  LB is the
-  // candidate with the smallest estimate of the three together (us; the constants are measured: profiles/r04_small_msm.txt
-  // -- 2^19 buckets: 16, a batch of four: 64, an 8-way shard's 2^15: 1, four sets of 2^12: 4).
-  // The host takes over when at most HOST_ITEMS items per set are left: a launch that folds two or three items is a
-  // ~55 us chain on one wave, the same fold is a handful of additions (~1 us each) in the host fold below.
-  constexpr u32 HOST_ITEMS = 4;
-  struct RedPlan {
-    u32 lb, n1, host_items;
-    std::vector<u32> groups;
-    double est;
-  };
-  auto red_plan = [&](u32 lb) {
-    RedPlan p;
-    p.lb = lb;
-    p.n1 = (g.nbuckets / lb + GROUP - 1) / GROUP;   // waves per set in level 1
-    p.host_items = p.n1;
-    while (p.host_items > HOST_ITEMS) {
-      p.host_items = (p.host_items + GROUP - 1) / GROUP;
-      p.groups.push_back(p.host_items);
-    }
-    const double waves = (double)p.n1 * nsets_all, slots = (double)ctx->num_cus * RED_WAVES;
-    const double rounds = std::ceil(waves / slots), n_seq = (PLANES + 2) + PLANES * (double)p.groups.size();
-    p.est = rounds * (2.0 * lb + 6.0) * 9.0 + 65.0 * (double)p.groups.size() +
-            (double)nsets_all * n_seq * (0.35 * p.host_items + 0.7 * (p.host_items - 1));
-    return p;
-  };
-  RedPlan plan = red_plan(1);
-  if (ctx->opt_msm_lb) {
-    plan = red_plan(std::min<u32>((u32)ctx->opt_msm_lb, g.nbuckets));
-  } else {
-    for (u32 lb = 2; lb <= 256 && lb <= g.nbuckets; lb *= 2) {
-      RedPlan p = red_plan(lb);
-      if (p.est < plan.est) plan = p;
-    }
-  }
-  const u32 LB = plan.lb;
-  u32 log_lb = 0;
-  while ((1u << log_lb) < LB) ++log_lb;
-  const u32 n1 = plan.n1, host_items = plan.host_items;
-  const std::vector<u32>& lvl_groups = plan.groups;   // group counts of the follow-up levels
-  const u32 n_dev = (u32)lvl_groups.size();   // follow-up launches
-  if (n_dev > 3) return set_err(ctx, PM_ERR_BAD_ARG, "internal: bucket reduction deeper than four levels");
-  // what the host receives: 7 + 5 n_dev sequences (Tt, five planes per level, W) of host_items entries per set
-  const u32 n_seq_host = (PLANES + 2) + PLANES * n_dev;
-
-  // workspace layout
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    size_t o = off;
-    off = align_up(off + bytes, 256);
-    return o;
-  };
-  // bucket fill: integer scalars + per-tile count rows (histogram -> scatter), partitioned pairs, sorted keys / values
-  const size_t o_canon = take((size_t)n * batch * 32), o_rows = take((size_t)batch * g.tiles * g.bins * 2);
-  const size_t o_pairs = take(m * 8), o_keys1 = take(m * 4 + 4), o_vals1 = take(m * 4 + 4);
-  const size_t o_buckets = take(total_buckets * 256);
-  std::vector<size_t> o_pkeys(lv.size()), o_ppts(lv.size());
-  for (size_t i = 1; i < lv.size(); ++i) {
-    o_pkeys[i] = take(lv[i].len * 4);
-    o_ppts[i] = take(lv[i].len * 256);
-  }
-  const size_t o_heads = take(lv.size() > 1 ? l1_threads * 256 : 0);
-  // level 1 writes 7 sequences of one record per wave, every further level 5 sequences more of one record per group;
-  // the last one writes to o_win (sequence-major: nsets_all x host_items records per sequence), which the host reads
-  const size_t o_l1 = take((size_t)(PLANES + 2) * nsets_all * n1 * 256);
-  std::vector<size_t> o_lvl(n_dev);
-  for (u32 k = 0; k < n_dev; ++k) o_lvl[k] = take((size_t)((PLANES + 2) + PLANES * (k + 1)) * nsets_all * lvl_groups[k] * 256);
-  const size_t o_win = take((size_t)n_seq_host * nsets_all * host_items * 256);
-  // Who applies the weights: the host fold (~1 us per addition, ~0.65 us per doubling, per set) or one more launch
-  // (msm_reduce_finish_kernel: a fixed chain whatever the number of sets).  One or a few sets: the host.
-  const u32 nplanes = PLANES * (n_dev + 1);
-  const double fold_host_us = (double)nsets_all * (n_seq_host * (0.3 * host_items + 1.0 * (host_items - 1)) + 1.65 * nplanes);
-  const double fold_dev_us = (host_items + 0.72 * (log_lb + nplanes + 1) + 5.0) * 9.0 + 20.0 + 0.5 * nsets_all;
-  const bool use_finish = fold_host_us > fold_dev_us;
-  const size_t o_fin = take(use_finish ? (size_t)nsets_all * 256 : 0);
-  const size_t pinned_bytes = use_finish ? (size_t)nsets_all * 256 : (size_t)n_seq_host * nsets_all * host_items * 256;
-  if (!ws) {
-    *need_ws = off;
-    *need_pinned = pinned_bytes;
-    return PM_OK;
-  }
-  u32 *keys1 = (u32*)(ws + o_keys1), *vals1 = (u32*)(ws + o_vals1);
-  g.ctl_cap = ctx->msm_ctl_cap;   // the block's layout is fixed per allocation, whatever this MSM's partition count
-  u32* ctl = (u32*)ctx->msm_ctl.ptr;
-  u32x4* buckets = (u32x4*)(ws + o_buckets);
-
-  // 1 + 2 bucket fill (msm_sort.hip.h)
-  {
-    u32 tiles_per_wg = 1;   // at most ~2 K workgroups: the partition totals cost one atomic per (workgroup-tile, partition)
-    while ((size_t)batch * ((g.tiles + tiles_per_wg - 1) / tiles_per_wg) > 2048) ++tiles_per_wg;
-    const u32 wgs_per_msm = (g.tiles + tiles_per_wg - 1) / tiles_per_wg;
-    const size_t lds1 = sort_scatter_lds(g), lds2 = sort_local_lds(g);
-    const void* k1 = (const void*)msm_digits_scatter_kernel<SORT_THREADS1>;
-    const void* k2 = (const void*)msm_sort_local_kernel;
-    if (int lrc = raise_lds_limit(ctx, k1, lds1)) return lrc;
-    if (int lrc = raise_lds_limit(ctx, k2, lds2)) return lrc;
-    {
-      ProfScope prof(ctx, st, "msm_digits");
-      hipLaunchKernelGGL(msm_digits_hist_kernel<SORT_THREADS0>, dim3(batch * wgs_per_msm), dim3(SORT_THREADS0), (size_t)g.bins * 4, st,
-                         (const u32x4*)d_scalars, n, sc_stride, scalar_form, g, tiles_per_wg, wgs_per_msm, (u32)l1_threads,
-                         ctx->opt_msm_chunk ? L1 : chunk_lo, ctl, (u32x4*)(ws + o_canon), (unsigned short*)(ws + o_rows));
-      MSM_STAGE(ctx, st, "digits histogram");
-      hipLaunchKernelGGL(msm_digits_scatter_kernel<SORT_THREADS1>, dim3(std::min<u32>(batch * g.tiles, (u32)ctx->num_cus)),
-                         dim3(SORT_THREADS1), lds1, st, (const u32x4*)(ws + o_canon), (const unsigned short*)(ws + o_rows), n, g,
-                         (u32)offset, ctl, (u64*)(ws + o_pairs), batch * g.tiles);
-      MSM_STAGE(ctx, st, "digits scatter");
-    }
-    PM_HIP(ctx, hipGetLastError());
-    {
-      ProfScope prof(ctx, st, "msm_sort_pairs");
-      hipLaunchKernelGGL(msm_sort_local_kernel, dim3(g.np), dim3(SORT_THREADS), lds2, st, g, (const u32*)ctl,
-                         (const u64*)(ws + o_pairs), keys1, vals1);
-      MSM_STAGE(ctx, st, "local sort");
-    }
-    PM_HIP(ctx, hipGetLastError());
-  }
-  // 3 accumulate
-  // empty buckets = the identity = ZZ all zero: only that quarter of every 256-byte record is cleared
-  hipLaunchKernelGGL(msm_clear_buckets_kernel, dim3((unsigned)((total_buckets * 4 + 255) / 256)), dim3(256), 0, st, buckets,
-                     total_buckets);
-  PM_HIP(ctx, hipGetLastError());
-  AccArgs a;
-  memset(&a, 0, sizeof a);
-  a.bases = (const u32x4*)(bases->table_c ? bases->d_table : bases->d_xy);
-  a.trash = g.trash;
-  a.ctl = ctl;
-  a.grid_threads = l1_threads;
-  a.buckets = buckets;
-  a.head_pts = (u32x4*)(ws + o_heads);
-  for (size_t lvl = 0; lvl < lv.size(); ++lvl) {
-    const bool last = (lvl + 1 == lv.size());
-    a.len = lv[lvl].len;
-    a.chunk = lv[lvl].chunk;
-    a.offset = lv[lvl].offset;
-    a.final_level = last ? 1u : 0u;
-    if (lvl == 0) {
-      a.keys = keys1;
-      a.vals = vals1;
-    } else {
-      a.keys = (const u32*)(ws + o_pkeys[lvl]);
-      a.pts_in = (const u32x4*)(ws + o_ppts[lvl]);
-    }
-    if (!last) {
-      a.part_keys = (u32*)(ws + o_pkeys[lvl + 1]);
-      a.part_pts = (u32x4*)(ws + o_ppts[lvl + 1]);
-    }
-    const size_t nthr = lvl == 0 ? l1_threads : (a.len + a.offset + a.chunk - 1) / a.chunk;
-    const unsigned blocks = (unsigned)((nthr + 127) / 128);
-    if (lvl > 0 && last && nthr > 64) return set_err(ctx, PM_ERR_BAD_ARG, "internal: final MSM level wider than a wave");
-    {
-      ProfScope prof(ctx, st, lvl == 0 ? "msm_accumulate_l1" : "msm_accumulate_ln");
-      if (lvl == 0) {
-        // Two waves that share a SIMD run one after the other (oldest first, section 4 of DESIGN.md), and two-wave workgroups
-        // are not spread evenly: a grid of at most one (two) waves per SIMD is launched as four-wave workgroups -- a wave per
-        // SIMD of a CU -- with an LDS request that keeps a second (third) workgroup off the CU.  The kernel uses no LDS.
-        const size_t waves = (nthr + 63) / 64;
-        size_t place_lds = 0;
-        // (just over a half / a third of the CU's 160 KB: what is left -- 79 KB / 52 KB -- still takes the workgroups of the
-        // prover's side stream, the coset transforms that run beside the commitments of rounds 1 and 2; with 96 / 72 KB those
-        // kept accumulate workgroups waiting for a CU: 2^16-gate proofs took 4.13 ms or 4.47 ms, at random)
-        if (waves <= lone_waves) place_lds = 81 * 1024;
-        else if (waves <= 2 * lone_waves) place_lds = 54 * 1024;
-        if (place_lds) {
-          if (int lrc = raise_lds_limit(ctx, (const void*)msm_accumulate_l1_kernel, place_lds)) return lrc;
-          hipLaunchKernelGGL(msm_accumulate_l1_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), place_lds, st, a);
-        } else {
-          hipLaunchKernelGGL(msm_accumulate_l1_kernel, dim3(blocks), dim3(128), 0, st, a);
-        }
-      } else {
-        hipLaunchKernelGGL(msm_accumulate_ln_kernel, dim3(blocks), dim3(128), 0, st, a);
-      }
-      MSM_STAGE(ctx, st, lvl == 0 ? "accumulate level 1" : "accumulate level n");
-    }
-    PM_HIP(ctx, hipGetLastError());
-  }
-  if (front_done) PM_HIP(ctx, hipEventRecord(front_done, st));
-  // 4 bucket reduce: level 1 over the buckets, then the small levels (see msm_bucket_reduce_kernel)
-  u32x4* win = (u32x4*)(ws + o_win);
-  const u32 n_waves = nsets_all * n1;
 #ifdef PM_DEV_STAMPS
-  static unsigned long long* d_stamps = nullptr;
+// PM_MSM_STAMPS in the environment: a stamp buffer for the n_waves waves of the next msm_bucket_reduce_kernel ...
+static unsigned long long* d_stamps = nullptr;
+static int bucket_stamps_arm(pm_ctx* ctx, hipStream_t st, u32 n_waves) {
   if (getenv("PM_MSM_STAMPS")) {
     if (d_stamps) (void)hipFree(d_stamps);
     PM_HIP(ctx, hipMalloc(&d_stamps, (size_t)n_waves * 128));
     PM_HIP(ctx, hipMemsetAsync(d_stamps, 0, (size_t)n_waves * 128, st));
     PM_HIP(ctx, hipMemcpyToSymbolAsync(HIP_SYMBOL(g_bucket_stamps), &d_stamps, sizeof d_stamps, 0, hipMemcpyHostToDevice, st));
   }
-#endif
-  {
-    ProfScope prof(ctx, st, "msm_bucket_chunk");
-    // four-wave workgroups, ONE per CU (its LDS request keeps a second one out): a wave per SIMD
-    const size_t red_lds = (size_t)RED_WAVES * RED_SLOTS * 256;
-    if (int lrc = raise_lds_limit(ctx, (const void*)msm_bucket_reduce_kernel, red_lds)) return lrc;
-    hipLaunchKernelGGL(msm_bucket_reduce_kernel, dim3((n_waves + RED_WAVES - 1) / RED_WAVES), dim3(64 * RED_WAVES), red_lds, st,
-                       (const u32x4*)buckets, g.nbuckets, LB, n1, n_waves, n_dev == 0 && !use_finish ? 1u : 0u,
-                       n_dev == 0 ? win : (u32x4*)(ws + o_l1), (size_t)n_waves * 16);
-  }
-  PM_HIP(ctx, hipGetLastError());
-#ifdef PM_DEV_STAMPS
+  return PM_OK;
+}
+// ... and what its waves left there, on stderr (synchronises the stream)
+static int bucket_stamps_dump(pm_ctx* ctx, hipStream_t st, u32 n_waves, u32 LB) {
   if (getenv("PM_MSM_STAMPS") && d_stamps) {
     PM_HIP(ctx, hipStreamSynchronize(st));
     std::vector<unsigned long long> h((size_t)n_waves * 16);
@@ -993,44 +726,163 @@ static int msm_piece(pm_ctx* ctx, const pm_bases* bases, size_t offset, size_t n
     for (int k = 0; k < 11; ++k) fprintf(stderr, " %u", hist[k]);
     fprintf(stderr, "\n");
   }
+  return PM_OK;
+}
 #endif
-  if (n_dev) {
+
+static MsmTune msm_tune(const pm_ctx* ctx) {
+  return MsmTune{ctx->opt_msm_window_bits, ctx->opt_msm_chunk, ctx->opt_msm_lb, (unsigned)ctx->num_cus};
+}
+static int msm_plan_for(pm_ctx* ctx, const pm_bases* bases, size_t n, u32 batch, MsmPlan* plan) {
+  const char* why = nullptr;
+  const int rc = msm_plan(n, bases->n, batch, bases->table_c, msm_tune(ctx), plan, &why);
+  return rc ? set_err(ctx, rc, why) : PM_OK;
+}
+
+// What the host needs to finish one piece of an MSM call (a sub-batch that went through the kernels on its own).
+struct MsmPiece {
+  const MsmPlan* plan;  // (use_finish: the device applied the weights -- msm_reduce_finish_kernel -- ONE record per set)
+  const u32* hw;        // pinned host memory: (7 + 5 n_dev) sequences x nsets_all x host_items XYZZ records
+};
+// One piece, as planned (msm_plan.h: every size, grid and offset below is the plan's): every kernel of the pipeline plus the
+// copy of its result points to `pinned` (p.pinned_bytes), enqueued on `st` -- no host synchronisation.  ws: p.ws_bytes of
+// device memory.  front_done (optional) is recorded after the last accumulate level: from there on the piece only reads its
+// own buckets (not the control block of the bucket fill).
+static int msm_enqueue(pm_ctx* ctx, const MsmPlan& p, const pm_bases* bases, size_t offset, const void* d_scalars,
+                       size_t sc_stride, u32 scalar_form, hipStream_t st, hipEvent_t front_done, char* ws, void* pinned,
+                       MsmPiece* piece) {
+  const MsmLayout& at = p.at;
+  MsmGeom g = p.g;
+  g.ctl_cap = ctx->msm_ctl_cap;   // the block's layout is fixed per allocation, whatever this MSM's partition count
+  const u32 batch = g.batch, nsets_all = p.nsets_all;
+  u32 *keys1 = (u32*)(ws + at.keys1), *vals1 = (u32*)(ws + at.vals1);
+  u32* ctl = (u32*)ctx->msm_ctl.ptr;
+  u32x4* buckets = (u32x4*)(ws + at.buckets);
+
+  // 1 + 2 bucket fill (msm_sort.hip.h)
+  {
+    const size_t lds1 = sort_scatter_lds(g), lds2 = sort_local_lds(g);
+    const void* k1 = (const void*)msm_digits_scatter_kernel<SORT_THREADS1>;
+    const void* k2 = (const void*)msm_sort_local_kernel;
+    if (int lrc = raise_lds_limit(ctx, k1, lds1)) return lrc;
+    if (int lrc = raise_lds_limit(ctx, k2, lds2)) return lrc;
+    {
+      ProfScope prof(ctx, st, "msm_digits");
+      hipLaunchKernelGGL(msm_digits_hist_kernel<SORT_THREADS0>, dim3(batch * p.wgs_per_msm), dim3(SORT_THREADS0), (size_t)g.bins * 4,
+                         st, (const u32x4*)d_scalars, p.n, sc_stride, scalar_form, g, p.tiles_per_wg, p.wgs_per_msm,
+                         (u32)p.l1_threads, p.chunk_arg, ctl, (u32x4*)(ws + at.canon), (unsigned short*)(ws + at.rows));
+      MSM_STAGE(ctx, st, "digits histogram");
+      hipLaunchKernelGGL(msm_digits_scatter_kernel<SORT_THREADS1>, dim3(p.scatter_wgs), dim3(SORT_THREADS1), lds1, st,
+                         (const u32x4*)(ws + at.canon), (const unsigned short*)(ws + at.rows), p.n, g, (u32)offset, ctl,
+                         (u64*)(ws + at.pairs), batch * g.tiles);
+      MSM_STAGE(ctx, st, "digits scatter");
+    }
+    PM_HIP(ctx, hipGetLastError());
+    {
+      ProfScope prof(ctx, st, "msm_sort_pairs");
+      hipLaunchKernelGGL(msm_sort_local_kernel, dim3(g.np), dim3(SORT_THREADS), lds2, st, g, (const u32*)ctl,
+                         (const u64*)(ws + at.pairs), keys1, vals1);
+      MSM_STAGE(ctx, st, "local sort");
+    }
+    PM_HIP(ctx, hipGetLastError());
+  }
+  // 3 accumulate
+  // empty buckets = the identity = ZZ all zero: only that quarter of every 256-byte record is cleared
+  const size_t total_buckets = (size_t)g.nbuckets * nsets_all;
+  hipLaunchKernelGGL(msm_clear_buckets_kernel, dim3((unsigned)((total_buckets * 4 + 255) / 256)), dim3(256), 0, st, buckets,
+                     total_buckets);
+  PM_HIP(ctx, hipGetLastError());
+  AccArgs a;
+  memset(&a, 0, sizeof a);
+  a.bases = (const u32x4*)(bases->table_c ? bases->d_table : bases->d_xy);
+  a.trash = g.trash;
+  a.ctl = ctl;
+  a.grid_threads = p.l1_threads;
+  a.buckets = buckets;
+  a.head_pts = (u32x4*)(ws + at.heads);
+  for (u32 lvl = 0; lvl < p.n_levels; ++lvl) {
+    const MsmPlan::Level& l = p.lv[lvl];
+    const bool last = (lvl + 1 == p.n_levels);
+    a.len = l.len;
+    a.chunk = l.chunk;
+    a.offset = l.offset;
+    a.final_level = last ? 1u : 0u;
+    if (lvl == 0) {
+      a.keys = keys1;
+      a.vals = vals1;
+    } else {
+      a.keys = (const u32*)(ws + at.pkeys[lvl]);
+      a.pts_in = (const u32x4*)(ws + at.ppts[lvl]);
+    }
+    if (!last) {
+      a.part_keys = (u32*)(ws + at.pkeys[lvl + 1]);
+      a.part_pts = (u32x4*)(ws + at.ppts[lvl + 1]);
+    }
+    {
+      ProfScope prof(ctx, st, lvl == 0 ? "msm_accumulate_l1" : "msm_accumulate_ln");
+      if (lvl == 0) {
+        // (p.place_lds: the kernel uses no LDS, the request places its workgroups -- msm_plan)
+        if (p.place_lds) {
+          if (int lrc = raise_lds_limit(ctx, (const void*)msm_accumulate_l1_kernel, p.place_lds)) return lrc;
+        }
+        hipLaunchKernelGGL(msm_accumulate_l1_kernel, dim3(l.blocks), dim3(l.threads), p.place_lds, st, a);
+      } else {
+        hipLaunchKernelGGL(msm_accumulate_ln_kernel, dim3(l.blocks), dim3(l.threads), 0, st, a);
+      }
+      MSM_STAGE(ctx, st, lvl == 0 ? "accumulate level 1" : "accumulate level n");
+    }
+    PM_HIP(ctx, hipGetLastError());
+  }
+  if (front_done) PM_HIP(ctx, hipEventRecord(front_done, st));
+  // 4 bucket reduce: level 1 over the buckets, then the small levels (see msm_bucket_reduce_kernel)
+  u32x4* win = (u32x4*)(ws + at.win);
+  const u32 n_waves = nsets_all * p.n1;
+#ifdef PM_DEV_STAMPS
+  if (int lrc = bucket_stamps_arm(ctx, st, n_waves)) return lrc;
+#endif
+  {
+    ProfScope prof(ctx, st, "msm_bucket_chunk");
+    // four-wave workgroups, ONE per CU (its LDS request keeps a second one out): a wave per SIMD
+    const size_t red_lds = (size_t)RED_WAVES * RED_SLOTS * 256;
+    if (int lrc = raise_lds_limit(ctx, (const void*)msm_bucket_reduce_kernel, red_lds)) return lrc;
+    hipLaunchKernelGGL(msm_bucket_reduce_kernel, dim3((n_waves + RED_WAVES - 1) / RED_WAVES), dim3(64 * RED_WAVES), red_lds, st,
+                       (const u32x4*)buckets, g.nbuckets, p.lb, p.n1, n_waves, p.n_dev == 0 && !p.use_finish ? 1u : 0u,
+                       p.n_dev == 0 ? win : (u32x4*)(ws + at.l1), (size_t)n_waves * 16);
+  }
+  PM_HIP(ctx, hipGetLastError());
+#ifdef PM_DEV_STAMPS
+  if (int lrc = bucket_stamps_dump(ctx, st, n_waves, p.lb)) return lrc;
+#endif
+  if (p.n_dev) {
     ProfScope prof(ctx, st, "msm_window_sum");
-    const u32x4* in = (const u32x4*)(ws + o_l1);
-    u32 items = n1, n_seq = PLANES + 2;
-    for (u32 k = 0; k < n_dev; ++k) {
-      const u32 groups = lvl_groups[k];
-      const bool last = k + 1 == n_dev;   // writes the host's sequences, fit for conversion
+    const u32x4* in = (const u32x4*)(ws + at.l1);
+    u32 items = p.n1, n_seq = PLANES + 2;
+    for (u32 k = 0; k < p.n_dev; ++k) {
+      const u32 groups = p.groups[k];
+      const bool last = k + 1 == p.n_dev;   // writes the host's sequences, fit for conversion
       RedLevelArgs la;
       la.in = in;
-      la.out = last ? win : (u32x4*)(ws + o_lvl[k]);
+      la.out = last ? win : (u32x4*)(ws + at.lvl[k]);
       la.in_stride = (size_t)nsets_all * items * 16;
       la.out_stride = (size_t)nsets_all * groups * 16;
       la.n_seq_in = n_seq;
       la.n_items = items;
       la.n_groups = groups;
-      la.finalize = last && !use_finish ? 1u : 0u;
+      la.finalize = last && !p.use_finish ? 1u : 0u;
       hipLaunchKernelGGL(msm_reduce_level_kernel, dim3(nsets_all * groups, n_seq), dim3(64), 0, st, la);
       in = la.out;
       items = groups;
       n_seq += PLANES;
     }
   }
-  if (use_finish) {
+  if (p.use_finish) {
     ProfScope prof(ctx, st, "msm_window_sum");
     hipLaunchKernelGGL(msm_reduce_finish_kernel, dim3(nsets_all), dim3(64), 0, st, (const u32x4*)win,
-                       (size_t)nsets_all * host_items * 16, nsets_all, host_items, nplanes, log_lb, (u32x4*)(ws + o_fin));
+                       (size_t)nsets_all * p.host_items * 16, nsets_all, p.host_items, p.nplanes, p.log_lb, (u32x4*)(ws + at.fin));
   }
   PM_HIP(ctx, hipGetLastError());
-  PM_HIP(ctx, hipMemcpyAsync(pinned, ws + (use_finish ? o_fin : o_win), pinned_bytes, hipMemcpyDeviceToHost, st));
-  piece->batch = batch;
-  piece->nsets = g.nsets;
-  piece->c = g.c;
-  piece->n_dev = n_dev;
-  piece->host_items = host_items;
-  piece->finished = use_finish;
-  piece->log_lb = log_lb;
-  piece->nsets_all = nsets_all;
+  PM_HIP(ctx, hipMemcpyAsync(pinned, ws + (p.use_finish ? at.fin : at.win), p.pinned_bytes, hipMemcpyDeviceToHost, st));
+  piece->plan = &p;
   piece->hw = (const u32*)pinned;
   return PM_OK;
 }
@@ -1038,22 +890,23 @@ static int msm_piece(pm_ctx* ctx, const pm_bases* bases, size_t offset, size_t n
 // Tt, the planes Q_0 .. Q_(5 L - 1) (L = n_dev + 1; plane b = the sum of S over the chunks whose index has bit b set) and the
 // last W.  The set's total is  Tt + lb (sum_b 2^b Q_b + 32^L sum_l l W_l),  by Horner's rule from the top.
 static void msm_fold(const MsmPiece& pc, XYZZ* totals) {
+  const MsmPlan& p = *pc.plan;
   const u32* hw = pc.hw;
   auto entry = [&](u32 seq, size_t set, u32 item) {
-    return xyzz_to_host(hw + 64 * (((size_t)seq * pc.nsets_all + set) * pc.host_items + item));
+    return xyzz_to_host(hw + 64 * (((size_t)seq * p.nsets_all + set) * p.host_items + item));
   };
   auto seq_sum = [&](u32 seq, size_t set) {
     XYZZ f = entry(seq, set, 0);
-    for (u32 l = 1; l < pc.host_items; ++l) f = host::xyzz_add(f, entry(seq, set, l));
+    for (u32 l = 1; l < p.host_items; ++l) f = host::xyzz_add(f, entry(seq, set, l));
     return f;
   };
   auto set_total = [&](size_t set) {
-    if (pc.finished) return xyzz_to_host(hw + 64 * set);
-    const u32 nplanes = PLANES * (pc.n_dev + 1), w_seq = nplanes + 1;
+    if (p.use_finish) return xyzz_to_host(hw + 64 * set);
+    const u32 nplanes = p.nplanes, w_seq = nplanes + 1;
     XYZZ acc = host::xyzz_identity();
-    if (pc.host_items > 1) {   // sum_l l W_l as the sum of the suffix sums from l = 1
+    if (p.host_items > 1) {   // sum_l l W_l as the sum of the suffix sums from l = 1
       XYZZ suffix = host::xyzz_identity();
-      for (u32 l = pc.host_items; l-- > 1;) {
+      for (u32 l = p.host_items; l-- > 1;) {
         suffix = host::xyzz_add(suffix, entry(w_seq, set, l));
         acc = host::xyzz_add(acc, suffix);
       }
@@ -1062,15 +915,15 @@ static void msm_fold(const MsmPiece& pc, XYZZ* totals) {
       acc = host::xyzz_double(acc);
       acc = host::xyzz_add(acc, seq_sum(1 + b, set));
     }
-    for (u32 d = 0; d < pc.log_lb; ++d) acc = host::xyzz_double(acc);
+    for (u32 d = 0; d < p.log_lb; ++d) acc = host::xyzz_double(acc);
     return host::xyzz_add(acc, seq_sum(0, set));
   };
-  for (u32 j = 0; j < pc.batch; ++j) {
+  for (u32 j = 0; j < p.g.batch; ++j) {
     XYZZ total = host::xyzz_identity();
-    for (u32 w = pc.nsets; w-- > 0;) {  // one set (table mode): no window doublings at all
-      if (w + 1 < pc.nsets)
-        for (u32 k = 0; k < pc.c; ++k) total = host::xyzz_double(total);
-      total = host::xyzz_add(total, set_total((size_t)j * pc.nsets + w));
+    for (u32 w = p.g.nsets; w-- > 0;) {  // one set (table mode): no window doublings at all
+      if (w + 1 < p.g.nsets)
+        for (u32 k = 0; k < p.g.c; ++k) total = host::xyzz_double(total);
+      total = host::xyzz_add(total, set_total((size_t)j * p.g.nsets + w));
     }
     totals[j] = total;
   }
@@ -1101,19 +954,20 @@ int msm_run(pm_ctx* ctx, const pm_bases* bases, size_t offset, size_t n, const v
   if (order_scope.rc) return order_scope.rc;
   // pieces: pair indices are 31-bit, so a piece holds at most 2^31 - 1 (digit, point) pairs (the 15 key polynomials of
   // a 2^24-gate circuit do not fit one)
-  const size_t pairs_per_msm = n * make_geom(n, ctx->opt_msm_window_bits, bases->table_c, bases->n, 1).nwin;
+  const size_t pairs_per_msm = n * msm_windows(msm_window_bits(n, ctx->opt_msm_window_bits, bases->table_c));
   const size_t max_pairs = ctx->opt_msm_max_pairs ? (size_t)ctx->opt_msm_max_pairs : (size_t)0x7fffffffu;
   if (pairs_per_msm > max_pairs) return set_err(ctx, PM_ERR_LENGTH, "n * windows exceeds 2^31 pairs");
   u32 npieces = ctx->opt_msm_pipeline ? std::min<u32>(batch, 4u) : 1u;
   while ((size_t)((batch + npieces - 1) / npieces) * pairs_per_msm > max_pairs) ++npieces;
   const u32 per_piece = (batch + npieces - 1) / npieces;
   npieces = (batch + per_piece - 1) / per_piece;
-  // sizes: all pieces but the last have per_piece vectors
-  size_t region = 0, pin_each = 0;
-  int rc = msm_piece(ctx, bases, offset, n, d_scalars, sc_stride, per_piece, scalar_form, st, nullptr, nullptr, &region, nullptr,
-                     &pin_each, nullptr);
+  // plans: all pieces but the last have per_piece vectors (and the buffers are sized for those)
+  const u32 last_cnt = batch - (npieces - 1) * per_piece;
+  MsmPlan plan, plan_last;
+  int rc = msm_plan_for(ctx, bases, n, per_piece, &plan);
+  if (rc == PM_OK && last_cnt != per_piece) rc = msm_plan_for(ctx, bases, n, last_cnt, &plan_last);
   if (rc) return rc;
-  region = align_up(region, 4096);
+  const size_t region = msm_align_up(plan.ws_bytes, 4096), pin_each = plan.pinned_bytes;
   rc = ensure_buffer(ctx, ctx->msm_ws, npieces > 1 ? 2 * region : region);
   if (rc) return rc;
   if (ctx->msm_host_pinned_bytes < pin_each * npieces) {
@@ -1122,16 +976,13 @@ int msm_run(pm_ctx* ctx, const pm_bases* bases, size_t offset, size_t n, const v
     ctx->msm_host_pinned_bytes = std::max<size_t>(64 * 256, pin_each * npieces);
     PM_HIP(ctx, hipHostMalloc(&ctx->msm_host_pinned, ctx->msm_host_pinned_bytes, hipHostMallocDefault));
   }
-  {
-    // control block of the bucket fill: zero when idle (the histogram kernel restores that), zeroed when (re)allocated
-    const MsmGeom g1 = make_geom(n, ctx->opt_msm_window_bits, bases->table_c, bases->n, per_piece);
-    if (ctx->msm_ctl_cap < g1.np) {
-      const u32 cap = std::max<u32>(g1.np, 1u << 16);
-      rc = ensure_buffer(ctx, ctx->msm_ctl, sort_ctl_words(cap) * 4);
-      if (rc) return rc;
-      PM_HIP(ctx, hipMemsetAsync(ctx->msm_ctl.ptr, 0, ctx->msm_ctl.bytes, st));
-      ctx->msm_ctl_cap = cap;
-    }
+  // control block of the bucket fill: zero when idle (the histogram kernel restores that), zeroed when (re)allocated
+  if (ctx->msm_ctl_cap < plan.g.np) {
+    const u32 cap = std::max<u32>(plan.g.np, 1u << 16);
+    rc = ensure_buffer(ctx, ctx->msm_ctl, sort_ctl_words(cap) * 4);
+    if (rc) return rc;
+    PM_HIP(ctx, hipMemsetAsync(ctx->msm_ctl.ptr, 0, ctx->msm_ctl.bytes, st));
+    ctx->msm_ctl_cap = cap;
   }
   hipStream_t streams[2] = {st, st};
   if (npieces > 1) {
@@ -1156,10 +1007,10 @@ int msm_run(pm_ctx* ctx, const pm_bases* bases, size_t offset, size_t n, const v
         break;
       }
     }
-    size_t dummy_ws = 0, dummy_pin = 0;
-    rc = msm_piece(ctx, bases, offset, n, (const char*)d_scalars + (size_t)first * sc_stride * 32, sc_stride, cnt, scalar_form, si,
-                   npieces > 1 ? ctx->msm_events[i] : nullptr, (char*)ctx->msm_ws.ptr + (size_t)(i & 1) * region, &dummy_ws,
-                   (char*)ctx->msm_host_pinned + (size_t)i * pin_each, &dummy_pin, &pieces[i]);
+    rc = msm_enqueue(ctx, cnt == per_piece ? plan : plan_last, bases, offset,
+                     (const char*)d_scalars + (size_t)first * sc_stride * 32, sc_stride, scalar_form, si,
+                     npieces > 1 ? ctx->msm_events[i] : nullptr, (char*)ctx->msm_ws.ptr + (size_t)(i & 1) * region,
+                     (char*)ctx->msm_host_pinned + (size_t)i * pin_each, &pieces[i]);
   }
   // whatever was enqueued is waited for, also on an error path: the side stream must be idle when the call returns
   host_mark(ctx, "msm: enqueued");
@@ -1318,26 +1169,45 @@ extern "C" int pm_g1_bases_precompute(pm_ctx* ctx, pm_bases* bases, uint32_t win
 
 extern "C" size_t pm_g1_bases_len(const pm_bases* bases) { return bases ? bases->n : 0; }
 
-// test hook (pure host): what one piece of an MSM call of this shape would take -- the library's own sizing pass, on a
-// context that never touches a device.  out[4]: return code of the sizing pass, device workspace bytes, pinned host bytes,
-// (digit, point) pairs at most.
+// test hook (pure host): what one piece of an MSM call of this shape would take -- the plan the library itself sizes its
+// buffers from (msm_plan.h).  out[4]: return code of the plan, device workspace bytes, pinned host bytes, (digit, point)
+// pairs at most.
 extern "C" int pm_test_msm_sizing(size_t n, uint32_t batch, long window_bits, uint32_t table_window_bits, uint32_t num_cus,
                                   uint64_t out[4]) {
   if (!out || !batch) return PM_ERR_BAD_ARG;
-  pm_ctx ctx;
-  ctx.num_cus = num_cus ? (int)num_cus : 256;
-  ctx.opt_msm_window_bits = window_bits;
-  pm_bases bases;
-  bases.n = n;
-  bases.table_c = table_window_bits;
-  size_t need_ws = 0, need_pin = 0;
-  const int rc = n ? msm_piece(&ctx, &bases, 0, n, nullptr, n, batch, PM_SCALAR_MONTGOMERY, nullptr, nullptr, nullptr, &need_ws,
-                               nullptr, &need_pin, nullptr)
+  MsmPlan plan = MsmPlan();
+  const char* why = nullptr;
+  const int rc = n ? msm_plan(n, n, batch, table_window_bits, MsmTune{window_bits, 0, 0, num_cus ? num_cus : 256u}, &plan, &why)
                    : PM_OK;
   out[0] = (uint64_t)(int64_t)rc;
-  out[1] = need_ws;
-  out[2] = need_pin;
-  out[3] = n ? (uint64_t)n * batch * make_geom(n, window_bits, table_window_bits, table_window_bits ? n : 0, batch).nwin : 0;
+  out[1] = plan.ws_bytes;
+  out[2] = plan.pinned_bytes;
+  out[3] = n ? (uint64_t)n * batch * plan.g.nwin : 0;
+  return PM_OK;
+}
+
+// test hook (pure host): the decisions of that plan; chunk / lb as the options "msm_chunk" / "msm_lb" (0 = the library's
+// choice), num_cus 0 = 256.  out[32]: 0 return code of the plan, 1 window bits, 2 bucket sets of the piece, 3 level-1
+// chunk, 4 shortest chunk for sparse inputs, 5 chunk handed to the histogram kernel, 6 accumulate levels, 7 level-1
+// threads, 8 level-1 workgroups, 9 threads per level-1 workgroup, 10 level-1 placement request (LDS bytes), 11 buckets per
+// lane pair (lb), 12 log2 lb, 13 level-1 waves per set (n1), 14 follow-up reduction levels (n_dev), 15-17 their groups
+// per set, 18 items per set left for the fold, 19 sequences the fold receives, 20 bit planes among them, 21 the device
+// applies the weights (use_finish), 22 tiles per histogram workgroup, 23 histogram workgroups per MSM, 24 scatter
+// workgroups, 25 partitions (control-block entries), 26-31 zero.  level_len (may be NULL): entries read by each of the
+// first eight accumulate levels, saturated to 32 bits, zero beyond the last level.
+extern "C" int pm_test_msm_plan(size_t n, uint32_t batch, long window_bits, uint32_t table_window_bits, uint32_t num_cus,
+                                long chunk, long lb, uint32_t out[32], uint32_t* level_len) {
+  if (!out || !n || !batch) return PM_ERR_BAD_ARG;
+  MsmPlan p = MsmPlan();
+  const char* why = nullptr;
+  const int rc = msm_plan(n, n, batch, table_window_bits, MsmTune{window_bits, chunk, lb, num_cus ? num_cus : 256u}, &p, &why);
+  const uint32_t v[32] = {(uint32_t)rc, p.g.c, p.nsets_all, p.lv[0].chunk, p.chunk_lo, p.chunk_arg, p.n_levels,
+                          (uint32_t)p.l1_threads, p.lv[0].blocks, p.lv[0].threads, (uint32_t)p.place_lds, p.lb, p.log_lb, p.n1,
+                          p.n_dev, p.groups[0], p.groups[1], p.groups[2], p.host_items, p.n_seq_host, p.nplanes,
+                          p.use_finish ? 1u : 0u, p.tiles_per_wg, p.wgs_per_msm, p.scatter_wgs, p.g.np};
+  memcpy(out, v, sizeof v);
+  for (u32 i = 0; i < 8 && level_len; ++i)
+    level_len[i] = i < p.n_levels ? (uint32_t)std::min<size_t>(p.lv[i].len, 0xffffffffu) : 0u;
   return PM_OK;
 }
 

@@ -29,49 +29,19 @@
 
 #include "../../include/plonk_mi355x.h"
 #include "fields.hip.h"
+#include "msm_plan.h"   // MsmGeom, make_geom, part_of, part_range and the layout limits they share with these kernels
 
 namespace pm {
 
 static constexpr u32 KEY_INVALID = 0xffffffffu;
 
 static constexpr u32 SORT_THREADS = 1024;        // local sort: 16 waves
-#ifndef SORT_T1
-#define SORT_T1 1024
-#endif
-static constexpr u32 SORT_THREADS1 = SORT_T1;    // scatter kernel: threads = scalars per tile at most
 #ifndef SORT_T0
 #define SORT_T0 256
 #endif
 static constexpr u32 SORT_THREADS0 = SORT_T0;    // histogram kernel (a tile is walked in steps of this many scalars)
-static constexpr u32 SORT_TILE1_PAIRS = 14 * SORT_THREADS1;   // scatter kernel: pairs staged per tile (8 B each in LDS)
 static constexpr u32 SORT_IPT = 16;              // local sort: pairs per thread and tile
 static constexpr u32 SORT_TILE2_PAIRS = SORT_THREADS * SORT_IPT;
-static constexpr u32 SORT_MAX_BINS = 4096;       // partitions one MSM of a batch may have (LDS histogram of a tile)
-static constexpr u32 SORT_MAX_RBITS = 12;        // local bins: 2^R counters + 2^R cursors in LDS
-
-struct MsmGeom {
-  u32 c;         // window bits
-  u32 nwin;      // digit windows
-  u32 nsets;     // bucket sets per MSM: nwin, or 1 when the bases carry a table of 2^(c w) P
-  u32 batch;     // MSMs sharing the bases in this launch sequence (their sets are laid side by side)
-  u32 bbits;     // c - 1: bits of the bucket field
-  u32 nbuckets;  // 1 << bbits per set
-  u32 trash;     // first key that is not a bucket (nsets * batch << bbits)
-  u32 row_stride;  // table mode: points per table row (value = window * row_stride + index)
-  // the sort plan
-  u32 pbits;     // P: bits of the bucket index that select the partition
-  u32 rbits;     // R = bbits - P: bits left for the local sort
-  u32 sa;        // table mode: the buckets below a_size (the short TOP window's digits land there, on top of every
-  u32 a_size;    //   other window's share) are cut into partitions 2^sa times narrower; 0 = one width everywhere
-  u32 na;        // partitions below a_size
-  u32 na_off;    // na - (a_size >> R): what the narrow region adds to the partition index of the rest
-  u32 pps;       // partitions per bucket set: (1 << P) + na_off
-  u32 bins;      // partitions per MSM of the batch: nsets * pps
-  u32 np;        // partitions in all: batch * bins
-  u32 ts;        // scalars per tile of the histogram / scatter kernels
-  u32 tiles;     // tiles per MSM of the batch
-  u32 ctl_cap;   // partitions the control block is laid out for (>= np; fixed per allocation, set by the caller)
-};
 
 // control block (u32 words) in device memory, zero when idle: the histogram kernel leaves it zeroed again
 static constexpr u32 CTL_TICKET = 0;     // workgroups of the histogram kernel that have flushed
@@ -82,62 +52,6 @@ static constexpr u32 CTL_HEADER = 8;
 // allocated -- NOT the np of the current MSM: only count[] returns to zero, and with offsets that moved with np the
 // counters of one MSM would land on the offsets the previous one left behind
 static inline size_t sort_ctl_words(u32 cap) { return CTL_HEADER + 3 * (size_t)cap + 1; }
-
-static inline MsmGeom make_geom(size_t n, long opt_c, u32 table_c, size_t table_stride, u32 batch) {
-  MsmGeom g;
-  u32 lg = 0;
-  while (((size_t)1 << (lg + 1)) <= (n > 1 ? n : 1)) ++lg;
-  long c = opt_c ? opt_c : (lg < 9 ? 5 : (lg > 20 ? 16 : (long)lg - 4));
-  if (table_c) c = table_c;  // fixed when the table was built
-  g.c = (u32)c;
-  g.nwin = (256 + g.c - 1) / g.c;
-  g.nsets = table_c ? 1u : g.nwin;
-  g.batch = batch;
-  g.bbits = g.c - 1;
-  g.nbuckets = 1u << g.bbits;
-  g.trash = (g.nsets * batch) << g.bbits;
-  g.row_stride = (u32)table_stride;
-  // partitions of ~13 K pairs (one tile of the local sort with room for the spread of uniform digits), as long as a
-  // tile of the scatter kernel still writes runs of several pairs per partition
-  const size_t per_set = table_c ? n * g.nwin : n;
-  u32 p = 0;
-  while (p < g.bbits && (per_set >> p) > 13500) ++p;
-  const u32 p_min = g.bbits > SORT_MAX_RBITS ? g.bbits - SORT_MAX_RBITS : 0u;
-  u32 p_max = 10;
-  while (p_max > p_min && (g.nsets << p_max) > SORT_MAX_BINS) --p_max;
-  if (p > p_max) p = p_max;
-  if (p < p_min) p = p_min;
-  g.pbits = p;
-  g.rbits = g.bbits - p;
-  // With the window table every window feeds ONE bucket set, and the top window is short (c = 20: 16 bits, digits
-  // below 2^15 of 2^19 buckets): the low buckets carry (windows - 1) / 2^bbits + 1 / 2^tb of the pairs each instead
-  // of (windows - 1) / 2^bbits -- 2.3 times the others for c = 20, 24 times for c = 22.  Partitions of equal width
-  // would make 64 (c = 22: 8) workgroups of the local sort run two (ten) tiles while the rest run one; the low
-  // region is cut 2^sa times finer instead, so that every partition holds about the same number of pairs.
-  g.sa = g.a_size = g.na = g.na_off = 0;
-  if (table_c && g.nwin > 1 && p >= 1) {
-    const u32 tbits = 256 - g.c * (g.nwin - 1);   // bits of the top window; the scalar is below 2^255
-    if (tbits < g.c && tbits >= 2 && tbits - 1 >= g.rbits) {
-      const u32 tb = tbits - 1;
-      const double ratio = 1.0 + (double)(1u << (g.bbits - tb)) / (double)(g.nwin - 1);
-      u32 sa = 0;
-      while (ratio / (double)(1u << sa) > 1.18 && sa < g.rbits) ++sa;
-      if (sa) {
-        g.sa = sa;
-        g.a_size = 1u << tb;
-        g.na = g.a_size >> (g.rbits - sa);
-        g.na_off = g.na - (g.a_size >> g.rbits);
-      }
-    }
-  }
-  g.pps = (1u << p) + g.na_off;
-  g.bins = g.nsets * g.pps;
-  g.np = batch * g.bins;
-  g.ts = SORT_TILE1_PAIRS / g.nwin < SORT_THREADS1 ? SORT_TILE1_PAIRS / g.nwin : SORT_THREADS1;
-  g.tiles = (u32)((n + g.ts - 1) / g.ts);
-  g.ctl_cap = g.np;
-  return g;
-}
 
 #ifdef SORT_TIMING   // tools/sort_bench.hip: phase timestamps (100 MHz wall clock) of one workgroup per kernel
 __device__ unsigned long long sort_dbg[3][16];
@@ -154,20 +68,6 @@ __device__ unsigned long long sort_span[3][4096][2];   // [kernel][workgroup]: f
 #else
 #define SORT_T(kern, i)
 #endif
-
-// partition of a bucket inside its set, and back: first bucket and bucket-index bits of a partition
-__host__ __device__ inline u32 part_of(const MsmGeom& g, u32 bucket) {
-  return bucket < g.a_size ? bucket >> (g.rbits - g.sa) : g.na_off + (bucket >> g.rbits);
-}
-__host__ __device__ inline void part_range(const MsmGeom& g, u32 pl, u32& first_bucket, u32& bits) {
-  if (pl < g.na) {
-    bits = g.rbits - g.sa;
-    first_bucket = pl << bits;
-  } else {
-    bits = g.rbits;
-    first_bucket = (pl - g.na_off) << bits;
-  }
-}
 
 // ------------------------------------------------------------------ shared pieces
 // A wave-uniform word that an earlier kernel wrote (partition offsets, the pair count), read with an agent-scope

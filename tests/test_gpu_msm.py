@@ -208,6 +208,52 @@ def test_batched_commits(ctx, oracle, table):
     assert np.array_equal(split, got)
 
 
+def test_plans_of_every_branch_back_to_back(ctx, oracle):
+    """One context, MSMs whose plans (csrc/msm_plan.h) differ in every branch, one after the other -- workspace, pinned buffer
+    and control block are reused across them: two accumulate levels and the device's finish (n = 33), the window table with
+    a follow-up reduction level and the host fold (4097), many sets in a batch (5000 points, 8-bit windows, four vectors),
+    two follow-up reduction levels (2^14, table, msm_lb = 1), deep accumulate levels on an unplaced grid (2^14, msm_chunk =
+    1), and the first shape again.  tests/test_msm_geometry.py holds the recorded decisions of these shapes."""
+    import plonk_prototype_amd as pa
+    import torch
+    n = 1 << 14
+    pts, sc = _edge_inputs(oracle, n, 4242)
+
+    def expect(m, vec=sc):
+        return oracle.g1_msm(pts[:m], vec[:m], SCALAR_MONTGOMERY, 8)
+
+    exp33, exp_n = expect(33), expect(n)
+    bases = []
+
+    def make(points):
+        bases.append(pa.host.Bases(ctx, points))
+        return bases[-1]
+
+    try:
+        t13, t16, plain = make(pts[:4097]).precompute(13), make(pts).precompute(16), make(pts[:5000])
+        assert np.array_equal(gpu_msm_affine(ctx, pts[:33], sc[:33]), exp33)
+        assert np.array_equal(pa.g1_to_affine(t13.msm(sc[:4097]))[0], expect(4097))
+        vecs = [sc[:5000]] + [oracle.fr_sample(4300 + j, 5000) for j in range(3)]
+        d = torch.from_numpy(np.ascontiguousarray(np.concatenate(vecs)).view(np.int64)).cuda()
+        ctx.set_option("msm_window_bits", 8)
+        got = plain.msm_batch_dev(d.data_ptr(), 5000, 4)
+        ctx.set_option("msm_window_bits", 0)
+        for j in range(4):
+            assert np.array_equal(pa.g1_to_affine(got[j])[0], expect(5000, vecs[j])), j
+        ctx.set_option("msm_lb", 1)
+        assert np.array_equal(pa.g1_to_affine(t16.msm(sc))[0], exp_n)
+        ctx.set_option("msm_lb", 0)
+        ctx.set_option("msm_chunk", 1)
+        assert np.array_equal(gpu_msm_affine(ctx, pts, sc), exp_n)
+        ctx.set_option("msm_chunk", 0)
+        assert np.array_equal(gpu_msm_affine(ctx, pts[:33], sc[:33]), exp33)
+    finally:
+        for opt in ("msm_window_bits", "msm_lb", "msm_chunk"):
+            ctx.set_option(opt, 0)
+        for b in bases:
+            b.free()
+
+
 def test_sharded_msm_fold(ctx, oracle):
     """The multi-GPU decomposition on one GPU: shard by points, fold the partials."""
     import plonk_prototype_amd as pa

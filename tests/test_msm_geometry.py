@@ -2,6 +2,8 @@
 pure-host test hook -- no GPU: for every shape the library accepts, the layout fits the kernels' fixed resources and the
 bucket -> partition map is a monotone cover whose inverse (first bucket, width) agrees with it."""
 import ctypes as C
+import json
+import os
 
 import numpy as np
 import pytest
@@ -54,7 +56,7 @@ def test_layout_fits_the_kernels_and_the_partition_map_is_a_cover(lib):
         assert g["nwin"] == -(-256 // g["c"]) and g["nsets"] == (1 if table_c else g["nwin"]), tag
         assert g["bbits"] == g["c"] - 1 and g["pbits"] + g["rbits"] == g["bbits"], tag
         assert g["bins"] == g["nsets"] * g["pps"] and g["np"] == batch * g["bins"], tag
-        # what msm_piece refuses (PM_ERR_BAD_ARG) instead of launching: more bins or local bits than the kernels hold
+        # what msm_plan refuses (PM_ERR_BAD_ARG) instead of launching: more bins or local bits than the kernels hold
         if g["bins"] > MAX_BINS or g["rbits"] > MAX_RBITS or g["ts"] == 0:
             continue
         assert g["lds_scatter"] <= LDS_BYTES and g["lds_local"] <= LDS_BYTES, tag
@@ -101,7 +103,7 @@ def _sizing(lib, n, batch=1, c=0, table_c=0, cus=0):
 
 
 def test_sizing_pass_accepts_every_shape_and_stays_proportionate(lib):
-    """The library's own sizing pass (msm_piece without a workspace), on a context that never touches a device: every
+    """The library's own sizing (the plan of csrc/msm_plan.h, which msm_run sizes its buffers from), no device: every
     shape up to 2^27 points is accepted, the workspace is what the layout says -- pairs three times over (partitioned,
     sorted keys, sorted values) plus 32 B of integer scalar per point, 256 B per bucket, the partial lists -- and grows
     with n (without a table the width follows n)."""
@@ -131,3 +133,72 @@ def test_sizing_pass_accepts_every_shape_and_stays_proportionate(lib):
     # fewer CUs (a partitioned device): still accepted, same pair count
     assert _sizing(lib, 1 << 20, 4, 0, 20, 64)[0] == 0
     assert _sizing(lib, 0)[0:2] == (0, 0)
+
+
+def test_sizing_is_what_the_driver_computed_before_the_plan_moved(lib):
+    """tests/golden/msm_sizing.json: pm_test_msm_sizing's four outputs recorded from the library as it was before the
+    driver's planning moved out of the launch function into csrc/msm_plan.h.  Workspace and pinned bytes depend on the
+    level-1 chunk (through the partial lists and the head slots), on lb, n1, the follow-up groups, the items left for the
+    fold and on who applies the weights, so equality on this grid pins almost the whole plan."""
+    with open(os.path.join(os.path.dirname(__file__), "golden", "msm_sizing.json")) as fh:
+        rec = json.load(fh)
+    assert rec["columns"] == ["table_c", "batch", "n", "num_cus", "rc", "ws_bytes", "pinned_bytes", "pairs"]
+    assert len(rec["rows"]) == 7 * 4 * 24 * 2
+    for table_c, batch, n, cus, rc, ws, pinned, pairs in rec["rows"]:
+        assert _sizing(lib, n, batch, 0, table_c, cus) == (rc, ws, pinned, pairs), (table_c, batch, n, cus)
+
+
+PLAN_KEYS = ("rc", "c", "nsets_all", "L1", "chunk_lo", "chunk_arg", "levels", "l1_threads", "l1_blocks", "l1_block_threads",
+             "place_lds", "lb", "log_lb", "n1", "n_dev", "groups0", "groups1", "groups2", "host_items", "n_seq_host", "nplanes",
+             "use_finish", "tiles_per_wg", "wgs_per_msm", "scatter_wgs", "np")
+
+
+def _plan(lib, n, batch=1, c=0, table_c=0, cus=256, chunk=0, lb=0):
+    out, lens = (C.c_uint32 * 32)(), (C.c_uint32 * 8)()
+    assert lib.pm_test_msm_plan(n, batch, c, table_c, cus, chunk, lb, out, lens) == 0
+    p = dict(zip(PLAN_KEYS, list(out)))
+    assert p["rc"] == 0 and not any(out[len(PLAN_KEYS):])
+    p["level_len"] = [int(v) for v in lens][: p["levels"]]
+    return p
+
+
+# (shape) -> L1, chunk_lo, accumulate levels, lb, n1, n_dev, host_items, use_finish, place_lds: printed by the driver as it
+# was before the plan moved (a throwaway print in its launch function), never taken from msm_plan.h
+PLAN_CHECKED = ("L1", "chunk_lo", "levels", "lb", "n1", "n_dev", "host_items", "use_finish", "place_lds")
+PLAN_RECORDED = [
+    (dict(n=1 << 20, table_c=20), (104, 12, 4, 16, 1024, 2, 1, 0, 54 * 1024)),   # 104-entry chunks, lb 16 for 2^19 buckets
+    (dict(n=1 << 20, table_c=20, batch=4), (104, 12, 4, 64, 256, 2, 1, 0, 0)),   # lb 64 for a batch of four; the grid is not placed
+    (dict(n=1 << 17, table_c=16), (16, 12, 4, 1, 1024, 2, 1, 0, 54 * 1024)),   # an 8-way shard: lb 1 for 2^15 buckets
+    (dict(n=1 << 12, table_c=13), (3, 2, 3, 2, 64, 1, 2, 0, 81 * 1024)),   # the latency model's chunk
+    (dict(n=1 << 12, table_c=13, batch=4), (5, 5, 4, 4, 32, 1, 1, 0, 81 * 1024)),   # lb 4 for four sets of 2^12, a chunk of 5
+    (dict(n=1 << 14, table_c=16, batch=4), (16, 5, 4, 4, 256, 2, 1, 0, 81 * 1024)),
+    (dict(n=1 << 10, batch=4), (3, 3, 3, 1, 1, 0, 1, 1, 81 * 1024)),   # 172 sets: the device applies the weights
+    (dict(n=5000, c=8), (3, 3, 3, 4, 1, 0, 1, 1, 81 * 1024)),
+    (dict(n=1 << 20, table_c=20, lb=1), (104, 12, 4, 1, 16384, 3, 1, 0, 54 * 1024)),   # three follow-up reduction levels
+    (dict(n=1 << 14, chunk=1), (1, 12, 4, 1, 16, 1, 1, 1, 0)),   # deep accumulate levels, not placed
+    (dict(n=1 << 20, table_c=20, batch=4, cus=64), (128, 12, 4, 256, 64, 1, 2, 0, 0)),   # a partitioned device
+    (dict(n=1, chunk=64), (64, 4, 1, 1, 1, 0, 1, 1, 81 * 1024)),   # one thread holds every pair: a single accumulate level
+    (dict(n=33), (2, 2, 2, 1, 1, 0, 1, 1, 81 * 1024)),   # the shapes tests/test_gpu_msm.py runs back to back, from here on
+    (dict(n=4097, table_c=13), (3, 2, 3, 2, 64, 1, 2, 0, 81 * 1024)),
+    (dict(n=5000, c=8, batch=4), (10, 10, 4, 4, 1, 0, 1, 1, 81 * 1024)),
+    (dict(n=1 << 14, table_c=16, lb=1), (4, 4, 4, 1, 1024, 2, 1, 0, 81 * 1024)),
+]
+
+
+@pytest.mark.parametrize("shape,expected", PLAN_RECORDED, ids=[str(i) for i in range(len(PLAN_RECORDED))])
+def test_plan_decisions_are_the_recorded_ones(lib, shape, expected):
+    p = _plan(lib, **shape)
+    assert tuple(p[k] for k in PLAN_CHECKED) == expected, (shape, p)
+    # what follows from them
+    assert p["log_lb"] == p["lb"].bit_length() - 1 and p["nplanes"] == 5 * (p["n_dev"] + 1) and p["n_seq_host"] == p["nplanes"] + 2
+    assert p["chunk_arg"] == (p["L1"] if shape.get("chunk") else p["chunk_lo"])
+    assert p["level_len"][0] // p["L1"] <= p["l1_threads"] <= p["level_len"][0] // p["L1"] + 1
+    threads = 256 if p["place_lds"] else 128
+    assert p["l1_block_threads"] == threads and p["l1_blocks"] == -(-p["l1_threads"] // threads)
+    assert p["level_len"][-1] < 64 or p["levels"] == 1
+
+
+def test_recorded_plans_cover_every_branch():
+    col = {k: {e[i] for _, e in PLAN_RECORDED} for i, k in enumerate(PLAN_CHECKED)}
+    assert col["use_finish"] == {0, 1} and col["place_lds"] == {81 * 1024, 54 * 1024, 0}
+    assert 0 in col["n_dev"] and max(col["n_dev"]) >= 1 and 1 in col["levels"] and max(col["levels"]) >= 3

@@ -11,12 +11,12 @@ for SAN in address undefined; do
   cd $R/plonk-prototype_amd/csrc
   EXTRA="-Xarch_host -fno-omit-frame-pointer"
   [ $SAN = undefined ] && EXTRA="-Xarch_host -fno-sanitize-recover=undefined"
-  for f in api ntt ntt4 msm poly plonk_rounds transcript prover comm; do
+  for f in api ntt ntt4 msm poly plonk_rounds transcript prover comm ec_ntt; do
     /opt/rocm/bin/hipcc -O1 -g -std=c++17 -fPIC --offload-arch=gfx950 -mllvm -pragma-unroll-threshold=1000000 -Wno-unused-function -Wno-pass-failed \
       -Wno-option-ignored -Xarch_host -fsanitize=$SAN $EXTRA -c $f.hip -o $B/$f.o &
   done
   wait
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -Wno-option-ignored -fsanitize=$SAN -o $B/libplonk_$SAN.so $B/{api,ntt,ntt4,msm,poly,plonk_rounds,transcript,prover,comm}.o -ldl
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -Wno-option-ignored -fsanitize=$SAN -o $B/libplonk_$SAN.so $B/{api,ntt,ntt4,msm,poly,plonk_rounds,transcript,prover,comm,ec_ntt}.o -ldl
   RT=$(/opt/rocm/lib/llvm/bin/clang -print-file-name=libclang_rt.asan-x86_64.so)
   [ $SAN = undefined ] && RT=$(/opt/rocm/lib/llvm/bin/clang -print-file-name=libclang_rt.ubsan_standalone-x86_64.so)
   cd $R
