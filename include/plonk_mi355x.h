@@ -23,6 +23,8 @@
  *   pm_plonk_preprocess / _prove <- proof_system::{ProverKey, Prover::prove_with_preprocessed}:
  *                                   the whole five-round prover behind one call        8f N1-N3
  *   pm_g1_fixed_base_mul_dev     <- PublicParameters::setup (powers of tau)             8f N4
+ *   pm_g1_bases_from_compressed  <- CommitKey::from_slice / PublicParameters::from_slice (checked SRS loading),
+ *   pm_g1_decompress / _compress    G1Affine::{from_compressed, to_compressed}           8f N4
  * (include/plonk_mi355x.hpp is the C++ mirror of the same interfaces.)
  *
  * Data layouts are the Rust types' memory, so slices can be passed without marshalling:
@@ -66,7 +68,8 @@ typedef enum {
   PM_ERR_NO_DEVICE = -5,
   PM_ERR_LENGTH = -6,           /* in_len > 2^log_n, or n > number of uploaded bases */
   PM_ERR_EXCHANGE = -7,         /* a multi-GPU exchange (callback or RCCL) failed or a peer gave up */
-  PM_ERR_BUSY = -8              /* the prover key's workspace is in use by another proof */
+  PM_ERR_BUSY = -8,             /* the prover key's workspace is in use by another proof */
+  PM_ERR_POINT = -9             /* a point failed decoding or a requested check; see bad_index / bad_reason */
 } pm_status;
 
 /* pm_fr_ntt flags */
@@ -228,6 +231,39 @@ int pm_g1_fixed_base_mul_dev(pm_ctx* ctx, const uint64_t base_xy[12], const void
  * the inverse NTT of the first n bases); identities allowed.  PM_ERR_LENGTH when n exceeds the bases,
  * PM_ERR_DOMAIN_TOO_LARGE when log_n >= 32.  Allocates n x 320 + n x 32 bytes of scratch for the call; blocks until done. */
 int pm_g1_bases_lagrange(pm_ctx* ctx, const pm_bases* powers, uint32_t log_n, void* d_out_xy, void* hip_stream);
+
+/* ---- Checked commit-key loading: compressed G1 and point checks ----------------------------
+ * The 48-byte zcash encoding of G1Affine::{to_compressed, from_compressed} (dusk's CommitKey::to_var_bytes / from_slice
+ * is n of them back to back): big-endian x; byte 0 bit 7 = compressed (must be set), bit 6 = infinity (then every other
+ * bit must be zero), bit 5 = y is the root above (p - 1) / 2.  Decoding checks x < p and y^2 = x^3 + 4, and with
+ * PM_G1_CHECK_SUBGROUP also [r]P = identity (the identity passes).  Points are ABI affine (x | y, Montgomery R = 2^384,
+ * (0, 0) = identity).  A failed point gives PM_ERR_POINT; bad_index / bad_reason (either may be NULL) receive the LOWEST
+ * failing index and, for that point, the lowest reason that applies -- the same on every run.  The output is always
+ * written in full; a rejected point comes back as (0, 0).  n == 0 is PM_OK; null pointers and unknown flag bits are
+ * PM_ERR_BAD_ARG. */
+#define PM_G1_CHECK_SUBGROUP 1u
+#define PM_G1_BAD_ENCODING 1u          /* malformed encoding, or a coordinate that is not below p */
+#define PM_G1_BAD_NOT_ON_CURVE 2u
+#define PM_G1_BAD_NOT_IN_SUBGROUP 3u
+/* Pure host, no context: one point (a proof's commitments, a verifier key). */
+int pm_g1_compress(const uint64_t xy[12], uint8_t out[48]);
+int pm_g1_decompress(const uint8_t in[48], uint32_t flags, uint64_t xy[12], uint32_t* bad_reason);
+/* Device buffers (n x 48 bytes / n x 96 bytes); the checking calls block until the verdict is on the host. */
+int pm_g1_decompress_dev(pm_ctx* ctx, const void* d_bytes, size_t n, uint32_t flags, void* d_out_xy, uint64_t* bad_index,
+                         uint32_t* bad_reason, void* hip_stream);
+/* Points already in ABI affine form (a key loaded raw): both coordinates below p and on the curve, or the pair (0, 0);
+ * with PM_G1_CHECK_SUBGROUP also in the subgroup.  Reads only. */
+int pm_g1_check_dev(pm_ctx* ctx, const void* d_xy, size_t n, uint32_t flags, uint64_t* bad_index, uint32_t* bad_reason,
+                    void* hip_stream);
+int pm_g1_compress_dev(pm_ctx* ctx, const void* d_xy, size_t n, void* d_bytes_out, void* hip_stream);
+/* The same check on resident bases (pm_g1_bases_upload reduces coordinates mod p, so reason 1 cannot occur here). */
+int pm_g1_bases_check(pm_ctx* ctx, const pm_bases* bases, uint32_t flags, uint64_t* bad_index, uint32_t* bad_reason);
+/* CommitKey::from_slice: n x 48 host bytes -> resident bases; decoded and checked on the device, the points never visit
+ * the host.  No pm_bases on failure (*out = NULL). */
+int pm_g1_bases_from_compressed(pm_ctx* ctx, const uint8_t* bytes, size_t n, uint32_t flags, pm_bases** out,
+                                uint64_t* bad_index, uint32_t* bad_reason);
+/* CommitKey::to_var_bytes: the resident bases as pm_g1_bases_len(bases) x 48 host bytes. */
+int pm_g1_bases_to_compressed(pm_ctx* ctx, const pm_bases* bases, uint8_t* bytes_out);
 
 /* out = sum of k projective points (the group-law "all-reduce" after an all-gather). Host. */
 int pm_g1_fold(const uint64_t* xyz_parts, size_t k, uint64_t out_xyz[18]);

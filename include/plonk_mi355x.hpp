@@ -35,7 +35,11 @@ using G1Projective = std::array<uint64_t, 18>;  // X | Y | Z, normalised by the 
 
 struct Error : std::runtime_error {
   int code;
+  uint64_t bad_index = 0;   // PM_ERR_POINT: the lowest failing point ...
+  uint32_t bad_reason = 0;  // ... and why (PM_G1_BAD_*)
   Error(int c, const std::string& what) : std::runtime_error(what), code(c) {}
+  Error(int c, const std::string& what, uint64_t index, uint32_t reason)
+      : std::runtime_error(what), code(c), bad_index(index), bad_reason(reason) {}
 };
 
 class Context {
@@ -181,6 +185,39 @@ class CommitKey {
   ~CommitKey() { if (bases_) pm_g1_bases_free(ctx_->get(), bases_); }
   CommitKey(const CommitKey&) = delete;
   CommitKey& operator=(const CommitKey&) = delete;
+  CommitKey(CommitKey&& o) noexcept : ctx_(o.ctx_), bases_(o.bases_) { o.bases_ = nullptr; }
+  // CommitKey::from_slice: n x 48 bytes of compressed G1, decoded and checked (encoding, on the curve, and with
+  // check_subgroup of order r) on the GPU.  Error{PM_ERR_POINT} carries bad_index / bad_reason
+  static CommitKey from_bytes(Context& ctx, const std::vector<uint8_t>& bytes, bool check_subgroup = true,
+                              bool precompute = false) {
+    if (bytes.size() % 48) throw Error(PM_ERR_LENGTH, "commit key length is not a multiple of 48");
+    pm_bases* b = nullptr;
+    uint64_t index = 0;
+    uint32_t reason = 0;
+    const uint8_t dummy = 0;
+    const int rc = pm_g1_bases_from_compressed(ctx.get(), bytes.empty() ? &dummy : bytes.data(), bytes.size() / 48,
+                                               check_subgroup ? PM_G1_CHECK_SUBGROUP : 0u, &b, &index, &reason);
+    if (rc == PM_ERR_POINT) throw Error(rc, pm_last_error(ctx.get()), index, reason);
+    ctx.check(rc);
+    CommitKey key(ctx, b);
+    if (precompute) ctx.check(pm_g1_bases_precompute(ctx.get(), key.bases_, 0));
+    return key;
+  }
+  // CommitKey::to_var_bytes: the powers as n x 48 bytes of compressed G1
+  std::vector<uint8_t> to_bytes() const {
+    std::vector<uint8_t> out(pm_g1_bases_len(bases_) * 48);
+    uint8_t dummy = 0;
+    ctx_->check(pm_g1_bases_to_compressed(ctx_->get(), bases_, out.empty() ? &dummy : out.data()));
+    return out;
+  }
+  // for a key loaded raw: every point on the curve (or the identity) and, with subgroup, of order r
+  void check(bool subgroup = true) const {
+    uint64_t index = 0;
+    uint32_t reason = 0;
+    const int rc = pm_g1_bases_check(ctx_->get(), bases_, subgroup ? PM_G1_CHECK_SUBGROUP : 0u, &index, &reason);
+    if (rc == PM_ERR_POINT) throw Error(rc, pm_last_error(ctx_->get()), index, reason);
+    ctx_->check(rc);
+  }
   size_t max_degree() const { return pm_g1_bases_len(bases_) - 1; }
   // commit(polynomial): Error{PM_ERR_LENGTH} = PolynomialDegreeTooLarge
   G1Affine commit(const std::vector<Fr>& coeffs) const {
@@ -196,6 +233,7 @@ class CommitKey {
   class LagrangeCommitKey lagrange(uint32_t log_n) const;
 
  private:
+  CommitKey(Context& ctx, pm_bases* bases) : ctx_(&ctx), bases_(bases) {}
   Context* ctx_;
   pm_bases* bases_ = nullptr;
 };

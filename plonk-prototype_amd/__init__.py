@@ -10,7 +10,7 @@ from ._lib import (BackendMissing, NTT_COSET, NTT_INVERSE, NTT_TRANSPOSED, SCALA
                    SCALAR_MONTGOMERY, load, LIB_PATH)
 from .host import (CommitKey, Context, DeviceVector, Error, EvaluationDomain, LagrangeCommitKey, Polynomial,  # noqa: F401
                    msm_variable_base,
-                   g1_fold, g1_to_affine, domain_info, ntt_plan)
+                   g1_fold, g1_to_affine, g1_compress, g1_decompress, domain_info, ntt_plan)
 from . import field, prover, srs, synthetic, transcript  # noqa: F401,E402
 from .prover import (BatchWorkspace, Circuit, Proof, ProverKey, preprocess, prove, prove_batch,  # noqa: F401,E402
                      random_blinders)

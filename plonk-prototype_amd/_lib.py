@@ -87,6 +87,16 @@ SIGNATURES = {
     "pm_g1_bases_from_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
     "pm_g1_fixed_base_mul_dev": (C.c_int, [C.c_void_p, u64p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p,
                                            C.c_void_p]),
+    "pm_g1_compress": (C.c_int, [u64p, C.POINTER(C.c_uint8)]),
+    "pm_g1_decompress": (C.c_int, [C.POINTER(C.c_uint8), C.c_uint32, u64p, u32p]),
+    "pm_g1_decompress_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, u64p, u32p,
+                                       C.c_void_p]),
+    "pm_g1_check_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, u64p, u32p, C.c_void_p]),
+    "pm_g1_compress_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "pm_g1_bases_check": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, u64p, u32p]),
+    "pm_g1_bases_from_compressed": (C.c_int, [C.c_void_p, C.c_char_p, C.c_size_t, C.c_uint32, C.POINTER(C.c_void_p),
+                                              u64p, u32p]),
+    "pm_g1_bases_to_compressed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "pm_g1_bases_lagrange": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "pm_g1_bases_precompute": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "pm_g1_bases_free": (None, [C.c_void_p, C.c_void_p]),
@@ -185,6 +195,11 @@ PM_ERR_NO_DEVICE = -5
 PM_ERR_LENGTH = -6
 PM_ERR_EXCHANGE = -7
 PM_ERR_BUSY = -8
+PM_ERR_POINT = -9
+
+G1_CHECK_SUBGROUP = 1         # pm_g1_decompress* / pm_g1_check_dev / pm_g1_bases_check flag
+G1_BAD_ENCODING, G1_BAD_NOT_ON_CURVE, G1_BAD_NOT_IN_SUBGROUP = 1, 2, 3
+G1_BAD_REASONS = {1: "malformed encoding or non-canonical coordinate", 2: "not on the curve", 3: "not in the subgroup"}
 
 PLONK_ZK_BLINDERS = 17        # pm_plonk_prove_zk: blinding scalars per proof
 PLONK_ZK_EXTRA_BASES = 10     # ... and commit-key points it needs beyond n

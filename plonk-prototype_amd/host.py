@@ -25,9 +25,11 @@ from ._lib import u64p
 class Error(Exception):
     """Non-zero ``pm_status`` from the C ABI (``code``) with the library's message."""
 
-    def __init__(self, code: int, msg: str):
+    def __init__(self, code: int, msg: str, bad_index: int | None = None, bad_reason: int | None = None):
         super().__init__(f"plonk_mi355x error {code}: {msg}")
         self.code = code
+        # PM_ERR_POINT: the lowest failing point and why (_lib.G1_BAD_*)
+        self.bad_index, self.bad_reason = bad_index, bad_reason
 
 
 def _p(a: np.ndarray):
@@ -57,6 +59,31 @@ class Context:
     def _check(self, rc: int):
         if rc != _lib.PM_OK:
             raise Error(rc, self._lib.pm_last_error(self._h).decode())
+
+    def _check_points(self, rc: int, idx, reason):
+        """As ``_check`` for the calls with a verdict: PM_ERR_POINT carries the failing index and the reason."""
+        if rc == _lib.PM_ERR_POINT:
+            raise Error(rc, self._lib.pm_last_error(self._h).decode(), int(idx.value), int(reason.value))
+        self._check(rc)
+
+    def g1_decompress_dev(self, d_bytes: int, n: int, d_out_xy: int, check_subgroup: bool = True, stream: int = 0):
+        """``pm_g1_decompress_dev``: n x 48 bytes -> n x 96 bytes ABI affine, both in device memory.  A bad point
+        raises :class:`Error` (PM_ERR_POINT, ``bad_index`` / ``bad_reason``); the output is written in full either way."""
+        idx, reason = C.c_uint64(0), C.c_uint32(0)
+        rc = self._lib.pm_g1_decompress_dev(self._h, C.c_void_p(d_bytes), n, _lib.G1_CHECK_SUBGROUP if check_subgroup else 0,
+                                            C.c_void_p(d_out_xy), C.byref(idx), C.byref(reason), C.c_void_p(stream))
+        self._check_points(rc, idx, reason)
+
+    def g1_check_dev(self, d_xy: int, n: int, subgroup: bool = True, stream: int = 0):
+        """``pm_g1_check_dev``: canonical, on the curve (or (0, 0)) and, with ``subgroup``, of order r."""
+        idx, reason = C.c_uint64(0), C.c_uint32(0)
+        rc = self._lib.pm_g1_check_dev(self._h, C.c_void_p(d_xy), n, _lib.G1_CHECK_SUBGROUP if subgroup else 0,
+                                       C.byref(idx), C.byref(reason), C.c_void_p(stream))
+        self._check_points(rc, idx, reason)
+
+    def g1_compress_dev(self, d_xy: int, n: int, d_bytes_out: int, stream: int = 0):
+        """``pm_g1_compress_dev``: n x 96 bytes ABI affine -> n x 48 bytes; asynchronous on ``stream``."""
+        self._check(self._lib.pm_g1_compress_dev(self._h, C.c_void_p(d_xy), n, C.c_void_p(d_bytes_out), C.c_void_p(stream)))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -527,6 +554,37 @@ class Bases:
         self._h = h
         return self
 
+    @classmethod
+    def from_compressed(cls, ctx: Context, data: bytes, check_subgroup: bool = True) -> "Bases":
+        """n x 48 bytes of compressed G1 -> resident bases, decoded and checked on the device
+        (``pm_g1_bases_from_compressed``).  A bad point raises :class:`Error` with PM_ERR_POINT."""
+        if len(data) % 48:
+            raise ValueError("compressed G1 points are 48 bytes each")
+        self = object.__new__(cls)
+        self.ctx, self.n = ctx, len(data) // 48
+        h, idx, reason = C.c_void_p(), C.c_uint64(0), C.c_uint32(0)
+        rc = ctx._lib.pm_g1_bases_from_compressed(ctx._h, bytes(data), self.n, _lib.G1_CHECK_SUBGROUP if check_subgroup else 0,
+                                                  C.byref(h), C.byref(idx), C.byref(reason))
+        self._h = None
+        ctx._check_points(rc, idx, reason)
+        self._h = h
+        return self
+
+    def check(self, subgroup: bool = True):
+        """On the curve (or the identity) and, with ``subgroup``, of order r (``pm_g1_bases_check``): for bases that
+        were uploaded unchecked.  Raises :class:`Error` with PM_ERR_POINT, ``bad_index`` and ``bad_reason``."""
+        idx, reason = C.c_uint64(0), C.c_uint32(0)
+        rc = self.ctx._lib.pm_g1_bases_check(self.ctx._h, self._h, _lib.G1_CHECK_SUBGROUP if subgroup else 0,
+                                             C.byref(idx), C.byref(reason))
+        self.ctx._check_points(rc, idx, reason)
+        return self
+
+    def to_bytes(self) -> bytes:
+        """The bases as n x 48 bytes of compressed G1 (``pm_g1_bases_to_compressed``)."""
+        out = C.create_string_buffer(max(self.n, 1) * 48)
+        self.ctx._check(self.ctx._lib.pm_g1_bases_to_compressed(self.ctx._h, self._h, out))
+        return out.raw[:self.n * 48]
+
     def precompute(self, window_bits: int = 0):
         """Build the resident table of window multiples (``pm_g1_bases_precompute``)."""
         self.ctx._check(self.ctx._lib.pm_g1_bases_precompute(self.ctx._h, self._h, window_bits))
@@ -598,6 +656,33 @@ def g1_fold(parts) -> np.ndarray:
     return out
 
 
+def g1_compress(xy) -> bytes:
+    """``G1Affine::to_compressed`` of one affine point [12] on the host (``pm_g1_compress``)."""
+    lib = _lib.load()
+    p = np.ascontiguousarray(xy, dtype=np.uint64).reshape(12)
+    out = (C.c_uint8 * 48)()
+    rc = lib.pm_g1_compress(_p(p), out)
+    if rc != _lib.PM_OK:
+        raise Error(rc, "pm_g1_compress")
+    return bytes(out)
+
+
+def g1_decompress(data: bytes, check_subgroup: bool = True) -> np.ndarray:
+    """``G1Affine::from_compressed`` (``from_compressed_unchecked`` without ``check_subgroup``) of one point on the
+    host (``pm_g1_decompress``) -> affine [12].  A rejected point raises :class:`Error` with PM_ERR_POINT and ``bad_reason``."""
+    if len(data) != 48:
+        raise ValueError("a compressed G1 point is 48 bytes")
+    lib = _lib.load()
+    out, reason = np.zeros(12, np.uint64), C.c_uint32(0)
+    rc = lib.pm_g1_decompress((C.c_uint8 * 48).from_buffer_copy(data), _lib.G1_CHECK_SUBGROUP if check_subgroup else 0,
+                              _p(out), C.byref(reason))
+    if rc == _lib.PM_ERR_POINT:
+        raise Error(rc, "compressed G1 point rejected: " + _lib.G1_BAD_REASONS[reason.value], 0, int(reason.value))
+    if rc != _lib.PM_OK:
+        raise Error(rc, "pm_g1_decompress")
+    return out
+
+
 def g1_to_affine(xyz):
     """-> (xy[12], is_identity)"""
     lib = _lib.load()
@@ -646,6 +731,31 @@ class CommitKey:
             powers.free()
         if precompute:
             self._bases.precompute()
+        return self
+
+    @classmethod
+    def from_bytes(cls, data: bytes, ctx: Context | None = None, check_subgroup: bool = True,
+                   precompute: bool = False) -> "CommitKey":
+        """``CommitKey::from_slice``: n x 48 bytes of compressed G1 (``srs.commit_key_to_bytes``; no length prefix),
+        decoded and checked -- encoding, on the curve, and with ``check_subgroup`` of order r -- on the GPU; the points go
+        from the decoder to the resident bases without visiting the host.  A bad point raises :class:`Error` with
+        PM_ERR_POINT; its ``bad_index`` / ``bad_reason`` name the lowest failing point."""
+        self = object.__new__(cls)
+        self.ctx = ctx or default_context()
+        self._bases = Bases.from_compressed(self.ctx, data, check_subgroup)
+        self.powers_of_g = None
+        if precompute:
+            self._bases.precompute()
+        return self
+
+    def to_bytes(self) -> bytes:
+        """``CommitKey::to_var_bytes``: the powers as n x 48 bytes of compressed G1, encoded on the GPU."""
+        return self._bases.to_bytes()
+
+    def check(self, subgroup: bool = True) -> "CommitKey":
+        """For a key loaded raw (``srs.commit_key_from_raw_bytes``): every point on the curve (or the identity) and,
+        with ``subgroup``, of order r.  Raises :class:`Error` with PM_ERR_POINT."""
+        self._bases.check(subgroup)
         return self
 
     def max_degree(self) -> int:
