@@ -623,6 +623,23 @@ int pm_profile_read(pm_ctx* ctx, char* buf, size_t cap);
  * n elements. */
 int pm_test_field_op(pm_ctx* ctx, int op, const uint64_t* a, const uint64_t* b, uint64_t* out,
                      size_t n);
+/* The shared inline device routines on RAW limbs (csrc/test_hooks.hip): operands are radix-2^W limbs as given (field 0 = Fr:
+ * 9 x 29 bit, 1 = Fp: 14 x 28 bit; one uint32 per limb, no unpacking, no reduction) and the result limbs come back as the
+ * routine left them (no canonical packing).  One thread per case; a case is IN elements in, OUT elements out, back to back.
+ * op (IN -> OUT): 0 fe_add (2 -> 1), 1 fe_norm, 2 fe_norm_full (1 -> 1), 3 fe_mul (2 -> 1), 4 fe_sqr (1 -> 1), 5 fe_mul_limb
+ * (a, b0 in limb 0 of the second: 2 -> 1), 6 fe_mul2 (a0 b0 a1 b1: 4 -> 2), 7 fe_mul3 (6 -> 3), 8 fe_mma2 (a0 b0 c0 d0 a1 b1:
+ * 6 -> 2), 9 fe_sqr2 (2 -> 2), 10 fe_reduce_weak, 11 fe_unpack (NS saturated words in the first limbs), 12 fe_canon_pack (NS
+ * saturated words out, then zeros), 13 fe_pow2 (limb 0 selects the exponent: 0 = W N, 1 = 2 W N - 32 NS, 2 = 64 NS + W N)
+ * (1 -> 1 each), 14 fe_mul_split<5,6> (x, 2 rows: 3 -> 1), 15 fe_mul_split<1,2> (x, 9 rows: 10 -> 1) (Fr), 16
+ * fp_is_zero_product, 17 fp_is_zero_lazy (1 -> 1, 0 / 1 in limb 0) (Fp), 18 dft8 (x[0..7], w1, w2, w3: 11 -> 8), 19 dft4
+ * (a0..a3, w4: 5 -> 4) (Fr), 32 + K fe_sub<K,1> (2 -> 1) for the K the library instantiates (Fr 2, 3, 5, 9; Fp 2, 3, 5, 6, 8,
+ * 11).  PM_ERR_BAD_ARG for any other (field, op).  Host pointers, n cases. */
+int pm_test_field_raw_op(pm_ctx* ctx, int field, int op, const uint32_t* in, uint32_t* out, size_t n);
+/* The XYZZ group law of csrc/ec.hip.h on raw limbs.  A point is 57 words: X, Y, ZZ, ZZZ (14 Fp limbs each), infinity flag.
+ * op 0 = xyzz_double_affine (X, Y of a), 1 = xyzz_double, 2 = xyzz_madd (X, Y of b: the affine operand), 3 = xyzz_add, 4 =
+ * xyzz_mul_small (word 0 of b: the multiplier), 5 = half_double, 6 = half_add (one point per lane pair, as the reduction
+ * kernels hold it).  b may be NULL for the doublings.  An infinite result has all limbs zero.  Host pointers, n cases. */
+int pm_test_g1_raw_op(pm_ctx* ctx, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t n);
 /* Pure host, no context: the host-side field arithmetic behind the MSM fold and the prover's challenge scalars
  * (csrc/host_field.h).  op 0 = Fr product, 1 = Fp product, 2 = Fr inverse (binary extended Euclid), 3 = Fp inverse, 4 / 5 =
  * the same inverses by exponentiation; Montgomery form in and out, n elements; b is ignored by the inversions. */

@@ -52,7 +52,7 @@ PM_DEV Xyzz xyzz_identity() {
 // 2 * (x, y) for an affine point (mdbl-2008-s-1); x, y in class
 PM_DEV Xyzz xyzz_double_affine(const Fp& x, const Fp& y) {
   Xyzz r;
-  Fp U = fe_add<FpP>(y, y);                                 // (2+, <10)
+  Fp U = fe_add<FpP>(y, y);                                 // (2++, <10): limbs < 2^29 + 32
   Fp V = fe_sqr<FpP>(U);
   Fp W = fe_mul<FpP>(U, V);
   Fp S = fe_mul<FpP>(x, V);
@@ -197,7 +197,7 @@ PM_DEV Half half_identity() {
 // 2 p (dbl-2008-s-1)
 PM_DEV Half half_double(const Half& p, bool isB) {
   if (p.inf) return p;
-  const Fp t = isB ? fe_add<FpP>(p.c0, p.c0) : p.c0;       // B: U = 2 y (2+, <10);  A: x
+  const Fp t = isB ? fe_add<FpP>(p.c0, p.c0) : p.c0;       // B: U = 2 y (2++, <10);  A: x
   const Fp s1 = fe_sqr<FpP>(t);                             // A: XX;  B: V
   const Fp s1o = fp_pair_swap(s1);                          // A: V;   B: XX
   const Fp s2 = fe_mul<FpP>(t, fp_select(isB, s1, s1o));    // A: S = x V;  B: W = U V

@@ -128,7 +128,7 @@ struct Consts {
     return r;
   }
   // k*m with every limb but the top biased by 2^(W+E) - 2^E so that a limb-wise
-  // `a + bias - b` cannot go negative for b limbs < 2^(W+E) - 2^E (top limb: < top of k*m - 2^E)
+  // `a + bias - b` cannot go negative for b limbs <= 2^(W+E) - 2^E (top limb: <= top of k*m - 2^E)
   static PM_HD Limbs<N> sub_bias(u32 k, int E) {
     Limbs<N> r = k_mod(k);
     for (int i = 0; i < N - 1; ++i) {
@@ -162,7 +162,8 @@ PM_DEV Fe<P> fe_add(const Fe<P>& a, const Fe<P>& b) {
   for (int i = 0; i < P::N; ++i) r.l[i] = a.l[i] + b.l[i];
   return r;
 }
-// a - b + K*m.  Requires b limbs < 2^(W+E) - 2^E and b's top limb < top(K*m) - 2^E.
+// a - b + K*m.  Requires b limbs <= 2^(W+E) - 2^E and b's top limb <= top(K*m) - 2^E (the limit itself is allowed: the
+// sum of two products, limbs 2^(W+1) - 2, is what the butterflies subtract with E = 1).
 // Result: value < a + K*m, limbs < a + 2^(W+E) + 2^W.
 template <class P, int K, int E>
 PM_DEV Fe<P> fe_sub(const Fe<P>& a, const Fe<P>& b) {
@@ -491,7 +492,8 @@ PM_DEV void fe_sqr2(const Fe<P>& a0, const Fe<P>& a1, Fe<P>& r0, Fe<P>& r1) {
 }
 
 // Cheap reduction without a Montgomery product: x (limbs < 2^32, value < 2^(W N)) -> normalised
-// limbs, same residue, value < m + m/2^16.  One-limb Barrett: q = floor(top(x) / (top(m)+1)) never
+// limbs, same residue, value < m + (q + 2) m / top(m): < m + m/2^16 for Fr (the only user; Fp's 17-bit top limb gives
+// m + m/2^5).  One-limb Barrett: q = floor(top(x) / (top(m)+1)) never
 // exceeds floor(x/m) and misses it by at most one; x - q m is formed as the low W N bits of
 // x + q (2^(W N) - m), so no borrow chain is needed.  ~4 VALU ops per limb.
 template <class P>
@@ -573,7 +575,7 @@ PM_DEV void fe_pack_raw(u32* s, const Fe<P>& a) {
     s[j] = x;
   }
 }
-// value < 2m (limbs < 2^32) -> canonical saturated limbs
+// value < 2m (limbs < 2^32 - 2^(32-W): the carry of fe_norm_full must fit) -> canonical saturated limbs
 template <class P>
 PM_DEV void fe_canon_pack(u32* s, const Fe<P>& a) {
   constexpr int N = P::N, W = P::W;

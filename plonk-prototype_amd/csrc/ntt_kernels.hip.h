@@ -154,7 +154,7 @@ PM_DEV Fr fr_pow(Fr b, unsigned long long e, Fr acc) {
   return acc;
 }
 
-// (x, y) <- (x + y, x - y + K r);  y limbs <= 2^30 - 2, y value < (K-1) r
+// (x, y) <- (x + y, x - y + K r);  y limbs <= 2^30 - 2 (the limit of fe_sub<K, 1>, reached by a sum of two products), y value < (K-1) r
 #define BFLY(K, A, B)                       \
   {                                         \
     Fr _s = fe_add<FrP>(A, B);              \
@@ -166,16 +166,16 @@ PM_DEV Fr fr_pow(Fr b, unsigned long long e, Fr acc) {
 // 8-point DIF network.  In: x[1..7] = (1, <2) products, x[0] = (<=1+, <V0) with V0 <= 24.
 // Out: x[p] = X[bitrev3(p)], every output (B < 5, V < 40).
 PM_DEV void dft8(Fr* x, const Fr& w1, const Fr& w2, const Fr& w3) {
-  BFLY(3, x[0], x[4]);  // sums (2,.), diffs (4,.)
+  BFLY(3, x[0], x[4]);  // sums (2,.), diffs (4,.); x0 and x4 carry x0's "+": (2+, <26), (4+, <27)
   BFLY(3, x[1], x[5]);
   BFLY(3, x[2], x[6]);
   BFLY(3, x[3], x[7]);
   x[5] = fe_mul<FrP>(x[5], w1);
   x[6] = fe_mul<FrP>(x[6], w2);
   x[7] = fe_mul<FrP>(x[7], w3);
-  BFLY(5, x[0], x[2]);  // x0 (4,.) x2 (5,.)
+  BFLY(5, x[0], x[2]);  // x0 (4+, <30) x2 (5+, <31)
   BFLY(5, x[1], x[3]);
-  BFLY(3, x[4], x[6]);  // x4 (5,.) x6 (7,.)
+  BFLY(3, x[4], x[6]);  // x4 (5+, <29) x6 (7+, <30)
   BFLY(3, x[5], x[7]);  // x5 (2,4) x7 (4,5)
   x[3] = fe_mul<FrP>(x[3], w2);
   x[7] = fe_mul<FrP>(x[7], w2);

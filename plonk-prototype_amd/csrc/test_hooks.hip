@@ -1,0 +1,249 @@
+// Raw-limb test hooks: the shared inline routines of fields.hip.h, ec.hip.h and ntt_kernels.hip.h, called as they are,
+// on operands given as radix-2^W limbs (no fe_unpack, no reduction) and with the result limbs returned as they come
+// (no fe_canon_pack).  One thread per case, one launch per call.  The tests (tests/test_gpu_field_bounds.py,
+// tests/test_gpu_g1_bounds.py) feed them the worst members of the operand classes the call sites document and compare
+// limb for limb with the big-integer model (oracle/fe_model.py).  What they check is the arithmetic and the bounds of
+// the routines; the code the compiler generates for a production kernel that inlines them is a different instance.
+#include <hip/hip_runtime.h>
+
+#include "context.h"
+#include "ec.hip.h"
+#include "fields.hip.h"
+#include "ntt_kernels.hip.h"
+
+namespace pm {
+
+enum RawOp {
+  RAW_ADD = 0, RAW_NORM, RAW_NORM_FULL, RAW_MUL, RAW_SQR, RAW_MUL_LIMB, RAW_MUL2, RAW_MUL3, RAW_MMA2, RAW_SQR2,
+  RAW_REDUCE_WEAK, RAW_UNPACK, RAW_CANON_PACK, RAW_POW2, RAW_SPLIT_5_6, RAW_SPLIT_1_2, RAW_ZERO_PRODUCT, RAW_ZERO_LAZY,
+  RAW_DFT8, RAW_DFT4, RAW_SUB = 32   // RAW_SUB + K: fe_sub<K, 1>
+};
+
+__host__ __device__ constexpr int raw_in(int op) {
+  return op == RAW_ADD || op == RAW_MUL || op == RAW_MUL_LIMB || op == RAW_SQR2 || op >= RAW_SUB ? 2
+         : op == RAW_MUL2                                                                         ? 4
+         : op == RAW_MUL3 || op == RAW_MMA2                                                       ? 6
+         : op == RAW_SPLIT_5_6                                                                    ? 3
+         : op == RAW_SPLIT_1_2                                                                    ? 10
+         : op == RAW_DFT8                                                                         ? 11
+         : op == RAW_DFT4                                                                         ? 5
+                                                                                                  : 1;
+}
+__host__ __device__ constexpr int raw_out(int op) {
+  return op == RAW_MUL2 || op == RAW_MMA2 || op == RAW_SQR2 ? 2 : op == RAW_MUL3 ? 3 : op == RAW_DFT8 ? 8 : op == RAW_DFT4 ? 4 : 1;
+}
+
+template <class P>
+PM_DEV Fe<P> ld_raw(const u32* p) {
+  Fe<P> r;
+#pragma unroll
+  for (int i = 0; i < P::N; ++i) r.l[i] = p[i];
+  return r;
+}
+template <class P>
+PM_DEV void st_raw(u32* p, const Fe<P>& v) {
+#pragma unroll
+  for (int i = 0; i < P::N; ++i) p[i] = v.l[i];
+}
+
+template <class P, int OP>
+__global__ void raw_op_kernel(const u32* in, u32* out, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  constexpr int N = P::N, NI = raw_in(OP), NO = raw_out(OP);
+  const u32* s = in + i * (size_t)(NI * N);
+  u32* d = out + i * (size_t)(NO * N);
+  Fe<P> x[NI], r[NO];
+#pragma unroll
+  for (int e = 0; e < NI; ++e) x[e] = ld_raw<P>(s + e * N);
+#pragma unroll
+  for (int e = 0; e < NO; ++e) r[e] = fe_zero<P>();
+  if constexpr (OP == RAW_ADD) r[0] = fe_add<P>(x[0], x[1]);
+  if constexpr (OP == RAW_NORM) r[0] = fe_norm<P>(x[0]);
+  if constexpr (OP == RAW_NORM_FULL) r[0] = fe_norm_full<P>(x[0]);
+  if constexpr (OP == RAW_MUL) r[0] = fe_mul<P>(x[0], x[1]);
+  if constexpr (OP == RAW_SQR) r[0] = fe_sqr<P>(x[0]);
+  if constexpr (OP == RAW_MUL_LIMB) r[0] = fe_mul_limb<P>(x[0], x[1].l[0]);
+  if constexpr (OP == RAW_MUL2) fe_mul2<P>(x[0], x[1], x[2], x[3], r[0], r[1]);
+  if constexpr (OP == RAW_MUL3) fe_mul3<P>(x[0], x[1], x[2], x[3], x[4], x[5], r[0], r[1], r[2]);
+  if constexpr (OP == RAW_MMA2) fe_mma2<P>(x[0], x[1], x[2], x[3], x[4], x[5], r[0], r[1]);
+  if constexpr (OP == RAW_SQR2) fe_sqr2<P>(x[0], x[1], r[0], r[1]);
+  if constexpr (OP == RAW_REDUCE_WEAK) r[0] = fe_reduce_weak<P>(x[0]);
+  if constexpr (OP == RAW_UNPACK) r[0] = fe_unpack<P>(x[0].l);          // the first NS words are the saturated limbs
+  if constexpr (OP == RAW_CANON_PACK) fe_canon_pack<P>(r[0].l, x[0]);   // NS saturated words, the rest stays zero
+  if constexpr (OP == RAW_POW2) {
+    const u32 sel = x[0].l[0];
+    r[0] = sel == 0 ? fe_pow2<P, P::W * P::N>() : sel == 1 ? fe_pow2<P, 2 * P::W * P::N - 32 * P::NS>() : fe_pow2<P, 64 * P::NS + P::W * P::N>();
+  }
+  if constexpr (OP == RAW_SPLIT_5_6) r[0] = fe_mul_split<P, 5, 6>(x[0], [&](int j, int b) { return x[1 + j].l[b]; });
+  if constexpr (OP == RAW_SPLIT_1_2) r[0] = fe_mul_split<P, 1, 2>(x[0], [&](int j, int b) { return x[1 + j].l[b]; });
+  if constexpr (OP == RAW_ZERO_PRODUCT) r[0].l[0] = fp_is_zero_product(x[0]) ? 1u : 0u;
+  if constexpr (OP == RAW_ZERO_LAZY) r[0].l[0] = fp_is_zero_lazy(x[0]) ? 1u : 0u;
+  if constexpr (OP == RAW_DFT8) {
+    dft8(x, x[8], x[9], x[10]);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) r[e] = x[e];
+  }
+  if constexpr (OP == RAW_DFT4) {
+    dft4(x[0], x[1], x[2], x[3], x[4]);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) r[e] = x[e];
+  }
+  if constexpr (OP >= RAW_SUB) r[0] = fe_sub<P, OP - RAW_SUB, 1>(x[0], x[1]);
+#pragma unroll
+  for (int e = 0; e < NO; ++e) st_raw<P>(d + e * N, r[e]);
+}
+
+// ---- group law: a point is 57 words, X | Y | ZZ | ZZZ (14 limbs each) | infinity flag
+constexpr int PT_WORDS = 57;
+enum G1Op { G1_DOUBLE_AFFINE = 0, G1_DOUBLE, G1_MADD, G1_ADD, G1_MUL_SMALL, G1_HALF_DOUBLE, G1_HALF_ADD };
+
+PM_DEV Xyzz ld_raw_point(const u32* p) {
+  Xyzz r;
+  r.x = ld_raw<FpP>(p);
+  r.y = ld_raw<FpP>(p + 14);
+  r.zz = ld_raw<FpP>(p + 28);
+  r.zzz = ld_raw<FpP>(p + 42);
+  r.inf = p[56] != 0;
+  return r;
+}
+
+template <int OP>
+__global__ void g1_raw_op_kernel(const u32* a, const u32* b, u32* out, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const Xyzz p = ld_raw_point(a + PT_WORDS * i), q = ld_raw_point(b + PT_WORDS * i);
+  Xyzz r;
+  if constexpr (OP == G1_DOUBLE_AFFINE) r = xyzz_double_affine(p.x, p.y);
+  if constexpr (OP == G1_DOUBLE) r = xyzz_double(p);
+  if constexpr (OP == G1_MADD) r = xyzz_madd(p, q.x, q.y);
+  if constexpr (OP == G1_ADD) r = xyzz_add(p, q);
+  if constexpr (OP == G1_MUL_SMALL) r = xyzz_mul_small(p, b[PT_WORDS * i]);
+  if (r.inf) r = xyzz_identity();
+  u32* d = out + PT_WORDS * i;
+  st_raw<FpP>(d, r.x);
+  st_raw<FpP>(d + 14, r.y);
+  st_raw<FpP>(d + 28, r.zz);
+  st_raw<FpP>(d + 42, r.zzz);
+  d[56] = r.inf ? 1u : 0u;
+}
+
+// one point per lane pair, as the reduction kernels hold it: the even lane X / ZZ, the odd lane Y / ZZZ
+template <int OP>
+__global__ void g1_half_op_kernel(const u32* a, const u32* b, u32* out, size_t n) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t i = t >> 1;
+  const bool isB = t & 1;
+  if (i >= n) return;   // both lanes of a pair leave together
+  auto ld = [&](const u32* p) {
+    Half h;
+    h.c0 = ld_raw<FpP>(p + (isB ? 14 : 0));
+    h.c1 = ld_raw<FpP>(p + (isB ? 42 : 28));
+    h.inf = p[56] != 0;
+    return h;
+  };
+  const Half p = ld(a + PT_WORDS * i), q = ld(b + PT_WORDS * i);
+  Half r = OP == G1_HALF_DOUBLE ? half_double(p, isB) : half_add(p, q, isB);
+  if (r.inf) r = half_identity();
+  u32* d = out + PT_WORDS * i;
+  st_raw<FpP>(d + (isB ? 14 : 0), r.c0);
+  st_raw<FpP>(d + (isB ? 42 : 28), r.c1);
+  if (!isB) d[56] = r.inf ? 1u : 0u;
+}
+
+struct FreeAll {   // the temporaries go away on every path, error returns included
+  void* p[3] = {nullptr, nullptr, nullptr};
+  ~FreeAll() {
+    for (void* q : p)
+      if (q) (void)hipFree(q);
+  }
+};
+
+template <class P>
+static bool launch_raw(int op, dim3 g, dim3 blk, hipStream_t st, const u32* in, u32* out, size_t n) {
+#define RAW_CASE(OP) \
+  case OP: hipLaunchKernelGGL((raw_op_kernel<P, OP>), g, blk, 0, st, in, out, n); return true;
+  constexpr bool FR = P::N == 9;
+  switch (op) {
+    RAW_CASE(RAW_ADD) RAW_CASE(RAW_NORM) RAW_CASE(RAW_NORM_FULL) RAW_CASE(RAW_MUL) RAW_CASE(RAW_SQR) RAW_CASE(RAW_MUL_LIMB)
+    RAW_CASE(RAW_MUL2) RAW_CASE(RAW_MUL3) RAW_CASE(RAW_MMA2) RAW_CASE(RAW_SQR2) RAW_CASE(RAW_REDUCE_WEAK) RAW_CASE(RAW_UNPACK)
+    RAW_CASE(RAW_CANON_PACK) RAW_CASE(RAW_POW2)
+    RAW_CASE(RAW_SUB + 2) RAW_CASE(RAW_SUB + 3) RAW_CASE(RAW_SUB + 5)
+  }
+  if constexpr (FR) {
+    switch (op) { RAW_CASE(RAW_SPLIT_5_6) RAW_CASE(RAW_SPLIT_1_2) RAW_CASE(RAW_DFT8) RAW_CASE(RAW_DFT4) RAW_CASE(RAW_SUB + 9) }
+  } else {
+    switch (op) { RAW_CASE(RAW_ZERO_PRODUCT) RAW_CASE(RAW_ZERO_LAZY) RAW_CASE(RAW_SUB + 6) RAW_CASE(RAW_SUB + 8) RAW_CASE(RAW_SUB + 11) }
+  }
+#undef RAW_CASE
+  return false;
+}
+
+}  // namespace pm
+
+using namespace pm;
+
+extern "C" int pm_test_field_raw_op(pm_ctx* ctx, int field, int op, const uint32_t* in, uint32_t* out, size_t n) {
+  if (!ctx || !in || !out || field < 0 || field > 1 || op < 0 || op > RAW_SUB + 11) return PM_ERR_BAD_ARG;
+  const bool fr = field == 0;
+  {   // the (field, op) pairs that exist: every fe_sub<K, 1> the library instantiates, the split product and the butterflies for Fr, the zero tests for Fp
+    const int k = op - RAW_SUB;
+    const bool sub_ok = k == 2 || k == 3 || k == 5 || (fr ? k == 9 : (k == 6 || k == 8 || k == 11));
+    const bool fr_only = op == RAW_SPLIT_5_6 || op == RAW_SPLIT_1_2 || op == RAW_DFT8 || op == RAW_DFT4;
+    const bool fp_only = op == RAW_ZERO_PRODUCT || op == RAW_ZERO_LAZY;
+    if (op >= RAW_SUB ? !sub_ok : (op > RAW_DFT4 || (fr_only && !fr) || (fp_only && fr))) return PM_ERR_BAD_ARG;
+  }
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (n == 0) return PM_OK;
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t limbs = fr ? FrP::N : FpP::N;
+  const size_t in_bytes = n * raw_in(op) * limbs * 4, out_bytes = n * raw_out(op) * limbs * 4;
+  FreeAll tmp;
+  PM_HIP(ctx, hipMalloc(&tmp.p[0], in_bytes));
+  PM_HIP(ctx, hipMalloc(&tmp.p[1], out_bytes));
+  PM_HIP(ctx, hipMemcpyAsync(tmp.p[0], in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
+  dim3 g((unsigned)((n + 63) / 64)), blk(64);
+  const u32* din = (const u32*)tmp.p[0];
+  u32* dout = (u32*)tmp.p[1];
+  const bool ok = fr ? launch_raw<FrP>(op, g, blk, ctx->stream, din, dout, n) : launch_raw<FpP>(op, g, blk, ctx->stream, din, dout, n);
+  if (!ok) return set_err(ctx, PM_ERR_BAD_ARG, "pm_test_field_raw_op: no such (field, op)");
+  PM_HIP(ctx, hipGetLastError());
+  PM_HIP(ctx, hipMemcpyAsync(out, tmp.p[1], out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return PM_OK;
+}
+
+extern "C" int pm_test_g1_raw_op(pm_ctx* ctx, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t n) {
+  if (!ctx || !a || !out || op < G1_DOUBLE_AFFINE || op > G1_HALF_ADD) return PM_ERR_BAD_ARG;
+  const bool unary = op == G1_DOUBLE_AFFINE || op == G1_DOUBLE || op == G1_HALF_DOUBLE;
+  if (!b) {
+    if (!unary) return PM_ERR_BAD_ARG;
+    b = a;   // the doublings ignore b
+  }
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (n == 0) return PM_OK;
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t bytes = n * PT_WORDS * 4;
+  FreeAll tmp;
+  for (int i = 0; i < 3; ++i) PM_HIP(ctx, hipMalloc(&tmp.p[i], bytes));
+  PM_HIP(ctx, hipMemcpyAsync(tmp.p[0], a, bytes, hipMemcpyHostToDevice, ctx->stream));
+  PM_HIP(ctx, hipMemcpyAsync(tmp.p[1], b, bytes, hipMemcpyHostToDevice, ctx->stream));
+  const u32 *da = (const u32*)tmp.p[0], *db = (const u32*)tmp.p[1];
+  u32* dc = (u32*)tmp.p[2];
+  const bool half = op >= G1_HALF_DOUBLE;
+  const size_t threads = half ? 2 * n : n;
+  dim3 g((unsigned)((threads + 63) / 64)), blk(64);
+  switch (op) {
+    case G1_DOUBLE_AFFINE: hipLaunchKernelGGL((g1_raw_op_kernel<G1_DOUBLE_AFFINE>), g, blk, 0, ctx->stream, da, db, dc, n); break;
+    case G1_DOUBLE: hipLaunchKernelGGL((g1_raw_op_kernel<G1_DOUBLE>), g, blk, 0, ctx->stream, da, db, dc, n); break;
+    case G1_MADD: hipLaunchKernelGGL((g1_raw_op_kernel<G1_MADD>), g, blk, 0, ctx->stream, da, db, dc, n); break;
+    case G1_ADD: hipLaunchKernelGGL((g1_raw_op_kernel<G1_ADD>), g, blk, 0, ctx->stream, da, db, dc, n); break;
+    case G1_MUL_SMALL: hipLaunchKernelGGL((g1_raw_op_kernel<G1_MUL_SMALL>), g, blk, 0, ctx->stream, da, db, dc, n); break;
+    case G1_HALF_DOUBLE: hipLaunchKernelGGL((g1_half_op_kernel<G1_HALF_DOUBLE>), g, blk, 0, ctx->stream, da, db, dc, n); break;
+    case G1_HALF_ADD: hipLaunchKernelGGL((g1_half_op_kernel<G1_HALF_ADD>), g, blk, 0, ctx->stream, da, db, dc, n); break;
+  }
+  PM_HIP(ctx, hipGetLastError());
+  PM_HIP(ctx, hipMemcpyAsync(out, tmp.p[2], bytes, hipMemcpyDeviceToHost, ctx->stream));
+  PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return PM_OK;
+}

@@ -283,6 +283,24 @@ class Context:
         self._check(self._lib.pm_test_field_op(self._h, op, _p(a), _p(b), _p(out), a.size // limbs))
         return out
 
+    def field_raw_op(self, field: int, op: int, x, n_out: int) -> np.ndarray:
+        """``pm_test_field_raw_op``: x is [cases, elements in, limbs] uint32 raw limbs; returns [cases, n_out, limbs]."""
+        x = np.ascontiguousarray(x, dtype=np.uint32)
+        out = np.zeros((x.shape[0], n_out, x.shape[2]), np.uint32)
+        self._check(self._lib.pm_test_field_raw_op(self._h, field, op, x.ctypes.data_as(_lib.u32p),
+                                                   out.ctypes.data_as(_lib.u32p), x.shape[0]))
+        return out
+
+    def g1_raw_op(self, op: int, a, b=None) -> np.ndarray:
+        """``pm_test_g1_raw_op``: a, b are [cases, 57] uint32 (X, Y, ZZ, ZZZ raw limbs, infinity flag)."""
+        a = np.ascontiguousarray(a, dtype=np.uint32)
+        out = np.zeros_like(a)
+        pb = None if b is None else np.ascontiguousarray(b, dtype=np.uint32)
+        self._check(self._lib.pm_test_g1_raw_op(self._h, op, a.ctypes.data_as(_lib.u32p),
+                                                None if pb is None else pb.ctypes.data_as(_lib.u32p),
+                                                out.ctypes.data_as(_lib.u32p), a.shape[0]))
+        return out
+
 
 class DeviceVector:
     """Canonical Fr vector in device memory (``pm_dev_alloc``): the currency of the polynomial

@@ -8,63 +8,11 @@ import random
 
 import pytest
 
-R_MOD = 0x73eda753299d7d483339d80809a1d80553bda402fffe5bfeffffffff00000001
-W, N = 29, 9
-MASK = (1 << W) - 1
-M = [(R_MOD >> (W * i)) & MASK for i in range(N)]
-RADIX = 1 << (W * N)            # the device Montgomery radix R = 2^261
+from oracle.fe_model import MASK, M, N, R_MOD, RADIX, W, limbs, mul_split, rows_of, value   # noqa: F401  (the model lives there)
+
 BX = 6                          # data limbs < BX * 2^W: the bound fe_mul_split states (the kernels stay below 5)
 SPLITS = [(5, 6), (1, 2)]       # (G, D): step twiddles, w4
 MACS = {(5, 6): 129, (1, 2): 97}
-
-
-def limbs(v):
-    return [(v >> (W * i)) & MASK for i in range(N)]
-
-
-def value(l):
-    return sum(x << (W * i) for i, x in enumerate(l))
-
-
-def rows_of(w_mont, G, D):
-    """row_j = w * 2^(W (jG + D - N)) mod r, canonical limbs (what step4_tw_kernel stores)"""
-    groups = (N + G - 1) // G
-    out = []
-    for j in range(groups):
-        e = W * (j * G + D - N)
-        f = pow(2, e, R_MOD) if e >= 0 else pow(pow(2, -e, R_MOD), -1, R_MOD)
-        out.append(limbs(w_mont * f % R_MOD))
-    return out
-
-
-def mul_split(x, rows, G, D):
-    """The device routine, limb for limb.  Returns (result limbs, largest column value seen, products issued)."""
-    assert M[0] == 1
-    acc, peak, macs = 0, 0, 0
-    q, r = [0] * D, [0] * N
-    for k in range(D + N - 1):
-        for i in range(N):
-            b = k - i % G
-            if 0 <= b < N:
-                acc += x[i] * rows[i // G][b]
-                macs += 1
-                peak = max(peak, acc)
-        for i in range(D):
-            l = k - i
-            if 1 <= l < N:
-                acc += q[i] * M[l]
-                macs += 1
-                peak = max(peak, acc)
-        if k < D:
-            q[k] = (-acc) & MASK
-            assert (acc + q[k]) >> W == (acc + MASK) >> W     # the carry does not wait for q
-            acc += MASK
-            peak = max(peak, acc)
-        else:
-            r[k - D] = acc & MASK
-        acc >>= W
-    r[N - 1] = acc
-    return r, peak, macs
 
 
 def check(x, rows, G, D):
