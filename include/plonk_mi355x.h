@@ -503,6 +503,53 @@ int pm_plonk_prove_batch_zk(pm_ctx* ctx, pm_prover_key* key, pm_plonk_batch* ws,
                             const void* d_witnesses, const uint64_t* const* pi_positions, const uint64_t* const* pi_values,
                             const size_t* n_pi, uint32_t flags, const uint64_t (*blinders)[PM_PLONK_ZK_BLINDERS][4],
                             pm_plonk_proof* out);
+/* ---- Witness check -------------------------------------------------------------------------
+ * The provers accept any witness: with one wrong wire value the quotient no longer divides by Z_H and the call still
+ * returns PM_OK and a well-formed proof that no verifier accepts.  pm_plonk_check_witness evaluates every identity of
+ * pm_plonk_quotient_args on the rows of H instead of the 4n coset, one kernel, and names the rows that fail and why
+ * (dusk-plonk: Composer::check_circuit_satisfied).  Row i, with a_next, b_next, d_next from row (i + 1) mod n and the
+ * selectors at row i, gets the mask
+ *   PM_PLONK_FAIL_ARITH       q_arith (q_m a b + q_l a + q_r b + q_o c + q_4 d + q_c) + PI_i != 0
+ *   PM_PLONK_FAIL_RANGE       q_range != 0 and one of the four delta(.) summands of R is != 0
+ *   PM_PLONK_FAIL_LOGIC       q_logic != 0 and one of the five summands of L is != 0
+ *   PM_PLONK_FAIL_FIXED_BASE  q_fixed_group_add != 0 and one of the four summands of F is != 0
+ *   PM_PLONK_FAIL_VAR_BASE    q_variable_group_add != 0 and one of the three summands of V is != 0
+ *   PM_PLONK_FAIL_COPY        for some wire j, w[j n + i] != w[sigma_index[j n + i]]
+ * The summands are what the separation challenge's powers join in R, L, F, V above: each is tested on its own, so the
+ * check takes no challenge and is exact ("the gate sum vanishes for every choice of the separation challenges").
+ * pm_plonk_key_enable_check (opt-in, idempotent; needs neither a commit key nor pm_plonk_key_commit) builds what the
+ * check reads: the non-trivial selectors on H (one batched forward transform of the key's coefficient forms), the 4n
+ * permutation indices as 32-bit words, and scratch of its own (dense public inputs, row masks, counters; grown to the
+ * largest batch seen) -- a check never touches the per-proof workspace and has its own busy flag.  The key keeps only
+ * sigma's field values, so the caller passes sigma_index again; it is verified against the key (the sigma values are
+ * recomputed from it and compared on the device): PM_ERR_BAD_ARG when it is another permutation.  added_bytes (may be
+ * NULL) receives the device bytes the state holds after the call; pm_plonk_key_free frees it.
+ * pm_plonk_check_witness takes the witness and public inputs of pm_plonk_prove (canonical Montgomery limbs) and returns
+ * PM_OK whenever the check ran, satisfied or not: the report carries the result, every field of it deterministic.
+ * row_mask_out (host, n bytes, may be NULL) receives the mask of every row.  pm_plonk_check_witness_batch takes the
+ * witnesses and public inputs of pm_plonk_prove_batch (1 <= batch <= PM_PLONK_MAX_BATCH); reports[b] and row b of
+ * row_masks_out (batch x n bytes, may be NULL) equal the single call on witness b.  Errors: key not enabled, NULL
+ * arguments, a batch out of range: PM_ERR_BAD_ARG; a position >= n: PM_ERR_LENGTH; a check already running on the key:
+ * PM_ERR_BUSY.  Single GPU only. */
+#define PM_PLONK_FAIL_ARITH 1u
+#define PM_PLONK_FAIL_RANGE 2u
+#define PM_PLONK_FAIL_LOGIC 4u
+#define PM_PLONK_FAIL_FIXED_BASE 8u
+#define PM_PLONK_FAIL_VAR_BASE 16u
+#define PM_PLONK_FAIL_COPY 32u
+typedef struct pm_plonk_witness_report {
+  uint64_t failed_rows;   /* rows with a non-zero mask */
+  uint64_t first_row;     /* the lowest failing row; UINT64_MAX when no row fails */
+  uint32_t first_mask;    /* that row's mask; 0 when no row fails */
+  uint32_t reserved;      /* 0 */
+  uint64_t count[6];      /* count[k]: rows with bit k set */
+} pm_plonk_witness_report;
+int pm_plonk_key_enable_check(pm_ctx* ctx, pm_prover_key* key, const int64_t* sigma_index, size_t* added_bytes);
+int pm_plonk_check_witness(pm_ctx* ctx, pm_prover_key* key, const void* d_witness, const uint64_t* pi_positions,
+                           const uint64_t* pi_values, size_t n_pi, pm_plonk_witness_report* out, uint8_t* row_mask_out);
+int pm_plonk_check_witness_batch(pm_ctx* ctx, pm_prover_key* key, uint32_t batch, const void* d_witnesses,
+                                 const uint64_t* const* pi_positions, const uint64_t* const* pi_values, const size_t* n_pi,
+                                 pm_plonk_witness_report* reports, uint8_t* row_masks_out);
 /* Proof::to_bytes: 11 x 48-byte compressed G1, then the 16 scalars of ProofEvaluations::to_bytes. */
 int pm_plonk_proof_to_bytes(const pm_plonk_proof* proof, uint8_t out[PM_PLONK_PROOF_BYTES]);
 /* ---- The prover with coefficient-range ownership end to end (SURVEY.md section 8e row 3 + 8f N5; configs[4]) ----------

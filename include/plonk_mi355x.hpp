@@ -452,6 +452,30 @@ class ProverKey {
                                   bind_public_inputs ? 0u : PM_PLONK_UPSTREAM_TRANSCRIPT, bl, &raw));
     return from_raw(raw);
   }
+  // Witness check (pm_plonk_key_enable_check): the selectors on H, the permutation as wire positions (sigma_index: the one
+  // the key was built from) and the check's own scratch, once (idempotent); returns the device bytes that state holds.
+  size_t enable_check(const std::vector<int64_t>& sigma_index) {
+    if (sigma_index.size() != 4 * n_) throw Error(PM_ERR_LENGTH, "sigma_index must have 4n entries");
+    size_t added = 0;
+    ctx_->check(pm_plonk_key_enable_check(ctx_->get(), key_, sigma_index.data(), &added));
+    return added;
+  }
+  // Does the witness satisfy the circuit (pm_plonk_check_witness; enable_check() first)?  The report names the lowest failing
+  // row and its PM_PLONK_FAIL_* mask; row_masks (optional) receives the mask of every row.
+  pm_plonk_witness_report check_witness(const DevicePolynomial& witness, const std::vector<PublicInput>& public_inputs = {},
+                                        std::vector<uint8_t>* row_masks = nullptr) const {
+    if (witness.len() != 4 * n_) throw Error(PM_ERR_LENGTH, "the witness must hold 4n wire values");
+    std::vector<uint64_t> pos, val;
+    for (const PublicInput& pi : public_inputs) {
+      pos.push_back(pi.position);
+      val.insert(val.end(), pi.value.begin(), pi.value.end());
+    }
+    if (row_masks) row_masks->assign(n_, 0);
+    pm_plonk_witness_report report;
+    ctx_->check(pm_plonk_check_witness(ctx_->get(), key_, witness.data(), pos.data(), val.data(), pos.size(), &report,
+                                       row_masks ? row_masks->data() : nullptr));
+    return report;
+  }
   // A workspace for prove_batch of up to max_batch (<= PM_PLONK_MAX_BATCH) proofs: about 42 n x 32 bytes per proof
   BatchWorkspace batch(uint32_t max_batch) const { return BatchWorkspace(*ctx_, key_, max_batch); }
   // B proofs in one call: witnesses holds B x [a | b | c | d] (B x 4n, proof-major), public_inputs[b] the inputs of proof b

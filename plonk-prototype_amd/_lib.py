@@ -38,6 +38,12 @@ class PlonkProof(C.Structure):
                 ("challenges", (C.c_uint64 * 4) * 10)]
 
 
+class WitnessReport(C.Structure):
+    """``pm_plonk_witness_report``"""
+    _fields_ = [("failed_rows", C.c_uint64), ("first_row", C.c_uint64), ("first_mask", C.c_uint32),
+                ("reserved", C.c_uint32), ("count", C.c_uint64 * 6)]
+
+
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, u64p, C.c_uint32)
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, u64p, u64p)
 COMM_MSG_WORDS = 289
@@ -148,6 +154,12 @@ SIGNATURES = {
     "pm_plonk_key_commit_dist": (C.c_int, [C.c_void_p, C.POINTER(Dist), C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p]),
     "pm_plonk_prove_dist": (C.c_int, [C.c_void_p, C.POINTER(Dist), C.c_void_p, C.c_void_p, C.c_void_p, u64p, u64p, C.c_size_t,
                                       C.c_uint32, C.POINTER(PlonkProof)]),
+    "pm_plonk_key_enable_check": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_size_t)]),
+    "pm_plonk_check_witness": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, u64p, u64p, C.c_size_t,
+                                         C.POINTER(WitnessReport), C.POINTER(C.c_uint8)]),
+    "pm_plonk_check_witness_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(u64p),
+                                               C.POINTER(u64p), C.POINTER(C.c_size_t), C.POINTER(WitnessReport),
+                                               C.POINTER(C.c_uint8)]),
     "pm_plonk_proof_to_bytes": (C.c_int, [C.POINTER(PlonkProof), C.POINTER(C.c_uint8)]),
     "pm_plonk_batch_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
     "pm_plonk_batch_free": (None, [C.c_void_p, C.c_void_p]),
@@ -205,6 +217,11 @@ G1_BAD_REASONS = {1: "malformed encoding or non-canonical coordinate", 2: "not o
 
 PLONK_ZK_BLINDERS = 17        # pm_plonk_prove_zk: blinding scalars per proof
 PLONK_ZK_EXTRA_BASES = 10     # ... and commit-key points it needs beyond n
+
+# pm_plonk_check_witness: bit k of a row's mask, and count[k] of the report
+PLONK_FAIL_ARITH, PLONK_FAIL_RANGE, PLONK_FAIL_LOGIC = 1, 2, 4
+PLONK_FAIL_FIXED_BASE, PLONK_FAIL_VAR_BASE, PLONK_FAIL_COPY = 8, 16, 32
+PLONK_FAIL_NAMES = ("arith", "range", "logic", "fixed_base", "var_base", "copy")
 
 NTT_INVERSE = 1
 NTT_COSET = 2

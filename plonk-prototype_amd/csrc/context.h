@@ -266,6 +266,23 @@ int zk_shift_batch(pm_ctx* ctx, const ZkShiftBatchArgs& a, const void* d_w8, uin
 // pieces of proof b go to d_t + 4 b stride with its blinders b_14..b_16 from the table
 int zk_combine_batch(pm_ctx* ctx, const void* d_blinders, const void* d_ab, const void* d_w8, uint32_t batch, size_t n,
                      size_t stride, const uint64_t inv2[4], const uint64_t inv2s[4], void* d_t, hipStream_t st);
+// Witness check (pm_plonk_check_witness; plonk_rounds.hip): every gate identity and the copy
+// constraints on the rows of H.  blockIdx.y = the witness; one mask byte per row and eight counters per witness.
+// Counters of witness b of `batch` (u64): [7 b .. 7 b + 5] rows with bit 0..5 set, [7 b + 6] failing rows, and [7 batch + b]
+// the minimum over failing rows of row * 64 + mask -- the launcher zeroes the first 7 batch words and sets the rest to ~0.
+constexpr uint32_t CHECK_COUNTERS = 8;
+struct WitnessCheckArgs {
+  const void* wires;               // [batch][a | b | c | d][n]
+  const void* sel[PM_PLONK_SELECTORS];   // values on H; nullptr = identically zero (q_arith: or identically one)
+  bool arith_is_one;
+  const void* pi;                  // [batch][n] dense public inputs
+  const uint32_t* sigma;           // [4 n] wire positions j' n + i'
+  uint8_t* masks;                  // [batch][n]
+  unsigned long long* counters;    // CHECK_COUNTERS x batch words, initialised by the launcher
+};
+int check_witness_rows(pm_ctx* ctx, const WitnessCheckArgs& a, size_t n, uint32_t batch, hipStream_t st);
+// *d_flag |= 1 when the n elements at d_a and d_b differ anywhere (d_flag: one zeroed word)
+int vec_differs(pm_ctx* ctx, const void* d_a, const void* d_b, size_t n, uint32_t* d_flag, hipStream_t st);
 // poly_evaluate_groups with a length per group
 int poly_evaluate_groups_n(pm_ctx* ctx, uint32_t groups, const uint32_t* k, const void* const* const* polys,
                            const uint64_t* const* points, uint64_t* const* outs, const size_t* ns);

@@ -813,6 +813,198 @@ int zk_shift_batch(pm_ctx* ctx, const ZkShiftBatchArgs& a, const void* d_w8, uin
   return PM_OK;
 }
 
+// ------------------------------------------------------------------ witness check
+// pm_plonk_check_witness: the identities of quotient_kernel on the rows of H -- "next" is row
+// i + 1 (the last row's: row 0), the selectors are their values on H -- with every summand a separation challenge joins
+// tested on its own, plus the copy constraints as plain equality of the wire values a cycle links.  One mask byte per row.
+struct CheckPtrs {
+  const u32x4* w;            // [batch][4][n]
+  const u32x4 *q_m, *q_l, *q_r, *q_o, *q_4, *q_c;     // nullptr = identically zero
+  const u32x4* q_arith;      // nullptr = identically zero, or identically one (arith_is_one)
+  const u32x4 *q_range, *q_logic, *q_fixed, *q_var;
+  const u32x4* pi;           // [batch][n]
+  const u32* sigma;          // [4 n]
+  unsigned char* masks;      // [batch][n]
+  unsigned long long* counters;
+  u32 arith_is_one;
+};
+// Is the value zero?  What wadd / wsub / wmul return is below 2 r, not below r: a zero may arrive as r, so the test is made on
+// the canonical limbs.
+PM_DEV bool wnonzero(const Fr& v) {
+  u32 s[8];
+  fe_canon_pack<FrP>(s, v);
+  return (s[0] | s[1] | s[2] | s[3] | s[4] | s[5] | s[6] | s[7]) != 0;
+}
+// canonical elements in memory, compared or tested as they are stored
+PM_DEV bool raw_nonzero(const u32x4* p, size_t i) {
+  const u32x4 lo = p[2 * i], hi = p[2 * i + 1];
+  return (lo.x | lo.y | lo.z | lo.w | hi.x | hi.y | hi.z | hi.w) != 0;
+}
+PM_DEV bool raw_differ(const u32x4* p, size_t i, size_t j) {
+  const u32x4 a0 = p[2 * i], a1 = p[2 * i + 1], b0 = p[2 * j], b1 = p[2 * j + 1];
+  return ((a0.x ^ b0.x) | (a0.y ^ b0.y) | (a0.z ^ b0.z) | (a0.w ^ b0.w) | (a1.x ^ b1.x) | (a1.y ^ b1.y) | (a1.z ^ b1.z) |
+          (a1.w ^ b1.w)) != 0;
+}
+PM_DEV Fr ld_dev_or_zero(const u32x4* p, size_t i) { return p ? to_dev(ld_canon(p, i)) : fe_zero<FrP>(); }
+
+// One thread per row, grid-stride by whole waves (the loop is wave-uniform: the ballots below see all 64 lanes), blockIdx.y =
+// the witness.  A widget is evaluated on the rows whose selector is not zero only.  On the way out a wave that saw a failure
+// adds its per-reason popcounts and its lowest failing row to the witness's counters: one atomic per wave and counter, none
+// at all for a wave of satisfied rows.
+template <bool WIDGETS>
+__global__ void __launch_bounds__(256) check_witness_kernel(const CheckPtrs p, const WidgetConsts wc, size_t n) {
+  const u32 proof = blockIdx.y, lane = threadIdx.x & 63;
+  const u32x4* const w = p.w + 2 * (size_t)proof * 4 * n;
+  const u32x4* const pi = p.pi + 2 * (size_t)proof * n;
+  unsigned char* const masks = p.masks + (size_t)proof * n;
+  unsigned long long* const ctr = p.counters + 7 * (size_t)proof;
+  unsigned long long* const first = p.counters + 7 * (size_t)gridDim.y + proof;
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i0 = (size_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); i0 < n; i0 += stride) {
+    const size_t i = i0 + lane;
+    u32 m = 0;
+    if (i < n) {
+      const size_t inext = i + 1 < n ? i + 1 : 0;
+      const Fr a = to_dev(ld_canon(w, i)), b = to_dev(ld_canon(w, n + i)), c = to_dev(ld_canon(w, 2 * n + i)),
+               d = to_dev(ld_canon(w, 3 * n + i));
+      {
+        // arithmetic identity, device form throughout
+        Fr g = ld_dev_or_zero(p.q_c, i);
+        if (p.q_m) g = wadd(g, wmul(to_dev(ld_canon(p.q_m, i)), wmul(a, b)));
+        if (p.q_l) g = wadd(g, wmul(to_dev(ld_canon(p.q_l, i)), a));
+        if (p.q_r) g = wadd(g, wmul(to_dev(ld_canon(p.q_r, i)), b));
+        if (p.q_o) g = wadd(g, wmul(to_dev(ld_canon(p.q_o, i)), c));
+        if (p.q_4) g = wadd(g, wmul(to_dev(ld_canon(p.q_4, i)), d));
+        if (!p.arith_is_one) g = wmul(g, ld_dev_or_zero(p.q_arith, i));
+        g = wadd(g, to_dev(ld_canon(pi, i)));
+        if (wnonzero(g)) m |= PM_PLONK_FAIL_ARITH;
+      }
+      if (WIDGETS) {
+        const Fr an = to_dev(ld_canon(w, inext)), bn = to_dev(ld_canon(w, n + inext)), dn = to_dev(ld_canon(w, 3 * n + inext));
+        if (p.q_range && raw_nonzero(p.q_range, i)) {
+          bool f = wnonzero(wdelta(wsub(c, wmul4(d)), wc));
+          f |= wnonzero(wdelta(wsub(b, wmul4(c)), wc));
+          f |= wnonzero(wdelta(wsub(a, wmul4(b)), wc));
+          f |= wnonzero(wdelta(wsub(dn, wmul4(a)), wc));
+          if (f) m |= PM_PLONK_FAIL_RANGE;
+        }
+        if (p.q_logic && raw_nonzero(p.q_logic, i)) {
+          const Fr qa = wsub(an, wmul4(a)), qb = wsub(bn, wmul4(b)), qd = wsub(dn, wmul4(d));
+          const Fr qc = ld_dev_or_zero(p.q_c, i);
+          bool f = wnonzero(wdelta(qa, wc));
+          f |= wnonzero(wdelta(qb, wc));
+          f |= wnonzero(wdelta(qd, wc));
+          f |= wnonzero(wsub(c, wmul(qa, qb)));
+          // delta_xor_and(qa, qb, w = c, qd, q_c)
+          const Fr s = wadd(qa, qb);
+          Fr in = wadd(wsub(wmul4(c), wmul2(wmul9(s))), fr_limbs(wc.c81));                         // 4w - 18(a+b) + 81
+          in = wadd(wmul(c, in), wmul2(wmul9(wadd(wsqr(qa), wsqr(qb)))));                          // w(..) + 18(a^2+b^2)
+          in = wadd(wsub(in, wmul(s, fr_limbs(wc.c81))), fr_limbs(wc.c83));                        // - 81(a+b) + 83
+          const Fr ff = wmul(c, in);
+          const Fr e = wsub(wmul3(wadd(s, qd)), wadd(ff, ff));                                    // 3(a+b+c) - 2f
+          const Fr bb = wmul(qc, wsub(wmul9(qd), wmul3(s)));                                      // q_c (9c - 3(a+b))
+          f |= wnonzero(wadd(bb, e));
+          if (f) m |= PM_PLONK_FAIL_LOGIC;
+        }
+        if (p.q_fixed && raw_nonzero(p.q_fixed, i)) {
+          const Fr xb = ld_dev_or_zero(p.q_l, i), yb = ld_dev_or_zero(p.q_r, i), xyb = ld_dev_or_zero(p.q_c, i);
+          const Fr one = fr_limbs(wc.c1);
+          const Fr bit = wsub(dn, wadd(d, d));
+          bool f = wnonzero(wmul(wmul(bit, wsub(bit, one)), wadd(bit, one)));                     // bit (bit-1)(bit+1)
+          const Fr ya = wadd(wmul(wsqr(bit), wsub(yb, one)), one);
+          const Fr xa = wmul(xb, bit);
+          f |= wnonzero(wsub(wmul(bit, xyb), c));
+          const Fr dxy = wmul(wmul(wmul(c, a), b), fr_limbs(wc.edwards_d));
+          f |= wnonzero(wsub(wadd(an, wmul(an, dxy)), wadd(wmul(a, ya), wmul(b, xa))));
+          f |= wnonzero(wsub(wsub(bn, wmul(bn, dxy)), wadd(wmul(b, ya), wmul(a, xa))));
+          if (f) m |= PM_PLONK_FAIL_FIXED_BASE;
+        }
+        if (p.q_var && raw_nonzero(p.q_var, i)) {
+          const Fr y1x2 = wmul(b, c), y1y2 = wmul(b, d), x1x2 = wmul(a, c);
+          bool f = wnonzero(wsub(wmul(a, d), dn));                                                // x1 y2 - x1y2
+          const Fr dd = wmul(wmul(dn, y1x2), fr_limbs(wc.edwards_d));
+          f |= wnonzero(wsub(wadd(dn, y1x2), wadd(an, wmul(an, dd))));
+          f |= wnonzero(wsub(wadd(y1y2, x1x2), wsub(bn, wmul(bn, dd))));
+          if (f) m |= PM_PLONK_FAIL_VAR_BASE;
+        }
+      }
+      // copy constraints: the witness is canonical, so equal values are equal words
+      bool cp = false;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) cp |= raw_differ(w, (size_t)j * n + i, p.sigma[(size_t)j * n + i]);
+      if (cp) m |= PM_PLONK_FAIL_COPY;
+      masks[i] = (unsigned char)m;
+    }
+    const unsigned long long failing = __ballot(m != 0);
+    if (failing) {   // wave-uniform
+#pragma unroll
+      for (u32 k = 0; k < 6; ++k) {
+        const u32 cnt = (u32)__popcll(__ballot((m >> k) & 1));
+        if (lane == 0 && cnt) atomicAdd(ctr + k, (unsigned long long)cnt);
+      }
+      // rows rise with the lane: the wave's lowest failing row sits in the lowest failing lane
+      if (lane == (u32)__ffsll((long long)failing) - 1) {
+        atomicAdd(ctr + 6, (unsigned long long)__popcll(failing));
+        atomicMin(first, (unsigned long long)i * 64 + m);
+      }
+    }
+  }
+}
+
+int check_witness_rows(pm_ctx* ctx, const WitnessCheckArgs& a, size_t n, uint32_t batch, hipStream_t st) {
+  if (!ctx || !a.wires || !a.pi || !a.sigma || !a.masks || !a.counters || batch == 0 || batch > PM_PLONK_MAX_BATCH)
+    return PM_ERR_BAD_ARG;
+  if (n < 4 || (n & (n - 1)) || 4 * n > ((size_t)1 << 32)) return PM_ERR_LENGTH;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  CheckPtrs p;
+  p.w = (const u32x4*)a.wires;
+  const u32x4* sel[PM_PLONK_SELECTORS];
+  for (int s_ = 0; s_ < PM_PLONK_SELECTORS; ++s_) sel[s_] = (const u32x4*)a.sel[s_];
+  p.q_m = sel[0], p.q_l = sel[1], p.q_r = sel[2], p.q_o = sel[3], p.q_c = sel[4], p.q_4 = sel[5];   // PM_PLONK_SELECTORS order
+  p.q_arith = sel[6], p.q_range = sel[7], p.q_logic = sel[8], p.q_fixed = sel[9], p.q_var = sel[10];
+  p.pi = (const u32x4*)a.pi;
+  p.sigma = a.sigma;
+  p.masks = a.masks;
+  p.counters = a.counters;
+  p.arith_is_one = a.arith_is_one;
+  const bool widgets = p.q_range || p.q_logic || p.q_fixed || p.q_var;
+  WidgetConsts wc;
+  pm_plonk_quotient_args no_challenges;
+  memset(&no_challenges, 0, sizeof no_challenges);
+  fill_widget_consts(wc, &no_challenges, widgets);   // the small constants and d; the check takes no separation challenge
+  if (!st) st = ctx->stream;
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  PM_HIP(ctx, hipMemsetAsync(a.counters, 0, 7 * (size_t)batch * 8, st));
+  PM_HIP(ctx, hipMemsetAsync(a.counters + 7 * (size_t)batch, 0xff, (size_t)batch * 8, st));
+  ProfScope prof(ctx, st, "plonk_check_witness");
+  const dim3 grid(grid_for(ctx, n), batch);
+  if (widgets) hipLaunchKernelGGL(check_witness_kernel<true>, grid, dim3(256), 0, st, p, wc, n);
+  else hipLaunchKernelGGL(check_witness_kernel<false>, grid, dim3(256), 0, st, p, wc, n);
+  PM_HIP(ctx, hipGetLastError());
+  return PM_OK;
+}
+
+__global__ void __launch_bounds__(256) vec_differs_kernel(const u32x4* a, const u32x4* b, size_t vecs, u32* flag) {
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  bool d = false;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < vecs; i += stride) {
+    const u32x4 x = a[i], y = b[i];
+    d |= ((x.x ^ y.x) | (x.y ^ y.y) | (x.z ^ y.z) | (x.w ^ y.w)) != 0;
+  }
+  if (__ballot(d) && (threadIdx.x & 63) == 0) atomicOr(flag, 1u);
+}
+int vec_differs(pm_ctx* ctx, const void* d_a, const void* d_b, size_t n, uint32_t* d_flag, hipStream_t st) {
+  if (!ctx || !d_a || !d_b || !d_flag) return PM_ERR_BAD_ARG;
+  if (n == 0) return PM_OK;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (!st) st = ctx->stream;
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  hipLaunchKernelGGL(vec_differs_kernel, dim3(grid_for(ctx, 2 * n)), dim3(256), 0, st, (const u32x4*)d_a, (const u32x4*)d_b, 2 * n,
+                     d_flag);
+  PM_HIP(ctx, hipGetLastError());
+  return PM_OK;
+}
+
 }  // namespace pm
 
 using namespace pm;

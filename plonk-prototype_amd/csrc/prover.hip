@@ -39,6 +39,12 @@ struct ZkState {
        *wit = nullptr;
 };
 
+// Witness check (pm_plonk_key_enable_check): prover_check.hip.h
+struct CheckState;
+namespace {
+void check_state_free(pm_ctx* ctx, CheckState* cs);
+}
+
 struct pm_prover_key {
   size_t n = 0;
   uint32_t log_n = 0;
@@ -63,6 +69,7 @@ struct pm_prover_key {
   const pm_bases* lagrange = nullptr;
   const pm_bases* lagrange_ck = nullptr;
   ZkState* zk = nullptr;               // pm_plonk_key_enable_zk
+  CheckState* check = nullptr;         // pm_plonk_key_enable_check
 };
 
 // side stream <- everything submitted on the context's stream so far / the reverse
@@ -113,6 +120,7 @@ extern "C" void pm_plonk_key_free(pm_ctx* ctx, pm_prover_key* pk) {
       if (p && ctx) (void)pm_dev_free(ctx, p);
     delete zs;
   }
+  check_state_free(ctx, pk->check);
   delete pk;
 }
 
@@ -954,4 +962,5 @@ extern "C" int pm_test_plonk_linearise(size_t n, const uint64_t (*evaluations)[4
 }
 
 #include "prover_batch.hip.h"
+#include "prover_check.hip.h"
 #include "prover_dist.hip.h"

@@ -117,6 +117,52 @@ class Proof:
         return p
 
 
+@dataclass
+class WitnessReport:
+    """``pm_plonk_witness_report``: what ``ProverKey.check_witness`` found.  ``first_row`` is the lowest failing row (None
+    when the witness is satisfied), ``first_reasons`` the names of that row's failed checks, ``counts[name]`` the number of
+    rows failing each check (names: ``_lib.PLONK_FAIL_NAMES``), ``row_masks`` the mask of every row ([n] uint8, bit k =
+    ``PLONK_FAIL_NAMES[k]``) when it was asked for."""
+    ok: bool
+    failed_rows: int
+    first_row: int | None
+    first_reasons: tuple
+    counts: dict
+    row_masks: np.ndarray | None = None
+
+    @staticmethod
+    def reasons(mask: int) -> tuple:
+        return tuple(nm for k, nm in enumerate(_lib.PLONK_FAIL_NAMES) if (int(mask) >> k) & 1)
+
+    @classmethod
+    def _from_raw(cls, raw, row_masks=None) -> "WitnessReport":
+        failed = int(raw.failed_rows)
+        return cls(ok=failed == 0, failed_rows=failed, first_row=int(raw.first_row) if failed else None,
+                   first_reasons=cls.reasons(raw.first_mask), counts={nm: int(raw.count[k]) for k, nm in
+                                                                      enumerate(_lib.PLONK_FAIL_NAMES)},
+                   row_masks=row_masks)
+
+    def describe(self) -> str:
+        if self.ok:
+            return "satisfied"
+        return f"row {self.first_row} fails ({', '.join(self.first_reasons)}); {self.failed_rows} failing row(s)"
+
+
+class UnsatisfiedWitness(ValueError):
+    """``prove(..., check=True)`` / ``prove_batch(..., check=True)``: the witness does not satisfy the circuit, nothing was
+    proved.  ``report`` is the :class:`WitnessReport` (of the first failing batch member), ``reports`` maps every failing
+    batch member to its report ({0: report} for ``prove``)."""
+
+    def __init__(self, report: WitnessReport | None = None, reports: dict | None = None):
+        self.reports = dict(reports) if reports is not None else {0: report}
+        self.report = report if report is not None else self.reports[min(self.reports)]
+        if reports is None:
+            msg = "the witness does not satisfy the circuit: " + self.report.describe()
+        else:
+            msg = "; ".join(f"witness {b} does not satisfy the circuit: {r.describe()}" for b, r in sorted(self.reports.items()))
+        super().__init__(msg)
+
+
 class ProverKey:
     """``pm_prover_key``: selector and sigma polynomials as coefficients and on the 4n coset, the coset
     points, L_1, 1/Z_H and the per-proof workspace -- built and owned by the library, all in HBM."""
@@ -137,6 +183,8 @@ class ProverKey:
         h = C.c_void_p()
         ctx._check(ctx._lib.pm_plonk_preprocess(ctx._h, ptrs, idx.ctypes.data_as(C.POINTER(C.c_int64)), self.n, C.byref(h)))
         self._h = h
+        self.sigma_index = idx                  # the check (enable_check) takes the permutation again: the key keeps sigma's values
+        self._check_enabled = False
         self.verifier_key: dict | None = None
         self.label = b"plonk"
 
@@ -174,6 +222,76 @@ class ProverKey:
         out = C.c_size_t()
         self.ctx._check(self.ctx._lib.pm_plonk_key_enable_zk(self.ctx._h, self._h, C.byref(out)))
         return int(out.value)
+
+    def enable_check(self) -> int:
+        """Make the key ready for ``check_witness`` (``pm_plonk_key_enable_check``; needs no commit key): the non-trivial
+        selectors on H, the permutation as wire positions and the check's own scratch.  Idempotent.  -> the device bytes the
+        check state holds."""
+        out = C.c_size_t()
+        self.ctx._check(self.ctx._lib.pm_plonk_key_enable_check(self.ctx._h, self._h, self.sigma_index.ctypes.data_as(
+            C.POINTER(C.c_int64)), C.byref(out)))
+        self._check_enabled = True
+        return int(out.value)
+
+    def _check_device(self, d_ptr, B: int, pairs, masks: bool) -> list:
+        """``pm_plonk_check_witness_batch`` on B proof-major witnesses in device memory; pairs: B (positions, values)."""
+        ctx, n = self.ctx, self.n
+        p_pos, p_val, counts = (_lib.u64p * B)(), (_lib.u64p * B)(), (C.c_size_t * B)()
+        for b, (pos, val) in enumerate(pairs):
+            counts[b] = pos.size
+            if pos.size:
+                p_pos[b], p_val[b] = pos.ctypes.data_as(_lib.u64p), val.ctypes.data_as(_lib.u64p)
+        raws = (_lib.WitnessReport * B)()
+        rows = np.zeros((B, n), np.uint8) if masks else None
+        ctx._check(ctx._lib.pm_plonk_check_witness_batch(ctx._h, self._h, B, d_ptr, p_pos, p_val, counts, raws,
+                                                         rows.ctypes.data_as(C.POINTER(C.c_uint8)) if masks else None))
+        return [WitnessReport._from_raw(raws[b], rows[b] if masks else None) for b in range(B)]
+
+    def check_witness(self, witness, public_inputs=None, masks: bool = False) -> WitnessReport:
+        """Does the witness satisfy the circuit?  One ``pm_plonk_check_witness`` call (``enable_check`` first): every gate
+        identity and copy constraint on every row, on the GPU.  witness and public_inputs as for
+        ``prove``; masks: also return every row's mask (``WitnessReport.row_masks``)."""
+        ctx, n = self.ctx, self.n
+        if isinstance(witness, DeviceVector):
+            if witness.n != 4 * n:
+                raise ValueError("device witness must hold 4n elements")
+            d_wit, own = witness, False
+        else:
+            d_wit, own = DeviceVector.from_host(ctx, np.ascontiguousarray(witness, dtype=np.uint64).reshape(4 * n, 4)), True
+        pos, val = _pi_pairs(public_inputs)
+        raw = _lib.WitnessReport()
+        rows = np.zeros(n, np.uint8) if masks else None
+        try:
+            ctx._check(ctx._lib.pm_plonk_check_witness(ctx._h, self._h, d_wit._p, pos.ctypes.data_as(_lib.u64p) if pos.size else None,
+                                                       val.ctypes.data_as(_lib.u64p) if pos.size else None, pos.size, C.byref(raw),
+                                                       rows.ctypes.data_as(C.POINTER(C.c_uint8)) if masks else None))
+        finally:
+            if own:
+                d_wit.free()
+        return WitnessReport._from_raw(raw, rows)
+
+    def check_witnesses(self, witnesses, public_inputs=None, masks: bool = False) -> list:
+        """``check_witness`` for B witnesses of the circuit in one ``pm_plonk_check_witness_batch`` call (B <= 64).  witnesses:
+        one DeviceVector of B x 4n elements (proof-major) or a list of host arrays [4, n, 4]; public_inputs: None or a list
+        of B entries as for ``prove``.  -> one report per witness, each equal to the single call's."""
+        ctx, n = self.ctx, self.n
+        if isinstance(witnesses, DeviceVector):
+            if witnesses.n % (4 * n) or witnesses.n == 0:
+                raise ValueError("a batch of device witnesses must hold a positive multiple of 4n elements")
+            d_wit, own, B = witnesses, False, witnesses.n // (4 * n)
+        else:
+            a = np.ascontiguousarray(np.stack([np.asarray(w, dtype=np.uint64).reshape(4 * n, 4) for w in witnesses]))
+            B = a.shape[0]
+            d_wit, own = DeviceVector.from_host(ctx, a.reshape(B * 4 * n, 4)), True
+        try:
+            if public_inputs is None:
+                public_inputs = [None] * B
+            if len(public_inputs) != B:
+                raise ValueError("one public-input entry per witness")
+            return self._check_device(d_wit._p, B, [_pi_pairs(p) for p in public_inputs], masks)
+        finally:
+            if own:
+                d_wit.free()
 
     def batch(self, max_batch: int, zero_knowledge: bool = False) -> "BatchWorkspace":
         """A workspace for ``prove_batch`` of up to ``max_batch`` (<= 64) proofs on this key: about 42 n x 32 bytes of
@@ -391,8 +509,12 @@ def random_blinders(count: int | None = None) -> np.ndarray:
 
 
 def prove(pk: ProverKey, ck: CommitKey, witness, public_inputs=None, bind_public_inputs: bool = True,
-          zero_knowledge: bool = False, blinders=None) -> Proof:
+          zero_knowledge: bool = False, blinders=None, check: bool = False) -> Proof:
     """``Prover::prove_with_preprocessed``: one ``pm_plonk_prove`` call.
+
+    check: run ``ProverKey.check_witness`` first (the key is made ready on first use) and raise
+    :class:`UnsatisfiedWitness`, which names the lowest failing row and why, instead of proving a witness that does not
+    satisfy the circuit.  The proof of a satisfied witness is the same bytes with and without it.
 
     witness: [4, n, 4] wire values (a, b, c, d rows) in Montgomery limbs, or a DeviceVector of 4n elements
     already in HBM.  public_inputs: dense [n, 4] evaluations of PI on H, or a (positions, values) pair, or None.
@@ -440,6 +562,12 @@ def prove(pk: ProverKey, ck: CommitKey, witness, public_inputs=None, bind_public
     p_pos = pos.ctypes.data_as(_lib.u64p) if pos.size else None
     p_val = val.ctypes.data_as(_lib.u64p) if pos.size else None
     try:
+        if check:
+            if not pk._check_enabled:
+                pk.enable_check()
+            report = pk._check_device(d_wit._p, 1, [(pos, val)], False)[0]
+            if not report.ok:
+                raise UnsatisfiedWitness(report)
         if hasattr(ck, "lo"):       # dist.ShardedCommitKey: this rank's slice of the SRS, partial sums exchanged
             cb = None if ck.native else _exchange_callback(ck)      # None: the library's RCCL communicator
             ctx._check(ctx._lib.pm_plonk_prove_sharded(ctx._h, pk._h, ck._bases._h, ck.lo, d_wit._p, p_pos, p_val, pos.size,
@@ -467,7 +595,8 @@ def _pi_pairs(public_inputs) -> tuple[np.ndarray, np.ndarray]:
 
 
 def prove_batch(pk: ProverKey, ck: CommitKey, witnesses, public_inputs=None, bind_public_inputs: bool = True,
-                workspace: BatchWorkspace | None = None, zero_knowledge: bool = False, blinders=None) -> list[Proof]:
+                workspace: BatchWorkspace | None = None, zero_knowledge: bool = False, blinders=None,
+                check: bool = False) -> list[Proof]:
     """B proofs of one circuit in one ``pm_plonk_prove_batch`` call; proof b equals ``prove(pk, ck, witness b, public
     inputs b)`` byte for byte.
 
@@ -483,7 +612,10 @@ def prove_batch(pk: ProverKey, ck: CommitKey, witnesses, public_inputs=None, bin
     per-proof witnesses -- DeviceVectors of 4n elements, copied device to device into the workspace's staging (one copy
     kernel per proof, 4n x 64 bytes of traffic each), or host arrays [4, n, 4], uploaded there.  public_inputs: None, or a
     list of B entries in any form ``prove`` takes (None, dense [n, 4], a (positions, values) pair).  workspace: a
-    ``ProverKey.batch`` workspace with max_batch >= B; None makes one for the call."""
+    ``ProverKey.batch`` workspace with max_batch >= B; None makes one for the call.
+
+    check: run ``ProverKey.check_witnesses`` on the batch first and raise :class:`UnsatisfiedWitness` with the reports of the
+    failing members (``.reports``: {b: report}) instead of proving; satisfied batches give the same bytes as without it."""
     ctx, n = pk.ctx, pk.n
     if ck.max_degree() + 1 < n:
         raise ValueError("commit key shorter than the circuit")
@@ -550,6 +682,12 @@ def prove_batch(pk: ProverKey, ck: CommitKey, witnesses, public_inputs=None, bin
             if pos.size:
                 p_pos[b] = pos.ctypes.data_as(_lib.u64p)
                 p_val[b] = val.ctypes.data_as(_lib.u64p)
+        if check:
+            if not pk._check_enabled:
+                pk.enable_check()
+            bad = {b: r for b, r in enumerate(pk._check_device(d_wit._p, B, pairs, False)) if not r.ok}
+            if bad:
+                raise UnsatisfiedWitness(reports=bad)
         raws = (_lib.PlonkProof * B)()
         flags = 0 if bind_public_inputs else _lib.PLONK_UPSTREAM_TRANSCRIPT
         if zero_knowledge:
