@@ -550,6 +550,44 @@ int pm_plonk_check_witness(pm_ctx* ctx, pm_prover_key* key, const void* d_witnes
 int pm_plonk_check_witness_batch(pm_ctx* ctx, pm_prover_key* key, uint32_t batch, const void* d_witnesses,
                                  const uint64_t* const* pi_positions, const uint64_t* const* pi_values, const size_t* n_pi,
                                  pm_plonk_witness_report* reports, uint8_t* row_masks_out);
+/* ---- Composer-form circuits: the permutation and the witness from wire variables ------------
+ * A constraint system holds four lists of variable ids per gate (dusk-plonk's w_l, w_r, w_o, w_4) and one assignment per
+ * variable, not a ready-made permutation and 4n dense wire values.  These calls take that form.
+ * wire_vars[j n + i] = the variable at wire j of gate i (the layout of the witness), an id in [0, num_vars) or
+ * PM_PLONK_NO_VAR.  The copy permutation is DEFINED as: the positions of a variable, ordered by rank r = 4 i + j (gate
+ * first, then a, b, c, d -- the order in which dusk's Permutation pushes Left(i), Right(i), Output(i), Fourth(i)), each
+ * map to the next one, the last to the first; a variable that occurs once maps to itself.  sigma_index is a pure function
+ * of wire_vars (a stable radix sort on the device, no ordering from atomics): the verifier key depends on it byte for
+ * byte.  A PM_PLONK_NO_VAR position belongs to no copy class: sigma fixes it and its wire value is 0 -- dusk's padding
+ * row (upstream's pad extends the wire lists with the zero variable without entering them in the variable map; restated
+ * from the public design and PARITY-UNPINNED, like the transcript labels).
+ * pm_plonk_sigma_from_wires: host in, host out (sigma_index_out: 4n x int64, the meaning pm_plonk_preprocess gives it);
+ * the _dev form takes and leaves device memory and has synchronised `stream` (NULL = the context's) when it returns.
+ * Scratch (two pair buffers and counts, about 64 n bytes) is freed before return.  An id that is >= num_vars and not
+ * PM_PLONK_NO_VAR: PM_ERR_BAD_ARG, pm_last_error names the lowest such position.  n <= 2^29, num_vars < 2^32.
+ * pm_plonk_preprocess_wires is pm_plonk_preprocess with the permutation given as wire_vars (host): sigma_index is built on
+ * the device and goes straight into the key; the key keeps the wire map on the device (16 n bytes) and is otherwise an
+ * ordinary pm_prover_key -- commit, prove, zk, batch, Lagrange attachment and free work as on any key.
+ * pm_plonk_key_enable_check on such a key accepts sigma_index = NULL and rebuilds the key's own permutation from its wire
+ * map (on a key from pm_plonk_preprocess NULL stays PM_ERR_BAD_ARG).  pm_plonk_key_num_vars: 0 for a key built from
+ * sigma_index.
+ * pm_plonk_witness_from_vars_dev expands assignments into witnesses on the device: d_vars holds batch x var_stride Fr
+ * (var_stride >= the key's num_vars), d_witness_out receives batch x 4n Fr, proof-major (what pm_plonk_prove_batch takes):
+ * w[b][p] = vars[b][wire_vars[p]], zero at PM_PLONK_NO_VAR positions.  Values are copied verbatim, with no range check,
+ * as the provers treat a dense witness.  Asynchronous on `stream` (NULL = the context's).
+ * The distributed prover is not extended: a caller of pm_plonk_preprocess_dist gets sigma_index from
+ * pm_plonk_sigma_from_wires and slices it itself.
+ * Errors: n not a power of two >= 4 (or above 2^29): PM_ERR_LENGTH; NULL pointers, an id out of range, batch 0 or above
+ * PM_PLONK_MAX_BATCH, var_stride < num_vars, a key that was not built from wires: PM_ERR_BAD_ARG. */
+#define PM_PLONK_NO_VAR 0xffffffffu
+int pm_plonk_sigma_from_wires(pm_ctx* ctx, const uint32_t* wire_vars, size_t num_vars, size_t n, int64_t* sigma_index_out);
+int pm_plonk_sigma_from_wires_dev(pm_ctx* ctx, const void* d_wire_vars, size_t num_vars, size_t n, void* d_sigma_index_out,
+                                  void* stream);
+int pm_plonk_preprocess_wires(pm_ctx* ctx, const uint64_t* const selectors[PM_PLONK_SELECTORS], const uint32_t* wire_vars,
+                              size_t num_vars, size_t n, pm_prover_key** out);
+size_t pm_plonk_key_num_vars(const pm_prover_key* key);
+int pm_plonk_witness_from_vars_dev(pm_ctx* ctx, const pm_prover_key* key, const void* d_vars, size_t var_stride,
+                                   uint32_t batch, void* d_witness_out, void* stream);
 /* Proof::to_bytes: 11 x 48-byte compressed G1, then the 16 scalars of ProofEvaluations::to_bytes. */
 int pm_plonk_proof_to_bytes(const pm_plonk_proof* proof, uint8_t out[PM_PLONK_PROOF_BYTES]);
 /* ---- The prover with coefficient-range ownership end to end (SURVEY.md section 8e row 3 + 8f N5; configs[4]) ----------
@@ -711,6 +749,11 @@ int pm_test_msm_plan(size_t n, uint32_t batch, long window_bits, uint32_t table_
  * a kernel, log2 group size of the blocked intermediate layout, 0}. */
 int pm_test_ntt_plan(uint32_t log_n, uint32_t batch, long tile_log, long max_radix, long radix, uint32_t num_cus,
                      uint32_t out[20]);
+/* Pure host, no context: the geometry of pm_plonk_sigma_from_wires' sort (csrc/wire_perm.hip) -- passes =
+ * max(1, ceil(bits(num_vars - 1) / 8)) 8-bit digit passes, tiles = ceil(4n / 4096) workgroups per pass, scratch_bytes = the
+ * transient device memory of the call.  Each out pointer may be NULL.  The errors of pm_plonk_sigma_from_wires for n and
+ * num_vars. */
+int pm_test_wire_sort_plan(size_t n, size_t num_vars, uint32_t* passes, uint32_t* tiles, size_t* scratch_bytes);
 /* Pure host, no context: the bucket-fill layout (csrc/msm_sort.hip.h) an MSM of this shape would run with -- out[16] =
  * {window bits, windows, bucket sets, bucket bits, partition bits, local bits, partitions per set, bins, partitions,
  * scalars per scatter tile, tiles, LDS bytes scatter, LDS bytes local sort, finer low partitions, their extra bits, 0} --

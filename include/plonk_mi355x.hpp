@@ -385,30 +385,37 @@ class ProverKey {
             const std::vector<int64_t>& sigma_index, const CommitKey& ck, const char* transcript_label = nullptr)
       : ctx_(&ctx), n_(selectors[0].size()) {
     const uint64_t* ptrs[PM_PLONK_SELECTORS];
-    for (int s = 0; s < PM_PLONK_SELECTORS; ++s) {
-      if (selectors[s].empty()) {
-        ptrs[s] = nullptr;
-        continue;
-      }
-      if (selectors[s].size() != n_ || n_ == 0) throw Error(PM_ERR_LENGTH, "selectors differ in length");
-      ptrs[s] = selectors[s][0].data();
-    }
+    selector_pointers(selectors, ptrs);
     if (sigma_index.size() != 4 * n_) throw Error(PM_ERR_LENGTH, "sigma_index must have 4n entries");
     ctx.check(pm_plonk_preprocess(ctx.get(), ptrs, sigma_index.data(), n_, &key_));
-    uint64_t vk[PM_PLONK_VK_POINTS][12];
-    int rc = pm_plonk_key_commit(ctx.get(), key_, ck.bases(), transcript_label, vk);
-    if (rc) {
-      pm_plonk_key_free(ctx.get(), key_);
-      key_ = nullptr;
-      ctx.check(rc);
-    }
-    for (int i = 0; i < PM_PLONK_VK_POINTS; ++i) std::copy(vk[i], vk[i] + 12, verifier_key_[i].begin());
+    commit(ck, transcript_label);
+  }
+  // The composer's form (pm_plonk_preprocess_wires): wire_vars[j n + i] = the variable at wire j of gate i, an id below
+  // num_vars or PM_PLONK_NO_VAR; the copy permutation is built on the device in dusk's order and the key keeps the wire map
+  // for witness_from_variables() and enable_check().
+  ProverKey(Context& ctx, const std::array<std::vector<Fr>, PM_PLONK_SELECTORS>& selectors,
+            const std::vector<uint32_t>& wire_vars, size_t num_vars, const CommitKey& ck, const char* transcript_label = nullptr)
+      : ctx_(&ctx), n_(selectors[0].size()) {
+    const uint64_t* ptrs[PM_PLONK_SELECTORS];
+    selector_pointers(selectors, ptrs);
+    if (wire_vars.size() != 4 * n_) throw Error(PM_ERR_LENGTH, "wire_vars must have 4n entries");
+    ctx.check(pm_plonk_preprocess_wires(ctx.get(), ptrs, wire_vars.data(), num_vars, n_, &key_));
+    commit(ck, transcript_label);
   }
   ~ProverKey() { if (key_) pm_plonk_key_free(ctx_->get(), key_); }
   ProverKey(const ProverKey&) = delete;
   ProverKey& operator=(const ProverKey&) = delete;
   size_t n() const { return n_; }
+  size_t num_vars() const { return pm_plonk_key_num_vars(key_); }   // 0: the key was built from sigma_index
   const std::array<G1Affine, PM_PLONK_VK_POINTS>& verifier_key() const { return verifier_key_; }
+  // batch x var_stride assignments on the device (var_stride >= num_vars()) -> batch x [a | b | c | d] witnesses, proof-major
+  // (pm_plonk_witness_from_vars_dev; a key built from wire variables)
+  DevicePolynomial witness_from_variables(const DevicePolynomial& variables, size_t var_stride, uint32_t batch = 1) const {
+    if (batch == 0 || variables.len() < (size_t)batch * var_stride) throw Error(PM_ERR_LENGTH, "variables must hold batch x var_stride values");
+    DevicePolynomial out(*ctx_, (size_t)batch * 4 * n_);
+    ctx_->check(pm_plonk_witness_from_vars_dev(ctx_->get(), key_, variables.data(), var_stride, batch, out.data(), nullptr));
+    return out;
+  }
   // round 1 commits the wires from the witness over lck (checked against ck; nullptr detaches); prove() must then be
   // given the same ck.  The proofs do not change.  lck must outlive the attachment.
   void use_lagrange(const CommitKey& ck, const LagrangeCommitKey* lck) {
@@ -458,6 +465,12 @@ class ProverKey {
     if (sigma_index.size() != 4 * n_) throw Error(PM_ERR_LENGTH, "sigma_index must have 4n entries");
     size_t added = 0;
     ctx_->check(pm_plonk_key_enable_check(ctx_->get(), key_, sigma_index.data(), &added));
+    return added;
+  }
+  // The same on a key built from wire variables: it rebuilds its own permutation from the wire map.
+  size_t enable_check() {
+    size_t added = 0;
+    ctx_->check(pm_plonk_key_enable_check(ctx_->get(), key_, nullptr, &added));
     return added;
   }
   // Does the witness satisfy the circuit (pm_plonk_check_witness; enable_check() first)?  The report names the lowest failing
@@ -542,6 +555,29 @@ class ProverKey {
   }
 
  private:
+  // the selector argument of the two preprocess calls (an empty vector = identically zero)
+  void selector_pointers(const std::array<std::vector<Fr>, PM_PLONK_SELECTORS>& selectors,
+                         const uint64_t* (&ptrs)[PM_PLONK_SELECTORS]) const {
+    for (int s = 0; s < PM_PLONK_SELECTORS; ++s) {
+      if (selectors[s].empty()) {
+        ptrs[s] = nullptr;
+        continue;
+      }
+      if (selectors[s].size() != n_ || n_ == 0) throw Error(PM_ERR_LENGTH, "selectors differ in length");
+      ptrs[s] = selectors[s][0].data();
+    }
+  }
+  // Prover::preprocess's second half: the verifier key, and the transcript every proof starts from
+  void commit(const CommitKey& ck, const char* transcript_label) {
+    uint64_t vk[PM_PLONK_VK_POINTS][12];
+    int rc = pm_plonk_key_commit(ctx_->get(), key_, ck.bases(), transcript_label, vk);
+    if (rc) {
+      pm_plonk_key_free(ctx_->get(), key_);
+      key_ = nullptr;
+      ctx_->check(rc);
+    }
+    for (int i = 0; i < PM_PLONK_VK_POINTS; ++i) std::copy(vk[i], vk[i] + 12, verifier_key_[i].begin());
+  }
   Proof from_raw(const pm_plonk_proof& raw) const {
     Proof p;
     for (int i = 0; i < 11; ++i) std::copy(raw.commitments[i], raw.commitments[i] + 12, p.commitments[i].begin());

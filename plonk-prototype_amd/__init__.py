@@ -13,5 +13,5 @@ from .host import (CommitKey, Context, DeviceVector, Error, EvaluationDomain, La
                    g1_fold, g1_to_affine, g1_compress, g1_decompress, domain_info, ntt_plan)
 from . import field, prover, srs, synthetic, transcript  # noqa: F401,E402
 from .prover import (BatchWorkspace, Circuit, Proof, ProverKey, UnsatisfiedWitness, WitnessReport,  # noqa: F401,E402
-                     preprocess, prove, prove_batch, random_blinders)
+                     preprocess, prove, prove_batch, random_blinders, sigma_from_wires)
 from .transcript import Transcript  # noqa: F401,E402

@@ -61,6 +61,8 @@ PLONK_SELECTORS, PLONK_PROOF_BYTES, PLONK_BIND_PUBLIC_INPUTS, PLONK_UPSTREAM_TRA
 COMM_ID_BYTES, COMM_MAX_POINTS = 128, 16
 LINCOMB_MAX = 16
 PLONK_MAX_BATCH = 64
+PLONK_NO_VAR = 0xffffffff     # PM_PLONK_NO_VAR: a wire position that belongs to no variable (value 0, sigma fixes it)
+WIRE_SORT_TILE = 4096         # pairs per workgroup and pass of pm_plonk_sigma_from_wires (csrc/wire_perm.hip)
 
 # name -> (restype, argtypes); must list every function the header declares
 SIGNATURES = {
@@ -160,6 +162,13 @@ SIGNATURES = {
     "pm_plonk_check_witness_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(u64p),
                                                C.POINTER(u64p), C.POINTER(C.c_size_t), C.POINTER(WitnessReport),
                                                C.POINTER(C.c_uint8)]),
+    "pm_plonk_sigma_from_wires": (C.c_int, [C.c_void_p, u32p, C.c_size_t, C.c_size_t, C.POINTER(C.c_int64)]),
+    "pm_plonk_sigma_from_wires_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "pm_plonk_preprocess_wires": (C.c_int, [C.c_void_p, C.POINTER(u64p), u32p, C.c_size_t, C.c_size_t,
+                                            C.POINTER(C.c_void_p)]),
+    "pm_plonk_key_num_vars": (C.c_size_t, [C.c_void_p]),
+    "pm_plonk_witness_from_vars_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p,
+                                                 C.c_void_p]),
     "pm_plonk_proof_to_bytes": (C.c_int, [C.POINTER(PlonkProof), C.POINTER(C.c_uint8)]),
     "pm_plonk_batch_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
     "pm_plonk_batch_free": (None, [C.c_void_p, C.c_void_p]),
@@ -192,6 +201,7 @@ SIGNATURES = {
     "pm_test_field_raw_op": (C.c_int, [C.c_void_p, C.c_int, C.c_int, u32p, u32p, C.c_size_t]),
     "pm_test_g1_raw_op": (C.c_int, [C.c_void_p, C.c_int, u32p, u32p, u32p, C.c_size_t]),
     "pm_test_ntt_plan": (C.c_int, [C.c_uint32, C.c_uint32, C.c_long, C.c_long, C.c_long, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "pm_test_wire_sort_plan": (C.c_int, [C.c_size_t, C.c_size_t, u32p, u32p, C.POINTER(C.c_size_t)]),
     "pm_test_msm_sizing": (C.c_int, [C.c_size_t, C.c_uint32, C.c_long, C.c_uint32, C.c_uint32, u64p]),
     "pm_test_msm_plan": (C.c_int, [C.c_size_t, C.c_uint32, C.c_long, C.c_uint32, C.c_uint32, C.c_long, C.c_long,
                                    u32p, u32p]),

@@ -175,6 +175,14 @@ int poly_evaluate_groups(pm_ctx* ctx, uint32_t groups, const uint32_t* k, const 
 int coset_expand(pm_ctx* ctx, const void* const* d_src, uint32_t count, const void* d_gs_pow, size_t m, void* d_out);
 int sigma_evals_from_index(pm_ctx* ctx, const int64_t* idx, size_t count, uint32_t log_n, const uint64_t omega[4],
                            const uint64_t k[3][4], void* d_out);
+int sigma_evals_from_index_dev(pm_ctx* ctx, const void* d_idx /* count x int64 */, size_t count, uint32_t log_n,
+                               const uint64_t omega[4], const uint64_t k[3][4], void* d_out);
+// Composer-form circuits (wire_perm.hip).  sigma_index_from_wires: device wire map (4n x uint32) ->
+// device sigma_index (4n x int64); synchronises st (nullptr = the context's stream) and fails on an id out of range.
+// witness_from_vars: out[b][p] = vars[b][wire_vars[p]] (32-byte elements), PM_PLONK_NO_VAR -> 0; asynchronous on st.
+int sigma_index_from_wires(pm_ctx* ctx, const void* d_wire_vars, size_t num_vars, size_t n, void* d_sigma_index, hipStream_t st);
+int witness_from_vars(pm_ctx* ctx, const void* d_wire_vars, size_t n, const void* d_vars, size_t var_stride, uint32_t batch,
+                      void* d_out, hipStream_t st);
 // Per-proof constants of the proof-batched kernels (pm_plonk_prove_batch): a pinned host buffer and its device twin of the
 // same size.  A launcher takes one region of both, fills the host side and sends it with one async copy on its stream;
 // kernels read the device side as a table indexed by the proof.  reset() once per call, after the previous call has

@@ -469,26 +469,25 @@ int coset_expand(pm_ctx* ctx, const void* const* d_src, uint32_t count, const vo
   return PM_OK;
 }
 
-// out[p] = k_j' w^i' for p < count, q = idx[p] = j' n + i' (host indices, already range-checked by the caller): two-level
-// tables of w (2 sqrt(n) entries) built on the device, one gather kernel.  Synchronises the context before it returns.
-int sigma_evals_from_index(pm_ctx* ctx, const int64_t* idx, size_t count, uint32_t log_n, const uint64_t omega[4],
-                           const uint64_t k[3][4], void* d_out) {
-  if (!ctx || !idx || !omega || !k || !d_out) return PM_ERR_BAD_ARG;
+// out[p] = k_j' w^i' for p < count, q = d_idx[p] = j' n + i' (device indices, every one in [0, 4n)): two-level tables of w
+// (2 sqrt(n) entries) built on the device, one gather kernel.  Synchronises the context before it returns.
+int sigma_evals_from_index_dev(pm_ctx* ctx, const void* d_idx, size_t count, uint32_t log_n, const uint64_t omega[4],
+                               const uint64_t k[3][4], void* d_out) {
+  if (!ctx || !d_idx || !omega || !k || !d_out) return PM_ERR_BAD_ARG;
   if (count == 0) return PM_OK;
   const host::Field<4>& F = host::FR();
   const uint32_t h = (log_n + 1) / 2;
   const size_t nlo = (size_t)1 << h, nhi = (size_t)1 << (log_n - h);
-  void *d_idx = nullptr, *d_lo = nullptr, *d_hi = nullptr;
-  struct Free3 {
+  void *d_lo = nullptr, *d_hi = nullptr;
+  struct Free2 {
     pm_ctx* c;
-    void **a, **b, **d;
-    ~Free3() {
-      for (void** p : {a, b, d})
+    void **a, **b;
+    ~Free2() {
+      for (void** p : {a, b})
         if (*p) (void)pm_dev_free(c, *p);
     }
-  } free3{ctx, &d_idx, &d_lo, &d_hi};
-  int rc = pm_dev_alloc(ctx, count * 8, &d_idx);
-  if (!rc) rc = pm_dev_alloc(ctx, nlo * 32, &d_lo);
+  } free2{ctx, &d_lo, &d_hi};
+  int rc = pm_dev_alloc(ctx, nlo * 32, &d_lo);
   if (!rc) rc = pm_dev_alloc(ctx, nhi * 32, &d_hi);
   if (rc) return rc;
   const HFr w = load_fr(omega), one = host::one(F);
@@ -496,7 +495,6 @@ int sigma_evals_from_index(pm_ctx* ctx, const int64_t* idx, size_t count, uint32
   const HFr step = host::pow<4>(w, e, 1, F);
   rc = pm_fr_powers_dev(ctx, w.l, one.l, nlo, d_lo, nullptr);
   if (!rc) rc = pm_fr_powers_dev(ctx, step.l, one.l, nhi, d_hi, nullptr);
-  if (!rc) rc = pm_dev_upload(ctx, d_idx, idx, count * 8);
   if (rc) return rc;
   {
     std::lock_guard<std::mutex> lk(ctx->mu);
@@ -510,6 +508,19 @@ int sigma_evals_from_index(pm_ctx* ctx, const int64_t* idx, size_t count, uint32
     PM_HIP(ctx, hipGetLastError());
   }
   return pm_sync(ctx);   // the temporaries go away when this returns
+}
+
+// The same from host indices (already range-checked by the caller).
+int sigma_evals_from_index(pm_ctx* ctx, const int64_t* idx, size_t count, uint32_t log_n, const uint64_t omega[4],
+                           const uint64_t k[3][4], void* d_out) {
+  if (!ctx || !idx || !omega || !k || !d_out) return PM_ERR_BAD_ARG;
+  if (count == 0) return PM_OK;
+  void* d_idx = nullptr;
+  int rc = pm_dev_alloc(ctx, count * 8, &d_idx);
+  if (!rc) rc = pm_dev_upload(ctx, d_idx, idx, count * 8);
+  if (!rc) rc = sigma_evals_from_index_dev(ctx, d_idx, count, log_n, omega, k, d_out);
+  if (d_idx) (void)pm_dev_free(ctx, d_idx);
+  return rc;
 }
 
 // ---- launchers of the proof-batched forms (pm_plonk_prove_batch, prover_batch.hip.h).  Each stages its per-proof

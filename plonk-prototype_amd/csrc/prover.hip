@@ -70,6 +70,9 @@ struct pm_prover_key {
   const pm_bases* lagrange_ck = nullptr;
   ZkState* zk = nullptr;               // pm_plonk_key_enable_zk
   CheckState* check = nullptr;         // pm_plonk_key_enable_check
+  // pm_plonk_preprocess_wires: the wire map (4n x uint32) the permutation was built from; nullptr on a key from sigma_index
+  void* wire_vars = nullptr;
+  size_t num_vars = 0;
 };
 
 // side stream <- everything submitted on the context's stream so far / the reverse
@@ -108,7 +111,8 @@ extern "C" void pm_plonk_key_free(pm_ctx* ctx, pm_prover_key* pk) {
   if (pk->ev_main) (void)hipEventDestroy(pk->ev_main);
   if (pk->ev_side) (void)hipEventDestroy(pk->ev_side);
   for (void* p : {pk->roots, pk->x4, pk->sel_coeffs, pk->sigma_evals, pk->sigma_coeffs, pk->sigma_coset,
-                  pk->l1_coset, pk->coeffs, pk->num, pk->den, pk->coset, pk->t, pk->r, pk->agg, pk->wit, pk->pi_evals})
+                  pk->l1_coset, pk->coeffs, pk->num, pk->den, pk->coset, pk->t, pk->r, pk->agg, pk->wit, pk->pi_evals,
+                  pk->wire_vars})
     if (p && ctx) (void)pm_dev_free(ctx, p);
   for (void* p : pk->sel_coset)
     if (p && ctx) (void)pm_dev_free(ctx, p);
@@ -124,9 +128,11 @@ extern "C" void pm_plonk_key_free(pm_ctx* ctx, pm_prover_key* pk) {
   delete pk;
 }
 
-extern "C" int pm_plonk_preprocess(pm_ctx* ctx, const uint64_t* const selectors[PM_PLONK_SELECTORS],
-                                   const int64_t* sigma_index, size_t n, pm_prover_key** out) {
-  if (!ctx || !selectors || !sigma_index || !out) return PM_ERR_BAD_ARG;
+// pm_plonk_preprocess (the permutation as sigma_index, host) and pm_plonk_preprocess_wires (as wire_vars, host: sigma_index is
+// built on the device and never leaves it) -- exactly one of the two is given
+static int preprocess_impl(pm_ctx* ctx, const uint64_t* const selectors[PM_PLONK_SELECTORS], const int64_t* sigma_index,
+                           const uint32_t* wire_vars, size_t num_vars, size_t n, pm_prover_key** out) {
+  if (!ctx || !selectors || (!sigma_index && !wire_vars) || !out) return PM_ERR_BAD_ARG;
   *out = nullptr;
   if (n < 4 || (n & (n - 1))) return PM_ERR_LENGTH;
   pm_prover_key* pk = new pm_prover_key();
@@ -185,7 +191,7 @@ extern "C" int pm_plonk_preprocess(pm_ctx* ctx, const uint64_t* const selectors[
       rc = pm_fr_ntt_dev(ctx, at(pk->sel_coeffs, s * n), n, n, pk->sel_coset[s], 4 * n, lg + 2, 1, PM_NTT_COSET, nullptr);
   // sigma_j(w^i) = k_j' w^i': the indices are checked here (a permutation of the 4n wire positions), the values gathered on
   // the device (r01 - r04: a 4n x 32-byte table went to the host and back)
-  if (!rc) {
+  if (!rc && sigma_index) {
     std::vector<uint8_t> seen(4 * n, 0);
     for (size_t p = 0; p < 4 * n && !rc; ++p) {
       const int64_t q = sigma_index[p];
@@ -193,10 +199,19 @@ extern "C" int pm_plonk_preprocess(pm_ctx* ctx, const uint64_t* const selectors[
       else seen[q] = 1;
     }
   }
-  if (!rc) {
-    u64 kk[3][4];
-    for (int j = 0; j < 3; ++j) put(kk[j], pk->k[j]);
-    rc = pm::sigma_evals_from_index(ctx, sigma_index, 4 * n, lg, pk->omega.l, kk, pk->sigma_evals);
+  u64 kk[3][4];
+  for (int j = 0; j < 3; ++j) put(kk[j], pk->k[j]);
+  if (!rc && sigma_index) rc = pm::sigma_evals_from_index(ctx, sigma_index, 4 * n, lg, pk->omega.l, kk, pk->sigma_evals);
+  if (!rc && wire_vars) {
+    // the cycles of the wire map are a permutation by construction: nothing to check on the host
+    void* d_idx = nullptr;
+    rc = pm_dev_alloc(ctx, 4 * n * 4, &pk->wire_vars);
+    if (!rc) rc = pm_dev_upload(ctx, pk->wire_vars, wire_vars, 4 * n * 4);
+    if (!rc) rc = pm_dev_alloc(ctx, 4 * n * 8, &d_idx);
+    if (!rc) rc = pm::sigma_index_from_wires(ctx, pk->wire_vars, num_vars, n, d_idx, nullptr);
+    if (!rc) rc = pm::sigma_evals_from_index_dev(ctx, d_idx, 4 * n, lg, pk->omega.l, kk, pk->sigma_evals);
+    if (d_idx) (void)pm_dev_free(ctx, d_idx);
+    pk->num_vars = num_vars;
   }
   if (!rc) rc = pm_fr_ntt_dev(ctx, pk->sigma_evals, n, n, pk->sigma_coeffs, n, lg, 4, PM_NTT_INVERSE, nullptr);
   if (!rc) rc = pm_fr_ntt_dev(ctx, pk->sigma_coeffs, n, n, pk->sigma_coset, 4 * n, lg + 2, 4, PM_NTT_COSET, nullptr);
@@ -215,6 +230,29 @@ extern "C" int pm_plonk_preprocess(pm_ctx* ctx, const uint64_t* const selectors[
   }
   *out = pk;
   return PM_OK;
+}
+
+extern "C" int pm_plonk_preprocess(pm_ctx* ctx, const uint64_t* const selectors[PM_PLONK_SELECTORS],
+                                   const int64_t* sigma_index, size_t n, pm_prover_key** out) {
+  if (!sigma_index) return PM_ERR_BAD_ARG;
+  return preprocess_impl(ctx, selectors, sigma_index, nullptr, 0, n, out);
+}
+
+extern "C" int pm_plonk_preprocess_wires(pm_ctx* ctx, const uint64_t* const selectors[PM_PLONK_SELECTORS],
+                                         const uint32_t* wire_vars, size_t num_vars, size_t n, pm_prover_key** out) {
+  if (!wire_vars) return PM_ERR_BAD_ARG;
+  return preprocess_impl(ctx, selectors, nullptr, wire_vars, num_vars, n, out);
+}
+
+extern "C" size_t pm_plonk_key_num_vars(const pm_prover_key* pk) { return pk && pk->wire_vars ? pk->num_vars : 0; }
+
+extern "C" int pm_plonk_witness_from_vars_dev(pm_ctx* ctx, const pm_prover_key* pk, const void* d_vars, size_t var_stride,
+                                              uint32_t batch, void* d_witness_out, void* stream) {
+  if (!ctx || !pk || !d_vars || !d_witness_out) return PM_ERR_BAD_ARG;
+  if (!pk->wire_vars) return pm::set_err(ctx, PM_ERR_BAD_ARG, "the key was not built from wire variables (pm_plonk_preprocess_wires)");
+  if (batch == 0 || batch > PM_PLONK_MAX_BATCH) return pm::set_err(ctx, PM_ERR_BAD_ARG, "batch must be in 1..PM_PLONK_MAX_BATCH");
+  if (var_stride < pk->num_vars) return pm::set_err(ctx, PM_ERR_BAD_ARG, "var_stride is below the key's num_vars");
+  return pm::witness_from_vars(ctx, pk->wire_vars, pk->n, d_vars, var_stride, batch, d_witness_out, (hipStream_t)stream);
 }
 
 // Commitments to `batch` coefficient vectors of n elements.  With the SRS split over ranks (shard.fn set)

@@ -122,12 +122,27 @@ int check_witness_impl(pm_ctx* ctx, pm_prover_key* pk, uint32_t B, const void* d
 }  // namespace
 
 extern "C" int pm_plonk_key_enable_check(pm_ctx* ctx, pm_prover_key* pk, const int64_t* sigma_index, size_t* added_bytes) {
-  if (!ctx || !pk || !sigma_index) return PM_ERR_BAD_ARG;
+  if (!ctx || !pk || (!sigma_index && !pk->wire_vars)) return PM_ERR_BAD_ARG;
   Busy guard(pk->busy);
   if (!guard.ok) return PM_ERR_BUSY;
   const size_t n = pk->n;
   const uint32_t lg = pk->log_n;
   if (4 * n > ((size_t)1 << 32)) return pm::set_err(ctx, PM_ERR_LENGTH, "the check keeps 32-bit wire positions");
+  if (!sigma_index && pk->check) {          // a key built from wires checks against its own permutation: nothing to compare
+    if (added_bytes) *added_bytes = pk->check->bytes;
+    return PM_OK;
+  }
+  std::vector<int64_t> own;                 // a key built from wires and no sigma_index: its permutation, rebuilt from the wire map
+  if (!sigma_index) {
+    void* d_idx = nullptr;
+    own.resize(4 * n);
+    int rc = pm_dev_alloc(ctx, 4 * n * 8, &d_idx);
+    if (!rc) rc = pm::sigma_index_from_wires(ctx, pk->wire_vars, pk->num_vars, n, d_idx, nullptr);
+    if (!rc) rc = pm_dev_download(ctx, own.data(), d_idx, 4 * n * 8);
+    if (d_idx) (void)pm_dev_free(ctx, d_idx);
+    if (rc != PM_OK) return rc;
+    sigma_index = own.data();
+  }
   std::vector<uint32_t> idx(4 * n);
   for (size_t p = 0; p < 4 * n; ++p) {
     if (sigma_index[p] < 0 || (size_t)sigma_index[p] >= 4 * n) return pm::set_err(ctx, PM_ERR_BAD_ARG, "sigma_index out of range");

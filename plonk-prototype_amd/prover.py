@@ -56,20 +56,33 @@ def transcript_labels() -> dict:
 
 @dataclass
 class Circuit:
-    """Selector evaluations on H ([n, 4] Montgomery limbs each; None = identically zero) and the copy
-    permutation: ``sigma_index[j, i] = j' * n + i'`` means wire j of gate i is followed by wire j' of gate i'."""
-    sigma_index: np.ndarray
-    q_m: np.ndarray
-    q_l: np.ndarray
-    q_r: np.ndarray
-    q_o: np.ndarray
-    q_c: np.ndarray
-    q_4: np.ndarray
-    q_arith: np.ndarray
+    """Selector evaluations on H ([n, 4] Montgomery limbs each; None = identically zero) and
+    the copy constraints, in exactly one of two forms: ``sigma_index[j, i] = j' * n + i'`` means wire j of gate i is followed
+    by wire j' of gate i'; or ``wire_vars[j, i]`` ([4, n] uint32) = the variable at wire j of gate i, an id below
+    ``num_vars`` or ``_lib.PLONK_NO_VAR``, from which the library builds the permutation on the device in dusk's order
+    (``pm_plonk_preprocess_wires``)."""
+    sigma_index: np.ndarray | None = None
+    q_m: np.ndarray | None = None
+    q_l: np.ndarray | None = None
+    q_r: np.ndarray | None = None
+    q_o: np.ndarray | None = None
+    q_c: np.ndarray | None = None
+    q_4: np.ndarray | None = None
+    q_arith: np.ndarray | None = None
     q_range: np.ndarray | None = None
     q_logic: np.ndarray | None = None
     q_fixed_group_add: np.ndarray | None = None
     q_variable_group_add: np.ndarray | None = None
+    wire_vars: np.ndarray | None = None
+    num_vars: int | None = None
+
+    def __post_init__(self):
+        if (self.sigma_index is None) == (self.wire_vars is None):
+            raise ValueError("give exactly one of sigma_index and wire_vars")
+        if self.wire_vars is not None and self.num_vars is None:
+            raise ValueError("wire_vars needs num_vars")
+        if self.wire_vars is None and self.num_vars is not None:
+            raise ValueError("num_vars goes with wire_vars")
 
     @property
     def n(self) -> int:
@@ -179,14 +192,62 @@ class ProverKey:
                     raise ValueError(f"selector {s} has the wrong length")
                 keep.append(a)
                 ptrs[i] = a.ctypes.data_as(_lib.u64p)
-        idx = np.ascontiguousarray(circuit.sigma_index, dtype=np.int64).reshape(-1)
         h = C.c_void_p()
-        ctx._check(ctx._lib.pm_plonk_preprocess(ctx._h, ptrs, idx.ctypes.data_as(C.POINTER(C.c_int64)), self.n, C.byref(h)))
+        if circuit.wire_vars is not None:
+            wv = _wire_vars(circuit.wire_vars, self.n)
+            ctx._check(ctx._lib.pm_plonk_preprocess_wires(ctx._h, ptrs, wv.ctypes.data_as(_lib.u32p), int(circuit.num_vars),
+                                                          self.n, C.byref(h)))
+            self.wire_vars, self.num_vars = wv, int(circuit.num_vars)
+            self._sigma_index = None            # filled from pm_plonk_sigma_from_wires when someone reads it
+        else:
+            idx = np.ascontiguousarray(circuit.sigma_index, dtype=np.int64).reshape(-1)
+            ctx._check(ctx._lib.pm_plonk_preprocess(ctx._h, ptrs, idx.ctypes.data_as(C.POINTER(C.c_int64)), self.n, C.byref(h)))
+            self.wire_vars, self.num_vars = None, 0
+            self._sigma_index = idx             # the check (enable_check) takes the permutation again: the key keeps sigma's values
         self._h = h
-        self.sigma_index = idx                  # the check (enable_check) takes the permutation again: the key keeps sigma's values
         self._check_enabled = False
         self.verifier_key: dict | None = None
         self.label = b"plonk"
+
+    @property
+    def sigma_index(self) -> np.ndarray:
+        """The copy permutation (flat int64 [4n]); on a key built from wire variables, computed on first use."""
+        if self._sigma_index is None:
+            self._sigma_index = sigma_from_wires(self.wire_vars, self.num_vars, self.ctx).reshape(-1)
+        return self._sigma_index
+
+    def witness_from_variables(self, variables) -> DeviceVector:
+        """Expand variable assignments into witnesses on the device (``pm_plonk_witness_from_vars_dev``; a key built from
+        ``wire_vars``).  variables: host [num_vars, 4] Montgomery limbs, a list of B of them, or a DeviceVector of
+        B x num_vars elements.  -> a DeviceVector of B x 4n elements, proof-major: w[b][j n + i] = variables[b][wire_vars[j, i]],
+        zero at ``PLONK_NO_VAR`` positions.  Values are copied as they are."""
+        ctx, n = self.ctx, self.n
+        if self.wire_vars is None:
+            raise ValueError("the key was not built from wire variables")
+        nv = self.num_vars
+        if isinstance(variables, DeviceVector):
+            if nv == 0 or variables.n == 0 or variables.n % nv:
+                raise ValueError("device variables must hold a positive multiple of num_vars elements")
+            d_vars, own, B = variables, False, variables.n // nv
+        else:
+            if isinstance(variables, (list, tuple)):
+                a = np.stack([np.asarray(v, dtype=np.uint64).reshape(nv, 4) for v in variables]) if len(variables) else None
+            else:
+                a = np.asarray(variables, dtype=np.uint64).reshape(1, nv, 4)
+            if a is None:
+                raise ValueError("empty batch")
+            B = a.shape[0]
+            d_vars, own = DeviceVector.from_host(ctx, np.ascontiguousarray(a).reshape(B * nv, 4)), True
+        out = DeviceVector(ctx, B * 4 * n)
+        try:
+            ctx._check(ctx._lib.pm_plonk_witness_from_vars_dev(ctx._h, self._h, d_vars._p, nv, B, out._p, None))
+        except Exception:
+            out.free()
+            raise
+        finally:
+            if own:
+                d_vars.free()               # pm_dev_free waits for the context's stream: the gather has read it
+        return out
 
     def commit(self, ck, label: bytes = b"plonk") -> dict:
         """``Prover::preprocess``'s second half: commit to the 15 polynomials of the key (the verifier
@@ -228,8 +289,8 @@ class ProverKey:
         selectors on H, the permutation as wire positions and the check's own scratch.  Idempotent.  -> the device bytes the
         check state holds."""
         out = C.c_size_t()
-        self.ctx._check(self.ctx._lib.pm_plonk_key_enable_check(self.ctx._h, self._h, self.sigma_index.ctypes.data_as(
-            C.POINTER(C.c_int64)), C.byref(out)))
+        idx = None if self.wire_vars is not None else self.sigma_index.ctypes.data_as(C.POINTER(C.c_int64))   # NULL: the key's own
+        self.ctx._check(self.ctx._lib.pm_plonk_key_enable_check(self.ctx._h, self._h, idx, C.byref(out)))
         self._check_enabled = True
         return int(out.value)
 
@@ -247,12 +308,15 @@ class ProverKey:
                                                          rows.ctypes.data_as(C.POINTER(C.c_uint8)) if masks else None))
         return [WitnessReport._from_raw(raws[b], rows[b] if masks else None) for b in range(B)]
 
-    def check_witness(self, witness, public_inputs=None, masks: bool = False) -> WitnessReport:
+    def check_witness(self, witness=None, public_inputs=None, masks: bool = False, variables=None) -> WitnessReport:
         """Does the witness satisfy the circuit?  One ``pm_plonk_check_witness`` call (``enable_check`` first): every gate
-        identity and copy constraint on every row, on the GPU.  witness and public_inputs as for
-        ``prove``; masks: also return every row's mask (``WitnessReport.row_masks``)."""
+        identity and copy constraint on every row, on the GPU.  witness (or variables) and
+        public_inputs as for ``prove``; masks: also return every row's mask (``WitnessReport.row_masks``)."""
         ctx, n = self.ctx, self.n
-        if isinstance(witness, DeviceVector):
+        _one_form(witness, variables, "witness")
+        if variables is not None:
+            d_wit, own = _single(self.witness_from_variables(variables), n), True
+        elif isinstance(witness, DeviceVector):
             if witness.n != 4 * n:
                 raise ValueError("device witness must hold 4n elements")
             d_wit, own = witness, False
@@ -270,12 +334,17 @@ class ProverKey:
                 d_wit.free()
         return WitnessReport._from_raw(raw, rows)
 
-    def check_witnesses(self, witnesses, public_inputs=None, masks: bool = False) -> list:
+    def check_witnesses(self, witnesses=None, public_inputs=None, masks: bool = False, variables=None) -> list:
         """``check_witness`` for B witnesses of the circuit in one ``pm_plonk_check_witness_batch`` call (B <= 64).  witnesses:
-        one DeviceVector of B x 4n elements (proof-major) or a list of host arrays [4, n, 4]; public_inputs: None or a list
-        of B entries as for ``prove``.  -> one report per witness, each equal to the single call's."""
+        one DeviceVector of B x 4n elements (proof-major) or a list of host arrays [4, n, 4]; or variables: what
+        ``witness_from_variables`` takes; public_inputs: None or a list of B entries as for ``prove``.  -> one report per
+        witness, each equal to the single call's."""
         ctx, n = self.ctx, self.n
-        if isinstance(witnesses, DeviceVector):
+        _one_form(witnesses, variables, "witnesses")
+        if variables is not None:
+            d_wit, own = self.witness_from_variables(variables), True
+            B = d_wit.n // (4 * n)
+        elif isinstance(witnesses, DeviceVector):
             if witnesses.n % (4 * n) or witnesses.n == 0:
                 raise ValueError("a batch of device witnesses must hold a positive multiple of 4n elements")
             d_wit, own, B = witnesses, False, witnesses.n // (4 * n)
@@ -377,6 +446,8 @@ class DistProverKey:
 
     def __init__(self, circuit: Circuit, ctx: Context, group):
         self.ctx, self.n, self.group = ctx, circuit.n, group
+        if circuit.sigma_index is None:
+            raise ValueError("the distributed key takes sigma_index: build it with sigma_from_wires and pass that")
         W, r = group.world, group.rank
         if self.n % W:
             raise ValueError("the ranks must divide the circuit size")
@@ -447,6 +518,45 @@ class DistProverKey:
             pass
 
 
+def _wire_vars(wire_vars, n: int | None = None) -> np.ndarray:
+    wv = np.asarray(wire_vars)
+    if wv.ndim != 2 or wv.shape[0] != 4 or (n is not None and wv.shape[1] != n):
+        raise ValueError("wire_vars must have the shape [4, n]")
+    if wv.dtype != np.uint32 and wv.size and (wv.min() < 0 or wv.max() > _lib.PLONK_NO_VAR):
+        raise ValueError("wire_vars holds 32-bit ids")
+    return np.ascontiguousarray(wv, dtype=np.uint32)
+
+
+def sigma_from_wires(wire_vars, num_vars: int, ctx: Context | None = None) -> np.ndarray:
+    """The copy permutation of a circuit given as wire variables (``pm_plonk_sigma_from_wires``, built on the GPU):
+    wire_vars [4, n] ids below num_vars or ``PLONK_NO_VAR`` -> sigma_index [4, n] int64 in which the positions of each
+    variable, ordered by gate and then wire, form one cycle (dusk's order).  ctx None: a context on device 0 for the call."""
+    wv = _wire_vars(wire_vars)
+    own = ctx is None
+    if own:
+        ctx = Context(0)
+    out = np.empty(wv.shape, np.int64)
+    try:
+        ctx._check(ctx._lib.pm_plonk_sigma_from_wires(ctx._h, wv.ctypes.data_as(_lib.u32p), int(num_vars), wv.shape[1],
+                                                      out.ctypes.data_as(C.POINTER(C.c_int64))))
+    finally:
+        if own:
+            ctx.close()
+    return out
+
+
+def _one_form(witness, variables, name: str):
+    if (witness is None) == (variables is None):
+        raise ValueError(f"give exactly one of {name} and variables")
+
+
+def _single(d_wit: DeviceVector, n: int) -> DeviceVector:
+    if d_wit.n != 4 * n:
+        d_wit.free()
+        raise ValueError("variables must hold one assignment")
+    return d_wit
+
+
 def _proof_from_raw(ctx: Context, raw) -> "Proof":
     proof = Proof()
     for i, name in enumerate(Proof.COMMITMENTS):
@@ -508,8 +618,8 @@ def random_blinders(count: int | None = None) -> np.ndarray:
     return np.stack([random_blinders() for _ in range(count)]) if count else np.zeros((0, _lib.PLONK_ZK_BLINDERS, 4), np.uint64)
 
 
-def prove(pk: ProverKey, ck: CommitKey, witness, public_inputs=None, bind_public_inputs: bool = True,
-          zero_knowledge: bool = False, blinders=None, check: bool = False) -> Proof:
+def prove(pk: ProverKey, ck: CommitKey, witness=None, public_inputs=None, bind_public_inputs: bool = True,
+          zero_knowledge: bool = False, blinders=None, check: bool = False, variables=None) -> Proof:
     """``Prover::prove_with_preprocessed``: one ``pm_plonk_prove`` call.
 
     check: run ``ProverKey.check_witness`` first (the key is made ready on first use) and raise
@@ -517,7 +627,9 @@ def prove(pk: ProverKey, ck: CommitKey, witness, public_inputs=None, bind_public
     satisfy the circuit.  The proof of a satisfied witness is the same bytes with and without it.
 
     witness: [4, n, 4] wire values (a, b, c, d rows) in Montgomery limbs, or a DeviceVector of 4n elements
-    already in HBM.  public_inputs: dense [n, 4] evaluations of PI on H, or a (positions, values) pair, or None.
+    already in HBM.  variables (instead of witness, on a key built from ``wire_vars``): one assignment per variable,
+    [num_vars, 4] or a DeviceVector, expanded on the device (``ProverKey.witness_from_variables``).  public_inputs:
+    dense [n, 4] evaluations of PI on H, or a (positions, values) pair, or None.
     bind_public_inputs: absorb the public inputs into the transcript before round 1 (dusk-plonk 0.8.2 does
     not; False reproduces the restated upstream transcript).
 
@@ -531,6 +643,7 @@ def prove(pk: ProverKey, ck: CommitKey, witness, public_inputs=None, bind_public
     None draws fresh ones with ``secrets.randbelow(r)`` -- pass fixed blinders in tests only: reusing blinders across
     proofs of different witnesses gives the witness away."""
     ctx, n = pk.ctx, pk.n
+    _one_form(witness, variables, "witness")
     if ck.max_degree() + 1 < n:
         raise ValueError("commit key shorter than the circuit")
     if blinders is not None and not zero_knowledge:
@@ -543,7 +656,9 @@ def prove(pk: ProverKey, ck: CommitKey, witness, public_inputs=None, bind_public
             raise ValueError(f"need {_lib.PLONK_ZK_BLINDERS} blinders")
     if pk.verifier_key is None:
         pk.commit(ck)
-    if isinstance(witness, DeviceVector):
+    if variables is not None:
+        d_wit, own = _single(pk.witness_from_variables(variables), n), True
+    elif isinstance(witness, DeviceVector):
         if witness.n != 4 * n:
             raise ValueError("device witness must hold 4n elements")
         d_wit, own = witness, False
@@ -594,9 +709,9 @@ def _pi_pairs(public_inputs) -> tuple[np.ndarray, np.ndarray]:
     return sparse_public_inputs(public_inputs)
 
 
-def prove_batch(pk: ProverKey, ck: CommitKey, witnesses, public_inputs=None, bind_public_inputs: bool = True,
+def prove_batch(pk: ProverKey, ck: CommitKey, witnesses=None, public_inputs=None, bind_public_inputs: bool = True,
                 workspace: BatchWorkspace | None = None, zero_knowledge: bool = False, blinders=None,
-                check: bool = False) -> list[Proof]:
+                check: bool = False, variables=None) -> list[Proof]:
     """B proofs of one circuit in one ``pm_plonk_prove_batch`` call; proof b equals ``prove(pk, ck, witness b, public
     inputs b)`` byte for byte.
 
@@ -610,13 +725,16 @@ def prove_batch(pk: ProverKey, ck: CommitKey, witnesses, public_inputs=None, bin
 
     witnesses: one DeviceVector of B x 4n elements (proof-major: proof b's [a | b | c | d] at 4 n b), or a list of B
     per-proof witnesses -- DeviceVectors of 4n elements, copied device to device into the workspace's staging (one copy
-    kernel per proof, 4n x 64 bytes of traffic each), or host arrays [4, n, 4], uploaded there.  public_inputs: None, or a
+    kernel per proof, 4n x 64 bytes of traffic each), or host arrays [4, n, 4], uploaded there.  variables (instead of
+    witnesses, on a key built from ``wire_vars``): a list of B assignments [num_vars, 4] or a DeviceVector of B x num_vars
+    elements, expanded on the device (``ProverKey.witness_from_variables``).  public_inputs: None, or a
     list of B entries in any form ``prove`` takes (None, dense [n, 4], a (positions, values) pair).  workspace: a
     ``ProverKey.batch`` workspace with max_batch >= B; None makes one for the call.
 
     check: run ``ProverKey.check_witnesses`` on the batch first and raise :class:`UnsatisfiedWitness` with the reports of the
     failing members (``.reports``: {b: report}) instead of proving; satisfied batches give the same bytes as without it."""
     ctx, n = pk.ctx, pk.n
+    _one_form(witnesses, variables, "witnesses")
     if ck.max_degree() + 1 < n:
         raise ValueError("commit key shorter than the circuit")
     if blinders is not None and not zero_knowledge:
@@ -628,6 +746,13 @@ def prove_batch(pk: ProverKey, ck: CommitKey, witnesses, public_inputs=None, bin
             raise ValueError("commit the key first")
     if pk.verifier_key is None:
         pk.commit(ck)
+    expanded = None
+    if variables is not None:
+        if not isinstance(variables, DeviceVector):
+            variables = list(variables)
+            if not variables:
+                raise ValueError("empty batch")
+        witnesses = expanded = pk.witness_from_variables(variables)
     if isinstance(witnesses, DeviceVector):
         if witnesses.n % (4 * n) or witnesses.n == 0:
             raise ValueError("a batch of device witnesses must hold a positive multiple of 4n elements")
@@ -699,6 +824,8 @@ def prove_batch(pk: ProverKey, ck: CommitKey, witnesses, public_inputs=None, bin
     finally:
         if own_ws:
             ws.free()
+        if expanded is not None:
+            expanded.free()
     return [_proof_from_raw(ctx, raws[b]) for b in range(B)]
 
 

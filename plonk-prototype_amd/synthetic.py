@@ -23,9 +23,8 @@ from .host import Context, DeviceVector
 from .prover import Circuit
 
 
-def chain_circuit(n: int, seed: int = 1, public_rows=(0,), zero_selectors=()):
-    """-> (Circuit, witness [4, n, 4], public_inputs [n, 4]) for a power-of-two n >= 4; PI is non-zero on `public_rows`;
-    the selectors named in `zero_selectors` (of q_m q_l q_r q_4 q_c) are identically zero."""
+def _chain(n: int, seed: int, public_rows, zero_selectors):
+    """chain_circuit's draws -> (selector arrays of Circuit, variable values [n + 1, 4], variable of every position, PI)."""
     rng = random.Random(seed)
     rnd = lambda: rng.getrandbits(256) % R_MOD   # noqa: E731
     q = {k: [rnd() for _ in range(n)] for k in ("q_m", "q_l", "q_r", "q_4", "q_c")}
@@ -43,13 +42,26 @@ def chain_circuit(n: int, seed: int = 1, public_rows=(0,), zero_selectors=()):
     vl = fr_vec_to_limbs(v)
     ar = np.arange(n, dtype=np.int64)
     var = np.concatenate([ar, np.maximum(ar - 1, 0), ar + 1, np.maximum(ar - 2, 0)])   # variable of position j n + i
-    witness = vl[var].reshape(4, n, 4)
-    sigma = _sigma_cycles(var)
     minus_one = fr_vec_to_limbs([R_MOD - 1])[0]
-    circuit = Circuit(q_m=fr_vec_to_limbs(qm), q_l=fr_vec_to_limbs(ql), q_r=fr_vec_to_limbs(qr),
-                      q_o=np.tile(minus_one, (n, 1)), q_4=fr_vec_to_limbs(q4), q_c=fr_vec_to_limbs(qc),
-                      q_arith=np.tile(fr_to_limbs(1), (n, 1)), sigma_index=sigma.reshape(4, n))
-    return circuit, witness, fr_vec_to_limbs(pi)
+    sel = dict(q_m=fr_vec_to_limbs(qm), q_l=fr_vec_to_limbs(ql), q_r=fr_vec_to_limbs(qr),
+               q_o=np.tile(minus_one, (n, 1)), q_4=fr_vec_to_limbs(q4), q_c=fr_vec_to_limbs(qc),
+               q_arith=np.tile(fr_to_limbs(1), (n, 1)))
+    return sel, vl, var, fr_vec_to_limbs(pi)
+
+
+def chain_circuit(n: int, seed: int = 1, public_rows=(0,), zero_selectors=()):
+    """-> (Circuit, witness [4, n, 4], public_inputs [n, 4]) for a power-of-two n >= 4; PI is non-zero on `public_rows`;
+    the selectors named in `zero_selectors` (of q_m q_l q_r q_4 q_c) are identically zero."""
+    sel, vl, var, pi = _chain(n, seed, public_rows, zero_selectors)
+    return Circuit(sigma_index=_sigma_cycles(var).reshape(4, n), **sel), vl[var].reshape(4, n, 4), pi
+
+
+def chain_circuit_wires(n: int, seed: int = 1, public_rows=(0,), zero_selectors=()):
+    """chain_circuit in composer form, from the same draws: -> (Circuit with ``wire_vars`` [4, n] and ``num_vars`` = n + 1,
+    variables [n + 1, 4], public_inputs [n, 4]).  ``variables[wire_vars]`` is chain_circuit's witness; the copy cycles are the
+    same sets of positions, linked in dusk's order (gate first, then wire) instead of column by column."""
+    sel, vl, var, pi = _chain(n, seed, public_rows, zero_selectors)
+    return Circuit(wire_vars=var.astype(np.uint32).reshape(4, n), num_vars=n + 1, **sel), vl, pi
 
 
 def chain_witnesses(n: int, seed: int = 1, count: int = 1, witness_seed: int = 1, public_rows=(0,), zero_selectors=()):
@@ -96,20 +108,8 @@ def _sigma_cycles(var: np.ndarray) -> np.ndarray:
     return sigma
 
 
-def boolean_circuit(n: int, seed: int = 1):
-    """-> (Circuit, witness [4, n, 4], public_inputs [n, 4]) shaped like the reference's bit-decomposition and range
-    gadgets (ref:src/zk/gadgets.rs:186-225): a witness that is almost all 0 and 1.  Power-of-two n >= 8.
-
-    Rows come in blocks of B = min(n, 64).  A block's first B - R rows are bit constraints
-    (q_m = 1, q_o = -1, a = b = c = bit, d = 0: bit^2 - bit = 0); its last R = min(7, max(1, B // 9)) rows recombine
-    2R + 1 of those bits into a value, two bits per row (q_l = 4, q_r = 2, q_4 = 1, q_o = -1):
-        c_0 = 4 bit_0 + 2 bit_1 + bit_2,   c_k = 4 c_(k-1) + 2 bit_(2k+1) + bit_(2k+2)   (a = c_(k-1), b, d = bits)
-    Copy constraints tie each bit row's a, b and c together, every use of a bit to its row, each c_k to the next
-    row's a, and all the d = 0 of bit rows to one another.  At least 95 % of the wire values are 0 or 1 from
-    B = 64 on (31 of 32 at n = 8).  No public input.
-
-    The seed draws only the bits: every seed gives the same circuit (selectors and sigma) with its own witness, so
-    ``boolean_circuit(n, s)`` for several s are distinct witnesses of one circuit (a batch for ``prove_batch``)."""
+def _boolean(n: int, seed: int):
+    """boolean_circuit's draws -> (selector arrays of Circuit, value and variable of every position [4n], variable count)."""
     if n < 8 or n & (n - 1):
         raise ValueError("boolean_circuit needs a power-of-two n >= 8")
     rng = np.random.default_rng(seed)
@@ -141,8 +141,6 @@ def boolean_circuit(n: int, seed: int = 1):
         val[:, :, row] = np.stack([a, b, acc, d])
         var[:, :, row] = np.stack([a_id, bit_id[:, 2 * k + 1], acc_id[:, k], bit_id[:, 2 * k + 2]])
     val, var = val.reshape(4 * n), var.reshape(4 * n)
-    uniq, inv = np.unique(val, return_inverse=True)        # a few hundred distinct small values
-    witness = fr_vec_to_limbs([int(u) for u in uniq])[inv.reshape(-1)].reshape(4, n, 4)
     recomb = np.zeros(B, bool)
     recomb[nb:] = True
     recomb = np.tile(recomb, blocks)
@@ -151,10 +149,45 @@ def boolean_circuit(n: int, seed: int = 1):
         c = fr_vec_to_limbs([on_bits, on_recomb])
         return np.where(recomb[:, None], c[1], c[0])
 
-    circuit = Circuit(q_m=sel(1, 0), q_l=sel(0, 4), q_r=sel(0, 2), q_o=sel(-1, -1), q_4=sel(0, 1),
-                      q_c=np.zeros((n, 4), np.uint64), q_arith=np.tile(fr_to_limbs(1), (n, 1)),
-                      sigma_index=_sigma_cycles(var).reshape(4, n))
-    return circuit, witness, np.zeros((n, 4), np.uint64)
+    sels = dict(q_m=sel(1, 0), q_l=sel(0, 4), q_r=sel(0, 2), q_o=sel(-1, -1), q_4=sel(0, 1),
+                q_c=np.zeros((n, 4), np.uint64), q_arith=np.tile(fr_to_limbs(1), (n, 1)))
+    return sels, val, var, zero_id + 1
+
+
+def _small_limbs(val: np.ndarray) -> np.ndarray:
+    """Small non-negative integers -> Montgomery limbs [len, 4] (a few hundred distinct values: converted once each)."""
+    uniq, inv = np.unique(val, return_inverse=True)
+    return fr_vec_to_limbs([int(u) for u in uniq])[inv.reshape(-1)]
+
+
+def boolean_circuit(n: int, seed: int = 1):
+    """-> (Circuit, witness [4, n, 4], public_inputs [n, 4]) shaped like the reference's bit-decomposition and range
+    gadgets (ref:src/zk/gadgets.rs:186-225): a witness that is almost all 0 and 1.  Power-of-two n >= 8.
+
+    Rows come in blocks of B = min(n, 64).  A block's first B - R rows are bit constraints
+    (q_m = 1, q_o = -1, a = b = c = bit, d = 0: bit^2 - bit = 0); its last R = min(7, max(1, B // 9)) rows recombine
+    2R + 1 of those bits into a value, two bits per row (q_l = 4, q_r = 2, q_4 = 1, q_o = -1):
+        c_0 = 4 bit_0 + 2 bit_1 + bit_2,   c_k = 4 c_(k-1) + 2 bit_(2k+1) + bit_(2k+2)   (a = c_(k-1), b, d = bits)
+    Copy constraints tie each bit row's a, b and c together, every use of a bit to its row, each c_k to the next
+    row's a, and all the d = 0 of bit rows to one another.  At least 95 % of the wire values are 0 or 1 from
+    B = 64 on (31 of 32 at n = 8).  No public input.
+
+    The seed draws only the bits: every seed gives the same circuit (selectors and sigma) with its own witness, so
+    ``boolean_circuit(n, s)`` for several s are distinct witnesses of one circuit (a batch for ``prove_batch``)."""
+    sels, val, var, _ = _boolean(n, seed)
+    circuit = Circuit(sigma_index=_sigma_cycles(var).reshape(4, n), **sels)
+    return circuit, _small_limbs(val).reshape(4, n, 4), np.zeros((n, 4), np.uint64)
+
+
+def boolean_circuit_wires(n: int, seed: int = 1):
+    """boolean_circuit in composer form, from the same draws: -> (Circuit with ``wire_vars`` [4, n] and ``num_vars`` = n + 1,
+    variables [n + 1, 4], public_inputs [n, 4]).  ``variables[wire_vars]`` is boolean_circuit's witness; the shared zero of the
+    d column is one variable at about n positions."""
+    sels, val, var, num_vars = _boolean(n, seed)
+    values = np.zeros(num_vars, np.int64)
+    values[var] = val                                      # every position of a variable holds the same value
+    circuit = Circuit(wire_vars=var.astype(np.uint32).reshape(4, n), num_vars=num_vars, **sels)
+    return circuit, _small_limbs(values), np.zeros((n, 4), np.uint64)
 
 
 # ------------------------------------------------------------------------------------------------
