@@ -25,6 +25,7 @@
  *   pm_g1_fixed_base_mul_dev     <- PublicParameters::setup (powers of tau)             8f N4
  *   pm_g1_bases_from_compressed  <- CommitKey::from_slice / PublicParameters::from_slice (checked SRS loading),
  *   pm_g1_decompress / _compress    G1Affine::{from_compressed, to_compressed}           8f N4
+ *   pm_g1_scalar_mul_dev         <- `G1Affine * Scalar` in bulk (an SRS update: powers[i] * delta^i)
  * (include/plonk_mi355x.hpp is the C++ mirror of the same interfaces.)
  *
  * Data layouts are the Rust types' memory, so slices can be passed without marshalling:
@@ -231,6 +232,31 @@ int pm_g1_fixed_base_mul_dev(pm_ctx* ctx, const uint64_t base_xy[12], const void
  * the inverse NTT of the first n bases); identities allowed.  PM_ERR_LENGTH when n exceeds the bases,
  * PM_ERR_DOMAIN_TOO_LARGE when log_n >= 32.  Allocates n x 320 + n x 32 bytes of scratch for the call; blocks until done. */
 int pm_g1_bases_lagrange(pm_ctx* ctx, const pm_bases* powers, uint32_t log_n, void* d_out_xy, void* hip_stream);
+
+/* ---- Per-point scalar multiplication -------------------------------------------------------
+ * out[i] = scalars[i] * points[i]: `G1Affine * Scalar` of dusk_bls12_381 in bulk, one thread per point.  Points and
+ * results are ABI affine (n x 96 bytes, Montgomery R = 2^384, (0, 0) = identity); scalars are n x 32 bytes in either
+ * PM_SCALAR_* form, below r.  A zero scalar or an identity point gives (0, 0).  d_out_xy == d_points_xy is allowed.
+ * flags = 0: a signed-window ladder over the whole scalar, valid for ANY point of the curve.
+ * PM_G1_POINTS_IN_SUBGROUP: the caller asserts that every point is the identity or has order r (a key from
+ * pm_g1_bases_from_compressed with PM_G1_CHECK_SUBGROUP, or one that passed pm_g1_check_dev / pm_g1_bases_check with it);
+ * the scalar is split k = k1 + k2 z^2 and the ladder runs over the two 128-bit halves with the endomorphism
+ * (x, y) -> (beta x, -y) = [z^2] P.  RESULTS UNDER THE FLAG ARE UNDEFINED FOR POINTS OUTSIDE THE SUBGROUP (the library
+ * does not check; a curve point of another order gives a wrong point, silently).
+ * n == 0 is PM_OK; null pointers, an unknown scalar form and unknown flag bits are PM_ERR_BAD_ARG.  Allocates n x 320
+ * bytes of scratch plus a window table (1792 bytes per thread in flight, at most 256 MiB) for the call; blocks until
+ * done. */
+#define PM_G1_POINTS_IN_SUBGROUP 1u /* caller asserts: every point is the identity or has order r */
+int pm_g1_scalar_mul_dev(pm_ctx* ctx, const void* d_points_xy, const void* d_scalars, size_t n, uint32_t scalar_form,
+                         uint32_t flags, void* d_out_xy, void* hip_stream);
+/* pm_g1_bases_lagrange with flags: 0 is exactly that call.  With PM_G1_POINTS_IN_SUBGROUP (same assertion, same caveat:
+ * undefined for points outside the subgroup) the twiddle multiplications take the split ladder; the bytes written are
+ * the same.  Unknown flag bits: PM_ERR_BAD_ARG. */
+int pm_g1_bases_lagrange_ex(pm_ctx* ctx, const pm_bases* powers, uint32_t log_n, uint32_t flags, void* d_out_xy,
+                            void* hip_stream);
+/* The inverse of pm_g1_bases_from_dev: the resident bases as ABI affine points (pm_g1_bases_len x 96 bytes) written to
+ * d_out_xy on the stream; the input of pm_g1_scalar_mul_dev for a key that never leaves the device.  Asynchronous. */
+int pm_g1_bases_to_dev(pm_ctx* ctx, const pm_bases* bases, void* d_out_xy, void* hip_stream);
 
 /* ---- Checked commit-key loading: compressed G1 and point checks ----------------------------
  * The 48-byte zcash encoding of G1Affine::{to_compressed, from_compressed} (dusk's CommitKey::to_var_bytes / from_slice
@@ -725,6 +751,12 @@ int pm_test_field_raw_op(pm_ctx* ctx, int field, int op, const uint32_t* in, uin
  * xyzz_mul_small (word 0 of b: the multiplier), 5 = half_double, 6 = half_add (one point per lane pair, as the reduction
  * kernels hold it).  b may be NULL for the doublings.  An infinite result has all limbs zero.  Host pointers, n cases. */
 int pm_test_g1_raw_op(pm_ctx* ctx, int op, const uint32_t* a, const uint32_t* b, uint32_t* out, size_t n);
+/* The GLV split of csrc/ec_mul.hip.h, k = k1 + k2 z^2 with z^2 = 0xac45a4010001a4020000000100000000, on the device as the
+ * kernels run it: n scalars (host pointer, n x 32 bytes, either PM_SCALAR_* form, below r) -> out, n x {k1 lo, k1 hi, k2
+ * lo, k2 hi} as uint64. */
+int pm_test_glv_split(pm_ctx* ctx, const uint64_t* scalars, size_t n, uint32_t scalar_form, uint64_t* out);
+/* Pure host, no context: the same routine compiled for the host, on one canonical k < r. */
+int pm_test_host_glv_split(const uint64_t k[4], uint64_t out[4]);
 /* Pure host, no context: the host-side field arithmetic behind the MSM fold and the prover's challenge scalars
  * (csrc/host_field.h).  op 0 = Fr product, 1 = Fp product, 2 = Fr inverse (binary extended Euclid), 3 = Fp inverse, 4 / 5 =
  * the same inverses by exponentiation; Montgomery form in and out, n elements; b is ignored by the inversions. */

@@ -230,7 +230,28 @@ class CommitKey {
   }
   const pm_bases* bases() const { return bases_; }
   // the Lagrange-form key [L_i(tau)]G of the 2^log_n domain (pm_g1_bases_lagrange): one inverse NTT over the first 2^log_n powers
-  class LagrangeCommitKey lagrange(uint32_t log_n) const;
+  // subgroup_points = true: the caller asserts that every power is in the order-r subgroup (a checked key); the twiddle
+  // multiplications take the GLV ladder (pm_g1_bases_lagrange_ex).  The same points; undefined outside the subgroup.
+  class LagrangeCommitKey lagrange(uint32_t log_n, bool subgroup_points = false) const;
+  // The key with powers delta^i P_i: the powers of tau become the powers of tau delta (one contribution to an updatable
+  // SRS).  On the device: pm_fr_powers_dev, pm_g1_bases_to_dev, pm_g1_scalar_mul_dev.  Verifying someone else's update
+  // needs pairings and is not part of this library.
+  CommitKey update(const Fr& delta, bool subgroup_points = false) const {
+    const size_t n = pm_g1_bases_len(bases_);
+    void *d_xy = nullptr, *d_pow = nullptr;
+    ctx_->check(pm_dev_alloc(ctx_->get(), (n ? n : 1) * 96, &d_xy));
+    int rc = pm_dev_alloc(ctx_->get(), (n ? n : 1) * 32, &d_pow);
+    pm_bases* out = nullptr;
+    if (!rc) rc = pm_fr_powers_dev(ctx_->get(), delta.data(), EvaluationDomain::one().data(), n, d_pow, nullptr);
+    if (!rc) rc = pm_g1_bases_to_dev(ctx_->get(), bases_, d_xy, nullptr);
+    if (!rc) rc = pm_g1_scalar_mul_dev(ctx_->get(), d_xy, d_pow, n, PM_SCALAR_MONTGOMERY,
+                                       subgroup_points ? PM_G1_POINTS_IN_SUBGROUP : 0u, d_xy, nullptr);
+    if (!rc) rc = pm_g1_bases_from_dev(ctx_->get(), d_xy, n, &out);
+    if (d_pow) pm_dev_free(ctx_->get(), d_pow);
+    pm_dev_free(ctx_->get(), d_xy);
+    ctx_->check(rc);
+    return CommitKey(*ctx_, out);
+  }
 
  private:
   CommitKey(Context& ctx, pm_bases* bases) : ctx_(&ctx), bases_(bases) {}
@@ -263,13 +284,14 @@ class LagrangeCommitKey {
   pm_bases* bases_ = nullptr;
 };
 
-inline LagrangeCommitKey CommitKey::lagrange(uint32_t log_n) const {
+inline LagrangeCommitKey CommitKey::lagrange(uint32_t log_n, bool subgroup_points) const {
   if (log_n >= 32) throw Error(PM_ERR_DOMAIN_TOO_LARGE, "log_n >= 32");
   const size_t n = (size_t)1 << log_n;
   void* d_xy = nullptr;
   ctx_->check(pm_dev_alloc(ctx_->get(), n * 96, &d_xy));
   pm_bases* out = nullptr;
-  int rc = pm_g1_bases_lagrange(ctx_->get(), bases_, log_n, d_xy, nullptr);
+  int rc = subgroup_points ? pm_g1_bases_lagrange_ex(ctx_->get(), bases_, log_n, PM_G1_POINTS_IN_SUBGROUP, d_xy, nullptr)
+                           : pm_g1_bases_lagrange(ctx_->get(), bases_, log_n, d_xy, nullptr);
   if (!rc) rc = pm_g1_bases_from_dev(ctx_->get(), d_xy, n, &out);
   pm_dev_free(ctx_->get(), d_xy);
   ctx_->check(rc);

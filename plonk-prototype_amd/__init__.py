@@ -9,7 +9,7 @@ runs in hand-written HIP kernels; importing works without a GPU, but creating a
 from ._lib import (BackendMissing, NTT_COSET, NTT_INVERSE, NTT_TRANSPOSED, SCALAR_CANONICAL,  # noqa: F401
                    SCALAR_MONTGOMERY, load, LIB_PATH)
 from .host import (CommitKey, Context, DeviceVector, Error, EvaluationDomain, LagrangeCommitKey, Polynomial,  # noqa: F401
-                   msm_variable_base,
+                   msm_variable_base, g1_scalar_mul,
                    g1_fold, g1_to_affine, g1_compress, g1_decompress, domain_info, ntt_plan)
 from . import field, prover, srs, synthetic, transcript  # noqa: F401,E402
 from .prover import (BatchWorkspace, Circuit, Proof, ProverKey, UnsatisfiedWitness, WitnessReport,  # noqa: F401,E402

@@ -106,6 +106,10 @@ SIGNATURES = {
                                               u64p, u32p]),
     "pm_g1_bases_to_compressed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "pm_g1_bases_lagrange": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "pm_g1_bases_lagrange_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "pm_g1_scalar_mul_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p,
+                                       C.c_void_p]),
+    "pm_g1_bases_to_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pm_g1_bases_precompute": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "pm_g1_bases_free": (None, [C.c_void_p, C.c_void_p]),
     "pm_g1_bases_len": (C.c_size_t, [C.c_void_p]),
@@ -200,6 +204,8 @@ SIGNATURES = {
     "pm_test_field_op": (C.c_int, [C.c_void_p, C.c_int, u64p, u64p, u64p, C.c_size_t]),
     "pm_test_field_raw_op": (C.c_int, [C.c_void_p, C.c_int, C.c_int, u32p, u32p, C.c_size_t]),
     "pm_test_g1_raw_op": (C.c_int, [C.c_void_p, C.c_int, u32p, u32p, u32p, C.c_size_t]),
+    "pm_test_glv_split": (C.c_int, [C.c_void_p, u64p, C.c_size_t, C.c_uint32, u64p]),
+    "pm_test_host_glv_split": (C.c_int, [u64p, u64p]),
     "pm_test_ntt_plan": (C.c_int, [C.c_uint32, C.c_uint32, C.c_long, C.c_long, C.c_long, C.c_uint32, C.POINTER(C.c_uint32)]),
     "pm_test_wire_sort_plan": (C.c_int, [C.c_size_t, C.c_size_t, u32p, u32p, C.POINTER(C.c_size_t)]),
     "pm_test_msm_sizing": (C.c_int, [C.c_size_t, C.c_uint32, C.c_long, C.c_uint32, C.c_uint32, u64p]),
@@ -222,6 +228,8 @@ PM_ERR_BUSY = -8
 PM_ERR_POINT = -9
 
 G1_CHECK_SUBGROUP = 1         # pm_g1_decompress* / pm_g1_check_dev / pm_g1_bases_check flag
+G1_POINTS_IN_SUBGROUP = 1     # pm_g1_scalar_mul_dev / pm_g1_bases_lagrange_ex flag: the caller asserts membership
+GLV_Z2 = 0xac45a4010001a4020000000100000000   # z^2: k = k1 + k2 z^2 is the split behind that flag (csrc/ec_mul.hip.h)
 G1_BAD_ENCODING, G1_BAD_NOT_ON_CURVE, G1_BAD_NOT_IN_SUBGROUP = 1, 2, 3
 G1_BAD_REASONS = {1: "malformed encoding or non-canonical coordinate", 2: "not on the curve", 3: "not in the subgroup"}
 

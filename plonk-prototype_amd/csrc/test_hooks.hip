@@ -7,7 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include "context.h"
-#include "ec.hip.h"
+#include "ec_mul.hip.h"
 #include "fields.hip.h"
 #include "ntt_kernels.hip.h"
 
@@ -151,6 +151,20 @@ __global__ void g1_half_op_kernel(const u32* a, const u32* b, u32* out, size_t n
   if (!isB) d[56] = r.inf ? 1u : 0u;
 }
 
+// the GLV split as the multiplication kernels run it: load, canonical conversion, fr_glv_split
+__global__ void glv_split_kernel(const u32x4* scalars, size_t n, u32 scalar_form, u32* out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  u32 w[8], k1[4], k2[4];
+  fr_load_canon(scalars + 2 * i, scalar_form == PM_SCALAR_MONTGOMERY, w);
+  fr_glv_split(w, k1, k2);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    out[8 * i + j] = k1[j];
+    out[8 * i + 4 + j] = k2[j];
+  }
+}
+
 struct FreeAll {   // the temporaries go away on every path, error returns included
   void* p[3] = {nullptr, nullptr, nullptr};
   ~FreeAll() {
@@ -245,5 +259,37 @@ extern "C" int pm_test_g1_raw_op(pm_ctx* ctx, int op, const uint32_t* a, const u
   PM_HIP(ctx, hipGetLastError());
   PM_HIP(ctx, hipMemcpyAsync(out, tmp.p[2], bytes, hipMemcpyDeviceToHost, ctx->stream));
   PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return PM_OK;
+}
+
+extern "C" int pm_test_glv_split(pm_ctx* ctx, const uint64_t* scalars, size_t n, uint32_t scalar_form, uint64_t* out) {
+  if (!ctx || !scalars || !out || scalar_form > PM_SCALAR_CANONICAL) return PM_ERR_BAD_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (n == 0) return PM_OK;
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  FreeAll tmp;
+  PM_HIP(ctx, hipMalloc(&tmp.p[0], n * 32));
+  PM_HIP(ctx, hipMalloc(&tmp.p[1], n * 32));
+  PM_HIP(ctx, hipMemcpyAsync(tmp.p[0], scalars, n * 32, hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(glv_split_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, (const u32x4*)tmp.p[0], n,
+                     scalar_form, (u32*)tmp.p[1]);
+  PM_HIP(ctx, hipGetLastError());
+  PM_HIP(ctx, hipMemcpyAsync(out, tmp.p[1], n * 32, hipMemcpyDeviceToHost, ctx->stream));
+  PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return PM_OK;
+}
+
+extern "C" int pm_test_host_glv_split(const uint64_t k[4], uint64_t out[4]) {
+  if (!k || !out) return PM_ERR_BAD_ARG;
+  GlvWords8 in{};
+  for (int i = 0; i < 4; ++i) {
+    in.w[2 * i] = (u32)k[i];
+    in.w[2 * i + 1] = (u32)(k[i] >> 32);
+  }
+  const GlvHalves h = glv_split_words(in);
+  out[0] = h.k1[0] | (uint64_t)h.k1[1] << 32;
+  out[1] = h.k1[2] | (uint64_t)h.k1[3] << 32;
+  out[2] = h.k2[0] | (uint64_t)h.k2[1] << 32;
+  out[3] = h.k2[2] | (uint64_t)h.k2[3] << 32;
   return PM_OK;
 }

@@ -85,6 +85,15 @@ class Context:
         """``pm_g1_compress_dev``: n x 96 bytes ABI affine -> n x 48 bytes; asynchronous on ``stream``."""
         self._check(self._lib.pm_g1_compress_dev(self._h, C.c_void_p(d_xy), n, C.c_void_p(d_bytes_out), C.c_void_p(stream)))
 
+    def g1_scalar_mul_dev(self, d_points: int, d_scalars: int, n: int, d_out: int,
+                          scalar_form: int = _lib.SCALAR_MONTGOMERY, subgroup_points: bool = False, stream: int = 0):
+        """``pm_g1_scalar_mul_dev``: out[i] = scalars[i] * points[i] on device buffers (n x 96 bytes ABI affine, n x 32
+        bytes of scalars); ``d_out`` may be ``d_points``.  ``subgroup_points=True`` asserts that every point is the
+        identity or has order r and takes the GLV ladder: undefined for any other point.  Blocks until done."""
+        self._check(self._lib.pm_g1_scalar_mul_dev(self._h, C.c_void_p(d_points), C.c_void_p(d_scalars), n, scalar_form,
+                                                   _lib.G1_POINTS_IN_SUBGROUP if subgroup_points else 0,
+                                                   C.c_void_p(d_out), C.c_void_p(stream)))
+
     def close(self):
         if getattr(self, "_h", None):
             self._lib.pm_shutdown(self._h)
@@ -664,6 +673,26 @@ def msm_variable_base(points, scalars, ctx: Context | None = None,
         b.free()
 
 
+def g1_scalar_mul(points, scalars, subgroup_points: bool = False, ctx: Context | None = None,
+                  scalar_form: int = _lib.SCALAR_MONTGOMERY) -> np.ndarray:
+    """``points[i] * scalars[i]`` (``G1Affine * Scalar``) for host arrays [n, 12] and [n, 4] -> [n, 12] affine.
+    ``subgroup_points=True``: the caller asserts that every point is in the order-r subgroup (GLV ladder; undefined
+    otherwise)."""
+    ctx = ctx or default_context()
+    p = np.ascontiguousarray(points, dtype=np.uint64).reshape(-1, 12)
+    s = _fr(scalars)
+    n = p.shape[0]
+    if n != s.shape[0]:
+        raise Error(_lib.PM_ERR_LENGTH, "points and scalars differ in length")
+    d_p, d_s = DeviceVector.from_host(ctx, p.reshape(-1, 4)), DeviceVector.from_host(ctx, s)
+    try:
+        ctx.g1_scalar_mul_dev(d_p.ptr, d_s.ptr, n, d_p.ptr, scalar_form, subgroup_points)
+        return d_p.to_host().reshape(n, 12)
+    finally:
+        d_p.free()
+        d_s.free()
+
+
 def g1_fold(parts) -> np.ndarray:
     lib = _lib.load()
     parts = np.ascontiguousarray(parts, dtype=np.uint64).reshape(-1, 18)
@@ -808,10 +837,35 @@ class CommitKey:
         xyz = self._bases.msm(c, _lib.SCALAR_MONTGOMERY)
         return g1_to_affine(xyz)[0]
 
-    def lagrange(self, log_n: int, precompute: bool = False) -> "LagrangeCommitKey":
+    def update(self, delta, subgroup_points: bool = False) -> "CommitKey":
+        """A new key with powers delta^i * P_i: the powers of tau become the powers of tau * delta -- one contribution
+        to PLONK's updatable universal SRS.  delta: Montgomery limbs [4], the contributor's secret.  Built on the
+        device (``pm_fr_powers_dev``, then ``pm_g1_scalar_mul_dev``); the points never visit the host.
+        ``subgroup_points=True`` asserts that this key was checked (``from_bytes(check_subgroup=True)`` or ``check()``)
+        and takes the GLV ladder.  Verifying SOMEONE ELSE'S update (that the new key is a scaling of the old one by a
+        delta its author knows) needs pairings and is not part of this library."""
+        ctx, n = self.ctx, self._bases.n
+        powers = DeviceVector(ctx, n)
+        pts = DeviceVector(ctx, 3 * n)                            # n affine points of 96 bytes
+        try:
+            ctx.fr_powers(delta, _one_mont(), n, powers.ptr)
+            ctx._check(ctx._lib.pm_g1_bases_to_dev(ctx._h, self._bases._h, pts._p, None))
+            ctx.g1_scalar_mul_dev(pts.ptr, powers.ptr, n, pts.ptr, _lib.SCALAR_MONTGOMERY, subgroup_points)
+            new = object.__new__(type(self))
+            new.ctx = ctx
+            new._bases = Bases.from_device(ctx, pts.ptr, n)
+            new.powers_of_g = None
+        finally:
+            pts.free()
+            powers.free()
+        return new
+
+    def lagrange(self, log_n: int, precompute: bool = False, subgroup_points: bool = False) -> "LagrangeCommitKey":
         """The Lagrange-form key [L_i(tau)]G of the 2^log_n domain, from the first 2^log_n powers by one inverse NTT over
         G1 on the GPU (``pm_g1_bases_lagrange``).  A one-time conversion per domain: save ``points()`` with
-        ``srs.commit_key_to_raw_bytes`` and load it with ``LagrangeCommitKey.from_points``."""
+        ``srs.commit_key_to_raw_bytes`` and load it with ``LagrangeCommitKey.from_points``.
+        ``subgroup_points=True`` asserts that every power is in the order-r subgroup (a checked key) and takes
+        ``pm_g1_bases_lagrange_ex`` with the GLV ladder: the same bytes; undefined for points outside the subgroup."""
         ctx = self.ctx
         if log_n >= 32:
             raise Error(_lib.PM_ERR_DOMAIN_TOO_LARGE, "log_n >= 32")
@@ -820,7 +874,11 @@ class CommitKey:
             raise Error(_lib.PM_ERR_LENGTH, "2^log_n exceeds the commit key")
         pts = DeviceVector(ctx, 3 * n)                            # n affine points of 96 bytes
         try:
-            ctx._check(ctx._lib.pm_g1_bases_lagrange(ctx._h, self._bases._h, log_n, pts._p, None))
+            if subgroup_points:
+                ctx._check(ctx._lib.pm_g1_bases_lagrange_ex(ctx._h, self._bases._h, log_n, _lib.G1_POINTS_IN_SUBGROUP,
+                                                            pts._p, None))
+            else:
+                ctx._check(ctx._lib.pm_g1_bases_lagrange(ctx._h, self._bases._h, log_n, pts._p, None))
             bases = Bases.from_device(ctx, pts.ptr, n)
             host = pts.to_host().reshape(n, 12)
         finally:
