@@ -614,6 +614,74 @@ int pm_plonk_preprocess_wires(pm_ctx* ctx, const uint64_t* const selectors[PM_PL
 size_t pm_plonk_key_num_vars(const pm_prover_key* key);
 int pm_plonk_witness_from_vars_dev(pm_ctx* ctx, const pm_prover_key* key, const void* d_vars, size_t var_stride,
                                    uint32_t batch, void* d_witness_out, void* stream);
+/* ---- Gadget witnesses: fill widget rows from their inputs -----------------------------------
+ * In a composer-form circuit most variables are not inputs but the internal accumulators of the four widget gadgets.
+ * These calls are the inverse of the witness check: given a gadget's inputs in the variable assignment, write the
+ * variables that make its rows hold, on the device, in the layout pm_plonk_witness_from_vars_dev reads.
+ * A gadget names its rows (first_row, count) and its input variables; what it writes are the variables the key's wire
+ * map holds at the positions below (PM_PLONK_NO_VAR positions are skipped).  Rows are relative to first_row, wires
+ * a b c d and the identities are those of pm_plonk_quotient_args.
+ *   RANGE, m = count rows, value v = in_var[0]: acc_0 = 0, acc_(k+1) = 4 acc_k + quad_k over the 4m quads of v, most
+ *     significant first.  Row i < m carries (a, b, c, d) = (acc_(4i+3), acc_(4i+2), acc_(4i+1), acc_(4i)), row m carries
+ *     d = acc_(4m).  PM_PLONK_GADGET_TOO_WIDE when v >= 2^(8m).
+ *   LOGIC, Q = count quads, inputs x = in_var[0], y = in_var[1], param 0 = AND, 1 = XOR: A, B, D are the accumulators of x,
+ *     y and x op y quad by quad, most significant first.  Row k < Q carries (A_k, B_k, qx_k qy_k, D_k), row Q carries a =
+ *     A_Q, b = B_Q, d = D_Q.  TOO_WIDE when an input >= 4^Q.
+ *   FIXED_BASE, R = count rounds (<= PM_PLONK_GADGET_MAX_ROUNDS), scalar s = in_var[0].  The start point is READ from a, b
+ *     of row 0 (the caller sets it; dusk uses the identity (0, 1)); the table point (x_b, y_b) of row k is the key's q_l,
+ *     q_r there.  Digits are the width-2 non-adjacent form: with x = 3 s, e_j = bit_(j+1)(x) - bit_(j+1)(s), and row k
+ *     uses bit_k = e_(R-1-k).  d_0 = 0, d_(k+1) = 2 d_k + bit_k (= (x >> (R-k+1)) - (s >> (R-k+1)), never negative);
+ *     c_k = bit_k x_b y_b; (a_(k+1), b_(k+1)) = (a_k, b_k) + (bit_k x_b, bit_k^2 (y_b - 1) + 1) under the twisted Edwards
+ *     law of JubJub, (x1, y1) + (x2, y2) = ((x1 y2 + y1 x2) / (1 + k), (y1 y2 + x1 x2) / (1 - k)), k = d x1 x2 y1 y2.  The
+ *     gadget writes d of rows 0..R, c of rows 0..R-1 and a, b of rows 1..R.  PM_PLONK_GADGET_SCALAR_TOO_LONG when some
+ *     e_j with j >= R is non-zero (every s < r has at most 256 digits).  The rounds are summed in another order than they
+ *     are defined in (a prefix scan): start and table points must lie on the curve, where the law is associative and
+ *     complete; for other points the values written are deterministic and unspecified.
+ *   CURVE_ADD (count ignored): reads (x1, y1, x2, y2) = a b c d of row 0 and writes a = x3, b = y3, d = x1 y2 in row 1.
+ *     PM_PLONK_GADGET_DEGENERATE, with a = b = 0 written, when 1 +- d x1 x2 y1 y2 is zero (impossible on the curve).
+ * Gadgets of one level are independent and run together; levels run in rising order, so a gadget may read what a lower
+ * level wrote.  Two gadgets of ONE level may name the same variable as an output only where the definitions give both the
+ * same value (the zero variable in d of a range's and a fixed-base's row 0, say); any other overlap is a race.  A gadget's
+ * inputs must not be among the outputs of its own level.  A failing gadget still writes: the values of its input cut to
+ * the width it has.  Every byte written and every report field is a pure function of the inputs; values are canonical
+ * Montgomery limbs.
+ * pm_plonk_key_set_gadgets (a key from pm_plonk_preprocess_wires; replaces an earlier table, count = 0 clears it) checks
+ * the table and keeps it on the device: one batched forward transform of the key's q_l, q_r, q_range, q_logic,
+ * q_fixed_group_add and q_variable_group_add into transient scratch (6 n x 32 bytes), a kernel that tests the selector of
+ * every claimed row (RANGE, LOGIC, FIXED_BASE: rows 0..count-1; CURVE_ADD: row 0) and gathers the table points of all
+ * fixed-base rounds (64 bytes each).  PM_ERR_BAD_ARG, with pm_last_error naming the lowest offending gadget, for: levels
+ * not in rising order, an unknown kind or param, rows (the trailing row included) outside [0, n), a claimed row whose
+ * selector is zero, a used in_var >= num_vars, count = 0 or a fixed-base count above PM_PLONK_GADGET_MAX_ROUNDS, a key
+ * that was not built from wires.  After a refusal the key keeps the table it had.  added_bytes (may be NULL): the device
+ * bytes the table holds.  pm_plonk_key_free frees it.
+ * pm_plonk_fill_gadgets_dev fills batch x var_stride assignments in place (var_stride >= num_vars, 1 <= batch <=
+ * PM_PLONK_MAX_BATCH), one launch per level and kind on `stream` (NULL = the context's).  reports (host, batch entries)
+ * may be NULL: the call is then asynchronous; otherwise it waits for the stream.  One fill at a time per key.  Errors:
+ * NULL arguments, no table, batch out of range, var_stride < num_vars: PM_ERR_BAD_ARG. */
+#define PM_PLONK_GADGET_RANGE 0u
+#define PM_PLONK_GADGET_LOGIC 1u
+#define PM_PLONK_GADGET_FIXED_BASE 2u
+#define PM_PLONK_GADGET_CURVE_ADD 3u
+#define PM_PLONK_GADGET_MAX_ROUNDS 256u
+#define PM_PLONK_GADGET_TOO_WIDE 1u
+#define PM_PLONK_GADGET_SCALAR_TOO_LONG 2u
+#define PM_PLONK_GADGET_DEGENERATE 3u
+typedef struct pm_plonk_gadget {
+  uint32_t kind, level;     /* gadgets of a level are independent; levels run in rising order */
+  uint64_t first_row;
+  uint32_t count;           /* RANGE: rows m (8m bits); LOGIC: quads Q; FIXED_BASE: rounds R; CURVE_ADD: ignored */
+  uint32_t param;           /* LOGIC: 0 = AND, 1 = XOR; otherwise 0 */
+  uint32_t in_var[2];       /* RANGE: value; LOGIC: a, b; FIXED_BASE: scalar; unused = PM_PLONK_NO_VAR */
+} pm_plonk_gadget;
+typedef struct pm_plonk_gadget_report {
+  uint64_t failed;        /* gadgets whose input did not fit */
+  uint64_t first_gadget;  /* lowest failing index, UINT64_MAX if none */
+  uint32_t first_reason;  /* PM_PLONK_GADGET_TOO_WIDE | _SCALAR_TOO_LONG | _DEGENERATE; 0 if none */
+  uint32_t reserved;      /* 0 */
+} pm_plonk_gadget_report;
+int pm_plonk_key_set_gadgets(pm_ctx* ctx, pm_prover_key* key, const pm_plonk_gadget* gadgets, size_t count, size_t* added_bytes);
+int pm_plonk_fill_gadgets_dev(pm_ctx* ctx, const pm_prover_key* key, void* d_vars, size_t var_stride, uint32_t batch,
+                              pm_plonk_gadget_report* reports, void* stream);
 /* Proof::to_bytes: 11 x 48-byte compressed G1, then the 16 scalars of ProofEvaluations::to_bytes. */
 int pm_plonk_proof_to_bytes(const pm_plonk_proof* proof, uint8_t out[PM_PLONK_PROOF_BYTES]);
 /* ---- The prover with coefficient-range ownership end to end (SURVEY.md section 8e row 3 + 8f N5; configs[4]) ----------
@@ -786,6 +854,10 @@ int pm_test_ntt_plan(uint32_t log_n, uint32_t batch, long tile_log, long max_rad
  * transient device memory of the call.  Each out pointer may be NULL.  The errors of pm_plonk_sigma_from_wires for n and
  * num_vars. */
 int pm_test_wire_sort_plan(size_t n, size_t num_vars, uint32_t* passes, uint32_t* tiles, size_t* scratch_bytes);
+/* Pure host, no context: the digit routine of the fixed-base gadget (csrc/gadgets.hip) compiled for the host.  s: a plain
+ * 256-bit integer (not Montgomery), 1 <= rounds <= PM_PLONK_GADGET_MAX_ROUNDS; digits_msb_first[k] = bit_k = e_(rounds-1-k)
+ * in {-1, 0, 1}; *too_long (may be NULL) = 1 when some e_j with j >= rounds is non-zero. */
+int pm_test_host_naf(const uint64_t s[4], uint32_t rounds, int8_t* digits_msb_first, int* too_long);
 /* Pure host, no context: the bucket-fill layout (csrc/msm_sort.hip.h) an MSM of this shape would run with -- out[16] =
  * {window bits, windows, bucket sets, bucket bits, partition bits, local bits, partitions per set, bins, partitions,
  * scalars per scatter tile, tiles, LDS bytes scatter, LDS bytes local sort, finer low partitions, their extra bits, 0} --

@@ -12,6 +12,6 @@ from .host import (CommitKey, Context, DeviceVector, Error, EvaluationDomain, La
                    msm_variable_base, g1_scalar_mul,
                    g1_fold, g1_to_affine, g1_compress, g1_decompress, domain_info, ntt_plan)
 from . import field, prover, srs, synthetic, transcript  # noqa: F401,E402
-from .prover import (BatchWorkspace, Circuit, Proof, ProverKey, UnsatisfiedWitness, WitnessReport,  # noqa: F401,E402
-                     preprocess, prove, prove_batch, random_blinders, sigma_from_wires)
+from .prover import (BatchWorkspace, Circuit, Gadget, GadgetInputError, GadgetReport, Proof, ProverKey,  # noqa: F401,E402
+                     UnsatisfiedWitness, WitnessReport, preprocess, prove, prove_batch, random_blinders, sigma_from_wires)
 from .transcript import Transcript  # noqa: F401,E402

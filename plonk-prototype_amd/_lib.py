@@ -44,6 +44,17 @@ class WitnessReport(C.Structure):
                 ("reserved", C.c_uint32), ("count", C.c_uint64 * 6)]
 
 
+class Gadget(C.Structure):
+    """``pm_plonk_gadget``"""
+    _fields_ = [("kind", C.c_uint32), ("level", C.c_uint32), ("first_row", C.c_uint64), ("count", C.c_uint32),
+                ("param", C.c_uint32), ("in_var", C.c_uint32 * 2)]
+
+
+class GadgetReport(C.Structure):
+    """``pm_plonk_gadget_report``"""
+    _fields_ = [("failed", C.c_uint64), ("first_gadget", C.c_uint64), ("first_reason", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, u64p, C.c_uint32)
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, u64p, u64p)
 COMM_MSG_WORDS = 289
@@ -173,6 +184,9 @@ SIGNATURES = {
     "pm_plonk_key_num_vars": (C.c_size_t, [C.c_void_p]),
     "pm_plonk_witness_from_vars_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p,
                                                  C.c_void_p]),
+    "pm_plonk_key_set_gadgets": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Gadget), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "pm_plonk_fill_gadgets_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32,
+                                            C.POINTER(GadgetReport), C.c_void_p]),
     "pm_plonk_proof_to_bytes": (C.c_int, [C.POINTER(PlonkProof), C.POINTER(C.c_uint8)]),
     "pm_plonk_batch_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
     "pm_plonk_batch_free": (None, [C.c_void_p, C.c_void_p]),
@@ -208,6 +222,7 @@ SIGNATURES = {
     "pm_test_host_glv_split": (C.c_int, [u64p, u64p]),
     "pm_test_ntt_plan": (C.c_int, [C.c_uint32, C.c_uint32, C.c_long, C.c_long, C.c_long, C.c_uint32, C.POINTER(C.c_uint32)]),
     "pm_test_wire_sort_plan": (C.c_int, [C.c_size_t, C.c_size_t, u32p, u32p, C.POINTER(C.c_size_t)]),
+    "pm_test_host_naf": (C.c_int, [u64p, C.c_uint32, C.POINTER(C.c_int8), C.POINTER(C.c_int)]),
     "pm_test_msm_sizing": (C.c_int, [C.c_size_t, C.c_uint32, C.c_long, C.c_uint32, C.c_uint32, u64p]),
     "pm_test_msm_plan": (C.c_int, [C.c_size_t, C.c_uint32, C.c_long, C.c_uint32, C.c_uint32, C.c_long, C.c_long,
                                    u32p, u32p]),
@@ -240,6 +255,13 @@ PLONK_ZK_EXTRA_BASES = 10     # ... and commit-key points it needs beyond n
 PLONK_FAIL_ARITH, PLONK_FAIL_RANGE, PLONK_FAIL_LOGIC = 1, 2, 4
 PLONK_FAIL_FIXED_BASE, PLONK_FAIL_VAR_BASE, PLONK_FAIL_COPY = 8, 16, 32
 PLONK_FAIL_NAMES = ("arith", "range", "logic", "fixed_base", "var_base", "copy")
+
+# pm_plonk_key_set_gadgets / pm_plonk_fill_gadgets_dev: gadget kinds and the reasons of a report
+PLONK_GADGET_RANGE, PLONK_GADGET_LOGIC, PLONK_GADGET_FIXED_BASE, PLONK_GADGET_CURVE_ADD = 0, 1, 2, 3
+PLONK_GADGET_MAX_ROUNDS = 256
+PLONK_GADGET_TOO_WIDE, PLONK_GADGET_SCALAR_TOO_LONG, PLONK_GADGET_DEGENERATE = 1, 2, 3
+PLONK_GADGET_KINDS = ("range", "logic", "fixed_base", "curve_add")
+PLONK_GADGET_REASONS = {1: "too_wide", 2: "scalar_too_long", 3: "degenerate"}
 
 NTT_INVERSE = 1
 NTT_COSET = 2

@@ -183,6 +183,27 @@ int sigma_evals_from_index_dev(pm_ctx* ctx, const void* d_idx /* count x int64 *
 int sigma_index_from_wires(pm_ctx* ctx, const void* d_wire_vars, size_t num_vars, size_t n, void* d_sigma_index, hipStream_t st);
 int witness_from_vars(pm_ctx* ctx, const void* d_wire_vars, size_t n, const void* d_vars, size_t var_stride, uint32_t batch,
                       void* d_out, hipStream_t st);
+// Gadget witnesses (gadgets.hip).  GadgetRec: one gadget as the kernels read it, in launch order
+// (level, then kind, then the caller's index); GadgetGroup: the records [first, first + count) of one launch.
+struct GadgetRec {
+  uint32_t kind, param;
+  uint32_t first_row, count;
+  uint32_t in_var[2];
+  uint32_t index;          // the caller's index: what a report names
+  uint32_t tab;            // FIXED_BASE: its first round in the table-point array
+};
+struct GadgetGroup {
+  uint32_t kind, first, count;
+};
+// set time: *d_bad = the lowest index among the records whose claimed rows miss their selector (~0: none), and the table points
+// of the fixed-base records into d_tab.  d_sel6: q_l q_r q_range q_logic q_fixed_group_add q_variable_group_add on H.  Asynchronous.
+int gadget_verify(pm_ctx* ctx, const void* d_recs, uint32_t count, size_t n, const void* d_sel6, void* d_tab, uint32_t* d_bad,
+                  hipStream_t st);
+// one launch per group on st; d_rep: 2 x batch words (failing gadgets, then min(index * 4 + reason)), copied to rep_host after
+// the launches when it is given -- the call then waits for the stream
+int gadget_fill(pm_ctx* ctx, const void* d_recs, const GadgetGroup* groups, size_t n_groups, const void* d_wire_vars, size_t n,
+                const void* d_tab, void* d_vars, size_t var_stride, uint32_t batch, void* d_rep, unsigned long long* rep_host,
+                hipStream_t st);
 // Per-proof constants of the proof-batched kernels (pm_plonk_prove_batch): a pinned host buffer and its device twin of the
 // same size.  A launcher takes one region of both, fills the host side and sends it with one async copy on its stream;
 // kernels read the device side as a table indexed by the proof.  reset() once per call, after the previous call has

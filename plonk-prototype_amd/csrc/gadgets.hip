@@ -1,0 +1,479 @@
+// Gadget witnesses: the inverse of the witness check.  Given the inputs of a range, logic, fixed-base
+// or curve-addition gadget, write the variables that make its rows hold (definitions: include/plonk_mi355x.h, pm_plonk_gadget).
+//
+//   gadget_verify_kernel       set time: every claimed row has its kind's selector, the table points of the fixed-base rounds
+//                              are gathered from q_l / q_r into a compact array
+//   gadget_range_kernel        one thread per (gadget, proof): quads of the canonical input, accumulators by 4 acc + quad
+//   gadget_logic_kernel        the same over two inputs, three accumulator columns and the quad products
+//   gadget_curve_add_kernel    one thread per (gadget, proof): the affine law with ONE inversion (of the two denominators' product)
+//   gadget_fixed_base_kernel   one WAVE per (gadget, proof), the hot path:
+//        every lane derives the width-2 NAF digits of its rounds from s and 3 s (e_j = bit_(j+1)(3s) - bit_(j+1)(s): no carry
+//        travels between lanes), owns a contiguous run of ceil(R / 64) rounds and sums its addends in extended coordinates;
+//        the lane totals go through an inclusive prefix scan with __shfl_up under the complete twisted Edwards law; each lane
+//        then walks its run again from the scanned start and normalises its <= 4 prefixes with one inversion (Montgomery's
+//        trick).  No lane ever runs more than one inversion and there is no chain of dependent per-round inversions.
+//        The addends are re-derived from the table in both walks rather than kept across the scan: what stays live over the
+//        scan is one point, and over the second walk the run's X, Y, Z (the variant kept: see DESIGN.md for the registers).
+//
+// Forms: variables are canonical Montgomery ("ABI", x 2^256); the point arithmetic runs in the device form x 2^261
+// (poly_common.hip.h).  Everything written goes through fe_store, i.e. is canonical.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <string>
+
+#include "context.h"
+#include "field_inv.hip.h"
+#include "poly_common.hip.h"
+
+namespace pm {
+namespace {
+
+#define PM_HOSTDEV __host__ __device__ inline
+
+// ------------------------------------------------------------------ bit work on little-endian 32-bit words (host and device)
+// w[i] without a dynamic index (the arrays stay in registers); 0 past the end
+template <int NW>
+PM_HOSTDEV u32 word_at(const u32 (&w)[NW], u32 i) {
+  u32 r = 0;
+#pragma unroll
+  for (int k = 0; k < NW; ++k) r = (u32)k == i ? w[k] : r;
+  return r;
+}
+template <int NW>
+PM_HOSTDEV u32 bit_at(const u32 (&w)[NW], u32 pos) {
+  return (word_at<NW>(w, pos >> 5) >> (pos & 31u)) & 1u;
+}
+template <int NW>
+PM_HOSTDEV u32 quad_at(const u32 (&w)[NW], u32 pos) {   // pos even
+  return (word_at<NW>(w, pos >> 5) >> (pos & 31u)) & 3u;
+}
+// w >> nbits != 0
+template <int NW>
+PM_HOSTDEV bool any_above(const u32 (&w)[NW], u32 nbits) {
+  u32 acc = 0;
+#pragma unroll
+  for (int k = 0; k < NW; ++k) {
+    const u32 lo = 32u * (u32)k;
+    if (lo >= nbits) acc |= w[k];
+    else if (lo + 32u > nbits) acc |= w[k] >> ((nbits - lo) & 31u);
+  }
+  return acc != 0;
+}
+// s (8 words) as 9 words and x = 3 s
+PM_HOSTDEV void naf_operands(const u32 (&s)[8], u32 (&s9)[9], u32 (&x9)[9]) {
+  u64 c = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    s9[i] = s[i];
+    c += 3ull * s[i];
+    x9[i] = (u32)c;
+    c >>= 32;
+  }
+  s9[8] = 0;
+  x9[8] = (u32)c;
+}
+// e_j = bit_(j+1)(3 s) - bit_(j+1)(s) in {-1, 0, 1}
+PM_HOSTDEV int naf_digit(const u32 (&x9)[9], const u32 (&s9)[9], u32 j) {
+  return (int)bit_at<9>(x9, j + 1) - (int)bit_at<9>(s9, j + 1);
+}
+// some e_j with j >= rounds is non-zero
+PM_HOSTDEV bool naf_too_long(const u32 (&x9)[9], const u32 (&s9)[9], u32 rounds) {
+  u32 t[9];
+#pragma unroll
+  for (int i = 0; i < 9; ++i) t[i] = x9[i] ^ s9[i];
+  return any_above<9>(t, rounds + 1);
+}
+
+// ------------------------------------------------------------------ device records and arguments
+struct GadgetFill {
+  const GadgetRec* recs;
+  const u32* wire_vars;     // [4][n]
+  const u32x4* tab;         // table points, 4 x 16 bytes per round: x | y canonical
+  u32x4* vars;              // [batch][var_stride] canonical
+  size_t var_stride, n;
+  unsigned long long* rep;  // [batch] failing gadgets, then [batch] min(index * 4 + reason); batch = gridDim.y
+  u32 edwards_d[9];         // device form
+};
+
+PM_DEV void gadget_fail(const GadgetFill& a, u32 proof, u32 index, u32 reason) {
+  atomicAdd(a.rep + proof, 1ull);                                              // a count and a minimum: order-free
+  atomicMin(a.rep + gridDim.y + proof, (unsigned long long)index * 4 + reason);
+}
+PM_DEV u32 var_id(const GadgetFill& a, u32 wire, size_t row) { return a.wire_vars[(size_t)wire * a.n + row]; }
+PM_DEV Fr ld_var(const u32x4* vars, u32 id) { return id == PM_PLONK_NO_VAR ? fe_zero<FrP>() : ld_canon(vars, id); }
+PM_DEV void st_var(u32x4* vars, u32 id, const Fr& v) {
+  if (id != PM_PLONK_NO_VAR) st_canon(vars, id, v);
+}
+
+// ------------------------------------------------------------------ field helpers (operands normalised, values < 2 r)
+PM_DEV Fr gadd(const Fr& a, const Fr& b) { return fe_reduce_weak<FrP>(fe_add<FrP>(a, b)); }
+PM_DEV Fr gsub(const Fr& a, const Fr& b) { return fe_reduce_weak<FrP>(fe_sub<FrP, 2, 1>(a, b)); }
+PM_DEV Fr gmul(const Fr& a, const Fr& b) { return fe_mul<FrP>(a, b); }
+PM_DEV Fr gneg(const Fr& a) { return gsub(fe_zero<FrP>(), a); }
+PM_DEV Fr g_to_dev(const Fr& abi) { return fe_reduce_weak<FrP>(fr_shl5(abi)); }
+PM_DEV Fr g_to_abi(const Fr& dev) { return fe_mul<FrP>(dev, fe_pow2<FrP, 256>()); }          // x 2^261 * 2^256 / 2^261
+PM_DEV Fr g_one_abi() { return fe_pow2<FrP, 256>(); }
+PM_DEV Fr g_sel(bool c, const Fr& a, const Fr& b) {
+  Fr r;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) r.l[i] = c ? a.l[i] : b.l[i];
+  return r;
+}
+PM_DEV bool g_is_zero(const Fr& v) {   // a zero may arrive as r: test the canonical words
+  u32 s[8];
+  fe_canon_pack<FrP>(s, v);
+  return (s[0] | s[1] | s[2] | s[3] | s[4] | s[5] | s[6] | s[7]) == 0;
+}
+// canonical Montgomery element -> the integer below r it stands for
+PM_DEV void g_to_int(const Fr& abi, u32 (&w)[8]) { fe_canon_pack<FrP>(w, fe_mul_limb<FrP>(abi, 32u)); }   // x 2^256 * 2^5 / 2^261
+// integer below 2^256 -> Montgomery (ABI) element, value < 2 r
+PM_DEV Fr g_from_int(const u32 (&w)[8]) { return fe_mul<FrP>(fe_unpack<FrP>(w), fe_pow2<FrP, 256 + 261>()); }
+PM_DEV Fr g_small(u32 c) {             // c < 2^29
+  Fr t = fe_zero<FrP>();
+  t.l[0] = c;
+  return fe_mul<FrP>(t, fe_pow2<FrP, 256 + 261>());
+}
+// 4 acc + q, q in 0..3 (ABI form in and out): limbs < 2^31 + 3 * 2^29, value < 8 r before the reduction
+PM_DEV Fr g_acc_step(const Fr& acc, u32 q) {
+  const Fr one = g_one_abi();
+  Fr t = fe_add<FrP>(acc, acc);
+  t = fe_add<FrP>(t, t);
+#pragma unroll
+  for (int i = 0; i < 9; ++i) t.l[i] += q * one.l[i];
+  return fe_reduce_weak<FrP>(t);
+}
+
+// ------------------------------------------------------------------ set time: selectors of the claimed rows, table points
+// sel: six vectors of n values on H -- q_l q_r q_range q_logic q_fixed_group_add q_variable_group_add
+__global__ void __launch_bounds__(256) gadget_verify_kernel(const GadgetRec* recs, const u32x4* sel, size_t n, u32x4* tab, u32* bad) {
+  const GadgetRec rec = recs[blockIdx.x];
+  const u32 rows = rec.kind == PM_PLONK_GADGET_CURVE_ADD ? 1u : rec.count;
+  const u32x4* q = sel + 2 * n * (2 + (size_t)rec.kind);
+  bool miss = false;
+  for (u32 t = threadIdx.x; t < rows; t += 256) {
+    const size_t row = (size_t)rec.first_row + t;
+    const u32x4 lo = q[2 * row], hi = q[2 * row + 1];
+    miss |= (lo.x | lo.y | lo.z | lo.w | hi.x | hi.y | hi.z | hi.w) == 0;
+    if (rec.kind == PM_PLONK_GADGET_FIXED_BASE) {
+      u32x4* o = tab + 4 * ((size_t)rec.tab + t);
+      o[0] = sel[2 * row];
+      o[1] = sel[2 * row + 1];
+      o[2] = sel[2 * (n + row)];
+      o[3] = sel[2 * (n + row) + 1];
+    }
+  }
+  if (miss) atomicMin(bad, rec.index);
+}
+
+// ------------------------------------------------------------------ range and logic
+__global__ void __launch_bounds__(64) gadget_range_kernel(const GadgetFill a, u32 first, u32 count) {
+  const u32 g = blockIdx.x * 64 + threadIdx.x, proof = blockIdx.y;
+  if (g >= count) return;
+  const GadgetRec rec = a.recs[first + g];
+  u32x4* const vars = a.vars + 2 * a.var_stride * proof;
+  u32 v[8];
+  g_to_int(ld_canon(vars, rec.in_var[0]), v);
+  const u32 quads = 4 * rec.count;
+  if (any_above<8>(v, 2 * quads)) gadget_fail(a, proof, rec.index, PM_PLONK_GADGET_TOO_WIDE);
+  Fr acc = fe_zero<FrP>();
+  for (u32 k = 0;; ++k) {   // acc_k sits at row k / 4, wire d, c, b, a for k mod 4 = 0, 1, 2, 3
+    st_var(vars, var_id(a, 3 - (k & 3u), (size_t)rec.first_row + (k >> 2)), acc);
+    if (k == quads) break;
+    acc = g_acc_step(acc, quad_at<8>(v, 2 * (quads - 1 - k)));
+  }
+}
+
+__global__ void __launch_bounds__(64) gadget_logic_kernel(const GadgetFill a, u32 first, u32 count) {
+  const u32 g = blockIdx.x * 64 + threadIdx.x, proof = blockIdx.y;
+  if (g >= count) return;
+  const GadgetRec rec = a.recs[first + g];
+  u32x4* const vars = a.vars + 2 * a.var_stride * proof;
+  u32 x[8], y[8];
+  g_to_int(ld_canon(vars, rec.in_var[0]), x);
+  g_to_int(ld_canon(vars, rec.in_var[1]), y);
+  const u32 Q = rec.count;
+  if (any_above<8>(x, 2 * Q) || any_above<8>(y, 2 * Q)) gadget_fail(a, proof, rec.index, PM_PLONK_GADGET_TOO_WIDE);
+  Fr A = fe_zero<FrP>(), B = A, D = A;
+  for (u32 k = 0;; ++k) {
+    const size_t row = (size_t)rec.first_row + k;
+    st_var(vars, var_id(a, 0, row), A);
+    st_var(vars, var_id(a, 1, row), B);
+    st_var(vars, var_id(a, 3, row), D);
+    if (k == Q) break;
+    const u32 qx = quad_at<8>(x, 2 * (Q - 1 - k)), qy = quad_at<8>(y, 2 * (Q - 1 - k));
+    st_var(vars, var_id(a, 2, row), g_small(qx * qy));
+    A = g_acc_step(A, qx);
+    B = g_acc_step(B, qy);
+    D = g_acc_step(D, rec.param ? (qx ^ qy) : (qx & qy));
+  }
+}
+
+// ------------------------------------------------------------------ JubJub: -x^2 + y^2 = 1 + d x^2 y^2, device form throughout
+// (x1, y1) + (x2, y2) = ((x1 y2 + y1 x2) / (1 + k), (y1 y2 + x1 x2) / (1 - k)), k = d x1 x2 y1 y2: complete on the curve.
+// One thread per (gadget, proof).  The inversion votes across the wave (field_inv.hip.h), so no lane leaves early: a lane
+// past the end works on the last gadget and writes nothing.
+__global__ void __launch_bounds__(64) gadget_curve_add_kernel(const GadgetFill a, u32 first, u32 count) {
+  const u32 g0 = blockIdx.x * 64 + threadIdx.x, proof = blockIdx.y;
+  const bool live = g0 < count;
+  const GadgetRec rec = a.recs[first + (live ? g0 : count - 1)];
+  u32x4* const vars = a.vars + 2 * a.var_stride * proof;
+  const size_t row = rec.first_row;
+  const Fr x1 = g_to_dev(ld_var(vars, var_id(a, 0, row))), y1 = g_to_dev(ld_var(vars, var_id(a, 1, row)));
+  const Fr x2 = g_to_dev(ld_var(vars, var_id(a, 2, row))), y2 = g_to_dev(ld_var(vars, var_id(a, 3, row)));
+  const Fr one = fe_one<FrP>();
+  const Fr x1y2 = gmul(x1, y2), y1x2 = gmul(y1, x2), y1y2 = gmul(y1, y2), x1x2 = gmul(x1, x2);
+  const Fr k = gmul(gmul(x1y2, y1x2), fr_limbs(a.edwards_d));
+  const Fr den1 = gadd(one, k), den2 = gsub(one, k);
+  const Fr dd = gmul(den1, den2);
+  const Fr inv = fe_inv_dev<FrP>(dd);                  // 0 -> 0: a degenerate pair gets x3 = y3 = 0
+  const Fr x3 = gmul(gmul(gadd(x1y2, y1x2), den2), inv), y3 = gmul(gmul(gadd(y1y2, x1x2), den1), inv);
+  if (!live) return;
+  if (g_is_zero(dd)) gadget_fail(a, proof, rec.index, PM_PLONK_GADGET_DEGENERATE);
+  st_var(vars, var_id(a, 0, row + 1), g_to_abi(x3));
+  st_var(vars, var_id(a, 1, row + 1), g_to_abi(y3));
+  st_var(vars, var_id(a, 3, row + 1), g_to_abi(x1y2));
+}
+
+// extended coordinates: x = X / Z, y = Y / Z, T = X Y / Z
+struct EdPoint {
+  Fr X, Y, Z, T;
+};
+// unified addition for a = -1 (Hisil, Wong, Carter, Dawson 2008): the projective form of the affine law above, with the same
+// exceptional cases -- none on the curve.  9 products.
+PM_DEV EdPoint ed_add(const EdPoint& p, const EdPoint& q, const Fr& d) {
+  const Fr A = gmul(p.X, q.X), B = gmul(p.Y, q.Y), C = gmul(gmul(p.T, q.T), d), D = gmul(p.Z, q.Z);
+  const Fr E = gsub(gsub(gmul(gadd(p.X, p.Y), gadd(q.X, q.Y)), A), B);
+  const Fr F = gsub(D, C), G = gadd(D, C), H = gadd(B, A);
+  return EdPoint{gmul(E, F), gmul(G, H), gmul(F, G), gmul(E, H)};
+}
+// the same with an affine second operand (x, y, t = x y): 8 products
+PM_DEV EdPoint ed_madd(const EdPoint& p, const Fr& x, const Fr& y, const Fr& t, const Fr& d) {
+  const Fr A = gmul(p.X, x), B = gmul(p.Y, y), C = gmul(gmul(p.T, t), d);
+  const Fr E = gsub(gsub(gmul(gadd(p.X, p.Y), gadd(x, y)), A), B);
+  const Fr F = gsub(p.Z, C), G = gadd(p.Z, C), H = gadd(B, A);
+  return EdPoint{gmul(E, F), gmul(G, H), gmul(F, G), gmul(E, H)};
+}
+PM_DEV Fr fr_shfl_up(const Fr& v, u32 delta) {
+  Fr r;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) r.l[i] = __shfl_up(v.l[i], delta);
+  return r;
+}
+PM_DEV EdPoint ed_shfl_up(const EdPoint& p, u32 delta) {
+  return EdPoint{fr_shfl_up(p.X, delta), fr_shfl_up(p.Y, delta), fr_shfl_up(p.Z, delta), fr_shfl_up(p.T, delta)};
+}
+PM_DEV EdPoint ed_sel(bool c, const EdPoint& a, const EdPoint& b) {
+  return EdPoint{g_sel(c, a.X, b.X), g_sel(c, a.Y, b.Y), g_sel(c, a.Z, b.Z), g_sel(c, a.T, b.T)};
+}
+
+constexpr u32 FB_RUN = PM_PLONK_GADGET_MAX_ROUNDS / 64;   // rounds a lane owns at most
+
+// the addend of a round in device form: bit (x_b, y_b) = (bit x_b, bit^2 (y_b - 1) + 1), t = bit x_b y_b; c_abi = t in ABI form
+struct Addend {
+  Fr x, y, t;
+};
+PM_DEV Addend fb_addend(const u32x4* tab, size_t round, int bit, Fr* c_abi) {
+  const Fr xb_abi = ld_canon(tab, 2 * round), xb = g_to_dev(xb_abi), yb = g_to_dev(ld_canon(tab, 2 * round + 1));
+  const Fr t = gmul(xb, yb), one = fe_one<FrP>(), zero = fe_zero<FrP>();
+  if (c_abi) {
+    const Fr c = gmul(xb_abi, yb);                      // ABI x device -> ABI
+    *c_abi = g_sel(bit == 0, zero, g_sel(bit < 0, gneg(c), fe_reduce_weak<FrP>(c)));
+  }
+  Addend r;
+  r.x = g_sel(bit == 0, zero, g_sel(bit < 0, gneg(xb), xb));
+  r.y = g_sel(bit == 0, one, yb);
+  r.t = g_sel(bit == 0, zero, g_sel(bit < 0, gneg(t), t));
+  return r;
+}
+
+// One wave per (gadget, proof): blockIdx.x = the gadget within the launch, blockIdx.y = the proof.  Every branch below that
+// holds field work is wave-uniform (L, `used` and the loop bounds depend on the gadget only).
+__global__ void __launch_bounds__(64) gadget_fixed_base_kernel(const GadgetFill a, u32 first) {
+  const u32 lane = threadIdx.x, proof = blockIdx.y;
+  const GadgetRec rec = a.recs[first + blockIdx.x];
+  u32x4* const vars = a.vars + 2 * a.var_stride * proof;
+  const u32 R = rec.count, L = (R + 63) >> 6, k0 = lane * L, used = (R + L - 1) / L;   // lanes that own a round
+  const size_t row0 = rec.first_row;
+  const Fr d = fr_limbs(a.edwards_d), one = fe_one<FrP>(), zero = fe_zero<FrP>();
+
+  // ---- digits: this lane's rounds k0 .. k0 + L - 1, bit_k = e_(R - 1 - k)
+  u32 s8[8], s9[9], x9[9];
+  g_to_int(ld_canon(vars, rec.in_var[0]), s8);
+  naf_operands(s8, s9, x9);
+  if (lane == 0 && naf_too_long(x9, s9, R)) gadget_fail(a, proof, rec.index, PM_PLONK_GADGET_SCALAR_TOO_LONG);
+  int bit[FB_RUN];
+#pragma unroll
+  for (u32 j = 0; j < FB_RUN; ++j) {
+    const u32 k = k0 + j;
+    bit[j] = (j < L && k < R) ? naf_digit(x9, s9, R - 1 - (k < R ? k : 0)) : 0;
+  }
+  // ---- the start point (a, b of row 0), every lane reads the same words
+  const Fr sx = g_to_dev(ld_var(vars, var_id(a, 0, row0))), sy = g_to_dev(ld_var(vars, var_id(a, 1, row0)));
+  const EdPoint start{sx, sy, one, gmul(sx, sy)}, neutral{zero, one, one, zero};
+
+  // ---- the scalar accumulator d: d_k = (x' >> (R - k + 1)) - (s' >> (R - k + 1)) on x', s' cut to R + 1 bits, then
+  // d_(k+1) = 2 d_k + bit_k along the run; c_k = bit_k x_b y_b on the way
+  {
+    const u32 sh = k0 <= R ? R - k0 + 1 : 1, ws = sh >> 5, bs = sh & 31u;
+    u32 xm[9], sm[9], xs[8], ss[8];
+#pragma unroll
+    for (u32 w = 0; w < 9; ++w) {   // the low R + 1 bits
+      const u32 lo = 32 * w, keep = R + 1;
+      const u32 m = lo + 32 <= keep ? 0xffffffffu : (lo >= keep ? 0u : ((1u << ((keep - lo) & 31u)) - 1u));
+      xm[w] = x9[w] & m;
+      sm[w] = s9[w] & m;
+    }
+#pragma unroll
+    for (u32 i = 0; i < 8; ++i) {
+      const u32 xl = word_at<9>(xm, i + ws), xh = word_at<9>(xm, i + ws + 1);
+      const u32 sl = word_at<9>(sm, i + ws), sh2 = word_at<9>(sm, i + ws + 1);
+      xs[i] = bs ? (xl >> bs) | (xh << (32 - bs)) : xl;
+      ss[i] = bs ? (sl >> bs) | (sh2 << (32 - bs)) : sl;
+    }
+    Fr dk = gsub(g_from_int(xs), g_from_int(ss));
+    if (lane == 0) st_var(vars, var_id(a, 3, row0), zero);                          // d_0 = 0
+    const Fr one_abi = g_one_abi();
+#pragma unroll
+    for (u32 j = 0; j < FB_RUN; ++j) {
+      if (j < L) {
+        const u32 k = k0 + j;
+        const bool valid = k < R;
+        const Fr d2 = gadd(dk, dk);
+        dk = g_sel(bit[j] == 0, d2, g_sel(bit[j] < 0, gsub(d2, one_abi), gadd(d2, one_abi)));
+        if (valid) st_var(vars, var_id(a, 3, row0 + k + 1), dk);
+      }
+    }
+  }
+
+  // ---- first walk: the lane's total (lane 0 starts from the start point) and c_k
+  EdPoint P = ed_sel(lane == 0, start, neutral);
+#pragma unroll
+  for (u32 j = 0; j < FB_RUN; ++j) {
+    if (j < L) {
+      const u32 k = k0 + j;
+      const bool valid = k < R;
+      Fr c;
+      const Addend ad = fb_addend(a.tab, (size_t)rec.tab + (valid ? k : R - 1), bit[j], &c);
+      if (valid) st_var(vars, var_id(a, 2, row0 + k), c);
+      P = ed_madd(P, ad.x, ad.y, ad.t, d);
+    }
+  }
+  // ---- inclusive scan of the lane totals
+#pragma unroll 1
+  for (u32 delta = 1; delta < used; delta <<= 1) {
+    const EdPoint Q = ed_shfl_up(P, delta);
+    const EdPoint S = ed_add(Q, P, d);
+    P = ed_sel(lane >= delta, S, P);
+  }
+  // ---- second walk from the exclusive prefix; X, Y, Z of the run's points are kept for the shared inversion
+  EdPoint Q = ed_shfl_up(P, 1);
+  Q = ed_sel(lane == 0, start, Q);
+  Fr PX[FB_RUN], PY[FB_RUN], PZ[FB_RUN], pre[FB_RUN];
+  Fr prod = one;
+#pragma unroll
+  for (u32 j = 0; j < FB_RUN; ++j) {
+    if (j < L) {
+      const u32 k = k0 + j;
+      const Addend ad = fb_addend(a.tab, (size_t)rec.tab + (k < R ? k : R - 1), bit[j], nullptr);
+      Q = ed_madd(Q, ad.x, ad.y, ad.t, d);
+      PX[j] = Q.X, PY[j] = Q.Y, PZ[j] = Q.Z;
+      pre[j] = prod;
+      prod = gmul(prod, Q.Z);
+    }
+  }
+  Fr inv = fe_inv_dev<FrP>(prod);      // the lane's one inversion; all 64 lanes are here
+#pragma unroll
+  for (int j = FB_RUN - 1; j >= 0; --j) {
+    if ((u32)j < L) {
+      const u32 k = k0 + j;
+      const Fr zi = g_to_abi(gmul(inv, pre[j]));          // 1 / Z_j, ABI form: device x ABI -> ABI below
+      inv = gmul(inv, PZ[j]);
+      if (k < R) {
+        st_var(vars, var_id(a, 0, row0 + k + 1), gmul(PX[j], zi));
+        st_var(vars, var_id(a, 1, row0 + k + 1), gmul(PY[j], zi));
+      }
+    }
+  }
+}
+
+}  // namespace
+
+int gadget_verify(pm_ctx* ctx, const void* d_recs, uint32_t count, size_t n, const void* d_sel6, void* d_tab, uint32_t* d_bad,
+                  hipStream_t st) {
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (!st) st = ctx->stream;
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  PM_HIP(ctx, hipMemsetAsync(d_bad, 0xff, 4, st));
+  hipLaunchKernelGGL(gadget_verify_kernel, dim3(count), dim3(256), 0, st, (const GadgetRec*)d_recs, (const u32x4*)d_sel6, n,
+                     (u32x4*)d_tab, d_bad);
+  PM_HIP(ctx, hipGetLastError());
+  return PM_OK;
+}
+
+int gadget_fill(pm_ctx* ctx, const void* d_recs, const GadgetGroup* groups, size_t n_groups, const void* d_wire_vars, size_t n,
+                const void* d_tab, void* d_vars, size_t var_stride, uint32_t batch, void* d_rep, unsigned long long* rep_host,
+                hipStream_t st) {
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (!st) st = ctx->stream;
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  GadgetFill a;
+  a.recs = (const GadgetRec*)d_recs;
+  a.wire_vars = (const u32*)d_wire_vars;
+  a.tab = (const u32x4*)d_tab;
+  a.vars = (u32x4*)d_vars;
+  a.var_stride = var_stride;
+  a.n = n;
+  a.rep = (unsigned long long*)d_rep;
+  {
+    const host::Field<4>& F = host::FR();   // JubJub d = -(10240 / 10241)
+    const HFr q = host::mul(host::from_u64(10240, F), host::inv(host::from_u64(10241, F), F), F);
+    to_limbs29_shift(a.edwards_d, host::sub(host::zero<4>(), q, F), 1);
+  }
+  PM_HIP(ctx, hipMemsetAsync(d_rep, 0, (size_t)batch * 8, st));
+  PM_HIP(ctx, hipMemsetAsync((char*)d_rep + (size_t)batch * 8, 0xff, (size_t)batch * 8, st));
+  {
+    ProfScope prof(ctx, st, "plonk_gadget_fill");
+    for (size_t i = 0; i < n_groups; ++i) {
+      const GadgetGroup& g = groups[i];
+      const dim3 per_thread((g.count + 63) / 64, batch), per_wave(g.count, batch);
+      switch (g.kind) {
+        case PM_PLONK_GADGET_RANGE:
+          hipLaunchKernelGGL(gadget_range_kernel, per_thread, dim3(64), 0, st, a, g.first, g.count);
+          break;
+        case PM_PLONK_GADGET_LOGIC:
+          hipLaunchKernelGGL(gadget_logic_kernel, per_thread, dim3(64), 0, st, a, g.first, g.count);
+          break;
+        case PM_PLONK_GADGET_FIXED_BASE:
+          hipLaunchKernelGGL(gadget_fixed_base_kernel, per_wave, dim3(64), 0, st, a, g.first);
+          break;
+        default:
+          hipLaunchKernelGGL(gadget_curve_add_kernel, per_thread, dim3(64), 0, st, a, g.first, g.count);
+          break;
+      }
+    }
+  }
+  PM_HIP(ctx, hipGetLastError());
+  if (rep_host) {
+    PM_HIP(ctx, hipMemcpyAsync(rep_host, d_rep, (size_t)batch * 16, hipMemcpyDeviceToHost, st));
+    PM_HIP(ctx, hipStreamSynchronize(st));
+  }
+  return PM_OK;
+}
+
+}  // namespace pm
+
+using namespace pm;
+
+extern "C" int pm_test_host_naf(const uint64_t s[4], uint32_t rounds, int8_t* digits_msb_first, int* too_long) {
+  if (!s || !digits_msb_first || rounds == 0 || rounds > PM_PLONK_GADGET_MAX_ROUNDS) return PM_ERR_BAD_ARG;
+  u32 s8[8], s9[9], x9[9];
+  for (int i = 0; i < 4; ++i) {
+    s8[2 * i] = (u32)s[i];
+    s8[2 * i + 1] = (u32)(s[i] >> 32);
+  }
+  naf_operands(s8, s9, x9);
+  for (u32 k = 0; k < rounds; ++k) digits_msb_first[k] = (int8_t)naf_digit(x9, s9, rounds - 1 - k);
+  if (too_long) *too_long = naf_too_long(x9, s9, rounds) ? 1 : 0;
+  return PM_OK;
+}

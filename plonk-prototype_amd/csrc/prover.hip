@@ -41,8 +41,11 @@ struct ZkState {
 
 // Witness check (pm_plonk_key_enable_check): prover_check.hip.h
 struct CheckState;
+// Gadget witnesses (pm_plonk_key_set_gadgets): prover_gadgets.hip.h
+struct GadgetState;
 namespace {
 void check_state_free(pm_ctx* ctx, CheckState* cs);
+void gadget_state_free(pm_ctx* ctx, GadgetState* gs);
 }
 
 struct pm_prover_key {
@@ -73,6 +76,7 @@ struct pm_prover_key {
   // pm_plonk_preprocess_wires: the wire map (4n x uint32) the permutation was built from; nullptr on a key from sigma_index
   void* wire_vars = nullptr;
   size_t num_vars = 0;
+  GadgetState* gadgets = nullptr;      // pm_plonk_key_set_gadgets
 };
 
 // side stream <- everything submitted on the context's stream so far / the reverse
@@ -125,6 +129,7 @@ extern "C" void pm_plonk_key_free(pm_ctx* ctx, pm_prover_key* pk) {
     delete zs;
   }
   check_state_free(ctx, pk->check);
+  gadget_state_free(ctx, pk->gadgets);
   delete pk;
 }
 
@@ -1001,4 +1006,5 @@ extern "C" int pm_test_plonk_linearise(size_t n, const uint64_t (*evaluations)[4
 
 #include "prover_batch.hip.h"
 #include "prover_check.hip.h"
+#include "prover_gadgets.hip.h"
 #include "prover_dist.hip.h"

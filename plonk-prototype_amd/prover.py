@@ -176,6 +176,76 @@ class UnsatisfiedWitness(ValueError):
         super().__init__(msg)
 
 
+@dataclass(frozen=True)
+class Gadget:
+    """``pm_plonk_gadget``: one widget gadget of a composer-form circuit whose rows ``ProverKey.fill_gadgets`` fills from
+    its input variables (the definitions are in include/plonk_mi355x.h).  Gadgets of one ``level``
+    are independent; levels run in rising order, and a list given to ``ProverKey.set_gadgets`` is sorted by level."""
+    kind: int
+    first_row: int
+    count: int = 0
+    level: int = 0
+    param: int = 0
+    in_vars: tuple = ()
+
+    @classmethod
+    def range(cls, first_row: int, rows: int, value_var: int, level: int = 0) -> "Gadget":
+        """A range check of 8 x rows bits on variable ``value_var``: rows [first_row, first_row + rows] hold the quad accumulators."""
+        return cls(_lib.PLONK_GADGET_RANGE, int(first_row), int(rows), int(level), 0, (int(value_var),))
+
+    @classmethod
+    def logic(cls, first_row: int, quads: int, a_var: int, b_var: int, xor: bool = False, level: int = 0) -> "Gadget":
+        """AND (or XOR) of the low 2 x quads bits of two variables: rows [first_row, first_row + quads]."""
+        return cls(_lib.PLONK_GADGET_LOGIC, int(first_row), int(quads), int(level), 1 if xor else 0, (int(a_var), int(b_var)))
+
+    @classmethod
+    def fixed_base(cls, first_row: int, rounds: int, scalar_var: int, level: int = 0) -> "Gadget":
+        """JubJub fixed-base scalar multiplication in ``rounds`` <= 256 rounds: rows [first_row, first_row + rounds]; the
+        start point is read from a, b of the first row, the table points are the key's q_l, q_r."""
+        return cls(_lib.PLONK_GADGET_FIXED_BASE, int(first_row), int(rounds), int(level), 0, (int(scalar_var),))
+
+    @classmethod
+    def curve_add(cls, first_row: int, level: int = 0) -> "Gadget":
+        """JubJub addition of the points in a b and c d of ``first_row``; the sum goes to a b of the next row."""
+        return cls(_lib.PLONK_GADGET_CURVE_ADD, int(first_row), 0, int(level), 0, ())
+
+    def _raw(self) -> "_lib.Gadget":
+        iv = tuple(self.in_vars) + (_lib.PLONK_NO_VAR,) * (2 - len(self.in_vars))
+        return _lib.Gadget(self.kind, self.level, self.first_row, self.count, self.param, (C.c_uint32 * 2)(*iv))
+
+
+@dataclass
+class GadgetReport:
+    """``pm_plonk_gadget_report`` of one assignment: how many gadgets' inputs did not fit, the lowest such gadget (its index
+    in the list given to ``set_gadgets``) and why (``_lib.PLONK_GADGET_REASONS``)."""
+    ok: bool
+    failed: int
+    first_gadget: int | None
+    first_reason: str | None
+
+    @classmethod
+    def _from_raw(cls, raw) -> "GadgetReport":
+        failed = int(raw.failed)
+        return cls(ok=failed == 0, failed=failed, first_gadget=int(raw.first_gadget) if failed else None,
+                   first_reason=_lib.PLONK_GADGET_REASONS.get(int(raw.first_reason)) if failed else None)
+
+
+class GadgetInputError(ValueError):
+    """``fill=True``: an input does not fit its gadget (a value too wide for its range, a scalar with too many digits, a
+    degenerate addition); nothing was proved or checked.  ``reports``: {proof: GadgetReport} of the failing assignments."""
+
+    def __init__(self, reports: dict, gadgets=None):
+        self.reports = dict(reports)
+        self.report = self.reports[min(self.reports)]
+
+        def one(b, r):
+            kind = ""
+            if gadgets is not None and r.first_gadget is not None and r.first_gadget < len(gadgets):
+                kind = f" ({_lib.PLONK_GADGET_KINDS[gadgets[r.first_gadget].kind]} at row {gadgets[r.first_gadget].first_row})"
+            return f"proof {b}: gadget {r.first_gadget}{kind}: {r.first_reason}; {r.failed} failing gadget(s)"
+        super().__init__("; ".join(one(b, r) for b, r in sorted(self.reports.items())))
+
+
 class ProverKey:
     """``pm_prover_key``: selector and sigma polynomials as coefficients and on the 4n coset, the coset
     points, L_1, 1/Z_H and the per-proof workspace -- built and owned by the library, all in HBM."""
@@ -206,6 +276,7 @@ class ProverKey:
             self._sigma_index = idx             # the check (enable_check) takes the permutation again: the key keeps sigma's values
         self._h = h
         self._check_enabled = False
+        self.gadgets: list = []                 # set_gadgets
         self.verifier_key: dict | None = None
         self.label = b"plonk"
 
@@ -216,11 +287,55 @@ class ProverKey:
             self._sigma_index = sigma_from_wires(self.wire_vars, self.num_vars, self.ctx).reshape(-1)
         return self._sigma_index
 
-    def witness_from_variables(self, variables) -> DeviceVector:
+    def set_gadgets(self, gadgets) -> int:
+        """Give the key its gadget table (``pm_plonk_key_set_gadgets``; a key built from ``wire_vars``): a list of
+        :class:`Gadget` sorted by level, checked on the device against the key's selectors.  Replaces an earlier table; an
+        empty list clears it.  -> the device bytes the table holds."""
+        gadgets = list(gadgets)
+        raw = (_lib.Gadget * max(len(gadgets), 1))(*[g._raw() for g in gadgets])
+        out = C.c_size_t()
+        self.ctx._check(self.ctx._lib.pm_plonk_key_set_gadgets(self.ctx._h, self._h, raw if gadgets else None, len(gadgets),
+                                                               C.byref(out)))
+        self.gadgets = gadgets
+        return int(out.value)
+
+    def _fill_device(self, d_ptr, B: int, stride: int) -> list:
+        """``pm_plonk_fill_gadgets_dev`` on B assignments in device memory -> one GadgetReport each."""
+        raws = (_lib.GadgetReport * B)()
+        self.ctx._check(self.ctx._lib.pm_plonk_fill_gadgets_dev(self.ctx._h, self._h, d_ptr, stride, B, raws, None))
+        return [GadgetReport._from_raw(raws[b]) for b in range(B)]
+
+    def fill_gadgets(self, variables):
+        """Fill the variables the key's gadgets define from their inputs, on the device (``set_gadgets`` first).  variables:
+        host [num_vars, 4] Montgomery limbs -> the filled array; a list of B of them -> [B, num_vars, 4]; a DeviceVector of
+        B x num_vars elements -> the same vector, filled in place.  Only the inputs need real values: gadget inputs, the
+        start points of fixed-base gadgets and what the arithmetic gates use.  -> (filled, [GadgetReport] x B); a failing
+        gadget has written the values of its input cut to the width it has."""
+        ctx, nv = self.ctx, self.num_vars
+        if self.wire_vars is None:
+            raise ValueError("the key was not built from wire variables")
+        if isinstance(variables, DeviceVector):
+            if nv == 0 or variables.n == 0 or variables.n % nv:
+                raise ValueError("device variables must hold a positive multiple of num_vars elements")
+            return variables, self._fill_device(variables._p, variables.n // nv, nv)
+        single = not isinstance(variables, (list, tuple))
+        a = np.stack([np.asarray(v, dtype=np.uint64).reshape(nv, 4) for v in ([variables] if single else variables)])
+        B = a.shape[0]
+        d_vars = DeviceVector.from_host(ctx, np.ascontiguousarray(a).reshape(B * nv, 4))
+        try:
+            reports = self._fill_device(d_vars._p, B, nv)
+            out = d_vars.to_host().reshape(B, nv, 4)
+        finally:
+            d_vars.free()
+        return (out[0] if single else out), reports
+
+    def witness_from_variables(self, variables, fill: bool = False) -> DeviceVector:
         """Expand variable assignments into witnesses on the device (``pm_plonk_witness_from_vars_dev``; a key built from
         ``wire_vars``).  variables: host [num_vars, 4] Montgomery limbs, a list of B of them, or a DeviceVector of
         B x num_vars elements.  -> a DeviceVector of B x 4n elements, proof-major: w[b][j n + i] = variables[b][wire_vars[j, i]],
-        zero at ``PLONK_NO_VAR`` positions.  Values are copied as they are."""
+        zero at ``PLONK_NO_VAR`` positions.  Values are copied as they are.  fill: run the key's gadgets on the assignments
+        first (``fill_gadgets``; a DeviceVector is filled in place) and raise :class:`GadgetInputError` when an input does
+        not fit."""
         ctx, n = self.ctx, self.n
         if self.wire_vars is None:
             raise ValueError("the key was not built from wire variables")
@@ -238,11 +353,17 @@ class ProverKey:
                 raise ValueError("empty batch")
             B = a.shape[0]
             d_vars, own = DeviceVector.from_host(ctx, np.ascontiguousarray(a).reshape(B * nv, 4)), True
-        out = DeviceVector(ctx, B * 4 * n)
+        out = None
         try:
+            if fill:
+                bad = {b: r for b, r in enumerate(self._fill_device(d_vars._p, B, nv)) if not r.ok}
+                if bad:
+                    raise GadgetInputError(bad, self.gadgets)
+            out = DeviceVector(ctx, B * 4 * n)
             ctx._check(ctx._lib.pm_plonk_witness_from_vars_dev(ctx._h, self._h, d_vars._p, nv, B, out._p, None))
         except Exception:
-            out.free()
+            if out is not None:
+                out.free()
             raise
         finally:
             if own:
@@ -308,14 +429,17 @@ class ProverKey:
                                                          rows.ctypes.data_as(C.POINTER(C.c_uint8)) if masks else None))
         return [WitnessReport._from_raw(raws[b], rows[b] if masks else None) for b in range(B)]
 
-    def check_witness(self, witness=None, public_inputs=None, masks: bool = False, variables=None) -> WitnessReport:
+    def check_witness(self, witness=None, public_inputs=None, masks: bool = False, variables=None,
+                      fill: bool = False) -> WitnessReport:
         """Does the witness satisfy the circuit?  One ``pm_plonk_check_witness`` call (``enable_check`` first): every gate
         identity and copy constraint on every row, on the GPU.  witness (or variables) and
-        public_inputs as for ``prove``; masks: also return every row's mask (``WitnessReport.row_masks``)."""
+        public_inputs as for ``prove``; masks: also return every row's mask (``WitnessReport.row_masks``); fill (with
+        variables): fill the key's gadgets on the device first, as ``prove`` does."""
         ctx, n = self.ctx, self.n
         _one_form(witness, variables, "witness")
+        _fill_needs_variables(fill, variables)
         if variables is not None:
-            d_wit, own = _single(self.witness_from_variables(variables), n), True
+            d_wit, own = _single(self.witness_from_variables(variables, fill), n), True
         elif isinstance(witness, DeviceVector):
             if witness.n != 4 * n:
                 raise ValueError("device witness must hold 4n elements")
@@ -334,15 +458,17 @@ class ProverKey:
                 d_wit.free()
         return WitnessReport._from_raw(raw, rows)
 
-    def check_witnesses(self, witnesses=None, public_inputs=None, masks: bool = False, variables=None) -> list:
+    def check_witnesses(self, witnesses=None, public_inputs=None, masks: bool = False, variables=None,
+                        fill: bool = False) -> list:
         """``check_witness`` for B witnesses of the circuit in one ``pm_plonk_check_witness_batch`` call (B <= 64).  witnesses:
         one DeviceVector of B x 4n elements (proof-major) or a list of host arrays [4, n, 4]; or variables: what
         ``witness_from_variables`` takes; public_inputs: None or a list of B entries as for ``prove``.  -> one report per
-        witness, each equal to the single call's."""
+        witness, each equal to the single call's.  fill (with variables): fill the key's gadgets on the device first."""
         ctx, n = self.ctx, self.n
         _one_form(witnesses, variables, "witnesses")
+        _fill_needs_variables(fill, variables)
         if variables is not None:
-            d_wit, own = self.witness_from_variables(variables), True
+            d_wit, own = self.witness_from_variables(variables, fill), True
             B = d_wit.n // (4 * n)
         elif isinstance(witnesses, DeviceVector):
             if witnesses.n % (4 * n) or witnesses.n == 0:
@@ -550,6 +676,11 @@ def _one_form(witness, variables, name: str):
         raise ValueError(f"give exactly one of {name} and variables")
 
 
+def _fill_needs_variables(fill: bool, variables):
+    if fill and variables is None:
+        raise ValueError("fill=True works on variables")
+
+
 def _single(d_wit: DeviceVector, n: int) -> DeviceVector:
     if d_wit.n != 4 * n:
         d_wit.free()
@@ -619,7 +750,7 @@ def random_blinders(count: int | None = None) -> np.ndarray:
 
 
 def prove(pk: ProverKey, ck: CommitKey, witness=None, public_inputs=None, bind_public_inputs: bool = True,
-          zero_knowledge: bool = False, blinders=None, check: bool = False, variables=None) -> Proof:
+          zero_knowledge: bool = False, blinders=None, check: bool = False, variables=None, fill: bool = False) -> Proof:
     """``Prover::prove_with_preprocessed``: one ``pm_plonk_prove`` call.
 
     check: run ``ProverKey.check_witness`` first (the key is made ready on first use) and raise
@@ -628,7 +759,10 @@ def prove(pk: ProverKey, ck: CommitKey, witness=None, public_inputs=None, bind_p
 
     witness: [4, n, 4] wire values (a, b, c, d rows) in Montgomery limbs, or a DeviceVector of 4n elements
     already in HBM.  variables (instead of witness, on a key built from ``wire_vars``): one assignment per variable,
-    [num_vars, 4] or a DeviceVector, expanded on the device (``ProverKey.witness_from_variables``).  public_inputs:
+    [num_vars, 4] or a DeviceVector, expanded on the device (``ProverKey.witness_from_variables``).  fill (with
+    variables, ``ProverKey.set_gadgets`` first): only the inputs of the variables need values; the gadgets' internal
+    variables are computed on the device between the upload and the expansion (``ProverKey.fill_gadgets``), and
+    :class:`GadgetInputError` names proof, gadget and reason when an input does not fit.  public_inputs:
     dense [n, 4] evaluations of PI on H, or a (positions, values) pair, or None.
     bind_public_inputs: absorb the public inputs into the transcript before round 1 (dusk-plonk 0.8.2 does
     not; False reproduces the restated upstream transcript).
@@ -644,6 +778,7 @@ def prove(pk: ProverKey, ck: CommitKey, witness=None, public_inputs=None, bind_p
     proofs of different witnesses gives the witness away."""
     ctx, n = pk.ctx, pk.n
     _one_form(witness, variables, "witness")
+    _fill_needs_variables(fill, variables)
     if ck.max_degree() + 1 < n:
         raise ValueError("commit key shorter than the circuit")
     if blinders is not None and not zero_knowledge:
@@ -657,7 +792,7 @@ def prove(pk: ProverKey, ck: CommitKey, witness=None, public_inputs=None, bind_p
     if pk.verifier_key is None:
         pk.commit(ck)
     if variables is not None:
-        d_wit, own = _single(pk.witness_from_variables(variables), n), True
+        d_wit, own = _single(pk.witness_from_variables(variables, fill), n), True
     elif isinstance(witness, DeviceVector):
         if witness.n != 4 * n:
             raise ValueError("device witness must hold 4n elements")
@@ -711,7 +846,7 @@ def _pi_pairs(public_inputs) -> tuple[np.ndarray, np.ndarray]:
 
 def prove_batch(pk: ProverKey, ck: CommitKey, witnesses=None, public_inputs=None, bind_public_inputs: bool = True,
                 workspace: BatchWorkspace | None = None, zero_knowledge: bool = False, blinders=None,
-                check: bool = False, variables=None) -> list[Proof]:
+                check: bool = False, variables=None, fill: bool = False) -> list[Proof]:
     """B proofs of one circuit in one ``pm_plonk_prove_batch`` call; proof b equals ``prove(pk, ck, witness b, public
     inputs b)`` byte for byte.
 
@@ -727,7 +862,8 @@ def prove_batch(pk: ProverKey, ck: CommitKey, witnesses=None, public_inputs=None
     per-proof witnesses -- DeviceVectors of 4n elements, copied device to device into the workspace's staging (one copy
     kernel per proof, 4n x 64 bytes of traffic each), or host arrays [4, n, 4], uploaded there.  variables (instead of
     witnesses, on a key built from ``wire_vars``): a list of B assignments [num_vars, 4] or a DeviceVector of B x num_vars
-    elements, expanded on the device (``ProverKey.witness_from_variables``).  public_inputs: None, or a
+    elements, expanded on the device (``ProverKey.witness_from_variables``); fill: as for ``prove``, one fill for the
+    batch.  public_inputs: None, or a
     list of B entries in any form ``prove`` takes (None, dense [n, 4], a (positions, values) pair).  workspace: a
     ``ProverKey.batch`` workspace with max_batch >= B; None makes one for the call.
 
@@ -735,6 +871,7 @@ def prove_batch(pk: ProverKey, ck: CommitKey, witnesses=None, public_inputs=None
     failing members (``.reports``: {b: report}) instead of proving; satisfied batches give the same bytes as without it."""
     ctx, n = pk.ctx, pk.n
     _one_form(witnesses, variables, "witnesses")
+    _fill_needs_variables(fill, variables)
     if ck.max_degree() + 1 < n:
         raise ValueError("commit key shorter than the circuit")
     if blinders is not None and not zero_knowledge:
@@ -752,7 +889,7 @@ def prove_batch(pk: ProverKey, ck: CommitKey, witnesses=None, public_inputs=None
             variables = list(variables)
             if not variables:
                 raise ValueError("empty batch")
-        witnesses = expanded = pk.witness_from_variables(variables)
+        witnesses = expanded = pk.witness_from_variables(variables, fill)
     if isinstance(witnesses, DeviceVector):
         if witnesses.n % (4 * n) or witnesses.n == 0:
             raise ValueError("a batch of device witnesses must hold a positive multiple of 4n elements")
