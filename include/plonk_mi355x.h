@@ -849,6 +849,11 @@ int pm_test_msm_plan(size_t n, uint32_t batch, long window_bits, uint32_t table_
  * a kernel, log2 group size of the blocked intermediate layout, 0}. */
 int pm_test_ntt_plan(uint32_t log_n, uint32_t batch, long tile_log, long max_radix, long radix, uint32_t num_cus,
                      uint32_t out[20]);
+/* The radix-4 step table of radix 2^S (2 <= S <= 10) of one direction as the pass kernels read it, built on first use:
+ * seven head constants of 84 words (w4, then w16^e for e = 1, 2, 3, 6, 9, 0; word 9 b + j = limb b of w 2^(29 (j - 7)) mod r,
+ * w in the device Montgomery form), then 20 words per step-twiddle entry.  *words = its size in 32-bit words (may be
+ * NULL); up to max_words of them are copied to out. */
+int pm_test_ntt_step4_table(pm_ctx* ctx, uint32_t inverse, uint32_t S, uint32_t* out, size_t max_words, size_t* words);
 /* Pure host, no context: the geometry of pm_plonk_sigma_from_wires' sort (csrc/wire_perm.hip) -- passes =
  * max(1, ceil(bits(num_vars - 1) / 8)) 8-bit digit passes, tiles = ceil(4n / 4096) workgroups per pass, scratch_bytes = the
  * transient device memory of the call.  Each out pointer may be NULL.  The errors of pm_plonk_sigma_from_wires for n and

@@ -51,6 +51,7 @@ static pass_fn find_pass(int S, int LT, int role) {
 size_t pass4_lds(int S, int LT);
 unsigned pass4_threads(int S, int LT);
 int build_step4_table(pm_ctx* ctx, void** out, const NttConsts& c, unsigned S, hipStream_t st);
+size_t step4_table_bytes(unsigned S);
 
 struct Plan {
   int npass = 0;
@@ -162,12 +163,15 @@ static int get_step4_table(pm_ctx* ctx, int dir, unsigned S, void** out, hipStre
   }
   HFr wR = domain_gen(S);
   if (dir) wR = host::inv(wR, host::FR());
-  HFr w4 = domain_gen(2);   // the table starts with the split rows of this direction's w4
+  HFr w4 = domain_gen(2);   // the table starts with the split rows of this direction's w4 and of the powers of its w16
+  HFr w16 = domain_gen(4);
   if (dir) w4 = host::inv(w4, host::FR());
+  if (dir) w16 = host::inv(w16, host::FR());
   NttConsts c;
   memset(&c, 0, sizeof c);
   to_limbs(c.w8[0], wR);
   to_limbs(c.w8[1], w4);
+  to_limbs(c.w8[2], w16);
   to_limbs(c.one, host::one(host::FR()));
   void* d = nullptr;
   int rc = build_step4_table(ctx, &d, c, S, st);
@@ -598,6 +602,26 @@ extern "C" int pm_test_ntt_plan(uint32_t log_n, uint32_t batch, long tile_log, l
     if ((r4 ? find_pass4(S, LT, role) : find_pass(S, LT, role)) != nullptr) out[17] |= 1u << i;
   }
   out[18] = plan.npass ? plan_wide_glog(plan) : 0u;
+  return PM_OK;
+}
+
+// test hook: the radix-4 step table of radix 2^S (head, then entries) as the kernels read it, built on first use like
+// any transform's.  *words = its size in 32-bit words; up to max_words of them are copied to out.
+extern "C" int pm_test_ntt_step4_table(pm_ctx* ctx, uint32_t inverse, uint32_t S, uint32_t* out, size_t max_words,
+                                       size_t* words) {
+  if (!ctx || inverse > 1 || S < 2 || S > 10 || (!out && max_words)) return PM_ERR_BAD_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  OrderScope order_scope(ctx, ctx->ord_ntt, ctx->stream);
+  if (order_scope.rc) return order_scope.rc;
+  void* tab = nullptr;
+  int rc = get_step4_table(ctx, (int)inverse, S, &tab, ctx->stream);
+  if (rc) return rc;
+  const size_t total = step4_table_bytes(S) / 4;
+  if (words) *words = total;
+  const size_t n = std::min(total, max_words);
+  if (n) PM_HIP(ctx, hipMemcpyAsync(out, tab, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return PM_OK;
 }
 

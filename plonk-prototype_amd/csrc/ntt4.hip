@@ -37,11 +37,17 @@ pass_fn find_pass4(int S, int LT, int role) {
 size_t pass4_lds(int S, int LT) { return pass4_lds_bytes(S, LT); }
 unsigned pass4_threads(int S, int LT) { return std::max(64u, (1u << (S + LT)) / 4); }
 
+// the head (w4 and the powers of w16, nine rows each) in front, then 80 B per entry
+size_t step4_table_bytes(unsigned S) {
+  return ((size_t)STEP4_HEAD + (size_t)step4_tw_total((int)S) * STEP4_ENTRY) * sizeof(u32x4);
+}
+
 int build_step4_table(pm_ctx* ctx, void** out, const NttConsts& c, unsigned S, hipStream_t st) {
   const u32 total = (u32)step4_tw_total((int)S);
-  // the w4 rows in front, then 80 B per entry; at least one block, so that the head is written for every S
-  PM_HIP(ctx, hipMalloc(out, ((size_t)STEP4_HEAD + (size_t)total * STEP4_ENTRY) * sizeof(u32x4)));
-  hipLaunchKernelGGL(step4_tw_kernel, dim3((std::max(total, 9u) + 255) / 256), dim3(256), 0, st, (u32x4*)*out, c, S);
+  // at least the threads of the head, so that it is written for every S
+  PM_HIP(ctx, hipMalloc(out, step4_table_bytes(S)));
+  hipLaunchKernelGGL(step4_tw_kernel, dim3((std::max(total, 9u * STEP4_HEAD_CONSTS) + 255) / 256), dim3(256), 0, st,
+                     (u32x4*)*out, c, S);
   PM_HIP(ctx, hipGetLastError());
   return PM_OK;
 }

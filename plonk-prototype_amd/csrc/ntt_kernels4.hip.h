@@ -25,16 +25,42 @@ __host__ __device__ constexpr size_t pass4_lds_bytes(int S, int LT) {
   return num_steps4(S) > 1 ? ((size_t)36 << (S + LT)) : 0;
 }
 
-// ---- step table of the radix-4 kernels: [w4 rows | entries] ------------------------------------------------
-// Head, 84 words: w4 for fe_mul_split<1, 2>, transposed: word 9 b + j = limb b of row_j = w4 2^(29 (j - 7)) mod r, so
-// the nine constants of column b are neighbours.  It is read through the constant address space: wave-uniform
+// ---- step table of the radix-4 kernels: [head: seven wave-uniform constants | entries] ---------------------
+// Head, seven blocks of 84 words: block 0 is w4 = w16^4, blocks 1..6 are w16^e for e = 1, 2, 3, 6, 9, 0 (w16 = wR^(R/16) of
+// the table's direction; the first-layer step twiddles w16^(t m), see L1_UNIFORM below).  A block holds its constant for
+// fe_mul_split<1, 2>, transposed: word 9 b + j = limb b of row_j = w 2^(29 (j - 7)) mod r, so the nine constants of
+// column b are neighbours; words 81..83 are padding.  The head is read through the constant address space: wave-uniform
 // addresses there are scalar loads, the limb is the scalar operand of its v_mad_u64_u32 and no VGPR holds it.
 // Entries, 80 B each: limbs of row_0 = w 2^-87, then of row_1 = w 2^58 (fe_mul_split<5, 6>), two words of padding.
-constexpr int STEP4_HEAD = 21;   // u32x4 units in front of entry 0
+constexpr int STEP4_HEAD_CONSTS = 7;
+constexpr int STEP4_HEAD_BLOCK = 84;                                   // words per head constant
+constexpr int STEP4_HEAD = STEP4_HEAD_CONSTS * STEP4_HEAD_BLOCK / 4;   // u32x4 units in front of entry 0
 constexpr int STEP4_ENTRY = 5;   // u32x4 units per entry
+__host__ __device__ constexpr int step4_head_exp(int blk) { return blk == 0 ? 4 : blk == 4 ? 6 : blk == 5 ? 9 : blk == 6 ? 0 : blk; }
 typedef const __attribute__((address_space(4))) u32* W4Rows;
 PM_DEV W4Rows w4_rows(const u32x4* step_tw) {
   return (W4Rows)(reinterpret_cast<const u32*>(step_tw));
+}
+// head block of w16^e, e = t m with t in 1..3, m in 0..3: a nibble per exponent (0, 1, 2, 3, 4, 6, 9 -> 6, 1, 2, 3, 0, 4, 5)
+PM_DEV W4Rows w16_rows(W4Rows head, u32 e) {
+  return head + STEP4_HEAD_BLOCK * (u32)((0x5004003216ull >> (4 * e)) & 15u);
+}
+// x * w for a head constant (w4_rows / w16_rows): x (B < 6, any V the limbs allow) -> (1, <2), 97 limb products
+PM_DEV Fr mul_head(const Fr& x, W4Rows rows) {
+  return fe_mul_split<FrP, 1, 2>(x, [&](int j, int b) { return rows[9 * b + j]; });
+}
+
+// First-layer step twiddles applied by their producer.  Step 1 of a pass multiplies its input m by w16^(k' m), k' = u & 3:
+// lane-varying there.  Step 0's thread u wrote that input as X[t] to slot 4u + t = m U + u' with k' = t, so the factor owed
+// to X[t] is w16^(t m) with m = u >> (log2 U - 2): t is a compile-time index and m is the same for all of a wave when the
+// wave's 64 >> LT values of u stay inside one aligned block of U/4.  Then step 0 applies it through the head's scalar
+// rows (97 limb products, no VGPR, no vector load) and step 1 takes its inputs from the LDS as they are.  The waves with
+// m = 0 multiply by w16^0 = 1 like the others: a branch around their products (fe_reduce_weak instead) measured slower,
+// every wave of the workgroup meets the same barrier.  Step 0 is never u-fast when a second step follows it (u-fast
+// belongs to a pass's last step).  Only passes that read the wide form (middle and last) take this path: the first and
+// single passes, whose step 0 follows the loads from HBM directly, measured 1 - 2 us slower per launch with it.
+__host__ __device__ constexpr bool step4_l1_uniform(int S, int LT, bool in_wide) {
+  return in_wide && num_steps4(S) >= 2 && step4_radix_log(S, 1) == 2 && (64 >> LT) <= ((1 << S) >> 4);
 }
 struct FrSplit2 {
   u32 l[18];
@@ -59,7 +85,7 @@ PM_DEV Fr mul_tw2(const Fr& x, const FrSplit2& w) {
 PM_DEV void dft4s(Fr& a0, Fr& a1, Fr& a2, Fr& a3, W4Rows w4) {
   BFLY(3, a0, a2);  // a0 (2+, <26)  a2 (4+, <27)
   BFLY(3, a1, a3);  // a1 (2, 4)     a3 (4, 5)
-  a3 = fe_mul_split<FrP, 1, 2>(a3, [&](int j, int b) { return w4[9 * b + j]; });
+  a3 = mul_head(a3, w4);
   a2 = fe_norm<FrP>(a2);
   BFLY(5, a0, a1);  // a0 = X0, a1 = X2
   BFLY(3, a2, a3);  // a2 = X1, a3 = X3
@@ -68,7 +94,7 @@ PM_DEV void dft4s(Fr& a0, Fr& a1, Fr& a2, Fr& a3, W4Rows w4) {
   a2 = t;
 }
 
-template <int S, int LT, int STEP, bool OUT_UFAST, bool OUT_WIDE>
+template <int S, int LT, int STEP, bool OUT_UFAST, bool IN_WIDE, bool OUT_WIDE>
 PM_DEV void ntt_step4(Fr (&x)[4], const NttPassArgs& a, const NttConsts& kc, u32x4* lds0, u32x4* lds1, u32* lds2,
                       W4Rows w4, u32 tid, size_t j0) {
   constexpr int R = 1 << S;
@@ -79,6 +105,8 @@ PM_DEV void ntt_step4(Fr (&x)[4], const NttPassArgs& a, const NttConsts& kc, u32
   constexpr u32 nsp = 1u << (2 * STEP);  // Ns'
   constexpr bool last = (STEP == NSTEPS - 1);
   constexpr bool ufast = OUT_UFAST && last;
+  constexpr bool L1_UNIFORM = step4_l1_uniform(S, LT, IN_WIDE);
+  static_assert(!(L1_UNIFORM && STEP == 0 && ufast), "the producer of the first-layer twiddles is in wave order");
   const u32 c = ufast ? tid / U : tid & (T - 1);
   const u32 u = ufast ? tid % U : tid >> LT;
   if (STEP > 0) {
@@ -94,17 +122,30 @@ PM_DEV void ntt_step4(Fr (&x)[4], const NttPassArgs& a, const NttConsts& kc, u32
   const u32x4* stw = a.step_tw + STEP4_HEAD + STEP4_ENTRY * step4_tw_offset(S, STEP);
   if constexpr (LQ == 2) {
     const u32 kp = u & (nsp - 1);
-    if (STEP > 0) {
+    if (STEP > 0 && !(L1_UNIFORM && STEP == 1)) {
       x[0] = fe_reduce_weak<FrP>(x[0]);
       x[1] = mul_tw2(x[1], ld_tw2(stw, 0 * nsp + kp));
       x[2] = mul_tw2(x[2], ld_tw2(stw, 1 * nsp + kp));
       x[3] = mul_tw2(x[3], ld_tw2(stw, 2 * nsp + kp));
     }
+    // L1_UNIFORM, step 1: step 0 left x[0] at (1, <1.01) and x[1..3] at (1, <2), the classes dft4s takes
     // every step reads the w4 rows anew (scalar loads, a column at a time): an opaque copy of the pointer, or the
     // rows of step 0 stay in 81 SGPRs for the whole kernel and spill
     W4Rows w4s = w4;
     asm volatile("" : "+s"(w4s));
     dft4s(x[0], x[1], x[2], x[3], w4s);  // X[t] in x[t]
+    if constexpr (L1_UNIFORM && STEP == 0) {
+      // what step 1 owes its inputs, here: X[0] (<5, <40) -> (1, <1.01); X[t] (<5, <40) times w16^(t m) -> (1, <2).  The
+      // rows of each product through an opaque pointer of its own, as above.
+      const u32 m = __builtin_amdgcn_readfirstlane(u >> (S - 4));
+      x[0] = fe_reduce_weak<FrP>(x[0]);
+#pragma unroll
+      for (int t = 1; t < 4; ++t) {
+        W4Rows rows = w16_rows(w4, t * m);
+        asm volatile("" : "+s"(rows));
+        x[t] = mul_head(x[t], rows);
+      }
+    }
     if constexpr (!last) {
       __syncthreads();
       const u32 base = (u - kp) * 4 + kp;
@@ -214,26 +255,29 @@ __global__ void __launch_bounds__((1 << (S + LT)) / 4 < 64 ? 64 : (1 << (S + LT)
       }
     }
   }
-  ntt_step4<S, LT, 0, OUT_UFAST, OUT_WIDE>(x, a, kc, lds0, lds1, lds2, w4, tid, j0);
-  if constexpr (NSTEPS > 1) ntt_step4<S, LT, 1, OUT_UFAST, OUT_WIDE>(x, a, kc, lds0, lds1, lds2, w4, tid, j0);
-  if constexpr (NSTEPS > 2) ntt_step4<S, LT, 2, OUT_UFAST, OUT_WIDE>(x, a, kc, lds0, lds1, lds2, w4, tid, j0);
-  if constexpr (NSTEPS > 3) ntt_step4<S, LT, 3, OUT_UFAST, OUT_WIDE>(x, a, kc, lds0, lds1, lds2, w4, tid, j0);
-  if constexpr (NSTEPS > 4) ntt_step4<S, LT, 4, OUT_UFAST, OUT_WIDE>(x, a, kc, lds0, lds1, lds2, w4, tid, j0);
-  if constexpr (NSTEPS > 5) ntt_step4<S, LT, 5, OUT_UFAST, OUT_WIDE>(x, a, kc, lds0, lds1, lds2, w4, tid, j0);
+  ntt_step4<S, LT, 0, OUT_UFAST, IN_WIDE, OUT_WIDE>(x, a, kc, lds0, lds1, lds2, w4, tid, j0);
+  if constexpr (NSTEPS > 1) ntt_step4<S, LT, 1, OUT_UFAST, IN_WIDE, OUT_WIDE>(x, a, kc, lds0, lds1, lds2, w4, tid, j0);
+  if constexpr (NSTEPS > 2) ntt_step4<S, LT, 2, OUT_UFAST, IN_WIDE, OUT_WIDE>(x, a, kc, lds0, lds1, lds2, w4, tid, j0);
+  if constexpr (NSTEPS > 3) ntt_step4<S, LT, 3, OUT_UFAST, IN_WIDE, OUT_WIDE>(x, a, kc, lds0, lds1, lds2, w4, tid, j0);
+  if constexpr (NSTEPS > 4) ntt_step4<S, LT, 4, OUT_UFAST, IN_WIDE, OUT_WIDE>(x, a, kc, lds0, lds1, lds2, w4, tid, j0);
+  if constexpr (NSTEPS > 5) ntt_step4<S, LT, 5, OUT_UFAST, IN_WIDE, OUT_WIDE>(x, a, kc, lds0, lds1, lds2, w4, tid, j0);
 }
 
 // step twiddles of the radix-4 kernel: block s, entry [(t-1)*Ns' + k'] = wR^(k' t R/(Ns' q)), Ns' = 4^s, both rows
-// of each (canonical limbs); the first nine threads also write the rows of w4 = c.w8[1] into the head.
+// of each (canonical limbs); the first 63 threads also write the head: nine rows each of w4 = c.w8[1] and of the six
+// powers of w16 = c.w8[2].
 // Multiplying by 2^e in Montgomery form (fe_pow2<261 + e>) is the shift by e: 261 - 87 = 174, 261 + 58 = 319.
 static __global__ void step4_tw_kernel(u32x4* out, const NttConsts c, u32 S) {
   const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < 9) {  // row_i = w4 2^(29 (i - 7)): 2^(29 (i + 2)) in Montgomery form, walked up from 2^58
+  if (i < 9 * STEP4_HEAD_CONSTS) {  // row_j = w 2^(29 (j - 7)): 2^(29 (j + 2)) in Montgomery form, walked up from 2^58
+    const u32 blk = i / 9, j = i % 9;
+    const Fr w = blk == 0 ? fr_limbs(c.w8[1]) : fr_pow(fr_limbs(c.w8[2]), (u32)step4_head_exp((int)blk), fr_limbs(c.one));
     Fr p = fe_pow2<FrP, 58>();
-    for (u32 k = 0; k < i; ++k) p = fe_mul<FrP>(p, fe_pow2<FrP, 261 + 29>());
-    const Fr row = fr_canon(fe_mul<FrP>(fr_limbs(c.w8[1]), p));
-    u32* head = reinterpret_cast<u32*>(out);
-    for (u32 b = 0; b < 9; ++b) head[9 * b + i] = row.l[b];
-    if (i < 3) head[81 + i] = 0u;
+    for (u32 k = 0; k < j; ++k) p = fe_mul<FrP>(p, fe_pow2<FrP, 261 + 29>());
+    const Fr row = fr_canon(fe_mul<FrP>(w, p));
+    u32* head = reinterpret_cast<u32*>(out) + STEP4_HEAD_BLOCK * blk;
+    for (u32 b = 0; b < 9; ++b) head[9 * b + j] = row.l[b];
+    if (j < 3) head[81 + j] = 0u;
   }
   u32x4* ent = out + STEP4_HEAD;
   u32 off = 0;
