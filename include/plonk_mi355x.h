@@ -614,7 +614,7 @@ int pm_plonk_preprocess_wires(pm_ctx* ctx, const uint64_t* const selectors[PM_PL
 size_t pm_plonk_key_num_vars(const pm_prover_key* key);
 int pm_plonk_witness_from_vars_dev(pm_ctx* ctx, const pm_prover_key* key, const void* d_vars, size_t var_stride,
                                    uint32_t batch, void* d_witness_out, void* stream);
-/* ---- Gadget witnesses: fill widget rows from their inputs -----------------------------------
+/* ---- Gadget witnesses: fill widget rows from their inputs (DESIGN.md sections 7.2f, 7.2g) ----------------------------
  * In a composer-form circuit most variables are not inputs but the internal accumulators of the four widget gadgets.
  * These calls are the inverse of the witness check: given a gadget's inputs in the variable assignment, write the
  * variables that make its rows hold, on the device, in the layout pm_plonk_witness_from_vars_dev reads.
@@ -639,6 +639,25 @@ int pm_plonk_witness_from_vars_dev(pm_ctx* ctx, const pm_prover_key* key, const 
  *     complete; for other points the values written are deterministic and unspecified.
  *   CURVE_ADD (count ignored): reads (x1, y1, x2, y2) = a b c d of row 0 and writes a = x3, b = y3, d = x1 y2 in row 1.
  *     PM_PLONK_GADGET_DEGENERATE, with a = b = 0 written, when 1 +- d x1 x2 y1 y2 is zero (impossible on the curve).
+ * Composed gadgets: what a circuit builds from plain arithmetic rows.  They claim no widget row and
+ * have no trailing row; the identity of their rows is q_arith (q_m a b + q_l a + q_r b + q_o c + q_4 d + q_c + PI) = 0.
+ * None of them reports: no input is refused.
+ *   ARITH, count >= 1 rows, no in_var: for i = 0 .. count-1 in row order, read a, b, d of row i and then write
+ *     c := q_m a b + q_l a + q_r b + q_4 d + q_c (the row's own coefficients; every row has q_o = -1 and a c variable), so a
+ *     later row reads what an earlier row of the same gadget wrote.  PI is taken as ZERO: a row carrying a public input is not
+ *     for this gadget.  One thread walks the rows of a gadget one after the other: it is meant for the short glue between
+ *     gadgets (a difference, a product of two flags); independent runs should be SEPARATE gadgets of one level, which run in
+ *     parallel.
+ *   BITS, B = count bits (1 <= B <= PM_PLONK_COMPOSED_MAX_BITS), value v = in_var[0], 2B rows -- the loop of a bit
+ *     decomposition.  Row 2k is the boolean gate of bit k: a = b = c = bit_k, q_m = 1, q_o = -1.  Row 2k+1 accumulates:
+ *     a = bit_k, b = acc_(k-1), c = acc_k, q_l = 2^k, q_r = 1, q_o = -1.  Every coefficient not named is zero.  With V the
+ *     canonical integer of v (below r): bit_k = (V >> k) & 1; acc_(-1) is READ from b of row 1 (a circuit usually puts its
+ *     zero variable there); acc_k = acc_(-1) + (V mod 2^(k+1)).  The gadget writes a of row 2k and c of row 2k+1.  V >= 2^B
+ *     is no error: it is what the circuit around the gadget detects (acc_(B-1) != v).
+ *   MAYBE_EQUAL (count ignored, no in_var), 3 rows.  Row 0: c = u = a - b (q_l = 1, q_r = -1, q_o = -1).  Row 1: a = z,
+ *     b = u, c = y = 1 - u z (q_m = -1, q_c = 1, q_o = -1).  Row 2: a = y, b = u, q_m = 1, q_o = 0 (y u = 0).  Every
+ *     coefficient not named is zero.  The gadget reads a, b of row 0 and writes u to c of row 0, z = 1 / u (0 when u = 0)
+ *     to a of row 1 and y to c of row 1: y is 1 when the two inputs are equal and 0 otherwise.
  * Gadgets of one level are independent and run together; levels run in rising order, so a gadget may read what a lower
  * level wrote.  Two gadgets of ONE level may name the same variable as an output only where the definitions give both the
  * same value (the zero variable in d of a range's and a fixed-base's row 0, say); any other overlap is a race.  A gadget's
@@ -649,7 +668,17 @@ int pm_plonk_witness_from_vars_dev(pm_ctx* ctx, const pm_prover_key* key, const 
  * the table and keeps it on the device: one batched forward transform of the key's q_l, q_r, q_range, q_logic,
  * q_fixed_group_add and q_variable_group_add into transient scratch (6 n x 32 bytes), a kernel that tests the selector of
  * every claimed row (RANGE, LOGIC, FIXED_BASE: rows 0..count-1; CURVE_ADD: row 0) and gathers the table points of all
- * fixed-base rounds (64 bytes each).  PM_ERR_BAD_ARG, with pm_last_error naming the lowest offending gadget, for: levels
+ * fixed-base rounds (64 bytes each).  A table that holds a composed kind transforms all eleven selectors instead (11 n x
+ * 32 bytes of transient scratch) and tests on every row such a gadget claims: q_arith is non-zero and the four widget
+ * selectors are zero; ARITH: q_o = -1 and c is a variable; BITS and MAYBE_EQUAL: every coefficient has exactly the value
+ * given above and the wire map has the ids the layout implies (BITS: a = b = c on row 2k, a of row 2k+1 = a of row 2k, b of
+ * row 2k+1 = c of row 2k-1 for k >= 1; MAYBE_EQUAL: b of rows 1 and 2 = c of row 0, a of row 2 = c of row 1), the written
+ * positions being variables -- so a BITS or MAYBE_EQUAL gadget that is accepted is satisfied by what the fill writes,
+ * provided the variables it reads (BITS: the value and b of row 1; MAYBE_EQUAL: a, b of row 0) are not among those it writes
+ * and its written variables are distinct from one another: that is not tested and stays the caller's to keep.  The
+ * same kernel gathers q_m q_l q_r q_4 q_c of all ARITH rows (160 bytes each, counted in added_bytes); BITS and MAYBE_EQUAL
+ * keep nothing.  BITS: 1 <= count <= PM_PLONK_COMPOSED_MAX_BITS and in_var[0] < num_vars; rows are count (ARITH), 2 count
+ * (BITS) and 3 (MAYBE_EQUAL).  PM_ERR_BAD_ARG, with pm_last_error naming the lowest offending gadget, for: levels
  * not in rising order, an unknown kind or param, rows (the trailing row included) outside [0, n), a claimed row whose
  * selector is zero, a used in_var >= num_vars, count = 0 or a fixed-base count above PM_PLONK_GADGET_MAX_ROUNDS, a key
  * that was not built from wires.  After a refusal the key keeps the table it had.  added_bytes (may be NULL): the device
@@ -666,6 +695,10 @@ int pm_plonk_witness_from_vars_dev(pm_ctx* ctx, const pm_prover_key* key, const 
 #define PM_PLONK_GADGET_TOO_WIDE 1u
 #define PM_PLONK_GADGET_SCALAR_TOO_LONG 2u
 #define PM_PLONK_GADGET_DEGENERATE 3u
+#define PM_PLONK_COMPOSED_ARITH 4u         /* kinds 4..6 of pm_plonk_gadget.kind */
+#define PM_PLONK_COMPOSED_BITS 5u
+#define PM_PLONK_COMPOSED_MAYBE_EQUAL 6u
+#define PM_PLONK_COMPOSED_MAX_BITS 256u
 typedef struct pm_plonk_gadget {
   uint32_t kind, level;     /* gadgets of a level are independent; levels run in rising order */
   uint64_t first_row;

@@ -263,6 +263,10 @@ PLONK_GADGET_MAX_ROUNDS = 256
 PLONK_GADGET_TOO_WIDE, PLONK_GADGET_SCALAR_TOO_LONG, PLONK_GADGET_DEGENERATE = 1, 2, 3
 PLONK_GADGET_KINDS = ("range", "logic", "fixed_base", "curve_add")
 PLONK_GADGET_REASONS = {1: "too_wide", 2: "scalar_too_long", 3: "degenerate"}
+# the composed kinds of the same table (arithmetic rows only; they never fail a fill)
+PLONK_COMPOSED_ARITH, PLONK_COMPOSED_BITS, PLONK_COMPOSED_MAYBE_EQUAL = 4, 5, 6
+PLONK_COMPOSED_MAX_BITS = 256
+PLONK_COMPOSED_KINDS = {4: "arith", 5: "bits", 6: "maybe_equal"}
 
 NTT_INVERSE = 1
 NTT_COSET = 2

@@ -190,20 +190,23 @@ struct GadgetRec {
   uint32_t first_row, count;
   uint32_t in_var[2];
   uint32_t index;          // the caller's index: what a report names
-  uint32_t tab;            // FIXED_BASE: its first round in the table-point array
+  uint32_t tab;            // FIXED_BASE: its first round in the table-point array; ARITH: its first row in the coefficient array
 };
 struct GadgetGroup {
   uint32_t kind, first, count;
+  uint32_t span;           // BITS: the largest count of the group (the bits run along the grid's x)
 };
-// set time: *d_bad = the lowest index among the records whose claimed rows miss their selector (~0: none), and the table points
-// of the fixed-base records into d_tab.  d_sel6: q_l q_r q_range q_logic q_fixed_group_add q_variable_group_add on H.  Asynchronous.
-int gadget_verify(pm_ctx* ctx, const void* d_recs, uint32_t count, size_t n, const void* d_sel6, void* d_tab, uint32_t* d_bad,
-                  hipStream_t st);
+// set time: *d_bad = the lowest index among the records whose claimed rows miss what their kind needs (~0: none), the table
+// points of the fixed-base records into d_tab and the coefficients of the ARITH rows into d_coef.  d_sel: values on H, either
+// q_l q_r q_range q_logic q_fixed_group_add q_variable_group_add (all11 = false: tables of the four widget kinds) or all eleven
+// selectors in the order of PM_PLONK_SELECTORS, which the composed kinds need; d_wire_vars is read for those only.  Asynchronous.
+int gadget_verify(pm_ctx* ctx, const void* d_recs, uint32_t count, size_t n, const void* d_sel, bool all11, const void* d_wire_vars,
+                  void* d_tab, void* d_coef, uint32_t* d_bad, hipStream_t st);
 // one launch per group on st; d_rep: 2 x batch words (failing gadgets, then min(index * 4 + reason)), copied to rep_host after
 // the launches when it is given -- the call then waits for the stream
 int gadget_fill(pm_ctx* ctx, const void* d_recs, const GadgetGroup* groups, size_t n_groups, const void* d_wire_vars, size_t n,
-                const void* d_tab, void* d_vars, size_t var_stride, uint32_t batch, void* d_rep, unsigned long long* rep_host,
-                hipStream_t st);
+                const void* d_tab, const void* d_coef, void* d_vars, size_t var_stride, uint32_t batch, void* d_rep,
+                unsigned long long* rep_host, hipStream_t st);
 // Per-proof constants of the proof-batched kernels (pm_plonk_prove_batch): a pinned host buffer and its device twin of the
 // same size.  A launcher takes one region of both, fills the host side and sends it with one async copy on its stream;
 // kernels read the device side as a table indexed by the proof.  reset() once per call, after the previous call has

@@ -1,8 +1,15 @@
 // Gadget witnesses: the inverse of the witness check.  Given the inputs of a range, logic, fixed-base
 // or curve-addition gadget, write the variables that make its rows hold (definitions: include/plonk_mi355x.h, pm_plonk_gadget).
+// Section 7.2g adds the gadgets a circuit composes from arithmetic rows: runs of them, bit decompositions and maybe_equal.
 //
 //   gadget_verify_kernel       set time: every claimed row has its kind's selector, the table points of the fixed-base rounds
 //                              are gathered from q_l / q_r into a compact array
+//   composed_verify_kernel     set time, composed kinds: arithmetic rows without a widget, the coefficients and wire ids a BITS
+//                              or MAYBE_EQUAL layout implies; gathers q_m q_l q_r q_4 q_c of the ARITH rows
+//   gadget_arith_kernel        one thread per (gadget, proof): c = q_m a b + q_l a + q_r b + q_4 d + q_c, row after row
+//   gadget_bits_kernel         one thread per (gadget, proof, bit): acc_k = acc_(-1) + (V mod 2^(k+1)) is a masked copy of V, so
+//                              no bit waits for another
+//   gadget_maybe_equal_kernel  one thread per (gadget, proof): u = a - b, z = 1 / u (0 -> 0), y = [u = 0]
 //   gadget_range_kernel        one thread per (gadget, proof): quads of the canonical input, accumulators by 4 acc + quad
 //   gadget_logic_kernel        the same over two inputs, three accumulator columns and the quad products
 //   gadget_curve_add_kernel    one thread per (gadget, proof): the affine law with ONE inversion (of the two denominators' product)
@@ -90,6 +97,7 @@ struct GadgetFill {
   const GadgetRec* recs;
   const u32* wire_vars;     // [4][n]
   const u32x4* tab;         // table points, 4 x 16 bytes per round: x | y canonical
+  const u32x4* coef;        // ARITH rows, 10 x 16 bytes each: q_m q_l q_r q_4 q_c canonical
   u32x4* vars;              // [batch][var_stride] canonical
   size_t var_stride, n;
   unsigned long long* rep;  // [batch] failing gadgets, then [batch] min(index * 4 + reason); batch = gridDim.y
@@ -145,11 +153,15 @@ PM_DEV Fr g_acc_step(const Fr& acc, u32 q) {
 }
 
 // ------------------------------------------------------------------ set time: selectors of the claimed rows, table points
-// sel: six vectors of n values on H -- q_l q_r q_range q_logic q_fixed_group_add q_variable_group_add
-__global__ void __launch_bounds__(256) gadget_verify_kernel(const GadgetRec* recs, const u32x4* sel, size_t n, u32x4* tab, u32* bad) {
+// sel: vectors of n values on H; q_l, q_r are vectors ql, ql + 1 and the four widget selectors wid .. wid + 3 (0 and 2 of
+// q_l q_r q_range q_logic q_fixed_group_add q_variable_group_add; 1 and 7 of all eleven)
+__global__ void __launch_bounds__(256) gadget_verify_kernel(const GadgetRec* recs, const u32x4* sel_all, size_t n, u32 ql, u32 wid,
+                                                            u32x4* tab, u32* bad) {
   const GadgetRec rec = recs[blockIdx.x];
+  if (rec.kind > PM_PLONK_GADGET_CURVE_ADD) return;   // composed_verify_kernel
   const u32 rows = rec.kind == PM_PLONK_GADGET_CURVE_ADD ? 1u : rec.count;
-  const u32x4* q = sel + 2 * n * (2 + (size_t)rec.kind);
+  const u32x4* sel = sel_all + 2 * n * ql;
+  const u32x4* q = sel_all + 2 * n * (wid + (size_t)rec.kind);
   bool miss = false;
   for (u32 t = threadIdx.x; t < rows; t += 256) {
     const size_t row = (size_t)rec.first_row + t;
@@ -161,6 +173,90 @@ __global__ void __launch_bounds__(256) gadget_verify_kernel(const GadgetRec* rec
       o[1] = sel[2 * row + 1];
       o[2] = sel[2 * (n + row)];
       o[3] = sel[2 * (n + row) + 1];
+    }
+  }
+  if (miss) atomicMin(bad, rec.index);
+}
+
+// The composed kinds (include/plonk_mi355x.h): what a row's six coefficients must be.  sel: all eleven selectors on H in the
+// order of PM_PLONK_SELECTORS -- q_m q_l q_r q_o q_c q_4 q_arith, then the four widget selectors.
+enum : u32 { CO_ZERO, CO_ONE, CO_NEG, CO_POW, CO_ANY };
+PM_DEV void sel_words(const u32x4* sel, size_t n, u32 s, size_t row, u32 (&w)[8]) {
+  const u32x4 lo = sel[2 * (n * s + row)], hi = sel[2 * (n * s + row) + 1];
+  w[0] = lo.x, w[1] = lo.y, w[2] = lo.z, w[3] = lo.w, w[4] = hi.x, w[5] = hi.y, w[6] = hi.z, w[7] = hi.w;
+}
+__global__ void __launch_bounds__(256) composed_verify_kernel(const GadgetRec* recs, const u32x4* sel, size_t n, const u32* wire_vars,
+                                                              u32x4* coef, u32* bad) {
+  const GadgetRec rec = recs[blockIdx.x];
+  if (rec.kind < PM_PLONK_COMPOSED_ARITH) return;
+  const bool arith = rec.kind == PM_PLONK_COMPOSED_ARITH, bits = rec.kind == PM_PLONK_COMPOSED_BITS;
+  const u32 rows = arith ? rec.count : bits ? 2 * rec.count : 3u;
+  u32 one[8], neg[8];
+  fe_canon_pack<FrP>(one, g_one_abi());
+  fe_canon_pack<FrP>(neg, gneg(g_one_abi()));
+  bool miss = false;
+  for (u32 t = threadIdx.x; t < rows; t += 256) {
+    const size_t row = (size_t)rec.first_row + t;
+    u32 w[8];
+    // an arithmetic row and nothing else
+    sel_words(sel, n, 6, row, w);
+    miss |= (w[0] | w[1] | w[2] | w[3] | w[4] | w[5] | w[6] | w[7]) == 0;
+    u32 widget = 0;
+#pragma unroll
+    for (u32 s = 7; s < 11; ++s) {
+      sel_words(sel, n, s, row, w);
+      widget |= w[0] | w[1] | w[2] | w[3] | w[4] | w[5] | w[6] | w[7];
+    }
+    miss |= widget != 0;
+    // q_m q_l q_r q_o q_c q_4
+    u32 want[6] = {CO_ANY, CO_ANY, CO_ANY, CO_NEG, CO_ANY, CO_ANY};
+    u32 pw[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const u32 va = wire_vars[row], vb = wire_vars[n + row], vc = wire_vars[2 * n + row];
+    if (arith) {
+      miss |= vc == PM_PLONK_NO_VAR;
+    } else if (bits) {
+      const u32 k = t >> 1;
+      if ((t & 1u) == 0) {   // the boolean row: bit * bit - bit
+        want[0] = CO_ONE, want[1] = want[2] = want[4] = want[5] = CO_ZERO;
+        miss |= va == PM_PLONK_NO_VAR || vb != va || vc != va;
+      } else {               // 2^k bit + acc_(k-1) - acc_k
+        want[0] = want[4] = want[5] = CO_ZERO, want[1] = CO_POW, want[2] = CO_ONE;
+        u32 e[8];
+#pragma unroll
+        for (u32 i = 0; i < 8; ++i) e[i] = i == (k >> 5) ? 1u << (k & 31u) : 0u;
+        fe_canon_pack<FrP>(pw, g_from_int(e));
+        miss |= vc == PM_PLONK_NO_VAR || va != wire_vars[row - 1];
+        if (k) miss |= vb != wire_vars[2 * n + row - 2];
+      }
+    } else {
+      const size_t r0 = rec.first_row;
+      const u32 u = wire_vars[2 * n + r0], y = wire_vars[2 * n + r0 + 1];
+      if (t == 0) {          // a - b - u
+        want[0] = want[4] = want[5] = CO_ZERO, want[1] = CO_ONE, want[2] = CO_NEG;
+        miss |= vc == PM_PLONK_NO_VAR;
+      } else if (t == 1) {   // 1 - z u - y
+        want[0] = CO_NEG, want[4] = CO_ONE, want[1] = want[2] = want[5] = CO_ZERO;
+        miss |= va == PM_PLONK_NO_VAR || vc == PM_PLONK_NO_VAR || vb != u;
+      } else {               // y u
+        want[0] = CO_ONE, want[1] = want[2] = want[3] = want[4] = want[5] = CO_ZERO;
+        miss |= va != y || vb != u;
+      }
+    }
+#pragma unroll
+    for (u32 s = 0; s < 6; ++s) {
+      sel_words(sel, n, s, row, w);
+      u32 diff = 0;
+#pragma unroll
+      for (u32 i = 0; i < 8; ++i) {
+        const u32 x = want[s] == CO_ONE ? one[i] : want[s] == CO_NEG ? neg[i] : want[s] == CO_POW ? pw[i] : 0u;
+        diff |= w[i] ^ x;
+      }
+      miss |= want[s] != CO_ANY && diff != 0;
+      if (arith && s != 3) {   // q_m q_l q_r q_c q_4 -> slots 0 1 2 4 3
+        u32x4* o = coef + 10 * ((size_t)rec.tab + t) + 2 * (s < 3 ? s : s == 4 ? 4u : 3u);
+        o[0] = u32x4{w[0], w[1], w[2], w[3]};
+        o[1] = u32x4{w[4], w[5], w[6], w[7]};
+      }
     }
   }
   if (miss) atomicMin(bad, rec.index);
@@ -233,6 +329,65 @@ __global__ void __launch_bounds__(64) gadget_curve_add_kernel(const GadgetFill a
   st_var(vars, var_id(a, 0, row + 1), g_to_abi(x3));
   st_var(vars, var_id(a, 1, row + 1), g_to_abi(y3));
   st_var(vars, var_id(a, 3, row + 1), g_to_abi(x1y2));
+}
+
+// ------------------------------------------------------------------ composed gadgets
+// A run of arithmetic rows with q_o = -1 (verified at set time): c = q_m a b + q_l a + q_r b + q_4 d + q_c, one row after the
+// other, so a row reads what the rows before it wrote.  One thread per (gadget, proof); the coefficients were gathered at set time.
+__global__ void __launch_bounds__(64) gadget_arith_kernel(const GadgetFill a, u32 first, u32 count) {
+  const u32 g = blockIdx.x * 64 + threadIdx.x, proof = blockIdx.y;
+  if (g >= count) return;
+  const GadgetRec rec = a.recs[first + g];
+  u32x4* const vars = a.vars + 2 * a.var_stride * proof;
+#pragma unroll 1
+  for (u32 i = 0; i < rec.count; ++i) {
+    const size_t row = (size_t)rec.first_row + i;
+    const u32x4* q = a.coef + 10 * ((size_t)rec.tab + i);
+    const Fr A = ld_var(vars, var_id(a, 0, row)), B = ld_var(vars, var_id(a, 1, row)), D = ld_var(vars, var_id(a, 3, row));
+    // coefficient in the device form x value in the ABI form -> ABI
+    Fr c = gmul(g_to_dev(gmul(g_to_dev(ld_canon(q, 0)), A)), B);
+    c = gadd(c, gmul(g_to_dev(ld_canon(q, 1)), A));
+    c = gadd(c, gmul(g_to_dev(ld_canon(q, 2)), B));
+    c = gadd(c, gmul(g_to_dev(ld_canon(q, 3)), D));
+    c = gadd(c, ld_canon(q, 4));
+    st_var(vars, var_id(a, 2, row), c);
+  }
+}
+
+// Bit decomposition: blockIdx.x * 64 + threadIdx.x = the bit k, blockIdx.y = the gadget within the launch, blockIdx.z = the
+// proof.  acc_k = acc_(-1) + (V mod 2^(k+1)): every thread masks its own copy of V, nothing is passed from bit to bit.
+__global__ void __launch_bounds__(64) gadget_bits_kernel(const GadgetFill a, u32 first) {
+  const u32 k = blockIdx.x * 64 + threadIdx.x, proof = blockIdx.z;
+  const GadgetRec rec = a.recs[first + blockIdx.y];
+  if (k >= rec.count) return;
+  u32x4* const vars = a.vars + 2 * a.var_stride * proof;
+  const size_t row0 = rec.first_row;
+  u32 v[8], m[8];
+  g_to_int(ld_canon(vars, rec.in_var[0]), v);
+#pragma unroll
+  for (u32 w = 0; w < 8; ++w) {   // the low k + 1 bits
+    const u32 lo = 32 * w, keep = k + 1;
+    m[w] = v[w] & (lo + 32 <= keep ? 0xffffffffu : (lo >= keep ? 0u : ((1u << ((keep - lo) & 31u)) - 1u)));
+  }
+  const Fr acc = gadd(g_from_int(m), ld_var(vars, var_id(a, 1, row0 + 1)));
+  st_var(vars, var_id(a, 0, row0 + 2 * (size_t)k), g_sel(bit_at<8>(v, k) != 0, g_one_abi(), fe_zero<FrP>()));
+  st_var(vars, var_id(a, 2, row0 + 2 * (size_t)k + 1), acc);
+}
+
+// u = a - b, z = 1 / u or 0, y = 1 - u z = [u = 0].  One thread per (gadget, proof); the inversion votes across the wave, so
+// (as in gadget_curve_add_kernel) a lane past the end works on the last gadget and writes nothing.
+__global__ void __launch_bounds__(64) gadget_maybe_equal_kernel(const GadgetFill a, u32 first, u32 count) {
+  const u32 g0 = blockIdx.x * 64 + threadIdx.x, proof = blockIdx.y;
+  const bool live = g0 < count;
+  const GadgetRec rec = a.recs[first + (live ? g0 : count - 1)];
+  u32x4* const vars = a.vars + 2 * a.var_stride * proof;
+  const size_t row = rec.first_row;
+  const Fr u = gsub(ld_var(vars, var_id(a, 0, row)), ld_var(vars, var_id(a, 1, row)));
+  const Fr inv = fe_inv_dev<FrP>(g_to_dev(u));         // 0 -> 0
+  if (!live) return;
+  st_var(vars, var_id(a, 2, row), u);
+  st_var(vars, var_id(a, 0, row + 1), g_to_abi(inv));
+  st_var(vars, var_id(a, 2, row + 1), g_sel(g_is_zero(u), g_one_abi(), fe_zero<FrP>()));
 }
 
 // extended coordinates: x = X / Z, y = Y / Z, T = X Y / Z
@@ -399,21 +554,24 @@ __global__ void __launch_bounds__(64) gadget_fixed_base_kernel(const GadgetFill 
 
 }  // namespace
 
-int gadget_verify(pm_ctx* ctx, const void* d_recs, uint32_t count, size_t n, const void* d_sel6, void* d_tab, uint32_t* d_bad,
-                  hipStream_t st) {
+int gadget_verify(pm_ctx* ctx, const void* d_recs, uint32_t count, size_t n, const void* d_sel, bool all11, const void* d_wire_vars,
+                  void* d_tab, void* d_coef, uint32_t* d_bad, hipStream_t st) {
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (!st) st = ctx->stream;
   PM_HIP(ctx, hipSetDevice(ctx->device));
   PM_HIP(ctx, hipMemsetAsync(d_bad, 0xff, 4, st));
-  hipLaunchKernelGGL(gadget_verify_kernel, dim3(count), dim3(256), 0, st, (const GadgetRec*)d_recs, (const u32x4*)d_sel6, n,
-                     (u32x4*)d_tab, d_bad);
+  hipLaunchKernelGGL(gadget_verify_kernel, dim3(count), dim3(256), 0, st, (const GadgetRec*)d_recs, (const u32x4*)d_sel, n,
+                     all11 ? 1u : 0u, all11 ? 7u : 2u, (u32x4*)d_tab, d_bad);
+  if (all11)
+    hipLaunchKernelGGL(composed_verify_kernel, dim3(count), dim3(256), 0, st, (const GadgetRec*)d_recs, (const u32x4*)d_sel, n,
+                       (const u32*)d_wire_vars, (u32x4*)d_coef, d_bad);
   PM_HIP(ctx, hipGetLastError());
   return PM_OK;
 }
 
 int gadget_fill(pm_ctx* ctx, const void* d_recs, const GadgetGroup* groups, size_t n_groups, const void* d_wire_vars, size_t n,
-                const void* d_tab, void* d_vars, size_t var_stride, uint32_t batch, void* d_rep, unsigned long long* rep_host,
-                hipStream_t st) {
+                const void* d_tab, const void* d_coef, void* d_vars, size_t var_stride, uint32_t batch, void* d_rep,
+                unsigned long long* rep_host, hipStream_t st) {
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (!st) st = ctx->stream;
   PM_HIP(ctx, hipSetDevice(ctx->device));
@@ -421,6 +579,7 @@ int gadget_fill(pm_ctx* ctx, const void* d_recs, const GadgetGroup* groups, size
   a.recs = (const GadgetRec*)d_recs;
   a.wire_vars = (const u32*)d_wire_vars;
   a.tab = (const u32x4*)d_tab;
+  a.coef = (const u32x4*)d_coef;
   a.vars = (u32x4*)d_vars;
   a.var_stride = var_stride;
   a.n = n;
@@ -447,8 +606,19 @@ int gadget_fill(pm_ctx* ctx, const void* d_recs, const GadgetGroup* groups, size
         case PM_PLONK_GADGET_FIXED_BASE:
           hipLaunchKernelGGL(gadget_fixed_base_kernel, per_wave, dim3(64), 0, st, a, g.first);
           break;
-        default:
+        case PM_PLONK_GADGET_CURVE_ADD:
           hipLaunchKernelGGL(gadget_curve_add_kernel, per_thread, dim3(64), 0, st, a, g.first, g.count);
+          break;
+        case PM_PLONK_COMPOSED_ARITH:
+          hipLaunchKernelGGL(gadget_arith_kernel, per_thread, dim3(64), 0, st, a, g.first, g.count);
+          break;
+        case PM_PLONK_COMPOSED_BITS:   // the gadgets along y, at most 65535 a launch
+          for (u32 lo = 0; lo < g.count; lo += 65535u)
+            hipLaunchKernelGGL(gadget_bits_kernel, dim3((g.span + 63) / 64, std::min(g.count - lo, 65535u), batch), dim3(64), 0, st, a,
+                               g.first + lo);
+          break;
+        default:
+          hipLaunchKernelGGL(gadget_maybe_equal_kernel, per_thread, dim3(64), 0, st, a, g.first, g.count);
           break;
       }
     }

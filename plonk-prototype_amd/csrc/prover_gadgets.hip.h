@@ -1,11 +1,12 @@
 // Gadget witnesses: pm_plonk_key_set_gadgets / pm_plonk_fill_gadgets_dev (included by prover.hip: the key is pm_plonk_prove's;
-// DESIGN.md section 7.2f).  The kernels and what each gadget writes are in gadgets.hip; here is the table a key holds and the
+// DESIGN.md sections 7.2f and 7.2g).  The kernels and what each gadget writes are in gadgets.hip; here is the table a key holds and the
 // host side of the two calls.
 struct GadgetState {
   size_t bytes = 0;                        // device bytes held
   size_t count = 0;                        // gadgets
   void* recs = nullptr;                    // pm::GadgetRec x count, in launch order
   void* tab = nullptr;                     // table points of the fixed-base rounds, 64 bytes each
+  void* coef = nullptr;                    // q_m q_l q_r q_4 q_c of the ARITH rows, 160 bytes each; nullptr without such rows
   void* rep = nullptr;                     // 2 x PM_PLONK_MAX_BATCH report words
   std::vector<pm::GadgetGroup> groups;     // one launch each, levels rising
 };
@@ -13,7 +14,7 @@ struct GadgetState {
 namespace {
 void gadget_state_free(pm_ctx* ctx, GadgetState* gs) {
   if (!gs) return;
-  for (void* p : {gs->recs, gs->tab, gs->rep})
+  for (void* p : {gs->recs, gs->tab, gs->coef, gs->rep})
     if (p && ctx) (void)pm_dev_free(ctx, p);
   delete gs;
 }
@@ -21,14 +22,17 @@ void gadget_state_free(pm_ctx* ctx, GadgetState* gs) {
 // what the host can tell about gadget g; empty = nothing
 std::string gadget_host_fault(const pm_plonk_gadget& g, const pm_plonk_gadget* prev, size_t n, size_t num_vars) {
   if (prev && g.level < prev->level) return "levels must not fall";
-  if (g.kind > PM_PLONK_GADGET_CURVE_ADD) return "unknown kind";
+  if (g.kind > PM_PLONK_COMPOSED_MAYBE_EQUAL) return "unknown kind";
   if (g.param > (g.kind == PM_PLONK_GADGET_LOGIC ? 1u : 0u)) return "unknown param";
-  const bool add = g.kind == PM_PLONK_GADGET_CURVE_ADD;
-  if (!add && g.count == 0) return "count is 0";
+  const bool add = g.kind == PM_PLONK_GADGET_CURVE_ADD, eq = g.kind == PM_PLONK_COMPOSED_MAYBE_EQUAL;
+  const bool run = g.kind == PM_PLONK_COMPOSED_ARITH, bits = g.kind == PM_PLONK_COMPOSED_BITS;
+  if (!add && !eq && g.count == 0) return "count is 0";
   if (g.kind == PM_PLONK_GADGET_FIXED_BASE && g.count > PM_PLONK_GADGET_MAX_ROUNDS) return "more than PM_PLONK_GADGET_MAX_ROUNDS rounds";
-  const uint64_t rows = add ? 2 : (uint64_t)g.count + 1;   // the trailing row included
+  if (bits && g.count > PM_PLONK_COMPOSED_MAX_BITS) return "more than PM_PLONK_COMPOSED_MAX_BITS bits";
+  // the widget kinds: the trailing row included; the composed kinds have none
+  const uint64_t rows = add ? 2 : eq ? 3 : run ? (uint64_t)g.count : bits ? 2 * (uint64_t)g.count : (uint64_t)g.count + 1;
   if (g.first_row >= n || rows > n - g.first_row) return "its rows leave [0, n)";
-  const int used = add ? 0 : g.kind == PM_PLONK_GADGET_LOGIC ? 2 : 1;
+  const int used = add || eq || run ? 0 : g.kind == PM_PLONK_GADGET_LOGIC ? 2 : 1;
   for (int i = 0; i < used; ++i)
     if (g.in_var[i] >= num_vars) return "in_var is not below num_vars";
   return "";
@@ -59,16 +63,24 @@ extern "C" int pm_plonk_key_set_gadgets(pm_ctx* ctx, pm_prover_key* pk, const pm
   std::vector<pm::GadgetRec> recs;
   std::vector<pm::GadgetGroup> groups;
   uint32_t rounds = 0;
+  uint64_t arith_rows = 0;
+  bool composed = false;                   // a kind that needs all eleven selectors on H
   for (size_t lo = 0; lo < lim;) {
     size_t hi = lo;
     while (hi < lim && gadgets[hi].level == gadgets[lo].level) ++hi;
-    for (uint32_t kind = 0; kind <= PM_PLONK_GADGET_CURVE_ADD; ++kind) {
-      pm::GadgetGroup grp{kind, (uint32_t)recs.size(), 0};
+    for (uint32_t kind = 0; kind <= PM_PLONK_COMPOSED_MAYBE_EQUAL; ++kind) {
+      pm::GadgetGroup grp{kind, (uint32_t)recs.size(), 0, 0};
       for (size_t i = lo; i < hi; ++i) {
         const pm_plonk_gadget& g = gadgets[i];
         if (g.kind != kind) continue;
-        pm::GadgetRec r{g.kind, g.param, (uint32_t)g.first_row, g.count, {g.in_var[0], g.in_var[1]}, (uint32_t)i, rounds};
+        const bool run = kind == PM_PLONK_COMPOSED_ARITH;
+        pm::GadgetRec r{g.kind, g.param, (uint32_t)g.first_row, g.count, {g.in_var[0], g.in_var[1]}, (uint32_t)i,
+                        run ? (uint32_t)arith_rows : rounds};
         if (kind == PM_PLONK_GADGET_FIXED_BASE) rounds += g.count;
+        if (run) arith_rows += g.count;
+        if (arith_rows > 0xffffffffull) return pm::set_err(ctx, PM_ERR_BAD_ARG, "too many ARITH rows");
+        composed |= kind >= PM_PLONK_COMPOSED_ARITH;
+        if (kind == PM_PLONK_COMPOSED_BITS) grp.span = std::max(grp.span, g.count);
         recs.push_back(r);
         ++grp.count;
       }
@@ -85,22 +97,37 @@ extern "C" int pm_plonk_key_set_gadgets(pm_ctx* ctx, pm_prover_key* pk, const pm
     PK_TRY(pm_dev_alloc(ctx, std::max<size_t>(rounds, 1) * 64, &gs->tab));
     PK_TRY(pm_dev_alloc(ctx, 2 * (size_t)PM_PLONK_MAX_BATCH * 8, &gs->rep));
     gs->bytes = recs.size() * sizeof(pm::GadgetRec) + std::max<size_t>(rounds, 1) * 64 + 2 * (size_t)PM_PLONK_MAX_BATCH * 8;
+    if (arith_rows) {
+      PK_TRY(pm_dev_alloc(ctx, (size_t)arith_rows * 160, &gs->coef));
+      gs->bytes += (size_t)arith_rows * 160;
+    }
     PK_TRY(pm_dev_upload(ctx, gs->recs, recs.data(), recs.size() * sizeof(pm::GadgetRec)));
     // q_l q_r | q_range q_logic q_fixed_group_add q_variable_group_add: coefficients -> values on H, one batched transform
-    PK_TRY(pm_dev_alloc(ctx, 6 * n * 32, &sel6));
+    // a table with a composed kind: all eleven (the rows' coefficients are part of what is checked)
     PM_HIP(ctx, hipSetDevice(ctx->device));
-    PM_HIP(ctx, hipMemcpyAsync(sel6, at(pk->sel_coeffs, (size_t)Q_L * n), 2 * n * 32, hipMemcpyDeviceToDevice, ctx->stream));
-    PM_HIP(ctx, hipMemcpyAsync(at(sel6, 2 * n), at(pk->sel_coeffs, (size_t)Q_RANGE * n), 4 * n * 32, hipMemcpyDeviceToDevice,
-                               ctx->stream));
-    PK_TRY(pm_fr_ntt_dev(ctx, sel6, n, n, sel6, n, pk->log_n, 6, 0, nullptr));
-    PK_TRY(pm::gadget_verify(ctx, gs->recs, (uint32_t)recs.size(), n, sel6, gs->tab, (uint32_t*)gs->rep, nullptr));
+    if (composed) {
+      PK_TRY(pm_dev_alloc(ctx, (size_t)NSEL * n * 32, &sel6));
+      PK_TRY(pm_fr_ntt_dev(ctx, pk->sel_coeffs, n, n, sel6, n, pk->log_n, NSEL, 0, nullptr));
+    } else {
+      PK_TRY(pm_dev_alloc(ctx, 6 * n * 32, &sel6));
+      PM_HIP(ctx, hipMemcpyAsync(sel6, at(pk->sel_coeffs, (size_t)Q_L * n), 2 * n * 32, hipMemcpyDeviceToDevice, ctx->stream));
+      PM_HIP(ctx, hipMemcpyAsync(at(sel6, 2 * n), at(pk->sel_coeffs, (size_t)Q_RANGE * n), 4 * n * 32, hipMemcpyDeviceToDevice,
+                                 ctx->stream));
+      PK_TRY(pm_fr_ntt_dev(ctx, sel6, n, n, sel6, n, pk->log_n, 6, 0, nullptr));
+    }
+    PK_TRY(pm::gadget_verify(ctx, gs->recs, (uint32_t)recs.size(), n, sel6, composed, pk->wire_vars, gs->tab, gs->coef,
+                             (uint32_t*)gs->rep, nullptr));
     PK_TRY(pm_dev_download(ctx, &bad, gs->rep, 4));
     return pm_sync(ctx);
   };
   int rc = body();
   if (sel6) (void)pm_dev_free(ctx, sel6);
   if (rc == PM_OK && bad != 0xffffffffu)
-    rc = pm::set_err(ctx, PM_ERR_BAD_ARG, "gadget " + std::to_string(bad) + ": a row it claims does not have its kind's selector");
+    rc = pm::set_err(ctx, PM_ERR_BAD_ARG,
+                     "gadget " + std::to_string(bad) +
+                         (gadgets[bad].kind >= PM_PLONK_COMPOSED_ARITH
+                              ? ": a row it claims is not the arithmetic row its kind lays out (selectors, coefficients or wire variables)"
+                              : ": a row it claims does not have its kind's selector"));
   else if (rc == PM_OK && lim < count)
     rc = pm::set_err(ctx, PM_ERR_BAD_ARG, "gadget " + std::to_string(lim) + ": " + why);
   if (rc != PM_OK) {
@@ -125,7 +152,7 @@ extern "C" int pm_plonk_fill_gadgets_dev(pm_ctx* ctx, const pm_prover_key* pk, v
   if (batch == 0 || batch > PM_PLONK_MAX_BATCH) return pm::set_err(ctx, PM_ERR_BAD_ARG, "batch must be in 1..PM_PLONK_MAX_BATCH");
   if (var_stride < pk->num_vars) return pm::set_err(ctx, PM_ERR_BAD_ARG, "var_stride is below the key's num_vars");
   unsigned long long rep[2 * PM_PLONK_MAX_BATCH];
-  PK_TRY(pm::gadget_fill(ctx, gs->recs, gs->groups.data(), gs->groups.size(), pk->wire_vars, pk->n, gs->tab, d_vars, var_stride,
+  PK_TRY(pm::gadget_fill(ctx, gs->recs, gs->groups.data(), gs->groups.size(), pk->wire_vars, pk->n, gs->tab, gs->coef, d_vars, var_stride,
                          batch, gs->rep, reports ? rep : nullptr, (hipStream_t)stream));
   if (reports)
     for (uint32_t b = 0; b < batch; ++b) {

@@ -179,7 +179,7 @@ class UnsatisfiedWitness(ValueError):
 @dataclass(frozen=True)
 class Gadget:
     """``pm_plonk_gadget``: one widget gadget of a composer-form circuit whose rows ``ProverKey.fill_gadgets`` fills from
-    its input variables (the definitions are in include/plonk_mi355x.h).  Gadgets of one ``level``
+    its input variables (the definitions are in include/plonk_mi355x.h; DESIGN.md sections 7.2f and 7.2g).  Gadgets of one ``level``
     are independent; levels run in rising order, and a list given to ``ProverKey.set_gadgets`` is sorted by level."""
     kind: int
     first_row: int
@@ -208,6 +208,29 @@ class Gadget:
     def curve_add(cls, first_row: int, level: int = 0) -> "Gadget":
         """JubJub addition of the points in a b and c d of ``first_row``; the sum goes to a b of the next row."""
         return cls(_lib.PLONK_GADGET_CURVE_ADD, int(first_row), 0, int(level), 0, ())
+
+    @classmethod
+    def arith(cls, first_row: int, rows: int, level: int = 0) -> "Gadget":
+        """A run of ``rows`` arithmetic rows with q_o = -1, solved for c one after the other (a later row may read an earlier
+        one's c).  Sequential: independent runs belong in separate gadgets of one level."""
+        return cls(_lib.PLONK_COMPOSED_ARITH, int(first_row), int(rows), int(level), 0, ())
+
+    @classmethod
+    def bits(cls, first_row: int, num_bits: int, value_var: int, level: int = 0) -> "Gadget":
+        """The ``num_bits`` <= 256 low bits of variable ``value_var`` and their running sums: rows [first_row, first_row +
+        2 num_bits), a boolean row and an accumulating row per bit; the sum starts from b of the second row."""
+        return cls(_lib.PLONK_COMPOSED_BITS, int(first_row), int(num_bits), int(level), 0, (int(value_var),))
+
+    @classmethod
+    def maybe_equal(cls, first_row: int, level: int = 0) -> "Gadget":
+        """Three rows: u = a - b of ``first_row``, z = 1 / u (or 0) and y = 1 - u z, which is 1 exactly when a = b."""
+        return cls(_lib.PLONK_COMPOSED_MAYBE_EQUAL, int(first_row), 0, int(level), 0, ())
+
+    @classmethod
+    def decomposition(cls, first_row: int, num_bits: int, value_var: int, level: int = 0) -> list:
+        """A whole scalar decomposition: the bits at ``level``, then the comparison of their sum with the value in the three
+        rows that follow, one level later.  -> [bits, maybe_equal]"""
+        return [cls.bits(first_row, num_bits, value_var, level), cls.maybe_equal(int(first_row) + 2 * int(num_bits), int(level) + 1)]
 
     def _raw(self) -> "_lib.Gadget":
         iv = tuple(self.in_vars) + (_lib.PLONK_NO_VAR,) * (2 - len(self.in_vars))
@@ -241,7 +264,9 @@ class GadgetInputError(ValueError):
         def one(b, r):
             kind = ""
             if gadgets is not None and r.first_gadget is not None and r.first_gadget < len(gadgets):
-                kind = f" ({_lib.PLONK_GADGET_KINDS[gadgets[r.first_gadget].kind]} at row {gadgets[r.first_gadget].first_row})"
+                k = gadgets[r.first_gadget].kind
+                name = _lib.PLONK_GADGET_KINDS[k] if k < len(_lib.PLONK_GADGET_KINDS) else _lib.PLONK_COMPOSED_KINDS.get(k, f"kind {k}")
+                kind = f" ({name} at row {gadgets[r.first_gadget].first_row})"
             return f"proof {b}: gadget {r.first_gadget}{kind}: {r.first_reason}; {r.failed} failing gadget(s)"
         super().__init__("; ".join(one(b, r) for b, r in sorted(self.reports.items())))
 
