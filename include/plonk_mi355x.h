@@ -658,6 +658,21 @@ int pm_plonk_witness_from_vars_dev(pm_ctx* ctx, const pm_prover_key* key, const 
  *     b = u, c = y = 1 - u z (q_m = -1, q_c = 1, q_o = -1).  Row 2: a = y, b = u, q_m = 1, q_o = 0 (y u = 0).  Every
  *     coefficient not named is zero.  The gadget reads a, b of row 0 and writes u to c of row 0, z = 1 / u (0 when u = 0)
  *     to a of row 1 and y to c of row 1: y is 1 when the two inputs are equal and 0 otherwise.
+ * Permutation gadgets: the rows of a whole permutation, filled by one wave per gadget and proof.
+ *   HADES (kind PM_PLONK_PERMUTATION_HADES), one Hades permutation of width PM_PLONK_HADES_WIDTH = 5, as a Poseidon sponge
+ *     uses it.  count = R >= 1 rounds, param = F full rounds, F even and 0 <= F <= R; no in_var, nothing reported.  Round rho is
+ *     FULL when rho < F / 2 or rho >= R - F / 2 and PARTIAL otherwise.  Every row is an arithmetic row with q_o = -1 and no
+ *     public input, as for ARITH; every coefficient not named is zero.  The rows of a round, in order, on the state s[0..4]:
+ *       round keys, 5 rows: row j has a = s[j], c = s'[j] = s[j] + q_c, q_l = 1, q_c = any value (the round constant); b
+ *         and d are not read (q_r = q_4 = 0);
+ *       s-box, 3 rows per word, for j = 0..4 in order in a full round and for j = 4 only in a partial one: with x = s'[j],
+ *         (a = b = x, c = x2), (a = b = x2, c = x4), (a = x4, b = x, c = x5), each with q_m = 1; x5 replaces the word;
+ *       matrix, 2 rows for each i = 0..4, v the state after the s-box: (a = v0, b = v1, d = v2, c = z_i) with q_l, q_r, q_4 =
+ *         any values, then (a = v3, b = v4, d = z_i, c = o_i) with q_l, q_r = any values and q_4 = 1: the five coefficients are
+ *         row i of the matrix, o[0..4] is the state of the next round.
+ *     A full round has 30 rows and a partial one 18: the gadget claims 30 F + 18 (R - F) rows (dusk-hades: R = 67, F = 8,
+ *     1302 rows).  It reads a of its first five rows (PM_PLONK_NO_VAR reads as zero; the five may alias) and writes c of
+ *     every row, byte for byte what an ARITH run over the same rows writes.
  * Gadgets of one level are independent and run together; levels run in rising order, so a gadget may read what a lower
  * level wrote.  Two gadgets of ONE level may name the same variable as an output only where the definitions give both the
  * same value (the zero variable in d of a range's and a fixed-base's row 0, say); any other overlap is a race.  A gadget's
@@ -678,7 +693,15 @@ int pm_plonk_witness_from_vars_dev(pm_ctx* ctx, const pm_prover_key* key, const 
  * and its written variables are distinct from one another: that is not tested and stays the caller's to keep.  The
  * same kernel gathers q_m q_l q_r q_4 q_c of all ARITH rows (160 bytes each, counted in added_bytes); BITS and MAYBE_EQUAL
  * keep nothing.  BITS: 1 <= count <= PM_PLONK_COMPOSED_MAX_BITS and in_var[0] < num_vars; rows are count (ARITH), 2 count
- * (BITS) and 3 (MAYBE_EQUAL).  PM_ERR_BAD_ARG, with pm_last_error naming the lowest offending gadget, for: levels
+ * (BITS) and 3 (MAYBE_EQUAL).  HADES is checked like a composed kind (all eleven selectors): on every claimed row q_arith is
+ * non-zero, the widget selectors are zero, q_o = -1, every coefficient the layout fixes has exactly that value, the wire map
+ * has the ids the layout implies (a of a key row of round rho >= 1 = c of the row of o_j in round rho - 1; the s-box and
+ * matrix rows read the c's named above) and c is a variable -- so an accepted gadget is satisfied by what the fill writes,
+ * provided its written variables are distinct from one another and from the five inputs, which stays the caller's to keep.
+ * The free coefficients are gathered per round (5 round keys and 25 matrix entries, 960 bytes) and so are the c ids of the
+ * round's rows (30 ids, 120 bytes), so that the fill never walks the wire map: 1080 bytes a round, counted in added_bytes
+ * (R = 67: 64,320 + 8,040 = 72,360 bytes); a table without a HADES gadget holds what it held.  HADES: count >= 1, param even
+ * and <= count, at most 2^32 HADES rows in a table.  PM_ERR_BAD_ARG, with pm_last_error naming the lowest offending gadget, for: levels
  * not in rising order, an unknown kind or param, rows (the trailing row included) outside [0, n), a claimed row whose
  * selector is zero, a used in_var >= num_vars, count = 0 or a fixed-base count above PM_PLONK_GADGET_MAX_ROUNDS, a key
  * that was not built from wires.  After a refusal the key keeps the table it had.  added_bytes (may be NULL): the device
@@ -699,11 +722,13 @@ int pm_plonk_witness_from_vars_dev(pm_ctx* ctx, const pm_prover_key* key, const 
 #define PM_PLONK_COMPOSED_BITS 5u
 #define PM_PLONK_COMPOSED_MAYBE_EQUAL 6u
 #define PM_PLONK_COMPOSED_MAX_BITS 256u
+#define PM_PLONK_PERMUTATION_HADES 7u      /* kind 7: count = rounds R, param = full rounds F */
+#define PM_PLONK_HADES_WIDTH 5u
 typedef struct pm_plonk_gadget {
   uint32_t kind, level;     /* gadgets of a level are independent; levels run in rising order */
   uint64_t first_row;
-  uint32_t count;           /* RANGE: rows m (8m bits); LOGIC: quads Q; FIXED_BASE: rounds R; CURVE_ADD: ignored */
-  uint32_t param;           /* LOGIC: 0 = AND, 1 = XOR; otherwise 0 */
+  uint32_t count;           /* RANGE: rows m (8m bits); LOGIC: quads Q; FIXED_BASE: rounds R; CURVE_ADD: ignored; HADES: rounds R */
+  uint32_t param;           /* LOGIC: 0 = AND, 1 = XOR; HADES: full rounds F; otherwise 0 */
   uint32_t in_var[2];       /* RANGE: value; LOGIC: a, b; FIXED_BASE: scalar; unused = PM_PLONK_NO_VAR */
 } pm_plonk_gadget;
 typedef struct pm_plonk_gadget_report {
@@ -715,6 +740,11 @@ typedef struct pm_plonk_gadget_report {
 int pm_plonk_key_set_gadgets(pm_ctx* ctx, pm_prover_key* key, const pm_plonk_gadget* gadgets, size_t count, size_t* added_bytes);
 int pm_plonk_fill_gadgets_dev(pm_ctx* ctx, const pm_prover_key* key, void* d_vars, size_t var_stride, uint32_t batch,
                               pm_plonk_gadget_report* reports, void* stream);
+/* Pure host, no context: the rows a gadget claims, its trailing row included (RANGE, LOGIC, FIXED_BASE: count + 1; CURVE_ADD:
+ * 2; ARITH: count; BITS: 2 count; MAYBE_EQUAL: 3; HADES: 30 F + 18 (R - F)).  0 for NULL, an unknown kind and a count or param
+ * that pm_plonk_key_set_gadgets refuses on its own: count 0 where a count is needed, a count above its kind's cap, HADES with
+ * F odd or F > R. */
+uint64_t pm_plonk_gadget_rows(const pm_plonk_gadget* g);
 /* Proof::to_bytes: 11 x 48-byte compressed G1, then the 16 scalars of ProofEvaluations::to_bytes. */
 int pm_plonk_proof_to_bytes(const pm_plonk_proof* proof, uint8_t out[PM_PLONK_PROOF_BYTES]);
 /* ---- The prover with coefficient-range ownership end to end (SURVEY.md section 8e row 3 + 8f N5; configs[4]) ----------

@@ -187,6 +187,7 @@ SIGNATURES = {
     "pm_plonk_key_set_gadgets": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(Gadget), C.c_size_t, C.POINTER(C.c_size_t)]),
     "pm_plonk_fill_gadgets_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32,
                                             C.POINTER(GadgetReport), C.c_void_p]),
+    "pm_plonk_gadget_rows": (C.c_uint64, [C.POINTER(Gadget)]),
     "pm_plonk_proof_to_bytes": (C.c_int, [C.POINTER(PlonkProof), C.POINTER(C.c_uint8)]),
     "pm_plonk_batch_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
     "pm_plonk_batch_free": (None, [C.c_void_p, C.c_void_p]),
@@ -267,6 +268,10 @@ PLONK_GADGET_REASONS = {1: "too_wide", 2: "scalar_too_long", 3: "degenerate"}
 PLONK_COMPOSED_ARITH, PLONK_COMPOSED_BITS, PLONK_COMPOSED_MAYBE_EQUAL = 4, 5, 6
 PLONK_COMPOSED_MAX_BITS = 256
 PLONK_COMPOSED_KINDS = {4: "arith", 5: "bits", 6: "maybe_equal"}
+# ... and a whole permutation (include/plonk_mi355x.h, PM_PLONK_PERMUTATION_HADES: count = rounds, param = full rounds)
+PLONK_PERMUTATION_HADES = 7
+PLONK_PERMUTATION_KINDS = {7: "hades"}
+PLONK_HADES_WIDTH = 5
 
 NTT_INVERSE = 1
 NTT_COSET = 2

@@ -190,7 +190,8 @@ struct GadgetRec {
   uint32_t first_row, count;
   uint32_t in_var[2];
   uint32_t index;          // the caller's index: what a report names
-  uint32_t tab;            // FIXED_BASE: its first round in the table-point array; ARITH: its first row in the coefficient array
+  uint32_t tab;            // FIXED_BASE: its first round in the table-point array; ARITH: its first row in the coefficient array;
+                           // HADES: its first round in the round-coefficient and round-id arrays
 };
 struct GadgetGroup {
   uint32_t kind, first, count;
@@ -199,14 +200,17 @@ struct GadgetGroup {
 // set time: *d_bad = the lowest index among the records whose claimed rows miss what their kind needs (~0: none), the table
 // points of the fixed-base records into d_tab and the coefficients of the ARITH rows into d_coef.  d_sel: values on H, either
 // q_l q_r q_range q_logic q_fixed_group_add q_variable_group_add (all11 = false: tables of the four widget kinds) or all eleven
-// selectors in the order of PM_PLONK_SELECTORS, which the composed kinds need; d_wire_vars is read for those only.  Asynchronous.
+// selectors in the order of PM_PLONK_SELECTORS, which the composed kinds need; d_wire_vars is read for those only.  HADES
+// records: per round 30 coefficients (slot 5 i + j = matrix entry (i, j), slot 25 + j = round key j; 960 bytes) into d_hcoef
+// and 30 c ids (slot 5 k + j: key row, x2, x4, x5 of word j for k = 0..3; slot 20 + 2 i + k: z_i, o_i; PM_PLONK_NO_VAR for
+// the s-box rows a partial round does not have; 120 bytes) into d_hids, which the call presets.  Asynchronous.
 int gadget_verify(pm_ctx* ctx, const void* d_recs, uint32_t count, size_t n, const void* d_sel, bool all11, const void* d_wire_vars,
-                  void* d_tab, void* d_coef, uint32_t* d_bad, hipStream_t st);
+                  void* d_tab, void* d_coef, void* d_hcoef, void* d_hids, size_t hades_rounds, uint32_t* d_bad, hipStream_t st);
 // one launch per group on st; d_rep: 2 x batch words (failing gadgets, then min(index * 4 + reason)), copied to rep_host after
 // the launches when it is given -- the call then waits for the stream
 int gadget_fill(pm_ctx* ctx, const void* d_recs, const GadgetGroup* groups, size_t n_groups, const void* d_wire_vars, size_t n,
-                const void* d_tab, const void* d_coef, void* d_vars, size_t var_stride, uint32_t batch, void* d_rep,
-                unsigned long long* rep_host, hipStream_t st);
+                const void* d_tab, const void* d_coef, const void* d_hcoef, const void* d_hids, void* d_vars, size_t var_stride,
+                uint32_t batch, void* d_rep, unsigned long long* rep_host, hipStream_t st);
 // Per-proof constants of the proof-batched kernels (pm_plonk_prove_batch): a pinned host buffer and its device twin of the
 // same size.  A launcher takes one region of both, fills the host side and sends it with one async copy on its stream;
 // kernels read the device side as a table indexed by the proof.  reset() once per call, after the previous call has

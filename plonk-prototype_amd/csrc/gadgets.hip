@@ -1,15 +1,19 @@
 // Gadget witnesses: the inverse of the witness check.  Given the inputs of a range, logic, fixed-base
 // or curve-addition gadget, write the variables that make its rows hold (definitions: include/plonk_mi355x.h, pm_plonk_gadget).
-// Section 7.2g adds the gadgets a circuit composes from arithmetic rows: runs of them, bit decompositions and maybe_equal.
+// Section 7.2g adds the gadgets a circuit composes from arithmetic rows: runs of them, bit decompositions and maybe_equal;
+// section 7.2h the rows of a whole Hades permutation.
 //
 //   gadget_verify_kernel       set time: every claimed row has its kind's selector, the table points of the fixed-base rounds
 //                              are gathered from q_l / q_r into a compact array
-//   composed_verify_kernel     set time, composed kinds: arithmetic rows without a widget, the coefficients and wire ids a BITS
-//                              or MAYBE_EQUAL layout implies; gathers q_m q_l q_r q_4 q_c of the ARITH rows
+//   composed_verify_kernel     set time, composed kinds: arithmetic rows without a widget, the coefficients and wire ids a BITS,
+//                              MAYBE_EQUAL or HADES layout implies; gathers q_m q_l q_r q_4 q_c of the ARITH rows and, round by
+//                              round, the round keys, matrix entries and c ids of the HADES rows
 //   gadget_arith_kernel        one thread per (gadget, proof): c = q_m a b + q_l a + q_r b + q_4 d + q_c, row after row
 //   gadget_bits_kernel         one thread per (gadget, proof, bit): acc_k = acc_(-1) + (V mod 2^(k+1)) is a masked copy of V, so
 //                              no bit waits for another
 //   gadget_maybe_equal_kernel  one thread per (gadget, proof): u = a - b, z = 1 / u (0 -> 0), y = [u = 0]
+//   gadget_hades_kernel        one WAVE per (gadget, proof): lane 5 i + j < 25 holds state word j and matrix entry (i, j); a round
+//                              is four dependent products (x^2, x^4, x^5, M x) and the row sums go across lanes
 //   gadget_range_kernel        one thread per (gadget, proof): quads of the canonical input, accumulators by 4 acc + quad
 //   gadget_logic_kernel        the same over two inputs, three accumulator columns and the quad products
 //   gadget_curve_add_kernel    one thread per (gadget, proof): the affine law with ONE inversion (of the two denominators' product)
@@ -98,6 +102,8 @@ struct GadgetFill {
   const u32* wire_vars;     // [4][n]
   const u32x4* tab;         // table points, 4 x 16 bytes per round: x | y canonical
   const u32x4* coef;        // ARITH rows, 10 x 16 bytes each: q_m q_l q_r q_4 q_c canonical
+  const u32x4* hcoef;       // HADES rounds, 60 x 16 bytes each: 25 matrix entries, 5 round keys, canonical (context.h)
+  const u32* hids;          // HADES rounds, 30 ids each: the c variables of the round's rows (context.h)
   u32x4* vars;              // [batch][var_stride] canonical
   size_t var_stride, n;
   unsigned long long* rep;  // [batch] failing gadgets, then [batch] min(index * 4 + reason); batch = gridDim.y
@@ -186,11 +192,14 @@ PM_DEV void sel_words(const u32x4* sel, size_t n, u32 s, size_t row, u32 (&w)[8]
   w[0] = lo.x, w[1] = lo.y, w[2] = lo.z, w[3] = lo.w, w[4] = hi.x, w[5] = hi.y, w[6] = hi.z, w[7] = hi.w;
 }
 __global__ void __launch_bounds__(256) composed_verify_kernel(const GadgetRec* recs, const u32x4* sel, size_t n, const u32* wire_vars,
-                                                              u32x4* coef, u32* bad) {
+                                                              u32x4* coef, u32x4* hcoef, u32* hids, u32* bad) {
   const GadgetRec rec = recs[blockIdx.x];
   if (rec.kind < PM_PLONK_COMPOSED_ARITH) return;
   const bool arith = rec.kind == PM_PLONK_COMPOSED_ARITH, bits = rec.kind == PM_PLONK_COMPOSED_BITS;
-  const u32 rows = arith ? rec.count : bits ? 2 * rec.count : 3u;
+  const bool hades = rec.kind == PM_PLONK_PERMUTATION_HADES;
+  // HADES: H full rounds, rec.count - 2 H partial ones, H full ones; 30 rows a full round and 18 a partial one
+  const u32 H = rec.param >> 1, rows_head = 30 * H, rows_mid = 18 * (rec.count - 2 * H);
+  const u32 rows = arith ? rec.count : bits ? 2 * rec.count : hades ? 2 * rows_head + rows_mid : 3u;
   u32 one[8], neg[8];
   fe_canon_pack<FrP>(one, g_one_abi());
   fe_canon_pack<FrP>(neg, gneg(g_one_abi()));
@@ -212,8 +221,54 @@ __global__ void __launch_bounds__(256) composed_verify_kernel(const GadgetRec* r
     u32 want[6] = {CO_ANY, CO_ANY, CO_ANY, CO_NEG, CO_ANY, CO_ANY};
     u32 pw[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const u32 va = wire_vars[row], vb = wire_vars[n + row], vc = wire_vars[2 * n + row];
+    u32 slot[6] = {~0u, ~0u, ~0u, ~0u, ~0u, ~0u};   // HADES: where a selector's value goes in the round's 30 coefficients
+    size_t round = 0;
     if (arith) {
       miss |= vc == PM_PLONK_NO_VAR;
+    } else if (hades) {
+      // the round, whether it is full, and the row's place in it
+      u32 rho, pos;
+      bool full = true;
+      if (t < rows_head) {
+        rho = t / 30, pos = t % 30;
+      } else if (t < rows_head + rows_mid) {
+        rho = H + (t - rows_head) / 18, pos = (t - rows_head) % 18, full = false;
+      } else {
+        rho = rec.count - H + (t - rows_head - rows_mid) / 30, pos = (t - rows_head - rows_mid) % 30;
+      }
+      round = (size_t)rec.tab + rho;
+      const size_t rb = row - pos;                   // the round's first row
+      const u32* const cw = wire_vars + 2 * n;       // the c ids
+      const u32 sbox_rows = full ? 15u : 3u;
+      want[0] = want[1] = want[2] = want[4] = want[5] = CO_ZERO;
+      miss |= vc == PM_PLONK_NO_VAR;
+      u32 id_slot;
+      if (pos < 5) {                                 // s'[j] = s[j] + q_c; s[j] is o_j of the round before
+        want[1] = CO_ONE, want[4] = CO_ANY;
+        slot[4] = 25 + pos;
+        if (rho) miss |= va != cw[rb - 10 + 2 * pos + 1];
+        id_slot = pos;
+      } else if (pos < 5 + sbox_rows) {              // x2 = x x, x4 = x2 x2, x5 = x4 x
+        const u32 u = pos - 5, j = full ? u / 3 : 4u, k = u % 3;
+        const u32 x = cw[rb + j];
+        want[0] = CO_ONE;
+        miss |= va != (k ? cw[row - 1] : x) || vb != (k == 1 ? cw[row - 1] : x);
+        id_slot = 5 * (k + 1) + j;
+      } else {                                       // z_i = M_i0 v0 + M_i1 v1 + M_i2 v2, o_i = M_i3 v3 + M_i4 v4 + z_i
+        const u32 u = pos - 5 - sbox_rows, i = u >> 1, k = u & 1u;
+        u32 v[3];
+#pragma unroll
+        for (u32 e = 0; e < 3; ++e) {
+          const u32 j = 3 * k + e;                   // j = 5 (k = 1, e = 2) is z_i
+          v[e] = j == 5 ? cw[row - 1] : full ? cw[rb + 5 + 3 * j + 2] : j == 4 ? cw[rb + 7] : cw[rb + j];
+        }
+        want[1] = want[2] = CO_ANY, want[5] = k ? CO_ONE : CO_ANY;
+        slot[1] = 5 * i + 3 * k, slot[2] = 5 * i + 3 * k + 1;
+        if (!k) slot[5] = 5 * i + 2;
+        miss |= va != v[0] || vb != v[1] || wire_vars[3 * n + row] != v[2];
+        id_slot = 20 + u;
+      }
+      hids[30 * round + id_slot] = vc;
     } else if (bits) {
       const u32 k = t >> 1;
       if ((t & 1u) == 0) {   // the boolean row: bit * bit - bit
@@ -254,6 +309,11 @@ __global__ void __launch_bounds__(256) composed_verify_kernel(const GadgetRec* r
       miss |= want[s] != CO_ANY && diff != 0;
       if (arith && s != 3) {   // q_m q_l q_r q_c q_4 -> slots 0 1 2 4 3
         u32x4* o = coef + 10 * ((size_t)rec.tab + t) + 2 * (s < 3 ? s : s == 4 ? 4u : 3u);
+        o[0] = u32x4{w[0], w[1], w[2], w[3]};
+        o[1] = u32x4{w[4], w[5], w[6], w[7]};
+      }
+      if (slot[s] != ~0u) {
+        u32x4* o = hcoef + 2 * (30 * round + slot[s]);
         o[0] = u32x4{w[0], w[1], w[2], w[3]};
         o[1] = u32x4{w[4], w[5], w[6], w[7]};
       }
@@ -388,6 +448,52 @@ __global__ void __launch_bounds__(64) gadget_maybe_equal_kernel(const GadgetFill
   st_var(vars, var_id(a, 2, row), u);
   st_var(vars, var_id(a, 0, row + 1), g_to_abi(inv));
   st_var(vars, var_id(a, 2, row + 1), g_sel(g_is_zero(u), g_one_abi(), fe_zero<FrP>()));
+}
+
+// ------------------------------------------------------------------ a Hades permutation of width 5
+PM_DEV Fr fr_shfl(const Fr& v, u32 src) {
+  Fr r;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) r.l[i] = __shfl(v.l[i], (int)src);
+  return r;
+}
+// One wave per (gadget, proof): blockIdx.x = the gadget within the launch, blockIdx.y = the proof.  Lane 5 i + j (i, j < 5) holds
+// state word j and the matrix entry (i, j); lanes 25..63 leave at once and no cross-lane read names them: every source below is
+// 5 i + e or 5 j with e < 5.  The loop and the kind of a round depend on the gadget only, so the 25 lanes stay together; which of
+// x and x^5 a lane keeps is a select.  Every lane of row group i ends a round with z_i and o_i, every lane of column j with
+// x, x^2, x^4, x^5 of word j, so the stores are spread: lane (k, j), k < 4, writes the k-th of the latter four, lanes (i, 0) and
+// (i, 1) write z_i and o_i -- two stores a round and lane, their ids gathered at set time in exactly that order (NO_VAR where a
+// partial round has no such row).  The next round's two coefficients and two ids are loaded before this round's arithmetic.
+// Forms as in gadget_arith_kernel: the state is in the ABI form, one operand of each product goes through g_to_dev.
+__global__ void __launch_bounds__(64) gadget_hades_kernel(const GadgetFill a, u32 first) {
+  const u32 lane = threadIdx.x, proof = blockIdx.y;
+  if (lane >= 25) return;
+  const GadgetRec rec = a.recs[first + blockIdx.x];
+  u32x4* const vars = a.vars + 2 * a.var_stride * proof;
+  const u32 i = lane / 5, j = lane - 5 * i;
+  const u32 R = rec.count, H = rec.param >> 1;
+  const u32x4* const q = a.hcoef + 60 * (size_t)rec.tab;
+  const u32* const ids = a.hids + 30 * (size_t)rec.tab;
+  const u32 slot_a = lane < 20 ? lane : 0, slot_b = 20 + 2 * i + (j & 1u);
+  Fr s = ld_var(vars, var_id(a, 0, (size_t)rec.first_row + j));
+  Fr key = ld_canon(q, 25 + j), m = ld_canon(q, lane);
+  u32 id_a = ids[slot_a], id_b = ids[slot_b];
+#pragma unroll 1
+  for (u32 rho = 0; rho < R; ++rho) {
+    const size_t nx = rho + 1 < R ? rho + 1 : rho;   // the last round loads its own again
+    const Fr key_n = ld_canon(q, 30 * nx + 25 + j), m_n = ld_canon(q, 30 * nx + lane);
+    const u32 id_a_n = ids[30 * nx + slot_a], id_b_n = ids[30 * nx + slot_b];
+    const bool full = rho < H || rho >= R - H;
+    const Fr x = gadd(s, key), xd = g_to_dev(x);
+    const Fr x2 = gmul(xd, x), x4 = gmul(g_to_dev(x2), x2), x5 = gmul(xd, x4);
+    st_var(vars, lane < 20 ? id_a : PM_PLONK_NO_VAR, g_sel(i < 2, g_sel(i == 0, x, x2), g_sel(i == 2, x4, x5)));
+    const Fr p = gmul(g_to_dev(m), g_sel(full || j == 4, x5, x));
+    const Fr z = gadd(gadd(fr_shfl(p, 5 * i), fr_shfl(p, 5 * i + 1)), fr_shfl(p, 5 * i + 2));
+    const Fr o = gadd(gadd(fr_shfl(p, 5 * i + 3), fr_shfl(p, 5 * i + 4)), z);
+    st_var(vars, j < 2 ? id_b : PM_PLONK_NO_VAR, g_sel(j == 0, z, o));
+    s = fr_shfl(o, 5 * j);
+    key = key_n, m = m_n, id_a = id_a_n, id_b = id_b_n;
+  }
 }
 
 // extended coordinates: x = X / Z, y = Y / Z, T = X Y / Z
@@ -555,23 +661,24 @@ __global__ void __launch_bounds__(64) gadget_fixed_base_kernel(const GadgetFill 
 }  // namespace
 
 int gadget_verify(pm_ctx* ctx, const void* d_recs, uint32_t count, size_t n, const void* d_sel, bool all11, const void* d_wire_vars,
-                  void* d_tab, void* d_coef, uint32_t* d_bad, hipStream_t st) {
+                  void* d_tab, void* d_coef, void* d_hcoef, void* d_hids, size_t hades_rounds, uint32_t* d_bad, hipStream_t st) {
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (!st) st = ctx->stream;
   PM_HIP(ctx, hipSetDevice(ctx->device));
   PM_HIP(ctx, hipMemsetAsync(d_bad, 0xff, 4, st));
+  if (hades_rounds) PM_HIP(ctx, hipMemsetAsync(d_hids, 0xff, hades_rounds * 120, st));   // PM_PLONK_NO_VAR where no row writes
   hipLaunchKernelGGL(gadget_verify_kernel, dim3(count), dim3(256), 0, st, (const GadgetRec*)d_recs, (const u32x4*)d_sel, n,
                      all11 ? 1u : 0u, all11 ? 7u : 2u, (u32x4*)d_tab, d_bad);
   if (all11)
     hipLaunchKernelGGL(composed_verify_kernel, dim3(count), dim3(256), 0, st, (const GadgetRec*)d_recs, (const u32x4*)d_sel, n,
-                       (const u32*)d_wire_vars, (u32x4*)d_coef, d_bad);
+                       (const u32*)d_wire_vars, (u32x4*)d_coef, (u32x4*)d_hcoef, (u32*)d_hids, d_bad);
   PM_HIP(ctx, hipGetLastError());
   return PM_OK;
 }
 
 int gadget_fill(pm_ctx* ctx, const void* d_recs, const GadgetGroup* groups, size_t n_groups, const void* d_wire_vars, size_t n,
-                const void* d_tab, const void* d_coef, void* d_vars, size_t var_stride, uint32_t batch, void* d_rep,
-                unsigned long long* rep_host, hipStream_t st) {
+                const void* d_tab, const void* d_coef, const void* d_hcoef, const void* d_hids, void* d_vars, size_t var_stride,
+                uint32_t batch, void* d_rep, unsigned long long* rep_host, hipStream_t st) {
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (!st) st = ctx->stream;
   PM_HIP(ctx, hipSetDevice(ctx->device));
@@ -580,6 +687,8 @@ int gadget_fill(pm_ctx* ctx, const void* d_recs, const GadgetGroup* groups, size
   a.wire_vars = (const u32*)d_wire_vars;
   a.tab = (const u32x4*)d_tab;
   a.coef = (const u32x4*)d_coef;
+  a.hcoef = (const u32x4*)d_hcoef;
+  a.hids = (const u32*)d_hids;
   a.vars = (u32x4*)d_vars;
   a.var_stride = var_stride;
   a.n = n;
@@ -617,8 +726,11 @@ int gadget_fill(pm_ctx* ctx, const void* d_recs, const GadgetGroup* groups, size
             hipLaunchKernelGGL(gadget_bits_kernel, dim3((g.span + 63) / 64, std::min(g.count - lo, 65535u), batch), dim3(64), 0, st, a,
                                g.first + lo);
           break;
-        default:
+        case PM_PLONK_COMPOSED_MAYBE_EQUAL:
           hipLaunchKernelGGL(gadget_maybe_equal_kernel, per_thread, dim3(64), 0, st, a, g.first, g.count);
+          break;
+        default:                       // PM_PLONK_PERMUTATION_HADES; the gadgets along x, at most 2^31 - 1 a launch
+          hipLaunchKernelGGL(gadget_hades_kernel, per_wave, dim3(64), 0, st, a, g.first);
           break;
       }
     }

@@ -179,7 +179,7 @@ class UnsatisfiedWitness(ValueError):
 @dataclass(frozen=True)
 class Gadget:
     """``pm_plonk_gadget``: one widget gadget of a composer-form circuit whose rows ``ProverKey.fill_gadgets`` fills from
-    its input variables (the definitions are in include/plonk_mi355x.h; DESIGN.md sections 7.2f and 7.2g).  Gadgets of one ``level``
+    its input variables (the definitions are in include/plonk_mi355x.h; DESIGN.md sections 7.2f to 7.2h).  Gadgets of one ``level``
     are independent; levels run in rising order, and a list given to ``ProverKey.set_gadgets`` is sorted by level."""
     kind: int
     first_row: int
@@ -232,6 +232,20 @@ class Gadget:
         rows that follow, one level later.  -> [bits, maybe_equal]"""
         return [cls.bits(first_row, num_bits, value_var, level), cls.maybe_equal(int(first_row) + 2 * int(num_bits), int(level) + 1)]
 
+    @classmethod
+    def hades(cls, first_row: int, rounds: int = 67, full_rounds: int = 8, level: int = 0) -> "Gadget":
+        """One Hades permutation of width 5 (a Poseidon sponge's): ``rounds`` rounds of which the first and the last
+        ``full_rounds`` / 2 are full, 30 rows a full round and 18 a partial one from ``first_row`` on; the state is read from
+        a of the first five rows, the round constants and the matrix are the rows' own coefficients.  The defaults are
+        dusk-hades' (1302 rows)."""
+        return cls(_lib.PLONK_PERMUTATION_HADES, int(first_row), int(rounds), int(level), int(full_rounds), ())
+
+    @property
+    def rows(self) -> int:
+        """The rows the gadget claims, a trailing row included (``pm_plonk_gadget_rows``); 0 for a kind, count or param that
+        ``set_gadgets`` refuses whatever the circuit."""
+        return int(_lib.load().pm_plonk_gadget_rows(C.byref(self._raw())))
+
     def _raw(self) -> "_lib.Gadget":
         iv = tuple(self.in_vars) + (_lib.PLONK_NO_VAR,) * (2 - len(self.in_vars))
         return _lib.Gadget(self.kind, self.level, self.first_row, self.count, self.param, (C.c_uint32 * 2)(*iv))
@@ -265,7 +279,7 @@ class GadgetInputError(ValueError):
             kind = ""
             if gadgets is not None and r.first_gadget is not None and r.first_gadget < len(gadgets):
                 k = gadgets[r.first_gadget].kind
-                name = _lib.PLONK_GADGET_KINDS[k] if k < len(_lib.PLONK_GADGET_KINDS) else _lib.PLONK_COMPOSED_KINDS.get(k, f"kind {k}")
+                name = _lib.PLONK_GADGET_KINDS[k] if k < len(_lib.PLONK_GADGET_KINDS) else {**_lib.PLONK_COMPOSED_KINDS, **_lib.PLONK_PERMUTATION_KINDS}.get(k, f"kind {k}")
                 kind = f" ({name} at row {gadgets[r.first_gadget].first_row})"
             return f"proof {b}: gadget {r.first_gadget}{kind}: {r.first_reason}; {r.failed} failing gadget(s)"
         super().__init__("; ".join(one(b, r) for b, r in sorted(self.reports.items())))
