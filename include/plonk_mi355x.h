@@ -614,7 +614,7 @@ int pm_plonk_preprocess_wires(pm_ctx* ctx, const uint64_t* const selectors[PM_PL
 size_t pm_plonk_key_num_vars(const pm_prover_key* key);
 int pm_plonk_witness_from_vars_dev(pm_ctx* ctx, const pm_prover_key* key, const void* d_vars, size_t var_stride,
                                    uint32_t batch, void* d_witness_out, void* stream);
-/* ---- Gadget witnesses: fill widget rows from their inputs (DESIGN.md sections 7.2f, 7.2g) ----------------------------
+/* ---- Gadget witnesses: fill widget rows from their inputs (DESIGN.md sections 7.2f to 7.2i) ---------------------------
  * In a composer-form circuit most variables are not inputs but the internal accumulators of the four widget gadgets.
  * These calls are the inverse of the witness check: given a gadget's inputs in the variable assignment, write the
  * variables that make its rows hold, on the device, in the layout pm_plonk_witness_from_vars_dev reads.
@@ -673,6 +673,28 @@ int pm_plonk_witness_from_vars_dev(pm_ctx* ctx, const pm_prover_key* key, const 
  *     A full round has 30 rows and a partial one 18: the gadget claims 30 F + 18 (R - F) rows (dusk-hades: R = 67, F = 8,
  *     1302 rows).  It reads a of its first five rows (PM_PLONK_NO_VAR reads as zero; the five may alias) and writes c of
  *     every row, byte for byte what an ARITH run over the same rows writes.
+ * Variable-base scalar multiplication, kind PM_PLONK_GADGET_VAR_BASE = 10 (8 and 9 are no kinds):
+ *   dusk-plonk's variable_base_scalar_mul, one wave per gadget and proof.  count = R rounds, 1 <= R <=
+ *     PM_PLONK_GADGET_MAX_ROUNDS (dusk: 252), param = 0, no in_var; 6 R rows, no trailing row.  Round k is rows 6k .. 6k+5:
+ *       6k    doubling          (a, b, c, d) = (acc.x, acc.y, acc.x, acc.y)      q_variable_group_add != 0
+ *       6k+1  its second row    (dbl.x, dbl.y, -, acc.x acc.y)                   selectors not looked at
+ *       6k+2  select x          (bit_k, P.x, sx, -)   arithmetic, q_m = 1, q_o = -1: sx = bit_k P.x
+ *       6k+3  select y          (bit_k, P.y, sy, -)   arithmetic, q_m = 1, q_l = -1, q_c = 1, q_o = -1: sy = bit_k P.y - bit_k + 1
+ *       6k+4  addition          (dbl.x, dbl.y, sx, sy)                           q_variable_group_add != 0
+ *       6k+5  its second row    (new.x, new.y, -, dbl.x sy)                      selectors not looked at
+ *     with dbl = acc + acc and new = dbl + (sx, sy) under the affine law above, acc of round k + 1 = new of round k; every
+ *     coefficient of a select row that is not named is zero.  bit_0 is the MOST significant bit: from the identity the last
+ *     (a, b) is (sum_k bit_k 2^(R-1-k)) P, from a start point S it is 2^R S plus that.  The gadget READS the start point from
+ *     a, b of row 0 (the caller sets it; dusk uses the identity (0, 1)), bit_k from a of row 6k+2 and P from b of rows 2 and
+ *     3 (PM_PLONK_NO_VAR reads as zero).  It WRITES a, b, d of rows 6k+1 and 6k+5 and c of rows 6k+2 and 6k+3; c of rows
+ *     6k+1 and 6k+5 (dusk's zero variable) is not touched.  The select rows are exactly bit P.x and bit P.y - bit + 1
+ *     whatever value the bit variable has.  While every bit is 0 or 1 and no denominator 1 +- d x1 x2 y1 y2 vanishes, every
+ *     byte equals what CURVE_ADD at rows 6k and 6k+4 and an ARITH run of 2 rows at 6k+2 write on 2R levels -- for ANY field
+ *     elements as start point and P, on the curve or not (the chain runs in the order of the definition, in extended
+ *     coordinates under the unified law, and is normalised with one inversion per lane).  PM_PLONK_GADGET_TOO_WIDE when a
+ *     bit variable is neither 0 nor 1 (it counts as 0 in the chain); PM_PLONK_GADGET_DEGENERATE when a denominator vanishes
+ *     (impossible on the curve); one report a gadget, TOO_WIDE first.  In both cases the select rows are still exact and
+ *     the points and products written are deterministic and unspecified.
  * Gadgets of one level are independent and run together; levels run in rising order, so a gadget may read what a lower
  * level wrote.  Two gadgets of ONE level may name the same variable as an output only where the definitions give both the
  * same value (the zero variable in d of a range's and a fixed-base's row 0, say); any other overlap is a race.  A gadget's
@@ -701,9 +723,17 @@ int pm_plonk_witness_from_vars_dev(pm_ctx* ctx, const pm_prover_key* key, const 
  * The free coefficients are gathered per round (5 round keys and 25 matrix entries, 960 bytes) and so are the c ids of the
  * round's rows (30 ids, 120 bytes), so that the fill never walks the wire map: 1080 bytes a round, counted in added_bytes
  * (R = 67: 64,320 + 8,040 = 72,360 bytes); a table without a HADES gadget holds what it held.  HADES: count >= 1, param even
- * and <= count, at most 2^32 HADES rows in a table.  PM_ERR_BAD_ARG, with pm_last_error naming the lowest offending gadget, for: levels
+ * and <= count, at most 2^32 HADES rows in a table.  VAR_BASE also takes the all-eleven-selectors path and is tested round by
+ * round: q_variable_group_add is non-zero on rows 6k and 6k+4; rows 6k+2 and 6k+3 have q_arith non-zero, no widget selector and
+ * exactly the six coefficients above; the wire map has c = a and d = b on row 6k, a, b of row 6k+4 = a, b of row 6k+1, c, d of
+ * row 6k+4 = c of rows 6k+2 and 6k+3, a of row 6k+3 = a of row 6k+2, b of rows 6k+2 and 6k+3 = b of rows 2 and 3, a, b of row
+ * 6(k+1) = a, b of row 6k+5; and every written position is a variable -- so an accepted gadget is satisfied by what the fill
+ * writes, provided its written variables are distinct from one another and from those it reads (start point, bits, P), which is
+ * not tested and stays the caller's to keep.  It keeps nothing beyond its record: the fill reads the ids of its rows from the
+ * key's wire map (a lane those of its own <= 4 rounds), so added_bytes grows by the 32 bytes of the record alone.  VAR_BASE:
+ * 1 <= count <= PM_PLONK_GADGET_MAX_ROUNDS, param = 0; kinds 8 and 9 are refused as unknown.  PM_ERR_BAD_ARG, with pm_last_error naming the lowest offending gadget, for: levels
  * not in rising order, an unknown kind or param, rows (the trailing row included) outside [0, n), a claimed row whose
- * selector is zero, a used in_var >= num_vars, count = 0 or a fixed-base count above PM_PLONK_GADGET_MAX_ROUNDS, a key
+ * selector is zero, a used in_var >= num_vars, count = 0 or a fixed-base or variable-base count above PM_PLONK_GADGET_MAX_ROUNDS, a key
  * that was not built from wires.  After a refusal the key keeps the table it had.  added_bytes (may be NULL): the device
  * bytes the table holds.  pm_plonk_key_free frees it.
  * pm_plonk_fill_gadgets_dev fills batch x var_stride assignments in place (var_stride >= num_vars, 1 <= batch <=
@@ -724,10 +754,11 @@ int pm_plonk_witness_from_vars_dev(pm_ctx* ctx, const pm_prover_key* key, const 
 #define PM_PLONK_COMPOSED_MAX_BITS 256u
 #define PM_PLONK_PERMUTATION_HADES 7u      /* kind 7: count = rounds R, param = full rounds F */
 #define PM_PLONK_HADES_WIDTH 5u
+#define PM_PLONK_GADGET_VAR_BASE (10u)     /* kind 10: count = rounds R <= PM_PLONK_GADGET_MAX_ROUNDS; 8 and 9 are no kinds */
 typedef struct pm_plonk_gadget {
   uint32_t kind, level;     /* gadgets of a level are independent; levels run in rising order */
   uint64_t first_row;
-  uint32_t count;           /* RANGE: rows m (8m bits); LOGIC: quads Q; FIXED_BASE: rounds R; CURVE_ADD: ignored; HADES: rounds R */
+  uint32_t count;           /* RANGE: rows m (8m bits); LOGIC: quads Q; FIXED_BASE: rounds R; CURVE_ADD: ignored; HADES, VAR_BASE: rounds R */
   uint32_t param;           /* LOGIC: 0 = AND, 1 = XOR; HADES: full rounds F; otherwise 0 */
   uint32_t in_var[2];       /* RANGE: value; LOGIC: a, b; FIXED_BASE: scalar; unused = PM_PLONK_NO_VAR */
 } pm_plonk_gadget;
@@ -741,7 +772,7 @@ int pm_plonk_key_set_gadgets(pm_ctx* ctx, pm_prover_key* key, const pm_plonk_gad
 int pm_plonk_fill_gadgets_dev(pm_ctx* ctx, const pm_prover_key* key, void* d_vars, size_t var_stride, uint32_t batch,
                               pm_plonk_gadget_report* reports, void* stream);
 /* Pure host, no context: the rows a gadget claims, its trailing row included (RANGE, LOGIC, FIXED_BASE: count + 1; CURVE_ADD:
- * 2; ARITH: count; BITS: 2 count; MAYBE_EQUAL: 3; HADES: 30 F + 18 (R - F)).  0 for NULL, an unknown kind and a count or param
+ * 2; ARITH: count; BITS: 2 count; MAYBE_EQUAL: 3; HADES: 30 F + 18 (R - F); VAR_BASE: 6 R).  0 for NULL, an unknown kind and a count or param
  * that pm_plonk_key_set_gadgets refuses on its own: count 0 where a count is needed, a count above its kind's cap, HADES with
  * F odd or F > R. */
 uint64_t pm_plonk_gadget_rows(const pm_plonk_gadget* g);

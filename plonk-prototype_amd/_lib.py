@@ -272,6 +272,9 @@ PLONK_COMPOSED_KINDS = {4: "arith", 5: "bits", 6: "maybe_equal"}
 PLONK_PERMUTATION_HADES = 7
 PLONK_PERMUTATION_KINDS = {7: "hades"}
 PLONK_HADES_WIDTH = 5
+# ... and a variable-base scalar multiplication (PM_PLONK_GADGET_VAR_BASE: count = rounds; 8 and 9 are no kinds)
+PLONK_GADGET_VAR_BASE = 10
+PLONK_CHAIN_KINDS = {10: "variable_base"}
 
 NTT_INVERSE = 1
 NTT_COSET = 2

@@ -1,13 +1,14 @@
 // Gadget witnesses: the inverse of the witness check.  Given the inputs of a range, logic, fixed-base
 // or curve-addition gadget, write the variables that make its rows hold (definitions: include/plonk_mi355x.h, pm_plonk_gadget).
 // Section 7.2g adds the gadgets a circuit composes from arithmetic rows: runs of them, bit decompositions and maybe_equal;
-// section 7.2h the rows of a whole Hades permutation.
+// section 7.2h the rows of a whole Hades permutation; section 7.2i those of a variable-base scalar multiplication.
 //
 //   gadget_verify_kernel       set time: every claimed row has its kind's selector, the table points of the fixed-base rounds
 //                              are gathered from q_l / q_r into a compact array
 //   composed_verify_kernel     set time, composed kinds: arithmetic rows without a widget, the coefficients and wire ids a BITS,
 //                              MAYBE_EQUAL or HADES layout implies; gathers q_m q_l q_r q_4 q_c of the ARITH rows and, round by
-//                              round, the round keys, matrix entries and c ids of the HADES rows
+//                              round, the round keys, matrix entries and c ids of the HADES rows; VAR_BASE: the selectors,
+//                              select-row coefficients and wire ids of its six rows a round
 //   gadget_arith_kernel        one thread per (gadget, proof): c = q_m a b + q_l a + q_r b + q_4 d + q_c, row after row
 //   gadget_bits_kernel         one thread per (gadget, proof, bit): acc_k = acc_(-1) + (V mod 2^(k+1)) is a masked copy of V, so
 //                              no bit waits for another
@@ -25,6 +26,9 @@
 //        trick).  No lane ever runs more than one inversion and there is no chain of dependent per-round inversions.
 //        The addends are re-derived from the table in both walks rather than kept across the scan: what stays live over the
 //        scan is one point, and over the second walk the run's X, Y, Z (the variant kept: see DESIGN.md for the registers).
+//   gadget_var_base_kernel     one WAVE per (gadget, proof): every lane walks the same double-and-add chain in extended
+//        coordinates (a wave instruction costs the same for 64 lanes as for one), lane l keeps the points of rounds
+//        l L .. (l + 1) L - 1, L = ceil(R / 64), and normalises them with its one inversion.  No per-round inversion.
 //
 // Forms: variables are canonical Montgomery ("ABI", x 2^256); the point arithmetic runs in the device form x 2^261
 // (poly_common.hip.h).  Everything written goes through fe_store, i.e. is canonical.
@@ -196,10 +200,10 @@ __global__ void __launch_bounds__(256) composed_verify_kernel(const GadgetRec* r
   const GadgetRec rec = recs[blockIdx.x];
   if (rec.kind < PM_PLONK_COMPOSED_ARITH) return;
   const bool arith = rec.kind == PM_PLONK_COMPOSED_ARITH, bits = rec.kind == PM_PLONK_COMPOSED_BITS;
-  const bool hades = rec.kind == PM_PLONK_PERMUTATION_HADES;
+  const bool hades = rec.kind == PM_PLONK_PERMUTATION_HADES, vbase = rec.kind == PM_PLONK_GADGET_VAR_BASE;
   // HADES: H full rounds, rec.count - 2 H partial ones, H full ones; 30 rows a full round and 18 a partial one
   const u32 H = rec.param >> 1, rows_head = 30 * H, rows_mid = 18 * (rec.count - 2 * H);
-  const u32 rows = arith ? rec.count : bits ? 2 * rec.count : hades ? 2 * rows_head + rows_mid : 3u;
+  const u32 rows = arith ? rec.count : bits ? 2 * rec.count : hades ? 2 * rows_head + rows_mid : vbase ? 6 * rec.count : 3u;
   u32 one[8], neg[8];
   fe_canon_pack<FrP>(one, g_one_abi());
   fe_canon_pack<FrP>(neg, gneg(g_one_abi()));
@@ -207,16 +211,20 @@ __global__ void __launch_bounds__(256) composed_verify_kernel(const GadgetRec* r
   for (u32 t = threadIdx.x; t < rows; t += 256) {
     const size_t row = (size_t)rec.first_row + t;
     u32 w[8];
-    // an arithmetic row and nothing else
+    // an arithmetic row and nothing else; VAR_BASE: that on its select rows (2, 3 of six), q_variable_group_add on rows 0
+    // and 4, and rows 1 and 5 carry results only: their selectors are not looked at
+    const u32 pos = vbase ? t % 6 : 2u;
     sel_words(sel, n, 6, row, w);
-    miss |= (w[0] | w[1] | w[2] | w[3] | w[4] | w[5] | w[6] | w[7]) == 0;
-    u32 widget = 0;
+    const bool no_arith = (w[0] | w[1] | w[2] | w[3] | w[4] | w[5] | w[6] | w[7]) == 0;
+    u32 widget = 0, last = 0;
 #pragma unroll
     for (u32 s = 7; s < 11; ++s) {
       sel_words(sel, n, s, row, w);
-      widget |= w[0] | w[1] | w[2] | w[3] | w[4] | w[5] | w[6] | w[7];
+      last = w[0] | w[1] | w[2] | w[3] | w[4] | w[5] | w[6] | w[7];
+      widget |= last;
     }
-    miss |= widget != 0;
+    if (pos == 2 || pos == 3) miss |= no_arith || widget != 0;
+    else if (pos == 0 || pos == 4) miss |= last == 0;
     // q_m q_l q_r q_o q_c q_4
     u32 want[6] = {CO_ANY, CO_ANY, CO_ANY, CO_NEG, CO_ANY, CO_ANY};
     u32 pw[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -225,6 +233,27 @@ __global__ void __launch_bounds__(256) composed_verify_kernel(const GadgetRec* r
     size_t round = 0;
     if (arith) {
       miss |= vc == PM_PLONK_NO_VAR;
+    } else if (vbase) {
+      const u32 vd = wire_vars[3 * n + row];
+      const size_t r0 = rec.first_row, rb = row - pos;   // the gadget's and the round's first row
+      const u32* const aw = wire_vars;
+      const u32* const bw = wire_vars + n;
+      const u32* const cw = wire_vars + 2 * n;
+      want[3] = CO_ANY;
+      if (pos == 0) {          // acc + acc; acc is what the round before wrote
+        miss |= vc != va || vd != vb;
+        if (rb != r0) miss |= va != aw[rb - 1] || vb != bw[rb - 1];
+      } else if (pos == 1 || pos == 5) {   // a result row: x, y and the product are written
+        miss |= va == PM_PLONK_NO_VAR || vb == PM_PLONK_NO_VAR || vd == PM_PLONK_NO_VAR;
+      } else if (pos == 2) {   // sx = bit P.x
+        want[0] = CO_ONE, want[3] = CO_NEG, want[1] = want[2] = want[4] = want[5] = CO_ZERO;
+        miss |= vc == PM_PLONK_NO_VAR || vb != bw[r0 + 2];
+      } else if (pos == 3) {   // sy = bit P.y - bit + 1
+        want[0] = CO_ONE, want[1] = CO_NEG, want[3] = CO_NEG, want[4] = CO_ONE, want[2] = want[5] = CO_ZERO;
+        miss |= vc == PM_PLONK_NO_VAR || va != aw[row - 1] || vb != bw[r0 + 3];
+      } else {                 // dbl + (sx, sy)
+        miss |= va != aw[rb + 1] || vb != bw[rb + 1] || vc != cw[rb + 2] || vd != cw[rb + 3];
+      }
     } else if (hades) {
       // the round, whether it is full, and the row's place in it
       u32 rho, pos;
@@ -658,6 +687,112 @@ __global__ void __launch_bounds__(64) gadget_fixed_base_kernel(const GadgetFill 
   }
 }
 
+// ------------------------------------------------------------------ variable-base scalar multiplication
+constexpr u32 VB_RUN = PM_PLONK_GADGET_MAX_ROUNDS / 64;   // rounds a lane owns at most
+// One wave per (gadget, proof): blockIdx.x = the gadget within the launch, blockIdx.y = the proof.  Round k of the chain is
+// dbl = acc + acc (the unified law: start and P may lie off the curve, so no formula that uses the curve equation) and
+// new = dbl + (bit_k P.x, bit_k P.y - bit_k + 1), which for a bit of 0 is dbl itself.  The chain is R rounds deep whatever is
+// done, so ALL 64 lanes walk ALL of it, in step: the loop, the bit of a round and the branch on it are wave-uniform.  What the
+// lanes share out is the rest: lane l owns rounds l L .. (l + 1) L - 1, L = ceil(R / 64).  It reads the bits of its rounds
+// (a ballot per slot turns them into wave-uniform masks), writes their select rows, keeps X, Y, Z of dbl and new when the
+// chain passes through them, inverts the product of those <= 2 L values of Z once (all 64 lanes reach fe_inv_dev, which votes
+// across the wave) and writes its rounds.  A lane without a round keeps Z = 1.  Some Z of the chain is zero exactly when a
+// denominator of the affine law vanishes in that round, and the lane that owns the round sees it in its product.
+__global__ void __launch_bounds__(64) gadget_var_base_kernel(const GadgetFill a, u32 first) {
+  const u32 lane = threadIdx.x, proof = blockIdx.y;
+  const GadgetRec rec = a.recs[first + blockIdx.x];
+  u32x4* const vars = a.vars + 2 * a.var_stride * proof;
+  const u32 R = rec.count, L = (R + 63) >> 6, k0 = lane * L;
+  const size_t row0 = rec.first_row;
+  const Fr d = fr_limbs(a.edwards_d), one = fe_one<FrP>(), zero = fe_zero<FrP>(), one_abi = g_one_abi();
+
+  // ---- the start point and P, every lane reads the same words
+  const Fr sx_abi = ld_var(vars, var_id(a, 0, row0)), sy_abi = ld_var(vars, var_id(a, 1, row0));
+  const Fr px_abi = ld_var(vars, var_id(a, 1, row0 + 2)), py_abi = ld_var(vars, var_id(a, 1, row0 + 3));
+  const Fr px = g_to_dev(px_abi), py = g_to_dev(py_abi), pt = gmul(px, py);
+
+  // ---- this lane's bits and select rows: exact for any value of the bit variable
+  unsigned long long ones[VB_RUN];   // bit l of ones[j]: the bit of round l L + j is 1
+  u32 mine = 0;
+  bool wide = false;
+#pragma unroll
+  for (u32 j = 0; j < VB_RUN; ++j) {
+    const u32 k = k0 + j;
+    const bool valid = j < L && k < R;
+    const size_t row = row0 + 6 * (size_t)(valid ? k : 0);
+    const Fr bit = ld_var(vars, var_id(a, 0, row + 2)), bit_dev = g_to_dev(bit);
+    const bool is_one = g_is_zero(gsub(bit, one_abi));
+    wide |= valid && !is_one && !g_is_zero(bit);
+    if (valid) {
+      st_var(vars, var_id(a, 2, row + 2), gmul(bit_dev, px_abi));
+      st_var(vars, var_id(a, 2, row + 3), gadd(gsub(gmul(bit_dev, py_abi), bit), one_abi));
+    }
+    ones[j] = __ballot(valid && is_one);
+    mine |= valid && is_one ? 1u << j : 0u;
+  }
+
+  // ---- the chain
+  const Fr sx = g_to_dev(sx_abi), sy = g_to_dev(sy_abi);
+  EdPoint Q{sx, sy, one, gmul(sx, sy)};
+  Fr DX[VB_RUN], DY[VB_RUN], DZ[VB_RUN], NX[VB_RUN], NY[VB_RUN], NZ[VB_RUN];
+#pragma unroll
+  for (u32 j = 0; j < VB_RUN; ++j) DX[j] = NX[j] = zero, DY[j] = NY[j] = DZ[j] = NZ[j] = one;
+  u32 owner = 0, slot = 0;           // round k = owner L + slot
+#pragma unroll 1
+  for (u32 k = 0; k < R; ++k) {
+    const unsigned long long m = slot == 0 ? ones[0] : slot == 1 ? ones[1] : slot == 2 ? ones[2] : ones[3];
+    const EdPoint D = ed_add(Q, Q, d);
+    Q = D;
+    if ((m >> owner) & 1ull) Q = ed_madd(D, px, py, pt, d);
+#pragma unroll
+    for (u32 j = 0; j < VB_RUN; ++j) {
+      const bool keep = owner == lane && slot == j;
+      DX[j] = g_sel(keep, D.X, DX[j]), DY[j] = g_sel(keep, D.Y, DY[j]), DZ[j] = g_sel(keep, D.Z, DZ[j]);
+      NX[j] = g_sel(keep, Q.X, NX[j]), NY[j] = g_sel(keep, Q.Y, NY[j]), NZ[j] = g_sel(keep, Q.Z, NZ[j]);
+    }
+    if (++slot == L) slot = 0, ++owner;
+  }
+
+  // ---- one inversion for the lane's <= 2 L points (Montgomery's trick), then its rows
+  Fr pre[2 * VB_RUN];
+  Fr prod = one;
+#pragma unroll
+  for (u32 j = 0; j < VB_RUN; ++j) {
+    if (j < L) {
+      pre[2 * j] = prod;
+      prod = gmul(prod, DZ[j]);
+      pre[2 * j + 1] = prod;
+      prod = gmul(prod, NZ[j]);
+    }
+  }
+  const bool any_wide = __any(wide), any_zero = __any(g_is_zero(prod));
+  if (lane == 0 && (any_wide || any_zero))   // one report a gadget; a wide bit comes first
+    gadget_fail(a, proof, rec.index, any_wide ? PM_PLONK_GADGET_TOO_WIDE : PM_PLONK_GADGET_DEGENERATE);
+  Fr inv = fe_inv_dev<FrP>(prod);    // 0 -> 0: the lane that owns a degenerate round writes zeros; all 64 lanes are here
+  if (lane == 0) st_var(vars, var_id(a, 3, row0 + 1), gmul(sx, sy_abi));
+#pragma unroll
+  for (int j = VB_RUN - 1; j >= 0; --j) {
+    if ((u32)j < L) {
+      const u32 k = k0 + j;
+      const Fr zn = g_to_abi(gmul(inv, pre[2 * j + 1]));   // 1 / Z, ABI form: device x ABI -> ABI below
+      inv = gmul(inv, NZ[j]);
+      const Fr zd = g_to_abi(gmul(inv, pre[2 * j]));
+      inv = gmul(inv, DZ[j]);
+      if (k < R) {
+        const size_t row = row0 + 6 * (size_t)k;
+        const Fr dx = gmul(DX[j], zd), dy = gmul(DY[j], zd), nx = gmul(NX[j], zn), ny = gmul(NY[j], zn);
+        st_var(vars, var_id(a, 0, row + 1), dx);
+        st_var(vars, var_id(a, 1, row + 1), dy);
+        st_var(vars, var_id(a, 0, row + 5), nx);
+        st_var(vars, var_id(a, 1, row + 5), ny);
+        // dbl.x sy with sy = P.y or 1; new.x new.y belongs to the next round's doubling
+        st_var(vars, var_id(a, 3, row + 5), g_sel((mine >> j) & 1u, gmul(g_to_dev(dx), py_abi), dx));
+        if (k + 1 < R) st_var(vars, var_id(a, 3, row + 7), gmul(g_to_dev(nx), ny));
+      }
+    }
+  }
+}
+
 }  // namespace
 
 int gadget_verify(pm_ctx* ctx, const void* d_recs, uint32_t count, size_t n, const void* d_sel, bool all11, const void* d_wire_vars,
@@ -729,8 +864,11 @@ int gadget_fill(pm_ctx* ctx, const void* d_recs, const GadgetGroup* groups, size
         case PM_PLONK_COMPOSED_MAYBE_EQUAL:
           hipLaunchKernelGGL(gadget_maybe_equal_kernel, per_thread, dim3(64), 0, st, a, g.first, g.count);
           break;
-        default:                       // PM_PLONK_PERMUTATION_HADES; the gadgets along x, at most 2^31 - 1 a launch
+        case PM_PLONK_PERMUTATION_HADES:   // the gadgets along x, at most 2^31 - 1 a launch
           hipLaunchKernelGGL(gadget_hades_kernel, per_wave, dim3(64), 0, st, a, g.first);
+          break;
+        default:                       // PM_PLONK_GADGET_VAR_BASE
+          hipLaunchKernelGGL(gadget_var_base_kernel, per_wave, dim3(64), 0, st, a, g.first);
           break;
       }
     }

@@ -1,5 +1,5 @@
 // Gadget witnesses: pm_plonk_key_set_gadgets / pm_plonk_fill_gadgets_dev (included by prover.hip: the key is pm_plonk_prove's;
-// DESIGN.md sections 7.2f to 7.2h).  The kernels and what each gadget writes are in gadgets.hip; here is the table a key holds and the
+// DESIGN.md sections 7.2f to 7.2i).  The kernels and what each gadget writes are in gadgets.hip; here is the table a key holds and the
 // host side of the two calls.
 struct GadgetState {
   size_t bytes = 0;                        // device bytes held
@@ -13,7 +13,7 @@ struct GadgetState {
   std::vector<pm::GadgetGroup> groups;     // one launch each, levels rising
 };
 
-// the rows a gadget claims (the widget kinds: the trailing row included; the composed kinds and HADES have none); 0: a kind,
+// the rows a gadget claims (the widget kinds: the trailing row included; the composed kinds, HADES and VAR_BASE have none); 0: a kind,
 // count or param that is refused whatever the circuit
 extern "C" uint64_t pm_plonk_gadget_rows(const pm_plonk_gadget* g) {
   if (!g) return 0;
@@ -34,6 +34,8 @@ extern "C" uint64_t pm_plonk_gadget_rows(const pm_plonk_gadget* g) {
       return 3;
     case PM_PLONK_PERMUTATION_HADES:   // 30 rows a full round, 18 a partial one
       return c && !(f & 1) && f <= c ? 30 * f + 18 * (c - f) : 0;
+    case PM_PLONK_GADGET_VAR_BASE:     // doubling, select x, select y, addition: 2 + 1 + 1 + 2 rows a round
+      return c && c <= PM_PLONK_GADGET_MAX_ROUNDS ? 6 * c : 0;
     default:
       return 0;
   }
@@ -50,18 +52,18 @@ void gadget_state_free(pm_ctx* ctx, GadgetState* gs) {
 // what the host can tell about gadget g; empty = nothing
 std::string gadget_host_fault(const pm_plonk_gadget& g, const pm_plonk_gadget* prev, size_t n, size_t num_vars) {
   if (prev && g.level < prev->level) return "levels must not fall";
-  if (g.kind > PM_PLONK_PERMUTATION_HADES) return "unknown kind";
-  const bool hades = g.kind == PM_PLONK_PERMUTATION_HADES;
+  const bool hades = g.kind == PM_PLONK_PERMUTATION_HADES, vbase = g.kind == PM_PLONK_GADGET_VAR_BASE;
+  if (g.kind > PM_PLONK_PERMUTATION_HADES && !vbase) return "unknown kind";   // 8 and 9 are no kinds
   if (!hades && g.param > (g.kind == PM_PLONK_GADGET_LOGIC ? 1u : 0u)) return "unknown param";
   const bool add = g.kind == PM_PLONK_GADGET_CURVE_ADD, eq = g.kind == PM_PLONK_COMPOSED_MAYBE_EQUAL;
   const bool run = g.kind == PM_PLONK_COMPOSED_ARITH, bits = g.kind == PM_PLONK_COMPOSED_BITS;
   if (!add && !eq && g.count == 0) return "count is 0";
-  if (g.kind == PM_PLONK_GADGET_FIXED_BASE && g.count > PM_PLONK_GADGET_MAX_ROUNDS) return "more than PM_PLONK_GADGET_MAX_ROUNDS rounds";
+  if ((g.kind == PM_PLONK_GADGET_FIXED_BASE || vbase) && g.count > PM_PLONK_GADGET_MAX_ROUNDS) return "more than PM_PLONK_GADGET_MAX_ROUNDS rounds";
   if (bits && g.count > PM_PLONK_COMPOSED_MAX_BITS) return "more than PM_PLONK_COMPOSED_MAX_BITS bits";
   if (hades && ((g.param & 1u) || g.param > g.count)) return "its full rounds (param) must be even and at most its rounds (count)";
   const uint64_t rows = pm_plonk_gadget_rows(&g);   // not 0: what makes it 0 was refused above
   if (g.first_row >= n || rows > n - g.first_row) return "its rows leave [0, n)";
-  const int used = add || eq || run || hades ? 0 : g.kind == PM_PLONK_GADGET_LOGIC ? 2 : 1;
+  const int used = add || eq || run || hades || vbase ? 0 : g.kind == PM_PLONK_GADGET_LOGIC ? 2 : 1;
   for (int i = 0; i < used; ++i)
     if (g.in_var[i] >= num_vars) return "in_var is not below num_vars";
   return "";
@@ -97,7 +99,7 @@ extern "C" int pm_plonk_key_set_gadgets(pm_ctx* ctx, pm_prover_key* pk, const pm
   for (size_t lo = 0; lo < lim;) {
     size_t hi = lo;
     while (hi < lim && gadgets[hi].level == gadgets[lo].level) ++hi;
-    for (uint32_t kind = 0; kind <= PM_PLONK_PERMUTATION_HADES; ++kind) {
+    for (uint32_t kind = 0; kind <= PM_PLONK_GADGET_VAR_BASE; ++kind) {
       pm::GadgetGroup grp{kind, (uint32_t)recs.size(), 0, 0};
       for (size_t i = lo; i < hi; ++i) {
         const pm_plonk_gadget& g = gadgets[i];
@@ -161,7 +163,9 @@ extern "C" int pm_plonk_key_set_gadgets(pm_ctx* ctx, pm_prover_key* pk, const pm
   if (rc == PM_OK && bad != 0xffffffffu)
     rc = pm::set_err(ctx, PM_ERR_BAD_ARG,
                      "gadget " + std::to_string(bad) +
-                         (gadgets[bad].kind >= PM_PLONK_COMPOSED_ARITH
+                         (gadgets[bad].kind == PM_PLONK_GADGET_VAR_BASE
+                              ? ": a row it claims is not the row a variable-base round lays out (selectors, coefficients or wire variables)"
+                          : gadgets[bad].kind >= PM_PLONK_COMPOSED_ARITH
                               ? ": a row it claims is not the arithmetic row its kind lays out (selectors, coefficients or wire variables)"
                               : ": a row it claims does not have its kind's selector"));
   else if (rc == PM_OK && lim < count)

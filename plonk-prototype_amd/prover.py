@@ -179,7 +179,7 @@ class UnsatisfiedWitness(ValueError):
 @dataclass(frozen=True)
 class Gadget:
     """``pm_plonk_gadget``: one widget gadget of a composer-form circuit whose rows ``ProverKey.fill_gadgets`` fills from
-    its input variables (the definitions are in include/plonk_mi355x.h; DESIGN.md sections 7.2f to 7.2h).  Gadgets of one ``level``
+    its input variables (the definitions are in include/plonk_mi355x.h; DESIGN.md sections 7.2f to 7.2i).  Gadgets of one ``level``
     are independent; levels run in rising order, and a list given to ``ProverKey.set_gadgets`` is sorted by level."""
     kind: int
     first_row: int
@@ -240,6 +240,13 @@ class Gadget:
         dusk-hades' (1302 rows)."""
         return cls(_lib.PLONK_PERMUTATION_HADES, int(first_row), int(rounds), int(level), int(full_rounds), ())
 
+    @classmethod
+    def variable_base(cls, first_row: int, rounds: int = 252, level: int = 0) -> "Gadget":
+        """dusk-plonk's ``variable_base_scalar_mul``: ``rounds`` rounds of six rows from ``first_row`` on (a doubling, the two
+        rows that select bit P, an addition).  The start point is read from a, b of the first row, bit k from a of row 6k + 2
+        (most significant first) and P from b of rows 2 and 3; one wave fills the whole chain.  The default is dusk's 252."""
+        return cls(_lib.PLONK_GADGET_VAR_BASE, int(first_row), int(rounds), int(level), 0, ())
+
     @property
     def rows(self) -> int:
         """The rows the gadget claims, a trailing row included (``pm_plonk_gadget_rows``); 0 for a kind, count or param that
@@ -279,7 +286,7 @@ class GadgetInputError(ValueError):
             kind = ""
             if gadgets is not None and r.first_gadget is not None and r.first_gadget < len(gadgets):
                 k = gadgets[r.first_gadget].kind
-                name = _lib.PLONK_GADGET_KINDS[k] if k < len(_lib.PLONK_GADGET_KINDS) else {**_lib.PLONK_COMPOSED_KINDS, **_lib.PLONK_PERMUTATION_KINDS}.get(k, f"kind {k}")
+                name = _lib.PLONK_GADGET_KINDS[k] if k < len(_lib.PLONK_GADGET_KINDS) else {**_lib.PLONK_COMPOSED_KINDS, **_lib.PLONK_PERMUTATION_KINDS, **_lib.PLONK_CHAIN_KINDS}.get(k, f"kind {k}")
                 kind = f" ({name} at row {gadgets[r.first_gadget].first_row})"
             return f"proof {b}: gadget {r.first_gadget}{kind}: {r.first_reason}; {r.failed} failing gadget(s)"
         super().__init__("; ".join(one(b, r) for b, r in sorted(self.reports.items())))
