@@ -190,27 +190,37 @@ struct GadgetRec {
   uint32_t first_row, count;
   uint32_t in_var[2];
   uint32_t index;          // the caller's index: what a report names
-  uint32_t tab;            // FIXED_BASE: its first round in the table-point array; ARITH: its first row in the coefficient array;
-                           // HADES: its first round in the round-coefficient and round-id arrays
+  uint32_t tab;            // its first unit in the array its kind gathers into (gadget_kinds.h, GadgetTab)
 };
 struct GadgetGroup {
   uint32_t kind, first, count;
   uint32_t span;           // BITS: the largest count of the group (the bits run along the grid's x)
 };
-// set time: *d_bad = the lowest index among the records whose claimed rows miss what their kind needs (~0: none), the table
-// points of the fixed-base records into d_tab and the coefficients of the ARITH rows into d_coef.  d_sel: values on H, either
-// q_l q_r q_range q_logic q_fixed_group_add q_variable_group_add (all11 = false: tables of the four widget kinds) or all eleven
-// selectors in the order of PM_PLONK_SELECTORS, which the composed kinds need; d_wire_vars is read for those only.  HADES
-// records: per round 30 coefficients (slot 5 i + j = matrix entry (i, j), slot 25 + j = round key j; 960 bytes) into d_hcoef
-// and 30 c ids (slot 5 k + j: key row, x2, x4, x5 of word j for k = 0..3; slot 20 + 2 i + k: z_i, o_i; PM_PLONK_NO_VAR for
-// the s-box rows a partial round does not have; 120 bytes) into d_hids, which the call presets.  Asynchronous.
-int gadget_verify(pm_ctx* ctx, const void* d_recs, uint32_t count, size_t n, const void* d_sel, bool all11, const void* d_wire_vars,
-                  void* d_tab, void* d_coef, void* d_hcoef, void* d_hids, size_t hades_rounds, uint32_t* d_bad, hipStream_t st);
-// one launch per group on st; d_rep: 2 x batch words (failing gadgets, then min(index * 4 + reason)), copied to rep_host after
+// What a key's gadget table holds on the device: the records, the report words of a fill (set time's verdict is the first) and
+// what set time gathers for the fills.  A table point of a FIXED_BASE round is x | y; an ARITH row keeps q_m q_l q_r q_4 q_c; a
+// HADES round 30 coefficients (slot 5 i + j = matrix entry (i, j), slot 25 + j = round key j) and the 30 c ids of its rows (slot
+// 5 k + j = key row, x2, x4, x5 of word j for k = 0..3, slot 20 + 2 i + k = z_i, o_i; PM_PLONK_NO_VAR: a partial round has none)
+constexpr size_t GADGET_POINT_BYTES = 64, GADGET_COEF_BYTES = 5 * 32, GADGET_REPORT_BYTES = 2 * 8 * (size_t)PM_PLONK_MAX_BATCH;
+constexpr size_t GADGET_ROUND_COEFS = 30, GADGET_ROUND_IDS = 30, GADGET_ROUND_COEF_BYTES = GADGET_ROUND_COEFS * 32, GADGET_ROUND_ID_BYTES = GADGET_ROUND_IDS * 4;
+struct GadgetTables {
+  void *recs = nullptr, *tab = nullptr, *rep = nullptr, *coef = nullptr, *hcoef = nullptr, *hids = nullptr;
+  size_t count = 0, points = 0, arith_rows = 0, hades_rounds = 0;   // GadgetRec; what rec.tab counts for the kinds that gather
+  // every array as f(pointer, units, bytes a unit): allocated (tab: one unit at least), counted in added_bytes and freed
+  template <class F>
+  void each_array(F f) {
+    f(recs, count, sizeof(GadgetRec)), f(tab, points ? points : 1, GADGET_POINT_BYTES), f(rep, 1, GADGET_REPORT_BYTES);
+    f(coef, arith_rows, GADGET_COEF_BYTES), f(hcoef, hades_rounds, GADGET_ROUND_COEF_BYTES), f(hids, hades_rounds, GADGET_ROUND_ID_BYTES);
+  }
+};
+// set time: the first word of t.rep = the lowest index among the records whose claimed rows miss what their kind needs (~0:
+// none); the gathered arrays of t are written.  d_sel: values on H, either q_l q_r q_range q_logic q_fixed_group_add
+// q_variable_group_add (all11 = false: tables of the four widget kinds) or all eleven selectors in the order of
+// PM_PLONK_SELECTORS, which the other kinds need; d_wire_vars is read for those only.  Asynchronous.
+int gadget_verify(pm_ctx* ctx, const GadgetTables& t, size_t n, const void* d_sel, bool all11, const void* d_wire_vars, hipStream_t st);
+// one launch per group on st; t.rep: 2 x batch words (failing gadgets, then min(index * 4 + reason)), copied to rep_host after
 // the launches when it is given -- the call then waits for the stream
-int gadget_fill(pm_ctx* ctx, const void* d_recs, const GadgetGroup* groups, size_t n_groups, const void* d_wire_vars, size_t n,
-                const void* d_tab, const void* d_coef, const void* d_hcoef, const void* d_hids, void* d_vars, size_t var_stride,
-                uint32_t batch, void* d_rep, unsigned long long* rep_host, hipStream_t st);
+int gadget_fill(pm_ctx* ctx, const GadgetTables& t, const std::vector<GadgetGroup>& groups, const void* d_wire_vars, size_t n,
+                void* d_vars, size_t var_stride, uint32_t batch, unsigned long long* rep_host, hipStream_t st);
 // Per-proof constants of the proof-batched kernels (pm_plonk_prove_batch): a pinned host buffer and its device twin of the
 // same size.  A launcher takes one region of both, fills the host side and sends it with one async copy on its stream;
 // kernels read the device side as a table indexed by the proof.  reset() once per call, after the previous call has

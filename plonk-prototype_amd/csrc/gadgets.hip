@@ -1,34 +1,14 @@
-// Gadget witnesses: the inverse of the witness check.  Given the inputs of a range, logic, fixed-base
-// or curve-addition gadget, write the variables that make its rows hold (definitions: include/plonk_mi355x.h, pm_plonk_gadget).
-// Section 7.2g adds the gadgets a circuit composes from arithmetic rows: runs of them, bit decompositions and maybe_equal;
-// section 7.2h the rows of a whole Hades permutation; section 7.2i those of a variable-base scalar multiplication.
+// Gadget witnesses (DESIGN.md sections 7.2f to 7.2i): the inverse of the witness check.  Given the inputs of a gadget, write the
+// variables that make its rows hold (definitions: include/plonk_mi355x.h, pm_plonk_gadget).  A kind is three things: its record
+// in gadget_kinds.h (rows, limits, what set time gathers for it, launch shape), its set-time rule here -- the widget kinds have
+// their selector on every row but the last (gadget_verify_kernel, which also gathers the table points of the fixed-base rounds
+// from q_l / q_r); the kinds laid out in arithmetic rows have a rule_<kind> function that says what each row must be, and
+// composed_verify_kernel compares and gathers what the rule names -- and its fill kernel, entered in FILL_KERNELS.  To add a
+// kind: a row of the table, a rule function with its case in composed_verify_kernel, and a fill kernel.
 //
-//   gadget_verify_kernel       set time: every claimed row has its kind's selector, the table points of the fixed-base rounds
-//                              are gathered from q_l / q_r into a compact array
-//   composed_verify_kernel     set time, composed kinds: arithmetic rows without a widget, the coefficients and wire ids a BITS,
-//                              MAYBE_EQUAL or HADES layout implies; gathers q_m q_l q_r q_4 q_c of the ARITH rows and, round by
-//                              round, the round keys, matrix entries and c ids of the HADES rows; VAR_BASE: the selectors,
-//                              select-row coefficients and wire ids of its six rows a round
-//   gadget_arith_kernel        one thread per (gadget, proof): c = q_m a b + q_l a + q_r b + q_4 d + q_c, row after row
-//   gadget_bits_kernel         one thread per (gadget, proof, bit): acc_k = acc_(-1) + (V mod 2^(k+1)) is a masked copy of V, so
-//                              no bit waits for another
-//   gadget_maybe_equal_kernel  one thread per (gadget, proof): u = a - b, z = 1 / u (0 -> 0), y = [u = 0]
-//   gadget_hades_kernel        one WAVE per (gadget, proof): lane 5 i + j < 25 holds state word j and matrix entry (i, j); a round
-//                              is four dependent products (x^2, x^4, x^5, M x) and the row sums go across lanes
-//   gadget_range_kernel        one thread per (gadget, proof): quads of the canonical input, accumulators by 4 acc + quad
-//   gadget_logic_kernel        the same over two inputs, three accumulator columns and the quad products
-//   gadget_curve_add_kernel    one thread per (gadget, proof): the affine law with ONE inversion (of the two denominators' product)
-//   gadget_fixed_base_kernel   one WAVE per (gadget, proof), the hot path:
-//        every lane derives the width-2 NAF digits of its rounds from s and 3 s (e_j = bit_(j+1)(3s) - bit_(j+1)(s): no carry
-//        travels between lanes), owns a contiguous run of ceil(R / 64) rounds and sums its addends in extended coordinates;
-//        the lane totals go through an inclusive prefix scan with __shfl_up under the complete twisted Edwards law; each lane
-//        then walks its run again from the scanned start and normalises its <= 4 prefixes with one inversion (Montgomery's
-//        trick).  No lane ever runs more than one inversion and there is no chain of dependent per-round inversions.
-//        The addends are re-derived from the table in both walks rather than kept across the scan: what stays live over the
-//        scan is one point, and over the second walk the run's X, Y, Z (the variant kept: see DESIGN.md for the registers).
-//   gadget_var_base_kernel     one WAVE per (gadget, proof): every lane walks the same double-and-add chain in extended
-//        coordinates (a wave instruction costs the same for 64 lanes as for one), lane l keeps the points of rounds
-//        l L .. (l + 1) L - 1, L = ceil(R / 64), and normalises them with its one inversion.  No per-round inversion.
+// The fill kernels carry their reasoning where they stand.  One thread per (gadget, proof): range and logic (quads of the
+// canonical inputs, accumulators by 4 acc + quad, the quad products), curve_add, arith, maybe_equal; per bit as well: bits; one
+// WAVE per (gadget, proof): hades, fixed_base (the hot path) and var_base.
 //
 // Forms: variables are canonical Montgomery ("ABI", x 2^256); the point arithmetic runs in the device form x 2^261
 // (poly_common.hip.h).  Everything written goes through fe_store, i.e. is canonical.
@@ -39,6 +19,7 @@
 
 #include "context.h"
 #include "field_inv.hip.h"
+#include "gadget_kinds.h"
 #include "poly_common.hip.h"
 
 namespace pm {
@@ -75,6 +56,18 @@ PM_HOSTDEV bool any_above(const u32 (&w)[NW], u32 nbits) {
   }
   return acc != 0;
 }
+// word w of the mask of the low `keep` bits
+PM_HOSTDEV u32 low_bits_mask(u32 w, u32 keep) {
+  const u32 lo = 32 * w;
+  return lo + 32 <= keep ? 0xffffffffu : (lo >= keep ? 0u : ((1u << ((keep - lo) & 31u)) - 1u));
+}
+template <int NW>
+PM_HOSTDEV u32 words_or(const u32 (&w)[NW]) {
+  u32 acc = 0;
+#pragma unroll
+  for (int k = 0; k < NW; ++k) acc |= w[k];
+  return acc;
+}
 // s (8 words) as 9 words and x = 3 s
 PM_HOSTDEV void naf_operands(const u32 (&s)[8], u32 (&s9)[9], u32 (&x9)[9]) {
   u64 c = 0;
@@ -110,11 +103,11 @@ struct GadgetFill {
   const u32* hids;          // HADES rounds, 30 ids each: the c variables of the round's rows (context.h)
   u32x4* vars;              // [batch][var_stride] canonical
   size_t var_stride, n;
-  unsigned long long* rep;  // [batch] failing gadgets, then [batch] min(index * 4 + reason); batch = gridDim.y
+  unsigned long long* rep;  // [batch] failing gadgets, then [batch] min(index * 4 + reason)
   u32 edwards_d[9];         // device form
 };
 
-PM_DEV void gadget_fail(const GadgetFill& a, u32 proof, u32 index, u32 reason) {
+PM_DEV void gadget_fail(const GadgetFill& a, u32 proof, u32 index, u32 reason) {   // batch = gridDim.y: not for a BITS_X kernel
   atomicAdd(a.rep + proof, 1ull);                                              // a count and a minimum: order-free
   atomicMin(a.rep + gridDim.y + proof, (unsigned long long)index * 4 + reason);
 }
@@ -141,7 +134,7 @@ PM_DEV Fr g_sel(bool c, const Fr& a, const Fr& b) {
 PM_DEV bool g_is_zero(const Fr& v) {   // a zero may arrive as r: test the canonical words
   u32 s[8];
   fe_canon_pack<FrP>(s, v);
-  return (s[0] | s[1] | s[2] | s[3] | s[4] | s[5] | s[6] | s[7]) == 0;
+  return words_or<8>(s) == 0;
 }
 // canonical Montgomery element -> the integer below r it stands for
 PM_DEV void g_to_int(const Fr& abi, u32 (&w)[8]) { fe_canon_pack<FrP>(w, fe_mul_limb<FrP>(abi, 32u)); }   // x 2^256 * 2^5 / 2^261
@@ -163,189 +156,194 @@ PM_DEV Fr g_acc_step(const Fr& acc, u32 q) {
 }
 
 // ------------------------------------------------------------------ set time: selectors of the claimed rows, table points
-// sel: vectors of n values on H; q_l, q_r are vectors ql, ql + 1 and the four widget selectors wid .. wid + 3 (0 and 2 of
-// q_l q_r q_range q_logic q_fixed_group_add q_variable_group_add; 1 and 7 of all eleven)
-__global__ void __launch_bounds__(256) gadget_verify_kernel(const GadgetRec* recs, const u32x4* sel_all, size_t n, u32 ql, u32 wid,
-                                                            u32x4* tab, u32* bad) {
-  const GadgetRec rec = recs[blockIdx.x];
-  if (rec.kind > PM_PLONK_GADGET_CURVE_ADD) return;   // composed_verify_kernel
-  const u32 rows = rec.kind == PM_PLONK_GADGET_CURVE_ADD ? 1u : rec.count;
-  const u32x4* sel = sel_all + 2 * n * ql;
-  const u32x4* q = sel_all + 2 * n * (wid + (size_t)rec.kind);
-  bool miss = false;
-  for (u32 t = threadIdx.x; t < rows; t += 256) {
-    const size_t row = (size_t)rec.first_row + t;
-    const u32x4 lo = q[2 * row], hi = q[2 * row + 1];
-    miss |= (lo.x | lo.y | lo.z | lo.w | hi.x | hi.y | hi.z | hi.w) == 0;
-    if (rec.kind == PM_PLONK_GADGET_FIXED_BASE) {
-      u32x4* o = tab + 4 * ((size_t)rec.tab + t);
-      o[0] = sel[2 * row];
-      o[1] = sel[2 * row + 1];
-      o[2] = sel[2 * (n + row)];
-      o[3] = sel[2 * (n + row) + 1];
-    }
-  }
-  if (miss) atomicMin(bad, rec.index);
-}
-
-// The composed kinds (include/plonk_mi355x.h): what a row's six coefficients must be.  sel: all eleven selectors on H in the
-// order of PM_PLONK_SELECTORS -- q_m q_l q_r q_o q_c q_4 q_arith, then the four widget selectors.
-enum : u32 { CO_ZERO, CO_ONE, CO_NEG, CO_POW, CO_ANY };
 PM_DEV void sel_words(const u32x4* sel, size_t n, u32 s, size_t row, u32 (&w)[8]) {
   const u32x4 lo = sel[2 * (n * s + row)], hi = sel[2 * (n * s + row) + 1];
   w[0] = lo.x, w[1] = lo.y, w[2] = lo.z, w[3] = lo.w, w[4] = hi.x, w[5] = hi.y, w[6] = hi.z, w[7] = hi.w;
 }
+PM_DEV u32 sel_or(const u32x4* sel, size_t n, u32 s, size_t row) {   // 0: the selector vanishes on the row
+  u32 w[8];
+  sel_words(sel, n, s, row, w);
+  return words_or<8>(w);
+}
+PM_DEV void st_words8(u32x4* o, const u32 (&w)[8]) {
+  o[0] = u32x4{w[0], w[1], w[2], w[3]};
+  o[1] = u32x4{w[4], w[5], w[6], w[7]};
+}
+// The widget kinds.  sel: vectors of n values on H; q_l, q_r are vectors ql, ql + 1 and the four widget selectors wid .. wid + 3
+// (0 and 2 of q_l q_r q_range q_logic q_fixed_group_add q_variable_group_add; 1 and 7 of all eleven)
+__global__ void __launch_bounds__(256) gadget_verify_kernel(const GadgetRec* recs, const u32x4* sel, size_t n, u32 ql, u32 wid,
+                                                            u32x4* tab, u32* bad) {
+  const GadgetRec rec = recs[blockIdx.x];
+  const GadgetKind kind = gadget_kind(rec.kind);
+  if (kind.all_selectors) return;   // composed_verify_kernel
+  const u32 rows = (u32)gadget_kind_rows(kind, rec.count, rec.param) - kind.trailing;
+  bool miss = false;
+  for (u32 t = threadIdx.x; t < rows; t += 256) {
+    const size_t row = (size_t)rec.first_row + t;
+    u32 w[8];
+    miss |= sel_or(sel, n, wid + rec.kind, row) == 0;
+    if (kind.tab == GadgetTab::POINTS)
+      for (u32 s = 0; s < 2; ++s) {   // x | y of the round's table point
+        sel_words(sel, n, ql + s, row, w);
+        st_words8(tab + 4 * ((size_t)rec.tab + t) + 2 * s, w);
+      }
+  }
+  if (miss) atomicMin(bad, rec.index);
+}
+
+// The kinds laid out in arithmetic rows (include/plonk_mi355x.h).  A kind's rule says what row t of a gadget must be;
+// composed_verify_kernel below reads the row and compares.
+enum : u32 { ROW_ARITH, ROW_VAR_ADD, ROW_RESULT };   // q_arith and no widget selector; q_variable_group_add; selectors not looked at
+constexpr u32 NO_SLOT = ~0u;
+struct Wires { const u32 *a, *b, *c, *d; };   // [n] each
+struct RowRule {
+  const char* want = "***-**";            // q_m q_l q_r q_o q_c q_4: 0, 1, - (minus one), P (the power of two pw) or * (free)
+  u32 pw[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sel = ROW_ARITH;
+  bool miss = false;                      // a wire id is not what the layout implies, or a written position is no variable
+  // gathered for the fill: coefficient s to 32-byte slot[s] of unit `unit` (an ARITH row, a HADES round), the c id to id_slot
+  size_t unit = 0;
+  u32 slot[6] = {NO_SLOT, NO_SLOT, NO_SLOT, NO_SLOT, NO_SLOT, NO_SLOT}, id_slot = NO_SLOT;
+};
+
+// c = q_m a b + q_l a + q_r b + q_4 d + q_c: q_o = -1 and c is written; q_m q_l q_r q_4 q_c are gathered in that order
+PM_DEV RowRule rule_arith(const GadgetRec& rec, u32 t, size_t row, const Wires& w) {
+  RowRule r;
+  r.miss = w.c[row] == PM_PLONK_NO_VAR;
+  r.unit = (size_t)rec.tab + t;
+  r.slot[0] = 0, r.slot[1] = 1, r.slot[2] = 2, r.slot[4] = 4, r.slot[5] = 3;
+  return r;
+}
+
+// two rows a bit k: bit * bit - bit, then 2^k bit + acc_(k-1) - acc_k
+PM_DEV RowRule rule_bits(const GadgetRec& rec, u32 t, size_t row, const Wires& w) {
+  RowRule r;
+  const u32 k = t >> 1, va = w.a[row], vb = w.b[row], vc = w.c[row];
+  if ((t & 1u) == 0) {
+    r.want = "100-00";
+    r.miss = va == PM_PLONK_NO_VAR || vb != va || vc != va;
+  } else {
+    r.want = "0P1-00";
+    u32 e[8];
+#pragma unroll
+    for (u32 i = 0; i < 8; ++i) e[i] = i == (k >> 5) ? 1u << (k & 31u) : 0u;
+    fe_canon_pack<FrP>(r.pw, g_from_int(e));
+    r.miss = vc == PM_PLONK_NO_VAR || va != w.a[row - 1] || (k && vb != w.c[row - 2]);
+  }
+  return r;
+}
+
+// a - b - u, then 1 - z u - y, then y u
+PM_DEV RowRule rule_maybe_equal(const GadgetRec& rec, u32 t, size_t row, const Wires& w) {
+  RowRule r;
+  const u32 va = w.a[row], vb = w.b[row], vc = w.c[row], u = w.c[rec.first_row], y = w.c[(size_t)rec.first_row + 1];
+  r.want = t == 0 ? "01--00" : t == 1 ? "-00-10" : "100000";
+  r.miss = t == 0 ? vc == PM_PLONK_NO_VAR : t == 1 ? va == PM_PLONK_NO_VAR || vc == PM_PLONK_NO_VAR || vb != u : va != y || vb != u;
+  return r;
+}
+
+// H = param / 2 full rounds, count - 2 H partial ones, H full ones; 30 rows a full round and 18 a partial one: 5 key rows, 3
+// s-box rows for every word (full) or for word 4 (partial), 10 matrix rows.  Every c is written; its id and the round's keys
+// and matrix entries are gathered (context.h, GADGET_ROUND_COEFS)
+PM_DEV RowRule rule_hades(const GadgetRec& rec, u32 t, size_t row, const Wires& w) {
+  RowRule r;
+  const u32 H = rec.param >> 1, rows_head = 30 * H, rows_mid = 18 * (rec.count - 2 * H);
+  const bool head = t < rows_head, full = head || t >= rows_head + rows_mid;
+  const u32 first = head ? 0u : full ? rec.count - H : H;                      // the first round of the row's run of rounds ...
+  const u32 tr = head ? t : full ? t - rows_head - rows_mid : t - rows_head;   // ... and the row within that run
+  const u32 rho = first + tr / (full ? 30u : 18u), pos = tr % (full ? 30u : 18u);   // the round and the row's place in it
+  const size_t rb = row - pos;                     // the round's first row
+  const u32 sbox_rows = full ? 15u : 3u, va = w.a[row], vb = w.b[row];
+  r.unit = (size_t)rec.tab + rho;
+  r.miss = w.c[row] == PM_PLONK_NO_VAR;
+  if (pos < 5) {                                   // s'[j] = s[j] + q_c; s[j] is o_j of the round before
+    r.want = "010-*0";
+    r.slot[4] = 25 + pos;
+    if (rho) r.miss |= va != w.c[rb - 10 + 2 * pos + 1];
+    r.id_slot = pos;
+  } else if (pos < 5 + sbox_rows) {                // x2 = x x, x4 = x2 x2, x5 = x4 x
+    const u32 u = pos - 5, j = full ? u / 3 : 4u, k = u % 3;
+    const u32 x = w.c[rb + j];
+    r.want = "100-00";
+    r.miss |= va != (k ? w.c[row - 1] : x) || vb != (k == 1 ? w.c[row - 1] : x);
+    r.id_slot = 5 * (k + 1) + j;
+  } else {                                         // z_i = M_i0 v0 + M_i1 v1 + M_i2 v2, o_i = M_i3 v3 + M_i4 v4 + z_i
+    const u32 u = pos - 5 - sbox_rows, i = u >> 1, k = u & 1u;
+    u32 v[3];
+#pragma unroll
+    for (u32 e = 0; e < 3; ++e) {
+      const u32 j = 3 * k + e;                     // j = 5 (k = 1, e = 2) is z_i
+      v[e] = j == 5 ? w.c[row - 1] : full ? w.c[rb + 5 + 3 * j + 2] : j == 4 ? w.c[rb + 7] : w.c[rb + j];
+    }
+    r.want = k ? "0**-01" : "0**-0*";
+    r.slot[1] = 5 * i + 3 * k, r.slot[2] = 5 * i + 3 * k + 1;
+    if (!k) r.slot[5] = 5 * i + 2;
+    r.miss |= va != v[0] || vb != v[1] || w.d[row] != v[2];
+    r.id_slot = 20 + u;
+  }
+  return r;
+}
+
+// six rows a round: the doubling (q_variable_group_add) and its result row, sx = bit P.x, sy = bit P.y - bit + 1 (arithmetic
+// rows), the addition of (sx, sy) and its result row
+PM_DEV RowRule rule_var_base(const GadgetRec& rec, u32 t, size_t row, const Wires& w) {
+  RowRule r;
+  const u32 pos = t % 6, va = w.a[row], vb = w.b[row], vc = w.c[row], vd = w.d[row];
+  const size_t r0 = rec.first_row, rb = row - pos;   // the gadget's and the round's first row
+  r.want = pos == 2 ? "100-00" : pos == 3 ? "1-0-10" : "******";
+  r.sel = pos == 0 || pos == 4 ? ROW_VAR_ADD : pos == 1 || pos == 5 ? ROW_RESULT : ROW_ARITH;
+  switch (pos) {
+    case 0: r.miss = vc != va || vd != vb || (rb != r0 && (va != w.a[rb - 1] || vb != w.b[rb - 1])); break;   // acc + acc; acc: the round before
+    case 2: r.miss = vc == PM_PLONK_NO_VAR || vb != w.b[r0 + 2]; break;                                       // sx = bit P.x
+    case 3: r.miss = vc == PM_PLONK_NO_VAR || va != w.a[row - 1] || vb != w.b[r0 + 3]; break;                 // sy = bit P.y - bit + 1
+    case 4: r.miss = va != w.a[rb + 1] || vb != w.b[rb + 1] || vc != w.c[rb + 2] || vd != w.c[rb + 3]; break;   // dbl + (sx, sy)
+    default: r.miss = va == PM_PLONK_NO_VAR || vb == PM_PLONK_NO_VAR || vd == PM_PLONK_NO_VAR; break;         // a result row: x, y, product
+  }
+  return r;
+}
+
+// sel: all eleven selectors on H in the order of PM_PLONK_SELECTORS -- q_m q_l q_r q_o q_c q_4 q_arith, then the four widget
+// selectors, q_variable_group_add last
 __global__ void __launch_bounds__(256) composed_verify_kernel(const GadgetRec* recs, const u32x4* sel, size_t n, const u32* wire_vars,
                                                               u32x4* coef, u32x4* hcoef, u32* hids, u32* bad) {
   const GadgetRec rec = recs[blockIdx.x];
-  if (rec.kind < PM_PLONK_COMPOSED_ARITH) return;
-  const bool arith = rec.kind == PM_PLONK_COMPOSED_ARITH, bits = rec.kind == PM_PLONK_COMPOSED_BITS;
-  const bool hades = rec.kind == PM_PLONK_PERMUTATION_HADES, vbase = rec.kind == PM_PLONK_GADGET_VAR_BASE;
-  // HADES: H full rounds, rec.count - 2 H partial ones, H full ones; 30 rows a full round and 18 a partial one
-  const u32 H = rec.param >> 1, rows_head = 30 * H, rows_mid = 18 * (rec.count - 2 * H);
-  const u32 rows = arith ? rec.count : bits ? 2 * rec.count : hades ? 2 * rows_head + rows_mid : vbase ? 6 * rec.count : 3u;
+  const GadgetKind kind = gadget_kind(rec.kind);
+  if (!kind.all_selectors) return;   // gadget_verify_kernel
+  const u32 rows = (u32)gadget_kind_rows(kind, rec.count, rec.param);
+  const Wires wires{wire_vars, wire_vars + n, wire_vars + 2 * n, wire_vars + 3 * n};
   u32 one[8], neg[8];
   fe_canon_pack<FrP>(one, g_one_abi());
   fe_canon_pack<FrP>(neg, gneg(g_one_abi()));
   bool miss = false;
   for (u32 t = threadIdx.x; t < rows; t += 256) {
     const size_t row = (size_t)rec.first_row + t;
-    u32 w[8];
-    // an arithmetic row and nothing else; VAR_BASE: that on its select rows (2, 3 of six), q_variable_group_add on rows 0
-    // and 4, and rows 1 and 5 carry results only: their selectors are not looked at
-    const u32 pos = vbase ? t % 6 : 2u;
-    sel_words(sel, n, 6, row, w);
-    const bool no_arith = (w[0] | w[1] | w[2] | w[3] | w[4] | w[5] | w[6] | w[7]) == 0;
-    u32 widget = 0, last = 0;
-#pragma unroll
-    for (u32 s = 7; s < 11; ++s) {
-      sel_words(sel, n, s, row, w);
-      last = w[0] | w[1] | w[2] | w[3] | w[4] | w[5] | w[6] | w[7];
-      widget |= last;
+    RowRule r;
+    switch (rec.kind) {
+      case PM_PLONK_COMPOSED_ARITH: r = rule_arith(rec, t, row, wires); break;
+      case PM_PLONK_COMPOSED_BITS: r = rule_bits(rec, t, row, wires); break;
+      case PM_PLONK_COMPOSED_MAYBE_EQUAL: r = rule_maybe_equal(rec, t, row, wires); break;
+      case PM_PLONK_PERMUTATION_HADES: r = rule_hades(rec, t, row, wires); break;
+      case PM_PLONK_GADGET_VAR_BASE: r = rule_var_base(rec, t, row, wires); break;
     }
-    if (pos == 2 || pos == 3) miss |= no_arith || widget != 0;
-    else if (pos == 0 || pos == 4) miss |= last == 0;
-    // q_m q_l q_r q_o q_c q_4
-    u32 want[6] = {CO_ANY, CO_ANY, CO_ANY, CO_NEG, CO_ANY, CO_ANY};
-    u32 pw[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const u32 va = wire_vars[row], vb = wire_vars[n + row], vc = wire_vars[2 * n + row];
-    u32 slot[6] = {~0u, ~0u, ~0u, ~0u, ~0u, ~0u};   // HADES: where a selector's value goes in the round's 30 coefficients
-    size_t round = 0;
-    if (arith) {
-      miss |= vc == PM_PLONK_NO_VAR;
-    } else if (vbase) {
-      const u32 vd = wire_vars[3 * n + row];
-      const size_t r0 = rec.first_row, rb = row - pos;   // the gadget's and the round's first row
-      const u32* const aw = wire_vars;
-      const u32* const bw = wire_vars + n;
-      const u32* const cw = wire_vars + 2 * n;
-      want[3] = CO_ANY;
-      if (pos == 0) {          // acc + acc; acc is what the round before wrote
-        miss |= vc != va || vd != vb;
-        if (rb != r0) miss |= va != aw[rb - 1] || vb != bw[rb - 1];
-      } else if (pos == 1 || pos == 5) {   // a result row: x, y and the product are written
-        miss |= va == PM_PLONK_NO_VAR || vb == PM_PLONK_NO_VAR || vd == PM_PLONK_NO_VAR;
-      } else if (pos == 2) {   // sx = bit P.x
-        want[0] = CO_ONE, want[3] = CO_NEG, want[1] = want[2] = want[4] = want[5] = CO_ZERO;
-        miss |= vc == PM_PLONK_NO_VAR || vb != bw[r0 + 2];
-      } else if (pos == 3) {   // sy = bit P.y - bit + 1
-        want[0] = CO_ONE, want[1] = CO_NEG, want[3] = CO_NEG, want[4] = CO_ONE, want[2] = want[5] = CO_ZERO;
-        miss |= vc == PM_PLONK_NO_VAR || va != aw[row - 1] || vb != bw[r0 + 3];
-      } else {                 // dbl + (sx, sy)
-        miss |= va != aw[rb + 1] || vb != bw[rb + 1] || vc != cw[rb + 2] || vd != cw[rb + 3];
-      }
-    } else if (hades) {
-      // the round, whether it is full, and the row's place in it
-      u32 rho, pos;
-      bool full = true;
-      if (t < rows_head) {
-        rho = t / 30, pos = t % 30;
-      } else if (t < rows_head + rows_mid) {
-        rho = H + (t - rows_head) / 18, pos = (t - rows_head) % 18, full = false;
-      } else {
-        rho = rec.count - H + (t - rows_head - rows_mid) / 30, pos = (t - rows_head - rows_mid) % 30;
-      }
-      round = (size_t)rec.tab + rho;
-      const size_t rb = row - pos;                   // the round's first row
-      const u32* const cw = wire_vars + 2 * n;       // the c ids
-      const u32 sbox_rows = full ? 15u : 3u;
-      want[0] = want[1] = want[2] = want[4] = want[5] = CO_ZERO;
-      miss |= vc == PM_PLONK_NO_VAR;
-      u32 id_slot;
-      if (pos < 5) {                                 // s'[j] = s[j] + q_c; s[j] is o_j of the round before
-        want[1] = CO_ONE, want[4] = CO_ANY;
-        slot[4] = 25 + pos;
-        if (rho) miss |= va != cw[rb - 10 + 2 * pos + 1];
-        id_slot = pos;
-      } else if (pos < 5 + sbox_rows) {              // x2 = x x, x4 = x2 x2, x5 = x4 x
-        const u32 u = pos - 5, j = full ? u / 3 : 4u, k = u % 3;
-        const u32 x = cw[rb + j];
-        want[0] = CO_ONE;
-        miss |= va != (k ? cw[row - 1] : x) || vb != (k == 1 ? cw[row - 1] : x);
-        id_slot = 5 * (k + 1) + j;
-      } else {                                       // z_i = M_i0 v0 + M_i1 v1 + M_i2 v2, o_i = M_i3 v3 + M_i4 v4 + z_i
-        const u32 u = pos - 5 - sbox_rows, i = u >> 1, k = u & 1u;
-        u32 v[3];
+    miss |= r.miss;
+    const bool no_arith = sel_or(sel, n, 6, row) == 0;
+    u32 w[8], widget = 0, last = 0;
 #pragma unroll
-        for (u32 e = 0; e < 3; ++e) {
-          const u32 j = 3 * k + e;                   // j = 5 (k = 1, e = 2) is z_i
-          v[e] = j == 5 ? cw[row - 1] : full ? cw[rb + 5 + 3 * j + 2] : j == 4 ? cw[rb + 7] : cw[rb + j];
-        }
-        want[1] = want[2] = CO_ANY, want[5] = k ? CO_ONE : CO_ANY;
-        slot[1] = 5 * i + 3 * k, slot[2] = 5 * i + 3 * k + 1;
-        if (!k) slot[5] = 5 * i + 2;
-        miss |= va != v[0] || vb != v[1] || wire_vars[3 * n + row] != v[2];
-        id_slot = 20 + u;
-      }
-      hids[30 * round + id_slot] = vc;
-    } else if (bits) {
-      const u32 k = t >> 1;
-      if ((t & 1u) == 0) {   // the boolean row: bit * bit - bit
-        want[0] = CO_ONE, want[1] = want[2] = want[4] = want[5] = CO_ZERO;
-        miss |= va == PM_PLONK_NO_VAR || vb != va || vc != va;
-      } else {               // 2^k bit + acc_(k-1) - acc_k
-        want[0] = want[4] = want[5] = CO_ZERO, want[1] = CO_POW, want[2] = CO_ONE;
-        u32 e[8];
-#pragma unroll
-        for (u32 i = 0; i < 8; ++i) e[i] = i == (k >> 5) ? 1u << (k & 31u) : 0u;
-        fe_canon_pack<FrP>(pw, g_from_int(e));
-        miss |= vc == PM_PLONK_NO_VAR || va != wire_vars[row - 1];
-        if (k) miss |= vb != wire_vars[2 * n + row - 2];
-      }
-    } else {
-      const size_t r0 = rec.first_row;
-      const u32 u = wire_vars[2 * n + r0], y = wire_vars[2 * n + r0 + 1];
-      if (t == 0) {          // a - b - u
-        want[0] = want[4] = want[5] = CO_ZERO, want[1] = CO_ONE, want[2] = CO_NEG;
-        miss |= vc == PM_PLONK_NO_VAR;
-      } else if (t == 1) {   // 1 - z u - y
-        want[0] = CO_NEG, want[4] = CO_ONE, want[1] = want[2] = want[5] = CO_ZERO;
-        miss |= va == PM_PLONK_NO_VAR || vc == PM_PLONK_NO_VAR || vb != u;
-      } else {               // y u
-        want[0] = CO_ONE, want[1] = want[2] = want[3] = want[4] = want[5] = CO_ZERO;
-        miss |= va != y || vb != u;
-      }
-    }
+    for (u32 s = 7; s < 11; ++s) widget |= last = sel_or(sel, n, s, row);
+    if (r.sel == ROW_ARITH) miss |= no_arith || widget != 0;
+    else if (r.sel == ROW_VAR_ADD) miss |= last == 0;
+    u32x4* const out = kind.tab == GadgetTab::COEF ? coef + 2 * (GADGET_COEF_BYTES / 32) * r.unit : hcoef + 2 * GADGET_ROUND_COEFS * r.unit;
+    if (r.id_slot != NO_SLOT) hids[GADGET_ROUND_IDS * r.unit + r.id_slot] = wires.c[row];
 #pragma unroll
     for (u32 s = 0; s < 6; ++s) {
       sel_words(sel, n, s, row, w);
       u32 diff = 0;
 #pragma unroll
       for (u32 i = 0; i < 8; ++i) {
-        const u32 x = want[s] == CO_ONE ? one[i] : want[s] == CO_NEG ? neg[i] : want[s] == CO_POW ? pw[i] : 0u;
+        const u32 x = r.want[s] == '1' ? one[i] : r.want[s] == '-' ? neg[i] : r.want[s] == 'P' ? r.pw[i] : 0u;
         diff |= w[i] ^ x;
       }
-      miss |= want[s] != CO_ANY && diff != 0;
-      if (arith && s != 3) {   // q_m q_l q_r q_c q_4 -> slots 0 1 2 4 3
-        u32x4* o = coef + 10 * ((size_t)rec.tab + t) + 2 * (s < 3 ? s : s == 4 ? 4u : 3u);
-        o[0] = u32x4{w[0], w[1], w[2], w[3]};
-        o[1] = u32x4{w[4], w[5], w[6], w[7]};
-      }
-      if (slot[s] != ~0u) {
-        u32x4* o = hcoef + 2 * (30 * round + slot[s]);
-        o[0] = u32x4{w[0], w[1], w[2], w[3]};
-        o[1] = u32x4{w[4], w[5], w[6], w[7]};
-      }
+      miss |= r.want[s] != '*' && diff != 0;
+      if (r.slot[s] != NO_SLOT) st_words8(out + 2 * r.slot[s], w);
     }
   }
   if (miss) atomicMin(bad, rec.index);
@@ -396,12 +394,17 @@ __global__ void __launch_bounds__(64) gadget_logic_kernel(const GadgetFill a, u3
 
 // ------------------------------------------------------------------ JubJub: -x^2 + y^2 = 1 + d x^2 y^2, device form throughout
 // (x1, y1) + (x2, y2) = ((x1 y2 + y1 x2) / (1 + k), (y1 y2 + x1 x2) / (1 - k)), k = d x1 x2 y1 y2: complete on the curve.
-// One thread per (gadget, proof).  The inversion votes across the wave (field_inv.hip.h), so no lane leaves early: a lane
-// past the end works on the last gadget and writes nothing.
+// One thread per (gadget, proof) of a kernel whose inversion votes across the wave (field_inv.hip.h), so that no lane may leave
+// early: a lane past the end works on the last gadget and, not being `live`, writes nothing.
+PM_DEV GadgetRec clamped_rec(const GadgetFill& a, u32 first, u32 count, bool& live) {
+  const u32 g = blockIdx.x * 64 + threadIdx.x;
+  live = g < count;
+  return a.recs[first + (live ? g : count - 1)];
+}
 __global__ void __launch_bounds__(64) gadget_curve_add_kernel(const GadgetFill a, u32 first, u32 count) {
-  const u32 g0 = blockIdx.x * 64 + threadIdx.x, proof = blockIdx.y;
-  const bool live = g0 < count;
-  const GadgetRec rec = a.recs[first + (live ? g0 : count - 1)];
+  const u32 proof = blockIdx.y;
+  bool live;
+  const GadgetRec rec = clamped_rec(a, first, count, live);
   u32x4* const vars = a.vars + 2 * a.var_stride * proof;
   const size_t row = rec.first_row;
   const Fr x1 = g_to_dev(ld_var(vars, var_id(a, 0, row))), y1 = g_to_dev(ld_var(vars, var_id(a, 1, row)));
@@ -445,7 +448,7 @@ __global__ void __launch_bounds__(64) gadget_arith_kernel(const GadgetFill a, u3
 
 // Bit decomposition: blockIdx.x * 64 + threadIdx.x = the bit k, blockIdx.y = the gadget within the launch, blockIdx.z = the
 // proof.  acc_k = acc_(-1) + (V mod 2^(k+1)): every thread masks its own copy of V, nothing is passed from bit to bit.
-__global__ void __launch_bounds__(64) gadget_bits_kernel(const GadgetFill a, u32 first) {
+__global__ void __launch_bounds__(64) gadget_bits_kernel(const GadgetFill a, u32 first, u32) {
   const u32 k = blockIdx.x * 64 + threadIdx.x, proof = blockIdx.z;
   const GadgetRec rec = a.recs[first + blockIdx.y];
   if (k >= rec.count) return;
@@ -454,21 +457,17 @@ __global__ void __launch_bounds__(64) gadget_bits_kernel(const GadgetFill a, u32
   u32 v[8], m[8];
   g_to_int(ld_canon(vars, rec.in_var[0]), v);
 #pragma unroll
-  for (u32 w = 0; w < 8; ++w) {   // the low k + 1 bits
-    const u32 lo = 32 * w, keep = k + 1;
-    m[w] = v[w] & (lo + 32 <= keep ? 0xffffffffu : (lo >= keep ? 0u : ((1u << ((keep - lo) & 31u)) - 1u)));
-  }
+  for (u32 w = 0; w < 8; ++w) m[w] = v[w] & low_bits_mask(w, k + 1);
   const Fr acc = gadd(g_from_int(m), ld_var(vars, var_id(a, 1, row0 + 1)));
   st_var(vars, var_id(a, 0, row0 + 2 * (size_t)k), g_sel(bit_at<8>(v, k) != 0, g_one_abi(), fe_zero<FrP>()));
   st_var(vars, var_id(a, 2, row0 + 2 * (size_t)k + 1), acc);
 }
 
-// u = a - b, z = 1 / u or 0, y = 1 - u z = [u = 0].  One thread per (gadget, proof); the inversion votes across the wave, so
-// (as in gadget_curve_add_kernel) a lane past the end works on the last gadget and writes nothing.
+// u = a - b, z = 1 / u or 0, y = 1 - u z = [u = 0].  One thread per (gadget, proof), clamped as in gadget_curve_add_kernel.
 __global__ void __launch_bounds__(64) gadget_maybe_equal_kernel(const GadgetFill a, u32 first, u32 count) {
-  const u32 g0 = blockIdx.x * 64 + threadIdx.x, proof = blockIdx.y;
-  const bool live = g0 < count;
-  const GadgetRec rec = a.recs[first + (live ? g0 : count - 1)];
+  const u32 proof = blockIdx.y;
+  bool live;
+  const GadgetRec rec = clamped_rec(a, first, count, live);
   u32x4* const vars = a.vars + 2 * a.var_stride * proof;
   const size_t row = rec.first_row;
   const Fr u = gsub(ld_var(vars, var_id(a, 0, row)), ld_var(vars, var_id(a, 1, row)));
@@ -479,13 +478,22 @@ __global__ void __launch_bounds__(64) gadget_maybe_equal_kernel(const GadgetFill
   st_var(vars, var_id(a, 2, row + 1), g_sel(g_is_zero(u), g_one_abi(), fe_zero<FrP>()));
 }
 
-// ------------------------------------------------------------------ a Hades permutation of width 5 (DESIGN.md section 7.2h)
+// ------------------------------------------------------------------ the wave kernels: an element from another lane
 PM_DEV Fr fr_shfl(const Fr& v, u32 src) {
   Fr r;
 #pragma unroll
   for (int i = 0; i < 9; ++i) r.l[i] = __shfl(v.l[i], (int)src);
   return r;
 }
+PM_DEV Fr fr_shfl_up(const Fr& v, u32 delta) {
+  Fr r;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) r.l[i] = __shfl_up(v.l[i], delta);
+  return r;
+}
+constexpr u32 GADGET_RUN = PM_PLONK_GADGET_MAX_ROUNDS / 64;   // rounds a lane of a wave kernel owns at most
+
+// ------------------------------------------------------------------ a Hades permutation of width 5 (DESIGN.md section 7.2h)
 // One wave per (gadget, proof): blockIdx.x = the gadget within the launch, blockIdx.y = the proof.  Lane 5 i + j (i, j < 5) holds
 // state word j and the matrix entry (i, j); lanes 25..63 leave at once and no cross-lane read names them: every source below is
 // 5 i + e or 5 j with e < 5.  The loop and the kind of a round depend on the gadget only, so the 25 lanes stay together; which of
@@ -494,7 +502,7 @@ PM_DEV Fr fr_shfl(const Fr& v, u32 src) {
 // (i, 1) write z_i and o_i -- two stores a round and lane, their ids gathered at set time in exactly that order (NO_VAR where a
 // partial round has no such row).  The next round's two coefficients and two ids are loaded before this round's arithmetic.
 // Forms as in gadget_arith_kernel: the state is in the ABI form, one operand of each product goes through g_to_dev.
-__global__ void __launch_bounds__(64) gadget_hades_kernel(const GadgetFill a, u32 first) {
+__global__ void __launch_bounds__(64) gadget_hades_kernel(const GadgetFill a, u32 first, u32) {
   const u32 lane = threadIdx.x, proof = blockIdx.y;
   if (lane >= 25) return;
   const GadgetRec rec = a.recs[first + blockIdx.x];
@@ -544,20 +552,12 @@ PM_DEV EdPoint ed_madd(const EdPoint& p, const Fr& x, const Fr& y, const Fr& t, 
   const Fr F = gsub(p.Z, C), G = gadd(p.Z, C), H = gadd(B, A);
   return EdPoint{gmul(E, F), gmul(G, H), gmul(F, G), gmul(E, H)};
 }
-PM_DEV Fr fr_shfl_up(const Fr& v, u32 delta) {
-  Fr r;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) r.l[i] = __shfl_up(v.l[i], delta);
-  return r;
-}
 PM_DEV EdPoint ed_shfl_up(const EdPoint& p, u32 delta) {
   return EdPoint{fr_shfl_up(p.X, delta), fr_shfl_up(p.Y, delta), fr_shfl_up(p.Z, delta), fr_shfl_up(p.T, delta)};
 }
 PM_DEV EdPoint ed_sel(bool c, const EdPoint& a, const EdPoint& b) {
   return EdPoint{g_sel(c, a.X, b.X), g_sel(c, a.Y, b.Y), g_sel(c, a.Z, b.Z), g_sel(c, a.T, b.T)};
 }
-
-constexpr u32 FB_RUN = PM_PLONK_GADGET_MAX_ROUNDS / 64;   // rounds a lane owns at most
 
 // the addend of a round in device form: bit (x_b, y_b) = (bit x_b, bit^2 (y_b - 1) + 1), t = bit x_b y_b; c_abi = t in ABI form
 struct Addend {
@@ -579,7 +579,14 @@ PM_DEV Addend fb_addend(const u32x4* tab, size_t round, int bit, Fr* c_abi) {
 
 // One wave per (gadget, proof): blockIdx.x = the gadget within the launch, blockIdx.y = the proof.  Every branch below that
 // holds field work is wave-uniform (L, `used` and the loop bounds depend on the gadget only).
-__global__ void __launch_bounds__(64) gadget_fixed_base_kernel(const GadgetFill a, u32 first) {
+// The hot path.  Every lane derives the width-2 NAF digits of its rounds from s and 3 s (e_j = bit_(j+1)(3s) - bit_(j+1)(s): no
+// carry travels between lanes), owns a contiguous run of ceil(R / 64) rounds and sums its addends in extended coordinates; the
+// lane totals go through an inclusive prefix scan with __shfl_up under the complete twisted Edwards law; each lane then walks
+// its run again from the scanned start and normalises its <= 4 prefixes with one inversion (Montgomery's trick).  No lane ever
+// runs more than one inversion and there is no chain of dependent per-round inversions.  The addends are re-derived from the
+// table in both walks rather than kept across the scan: what stays live over the scan is one point, and over the second walk
+// the run's X, Y, Z (the variant kept: see DESIGN.md for the registers).
+__global__ void __launch_bounds__(64) gadget_fixed_base_kernel(const GadgetFill a, u32 first, u32) {
   const u32 lane = threadIdx.x, proof = blockIdx.y;
   const GadgetRec rec = a.recs[first + blockIdx.x];
   u32x4* const vars = a.vars + 2 * a.var_stride * proof;
@@ -592,9 +599,9 @@ __global__ void __launch_bounds__(64) gadget_fixed_base_kernel(const GadgetFill 
   g_to_int(ld_canon(vars, rec.in_var[0]), s8);
   naf_operands(s8, s9, x9);
   if (lane == 0 && naf_too_long(x9, s9, R)) gadget_fail(a, proof, rec.index, PM_PLONK_GADGET_SCALAR_TOO_LONG);
-  int bit[FB_RUN];
+  int bit[GADGET_RUN];
 #pragma unroll
-  for (u32 j = 0; j < FB_RUN; ++j) {
+  for (u32 j = 0; j < GADGET_RUN; ++j) {
     const u32 k = k0 + j;
     bit[j] = (j < L && k < R) ? naf_digit(x9, s9, R - 1 - (k < R ? k : 0)) : 0;
   }
@@ -608,12 +615,7 @@ __global__ void __launch_bounds__(64) gadget_fixed_base_kernel(const GadgetFill 
     const u32 sh = k0 <= R ? R - k0 + 1 : 1, ws = sh >> 5, bs = sh & 31u;
     u32 xm[9], sm[9], xs[8], ss[8];
 #pragma unroll
-    for (u32 w = 0; w < 9; ++w) {   // the low R + 1 bits
-      const u32 lo = 32 * w, keep = R + 1;
-      const u32 m = lo + 32 <= keep ? 0xffffffffu : (lo >= keep ? 0u : ((1u << ((keep - lo) & 31u)) - 1u));
-      xm[w] = x9[w] & m;
-      sm[w] = s9[w] & m;
-    }
+    for (u32 w = 0; w < 9; ++w) xm[w] = x9[w] & low_bits_mask(w, R + 1), sm[w] = s9[w] & low_bits_mask(w, R + 1);
 #pragma unroll
     for (u32 i = 0; i < 8; ++i) {
       const u32 xl = word_at<9>(xm, i + ws), xh = word_at<9>(xm, i + ws + 1);
@@ -625,7 +627,7 @@ __global__ void __launch_bounds__(64) gadget_fixed_base_kernel(const GadgetFill 
     if (lane == 0) st_var(vars, var_id(a, 3, row0), zero);                          // d_0 = 0
     const Fr one_abi = g_one_abi();
 #pragma unroll
-    for (u32 j = 0; j < FB_RUN; ++j) {
+    for (u32 j = 0; j < GADGET_RUN; ++j) {
       if (j < L) {
         const u32 k = k0 + j;
         const bool valid = k < R;
@@ -639,7 +641,7 @@ __global__ void __launch_bounds__(64) gadget_fixed_base_kernel(const GadgetFill 
   // ---- first walk: the lane's total (lane 0 starts from the start point) and c_k
   EdPoint P = ed_sel(lane == 0, start, neutral);
 #pragma unroll
-  for (u32 j = 0; j < FB_RUN; ++j) {
+  for (u32 j = 0; j < GADGET_RUN; ++j) {
     if (j < L) {
       const u32 k = k0 + j;
       const bool valid = k < R;
@@ -659,10 +661,10 @@ __global__ void __launch_bounds__(64) gadget_fixed_base_kernel(const GadgetFill 
   // ---- second walk from the exclusive prefix; X, Y, Z of the run's points are kept for the shared inversion
   EdPoint Q = ed_shfl_up(P, 1);
   Q = ed_sel(lane == 0, start, Q);
-  Fr PX[FB_RUN], PY[FB_RUN], PZ[FB_RUN], pre[FB_RUN];
+  Fr PX[GADGET_RUN], PY[GADGET_RUN], PZ[GADGET_RUN], pre[GADGET_RUN];
   Fr prod = one;
 #pragma unroll
-  for (u32 j = 0; j < FB_RUN; ++j) {
+  for (u32 j = 0; j < GADGET_RUN; ++j) {
     if (j < L) {
       const u32 k = k0 + j;
       const Addend ad = fb_addend(a.tab, (size_t)rec.tab + (k < R ? k : R - 1), bit[j], nullptr);
@@ -674,7 +676,7 @@ __global__ void __launch_bounds__(64) gadget_fixed_base_kernel(const GadgetFill 
   }
   Fr inv = fe_inv_dev<FrP>(prod);      // the lane's one inversion; all 64 lanes are here
 #pragma unroll
-  for (int j = FB_RUN - 1; j >= 0; --j) {
+  for (int j = GADGET_RUN - 1; j >= 0; --j) {
     if ((u32)j < L) {
       const u32 k = k0 + j;
       const Fr zi = g_to_abi(gmul(inv, pre[j]));          // 1 / Z_j, ABI form: device x ABI -> ABI below
@@ -688,7 +690,6 @@ __global__ void __launch_bounds__(64) gadget_fixed_base_kernel(const GadgetFill 
 }
 
 // ------------------------------------------------------------------ variable-base scalar multiplication
-constexpr u32 VB_RUN = PM_PLONK_GADGET_MAX_ROUNDS / 64;   // rounds a lane owns at most
 // One wave per (gadget, proof): blockIdx.x = the gadget within the launch, blockIdx.y = the proof.  Round k of the chain is
 // dbl = acc + acc (the unified law: start and P may lie off the curve, so no formula that uses the curve equation) and
 // new = dbl + (bit_k P.x, bit_k P.y - bit_k + 1), which for a bit of 0 is dbl itself.  The chain is R rounds deep whatever is
@@ -698,7 +699,7 @@ constexpr u32 VB_RUN = PM_PLONK_GADGET_MAX_ROUNDS / 64;   // rounds a lane owns 
 // chain passes through them, inverts the product of those <= 2 L values of Z once (all 64 lanes reach fe_inv_dev, which votes
 // across the wave) and writes its rounds.  A lane without a round keeps Z = 1.  Some Z of the chain is zero exactly when a
 // denominator of the affine law vanishes in that round, and the lane that owns the round sees it in its product.
-__global__ void __launch_bounds__(64) gadget_var_base_kernel(const GadgetFill a, u32 first) {
+__global__ void __launch_bounds__(64) gadget_var_base_kernel(const GadgetFill a, u32 first, u32) {
   const u32 lane = threadIdx.x, proof = blockIdx.y;
   const GadgetRec rec = a.recs[first + blockIdx.x];
   u32x4* const vars = a.vars + 2 * a.var_stride * proof;
@@ -712,11 +713,11 @@ __global__ void __launch_bounds__(64) gadget_var_base_kernel(const GadgetFill a,
   const Fr px = g_to_dev(px_abi), py = g_to_dev(py_abi), pt = gmul(px, py);
 
   // ---- this lane's bits and select rows: exact for any value of the bit variable
-  unsigned long long ones[VB_RUN];   // bit l of ones[j]: the bit of round l L + j is 1
+  unsigned long long ones[GADGET_RUN];   // bit l of ones[j]: the bit of round l L + j is 1
   u32 mine = 0;
   bool wide = false;
 #pragma unroll
-  for (u32 j = 0; j < VB_RUN; ++j) {
+  for (u32 j = 0; j < GADGET_RUN; ++j) {
     const u32 k = k0 + j;
     const bool valid = j < L && k < R;
     const size_t row = row0 + 6 * (size_t)(valid ? k : 0);
@@ -734,9 +735,9 @@ __global__ void __launch_bounds__(64) gadget_var_base_kernel(const GadgetFill a,
   // ---- the chain
   const Fr sx = g_to_dev(sx_abi), sy = g_to_dev(sy_abi);
   EdPoint Q{sx, sy, one, gmul(sx, sy)};
-  Fr DX[VB_RUN], DY[VB_RUN], DZ[VB_RUN], NX[VB_RUN], NY[VB_RUN], NZ[VB_RUN];
+  Fr DX[GADGET_RUN], DY[GADGET_RUN], DZ[GADGET_RUN], NX[GADGET_RUN], NY[GADGET_RUN], NZ[GADGET_RUN];
 #pragma unroll
-  for (u32 j = 0; j < VB_RUN; ++j) DX[j] = NX[j] = zero, DY[j] = NY[j] = DZ[j] = NZ[j] = one;
+  for (u32 j = 0; j < GADGET_RUN; ++j) DX[j] = NX[j] = zero, DY[j] = NY[j] = DZ[j] = NZ[j] = one;
   u32 owner = 0, slot = 0;           // round k = owner L + slot
 #pragma unroll 1
   for (u32 k = 0; k < R; ++k) {
@@ -745,7 +746,7 @@ __global__ void __launch_bounds__(64) gadget_var_base_kernel(const GadgetFill a,
     Q = D;
     if ((m >> owner) & 1ull) Q = ed_madd(D, px, py, pt, d);
 #pragma unroll
-    for (u32 j = 0; j < VB_RUN; ++j) {
+    for (u32 j = 0; j < GADGET_RUN; ++j) {
       const bool keep = owner == lane && slot == j;
       DX[j] = g_sel(keep, D.X, DX[j]), DY[j] = g_sel(keep, D.Y, DY[j]), DZ[j] = g_sel(keep, D.Z, DZ[j]);
       NX[j] = g_sel(keep, Q.X, NX[j]), NY[j] = g_sel(keep, Q.Y, NY[j]), NZ[j] = g_sel(keep, Q.Z, NZ[j]);
@@ -754,10 +755,10 @@ __global__ void __launch_bounds__(64) gadget_var_base_kernel(const GadgetFill a,
   }
 
   // ---- one inversion for the lane's <= 2 L points (Montgomery's trick), then its rows
-  Fr pre[2 * VB_RUN];
+  Fr pre[2 * GADGET_RUN];
   Fr prod = one;
 #pragma unroll
-  for (u32 j = 0; j < VB_RUN; ++j) {
+  for (u32 j = 0; j < GADGET_RUN; ++j) {
     if (j < L) {
       pre[2 * j] = prod;
       prod = gmul(prod, DZ[j]);
@@ -771,7 +772,7 @@ __global__ void __launch_bounds__(64) gadget_var_base_kernel(const GadgetFill a,
   Fr inv = fe_inv_dev<FrP>(prod);    // 0 -> 0: the lane that owns a degenerate round writes zeros; all 64 lanes are here
   if (lane == 0) st_var(vars, var_id(a, 3, row0 + 1), gmul(sx, sy_abi));
 #pragma unroll
-  for (int j = VB_RUN - 1; j >= 0; --j) {
+  for (int j = GADGET_RUN - 1; j >= 0; --j) {
     if ((u32)j < L) {
       const u32 k = k0 + j;
       const Fr zn = g_to_abi(gmul(inv, pre[2 * j + 1]));   // 1 / Z, ABI form: device x ABI -> ABI below
@@ -793,89 +794,60 @@ __global__ void __launch_bounds__(64) gadget_var_base_kernel(const GadgetFill a,
   }
 }
 
+// a kind's fill kernel: (arguments, first record of the launch, records); the kind table has the launch shape
+void (*const FILL_KERNELS[GADGET_KINDS])(GadgetFill, u32, u32) = {
+    gadget_range_kernel,       gadget_logic_kernel, gadget_fixed_base_kernel, gadget_curve_add_kernel, gadget_arith_kernel, gadget_bits_kernel,
+    gadget_maybe_equal_kernel, gadget_hades_kernel, nullptr /* 8 */,          nullptr /* 9 */,         gadget_var_base_kernel};
 }  // namespace
 
-int gadget_verify(pm_ctx* ctx, const void* d_recs, uint32_t count, size_t n, const void* d_sel, bool all11, const void* d_wire_vars,
-                  void* d_tab, void* d_coef, void* d_hcoef, void* d_hids, size_t hades_rounds, uint32_t* d_bad, hipStream_t st) {
+int gadget_verify(pm_ctx* ctx, const GadgetTables& t, size_t n, const void* d_sel, bool all11, const void* d_wire_vars, hipStream_t st) {
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (!st) st = ctx->stream;
   PM_HIP(ctx, hipSetDevice(ctx->device));
+  u32* const d_bad = (u32*)t.rep;
   PM_HIP(ctx, hipMemsetAsync(d_bad, 0xff, 4, st));
-  if (hades_rounds) PM_HIP(ctx, hipMemsetAsync(d_hids, 0xff, hades_rounds * 120, st));   // PM_PLONK_NO_VAR where no row writes
-  hipLaunchKernelGGL(gadget_verify_kernel, dim3(count), dim3(256), 0, st, (const GadgetRec*)d_recs, (const u32x4*)d_sel, n,
-                     all11 ? 1u : 0u, all11 ? 7u : 2u, (u32x4*)d_tab, d_bad);
+  if (t.hades_rounds) PM_HIP(ctx, hipMemsetAsync(t.hids, 0xff, t.hades_rounds * GADGET_ROUND_ID_BYTES, st));   // PM_PLONK_NO_VAR where no row writes
+  hipLaunchKernelGGL(gadget_verify_kernel, dim3(t.count), dim3(256), 0, st, (const GadgetRec*)t.recs, (const u32x4*)d_sel, n,
+                     all11 ? 1u : 0u, all11 ? 7u : 2u, (u32x4*)t.tab, d_bad);
   if (all11)
-    hipLaunchKernelGGL(composed_verify_kernel, dim3(count), dim3(256), 0, st, (const GadgetRec*)d_recs, (const u32x4*)d_sel, n,
-                       (const u32*)d_wire_vars, (u32x4*)d_coef, (u32x4*)d_hcoef, (u32*)d_hids, d_bad);
+    hipLaunchKernelGGL(composed_verify_kernel, dim3(t.count), dim3(256), 0, st, (const GadgetRec*)t.recs, (const u32x4*)d_sel, n,
+                       (const u32*)d_wire_vars, (u32x4*)t.coef, (u32x4*)t.hcoef, (u32*)t.hids, d_bad);
   PM_HIP(ctx, hipGetLastError());
   return PM_OK;
 }
 
-int gadget_fill(pm_ctx* ctx, const void* d_recs, const GadgetGroup* groups, size_t n_groups, const void* d_wire_vars, size_t n,
-                const void* d_tab, const void* d_coef, const void* d_hcoef, const void* d_hids, void* d_vars, size_t var_stride,
-                uint32_t batch, void* d_rep, unsigned long long* rep_host, hipStream_t st) {
+int gadget_fill(pm_ctx* ctx, const GadgetTables& t, const std::vector<GadgetGroup>& groups, const void* d_wire_vars, size_t n,
+                void* d_vars, size_t var_stride, uint32_t batch, unsigned long long* rep_host, hipStream_t st) {
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (!st) st = ctx->stream;
   PM_HIP(ctx, hipSetDevice(ctx->device));
-  GadgetFill a;
-  a.recs = (const GadgetRec*)d_recs;
-  a.wire_vars = (const u32*)d_wire_vars;
-  a.tab = (const u32x4*)d_tab;
-  a.coef = (const u32x4*)d_coef;
-  a.hcoef = (const u32x4*)d_hcoef;
-  a.hids = (const u32*)d_hids;
-  a.vars = (u32x4*)d_vars;
-  a.var_stride = var_stride;
-  a.n = n;
-  a.rep = (unsigned long long*)d_rep;
-  {
-    const host::Field<4>& F = host::FR();   // JubJub d = -(10240 / 10241)
-    const HFr q = host::mul(host::from_u64(10240, F), host::inv(host::from_u64(10241, F), F), F);
-    to_limbs29_shift(a.edwards_d, host::sub(host::zero<4>(), q, F), 1);
-  }
-  PM_HIP(ctx, hipMemsetAsync(d_rep, 0, (size_t)batch * 8, st));
-  PM_HIP(ctx, hipMemsetAsync((char*)d_rep + (size_t)batch * 8, 0xff, (size_t)batch * 8, st));
+  GadgetFill a{.recs = (const GadgetRec*)t.recs, .wire_vars = (const u32*)d_wire_vars, .tab = (const u32x4*)t.tab, .coef = (const u32x4*)t.coef,
+               .hcoef = (const u32x4*)t.hcoef, .hids = (const u32*)t.hids, .vars = (u32x4*)d_vars, .var_stride = var_stride, .n = n,
+               .rep = (unsigned long long*)t.rep, .edwards_d = {}};
+  const host::Field<4>& F = host::FR();   // JubJub d = -(10240 / 10241): the inversion once, not per call
+  static const HFr edwards_d = host::sub(host::zero<4>(), host::mul(host::from_u64(10240, F), host::inv(host::from_u64(10241, F), F), F), F);
+  to_limbs29_shift(a.edwards_d, edwards_d, 1);
+  PM_HIP(ctx, hipMemsetAsync(t.rep, 0, (size_t)batch * 8, st));
+  PM_HIP(ctx, hipMemsetAsync((char*)t.rep + (size_t)batch * 8, 0xff, (size_t)batch * 8, st));
   {
     ProfScope prof(ctx, st, "plonk_gadget_fill");
-    for (size_t i = 0; i < n_groups; ++i) {
-      const GadgetGroup& g = groups[i];
-      const dim3 per_thread((g.count + 63) / 64, batch), per_wave(g.count, batch);
-      switch (g.kind) {
-        case PM_PLONK_GADGET_RANGE:
-          hipLaunchKernelGGL(gadget_range_kernel, per_thread, dim3(64), 0, st, a, g.first, g.count);
-          break;
-        case PM_PLONK_GADGET_LOGIC:
-          hipLaunchKernelGGL(gadget_logic_kernel, per_thread, dim3(64), 0, st, a, g.first, g.count);
-          break;
-        case PM_PLONK_GADGET_FIXED_BASE:
-          hipLaunchKernelGGL(gadget_fixed_base_kernel, per_wave, dim3(64), 0, st, a, g.first);
-          break;
-        case PM_PLONK_GADGET_CURVE_ADD:
-          hipLaunchKernelGGL(gadget_curve_add_kernel, per_thread, dim3(64), 0, st, a, g.first, g.count);
-          break;
-        case PM_PLONK_COMPOSED_ARITH:
-          hipLaunchKernelGGL(gadget_arith_kernel, per_thread, dim3(64), 0, st, a, g.first, g.count);
-          break;
-        case PM_PLONK_COMPOSED_BITS:   // the gadgets along y, at most 65535 a launch
-          for (u32 lo = 0; lo < g.count; lo += 65535u)
-            hipLaunchKernelGGL(gadget_bits_kernel, dim3((g.span + 63) / 64, std::min(g.count - lo, 65535u), batch), dim3(64), 0, st, a,
-                               g.first + lo);
-          break;
-        case PM_PLONK_COMPOSED_MAYBE_EQUAL:
-          hipLaunchKernelGGL(gadget_maybe_equal_kernel, per_thread, dim3(64), 0, st, a, g.first, g.count);
-          break;
-        case PM_PLONK_PERMUTATION_HADES:   // the gadgets along x, at most 2^31 - 1 a launch
-          hipLaunchKernelGGL(gadget_hades_kernel, per_wave, dim3(64), 0, st, a, g.first);
-          break;
-        default:                       // PM_PLONK_GADGET_VAR_BASE
-          hipLaunchKernelGGL(gadget_var_base_kernel, per_wave, dim3(64), 0, st, a, g.first);
-          break;
+    for (const GadgetGroup& g : groups) {
+      const auto kernel = FILL_KERNELS[g.kind];   // a group's kind is one set time knew
+      const GadgetLaunch shape = gadget_kind(g.kind).launch;
+      if (shape == GadgetLaunch::NONE) return set_err(ctx, PM_ERR_BAD_ARG, "a gadget group of no kind");
+      // a thread or a wave per gadget: the gadgets along x, one launch (at most 2^31 - 1).  BITS_X: along y, at most 65535 a launch
+      const u32 most = shape == GadgetLaunch::BITS_X ? 65535u : g.count;
+      for (u32 lo = 0; lo < g.count; lo += most) {
+        const u32 part = std::min(g.count - lo, most);
+        const dim3 grid = shape == GadgetLaunch::BITS_X ? dim3((g.span + 63) / 64, part, batch)
+                                                        : dim3(shape == GadgetLaunch::PER_WAVE ? part : (part + 63) / 64, batch);
+        hipLaunchKernelGGL(kernel, grid, dim3(64), 0, st, a, g.first + lo, part);
       }
     }
   }
   PM_HIP(ctx, hipGetLastError());
   if (rep_host) {
-    PM_HIP(ctx, hipMemcpyAsync(rep_host, d_rep, (size_t)batch * 16, hipMemcpyDeviceToHost, st));
+    PM_HIP(ctx, hipMemcpyAsync(rep_host, t.rep, (size_t)batch * 16, hipMemcpyDeviceToHost, st));
     PM_HIP(ctx, hipStreamSynchronize(st));
   }
   return PM_OK;

@@ -1,70 +1,42 @@
 // Gadget witnesses: pm_plonk_key_set_gadgets / pm_plonk_fill_gadgets_dev (included by prover.hip: the key is pm_plonk_prove's;
-// DESIGN.md sections 7.2f to 7.2i).  The kernels and what each gadget writes are in gadgets.hip; here is the table a key holds and the
-// host side of the two calls.
+// DESIGN.md sections 7.2f to 7.2i).  The kernels and what each gadget writes are in gadgets.hip, what the host needs to know of a
+// kind in gadget_kinds.h; here is the table a key holds and the host side of the two calls.
+#include "gadget_kinds.h"
+
 struct GadgetState {
   size_t bytes = 0;                        // device bytes held
-  size_t count = 0;                        // gadgets
-  void* recs = nullptr;                    // pm::GadgetRec x count, in launch order
-  void* tab = nullptr;                     // table points of the fixed-base rounds, 64 bytes each
-  void* coef = nullptr;                    // q_m q_l q_r q_4 q_c of the ARITH rows, 160 bytes each; nullptr without such rows
-  void* hcoef = nullptr;                   // round keys and matrix entries of the HADES rounds, 960 bytes each; nullptr without
-  void* hids = nullptr;                    // c ids of the rows of the HADES rounds, 120 bytes each; nullptr without
-  void* rep = nullptr;                     // 2 x PM_PLONK_MAX_BATCH report words
+  pm::GadgetTables dev;
   std::vector<pm::GadgetGroup> groups;     // one launch each, levels rising
 };
 
-// the rows a gadget claims (the widget kinds: the trailing row included; the composed kinds, HADES and VAR_BASE have none); 0: a kind,
-// count or param that is refused whatever the circuit
+// the rows a gadget claims (the widget kinds: the trailing row included); 0: a kind, count or param that is refused whatever the
+// circuit
 extern "C" uint64_t pm_plonk_gadget_rows(const pm_plonk_gadget* g) {
   if (!g) return 0;
-  const uint64_t c = g->count, f = g->param;
-  switch (g->kind) {
-    case PM_PLONK_GADGET_RANGE:
-    case PM_PLONK_GADGET_LOGIC:
-      return c ? c + 1 : 0;
-    case PM_PLONK_GADGET_FIXED_BASE:
-      return c && c <= PM_PLONK_GADGET_MAX_ROUNDS ? c + 1 : 0;
-    case PM_PLONK_GADGET_CURVE_ADD:
-      return 2;
-    case PM_PLONK_COMPOSED_ARITH:
-      return c;
-    case PM_PLONK_COMPOSED_BITS:
-      return c && c <= PM_PLONK_COMPOSED_MAX_BITS ? 2 * c : 0;
-    case PM_PLONK_COMPOSED_MAYBE_EQUAL:
-      return 3;
-    case PM_PLONK_PERMUTATION_HADES:   // 30 rows a full round, 18 a partial one
-      return c && !(f & 1) && f <= c ? 30 * f + 18 * (c - f) : 0;
-    case PM_PLONK_GADGET_VAR_BASE:     // doubling, select x, select y, addition: 2 + 1 + 1 + 2 rows a round
-      return c && c <= PM_PLONK_GADGET_MAX_ROUNDS ? 6 * c : 0;
-    default:
-      return 0;
-  }
+  return pm::gadget_kind_rows(pm::gadget_kind(g->kind), g->count, g->param);
 }
 
 namespace {
 void gadget_state_free(pm_ctx* ctx, GadgetState* gs) {
   if (!gs) return;
-  for (void* p : {gs->recs, gs->tab, gs->coef, gs->hcoef, gs->hids, gs->rep})
+  gs->dev.each_array([&](void* p, size_t, size_t) {
     if (p && ctx) (void)pm_dev_free(ctx, p);
+  });
   delete gs;
 }
 
 // what the host can tell about gadget g; empty = nothing
 std::string gadget_host_fault(const pm_plonk_gadget& g, const pm_plonk_gadget* prev, size_t n, size_t num_vars) {
   if (prev && g.level < prev->level) return "levels must not fall";
-  const bool hades = g.kind == PM_PLONK_PERMUTATION_HADES, vbase = g.kind == PM_PLONK_GADGET_VAR_BASE;
-  if (g.kind > PM_PLONK_PERMUTATION_HADES && !vbase) return "unknown kind";   // 8 and 9 are no kinds
-  if (!hades && g.param > (g.kind == PM_PLONK_GADGET_LOGIC ? 1u : 0u)) return "unknown param";
-  const bool add = g.kind == PM_PLONK_GADGET_CURVE_ADD, eq = g.kind == PM_PLONK_COMPOSED_MAYBE_EQUAL;
-  const bool run = g.kind == PM_PLONK_COMPOSED_ARITH, bits = g.kind == PM_PLONK_COMPOSED_BITS;
-  if (!add && !eq && g.count == 0) return "count is 0";
-  if ((g.kind == PM_PLONK_GADGET_FIXED_BASE || vbase) && g.count > PM_PLONK_GADGET_MAX_ROUNDS) return "more than PM_PLONK_GADGET_MAX_ROUNDS rounds";
-  if (bits && g.count > PM_PLONK_COMPOSED_MAX_BITS) return "more than PM_PLONK_COMPOSED_MAX_BITS bits";
-  if (hades && ((g.param & 1u) || g.param > g.count)) return "its full rounds (param) must be even and at most its rounds (count)";
-  const uint64_t rows = pm_plonk_gadget_rows(&g);   // not 0: what makes it 0 was refused above
+  const pm::GadgetKind k = pm::gadget_kind(g.kind);
+  if (k.launch == pm::GadgetLaunch::NONE) return "unknown kind";
+  if (!k.rows_per_param && g.param > k.max_param) return "unknown param";
+  if (k.rows_per && g.count == 0) return "count is 0";
+  if (k.max_count && g.count > k.max_count) return k.over_max;
+  const uint64_t rows = pm::gadget_kind_rows(k, g.count, g.param);   // 0: what is left, the param of a kind with rows_per_param
+  if (!rows) return "its full rounds (param) must be even and at most its rounds (count)";
   if (g.first_row >= n || rows > n - g.first_row) return "its rows leave [0, n)";
-  const int used = add || eq || run || hades || vbase ? 0 : g.kind == PM_PLONK_GADGET_LOGIC ? 2 : 1;
-  for (int i = 0; i < used; ++i)
+  for (uint32_t i = 0; i < k.in_vars; ++i)
     if (g.in_var[i] >= num_vars) return "in_var is not below num_vars";
   return "";
 }
@@ -93,28 +65,26 @@ extern "C" int pm_plonk_key_set_gadgets(pm_ctx* ctx, pm_prover_key* pk, const pm
   // launch order: level, kind, index (the levels already rise: a stable order by kind inside each level)
   std::vector<pm::GadgetRec> recs;
   std::vector<pm::GadgetGroup> groups;
-  uint32_t rounds = 0;
-  uint64_t arith_rows = 0, hades_rounds = 0, hades_rows = 0;
-  bool composed = false;                   // a kind that needs all eleven selectors on H
+  uint64_t units[4] = {0, 0, 0, 0};        // by pm::GadgetTab: what the gadgets so far take of each gathered array
+  uint64_t hades_rows = 0;
+  bool all11 = false;
   for (size_t lo = 0; lo < lim;) {
     size_t hi = lo;
     while (hi < lim && gadgets[hi].level == gadgets[lo].level) ++hi;
-    for (uint32_t kind = 0; kind <= PM_PLONK_GADGET_VAR_BASE; ++kind) {
+    for (uint32_t kind = 0; kind < pm::GADGET_KINDS; ++kind) {
+      const pm::GadgetKind k = pm::gadget_kind(kind);
       pm::GadgetGroup grp{kind, (uint32_t)recs.size(), 0, 0};
       for (size_t i = lo; i < hi; ++i) {
         const pm_plonk_gadget& g = gadgets[i];
         if (g.kind != kind) continue;
-        const bool run = kind == PM_PLONK_COMPOSED_ARITH, hades = kind == PM_PLONK_PERMUTATION_HADES;
-        pm::GadgetRec r{g.kind, g.param, (uint32_t)g.first_row, g.count, {g.in_var[0], g.in_var[1]}, (uint32_t)i,
-                        run ? (uint32_t)arith_rows : hades ? (uint32_t)hades_rounds : rounds};
-        if (kind == PM_PLONK_GADGET_FIXED_BASE) rounds += g.count;
-        if (run) arith_rows += g.count;
-        if (arith_rows > 0xffffffffull) return pm::set_err(ctx, PM_ERR_BAD_ARG, "too many ARITH rows");
-        if (hades) hades_rounds += g.count, hades_rows += pm_plonk_gadget_rows(&g);
+        uint64_t& used = units[(size_t)k.tab];
+        recs.push_back({g.kind, g.param, (uint32_t)g.first_row, g.count, {g.in_var[0], g.in_var[1]}, (uint32_t)i, (uint32_t)used});
+        if (k.tab != pm::GadgetTab::NONE) used += g.count;
+        if (k.tab == pm::GadgetTab::COEF && used > 0xffffffffull) return pm::set_err(ctx, PM_ERR_BAD_ARG, "too many ARITH rows");
+        if (k.tab == pm::GadgetTab::ROUNDS) hades_rows += pm::gadget_kind_rows(k, g.count, g.param);
         if (hades_rows > 0x100000000ull) return pm::set_err(ctx, PM_ERR_BAD_ARG, "too many HADES rows");
-        composed |= kind >= PM_PLONK_COMPOSED_ARITH;
-        if (kind == PM_PLONK_COMPOSED_BITS) grp.span = std::max(grp.span, g.count);
-        recs.push_back(r);
+        all11 |= k.all_selectors;
+        if (k.launch == pm::GadgetLaunch::BITS_X) grp.span = std::max(grp.span, g.count);
         ++grp.count;
       }
       if (grp.count) groups.push_back(grp);
@@ -126,24 +96,19 @@ extern "C" int pm_plonk_key_set_gadgets(pm_ctx* ctx, pm_prover_key* pk, const pm
   uint32_t bad = 0xffffffffu;
   auto body = [&]() -> int {
     if (recs.empty()) return PM_OK;
-    PK_TRY(pm_dev_alloc(ctx, recs.size() * sizeof(pm::GadgetRec), &gs->recs));
-    PK_TRY(pm_dev_alloc(ctx, std::max<size_t>(rounds, 1) * 64, &gs->tab));
-    PK_TRY(pm_dev_alloc(ctx, 2 * (size_t)PM_PLONK_MAX_BATCH * 8, &gs->rep));
-    gs->bytes = recs.size() * sizeof(pm::GadgetRec) + std::max<size_t>(rounds, 1) * 64 + 2 * (size_t)PM_PLONK_MAX_BATCH * 8;
-    if (arith_rows) {
-      PK_TRY(pm_dev_alloc(ctx, (size_t)arith_rows * 160, &gs->coef));
-      gs->bytes += (size_t)arith_rows * 160;
-    }
-    if (hades_rounds) {
-      PK_TRY(pm_dev_alloc(ctx, (size_t)hades_rounds * 960, &gs->hcoef));
-      PK_TRY(pm_dev_alloc(ctx, (size_t)hades_rounds * 120, &gs->hids));
-      gs->bytes += (size_t)hades_rounds * 1080;
-    }
-    PK_TRY(pm_dev_upload(ctx, gs->recs, recs.data(), recs.size() * sizeof(pm::GadgetRec)));
+    pm::GadgetTables& t = gs->dev;
+    t.count = recs.size(), t.points = units[(size_t)pm::GadgetTab::POINTS], t.arith_rows = units[(size_t)pm::GadgetTab::COEF];
+    t.hades_rounds = units[(size_t)pm::GadgetTab::ROUNDS];
+    int rc = PM_OK;
+    t.each_array([&](void*& p, size_t n_units, size_t unit_bytes) {
+      if (rc == PM_OK && n_units) rc = pm_dev_alloc(ctx, n_units * unit_bytes, &p), gs->bytes += n_units * unit_bytes;
+    });
+    PK_TRY(rc);
+    PK_TRY(pm_dev_upload(ctx, t.recs, recs.data(), recs.size() * sizeof(pm::GadgetRec)));
     // q_l q_r | q_range q_logic q_fixed_group_add q_variable_group_add: coefficients -> values on H, one batched transform
-    // a table with a composed kind: all eleven (the rows' coefficients are part of what is checked)
+    // a table with a kind that says so: all eleven (the rows' coefficients are part of what is checked)
     PM_HIP(ctx, hipSetDevice(ctx->device));
-    if (composed) {
+    if (all11) {
       PK_TRY(pm_dev_alloc(ctx, (size_t)NSEL * n * 32, &sel6));
       PK_TRY(pm_fr_ntt_dev(ctx, pk->sel_coeffs, n, n, sel6, n, pk->log_n, NSEL, 0, nullptr));
     } else {
@@ -153,28 +118,20 @@ extern "C" int pm_plonk_key_set_gadgets(pm_ctx* ctx, pm_prover_key* pk, const pm
                                  ctx->stream));
       PK_TRY(pm_fr_ntt_dev(ctx, sel6, n, n, sel6, n, pk->log_n, 6, 0, nullptr));
     }
-    PK_TRY(pm::gadget_verify(ctx, gs->recs, (uint32_t)recs.size(), n, sel6, composed, pk->wire_vars, gs->tab, gs->coef,
-                             gs->hcoef, gs->hids, (size_t)hades_rounds, (uint32_t*)gs->rep, nullptr));
-    PK_TRY(pm_dev_download(ctx, &bad, gs->rep, 4));
+    PK_TRY(pm::gadget_verify(ctx, t, n, sel6, all11, pk->wire_vars, nullptr));
+    PK_TRY(pm_dev_download(ctx, &bad, t.rep, 4));
     return pm_sync(ctx);
   };
   int rc = body();
   if (sel6) (void)pm_dev_free(ctx, sel6);
   if (rc == PM_OK && bad != 0xffffffffu)
-    rc = pm::set_err(ctx, PM_ERR_BAD_ARG,
-                     "gadget " + std::to_string(bad) +
-                         (gadgets[bad].kind == PM_PLONK_GADGET_VAR_BASE
-                              ? ": a row it claims is not the row a variable-base round lays out (selectors, coefficients or wire variables)"
-                          : gadgets[bad].kind >= PM_PLONK_COMPOSED_ARITH
-                              ? ": a row it claims is not the arithmetic row its kind lays out (selectors, coefficients or wire variables)"
-                              : ": a row it claims does not have its kind's selector"));
+    rc = pm::set_err(ctx, PM_ERR_BAD_ARG, "gadget " + std::to_string(bad) + pm::gadget_kind(gadgets[bad].kind).refusal);
   else if (rc == PM_OK && lim < count)
     rc = pm::set_err(ctx, PM_ERR_BAD_ARG, "gadget " + std::to_string(lim) + ": " + why);
   if (rc != PM_OK) {
     gadget_state_free(ctx, gs);
     return rc;
   }
-  gs->count = count;
   gs->groups = std::move(groups);
   PK_TRY(pm_sync(ctx));                    // a fill on the table being replaced has finished
   gadget_state_free(ctx, pk->gadgets);
@@ -192,8 +149,8 @@ extern "C" int pm_plonk_fill_gadgets_dev(pm_ctx* ctx, const pm_prover_key* pk, v
   if (batch == 0 || batch > PM_PLONK_MAX_BATCH) return pm::set_err(ctx, PM_ERR_BAD_ARG, "batch must be in 1..PM_PLONK_MAX_BATCH");
   if (var_stride < pk->num_vars) return pm::set_err(ctx, PM_ERR_BAD_ARG, "var_stride is below the key's num_vars");
   unsigned long long rep[2 * PM_PLONK_MAX_BATCH];
-  PK_TRY(pm::gadget_fill(ctx, gs->recs, gs->groups.data(), gs->groups.size(), pk->wire_vars, pk->n, gs->tab, gs->coef, gs->hcoef, gs->hids, d_vars,
-                         var_stride, batch, gs->rep, reports ? rep : nullptr, (hipStream_t)stream));
+  PK_TRY(pm::gadget_fill(ctx, gs->dev, gs->groups, pk->wire_vars, pk->n, d_vars, var_stride, batch, reports ? rep : nullptr,
+                         (hipStream_t)stream));
   if (reports)
     for (uint32_t b = 0; b < batch; ++b) {
       pm_plonk_gadget_report& r = reports[b];

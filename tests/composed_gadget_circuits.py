@@ -195,3 +195,105 @@ def refusal_case():
     arith = b.fill_arithmetic(28)
     rng = random.Random(28)
     return b, {v: rng.getrandbits(16), w: rng.getrandbits(4), **arith}, decoys
+
+
+# ---------------------------------------------------------------------------------------------- every set-time rule, one decoy each
+# What pm_plonk_key_set_gadgets checks on the rows a composed gadget claims.  On EVERY row: q_arith is not zero and the four
+# widget selectors are zero.  Then, with the coefficients in the order q_m q_l q_r q_o q_c q_4:
+#   ARITH, every row:              q_o = -1, c is a variable; nothing else
+#   BITS, boolean row of bit k:    1 0 0 -1 0 0; a is a variable, b = a, c = a
+#   BITS, sum row of bit k:        0 2^k 1 -1 0 0; c is a variable, a = the bit (a of the row before), and for k > 0
+#                                  b = acc_(k-1) (c of the row two before); b of bit 0 is free: the start of the sum
+#   MAYBE_EQUAL row 0 (u):         0 1 -1 -1 0 0; c is a variable
+#   MAYBE_EQUAL row 1 (y):         -1 0 0 -1 1 0; a and c are variables, b = u
+#   MAYBE_EQUAL row 2:             1 0 0 0 0 0; a = y, b = u
+# d is never looked at, nor is c of the last MAYBE_EQUAL row.
+COEFF_ORDER = ("q_m", "q_l", "q_r", "q_o", "q_c", "q_4")
+_WIDGETS = ("q_range", "q_logic", "q_fixed_group_add", "q_variable_group_add")
+DECOY_BITS = 2                                     # k = 0 and k > 0
+
+
+def _wrong(x):
+    return 2 if x % R == 1 else 1
+
+
+@functools.lru_cache(maxsize=None)
+def rule_decoys_case():
+    """a good table (a glue row, two BITS, two MAYBE_EQUAL and two ARITH runs: the second of each kind sits at a non-zero
+    offset of whatever is gathered for it) and, beside it, gadgets of DECOY_BITS bits, MAYBE_EQUALs and one-row ARITH runs that
+    are wrong in ONE place of the list above; the good table never claims them.
+    -> (builder, input assignment, {kind: {name: first row}}), an untouched "good" one of every kind among them"""
+    b = CM.Builder(512)
+    v, w, other = b.var(True), b.var(True), b.var(True)
+    t = b.add(v, w, q_l=3, q_r=5, q_c=7, level=0)
+    b.arith([(v, w, None, t, dict(q_m=2, q_l=3, q_r=5, q_4=11, q_c=7)), (w, v, None, None, dict(q_m=R - 1, q_c=1))], level=1)
+    b.decomposition(t, 8, level=1)
+    b.decomposition(w, 3, level=1)
+    decoys = {"bits": {}, "maybe_equal": {}, "arith": {}}
+
+    def no_var(r0, rows, row):
+        """c of the row is no variable, and neither is any position of the gadget that names it"""
+        x = b.wires[2][r0 + row]
+        for j in range(4):
+            for i in range(r0, r0 + rows):
+                if b.wires[j][i] == x:
+                    b.wires[j][i] = CM.NO_VAR
+
+    def lay(kind):
+        r0 = b.row
+        if kind == "bits":
+            bit, acc = [b.var() for _ in range(DECOY_BITS)], [b.var() for _ in range(DECOY_BITS)]
+            for k in range(DECOY_BITS):
+                b.gate(bit[k], bit[k], bit[k], q_m=1, q_o=R - 1)
+                b.gate(bit[k], acc[k - 1] if k else v, acc[k], q_l=1 << k, q_r=1, q_o=R - 1)
+        elif kind == "maybe_equal":
+            u, z, y = b.var(), b.var(), b.var()
+            b.gate(v, w, u, q_l=1, q_r=R - 1, q_o=R - 1)
+            b.gate(z, u, y, q_m=R - 1, q_c=1, q_o=R - 1)
+            b.gate(y, u, u, q_m=1)
+        else:
+            b.gate(v, w, b.var(), q_m=3, q_l=1, q_r=1, q_o=R - 1)
+        return r0, b.row - r0
+
+    def decoy(kind, name, spoil):
+        r0, rows = lay(kind)
+        before = ([list(x) for x in b.wires], {k: list(x) for k, x in b.sel.items()})
+        spoil(r0, rows)
+        assert name == "good" or before != ([list(x) for x in b.wires], {k: list(x) for k, x in b.sel.items()}), name
+        assert name not in decoys[kind]
+        decoys[kind][name] = r0
+
+    def sel(key, row, value=None):
+        return lambda r0, rows: b.sel[key].__setitem__(r0 + row, _wrong(b.sel[key][r0 + row]) if value is None else value)
+
+    def wire(j, row, var=other):
+        return lambda r0, rows: b.wires[j].__setitem__(r0 + row, var)
+
+    for kind, rows in (("bits", 2 * DECOY_BITS), ("maybe_equal", 3), ("arith", 1)):
+        decoy(kind, "good", lambda r0, rows: None)
+        for row in range(rows):
+            for q in (("q_o",) if kind == "arith" else COEFF_ORDER):      # ARITH: the other five are free
+                if (kind, row, q) != ("maybe_equal", 2, "q_o"):
+                    decoy(kind, f"row{row}_{q}", sel(q, row))
+            decoy(kind, f"row{row}_no_arith", sel("q_arith", row, 0))
+            decoy(kind, f"row{row}_widget", sel(_WIDGETS[row % 4], row, 1))
+    decoy("maybe_equal", "row2_q_o", sel("q_o", 2, R - 1))               # 0 expected on this row, not -1
+    decoy("bits", "row3_q_l_is_4", sel("q_l", 3, 4))                       # 2^1 expected, not the next power
+    decoy("bits", "bool_b", wire(1, 2))
+    decoy("bits", "bool_c", wire(2, 0))
+    decoy("bits", "bool_no_var", lambda r0, rows: no_var(r0, rows, 2))    # a = b = c = a of the sum row: all no variable
+    decoy("bits", "sum_bit_k0", wire(0, 1))
+    decoy("bits", "sum_bit_k1", wire(0, 3))
+    decoy("bits", "sum_link", wire(1, 3))
+    decoy("bits", "sum_no_var_k0", lambda r0, rows: no_var(r0, rows, 1))
+    decoy("bits", "sum_no_var_k1", lambda r0, rows: no_var(r0, rows, 3))
+    decoy("maybe_equal", "no_var_u", lambda r0, rows: no_var(r0, rows, 0))
+    decoy("maybe_equal", "no_var_z", wire(0, 1, CM.NO_VAR))
+    decoy("maybe_equal", "no_var_y", lambda r0, rows: no_var(r0, rows, 1))
+    decoy("maybe_equal", "row1_b", wire(1, 1))
+    decoy("maybe_equal", "row2_a", wire(0, 2))
+    decoy("maybe_equal", "row2_b", wire(1, 2))
+    decoy("arith", "no_var", wire(2, 0, CM.NO_VAR))
+    arith = b.fill_arithmetic(29)
+    rng = random.Random(29)
+    return b, {v: rng.getrandbits(16), w: rng.getrandbits(3), other: rng.randrange(R), **arith}, decoys

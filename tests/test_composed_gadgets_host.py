@@ -96,6 +96,23 @@ def test_model_satisfies_the_circuits_of_the_gpu_tests():
     assert bad and all(any(r0 <= i < r0 + 8 for r0 in decoys.values()) for i in bad)
 
 
+def test_rule_decoys_are_each_wrong_in_one_place():
+    """composed_gadget_circuits.rule_decoys_case: every decoy differs from the rows its kind lays (the case asserts that), the
+    good table holds two gadgets of every composed kind, is satisfied by the model and never claims a decoy"""
+    b, a, decoys = CC.rule_decoys_case()
+    assert b.n <= 1024 and sorted(g[0] for g in b.gadgets) == ["arith", "arith", "bits", "bits", "maybe_equal", "maybe_equal"]
+    rows = {"bits": 2 * CC.DECOY_BITS, "maybe_equal": 3, "arith": 1}
+    claimed_end = max(g[2] + 3 for g in b.gadgets)
+    spans = [(r0, r0 + rows[kind]) for kind, table in decoys.items() for r0 in table.values()]
+    assert min(lo for lo, _ in spans) >= claimed_end and len(set(spans)) == len(spans)
+    assert all("good" in table for table in decoys.values())
+    assert len(decoys["bits"]) >= 30 and len(decoys["maybe_equal"]) >= 25 and len(decoys["arith"]) == 5
+    only, full, reasons = b.model(a)
+    assert not reasons
+    bad = set(b.arithmetic_failures(full))
+    assert bad and all(any(lo <= i < hi for lo, hi in spans) for i in bad)
+
+
 @pytest.mark.parametrize("bounds", [(CC.RANGE_MIN, CC.RANGE_MAX), (0, 1 << 64), (5, 6), (1, 1 << 31)])
 def test_range_check_is_one_inside_the_bounds(bounds):
     lo, hi = bounds

@@ -190,6 +190,38 @@ def test_refusals_name_the_gadget_and_keep_the_table(ctx):
         pk.free()
 
 
+def test_every_set_time_rule_refuses_its_decoy(ctx):
+    """composed_gadget_circuits.rule_decoys_case: every field the set-time check looks at, wrong in that one place only"""
+    import plonk_prototype_amd as pa
+    b, a, decoys = CC.rule_decoys_case()
+    pk = pa.preprocess(b.circuit(), ctx)
+    good = b.gadget_records()
+    assert [g.kind for g in good] == [4, 4, 5, 5, 6, 6] and good[-1].level == 2
+    G = pa.Gadget
+    make = {"bits": lambda r0: G.bits(r0, CC.DECOY_BITS, 1, level=2), "maybe_equal": lambda r0: G.maybe_equal(r0, level=2),
+            "arith": lambda r0: G.arith(r0, 1, level=2)}
+    why = "a row it claims is not the arithmetic row its kind lays out (selectors, coefficients or wire variables)"
+    try:
+        added = pk.set_gadgets(good)
+        assert added > 0
+        for kind, table in decoys.items():
+            assert len(table) >= 5
+            assert pk.set_gadgets(good + [make[kind](table["good"])]) > added      # an untouched one is fine
+            assert pk.set_gadgets(good) == added
+            for name, r0 in table.items():
+                if name == "good":
+                    continue
+                with pytest.raises(pa.Error) as e:
+                    pk.set_gadgets(good + [make[kind](r0)])
+                assert str(e.value).endswith(f"gadget {len(good)}: {why}"), (kind, name, str(e.value))
+        # after all that the key still has the table it was given: the second gadget of every kind fills from its own offset
+        model = b.model(a)
+        got, reps = pk.fill_gadgets(M.to_limbs(model[0]))
+        assert reps[0].ok and got.tobytes() == M.to_limbs(model[1]).tobytes()
+    finally:
+        pk.free()
+
+
 # ---------------------------------------------------------------------------------- 7. tables of the widget kinds are as before
 # pm_plonk_key_set_gadgets' added_bytes for the table of test_gpu_gadgets._small_circuit (a fixed-base of 8 rounds, a range, a
 # logic and a curve addition), as the commit before the composed kinds reports it on an MI355X

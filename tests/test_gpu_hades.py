@@ -173,6 +173,34 @@ def test_refusals_name_the_gadget_and_keep_the_table(ctx):
         pk.free()
 
 
+@pytest.mark.parametrize("part", range(HC.RULE_PARTS))
+def test_every_set_time_rule_refuses_its_decoy(ctx, part):
+    """hades_circuits.rule_decoys_case: every field the set-time check looks at, wrong in that one place only"""
+    import plonk_prototype_amd as pa
+    b, a, decoys = HC.rule_decoys_case(part)
+    pk = pa.preprocess(b.circuit(), ctx)
+    good = b.gadget_records()
+    assert [g.kind for g in good] == [4, 7, 7] and good[-1].level == 1
+    why = "a row it claims is not the arithmetic row its kind lays out (selectors, coefficients or wire variables)"
+    try:
+        added = pk.set_gadgets(good)
+        assert added > 0
+        assert pk.set_gadgets(good + [pa.Gadget.hades(decoys["good"], *HC.DECOY_SHAPE, level=1)]) == added + RECORD_BYTES + 4 * ROUND_BYTES
+        assert pk.set_gadgets(good) == added
+        for name, r0 in decoys.items():
+            if name == "good":
+                continue
+            with pytest.raises(pa.Error) as e:
+                pk.set_gadgets(good + [pa.Gadget.hades(r0, *HC.DECOY_SHAPE, level=1)])
+            assert str(e.value).endswith(f"gadget {len(good)}: {why}"), (name, str(e.value))
+        # after all that the key still has the table it was given: the second permutation fills from its own offset
+        model = b.model(a)
+        got, reps = pk.fill_gadgets(HM.to_limbs(model[0]))
+        assert reps[0].ok and got.tobytes() == HM.to_limbs(model[1]).tobytes()
+    finally:
+        pk.free()
+
+
 # ---------------------------------------------------------------------------------- 6. what a table holds
 def test_added_bytes(ctx):
     import plonk_prototype_amd as pa

@@ -114,6 +114,25 @@ def test_model_satisfies_the_circuits_of_the_gpu_tests():
     assert bad and all(any(r0 <= i < r0 + 18 for r0 in decoys.values()) for i in bad)
 
 
+def test_rule_decoys_are_each_wrong_in_one_place():
+    """hades_circuits.rule_decoys_case: distinct names over the parts, every decoy differs from the rows the builder lays (the
+    case asserts that), the good table is satisfied by the model and never claims a decoy"""
+    rows, names = HM.hades_rows(*HC.DECOY_SHAPE), []
+    assert rows == 96 and HC._ROUND == (0, 30, 48, 66)
+    for part in range(HC.RULE_PARTS):
+        b, a, decoys = HC.rule_decoys_case(part)
+        assert b.n <= 1024 and "good" in decoys and 2 <= len(decoys) <= HC.RULE_DECOYS_PER_CIRCUIT + 1
+        names += [k for k in decoys if k != "good"]
+        assert [(g[0], g[1], g[3], g[4]) for g in b.gadgets] == [("arith", 0, 1, 0), ("hades", 1, 1, 0), ("hades", 1, 1, 0)]
+        claimed_end = max(g[2] for g in b.gadgets) + 18
+        assert min(decoys.values()) >= claimed_end
+        only, full, reasons = b.model(a)
+        assert not reasons
+        bad = set(b.arithmetic_failures(full))               # everything but the rows nobody fills
+        assert bad and all(any(r0 <= i < r0 + rows for r0 in decoys.values()) for i in bad)
+    assert len(set(names)) == len(names) >= 60
+
+
 @pytest.mark.parametrize("shape", [(5, 2), HC.DUSK])
 def test_model_equals_the_arith_form(shape):
     (b1, a1, m1), (b2, a2, m2) = HC.cross_case(*shape)

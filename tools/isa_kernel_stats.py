@@ -34,7 +34,7 @@ def main():
     names = demangle(sorted(bodies))
     print("# kernel; v_mad_u64_u32; VALU; s_load; vgpr_count; sgpr_count; scratch_bytes")
     for mangled in sorted(bodies, key=lambda k: names[k]):
-        dn = names[mangled].replace("pm::", "")
+        dn = names[mangled].replace("pm::", "").replace("(anonymous namespace)::", "")
         if sub not in dn or mangled not in meta:
             continue
         ops = re.findall(r"^\s+([vs]_\w+)", bodies[mangled], re.M)
