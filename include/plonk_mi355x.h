@@ -776,6 +776,65 @@ int pm_plonk_fill_gadgets_dev(pm_ctx* ctx, const pm_prover_key* key, void* d_var
  * that pm_plonk_key_set_gadgets refuses on its own: count 0 where a count is needed, a count above its kind's cap, HADES with
  * F odd or F > R. */
 uint64_t pm_plonk_gadget_rows(const pm_plonk_gadget* g);
+/* ---- Native Poseidon: the Hades permutation outside a circuit, a sponge, a Merkle tree -------------
+ * The permutation is the one PM_PLONK_PERMUTATION_HADES lays out in rows, width 5: R >= 1 rounds, F of them full (F even,
+ * F <= R; round rho is full when rho < F / 2 or rho >= R - F / 2); a round adds its five round keys, raises every word (full)
+ * or the last word (partial) to the fifth power and multiplies by its matrix: new[i] = sum_j mds[i][j] s[j].
+ * pm_hades_params: the constants of one permutation, an opaque handle that owns a small device table (36 bytes a constant).
+ *   _create: ark = [R][5] round keys, mds = [n_mds][5][5] matrices with n_mds = 1 (one matrix for every round: dusk-hades) or
+ *     n_mds = R (round rho has its own: what the gadget kind allows), canonical Montgomery limbs.  PM_ERR_BAD_ARG, with
+ *     pm_last_error saying which, for R = 0, F odd, F > R, any other n_mds, a constant that is not below the modulus, NULL.
+ *   _from_key: the constants of gadget `gadget_index` (the caller's index) of the key's current gadget table, which must be
+ *     of kind PM_PLONK_PERMUTATION_HADES: a copy of the 30 coefficients a round that pm_plonk_key_set_gadgets gathered, so the
+ *     native permutation computes what the rows of that gadget constrain; n_mds = R.  Waits for the context's stream.
+ *     PM_ERR_BAD_ARG for another kind, a key without a table, an index out of range.  The handle does not refer to the key:
+ *     it stays valid after the table is replaced or the key is freed.
+ *   _info: any of the three outputs may be NULL.  _free waits for the device before it releases the table.
+ * The device calls are asynchronous on `hip_stream` (NULL = the context's stream), take addresses on the context's GPU
+ * (16-byte aligned) and canonical Montgomery elements, use no context scratch, and launch nothing for n = 0 (PM_OK).  `flags`
+ * picks the kernel: PM_HADES_FORM_THREAD runs one permutation per lane (throughput), PM_HADES_FORM_WAVE lets 25 lanes
+ * cooperate on one, two permutations a wave (latency), PM_HADES_FORM_AUTO takes WAVE for small n and THREAD from the measured
+ * crossover on; any other value is PM_ERR_BAD_ARG.  The forms write identical bytes.
+ *   pm_hades_permute_dev: n states of 5 elements (160 bytes each, contiguous), permuted in place.
+ *   pm_poseidon_hash_dev: n messages of msg_len >= 1 elements, message i at element i * msg_stride (msg_stride >= msg_len),
+ *     one element of output a message; d_out must not overlap d_msgs.  This is the project's MODELLED sponge of rate 4, the
+ *     one tests/hades_model.py lays out as a circuit -- the state starts as (capacity, 0, 0, 0, 0); every chunk of up to four
+ *     inputs is added to words 1..4, a chunk shorter than four also adds 1 to the word after its last input, one permutation
+ *     follows each chunk; the hash is word 1 of the final state.  capacity = 0 reproduces the modelled circuit.  It is NOT
+ *     claimed to be dusk-poseidon's sponge: its padding and constants are as unpinned here as the transcript labels are.
+ *     Absorption and permutation run in one kernel; the state stays in registers across chunks.
+ *   pm_poseidon_merkle_dev: a tree of arity 4 over 4^height leaves, 1 <= height <= PM_POSEIDON_MERKLE_MAX_HEIGHT.  A node is
+ *     word 1 of the permutation of (capacity, c0, c1, c2, c3), its four children: the hash above of a message of four.
+ *     d_tree receives levels 1..height one after the other -- level l has 4^(height - l) nodes, the root is last --
+ *     (4^height - 1) / 3 elements that must not overlap the leaves.  One launch a level; AUTO chooses the form per level.
+ *   pm_poseidon_merkle_paths_dev: for each of k leaf indices (uint64, device memory) the four children of every ancestor:
+ *     out[j][l][c], l < height, c < 4, is node ((i >> 2l) & ~3) + c of level l (level 0 = the leaves), i = indices[j] -- the
+ *     path node itself is child (i >> 2l) & 3.  k x height x 4 elements.  An index >= 4^height is refused with
+ *     PM_ERR_BAD_ARG, pm_last_error naming the lowest offending position; finding that out takes one 8-byte readback, so this
+ *     call WAITS for the stream.  Nothing is read for a refused index; the entries of the others are written.
+ * The two host forms need no context and no GPU (csrc/host_field.h): the same permutation and sponge for a one-off hash.
+ * They return PM_ERR_BAD_ARG for what _create refuses, a non-canonical input, NULL and msg_len = 0. */
+#define PM_HADES_FORM_AUTO 0u
+#define PM_HADES_FORM_THREAD 1u
+#define PM_HADES_FORM_WAVE 2u
+#define PM_POSEIDON_MERKLE_MAX_HEIGHT 15u
+typedef struct pm_hades_params pm_hades_params;
+int pm_hades_params_create(pm_ctx* ctx, uint32_t rounds, uint32_t full_rounds, const uint64_t* ark, const uint64_t* mds,
+                           uint32_t n_mds, pm_hades_params** out);
+int pm_hades_params_from_key(pm_ctx* ctx, const pm_prover_key* key, size_t gadget_index, pm_hades_params** out);
+int pm_hades_params_info(const pm_hades_params* params, uint32_t* rounds, uint32_t* full_rounds, uint32_t* n_mds);
+void pm_hades_params_free(pm_ctx* ctx, pm_hades_params* params);
+int pm_hades_permute_dev(pm_ctx* ctx, const pm_hades_params* params, void* d_states, size_t n, uint32_t flags, void* hip_stream);
+int pm_poseidon_hash_dev(pm_ctx* ctx, const pm_hades_params* params, const uint64_t capacity[4], const void* d_msgs,
+                         size_t msg_len, size_t msg_stride, size_t n, void* d_out, uint32_t flags, void* hip_stream);
+int pm_poseidon_merkle_dev(pm_ctx* ctx, const pm_hades_params* params, const uint64_t capacity[4], const void* d_leaves,
+                           uint32_t height, void* d_tree, uint32_t flags, void* hip_stream);
+int pm_poseidon_merkle_paths_dev(pm_ctx* ctx, const void* d_leaves, const void* d_tree, uint32_t height, const void* d_indices,
+                                 size_t k, void* d_out, void* hip_stream);
+int pm_hades_permute_host(uint32_t rounds, uint32_t full_rounds, const uint64_t* ark, const uint64_t* mds, uint32_t n_mds,
+                          uint64_t state[20]);
+int pm_poseidon_hash_host(uint32_t rounds, uint32_t full_rounds, const uint64_t* ark, const uint64_t* mds, uint32_t n_mds,
+                          const uint64_t capacity[4], const uint64_t* msg, size_t msg_len, uint64_t out[4]);
 /* Proof::to_bytes: 11 x 48-byte compressed G1, then the 16 scalars of ProofEvaluations::to_bytes. */
 int pm_plonk_proof_to_bytes(const pm_plonk_proof* proof, uint8_t out[PM_PLONK_PROOF_BYTES]);
 /* ---- The prover with coefficient-range ownership end to end (SURVEY.md section 8e row 3 + 8f N5; configs[4]) ----------

@@ -428,6 +428,7 @@ class ProverKey {
   ProverKey(const ProverKey&) = delete;
   ProverKey& operator=(const ProverKey&) = delete;
   size_t n() const { return n_; }
+  const pm_prover_key* get() const { return key_; }
   size_t num_vars() const { return pm_plonk_key_num_vars(key_); }   // 0: the key was built from sigma_index
   const std::array<G1Affine, PM_PLONK_VK_POINTS>& verifier_key() const { return verifier_key_; }
   // batch x var_stride assignments on the device (var_stride >= num_vars()) -> batch x [a | b | c | d] witnesses, proof-major
@@ -676,6 +677,92 @@ class DistProverKey {
   size_t n_;
   pm_dist_key* key_ = nullptr;
   std::array<G1Affine, PM_PLONK_VK_POINTS> verifier_key_;
+};
+
+// ------------------------------------------------------------------------------------------------
+// Native Poseidon (pm_hades_* / pm_poseidon_*): the constants of one Hades permutation of width 5 on
+// the context's GPU and what runs with them -- permutations, the modelled sponge of rate 4, an arity-4 Merkle tree and the
+// sibling paths of its leaves.  `form` is PM_HADES_FORM_AUTO, _THREAD or _WAVE; the bytes do not depend on it.
+class Hades {
+ public:
+  // ark: rounds x 5 round keys; mds: 25 entries (one matrix for every round) or rounds x 25
+  Hades(Context& ctx, const std::vector<Fr>& ark, const std::vector<Fr>& mds, uint32_t rounds = 67, uint32_t full_rounds = 8)
+      : ctx_(&ctx) {
+    if (ark.size() != 5 * (size_t)rounds || mds.empty() || mds.size() % 25) throw Error(PM_ERR_LENGTH, "ark: rounds x 5, mds: whole 5 x 5 matrices");
+    ctx.check(pm_hades_params_create(ctx.get(), rounds, full_rounds, ark[0].data(), mds[0].data(), (uint32_t)(mds.size() / 25), &p_));
+  }
+  // the constants of HADES gadget `gadget_index` of the key's gadget table; independent of the key afterwards
+  static Hades from_key(Context& ctx, const ProverKey& key, size_t gadget_index) {
+    Hades h(ctx);
+    ctx.check(pm_hades_params_from_key(ctx.get(), key.get(), gadget_index, &h.p_));
+    return h;
+  }
+  ~Hades() { if (p_) pm_hades_params_free(ctx_->get(), p_); }
+  Hades(const Hades&) = delete;
+  Hades& operator=(const Hades&) = delete;
+  Hades(Hades&& o) noexcept : ctx_(o.ctx_), p_(o.p_) { o.p_ = nullptr; }
+  uint32_t rounds() const { return info(0); }
+  uint32_t full_rounds() const { return info(1); }
+  uint32_t n_mds() const { return info(2); }
+  // n states of 5 elements, in place; asynchronous on the context's stream
+  void permute(DevicePolynomial& states, uint32_t form = PM_HADES_FORM_AUTO) const {
+    if (states.len() % 5) throw Error(PM_ERR_LENGTH, "states must hold whole states of 5 elements");
+    ctx_->check(pm_hades_permute_dev(ctx_->get(), p_, states.data(), states.len() / 5, form, nullptr));
+  }
+  std::vector<Fr> permute(const std::vector<Fr>& states, uint32_t form = PM_HADES_FORM_AUTO) const {
+    DevicePolynomial d(*ctx_, states);
+    permute(d, form);
+    return d.to_host();
+  }
+  // messages.len() / msg_len messages of msg_len elements -> one hash each
+  DevicePolynomial hash(const DevicePolynomial& messages, size_t msg_len, const Fr& capacity = Fr{},
+                        uint32_t form = PM_HADES_FORM_AUTO) const {
+    if (msg_len == 0 || messages.len() % msg_len) throw Error(PM_ERR_LENGTH, "messages must hold whole messages of msg_len >= 1 elements");
+    DevicePolynomial out(*ctx_, messages.len() / msg_len);
+    ctx_->check(pm_poseidon_hash_dev(ctx_->get(), p_, capacity.data(), messages.data(), msg_len, msg_len, out.len(), out.data(), form,
+                                     nullptr));
+    return out;
+  }
+  // 4^height leaves -> levels 1..height one after the other, the root last
+  DevicePolynomial merkle(const DevicePolynomial& leaves, uint32_t height, const Fr& capacity = Fr{},
+                          uint32_t form = PM_HADES_FORM_AUTO) const {
+    if (height < 1 || height > PM_POSEIDON_MERKLE_MAX_HEIGHT || leaves.len() != (size_t)1 << (2 * height))
+      throw Error(PM_ERR_LENGTH, "leaves must hold 4^height elements, 1 <= height <= 15");
+    DevicePolynomial tree(*ctx_, (leaves.len() - 1) / 3);
+    ctx_->check(pm_poseidon_merkle_dev(ctx_->get(), p_, capacity.data(), leaves.data(), height, tree.data(), form, nullptr));
+    return tree;
+  }
+  // out[j][l][c]: child c of the level-(l + 1) ancestor of leaf indices[j]; k x height x 4 elements.  Waits for the stream.
+  static std::vector<Fr> merkle_paths(Context& ctx, const DevicePolynomial& leaves, const DevicePolynomial& tree, uint32_t height,
+                                      const std::vector<uint64_t>& indices) {
+    if (indices.empty()) return {};
+    void* d_idx = nullptr;
+    ctx.check(pm_dev_alloc(ctx.get(), indices.size() * 8, &d_idx));
+    DevicePolynomial out(ctx, indices.size() * height * 4);
+    int rc = pm_dev_upload(ctx.get(), d_idx, indices.data(), indices.size() * 8);
+    if (!rc) rc = pm_poseidon_merkle_paths_dev(ctx.get(), leaves.data(), tree.data(), height, d_idx, indices.size(), out.data(), nullptr);
+    pm_dev_free(ctx.get(), d_idx);
+    ctx.check(rc);
+    return out.to_host();
+  }
+  // no context, no GPU
+  static std::array<Fr, 5> permute_host(const std::vector<Fr>& ark, const std::vector<Fr>& mds, std::array<Fr, 5> state,
+                                        uint32_t rounds = 67, uint32_t full_rounds = 8) {
+    if (ark.size() != 5 * (size_t)rounds || mds.empty() || mds.size() % 25 ||
+        pm_hades_permute_host(rounds, full_rounds, ark[0].data(), mds[0].data(), (uint32_t)(mds.size() / 25), state[0].data()))
+      throw Error(PM_ERR_BAD_ARG, "pm_hades_permute_host refused its arguments");
+    return state;
+  }
+
+ private:
+  explicit Hades(Context& ctx) : ctx_(&ctx) {}
+  uint32_t info(int which) const {
+    uint32_t v[3] = {0, 0, 0};
+    ctx_->check(pm_hades_params_info(p_, &v[0], &v[1], &v[2]));
+    return v[which];
+  }
+  Context* ctx_;
+  pm_hades_params* p_ = nullptr;
 };
 
 }  // namespace plonk_mi355x

@@ -188,6 +188,19 @@ SIGNATURES = {
     "pm_plonk_fill_gadgets_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32,
                                             C.POINTER(GadgetReport), C.c_void_p]),
     "pm_plonk_gadget_rows": (C.c_uint64, [C.POINTER(Gadget)]),
+    "pm_hades_params_create": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, u64p, u64p, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "pm_hades_params_from_key": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
+    "pm_hades_params_info": (C.c_int, [C.c_void_p, u32p, u32p, u32p]),
+    "pm_hades_params_free": (None, [C.c_void_p, C.c_void_p]),
+    "pm_hades_permute_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
+    "pm_poseidon_hash_dev": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t,
+                                       C.c_void_p, C.c_uint32, C.c_void_p]),
+    "pm_poseidon_merkle_dev": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                         C.c_void_p]),
+    "pm_poseidon_merkle_paths_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t,
+                                               C.c_void_p, C.c_void_p]),
+    "pm_hades_permute_host": (C.c_int, [C.c_uint32, C.c_uint32, u64p, u64p, C.c_uint32, u64p]),
+    "pm_poseidon_hash_host": (C.c_int, [C.c_uint32, C.c_uint32, u64p, u64p, C.c_uint32, u64p, u64p, C.c_size_t, u64p]),
     "pm_plonk_proof_to_bytes": (C.c_int, [C.POINTER(PlonkProof), C.POINTER(C.c_uint8)]),
     "pm_plonk_batch_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
     "pm_plonk_batch_free": (None, [C.c_void_p, C.c_void_p]),
@@ -275,6 +288,9 @@ PLONK_HADES_WIDTH = 5
 # ... and a variable-base scalar multiplication (PM_PLONK_GADGET_VAR_BASE: count = rounds; 8 and 9 are no kinds)
 PLONK_GADGET_VAR_BASE = 10
 PLONK_CHAIN_KINDS = {10: "variable_base"}
+# pm_hades_permute_dev / pm_poseidon_*_dev: which kernel form runs (the bytes do not depend on it)
+HADES_FORM_AUTO, HADES_FORM_THREAD, HADES_FORM_WAVE = 0, 1, 2
+POSEIDON_MERKLE_MAX_HEIGHT = 15
 
 NTT_INVERSE = 1
 NTT_COSET = 2

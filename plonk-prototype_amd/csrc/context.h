@@ -221,6 +221,10 @@ int gadget_verify(pm_ctx* ctx, const GadgetTables& t, size_t n, const void* d_se
 // the launches when it is given -- the call then waits for the stream
 int gadget_fill(pm_ctx* ctx, const GadgetTables& t, const std::vector<GadgetGroup>& groups, const void* d_wire_vars, size_t n,
                 void* d_vars, size_t var_stride, uint32_t batch, unsigned long long* rep_host, hipStream_t st);
+// Native Poseidon (hades.hip): a pm_hades_params from the rounds gathered for a HADES gadget -- R rounds
+// of GADGET_ROUND_COEFS canonical coefficients at d_rounds, copied: the handle does not refer to the table.  Waits for the
+// context's stream (the gather of set time has then finished).
+int hades_params_from_rounds(pm_ctx* ctx, const void* d_rounds, uint32_t R, uint32_t F, pm_hades_params** out);
 // Per-proof constants of the proof-batched kernels (pm_plonk_prove_batch): a pinned host buffer and its device twin of the
 // same size.  A launcher takes one region of both, fills the host side and sends it with one async copy on its stream;
 // kernels read the device side as a table indexed by the proof.  reset() once per call, after the previous call has

@@ -1,0 +1,520 @@
+// Native Poseidon: the Hades permutation of width 5 outside a circuit, the modelled sponge on top of it,
+// an arity-4 Merkle tree and the sibling paths of its leaves.  gadgets.hip fills the ROWS of one permutation (25 lanes of a wave,
+// every intermediate stored); here only the final state leaves the kernel, in two forms that produce the same bytes:
+//
+//   THREAD  one permutation per lane, the five words in registers in the device form (x 2^261).  Round keys and matrices are
+//           wave-uniform: they sit in one device table in the constant address space, every index is uniform, so they arrive by
+//           scalar loads and enter the multiply-adds as scalar operands -- no vector register and no LDS holds a constant.  A row
+//           of the matrix is ONE reduction: the five products of a row go into the same column accumulators (45 limb products a
+//           column set, 9 * 5 + 8 = 53 < 64 in units of 2^58: within the bound of fe_mont_cols for normalised operands), and the
+//           next round's key is added at the columns above the radix, (T + key 2^261) / 2^261 = T / 2^261 + key.  A round is
+//           5 x (405 + 72) limb products for the matrix and 117 + 117 + 153 for each s-box instead of 28 (or 40) x 153.
+//           Values: state words are normalised limbs below 2.1 r throughout (5 * 2.1 r * r / 2^261 + r + key).
+//   WAVE    lanes cooperate: lane 5 i + j of a half-wave holds word j and matrix entry (i, j) as in gadget_hades_kernel; two
+//           permutations a wave (lanes 0..24 and 32..56).  Four dependent products a round instead of 28; lane (i, j) takes its
+//           next word straight from the five products of row j (45 cross-lane reads a round, no second exchange).
+//
+// Both keep the sponge's state in registers across chunks; a tree level is the sponge on messages of four (no padding).  What is
+// stored goes through fe_store: canonical whatever representative the form arrived at.
+#include <hip/hip_runtime.h>
+
+#include <string>
+#include <vector>
+
+#include "context.h"
+#include "poly_common.hip.h"
+
+struct pm_hades_params {
+  int device = 0;
+  uint32_t rounds = 0, full = 0, n_mds = 0;
+  void* d_tab = nullptr;   // u32: mds [n_mds][25][9], then ark [rounds + 1][5][9] (the last row zero), device form
+};
+
+namespace pm {
+namespace {
+
+using host::HFr;
+
+// ------------------------------------------------------------------ the definition on the host (csrc/host_field.h)
+bool hfr_canonical(const uint64_t* v) { return !host::geq<4>(v, host::FR().m); }
+HFr hfr_load(const uint64_t* v) {
+  HFr r;
+  memcpy(r.l, v, 32);
+  return r;
+}
+bool round_is_full(uint32_t rho, uint32_t R, uint32_t F) { return rho < F / 2 || rho >= R - F / 2; }
+
+void host_permute(uint32_t R, uint32_t F, const uint64_t* ark, const uint64_t* mds, uint32_t n_mds, HFr (&s)[5]) {
+  const host::Field<4>& Fq = host::FR();
+  for (uint32_t rho = 0; rho < R; ++rho) {
+    for (int j = 0; j < 5; ++j) s[j] = host::add(s[j], hfr_load(ark + 4 * (5 * (size_t)rho + j)), Fq);
+    for (int j = round_is_full(rho, R, F) ? 0 : 4; j < 5; ++j) {
+      const HFr x2 = host::mul(s[j], s[j], Fq), x4 = host::mul(x2, x2, Fq);
+      s[j] = host::mul(x4, s[j], Fq);
+    }
+    const uint64_t* m = mds + 100 * (size_t)(n_mds == 1 ? 0 : rho);
+    HFr o[5];
+    for (int i = 0; i < 5; ++i) {
+      o[i] = host::zero<4>();
+      for (int j = 0; j < 5; ++j) o[i] = host::add(o[i], host::mul(hfr_load(m + 4 * (5 * i + j)), s[j], Fq), Fq);
+    }
+    for (int i = 0; i < 5; ++i) s[i] = o[i];
+  }
+}
+
+// R, F, n_mds and every constant; empty = fine
+std::string params_fault(uint32_t R, uint32_t F, const uint64_t* ark, const uint64_t* mds, uint32_t n_mds) {
+  if (!ark || !mds) return "null constants";
+  if (R == 0) return "rounds must be at least 1";
+  if (F & 1u) return "full_rounds must be even";
+  if (F > R) return "full_rounds exceeds rounds";
+  if (n_mds != 1 && n_mds != R) return "n_mds must be 1 or rounds";
+  for (size_t k = 0; k < 5 * (size_t)R; ++k)
+    if (!hfr_canonical(ark + 4 * k)) return "round key " + std::to_string(k) + " is not canonical";
+  for (size_t k = 0; k < 25 * (size_t)n_mds; ++k)
+    if (!hfr_canonical(mds + 4 * k)) return "matrix entry " + std::to_string(k) + " is not canonical";
+  return "";
+}
+
+// ------------------------------------------------------------------ device side
+struct HadesTab {
+  const PM_KCONST u32* mds;   // [n_mds][25][9]
+  const PM_KCONST u32* ark;   // [rounds + 1][5][9], the last row zero
+  u32 rounds, half_full;      // R, F / 2
+  u32 mds_stride;             // words between the matrices of two rounds: 225 or 0
+};
+struct HadesIo {
+  u32x4* states;              // permute: n x 5 elements, in place
+  const u32x4* msgs;          // hash: message i at element i * msg_stride
+  u32x4* out;                 // hash: one element a message
+  size_t n, msg_stride;
+  u32 msg_len;
+  u32 capacity[9];            // device form
+};
+
+PM_DEV Fr h_to_dev(const Fr& abi) { return fe_reduce_weak<FrP>(fr_shl5(abi)); }
+PM_DEV Fr h_to_abi(const Fr& dev) { return fe_mul<FrP>(dev, fe_pow2<FrP, 256>()); }
+PM_DEV Fr h_const(const PM_KCONST u32* p) {
+  Fr r;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) r.l[i] = p[i];
+  return r;
+}
+PM_DEV Fr h_sbox(const Fr& x) {
+  const Fr x2 = fe_sqr<FrP>(x), x4 = fe_sqr<FrP>(x2);
+  return fe_mul<FrP>(x4, x);
+}
+// (sum_j m[j] v[j]) / 2^261 + key: one reduction for the row (the bound is in the file comment); v normalised, m and key canonical
+PM_DEV Fr h_row(const Fr (&v)[5], const PM_KCONST u32* m, const PM_KCONST u32* key) {
+  Fr t;
+  Fr* const out[1] = {&t};
+  fe_mont_cols<FrP, 1>(
+      [&](int k, u64* acc, u32& tok) {
+#pragma unroll
+        for (int j = 0; j < 5; ++j)
+#pragma unroll
+          for (int i = 0; i < 9; ++i) {
+            const int l = k - i;
+            if (l < 0 || l >= 9) continue;
+            fe_mac(acc[0], v[j].l[i], m[9 * j + l], tok);
+          }
+        if (k >= 9) acc[0] += key[k - 9];
+      },
+      out);
+  t.l[8] += key[8];   // the top limb keeps the rest
+  return t;
+}
+// the rounds of one permutation on a lane's own state; s already holds the keys of round 0
+PM_DEV void h_rounds_thread(Fr (&s)[5], const HadesTab& tab) {
+#pragma unroll 1
+  for (u32 rho = 0; rho < tab.rounds; ++rho) {
+    if (rho < tab.half_full || rho >= tab.rounds - tab.half_full) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s[j] = h_sbox(s[j]);
+    }
+    s[4] = h_sbox(s[4]);
+    const PM_KCONST u32* const m = tab.mds + (size_t)tab.mds_stride * rho;
+    const PM_KCONST u32* const key = tab.ark + 45 * (size_t)(rho + 1);
+    Fr o[5];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) o[i] = h_row(s, m + 45 * i, key + 9 * i);
+#pragma unroll
+    for (int i = 0; i < 5; ++i) s[i] = o[i];
+  }
+}
+// s += add + the keys of round 0 (limbs below 3 * 2^29, value below 4.2 r)
+PM_DEV Fr h_absorb(const Fr& s, const Fr& add, const PM_KCONST u32* key0) {
+  return fe_reduce_weak<FrP>(fe_add<FrP>(fe_add<FrP>(s, add), h_const(key0)));
+}
+// word t (0..3) of the chunk that starts at element `at` of a message with `left` elements to go: the input, the padding 1
+// after a short chunk's last input, or nothing
+PM_DEV Fr h_chunk_word(const u32x4* msg, size_t at, u32 left, u32 t) {
+  if (t < left) return h_to_dev(ld_canon(msg, at + t));
+  return t == left ? fe_one<FrP>() : fe_zero<FrP>();
+}
+
+template <bool HASH>
+__global__ void __launch_bounds__(64) hades_thread_kernel(const HadesTab tab, const HadesIo io) {
+  const size_t idx = (size_t)blockIdx.x * 64 + threadIdx.x;
+  if (idx >= io.n) return;
+  Fr s[5];
+  if (!HASH) {
+    u32x4* const p = io.states + 10 * idx;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) s[j] = h_absorb(h_to_dev(ld_canon(p, j)), fe_zero<FrP>(), tab.ark + 9 * j);
+    h_rounds_thread(s, tab);
+#pragma unroll
+    for (int j = 0; j < 5; ++j) st_canon(p, j, h_to_abi(s[j]));
+  } else {
+    const u32x4* const msg = io.msgs + 2 * io.msg_stride * idx;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) s[0].l[i] = io.capacity[i];
+#pragma unroll
+    for (int j = 1; j < 5; ++j) s[j] = fe_zero<FrP>();
+#pragma unroll 1
+    for (u32 at = 0; at < io.msg_len; at += 4) {
+      s[0] = h_absorb(s[0], fe_zero<FrP>(), tab.ark);
+#pragma unroll
+      for (int j = 1; j < 5; ++j) s[j] = h_absorb(s[j], h_chunk_word(msg, at, io.msg_len - at, j - 1), tab.ark + 9 * j);
+      h_rounds_thread(s, tab);
+    }
+    st_canon(io.out, idx, h_to_abi(s[1]));
+  }
+}
+
+PM_DEV Fr h_shfl(const Fr& v, u32 src) {
+  Fr r;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) r.l[i] = __shfl(v.l[i], (int)src);
+  return r;
+}
+PM_DEV Fr h_sel(bool c, const Fr& a, const Fr& b) {
+  Fr r;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) r.l[i] = c ? a.l[i] : b.l[i];
+  return r;
+}
+PM_DEV Fr h_lane_const(const u32* p) {
+  Fr r;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) r.l[i] = p[i];
+  return r;
+}
+// the rounds with lane (i, j) of a half-wave holding word j (keys of round 0 added) and entry (i, j); base = the half's lane 0.
+// Every lane of the wave runs every round: the loop and the kind of a round depend on the parameters only.
+PM_DEV Fr h_rounds_wave(Fr s, const u32* mds, const u32* ark, const HadesTab& tab, u32 base, u32 i, u32 j) {
+  Fr m = h_lane_const(mds + 9 * (5 * i + j)), key = h_lane_const(ark + 45 + 9 * j);
+#pragma unroll 1
+  for (u32 rho = 0; rho < tab.rounds; ++rho) {
+    const u32 nx = rho + 1 < tab.rounds ? rho + 1 : rho;   // the last round loads its own again
+    const Fr m_n = h_lane_const(mds + (size_t)tab.mds_stride * nx + 9 * (5 * i + j));
+    const Fr key_n = h_lane_const(ark + 45 * (size_t)(nx + 1) + 9 * j);
+    const bool full = rho < tab.half_full || rho >= tab.rounds - tab.half_full;
+    const Fr x5 = h_sbox(s);
+    const Fr p = fe_mul<FrP>(m, h_sel(full || j == 4, x5, s));
+    Fr sum = fe_add<FrP>(h_shfl(p, base + 5 * j), key);    // row j: the word this lane holds next
+#pragma unroll
+    for (u32 e = 1; e < 5; ++e) sum = fe_add<FrP>(sum, h_shfl(p, base + 5 * j + e));
+    s = fe_reduce_weak<FrP>(sum);                          // limbs below 6 * 2^29, value below 6.1 r
+    m = m_n, key = key_n;
+  }
+  return s;
+}
+
+template <bool HASH>
+__global__ void __launch_bounds__(64) hades_wave_kernel(const HadesTab tab, const HadesIo io) {
+  const u32 lane = threadIdx.x, base = lane & 32u, l = (lane & 31u) < 25u ? (lane & 31u) : 24u;   // lanes 25..31 shadow lane 24
+  const bool owner = (lane & 31u) < 25u;
+  const u32 i = l / 5, j = l - 5 * i;
+  size_t idx = 2 * (size_t)blockIdx.x + (base >> 5);
+  const bool live = idx < io.n;                            // an odd n: the last wave's second half repeats the first
+  if (!live) idx = io.n - 1;
+  const u32* const mds = (const u32*)tab.mds;
+  const u32* const ark = (const u32*)tab.ark;
+  const Fr key0 = h_lane_const(ark + 9 * j);
+  if (!HASH) {
+    u32x4* const p = io.states + 10 * idx;
+    Fr s = fe_reduce_weak<FrP>(fe_add<FrP>(h_to_dev(ld_canon(p, j)), key0));
+    s = h_rounds_wave(s, mds, ark, tab, base, i, j);
+    if (live && owner && i == 0) st_canon(p, j, h_to_abi(s));
+  } else {
+    const u32x4* const msg = io.msgs + 2 * io.msg_stride * idx;
+    Fr s = fe_zero<FrP>();
+    if (j == 0) {
+#pragma unroll
+      for (int k = 0; k < 9; ++k) s.l[k] = io.capacity[k];
+    }
+#pragma unroll 1
+    for (u32 at = 0; at < io.msg_len; at += 4) {
+      const Fr add = j == 0 ? fe_zero<FrP>() : h_chunk_word(msg, at, io.msg_len - at, j - 1);
+      s = fe_reduce_weak<FrP>(fe_add<FrP>(fe_add<FrP>(s, add), key0));
+      s = h_rounds_wave(s, mds, ark, tab, base, i, j);
+    }
+    if (live && owner && l == 1) st_canon(io.out, idx, h_to_abi(s));
+  }
+}
+
+// out[j][l][c] = child c of the level-(l + 1) ancestor of leaf idx[j]: node ((i >> 2l) & ~3) + c of level l (level 0 = the leaves)
+__global__ void __launch_bounds__(256) merkle_paths_kernel(const u32x4* leaves, const u32x4* tree, u32 h, const u64* idx, size_t k,
+                                                           u32x4* out) {
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;   // one thread a node: (j, l, c)
+  if (t >= k * h * 4) return;
+  const u32 c = (u32)(t & 3u), l = (u32)((t >> 2) % h);
+  const size_t j = (t >> 2) / h;
+  const u64 leaf = idx[j];
+  if (leaf >> (2 * h)) return;                               // refused by the host after the call; nothing is read for it
+  const u64 node = ((leaf >> (2 * l)) & ~3ull) + c;
+  const u32x4* src = leaves;
+  if (l) {
+    u64 off = 0;                                             // levels 1..l-1 come before level l in the tree
+    for (u32 q = 1; q < l; ++q) off += 1ull << (2 * (h - q));
+    src = tree + 2 * off;
+  }
+  out[2 * t] = src[2 * node];
+  out[2 * t + 1] = src[2 * node + 1];
+}
+__global__ void __launch_bounds__(256) merkle_index_check_kernel(const u64* idx, size_t k, u32 h, unsigned long long* bad) {
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (t < k && (idx[t] >> (2 * h))) atomicMin(bad, (unsigned long long)t);
+}
+
+// ------------------------------------------------------------------ launches
+// AUTO: the WAVE form below this many permutations, the THREAD form from it on.  Measured at (67, 8), DESIGN.md section 7.2j:
+// THREAD takes 0.48 ms for anything up to one wave a SIMD, WAVE grows by 0.054 ms a 1024 permutations and meets it at 8192.
+constexpr size_t HADES_AUTO_CROSSOVER = 8192;
+
+HadesTab tab_of(const pm_hades_params* p) {
+  const u32* t = (const u32*)p->d_tab;
+  return HadesTab{(const PM_KCONST u32*)t, (const PM_KCONST u32*)(t + 225 * (size_t)p->n_mds), p->rounds, p->full / 2,
+                  p->n_mds == 1 ? 0u : 225u};
+}
+bool use_wave(size_t n, uint32_t flags) { return flags == PM_HADES_FORM_WAVE || (flags == PM_HADES_FORM_AUTO && n < HADES_AUTO_CROSSOVER); }
+
+template <bool HASH>
+hipError_t launch(const pm_hades_params* p, const HadesIo& io, uint32_t flags, hipStream_t st) {
+  const HadesTab tab = tab_of(p);
+  if (use_wave(io.n, flags))
+    hipLaunchKernelGGL((hades_wave_kernel<HASH>), dim3((unsigned)((io.n + 1) / 2)), dim3(64), 0, st, tab, io);
+  else
+    hipLaunchKernelGGL((hades_thread_kernel<HASH>), dim3((unsigned)((io.n + 63) / 64)), dim3(64), 0, st, tab, io);
+  return hipGetLastError();
+}
+
+int common_fault(pm_ctx* ctx, const pm_hades_params* p, uint32_t flags) {
+  if (!p) return set_err(ctx, PM_ERR_BAD_ARG, "null params");
+  if (p->device != ctx->device) return set_err(ctx, PM_ERR_BAD_ARG, "the params belong to another device");
+  if (flags > PM_HADES_FORM_WAVE) return set_err(ctx, PM_ERR_BAD_ARG, "flags must be PM_HADES_FORM_AUTO, _THREAD or _WAVE");
+  return PM_OK;
+}
+int capacity_to_dev(pm_ctx* ctx, const uint64_t* capacity, u32 (&out)[9]) {
+  if (!capacity) return set_err(ctx, PM_ERR_BAD_ARG, "null capacity");
+  if (!hfr_canonical(capacity)) return set_err(ctx, PM_ERR_BAD_ARG, "capacity is not canonical");
+  to_limbs29(out, hfr_load(capacity));
+  return PM_OK;
+}
+bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return x < y + b_bytes && y < x + a_bytes;
+}
+
+// ark [R][5], mds [n_mds][5][5] (validated) -> the handle with its device table
+int params_build(pm_ctx* ctx, uint32_t R, uint32_t F, const uint64_t* ark, const uint64_t* mds, uint32_t n_mds, pm_hades_params** out) {
+  std::vector<u32> tab(225 * (size_t)n_mds + 45 * ((size_t)R + 1), 0u);
+  for (size_t k = 0; k < 25 * (size_t)n_mds; ++k) to_limbs29(&tab[9 * k], hfr_load(mds + 4 * k));
+  u32* const a = &tab[225 * (size_t)n_mds];
+  for (size_t k = 0; k < 5 * (size_t)R; ++k) to_limbs29(a + 9 * k, hfr_load(ark + 4 * k));
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  void* d = nullptr;
+  PM_HIP(ctx, hipMalloc(&d, tab.size() * 4));
+  const hipError_t e = hipMemcpy(d, tab.data(), tab.size() * 4, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(d);
+    return set_err(ctx, PM_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
+  }
+  pm_hades_params* p = new pm_hades_params();
+  p->device = ctx->device, p->rounds = R, p->full = F, p->n_mds = n_mds, p->d_tab = d;
+  *out = p;
+  return PM_OK;
+}
+
+}  // namespace
+
+// context.h: the rounds gathered for a HADES gadget (GadgetTables::hcoef at its offset: R x 30 canonical coefficients, 25 matrix
+// entries then 5 round keys) -> a handle with a matrix a round.  Waits for the context's stream.
+int hades_params_from_rounds(pm_ctx* ctx, const void* d_rounds, uint32_t R, uint32_t F, pm_hades_params** out) {
+  std::vector<uint64_t> raw(120 * (size_t)R), ark(20 * (size_t)R), mds(100 * (size_t)R);
+  {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    PM_HIP(ctx, hipSetDevice(ctx->device));
+    PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    PM_HIP(ctx, hipMemcpy(raw.data(), d_rounds, raw.size() * 8, hipMemcpyDeviceToHost));
+  }
+  for (size_t rho = 0; rho < R; ++rho) {
+    memcpy(&mds[100 * rho], &raw[120 * rho], 800);
+    memcpy(&ark[20 * rho], &raw[120 * rho + 100], 160);
+  }
+  const std::string why = params_fault(R, F, ark.data(), mds.data(), R);
+  if (!why.empty()) return set_err(ctx, PM_ERR_BAD_ARG, "pm_hades_params_from_key: " + why);
+  return params_build(ctx, R, F, ark.data(), mds.data(), R, out);
+}
+
+}  // namespace pm
+
+using namespace pm;
+
+extern "C" int pm_hades_params_create(pm_ctx* ctx, uint32_t rounds, uint32_t full_rounds, const uint64_t* ark, const uint64_t* mds,
+                                      uint32_t n_mds, pm_hades_params** out) {
+  if (!ctx || !out) return PM_ERR_BAD_ARG;
+  const std::string why = params_fault(rounds, full_rounds, ark, mds, n_mds);
+  if (!why.empty()) return set_err(ctx, PM_ERR_BAD_ARG, "pm_hades_params_create: " + why);
+  return params_build(ctx, rounds, full_rounds, ark, mds, n_mds, out);
+}
+
+extern "C" int pm_hades_params_info(const pm_hades_params* params, uint32_t* rounds, uint32_t* full_rounds, uint32_t* n_mds) {
+  if (!params) return PM_ERR_BAD_ARG;
+  if (rounds) *rounds = params->rounds;
+  if (full_rounds) *full_rounds = params->full;
+  if (n_mds) *n_mds = params->n_mds;
+  return PM_OK;
+}
+
+extern "C" void pm_hades_params_free(pm_ctx* ctx, pm_hades_params* params) {
+  if (!params) return;
+  if (ctx) {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+    if (params->d_tab) (void)hipFree(params->d_tab);   // hipFree waits for the device: launches on caller streams included
+  }
+  delete params;
+}
+
+extern "C" int pm_hades_permute_dev(pm_ctx* ctx, const pm_hades_params* params, void* d_states, size_t n, uint32_t flags,
+                                    void* hip_stream) {
+  if (!ctx) return PM_ERR_BAD_ARG;
+  if (int rc = common_fault(ctx, params, flags)) return rc;
+  if (n == 0) return PM_OK;
+  if (!d_states || ((uintptr_t)d_states & 15u)) return set_err(ctx, PM_ERR_BAD_ARG, "null or unaligned device pointer");
+  if (n > 0x7fffffffu) return set_err(ctx, PM_ERR_LENGTH, "n > 2^31");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  HadesIo io{};
+  io.states = (u32x4*)d_states, io.n = n;
+  ProfScope prof(ctx, st, "hades_permute");
+  PM_HIP(ctx, launch<false>(params, io, flags, st));
+  return PM_OK;
+}
+
+extern "C" int pm_poseidon_hash_dev(pm_ctx* ctx, const pm_hades_params* params, const uint64_t capacity[4], const void* d_msgs,
+                                    size_t msg_len, size_t msg_stride, size_t n, void* d_out, uint32_t flags, void* hip_stream) {
+  if (!ctx) return PM_ERR_BAD_ARG;
+  if (int rc = common_fault(ctx, params, flags)) return rc;
+  HadesIo io{};
+  if (int rc = capacity_to_dev(ctx, capacity, io.capacity)) return rc;
+  if (msg_len == 0 || msg_len > 0xffffffffull) return set_err(ctx, PM_ERR_BAD_ARG, "msg_len must be in 1 .. 2^32 - 1");
+  if (msg_stride < msg_len) return set_err(ctx, PM_ERR_BAD_ARG, "msg_stride is below msg_len");
+  if (n == 0) return PM_OK;
+  if (!d_msgs || !d_out || (((uintptr_t)d_msgs | (uintptr_t)d_out) & 15u))
+    return set_err(ctx, PM_ERR_BAD_ARG, "null or unaligned device pointer");
+  if (n > 0x7fffffffu) return set_err(ctx, PM_ERR_LENGTH, "n > 2^31");
+  if (overlap(d_msgs, ((n - 1) * msg_stride + msg_len) * 32, d_out, n * 32)) return set_err(ctx, PM_ERR_BAD_ARG, "d_out overlaps d_msgs");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  io.msgs = (const u32x4*)d_msgs, io.out = (u32x4*)d_out, io.n = n, io.msg_stride = msg_stride, io.msg_len = (u32)msg_len;
+  ProfScope prof(ctx, st, "poseidon_hash");
+  PM_HIP(ctx, launch<true>(params, io, flags, st));
+  return PM_OK;
+}
+
+extern "C" int pm_poseidon_merkle_dev(pm_ctx* ctx, const pm_hades_params* params, const uint64_t capacity[4], const void* d_leaves,
+                                      uint32_t height, void* d_tree, uint32_t flags, void* hip_stream) {
+  if (!ctx) return PM_ERR_BAD_ARG;
+  if (int rc = common_fault(ctx, params, flags)) return rc;
+  HadesIo io{};
+  if (int rc = capacity_to_dev(ctx, capacity, io.capacity)) return rc;
+  if (height < 1 || height > PM_POSEIDON_MERKLE_MAX_HEIGHT) return set_err(ctx, PM_ERR_BAD_ARG, "height must be in 1 .. 15");
+  if (!d_leaves || !d_tree || (((uintptr_t)d_leaves | (uintptr_t)d_tree) & 15u))
+    return set_err(ctx, PM_ERR_BAD_ARG, "null or unaligned device pointer");
+  const size_t leaves = (size_t)1 << (2 * height);
+  if (overlap(d_leaves, leaves * 32, d_tree, (leaves - 1) / 3 * 32)) return set_err(ctx, PM_ERR_BAD_ARG, "d_tree overlaps d_leaves");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  ProfScope prof(ctx, st, "poseidon_merkle");
+  const u32x4* below = (const u32x4*)d_leaves;
+  u32x4* level = (u32x4*)d_tree;
+  io.msg_len = 4, io.msg_stride = 4;
+  for (uint32_t l = 1; l <= height; ++l) {                   // a launch a level: level l reads level l - 1
+    io.n = (size_t)1 << (2 * (height - l));
+    io.msgs = below, io.out = level;
+    PM_HIP(ctx, launch<true>(params, io, flags, st));
+    below = level, level += 2 * io.n;
+  }
+  return PM_OK;
+}
+
+extern "C" int pm_poseidon_merkle_paths_dev(pm_ctx* ctx, const void* d_leaves, const void* d_tree, uint32_t height,
+                                            const void* d_indices, size_t k, void* d_out, void* hip_stream) {
+  if (!ctx) return PM_ERR_BAD_ARG;
+  if (height < 1 || height > PM_POSEIDON_MERKLE_MAX_HEIGHT) return set_err(ctx, PM_ERR_BAD_ARG, "height must be in 1 .. 15");
+  if (k == 0) return PM_OK;
+  if (!d_leaves || !d_tree || !d_indices || !d_out || (((uintptr_t)d_leaves | (uintptr_t)d_tree | (uintptr_t)d_out) & 15u) ||
+      ((uintptr_t)d_indices & 7u))
+    return set_err(ctx, PM_ERR_BAD_ARG, "null or unaligned device pointer");
+  if (k > 0x7fffffffu / (4 * height)) return set_err(ctx, PM_ERR_LENGTH, "too many paths for one call");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  unsigned long long* d_bad = nullptr;
+  unsigned long long bad = ~0ull;
+  PM_HIP(ctx, hipMalloc((void**)&d_bad, 8));
+  hipError_t e = hipMemcpyAsync(d_bad, &bad, 8, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(merkle_index_check_kernel, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, st, (const u64*)d_indices, k,
+                       height, d_bad);
+    const size_t nodes = k * height * 4;
+    hipLaunchKernelGGL(merkle_paths_kernel, dim3((unsigned)((nodes + 255) / 256)), dim3(256), 0, st, (const u32x4*)d_leaves,
+                       (const u32x4*)d_tree, height, (const u64*)d_indices, k, (u32x4*)d_out);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  (void)hipFree(d_bad);
+  if (e != hipSuccess) return set_err(ctx, PM_ERR_HIP, std::string("pm_poseidon_merkle_paths_dev: ") + hipGetErrorString(e));
+  if (bad != ~0ull) return set_err(ctx, PM_ERR_BAD_ARG, "index " + std::to_string(bad) + " is not below 4^height");
+  return PM_OK;
+}
+
+extern "C" int pm_hades_permute_host(uint32_t rounds, uint32_t full_rounds, const uint64_t* ark, const uint64_t* mds, uint32_t n_mds,
+                                     uint64_t state[20]) {
+  if (!state || !params_fault(rounds, full_rounds, ark, mds, n_mds).empty()) return PM_ERR_BAD_ARG;
+  HFr s[5];
+  for (int j = 0; j < 5; ++j) {
+    if (!hfr_canonical(state + 4 * j)) return PM_ERR_BAD_ARG;
+    s[j] = hfr_load(state + 4 * j);
+  }
+  host_permute(rounds, full_rounds, ark, mds, n_mds, s);
+  memcpy(state, s, 160);
+  return PM_OK;
+}
+
+extern "C" int pm_poseidon_hash_host(uint32_t rounds, uint32_t full_rounds, const uint64_t* ark, const uint64_t* mds, uint32_t n_mds,
+                                     const uint64_t capacity[4], const uint64_t* msg, size_t msg_len, uint64_t out[4]) {
+  if (!capacity || !msg || !out || msg_len == 0 || !params_fault(rounds, full_rounds, ark, mds, n_mds).empty()) return PM_ERR_BAD_ARG;
+  if (!hfr_canonical(capacity)) return PM_ERR_BAD_ARG;
+  for (size_t k = 0; k < msg_len; ++k)
+    if (!hfr_canonical(msg + 4 * k)) return PM_ERR_BAD_ARG;
+  const host::Field<4>& Fq = host::FR();
+  HFr s[5] = {hfr_load(capacity), host::zero<4>(), host::zero<4>(), host::zero<4>(), host::zero<4>()};
+  for (size_t at = 0; at < msg_len; at += 4) {
+    const size_t left = msg_len - at < 4 ? msg_len - at : 4;
+    for (size_t t = 0; t < left; ++t) s[1 + t] = host::add(s[1 + t], hfr_load(msg + 4 * (at + t)), Fq);
+    if (left < 4) s[1 + left] = host::add(s[1 + left], host::one<4>(Fq), Fq);
+    host_permute(rounds, full_rounds, ark, mds, n_mds, s);
+  }
+  memcpy(out, s[1].l, 32);
+  return PM_OK;
+}

@@ -7,6 +7,7 @@ struct GadgetState {
   size_t bytes = 0;                        // device bytes held
   pm::GadgetTables dev;
   std::vector<pm::GadgetGroup> groups;     // one launch each, levels rising
+  std::vector<pm::GadgetRec> recs;         // the host's copy of dev.recs (launch order): pm_hades_params_from_key
 };
 
 // the rows a gadget claims (the widget kinds: the trailing row included); 0: a kind, count or param that is refused whatever the
@@ -133,6 +134,7 @@ extern "C" int pm_plonk_key_set_gadgets(pm_ctx* ctx, pm_prover_key* pk, const pm
     return rc;
   }
   gs->groups = std::move(groups);
+  gs->recs = std::move(recs);
   PK_TRY(pm_sync(ctx));                    // a fill on the table being replaced has finished
   gadget_state_free(ctx, pk->gadgets);
   pk->gadgets = gs;
@@ -160,4 +162,18 @@ extern "C" int pm_plonk_fill_gadgets_dev(pm_ctx* ctx, const pm_prover_key* pk, v
       r.first_reason = r.failed ? (uint32_t)(rep[batch + b] & 3) : 0;
     }
   return PM_OK;
+}
+
+// Native Poseidon with the constants of a HADES gadget (hades.hip): the rounds set time gathered for it
+extern "C" int pm_hades_params_from_key(pm_ctx* ctx, const pm_prover_key* pk, size_t gadget_index, pm_hades_params** out) {
+  if (!ctx || !pk || !out) return PM_ERR_BAD_ARG;
+  const GadgetState* gs = pk->gadgets;
+  if (!gs) return pm::set_err(ctx, PM_ERR_BAD_ARG, "the key has no gadget table (pm_plonk_key_set_gadgets first)");
+  for (const pm::GadgetRec& rec : gs->recs) {
+    if (rec.index != gadget_index) continue;
+    if (rec.kind != PM_PLONK_PERMUTATION_HADES)
+      return pm::set_err(ctx, PM_ERR_BAD_ARG, "gadget " + std::to_string(gadget_index) + " is not of kind PM_PLONK_PERMUTATION_HADES");
+    return pm::hades_params_from_rounds(ctx, at(gs->dev.hcoef, (size_t)rec.tab * pm::GADGET_ROUND_COEFS), rec.count, rec.param, out);
+  }
+  return pm::set_err(ctx, PM_ERR_BAD_ARG, "gadget_index is not below the table's count");
 }
