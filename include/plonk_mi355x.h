@@ -835,6 +835,51 @@ int pm_hades_permute_host(uint32_t rounds, uint32_t full_rounds, const uint64_t*
                           uint64_t state[20]);
 int pm_poseidon_hash_host(uint32_t rounds, uint32_t full_rounds, const uint64_t* ark, const uint64_t* mds, uint32_t n_mds,
                           const uint64_t capacity[4], const uint64_t* msg, size_t msg_len, uint64_t out[4]);
+/* ---- Native JubJub: scalar multiplications on the embedded curve outside a circuit ------------------
+ * The curve is the one the FIXED_BASE, CURVE_ADD and VAR_BASE gadgets constrain: -x^2 + y^2 = 1 + d x^2 y^2 over Fr with
+ * d = -(10240 / 10241), under the law (x1, y1) + (x2, y2) = ((x1 y2 + y1 x2) / (1 + k), (y1 y2 + x1 x2) / (1 - k)),
+ * k = d x1 x2 y1 y2.  A point is affine (x, y): two canonical Montgomery elements, 64 bytes; the identity is (0, 1).  The
+ * multiplier of a point is the INTEGER 0 <= s < r its scalar stands for (scalar_form: PM_SCALAR_MONTGOMERY or
+ * PM_SCALAR_CANONICAL, anything else is PM_ERR_BAD_ARG), never reduced modulo the order of the subgroup: this matters for
+ * points outside the prime-order subgroup.
+ * pm_jubjub_base: one point B with a device table of j 16^w B (w < 64, j = 1..8; 56 KiB), an opaque handle.
+ *   _create: PM_ERR_BAD_ARG for a point off the curve, a coordinate >= r, NULL.  The table is built once, on the host.
+ *   _from_key: the base of gadget `gadget_index` (the caller's index) of the key's current gadget table, which must be of kind
+ *     PM_PLONK_GADGET_FIXED_BASE and whose table points t[0..R) as gathered by pm_plonk_key_set_gadgets (most significant round
+ *     first: the order of dusk's gadget) must be curve points with t[k] = 2 t[k + 1]; the base is t[R - 1], the very point the
+ *     gadget multiplies.  Anything else is PM_ERR_BAD_ARG.  Waits for the context's stream.  The handle does not refer to
+ *     the key afterwards.
+ *   _point: the point back (pure host; PM_ERR_BAD_ARG for NULL).  _free waits for the device before it releases the table.
+ * The device calls take addresses on the context's GPU (16-byte aligned), NULL among them is PM_ERR_BAD_ARG, and launch
+ * nothing for n = 0 (PM_OK); they run on `hip_stream` (NULL = the context's stream).
+ *   pm_jubjub_fixed_mul_dev: out[i] = s_i B.  One kernel, no allocation; asynchronous.
+ *   pm_jubjub_commit_dev: out[i] = v_i G + b_i H (a Pedersen commitment; g and h may be the same handle) in one pass over
+ *     both scalars.  One kernel, no allocation; asynchronous.
+ *   pm_jubjub_mul_dev: out[i] = s_i P_i.  d_out_xy == d_points_xy is allowed.  The points are NOT validated: for a point on
+ *     the curve the law is complete; for any other input the output is unspecified, but the call does not fault (an
+ *     inversion of 0 yields 0, as everywhere in this library).  The kernel is ordered on the stream like the others; the
+ *     call allocates a window table for the threads in flight and releases it before it returns, which WAITS for the device.
+ *   pm_jubjub_check_dev: *first_bad = the lowest index whose point is off the curve or has a coordinate >= r, n when every
+ *     point passes.  WAITS for the stream.
+ * The two host forms need no context and no GPU (csrc/host_field.h): plain double-and-add over the affine law, on purpose
+ * another algorithm than the device's signed windows.  PM_ERR_BAD_ARG for a point off the curve, a coordinate or a scalar
+ * >= r, an unknown scalar_form, NULL.
+ * None of these calls is hardened against side channels: table addresses (device) and the sequence of additions (host)
+ * depend on the scalar. */
+typedef struct pm_jubjub_base pm_jubjub_base;
+int pm_jubjub_base_create(pm_ctx* ctx, const uint64_t xy[8], pm_jubjub_base** out);
+int pm_jubjub_base_from_key(pm_ctx* ctx, const pm_prover_key* key, size_t gadget_index, pm_jubjub_base** out);
+int pm_jubjub_base_point(const pm_jubjub_base* base, uint64_t xy[8]);
+void pm_jubjub_base_free(pm_ctx* ctx, pm_jubjub_base* base);
+int pm_jubjub_fixed_mul_dev(pm_ctx* ctx, const pm_jubjub_base* base, const void* d_scalars, size_t n, uint32_t scalar_form,
+                            void* d_out_xy, void* hip_stream);
+int pm_jubjub_commit_dev(pm_ctx* ctx, const pm_jubjub_base* g, const pm_jubjub_base* h, const void* d_values,
+                         const void* d_blinders, size_t n, uint32_t scalar_form, void* d_out_xy, void* hip_stream);
+int pm_jubjub_mul_dev(pm_ctx* ctx, const void* d_points_xy, const void* d_scalars, size_t n, uint32_t scalar_form,
+                      void* d_out_xy, void* hip_stream);
+int pm_jubjub_check_dev(pm_ctx* ctx, const void* d_points_xy, size_t n, size_t* first_bad, void* hip_stream);
+int pm_jubjub_mul_host(const uint64_t xy[8], const uint64_t scalar[4], uint32_t scalar_form, uint64_t out_xy[8]);
+int pm_jubjub_add_host(const uint64_t p[8], const uint64_t q[8], uint64_t out_xy[8]);
 /* Proof::to_bytes: 11 x 48-byte compressed G1, then the 16 scalars of ProofEvaluations::to_bytes. */
 int pm_plonk_proof_to_bytes(const pm_plonk_proof* proof, uint8_t out[PM_PLONK_PROOF_BYTES]);
 /* ---- The prover with coefficient-range ownership end to end (SURVEY.md section 8e row 3 + 8f N5; configs[4]) ----------

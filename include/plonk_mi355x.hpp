@@ -765,5 +765,71 @@ class Hades {
   pm_hades_params* p_ = nullptr;
 };
 
+// ------------------------------------------------------------------------------------------------
+// Native JubJub (pm_jubjub_*): one point of the embedded curve on the context's GPU with its window
+// table, and what runs with it.  A point is two elements (x, y), the identity (0, 1); scalars are Montgomery elements
+// (PM_SCALAR_MONTGOMERY) and multiply as the integers below r they stand for.  Not hardened against side channels.
+class JubJubBase {
+ public:
+  using Point = std::array<Fr, 2>;
+  JubJubBase(Context& ctx, const Point& xy) : ctx_(&ctx) { ctx.check(pm_jubjub_base_create(ctx.get(), xy[0].data(), &p_)); }
+  // the point FIXED_BASE gadget `gadget_index` of the key's gadget table multiplies; independent of the key afterwards
+  static JubJubBase from_key(Context& ctx, const ProverKey& key, size_t gadget_index) {
+    JubJubBase b(ctx);
+    ctx.check(pm_jubjub_base_from_key(ctx.get(), key.get(), gadget_index, &b.p_));
+    return b;
+  }
+  ~JubJubBase() { if (p_) pm_jubjub_base_free(ctx_->get(), p_); }
+  JubJubBase(const JubJubBase&) = delete;
+  JubJubBase& operator=(const JubJubBase&) = delete;
+  JubJubBase(JubJubBase&& o) noexcept : ctx_(o.ctx_), p_(o.p_) { o.p_ = nullptr; }
+  Point point() const {
+    Point xy{};
+    ctx_->check(pm_jubjub_base_point(p_, xy[0].data()));
+    return xy;
+  }
+  // n scalars -> n points (2 n elements); asynchronous on the context's stream
+  DevicePolynomial mul(const DevicePolynomial& scalars) const {
+    DevicePolynomial out(*ctx_, 2 * scalars.len());
+    ctx_->check(pm_jubjub_fixed_mul_dev(ctx_->get(), p_, scalars.data(), scalars.len(), PM_SCALAR_MONTGOMERY, out.data(), nullptr));
+    return out;
+  }
+  // out[i] = values[i] * g + blinders[i] * h in one pass
+  static DevicePolynomial commit(const JubJubBase& g, const JubJubBase& h, const DevicePolynomial& values, const DevicePolynomial& blinders) {
+    if (values.len() != blinders.len()) throw Error(PM_ERR_LENGTH, "one blinder per value");
+    DevicePolynomial out(*g.ctx_, 2 * values.len());
+    g.ctx_->check(pm_jubjub_commit_dev(g.ctx_->get(), g.p_, h.p_, values.data(), blinders.data(), values.len(), PM_SCALAR_MONTGOMERY,
+                                       out.data(), nullptr));
+    return out;
+  }
+  // points[i] <- scalars[i] * points[i], in place; the points are not validated.  Waits for the device.
+  static void mul_points(Context& ctx, DevicePolynomial& points, const DevicePolynomial& scalars) {
+    if (points.len() != 2 * scalars.len()) throw Error(PM_ERR_LENGTH, "one scalar per point");
+    ctx.check(pm_jubjub_mul_dev(ctx.get(), points.data(), scalars.data(), scalars.len(), PM_SCALAR_MONTGOMERY, points.data(), nullptr));
+  }
+  // the lowest index whose point is off the curve or not canonical; points.len() / 2 when there is none.  Waits for the stream.
+  static size_t check(Context& ctx, const DevicePolynomial& points) {
+    size_t bad = 0;
+    ctx.check(pm_jubjub_check_dev(ctx.get(), points.data(), points.len() / 2, &bad, nullptr));
+    return bad;
+  }
+  // no context, no GPU
+  static Point mul_host(const Point& xy, const Fr& scalar) {
+    Point out{};
+    if (pm_jubjub_mul_host(xy[0].data(), scalar.data(), PM_SCALAR_MONTGOMERY, out[0].data())) throw Error(PM_ERR_BAD_ARG, "pm_jubjub_mul_host refused its arguments");
+    return out;
+  }
+  static Point add_host(const Point& p, const Point& q) {
+    Point out{};
+    if (pm_jubjub_add_host(p[0].data(), q[0].data(), out[0].data())) throw Error(PM_ERR_BAD_ARG, "pm_jubjub_add_host refused its arguments");
+    return out;
+  }
+
+ private:
+  explicit JubJubBase(Context& ctx) : ctx_(&ctx) {}
+  Context* ctx_;
+  pm_jubjub_base* p_ = nullptr;
+};
+
 }  // namespace plonk_mi355x
 #endif  // PLONK_MI355X_HPP

@@ -201,6 +201,17 @@ SIGNATURES = {
                                                C.c_void_p, C.c_void_p]),
     "pm_hades_permute_host": (C.c_int, [C.c_uint32, C.c_uint32, u64p, u64p, C.c_uint32, u64p]),
     "pm_poseidon_hash_host": (C.c_int, [C.c_uint32, C.c_uint32, u64p, u64p, C.c_uint32, u64p, u64p, C.c_size_t, u64p]),
+    "pm_jubjub_base_create": (C.c_int, [C.c_void_p, u64p, C.POINTER(C.c_void_p)]),
+    "pm_jubjub_base_from_key": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
+    "pm_jubjub_base_point": (C.c_int, [C.c_void_p, u64p]),
+    "pm_jubjub_base_free": (None, [C.c_void_p, C.c_void_p]),
+    "pm_jubjub_fixed_mul_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "pm_jubjub_commit_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32,
+                                       C.c_void_p, C.c_void_p]),
+    "pm_jubjub_mul_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "pm_jubjub_check_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]),
+    "pm_jubjub_mul_host": (C.c_int, [u64p, u64p, C.c_uint32, u64p]),
+    "pm_jubjub_add_host": (C.c_int, [u64p, u64p, u64p]),
     "pm_plonk_proof_to_bytes": (C.c_int, [C.POINTER(PlonkProof), C.POINTER(C.c_uint8)]),
     "pm_plonk_batch_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
     "pm_plonk_batch_free": (None, [C.c_void_p, C.c_void_p]),

@@ -225,6 +225,10 @@ int gadget_fill(pm_ctx* ctx, const GadgetTables& t, const std::vector<GadgetGrou
 // of GADGET_ROUND_COEFS canonical coefficients at d_rounds, copied: the handle does not refer to the table.  Waits for the
 // context's stream (the gather of set time has then finished).
 int hades_params_from_rounds(pm_ctx* ctx, const void* d_rounds, uint32_t R, uint32_t F, pm_hades_params** out);
+// Native JubJub (jubjub.hip): a pm_jubjub_base from the table points gathered for a FIXED_BASE gadget -- R
+// points of GADGET_POINT_BYTES at d_points, most significant round first; the base is the last one and the points before it
+// must double it round by round.  The handle does not refer to the table.  Waits for the context's stream.
+int jubjub_base_from_table(pm_ctx* ctx, const void* d_points, uint32_t R, pm_jubjub_base** out);
 // Per-proof constants of the proof-batched kernels (pm_plonk_prove_batch): a pinned host buffer and its device twin of the
 // same size.  A launcher takes one region of both, fills the host side and sends it with one async copy on its stream;
 // kernels read the device side as a table indexed by the proof.  reset() once per call, after the previous call has

@@ -20,6 +20,7 @@
 #include "context.h"
 #include "field_inv.hip.h"
 #include "gadget_kinds.h"
+#include "jubjub.hip.h"
 #include "poly_common.hip.h"
 
 namespace pm {
@@ -117,20 +118,7 @@ PM_DEV void st_var(u32x4* vars, u32 id, const Fr& v) {
   if (id != PM_PLONK_NO_VAR) st_canon(vars, id, v);
 }
 
-// ------------------------------------------------------------------ field helpers (operands normalised, values < 2 r)
-PM_DEV Fr gadd(const Fr& a, const Fr& b) { return fe_reduce_weak<FrP>(fe_add<FrP>(a, b)); }
-PM_DEV Fr gsub(const Fr& a, const Fr& b) { return fe_reduce_weak<FrP>(fe_sub<FrP, 2, 1>(a, b)); }
-PM_DEV Fr gmul(const Fr& a, const Fr& b) { return fe_mul<FrP>(a, b); }
-PM_DEV Fr gneg(const Fr& a) { return gsub(fe_zero<FrP>(), a); }
-PM_DEV Fr g_to_dev(const Fr& abi) { return fe_reduce_weak<FrP>(fr_shl5(abi)); }
-PM_DEV Fr g_to_abi(const Fr& dev) { return fe_mul<FrP>(dev, fe_pow2<FrP, 256>()); }          // x 2^261 * 2^256 / 2^261
-PM_DEV Fr g_one_abi() { return fe_pow2<FrP, 256>(); }
-PM_DEV Fr g_sel(bool c, const Fr& a, const Fr& b) {
-  Fr r;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) r.l[i] = c ? a.l[i] : b.l[i];
-  return r;
-}
+// ------------------------------------------------------------------ field helpers: gadd .. g_sel are in jubjub.hip.h
 PM_DEV bool g_is_zero(const Fr& v) {   // a zero may arrive as r: test the canonical words
   u32 s[8];
   fe_canon_pack<FrP>(s, v);
@@ -533,30 +521,9 @@ __global__ void __launch_bounds__(64) gadget_hades_kernel(const GadgetFill a, u3
   }
 }
 
-// extended coordinates: x = X / Z, y = Y / Z, T = X Y / Z
-struct EdPoint {
-  Fr X, Y, Z, T;
-};
-// unified addition for a = -1 (Hisil, Wong, Carter, Dawson 2008): the projective form of the affine law above, with the same
-// exceptional cases -- none on the curve.  9 products.
-PM_DEV EdPoint ed_add(const EdPoint& p, const EdPoint& q, const Fr& d) {
-  const Fr A = gmul(p.X, q.X), B = gmul(p.Y, q.Y), C = gmul(gmul(p.T, q.T), d), D = gmul(p.Z, q.Z);
-  const Fr E = gsub(gsub(gmul(gadd(p.X, p.Y), gadd(q.X, q.Y)), A), B);
-  const Fr F = gsub(D, C), G = gadd(D, C), H = gadd(B, A);
-  return EdPoint{gmul(E, F), gmul(G, H), gmul(F, G), gmul(E, H)};
-}
-// the same with an affine second operand (x, y, t = x y): 8 products
-PM_DEV EdPoint ed_madd(const EdPoint& p, const Fr& x, const Fr& y, const Fr& t, const Fr& d) {
-  const Fr A = gmul(p.X, x), B = gmul(p.Y, y), C = gmul(gmul(p.T, t), d);
-  const Fr E = gsub(gsub(gmul(gadd(p.X, p.Y), gadd(x, y)), A), B);
-  const Fr F = gsub(p.Z, C), G = gadd(p.Z, C), H = gadd(B, A);
-  return EdPoint{gmul(E, F), gmul(G, H), gmul(F, G), gmul(E, H)};
-}
+// EdPoint, ed_add, ed_madd, ed_sel: jubjub.hip.h
 PM_DEV EdPoint ed_shfl_up(const EdPoint& p, u32 delta) {
   return EdPoint{fr_shfl_up(p.X, delta), fr_shfl_up(p.Y, delta), fr_shfl_up(p.Z, delta), fr_shfl_up(p.T, delta)};
-}
-PM_DEV EdPoint ed_sel(bool c, const EdPoint& a, const EdPoint& b) {
-  return EdPoint{g_sel(c, a.X, b.X), g_sel(c, a.Y, b.Y), g_sel(c, a.Z, b.Z), g_sel(c, a.T, b.T)};
 }
 
 // the addend of a round in device form: bit (x_b, y_b) = (bit x_b, bit^2 (y_b - 1) + 1), t = bit x_b y_b; c_abi = t in ABI form
@@ -824,9 +791,7 @@ int gadget_fill(pm_ctx* ctx, const GadgetTables& t, const std::vector<GadgetGrou
   GadgetFill a{.recs = (const GadgetRec*)t.recs, .wire_vars = (const u32*)d_wire_vars, .tab = (const u32x4*)t.tab, .coef = (const u32x4*)t.coef,
                .hcoef = (const u32x4*)t.hcoef, .hids = (const u32*)t.hids, .vars = (u32x4*)d_vars, .var_stride = var_stride, .n = n,
                .rep = (unsigned long long*)t.rep, .edwards_d = {}};
-  const host::Field<4>& F = host::FR();   // JubJub d = -(10240 / 10241): the inversion once, not per call
-  static const HFr edwards_d = host::sub(host::zero<4>(), host::mul(host::from_u64(10240, F), host::inv(host::from_u64(10241, F), F), F), F);
-  to_limbs29_shift(a.edwards_d, edwards_d, 1);
+  jubjub_d_limbs(a.edwards_d);
   PM_HIP(ctx, hipMemsetAsync(t.rep, 0, (size_t)batch * 8, st));
   PM_HIP(ctx, hipMemsetAsync((char*)t.rep + (size_t)batch * 8, 0xff, (size_t)batch * 8, st));
   {

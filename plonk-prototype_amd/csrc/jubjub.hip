@@ -1,0 +1,537 @@
+// Native JubJub: scalar multiplications on the embedded curve outside a circuit.  gadgets.hip fills the
+// ROWS of a multiplication (one wave each, every intermediate point stored); here only the product leaves the kernel, one thread
+// per output, with the group law of jubjub.hip.h:
+//
+//   fixed base   out[i] = s_i B.  A pm_jubjub_base owns the table j 16^w B, w < 64, j = 1..8, affine (x, y, t = x y) in the
+//                device form; 64 ed_madd into one extended accumulator.
+//   commitment   out[i] = v_i G + b_i H: both digit strings walk into the SAME accumulator, 128 ed_madd.
+//   variable     out[i] = s_i P_i: a thread's table 1 P .. 8 P in a scratch buffer, 64 windows of four doublings and an addition.
+//   check        the lowest index whose point is off the curve or has a coordinate that is not below r.
+// Each of the first three ends with ONE inversion (of Z) and two products.
+//
+// Digits.  The scalar is the INTEGER 0 <= s < r, never reduced modulo the order of a point.  Its 64 nibbles n_w become signed
+// digits d_w in [-8, 8] with a carry: v = n_w + c_w; v > 8 gives d_w = v - 16 and c_(w+1) = 1, anything else d_w = v and
+// c_(w+1) = 0.  Because s < r < 2^255 the top nibble is at most 7, so d_63 <= 8 and the carry out of it is 0: there is no 65th
+// digit.  A digit picks entry |d| of its window (entry 1 for d = 0, so that every lane loads something) and g_sel turns what was
+// loaded into the addend: negated for d < 0, the neutral addend (0, 1, 0) for d = 0.  No branch and no loop bound depends on a
+// scalar or a lane; only the table index differs between the lanes of a wave.
+//
+// fe_inv_dev votes across the wave (field_inv.hip.h), so every lane of every wave reaches it: a lane past n works on element
+// n - 1 and, not being live, stores nothing.
+//
+// These kernels are NOT hardened against side channels: table addresses depend on the scalar.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "context.h"
+#include "field_inv.hip.h"
+#include "jubjub.hip.h"
+
+struct pm_jubjub_base {
+  int device = 0;
+  uint64_t xy[8] = {0};     // the point, canonical Montgomery
+  void* d_tab = nullptr;    // JJ_WINDOWS x 8 entries of JJ_ENTRY_CHUNKS x 16 bytes (entry_limbs below)
+};
+
+namespace pm {
+namespace {
+
+using host::HFr;
+
+constexpr u32 JJ_WINDOWS = 64;       // signed base-16 digits of a scalar below 2^255
+constexpr u32 JJ_ENTRY_CHUNKS = 7;   // fixed-base entry: x, y, t as 27 limbs and one word of padding, 112 bytes
+constexpr u32 JJ_POINT_CHUNKS = 9;   // variable-base entry: X, Y, Z, T as 36 limbs, 144 bytes
+constexpr size_t JJ_BASE_TABLE_BYTES = (size_t)JJ_WINDOWS * 8 * JJ_ENTRY_CHUNKS * 16;   // 57344
+constexpr size_t JJ_MUL_TABLE_BYTES = 8 * (size_t)JJ_POINT_CHUNKS * 16;                 // per thread in flight: 1152
+
+// ------------------------------------------------------------------ the affine law on the host (csrc/host_field.h)
+struct HPoint {
+  HFr x, y;
+};
+bool hfr_canonical(const uint64_t* v) { return !host::geq<4>(v, host::FR().m); }
+HFr hfr_load(const uint64_t* v) {
+  HFr r;
+  memcpy(r.l, v, 32);
+  return r;
+}
+HPoint hpoint_load(const uint64_t* xy) { return HPoint{hfr_load(xy), hfr_load(xy + 4)}; }
+HPoint hpoint_identity() { return HPoint{host::zero<4>(), host::one<4>(host::FR())}; }
+bool hpoint_on_curve(const HPoint& p) {
+  const host::Field<4>& F = host::FR();
+  const HFr x2 = host::mul(p.x, p.x, F), y2 = host::mul(p.y, p.y, F);
+  const HFr rhs = host::add(host::one<4>(F), host::mul(jubjub_d_host(), host::mul(x2, y2, F), F), F);
+  return host::eq(host::sub(y2, x2, F), rhs);
+}
+// (x1, y1) + (x2, y2) = ((x1 y2 + y1 x2) / (1 + k), (y1 y2 + x1 x2) / (1 - k)), k = d x1 x2 y1 y2: complete on the curve
+HPoint hpoint_add(const HPoint& p, const HPoint& q) {
+  const host::Field<4>& F = host::FR();
+  const HFr x1y2 = host::mul(p.x, q.y, F), y1x2 = host::mul(p.y, q.x, F), y1y2 = host::mul(p.y, q.y, F), x1x2 = host::mul(p.x, q.x, F);
+  const HFr k = host::mul(jubjub_d_host(), host::mul(x1y2, y1x2, F), F), one = host::one<4>(F);
+  const HFr inv = host::inv(host::mul(host::add(one, k, F), host::sub(one, k, F), F), F);   // one inversion for both denominators
+  return HPoint{host::mul(host::mul(host::add(x1y2, y1x2, F), host::sub(one, k, F), F), inv, F),
+                host::mul(host::mul(host::add(y1y2, x1x2, F), host::add(one, k, F), F), inv, F)};
+}
+// canonical or Montgomery scalar in memory -> the integer below r; false: not below r
+bool scalar_to_int(const uint64_t* s, uint32_t form, uint64_t (&out)[4]) {
+  if (!hfr_canonical(s)) return false;
+  if (form == PM_SCALAR_CANONICAL) {
+    memcpy(out, s, 32);
+    return true;
+  }
+  HFr one_int = host::zero<4>();
+  one_int.l[0] = 1;                                         // x R * 1 / R = x
+  const HFr v = host::mul(hfr_load(s), one_int, host::FR());
+  memcpy(out, v.l, 32);
+  return true;
+}
+// plain double-and-add from the top bit: NOT the device's algorithm
+HPoint hpoint_mul(const HPoint& p, const uint64_t (&k)[4]) {
+  HPoint acc = hpoint_identity();
+  for (int i = 254; i >= 0; --i) {
+    acc = hpoint_add(acc, acc);
+    if ((k[i / 64] >> (i % 64)) & 1) acc = hpoint_add(acc, p);
+  }
+  return acc;
+}
+bool point_fault(const uint64_t* xy) { return !hfr_canonical(xy) || !hfr_canonical(xy + 4) || !hpoint_on_curve(hpoint_load(xy)); }
+
+// ------------------------------------------------------------------ device side
+struct JubjubMul {
+  const u32x4* tab_g;       // fixed base, commitment: the table of the (first) base
+  const u32x4* tab_h;       // commitment: the table of the second base
+  const u32x4* points;      // variable base: n x (x | y)
+  const u32x4* scalars;     // n elements
+  const u32x4* scalars_h;   // commitment: the blinders
+  u32x4* out;               // n x (x | y)
+  u32x4* scratch;           // variable base: [entry][chunk][thread of the grid]
+  size_t n;
+  u32 montgomery;           // the scalars are Montgomery elements, not plain integers
+  u32 edwards_d[9];         // device form
+};
+
+// the scalar at p as four 64-bit words of the integer below r
+PM_DEV void jj_load_scalar(const u32x4* p, bool montgomery, u64 (&k)[4]) {
+  Fr f;
+  if (montgomery) {
+    f = fe_zero<FrP>();
+    f.l[0] = 32u;           // x 2^256 * 2^5 / 2^261 = x
+  } else {
+    f = fe_one<FrP>();
+  }
+  u32 w[8];
+  fe_canon_pack<FrP>(w, fe_mul<FrP>(fe_load<FrP>(p), f));
+#pragma unroll
+  for (int i = 0; i < 4; ++i) k[i] = (u64)w[2 * i] | ((u64)w[2 * i + 1] << 32);
+}
+PM_DEV void jj_shr4(u64 (&k)[4]) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) k[i] = (k[i] >> 4) | (k[i + 1] << 60);
+  k[3] >>= 4;
+}
+PM_DEV void jj_shl4(u64 (&k)[4]) {
+#pragma unroll
+  for (int i = 3; i > 0; --i) k[i] = (k[i] << 4) | (k[i - 1] >> 60);
+  k[0] <<= 4;
+}
+// the signed digit of nibble `nib` with carry `c` in; c becomes the carry out (the file comment)
+PM_DEV int jj_digit(u32 nib, u32& c) {
+  const u32 v = nib + c;
+  c = v > 8u ? 1u : 0u;
+  return (int)v - (c ? 16 : 0);
+}
+// bit w = the carry INTO digit w, for the walk from the top digit down
+PM_DEV u64 jj_carries(u64 (&k)[4]) {
+  u64 t[4] = {k[0], k[1], k[2], k[3]}, m = 0;
+  u32 c = 0;
+#pragma unroll 1
+  for (u32 w = 0; w < JJ_WINDOWS; ++w) {
+    m |= (u64)c << w;
+    (void)jj_digit((u32)t[0] & 15u, c);
+    jj_shr4(t);
+  }
+  return m;
+}
+PM_DEV Fr jj_limbs(const u32x4& a, const u32x4& b, u32 c) {
+  Fr r;
+  r.l[0] = a.x, r.l[1] = a.y, r.l[2] = a.z, r.l[3] = a.w, r.l[4] = b.x, r.l[5] = b.y, r.l[6] = b.z, r.l[7] = b.w, r.l[8] = c;
+  return r;
+}
+// acc += d * (entry |d| of window w of tab): entry e of window w sits at chunk (8 w + e - 1) * 7
+PM_DEV EdPoint jj_fixed_step(const EdPoint& acc, const u32x4* tab, u32 w, int d, const Fr& ed) {
+  const u32 mag = (u32)(d < 0 ? -d : d), e = mag == 0 ? 1u : (mag > 8u ? 8u : mag);
+  const u32x4* p = tab + (size_t)(8 * w + e - 1) * JJ_ENTRY_CHUNKS;
+  const u32x4 c0 = p[0], c1 = p[1], c2 = p[2], c3 = p[3], c4 = p[4], c5 = p[5], c6 = p[6];
+  const Fr x = jj_limbs(c0, c1, c2.x);
+  const Fr y = jj_limbs(u32x4{c2.y, c2.z, c2.w, c3.x}, u32x4{c3.y, c3.z, c3.w, c4.x}, c4.y);
+  const Fr t = jj_limbs(u32x4{c4.z, c4.w, c5.x, c5.y}, u32x4{c5.z, c5.w, c6.x, c6.y}, c6.z);
+  const Fr zero = fe_zero<FrP>(), one = fe_one<FrP>();
+  const Fr ax = g_sel(d == 0, zero, g_sel(d < 0, gneg(x), x));
+  const Fr ay = g_sel(d == 0, one, y);
+  const Fr at = g_sel(d == 0, zero, g_sel(d < 0, gneg(t), t));
+  return ed_madd(acc, ax, ay, at, ed);
+}
+// (X / Z, Y / Z) to element i of out when live: one inversion, two products (and the change of form); Z = 0 gives (0, 0)
+PM_DEV void jj_store_affine(u32x4* out, size_t i, bool live, const EdPoint& p) {
+  const Fr zi = g_to_abi(fe_inv_dev<FrP>(p.Z));             // every lane of the wave is here
+  if (!live) return;
+  st_canon(out, 2 * i, gmul(p.X, zi));                      // device x ABI -> ABI
+  st_canon(out, 2 * i + 1, gmul(p.Y, zi));
+}
+// v, hidden from the optimiser: what it derives from a loop-invariant operand of a product it otherwise keeps in registers
+// across the whole loop (the table build below then needs all 512 registers of a lone wave and scratch on top)
+PM_DEV void jj_opaque(Fr& v) {
+#pragma unroll
+  for (int i = 0; i < 9; ++i) asm volatile("" : "+v"(v.l[i]));
+}
+PM_DEV EdPoint jj_neutral() { return EdPoint{fe_zero<FrP>(), fe_one<FrP>(), fe_one<FrP>(), fe_zero<FrP>()}; }
+
+// fixed base (COMMIT = false) and commitment (true): the digits from the bottom up, the order of a sum being free
+template <bool COMMIT>
+__global__ void __launch_bounds__(64) jubjub_fixed_kernel(const JubjubMul a) {
+  const size_t g = (size_t)blockIdx.x * 64 + threadIdx.x;
+  const bool live = g < a.n;
+  const size_t i = live ? g : a.n - 1;
+  const Fr ed = fr_limbs(a.edwards_d);
+  u64 k[4], kh[4] = {0, 0, 0, 0};
+  jj_load_scalar(a.scalars + 2 * i, a.montgomery != 0, k);
+  if (COMMIT) jj_load_scalar(a.scalars_h + 2 * i, a.montgomery != 0, kh);
+  u32 c = 0, ch = 0;
+  EdPoint acc = jj_neutral();
+#pragma unroll 1
+  for (u32 w = 0; w < JJ_WINDOWS; ++w) {
+    acc = jj_fixed_step(acc, a.tab_g, w, jj_digit((u32)k[0] & 15u, c), ed);
+    jj_shr4(k);
+    if (COMMIT) {
+      acc = jj_fixed_step(acc, a.tab_h, w, jj_digit((u32)kh[0] & 15u, ch), ed);
+      jj_shr4(kh);
+    }
+  }
+  jj_store_affine(a.out, i, live, acc);
+}
+
+// variable base.  One thread's table: chunk c of entry e (e P, e = 1..8, X Y Z T as 36 limbs) at base[((e - 1) * 9 + c) * stride],
+// base = scratch + thread, stride = the threads of the grid: the lanes of a wave read and write consecutive 16-byte chunks when
+// they share a digit and stay aligned when they do not.  A bounded grid walks n in strides (the table is per thread in flight);
+// every wave runs the same number of rounds with its lanes clamped, and an element is read before the same thread writes it,
+// so out may be the points.
+PM_DEV void jj_table_store(u32x4* base, size_t stride, u32 e, const EdPoint& p) {
+  u32 l[36];
+#pragma unroll
+  for (int j = 0; j < 9; ++j) l[j] = p.X.l[j], l[9 + j] = p.Y.l[j], l[18 + j] = p.Z.l[j], l[27 + j] = p.T.l[j];
+  u32x4* q = base + (size_t)(e - 1) * JJ_POINT_CHUNKS * stride;
+#pragma unroll
+  for (int c = 0; c < 9; ++c) q[c * stride] = u32x4{l[4 * c], l[4 * c + 1], l[4 * c + 2], l[4 * c + 3]};
+}
+PM_DEV EdPoint jj_table_load(const u32x4* base, size_t stride, u32 e) {
+  u32 l[36];
+  const u32x4* q = base + (size_t)(e - 1) * JJ_POINT_CHUNKS * stride;
+#pragma unroll
+  for (int c = 0; c < 9; ++c) {
+    const u32x4 v = q[c * stride];
+    l[4 * c] = v.x, l[4 * c + 1] = v.y, l[4 * c + 2] = v.z, l[4 * c + 3] = v.w;
+  }
+  EdPoint p;
+#pragma unroll
+  for (int j = 0; j < 9; ++j) p.X.l[j] = l[j], p.Y.l[j] = l[9 + j], p.Z.l[j] = l[18 + j], p.T.l[j] = l[27 + j];
+  return p;
+}
+// two waves a SIMD: the register budget the allocator meets without scratch
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) jubjub_var_kernel(const JubjubMul a) {
+  const size_t T = (size_t)gridDim.x * 64, tid = (size_t)blockIdx.x * 64 + threadIdx.x;
+  u32x4* const tbl = a.scratch + tid;
+  const Fr ed = fr_limbs(a.edwards_d);
+#pragma unroll 1
+  for (size_t first = (size_t)blockIdx.x * 64; first < a.n; first += T) {   // wave-uniform: the lanes stay together
+    const size_t g = first + threadIdx.x;
+    const bool live = g < a.n;
+    const size_t i = live ? g : a.n - 1;
+    const Fr px = g_to_dev(ld_canon(a.points, 2 * i)), py = g_to_dev(ld_canon(a.points, 2 * i + 1)), pt = gmul(px, py);
+    u64 k[4];
+    jj_load_scalar(a.scalars + 2 * i, a.montgomery != 0, k);
+    u64 carries = jj_carries(k);
+    // ---- the table: e P = (e - 1) P + P
+    EdPoint acc{px, py, fe_one<FrP>(), pt};
+    jj_table_store(tbl, T, 1, acc);
+#pragma unroll 1
+    for (u32 e = 2; e <= 8; ++e) {
+      Fr x = px, y = py, t = pt;
+      jj_opaque(x), jj_opaque(y), jj_opaque(t);
+      acc = ed_madd(acc, x, y, t, ed);
+      jj_table_store(tbl, T, e, acc);
+    }
+    // ---- the ladder from the top digit down
+    acc = jj_neutral();
+#pragma unroll 1
+    for (u32 w = 0; w < JJ_WINDOWS; ++w) {
+#pragma unroll 1
+      for (u32 j = 0; j < 4; ++j) acc = ed_add(acc, acc, ed);
+      u32 c = (u32)(carries >> 63);
+      const int d = jj_digit((u32)(k[3] >> 60), c);
+      jj_shl4(k);
+      carries <<= 1;
+      const u32 mag = (u32)(d < 0 ? -d : d), e = mag == 0 ? 1u : (mag > 8u ? 8u : mag);
+      const EdPoint q = jj_table_load(tbl, T, e);
+      const EdPoint s{g_sel(d < 0, gneg(q.X), q.X), q.Y, q.Z, g_sel(d < 0, gneg(q.T), q.T)};
+      acc = ed_add(acc, ed_sel(d == 0, jj_neutral(), s), ed);
+    }
+    jj_store_affine(a.out, i, live, acc);
+  }
+}
+
+// the words of r, most significant first
+constexpr u32 JJ_R_WORDS[8] = {0x73eda753u, 0x299d7d48u, 0x3339d808u, 0x09a1d805u, 0x53bda402u, 0xfffe5bfeu, 0xffffffffu, 0x00000001u};
+PM_DEV bool jj_below_r(const u32x4& lo, const u32x4& hi) {
+  const u32 w[8] = {hi.w, hi.z, hi.y, hi.x, lo.w, lo.z, lo.y, lo.x};
+  bool below = false, decided = false;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    below = (!decided && w[j] < JJ_R_WORDS[j]) ? true : below;
+    decided = decided || w[j] != JJ_R_WORDS[j];
+  }
+  return below;
+}
+__global__ void __launch_bounds__(64) jubjub_check_kernel(const u32x4* points, size_t n, const JubjubMul a /* edwards_d */,
+                                                          unsigned long long* first_bad) {
+  const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  const u32x4* p = points + 4 * i;
+  const bool canonical = jj_below_r(p[0], p[1]) && jj_below_r(p[2], p[3]);
+  const Fr x = g_to_dev(ld_canon(points, 2 * i)), y = g_to_dev(ld_canon(points, 2 * i + 1));
+  const Fr x2 = gmul(x, x), y2 = gmul(y, y);
+  const Fr rhs = gadd(fe_one<FrP>(), gmul(gmul(x2, y2), fr_limbs(a.edwards_d)));
+  u32 s[8], any = 0;
+  fe_canon_pack<FrP>(s, gsub(gsub(y2, x2), rhs));
+#pragma unroll
+  for (int j = 0; j < 8; ++j) any |= s[j];
+  if (!canonical || any) atomicMin(first_bad, (unsigned long long)i);
+}
+
+// ------------------------------------------------------------------ handles and launches
+// x, y, t of one table entry in the device form, 27 limbs and a zero word
+void entry_limbs(u32* dst, const HPoint& p) {
+  to_limbs29(dst, p.x);
+  to_limbs29(dst + 9, p.y);
+  to_limbs29(dst + 18, host::mul(p.x, p.y, host::FR()));
+  dst[27] = 0;
+}
+// the point (validated) -> a handle with its table: j 16^w B built on the host with the affine law, once
+int base_build(pm_ctx* ctx, const uint64_t* xy, pm_jubjub_base** out) {
+  std::vector<u32> tab(JJ_BASE_TABLE_BYTES / 4);
+  HPoint bw = hpoint_load(xy);                               // 16^w B
+  for (u32 w = 0; w < JJ_WINDOWS; ++w) {
+    HPoint e = bw;
+    for (u32 j = 1; j <= 8; ++j) {
+      entry_limbs(&tab[(size_t)(8 * w + j - 1) * JJ_ENTRY_CHUNKS * 4], e);
+      if (j < 8) e = hpoint_add(e, bw);
+    }
+    bw = hpoint_add(e, e);                                   // 16 = 2 * 8
+  }
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  void* d = nullptr;
+  PM_HIP(ctx, hipMalloc(&d, JJ_BASE_TABLE_BYTES));
+  const hipError_t e = hipMemcpy(d, tab.data(), JJ_BASE_TABLE_BYTES, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(d);
+    return set_err(ctx, PM_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
+  }
+  pm_jubjub_base* b = new pm_jubjub_base();
+  b->device = ctx->device, b->d_tab = d;
+  memcpy(b->xy, xy, 64);
+  *out = b;
+  return PM_OK;
+}
+
+int form_fault(pm_ctx* ctx, uint32_t scalar_form) {
+  if (scalar_form != PM_SCALAR_MONTGOMERY && scalar_form != PM_SCALAR_CANONICAL)
+    return set_err(ctx, PM_ERR_BAD_ARG, "scalar_form must be PM_SCALAR_MONTGOMERY or PM_SCALAR_CANONICAL");
+  return PM_OK;
+}
+int base_fault(pm_ctx* ctx, const pm_jubjub_base* b) {
+  if (!b) return set_err(ctx, PM_ERR_BAD_ARG, "null base");
+  if (b->device != ctx->device) return set_err(ctx, PM_ERR_BAD_ARG, "the base belongs to another device");
+  return PM_OK;
+}
+bool unaligned(std::initializer_list<const void*> ps) {
+  uintptr_t acc = 0;
+  for (const void* p : ps) acc |= (uintptr_t)p;
+  return (acc & 15u) != 0;
+}
+
+}  // namespace
+
+// context.h: the table gathered for a FIXED_BASE gadget (GadgetTables::tab at its offset: R points x | y, canonical) -> a handle
+// for its base t[R - 1], when t[k] = 2 t[k + 1] throughout.  Waits for the context's stream.
+int jubjub_base_from_table(pm_ctx* ctx, const void* d_points, uint32_t R, pm_jubjub_base** out) {
+  std::vector<uint64_t> t(8 * (size_t)R);
+  {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    PM_HIP(ctx, hipSetDevice(ctx->device));
+    PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    PM_HIP(ctx, hipMemcpy(t.data(), d_points, t.size() * 8, hipMemcpyDeviceToHost));
+  }
+  for (size_t k = 0; k < R; ++k)
+    if (point_fault(&t[8 * k]))
+      return set_err(ctx, PM_ERR_BAD_ARG, "pm_jubjub_base_from_key: table point " + std::to_string(k) + " is not a canonical curve point");
+  for (size_t k = 0; k + 1 < R; ++k) {
+    const HPoint next = hpoint_load(&t[8 * (k + 1)]), twice = hpoint_add(next, next), here = hpoint_load(&t[8 * k]);
+    if (!host::eq(twice.x, here.x) || !host::eq(twice.y, here.y))
+      return set_err(ctx, PM_ERR_BAD_ARG, "pm_jubjub_base_from_key: the gadget's table is not a doubling chain at round " + std::to_string(k));
+  }
+  return base_build(ctx, &t[8 * ((size_t)R - 1)], out);
+}
+
+}  // namespace pm
+
+using namespace pm;
+
+extern "C" int pm_jubjub_base_create(pm_ctx* ctx, const uint64_t xy[8], pm_jubjub_base** out) {
+  if (!ctx || !out) return PM_ERR_BAD_ARG;
+  if (!xy) return set_err(ctx, PM_ERR_BAD_ARG, "null point");
+  if (point_fault(xy)) return set_err(ctx, PM_ERR_BAD_ARG, "pm_jubjub_base_create: the point is not a canonical point of the curve");
+  return base_build(ctx, xy, out);
+}
+
+extern "C" int pm_jubjub_base_point(const pm_jubjub_base* base, uint64_t xy[8]) {
+  if (!base || !xy) return PM_ERR_BAD_ARG;
+  memcpy(xy, base->xy, 64);
+  return PM_OK;
+}
+
+extern "C" void pm_jubjub_base_free(pm_ctx* ctx, pm_jubjub_base* base) {
+  if (!base) return;
+  if (ctx) {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+    if (base->d_tab) (void)hipFree(base->d_tab);   // hipFree waits for the device: launches on caller streams included
+  }
+  delete base;
+}
+
+extern "C" int pm_jubjub_fixed_mul_dev(pm_ctx* ctx, const pm_jubjub_base* base, const void* d_scalars, size_t n, uint32_t scalar_form,
+                                       void* d_out_xy, void* hip_stream) {
+  if (!ctx) return PM_ERR_BAD_ARG;
+  if (int rc = base_fault(ctx, base)) return rc;
+  if (int rc = form_fault(ctx, scalar_form)) return rc;
+  if (!d_scalars || !d_out_xy || unaligned({d_scalars, d_out_xy})) return set_err(ctx, PM_ERR_BAD_ARG, "null or unaligned device pointer");
+  if (n == 0) return PM_OK;
+  if (n > 0x7fffffffu) return set_err(ctx, PM_ERR_LENGTH, "n > 2^31");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  JubjubMul a{};
+  a.tab_g = (const u32x4*)base->d_tab, a.scalars = (const u32x4*)d_scalars, a.out = (u32x4*)d_out_xy, a.n = n;
+  a.montgomery = scalar_form == PM_SCALAR_MONTGOMERY;
+  jubjub_d_limbs(a.edwards_d);
+  ProfScope prof(ctx, st, "jubjub_fixed_mul");
+  hipLaunchKernelGGL((jubjub_fixed_kernel<false>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, a);
+  PM_HIP(ctx, hipGetLastError());
+  return PM_OK;
+}
+
+extern "C" int pm_jubjub_commit_dev(pm_ctx* ctx, const pm_jubjub_base* g, const pm_jubjub_base* h, const void* d_values,
+                                    const void* d_blinders, size_t n, uint32_t scalar_form, void* d_out_xy, void* hip_stream) {
+  if (!ctx) return PM_ERR_BAD_ARG;
+  if (int rc = base_fault(ctx, g)) return rc;
+  if (int rc = base_fault(ctx, h)) return rc;
+  if (int rc = form_fault(ctx, scalar_form)) return rc;
+  if (!d_values || !d_blinders || !d_out_xy || unaligned({d_values, d_blinders, d_out_xy}))
+    return set_err(ctx, PM_ERR_BAD_ARG, "null or unaligned device pointer");
+  if (n == 0) return PM_OK;
+  if (n > 0x7fffffffu) return set_err(ctx, PM_ERR_LENGTH, "n > 2^31");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  JubjubMul a{};
+  a.tab_g = (const u32x4*)g->d_tab, a.tab_h = (const u32x4*)h->d_tab, a.scalars = (const u32x4*)d_values;
+  a.scalars_h = (const u32x4*)d_blinders, a.out = (u32x4*)d_out_xy, a.n = n, a.montgomery = scalar_form == PM_SCALAR_MONTGOMERY;
+  jubjub_d_limbs(a.edwards_d);
+  ProfScope prof(ctx, st, "jubjub_commit");
+  hipLaunchKernelGGL((jubjub_fixed_kernel<true>), dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, a);
+  PM_HIP(ctx, hipGetLastError());
+  return PM_OK;
+}
+
+extern "C" int pm_jubjub_mul_dev(pm_ctx* ctx, const void* d_points_xy, const void* d_scalars, size_t n, uint32_t scalar_form,
+                                 void* d_out_xy, void* hip_stream) {
+  if (!ctx) return PM_ERR_BAD_ARG;
+  if (int rc = form_fault(ctx, scalar_form)) return rc;
+  if (!d_points_xy || !d_scalars || !d_out_xy || unaligned({d_points_xy, d_scalars, d_out_xy}))
+    return set_err(ctx, PM_ERR_BAD_ARG, "null or unaligned device pointer");
+  if (n == 0) return PM_OK;
+  if (n > 0x7fffffffu) return set_err(ctx, PM_ERR_LENGTH, "n > 2^31");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  // the window tables of the threads in flight: eight workgroups of 64 a CU at the most, 1152 bytes a thread
+  const size_t blocks = std::max<size_t>(std::min<size_t>((n + 63) / 64, (size_t)std::max(ctx->num_cus, 1) * 8), 1);
+  void* scratch = nullptr;
+  PM_HIP(ctx, hipMalloc(&scratch, blocks * 64 * JJ_MUL_TABLE_BYTES));
+  JubjubMul a{};
+  a.points = (const u32x4*)d_points_xy, a.scalars = (const u32x4*)d_scalars, a.out = (u32x4*)d_out_xy, a.scratch = (u32x4*)scratch;
+  a.n = n, a.montgomery = scalar_form == PM_SCALAR_MONTGOMERY;
+  jubjub_d_limbs(a.edwards_d);
+  hipError_t e;
+  {
+    ProfScope prof(ctx, st, "jubjub_mul");
+    hipLaunchKernelGGL(jubjub_var_kernel, dim3((unsigned)blocks), dim3(64), 0, st, a);
+    e = hipGetLastError();
+  }
+  // the launch is ordered on the stream like any other; releasing the scratch waits for it (hipFree waits for the device)
+  const hipError_t e2 = hipFree(scratch);
+  if (e == hipSuccess) e = e2;
+  if (e != hipSuccess) return set_err(ctx, PM_ERR_HIP, std::string("pm_jubjub_mul_dev: ") + hipGetErrorString(e));
+  return PM_OK;
+}
+
+extern "C" int pm_jubjub_check_dev(pm_ctx* ctx, const void* d_points_xy, size_t n, size_t* first_bad, void* hip_stream) {
+  if (!ctx) return PM_ERR_BAD_ARG;
+  if (!first_bad) return set_err(ctx, PM_ERR_BAD_ARG, "null first_bad");
+  *first_bad = n;
+  if (n == 0) return PM_OK;
+  if (!d_points_xy || unaligned({d_points_xy})) return set_err(ctx, PM_ERR_BAD_ARG, "null or unaligned device pointer");
+  if (n > 0x7fffffffu) return set_err(ctx, PM_ERR_LENGTH, "n > 2^31");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  unsigned long long* d_bad = nullptr;
+  unsigned long long bad = n;
+  PM_HIP(ctx, hipMalloc((void**)&d_bad, 8));
+  JubjubMul a{};
+  jubjub_d_limbs(a.edwards_d);
+  hipError_t e = hipMemcpyAsync(d_bad, &bad, 8, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(jubjub_check_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, (const u32x4*)d_points_xy, n, a, d_bad);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  (void)hipFree(d_bad);
+  if (e != hipSuccess) return set_err(ctx, PM_ERR_HIP, std::string("pm_jubjub_check_dev: ") + hipGetErrorString(e));
+  *first_bad = (size_t)bad;
+  return PM_OK;
+}
+
+extern "C" int pm_jubjub_mul_host(const uint64_t xy[8], const uint64_t scalar[4], uint32_t scalar_form, uint64_t out_xy[8]) {
+  if (!xy || !scalar || !out_xy) return PM_ERR_BAD_ARG;
+  if (scalar_form != PM_SCALAR_MONTGOMERY && scalar_form != PM_SCALAR_CANONICAL) return PM_ERR_BAD_ARG;
+  uint64_t k[4];
+  if (point_fault(xy) || !scalar_to_int(scalar, scalar_form, k)) return PM_ERR_BAD_ARG;
+  const HPoint r = hpoint_mul(hpoint_load(xy), k);
+  memcpy(out_xy, r.x.l, 32);
+  memcpy(out_xy + 4, r.y.l, 32);
+  return PM_OK;
+}
+
+extern "C" int pm_jubjub_add_host(const uint64_t p[8], const uint64_t q[8], uint64_t out_xy[8]) {
+  if (!p || !q || !out_xy) return PM_ERR_BAD_ARG;
+  if (point_fault(p) || point_fault(q)) return PM_ERR_BAD_ARG;
+  const HPoint r = hpoint_add(hpoint_load(p), hpoint_load(q));
+  memcpy(out_xy, r.x.l, 32);
+  memcpy(out_xy + 4, r.y.l, 32);
+  return PM_OK;
+}

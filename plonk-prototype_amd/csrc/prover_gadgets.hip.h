@@ -7,7 +7,7 @@ struct GadgetState {
   size_t bytes = 0;                        // device bytes held
   pm::GadgetTables dev;
   std::vector<pm::GadgetGroup> groups;     // one launch each, levels rising
-  std::vector<pm::GadgetRec> recs;         // the host's copy of dev.recs (launch order): pm_hades_params_from_key
+  std::vector<pm::GadgetRec> recs;         // the host's copy of dev.recs (launch order): pm_hades_params_from_key, pm_jubjub_base_from_key
 };
 
 // the rows a gadget claims (the widget kinds: the trailing row included); 0: a kind, count or param that is refused whatever the
@@ -174,6 +174,20 @@ extern "C" int pm_hades_params_from_key(pm_ctx* ctx, const pm_prover_key* pk, si
     if (rec.kind != PM_PLONK_PERMUTATION_HADES)
       return pm::set_err(ctx, PM_ERR_BAD_ARG, "gadget " + std::to_string(gadget_index) + " is not of kind PM_PLONK_PERMUTATION_HADES");
     return pm::hades_params_from_rounds(ctx, at(gs->dev.hcoef, (size_t)rec.tab * pm::GADGET_ROUND_COEFS), rec.count, rec.param, out);
+  }
+  return pm::set_err(ctx, PM_ERR_BAD_ARG, "gadget_index is not below the table's count");
+}
+
+// Native JubJub with the base of a FIXED_BASE gadget (jubjub.hip): the table points set time gathered for it
+extern "C" int pm_jubjub_base_from_key(pm_ctx* ctx, const pm_prover_key* pk, size_t gadget_index, pm_jubjub_base** out) {
+  if (!ctx || !pk || !out) return PM_ERR_BAD_ARG;
+  const GadgetState* gs = pk->gadgets;
+  if (!gs) return pm::set_err(ctx, PM_ERR_BAD_ARG, "the key has no gadget table (pm_plonk_key_set_gadgets first)");
+  for (const pm::GadgetRec& rec : gs->recs) {
+    if (rec.index != gadget_index) continue;
+    if (rec.kind != PM_PLONK_GADGET_FIXED_BASE)
+      return pm::set_err(ctx, PM_ERR_BAD_ARG, "gadget " + std::to_string(gadget_index) + " is not of kind PM_PLONK_GADGET_FIXED_BASE");
+    return pm::jubjub_base_from_table(ctx, at(gs->dev.tab, 2 * (size_t)rec.tab), rec.count, out);
   }
   return pm::set_err(ctx, PM_ERR_BAD_ARG, "gadget_index is not below the table's count");
 }

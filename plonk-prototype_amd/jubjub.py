@@ -1,0 +1,195 @@
+"""Native JubJub on the GPU (``pm_jubjub_*``): scalar multiplications on the embedded curve outside a
+circuit -- bulk fixed-base multiplication, two-base (Pedersen) commitments in one pass and per-point variable-base
+multiplication.
+
+A point is affine ``(x, y)``: Montgomery limbs ``[2, 4]`` (``uint64``) or a pair of Python integers; the identity is ``(0, 1)``.
+Scalars are Montgomery limb arrays (``uint64``, last axis 4: ``PM_SCALAR_MONTGOMERY``) or Python integers, which go in as
+``PM_SCALAR_CANONICAL``.  The multiplier of a point is the integer ``0 <= s < r`` itself, never reduced modulo the order of
+the subgroup.  With ``JubJubBase.from_key`` the base is the very point a key's FIXED_BASE gadget multiplies.  None of this is
+hardened against side channels.
+
+``JUBJUB_GENERATOR`` is the point with ``y = 0x12``; this repository checks that it lies on the curve and that the subgroup
+order ``JUBJUB_ORDER`` takes it to the identity.  That it is dusk-jubjub's ``GENERATOR`` is prior knowledge, not something this
+repository can verify.  No second generator is shipped: callers pass their own H."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .field import R_MOD, fr_vec_to_limbs
+from .host import Context, DeviceVector, _p
+
+#: The point with ``y = 0x12`` and the ``x`` below.  Checked in this repository (tests/test_jubjub_host.py): it lies on the
+#: curve and the subgroup order ``JUBJUB_ORDER`` takes it to the identity.  That it is dusk-jubjub's ``GENERATOR`` is prior
+#: knowledge, not something this repository can verify.  No second generator is shipped: callers pass their own H.
+JUBJUB_GENERATOR = (0x3FD2814C43AC65A6F1FBF02D0FD6CCE62E3EBB21FD6C54ED4DF7B7FFEC7BEACA, 0x12)
+JUBJUB_ORDER = 0x0E7DB4EA6533AFA906673B0101343B00A6682093CCC81082D0970E5ED6F72CB7
+
+
+def _points(x) -> np.ndarray:
+    """limbs (uint64, [..., 2, 4]) or (x, y) integer pairs -> [n, 2, 4] Montgomery limbs"""
+    if isinstance(x, np.ndarray) and x.dtype == np.uint64:
+        return np.ascontiguousarray(x).reshape(-1, 2, 4)
+    flat = [int(v) for v in np.asarray(x, dtype=object).reshape(-1)]
+    if len(flat) % 2:
+        raise ValueError("points are (x, y) pairs")
+    return fr_vec_to_limbs(flat).reshape(-1, 2, 4)
+
+
+def _scalars(x):
+    """-> ([n, 4] uint64, scalar_form): limb arrays are Montgomery elements, integers go in as they are (canonical)"""
+    if isinstance(x, np.ndarray) and x.dtype == np.uint64:
+        return np.ascontiguousarray(x).reshape(-1, 4), _lib.SCALAR_MONTGOMERY
+    vals = [int(v) for v in np.asarray(x, dtype=object).reshape(-1)]
+    if any(not 0 <= v < R_MOD for v in vals):
+        raise ValueError("a scalar is not in [0, r)")
+    buf = b"".join(v.to_bytes(32, "little") for v in vals)
+    return np.frombuffer(buf, dtype=np.uint64).reshape(-1, 4).copy(), _lib.SCALAR_CANONICAL
+
+
+def jubjub_mul_host(point, scalar) -> np.ndarray:
+    """``pm_jubjub_mul_host``: ``scalar * point`` on the CPU by double-and-add, no context -> [2, 4] limbs"""
+    p, (s, form) = _points(point), _scalars(scalar)
+    if p.shape[0] != 1 or s.shape[0] != 1:
+        raise ValueError("one point and one scalar")
+    out = np.zeros((2, 4), np.uint64)
+    if _lib.load().pm_jubjub_mul_host(_p(p), _p(s), form, _p(out)) != _lib.PM_OK:
+        raise ValueError("pm_jubjub_mul_host refused its arguments")
+    return out
+
+
+def jubjub_add_host(p, q) -> np.ndarray:
+    """``pm_jubjub_add_host``: ``p + q`` on the CPU, no context -> [2, 4] limbs"""
+    a, b = _points(p), _points(q)
+    if a.shape[0] != 1 or b.shape[0] != 1:
+        raise ValueError("one point each")
+    out = np.zeros((2, 4), np.uint64)
+    if _lib.load().pm_jubjub_add_host(_p(a), _p(b), _p(out)) != _lib.PM_OK:
+        raise ValueError("pm_jubjub_add_host refused its arguments")
+    return out
+
+
+class JubJubBase:
+    """One point B on a context's GPU with its window table (``pm_jubjub_base``): ``.point``, ``.mul(scalars)``, ``.mul_dev``."""
+
+    def __init__(self, ctx: Context, point):
+        p = _points(point)
+        if p.shape[0] != 1:
+            raise ValueError("one point")
+        h = C.c_void_p()
+        ctx._check(ctx._lib.pm_jubjub_base_create(ctx._h, _p(p), C.byref(h)))
+        self.ctx, self._h = ctx, h
+
+    @classmethod
+    def from_key(cls, pk, gadget_index: int) -> "JubJubBase":
+        """``pm_jubjub_base_from_key``: the base of gadget ``gadget_index`` of ``pk``'s gadget table (kind FIXED_BASE, its table
+        a doubling chain).  The result does not depend on the key afterwards."""
+        ctx = pk.ctx
+        h = C.c_void_p()
+        ctx._check(ctx._lib.pm_jubjub_base_from_key(ctx._h, pk._h, int(gadget_index), C.byref(h)))
+        self = object.__new__(cls)
+        self.ctx, self._h = ctx, h
+        return self
+
+    @property
+    def point(self) -> np.ndarray:
+        """[2, 4] limbs"""
+        out = np.zeros((2, 4), np.uint64)
+        self.ctx._check(self.ctx._lib.pm_jubjub_base_point(self._h, _p(out)))
+        return out
+
+    def free(self):
+        if getattr(self, "_h", None) and self.ctx._h:
+            self.ctx._lib.pm_jubjub_base_free(self.ctx._h, self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    def mul_dev(self, d_scalars: int, n: int, d_out: int, scalar_form: int = _lib.SCALAR_MONTGOMERY, stream: int = 0):
+        """``pm_jubjub_fixed_mul_dev``: n scalars at ``d_scalars`` -> n points (2 elements each) at ``d_out``; asynchronous"""
+        c = self.ctx
+        c._check(c._lib.pm_jubjub_fixed_mul_dev(c._h, self._h, C.c_void_p(d_scalars), n, scalar_form, C.c_void_p(d_out),
+                                                C.c_void_p(stream)))
+
+    def mul(self, scalars) -> np.ndarray:
+        """scalars -> [n, 2, 4] limbs of ``s_i * B``"""
+        s, form = _scalars(scalars)
+        n = s.shape[0]
+        if n == 0:
+            return np.zeros((0, 2, 4), np.uint64)
+        d, out = DeviceVector.from_host(self.ctx, s), DeviceVector(self.ctx, 2 * n)
+        try:
+            self.mul_dev(d.ptr, n, out.ptr, form)
+            return out.to_host().reshape(n, 2, 4)
+        finally:
+            d.free(), out.free()
+
+
+def jubjub_commit_dev(g: JubJubBase, h: JubJubBase, d_values: int, d_blinders: int, n: int, d_out: int,
+                      scalar_form: int = _lib.SCALAR_MONTGOMERY, stream: int = 0):
+    """``pm_jubjub_commit_dev``: ``out[i] = v_i G + b_i H``, n points (2 elements each) at ``d_out``; asynchronous"""
+    c = g.ctx
+    c._check(c._lib.pm_jubjub_commit_dev(c._h, g._h, h._h, C.c_void_p(d_values), C.c_void_p(d_blinders), n, scalar_form,
+                                         C.c_void_p(d_out), C.c_void_p(stream)))
+
+
+def jubjub_commit(g: JubJubBase, h: JubJubBase, values, blinders) -> np.ndarray:
+    """-> [n, 2, 4] limbs of ``v_i G + b_i H``; values and blinders in the same form"""
+    (v, form), (b, form_b) = _scalars(values), _scalars(blinders)
+    if form != form_b or v.shape != b.shape:
+        raise ValueError("values and blinders must have one form and one length")
+    n = v.shape[0]
+    if n == 0:
+        return np.zeros((0, 2, 4), np.uint64)
+    dv, db, out = DeviceVector.from_host(g.ctx, v), DeviceVector.from_host(g.ctx, b), DeviceVector(g.ctx, 2 * n)
+    try:
+        jubjub_commit_dev(g, h, dv.ptr, db.ptr, n, out.ptr, form)
+        return out.to_host().reshape(n, 2, 4)
+    finally:
+        dv.free(), db.free(), out.free()
+
+
+def jubjub_mul_dev(ctx: Context, d_points: int, d_scalars: int, n: int, d_out: int, scalar_form: int = _lib.SCALAR_MONTGOMERY,
+                   stream: int = 0):
+    """``pm_jubjub_mul_dev``: ``out[i] = s_i P_i``; ``d_out`` may be ``d_points``.  The points are not validated."""
+    ctx._check(ctx._lib.pm_jubjub_mul_dev(ctx._h, C.c_void_p(d_points), C.c_void_p(d_scalars), n, scalar_form, C.c_void_p(d_out),
+                                          C.c_void_p(stream)))
+
+
+def jubjub_mul(ctx: Context, points, scalars) -> np.ndarray:
+    """-> [n, 2, 4] limbs of ``s_i P_i``"""
+    p, (s, form) = _points(points), _scalars(scalars)
+    n = s.shape[0]
+    if p.shape[0] != n:
+        raise ValueError("one scalar per point")
+    if n == 0:
+        return np.zeros((0, 2, 4), np.uint64)
+    dp, ds = DeviceVector.from_host(ctx, p), DeviceVector.from_host(ctx, s)
+    try:
+        jubjub_mul_dev(ctx, dp.ptr, ds.ptr, n, dp.ptr, form)
+        return dp.to_host().reshape(n, 2, 4)
+    finally:
+        dp.free(), ds.free()
+
+
+def jubjub_check(ctx: Context, points):
+    """``pm_jubjub_check_dev``: None when every point is a canonical point of the curve, else the lowest bad index.  ``points``:
+    limbs, integer pairs or a :class:`DeviceVector` of 2 n elements."""
+    if isinstance(points, DeviceVector):
+        d, n, own = points, points.n // 2, False
+    else:
+        p = _points(points)
+        d, n, own = DeviceVector.from_host(ctx, p), p.shape[0], True
+    try:
+        bad = C.c_size_t()
+        ctx._check(ctx._lib.pm_jubjub_check_dev(ctx._h, C.c_void_p(d.ptr), n, C.byref(bad), None))
+        return None if bad.value == n else int(bad.value)
+    finally:
+        if own:
+            d.free()
