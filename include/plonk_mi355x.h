@@ -1052,6 +1052,13 @@ int pm_test_ntt_plan(uint32_t log_n, uint32_t batch, long tile_log, long max_rad
  * w in the device Montgomery form), then 20 words per step-twiddle entry.  *words = its size in 32-bit words (may be
  * NULL); up to max_words of them are copied to out. */
 int pm_test_ntt_step4_table(pm_ctx* ctx, uint32_t inverse, uint32_t S, uint32_t* out, size_t max_words, size_t* words);
+/* Pure host, no context: thread tid of a radix-4 first or single pass of even radix 2^S (4 <= S <= 10) with 2^LT columns
+ * per tile, at its step `step`, in the plane-major exchange of csrc/ntt_kernels4.hip.h (ufast: the pass writes its output
+ * u-fast, as a first pass does, which changes the thread order of the last step) -- out[12] = {0 the Stockham butterfly it owns, 1 its column, 2-5 the tile
+ * elements it writes X[0..3] to (0xFFFFFFFF at the last step), 6-9 the tile elements it reads its inputs 0..3 from
+ * (0xFFFFFFFF at step 0), 10 its step-twiddle digit k', 11 whether the step takes its twiddles from the head's scalar
+ * rows (step 1 with a wave-uniform digit)}.  PM_ERR_BAD_ARG for a shape that keeps the Stockham exchange. */
+int pm_test_ntt_exchange_map(uint32_t S, uint32_t LT, uint32_t ufast, uint32_t step, uint32_t tid, uint32_t out[12]);
 /* Pure host, no context: the geometry of pm_plonk_sigma_from_wires' sort (csrc/wire_perm.hip) -- passes =
  * max(1, ceil(bits(num_vars - 1) / 8)) 8-bit digit passes, tiles = ceil(4n / 4096) workgroups per pass, scratch_bytes = the
  * transient device memory of the call.  Each out pointer may be NULL.  The errors of pm_plonk_sigma_from_wires for n and

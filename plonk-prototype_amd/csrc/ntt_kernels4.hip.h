@@ -15,6 +15,9 @@ namespace pm {
 
 __host__ __device__ constexpr int step4_radix_log(int S, int s) { return (S - 2 * s) >= 2 ? 2 : 1; }
 __host__ __device__ constexpr int num_steps4(int S) { return (S + 1) / 2; }
+// passes of radix-4 steps only, two at least, that read the plain form (first and single passes): their exchanges are
+// plane-major (below), the others keep Stockham's slots
+__host__ __device__ constexpr bool step4_plane_major(int S, bool in_wide) { return !in_wide && S >= 4 && S % 2 == 0; }
 __host__ __device__ constexpr int step4_tw_offset(int S, int s) {
   int off = 0;
   for (int i = 0; i < s; ++i) off += ((1 << step4_radix_log(S, i)) - 1) << (2 * i);
@@ -58,10 +61,82 @@ PM_DEV Fr mul_head(const Fr& x, W4Rows rows) {
 // m = 0 multiply by w16^0 = 1 like the others: a branch around their products (fe_reduce_weak instead) measured slower,
 // every wave of the workgroup meets the same barrier.  Step 0 is never u-fast when a second step follows it (u-fast
 // belongs to a pass's last step).  Only passes that read the wide form (middle and last) take this path: the first and
-// single passes, whose step 0 follows the loads from HBM directly, measured 1 - 2 us slower per launch with it.
+// single passes, whose step 0 follows the loads from HBM directly, measured 1 - 2 us slower per launch with it; those of
+// even S apply the same products on the consumer side of a plane-major exchange (below).
 __host__ __device__ constexpr bool step4_l1_uniform(int S, int LT, bool in_wide) {
   return in_wide && num_steps4(S) >= 2 && step4_radix_log(S, 1) == 2 && (64 >> LT) <= ((1 << S) >> 4);
 }
+
+// ---- plane-major exchanges: first and single passes of even S >= 4 (radix-4 steps only) ------------------------------
+// The passes that read the wide form keep the exchange and the producer-side products above.  On this one, with
+// consumer-side products, the <10, 1> last pass lost its bank conflicts and measured 0.7 us slower per launch; with its
+// producer-side products the 2^20 step measured 0.5 us behind: those launches are bound by VALU
+// issue, not by the LDS, and the swizzles cost them instructions.
+// Thread tau = tid >> LT of column c = tid & (T - 1) owns, at step s, the butterfly g_s(tau) = tau rotated left by 2 s
+// inside its S - 2 bits: g_0 and g_last are the identity, so the HBM side of a pass is that of the Stockham map.  Its
+// twiddle digit k' = g_s(tau) & (4^s - 1) is the top 2 s bits of tau.  After step s the thread writes X[t] to plane t at
+// its own place, element t U T + tid of the tile: lane-contiguous stores, no index to compute.  Stockham puts that
+// output at logical position (h : t : k'), g_s(tau) = (h : k'); step s + 1 reads logical positions m U + u'', so the
+// reader of plane t is the thread (t : tau without the top two bits of h), whose four inputs m = 0..3 sit at its own tau
+// with m put back where those two bits were: bits p + 1, p of the place inside the plane, p = S - 4 - 2 s.  A reader's
+// lanes therefore see runs of 2^q consecutive elements, q = p + LT.  Runs under 32 elements would meet on the LDS banks, so
+// both sides of such an exchange XOR a few higher bits of the element index into its low bits (XchgSwz: bits
+// k .. k + w - 1 into bits j .. j + w - 1; disjoint fields, a bijection of the tile).  Writers stay conflict-free
+// under it, an aligned group of lanes sees the XORed bits constant.  The last step of a u-fast pass (tid = c U + tau)
+// strides its reads by 4 T elements and takes the low bits of tau into the bank bits instead.  The step-1 digit is
+// tau >> (S - 4): the same for all of a wave when its 64 >> LT values of tau fit U/4, then step 1 multiplies through the
+// head's scalar rows (step4_l1_consumer).  tests/test_ntt_plane_major.py walks these maps and a model of the banks
+// through pm_test_ntt_exchange_map.
+struct XchgSwz {
+  int k, w, j;
+};
+// swizzle of exchange x (between steps x and x + 1); ufast: the pass's OUT_UFAST, it matters for the last exchange only
+__host__ __device__ constexpr XchgSwz step4_xchg_swizzle(int S, int LT, bool ufast, int x) {
+  const int q = S - 4 - 2 * x + LT;
+  if (ufast && x == S / 2 - 2 && LT > 0) {
+    // bits from LT + 2 up are tau; with U < 32 the wave's columns vary in bits 0 .. j - 1, which stay as they are
+    const int k = LT + 2 > 4 ? LT + 2 : 4;
+    int j = 0;
+    while (((1 << (S - 2)) << j) < 32) ++j;
+    int w = 5 - j;
+    if (w > S + LT - k) w = S + LT - k;
+    if (w > LT + 2 - j) w = LT + 2 - j;
+    return XchgSwz{k, w, j};
+  }
+  if (q >= 5) return XchgSwz{0, 0, 0};
+  return XchgSwz{q + 2 > 5 ? q + 2 : 5, 5 - q < 2 ? 5 - q : 2, q};
+}
+__host__ __device__ constexpr u32 step4_swizzled(XchgSwz z, u32 e) {
+  return z.w == 0 ? e : e ^ (((e >> z.k) & ((1u << z.w) - 1u)) << z.j);
+}
+// (tau, c) of a thread at step s
+__host__ __device__ constexpr u32 step4_pm_tau(int S, int LT, bool ufast, int s, u32 tid) {
+  return ufast && s == S / 2 - 1 ? tid & ((1u << (S - 2)) - 1u) : tid >> LT;
+}
+__host__ __device__ constexpr u32 step4_pm_col(int S, int LT, bool ufast, int s, u32 tid) {
+  return ufast && s == S / 2 - 1 ? tid >> (S - 2) : tid & ((1u << LT) - 1u);
+}
+__host__ __device__ constexpr u32 step4_pm_butterfly(int S, int s, u32 tau) {
+  return ((tau << (2 * s)) & ((1u << (S - 2)) - 1u)) | (tau >> (S - 2 - 2 * s));
+}
+__host__ __device__ constexpr u32 step4_pm_digit(int S, int s, u32 tau) { return s == 0 ? 0u : tau >> (S - 2 - 2 * s); }
+// element of the tile that step s < last writes X[t] to
+__host__ __device__ constexpr u32 step4_pm_write(int S, int LT, bool ufast, int s, u32 tid, int t) {
+  return step4_swizzled(step4_xchg_swizzle(S, LT, ufast, s), ((u32)t << (S - 2 + LT)) + tid);
+}
+// element of the tile that step s > 0 reads its input m from
+__host__ __device__ constexpr u32 step4_pm_read(int S, int LT, bool ufast, int s, u32 tid, int m) {
+  const u32 tau = step4_pm_tau(S, LT, ufast, s, tid), c = step4_pm_col(S, LT, ufast, s, tid);
+  const int p = S - 2 - 2 * s;
+  const u32 lo = tau & ((1u << (S - 4)) - 1u), t = tau >> (S - 4);
+  const u32 place = ((lo >> p) << (p + 2)) | ((u32)m << p) | (lo & ((1u << p) - 1u));
+  return step4_swizzled(step4_xchg_swizzle(S, LT, ufast, s - 1), ((((t << (S - 2)) | place)) << LT) + c);
+}
+// step 1 of a plane-major pass takes its twiddles from the head's scalar rows: its digit tau >> (S - 4) is wave-uniform
+__host__ __device__ constexpr bool step4_l1_consumer(int S, int LT, bool ufast) {
+  return step4_plane_major(S, false) && (64 >> LT) <= ((1 << S) >> 4) && !(ufast && S == 4);
+}
+
 struct FrSplit2 {
   u32 l[18];
 };
@@ -106,13 +181,15 @@ PM_DEV void ntt_step4(Fr (&x)[4], const NttPassArgs& a, const NttConsts& kc, u32
   constexpr bool last = (STEP == NSTEPS - 1);
   constexpr bool ufast = OUT_UFAST && last;
   constexpr bool L1_UNIFORM = step4_l1_uniform(S, LT, IN_WIDE);
+  constexpr bool PM = step4_plane_major(S, IN_WIDE);            // plane-major exchanges: u below is tau
+  constexpr bool L1_CONSUMER = PM && step4_l1_consumer(S, LT, OUT_UFAST);
   static_assert(!(L1_UNIFORM && STEP == 0 && ufast), "the producer of the first-layer twiddles is in wave order");
   const u32 c = ufast ? tid / U : tid & (T - 1);
   const u32 u = ufast ? tid % U : tid >> LT;
   if (STEP > 0) {
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
-      const u32 e = (u + m * U) * T + c;
+      const u32 e = PM ? step4_pm_read(S, LT, OUT_UFAST, STEP, tid, m) : (u + m * U) * T + c;
       u32x4 lo = lds0[e], hi = lds1[e];
       x[m].l[0] = lo.x; x[m].l[1] = lo.y; x[m].l[2] = lo.z; x[m].l[3] = lo.w;
       x[m].l[4] = hi.x; x[m].l[5] = hi.y; x[m].l[6] = hi.z; x[m].l[7] = hi.w;
@@ -121,8 +198,19 @@ PM_DEV void ntt_step4(Fr (&x)[4], const NttPassArgs& a, const NttConsts& kc, u32
   }
   const u32x4* stw = a.step_tw + STEP4_HEAD + STEP4_ENTRY * step4_tw_offset(S, STEP);
   if constexpr (LQ == 2) {
-    const u32 kp = u & (nsp - 1);
-    if (STEP > 0 && !(L1_UNIFORM && STEP == 1)) {
+    const u32 kp = PM ? step4_pm_digit(S, STEP, u) : u & (nsp - 1);
+    if constexpr (L1_CONSUMER && STEP == 1) {
+      // k' is the wave's: X[0] (<5, <40) -> (1, <1.01), X[m] (<5, <40) times w16^(k' m) -> (1, <2) through the head's scalar
+      // rows, each product's rows through an opaque pointer of its own (see below).  The waves with k' = 0 multiply by 1.
+      const u32 ku = __builtin_amdgcn_readfirstlane(kp);
+      x[0] = fe_reduce_weak<FrP>(x[0]);
+#pragma unroll
+      for (int m = 1; m < 4; ++m) {
+        W4Rows rows = w16_rows(w4, ku * m);
+        asm volatile("" : "+s"(rows));
+        x[m] = mul_head(x[m], rows);
+      }
+    } else if (STEP > 0 && !(L1_UNIFORM && STEP == 1)) {
       x[0] = fe_reduce_weak<FrP>(x[0]);
       x[1] = mul_tw2(x[1], ld_tw2(stw, 0 * nsp + kp));
       x[2] = mul_tw2(x[2], ld_tw2(stw, 1 * nsp + kp));
@@ -151,7 +239,7 @@ PM_DEV void ntt_step4(Fr (&x)[4], const NttPassArgs& a, const NttConsts& kc, u32
       const u32 base = (u - kp) * 4 + kp;
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
-        const u32 e = (base + t * nsp) * T + c;
+        const u32 e = PM ? step4_pm_write(S, LT, OUT_UFAST, STEP, tid, t) : (base + t * nsp) * T + c;
         lds0[e] = u32x4{x[t].l[0], x[t].l[1], x[t].l[2], x[t].l[3]};
         lds1[e] = u32x4{x[t].l[4], x[t].l[5], x[t].l[6], x[t].l[7]};
         lds2[e] = x[t].l[8];

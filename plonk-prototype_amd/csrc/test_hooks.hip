@@ -10,6 +10,7 @@
 #include "ec_mul.hip.h"
 #include "fields.hip.h"
 #include "ntt_kernels.hip.h"
+#include "ntt_kernels4.hip.h"
 
 namespace pm {
 
@@ -291,5 +292,21 @@ extern "C" int pm_test_host_glv_split(const uint64_t k[4], uint64_t out[4]) {
   out[1] = h.k1[2] | (uint64_t)h.k1[3] << 32;
   out[2] = h.k2[0] | (uint64_t)h.k2[1] << 32;
   out[3] = h.k2[2] | (uint64_t)h.k2[3] << 32;
+  return PM_OK;
+}
+
+// the plane-major exchange of the radix-4 first and single pass kernels, from the constexpr maps the kernels themselves index with
+extern "C" int pm_test_ntt_exchange_map(uint32_t S, uint32_t LT, uint32_t ufast, uint32_t step, uint32_t tid, uint32_t out[12]) {
+  if (!out || S > 10 || LT > 6 || ufast > 1 || !step4_plane_major((int)S, false)) return PM_ERR_BAD_ARG;
+  const int s = (int)step, last = (int)S / 2 - 1, si = (int)S, lt = (int)LT;
+  if (s > last || tid >= (1u << (S - 2 + LT))) return PM_ERR_BAD_ARG;
+  const bool uf = ufast != 0;
+  const u32 tau = step4_pm_tau(si, lt, uf, s, tid);
+  out[0] = step4_pm_butterfly(si, s, tau);
+  out[1] = step4_pm_col(si, lt, uf, s, tid);
+  for (int t = 0; t < 4; ++t) out[2 + t] = s < last ? step4_pm_write(si, lt, uf, s, tid, t) : 0xFFFFFFFFu;
+  for (int m = 0; m < 4; ++m) out[6 + m] = s > 0 ? step4_pm_read(si, lt, uf, s, tid, m) : 0xFFFFFFFFu;
+  out[10] = step4_pm_digit(si, s, tau);
+  out[11] = s == 1 && step4_l1_consumer(si, lt, uf) ? 1u : 0u;
   return PM_OK;
 }
