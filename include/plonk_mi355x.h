@@ -1009,8 +1009,9 @@ int pm_test_field_op(pm_ctx* ctx, int op, const uint64_t* a, const uint64_t* b, 
  * saturated words out, then zeros), 13 fe_pow2 (limb 0 selects the exponent: 0 = W N, 1 = 2 W N - 32 NS, 2 = 64 NS + W N)
  * (1 -> 1 each), 14 fe_mul_split<5,6> (x, 2 rows: 3 -> 1), 15 fe_mul_split<1,2> (x, 9 rows: 10 -> 1) (Fr), 16
  * fp_is_zero_product, 17 fp_is_zero_lazy (1 -> 1, 0 / 1 in limb 0) (Fp), 18 dft8 (x[0..7], w1, w2, w3: 11 -> 8), 19 dft4
- * (a0..a3, w4: 5 -> 4) (Fr), 32 + K fe_sub<K,1> (2 -> 1) for the K the library instantiates (Fr 2, 3, 5, 9; Fp 2, 3, 5, 6, 8,
- * 11).  PM_ERR_BAD_ARG for any other (field, op).  Host pointers, n cases. */
+ * (a0..a3, w4: 5 -> 4) (Fr), 20 fe_canon_limbs, 21 fe_inv_int, 22 fe_inv_dev (csrc/field_inv.hip.h; 1 -> 1; cases 64 k ..
+ * 64 k + 63 share a wave, whose vote ends the rounds of fe_inv_int), 32 + K fe_sub<K,1> (2 -> 1) for the K the library
+ * instantiates (Fr 2, 3, 5, 9; Fp 2, 3, 5, 6, 8, 11).  PM_ERR_BAD_ARG for any other (field, op).  Host pointers, n cases. */
 int pm_test_field_raw_op(pm_ctx* ctx, int field, int op, const uint32_t* in, uint32_t* out, size_t n);
 /* The XYZZ group law of csrc/ec.hip.h on raw limbs.  A point is 57 words: X, Y, ZZ, ZZZ (14 Fp limbs each), infinity flag.
  * op 0 = xyzz_double_affine (X, Y of a), 1 = xyzz_double, 2 = xyzz_madd (X, Y of b: the affine operand), 3 = xyzz_add, 4 =

@@ -1,5 +1,6 @@
-"""Limb-exact big-integer model of the device field arithmetic (csrc/fields.hip.h), of the butterfly networks built on
-it (dft8 / dft4, csrc/ntt_kernels.hip.h) and of the XYZZ group law (csrc/ec.hip.h) -- plain Python, no GPU, no library.
+"""Limb-exact big-integer model of the device field arithmetic (csrc/fields.hip.h), of the binary-GCD inversion
+(csrc/field_inv.hip.h), of the butterfly networks built on it (dft8 / dft4, csrc/ntt_kernels.hip.h) and of the XYZZ group
+law (csrc/ec.hip.h) -- plain Python, no GPU, no library.
 
 Every routine walks the device code limb for limb: the same 32-bit limb sums, the same 64-bit column accumulators, the
 same digits and shifts, for both parameter sets (FR: W = 29, N = 9; FP: W = 28, N = 14).  Python integers do not wrap, so
@@ -65,6 +66,22 @@ def _u64(x, what):
     if not 0 <= x <= M64:
         flag(f"u64 wrap in {what}: {x:#x}")
     return x & M64
+
+
+def _i32(x, what):
+    """an int32_t value: wraps to two's complement"""
+    if not -(1 << 31) <= x < 1 << 31:
+        flag(f"i32 wrap in {what}: {x:#x}")
+        return ((x + (1 << 31)) & M32) - (1 << 31)
+    return x
+
+
+def _i64(x, what):
+    """a long long value"""
+    if not -(1 << 63) <= x < 1 << 63:
+        flag(f"i64 wrap in {what}: {x:#x}")
+        return ((x + (1 << 63)) & M64) - (1 << 63)
+    return x
 
 
 def in_class(f, x, Bl, V, plus=False):
@@ -433,6 +450,173 @@ def fe_canon_pack(f, a):
     return s
 
 
+# ------------------------------------------------------------------ inversion (csrc/field_inv.hip.h)
+def fr_shl5(t):
+    """poly_common.hip.h: value * 2^5 of a normalised Fr value < 2r -> limbs normalised, value < 64 r"""
+    f = FR
+    expect(f, t, 1, 2, False, "fr_shl5 in")
+    r = [(t[0] << 5) & f.MASK]
+    for i in range(1, 8):
+        r.append(((t[i] << 5) & f.MASK) | (t[i - 1] >> 24))
+    r.append(_u32(t[8] << 5, "fr_shl5 top") | (t[7] >> 24))
+    if value_of(f, r) != value_of(f, t) << 5:
+        flag("fr_shl5 result: value")
+    return r
+
+
+def canon_limb_max(f):
+    """the largest limb fe_canon_limbs / fe_canon_pack admit: a carry < 2^(32-W) on top of it still fits 32 bits"""
+    return M32 - f.SLACK
+
+
+def fe_canon_limbs(f, a):
+    """value < 2m, limbs < 2^32 - 2^(32-W) (the carry of fe_norm_full must fit) -> the canonical representative, limbs < 2^W"""
+    N, W = f.N, f.W
+    if value_of(f, a) >= 2 * f.mod:
+        flag("fe_canon_limbs precondition: value >= 2m")
+    if any(not 0 <= v <= canon_limb_max(f) for v in a):
+        flag(f"fe_canon_limbs precondition: limb {max(a):#x} >= 2^32 - 2^(32-W)")
+    x = fe_norm_full(f, a)
+    d, c = [], 0
+    for i in range(N - 1):
+        t = _i32(_i32(x[i], "fe_canon_limbs limb as int32") - f.M[i] + c, "fe_canon_limbs borrow chain")
+        d.append(t & f.MASK)
+        c = t >> W                                                   # arithmetic shift: 0 or -1
+    top = _i32(_i32(x[N - 1], "fe_canon_limbs top limb as int32") - f.M[N - 1] + c, "fe_canon_limbs top")
+    d.append(top & M32)
+    r = x if top < 0 else d
+    if r != limbs_of(f, value_of(f, a) % f.mod):
+        flag("fe_canon_limbs result: not canonical")
+    return r
+
+
+def inv_rounds(f):
+    """ROUNDS = ceil((2 bits(m) - 1) / W)"""
+    return (2 * f.mod.bit_length() - 1 + f.W - 1) // f.W
+
+
+def _signed_value(f, l):
+    return sum(x << (f.W * i) for i, x in enumerate(l))             # the top limb carries the sign
+
+
+def fe_inv_int(f, y, trace=None):
+    """y canonical limbs -> v >= 0 with v y = 1 (mod m) as plain integers, limbs < 2^W, value < 64 m; 0 -> 0.
+
+    The lane runs until its own a is zero: a further round leaves b and v limb for limb as they are (the low limb of 2^W v is
+    zero, so the multiple of m that clears it is zero), hence the device result does not depend on when the wave's vote lets
+    the lane go.  trace, a dict, receives "rounds" (rounds run with a != 0), "v_rounds" (the last round that changed v: the
+    round in which a = b = 1 turns a into 0 does not), "steps" (per round: a row negated, b row negated, exact path taken) and
+    "max_u", "max_v" (the largest |u|, |v| after any round, as integers: divide by f.mod)."""
+    N, W, MASK = f.N, f.W, f.MASK
+    S = 64 - 2 * W
+    assert N >= 3 and W <= 30 and S >= 2
+    expect(f, y, 1, 1, False, "fe_inv_int in (canonical limbs)")
+    a, b = list(y), list(f.M)
+    u, v = [1] + [0] * (N - 1), [0] * N
+    rounds, v_rounds, steps, max_u, max_v = 0, 0, [], 1, 0
+    for _ in range(inv_rounds(f)):
+        if not any(a):
+            break
+        rounds += 1
+        # ---- approximations: low W bits | top W + 2 bits of max(a, b)
+        a2 = a1 = a0 = b2 = b1 = b0 = 0
+        found = False
+        for i in range(N - 1, 1, -1):
+            nz = (a[i] | b[i]) != 0
+            if nz and not found:
+                a2, a1, a0, b2, b1, b0 = a[i], a[i - 1], a[i - 2], b[i], b[i - 1], b[i - 2]
+            found = found or nz
+        above = 0
+        for i in range(3, N):
+            above |= a[i] | b[i]
+        exact = above == 0 and (a[2] | b[2]) < 4
+        xa = _u64(a2 << (W + S), "fe_inv_int xa") | _u64(a1 << S, "fe_inv_int xa") | (a0 >> (W - S))
+        xb = _u64(b2 << (W + S), "fe_inv_int xb") | _u64(b1 << S, "fe_inv_int xb") | (b0 >> (W - S))
+        lz = 64 - (xa | xb | 1).bit_length()
+        ah = (_u64(xa << lz, "fe_inv_int lz shift") >> (64 - (W + 2)) << W) | a[0]
+        bh = (_u64(xb << lz, "fe_inv_int lz shift") >> (64 - (W + 2)) << W) | b[0]
+        if exact:
+            ah = a[0] | (a[1] << W) | ((a[2] & 3) << (2 * W))
+            bh = b[0] | (b[1] << W) | ((b[2] & 3) << (2 * W))
+        # ---- W binary-GCD steps on the approximations
+        f0, g0, f1, g1 = 1, 0, 0, 1
+        for _i in range(W):
+            odd = ah & 1
+            if odd and ah < bh:
+                ah, bh, f0, f1, g0, g1 = bh, ah, f1, f0, g1, g0
+            if odd:
+                ah = _u64(ah - bh, "fe_inv_int step difference")
+                f0 = _i32(f0 - f1, "fe_inv_int f0")
+                g0 = _i32(g0 - g1, "fe_inv_int g0")
+            ah >>= 1
+            f1 = _i32(f1 << 1, "fe_inv_int f1")
+            g1 = _i32(g1 << 1, "fe_inv_int g1")
+        # ---- (a, b) <- (f0 a + g0 b, f1 a + g1 b) / 2^W
+        na, nb, ca, cb = [0] * N, [0] * N, 0, 0
+        for i in range(N):
+            ca = _i64(ca + _i64(f0 * a[i], "fe_inv_int ca") + _i64(g0 * b[i], "fe_inv_int ca"), "fe_inv_int ca")
+            cb = _i64(cb + _i64(f1 * a[i], "fe_inv_int cb") + _i64(g1 * b[i], "fe_inv_int cb"), "fe_inv_int cb")
+            if i > 0:
+                na[i - 1], nb[i - 1] = ca & MASK, cb & MASK
+            elif (ca | cb) & MASK:
+                flag("fe_inv_int: the low limb of a row of (a, b) is not zero")
+            ca >>= W
+            cb >>= W
+        na[N - 1] = _i32(ca, "fe_inv_int ca top") & M32
+        nb[N - 1] = _i32(cb, "fe_inv_int cb top") & M32
+        sa, sb = ca < 0, cb < 0
+        ma, mb = (M32 if sa else 0), (M32 if sb else 0)
+        cya, cyb = int(sa), int(sb)
+        for i in range(N - 1):
+            ta, tb = ((na[i] ^ ma) & MASK) + cya, ((nb[i] ^ mb) & MASK) + cyb
+            a[i], b[i] = ta & MASK, tb & MASK
+            cya, cyb = ta >> W, tb >> W
+        a[N - 1] = _u32((na[N - 1] ^ ma) + cya, "fe_inv_int a top")
+        b[N - 1] = _u32((nb[N - 1] ^ mb) + cyb, "fe_inv_int b top")
+        if sa:
+            f0, g0 = _i32(-f0, "fe_inv_int -f0"), _i32(-g0, "fe_inv_int -g0")
+        if sb:
+            f1, g1 = _i32(-f1, "fe_inv_int -f1"), _i32(-g1, "fe_inv_int -g1")
+        # ---- (u, v) <- (f0 u + g0 v, f1 u + g1 v) / 2^W mod m; the digits are computed modulo 2^32 by design
+        lu, lv = (f0 * u[0] + g0 * v[0]) & MASK, (f1 * u[0] + g1 * v[0]) & MASK
+        qu, qv = (lu * f.NINV) & MASK, (lv * f.NINV) & MASK
+        nu, nv, cu, cv = [0] * N, [0] * N, 0, 0
+        for i in range(N):
+            cu = _i64(cu + _i64(f0 * u[i], "fe_inv_int cu") + _i64(g0 * v[i], "fe_inv_int cu") + qu * f.M[i], "fe_inv_int cu")
+            cv = _i64(cv + _i64(f1 * u[i], "fe_inv_int cv") + _i64(g1 * v[i], "fe_inv_int cv") + qv * f.M[i], "fe_inv_int cv")
+            if i > 0:
+                nu[i - 1], nv[i - 1] = cu & MASK, cv & MASK
+            elif (cu | cv) & MASK:
+                flag("fe_inv_int: the low limb of a row of (u, v) is not zero")
+            cu >>= W
+            cv >>= W
+        nu[N - 1] = _i32(cu, "fe_inv_int u top")
+        nv[N - 1] = _i32(cv, "fe_inv_int v top")
+        if nv != v:
+            v_rounds = rounds
+        u, v = nu, nv
+        steps.append((sa, sb, exact))
+        max_u, max_v = max(max_u, abs(_signed_value(f, u))), max(max_v, abs(_signed_value(f, v)))
+    if trace is not None:
+        trace.update(rounds=rounds, v_rounds=v_rounds, steps=steps, max_u=max_u, max_v=max_v)
+    # ---- |v| < 32 m: add 32 m and carry
+    if abs(_signed_value(f, v)) >= 32 * f.mod:
+        flag(f"fe_inv_int: |v| / m = {abs(_signed_value(f, v)) / f.mod:.3f}, not below 32")
+    k32 = k_mod(f, 32)
+    r = [_u32(v[i] + k32[i], "fe_inv_int v + 32 m") for i in range(N - 1)]
+    top = v[N - 1] + k32[N - 1]
+    if not 0 <= top <= M32:
+        flag(f"fe_inv_int: top limb of v + 32 m out of u32: {top:#x}")
+    r.append(top & M32)
+    return expect(f, fe_norm_full(f, r), 1, 64, False, "fe_inv_int out")
+
+
+def fe_inv_dev(f, x):
+    """x in the device Montgomery form (any representative < 2 m of fe_canon_limbs' class) -> 1 / x in the same form, in
+    fe_mul's result class; 0 -> 0"""
+    return fe_mul(f, fe_inv_int(f, fe_canon_limbs(f, x)), fe_pow2(f, 3 * f.W * f.N))
+
+
 # ------------------------------------------------------------------ butterflies (csrc/ntt_kernels.hip.h)
 def bfly(K, a, b, what="BFLY"):
     """(x, y) <- (x + y, x - y + K r);  y limbs <= 2^30 - 2, y value < (K - 1) r"""
@@ -647,9 +831,11 @@ def to_affine(p):
 
 
 # ------------------------------------------------------------------ class generator
-def most_redundant(f, v, Bl, plus=False):
-    """limbs of v with 2^W pushed down from limb i+1 to limb i while the class (limbs < Bl 2^W (+ slack)) allows it"""
-    top = Bl * (1 << f.W) + (f.SLACK if plus else 0) - 1
+def most_redundant(f, v, Bl, plus=False, top=None):
+    """limbs of v with 2^W pushed down from limb i+1 to limb i while the class (limbs < Bl 2^W (+ slack), or limbs <= top
+    where a class is not of that shape) allows it"""
+    if top is None:
+        top = Bl * (1 << f.W) + (f.SLACK if plus else 0) - 1
     l = limbs_of(f, v)
     for i in range(f.N - 2, -1, -1):
         k = min(l[i + 1], (top - l[i]) >> f.W)

@@ -9,6 +9,12 @@
 //
 // Invariants (integers, y the input): a = y u, b = y v (mod m); start a = y, b = m, u = 1, v = 0; after all rounds
 // a = 0, b = gcd = 1 and v = 1 / y; y = 0 gives v = 0 ("zeros stay zero", util::batch_inversion).
+//
+// Tests: oracle/fe_model.py walks fe_canon_limbs, fe_inv_int and fe_inv_dev limb for limb and records every int32 / int64
+// wrap (tests/test_fe_inv_model.py, no GPU; largest |u|, |v| seen there: 4.09 m / 4.52 m against the 32 m the last step
+// allows); tests/inv_cases.py lists the integers y that reach every round count up to ROUNDS, the exact path and the sign
+// repair of either row; tests/test_gpu_field_inv.py runs them through the raw hooks of test_hooks.hip (model parity limb for
+// limb, every case in four different wave companies) and through the production kernels with y chosen.
 #pragma once
 #include "fields.hip.h"
 
@@ -25,7 +31,10 @@ struct InvParams<FpP> {
   static constexpr int BITS = 381;
 };
 
-// value < 2 m, any limbs < 2^32 -> the canonical representative, every limb < 2^W
+// value < 2 m, limbs < 2^32 - 2^(32-W) (fe_canon_pack's class: the sequential carry of fe_norm_full, < 2^(32-W), must fit on
+// top of a limb -- Fr limbs {2^29, 2^32 - 1, 0, ...} wrap) -> the canonical representative, every limb < 2^W.  Every call site
+// hands over a product (fe_mul: limbs < 2^W, value < 2 m), fe_one or a weak reduction (normalised, < m + m / 2^16), all well
+// inside (walked in tests/test_fe_inv_model.py).
 template <class P>
 PM_DEV Fe<P> fe_canon_limbs(const Fe<P>& a) {
   constexpr int N = P::N, W = P::W;
@@ -68,11 +77,12 @@ PM_DEV Fe<P> fe_inv_int(const Fe<P>& y) {
     v[i] = 0;
   }
   for (int round = 0; round < ROUNDS; ++round) {
-    // ---- a == 0 in every lane of the wave: the remaining rounds only multiply b's row of the matrix by 2^W and divide
-    // it out again (b and v keep their values, v up to a multiple of m), so the wave leaves together.  ROUNDS covers the
-    // worst case (2 bits(m) - 1 steps); random inputs need ~1.41 bits(m) steps (Fr: 13 of the 18 rounds, r06).  The vote
-    // is wave-uniform: no divergence, and the result does not depend on which lanes share the wave (the skipped rounds
-    // change the representative of v, not its class; callers reduce it)
+    // ---- a == 0 in every lane of the wave: the wave leaves together.  ROUNDS covers the worst case (2 bits(m) - 1 steps);
+    // random inputs need ~1.41 bits(m) steps (Fr: 13 of the 18 rounds, r06).  The vote is wave-uniform: no divergence, and the
+    // result does not depend on which lanes share the wave, LIMB FOR LIMB -- a round run with a == 0 leaves b and v exactly
+    // as they are: ah = 0, so no step is odd and the matrix is (1, 0; 0, 2^W), b <- 2^W b / 2^W; and the low limb of
+    // 2^W v is zero, so qv = 0, no multiple of m is added and v <- 2^W v / 2^W.  (u does change; it is not used.)
+    // tests/test_gpu_field_inv.py runs every case in waves that leave early, late and at ROUNDS and compares raw limbs
     {
       u32 any_a = 0;
 #pragma unroll

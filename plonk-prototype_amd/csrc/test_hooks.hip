@@ -1,13 +1,17 @@
-// Raw-limb test hooks: the shared inline routines of fields.hip.h, ec.hip.h and ntt_kernels.hip.h, called as they are,
-// on operands given as radix-2^W limbs (no fe_unpack, no reduction) and with the result limbs returned as they come
-// (no fe_canon_pack).  One thread per case, one launch per call.  The tests (tests/test_gpu_field_bounds.py,
+// Raw-limb test hooks: the shared inline routines of fields.hip.h, field_inv.hip.h, ec.hip.h and ntt_kernels.hip.h, called
+// as they are, on operands given as radix-2^W limbs (no fe_unpack, no reduction) and with the result limbs returned as they
+// come (no fe_canon_pack).  One thread per case, one launch per call.  The tests (tests/test_gpu_field_bounds.py,
 // tests/test_gpu_g1_bounds.py) feed them the worst members of the operand classes the call sites document and compare
 // limb for limb with the big-integer model (oracle/fe_model.py).  What they check is the arithmetic and the bounds of
 // the routines; the code the compiler generates for a production kernel that inlines them is a different instance.
+// The inversion routines (fe_canon_limbs, fe_inv_int, fe_inv_dev) have a kernel of their own, raw_inv_kernel: fe_inv_int votes
+// across the wave, and tests/test_gpu_field_inv.py chooses the integers the binary GCD iterates on and the company a case keeps
+// in its wave.
 #include <hip/hip_runtime.h>
 
 #include "context.h"
 #include "ec_mul.hip.h"
+#include "field_inv.hip.h"
 #include "fields.hip.h"
 #include "ntt_kernels.hip.h"
 #include "ntt_kernels4.hip.h"
@@ -17,7 +21,7 @@ namespace pm {
 enum RawOp {
   RAW_ADD = 0, RAW_NORM, RAW_NORM_FULL, RAW_MUL, RAW_SQR, RAW_MUL_LIMB, RAW_MUL2, RAW_MUL3, RAW_MMA2, RAW_SQR2,
   RAW_REDUCE_WEAK, RAW_UNPACK, RAW_CANON_PACK, RAW_POW2, RAW_SPLIT_5_6, RAW_SPLIT_1_2, RAW_ZERO_PRODUCT, RAW_ZERO_LAZY,
-  RAW_DFT8, RAW_DFT4, RAW_SUB = 32   // RAW_SUB + K: fe_sub<K, 1>
+  RAW_DFT8, RAW_DFT4, RAW_CANON_LIMBS, RAW_INV_INT, RAW_INV_DEV, RAW_SUB = 32   // RAW_SUB + K: fe_sub<K, 1>
 };
 
 __host__ __device__ constexpr int raw_in(int op) {
@@ -93,6 +97,23 @@ __global__ void raw_op_kernel(const u32* in, u32* out, size_t n) {
   if constexpr (OP >= RAW_SUB) r[0] = fe_sub<P, OP - RAW_SUB, 1>(x[0], x[1]);
 #pragma unroll
   for (int e = 0; e < NO; ++e) st_raw<P>(d + e * N, r[e]);
+}
+
+// ---- inversion (field_inv.hip.h), one operand in, one result out.  The kernel has the shape of the production call sites:
+// fe_inv_int leaves its loop through a wave-wide vote, so every lane of every wave has to reach it -- a lane past n works on
+// element n - 1 and stores nothing.  A block is 64 threads, ONE wave: cases 64 k .. 64 k + 63 share a wave and its vote.  The
+// tests rely on that; they place a case in the company they want by ordering the inputs.
+template <class P, int OP>
+__global__ void __launch_bounds__(64) raw_inv_kernel(const u32* in, u32* out, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = i < n;
+  const Fe<P> x = ld_raw<P>(in + (live ? i : n - 1) * (size_t)P::N);
+  Fe<P> r;
+  if constexpr (OP == RAW_CANON_LIMBS) r = fe_canon_limbs<P>(x);
+  if constexpr (OP == RAW_INV_INT) r = fe_inv_int<P>(x);
+  if constexpr (OP == RAW_INV_DEV) r = fe_inv_dev<P>(x);
+  if (!live) return;
+  st_raw<P>(out + i * (size_t)P::N, r);
 }
 
 // ---- group law: a point is 57 words, X | Y | ZZ | ZZZ (14 limbs each) | infinity flag
@@ -191,6 +212,10 @@ static bool launch_raw(int op, dim3 g, dim3 blk, hipStream_t st, const u32* in, 
     switch (op) { RAW_CASE(RAW_ZERO_PRODUCT) RAW_CASE(RAW_ZERO_LAZY) RAW_CASE(RAW_SUB + 6) RAW_CASE(RAW_SUB + 8) RAW_CASE(RAW_SUB + 11) }
   }
 #undef RAW_CASE
+#define RAW_INV_CASE(OP) \
+  case OP: hipLaunchKernelGGL((raw_inv_kernel<P, OP>), g, blk, 0, st, in, out, n); return true;
+  switch (op) { RAW_INV_CASE(RAW_CANON_LIMBS) RAW_INV_CASE(RAW_INV_INT) RAW_INV_CASE(RAW_INV_DEV) }
+#undef RAW_INV_CASE
   return false;
 }
 
@@ -201,12 +226,12 @@ using namespace pm;
 extern "C" int pm_test_field_raw_op(pm_ctx* ctx, int field, int op, const uint32_t* in, uint32_t* out, size_t n) {
   if (!ctx || !in || !out || field < 0 || field > 1 || op < 0 || op > RAW_SUB + 11) return PM_ERR_BAD_ARG;
   const bool fr = field == 0;
-  {   // the (field, op) pairs that exist: every fe_sub<K, 1> the library instantiates, the split product and the butterflies for Fr, the zero tests for Fp
+  {   // the (field, op) pairs that exist: every fe_sub<K, 1> the library instantiates, the split product and the butterflies for Fr, the zero tests for Fp, the inversion routines for both
     const int k = op - RAW_SUB;
     const bool sub_ok = k == 2 || k == 3 || k == 5 || (fr ? k == 9 : (k == 6 || k == 8 || k == 11));
     const bool fr_only = op == RAW_SPLIT_5_6 || op == RAW_SPLIT_1_2 || op == RAW_DFT8 || op == RAW_DFT4;
     const bool fp_only = op == RAW_ZERO_PRODUCT || op == RAW_ZERO_LAZY;
-    if (op >= RAW_SUB ? !sub_ok : (op > RAW_DFT4 || (fr_only && !fr) || (fp_only && fr))) return PM_ERR_BAD_ARG;
+    if (op >= RAW_SUB ? !sub_ok : (op > RAW_INV_DEV || (fr_only && !fr) || (fp_only && fr))) return PM_ERR_BAD_ARG;
   }
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (n == 0) return PM_OK;
@@ -217,7 +242,7 @@ extern "C" int pm_test_field_raw_op(pm_ctx* ctx, int field, int op, const uint32
   PM_HIP(ctx, hipMalloc(&tmp.p[0], in_bytes));
   PM_HIP(ctx, hipMalloc(&tmp.p[1], out_bytes));
   PM_HIP(ctx, hipMemcpyAsync(tmp.p[0], in, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-  dim3 g((unsigned)((n + 63) / 64)), blk(64);
+  dim3 g((unsigned)((n + 63) / 64)), blk(64);   // 64: raw_inv_kernel's waves are its blocks
   const u32* din = (const u32*)tmp.p[0];
   u32* dout = (u32*)tmp.p[1];
   const bool ok = fr ? launch_raw<FrP>(op, g, blk, ctx->stream, din, dout, n) : launch_raw<FpP>(op, g, blk, ctx->stream, din, dout, n);

@@ -31,7 +31,12 @@ def test_mul_add_sub(ctx, oracle, field):
 @pytest.mark.parametrize("field", ["fr", "fp"])
 def test_inverse(ctx, oracle, field):
     """The binary-GCD inversion of csrc/field_inv.hip.h against pow(x, -1, m): edge values (0 stays 0, 1, m - 1, powers of
-    two, small numbers whose approximations are exact from the first round on) and random ones."""
+    two, small numbers) and random ones, handed over in the Montgomery form.  The integer the GCD iterates on is therefore
+    x * 2^256 mod r (Fr) / x * 2^384 mod p (Fp), a full-width number with nothing special about it even for x = 1 or 2^k
+    (and no non-zero input takes the exact path in its first round at all: b starts as the modulus).  The second part hands
+    the small numbers and the powers of two over as the raw ABI limbs, so that the GCD iterates on THEM; what comes back
+    is then y^-1 * 2^(64 NS) mod m as a raw integer (api.hip, field_op_kernel).  tests/test_gpu_field_inv.py does this for
+    lists that reach every round count and both sign repairs."""
     mod, nl, op = (B.R_MOD, 4, 6) if field == "fr" else (B.P_MOD, 6, 7)
     rng = B.sample_fr(5 if field == "fr" else 6, 3000)
     vals = [v * 0x9E3779B97F4A7C15 % mod for v in rng] if field == "fp" else rng
@@ -41,6 +46,11 @@ def test_inverse(ctx, oracle, field):
     am = to_mont(ints_to_limbs(a, nl))
     got = limbs_to_ints(from_mont(ctx.field_op(op, am, am)))
     assert got == [pow(x, -1, mod) if x else 0 for x in a], field
+    ys = list(range(40)) + [1 << k for k in range(mod.bit_length())]
+    k2 = pow(2, 64 * 2 * nl, mod)                                    # R^2, R = 2^(32 NS)
+    yl = ints_to_limbs(ys, nl)
+    got = limbs_to_ints(ctx.field_op(op, yl, yl))
+    assert got == [pow(y, -1, mod) * k2 % mod if y else 0 for y in ys], field
 
 
 def test_inverse_ignores_b(ctx, oracle):

@@ -25,7 +25,7 @@ FIELD_ID = {"fr": 0, "fp": 1}
 FIELDS = [M.FR, M.FP]
 SUB_K = {"fr": (2, 3, 5, 9), "fp": (2, 3, 5, 6, 8, 11)}
 (ADD, NORM, NORM_FULL, MUL, SQR, MUL_LIMB, MUL2, MUL3, MMA2, SQR2, REDUCE_WEAK, UNPACK, CANON_PACK, POW2, SPLIT_5_6, SPLIT_1_2,
- ZERO_PRODUCT, ZERO_LAZY, DFT8, DFT4) = range(20)
+ ZERO_PRODUCT, ZERO_LAZY, DFT8, DFT4, CANON_LIMBS, INV_INT, INV_DEV) = range(23)   # 20 - 22: tests/test_gpu_field_inv.py
 SUB = 32
 
 
@@ -112,7 +112,7 @@ def test_sub_rejects_what_the_library_does_not_instantiate(ctx):
     from plonk_prototype_amd import _lib
     x = np.zeros((1, 2, 9), np.uint32)
     out = np.zeros((1, 1, 9), np.uint32)
-    for field, op in ((0, SUB + 4), (0, SUB + 11), (1, SUB + 9), (0, ZERO_LAZY), (1, DFT8), (1, SPLIT_5_6), (0, 20), (2, ADD)):
+    for field, op in ((0, SUB + 4), (0, SUB + 11), (1, SUB + 9), (0, ZERO_LAZY), (1, DFT8), (1, SPLIT_5_6), (0, INV_DEV + 1), (1, 31), (2, ADD)):
         rc = ctx._lib.pm_test_field_raw_op(ctx._h, field, op, x.ctypes.data_as(_lib.u32p), out.ctypes.data_as(_lib.u32p), 1)
         assert rc == _lib.PM_ERR_BAD_ARG, (field, op)
 
