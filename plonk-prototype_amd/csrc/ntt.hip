@@ -50,6 +50,7 @@ static pass_fn find_pass(int S, int LT, int role) {
 // radix-4 kernels (ntt4.hip)
 size_t pass4_lds(int S, int LT);
 unsigned pass4_threads(int S, int LT);
+bool pass4_tw_producer(int S, int LT, int role);
 int build_step4_table(pm_ctx* ctx, void** out, const NttConsts& c, unsigned S, hipStream_t st);
 size_t step4_table_bytes(unsigned S);
 
@@ -346,6 +347,7 @@ int ntt_run(pm_ctx* ctx, const void* d_in, size_t in_len, size_t in_stride, void
   unsigned log_ns = 0;
   a.wide_total = (unsigned long long)batch * n;
   a.wide_glog = plan_wide_glog(plan);
+  bool tw_applied = false;   // the previous pass ran with PASS_TW_OUT
   for (int i = 0; i < plan.npass; ++i) {
     const bool last = (i == plan.npass - 1);
     const int S = plan.S[i], LT = plan.LT[i];
@@ -368,13 +370,30 @@ int ntt_run(pm_ctx* ctx, const void* d_in, size_t in_len, size_t in_stride, void
     a.log_ns = log_ns;
     u32 post_i = last ? post : 0u;
     a.pass_tw = nullptr;
+    a.pass_tw_out = nullptr;
     u32 tw_flag = 0;
-    if (i > 0 && direct_tw) {
+    if (tw_applied) {   // the pass before this one multiplied by this pass's table
+      tw_flag = PASS_TW_APPLIED;
+    } else if (i > 0 && direct_tw) {
       void* ptw = nullptr;
       rc = get_pass_tw(ctx, dt, i, last, dir, log_n, log_ns, S, a.wide_glog, kc, st, &ptw);
       if (rc) return rc;
       a.pass_tw = ptw;
       tw_flag = PASS_DIRECT_TW;
+    }
+    // this pass applies the next one's table to its outputs where both are radix-4 kernels and its shape takes the product
+    tw_applied = false;
+    if (!last && direct_tw && ctx->opt_ntt_tw_producer && r4 && pass4_tw_producer(S, LT, role)) {
+      const bool next_last = (i + 1 == plan.npass - 1);
+      const int nS = plan.S[i + 1];
+      if (find_pass4(nS, plan.LT[i + 1], next_last ? ROLE_LAST : ROLE_MIDDLE) != nullptr) {
+        void* ptw = nullptr;
+        rc = get_pass_tw(ctx, dt, i + 1, next_last, dir, log_n, log_ns + (unsigned)S, nS, a.wide_glog, kc, st, &ptw);
+        if (rc) return rc;
+        a.pass_tw_out = ptw;
+        tw_flag |= PASS_TW_OUT;
+        tw_applied = true;
+      }
     }
     a.flags = (i == 0 ? pre : 0u) | post_i | tw_flag | (ctx->opt_ntt_xcd ? PASS_XCD_REMAP : 0u);
     const unsigned threads = r4 ? pass4_threads(S, LT) : std::max(64u, (1u << (S + LT)) / 8);

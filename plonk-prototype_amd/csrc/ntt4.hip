@@ -34,6 +34,10 @@ pass_fn find_pass4(int S, int LT, int role) {
     if (e.S == S && e.LT == LT && e.role == role) return e.fn;
   return nullptr;
 }
+// does the first (role 1) or middle (role 2) pass of this shape apply the next pass's twiddles when asked (PASS_TW_OUT)
+bool pass4_tw_producer(int S, int LT, int role) {
+  return (role == 1 || role == 2) && find_pass4(S, LT, role) != nullptr && step4_tw_producer(S, LT, role == 1, role == 2);
+}
 size_t pass4_lds(int S, int LT) { return pass4_lds_bytes(S, LT); }
 unsigned pass4_threads(int S, int LT) { return std::max(64u, (1u << (S + LT)) / 4); }
 

@@ -44,6 +44,7 @@ struct NttPassArgs {
   const u32x4* cs_hi;     // coset powers g^(x << lh) (fwd) or g^-(x << lh) (inv)
   const u32x4* cs_lo;     // g^x / g^-x           x < 1 << lh
   const void* pass_tw;    // PASS_DIRECT_TW: this pass's input twiddles as wide planes, element order
+  const void* pass_tw_out;  // PASS_TW_OUT: the next pass's table (its pass_tw), applied to this pass's outputs
   unsigned long long batch_stride_in;   // elements between batch vectors (canonical side)
   unsigned long long batch_stride_out;
   unsigned long long wide_total;        // elements in one wide buffer (batch * N)
@@ -61,6 +62,8 @@ enum : u32 {
                          // folded into the last pass's twiddle table)
   PASS_POST_COSET = 8u,  // multiply output i by cs_hi/lo (coset_ifft)
   PASS_XCD_REMAP = 16u,  // blockIdx -> tile so that each XCD walks a contiguous range of tiles
+  PASS_TW_OUT = 32u,     // the last step multiplies output idx by pass_tw_out[idx] (radix-4 family, wide output)
+  PASS_TW_APPLIED = 64u, // the wide input carries its inter-pass twiddle already: its producer ran with PASS_TW_OUT
 };
 
 // Workgroups are dealt round-robin over the 8 XCDs (blocks b and b+8 share an L2).  Giving XCD x

@@ -137,6 +137,32 @@ __host__ __device__ constexpr bool step4_l1_consumer(int S, int LT, bool ufast) 
   return step4_plane_major(S, false) && (64 >> LT) <= ((1 << S) >> 4) && !(ufast && S == 4);
 }
 
+// step s of a pass multiplies by per-lane table twiddles (vector loads) in a radix-4 step
+__host__ __device__ constexpr bool step4_generic(int S, int LT, bool ufast, bool in_wide, int s) {
+  return s > 0 && step4_radix_log(S, s) == 2 &&
+         !(s == 1 && (step4_l1_uniform(S, LT, in_wide) || (step4_plane_major(S, in_wide) && step4_l1_consumer(S, LT, ufast))));
+}
+
+// Inter-pass twiddles applied by their producer (PASS_TW_OUT).  The pass that follows a wide store multiplies element idx
+// by its table entry pass_tw[idx] before its first butterfly, so it cannot issue anything before both 36 B loads are back,
+// and every workgroup of the launch is in that state at once.  The pass that writes element idx does the product
+// instead, X[m] (<5, <40) times a canonical entry -> (1, <2) just before st_wide: the class the consumer's own product
+// hands dft4s, and the consumer (PASS_TW_APPLIED) takes what it loads as it is.  The table, its layout and n^-1 folded into
+// the last pass's table are unchanged; the multiply-adds only move from one launch to the one before.
+// Where the producer issues the four loads decides whether it pays: vector loads return in order, so
+// a step-twiddle load issued behind them waits for HBM with them, in every workgroup at once.  They go two and two behind
+// the last twiddle load of the second-to-last and of the last step, each pair with that step's third product and dft4s in
+// front of the next load.  All four ahead of the last exchange's barrier made the 2^20 step 5 us slower than consumer-side
+// products.  The placement needs the last two steps to be radix-4 steps with table twiddles (even S >= 8).  Of those
+// shapes the first passes of radix 2^10 are the producers: with them the 2^20 step is 2.7 - 3.6 us faster.  The radix-2^8 shapes
+// keep the consumer side: as producers (first and middle pass of 2^24, first pass of 2^22) they measured no difference,
+// the first pass paid what the last one gained (profiles/tw_producer_full_ab.txt), and the <8, 3> middle pass would need 130
+// VGPRs.  A middle pass of radix 2^10 occurs in no plan that has direct tables.  ntt_run() asks through pass4_tw_producer().
+__host__ __device__ constexpr bool step4_tw_producer(int S, int LT, bool ufast, bool in_wide) {
+  return S == 10 && !in_wide && step4_generic(S, LT, ufast, in_wide, num_steps4(S) - 2) &&
+         step4_generic(S, LT, ufast, in_wide, num_steps4(S) - 1);
+}
+
 struct FrSplit2 {
   u32 l[18];
 };
@@ -169,9 +195,22 @@ PM_DEV void dft4s(Fr& a0, Fr& a1, Fr& a2, Fr& a3, W4Rows w4) {
   a2 = t;
 }
 
+// element of the output vector (batch offset apart) that the last step of a pass stores its x[m] to
+template <int S, int LT, bool OUT_UFAST>
+PM_DEV size_t pass4_out_index(const NttPassArgs& a, u32 tid, size_t j0, int m) {
+  constexpr int R = 1 << S;
+  constexpr int U = R / 4;
+  const u32 c = OUT_UFAST ? tid / U : tid & ((1u << LT) - 1u);
+  const u32 u = OUT_UFAST ? tid % U : tid >> LT;
+  const size_t j = j0 + c;
+  const size_t ns = (size_t)1 << a.log_ns;
+  const size_t k = j & (ns - 1);
+  return (j - k) * R + k + (size_t)(u + m * U) * ns;
+}
+
 template <int S, int LT, int STEP, bool OUT_UFAST, bool IN_WIDE, bool OUT_WIDE>
-PM_DEV void ntt_step4(Fr (&x)[4], const NttPassArgs& a, const NttConsts& kc, u32x4* lds0, u32x4* lds1, u32* lds2,
-                      W4Rows w4, u32 tid, size_t j0) {
+PM_DEV void ntt_step4(Fr (&x)[4], Fr (&ptw)[4], const NttPassArgs& a, const NttConsts& kc, u32x4* lds0, u32x4* lds1,
+                      u32* lds2, W4Rows w4, u32 tid, size_t j0) {
   constexpr int R = 1 << S;
   constexpr int T = 1 << LT;
   constexpr int U = R / 4;
@@ -183,6 +222,7 @@ PM_DEV void ntt_step4(Fr (&x)[4], const NttPassArgs& a, const NttConsts& kc, u32
   constexpr bool L1_UNIFORM = step4_l1_uniform(S, LT, IN_WIDE);
   constexpr bool PM = step4_plane_major(S, IN_WIDE);            // plane-major exchanges: u below is tau
   constexpr bool L1_CONSUMER = PM && step4_l1_consumer(S, LT, OUT_UFAST);
+  constexpr bool TW_PRODUCER = OUT_WIDE && step4_tw_producer(S, LT, OUT_UFAST, IN_WIDE);
   static_assert(!(L1_UNIFORM && STEP == 0 && ufast), "the producer of the first-layer twiddles is in wave order");
   const u32 c = ufast ? tid / U : tid & (T - 1);
   const u32 u = ufast ? tid % U : tid >> LT;
@@ -214,7 +254,20 @@ PM_DEV void ntt_step4(Fr (&x)[4], const NttPassArgs& a, const NttConsts& kc, u32
       x[0] = fe_reduce_weak<FrP>(x[0]);
       x[1] = mul_tw2(x[1], ld_tw2(stw, 0 * nsp + kp));
       x[2] = mul_tw2(x[2], ld_tw2(stw, 1 * nsp + kp));
-      x[3] = mul_tw2(x[3], ld_tw2(stw, 2 * nsp + kp));
+      const FrSplit2 w3 = ld_tw2(stw, 2 * nsp + kp);
+      if constexpr (TW_PRODUCER && STEP >= NSTEPS - 2) {
+        // the next pass's twiddles of outputs 0, 1 (second-to-last step) and 2, 3 (last step), issued behind the step's
+        // own last twiddle load: loads return in order, so nothing this thread needs soon may queue behind them
+        if (a.flags & PASS_TW_OUT) {
+          const WidePtr wtw = wide_ptrs(const_cast<void*>(a.pass_tw_out), a.wide_glog);
+          constexpr int m0 = last ? 2 : 0;
+          __builtin_amdgcn_sched_barrier(0);
+          ptw[m0] = ld_wide(wtw, pass4_out_index<S, LT, OUT_UFAST>(a, tid, j0, m0));
+          ptw[m0 + 1] = ld_wide(wtw, pass4_out_index<S, LT, OUT_UFAST>(a, tid, j0, m0 + 1));
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
+      x[3] = mul_tw2(x[3], w3);
     }
     // L1_UNIFORM, step 1: step 0 left x[0] at (1, <1.01) and x[1..3] at (1, <2), the classes dft4s takes
     // every step reads the w4 rows anew (scalar loads, a column at a time): an opaque copy of the pointer, or the
@@ -257,16 +310,22 @@ PM_DEV void ntt_step4(Fr (&x)[4], const NttPassArgs& a, const NttConsts& kc, u32
   }
   if constexpr (last) {
     const size_t n = (size_t)1 << a.log_n;
-    const size_t j = j0 + c;
-    const size_t ns = (size_t)1 << a.log_ns;
-    const size_t k = j & (ns - 1);
-    const size_t obase = (j - k) * R + k;
     if constexpr (OUT_WIDE) {
       const WidePtr wout = wide_ptrs(a.out, a.wide_glog);
       const size_t boff = (size_t)blockIdx.y * n;
+      if constexpr (TW_PRODUCER) {
+        if (a.flags & PASS_TW_OUT) {
 #pragma unroll
-      for (int m = 0; m < 4; ++m) st_wide(wout, boff + obase + (size_t)(u + m * U) * ns, x[m]);
+          for (int m = 0; m < 4; ++m) x[m] = fe_mul<FrP>(x[m], ptw[m]);  // (<5, <40) * canonical -> (1, <2)
+        }
+      }
+#pragma unroll
+      for (int m = 0; m < 4; ++m) st_wide(wout, boff + pass4_out_index<S, LT, OUT_UFAST>(a, tid, j0, m), x[m]);
     } else {
+      const size_t j = j0 + c;
+      const size_t ns = (size_t)1 << a.log_ns;
+      const size_t k = j & (ns - 1);
+      const size_t obase = (j - k) * R + k;
       u32x4* gout = reinterpret_cast<u32x4*>(a.out) + 2 * (size_t)blockIdx.y * a.batch_stride_out;
 #pragma unroll
       for (int m = 0; m < 4; ++m) {
@@ -302,7 +361,7 @@ __global__ void __launch_bounds__((1 << (S + LT)) / 4 < 64 ? 64 : (1 << (S + LT)
   const size_t j0 = (size_t)xcd_tile(blockIdx.x, gridDim.x, a.flags) * T;
   const W4Rows w4 = w4_rows(a.step_tw);
 
-  Fr x[4];
+  Fr x[4], ptw[4];  // ptw: the next pass's twiddles (PASS_TW_OUT), loaded by the last two steps
   {
     constexpr bool ufast = OUT_UFAST && NSTEPS == 1;
     const u32 c = ufast ? tid / U : tid & (T - 1);
@@ -313,7 +372,10 @@ __global__ void __launch_bounds__((1 << (S + LT)) / 4 < 64 ? 64 : (1 << (S + LT)
       const size_t boff = (size_t)blockIdx.y * n;
       const u32 k = (u32)(j & (((size_t)1 << a.log_ns) - 1));
       const u32 tw_shift = log_n - a.log_ns - S;
-      if (a.flags & PASS_DIRECT_TW) {
+      if (a.flags & PASS_TW_APPLIED) {  // (1, <2) products of the producing pass
+#pragma unroll
+        for (int m = 0; m < 4; ++m) x[m] = ld_wide(win, boff + j + (size_t)(u + m * U) * n_cols);
+      } else if (a.flags & PASS_DIRECT_TW) {
         const WidePtr wtw = wide_ptrs(const_cast<void*>(a.pass_tw), a.wide_glog);
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
@@ -343,12 +405,12 @@ __global__ void __launch_bounds__((1 << (S + LT)) / 4 < 64 ? 64 : (1 << (S + LT)
       }
     }
   }
-  ntt_step4<S, LT, 0, OUT_UFAST, IN_WIDE, OUT_WIDE>(x, a, kc, lds0, lds1, lds2, w4, tid, j0);
-  if constexpr (NSTEPS > 1) ntt_step4<S, LT, 1, OUT_UFAST, IN_WIDE, OUT_WIDE>(x, a, kc, lds0, lds1, lds2, w4, tid, j0);
-  if constexpr (NSTEPS > 2) ntt_step4<S, LT, 2, OUT_UFAST, IN_WIDE, OUT_WIDE>(x, a, kc, lds0, lds1, lds2, w4, tid, j0);
-  if constexpr (NSTEPS > 3) ntt_step4<S, LT, 3, OUT_UFAST, IN_WIDE, OUT_WIDE>(x, a, kc, lds0, lds1, lds2, w4, tid, j0);
-  if constexpr (NSTEPS > 4) ntt_step4<S, LT, 4, OUT_UFAST, IN_WIDE, OUT_WIDE>(x, a, kc, lds0, lds1, lds2, w4, tid, j0);
-  if constexpr (NSTEPS > 5) ntt_step4<S, LT, 5, OUT_UFAST, IN_WIDE, OUT_WIDE>(x, a, kc, lds0, lds1, lds2, w4, tid, j0);
+  ntt_step4<S, LT, 0, OUT_UFAST, IN_WIDE, OUT_WIDE>(x, ptw, a, kc, lds0, lds1, lds2, w4, tid, j0);
+  if constexpr (NSTEPS > 1) ntt_step4<S, LT, 1, OUT_UFAST, IN_WIDE, OUT_WIDE>(x, ptw, a, kc, lds0, lds1, lds2, w4, tid, j0);
+  if constexpr (NSTEPS > 2) ntt_step4<S, LT, 2, OUT_UFAST, IN_WIDE, OUT_WIDE>(x, ptw, a, kc, lds0, lds1, lds2, w4, tid, j0);
+  if constexpr (NSTEPS > 3) ntt_step4<S, LT, 3, OUT_UFAST, IN_WIDE, OUT_WIDE>(x, ptw, a, kc, lds0, lds1, lds2, w4, tid, j0);
+  if constexpr (NSTEPS > 4) ntt_step4<S, LT, 4, OUT_UFAST, IN_WIDE, OUT_WIDE>(x, ptw, a, kc, lds0, lds1, lds2, w4, tid, j0);
+  if constexpr (NSTEPS > 5) ntt_step4<S, LT, 5, OUT_UFAST, IN_WIDE, OUT_WIDE>(x, ptw, a, kc, lds0, lds1, lds2, w4, tid, j0);
 }
 
 // step twiddles of the radix-4 kernel: block s, entry [(t-1)*Ns' + k'] = wR^(k' t R/(Ns' q)), Ns' = 4^s, both rows
