@@ -880,6 +880,65 @@ int pm_jubjub_mul_dev(pm_ctx* ctx, const void* d_points_xy, const void* d_scalar
 int pm_jubjub_check_dev(pm_ctx* ctx, const void* d_points_xy, size_t n, size_t* first_bad, void* hip_stream);
 int pm_jubjub_mul_host(const uint64_t xy[8], const uint64_t scalar[4], uint32_t scalar_form, uint64_t out_xy[8]);
 int pm_jubjub_add_host(const uint64_t p[8], const uint64_t q[8], uint64_t out_xy[8]);
+/* ---- Native Schnorr signatures on JubJub: batch signing and verification ------------------------------
+ * The check the VAR_BASE gadget exists for, outside a circuit: u G + c PK = R with c = H(R.x, R.y, m).  This is the SHAPE of
+ * dusk-schnorr 0.7's single-key signature as remembered -- prior knowledge that nothing in this repository pins, exactly like
+ * the sponge above and JUBJUB_GENERATOR: it is NOT claimed to produce dusk-schnorr's bytes.
+ *   g         a pm_jubjub_base whose point has order exactly l = JUBJUB_ORDER, the order of the prime subgroup.  Checked on the
+ *             host at the handle's first use here and remembered in the handle; PM_ERR_BAD_ARG, pm_last_error naming the cause,
+ *             for the identity and for any point with l g != (0, 1).
+ *   params    the Hades constants; capacity: the capacity word of pm_poseidon_hash_dev (canonical Montgomery).
+ *   challenge h = the modelled sponge of pm_poseidon_hash_dev over the message (R.x, R.y, m): three elements, one chunk, so the
+ *             sponge's padding 1 follows m.  c = the canonical integer of h with bits 250 and above cleared: c < 2^250 < l.
+ *   sign      secret key sk and nonce k, integers in [0, r): R = k G (affine), u = (k - c sk) mod l.  A signature is
+ *             (u, R.x, R.y): three 32-byte elements, 96 bytes.  The nonces are the CALLER's, as the blinders of
+ *             pm_plonk_prove_zk are: the library has no random number generator, and a repeated or predictable nonce gives the
+ *             key away.  sk = 0 or k = 0 modulo l are not refused.
+ *   verify    public key PK = sk G, message m, signature (u, R) -> a reason, the LOWEST that applies:
+ *               PM_SCHNORR_U_RANGE   u >= l (u + l would satisfy the equation as well)
+ *               PM_SCHNORR_R_POINT   R is off the curve or has a coordinate >= r
+ *               PM_SCHNORR_PK_POINT  the same for PK
+ *               PM_SCHNORR_EQUATION  u G + c PK != R as points
+ *               PM_SCHNORR_OK        none of them: valid
+ *             The multipliers are exact integers, as everywhere in pm_jubjub_*; no cofactor is cleared, so a PK with a component
+ *             of small order is judged exactly.
+ * scalar_form (PM_SCALAR_MONTGOMERY or PM_SCALAR_CANONICAL, anything else is PM_ERR_BAD_ARG) governs sk, k and u, in and out.
+ * Messages and coordinates are always canonical Montgomery elements; a message that is not below r is PM_ERR_BAD_ARG on the
+ * host forms and gives an unspecified result, without a fault, on the device forms.
+ * The device calls take addresses on the context's GPU (16-byte aligned; NULL among them is PM_ERR_BAD_ARG), run on
+ * `hip_stream` (NULL = the context's stream) and launch nothing for n = 0 (PM_OK).
+ *   pm_schnorr_sign_dev: n secret keys, nonces and messages (one element each) -> n signatures (three elements each) at d_sigs.
+ *     One kernel, one thread a signature: k G over the base's window table, one inversion (R is hashed, so it must be affine),
+ *     one permutation, the product modulo l.  Asynchronous, no allocation.  NOT hardened against side channels: the table
+ *     addresses depend on k, and the arithmetic modulo l is not constant-time either.
+ *   pm_schnorr_verify_dev: n public keys (two elements each), messages and signatures -> d_reasons, n uint32 (may be NULL), and
+ *     *first_bad (may be NULL), the lowest index with a reason other than 0, n when every signature passes; with both NULL the
+ *     call is PM_ERR_BAD_ARG.  No inversion: u G from the table, c PK by the signed 4-bit ladder of pm_jubjub_mul_dev over 63
+ *     windows, then X = R.x Z and Y = R.y Z.  Two kernels on the stream (the tests, the hash and u G; then the ladder and the
+ *     comparison), a pair per stride of the threads in flight.  The call allocates the ladder's window tables for those
+ *     threads and releases them before it returns, which WAITS for the device, as pm_jubjub_mul_dev does; with first_bad it
+ *     also waits for the stream.  A word of u that is not below r counts as u >= l in either form.
+ * The two host forms need no context and no GPU (csrc/host_field.h): the affine law, double-and-add and long division modulo l,
+ * on purpose other algorithms than the device's.  They take the base as a point and the Hades constants as
+ * pm_hades_permute_host does, and return PM_ERR_BAD_ARG for what the device forms refuse, for constants _create refuses, and for
+ * an sk, k, m or capacity that is not below r.  pm_schnorr_verify_host writes the reason; inputs it can judge are not errors. */
+#define PM_SCHNORR_OK 0u
+#define PM_SCHNORR_U_RANGE 1u
+#define PM_SCHNORR_R_POINT 2u
+#define PM_SCHNORR_PK_POINT 3u
+#define PM_SCHNORR_EQUATION 4u
+int pm_schnorr_sign_dev(pm_ctx* ctx, const pm_jubjub_base* g, const pm_hades_params* params, const uint64_t capacity[4],
+                        const void* d_secret_keys, const void* d_nonces, const void* d_msgs, size_t n, uint32_t scalar_form,
+                        void* d_sigs, void* hip_stream);
+int pm_schnorr_verify_dev(pm_ctx* ctx, const pm_jubjub_base* g, const pm_hades_params* params, const uint64_t capacity[4],
+                          const void* d_pks_xy, const void* d_msgs, const void* d_sigs, size_t n, uint32_t scalar_form,
+                          void* d_reasons, size_t* first_bad, void* hip_stream);
+int pm_schnorr_sign_host(const uint64_t g_xy[8], uint32_t rounds, uint32_t full_rounds, const uint64_t* ark, const uint64_t* mds,
+                         uint32_t n_mds, const uint64_t capacity[4], const uint64_t sk[4], const uint64_t nonce[4],
+                         const uint64_t msg[4], uint32_t scalar_form, uint64_t sig[12]);
+int pm_schnorr_verify_host(const uint64_t g_xy[8], uint32_t rounds, uint32_t full_rounds, const uint64_t* ark, const uint64_t* mds,
+                           uint32_t n_mds, const uint64_t capacity[4], const uint64_t pk_xy[8], const uint64_t msg[4],
+                           const uint64_t sig[12], uint32_t scalar_form, uint32_t* reason);
 /* Proof::to_bytes: 11 x 48-byte compressed G1, then the 16 scalars of ProofEvaluations::to_bytes. */
 int pm_plonk_proof_to_bytes(const pm_plonk_proof* proof, uint8_t out[PM_PLONK_PROOF_BYTES]);
 /* ---- The prover with coefficient-range ownership end to end (SURVEY.md section 8e row 3 + 8f N5; configs[4]) ----------
@@ -1026,6 +1085,14 @@ int pm_test_g1_raw_op(pm_ctx* ctx, int op, const uint32_t* a, const uint32_t* b,
 int pm_test_glv_split(pm_ctx* ctx, const uint64_t* scalars, size_t n, uint32_t scalar_form, uint64_t* out);
 /* Pure host, no context: the same routine compiled for the host, on one canonical k < r. */
 int pm_test_host_glv_split(const uint64_t k[4], uint64_t out[4]);
+/* The arithmetic modulo l = JUBJUB_ORDER behind the Schnorr calls (csrc/jubjub_scalar.hip.h), one thread a case: plain integers
+ * of four uint64 in and out, host pointers, n cases.  op 0 = a mod l (a < r; b and c are not read and may be NULL), 1 =
+ * (a - b c) mod l (a, b < r, c < 2^250), 2 = a < l as 0 / 1 in word 0 (the other words zero).  PM_ERR_BAD_ARG for another op. */
+int pm_test_jubjub_scalar_op(pm_ctx* ctx, int op, const uint64_t* a, const uint64_t* b, const uint64_t* c, uint64_t* out, size_t n);
+/* Pure host, no context: the same three operations by the host's long division (csrc/host_field.h), for any four-word operands. */
+int pm_test_host_jubjub_scalar_op(int op, const uint64_t* a, const uint64_t* b, const uint64_t* c, uint64_t* out, size_t n);
+/* Signatures pm_schnorr_verify_dev has in flight at once on this context's GPU: beyond it the kernel walks n in strides. */
+int pm_test_schnorr_stride(pm_ctx* ctx, size_t* stride);
 /* Pure host, no context: the host-side field arithmetic behind the MSM fold and the prover's challenge scalars
  * (csrc/host_field.h).  op 0 = Fr product, 1 = Fp product, 2 = Fr inverse (binary extended Euclid), 3 = Fp inverse, 4 / 5 =
  * the same inverses by exponentiation; Montgomery form in and out, n elements; b is ignored by the inversions. */

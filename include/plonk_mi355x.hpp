@@ -701,6 +701,7 @@ class Hades {
   Hades(const Hades&) = delete;
   Hades& operator=(const Hades&) = delete;
   Hades(Hades&& o) noexcept : ctx_(o.ctx_), p_(o.p_) { o.p_ = nullptr; }
+  const pm_hades_params* get() const { return p_; }
   uint32_t rounds() const { return info(0); }
   uint32_t full_rounds() const { return info(1); }
   uint32_t n_mds() const { return info(2); }
@@ -783,6 +784,7 @@ class JubJubBase {
   JubJubBase(const JubJubBase&) = delete;
   JubJubBase& operator=(const JubJubBase&) = delete;
   JubJubBase(JubJubBase&& o) noexcept : ctx_(o.ctx_), p_(o.p_) { o.p_ = nullptr; }
+  const pm_jubjub_base* get() const { return p_; }
   Point point() const {
     Point xy{};
     ctx_->check(pm_jubjub_base_point(p_, xy[0].data()));
@@ -829,6 +831,38 @@ class JubJubBase {
   explicit JubJubBase(Context& ctx) : ctx_(&ctx) {}
   Context* ctx_;
   pm_jubjub_base* p_ = nullptr;
+};
+
+// ------------------------------------------------------------------------------------------------
+// Native Schnorr signatures on JubJub (pm_schnorr_*): u G + c PK = R with c = H(R.x, R.y, m) below 2^250.
+// g must have order exactly JUBJUB_ORDER.  A signature is three elements (u, R.x, R.y); secret keys, nonces and u are Montgomery
+// elements (PM_SCALAR_MONTGOMERY).  The nonces are the caller's: the library has no random number generator.  Signing is not
+// hardened against side channels.  The base and the constants must outlive this object.
+class Schnorr {
+ public:
+  Schnorr(Context& ctx, const JubJubBase& g, const Hades& hades, const Fr& capacity = Fr{}) : ctx_(&ctx), g_(&g), h_(&hades), cap_(capacity) {}
+  // n secret keys, nonces and messages -> 3 n elements; asynchronous on the context's stream
+  DevicePolynomial sign(const DevicePolynomial& secret_keys, const DevicePolynomial& nonces, const DevicePolynomial& messages) const {
+    if (secret_keys.len() != nonces.len() || secret_keys.len() != messages.len()) throw Error(PM_ERR_LENGTH, "one nonce and one message per key");
+    DevicePolynomial out(*ctx_, 3 * secret_keys.len());
+    ctx_->check(pm_schnorr_sign_dev(ctx_->get(), g_->get(), h_->get(), cap_.data(), secret_keys.data(), nonces.data(), messages.data(),
+                                    secret_keys.len(), PM_SCALAR_MONTGOMERY, out.data(), nullptr));
+    return out;
+  }
+  // the lowest index whose signature is not valid; messages.len() when every one is.  Waits for the device.
+  size_t verify(const DevicePolynomial& public_keys, const DevicePolynomial& messages, const DevicePolynomial& signatures) const {
+    if (public_keys.len() != 2 * messages.len() || signatures.len() != 3 * messages.len()) throw Error(PM_ERR_LENGTH, "one key and one signature per message");
+    size_t bad = 0;
+    ctx_->check(pm_schnorr_verify_dev(ctx_->get(), g_->get(), h_->get(), cap_.data(), public_keys.data(), messages.data(), signatures.data(),
+                                      messages.len(), PM_SCALAR_MONTGOMERY, nullptr, &bad, nullptr));
+    return bad;
+  }
+
+ private:
+  Context* ctx_;
+  const JubJubBase* g_;
+  const Hades* h_;
+  Fr cap_;
 };
 
 }  // namespace plonk_mi355x

@@ -11,10 +11,11 @@ from ._lib import (BackendMissing, NTT_COSET, NTT_INVERSE, NTT_TRANSPOSED, SCALA
 from .host import (CommitKey, Context, DeviceVector, Error, EvaluationDomain, LagrangeCommitKey, Polynomial,  # noqa: F401
                    msm_variable_base, g1_scalar_mul,
                    g1_fold, g1_to_affine, g1_compress, g1_decompress, domain_info, ntt_plan)
-from . import field, jubjub, poseidon, prover, srs, synthetic, transcript  # noqa: F401,E402
+from . import field, jubjub, poseidon, prover, schnorr, srs, synthetic, transcript  # noqa: F401,E402
 from .jubjub import (JUBJUB_GENERATOR, JubJubBase, jubjub_add_host, jubjub_check, jubjub_commit,  # noqa: F401,E402
                      jubjub_commit_dev, jubjub_mul, jubjub_mul_dev, jubjub_mul_host)
 from .poseidon import Hades, MerkleTree, hades_permute_host, poseidon_hash_host  # noqa: F401,E402
 from .prover import (BatchWorkspace, Circuit, Gadget, GadgetInputError, GadgetReport, Proof, ProverKey,  # noqa: F401,E402
                      UnsatisfiedWitness, WitnessReport, preprocess, prove, prove_batch, random_blinders, sigma_from_wires)
+from .schnorr import SCHNORR_REASONS, Schnorr, schnorr_sign_host, schnorr_verify_host  # noqa: F401,E402
 from .transcript import Transcript  # noqa: F401,E402

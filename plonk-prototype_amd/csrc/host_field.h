@@ -236,6 +236,42 @@ inline El<N> inv_fermat(const El<N>& a, const Field<N>& F) {
   return pow<N>(a, e, N, F);
 }
 
+// ------------------------------------------------------------------ integers modulo l, the order of JubJub's prime subgroup
+// Plain integers of 4 words in and out, no Montgomery form: what a Schnorr signature's u = k - c sk lives in (DESIGN.md section
+// 7.2l).  The device (jubjub_scalar.hip.h) runs Montgomery products modulo l; here the remainder is taken by binary long
+// division, on purpose another algorithm.
+inline const u64* JUBJUB_L() {
+  static const u64 l[4] = {0xd0970e5ed6f72cb7ULL, 0xa6682093ccc81082ULL, 0x06673b0101343b00ULL, 0x0e7db4ea6533afa9ULL};
+  return l;
+}
+inline bool below_l(const u64* a) { return !geq<4>(a, JUBJUB_L()); }
+// x (nw words, any value) mod l: the bits enter the remainder from the top; rem < l < 2^252, so 2 rem + 1 fits four words
+inline void mod_l(const u64* x, int nw, u64 out[4]) {
+  u64 rem[4] = {0, 0, 0, 0};
+  for (int i = 64 * nw - 1; i >= 0; --i) {
+    for (int j = 3; j > 0; --j) rem[j] = (rem[j] << 1) | (rem[j - 1] >> 63);
+    rem[0] = (rem[0] << 1) | ((x[i / 64] >> (i % 64)) & 1);
+    if (geq<4>(rem, JUBJUB_L())) sub_n<4>(rem, rem, JUBJUB_L());
+  }
+  memcpy(out, rem, 32);
+}
+// (a - b c) mod l for any a, b, c of four words: the 512-bit product by the schoolbook, then two divisions
+inline void mulsub_l(const u64* a, const u64* b, const u64* c, u64 out[4]) {
+  u64 p[8] = {0}, pr[4], ar[4];
+  for (int i = 0; i < 4; ++i) {
+    u64 carry = 0;
+    for (int j = 0; j < 4; ++j) {
+      const u128 t = (u128)b[i] * c[j] + p[i + j] + carry;
+      p[i + j] = (u64)t;
+      carry = (u64)(t >> 64);
+    }
+    p[i + 4] = carry;
+  }
+  mod_l(p, 8, pr);
+  mod_l(a, 4, ar);
+  if (sub_n<4>(out, ar, pr)) add_n<4>(out, out, JUBJUB_L());
+}
+
 // ROOT_OF_UNITY = 7^((r-1)/2^32), Montgomery (order 2^32) -- SURVEY.md section 8c
 inline HFr fr_root_of_unity() {
   return HFr{{0xb9b58d8c5f0e466aULL, 0x5b1b4c801819d7ecULL, 0x0af53ae352a31e64ULL,

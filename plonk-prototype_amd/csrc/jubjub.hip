@@ -30,75 +30,12 @@
 #include "field_inv.hip.h"
 #include "jubjub.hip.h"
 
-struct pm_jubjub_base {
-  int device = 0;
-  uint64_t xy[8] = {0};     // the point, canonical Montgomery
-  void* d_tab = nullptr;    // JJ_WINDOWS x 8 entries of JJ_ENTRY_CHUNKS x 16 bytes (entry_limbs below)
-};
-
 namespace pm {
 namespace {
 
 using host::HFr;
 
-constexpr u32 JJ_WINDOWS = 64;       // signed base-16 digits of a scalar below 2^255
-constexpr u32 JJ_ENTRY_CHUNKS = 7;   // fixed-base entry: x, y, t as 27 limbs and one word of padding, 112 bytes
-constexpr u32 JJ_POINT_CHUNKS = 9;   // variable-base entry: X, Y, Z, T as 36 limbs, 144 bytes
-constexpr size_t JJ_BASE_TABLE_BYTES = (size_t)JJ_WINDOWS * 8 * JJ_ENTRY_CHUNKS * 16;   // 57344
-constexpr size_t JJ_MUL_TABLE_BYTES = 8 * (size_t)JJ_POINT_CHUNKS * 16;                 // per thread in flight: 1152
-
-// ------------------------------------------------------------------ the affine law on the host (csrc/host_field.h)
-struct HPoint {
-  HFr x, y;
-};
-bool hfr_canonical(const uint64_t* v) { return !host::geq<4>(v, host::FR().m); }
-HFr hfr_load(const uint64_t* v) {
-  HFr r;
-  memcpy(r.l, v, 32);
-  return r;
-}
-HPoint hpoint_load(const uint64_t* xy) { return HPoint{hfr_load(xy), hfr_load(xy + 4)}; }
-HPoint hpoint_identity() { return HPoint{host::zero<4>(), host::one<4>(host::FR())}; }
-bool hpoint_on_curve(const HPoint& p) {
-  const host::Field<4>& F = host::FR();
-  const HFr x2 = host::mul(p.x, p.x, F), y2 = host::mul(p.y, p.y, F);
-  const HFr rhs = host::add(host::one<4>(F), host::mul(jubjub_d_host(), host::mul(x2, y2, F), F), F);
-  return host::eq(host::sub(y2, x2, F), rhs);
-}
-// (x1, y1) + (x2, y2) = ((x1 y2 + y1 x2) / (1 + k), (y1 y2 + x1 x2) / (1 - k)), k = d x1 x2 y1 y2: complete on the curve
-HPoint hpoint_add(const HPoint& p, const HPoint& q) {
-  const host::Field<4>& F = host::FR();
-  const HFr x1y2 = host::mul(p.x, q.y, F), y1x2 = host::mul(p.y, q.x, F), y1y2 = host::mul(p.y, q.y, F), x1x2 = host::mul(p.x, q.x, F);
-  const HFr k = host::mul(jubjub_d_host(), host::mul(x1y2, y1x2, F), F), one = host::one<4>(F);
-  const HFr inv = host::inv(host::mul(host::add(one, k, F), host::sub(one, k, F), F), F);   // one inversion for both denominators
-  return HPoint{host::mul(host::mul(host::add(x1y2, y1x2, F), host::sub(one, k, F), F), inv, F),
-                host::mul(host::mul(host::add(y1y2, x1x2, F), host::add(one, k, F), F), inv, F)};
-}
-// canonical or Montgomery scalar in memory -> the integer below r; false: not below r
-bool scalar_to_int(const uint64_t* s, uint32_t form, uint64_t (&out)[4]) {
-  if (!hfr_canonical(s)) return false;
-  if (form == PM_SCALAR_CANONICAL) {
-    memcpy(out, s, 32);
-    return true;
-  }
-  HFr one_int = host::zero<4>();
-  one_int.l[0] = 1;                                         // x R * 1 / R = x
-  const HFr v = host::mul(hfr_load(s), one_int, host::FR());
-  memcpy(out, v.l, 32);
-  return true;
-}
-// plain double-and-add from the top bit: NOT the device's algorithm
-HPoint hpoint_mul(const HPoint& p, const uint64_t (&k)[4]) {
-  HPoint acc = hpoint_identity();
-  for (int i = 254; i >= 0; --i) {
-    acc = hpoint_add(acc, acc);
-    if ((k[i / 64] >> (i % 64)) & 1) acc = hpoint_add(acc, p);
-  }
-  return acc;
-}
-bool point_fault(const uint64_t* xy) { return !hfr_canonical(xy) || !hfr_canonical(xy + 4) || !hpoint_on_curve(hpoint_load(xy)); }
-
-// ------------------------------------------------------------------ device side
+// ------------------------------------------------------------------ device side (the shared routines: jubjub.hip.h)
 struct JubjubMul {
   const u32x4* tab_g;       // fixed base, commitment: the table of the (first) base
   const u32x4* tab_h;       // commitment: the table of the second base
@@ -111,82 +48,6 @@ struct JubjubMul {
   u32 montgomery;           // the scalars are Montgomery elements, not plain integers
   u32 edwards_d[9];         // device form
 };
-
-// the scalar at p as four 64-bit words of the integer below r
-PM_DEV void jj_load_scalar(const u32x4* p, bool montgomery, u64 (&k)[4]) {
-  Fr f;
-  if (montgomery) {
-    f = fe_zero<FrP>();
-    f.l[0] = 32u;           // x 2^256 * 2^5 / 2^261 = x
-  } else {
-    f = fe_one<FrP>();
-  }
-  u32 w[8];
-  fe_canon_pack<FrP>(w, fe_mul<FrP>(fe_load<FrP>(p), f));
-#pragma unroll
-  for (int i = 0; i < 4; ++i) k[i] = (u64)w[2 * i] | ((u64)w[2 * i + 1] << 32);
-}
-PM_DEV void jj_shr4(u64 (&k)[4]) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i) k[i] = (k[i] >> 4) | (k[i + 1] << 60);
-  k[3] >>= 4;
-}
-PM_DEV void jj_shl4(u64 (&k)[4]) {
-#pragma unroll
-  for (int i = 3; i > 0; --i) k[i] = (k[i] << 4) | (k[i - 1] >> 60);
-  k[0] <<= 4;
-}
-// the signed digit of nibble `nib` with carry `c` in; c becomes the carry out (the file comment)
-PM_DEV int jj_digit(u32 nib, u32& c) {
-  const u32 v = nib + c;
-  c = v > 8u ? 1u : 0u;
-  return (int)v - (c ? 16 : 0);
-}
-// bit w = the carry INTO digit w, for the walk from the top digit down
-PM_DEV u64 jj_carries(u64 (&k)[4]) {
-  u64 t[4] = {k[0], k[1], k[2], k[3]}, m = 0;
-  u32 c = 0;
-#pragma unroll 1
-  for (u32 w = 0; w < JJ_WINDOWS; ++w) {
-    m |= (u64)c << w;
-    (void)jj_digit((u32)t[0] & 15u, c);
-    jj_shr4(t);
-  }
-  return m;
-}
-PM_DEV Fr jj_limbs(const u32x4& a, const u32x4& b, u32 c) {
-  Fr r;
-  r.l[0] = a.x, r.l[1] = a.y, r.l[2] = a.z, r.l[3] = a.w, r.l[4] = b.x, r.l[5] = b.y, r.l[6] = b.z, r.l[7] = b.w, r.l[8] = c;
-  return r;
-}
-// acc += d * (entry |d| of window w of tab): entry e of window w sits at chunk (8 w + e - 1) * 7
-PM_DEV EdPoint jj_fixed_step(const EdPoint& acc, const u32x4* tab, u32 w, int d, const Fr& ed) {
-  const u32 mag = (u32)(d < 0 ? -d : d), e = mag == 0 ? 1u : (mag > 8u ? 8u : mag);
-  const u32x4* p = tab + (size_t)(8 * w + e - 1) * JJ_ENTRY_CHUNKS;
-  const u32x4 c0 = p[0], c1 = p[1], c2 = p[2], c3 = p[3], c4 = p[4], c5 = p[5], c6 = p[6];
-  const Fr x = jj_limbs(c0, c1, c2.x);
-  const Fr y = jj_limbs(u32x4{c2.y, c2.z, c2.w, c3.x}, u32x4{c3.y, c3.z, c3.w, c4.x}, c4.y);
-  const Fr t = jj_limbs(u32x4{c4.z, c4.w, c5.x, c5.y}, u32x4{c5.z, c5.w, c6.x, c6.y}, c6.z);
-  const Fr zero = fe_zero<FrP>(), one = fe_one<FrP>();
-  const Fr ax = g_sel(d == 0, zero, g_sel(d < 0, gneg(x), x));
-  const Fr ay = g_sel(d == 0, one, y);
-  const Fr at = g_sel(d == 0, zero, g_sel(d < 0, gneg(t), t));
-  return ed_madd(acc, ax, ay, at, ed);
-}
-// (X / Z, Y / Z) to element i of out when live: one inversion, two products (and the change of form); Z = 0 gives (0, 0)
-PM_DEV void jj_store_affine(u32x4* out, size_t i, bool live, const EdPoint& p) {
-  const Fr zi = g_to_abi(fe_inv_dev<FrP>(p.Z));             // every lane of the wave is here
-  if (!live) return;
-  st_canon(out, 2 * i, gmul(p.X, zi));                      // device x ABI -> ABI
-  st_canon(out, 2 * i + 1, gmul(p.Y, zi));
-}
-// v, hidden from the optimiser: what it derives from a loop-invariant operand of a product it otherwise keeps in registers
-// across the whole loop (the table build below then needs all 512 registers of a lone wave and scratch on top)
-PM_DEV void jj_opaque(Fr& v) {
-#pragma unroll
-  for (int i = 0; i < 9; ++i) asm volatile("" : "+v"(v.l[i]));
-}
-PM_DEV EdPoint jj_neutral() { return EdPoint{fe_zero<FrP>(), fe_one<FrP>(), fe_one<FrP>(), fe_zero<FrP>()}; }
 
 // fixed base (COMMIT = false) and commitment (true): the digits from the bottom up, the order of a sum being free
 template <bool COMMIT>
@@ -212,32 +73,6 @@ __global__ void __launch_bounds__(64) jubjub_fixed_kernel(const JubjubMul a) {
   jj_store_affine(a.out, i, live, acc);
 }
 
-// variable base.  One thread's table: chunk c of entry e (e P, e = 1..8, X Y Z T as 36 limbs) at base[((e - 1) * 9 + c) * stride],
-// base = scratch + thread, stride = the threads of the grid: the lanes of a wave read and write consecutive 16-byte chunks when
-// they share a digit and stay aligned when they do not.  A bounded grid walks n in strides (the table is per thread in flight);
-// every wave runs the same number of rounds with its lanes clamped, and an element is read before the same thread writes it,
-// so out may be the points.
-PM_DEV void jj_table_store(u32x4* base, size_t stride, u32 e, const EdPoint& p) {
-  u32 l[36];
-#pragma unroll
-  for (int j = 0; j < 9; ++j) l[j] = p.X.l[j], l[9 + j] = p.Y.l[j], l[18 + j] = p.Z.l[j], l[27 + j] = p.T.l[j];
-  u32x4* q = base + (size_t)(e - 1) * JJ_POINT_CHUNKS * stride;
-#pragma unroll
-  for (int c = 0; c < 9; ++c) q[c * stride] = u32x4{l[4 * c], l[4 * c + 1], l[4 * c + 2], l[4 * c + 3]};
-}
-PM_DEV EdPoint jj_table_load(const u32x4* base, size_t stride, u32 e) {
-  u32 l[36];
-  const u32x4* q = base + (size_t)(e - 1) * JJ_POINT_CHUNKS * stride;
-#pragma unroll
-  for (int c = 0; c < 9; ++c) {
-    const u32x4 v = q[c * stride];
-    l[4 * c] = v.x, l[4 * c + 1] = v.y, l[4 * c + 2] = v.z, l[4 * c + 3] = v.w;
-  }
-  EdPoint p;
-#pragma unroll
-  for (int j = 0; j < 9; ++j) p.X.l[j] = l[j], p.Y.l[j] = l[9 + j], p.Z.l[j] = l[18 + j], p.T.l[j] = l[27 + j];
-  return p;
-}
 // two waves a SIMD: the register budget the allocator meets without scratch
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) jubjub_var_kernel(const JubjubMul a) {
   const size_t T = (size_t)gridDim.x * 64, tid = (size_t)blockIdx.x * 64 + threadIdx.x;
@@ -281,18 +116,6 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   }
 }
 
-// the words of r, most significant first
-constexpr u32 JJ_R_WORDS[8] = {0x73eda753u, 0x299d7d48u, 0x3339d808u, 0x09a1d805u, 0x53bda402u, 0xfffe5bfeu, 0xffffffffu, 0x00000001u};
-PM_DEV bool jj_below_r(const u32x4& lo, const u32x4& hi) {
-  const u32 w[8] = {hi.w, hi.z, hi.y, hi.x, lo.w, lo.z, lo.y, lo.x};
-  bool below = false, decided = false;
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    below = (!decided && w[j] < JJ_R_WORDS[j]) ? true : below;
-    decided = decided || w[j] != JJ_R_WORDS[j];
-  }
-  return below;
-}
 __global__ void __launch_bounds__(64) jubjub_check_kernel(const u32x4* points, size_t n, const JubjubMul a /* edwards_d */,
                                                           unsigned long long* first_bad) {
   const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
@@ -343,22 +166,6 @@ int base_build(pm_ctx* ctx, const uint64_t* xy, pm_jubjub_base** out) {
   memcpy(b->xy, xy, 64);
   *out = b;
   return PM_OK;
-}
-
-int form_fault(pm_ctx* ctx, uint32_t scalar_form) {
-  if (scalar_form != PM_SCALAR_MONTGOMERY && scalar_form != PM_SCALAR_CANONICAL)
-    return set_err(ctx, PM_ERR_BAD_ARG, "scalar_form must be PM_SCALAR_MONTGOMERY or PM_SCALAR_CANONICAL");
-  return PM_OK;
-}
-int base_fault(pm_ctx* ctx, const pm_jubjub_base* b) {
-  if (!b) return set_err(ctx, PM_ERR_BAD_ARG, "null base");
-  if (b->device != ctx->device) return set_err(ctx, PM_ERR_BAD_ARG, "the base belongs to another device");
-  return PM_OK;
-}
-bool unaligned(std::initializer_list<const void*> ps) {
-  uintptr_t acc = 0;
-  for (const void* p : ps) acc |= (uintptr_t)p;
-  return (acc & 15u) != 0;
 }
 
 }  // namespace

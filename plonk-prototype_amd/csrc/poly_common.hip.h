@@ -55,6 +55,12 @@ struct FromTable {
 };
 
 // ------------------------------------------------------------------ host helpers
+static inline bool hfr_canonical(const uint64_t* v) { return !host::geq<4>(v, host::FR().m); }
+static inline HFr hfr_load(const uint64_t* v) {
+  HFr r;
+  memcpy(r.l, v, 32);
+  return r;
+}
 static inline void to_limbs29(u32* dst, HFr v) {  // ABI Montgomery -> device Montgomery limbs
   for (int i = 0; i < 5; ++i) v = host::add(v, v, host::FR());
   for (int i = 0; i < 9; ++i) {

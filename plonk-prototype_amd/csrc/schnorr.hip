@@ -1,0 +1,421 @@
+// Native Schnorr signatures on JubJub: the check u G + c PK = R, c = H(R.x, R.y, m), that the VAR_BASE
+// gadget exists to constrain, outside a circuit.  One thread per signature, over the routines of jubjub.hip.h (the group law,
+// the signed base-16 digits, the window tables), hades.hip.h (one permutation on a lane's own state) and jubjub_scalar.hip.h
+// (integers modulo the subgroup order l):
+//
+//   sign    R = k G from the base's window table (64 ed_madd), ONE inversion -- R is hashed, so it has to be affine --, one
+//           permutation over (capacity, R.x, R.y, m, 1), the truncation c = h mod 2^250, u = (k - c sk) mod l, three stores.
+//   verify  two kernels on the stream.  Head: the range test of u and the two point tests, the same hash, u G from the table.
+//           Tail: a thread's table 1 PK .. 8 PK in the scratch buffer and c PK by the ladder of jubjub_var_kernel over 63
+//           windows (c < 2^250), one addition, then X = R.x Z and Y = R.y Z.  No inversion.  u G, c and the reason of the early
+//           tests pass through the thread's scratch slot, so the ladder keeps the register budget jubjub_var_kernel has and
+//           the head its own (DESIGN.md has the compiler's table for this layout and for the fused kernel it was chosen over).
+//
+// Every lane runs everything: a lane past n works on element n - 1 and stores nothing (fe_inv_dev votes across the wave; its
+// scratch slot is its own), and a failed early test selects the reason, it does not branch around the ladder.  Nothing is read or written at an address that
+// depends on an input except the table entries, whose index is clamped to 1 .. 8.
+//
+// The scheme is the shape of dusk-schnorr 0.7's single-key signature as remembered: prior knowledge, pinned by nothing here.
+// NOT hardened against side channels: signing reads the table at addresses that depend on the nonce k, which with the public
+// (c, u) determines sk, and the arithmetic modulo l selects on its operands.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <string>
+
+#include "context.h"
+#include "field_inv.hip.h"
+#include "hades.hip.h"
+#include "jubjub.hip.h"
+#include "jubjub_scalar.hip.h"
+
+namespace pm {
+namespace {
+
+using host::HFr;
+
+constexpr u32 SCH_WINDOWS = 63;                             // signed base-16 digits of a challenge below 2^250 (the top one <= 4)
+constexpr u32 SCH_SLOT_ENTRIES = 9;                         // a thread's scratch: 1 PK .. 8 PK, then u G
+constexpr size_t SCH_SLOT_BYTES = (SCH_SLOT_ENTRIES * (size_t)JJ_POINT_CHUNKS + 3) * 16;   // 1344 per thread in flight
+constexpr size_t SCH_BLOCKS_PER_CU = 8;                     // as pm_jubjub_mul_dev: eight workgroups of 64 a CU at the most
+
+// ------------------------------------------------------------------ the host forms (csrc/host_field.h)
+// the point is not the identity and l times it is
+bool point_has_order_l(const uint64_t* xy) {
+  const HPoint p = hpoint_load(xy), id = hpoint_identity();
+  if (host::eq(p.x, id.x) && host::eq(p.y, id.y)) return false;
+  uint64_t l[4];
+  memcpy(l, host::JUBJUB_L(), 32);
+  const HPoint q = hpoint_mul(p, l);
+  return host::eq(q.x, id.x) && host::eq(q.y, id.y);
+}
+// c = the canonical integer of H(R.x, R.y, m) below 2^250
+void host_challenge(uint32_t R, uint32_t F, const uint64_t* ark, const uint64_t* mds, uint32_t n_mds, const uint64_t* capacity,
+                    const HPoint& r, const uint64_t* msg, uint64_t (&c)[4]) {
+  const host::Field<4>& Fq = host::FR();
+  HFr s[5] = {hfr_load(capacity), r.x, r.y, hfr_load(msg), host::one<4>(Fq)};   // three inputs, then the padding
+  host_permute(R, F, ark, mds, n_mds, s);
+  HFr one_int = host::zero<4>();
+  one_int.l[0] = 1;                                         // x R * 1 / R = x
+  const HFr h = host::mul(s[1], one_int, Fq);
+  memcpy(c, h.l, 32);
+  c[3] &= (1ull << 58) - 1;
+}
+// the integer u -> memory in `form`
+void scalar_from_int(const uint64_t (&u)[4], uint32_t form, uint64_t* out) {
+  if (form == PM_SCALAR_CANONICAL) {
+    memcpy(out, u, 32);
+    return;
+  }
+  HFr t, r2;
+  memcpy(t.l, u, 32);
+  memcpy(r2.l, host::FR().r2, 32);
+  const HFr v = host::mul(t, r2, host::FR());
+  memcpy(out, v.l, 32);
+}
+bool host_common_fault(const uint64_t* g_xy, uint32_t R, uint32_t F, const uint64_t* ark, const uint64_t* mds, uint32_t n_mds,
+                       const uint64_t* capacity, const uint64_t* msg, uint32_t form) {
+  if (!g_xy || !capacity || !msg || !params_fault(R, F, ark, mds, n_mds).empty()) return true;
+  if (form != PM_SCALAR_MONTGOMERY && form != PM_SCALAR_CANONICAL) return true;
+  if (!hfr_canonical(capacity) || !hfr_canonical(msg)) return true;
+  return point_fault(g_xy) || !point_has_order_l(g_xy);
+}
+
+// ------------------------------------------------------------------ device side
+struct SchnorrIo {
+  const u32x4* tab_g;       // the base's window table
+  const u32x4* keys;        // sign: n secret keys
+  const u32x4* nonces;      // sign: n nonces
+  const u32x4* pks;         // verify: n x (x | y)
+  const u32x4* msgs;        // n elements
+  const u32x4* sigs_in;     // verify: n x (u | R.x | R.y)
+  u32x4* sigs_out;          // sign: the same
+  u32* reasons;             // verify: n, or null
+  unsigned long long* first_bad;   // verify: the lowest failing index, or null
+  u32x4* scratch;           // verify: [entry][chunk][thread of the grid]
+  size_t n, base;           // verify: index 0 here is signature `base` of the call
+  u32 montgomery;           // sk, k and u are Montgomery elements, not plain integers
+  u32 edwards_d[9];         // device form
+  u32 capacity[9];          // device form
+};
+
+// the sponge of hades_thread_kernel over the one chunk (x, y, m), up to its permutation: s = the state with the keys of round 0
+// added; word 1 after h_rounds_thread is the hash.  x, y, m in the device form, normalised, below 2 r: with the round key a
+// word stays below the 4.2 r h_absorb reduces from.
+PM_DEV void sch_absorb(Fr (&s)[5], const Fr& x, const Fr& y, const Fr& m, const SchnorrIo& a, const HadesTab& tab) {
+  const Fr zero = fe_zero<FrP>();
+#pragma unroll
+  for (int i = 0; i < 9; ++i) s[0].l[i] = a.capacity[i];
+  s[0] = h_absorb(s[0], zero, tab.ark);
+  s[1] = h_absorb(zero, x, tab.ark + 9);
+  s[2] = h_absorb(zero, y, tab.ark + 18);
+  s[3] = h_absorb(zero, m, tab.ark + 27);
+  s[4] = h_absorb(zero, fe_one<FrP>(), tab.ark + 36);       // the padding after a chunk of three
+}
+// the canonical integer of h (device form) with bits 250 and above cleared
+PM_DEV void sch_challenge(const Fr& h, u64 (&c)[4]) {
+  u32 w[8];
+  fe_canon_pack<FrP>(w, fe_mul_limb<FrP>(h, 1u));           // x 2^261 * 1 / 2^261 = x
+#pragma unroll
+  for (int i = 0; i < 4; ++i) c[i] = (u64)w[2 * i] | ((u64)w[2 * i + 1] << 32);
+  c[3] &= (1ull << 58) - 1;
+}
+// the point at p (x | y): both coordinates below r and on the curve; x and y in the device form whatever the answer
+PM_DEV bool sch_point_ok(const u32x4* p, const Fr& ed, Fr& x, Fr& y) {
+  const bool canonical = jj_below_r(p[0], p[1]) && jj_below_r(p[2], p[3]);
+  x = g_to_dev(ld_canon(p, 0)), y = g_to_dev(ld_canon(p, 1));
+  const Fr x2 = gmul(x, x), y2 = gmul(y, y);
+  const Fr rhs = gadd(fe_one<FrP>(), gmul(gmul(x2, y2), ed));
+  u32 s[8], any = 0;
+  fe_canon_pack<FrP>(s, gsub(gsub(y2, x2), rhs));
+#pragma unroll
+  for (int j = 0; j < 8; ++j) any |= s[j];
+  return canonical && any == 0;
+}
+PM_DEV bool sch_is_zero(const Fr& v) {                      // v normalised, below 2 r
+  u32 s[8], any = 0;
+  fe_canon_pack<FrP>(s, v);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) any |= s[j];
+  return any == 0;
+}
+
+__global__ void __launch_bounds__(64) schnorr_sign_kernel(const HadesTab tab, const SchnorrIo a) {
+  const size_t g = (size_t)blockIdx.x * 64 + threadIdx.x;
+  const bool live = g < a.n;
+  const size_t i = live ? g : a.n - 1;
+  const Fr ed = fr_limbs(a.edwards_d);
+  // ---- R = k G
+  u64 k[4];
+  jj_load_scalar(a.nonces + 2 * i, a.montgomery != 0, k);
+  u32 cy = 0;
+  EdPoint acc = jj_neutral();
+#pragma unroll 1
+  for (u32 w = 0; w < JJ_WINDOWS; ++w) {
+    acc = jj_fixed_step(acc, a.tab_g, w, jj_digit((u32)k[0] & 15u, cy), ed);
+    jj_shr4(k);
+  }
+  const Fr zi = fe_inv_dev<FrP>(acc.Z);                     // every lane of the wave is here; nothing below crosses lanes
+  Fr s[5];
+  {
+    const Fr rx = gmul(acc.X, zi), ry = gmul(acc.Y, zi);    // device x device -> device
+    if (live) {                                             // R leaves before the hash: its 18 registers are free while the rounds run
+      st_canon(a.sigs_out, 3 * i + 1, g_to_abi(rx));
+      st_canon(a.sigs_out, 3 * i + 2, g_to_abi(ry));
+    }
+    sch_absorb(s, rx, ry, g_to_dev(ld_canon(a.msgs, i)), a, tab);
+  }
+  h_rounds_thread(s, tab);
+  // ---- c, then u = (k - c sk) mod l on the integers
+  u64 c[4], sk[4], u[4];
+  sch_challenge(s[1], c);
+  jj_load_scalar(a.nonces + 2 * i, a.montgomery != 0, k);   // the walk consumed it
+  jj_load_scalar(a.keys + 2 * i, a.montgomery != 0, sk);
+  scl_mulsub(u, k, sk, c);
+  if (!live) return;
+  u32 w[8];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) w[2 * j] = (u32)u[j], w[2 * j + 1] = (u32)(u[j] >> 32);
+  // the integer u < l times 2^261 (canonical) or 2^517 (Montgomery: u 2^256), over 2^261
+  const Fr f = g_sel(a.montgomery != 0, fe_pow2<FrP, 517>(), fe_one<FrP>());
+  st_canon(a.sigs_out, 3 * i, gmul(fe_unpack<FrP>(w), f));
+}
+
+// Verification is two kernels on the stream, each one thread a signature over at most one stride of them (the slots are per
+// thread in flight; the host walks n in strides as jubjub_var_kernel's loop does).  What the head hands to the tail goes through
+// the thread's slot: u G, the challenge (two chunks) and the reason of the early tests.
+// Two to four waves a SIMD: pinned to two, as the tail is, the scheduler spends the registers and the permutation's rounds spill.
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 4))) schnorr_verify_head_kernel(const HadesTab tab,
+                                                                                                             const SchnorrIo a) {
+  const size_t T = (size_t)gridDim.x * 64, tid = (size_t)blockIdx.x * 64 + threadIdx.x;
+  u32x4* const tbl = a.scratch + tid;
+  u32x4* const pass = tbl + (size_t)SCH_SLOT_ENTRIES * JJ_POINT_CHUNKS * T;
+  const size_t i = tid < a.n ? tid : a.n - 1;
+  const u32x4* const sig = a.sigs_in + 6 * i;
+  const Fr ed = fr_limbs(a.edwards_d);
+  // ---- u < l, and u G into the slot
+  u64 u[4];
+  jj_load_scalar(sig, a.montgomery != 0, u);
+  const bool u_ok = jj_below_r(sig[0], sig[1]) && scl_below_l(u);
+  u32 cy = 0;
+  EdPoint ug = jj_neutral();
+#pragma unroll 1
+  for (u32 w = 0; w < JJ_WINDOWS; ++w) {
+    ug = jj_fixed_step(ug, a.tab_g, w, jj_digit((u32)u[0] & 15u, cy), ed);
+    jj_shr4(u);
+  }
+  jj_table_store(tbl, T, SCH_SLOT_ENTRIES, ug);
+  // ---- the two points, the challenge
+  Fr s[5];
+  {
+    Fr rx, ry, px, py;
+    const bool pk_ok = sch_point_ok(a.pks + 4 * i, ed, px, py);
+    const bool r_ok = sch_point_ok(sig + 2, ed, rx, ry);
+    const u32 early = !u_ok ? PM_SCHNORR_U_RANGE : !r_ok ? PM_SCHNORR_R_POINT : !pk_ok ? PM_SCHNORR_PK_POINT : PM_SCHNORR_OK;
+    pass[2 * T] = u32x4{early, 0, 0, 0};
+    sch_absorb(s, rx, ry, g_to_dev(ld_canon(a.msgs, i)), a, tab);
+  }
+  h_rounds_thread(s, tab);
+  u64 c[4];
+  sch_challenge(s[1], c);
+  pass[0] = u32x4{(u32)c[0], (u32)(c[0] >> 32), (u32)c[1], (u32)(c[1] >> 32)};
+  pass[T] = u32x4{(u32)c[2], (u32)(c[2] >> 32), (u32)c[3], (u32)(c[3] >> 32)};
+}
+
+// two waves a SIMD: the ladder's register budget, as jubjub_var_kernel
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) schnorr_verify_tail_kernel(const SchnorrIo a) {
+  const size_t T = (size_t)gridDim.x * 64;
+  const u32 tid = blockIdx.x * 64 + threadIdx.x;
+  u32x4* const tbl = a.scratch + tid;
+  const bool live = tid < a.n;
+  const u32 i = live ? tid : (u32)a.n - 1;                  // n < 2^31; one register, not two, across the ladder
+  const Fr ed = fr_limbs(a.edwards_d);
+  u64 c[4];
+  {
+    const u32x4* const pass = tbl + (size_t)SCH_SLOT_ENTRIES * JJ_POINT_CHUNKS * T;
+    const u32x4 c0 = pass[0], c1 = pass[T];
+    c[0] = (u64)c0.x | ((u64)c0.y << 32), c[1] = (u64)c0.z | ((u64)c0.w << 32);
+    c[2] = (u64)c1.x | ((u64)c1.y << 32), c[3] = (u64)c1.z | ((u64)c1.w << 32);
+  }
+  // ---- the table of PK: e PK = (e - 1) PK + PK
+  const Fr px = g_to_dev(ld_canon(a.pks, 2 * (size_t)i)), py = g_to_dev(ld_canon(a.pks, 2 * (size_t)i + 1)), pt = gmul(px, py);
+  EdPoint acc{px, py, fe_one<FrP>(), pt};
+  jj_table_store(tbl, T, 1, acc);
+#pragma unroll 1
+  for (u32 e = 2; e <= 8; ++e) {
+    Fr x = px, y = py, t = pt;
+    jj_opaque(x), jj_opaque(y), jj_opaque(t);
+    acc = ed_madd(acc, x, y, t, ed);
+    jj_table_store(tbl, T, e, acc);
+  }
+  // ---- c PK from digit 62 down: digit 63 of c < 2^250 is zero and nothing carries into it
+  u64 carries = jj_carries(c) << 1;
+  jj_shl4(c);
+  acc = jj_neutral();
+#pragma unroll 1
+  for (u32 w = 0; w < SCH_WINDOWS; ++w) {
+#pragma unroll 1
+    for (u32 j = 0; j < 4; ++j) acc = ed_add(acc, acc, ed);
+    u32 cw = (u32)(carries >> 63);
+    const int d = jj_digit((u32)(c[3] >> 60), cw);
+    jj_shl4(c);
+    carries <<= 1;
+    const u32 mag = (u32)(d < 0 ? -d : d), e = mag == 0 ? 1u : (mag > 8u ? 8u : mag);
+    const EdPoint q = jj_table_load(tbl, T, e);
+    const EdPoint s{g_sel(d < 0, gneg(q.X), q.X), q.Y, q.Z, g_sel(d < 0, gneg(q.T), q.T)};
+    acc = ed_add(acc, ed_sel(d == 0, jj_neutral(), s), ed);
+  }
+  // ---- u G + c PK = R: X = R.x Z and Y = R.y Z
+  acc = ed_add(acc, jj_table_load(tbl, T, SCH_SLOT_ENTRIES), ed);
+  const Fr rx = g_to_dev(ld_canon(a.sigs_in, 3 * (size_t)i + 1)), ry = g_to_dev(ld_canon(a.sigs_in, 3 * (size_t)i + 2));
+  const bool same = sch_is_zero(gsub(acc.X, gmul(rx, acc.Z))) && sch_is_zero(gsub(acc.Y, gmul(ry, acc.Z)));
+  size_t at = ((size_t)SCH_SLOT_ENTRIES * JJ_POINT_CHUNKS + 2) * T;
+  asm volatile("" : "+s"(at));                               // formed here from tbl: no second address is held across the ladder
+  const u32 early = tbl[at].x;
+  const u32 reason = early != PM_SCHNORR_OK ? early : (same ? PM_SCHNORR_OK : PM_SCHNORR_EQUATION);
+  if (!live) return;
+  if (a.reasons) a.reasons[i] = reason;
+  if (a.first_bad && reason != PM_SCHNORR_OK) atomicMin(a.first_bad, (unsigned long long)(a.base + i));
+}
+
+// ------------------------------------------------------------------ launches
+size_t verify_blocks(const pm_ctx* ctx, size_t n) {
+  return std::max<size_t>(std::min<size_t>((n + 63) / 64, (size_t)std::max(ctx->num_cus, 1) * SCH_BLOCKS_PER_CU), 1);
+}
+// the base's order, once per handle; the caller holds the context's mutex
+int order_fault(pm_ctx* ctx, const pm_jubjub_base* g, const char* who) {
+  if (g->order_state == 0) g->order_state = point_has_order_l(g->xy) ? 1 : -1;
+  if (g->order_state < 0)
+    return set_err(ctx, PM_ERR_BAD_ARG, std::string(who) + ": the base is the identity or its order is not l (l g != (0, 1))");
+  return PM_OK;
+}
+int common_fault(pm_ctx* ctx, const pm_jubjub_base* g, const pm_hades_params* params, uint32_t scalar_form) {
+  if (int rc = base_fault(ctx, g)) return rc;
+  if (!params) return set_err(ctx, PM_ERR_BAD_ARG, "null params");
+  if (params->device != ctx->device) return set_err(ctx, PM_ERR_BAD_ARG, "the params belong to another device");
+  return form_fault(ctx, scalar_form);
+}
+
+}  // namespace
+}  // namespace pm
+
+using namespace pm;
+
+extern "C" int pm_schnorr_sign_dev(pm_ctx* ctx, const pm_jubjub_base* g, const pm_hades_params* params, const uint64_t capacity[4],
+                                   const void* d_secret_keys, const void* d_nonces, const void* d_msgs, size_t n,
+                                   uint32_t scalar_form, void* d_sigs, void* hip_stream) {
+  if (!ctx) return PM_ERR_BAD_ARG;
+  if (int rc = common_fault(ctx, g, params, scalar_form)) return rc;
+  SchnorrIo a{};
+  if (int rc = capacity_to_dev(ctx, capacity, a.capacity)) return rc;
+  if (!d_secret_keys || !d_nonces || !d_msgs || !d_sigs || unaligned({d_secret_keys, d_nonces, d_msgs, d_sigs}))
+    return set_err(ctx, PM_ERR_BAD_ARG, "null or unaligned device pointer");
+  if (n > 0x7fffffffu) return set_err(ctx, PM_ERR_LENGTH, "n > 2^31");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (int rc = order_fault(ctx, g, "pm_schnorr_sign_dev")) return rc;
+  if (n == 0) return PM_OK;
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  a.tab_g = (const u32x4*)g->d_tab, a.keys = (const u32x4*)d_secret_keys, a.nonces = (const u32x4*)d_nonces;
+  a.msgs = (const u32x4*)d_msgs, a.sigs_out = (u32x4*)d_sigs, a.n = n, a.montgomery = scalar_form == PM_SCALAR_MONTGOMERY;
+  jubjub_d_limbs(a.edwards_d);
+  ProfScope prof(ctx, st, "schnorr_sign");
+  hipLaunchKernelGGL(schnorr_sign_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, tab_of(params), a);
+  PM_HIP(ctx, hipGetLastError());
+  return PM_OK;
+}
+
+extern "C" int pm_schnorr_verify_dev(pm_ctx* ctx, const pm_jubjub_base* g, const pm_hades_params* params, const uint64_t capacity[4],
+                                     const void* d_pks_xy, const void* d_msgs, const void* d_sigs, size_t n, uint32_t scalar_form,
+                                     void* d_reasons, size_t* first_bad, void* hip_stream) {
+  if (!ctx) return PM_ERR_BAD_ARG;
+  if (int rc = common_fault(ctx, g, params, scalar_form)) return rc;
+  SchnorrIo a{};
+  if (int rc = capacity_to_dev(ctx, capacity, a.capacity)) return rc;
+  if (!d_reasons && !first_bad) return set_err(ctx, PM_ERR_BAD_ARG, "d_reasons and first_bad are both null");
+  if (!d_pks_xy || !d_msgs || !d_sigs || unaligned({d_pks_xy, d_msgs, d_sigs}) || ((uintptr_t)d_reasons & 3u))
+    return set_err(ctx, PM_ERR_BAD_ARG, "null or unaligned device pointer");
+  if (n > 0x7fffffffu) return set_err(ctx, PM_ERR_LENGTH, "n > 2^31");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (int rc = order_fault(ctx, g, "pm_schnorr_verify_dev")) return rc;
+  if (first_bad) *first_bad = n;
+  if (n == 0) return PM_OK;
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  // the slots of the threads in flight, and eight bytes for the lowest failing index
+  const size_t blocks = verify_blocks(ctx, n), slot_bytes = blocks * 64 * SCH_SLOT_BYTES;
+  void* scratch = nullptr;
+  PM_HIP(ctx, hipMalloc(&scratch, slot_bytes + 16));
+  unsigned long long* const d_bad = (unsigned long long*)((char*)scratch + slot_bytes);
+  unsigned long long bad = n;
+  a.tab_g = (const u32x4*)g->d_tab, a.first_bad = first_bad ? d_bad : nullptr, a.scratch = (u32x4*)scratch;
+  a.montgomery = scalar_form == PM_SCALAR_MONTGOMERY;
+  jubjub_d_limbs(a.edwards_d);
+  const HadesTab tab = tab_of(params);
+  hipError_t e = first_bad ? hipMemcpyAsync(d_bad, &bad, 8, hipMemcpyHostToDevice, st) : hipSuccess;
+  if (e == hipSuccess) {
+    ProfScope prof(ctx, st, "schnorr_verify");
+    const size_t stride = blocks * 64;
+    for (size_t off = 0; off < n && e == hipSuccess; off += stride) {   // a stride's tail is done before the next head reuses the slots
+      a.n = std::min(stride, n - off), a.base = off;
+      a.pks = (const u32x4*)d_pks_xy + 4 * off, a.msgs = (const u32x4*)d_msgs + 2 * off, a.sigs_in = (const u32x4*)d_sigs + 6 * off;
+      a.reasons = d_reasons ? (u32*)d_reasons + off : nullptr;
+      hipLaunchKernelGGL(schnorr_verify_head_kernel, dim3((unsigned)blocks), dim3(64), 0, st, tab, a);
+      hipLaunchKernelGGL(schnorr_verify_tail_kernel, dim3((unsigned)blocks), dim3(64), 0, st, a);
+      e = hipGetLastError();
+    }
+  }
+  if (e == hipSuccess && first_bad) {
+    e = hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+  }
+  // the launch is ordered on the stream like any other; releasing the scratch waits for it (hipFree waits for the device)
+  const hipError_t e2 = hipFree(scratch);
+  if (e == hipSuccess) e = e2;
+  if (e != hipSuccess) return set_err(ctx, PM_ERR_HIP, std::string("pm_schnorr_verify_dev: ") + hipGetErrorString(e));
+  if (first_bad) *first_bad = (size_t)bad;
+  return PM_OK;
+}
+
+extern "C" int pm_schnorr_sign_host(const uint64_t g_xy[8], uint32_t rounds, uint32_t full_rounds, const uint64_t* ark,
+                                    const uint64_t* mds, uint32_t n_mds, const uint64_t capacity[4], const uint64_t sk[4],
+                                    const uint64_t nonce[4], const uint64_t msg[4], uint32_t scalar_form, uint64_t sig[12]) {
+  if (!sk || !nonce || !sig || host_common_fault(g_xy, rounds, full_rounds, ark, mds, n_mds, capacity, msg, scalar_form))
+    return PM_ERR_BAD_ARG;
+  uint64_t ski[4], ki[4], c[4], u[4];
+  if (!scalar_to_int(sk, scalar_form, ski) || !scalar_to_int(nonce, scalar_form, ki)) return PM_ERR_BAD_ARG;
+  const HPoint r = hpoint_mul(hpoint_load(g_xy), ki);
+  host_challenge(rounds, full_rounds, ark, mds, n_mds, capacity, r, msg, c);
+  host::mulsub_l(ki, c, ski, u);
+  scalar_from_int(u, scalar_form, sig);
+  memcpy(sig + 4, r.x.l, 32);
+  memcpy(sig + 8, r.y.l, 32);
+  return PM_OK;
+}
+
+extern "C" int pm_schnorr_verify_host(const uint64_t g_xy[8], uint32_t rounds, uint32_t full_rounds, const uint64_t* ark,
+                                      const uint64_t* mds, uint32_t n_mds, const uint64_t capacity[4], const uint64_t pk_xy[8],
+                                      const uint64_t msg[4], const uint64_t sig[12], uint32_t scalar_form, uint32_t* reason) {
+  if (!pk_xy || !sig || !reason || host_common_fault(g_xy, rounds, full_rounds, ark, mds, n_mds, capacity, msg, scalar_form))
+    return PM_ERR_BAD_ARG;
+  uint64_t u[4], c[4];
+  if (!scalar_to_int(sig, scalar_form, u) || !host::below_l(u)) {   // a word that is not below r is not below l either
+    *reason = PM_SCHNORR_U_RANGE;
+  } else if (point_fault(sig + 4)) {
+    *reason = PM_SCHNORR_R_POINT;
+  } else if (point_fault(pk_xy)) {
+    *reason = PM_SCHNORR_PK_POINT;
+  } else {
+    const HPoint r = hpoint_load(sig + 4);
+    host_challenge(rounds, full_rounds, ark, mds, n_mds, capacity, r, msg, c);
+    const HPoint lhs = hpoint_add(hpoint_mul(hpoint_load(g_xy), u), hpoint_mul(hpoint_load(pk_xy), c));
+    *reason = host::eq(lhs.x, r.x) && host::eq(lhs.y, r.y) ? PM_SCHNORR_OK : PM_SCHNORR_EQUATION;
+  }
+  return PM_OK;
+}
+
+extern "C" int pm_test_schnorr_stride(pm_ctx* ctx, size_t* stride) {
+  if (!ctx || !stride) return PM_ERR_BAD_ARG;
+  *stride = verify_blocks(ctx, ~(size_t)0 >> 1) * 64;
+  return PM_OK;
+}

@@ -13,6 +13,8 @@
 #include "ec_mul.hip.h"
 #include "field_inv.hip.h"
 #include "fields.hip.h"
+#include "host_field.h"
+#include "jubjub_scalar.hip.h"
 #include "ntt_kernels.hip.h"
 #include "ntt_kernels4.hip.h"
 
@@ -187,6 +189,24 @@ __global__ void glv_split_kernel(const u32x4* scalars, size_t n, u32 scalar_form
   }
 }
 
+// the integers modulo l of jubjub_scalar.hip.h: four words a value, one thread a case
+__global__ void jubjub_scalar_op_kernel(int op, const u64* a, const u64* b, const u64* c, u64* out, size_t n) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  u64 x[4], y[4] = {0, 0, 0, 0}, z[4] = {0, 0, 0, 0}, r[4] = {0, 0, 0, 0};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) x[j] = a[4 * i + j];
+  if (op == 1) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) y[j] = b[4 * i + j], z[j] = c[4 * i + j];
+  }
+  if (op == 0) scl_reduce(r, x);
+  if (op == 1) scl_mulsub(r, x, y, z);
+  if (op == 2) r[0] = scl_below_l(x) ? 1u : 0u;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) out[4 * i + j] = r[j];
+}
+
 struct FreeAll {   // the temporaries go away on every path, error returns included
   void* p[3] = {nullptr, nullptr, nullptr};
   ~FreeAll() {
@@ -317,6 +337,41 @@ extern "C" int pm_test_host_glv_split(const uint64_t k[4], uint64_t out[4]) {
   out[1] = h.k1[2] | (uint64_t)h.k1[3] << 32;
   out[2] = h.k2[0] | (uint64_t)h.k2[1] << 32;
   out[3] = h.k2[2] | (uint64_t)h.k2[3] << 32;
+  return PM_OK;
+}
+
+extern "C" int pm_test_jubjub_scalar_op(pm_ctx* ctx, int op, const uint64_t* a, const uint64_t* b, const uint64_t* c, uint64_t* out,
+                                        size_t n) {
+  if (!ctx || !a || !out || op < 0 || op > 2 || (op == 1 && (!b || !c))) return PM_ERR_BAD_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (n == 0) return PM_OK;
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  FreeAll tmp;
+  PM_HIP(ctx, hipMalloc(&tmp.p[0], 3 * n * 32));             // a | b | c
+  PM_HIP(ctx, hipMalloc(&tmp.p[1], n * 32));
+  u64* const da = (u64*)tmp.p[0];
+  PM_HIP(ctx, hipMemcpyAsync(da, a, n * 32, hipMemcpyHostToDevice, ctx->stream));
+  if (op == 1) {
+    PM_HIP(ctx, hipMemcpyAsync(da + 4 * n, b, n * 32, hipMemcpyHostToDevice, ctx->stream));
+    PM_HIP(ctx, hipMemcpyAsync(da + 8 * n, c, n * 32, hipMemcpyHostToDevice, ctx->stream));
+  }
+  hipLaunchKernelGGL(jubjub_scalar_op_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, ctx->stream, op, da, da + 4 * n,
+                     da + 8 * n, (u64*)tmp.p[1], n);
+  PM_HIP(ctx, hipGetLastError());
+  PM_HIP(ctx, hipMemcpyAsync(out, tmp.p[1], n * 32, hipMemcpyDeviceToHost, ctx->stream));
+  PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return PM_OK;
+}
+
+extern "C" int pm_test_host_jubjub_scalar_op(int op, const uint64_t* a, const uint64_t* b, const uint64_t* c, uint64_t* out, size_t n) {
+  if (!a || !out || op < 0 || op > 2 || (op == 1 && (!b || !c))) return PM_ERR_BAD_ARG;
+  for (size_t i = 0; i < n; ++i) {
+    uint64_t r[4] = {0, 0, 0, 0};
+    if (op == 0) host::mod_l(a + 4 * i, 4, r);
+    if (op == 1) host::mulsub_l(a + 4 * i, b + 4 * i, c + 4 * i, r);
+    if (op == 2) r[0] = host::below_l(a + 4 * i) ? 1u : 0u;
+    memcpy(out + 4 * i, r, 32);
+  }
   return PM_OK;
 }
 

@@ -1,0 +1,179 @@
+"""Native Schnorr signatures on JubJub (``pm_schnorr_*``): batch signing and verification on the GPU of
+the check ``u G + c PK = R`` with ``c = H(R.x, R.y, m)`` truncated to 250 bits -- the construction the ``variable_base`` gadget
+exists to constrain, outside a circuit.
+
+This is the shape of dusk-schnorr 0.7's single-key signature as remembered: prior knowledge that nothing in this repository
+pins, like the sponge of :mod:`.poseidon` and ``JUBJUB_GENERATOR``.  ``H`` is the modelled sponge of ``pm_poseidon_hash_dev``.
+
+Secret keys, nonces and the ``u`` of a signature are scalars by the conventions of :mod:`.jubjub`: Montgomery limb arrays
+(``uint64``, last axis 4) or Python integers in ``[0, r)``, which go in as ``PM_SCALAR_CANONICAL``; what comes back is in the
+form that went in.  Messages and coordinates are always Montgomery limbs (or integers, converted).  A signature is
+``[3, 4]``: ``u``, ``R.x``, ``R.y``.
+
+With ``JubJubBase.from_key`` and ``Hades.from_key`` the base and the constants are those of a key's own FIXED_BASE and HADES
+gadgets, unchanged: a natively made signature is then the one that key's gadgets constrain.  Building the in-circuit check
+itself is not part of this module.
+
+Signing is NOT hardened against side channels: table addresses depend on the nonce."""
+from __future__ import annotations
+
+import ctypes as C
+import secrets
+
+import numpy as np
+
+from . import _lib
+from .field import fr_vec_to_limbs
+from .host import DeviceVector, _p
+from .jubjub import JUBJUB_ORDER, JubJubBase, _points, _scalars
+from .poseidon import Hades, _capacity, _elements
+
+SCHNORR_REASONS = _lib.SCHNORR_REASONS
+
+
+def _signatures(x, form: int) -> np.ndarray:
+    """limbs ([..., 3, 4], ``u`` in ``form``) or (u, R.x, R.y) integer triples -> [n, 3, 4]"""
+    if isinstance(x, np.ndarray) and x.dtype == np.uint64:
+        return np.ascontiguousarray(x).reshape(-1, 3, 4)
+    flat = [int(v) for v in np.asarray(x, dtype=object).reshape(-1)]
+    if len(flat) % 3:
+        raise ValueError("signatures are (u, R.x, R.y) triples")
+    us, fu = _scalars(flat[0::3])
+    if fu != form:
+        raise ValueError("integer signatures carry a canonical u")
+    rs = fr_vec_to_limbs([c for k in range(len(flat) // 3) for c in flat[3 * k + 1:3 * k + 3]]).reshape(-1, 2, 4)
+    return np.concatenate([us.reshape(-1, 1, 4), rs], axis=1)
+
+
+def _host_args(g, ark, mds, rounds, capacity):
+    gp, a, m = _points(g), _elements(ark), _elements(mds)
+    if gp.shape[0] != 1 or a.shape[0] != 5 * rounds or m.shape[0] % 25:
+        raise ValueError("one base point, rounds x 5 round keys and whole 5 x 5 matrices")
+    return gp, a, m, _capacity(capacity)
+
+
+def schnorr_sign_host(g, ark, mds, secret_key, nonce, message, capacity=0, rounds: int = 67, full_rounds: int = 8) -> np.ndarray:
+    """``pm_schnorr_sign_host``: one signature on the CPU, no context -> [3, 4] (``u`` in the form of ``secret_key``)"""
+    gp, a, m, cap = _host_args(g, ark, mds, rounds, capacity)
+    (sk, form), (k, form_k), msg = _scalars(secret_key), _scalars(nonce), _elements(message, 1)
+    if form != form_k or sk.shape[0] != 1 or k.shape[0] != 1:
+        raise ValueError("one secret key and one nonce, in one form")
+    out = np.zeros((3, 4), np.uint64)
+    rc = _lib.load().pm_schnorr_sign_host(_p(gp), rounds, full_rounds, _p(a), _p(m), m.shape[0] // 25, _p(cap), _p(sk), _p(k), _p(msg),
+                                          form, _p(out))
+    if rc != _lib.PM_OK:
+        raise ValueError("pm_schnorr_sign_host refused its arguments")
+    return out
+
+
+def schnorr_verify_host(g, ark, mds, public_key, message, signature, capacity=0, rounds: int = 67, full_rounds: int = 8,
+                        scalar_form: int | None = None) -> int:
+    """``pm_schnorr_verify_host``: the reason (0 = valid, else a key of ``SCHNORR_REASONS``) on the CPU, no context.  A limb
+    signature carries a Montgomery ``u`` unless ``scalar_form`` says otherwise; an integer triple a canonical one."""
+    gp, a, m, cap = _host_args(g, ark, mds, rounds, capacity)
+    limbs = isinstance(signature, np.ndarray) and signature.dtype == np.uint64
+    form = scalar_form if scalar_form is not None else (_lib.SCALAR_MONTGOMERY if limbs else _lib.SCALAR_CANONICAL)
+    pk, msg, sig = _points(public_key), _elements(message, 1), _signatures(signature, form)
+    if pk.shape[0] != 1 or sig.shape[0] != 1:
+        raise ValueError("one public key and one signature")
+    reason = C.c_uint32()
+    rc = _lib.load().pm_schnorr_verify_host(_p(gp), rounds, full_rounds, _p(a), _p(m), m.shape[0] // 25, _p(cap), _p(pk), _p(msg),
+                                            _p(sig), form, C.byref(reason))
+    if rc != _lib.PM_OK:
+        raise ValueError("pm_schnorr_verify_host refused its arguments")
+    return int(reason.value)
+
+
+class Schnorr:
+    """Signing and verification over one base and one set of Hades constants on a context's GPU.
+
+    ``Schnorr(g, hades, capacity=0)``: ``g`` a :class:`JubJubBase` whose point has order exactly ``JUBJUB_ORDER`` (checked by the
+    library at the first call, which raises otherwise), ``hades`` a :class:`Hades`, ``capacity`` the sponge's capacity word.
+    Handles from ``JubJubBase.from_key`` / ``Hades.from_key`` work unchanged (the module docstring)."""
+
+    def __init__(self, g: JubJubBase, hades: Hades, capacity=0):
+        if g.ctx is not hades.ctx:
+            raise ValueError("the base and the constants belong to different contexts")
+        self.ctx, self.g, self.hades, self._cap = g.ctx, g, hades, _capacity(capacity)
+
+    def public_keys(self, secret_keys) -> np.ndarray:
+        """``g.mul``: [n, 2, 4] limbs of ``sk_i G``"""
+        return self.g.mul(secret_keys)
+
+    # ------------------------------------------------------------------ device forms (addresses as integers)
+    def sign_dev(self, d_secret_keys: int, d_nonces: int, d_msgs: int, n: int, d_sigs: int,
+                 scalar_form: int = _lib.SCALAR_MONTGOMERY, stream: int = 0):
+        """``pm_schnorr_sign_dev``: n keys, nonces and messages -> n signatures (3 elements each) at ``d_sigs``; asynchronous.
+        Not hardened against side channels."""
+        c = self.ctx
+        c._check(c._lib.pm_schnorr_sign_dev(c._h, self.g._h, self.hades._h, _p(self._cap), C.c_void_p(d_secret_keys),
+                                            C.c_void_p(d_nonces), C.c_void_p(d_msgs), n, scalar_form, C.c_void_p(d_sigs),
+                                            C.c_void_p(stream)))
+
+    def verify_dev(self, d_pks: int, d_msgs: int, d_sigs: int, n: int, d_reasons: int = 0, want_first_bad: bool = True,
+                   scalar_form: int = _lib.SCALAR_MONTGOMERY, stream: int = 0):
+        """``pm_schnorr_verify_dev``: n reasons (``uint32``) at ``d_reasons`` (0 = none wanted); returns the lowest failing index,
+        ``n`` when all pass, or None when ``want_first_bad`` is false.  Waits for the device."""
+        c = self.ctx
+        bad = C.c_size_t()
+        c._check(c._lib.pm_schnorr_verify_dev(c._h, self.g._h, self.hades._h, _p(self._cap), C.c_void_p(d_pks), C.c_void_p(d_msgs),
+                                              C.c_void_p(d_sigs), n, scalar_form, C.c_void_p(d_reasons) if d_reasons else None,
+                                              C.byref(bad) if want_first_bad else None, C.c_void_p(stream)))
+        return int(bad.value) if want_first_bad else None
+
+    # ------------------------------------------------------------------ host arrays in, host arrays out
+    def sign(self, secret_keys, messages, nonces=None) -> np.ndarray:
+        """-> [n, 3, 4]: ``u`` (in the form of ``secret_keys``), ``R.x``, ``R.y``.  ``nonces=None`` draws them with :mod:`secrets`
+        in ``[1, l)``; the library itself has no random number generator."""
+        sk, form = _scalars(secret_keys)
+        n = sk.shape[0]
+        if nonces is None:
+            ks = [1 + secrets.randbelow(JUBJUB_ORDER - 1) for _ in range(n)]
+            k = (_scalars(ks)[0] if form == _lib.SCALAR_CANONICAL else fr_vec_to_limbs(ks)).reshape(-1, 4)
+        else:
+            k, form_k = _scalars(nonces)
+            if form_k != form:
+                raise ValueError("secret keys and nonces must have one form")
+        msg = _elements(messages)
+        if k.shape[0] != n or msg.shape[0] != n:
+            raise ValueError("one nonce and one message per secret key")
+        if n == 0:
+            return np.zeros((0, 3, 4), np.uint64)
+        ds, dk, dm = (DeviceVector.from_host(self.ctx, x) for x in (sk, k, msg))
+        out = DeviceVector(self.ctx, 3 * n)
+        try:
+            self.sign_dev(ds.ptr, dk.ptr, dm.ptr, n, out.ptr, form)
+            return out.to_host().reshape(n, 3, 4)
+        finally:
+            for x in (ds, dk, dm, out):
+                x.free()
+
+    def _verify(self, public_keys, messages, signatures, scalar_form, reasons: bool):
+        limbs = isinstance(signatures, np.ndarray) and signatures.dtype == np.uint64
+        form = scalar_form if scalar_form is not None else (_lib.SCALAR_MONTGOMERY if limbs else _lib.SCALAR_CANONICAL)
+        pk, msg, sig = _points(public_keys), _elements(messages), _signatures(signatures, form)
+        n = sig.shape[0]
+        if pk.shape[0] != n or msg.shape[0] != n:
+            raise ValueError("one public key and one message per signature")
+        if n == 0:
+            return np.zeros(0, np.uint32), 0, 0
+        dp, dm, ds = (DeviceVector.from_host(self.ctx, x) for x in (pk, msg, sig))
+        dr = DeviceVector(self.ctx, (n + 7) // 8) if reasons else None     # n uint32 in 32-byte elements
+        try:
+            bad = self.verify_dev(dp.ptr, dm.ptr, ds.ptr, n, dr.ptr if reasons else 0, True, form)
+            got = dr.to_host().view(np.uint32).reshape(-1)[:n].copy() if reasons else None
+            return got, bad, n
+        finally:
+            for x in (dp, dm, ds, dr):
+                if x is not None:
+                    x.free()
+
+    def verify(self, public_keys, messages, signatures, scalar_form: int | None = None) -> np.ndarray:
+        """-> [n] ``uint32`` reasons: 0 = valid, else a key of ``SCHNORR_REASONS``.  A limb array of signatures carries a Montgomery
+        ``u`` unless ``scalar_form`` says otherwise; integer triples a canonical one."""
+        return self._verify(public_keys, messages, signatures, scalar_form, True)[0]
+
+    def verify_all(self, public_keys, messages, signatures, scalar_form: int | None = None):
+        """None when every signature is valid, else the lowest bad index"""
+        _, bad, n = self._verify(public_keys, messages, signatures, scalar_form, False)
+        return None if bad == n else bad
