@@ -880,6 +880,34 @@ int pm_jubjub_mul_dev(pm_ctx* ctx, const void* d_points_xy, const void* d_scalar
 int pm_jubjub_check_dev(pm_ctx* ctx, const void* d_points_xy, size_t n, size_t* first_bad, void* hip_stream);
 int pm_jubjub_mul_host(const uint64_t xy[8], const uint64_t scalar[4], uint32_t scalar_form, uint64_t out_xy[8]);
 int pm_jubjub_add_host(const uint64_t p[8], const uint64_t q[8], uint64_t out_xy[8]);
+/* ---- Native JubJub MSM: vector commitments ------------------------------------------------------------
+ * pm_jubjub_msm_dev: out[b] = sum_i s_(b,i) P_i for `batch` >= 1 scalar vectors over the same n points: a Pedersen vector
+ *   commitment per vector.  Vector b starts at element b * scalar_stride of d_scalars (scalar_stride >= n, elements of 32 bytes);
+ *   d_out_xy receives `batch` affine points of 64 bytes, canonical Montgomery.  The multiplier of a point is the INTEGER
+ *   0 <= s < r its scalar stands for, never reduced modulo l (the signed windows are an identity on integers), so points
+ *   outside the prime-order subgroup are multiplied exactly.  n = 0 writes `batch` identities (0, 1).  The points are NOT
+ *   validated (pm_jubjub_check_dev does that): for points on the curve the law is complete; for any other bytes, points or
+ *   scalars (words >= r included), the output is unspecified but the call neither faults nor hangs -- every bucket index, count
+ *   and cursor is bounded for any 256-bit pattern.
+ *   The bucket method over signed c-bit windows, ceil(257 / c) of them (256 bits and the carry), 2^(c-1) buckets each; c follows
+ *   from n by the rule of csrc/jubjub_msm_plan.h, or is forced with the option "jubjub_msm_window_bits" (4 .. 16; 0 = the
+ *   rule; anything else PM_ERR_BAD_ARG).  The output BYTES do not depend on c, on the batch or on the order in which atomics
+ *   land: the law is exact and the point leaves in affine form after one inversion.  Skewed scalars (all equal, all zero)
+ *   are correct, only slower.
+ *   Refusals: PM_ERR_BAD_ARG for NULL (points and scalars may be NULL when n = 0) or unaligned pointers, batch = 0,
+ *   scalar_stride < n, a bad scalar_form, d_out_xy overlapping an input.  PM_ERR_LENGTH for what the plan cannot index:
+ *   n > 2^31 - 1, scalar_stride > 2^40, n x windows x batch > 2^32 - 1 (digit, point) pairs, or windows x batch x 2^(c-1)
+ *   > 2^28 buckets.  Asynchronous on `hip_stream` (NULL = the context's stream).  The workspace (4 bytes a pair, 144 a segment of 32
+ *   pairs and 160 a bucket: 0.2 GB at 2^20 points) is cached in the context, ordered across streams, and given back by pm_trim.
+ *   The floor: up to about 2^15 points the call is bound by latency (the doublings of one 256-bit chain, some 1.7 ms) exactly
+ *   as pm_jubjub_mul_dev is, which is then as quick or up to 15 % quicker; the MSM wins from between 2^16 and 2^18 points on, 5 x at 2^20
+ *   (DESIGN.md section 7.2m has the measurements).
+ * pm_jubjub_msm_host: the plain sum of double-and-add products over the affine law, no context and no GPU: on purpose another
+ *   algorithm than the device's.  PM_ERR_BAD_ARG for a point off the curve, a coordinate or scalar >= r, an unknown form, NULL
+ *   (points and scalars may be NULL when n = 0). */
+int pm_jubjub_msm_dev(pm_ctx* ctx, const void* d_points_xy, const void* d_scalars, size_t n, size_t scalar_stride, uint32_t batch,
+                      uint32_t scalar_form, void* d_out_xy, void* hip_stream);
+int pm_jubjub_msm_host(const uint64_t* points_xy, const uint64_t* scalars, size_t n, uint32_t scalar_form, uint64_t out_xy[8]);
 /* ---- Native Schnorr signatures on JubJub: batch signing and verification ------------------------------
  * The check the VAR_BASE gadget exists for, outside a circuit: u G + c PK = R with c = H(R.x, R.y, m).  This is the SHAPE of
  * dusk-schnorr 0.7's single-key signature as remembered -- prior knowledge that nothing in this repository pins, exactly like
@@ -939,6 +967,33 @@ int pm_schnorr_sign_host(const uint64_t g_xy[8], uint32_t rounds, uint32_t full_
 int pm_schnorr_verify_host(const uint64_t g_xy[8], uint32_t rounds, uint32_t full_rounds, const uint64_t* ark, const uint64_t* mds,
                            uint32_t n_mds, const uint64_t capacity[4], const uint64_t pk_xy[8], const uint64_t msg[4],
                            const uint64_t sig[12], uint32_t scalar_form, uint32_t* reason);
+/* pm_schnorr_verify_batch_dev: ONE equation for n signatures, a COFACTORED check.  With the caller's
+ * weights z_i it computes W = a G + sum b_i PK_i - sum z_i R_i, a = sum z_i u_i mod l, b_i = z_i c_i mod l, by one
+ * pm_jubjub_msm_dev over 2 n + 1 points, and accepts when 8 W = (0, 1).  The group has order 8 l, so the reductions modulo l
+ * and the factor 8 belong together.
+ *   d_weights  n integers 0 < z_i < 2^128, two uint64 each, little end first.  They are the CALLER's, as nonces and blinders are:
+ *              the library has no random number generator.  A weight of 0 would drop its signature: PM_ERR_BAD_ARG, and
+ *              pm_last_error names the lowest such index.
+ *   d_sum_xy   NULL, or 64 bytes that receive W itself in affine form.
+ *   *result, *first_bad (both required):
+ *              some entry fails a structural test of pm_schnorr_verify_dev (u < l, R on the curve, PK on the curve): the lowest
+ *                reason (PM_SCHNORR_U_RANGE / _R_POINT / _PK_POINT) of the lowest such index, and that index; such entries
+ *                enter the sum as the identity, so W is still a curve point;
+ *              all entries well formed and 8 W != (0, 1): PM_SCHNORR_EQUATION and n;
+ *              accepted: PM_SCHNORR_OK and n.
+ * What acceptance means.  A batch is accepted when every signature satisfies 8 (u G + c PK - R) = (0, 1); acceptance by the sum
+ * implies this except with probability at most 2^-128 over weights drawn uniformly and independently of the signatures.  This is
+ * WEAKER than pm_schnorr_verify_dev, which clears no cofactor: a signature its signer made with R = k G + T, T of small order,
+ * fails there with PM_SCHNORR_EQUATION and passes here.  Every signature pm_schnorr_verify_dev accepts, this call accepts.
+ * With predictable weights an attacker can make errors cancel.  On rejection, call pm_schnorr_verify_dev to find the culprit.
+ * g must have order l: the same check and refusal as pm_schnorr_verify_dev; pointers are 16-byte aligned device addresses,
+ * NULL among the inputs is PM_ERR_BAD_ARG unless n = 0 (accepted, W = (0, 1)); n > 2^30 - 1 is PM_ERR_LENGTH, as is what the
+ * MSM's plan cannot index.  The call allocates the MSM's input (224 bytes a signature) and releases it, and it WAITS for the
+ * stream, because it reads W back.  The floor: the batch wins from about 2^18 signatures on (2.4 x at 2^20); up to 2^12 the two
+ * take the same time within 5 %, and between 2^14 and 2^16 pm_schnorr_verify_dev is up to 1.4 x quicker. */
+int pm_schnorr_verify_batch_dev(pm_ctx* ctx, const pm_jubjub_base* g, const pm_hades_params* params, const uint64_t capacity[4],
+                                const void* d_pks_xy, const void* d_msgs, const void* d_sigs, const void* d_weights, size_t n,
+                                uint32_t scalar_form, void* d_sum_xy, uint32_t* result, size_t* first_bad, void* hip_stream);
 /* Proof::to_bytes: 11 x 48-byte compressed G1, then the 16 scalars of ProofEvaluations::to_bytes. */
 int pm_plonk_proof_to_bytes(const pm_plonk_proof* proof, uint8_t out[PM_PLONK_PROOF_BYTES]);
 /* ---- The prover with coefficient-range ownership end to end (SURVEY.md section 8e row 3 + 8f N5; configs[4]) ----------
@@ -1042,7 +1097,7 @@ void pm_keccak_f1600(uint8_t state[200]);
 
 /* Number of kernel launches and the Stockham radices the library will use for 2^log_n. */
 int pm_ntt_plan(uint32_t log_n, uint32_t radix_log2[4], uint32_t* n_passes);
-/* Override tunables: "msm_window_bits", "msm_chunk", "msm_lb", "msm_max_pairs", "msm_pipeline" (1 = a batched MSM as
+/* Override tunables: "msm_window_bits", "jubjub_msm_window_bits" (pm_jubjub_msm_dev: 4 .. 16, 0 = the rule), "msm_chunk", "msm_lb", "msm_max_pairs", "msm_pipeline" (1 = a batched MSM as
  * pipelined pieces on two streams; off: it measured slower), "ntt_tile_log", "ntt_radix", "ntt_max_radix", "ntt_xcd",
  * "ntt_direct_tw", "ntt_tw_producer" (1, the default: the radix-4 first pass of radix 2^10 multiplies its outputs by the next
  * pass's inter-pass twiddle table, so that pass starts on its data alone; 0: every pass multiplies its own inputs.  Same results either way;
@@ -1093,6 +1148,18 @@ int pm_test_jubjub_scalar_op(pm_ctx* ctx, int op, const uint64_t* a, const uint6
 int pm_test_host_jubjub_scalar_op(int op, const uint64_t* a, const uint64_t* b, const uint64_t* c, uint64_t* out, size_t n);
 /* Signatures pm_schnorr_verify_dev has in flight at once on this context's GPU: beyond it the kernel walks n in strides. */
 int pm_test_schnorr_stride(pm_ctx* ctx, size_t* stride);
+/* Pure host, no context: the plan of pm_jubjub_msm_dev for n points and `batch` vectors (csrc/jubjub_msm_plan.h); window_bits as
+ * the option "jubjub_msm_window_bits" (0 = the rule); num_cus is accepted for symmetry with the other plan hooks and not used:
+ * this plan does not depend on the machine.  out[8] = {0 window bits c, 1 windows of a scalar = ceil(257 / c), 2 buckets per
+ * window = 2^(c-1), 3 (digit, point) pairs at most = n x windows x batch, 4 workspace bytes, 5 bucket sets = windows x batch,
+ * 6 segments at most (accumulate threads), 7 buckets per thread of the window kernel}.  Returns what the call would:
+ * PM_ERR_BAD_ARG (batch = 0, a width outside 4 .. 16), PM_ERR_LENGTH (the limits of pm_jubjub_msm_dev); out is then zero. */
+int pm_test_jubjub_msm_plan(size_t n, uint32_t batch, long window_bits, uint32_t num_cus, uint64_t out[8]);
+/* Pure host, no context: the signed-window recoding the kernels run, compiled for the host, on ANY 256-bit integer (four words,
+ * little end first) at width c in 4 .. 16 (else PM_ERR_BAD_ARG): digits[k], k < *n_digits, with sum digits[k] 2^(c k) = the
+ * integer and |digits[k]| <= 2^(c-1).  *n_digits is the plan's window count; a carry out of the top window would show as one
+ * more digit (it never occurs).  digits must hold 66 entries. */
+int pm_test_jubjub_msm_digits(const uint64_t scalar[4], uint32_t c, int32_t* digits, uint32_t* n_digits);
 /* Pure host, no context: the host-side field arithmetic behind the MSM fold and the prover's challenge scalars
  * (csrc/host_field.h).  op 0 = Fr product, 1 = Fp product, 2 = Fr inverse (binary extended Euclid), 3 = Fp inverse, 4 / 5 =
  * the same inverses by exponentiation; Montgomery form in and out, n elements; b is ignored by the inversions. */

@@ -815,7 +815,25 @@ class JubJubBase {
     ctx.check(pm_jubjub_check_dev(ctx.get(), points.data(), points.len() / 2, &bad, nullptr));
     return bad;
   }
+  // sum scalars[b][i] * points[i] for `batch` scalar vectors at `scalar_stride` elements (0 = n) over the same n points -> batch
+  // points (2 batch elements), the bucket method of DESIGN.md section 7.2m; the points are not validated.  Asynchronous.
+  static DevicePolynomial msm(Context& ctx, const DevicePolynomial& points, const DevicePolynomial& scalars, uint32_t batch = 1,
+                              size_t scalar_stride = 0) {
+    const size_t n = points.len() / 2, stride = scalar_stride ? scalar_stride : n;
+    if (batch == 0 || stride < n || scalars.len() < (size_t)(batch - 1) * stride + n) throw Error(PM_ERR_LENGTH, "batch vectors of one scalar per point");
+    DevicePolynomial out(ctx, 2 * (size_t)batch);
+    ctx.check(pm_jubjub_msm_dev(ctx.get(), points.data(), scalars.data(), n, stride, batch, PM_SCALAR_MONTGOMERY, out.data(), nullptr));
+    return out;
+  }
   // no context, no GPU
+  static Point msm_host(const std::vector<Point>& points, const std::vector<Fr>& scalars) {
+    Point out{};
+    if (points.size() != scalars.size() ||
+        pm_jubjub_msm_host(points.empty() ? nullptr : points[0][0].data(), scalars.empty() ? nullptr : scalars[0].data(), points.size(),
+                           PM_SCALAR_MONTGOMERY, out[0].data()))
+      throw Error(PM_ERR_BAD_ARG, "pm_jubjub_msm_host refused its arguments");
+    return out;
+  }
   static Point mul_host(const Point& xy, const Fr& scalar) {
     Point out{};
     if (pm_jubjub_mul_host(xy[0].data(), scalar.data(), PM_SCALAR_MONTGOMERY, out[0].data())) throw Error(PM_ERR_BAD_ARG, "pm_jubjub_mul_host refused its arguments");
@@ -856,6 +874,20 @@ class Schnorr {
     ctx_->check(pm_schnorr_verify_dev(ctx_->get(), g_->get(), h_->get(), cap_.data(), public_keys.data(), messages.data(), signatures.data(),
                                       messages.len(), PM_SCALAR_MONTGOMERY, nullptr, &bad, nullptr));
     return bad;
+  }
+  // ONE cofactored equation for all signatures (pm_schnorr_verify_batch_dev) under the caller's weights: n x 16 bytes on the
+  // device, 0 < z_i < 2^128, fresh and unpredictable.  Weaker than verify (the header); true = accepted.  On false, *reason
+  // and *first_bad (either may be null) say why: a structural reason and its index, or PM_SCHNORR_EQUATION and n.  Waits.
+  bool verify_batch(const DevicePolynomial& public_keys, const DevicePolynomial& messages, const DevicePolynomial& signatures,
+                    const void* d_weights, uint32_t* reason = nullptr, size_t* first_bad = nullptr) const {
+    if (public_keys.len() != 2 * messages.len() || signatures.len() != 3 * messages.len()) throw Error(PM_ERR_LENGTH, "one key and one signature per message");
+    uint32_t r = 0;
+    size_t bad = 0;
+    ctx_->check(pm_schnorr_verify_batch_dev(ctx_->get(), g_->get(), h_->get(), cap_.data(), public_keys.data(), messages.data(),
+                                            signatures.data(), d_weights, messages.len(), PM_SCALAR_MONTGOMERY, nullptr, &r, &bad, nullptr));
+    if (reason) *reason = r;
+    if (first_bad) *first_bad = bad;
+    return r == PM_SCHNORR_OK;
   }
 
  private:

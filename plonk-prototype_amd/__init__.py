@@ -13,7 +13,8 @@ from .host import (CommitKey, Context, DeviceVector, Error, EvaluationDomain, La
                    g1_fold, g1_to_affine, g1_compress, g1_decompress, domain_info, ntt_plan)
 from . import field, jubjub, poseidon, prover, schnorr, srs, synthetic, transcript  # noqa: F401,E402
 from .jubjub import (JUBJUB_GENERATOR, JubJubBase, jubjub_add_host, jubjub_check, jubjub_commit,  # noqa: F401,E402
-                     jubjub_commit_dev, jubjub_mul, jubjub_mul_dev, jubjub_mul_host)
+                     jubjub_commit_dev, jubjub_msm, jubjub_msm_dev, jubjub_msm_host, jubjub_mul, jubjub_mul_dev,
+                     jubjub_mul_host)
 from .poseidon import Hades, MerkleTree, hades_permute_host, poseidon_hash_host  # noqa: F401,E402
 from .prover import (BatchWorkspace, Circuit, Gadget, GadgetInputError, GadgetReport, Proof, ProverKey,  # noqa: F401,E402
                      UnsatisfiedWitness, WitnessReport, preprocess, prove, prove_batch, random_blinders, sigma_from_wires)

@@ -212,6 +212,9 @@ SIGNATURES = {
     "pm_jubjub_check_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]),
     "pm_jubjub_mul_host": (C.c_int, [u64p, u64p, C.c_uint32, u64p]),
     "pm_jubjub_add_host": (C.c_int, [u64p, u64p, u64p]),
+    "pm_jubjub_msm_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p,
+                                    C.c_void_p]),
+    "pm_jubjub_msm_host": (C.c_int, [u64p, u64p, C.c_size_t, C.c_uint32, u64p]),
     "pm_schnorr_sign_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, u64p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                       C.c_uint32, C.c_void_p, C.c_void_p]),
     "pm_schnorr_verify_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, u64p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
@@ -220,6 +223,8 @@ SIGNATURES = {
                                        u64p]),
     "pm_schnorr_verify_host": (C.c_int, [u64p, C.c_uint32, C.c_uint32, u64p, u64p, C.c_uint32, u64p, u64p, u64p, u64p, C.c_uint32,
                                          u32p]),
+    "pm_schnorr_verify_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, u64p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_size_t, C.c_uint32, C.c_void_p, u32p, C.POINTER(C.c_size_t), C.c_void_p]),
     "pm_plonk_proof_to_bytes": (C.c_int, [C.POINTER(PlonkProof), C.POINTER(C.c_uint8)]),
     "pm_plonk_batch_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
     "pm_plonk_batch_free": (None, [C.c_void_p, C.c_void_p]),
@@ -256,6 +261,8 @@ SIGNATURES = {
     "pm_test_jubjub_scalar_op": (C.c_int, [C.c_void_p, C.c_int, u64p, u64p, u64p, u64p, C.c_size_t]),
     "pm_test_host_jubjub_scalar_op": (C.c_int, [C.c_int, u64p, u64p, u64p, u64p, C.c_size_t]),
     "pm_test_schnorr_stride": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),
+    "pm_test_jubjub_msm_plan": (C.c_int, [C.c_size_t, C.c_uint32, C.c_long, C.c_uint32, u64p]),
+    "pm_test_jubjub_msm_digits": (C.c_int, [u64p, C.c_uint32, C.POINTER(C.c_int32), u32p]),
     "pm_test_ntt_plan": (C.c_int, [C.c_uint32, C.c_uint32, C.c_long, C.c_long, C.c_long, C.c_uint32, C.POINTER(C.c_uint32)]),
     "pm_test_ntt_exchange_map": (C.c_int, [C.c_uint32] * 5 + [C.POINTER(C.c_uint32)]),
     "pm_test_ntt_step4_table": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, u32p, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -317,6 +324,9 @@ POSEIDON_MERKLE_MAX_HEIGHT = 15
 # pm_schnorr_verify_*: why a signature is not valid, the lowest that applies
 SCHNORR_OK, SCHNORR_U_RANGE, SCHNORR_R_POINT, SCHNORR_PK_POINT, SCHNORR_EQUATION = 0, 1, 2, 3, 4
 SCHNORR_REASONS = {1: "u_range", 2: "r_point", 3: "pk_point", 4: "equation"}
+
+# pm_jubjub_msm_dev: the window widths the option "jubjub_msm_window_bits" may force
+JUBJUB_MSM_MIN_WINDOW_BITS, JUBJUB_MSM_MAX_WINDOW_BITS = 4, 16
 
 NTT_INVERSE = 1
 NTT_COSET = 2

@@ -9,6 +9,7 @@
 #include "field_inv.hip.h"
 #include "fields.hip.h"
 #include "host_field.h"
+#include "jubjub_msm_plan.h"
 
 namespace pm {
 
@@ -165,7 +166,7 @@ static void release_caches(pm_ctx* ctx, bool all) {
     ctx->domain[d].clear();
   }
   for (DeviceBuffer* b : {&ctx->ntt_tmp[0], &ctx->ntt_tmp[1], &ctx->io_in, &ctx->io_out, &ctx->msm_ws, &ctx->msm_scalars,
-                          &ctx->poly_ws, &ctx->poly_tab}) {
+                          &ctx->poly_ws, &ctx->poly_tab, &ctx->jj_msm_ws}) {
     if (b->ptr) (void)hipFree(b->ptr);
     b->ptr = nullptr;
     b->bytes = 0;
@@ -198,7 +199,7 @@ extern "C" void pm_shutdown(pm_ctx* ctx) {
   if (ctx->poly_host_pinned) (void)hipHostFree(ctx->poly_host_pinned);
   if (ctx->msm_side) (void)hipStreamDestroy(ctx->msm_side);
   for (hipEvent_t e : ctx->msm_events) (void)hipEventDestroy(e);
-  for (StreamOrder* o : {&ctx->ord_ntt, &ctx->ord_msm, &ctx->ord_poly})
+  for (StreamOrder* o : {&ctx->ord_ntt, &ctx->ord_msm, &ctx->ord_poly, &ctx->ord_jj_msm})
     if (o->ev) (void)hipEventDestroy(o->ev);
   prof_collect(ctx);
   for (hipEvent_t e : ctx->prof_pool) (void)hipEventDestroy(e);
@@ -268,6 +269,12 @@ extern "C" int pm_set_option(pm_ctx* ctx, const char* key, long value) {
   if (!strcmp(key, "msm_window_bits")) {
     if (value != 0 && (value < 4 || value > 20)) return set_err(ctx, PM_ERR_BAD_ARG, "msm_window_bits out of range");
     ctx->opt_msm_window_bits = value;
+    return PM_OK;
+  }
+  if (!strcmp(key, "jubjub_msm_window_bits")) {
+    if (value != 0 && (value < (long)JMSM_MIN_C || value > (long)JMSM_MAX_C))
+      return set_err(ctx, PM_ERR_BAD_ARG, "jubjub_msm_window_bits out of range");
+    ctx->opt_jubjub_msm_window_bits = value;
     return PM_OK;
   }
   if (!strcmp(key, "msm_chunk")) {

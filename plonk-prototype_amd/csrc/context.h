@@ -76,6 +76,8 @@ struct pm_ctx {
   hipStream_t msm_side = nullptr;                       // second stream of the piece pipeline of a batched MSM (msm.hip)
   std::vector<hipEvent_t> msm_events;                   // "piece i has left the accumulate"
   pm::DeviceBuffer msm_scalars;
+  pm::DeviceBuffer jj_msm_ws;                           // workspace of pm_jubjub_msm_dev (jubjub_msm_plan.h), under ord_jj_msm
+  pm::StreamOrder ord_jj_msm;
   pm::DeviceBuffer poly_ws;                             // scratch of the polynomial helpers
   pm::DeviceBuffer poly_tab;                            // power tables of pm_fr_poly_ruffini_dev
   void* msm_host_pinned = nullptr;
@@ -116,6 +118,7 @@ struct pm_ctx {
   long opt_comm_timeout_ms = 0;  // > 0: every exchange on the context's RCCL communicator runs under this deadline (comm.hip)
   long opt_binv_quads = 0;       // batch inversion: quads (4 elements) per thread and inversion; 0 = auto
   long opt_poly_lookback = 1;    // prefix product in one pass (decoupled look-back) instead of totals / scan / replay
+  long opt_jubjub_msm_window_bits = 0;   // 0 = the rule of jubjub_msm_plan.h
   long opt_msm_pipeline = 0;     // 1: a batched MSM runs as up to four pieces on two streams (measured: loses, see msm.hip)
   int num_cus = 256;
 };
@@ -230,6 +233,10 @@ int hades_params_from_rounds(pm_ctx* ctx, const void* d_rounds, uint32_t R, uint
 // points of GADGET_POINT_BYTES at d_points, most significant round first; the base is the last one and the points before it
 // must double it round by round.  The handle does not refer to the table.  Waits for the context's stream.
 int jubjub_base_from_table(pm_ctx* ctx, const void* d_points, uint32_t R, pm_jubjub_base** out);
+// Native JubJub MSM (jubjub_msm.hip): the launches of pm_jubjub_msm_dev on st for arguments already
+// checked.  The caller holds the context's mutex and has selected the device.  Asynchronous.
+int jubjub_msm_enqueue(pm_ctx* ctx, const void* d_points_xy, const void* d_scalars, size_t n, size_t scalar_stride, uint32_t batch,
+                       bool montgomery, void* d_out_xy, hipStream_t st);
 // Per-proof constants of the proof-batched kernels (pm_plonk_prove_batch): a pinned host buffer and its device twin of the
 // same size.  A launcher takes one region of both, fills the host side and sends it with one async copy on its stream;
 // kernels read the device side as a table indexed by the proof.  reset() once per call, after the previous call has

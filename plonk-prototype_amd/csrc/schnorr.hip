@@ -10,6 +10,9 @@
 //           windows (c < 2^250), one addition, then X = R.x Z and Y = R.y Z.  No inversion.  u G, c and the reason of the early
 //           tests pass through the thread's scratch slot, so the ladder keeps the register budget jubjub_var_kernel has and
 //           the head its own (DESIGN.md has the compiler's table for this layout and for the fused kernel it was chosen over).
+//   batch   one equation for n signatures: a prep kernel (the head's tests and hash, z c and z u modulo l,
+//           the points PK_i, -R_i and their multipliers), a one-workgroup sum that appends (G, a), ONE MSM over 2 n + 1 points
+//           (jubjub_msm.hip) and three doublings of the sum on the host.  A cofactored check: weaker than verify.
 //
 // Every lane runs everything: a lane past n works on element n - 1 and stores nothing (fe_inv_dev votes across the wave; its
 // scratch slot is its own), and a failed early test selects the reason, it does not branch around the ladder.  Nothing is read or written at an address that
@@ -102,7 +105,8 @@ struct SchnorrIo {
 // the sponge of hades_thread_kernel over the one chunk (x, y, m), up to its permutation: s = the state with the keys of round 0
 // added; word 1 after h_rounds_thread is the hash.  x, y, m in the device form, normalised, below 2 r: with the round key a
 // word stays below the 4.2 r h_absorb reduces from.
-PM_DEV void sch_absorb(Fr (&s)[5], const Fr& x, const Fr& y, const Fr& m, const SchnorrIo& a, const HadesTab& tab) {
+template <class Io>
+PM_DEV void sch_absorb(Fr (&s)[5], const Fr& x, const Fr& y, const Fr& m, const Io& a, const HadesTab& tab) {
   const Fr zero = fe_zero<FrP>();
 #pragma unroll
   for (int i = 0; i < 9; ++i) s[0].l[i] = a.capacity[i];
@@ -278,6 +282,137 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   if (a.first_bad && reason != PM_SCHNORR_OK) atomicMin(a.first_bad, (unsigned long long)(a.base + i));
 }
 
+
+// ------------------------------------------------------------------ batch verification by one random linear combination
+// W = a G + sum b_i PK_i - sum z_i R_i with b_i = z_i c_i mod l and a = sum z_i u_i mod l, then 8 W = (0, 1): the group has
+// order 8 l, so reducing a multiplier modulo l changes a curve point's product by a point the factor 8 kills.  The prep kernel
+// is verify's head without u G: the three structural tests, the hash, two products modulo l, and the MSM's input -- points
+// PK_i and -R_i, canonical integers b_i and z_i, z_i u_i aside for the sum kernel.  An entry that fails a structural test goes
+// in as the identity with zero scalars, so nothing unspecified enters the sum.
+struct SchnorrBatchIo {
+  const u32x4* pks;         // n x (x | y)
+  const u32x4* msgs;        // n elements
+  const u32x4* sigs;        // n x (u | R.x | R.y)
+  const u32x4* weights;     // n x 16 bytes: z_i < 2^128, little end first
+  u32x4* points;            // the MSM's 2 n + 1 points: PK_i, -R_i, ..., G
+  u32x4* scalars;           // its 2 n + 1 canonical integers: b_i, z_i, ..., a
+  u32x4* zu;                // n integers z_i u_i mod l
+  unsigned long long* ctl;  // [0] min(index * 8 + reason) over structurally bad entries, [1] the lowest index of a zero weight
+  size_t n;
+  u32 montgomery;
+  u32 edwards_d[9], capacity[9];
+};
+struct SchnorrBasePoint {
+  u64 xy[8];                // canonical Montgomery
+};
+PM_DEV void sch_store_int(u32x4* at, const u64 (&v)[4], bool keep) {
+  const u64 m = keep ? ~0ull : 0ull;                         // a mask, not a select between vectors (that one goes through scratch)
+  const u64 w[4] = {v[0] & m, v[1] & m, v[2] & m, v[3] & m};
+  at[0] = u32x4{(u32)w[0], (u32)(w[0] >> 32), (u32)w[1], (u32)(w[1] >> 32)};
+  at[1] = u32x4{(u32)w[2], (u32)(w[2] >> 32), (u32)w[3], (u32)(w[3] >> 32)};
+}
+// a b mod l for a b < l 2^256
+PM_DEV void scl_mulmod(u64 (&r)[4], const u64 (&a)[4], const u64 (&b)[4]) {
+  const u64 r2[4] = {SCL_R2[0], SCL_R2[1], SCL_R2[2], SCL_R2[3]};
+  u64 t[4];
+  scl_mont(t, a, b);
+  scl_mont(r, t, r2);
+}
+// a + b mod l for a, b < l
+PM_DEV void scl_addmod(u64 (&r)[4], const u64 (&a)[4], const u64 (&b)[4]) {
+  const u64 l[4] = {SCL_L[0], SCL_L[1], SCL_L[2], SCL_L[3]};
+  u64 s[4], d[4], cy = 0;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const u64 x = a[i] + b[i], y = x + cy;
+    cy = (x < a[i] || y < x) ? 1u : 0u;
+    s[i] = y;
+  }
+  const bool below = scl_sub(d, s, l) != 0;                 // 2 l < 2^253: the sum did not wrap
+#pragma unroll
+  for (int i = 0; i < 4; ++i) r[i] = below ? s[i] : d[i];
+}
+
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 4))) schnorr_batch_prep_kernel(const HadesTab tab,
+                                                                                                            const SchnorrBatchIo a) {
+  const size_t g = (size_t)blockIdx.x * 64 + threadIdx.x;
+  const bool live = g < a.n;
+  const size_t i = live ? g : a.n - 1;
+  const u32x4* const sig = a.sigs + 6 * i;
+  const Fr ed = fr_limbs(a.edwards_d);
+  u64 u[4];
+  jj_load_scalar(sig, a.montgomery != 0, u);
+  const bool u_ok = jj_below_r(sig[0], sig[1]) && scl_below_l(u);
+  Fr s[5];
+  u32 early;
+  {
+    Fr rx, ry, px, py;
+    const bool pk_ok = sch_point_ok(a.pks + 4 * i, ed, px, py);
+    const bool r_ok = sch_point_ok(sig + 2, ed, rx, ry);
+    early = !u_ok ? PM_SCHNORR_U_RANGE : !r_ok ? PM_SCHNORR_R_POINT : !pk_ok ? PM_SCHNORR_PK_POINT : PM_SCHNORR_OK;
+    if (live) {                                              // PK_i and -R_i, or two identities
+      const bool ok = early == PM_SCHNORR_OK;
+      const Fr zero = fe_zero<FrP>(), one = g_one_abi();
+      st_canon(a.points, 4 * i, g_sel(ok, g_to_abi(px), zero));
+      st_canon(a.points, 4 * i + 1, g_sel(ok, g_to_abi(py), one));
+      st_canon(a.points, 4 * i + 2, g_sel(ok, g_to_abi(gneg(rx)), zero));
+      st_canon(a.points, 4 * i + 3, g_sel(ok, g_to_abi(ry), one));
+    }
+    sch_absorb(s, rx, ry, g_to_dev(ld_canon(a.msgs, i)), a, tab);
+  }
+  h_rounds_thread(s, tab);
+  u64 c[4], b[4], v[4];
+  sch_challenge(s[1], c);
+  const u32x4 wz = a.weights[i];
+  const u64 z[4] = {(u64)wz.x | ((u64)wz.y << 32), (u64)wz.z | ((u64)wz.w << 32), 0, 0};
+  scl_mulmod(b, z, c);                                       // z c < 2^378
+  scl_mulmod(v, z, u);                                       // z u < 2^383
+  if (!live) return;
+  const bool ok = early == PM_SCHNORR_OK;
+  sch_store_int(a.scalars + 4 * i, b, ok);
+  sch_store_int(a.scalars + 4 * i + 2, z, ok);
+  sch_store_int(a.zu + 2 * i, v, ok);
+  if (!ok) atomicMin(a.ctl, (unsigned long long)i * 8 + early);
+  if ((z[0] | z[1]) == 0) atomicMin(a.ctl + 1, (unsigned long long)i);
+}
+
+// a = sum z_i u_i mod l and the last entry of the MSM's input: (G, a).  One workgroup.
+__global__ void __launch_bounds__(256) schnorr_batch_sum_kernel(const SchnorrBatchIo a, const SchnorrBasePoint g) {
+  __shared__ u64 lds[4][256];
+  const u32 t = threadIdx.x;
+  u64 acc[4] = {0, 0, 0, 0};
+#pragma unroll 1
+  for (size_t i = t; i < a.n; i += 256) {
+    const u32x4 lo = a.zu[2 * i], hi = a.zu[2 * i + 1];
+    const u64 v[4] = {(u64)lo.x | ((u64)lo.y << 32), (u64)lo.z | ((u64)lo.w << 32), (u64)hi.x | ((u64)hi.y << 32), (u64)hi.z | ((u64)hi.w << 32)};
+    u64 r[4];
+    scl_addmod(r, acc, v);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] = r[j];
+  }
+#pragma unroll 1
+  for (u32 s = 128; s >= 1; s >>= 1) {
+    if (t >= s && t < 2 * s) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) lds[j][t] = acc[j];
+    }
+    __syncthreads();
+    if (t < s) {
+      const u64 o[4] = {lds[0][t + s], lds[1][t + s], lds[2][t + s], lds[3][t + s]};
+      u64 r[4];
+      scl_addmod(r, acc, o);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[j] = r[j];
+    }
+    __syncthreads();
+  }
+  if (t != 0) return;
+  sch_store_int(a.scalars + 4 * a.n, acc, true);
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    a.points[8 * a.n + j] = u32x4{(u32)g.xy[2 * j], (u32)(g.xy[2 * j] >> 32), (u32)g.xy[2 * j + 1], (u32)(g.xy[2 * j + 1] >> 32)};
+}
+
 // ------------------------------------------------------------------ launches
 size_t verify_blocks(const pm_ctx* ctx, size_t n) {
   return std::max<size_t>(std::min<size_t>((n + 63) / 64, (size_t)std::max(ctx->num_cus, 1) * SCH_BLOCKS_PER_CU), 1);
@@ -411,6 +546,74 @@ extern "C" int pm_schnorr_verify_host(const uint64_t g_xy[8], uint32_t rounds, u
     const HPoint lhs = hpoint_add(hpoint_mul(hpoint_load(g_xy), u), hpoint_mul(hpoint_load(pk_xy), c));
     *reason = host::eq(lhs.x, r.x) && host::eq(lhs.y, r.y) ? PM_SCHNORR_OK : PM_SCHNORR_EQUATION;
   }
+  return PM_OK;
+}
+
+extern "C" int pm_schnorr_verify_batch_dev(pm_ctx* ctx, const pm_jubjub_base* g, const pm_hades_params* params,
+                                           const uint64_t capacity[4], const void* d_pks_xy, const void* d_msgs, const void* d_sigs,
+                                           const void* d_weights, size_t n, uint32_t scalar_form, void* d_sum_xy, uint32_t* result,
+                                           size_t* first_bad, void* hip_stream) {
+  if (!ctx) return PM_ERR_BAD_ARG;
+  if (int rc = common_fault(ctx, g, params, scalar_form)) return rc;
+  SchnorrBatchIo a{};
+  if (int rc = capacity_to_dev(ctx, capacity, a.capacity)) return rc;
+  if (!result || !first_bad) return set_err(ctx, PM_ERR_BAD_ARG, "null result or first_bad");
+  if (unaligned({d_pks_xy, d_msgs, d_sigs, d_weights, d_sum_xy}) || (n != 0 && (!d_pks_xy || !d_msgs || !d_sigs || !d_weights)))
+    return set_err(ctx, PM_ERR_BAD_ARG, "null or unaligned device pointer");
+  if (n > 0x3fffffffu) return set_err(ctx, PM_ERR_LENGTH, "pm_schnorr_verify_batch_dev: n > 2^30 - 1");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (int rc = order_fault(ctx, g, "pm_schnorr_verify_batch_dev")) return rc;
+  *result = PM_SCHNORR_OK, *first_bad = n;
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  if (n == 0) {                                              // the empty sum: accepted, W = (0, 1)
+    if (!d_sum_xy) return PM_OK;
+    if (int rc = jubjub_msm_enqueue(ctx, nullptr, nullptr, 0, 0, 1, false, d_sum_xy, st)) return rc;
+    PM_HIP(ctx, hipStreamSynchronize(st));
+    return PM_OK;
+  }
+  // the MSM's input, z_i u_i, W and the two control words
+  const size_t m = 2 * n + 1, points_bytes = 64 * m, scalars_bytes = 32 * m, zu_bytes = 32 * n;
+  char* buf = nullptr;
+  PM_HIP(ctx, hipMalloc((void**)&buf, points_bytes + scalars_bytes + zu_bytes + 64 + 16));
+  a.pks = (const u32x4*)d_pks_xy, a.msgs = (const u32x4*)d_msgs, a.sigs = (const u32x4*)d_sigs, a.weights = (const u32x4*)d_weights;
+  a.points = (u32x4*)buf, a.scalars = (u32x4*)(buf + points_bytes), a.zu = (u32x4*)(buf + points_bytes + scalars_bytes);
+  void* const d_w = buf + points_bytes + scalars_bytes + zu_bytes;
+  a.ctl = (unsigned long long*)((char*)d_w + 64);
+  a.n = n, a.montgomery = scalar_form == PM_SCALAR_MONTGOMERY;
+  jubjub_d_limbs(a.edwards_d);
+  SchnorrBasePoint gp;
+  for (int j = 0; j < 8; ++j) gp.xy[j] = g->xy[j];
+  unsigned long long ctl[2] = {~0ull, ~0ull};
+  uint64_t w[8];
+  int rc = PM_OK;
+  hipError_t e = hipMemcpyAsync(a.ctl, ctl, 16, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    ProfScope prof(ctx, st, "schnorr_verify_batch");
+    hipLaunchKernelGGL(schnorr_batch_prep_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, tab_of(params), a);
+    hipLaunchKernelGGL(schnorr_batch_sum_kernel, dim3(1), dim3(256), 0, st, a, gp);
+    e = hipGetLastError();
+    if (e == hipSuccess) rc = jubjub_msm_enqueue(ctx, a.points, a.scalars, m, m, 1, false, d_w, st);
+  }
+  if (e == hipSuccess && rc == PM_OK) e = hipMemcpyAsync(w, d_w, 64, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && rc == PM_OK) e = hipMemcpyAsync(ctl, a.ctl, 16, hipMemcpyDeviceToHost, st);
+  if (e == hipSuccess && rc == PM_OK && d_sum_xy) e = hipMemcpyAsync(d_sum_xy, d_w, 64, hipMemcpyDeviceToDevice, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  const hipError_t e2 = hipFree(buf);
+  if (e == hipSuccess) e = e2;
+  if (e != hipSuccess) return set_err(ctx, PM_ERR_HIP, std::string("pm_schnorr_verify_batch_dev: ") + hipGetErrorString(e));
+  if (rc != PM_OK) return rc;
+  if (ctl[1] < n)
+    return set_err(ctx, PM_ERR_BAD_ARG, "pm_schnorr_verify_batch_dev: weight " + std::to_string(ctl[1]) + " is zero (it would drop its signature)");
+  if (ctl[0] != ~0ull) {
+    *result = (uint32_t)(ctl[0] & 7u), *first_bad = (size_t)(ctl[0] >> 3);
+    return PM_OK;
+  }
+  // 8 W = (0, 1) on the host: three doublings of one point
+  HPoint p = hpoint_load(w);
+  for (int j = 0; j < 3; ++j) p = hpoint_add(p, p);
+  const HPoint id = hpoint_identity();
+  if (!host::eq(p.x, id.x) || !host::eq(p.y, id.y)) *result = PM_SCHNORR_EQUATION;
   return PM_OK;
 }
 

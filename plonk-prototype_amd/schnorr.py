@@ -14,6 +14,9 @@ With ``JubJubBase.from_key`` and ``Hades.from_key`` the base and the constants a
 gadgets, unchanged: a natively made signature is then the one that key's gadgets constrain.  Building the in-circuit check
 itself is not part of this module.
 
+``Schnorr.verify_batch`` checks many signatures with ONE equation, a random linear combination summed by the JubJub MSM (section
+7.2m).  It is a COFACTORED check, weaker than ``verify``: see its docstring.
+
 Signing is NOT hardened against side channels: table addresses depend on the nonce."""
 from __future__ import annotations
 
@@ -121,6 +124,18 @@ class Schnorr:
                                               C.byref(bad) if want_first_bad else None, C.c_void_p(stream)))
         return int(bad.value) if want_first_bad else None
 
+    def verify_batch_dev(self, d_pks: int, d_msgs: int, d_sigs: int, d_weights: int, n: int, d_sum: int = 0,
+                         scalar_form: int = _lib.SCALAR_MONTGOMERY, stream: int = 0):
+        """``pm_schnorr_verify_batch_dev``: one cofactored equation for n signatures under the weights at ``d_weights`` (n x 16
+        bytes, ``0 < z_i < 2^128``); ``d_sum`` (0 = not wanted) receives the sum W, 2 elements.  Returns ``(result, first_bad)``:
+        ``(0, n)`` accepted, ``(4, n)`` the equation fails, else the structural reason and index of the lowest bad entry.  Waits."""
+        c = self.ctx
+        res, bad = C.c_uint32(), C.c_size_t()
+        c._check(c._lib.pm_schnorr_verify_batch_dev(c._h, self.g._h, self.hades._h, _p(self._cap), C.c_void_p(d_pks), C.c_void_p(d_msgs),
+                                                    C.c_void_p(d_sigs), C.c_void_p(d_weights), n, scalar_form,
+                                                    C.c_void_p(d_sum) if d_sum else None, C.byref(res), C.byref(bad), C.c_void_p(stream)))
+        return int(res.value), int(bad.value)
+
     # ------------------------------------------------------------------ host arrays in, host arrays out
     def sign(self, secret_keys, messages, nonces=None) -> np.ndarray:
         """-> [n, 3, 4]: ``u`` (in the form of ``secret_keys``), ``R.x``, ``R.y``.  ``nonces=None`` draws them with :mod:`secrets`
@@ -177,3 +192,46 @@ class Schnorr:
         """None when every signature is valid, else the lowest bad index"""
         _, bad, n = self._verify(public_keys, messages, signatures, scalar_form, False)
         return None if bad == n else bad
+
+    def verify_batch_report(self, public_keys, messages, signatures, weights=None, scalar_form: int | None = None):
+        """:meth:`verify_batch` with everything the call says: ``(result, first_bad, W)``, W as [2, 4] limbs"""
+        limbs = isinstance(signatures, np.ndarray) and signatures.dtype == np.uint64
+        form = scalar_form if scalar_form is not None else (_lib.SCALAR_MONTGOMERY if limbs else _lib.SCALAR_CANONICAL)
+        pk, msg, sig = _points(public_keys), _elements(messages), _signatures(signatures, form)
+        n = sig.shape[0]
+        if pk.shape[0] != n or msg.shape[0] != n:
+            raise ValueError("one public key and one message per signature")
+        zs = [1 + secrets.randbelow((1 << 128) - 1) for _ in range(n)] if weights is None else [int(z) for z in weights]
+        if len(zs) != n:
+            raise ValueError("one weight per signature")
+        if any(not 0 <= z < (1 << 128) for z in zs):
+            raise ValueError("a weight is not in [0, 2^128)")
+        out = DeviceVector(self.ctx, 2)
+        bufs = [out]
+        try:
+            if n:
+                w = np.frombuffer(b"".join(z.to_bytes(16, "little") for z in zs) + bytes(16 * (n % 2)), dtype=np.uint64).reshape(-1, 4)
+                bufs += [DeviceVector.from_host(self.ctx, x) for x in (pk, msg, sig, w.copy())]
+            ptrs = [b.ptr for b in bufs[1:]] if n else [0, 0, 0, 0]
+            res, bad = self.verify_batch_dev(ptrs[0], ptrs[1], ptrs[2], ptrs[3], n, out.ptr, form)
+            return res, bad, out.to_host().reshape(2, 4)
+        finally:
+            for x in bufs:
+                x.free()
+
+    def verify_batch(self, public_keys, messages, signatures, weights=None, scalar_form: int | None = None, return_sum: bool = False):
+        """All n signatures by ONE equation (``pm_schnorr_verify_batch_dev``) -> ``bool``, or ``(bool, W)`` with ``return_sum``.
+
+        ``W = a G + sum b_i PK_i - sum z_i R_i`` with ``a = sum z_i u_i mod l`` and ``b_i = z_i c_i mod l``, summed by one
+        :func:`~.jubjub.jubjub_msm_dev`; accepted when ``8 W`` is the identity.  ``weights=None`` draws the ``z_i`` with
+        :mod:`secrets` in ``[1, 2^128)``, as :meth:`sign` draws nonces; a zero weight raises :class:`~.host.Error` (the library refuses it).
+
+        This is a COFACTORED check: it accepts when every signature satisfies ``8 (u G + c PK - R) = O`` (and otherwise only
+        with probability ``2^-128`` over the weights).  That is weaker than :meth:`verify`, which clears no cofactor: a signature
+        its signer made with ``R = k G + T``, T of small order, fails there and passes here.  Whatever ``verify`` accepts, this
+        accepts.  With predictable weights an attacker can make errors cancel: pass your own only in tests.  A structurally bad
+        entry (``u >= l``, R or PK off the curve) raises nothing and returns ``False``; on ``False`` call :meth:`verify` to find
+        the culprit.  Worth it from about 2^18 signatures on (2.4 x at 2^20); up to 2^12 the two take the same time and in between
+        :meth:`verify_all` is up to 1.4 x quicker."""
+        res, _, w = self.verify_batch_report(public_keys, messages, signatures, weights, scalar_form)
+        return (res == _lib.SCHNORR_OK, w) if return_sum else res == _lib.SCHNORR_OK
