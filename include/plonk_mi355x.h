@@ -812,6 +812,21 @@ uint64_t pm_plonk_gadget_rows(const pm_plonk_gadget* g);
  *     path node itself is child (i >> 2l) & 3.  k x height x 4 elements.  An index >= 4^height is refused with
  *     PM_ERR_BAD_ARG, pm_last_error naming the lowest offending position; finding that out takes one 8-byte readback, so this
  *     call WAITS for the stream.  Nothing is read for a refused index; the entries of the others are written.
+ *   pm_poseidon_merkle_update_dev: leaves[indices[j]] = values[j] for k leaves, then every ancestor of
+ *     a changed leaf is hashed again, each once, and nothing else is written: afterwards leaves and tree hold the bytes
+ *     pm_poseidon_merkle_dev writes over the updated leaves, in both forms.  d_indices: k uint64 in device memory, STRICTLY
+ *     ASCENDING; d_values: k elements; d_work: caller-owned, 16-byte aligned, at least _update_work_bytes(k) bytes (a pure host
+ *     function; 0 for k = 0).  PM_ERR_BAD_ARG, pm_last_error naming the lowest offending position, for an index >= 4^height
+ *     or not above its predecessor -- the test runs on the device before anything is written, and A REFUSED CALL CHANGES NO
+ *     BYTE of leaves or tree.  Also refused: what pm_poseidon_merkle_dev refuses, k > 4^height, and d_values, d_indices or
+ *     d_work overlapping leaves or tree.  One launch chain without a readback between levels (AUTO chooses the form per level
+ *     by the bound min(k, 4^(height - l))); the call WAITS for the stream once, at the end, and reads verdict and count in one
+ *     copy.  *hashed (may be NULL) receives the permutations run: sum over l = 1..height of |{ indices[j] >> 2l }|.
+ *   pm_poseidon_merkle_verify_dev: folds k paths as _paths_dev writes them ([k][height][4] elements) to d_root (one element;
+ *     the tree's last element serves) and writes k uint32 to d_status: PM_MERKLE_PATH_OK; PM_MERKLE_PATH_INDEX for an index
+ *     >= 4^height (nothing of that path is read); PM_MERKLE_PATH_LINK + l for the lowest l < height at which the hash of
+ *     path[l] is not its successor -- child (index >> 2(l + 1)) & 3 of path[l + 1], the root for l = height - 1.  A bad path
+ *     is a result, not an error.  Asynchronous: no readback, no scratch; d_status must not overlap an input.
  * The two host forms need no context and no GPU (csrc/host_field.h): the same permutation and sponge for a one-off hash.
  * They return PM_ERR_BAD_ARG for what _create refuses, a non-canonical input, NULL and msg_len = 0. */
 #define PM_HADES_FORM_AUTO 0u
@@ -831,6 +846,16 @@ int pm_poseidon_merkle_dev(pm_ctx* ctx, const pm_hades_params* params, const uin
                            uint32_t height, void* d_tree, uint32_t flags, void* hip_stream);
 int pm_poseidon_merkle_paths_dev(pm_ctx* ctx, const void* d_leaves, const void* d_tree, uint32_t height, const void* d_indices,
                                  size_t k, void* d_out, void* hip_stream);
+#define PM_MERKLE_PATH_OK 0u
+#define PM_MERKLE_PATH_INDEX 1u
+#define PM_MERKLE_PATH_LINK 2u
+size_t pm_poseidon_merkle_update_work_bytes(size_t k);
+int pm_poseidon_merkle_update_dev(pm_ctx* ctx, const pm_hades_params* params, const uint64_t capacity[4], void* d_leaves,
+                                  void* d_tree, uint32_t height, const void* d_indices, const void* d_values, size_t k,
+                                  void* d_work, uint32_t flags, uint64_t* hashed, void* hip_stream);
+int pm_poseidon_merkle_verify_dev(pm_ctx* ctx, const pm_hades_params* params, const uint64_t capacity[4], const void* d_paths,
+                                  const void* d_indices, size_t k, uint32_t height, const void* d_root, void* d_status,
+                                  uint32_t flags, void* hip_stream);
 int pm_hades_permute_host(uint32_t rounds, uint32_t full_rounds, const uint64_t* ark, const uint64_t* mds, uint32_t n_mds,
                           uint64_t state[20]);
 int pm_poseidon_hash_host(uint32_t rounds, uint32_t full_rounds, const uint64_t* ark, const uint64_t* mds, uint32_t n_mds,

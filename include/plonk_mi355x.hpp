@@ -746,6 +746,46 @@ class Hades {
     ctx.check(rc);
     return out.to_host();
   }
+  // leaves[indices[j]] = values[j] (indices STRICTLY ASCENDING), then only the ancestors of the changed leaves are hashed
+  // again -> the permutations run.  Waits for the stream; a refused call changes nothing.
+  uint64_t merkle_update(DevicePolynomial& leaves, DevicePolynomial& tree, uint32_t height, const std::vector<uint64_t>& indices,
+                         const std::vector<Fr>& values, const Fr& capacity = Fr{}, uint32_t form = PM_HADES_FORM_AUTO) const {
+    if (indices.size() != values.size()) throw Error(PM_ERR_LENGTH, "one value an index");
+    if (indices.empty()) return 0;
+    const size_t k = indices.size();
+    void *d_idx = nullptr, *d_work = nullptr;
+    DevicePolynomial d_values(*ctx_, values);
+    ctx_->check(pm_dev_alloc(ctx_->get(), k * 8, &d_idx));
+    int rc = pm_dev_alloc(ctx_->get(), pm_poseidon_merkle_update_work_bytes(k), &d_work);
+    uint64_t hashed = 0;
+    if (!rc) rc = pm_dev_upload(ctx_->get(), d_idx, indices.data(), k * 8);
+    if (!rc) rc = pm_poseidon_merkle_update_dev(ctx_->get(), p_, capacity.data(), leaves.data(), tree.data(), height, d_idx,
+                                                d_values.data(), k, d_work, form, &hashed, nullptr);
+    pm_dev_free(ctx_->get(), d_idx);
+    if (d_work) pm_dev_free(ctx_->get(), d_work);
+    ctx_->check(rc);
+    return hashed;
+  }
+  // paths: k x height x 4 elements as merkle_paths returns them -> a status a path: PM_MERKLE_PATH_OK, _INDEX, _LINK + l
+  std::vector<uint32_t> merkle_verify(const std::vector<Fr>& paths, const std::vector<uint64_t>& indices, uint32_t height,
+                                      const Fr& root, const Fr& capacity = Fr{}, uint32_t form = PM_HADES_FORM_AUTO) const {
+    const size_t k = indices.size();
+    if (paths.size() != k * height * 4) throw Error(PM_ERR_LENGTH, "paths must hold k x height x 4 elements");
+    std::vector<uint32_t> status(k);
+    if (k == 0) return status;
+    DevicePolynomial d_paths(*ctx_, paths), d_root(*ctx_, std::vector<Fr>{root});
+    void *d_idx = nullptr, *d_status = nullptr;
+    ctx_->check(pm_dev_alloc(ctx_->get(), k * 8, &d_idx));
+    int rc = pm_dev_alloc(ctx_->get(), k * 4, &d_status);
+    if (!rc) rc = pm_dev_upload(ctx_->get(), d_idx, indices.data(), k * 8);
+    if (!rc) rc = pm_poseidon_merkle_verify_dev(ctx_->get(), p_, capacity.data(), d_paths.data(), d_idx, k, height, d_root.data(),
+                                                d_status, form, nullptr);
+    if (!rc) rc = pm_dev_download(ctx_->get(), status.data(), d_status, k * 4);
+    pm_dev_free(ctx_->get(), d_idx);
+    if (d_status) pm_dev_free(ctx_->get(), d_status);
+    ctx_->check(rc);
+    return status;
+  }
   // no context, no GPU
   static std::array<Fr, 5> permute_host(const std::vector<Fr>& ark, const std::vector<Fr>& mds, std::array<Fr, 5> state,
                                         uint32_t rounds = 67, uint32_t full_rounds = 8) {

@@ -199,6 +199,11 @@ SIGNATURES = {
                                          C.c_void_p]),
     "pm_poseidon_merkle_paths_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t,
                                                C.c_void_p, C.c_void_p]),
+    "pm_poseidon_merkle_update_work_bytes": (C.c_size_t, [C.c_size_t]),
+    "pm_poseidon_merkle_update_dev": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, u64p, C.c_void_p]),
+    "pm_poseidon_merkle_verify_dev": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32,
+                                                C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "pm_hades_permute_host": (C.c_int, [C.c_uint32, C.c_uint32, u64p, u64p, C.c_uint32, u64p]),
     "pm_poseidon_hash_host": (C.c_int, [C.c_uint32, C.c_uint32, u64p, u64p, C.c_uint32, u64p, u64p, C.c_size_t, u64p]),
     "pm_jubjub_base_create": (C.c_int, [C.c_void_p, u64p, C.POINTER(C.c_void_p)]),
@@ -321,6 +326,8 @@ PLONK_CHAIN_KINDS = {10: "variable_base"}
 # pm_hades_permute_dev / pm_poseidon_*_dev: which kernel form runs (the bytes do not depend on it)
 HADES_FORM_AUTO, HADES_FORM_THREAD, HADES_FORM_WAVE = 0, 1, 2
 POSEIDON_MERKLE_MAX_HEIGHT = 15
+# pm_poseidon_merkle_verify_dev: the status of a path; LINK + l = the hash of level l is not its successor
+MERKLE_PATH_OK, MERKLE_PATH_INDEX, MERKLE_PATH_LINK = 0, 1, 2
 # pm_schnorr_verify_*: why a signature is not valid, the lowest that applies
 SCHNORR_OK, SCHNORR_U_RANGE, SCHNORR_R_POINT, SCHNORR_PK_POINT, SCHNORR_EQUATION = 0, 1, 2, 3, 4
 SCHNORR_REASONS = {1: "u_range", 2: "r_point", 3: "pk_point", 4: "equation"}

@@ -16,9 +16,14 @@
 //
 // Both keep the sponge's state in registers across chunks; a tree level is the sponge on messages of four (no padding).  What is
 // stored goes through fe_store: canonical whatever representative the form arrived at.
+//
+// Section 7.2n adds the tree in place: an update of k leaves that hashes only their ancestors (the two hash kernels again, with
+// an argument block that takes slot i's node from a worklist in device memory; the worklists come from a compaction a level)
+// and the verification of paths, `height` dependent permutations a path from the same rounds.
 #include <hip/hip_runtime.h>
 
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "context.h"
@@ -39,11 +44,40 @@ struct HadesIo {
   u32 msg_len;
   u32 capacity[9];            // device form
 };
+// what an incremental tree update keeps in the caller's work area (section 7.2n): the verdict on the indices, the
+// permutations run, and the length of every level's worklist
+struct MerkleCtl {
+  u64 bad;                    // the lowest offending position, ~0 = none
+  u64 hashed;
+  u32 cnt[PM_POSEIDON_MERKLE_MAX_HEIGHT + 1];
+};
+constexpr u64 MERKLE_NONE = ~0ull;
+// the INDEXED hash: slot i hashes the four children of node ids[i] of one level.  n bounds the launch; the number of slots
+// is ctl->cnt[level], nothing runs after a bad verdict.  msgs = the level below, out = the level itself.
+struct HadesNodeIo : HadesIo {
+  const u32* ids;
+  const MerkleCtl* ctl;
+  u32 level;
+};
+PM_DEV size_t h_slots(const HadesIo& io) { return io.n; }
+PM_DEV size_t h_slots(const HadesNodeIo& io) {
+  const size_t have = io.ctl->bad == MERKLE_NONE ? io.ctl->cnt[io.level] : 0;
+  return have < io.n ? have : io.n;
+}
+// slot -> its message; out_at = the element of its output
+PM_DEV const u32x4* h_place(const HadesIo& io, size_t slot, size_t& out_at) {
+  out_at = slot;
+  return io.msgs + 2 * io.msg_stride * slot;
+}
+PM_DEV const u32x4* h_place(const HadesNodeIo& io, size_t slot, size_t& out_at) {
+  out_at = io.ids[slot];
+  return io.msgs + 8 * out_at;                               // the four children of the node
+}
 
-template <bool HASH>
-__global__ void __launch_bounds__(64) hades_thread_kernel(const HadesTab tab, const HadesIo io) {
+template <bool HASH, class Io = HadesIo>
+__global__ void __launch_bounds__(64) hades_thread_kernel(const HadesTab tab, const Io io) {
   const size_t idx = (size_t)blockIdx.x * 64 + threadIdx.x;
-  if (idx >= io.n) return;
+  if (idx >= h_slots(io)) return;
   Fr s[5];
   if (!HASH) {
     u32x4* const p = io.states + 10 * idx;
@@ -53,7 +87,8 @@ __global__ void __launch_bounds__(64) hades_thread_kernel(const HadesTab tab, co
 #pragma unroll
     for (int j = 0; j < 5; ++j) st_canon(p, j, h_to_abi(s[j]));
   } else {
-    const u32x4* const msg = io.msgs + 2 * io.msg_stride * idx;
+    size_t out_at;
+    const u32x4* const msg = h_place(io, idx, out_at);
 #pragma unroll
     for (int i = 0; i < 9; ++i) s[0].l[i] = io.capacity[i];
 #pragma unroll
@@ -65,7 +100,7 @@ __global__ void __launch_bounds__(64) hades_thread_kernel(const HadesTab tab, co
       for (int j = 1; j < 5; ++j) s[j] = h_absorb(s[j], h_chunk_word(msg, at, io.msg_len - at, j - 1), tab.ark + 9 * j);
       h_rounds_thread(s, tab);
     }
-    st_canon(io.out, idx, h_to_abi(s[1]));
+    st_canon(io.out, out_at, h_to_abi(s[1]));
   }
 }
 
@@ -108,14 +143,16 @@ PM_DEV Fr h_rounds_wave(Fr s, const u32* mds, const u32* ark, const HadesTab& ta
   return s;
 }
 
-template <bool HASH>
-__global__ void __launch_bounds__(64) hades_wave_kernel(const HadesTab tab, const HadesIo io) {
+template <bool HASH, class Io = HadesIo>
+__global__ void __launch_bounds__(64) hades_wave_kernel(const HadesTab tab, const Io io) {
   const u32 lane = threadIdx.x, base = lane & 32u, l = (lane & 31u) < 25u ? (lane & 31u) : 24u;   // lanes 25..31 shadow lane 24
   const bool owner = (lane & 31u) < 25u;
   const u32 i = l / 5, j = l - 5 * i;
   size_t idx = 2 * (size_t)blockIdx.x + (base >> 5);
-  const bool live = idx < io.n;                            // an odd n: the last wave's second half repeats the first
-  if (!live) idx = io.n - 1;
+  const size_t n = h_slots(io);
+  if (!std::is_same<Io, HadesIo>::value && 2 * (size_t)blockIdx.x >= n) return;   // a surplus wave: the whole wave leaves
+  const bool live = idx < n;                               // an odd n: the last wave's second half repeats the first
+  if (!live) idx = n - 1;
   const u32* const mds = (const u32*)tab.mds;
   const u32* const ark = (const u32*)tab.ark;
   const Fr key0 = h_lane_const(ark + 9 * j);
@@ -125,7 +162,8 @@ __global__ void __launch_bounds__(64) hades_wave_kernel(const HadesTab tab, cons
     s = h_rounds_wave(s, mds, ark, tab, base, i, j);
     if (live && owner && i == 0) st_canon(p, j, h_to_abi(s));
   } else {
-    const u32x4* const msg = io.msgs + 2 * io.msg_stride * idx;
+    size_t out_at;
+    const u32x4* const msg = h_place(io, idx, out_at);
     Fr s = fe_zero<FrP>();
     if (j == 0) {
 #pragma unroll
@@ -137,7 +175,7 @@ __global__ void __launch_bounds__(64) hades_wave_kernel(const HadesTab tab, cons
       s = fe_reduce_weak<FrP>(fe_add<FrP>(fe_add<FrP>(s, add), key0));
       s = h_rounds_wave(s, mds, ark, tab, base, i, j);
     }
-    if (live && owner && l == 1) st_canon(io.out, idx, h_to_abi(s));
+    if (live && owner && l == 1) st_canon(io.out, out_at, h_to_abi(s));
   }
 }
 
@@ -165,6 +203,166 @@ __global__ void __launch_bounds__(256) merkle_index_check_kernel(const u64* idx,
   if (t < k && (idx[t] >> (2 * h))) atomicMin(bad, (unsigned long long)t);
 }
 
+// ---- incremental update (section 7.2n).  The worklist of level l holds the distinct node ids of that level, ascending; the
+// list of level l + 1 is its heads -- the entries whose id >> 2 differs from the left neighbour's -- shifted and compacted in
+// order.  Every kernel after the validation reads the verdict first and does nothing when it is bad.
+constexpr u32 MERKLE_TILE = 128;   // worklist entries a workgroup of the compaction, one a thread: two waves
+
+// the first position whose index is not below 4^h or not above its predecessor
+__global__ void __launch_bounds__(256) merkle_update_check_kernel(const u64* idx, size_t k, u32 h, MerkleCtl* ctl) {
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= k) return;
+  const u64 i = idx[t];
+  if ((i >> (2 * h)) || (t && i <= idx[t - 1])) atomicMin((unsigned long long*)&ctl->bad, (unsigned long long)t);
+}
+// leaves[idx[t]] = values[t]; the worklist of level 0 is the indices themselves
+__global__ void __launch_bounds__(256) merkle_update_scatter_kernel(const u64* idx, const u32x4* values, size_t k, u32x4* leaves,
+                                                                    const MerkleCtl* ctl, u32* list) {
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (ctl->bad != MERKLE_NONE || t >= k) return;
+  const u64 i = idx[t];                                      // below 4^h <= 2^30: the verdict is good
+  leaves[2 * i] = values[2 * t];
+  leaves[2 * i + 1] = values[2 * t + 1];
+  list[t] = (u32)i;
+}
+PM_DEV u32 merkle_head(const u32* list, u32 t, u32 n) { return t < n && (t == 0 || (list[t] >> 2) != (list[t - 1] >> 2)) ? 1u : 0u; }
+// exclusive prefix of v over the MERKLE_TILE threads of a workgroup, and the sum
+PM_DEV u32 merkle_block_exclusive(u32 v, u32& total) {
+  __shared__ u32 wsum[MERKLE_TILE / 64];
+  const u32 lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  u32 inc = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const u32 t = __shfl_up(inc, d);
+    if ((int)lane >= d) inc += t;
+  }
+  if (lane == 63u) wsum[wave] = inc;
+  __syncthreads();
+  u32 before = 0;
+  total = 0;
+#pragma unroll
+  for (u32 w = 0; w < MERKLE_TILE / 64; ++w) {
+    const u32 t = wsum[w];
+    if (w < wave) before += t;
+    total += t;
+  }
+  __syncthreads();                                           // wsum may be written again
+  return before + inc - v;
+}
+// sums[tile] = the heads of one tile of the level's worklist; a tile past the list's end writes 0
+__global__ void __launch_bounds__(MERKLE_TILE) merkle_heads_kernel(const MerkleCtl* ctl, u32 level, const u32* list, u32* sums) {
+  if (ctl->bad != MERKLE_NONE) return;
+  u32 total;
+  merkle_block_exclusive(merkle_head(list, blockIdx.x * MERKLE_TILE + threadIdx.x, ctl->cnt[level]), total);
+  if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+// one workgroup: sums -> their exclusive prefixes; the total is the length of the next level's list and what that level hashes
+__global__ void __launch_bounds__(MERKLE_TILE) merkle_tile_scan_kernel(MerkleCtl* ctl, u32 level, u32* sums, u32 tiles) {
+  if (ctl->bad != MERKLE_NONE) return;
+  const u32 per = (tiles + MERKLE_TILE - 1) / MERKLE_TILE, first = threadIdx.x * per;
+  u32 mine = 0, total;
+  for (u32 j = first; j < first + per && j < tiles; ++j) mine += sums[j];
+  u32 at = merkle_block_exclusive(mine, total);
+  for (u32 j = first; j < first + per && j < tiles; ++j) {
+    const u32 c = sums[j];
+    sums[j] = at;
+    at += c;
+  }
+  if (threadIdx.x == 0) ctl->cnt[level + 1] = total, ctl->hashed += total;
+}
+// next[sums[tile] + rank] = list[t] >> 2 for every head t.  ALONE: the launch is this one tile; it keeps the count itself.
+template <bool ALONE>
+__global__ void __launch_bounds__(MERKLE_TILE) merkle_compact_kernel(MerkleCtl* ctl, u32 level, const u32* list, const u32* sums,
+                                                                     u32* next) {
+  if (ctl->bad != MERKLE_NONE) return;
+  const u32 t = blockIdx.x * MERKLE_TILE + threadIdx.x;
+  const u32 head = merkle_head(list, t, ctl->cnt[level]);
+  u32 total;
+  const u32 rank = merkle_block_exclusive(head, total);
+  if (head) next[(ALONE ? 0u : sums[blockIdx.x]) + rank] = list[t] >> 2;
+  if (ALONE && threadIdx.x == 0) ctl->cnt[level + 1] = total, ctl->hashed += total;
+}
+
+// ---- path verification (section 7.2n): `h` dependent permutations a path; the hash of a level stays in registers and is
+// compared, canonical, with the child the next level holds at the path's position (the root after the last level)
+struct MerkleVerifyIo {
+  const u32x4* paths;         // [k][h][4]
+  const u64* idx;
+  const u32x4* root;
+  u32* status;
+  size_t k;
+  u32 h;
+  u32 capacity[9];            // device form
+};
+PM_DEV bool merkle_same(const Fr& hash, const u32x4* want) {
+  u32 s[8];
+  fe_canon_pack<FrP>(s, h_to_abi(hash));
+  const u32x4 a = want[0], b = want[1];
+  return s[0] == a.x && s[1] == a.y && s[2] == a.z && s[3] == a.w && s[4] == b.x && s[5] == b.y && s[6] == b.z && s[7] == b.w;
+}
+// the element the hash of path level l must equal
+PM_DEV const u32x4* merkle_successor(const MerkleVerifyIo& io, const u32x4* path, u64 leaf, u32 l) {
+  return l + 1 < io.h ? path + 2 * (4 * (size_t)(l + 1) + ((leaf >> (2 * (l + 1))) & 3u)) : io.root;
+}
+
+__global__ void __launch_bounds__(64) merkle_verify_thread_kernel(const HadesTab tab, const MerkleVerifyIo io) {
+  const size_t p = (size_t)blockIdx.x * 64 + threadIdx.x;
+  if (p >= io.k) return;
+  const u64 leaf = io.idx[p];
+  if (leaf >> (2 * io.h)) {
+    io.status[p] = PM_MERKLE_PATH_INDEX;                     // nothing of the path is read
+    return;
+  }
+  const u32x4* const path = io.paths + 8 * (size_t)io.h * p;
+  u32 status = PM_MERKLE_PATH_OK;
+  Fr s[5];
+#pragma unroll 1
+  for (u32 l = 0; l < io.h; ++l) {
+#pragma unroll
+    for (int i = 0; i < 9; ++i) s[0].l[i] = io.capacity[i];
+    s[0] = h_absorb(s[0], fe_zero<FrP>(), tab.ark);
+#pragma unroll
+    for (int j = 1; j < 5; ++j) s[j] = h_absorb(fe_zero<FrP>(), h_to_dev(ld_canon(path, 4 * (size_t)l + j - 1)), tab.ark + 9 * j);
+    h_rounds_thread(s, tab);
+    if (!merkle_same(s[1], merkle_successor(io, path, leaf, l))) {
+      status = PM_MERKLE_PATH_LINK + l;                      // the lowest failing level
+      break;
+    }
+  }
+  io.status[p] = status;
+}
+
+__global__ void __launch_bounds__(64) merkle_verify_wave_kernel(const HadesTab tab, const MerkleVerifyIo io) {
+  const u32 lane = threadIdx.x, base = lane & 32u, l = (lane & 31u) < 25u ? (lane & 31u) : 24u;   // as in hades_wave_kernel
+  const bool owner = (lane & 31u) < 25u;
+  const u32 i = l / 5, j = l - 5 * i;
+  size_t p = 2 * (size_t)blockIdx.x + (base >> 5);
+  const bool live = p < io.k;
+  if (!live) p = io.k - 1;
+  const u32* const mds = (const u32*)tab.mds;
+  const u32* const ark = (const u32*)tab.ark;
+  const Fr key0 = h_lane_const(ark + 9 * j);
+  const u64 leaf = io.idx[p];
+  const bool readable = !(leaf >> (2 * io.h));               // an index out of range: its half runs the rounds on zeros
+  const u32x4* const path = io.paths + 8 * (size_t)io.h * p;
+  u32 status = readable ? PM_MERKLE_PATH_OK : PM_MERKLE_PATH_INDEX;
+#pragma unroll 1
+  for (u32 lv = 0; lv < io.h; ++lv) {
+    Fr s = fe_zero<FrP>();
+    if (j == 0) {
+#pragma unroll
+      for (int k = 0; k < 9; ++k) s.l[k] = io.capacity[k];
+    } else if (readable) {
+      s = h_to_dev(ld_canon(path, 4 * (size_t)lv + j - 1));
+    }
+    s = fe_reduce_weak<FrP>(fe_add<FrP>(s, key0));
+    s = h_rounds_wave(s, mds, ark, tab, base, i, j);
+    if (readable && l == 1 && status == PM_MERKLE_PATH_OK && !merkle_same(s, merkle_successor(io, path, leaf, lv)))
+      status = PM_MERKLE_PATH_LINK + lv;
+  }
+  if (live && owner && l == 1) io.status[p] = status;
+}
+
 // ------------------------------------------------------------------ launches
 // AUTO: the WAVE form below this many permutations, the THREAD form from it on.  Measured at (67, 8), DESIGN.md section 7.2j:
 // THREAD takes 0.48 ms for anything up to one wave a SIMD, WAVE grows by 0.054 ms a 1024 permutations and meets it at 8192.
@@ -172,13 +370,13 @@ constexpr size_t HADES_AUTO_CROSSOVER = 8192;
 
 bool use_wave(size_t n, uint32_t flags) { return flags == PM_HADES_FORM_WAVE || (flags == PM_HADES_FORM_AUTO && n < HADES_AUTO_CROSSOVER); }
 
-template <bool HASH>
-hipError_t launch(const pm_hades_params* p, const HadesIo& io, uint32_t flags, hipStream_t st) {
+template <bool HASH, class Io>
+hipError_t launch(const pm_hades_params* p, const Io& io, uint32_t flags, hipStream_t st) {
   const HadesTab tab = tab_of(p);
   if (use_wave(io.n, flags))
-    hipLaunchKernelGGL((hades_wave_kernel<HASH>), dim3((unsigned)((io.n + 1) / 2)), dim3(64), 0, st, tab, io);
+    hipLaunchKernelGGL((hades_wave_kernel<HASH, Io>), dim3((unsigned)((io.n + 1) / 2)), dim3(64), 0, st, tab, io);
   else
-    hipLaunchKernelGGL((hades_thread_kernel<HASH>), dim3((unsigned)((io.n + 63) / 64)), dim3(64), 0, st, tab, io);
+    hipLaunchKernelGGL((hades_thread_kernel<HASH, Io>), dim3((unsigned)((io.n + 63) / 64)), dim3(64), 0, st, tab, io);
   return hipGetLastError();
 }
 
@@ -361,6 +559,128 @@ extern "C" int pm_poseidon_merkle_paths_dev(pm_ctx* ctx, const void* d_leaves, c
   (void)hipFree(d_bad);
   if (e != hipSuccess) return set_err(ctx, PM_ERR_HIP, std::string("pm_poseidon_merkle_paths_dev: ") + hipGetErrorString(e));
   if (bad != ~0ull) return set_err(ctx, PM_ERR_BAD_ARG, "index " + std::to_string(bad) + " is not below 4^height");
+  return PM_OK;
+}
+
+namespace {
+// the caller's work area of an update: the control block, a sum a tile of the compaction, the worklists of two levels
+struct MerkleWork {
+  size_t sums, list0, list1, bytes;
+};
+MerkleWork merkle_work(size_t k) {
+  const auto a16 = [](size_t x) { return (x + 15) & ~(size_t)15; };
+  MerkleWork w{};
+  if (k == 0) return w;
+  static_assert(sizeof(MerkleCtl) <= 128, "the control block has 128 bytes");
+  w.sums = 128;
+  w.list0 = w.sums + a16(4 * ((k + MERKLE_TILE - 1) / MERKLE_TILE));
+  w.list1 = w.list0 + a16(4 * k);
+  w.bytes = w.list1 + a16(4 * k);
+  return w;
+}
+}  // namespace
+
+extern "C" size_t pm_poseidon_merkle_update_work_bytes(size_t k) { return merkle_work(k).bytes; }
+
+extern "C" int pm_poseidon_merkle_update_dev(pm_ctx* ctx, const pm_hades_params* params, const uint64_t capacity[4], void* d_leaves,
+                                             void* d_tree, uint32_t height, const void* d_indices, const void* d_values, size_t k,
+                                             void* d_work, uint32_t flags, uint64_t* hashed, void* hip_stream) {
+  if (!ctx) return PM_ERR_BAD_ARG;
+  if (int rc = common_fault(ctx, params, flags)) return rc;
+  HadesNodeIo io{};
+  if (int rc = capacity_to_dev(ctx, capacity, io.capacity)) return rc;
+  if (height < 1 || height > PM_POSEIDON_MERKLE_MAX_HEIGHT) return set_err(ctx, PM_ERR_BAD_ARG, "height must be in 1 .. 15");
+  if (hashed) *hashed = 0;
+  if (k == 0) return PM_OK;
+  if (!d_leaves || !d_tree || !d_indices || !d_values || !d_work ||
+      (((uintptr_t)d_leaves | (uintptr_t)d_tree | (uintptr_t)d_values | (uintptr_t)d_work) & 15u) || ((uintptr_t)d_indices & 7u))
+    return set_err(ctx, PM_ERR_BAD_ARG, "null or unaligned device pointer");
+  const size_t leaves = (size_t)1 << (2 * height), nodes = (leaves - 1) / 3;
+  if (k > leaves) return set_err(ctx, PM_ERR_BAD_ARG, "more indices than leaves: they cannot be strictly ascending");
+  const MerkleWork w = merkle_work(k);
+  if (overlap(d_leaves, leaves * 32, d_tree, nodes * 32)) return set_err(ctx, PM_ERR_BAD_ARG, "d_tree overlaps d_leaves");
+  const struct { const void* p; size_t bytes; const char* name; } ins[3] = {{d_values, k * 32, "d_values"}, {d_work, w.bytes, "d_work"},
+                                                                          {d_indices, k * 8, "d_indices"}};
+  for (const auto& in : ins)
+    if (overlap(in.p, in.bytes, d_leaves, leaves * 32) || overlap(in.p, in.bytes, d_tree, nodes * 32))
+      return set_err(ctx, PM_ERR_BAD_ARG, std::string(in.name) + " overlaps the leaves or the tree");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  ProfScope prof(ctx, st, "poseidon_merkle_update");
+  MerkleCtl* const ctl = (MerkleCtl*)d_work;
+  u32* const sums = (u32*)((char*)d_work + w.sums);
+  u32* const list[2] = {(u32*)((char*)d_work + w.list0), (u32*)((char*)d_work + w.list1)};
+  MerkleCtl start{};
+  start.bad = MERKLE_NONE, start.cnt[0] = (u32)k;
+  hipError_t e = hipMemcpyAsync(ctl, &start, sizeof start, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    const unsigned blocks = (unsigned)((k + 255) / 256);
+    hipLaunchKernelGGL(merkle_update_check_kernel, dim3(blocks), dim3(256), 0, st, (const u64*)d_indices, k, height, ctl);
+    hipLaunchKernelGGL(merkle_update_scatter_kernel, dim3(blocks), dim3(256), 0, st, (const u64*)d_indices, (const u32x4*)d_values, k,
+                       (u32x4*)d_leaves, ctl, list[0]);
+    e = hipGetLastError();
+  }
+  const u32x4* below = (const u32x4*)d_leaves;
+  u32x4* level = (u32x4*)d_tree;
+  io.msg_len = 4, io.msg_stride = 4, io.ctl = ctl;
+  size_t bound = k;                                          // of the list of level l - 1: min(k, 4^(height - l + 1))
+  for (uint32_t l = 1; l <= height && e == hipSuccess; ++l) {
+    const u32 tiles = (u32)((bound + MERKLE_TILE - 1) / MERKLE_TILE);
+    const u32* const from = list[(l - 1) & 1];
+    u32* const to = list[l & 1];
+    if (tiles == 1) {
+      hipLaunchKernelGGL(merkle_compact_kernel<true>, dim3(1), dim3(MERKLE_TILE), 0, st, ctl, l - 1, from, (const u32*)sums, to);
+    } else {
+      hipLaunchKernelGGL(merkle_heads_kernel, dim3(tiles), dim3(MERKLE_TILE), 0, st, (const MerkleCtl*)ctl, l - 1, from, sums);
+      hipLaunchKernelGGL(merkle_tile_scan_kernel, dim3(1), dim3(MERKLE_TILE), 0, st, ctl, l - 1, sums, tiles);
+      hipLaunchKernelGGL(merkle_compact_kernel<false>, dim3(tiles), dim3(MERKLE_TILE), 0, st, ctl, l - 1, from, (const u32*)sums, to);
+    }
+    const size_t width = (size_t)1 << (2 * (height - l));
+    bound = k < width ? k : width;
+    io.n = bound, io.ids = to, io.level = l, io.msgs = below, io.out = level;
+    e = launch<true>(params, io, flags, st);
+    below = level, level += 2 * width;
+  }
+  u64 verdict[2] = {0, 0};                                   // MerkleCtl::bad, ::hashed: one copy, one wait
+  if (e == hipSuccess) e = hipMemcpyAsync(verdict, ctl, sizeof verdict, hipMemcpyDeviceToHost, st);
+  const hipError_t waited = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = waited;
+  if (e != hipSuccess) return set_err(ctx, PM_ERR_HIP, std::string("pm_poseidon_merkle_update_dev: ") + hipGetErrorString(e));
+  if (verdict[0] != MERKLE_NONE)
+    return set_err(ctx, PM_ERR_BAD_ARG, "index " + std::to_string(verdict[0]) + " is not below 4^height or not above its predecessor");
+  if (hashed) *hashed = verdict[1];
+  return PM_OK;
+}
+
+extern "C" int pm_poseidon_merkle_verify_dev(pm_ctx* ctx, const pm_hades_params* params, const uint64_t capacity[4],
+                                             const void* d_paths, const void* d_indices, size_t k, uint32_t height, const void* d_root,
+                                             void* d_status, uint32_t flags, void* hip_stream) {
+  if (!ctx) return PM_ERR_BAD_ARG;
+  if (int rc = common_fault(ctx, params, flags)) return rc;
+  MerkleVerifyIo io{};
+  if (int rc = capacity_to_dev(ctx, capacity, io.capacity)) return rc;
+  if (height < 1 || height > PM_POSEIDON_MERKLE_MAX_HEIGHT) return set_err(ctx, PM_ERR_BAD_ARG, "height must be in 1 .. 15");
+  if (k == 0) return PM_OK;
+  if (!d_paths || !d_indices || !d_root || !d_status || (((uintptr_t)d_paths | (uintptr_t)d_root) & 15u) ||
+      ((uintptr_t)d_indices & 7u) || ((uintptr_t)d_status & 3u))
+    return set_err(ctx, PM_ERR_BAD_ARG, "null or unaligned device pointer");
+  if (k > 0x7fffffffu) return set_err(ctx, PM_ERR_LENGTH, "k > 2^31");
+  if (overlap(d_status, k * 4, d_paths, k * height * 128) || overlap(d_status, k * 4, d_indices, k * 8) ||
+      overlap(d_status, k * 4, d_root, 32))
+    return set_err(ctx, PM_ERR_BAD_ARG, "d_status overlaps an input");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  io.paths = (const u32x4*)d_paths, io.idx = (const u64*)d_indices, io.root = (const u32x4*)d_root, io.status = (u32*)d_status;
+  io.k = k, io.h = height;
+  const HadesTab tab = tab_of(params);
+  ProfScope prof(ctx, st, "poseidon_merkle_verify");
+  if (use_wave(k, flags))
+    hipLaunchKernelGGL(merkle_verify_wave_kernel, dim3((unsigned)((k + 1) / 2)), dim3(64), 0, st, tab, io);
+  else
+    hipLaunchKernelGGL(merkle_verify_thread_kernel, dim3((unsigned)((k + 63) / 64)), dim3(64), 0, st, tab, io);
+  PM_HIP(ctx, hipGetLastError());
   return PM_OK;
 }
 

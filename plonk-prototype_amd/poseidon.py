@@ -1,5 +1,6 @@
 """Native Poseidon on the GPU (``pm_hades_*`` / ``pm_poseidon_*``): the Hades permutation of width 5
-outside a circuit, the modelled sponge of rate 4 on top of it and an arity-4 Merkle tree with batched sibling paths.
+outside a circuit, the modelled sponge of rate 4 on top of it and an arity-4 Merkle tree with batched sibling paths, in-place
+leaf updates that hash only the changed leaves' ancestors and the bulk verification of paths (section 7.2n).
 
 Field elements cross this interface as Montgomery limbs, ``uint64`` arrays with a last axis of 4 (``field.fr_vec_to_limbs``);
 constants and the capacity may also be given as Python integers.  With ``Hades.from_key`` the constants are those of a key's own
@@ -162,15 +163,48 @@ class Hades:
         d_leaves = DeviceVector.from_host(self.ctx, a)
         d_tree = DeviceVector(self.ctx, (4 ** height - 1) // 3)
         self.merkle_dev(d_leaves.ptr, height, d_tree.ptr, capacity, form)
-        return MerkleTree(self.ctx, d_leaves, d_tree, height)
+        return MerkleTree(self.ctx, d_leaves, d_tree, height, hades=self, capacity=capacity)
+
+    def verify_paths_dev(self, d_paths: int, d_indices: int, k: int, height: int, d_root: int, d_status: int, capacity=0,
+                         form="auto", stream: int = 0):
+        """``pm_poseidon_merkle_verify_dev``: k paths of ``height`` x 4 elements -> k uint32 at ``d_status``; asynchronous"""
+        c = self.ctx
+        c._check(c._lib.pm_poseidon_merkle_verify_dev(c._h, self._h, _p(_capacity(capacity)), C.c_void_p(d_paths),
+                                                      C.c_void_p(d_indices), k, height, C.c_void_p(d_root), C.c_void_p(d_status),
+                                                      _form(form), C.c_void_p(stream)))
+
+    def verify_paths(self, paths, indices, root, height: int, capacity=0, form="auto") -> np.ndarray:
+        """[k, height, 4, 4] limbs as ``MerkleTree.paths`` gives them, k leaf indices and the root ([4] limbs or an integer)
+        -> [k] uint32: 0 = the path folds to the root, 1 = the index is not below 4^height, 2 + l = the hash of level l is
+        not the child the next level (the root after the last) holds at the path's position"""
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        k = idx.shape[0]
+        if k == 0:
+            return np.zeros(0, np.uint32)
+        a = _elements(paths, k * height * 4)
+        d_paths, d_root = DeviceVector.from_host(self.ctx, a), DeviceVector.from_host(self.ctx, _capacity(root).reshape(1, 4))
+        d_idx, d_status = _upload_words(self.ctx, idx), DeviceVector(self.ctx, (k + 7) // 8)
+        try:
+            self.verify_paths_dev(d_paths.ptr, d_idx.ptr, k, height, d_root.ptr, d_status.ptr, capacity, form)
+            return d_status.to_host().view(np.uint32).reshape(-1)[:k].copy()
+        finally:
+            d_paths.free(), d_root.free(), d_idx.free(), d_status.free()
+
+
+def _upload_words(ctx, words: np.ndarray) -> DeviceVector:
+    """k uint64 -> device memory, padded to whole elements of 32 bytes"""
+    return DeviceVector.from_host(ctx, np.concatenate([words, np.zeros((-words.shape[0]) % 4, np.uint64)]))
 
 
 class MerkleTree:
     """An arity-4 Poseidon tree in device memory: ``leaves`` (4^height elements) and ``nodes`` (levels 1..height one after the
-    other, the root last) as :class:`DeviceVector`; ``level(l)`` is a view of one level."""
+    other, the root last) as :class:`DeviceVector`; ``level(l)`` is a view of one level.  ``hades`` and ``capacity`` say how it
+    was hashed (``Hades.merkle`` passes them): ``update`` and ``verify`` need them."""
 
-    def __init__(self, ctx: Context, leaves: DeviceVector, nodes: DeviceVector, height: int):
+    def __init__(self, ctx: Context, leaves: DeviceVector, nodes: DeviceVector, height: int, hades: "Hades | None" = None,
+                 capacity=0):
         self.ctx, self.leaves, self.nodes, self.height = ctx, leaves, nodes, height
+        self.hades, self.capacity = hades, capacity
 
     def level(self, l: int) -> DeviceVector:
         if not 0 <= l <= self.height:
@@ -204,6 +238,47 @@ class MerkleTree:
             return out.to_host().reshape(k, self.height, 4, 4)
         finally:
             d_idx.free(), out.free()
+
+    def _hashed_by(self) -> "Hades":
+        if self.hades is None:
+            raise ValueError("this tree does not know its Hades constants: build it with Hades.merkle or pass hades=")
+        return self.hades
+
+    def update_dev(self, d_indices: int, d_values: int, k: int, d_work: int, form="auto", stream: int = 0) -> int:
+        """``pm_poseidon_merkle_update_dev``: k strictly ascending uint64 indices and k elements in device memory, ``d_work``
+        of ``pm_poseidon_merkle_update_work_bytes(k)`` bytes -> the permutations run; waits for the stream"""
+        h, c = self._hashed_by(), self.ctx
+        hashed = C.c_uint64(0)
+        c._check(c._lib.pm_poseidon_merkle_update_dev(c._h, h._h, _p(_capacity(self.capacity)), C.c_void_p(self.leaves.ptr),
+                                                      C.c_void_p(self.nodes.ptr), self.height, C.c_void_p(d_indices),
+                                                      C.c_void_p(d_values), k, C.c_void_p(d_work), _form(form),
+                                                      C.byref(hashed), C.c_void_p(stream)))
+        return hashed.value
+
+    def update(self, indices, values, form="auto") -> int:
+        """leaves[indices[j]] = values[j] ([k, 4] limbs or integers), then only the ancestors of the changed leaves are hashed
+        again -> the permutations run.  Any order of indices; a duplicate is a ``ValueError``."""
+        self._hashed_by()
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        k = idx.shape[0]
+        if k == 0:
+            return 0
+        vals = _elements(values, k)
+        order = np.argsort(idx, kind="stable")
+        idx, vals = idx[order], np.ascontiguousarray(vals[order])
+        if (idx[1:] == idx[:-1]).any():
+            raise ValueError("duplicate leaf indices")
+        d_idx, d_vals = _upload_words(self.ctx, idx), DeviceVector.from_host(self.ctx, vals)
+        work = DeviceVector(self.ctx, (self.ctx._lib.pm_poseidon_merkle_update_work_bytes(k) + 31) // 32)
+        try:
+            return self.update_dev(d_idx.ptr, d_vals.ptr, k, work.ptr, form)
+        finally:
+            d_idx.free(), d_vals.free(), work.free()
+
+    def verify(self, paths, indices, root=None, form="auto") -> np.ndarray:
+        """``Hades.verify_paths`` with this tree's constants, capacity and height; ``root`` defaults to the current root"""
+        return self._hashed_by().verify_paths(paths, indices, self.root if root is None else root, self.height, self.capacity,
+                                              form)
 
     def free(self):
         self.leaves.free(), self.nodes.free()
