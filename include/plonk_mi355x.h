@@ -1019,6 +1019,64 @@ int pm_schnorr_verify_host(const uint64_t g_xy[8], uint32_t rounds, uint32_t ful
 int pm_schnorr_verify_batch_dev(pm_ctx* ctx, const pm_jubjub_base* g, const pm_hades_params* params, const uint64_t capacity[4],
                                 const void* d_pks_xy, const void* d_msgs, const void* d_sigs, const void* d_weights, size_t n,
                                 uint32_t scalar_form, void* d_sum_xy, uint32_t* result, size_t* first_bad, void* hip_stream);
+/* ---- Poseidon cipher on JubJub keys: batch encryption, decryption and note scanning ------------------
+ * Encrypting a note to its recipient, and the recipient's side: trial-decrypting every note of a ledger under one viewing key.
+ * This is the SHAPE of dusk-poseidon's PoseidonCipher as remembered -- prior knowledge that nothing in this repository pins,
+ * exactly like the sponge and the Schnorr signature above: it is NOT claimed to produce dusk-poseidon's bytes.
+ *   P        the Hades permutation of `params` (width 5); L = msg_len, the message capacity, 1 .. 4 (dusk's is 2);
+ *            S = (S.x, S.y) a JubJub point, the shared secret; init = [2^32, L, S.x, S.y, nonce].
+ *   encrypt  s = P(init); for i < L: s[1 + i] += m[i], c[i] = s[1 + i]; s = P(s); c[L] = s[1].  A cipher is L + 1 elements.
+ *   decrypt  s = P(init); for i < L: m[i] = c[i] - s[1 + i], s[1 + i] = c[i]; s = P(s); accepted when c[L] = s[1].
+ *   a note   (R, nonce, c): the sender picks an ephemeral integer e, sends R = e G and encrypts under S = e PK, PK = vk G the
+ *            recipient's key; the recipient holds the viewing key vk and recovers S = vk R.  Multipliers are the exact integers
+ *            below r, as everywhere in pm_jubjub_*: no cofactor is cleared and nothing is reduced modulo l.
+ * The status of a decryption is the LOWEST that applies:
+ *   PM_CIPHER_OK     the tag matches
+ *   PM_CIPHER_POINT  the secret (decrypt) or the ephemeral key R (scan) is off the curve or has a coordinate >= r
+ *   PM_CIPHER_RANGE  the nonce or a cipher word is not below r
+ *   PM_CIPHER_TAG    the tag does not match: not this key's note, or tampered with
+ * For any status but PM_CIPHER_OK the L message words written are zero: the output bytes are deterministic and a wrong key's
+ * garbage never leaves the device.
+ * Elements and coordinates are canonical Montgomery, 32 bytes.  The device calls take addresses on the context's GPU (16-byte
+ * aligned; NULL among the required ones is PM_ERR_BAD_ARG), run on `hip_stream` (NULL = the context's stream) and launch
+ * nothing for n = 0 (PM_OK, *n_ok = 0).  msg_len outside 1 .. 4 is PM_ERR_BAD_ARG.  d_status receives n uint32 and may be NULL;
+ * n_ok may be NULL, and with it the call WAITS for the stream and returns the count of status 0.  With both NULL, decrypt and
+ * scan still write the messages, zero where refused.
+ *   pm_poseidon_cipher_encrypt_dev: n secrets (two elements each), nonces and messages (L elements each) -> n ciphers (L + 1
+ *     each).  One kernel, a thread a note, no allocation; asynchronous.  The secrets and messages are NOT validated: for
+ *     anything that is not a curve point or not below r the output is unspecified, but the call does not fault (the rule of
+ *     pm_jubjub_mul_dev).
+ *   pm_poseidon_cipher_decrypt_dev: n secrets, nonces and ciphers -> n messages at d_msgs_out and their status.  One kernel;
+ *     with n_ok it allocates the counter and releases it before it returns.
+ *   pm_poseidon_cipher_scan_dev: n notes (ephemeral keys at d_ephemeral_xy, two elements each) under ONE viewing key, a host
+ *     scalar in `scalar_form` (PM_SCALAR_MONTGOMERY or PM_SCALAR_CANONICAL, anything else is PM_ERR_BAD_ARG, as is a key that
+ *     is not below r).  The 64 signed base-16 digits of vk are recoded once on the host and travel in the kernel's arguments:
+ *     every thread multiplies by the same scalar, so a digit, its sign and the zero digit are wave-uniform.  Two kernels a
+ *     stride of the threads in flight: the ladder vk R over the thread's own table 1 R .. 8 R with ONE inversion (S is hashed, so
+ *     it must be affine), then the decryption with the curve test of R.  The call allocates the tables of those threads (1216
+ *     bytes each) and releases them before it returns, which WAITS for the device, as pm_jubjub_mul_dev does.  R is not
+ *     checked to lie in the prime-order subgroup.  NOT hardened against side channels: the table addresses depend on vk.
+ * The two host forms need no context and no GPU (csrc/host_field.h) and take the Hades constants as pm_hades_permute_host does.
+ * PM_ERR_BAD_ARG for constants _create refuses, msg_len outside 1 .. 4, NULL, and on encrypt for a secret off the curve or a
+ * word that is not below r.  pm_poseidon_cipher_decrypt_host writes the status; inputs it can judge are not errors. */
+#define PM_CIPHER_OK 0u
+#define PM_CIPHER_POINT 1u
+#define PM_CIPHER_RANGE 2u
+#define PM_CIPHER_TAG 3u
+int pm_poseidon_cipher_encrypt_dev(pm_ctx* ctx, const pm_hades_params* params, const void* d_secrets_xy, const void* d_nonces,
+                                   const void* d_msgs, uint32_t msg_len, size_t n, void* d_ciphers, void* hip_stream);
+int pm_poseidon_cipher_decrypt_dev(pm_ctx* ctx, const pm_hades_params* params, const void* d_secrets_xy, const void* d_nonces,
+                                   const void* d_ciphers, uint32_t msg_len, size_t n, void* d_msgs_out, void* d_status,
+                                   size_t* n_ok, void* hip_stream);
+int pm_poseidon_cipher_scan_dev(pm_ctx* ctx, const pm_hades_params* params, const uint64_t view_key[4], uint32_t scalar_form,
+                                const void* d_ephemeral_xy, const void* d_nonces, const void* d_ciphers, uint32_t msg_len, size_t n,
+                                void* d_msgs_out, void* d_status, size_t* n_ok, void* hip_stream);
+int pm_poseidon_cipher_encrypt_host(uint32_t rounds, uint32_t full_rounds, const uint64_t* ark, const uint64_t* mds, uint32_t n_mds,
+                                    const uint64_t secret_xy[8], const uint64_t nonce[4], const uint64_t* msg, uint32_t msg_len,
+                                    uint64_t* cipher_out);
+int pm_poseidon_cipher_decrypt_host(uint32_t rounds, uint32_t full_rounds, const uint64_t* ark, const uint64_t* mds, uint32_t n_mds,
+                                    const uint64_t secret_xy[8], const uint64_t nonce[4], const uint64_t* cipher, uint32_t msg_len,
+                                    uint64_t* msg_out, uint32_t* status);
 /* Proof::to_bytes: 11 x 48-byte compressed G1, then the 16 scalars of ProofEvaluations::to_bytes. */
 int pm_plonk_proof_to_bytes(const pm_plonk_proof* proof, uint8_t out[PM_PLONK_PROOF_BYTES]);
 /* ---- The prover with coefficient-range ownership end to end (SURVEY.md section 8e row 3 + 8f N5; configs[4]) ----------
@@ -1173,6 +1231,12 @@ int pm_test_jubjub_scalar_op(pm_ctx* ctx, int op, const uint64_t* a, const uint6
 int pm_test_host_jubjub_scalar_op(int op, const uint64_t* a, const uint64_t* b, const uint64_t* c, uint64_t* out, size_t n);
 /* Signatures pm_schnorr_verify_dev has in flight at once on this context's GPU: beyond it the kernel walks n in strides. */
 int pm_test_schnorr_stride(pm_ctx* ctx, size_t* stride);
+/* Notes pm_poseidon_cipher_scan_dev has in flight at once on this context's GPU: beyond it the call walks n in strides. */
+int pm_test_cipher_stride(pm_ctx* ctx, size_t* stride);
+/* Pure host, no context: the recoding of a viewing key that pm_poseidon_cipher_scan_dev passes to its kernel, 64 signed base-16
+ * digits with the TOP one first: digits[k] = d_(63 - k), sum d_w 16^w = the integer of the key, every |d_w| <= 8.
+ * PM_ERR_BAD_ARG for a key that is not below r, an unknown scalar_form, NULL. */
+int pm_test_cipher_digits(const uint64_t view_key[4], uint32_t scalar_form, int8_t digits[64]);
 /* Pure host, no context: the plan of pm_jubjub_msm_dev for n points and `batch` vectors (csrc/jubjub_msm_plan.h); window_bits as
  * the option "jubjub_msm_window_bits" (0 = the rule); num_cus is accepted for symmetry with the other plan hooks and not used:
  * this plan does not depend on the machine.  out[8] = {0 window bits c, 1 windows of a scalar = ceil(257 / c), 2 buckets per

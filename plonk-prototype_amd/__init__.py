@@ -11,7 +11,9 @@ from ._lib import (BackendMissing, NTT_COSET, NTT_INVERSE, NTT_TRANSPOSED, SCALA
 from .host import (CommitKey, Context, DeviceVector, Error, EvaluationDomain, LagrangeCommitKey, Polynomial,  # noqa: F401
                    msm_variable_base, g1_scalar_mul,
                    g1_fold, g1_to_affine, g1_compress, g1_decompress, domain_info, ntt_plan)
-from . import field, jubjub, poseidon, prover, schnorr, srs, synthetic, transcript  # noqa: F401,E402
+from . import cipher, field, jubjub, poseidon, prover, schnorr, srs, synthetic, transcript  # noqa: F401,E402
+from .cipher import (CIPHER_REASONS, PoseidonCipher, poseidon_cipher_decrypt_host,  # noqa: F401,E402
+                     poseidon_cipher_encrypt_host)
 from .jubjub import (JUBJUB_GENERATOR, JubJubBase, jubjub_add_host, jubjub_check, jubjub_commit,  # noqa: F401,E402
                      jubjub_commit_dev, jubjub_msm, jubjub_msm_dev, jubjub_msm_host, jubjub_mul, jubjub_mul_dev,
                      jubjub_mul_host)

@@ -230,6 +230,16 @@ SIGNATURES = {
                                          u32p]),
     "pm_schnorr_verify_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, u64p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_size_t, C.c_uint32, C.c_void_p, u32p, C.POINTER(C.c_size_t), C.c_void_p]),
+    "pm_poseidon_cipher_encrypt_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_size_t,
+                                                 C.c_void_p, C.c_void_p]),
+    "pm_poseidon_cipher_decrypt_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_size_t,
+                                                 C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), C.c_void_p]),
+    "pm_poseidon_cipher_scan_dev": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), C.c_void_p]),
+    "pm_poseidon_cipher_encrypt_host": (C.c_int, [C.c_uint32, C.c_uint32, u64p, u64p, C.c_uint32, u64p, u64p, u64p, C.c_uint32,
+                                                  u64p]),
+    "pm_poseidon_cipher_decrypt_host": (C.c_int, [C.c_uint32, C.c_uint32, u64p, u64p, C.c_uint32, u64p, u64p, u64p, C.c_uint32,
+                                                  u64p, u32p]),
     "pm_plonk_proof_to_bytes": (C.c_int, [C.POINTER(PlonkProof), C.POINTER(C.c_uint8)]),
     "pm_plonk_batch_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
     "pm_plonk_batch_free": (None, [C.c_void_p, C.c_void_p]),
@@ -266,6 +276,8 @@ SIGNATURES = {
     "pm_test_jubjub_scalar_op": (C.c_int, [C.c_void_p, C.c_int, u64p, u64p, u64p, u64p, C.c_size_t]),
     "pm_test_host_jubjub_scalar_op": (C.c_int, [C.c_int, u64p, u64p, u64p, u64p, C.c_size_t]),
     "pm_test_schnorr_stride": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),
+    "pm_test_cipher_stride": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),
+    "pm_test_cipher_digits": (C.c_int, [u64p, C.c_uint32, C.POINTER(C.c_int8)]),
     "pm_test_jubjub_msm_plan": (C.c_int, [C.c_size_t, C.c_uint32, C.c_long, C.c_uint32, u64p]),
     "pm_test_jubjub_msm_digits": (C.c_int, [u64p, C.c_uint32, C.POINTER(C.c_int32), u32p]),
     "pm_test_ntt_plan": (C.c_int, [C.c_uint32, C.c_uint32, C.c_long, C.c_long, C.c_long, C.c_uint32, C.POINTER(C.c_uint32)]),
@@ -331,6 +343,10 @@ MERKLE_PATH_OK, MERKLE_PATH_INDEX, MERKLE_PATH_LINK = 0, 1, 2
 # pm_schnorr_verify_*: why a signature is not valid, the lowest that applies
 SCHNORR_OK, SCHNORR_U_RANGE, SCHNORR_R_POINT, SCHNORR_PK_POINT, SCHNORR_EQUATION = 0, 1, 2, 3, 4
 SCHNORR_REASONS = {1: "u_range", 2: "r_point", 3: "pk_point", 4: "equation"}
+# pm_poseidon_cipher_decrypt_* / _scan_dev: the status of a decryption, the lowest that applies
+CIPHER_OK, CIPHER_POINT, CIPHER_RANGE, CIPHER_TAG = 0, 1, 2, 3
+CIPHER_REASONS = {1: "point", 2: "range", 3: "tag"}
+CIPHER_MAX_LEN = 4            # message words of a cipher: the rate of the width-5 permutation
 
 # pm_jubjub_msm_dev: the window widths the option "jubjub_msm_window_bits" may force
 JUBJUB_MSM_MIN_WINDOW_BITS, JUBJUB_MSM_MAX_WINDOW_BITS = 4, 16

@@ -1,0 +1,230 @@
+"""The Poseidon cipher on JubJub keys (``pm_poseidon_cipher_*``): batch encryption and decryption of
+notes on the GPU, and the recipient's side of a private ledger -- :meth:`PoseidonCipher.scan`, the trial decryption of every
+note under one viewing key.
+
+With ``P`` the Hades permutation, ``L`` the message capacity (1 .. 4) and ``S`` a JubJub point, the shared secret::
+
+    init    = [2^32, L, S.x, S.y, nonce]
+    encrypt : s = P(init); s[1 + i] += m[i], c[i] = s[1 + i] (i < L); s = P(s); c[L] = s[1]
+    decrypt : s = P(init); m[i] = c[i] - s[1 + i], s[1 + i] = c[i]; s = P(s); accepted when c[L] == s[1]
+
+A note is ``(R, nonce, c)``: the sender picks an ephemeral integer ``e``, sends ``R = e G`` and encrypts under ``S = e PK`` with
+``PK = vk G`` the recipient's key; the recipient recovers ``S = vk R``.  Multipliers are exact integers below ``r``.
+
+This is the shape of dusk-poseidon's ``PoseidonCipher`` as remembered: prior knowledge that nothing in this repository pins,
+like the sponge of :mod:`.poseidon` and the signature of :mod:`.schnorr`.  It is not claimed to produce dusk-poseidon's bytes.
+
+Elements, coordinates, nonces and cipher words are Montgomery limbs (``uint64``, last axis 4) or Python integers, converted.  A
+status is 0 when the tag matches, else a key of ``CIPHER_REASONS``, the lowest that applies; the messages of a refused note come
+back as zeros.
+
+The scan is NOT hardened against side channels: table addresses depend on the viewing key."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .host import DeviceVector, _p
+from .jubjub import JubJubBase, _points, _scalars, jubjub_mul
+from .poseidon import WIDTH, Hades, _elements
+
+CIPHER_REASONS = _lib.CIPHER_REASONS
+
+
+def _check_len(msg_len) -> int:
+    if not isinstance(msg_len, (int, np.integer)) or not 1 <= msg_len <= _lib.CIPHER_MAX_LEN:
+        raise ValueError("msg_len must be 1 .. 4")
+    return int(msg_len)
+
+
+def _words(x, width: int, pad: bool, what: str) -> np.ndarray:
+    """limbs ``[n, k, 4]`` or integers ``[n][k]`` (``[n]`` is k = 1) -> ``[n, width, 4]``; k < width is padded with zeros when
+    ``pad``, anything else raises"""
+    if isinstance(x, np.ndarray) and x.dtype != np.uint64 and x.dtype != object:
+        raise ValueError(f"{what}: limb arrays are uint64")
+    if isinstance(x, np.ndarray) and x.dtype == np.uint64:
+        if x.ndim != 3 or x.shape[2] != 4:
+            raise ValueError(f"{what}: limbs have the shape [n, k, 4]")
+        a = np.ascontiguousarray(x)
+    else:
+        obj = np.asarray(x, dtype=object)
+        if obj.ndim == 1:
+            obj = obj.reshape(-1, 1)
+        if obj.ndim != 2:
+            raise ValueError(f"{what}: integers have the shape [n] or [n][k]")
+        a = _elements(obj).reshape(obj.shape[0], obj.shape[1], 4) if obj.size else np.zeros((obj.shape[0], obj.shape[1], 4), np.uint64)
+    k = a.shape[1]
+    if k > width or k == 0 or (k < width and not pad):
+        raise ValueError(f"{what}: {k} words where {'at most ' if pad else ''}{width} are expected")
+    if k < width:
+        a = np.concatenate([a, np.zeros((a.shape[0], width - k, 4), np.uint64)], axis=1)
+    return a
+
+
+def _one(x):
+    """the words of ONE note, limbs ``[k, 4]`` or k integers, as a batch of one"""
+    if isinstance(x, np.ndarray) and x.dtype == np.uint64 and x.ndim == 2:
+        return x[None]
+    return [list(x)] if not isinstance(x, np.ndarray) else x
+
+
+def _nonces(x) -> np.ndarray:
+    if isinstance(x, np.ndarray) and x.dtype != np.uint64 and x.dtype != object:
+        raise ValueError("nonces: limb arrays are uint64")
+    return _elements(x)
+
+
+def _host_consts(ark, mds, rounds):
+    a, m = _elements(ark), _elements(mds)
+    if a.shape[0] != WIDTH * rounds or m.shape[0] % 25 or m.shape[0] == 0:
+        raise ValueError("rounds x 5 round keys and whole 5 x 5 matrices")
+    return a, m
+
+
+def poseidon_cipher_encrypt_host(ark, mds, secret, nonce, message, msg_len: int = 2, rounds: int = 67, full_rounds: int = 8) -> np.ndarray:
+    """``pm_poseidon_cipher_encrypt_host``: one note on the CPU, no context -> ``[msg_len + 1, 4]`` limbs.  A message shorter
+    than ``msg_len`` is padded with zeros."""
+    L = _check_len(msg_len)
+    a, m = _host_consts(ark, mds, rounds)
+    s, k = _points(secret), _nonces(nonce)
+    msg = _words(_one(message), L, True, "message")
+    if s.shape[0] != 1 or k.shape[0] != 1 or msg.shape[0] != 1:
+        raise ValueError("one secret, one nonce and one message")
+    out = np.zeros((L + 1, 4), np.uint64)
+    rc = _lib.load().pm_poseidon_cipher_encrypt_host(rounds, full_rounds, _p(a), _p(m), m.shape[0] // 25, _p(s), _p(k), _p(msg), L, _p(out))
+    if rc != _lib.PM_OK:
+        raise ValueError("pm_poseidon_cipher_encrypt_host refused its arguments")
+    return out
+
+
+def poseidon_cipher_decrypt_host(ark, mds, secret, nonce, cipher, msg_len: int = 2, rounds: int = 67, full_rounds: int = 8):
+    """``pm_poseidon_cipher_decrypt_host``: one note on the CPU, no context -> ``(message [msg_len, 4], status)``"""
+    L = _check_len(msg_len)
+    a, m = _host_consts(ark, mds, rounds)
+    s, k = _points(secret), _nonces(nonce)
+    c = _words(_one(cipher), L + 1, False, "cipher")
+    if s.shape[0] != 1 or k.shape[0] != 1 or c.shape[0] != 1:
+        raise ValueError("one secret, one nonce and one cipher")
+    out, status = np.zeros((L, 4), np.uint64), C.c_uint32()
+    rc = _lib.load().pm_poseidon_cipher_decrypt_host(rounds, full_rounds, _p(a), _p(m), m.shape[0] // 25, _p(s), _p(k), _p(c), L, _p(out),
+                                                     C.byref(status))
+    if rc != _lib.PM_OK:
+        raise ValueError("pm_poseidon_cipher_decrypt_host refused its arguments")
+    return out, int(status.value)
+
+
+class PoseidonCipher:
+    """The cipher over one set of Hades constants on a context's GPU.
+
+    ``PoseidonCipher(hades, msg_len=2)``: ``hades`` a :class:`Hades` (``Hades.from_key`` handles work unchanged), ``msg_len`` the
+    message capacity L, 1 .. 4."""
+
+    def __init__(self, hades: Hades, msg_len: int = 2):
+        if not isinstance(hades, Hades):
+            raise ValueError("hades must be a Hades handle")
+        self.ctx, self.hades, self.msg_len = hades.ctx, hades, _check_len(msg_len)
+
+    # ------------------------------------------------------------------ device forms (addresses as integers)
+    def encrypt_dev(self, d_secrets: int, d_nonces: int, d_msgs: int, n: int, d_ciphers: int, stream: int = 0):
+        """``pm_poseidon_cipher_encrypt_dev``: n secrets (2 elements each), nonces and messages (L each) -> n ciphers (L + 1
+        each) at ``d_ciphers``; asynchronous.  Secrets and messages are not validated."""
+        c = self.ctx
+        c._check(c._lib.pm_poseidon_cipher_encrypt_dev(c._h, self.hades._h, C.c_void_p(d_secrets), C.c_void_p(d_nonces), C.c_void_p(d_msgs),
+                                                       self.msg_len, n, C.c_void_p(d_ciphers), C.c_void_p(stream)))
+
+    def decrypt_dev(self, d_secrets: int, d_nonces: int, d_ciphers: int, n: int, d_msgs: int, d_status: int = 0,
+                    want_n_ok: bool = True, stream: int = 0):
+        """``pm_poseidon_cipher_decrypt_dev``: n messages (L elements each, zero where refused) at ``d_msgs`` and n ``uint32`` at
+        ``d_status`` (0 = not wanted).  Returns the count of status 0 and waits for the stream, or None, asynchronous, when
+        ``want_n_ok`` is false."""
+        c = self.ctx
+        ok = C.c_size_t()
+        c._check(c._lib.pm_poseidon_cipher_decrypt_dev(c._h, self.hades._h, C.c_void_p(d_secrets), C.c_void_p(d_nonces), C.c_void_p(d_ciphers),
+                                                       self.msg_len, n, C.c_void_p(d_msgs), C.c_void_p(d_status) if d_status else None,
+                                                       C.byref(ok) if want_n_ok else None, C.c_void_p(stream)))
+        return int(ok.value) if want_n_ok else None
+
+    def scan_dev(self, view_key, d_ephemeral: int, d_nonces: int, d_ciphers: int, n: int, d_msgs: int, d_status: int = 0,
+                 want_n_ok: bool = True, scalar_form: int | None = None, stream: int = 0):
+        """``pm_poseidon_cipher_scan_dev``: as :meth:`decrypt_dev` with the secrets ``vk R_i`` computed from the ephemeral keys at
+        ``d_ephemeral`` under ONE viewing key, an integer (canonical) or ``[4]`` limbs (Montgomery unless ``scalar_form`` says
+        otherwise).  Waits for the device.  Not hardened against side channels."""
+        vk, form = _scalars(view_key)
+        if vk.shape[0] != 1:
+            raise ValueError("one viewing key")
+        c = self.ctx
+        ok = C.c_size_t()
+        c._check(c._lib.pm_poseidon_cipher_scan_dev(c._h, self.hades._h, _p(vk), form if scalar_form is None else scalar_form,
+                                                    C.c_void_p(d_ephemeral), C.c_void_p(d_nonces), C.c_void_p(d_ciphers), self.msg_len, n,
+                                                    C.c_void_p(d_msgs), C.c_void_p(d_status) if d_status else None,
+                                                    C.byref(ok) if want_n_ok else None, C.c_void_p(stream)))
+        return int(ok.value) if want_n_ok else None
+
+    # ------------------------------------------------------------------ host arrays in, host arrays out
+    def encrypt(self, secrets, nonces, messages) -> np.ndarray:
+        """-> ``[n, L + 1, 4]`` limbs.  ``messages``: ``[n, k, 4]`` limbs or ``[n][k]`` integers, k <= L, padded with zeros."""
+        L = self.msg_len
+        s, k, m = _points(secrets), _nonces(nonces), _words(messages, L, True, "messages")
+        n = s.shape[0]
+        if k.shape[0] != n or m.shape[0] != n:
+            raise ValueError("one nonce and one message per secret")
+        if n == 0:
+            return np.zeros((0, L + 1, 4), np.uint64)
+        ds, dk, dm = (DeviceVector.from_host(self.ctx, x.reshape(-1, 4)) for x in (s, k, m))
+        out = DeviceVector(self.ctx, (L + 1) * n)
+        try:
+            self.encrypt_dev(ds.ptr, dk.ptr, dm.ptr, n, out.ptr)
+            return out.to_host().reshape(n, L + 1, 4)
+        finally:
+            for x in (ds, dk, dm, out):
+                x.free()
+
+    def _open(self, first, nonces, ciphers, call):
+        """the common half of decrypt and scan: ``first`` is [n, 2, 4], ``call(d_first, d_nonces, d_ciphers, n, d_msgs, d_status)``"""
+        L = self.msg_len
+        k, c = _nonces(nonces), _words(ciphers, L + 1, False, "ciphers")
+        n = first.shape[0]
+        if k.shape[0] != n or c.shape[0] != n:
+            raise ValueError("one nonce and one cipher per point")
+        if n == 0:
+            return np.zeros((0, L, 4), np.uint64), np.zeros(0, np.uint32)
+        dp, dk, dc = (DeviceVector.from_host(self.ctx, x.reshape(-1, 4)) for x in (first, k, c))
+        dm, ds = DeviceVector(self.ctx, L * n), DeviceVector(self.ctx, (n + 7) // 8)     # n uint32 in 32-byte elements
+        try:
+            call(dp.ptr, dk.ptr, dc.ptr, n, dm.ptr, ds.ptr)
+            return dm.to_host().reshape(n, L, 4), ds.to_host().view(np.uint32).reshape(-1)[:n].copy()
+        finally:
+            for x in (dp, dk, dc, dm, ds):
+                x.free()
+
+    def decrypt(self, secrets, nonces, ciphers):
+        """-> ``(messages [n, L, 4], status [n] uint32)``: status 0 = the tag matches, else a key of ``CIPHER_REASONS``; the
+        messages of a refused note are zero"""
+        return self._open(_points(secrets), nonces, ciphers, lambda *a: self.decrypt_dev(*a, want_n_ok=False))
+
+    def scan(self, view_key, ephemeral_keys, nonces, ciphers, scalar_form: int | None = None):
+        """The notes ``(R_i, nonce_i, c_i)`` under one viewing key -> ``(messages, status)`` as :meth:`decrypt`: status 0 marks
+        the key's own notes, 3 the others.  ``view_key``: an integer or ``[4]`` Montgomery limbs."""
+        vk, form = _scalars(view_key)
+        if vk.shape[0] != 1:
+            raise ValueError("one viewing key")
+        form = form if scalar_form is None else scalar_form
+        return self._open(_points(ephemeral_keys), nonces, ciphers,
+                          lambda *a: self.scan_dev(vk, *a, want_n_ok=False, scalar_form=form))
+
+    def encrypt_to(self, g: JubJubBase, public_keys, ephemeral_secrets, nonces, messages):
+        """The sender's side, composed from ``g.mul``, :func:`~.jubjub.jubjub_mul` and :meth:`encrypt`: note i is encrypted to
+        ``public_keys[i]`` under the ephemeral integer ``ephemeral_secrets[i]`` -> ``(ephemeral_keys [n, 2, 4] = e_i G, ciphers)``,
+        what :meth:`scan` reads.  Neither the keys nor the secrets are validated; the ephemeral secrets are the caller's, as
+        nonces are in :mod:`.schnorr`."""
+        if g.ctx is not self.ctx:
+            raise ValueError("the base and the constants belong to different contexts")
+        pk = _points(public_keys)
+        e, _ = _scalars(ephemeral_secrets)
+        if pk.shape[0] != e.shape[0]:
+            raise ValueError("one ephemeral secret per public key")
+        if e.shape[0] == 0:
+            return np.zeros((0, 2, 4), np.uint64), self.encrypt(pk, nonces, messages)
+        return g.mul(ephemeral_secrets), self.encrypt(jubjub_mul(self.ctx, pk, ephemeral_secrets), nonces, messages)

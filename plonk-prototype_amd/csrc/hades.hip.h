@@ -1,5 +1,5 @@
-// The Hades permutation of width 5 one lane at a time, shared by hades.hip (native Poseidon) and
-// schnorr.hip (the challenge of a signature, section 7.2l): the handle, the definition on the host, the per-lane rounds and
+// The Hades permutation of width 5 one lane at a time, shared by hades.hip (native Poseidon),
+// schnorr.hip (the challenge of a signature, section 7.2l) and cipher.hip (the Poseidon cipher, section 7.2o): the handle, the definition on the host, the per-lane rounds and
 // the sponge's absorption.  The forms, their bounds and the kernels are described in hades.hip.
 #pragma once
 #include <string>

@@ -1,5 +1,5 @@
 // JubJub on the device, shared by gadgets.hip (the rows of the curve gadgets), jubjub.hip (the native calls, DESIGN.md section
-// 7.2k) and schnorr.hip (signatures, section 7.2l): the twisted Edwards curve -x^2 + y^2 = 1 + d x^2 y^2 over Fr, d = -(10240 / 10241), in extended coordinates, with the
+// 7.2k), schnorr.hip (signatures, section 7.2l) and cipher.hip (note scanning, section 7.2o): the twisted Edwards curve -x^2 + y^2 = 1 + d x^2 y^2 over Fr, d = -(10240 / 10241), in extended coordinates, with the
 // field helpers the group law is written in.  Everything here runs in the device form (x 2^261, poly_common.hip.h).
 //
 // Affine addends.  ed_madd takes its second operand as (x, y, t) with t = x y; (0, 1, 0) is the neutral addend, so a digit of 0
@@ -235,6 +235,18 @@ PM_DEV bool jj_below_r(const u32x4& lo, const u32x4& hi) {
     decided = decided || w[j] != JJ_R_WORDS[j];
   }
   return below;
+}
+// the point at p (x | y): both coordinates below r and on the curve; x and y in the device form whatever the answer
+PM_DEV bool jj_point_ok(const u32x4* p, const Fr& ed, Fr& x, Fr& y) {
+  const bool canonical = jj_below_r(p[0], p[1]) && jj_below_r(p[2], p[3]);
+  x = g_to_dev(ld_canon(p, 0)), y = g_to_dev(ld_canon(p, 1));
+  const Fr x2 = gmul(x, x), y2 = gmul(y, y);
+  const Fr rhs = gadd(fe_one<FrP>(), gmul(gmul(x2, y2), ed));
+  u32 s[8], any = 0;
+  fe_canon_pack<FrP>(s, gsub(gsub(y2, x2), rhs));
+#pragma unroll
+  for (int j = 0; j < 8; ++j) any |= s[j];
+  return canonical && any == 0;
 }
 
 // ------------------------------------------------------------------ argument checks

@@ -124,18 +124,6 @@ PM_DEV void sch_challenge(const Fr& h, u64 (&c)[4]) {
   for (int i = 0; i < 4; ++i) c[i] = (u64)w[2 * i] | ((u64)w[2 * i + 1] << 32);
   c[3] &= (1ull << 58) - 1;
 }
-// the point at p (x | y): both coordinates below r and on the curve; x and y in the device form whatever the answer
-PM_DEV bool sch_point_ok(const u32x4* p, const Fr& ed, Fr& x, Fr& y) {
-  const bool canonical = jj_below_r(p[0], p[1]) && jj_below_r(p[2], p[3]);
-  x = g_to_dev(ld_canon(p, 0)), y = g_to_dev(ld_canon(p, 1));
-  const Fr x2 = gmul(x, x), y2 = gmul(y, y);
-  const Fr rhs = gadd(fe_one<FrP>(), gmul(gmul(x2, y2), ed));
-  u32 s[8], any = 0;
-  fe_canon_pack<FrP>(s, gsub(gsub(y2, x2), rhs));
-#pragma unroll
-  for (int j = 0; j < 8; ++j) any |= s[j];
-  return canonical && any == 0;
-}
 PM_DEV bool sch_is_zero(const Fr& v) {                      // v normalised, below 2 r
   u32 s[8], any = 0;
   fe_canon_pack<FrP>(s, v);
@@ -213,8 +201,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 4)))
   Fr s[5];
   {
     Fr rx, ry, px, py;
-    const bool pk_ok = sch_point_ok(a.pks + 4 * i, ed, px, py);
-    const bool r_ok = sch_point_ok(sig + 2, ed, rx, ry);
+    const bool pk_ok = jj_point_ok(a.pks + 4 * i, ed, px, py);
+    const bool r_ok = jj_point_ok(sig + 2, ed, rx, ry);
     const u32 early = !u_ok ? PM_SCHNORR_U_RANGE : !r_ok ? PM_SCHNORR_R_POINT : !pk_ok ? PM_SCHNORR_PK_POINT : PM_SCHNORR_OK;
     pass[2 * T] = u32x4{early, 0, 0, 0};
     sch_absorb(s, rx, ry, g_to_dev(ld_canon(a.msgs, i)), a, tab);
@@ -347,8 +335,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 4)))
   u32 early;
   {
     Fr rx, ry, px, py;
-    const bool pk_ok = sch_point_ok(a.pks + 4 * i, ed, px, py);
-    const bool r_ok = sch_point_ok(sig + 2, ed, rx, ry);
+    const bool pk_ok = jj_point_ok(a.pks + 4 * i, ed, px, py);
+    const bool r_ok = jj_point_ok(sig + 2, ed, rx, ry);
     early = !u_ok ? PM_SCHNORR_U_RANGE : !r_ok ? PM_SCHNORR_R_POINT : !pk_ok ? PM_SCHNORR_PK_POINT : PM_SCHNORR_OK;
     if (live) {                                              // PK_i and -R_i, or two identities
       const bool ok = early == PM_SCHNORR_OK;
