@@ -575,13 +575,12 @@ PM_DEV void fe_pack_raw(u32* s, const Fe<P>& a) {
     s[j] = x;
   }
 }
-// value < 2m (limbs < 2^32 - 2^(32-W): the carry of fe_norm_full must fit) -> canonical saturated limbs
+// fully normalised limbs, value < 2m -> canonical saturated limbs: the compare, subtract and select of fe_canon_pack
 template <class P>
-PM_DEV void fe_canon_pack(u32* s, const Fe<P>& a) {
+PM_DEV void fe_canon_pack_normalised(u32* s, Fe<P> x) {
   constexpr int N = P::N, W = P::W;
   constexpr u32 MASK = Consts<P>::MASK;
   constexpr Limbs<N> M = Consts<P>::mod_limbs();
-  Fe<P> x = fe_norm_full<P>(a);
   // d = x - m with a signed borrow chain
   Fe<P> d;
   int32_t c = 0;
@@ -597,6 +596,29 @@ PM_DEV void fe_canon_pack(u32* s, const Fe<P>& a) {
 #pragma unroll
   for (int i = 0; i < N; ++i) x.l[i] = neg ? x.l[i] : d.l[i];
   fe_pack_raw<P>(s, x);
+}
+// value < 2m (limbs < 2^32 - 2^(32-W): the carry of fe_norm_full must fit) -> canonical saturated limbs
+template <class P>
+PM_DEV void fe_canon_pack(u32* s, const Fe<P>& a) {
+  fe_canon_pack_normalised<P>(s, fe_norm_full<P>(a));
+}
+// fe_reduce_weak and fe_canon_pack in one, for Fr: x of fe_reduce_weak's class (limbs < 2^32, value < 2^(W N)) -> canonical
+// saturated limbs.  r = fe_reduce_weak(x) has every limb but the top below 2^W, so r < (top(r) + 1) 2^(W (N-1)); with
+// top(r) < top(m) that is <= top(m) 2^(W (N-1)) <= m: r is canonical already and packing its limbs is the whole exit.
+// r >= m therefore needs top(r) >= top(m), whatever the size of r.  What r < m + m / 2^16 (fe_reduce_weak's result bound
+// for Fr) adds is how seldom that is: r >= top(m) 2^232 leaves 4.3e-8 of [0, m) and the m / 2^16 above it, which only a
+// digit missed by one reaches, so about 4e-8 of uniformly distributed outputs.  The wave votes: only if one of its lanes
+// has such a top limb does it run the compare, subtract and select, which is exact for every r < 2m, on all of them.
+// The vote is the wave's, so the call site must be reached by whole waves (lanes that have left the kernel do not vote).
+template <class P>
+PM_DEV void fe_reduce_canon_pack(u32* s, const Fe<P>& x) {
+  static_assert(P::N == 9, "Fr only, as fe_reduce_weak's result bound is");
+  constexpr Limbs<P::N> M = Consts<P>::mod_limbs();
+  const Fe<P> r = fe_reduce_weak<P>(x);
+  if (__any(r.l[P::N - 1] >= M.v[P::N - 1]))
+    fe_canon_pack_normalised<P>(s, r);
+  else
+    fe_pack_raw<P>(s, r);
 }
 
 // ------------------------------------------------------------------ 16-byte vector IO
@@ -619,14 +641,19 @@ PM_DEV Fe<P> fe_load(const void* p) {
   }
   return fe_unpack<P>(s);
 }
+// saturated words -> element in memory, NS/4 aligned 16-byte stores
+template <class P>
+PM_DEV void fe_store_words(void* p, const u32 (&s)[P::NS]) {
+  u32x4* q = reinterpret_cast<u32x4*>(p);
+#pragma unroll
+  for (int i = 0; i < P::NS / 4; ++i) q[i] = u32x4{s[4 * i], s[4 * i + 1], s[4 * i + 2], s[4 * i + 3]};
+}
 // limbs (value < 2m) -> canonical element in memory
 template <class P>
 PM_DEV void fe_store(void* p, const Fe<P>& a) {
   u32 s[P::NS];
   fe_canon_pack<P>(s, a);
-  u32x4* q = reinterpret_cast<u32x4*>(p);
-#pragma unroll
-  for (int i = 0; i < P::NS / 4; ++i) q[i] = u32x4{s[4 * i], s[4 * i + 1], s[4 * i + 2], s[4 * i + 3]};
+  fe_store_words<P>(p, s);
 }
 
 }  // namespace pm

@@ -330,11 +330,21 @@ PM_DEV void ntt_step4(Fr (&x)[4], Fr (&ptw)[4], const NttPassArgs& a, const NttC
 #pragma unroll
       for (int m = 0; m < 4; ++m) {
         const size_t go = obase + (size_t)(u + m * U) * ns;
-        Fr v = x[m];
-        if (a.flags & PASS_POST_SCALE) v = fe_mul<FrP>(v, fr_limbs(kc.scale));
-        if (a.flags & PASS_POST_COSET) v = fe_mul<FrP>(v, two_level(a.cs_hi, a.cs_lo, (u32)go, a.lh));
-        if (!(a.flags & (PASS_POST_SCALE | PASS_POST_COSET))) v = fe_reduce_weak<FrP>(v);
-        fe_store<FrP>(gout + 2 * go, v);
+        // Both ends leave the eight words to ONE pair of stores behind them: with a store at the end of each, the compiler
+        // merged what the two had in common into a 4-byte, a 16-byte and a 12-byte store, the wide ones off their
+        // alignment, and the <10, 1> last pass measured 1 us slower per launch than with fe_store.
+        u32 w[8];
+        if (a.flags & (PASS_POST_SCALE | PASS_POST_COSET)) {
+          // a product is anywhere below 2 r: its top limb reaches that of r in a large share of the elements and the vote of
+          // fe_reduce_canon_pack would send nearly every wave down both paths
+          Fr v = x[m];
+          if (a.flags & PASS_POST_SCALE) v = fe_mul<FrP>(v, fr_limbs(kc.scale));
+          if (a.flags & PASS_POST_COSET) v = fe_mul<FrP>(v, two_level(a.cs_hi, a.cs_lo, (u32)go, a.lh));
+          fe_canon_pack<FrP>(w, v);
+        } else {
+          fe_reduce_canon_pack<FrP>(w, x[m]);  // (<5, <40); whole waves come here: the flags are the launch's
+        }
+        fe_store_words<FrP>(gout + 2 * go, w);
       }
     }
   }

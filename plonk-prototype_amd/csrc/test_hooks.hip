@@ -23,7 +23,7 @@ namespace pm {
 enum RawOp {
   RAW_ADD = 0, RAW_NORM, RAW_NORM_FULL, RAW_MUL, RAW_SQR, RAW_MUL_LIMB, RAW_MUL2, RAW_MUL3, RAW_MMA2, RAW_SQR2,
   RAW_REDUCE_WEAK, RAW_UNPACK, RAW_CANON_PACK, RAW_POW2, RAW_SPLIT_5_6, RAW_SPLIT_1_2, RAW_ZERO_PRODUCT, RAW_ZERO_LAZY,
-  RAW_DFT8, RAW_DFT4, RAW_CANON_LIMBS, RAW_INV_INT, RAW_INV_DEV, RAW_SUB = 32   // RAW_SUB + K: fe_sub<K, 1>
+  RAW_DFT8, RAW_DFT4, RAW_CANON_LIMBS, RAW_INV_INT, RAW_INV_DEV, RAW_REDUCE_CANON_PACK = 24, RAW_SUB = 32   // RAW_SUB + K: fe_sub<K, 1>
 };
 
 __host__ __device__ constexpr int raw_in(int op) {
@@ -78,6 +78,8 @@ __global__ void raw_op_kernel(const u32* in, u32* out, size_t n) {
   if constexpr (OP == RAW_REDUCE_WEAK) r[0] = fe_reduce_weak<P>(x[0]);
   if constexpr (OP == RAW_UNPACK) r[0] = fe_unpack<P>(x[0].l);          // the first NS words are the saturated limbs
   if constexpr (OP == RAW_CANON_PACK) fe_canon_pack<P>(r[0].l, x[0]);   // NS saturated words, the rest stays zero
+  // the exit of the radix-4 last passes: the wave votes, cases 64 k .. 64 k + 63 share a wave (lanes past n have left)
+  if constexpr (OP == RAW_REDUCE_CANON_PACK) fe_reduce_canon_pack<P>(r[0].l, x[0]);
   if constexpr (OP == RAW_POW2) {
     const u32 sel = x[0].l[0];
     r[0] = sel == 0 ? fe_pow2<P, P::W * P::N>() : sel == 1 ? fe_pow2<P, 2 * P::W * P::N - 32 * P::NS>() : fe_pow2<P, 64 * P::NS + P::W * P::N>();
@@ -227,7 +229,7 @@ static bool launch_raw(int op, dim3 g, dim3 blk, hipStream_t st, const u32* in, 
     RAW_CASE(RAW_SUB + 2) RAW_CASE(RAW_SUB + 3) RAW_CASE(RAW_SUB + 5)
   }
   if constexpr (FR) {
-    switch (op) { RAW_CASE(RAW_SPLIT_5_6) RAW_CASE(RAW_SPLIT_1_2) RAW_CASE(RAW_DFT8) RAW_CASE(RAW_DFT4) RAW_CASE(RAW_SUB + 9) }
+    switch (op) { RAW_CASE(RAW_SPLIT_5_6) RAW_CASE(RAW_SPLIT_1_2) RAW_CASE(RAW_DFT8) RAW_CASE(RAW_DFT4) RAW_CASE(RAW_REDUCE_CANON_PACK) RAW_CASE(RAW_SUB + 9) }
   } else {
     switch (op) { RAW_CASE(RAW_ZERO_PRODUCT) RAW_CASE(RAW_ZERO_LAZY) RAW_CASE(RAW_SUB + 6) RAW_CASE(RAW_SUB + 8) RAW_CASE(RAW_SUB + 11) }
   }
@@ -249,9 +251,9 @@ extern "C" int pm_test_field_raw_op(pm_ctx* ctx, int field, int op, const uint32
   {   // the (field, op) pairs that exist: every fe_sub<K, 1> the library instantiates, the split product and the butterflies for Fr, the zero tests for Fp, the inversion routines for both
     const int k = op - RAW_SUB;
     const bool sub_ok = k == 2 || k == 3 || k == 5 || (fr ? k == 9 : (k == 6 || k == 8 || k == 11));
-    const bool fr_only = op == RAW_SPLIT_5_6 || op == RAW_SPLIT_1_2 || op == RAW_DFT8 || op == RAW_DFT4;
+    const bool fr_only = op == RAW_SPLIT_5_6 || op == RAW_SPLIT_1_2 || op == RAW_DFT8 || op == RAW_DFT4 || op == RAW_REDUCE_CANON_PACK;
     const bool fp_only = op == RAW_ZERO_PRODUCT || op == RAW_ZERO_LAZY;
-    if (op >= RAW_SUB ? !sub_ok : (op > RAW_INV_DEV || (fr_only && !fr) || (fp_only && fr))) return PM_ERR_BAD_ARG;
+    if (op >= RAW_SUB ? !sub_ok : ((op > RAW_INV_DEV && op != RAW_REDUCE_CANON_PACK) || (fr_only && !fr) || (fp_only && fr))) return PM_ERR_BAD_ARG;
   }
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (n == 0) return PM_OK;
