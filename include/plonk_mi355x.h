@@ -1184,7 +1184,9 @@ int pm_ntt_plan(uint32_t log_n, uint32_t radix_log2[4], uint32_t* n_passes);
  * pipelined pieces on two streams; off: it measured slower), "ntt_tile_log", "ntt_radix", "ntt_max_radix", "ntt_xcd",
  * "ntt_direct_tw", "ntt_tw_producer" (1, the default: the radix-4 first pass of radix 2^10 multiplies its outputs by the next
  * pass's inter-pass twiddle table, so that pass starts on its data alone; 0: every pass multiplies its own inputs.  Same results either way;
- * it needs "ntt_direct_tw" = 1), "ntt_pipeline" (0 = no copy / compute overlap in pm_fr_ntt_batch), "poly_lookback" (prefix product in one
+ * it needs "ntt_direct_tw" = 1), "ntt_step_prio" (1, the default: the waves of a radix-4 pass of radix 2^10 lower their issue priority step by
+ * step, so that the two workgroups of a CU alternate instead of one running ahead; 0: age alone.  Same results either way; any other
+ * value is PM_ERR_BAD_ARG), "ntt_pipeline" (0 = no copy / compute overlap in pm_fr_ntt_batch), "poly_lookback" (prefix product in one
  * pass: 0 never, 1 while all tiles are resident -- the default --, 2 always).  PM_ERR_BAD_ARG if unknown. */
 int pm_set_option(pm_ctx* ctx, const char* key, long value);
 /* Opt-in per-kernel timing with hipEvents recorded on the launch stream (bench.py's roofline

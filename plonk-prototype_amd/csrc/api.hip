@@ -327,6 +327,11 @@ extern "C" int pm_set_option(pm_ctx* ctx, const char* key, long value) {
     ctx->opt_ntt_tw_producer = value != 0;
     return PM_OK;
   }
+  if (!strcmp(key, "ntt_step_prio")) {
+    if (value != 0 && value != 1) return set_err(ctx, PM_ERR_BAD_ARG, "ntt_step_prio must be 0 (off) or 1");
+    ctx->opt_ntt_step_prio = value;
+    return PM_OK;
+  }
   if (!strcmp(key, "ntt_radix")) {
     if (value != 4 && value != 8) return set_err(ctx, PM_ERR_BAD_ARG, "ntt_radix must be 4 or 8");
     ctx->opt_ntt_radix = value;

@@ -10,6 +10,11 @@
 
 #include "../../include/plonk_mi355x.h"
 
+// default of the option ntt_step_prio; A/B builds set the other one (make EXTRA=-DPM_NTT_STEP_PRIO_DEFAULT=0)
+#ifndef PM_NTT_STEP_PRIO_DEFAULT
+#define PM_NTT_STEP_PRIO_DEFAULT 1
+#endif
+
 namespace pm {
 
 class ExchangeWatch;                                    // comm.hip
@@ -112,6 +117,7 @@ struct pm_ctx {
   long opt_ntt_max_radix = 10;   // log2 of the largest pass radix (multi-pass plans)
   long opt_ntt_direct_tw = 1;    // inter-pass twiddles from per-pass N x 36 B tables (1) or from the two-level tables + one product (0)
   long opt_ntt_tw_producer = 1;  // with direct tables: radix-4 passes multiply their outputs by the next pass's table (1) or every pass its own inputs (0)
+  long opt_ntt_step_prio = PM_NTT_STEP_PRIO_DEFAULT;  // radix-4 passes of two steps or more: wave priorities by step (1), so that co-resident workgroups alternate, or age alone (0)
   long opt_msm_chunk = 0;        // 0 = auto (entries per thread in the level-1 accumulate)
   long opt_msm_max_pairs = 0;    // 0 = 2^31 - 1; a batched MSM with more (digit, point) pairs runs in halves
   long opt_msm_lb = 0;           // 0 = auto (buckets per thread in the bucket reduce)

@@ -51,6 +51,10 @@ static pass_fn find_pass(int S, int LT, int role) {
 size_t pass4_lds(int S, int LT);
 unsigned pass4_threads(int S, int LT);
 bool pass4_tw_producer(int S, int LT, int role);
+bool pass4_step_prio(int S, int LT, int role);
+#ifdef PM_DEV_STAMPS
+int ntt_stamps_arm(pm_ctx* ctx, hipStream_t st, int pass, size_t waves);
+#endif
 int build_step4_table(pm_ctx* ctx, void** out, const NttConsts& c, unsigned S, hipStream_t st);
 size_t step4_table_bytes(unsigned S);
 
@@ -396,11 +400,16 @@ int ntt_run(pm_ctx* ctx, const void* d_in, size_t in_len, size_t in_stride, void
       }
     }
     a.flags = (i == 0 ? pre : 0u) | post_i | tw_flag | (ctx->opt_ntt_xcd ? PASS_XCD_REMAP : 0u);
+    if (r4 && ctx->opt_ntt_step_prio && pass4_step_prio(S, LT, role)) a.flags |= PASS_STEP_PRIO;   // wave priorities by step
     const unsigned threads = r4 ? pass4_threads(S, LT) : std::max(64u, (1u << (S + LT)) / 8);
     const size_t lds = r4 ? pass4_lds(S, LT) : pass_lds_bytes(S, LT);
     if (lds > 64 * 1024)   // once per kernel and process, not per launch
       if (int lrc = raise_lds_limit(ctx, (const void*)fn, lds)) return lrc;
     const unsigned blocks = (unsigned)(n >> (S + LT));
+#ifdef PM_DEV_STAMPS
+    if (r4)
+      if (int lrc = ntt_stamps_arm(ctx, st, i, (size_t)blocks * batch * ((threads + 63) / 64))) return lrc;
+#endif
     {
       static const char* kRoleName[4] = {"ntt_pass_single", "ntt_pass_first", "ntt_pass_middle", "ntt_pass_last"};
       ProfScope prof(ctx, st, kRoleName[role]);

@@ -38,7 +38,27 @@ pass_fn find_pass4(int S, int LT, int role) {
 bool pass4_tw_producer(int S, int LT, int role) {
   return (role == 1 || role == 2) && find_pass4(S, LT, role) != nullptr && step4_tw_producer(S, LT, role == 1, role == 2);
 }
+// does this shape's kernel take wave priorities by step (PASS_STEP_PRIO)
+bool pass4_step_prio(int S, int LT, int role) { return find_pass4(S, LT, role) != nullptr && step4_has_prio(S); }
 size_t pass4_lds(int S, int LT) { return pass4_lds_bytes(S, LT); }
+
+#ifdef PM_DEV_STAMPS
+// Diagnostic build: the stamp buffer of the radix-4 pass launched next on st (see ntt_stamp in ntt_kernels4.hip.h), room for
+// `waves` waves; null switches the stamps off.  pm_dev_ntt_stamps() hands ntt_run() a buffer that it deals out pass by pass.
+static unsigned long long* g_host_stamps = nullptr;
+static size_t g_host_stamp_waves = 0;
+int ntt_stamps_arm(pm_ctx* ctx, hipStream_t st, int pass, size_t waves) {
+  unsigned long long* p = nullptr;
+  unsigned long long room = 0;
+  if (g_host_stamps && (size_t)(pass + 1) * waves <= g_host_stamp_waves) {
+    p = g_host_stamps + (size_t)pass * waves * NTT_STAMP_WORDS;
+    room = waves;
+  }
+  PM_HIP(ctx, hipMemcpyToSymbolAsync(HIP_SYMBOL(g_ntt_stamps), &p, sizeof p, 0, hipMemcpyHostToDevice, st));
+  PM_HIP(ctx, hipMemcpyToSymbolAsync(HIP_SYMBOL(g_ntt_stamp_waves), &room, sizeof room, 0, hipMemcpyHostToDevice, st));
+  return PM_OK;
+}
+#endif
 unsigned pass4_threads(int S, int LT) { return std::max(64u, (1u << (S + LT)) / 4); }
 
 // the head (w4 and the powers of w16, nine rows each) in front, then 80 B per entry
@@ -57,3 +77,12 @@ int build_step4_table(pm_ctx* ctx, void** out, const NttConsts& c, unsigned S, h
 }
 
 }  // namespace pm
+
+#ifdef PM_DEV_STAMPS
+// d_buf: room for `waves` x 40 words of 8 bytes (all passes of the transforms that follow, 320 B per wave); null: off
+extern "C" int pm_dev_ntt_stamps(void* d_buf, size_t waves) {
+  pm::g_host_stamps = (unsigned long long*)d_buf;
+  pm::g_host_stamp_waves = d_buf ? waves : 0;
+  return 0;
+}
+#endif

@@ -64,6 +64,7 @@ enum : u32 {
   PASS_XCD_REMAP = 16u,  // blockIdx -> tile so that each XCD walks a contiguous range of tiles
   PASS_TW_OUT = 32u,     // the last step multiplies output idx by pass_tw_out[idx] (radix-4 family, wide output)
   PASS_TW_APPLIED = 64u, // the wide input carries its inter-pass twiddle already: its producer ran with PASS_TW_OUT
+  PASS_STEP_PRIO = 128u, // radix-4 passes of two steps or more: wave priority by step, the wave behind is served first
 };
 
 // Workgroups are dealt round-robin over the 8 XCDs (blocks b and b+8 share an L2).  Giving XCD x

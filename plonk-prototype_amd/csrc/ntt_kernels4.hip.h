@@ -182,6 +182,64 @@ PM_DEV FrSplit2 ld_tw2(const u32x4* ent, size_t idx) {
 PM_DEV Fr mul_tw2(const Fr& x, const FrSplit2& w) {
   return fe_mul_split<FrP, 5, 6>(x, [&](int j, int b) { return w.l[9 * j + b]; });
 }
+// Wave priorities by step (PASS_STEP_PRIO, option ntt_step_prio).  The SIMD's issue arbiter compares the
+// user priority before the age of a wave, and by age alone the older of a CU's two workgroups issues whenever it can: the
+// younger one falls two to three steps behind and finishes alone, a quarter of the launch with half the waves
+// (profiles/ntt_prio_timeline_parent.txt).  With the flag a wave enters the kernel at 3 and takes step4_prio() at the top of
+// step s, behind the barrier that ends the exchange: of two co-resident workgroups the one a step behind is served first,
+// so they alternate, and equal steps fall back to age.  The flag is the launch's: every test is a scalar branch around one
+// s_setprio with a compile-time operand, at a place where a barrier bounds the compiler's scheduling already.  No result
+// depends on it.  Not kept: priority 3 from a step's last product until the next step's LDS reads are issued, alone or on
+// top of this rule (no gain, and its branches inside the steps cost every launch, flagged or not: 4 us of the 2^20 step).
+// The passes of radix 2^10 take the flag.  Those of radix 2^8 measured slower with it (forward + inverse 2^24 3.27 -> 3.41 ms,
+// coset 2^20 -> 2^22 449 -> 462 us, profiles/ntt_prio_headline_ab.txt): their kernels hold none of this code.
+__host__ __device__ constexpr bool step4_has_prio(int S) { return S >= 10 && num_steps4(S) >= 2; }
+__host__ __device__ constexpr int step4_prio(int S, int s) { return num_steps4(S) - 1 - s < 3 ? num_steps4(S) - 1 - s : 3; }
+
+// Diagnostic build only (make EXTRA=-DPM_DEV_STAMPS, tools/ntt_phase_timeline.py): lane 0 of every wave leaves shader-clock
+// and wall-clock stamps at its phase boundaries and its hardware placement in a buffer the host sets (ntt_stamps_arm in
+// ntt4.hip), NTT_STAMP_WORDS words per wave: stamp k in words 2 k (s_memtime) and 2 k + 1 (s_memrealtime), k = 0 kernel entry,
+// 1 entry loads returned, 2 + 3 s + {0, 1, 2} step s after its LDS reads / after its last product / after its second barrier,
+// 2 + 3 NSTEPS after the last store is issued; word 36 = HW_ID | XCC_ID << 32, word 37 = blockIdx.x | wave << 32 |
+// blockIdx.y << 48.  The product build has none of it.
+#ifdef PM_DEV_STAMPS
+constexpr int NTT_STAMP_WORDS = 40;
+static __device__ unsigned long long* g_ntt_stamps = nullptr;
+static __device__ unsigned long long g_ntt_stamp_waves = 0;   // waves the buffer has room for
+PM_DEV unsigned long long* ntt_stamp_slot() {
+  const unsigned long long w =
+      ((unsigned long long)blockIdx.y * gridDim.x + blockIdx.x) * ((blockDim.x + 63u) >> 6) + (threadIdx.x >> 6);
+  return (g_ntt_stamps && w < g_ntt_stamp_waves && (threadIdx.x & 63u) == 0) ? g_ntt_stamps + w * NTT_STAMP_WORDS : nullptr;
+}
+PM_DEV void ntt_stamp(int k) {
+  __builtin_amdgcn_sched_barrier(0);
+  unsigned long long t, r;
+  asm volatile("s_memtime %0\n\ts_memrealtime %1\n\ts_waitcnt lgkmcnt(0)" : "=&s"(t), "=&s"(r) : : "memory");
+  if (unsigned long long* p = ntt_stamp_slot()) {
+    p[2 * k] = t;
+    p[2 * k + 1] = r;
+  }
+  __builtin_amdgcn_sched_barrier(0);
+}
+PM_DEV void ntt_stamp_placement() {
+  const unsigned long long hw = __builtin_amdgcn_s_getreg(4 | (31 << 11));     // HW_REG_HW_ID, 32 bits
+  const unsigned long long xcc = __builtin_amdgcn_s_getreg(20 | (31 << 11));   // HW_REG_XCC_ID
+  if (unsigned long long* p = ntt_stamp_slot()) {
+    p[36] = hw | (xcc << 32);
+    p[37] = (unsigned long long)blockIdx.x | ((unsigned long long)(threadIdx.x >> 6) << 32) | ((unsigned long long)blockIdx.y << 48);
+  }
+}
+#define NTT_STAMP(k) ntt_stamp(k)
+#define NTT_STAMP_LOADS(k)                          \
+  do {                                              \
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); \
+    ntt_stamp(k);                                   \
+  } while (0)
+#else
+#define NTT_STAMP(k)
+#define NTT_STAMP_LOADS(k)
+#endif
+
 // 4-point DIF as dft4 (ntt_kernels.hip.h), the product by w4 through its split rows: a3 enters it at (4, 5)
 PM_DEV void dft4s(Fr& a0, Fr& a1, Fr& a2, Fr& a3, W4Rows w4) {
   BFLY(3, a0, a2);  // a0 (2+, <26)  a2 (4+, <27)
@@ -226,6 +284,10 @@ PM_DEV void ntt_step4(Fr (&x)[4], Fr (&ptw)[4], const NttPassArgs& a, const NttC
   static_assert(!(L1_UNIFORM && STEP == 0 && ufast), "the producer of the first-layer twiddles is in wave order");
   const u32 c = ufast ? tid / U : tid & (T - 1);
   const u32 u = ufast ? tid % U : tid >> LT;
+  constexpr int PRIO = step4_prio(S, STEP);   // PASS_STEP_PRIO: the further a wave has come, the lower (above step4_prio)
+  if constexpr (step4_has_prio(S) && STEP > 0 && PRIO != step4_prio(S, STEP - 1)) {
+    if (a.flags & PASS_STEP_PRIO) __builtin_amdgcn_s_setprio(PRIO);
+  }
   if (STEP > 0) {
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
@@ -236,6 +298,7 @@ PM_DEV void ntt_step4(Fr (&x)[4], Fr (&ptw)[4], const NttPassArgs& a, const NttC
       x[m].l[8] = lds2[e];
     }
   }
+  NTT_STAMP(2 + 3 * STEP);
   const u32x4* stw = a.step_tw + STEP4_HEAD + STEP4_ENTRY * step4_tw_offset(S, STEP);
   if constexpr (LQ == 2) {
     const u32 kp = PM ? step4_pm_digit(S, STEP, u) : u & (nsp - 1);
@@ -287,6 +350,7 @@ PM_DEV void ntt_step4(Fr (&x)[4], Fr (&ptw)[4], const NttPassArgs& a, const NttC
         x[t] = mul_head(x[t], rows);
       }
     }
+    NTT_STAMP(2 + 3 * STEP + 1);
     if constexpr (!last) {
       __syncthreads();
       const u32 base = (u - kp) * 4 + kp;
@@ -298,6 +362,7 @@ PM_DEV void ntt_step4(Fr (&x)[4], Fr (&ptw)[4], const NttPassArgs& a, const NttC
         lds2[e] = x[t].l[8];
       }
       __syncthreads();
+      NTT_STAMP(2 + 3 * STEP + 2);
     }
     // last: Ns' = R/4, k' = u: X[t] belongs to row u + t U = x[t] already
   } else {  // radix 2, always the last step: Ns' = R/2, k' = v = u + i U, pairs (x[i], x[i+2])
@@ -307,6 +372,7 @@ PM_DEV void ntt_step4(Fr (&x)[4], Fr (&ptw)[4], const NttPassArgs& a, const NttC
     x[3] = mul_tw2(x[3], ld_tw2(stw, u + U));
     BFLY(3, x[0], x[2]);
     BFLY(3, x[1], x[3]);
+    NTT_STAMP(2 + 3 * STEP + 1);
   }
   if constexpr (last) {
     const size_t n = (size_t)1 << a.log_n;
@@ -347,6 +413,7 @@ PM_DEV void ntt_step4(Fr (&x)[4], Fr (&ptw)[4], const NttPassArgs& a, const NttC
         fe_store_words<FrP>(gout + 2 * go, w);
       }
     }
+    NTT_STAMP(2 + 3 * NSTEPS);
   }
 }
 
@@ -365,6 +432,14 @@ __global__ void __launch_bounds__((1 << (S + LT)) / 4 < 64 ? 64 : (1 << (S + LT)
 
   const u32 tid = threadIdx.x;
   if (NTHREADS < 64 && tid >= NTHREADS) return;
+#ifdef PM_DEV_STAMPS
+  static_assert(2 + 3 * NSTEPS < 18, "stamp slots");
+  ntt_stamp_placement();
+#endif
+  NTT_STAMP(0);
+  if constexpr (step4_has_prio(S)) {   // the entry loads and step 0 run at 3
+    if (a.flags & PASS_STEP_PRIO) __builtin_amdgcn_s_setprio(3);
+  }
   const u32 log_n = a.log_n;
   const size_t n = (size_t)1 << log_n;
   const size_t n_cols = (size_t)1 << (log_n - S);
@@ -415,6 +490,7 @@ __global__ void __launch_bounds__((1 << (S + LT)) / 4 < 64 ? 64 : (1 << (S + LT)
       }
     }
   }
+  NTT_STAMP_LOADS(1);
   ntt_step4<S, LT, 0, OUT_UFAST, IN_WIDE, OUT_WIDE>(x, ptw, a, kc, lds0, lds1, lds2, w4, tid, j0);
   if constexpr (NSTEPS > 1) ntt_step4<S, LT, 1, OUT_UFAST, IN_WIDE, OUT_WIDE>(x, ptw, a, kc, lds0, lds1, lds2, w4, tid, j0);
   if constexpr (NSTEPS > 2) ntt_step4<S, LT, 2, OUT_UFAST, IN_WIDE, OUT_WIDE>(x, ptw, a, kc, lds0, lds1, lds2, w4, tid, j0);
