@@ -43,7 +43,6 @@ using host::HFr;
 
 constexpr u32 CPH_MAX_LEN = 4;                              // message words: the rate of the width-5 permutation
 constexpr size_t CPH_SLOT_BYTES = JJ_MUL_TABLE_BYTES + 64;  // a thread's scratch: 1 R .. 8 R, then S (x | y): 1216 in flight
-constexpr size_t CPH_BLOCKS_PER_CU = 8;                     // as pm_jubjub_mul_dev: eight workgroups of 64 a CU at the most
 
 // ------------------------------------------------------------------ the host forms (csrc/host_field.h)
 void host_init(HFr (&s)[5], const HPoint& secret, const uint64_t* nonce, uint32_t len) {
@@ -96,18 +95,6 @@ PM_DEV void cph_init(Fr (&s)[5], const Fr& x, const Fr& y, const Fr& nonce, cons
   s[2] = h_absorb(zero, x, tab.ark + 18);
   s[3] = h_absorb(zero, y, tab.ark + 27);
   s[4] = h_absorb(zero, nonce, tab.ark + 36);
-}
-
-// 2 p by the dedicated doubling for a = -1 (Hisil, Wong, Carter, Dawson 2008, section 3.3) with every output negated, which is
-// the same point: A = X^2, B = Y^2, C = 2 Z^2, H = A + B, G = B - A, F = C - G, E = (X + Y)^2 - H, then (E F, G H, F G, E H).
-// Four squarings and four products (three without T) where ed_add(p, p) takes nine products; no exceptional case on the curve,
-// and p.T is not read, so a run of doublings needs T from its last one only.
-template <bool WITH_T>
-PM_DEV EdPoint cph_double(const EdPoint& p) {
-  const Fr A = fe_sqr<FrP>(p.X), B = fe_sqr<FrP>(p.Y), zz = fe_sqr<FrP>(p.Z);
-  const Fr H = gadd(A, B), G = gsub(B, A), F = gsub(gadd(zz, zz), G);
-  const Fr E = gsub(fe_sqr<FrP>(gadd(p.X, p.Y)), H);
-  return EdPoint{gmul(E, F), gmul(G, H), gmul(F, G), WITH_T ? gmul(E, H) : p.T};
 }
 
 __global__ void __launch_bounds__(64) cipher_encrypt_kernel(const HadesTab tab, const CipherIo a) {
@@ -201,24 +188,15 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   u32x4* const tbl = a.scratch + tid;
   const size_t i = tid < a.n ? tid : a.n - 1;
   const Fr ed = fr_limbs(a.edwards_d);
-  // ---- the table of R: e R = (e - 1) R + R
-  const Fr px = g_to_dev(ld_canon(a.points, 2 * i)), py = g_to_dev(ld_canon(a.points, 2 * i + 1)), pt = gmul(px, py);
-  EdPoint acc{px, py, fe_one<FrP>(), pt};
-  jj_table_store(tbl, T, 1, acc);
-#pragma unroll 1
-  for (u32 e = 2; e <= 8; ++e) {
-    Fr x = px, y = py, t = pt;
-    jj_opaque(x), jj_opaque(y), jj_opaque(t);
-    acc = ed_madd(acc, x, y, t, ed);
-    jj_table_store(tbl, T, e, acc);
-  }
+  // ---- the table of R
+  jj_table_build(tbl, T, g_to_dev(ld_canon(a.points, 2 * i)), g_to_dev(ld_canon(a.points, 2 * i + 1)), ed);
   // ---- the ladder from the top digit down; d is the same in every lane of the grid
-  acc = jj_neutral();
+  EdPoint acc = jj_neutral();
 #pragma unroll 1
   for (u32 w = 0; w < JJ_WINDOWS; ++w) {
 #pragma unroll 1
-    for (u32 j = 0; j < 3; ++j) acc = cph_double<false>(acc);
-    acc = cph_double<true>(acc);                             // the addition reads T
+    for (u32 j = 0; j < 3; ++j) acc = ed_double<false>(acc);
+    acc = ed_double<true>(acc);                              // the addition reads T
     const int d = (int)(signed char)(a.digits[w >> 2] >> (8 * (w & 3u)));
     if (d != 0) {                                            // uniform: a zero digit adds nothing
       const u32 mag = (u32)(d < 0 ? -d : d), e = mag > 8u ? 8u : mag;
@@ -235,12 +213,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 }
 
 // ------------------------------------------------------------------ launches
-size_t scan_blocks(const pm_ctx* ctx, size_t n) {
-  return std::max<size_t>(std::min<size_t>((n + 63) / 64, (size_t)std::max(ctx->num_cus, 1) * CPH_BLOCKS_PER_CU), 1);
-}
 int common_fault(pm_ctx* ctx, const pm_hades_params* params, uint32_t msg_len) {
-  if (!params) return set_err(ctx, PM_ERR_BAD_ARG, "null params");
-  if (params->device != ctx->device) return set_err(ctx, PM_ERR_BAD_ARG, "the params belong to another device");
+  if (int rc = params_fault(ctx, params)) return rc;
   if (msg_len < 1 || msg_len > CPH_MAX_LEN) return set_err(ctx, PM_ERR_BAD_ARG, "msg_len must be 1 .. 4");
   return PM_OK;
 }
@@ -254,14 +228,7 @@ void io_consts(CipherIo& a, uint32_t msg_len) {
 // what decrypt and scan do once their kernels are on the stream: the count back when it is wanted, the buffer released
 int finish(pm_ctx* ctx, hipError_t e, hipStream_t st, void* buf, const unsigned long long* d_ok, size_t* n_ok, const char* who) {
   unsigned long long ok = 0;
-  if (e == hipSuccess && n_ok) {
-    e = hipMemcpyAsync(&ok, d_ok, 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-  }
-  // the launches are ordered on the stream like any other; releasing the buffer waits for them (hipFree waits for the device)
-  const hipError_t e2 = buf ? hipFree(buf) : hipSuccess;
-  if (e == hipSuccess) e = e2;
-  if (e != hipSuccess) return set_err(ctx, PM_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+  if (int rc = finish_call(ctx, e, st, n_ok ? &ok : nullptr, d_ok, 8, buf, who)) return rc;
   if (n_ok) *n_ok = (size_t)ok;
   return PM_OK;
 }
@@ -276,13 +243,10 @@ extern "C" int pm_poseidon_cipher_encrypt_dev(pm_ctx* ctx, const pm_hades_params
                                               void* d_ciphers, void* hip_stream) {
   if (!ctx) return PM_ERR_BAD_ARG;
   if (int rc = common_fault(ctx, params, msg_len)) return rc;
-  if (!d_secrets_xy || !d_nonces || !d_msgs || !d_ciphers || unaligned({d_secrets_xy, d_nonces, d_msgs, d_ciphers}))
-    return set_err(ctx, PM_ERR_BAD_ARG, "null or unaligned device pointer");
-  if (n > 0x7fffffffu) return set_err(ctx, PM_ERR_LENGTH, "n > 2^31");
+  if (int rc = pointer_fault(ctx, {d_secrets_xy, d_nonces, d_msgs, d_ciphers})) return rc;
+  if (int rc = count_fault(ctx, n)) return rc;
   if (n == 0) return PM_OK;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  PM_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  PM_ENTER(ctx, hip_stream, st);
   CipherIo a{};
   a.secrets = (const u32x4*)d_secrets_xy, a.nonces = (const u32x4*)d_nonces, a.in = (const u32x4*)d_msgs, a.out = (u32x4*)d_ciphers;
   a.n = n;
@@ -298,15 +262,11 @@ extern "C" int pm_poseidon_cipher_decrypt_dev(pm_ctx* ctx, const pm_hades_params
                                               void* d_msgs_out, void* d_status, size_t* n_ok, void* hip_stream) {
   if (!ctx) return PM_ERR_BAD_ARG;
   if (int rc = common_fault(ctx, params, msg_len)) return rc;
-  if (!d_secrets_xy || !d_nonces || !d_ciphers || !d_msgs_out || unaligned({d_secrets_xy, d_nonces, d_ciphers, d_msgs_out}) ||
-      ((uintptr_t)d_status & 3u))
-    return set_err(ctx, PM_ERR_BAD_ARG, "null or unaligned device pointer");
-  if (n > 0x7fffffffu) return set_err(ctx, PM_ERR_LENGTH, "n > 2^31");
+  if (int rc = pointer_fault(ctx, {d_secrets_xy, d_nonces, d_ciphers, d_msgs_out}, ((uintptr_t)d_status & 3u) != 0)) return rc;
+  if (int rc = count_fault(ctx, n)) return rc;
   if (n_ok) *n_ok = 0;
   if (n == 0) return PM_OK;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  PM_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  PM_ENTER(ctx, hip_stream, st);
   unsigned long long* d_ok = nullptr;
   if (n_ok) PM_HIP(ctx, hipMalloc((void**)&d_ok, 16));
   CipherIo a{};
@@ -331,22 +291,18 @@ extern "C" int pm_poseidon_cipher_scan_dev(pm_ctx* ctx, const pm_hades_params* p
   if (int rc = form_fault(ctx, scalar_form)) return rc;
   uint64_t vk[4];
   if (!view_key || !scalar_to_int(view_key, scalar_form, vk)) return set_err(ctx, PM_ERR_BAD_ARG, "the viewing key is null or not below r");
-  if (!d_ephemeral_xy || !d_nonces || !d_ciphers || !d_msgs_out || unaligned({d_ephemeral_xy, d_nonces, d_ciphers, d_msgs_out}) ||
-      ((uintptr_t)d_status & 3u))
-    return set_err(ctx, PM_ERR_BAD_ARG, "null or unaligned device pointer");
-  if (n > 0x7fffffffu) return set_err(ctx, PM_ERR_LENGTH, "n > 2^31");
+  if (int rc = pointer_fault(ctx, {d_ephemeral_xy, d_nonces, d_ciphers, d_msgs_out}, ((uintptr_t)d_status & 3u) != 0)) return rc;
+  if (int rc = count_fault(ctx, n)) return rc;
   if (n_ok) *n_ok = 0;
   if (n == 0) return PM_OK;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  PM_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  PM_ENTER(ctx, hip_stream, st);
   // the slots of the threads in flight, and the count of hits
-  const size_t blocks = scan_blocks(ctx, n), stride = blocks * 64, slot_bytes = stride * CPH_SLOT_BYTES;
-  char* scratch = nullptr;
-  PM_HIP(ctx, hipMalloc((void**)&scratch, slot_bytes + 16));
-  unsigned long long* const d_ok = (unsigned long long*)(scratch + slot_bytes);
+  SlotScratch scratch(ctx, n);
+  PM_HIP(ctx, scratch.alloc(CPH_SLOT_BYTES, 16));
+  const size_t stride = scratch.stride;
+  unsigned long long* const d_ok = scratch.tail();
   CipherScanIo l{};
-  l.scratch = (u32x4*)scratch;
+  l.scratch = scratch.slots();
   jubjub_d_limbs(l.edwards_d);
   signed char digits[JJ_WINDOWS];
   recode_digits(vk, digits);
@@ -363,12 +319,12 @@ extern "C" int pm_poseidon_cipher_scan_dev(pm_ctx* ctx, const pm_hades_params* p
       l.points = a.tested = (const u32x4*)d_ephemeral_xy + 4 * off;
       a.nonces = (const u32x4*)d_nonces + 2 * off, a.in = (const u32x4*)d_ciphers + 2 * (size_t)(msg_len + 1) * off;
       a.out = (u32x4*)d_msgs_out + 2 * (size_t)msg_len * off, a.status = d_status ? (u32*)d_status + off : nullptr;
-      hipLaunchKernelGGL(cipher_scan_ladder_kernel, dim3((unsigned)blocks), dim3(64), 0, st, l);
+      hipLaunchKernelGGL(cipher_scan_ladder_kernel, dim3((unsigned)scratch.blocks), dim3(64), 0, st, l);
       hipLaunchKernelGGL(cipher_decrypt_kernel<true>, dim3((unsigned)((a.n + 63) / 64)), dim3(64), 0, st, tab, a);
       e = hipGetLastError();
     }
   }
-  return finish(ctx, e, st, scratch, d_ok, n_ok, "pm_poseidon_cipher_scan_dev");
+  return finish(ctx, e, st, scratch.base, d_ok, n_ok, "pm_poseidon_cipher_scan_dev");
 }
 
 extern "C" int pm_poseidon_cipher_encrypt_host(uint32_t rounds, uint32_t full_rounds, const uint64_t* ark, const uint64_t* mds,
@@ -423,7 +379,7 @@ extern "C" int pm_poseidon_cipher_decrypt_host(uint32_t rounds, uint32_t full_ro
 
 extern "C" int pm_test_cipher_stride(pm_ctx* ctx, size_t* stride) {
   if (!ctx || !stride) return PM_ERR_BAD_ARG;
-  *stride = scan_blocks(ctx, ~(size_t)0 >> 1) * 64;
+  *stride = slot_blocks(ctx, ~(size_t)0 >> 1) * 64;
   return PM_OK;
 }
 

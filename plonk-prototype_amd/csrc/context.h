@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdint>
+#include <initializer_list>
 #include <map>
 #include <chrono>
 #include <mutex>
@@ -372,5 +374,52 @@ struct OrderScope {
       return pm::set_err(ctx, _e == hipErrorOutOfMemory ? PM_ERR_OOM : PM_ERR_HIP,          \
                          std::string(#call) + ": " + hipGetErrorString(_e));                \
   } while (0)
+
+// ------------------------------------------------------------------ the mechanics of a *_dev entry point
+// Used by the native calls (hades.hip, jubjub.hip, jubjub_msm.hip, schnorr.hip, cipher.hip).  They replace lines that were the
+// same in every entry and nothing else: each entry keeps its own order of checks, its return codes and its messages.
+// select the device and name the stream of the call; PM_ENTER takes the context's mutex first
+#define PM_DEVICE_STREAM(ctx, hip_stream, st)  \
+  PM_HIP(ctx, hipSetDevice(ctx->device));      \
+  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream
+#define PM_ENTER(ctx, hip_stream, st)          \
+  std::lock_guard<std::mutex> lk(ctx->mu);     \
+  PM_DEVICE_STREAM(ctx, hip_stream, st)
+
+inline int count_fault(pm_ctx* ctx, size_t n) {
+  if (n > 0x7fffffffu) return set_err(ctx, PM_ERR_LENGTH, "n > 2^31");
+  return PM_OK;
+}
+// a pointer of the list is not 16-byte aligned; null passes: for pointers that may be null
+inline bool unaligned(std::initializer_list<const void*> ps) {
+  uintptr_t acc = 0;
+  for (const void* p : ps) acc |= (uintptr_t)p;
+  return (acc & 15u) != 0;
+}
+// a pointer of the list is null or not 16-byte aligned, or `also`: what else the entry holds against its pointers
+inline int pointer_fault(pm_ctx* ctx, std::initializer_list<const void*> ps, bool also = false) {
+  bool null = false;
+  for (const void* p : ps) null = null || !p;
+  if (null || unaligned(ps) || also) return set_err(ctx, PM_ERR_BAD_ARG, "null or unaligned device pointer");
+  return PM_OK;
+}
+// the byte ranges share a byte; an empty range overlaps nothing
+inline bool overlap(const void* p, size_t pb, const void* q, size_t qb) {
+  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+  return pb && qb && a < b + qb && b < a + pb;
+}
+// What a call does once its launches are on the stream (e: their error so far): `bytes` of a small result back into host when
+// host is set, which waits for the stream; buf, the call's own allocation (may be null), released -- the launches are ordered on
+// the stream like any other and releasing the buffer waits for them (hipFree waits for the device); one message naming `who`.
+inline int finish_call(pm_ctx* ctx, hipError_t e, hipStream_t st, void* host, const void* dev, size_t bytes, void* buf, const char* who) {
+  if (e == hipSuccess && host) {
+    e = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+  }
+  const hipError_t e2 = buf ? hipFree(buf) : hipSuccess;
+  if (e == hipSuccess) e = e2;
+  if (e != hipSuccess) return set_err(ctx, PM_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
+  return PM_OK;
+}
 
 }  // namespace pm

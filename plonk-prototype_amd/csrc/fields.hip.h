@@ -655,5 +655,12 @@ PM_DEV void fe_store(void* p, const Fe<P>& a) {
   fe_canon_pack<P>(s, a);
   fe_store_words<P>(p, s);
 }
+// nine limbs as they travel in a kernel's arguments -> the element
+PM_DEV Fr fr_limbs(const u32* c) {
+  Fr r;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) r.l[i] = c[i];
+  return r;
+}
 
 }  // namespace pm

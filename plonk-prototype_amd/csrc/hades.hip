@@ -381,14 +381,9 @@ hipError_t launch(const pm_hades_params* p, const Io& io, uint32_t flags, hipStr
 }
 
 int common_fault(pm_ctx* ctx, const pm_hades_params* p, uint32_t flags) {
-  if (!p) return set_err(ctx, PM_ERR_BAD_ARG, "null params");
-  if (p->device != ctx->device) return set_err(ctx, PM_ERR_BAD_ARG, "the params belong to another device");
+  if (int rc = params_fault(ctx, p)) return rc;
   if (flags > PM_HADES_FORM_WAVE) return set_err(ctx, PM_ERR_BAD_ARG, "flags must be PM_HADES_FORM_AUTO, _THREAD or _WAVE");
   return PM_OK;
-}
-bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return x < y + b_bytes && y < x + a_bytes;
 }
 
 // ark [R][5], mds [n_mds][5][5] (validated) -> the handle with its device table
@@ -469,11 +464,9 @@ extern "C" int pm_hades_permute_dev(pm_ctx* ctx, const pm_hades_params* params, 
   if (!ctx) return PM_ERR_BAD_ARG;
   if (int rc = common_fault(ctx, params, flags)) return rc;
   if (n == 0) return PM_OK;
-  if (!d_states || ((uintptr_t)d_states & 15u)) return set_err(ctx, PM_ERR_BAD_ARG, "null or unaligned device pointer");
-  if (n > 0x7fffffffu) return set_err(ctx, PM_ERR_LENGTH, "n > 2^31");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  PM_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  if (int rc = pointer_fault(ctx, {d_states})) return rc;
+  if (int rc = count_fault(ctx, n)) return rc;
+  PM_ENTER(ctx, hip_stream, st);
   HadesIo io{};
   io.states = (u32x4*)d_states, io.n = n;
   ProfScope prof(ctx, st, "hades_permute");
@@ -490,13 +483,10 @@ extern "C" int pm_poseidon_hash_dev(pm_ctx* ctx, const pm_hades_params* params, 
   if (msg_len == 0 || msg_len > 0xffffffffull) return set_err(ctx, PM_ERR_BAD_ARG, "msg_len must be in 1 .. 2^32 - 1");
   if (msg_stride < msg_len) return set_err(ctx, PM_ERR_BAD_ARG, "msg_stride is below msg_len");
   if (n == 0) return PM_OK;
-  if (!d_msgs || !d_out || (((uintptr_t)d_msgs | (uintptr_t)d_out) & 15u))
-    return set_err(ctx, PM_ERR_BAD_ARG, "null or unaligned device pointer");
-  if (n > 0x7fffffffu) return set_err(ctx, PM_ERR_LENGTH, "n > 2^31");
+  if (int rc = pointer_fault(ctx, {d_msgs, d_out})) return rc;
+  if (int rc = count_fault(ctx, n)) return rc;
   if (overlap(d_msgs, ((n - 1) * msg_stride + msg_len) * 32, d_out, n * 32)) return set_err(ctx, PM_ERR_BAD_ARG, "d_out overlaps d_msgs");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  PM_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  PM_ENTER(ctx, hip_stream, st);
   io.msgs = (const u32x4*)d_msgs, io.out = (u32x4*)d_out, io.n = n, io.msg_stride = msg_stride, io.msg_len = (u32)msg_len;
   ProfScope prof(ctx, st, "poseidon_hash");
   PM_HIP(ctx, launch<true>(params, io, flags, st));
@@ -510,13 +500,10 @@ extern "C" int pm_poseidon_merkle_dev(pm_ctx* ctx, const pm_hades_params* params
   HadesIo io{};
   if (int rc = capacity_to_dev(ctx, capacity, io.capacity)) return rc;
   if (height < 1 || height > PM_POSEIDON_MERKLE_MAX_HEIGHT) return set_err(ctx, PM_ERR_BAD_ARG, "height must be in 1 .. 15");
-  if (!d_leaves || !d_tree || (((uintptr_t)d_leaves | (uintptr_t)d_tree) & 15u))
-    return set_err(ctx, PM_ERR_BAD_ARG, "null or unaligned device pointer");
+  if (int rc = pointer_fault(ctx, {d_leaves, d_tree})) return rc;
   const size_t leaves = (size_t)1 << (2 * height);
   if (overlap(d_leaves, leaves * 32, d_tree, (leaves - 1) / 3 * 32)) return set_err(ctx, PM_ERR_BAD_ARG, "d_tree overlaps d_leaves");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  PM_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  PM_ENTER(ctx, hip_stream, st);
   ProfScope prof(ctx, st, "poseidon_merkle");
   const u32x4* below = (const u32x4*)d_leaves;
   u32x4* level = (u32x4*)d_tree;
@@ -535,13 +522,9 @@ extern "C" int pm_poseidon_merkle_paths_dev(pm_ctx* ctx, const void* d_leaves, c
   if (!ctx) return PM_ERR_BAD_ARG;
   if (height < 1 || height > PM_POSEIDON_MERKLE_MAX_HEIGHT) return set_err(ctx, PM_ERR_BAD_ARG, "height must be in 1 .. 15");
   if (k == 0) return PM_OK;
-  if (!d_leaves || !d_tree || !d_indices || !d_out || (((uintptr_t)d_leaves | (uintptr_t)d_tree | (uintptr_t)d_out) & 15u) ||
-      ((uintptr_t)d_indices & 7u))
-    return set_err(ctx, PM_ERR_BAD_ARG, "null or unaligned device pointer");
+  if (int rc = pointer_fault(ctx, {d_leaves, d_tree, d_out}, !d_indices || ((uintptr_t)d_indices & 7u))) return rc;
   if (k > 0x7fffffffu / (4 * height)) return set_err(ctx, PM_ERR_LENGTH, "too many paths for one call");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  PM_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  PM_ENTER(ctx, hip_stream, st);
   unsigned long long* d_bad = nullptr;
   unsigned long long bad = ~0ull;
   PM_HIP(ctx, hipMalloc((void**)&d_bad, 8));
@@ -554,10 +537,7 @@ extern "C" int pm_poseidon_merkle_paths_dev(pm_ctx* ctx, const void* d_leaves, c
                        (const u32x4*)d_tree, height, (const u64*)d_indices, k, (u32x4*)d_out);
     e = hipGetLastError();
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  (void)hipFree(d_bad);
-  if (e != hipSuccess) return set_err(ctx, PM_ERR_HIP, std::string("pm_poseidon_merkle_paths_dev: ") + hipGetErrorString(e));
+  if (int rc = finish_call(ctx, e, st, &bad, d_bad, 8, d_bad, "pm_poseidon_merkle_paths_dev")) return rc;
   if (bad != ~0ull) return set_err(ctx, PM_ERR_BAD_ARG, "index " + std::to_string(bad) + " is not below 4^height");
   return PM_OK;
 }
@@ -592,9 +572,7 @@ extern "C" int pm_poseidon_merkle_update_dev(pm_ctx* ctx, const pm_hades_params*
   if (height < 1 || height > PM_POSEIDON_MERKLE_MAX_HEIGHT) return set_err(ctx, PM_ERR_BAD_ARG, "height must be in 1 .. 15");
   if (hashed) *hashed = 0;
   if (k == 0) return PM_OK;
-  if (!d_leaves || !d_tree || !d_indices || !d_values || !d_work ||
-      (((uintptr_t)d_leaves | (uintptr_t)d_tree | (uintptr_t)d_values | (uintptr_t)d_work) & 15u) || ((uintptr_t)d_indices & 7u))
-    return set_err(ctx, PM_ERR_BAD_ARG, "null or unaligned device pointer");
+  if (int rc = pointer_fault(ctx, {d_leaves, d_tree, d_values, d_work}, !d_indices || ((uintptr_t)d_indices & 7u))) return rc;
   const size_t leaves = (size_t)1 << (2 * height), nodes = (leaves - 1) / 3;
   if (k > leaves) return set_err(ctx, PM_ERR_BAD_ARG, "more indices than leaves: they cannot be strictly ascending");
   const MerkleWork w = merkle_work(k);
@@ -604,9 +582,7 @@ extern "C" int pm_poseidon_merkle_update_dev(pm_ctx* ctx, const pm_hades_params*
   for (const auto& in : ins)
     if (overlap(in.p, in.bytes, d_leaves, leaves * 32) || overlap(in.p, in.bytes, d_tree, nodes * 32))
       return set_err(ctx, PM_ERR_BAD_ARG, std::string(in.name) + " overlaps the leaves or the tree");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  PM_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  PM_ENTER(ctx, hip_stream, st);
   ProfScope prof(ctx, st, "poseidon_merkle_update");
   MerkleCtl* const ctl = (MerkleCtl*)d_work;
   u32* const sums = (u32*)((char*)d_work + w.sums);
@@ -662,16 +638,13 @@ extern "C" int pm_poseidon_merkle_verify_dev(pm_ctx* ctx, const pm_hades_params*
   if (int rc = capacity_to_dev(ctx, capacity, io.capacity)) return rc;
   if (height < 1 || height > PM_POSEIDON_MERKLE_MAX_HEIGHT) return set_err(ctx, PM_ERR_BAD_ARG, "height must be in 1 .. 15");
   if (k == 0) return PM_OK;
-  if (!d_paths || !d_indices || !d_root || !d_status || (((uintptr_t)d_paths | (uintptr_t)d_root) & 15u) ||
-      ((uintptr_t)d_indices & 7u) || ((uintptr_t)d_status & 3u))
-    return set_err(ctx, PM_ERR_BAD_ARG, "null or unaligned device pointer");
+  if (int rc = pointer_fault(ctx, {d_paths, d_root}, !d_indices || !d_status || ((uintptr_t)d_indices & 7u) || ((uintptr_t)d_status & 3u)))
+    return rc;
   if (k > 0x7fffffffu) return set_err(ctx, PM_ERR_LENGTH, "k > 2^31");
   if (overlap(d_status, k * 4, d_paths, k * height * 128) || overlap(d_status, k * 4, d_indices, k * 8) ||
       overlap(d_status, k * 4, d_root, 32))
     return set_err(ctx, PM_ERR_BAD_ARG, "d_status overlaps an input");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  PM_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  PM_ENTER(ctx, hip_stream, st);
   io.paths = (const u32x4*)d_paths, io.idx = (const u64*)d_indices, io.root = (const u32x4*)d_root, io.status = (u32*)d_status;
   io.k = k, io.h = height;
   const HadesTab tab = tab_of(params);

@@ -123,6 +123,12 @@ inline HadesTab tab_of(const pm_hades_params* p) {
   return HadesTab{(const PM_KCONST u32*)t, (const PM_KCONST u32*)(t + 225 * (size_t)p->n_mds), p->rounds, p->full / 2,
                   p->n_mds == 1 ? 0u : 225u};
 }
+// the handle a device call was given
+inline int params_fault(pm_ctx* ctx, const pm_hades_params* p) {
+  if (!p) return set_err(ctx, PM_ERR_BAD_ARG, "null params");
+  if (p->device != ctx->device) return set_err(ctx, PM_ERR_BAD_ARG, "the params belong to another device");
+  return PM_OK;
+}
 inline int capacity_to_dev(pm_ctx* ctx, const uint64_t* capacity, u32 (&out)[9]) {
   if (!capacity) return set_err(ctx, PM_ERR_BAD_ARG, "null capacity");
   if (!hfr_canonical(capacity)) return set_err(ctx, PM_ERR_BAD_ARG, "capacity is not canonical");

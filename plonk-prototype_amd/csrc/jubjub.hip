@@ -83,36 +83,12 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     const size_t g = first + threadIdx.x;
     const bool live = g < a.n;
     const size_t i = live ? g : a.n - 1;
-    const Fr px = g_to_dev(ld_canon(a.points, 2 * i)), py = g_to_dev(ld_canon(a.points, 2 * i + 1)), pt = gmul(px, py);
+    const Fr px = g_to_dev(ld_canon(a.points, 2 * i)), py = g_to_dev(ld_canon(a.points, 2 * i + 1));
     u64 k[4];
     jj_load_scalar(a.scalars + 2 * i, a.montgomery != 0, k);
-    u64 carries = jj_carries(k);
-    // ---- the table: e P = (e - 1) P + P
-    EdPoint acc{px, py, fe_one<FrP>(), pt};
-    jj_table_store(tbl, T, 1, acc);
-#pragma unroll 1
-    for (u32 e = 2; e <= 8; ++e) {
-      Fr x = px, y = py, t = pt;
-      jj_opaque(x), jj_opaque(y), jj_opaque(t);
-      acc = ed_madd(acc, x, y, t, ed);
-      jj_table_store(tbl, T, e, acc);
-    }
-    // ---- the ladder from the top digit down
-    acc = jj_neutral();
-#pragma unroll 1
-    for (u32 w = 0; w < JJ_WINDOWS; ++w) {
-#pragma unroll 1
-      for (u32 j = 0; j < 4; ++j) acc = ed_add(acc, acc, ed);
-      u32 c = (u32)(carries >> 63);
-      const int d = jj_digit((u32)(k[3] >> 60), c);
-      jj_shl4(k);
-      carries <<= 1;
-      const u32 mag = (u32)(d < 0 ? -d : d), e = mag == 0 ? 1u : (mag > 8u ? 8u : mag);
-      const EdPoint q = jj_table_load(tbl, T, e);
-      const EdPoint s{g_sel(d < 0, gneg(q.X), q.X), q.Y, q.Z, g_sel(d < 0, gneg(q.T), q.T)};
-      acc = ed_add(acc, ed_sel(d == 0, jj_neutral(), s), ed);
-    }
-    jj_store_affine(a.out, i, live, acc);
+    const u64 carries = jj_carries(k);
+    jj_table_build(tbl, T, px, py, ed);
+    jj_store_affine(a.out, i, live, jj_ladder(tbl, T, k, carries, JJ_WINDOWS, ed));
   }
 }
 
@@ -120,16 +96,8 @@ __global__ void __launch_bounds__(64) jubjub_check_kernel(const u32x4* points, s
                                                           unsigned long long* first_bad) {
   const size_t i = (size_t)blockIdx.x * 64 + threadIdx.x;
   if (i >= n) return;
-  const u32x4* p = points + 4 * i;
-  const bool canonical = jj_below_r(p[0], p[1]) && jj_below_r(p[2], p[3]);
-  const Fr x = g_to_dev(ld_canon(points, 2 * i)), y = g_to_dev(ld_canon(points, 2 * i + 1));
-  const Fr x2 = gmul(x, x), y2 = gmul(y, y);
-  const Fr rhs = gadd(fe_one<FrP>(), gmul(gmul(x2, y2), fr_limbs(a.edwards_d)));
-  u32 s[8], any = 0;
-  fe_canon_pack<FrP>(s, gsub(gsub(y2, x2), rhs));
-#pragma unroll
-  for (int j = 0; j < 8; ++j) any |= s[j];
-  if (!canonical || any) atomicMin(first_bad, (unsigned long long)i);
+  Fr x, y;
+  if (!jj_point_ok(points + 4 * i, fr_limbs(a.edwards_d), x, y)) atomicMin(first_bad, (unsigned long long)i);
 }
 
 // ------------------------------------------------------------------ handles and launches
@@ -224,12 +192,10 @@ extern "C" int pm_jubjub_fixed_mul_dev(pm_ctx* ctx, const pm_jubjub_base* base, 
   if (!ctx) return PM_ERR_BAD_ARG;
   if (int rc = base_fault(ctx, base)) return rc;
   if (int rc = form_fault(ctx, scalar_form)) return rc;
-  if (!d_scalars || !d_out_xy || unaligned({d_scalars, d_out_xy})) return set_err(ctx, PM_ERR_BAD_ARG, "null or unaligned device pointer");
+  if (int rc = pointer_fault(ctx, {d_scalars, d_out_xy})) return rc;
   if (n == 0) return PM_OK;
-  if (n > 0x7fffffffu) return set_err(ctx, PM_ERR_LENGTH, "n > 2^31");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  PM_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  if (int rc = count_fault(ctx, n)) return rc;
+  PM_ENTER(ctx, hip_stream, st);
   JubjubMul a{};
   a.tab_g = (const u32x4*)base->d_tab, a.scalars = (const u32x4*)d_scalars, a.out = (u32x4*)d_out_xy, a.n = n;
   a.montgomery = scalar_form == PM_SCALAR_MONTGOMERY;
@@ -246,13 +212,10 @@ extern "C" int pm_jubjub_commit_dev(pm_ctx* ctx, const pm_jubjub_base* g, const 
   if (int rc = base_fault(ctx, g)) return rc;
   if (int rc = base_fault(ctx, h)) return rc;
   if (int rc = form_fault(ctx, scalar_form)) return rc;
-  if (!d_values || !d_blinders || !d_out_xy || unaligned({d_values, d_blinders, d_out_xy}))
-    return set_err(ctx, PM_ERR_BAD_ARG, "null or unaligned device pointer");
+  if (int rc = pointer_fault(ctx, {d_values, d_blinders, d_out_xy})) return rc;
   if (n == 0) return PM_OK;
-  if (n > 0x7fffffffu) return set_err(ctx, PM_ERR_LENGTH, "n > 2^31");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  PM_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  if (int rc = count_fault(ctx, n)) return rc;
+  PM_ENTER(ctx, hip_stream, st);
   JubjubMul a{};
   a.tab_g = (const u32x4*)g->d_tab, a.tab_h = (const u32x4*)h->d_tab, a.scalars = (const u32x4*)d_values;
   a.scalars_h = (const u32x4*)d_blinders, a.out = (u32x4*)d_out_xy, a.n = n, a.montgomery = scalar_form == PM_SCALAR_MONTGOMERY;
@@ -267,32 +230,23 @@ extern "C" int pm_jubjub_mul_dev(pm_ctx* ctx, const void* d_points_xy, const voi
                                  void* d_out_xy, void* hip_stream) {
   if (!ctx) return PM_ERR_BAD_ARG;
   if (int rc = form_fault(ctx, scalar_form)) return rc;
-  if (!d_points_xy || !d_scalars || !d_out_xy || unaligned({d_points_xy, d_scalars, d_out_xy}))
-    return set_err(ctx, PM_ERR_BAD_ARG, "null or unaligned device pointer");
+  if (int rc = pointer_fault(ctx, {d_points_xy, d_scalars, d_out_xy})) return rc;
   if (n == 0) return PM_OK;
-  if (n > 0x7fffffffu) return set_err(ctx, PM_ERR_LENGTH, "n > 2^31");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  PM_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
-  // the window tables of the threads in flight: eight workgroups of 64 a CU at the most, 1152 bytes a thread
-  const size_t blocks = std::max<size_t>(std::min<size_t>((n + 63) / 64, (size_t)std::max(ctx->num_cus, 1) * 8), 1);
-  void* scratch = nullptr;
-  PM_HIP(ctx, hipMalloc(&scratch, blocks * 64 * JJ_MUL_TABLE_BYTES));
+  if (int rc = count_fault(ctx, n)) return rc;
+  PM_ENTER(ctx, hip_stream, st);
+  SlotScratch scratch(ctx, n);                               // the window tables of the threads in flight, 1152 bytes a thread
+  PM_HIP(ctx, scratch.alloc(JJ_MUL_TABLE_BYTES, 0));
   JubjubMul a{};
-  a.points = (const u32x4*)d_points_xy, a.scalars = (const u32x4*)d_scalars, a.out = (u32x4*)d_out_xy, a.scratch = (u32x4*)scratch;
+  a.points = (const u32x4*)d_points_xy, a.scalars = (const u32x4*)d_scalars, a.out = (u32x4*)d_out_xy, a.scratch = scratch.slots();
   a.n = n, a.montgomery = scalar_form == PM_SCALAR_MONTGOMERY;
   jubjub_d_limbs(a.edwards_d);
   hipError_t e;
   {
     ProfScope prof(ctx, st, "jubjub_mul");
-    hipLaunchKernelGGL(jubjub_var_kernel, dim3((unsigned)blocks), dim3(64), 0, st, a);
+    hipLaunchKernelGGL(jubjub_var_kernel, dim3((unsigned)scratch.blocks), dim3(64), 0, st, a);
     e = hipGetLastError();
   }
-  // the launch is ordered on the stream like any other; releasing the scratch waits for it (hipFree waits for the device)
-  const hipError_t e2 = hipFree(scratch);
-  if (e == hipSuccess) e = e2;
-  if (e != hipSuccess) return set_err(ctx, PM_ERR_HIP, std::string("pm_jubjub_mul_dev: ") + hipGetErrorString(e));
-  return PM_OK;
+  return finish_call(ctx, e, st, nullptr, nullptr, 0, scratch.base, "pm_jubjub_mul_dev");
 }
 
 extern "C" int pm_jubjub_check_dev(pm_ctx* ctx, const void* d_points_xy, size_t n, size_t* first_bad, void* hip_stream) {
@@ -300,11 +254,9 @@ extern "C" int pm_jubjub_check_dev(pm_ctx* ctx, const void* d_points_xy, size_t 
   if (!first_bad) return set_err(ctx, PM_ERR_BAD_ARG, "null first_bad");
   *first_bad = n;
   if (n == 0) return PM_OK;
-  if (!d_points_xy || unaligned({d_points_xy})) return set_err(ctx, PM_ERR_BAD_ARG, "null or unaligned device pointer");
-  if (n > 0x7fffffffu) return set_err(ctx, PM_ERR_LENGTH, "n > 2^31");
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  PM_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  if (int rc = pointer_fault(ctx, {d_points_xy})) return rc;
+  if (int rc = count_fault(ctx, n)) return rc;
+  PM_ENTER(ctx, hip_stream, st);
   unsigned long long* d_bad = nullptr;
   unsigned long long bad = n;
   PM_HIP(ctx, hipMalloc((void**)&d_bad, 8));
@@ -315,10 +267,7 @@ extern "C" int pm_jubjub_check_dev(pm_ctx* ctx, const void* d_points_xy, size_t 
     hipLaunchKernelGGL(jubjub_check_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, st, (const u32x4*)d_points_xy, n, a, d_bad);
     e = hipGetLastError();
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  (void)hipFree(d_bad);
-  if (e != hipSuccess) return set_err(ctx, PM_ERR_HIP, std::string("pm_jubjub_check_dev: ") + hipGetErrorString(e));
+  if (int rc = finish_call(ctx, e, st, &bad, d_bad, 8, d_bad, "pm_jubjub_check_dev")) return rc;
   *first_bad = (size_t)bad;
   return PM_OK;
 }
@@ -328,17 +277,13 @@ extern "C" int pm_jubjub_mul_host(const uint64_t xy[8], const uint64_t scalar[4]
   if (scalar_form != PM_SCALAR_MONTGOMERY && scalar_form != PM_SCALAR_CANONICAL) return PM_ERR_BAD_ARG;
   uint64_t k[4];
   if (point_fault(xy) || !scalar_to_int(scalar, scalar_form, k)) return PM_ERR_BAD_ARG;
-  const HPoint r = hpoint_mul(hpoint_load(xy), k);
-  memcpy(out_xy, r.x.l, 32);
-  memcpy(out_xy + 4, r.y.l, 32);
+  hpoint_store(out_xy, hpoint_mul(hpoint_load(xy), k));
   return PM_OK;
 }
 
 extern "C" int pm_jubjub_add_host(const uint64_t p[8], const uint64_t q[8], uint64_t out_xy[8]) {
   if (!p || !q || !out_xy) return PM_ERR_BAD_ARG;
   if (point_fault(p) || point_fault(q)) return PM_ERR_BAD_ARG;
-  const HPoint r = hpoint_add(hpoint_load(p), hpoint_load(q));
-  memcpy(out_xy, r.x.l, 32);
-  memcpy(out_xy + 4, r.y.l, 32);
+  hpoint_store(out_xy, hpoint_add(hpoint_load(p), hpoint_load(q)));
   return PM_OK;
 }

@@ -5,7 +5,7 @@
 // Affine addends.  ed_madd takes its second operand as (x, y, t) with t = x y; (0, 1, 0) is the neutral addend, so a digit of 0
 // selects it (g_sel) and the addition still runs: no branch depends on a digit.  -(x, y, t) = (-x, y, -t).
 #pragma once
-#include <initializer_list>
+#include <algorithm>
 #include <string>
 
 #include "context.h"
@@ -55,6 +55,17 @@ PM_DEV EdPoint ed_madd(const EdPoint& p, const Fr& x, const Fr& y, const Fr& t, 
   const Fr F = gsub(p.Z, C), G = gadd(p.Z, C), H = gadd(B, A);
   return EdPoint{gmul(E, F), gmul(G, H), gmul(F, G), gmul(E, H)};
 }
+// 2 p by the dedicated doubling for a = -1 (Hisil, Wong, Carter, Dawson 2008, section 3.3) with every output negated, which is
+// the same point: A = X^2, B = Y^2, C = 2 Z^2, H = A + B, G = B - A, F = C - G, E = (X + Y)^2 - H, then (E F, G H, F G, E H).
+// Four squarings and four products (three without T) where ed_add(p, p) takes nine products; no exceptional case on the curve,
+// and p.T is not read, so a run of doublings needs T from its last one only.
+template <bool WITH_T>
+PM_DEV EdPoint ed_double(const EdPoint& p) {
+  const Fr A = fe_sqr<FrP>(p.X), B = fe_sqr<FrP>(p.Y), zz = fe_sqr<FrP>(p.Z);
+  const Fr H = gadd(A, B), G = gsub(B, A), F = gsub(gadd(zz, zz), G);
+  const Fr E = gsub(fe_sqr<FrP>(gadd(p.X, p.Y)), H);
+  return EdPoint{gmul(E, F), gmul(G, H), gmul(F, G), WITH_T ? gmul(E, H) : p.T};
+}
 PM_DEV EdPoint ed_sel(bool c, const EdPoint& a, const EdPoint& b) {
   return EdPoint{g_sel(c, a.X, b.X), g_sel(c, a.Y, b.Y), g_sel(c, a.Z, b.Z), g_sel(c, a.T, b.T)};
 }
@@ -81,6 +92,10 @@ struct HPoint {
   HFr x, y;
 };
 inline HPoint hpoint_load(const uint64_t* xy) { return HPoint{hfr_load(xy), hfr_load(xy + 4)}; }
+inline void hpoint_store(uint64_t* xy, const HPoint& p) {
+  memcpy(xy, p.x.l, 32);
+  memcpy(xy + 4, p.y.l, 32);
+}
 inline HPoint hpoint_identity() { return HPoint{host::zero<4>(), host::one<4>(host::FR())}; }
 inline bool hpoint_on_curve(const HPoint& p) {
   const host::Field<4>& F = host::FR();
@@ -169,6 +184,7 @@ PM_DEV Fr jj_limbs(const u32x4& a, const u32x4& b, u32 c) {
   r.l[0] = a.x, r.l[1] = a.y, r.l[2] = a.z, r.l[3] = a.w, r.l[4] = b.x, r.l[5] = b.y, r.l[6] = b.z, r.l[7] = b.w, r.l[8] = c;
   return r;
 }
+PM_DEV EdPoint jj_neutral() { return EdPoint{fe_zero<FrP>(), fe_one<FrP>(), fe_one<FrP>(), fe_zero<FrP>()}; }
 // acc += d * (entry |d| of window w of tab): entry e of window w sits at chunk (8 w + e - 1) * 7
 PM_DEV EdPoint jj_fixed_step(const EdPoint& acc, const u32x4* tab, u32 w, int d, const Fr& ed) {
   const u32 mag = (u32)(d < 0 ? -d : d), e = mag == 0 ? 1u : (mag > 8u ? 8u : mag);
@@ -183,6 +199,17 @@ PM_DEV EdPoint jj_fixed_step(const EdPoint& acc, const u32x4* tab, u32 w, int d,
   const Fr at = g_sel(d == 0, zero, g_sel(d < 0, gneg(t), t));
   return ed_madd(acc, ax, ay, at, ed);
 }
+// k B from the window table of B, the digits from the bottom up (the order of a sum being free): 64 ed_madd.  Consumes k.
+PM_DEV EdPoint jj_fixed_walk(const u32x4* tab, u64 (&k)[4], const Fr& ed) {
+  u32 c = 0;
+  EdPoint acc = jj_neutral();
+#pragma unroll 1
+  for (u32 w = 0; w < JJ_WINDOWS; ++w) {
+    acc = jj_fixed_step(acc, tab, w, jj_digit((u32)k[0] & 15u, c), ed);
+    jj_shr4(k);
+  }
+  return acc;
+}
 // (X / Z, Y / Z) to element i of out when live: one inversion, two products (and the change of form); Z = 0 gives (0, 0)
 PM_DEV void jj_store_affine(u32x4* out, size_t i, bool live, const EdPoint& p) {
   const Fr zi = g_to_abi(fe_inv_dev<FrP>(p.Z));             // every lane of the wave is here
@@ -196,7 +223,6 @@ PM_DEV void jj_opaque(Fr& v) {
 #pragma unroll
   for (int i = 0; i < 9; ++i) asm volatile("" : "+v"(v.l[i]));
 }
-PM_DEV EdPoint jj_neutral() { return EdPoint{fe_zero<FrP>(), fe_one<FrP>(), fe_one<FrP>(), fe_zero<FrP>()}; }
 
 // variable base: one thread's table: chunk c of entry e (e P, e = 1..8, X Y Z T as 36 limbs) at base[((e - 1) * 9 + c) * stride],
 // base = scratch + thread, stride = the threads of the grid: the lanes of a wave read and write consecutive 16-byte chunks when
@@ -224,6 +250,39 @@ PM_DEV EdPoint jj_table_load(const u32x4* base, size_t stride, u32 e) {
   for (int j = 0; j < 9; ++j) p.X.l[j] = l[j], p.Y.l[j] = l[9 + j], p.Z.l[j] = l[18 + j], p.T.l[j] = l[27 + j];
   return p;
 }
+// the table of (px, py): e P = (e - 1) P + P, e = 1 .. 8
+PM_DEV void jj_table_build(u32x4* tbl, size_t T, const Fr& px, const Fr& py, const Fr& ed) {
+  const Fr pt = gmul(px, py);
+  EdPoint acc{px, py, fe_one<FrP>(), pt};
+  jj_table_store(tbl, T, 1, acc);
+#pragma unroll 1
+  for (u32 e = 2; e <= 8; ++e) {
+    Fr x = px, y = py, t = pt;
+    jj_opaque(x), jj_opaque(y), jj_opaque(t);
+    acc = ed_madd(acc, x, y, t, ed);
+    jj_table_store(tbl, T, e, acc);
+  }
+}
+// k P over that table from the top digit down: `windows` windows of four doublings and an addition.  The top digit is the top
+// nibble of k and bit 63 of carries the carry into it (jj_carries); a caller with fewer than JJ_WINDOWS digits shifts both up
+// first.  Consumes k.
+PM_DEV EdPoint jj_ladder(const u32x4* tbl, size_t T, u64 (&k)[4], u64 carries, u32 windows, const Fr& ed) {
+  EdPoint acc = jj_neutral();
+#pragma unroll 1
+  for (u32 w = 0; w < windows; ++w) {
+#pragma unroll 1
+    for (u32 j = 0; j < 4; ++j) acc = ed_add(acc, acc, ed);
+    u32 c = (u32)(carries >> 63);
+    const int d = jj_digit((u32)(k[3] >> 60), c);
+    jj_shl4(k);
+    carries <<= 1;
+    const u32 mag = (u32)(d < 0 ? -d : d), e = mag == 0 ? 1u : (mag > 8u ? 8u : mag);
+    const EdPoint q = jj_table_load(tbl, T, e);
+    const EdPoint s{g_sel(d < 0, gneg(q.X), q.X), q.Y, q.Z, g_sel(d < 0, gneg(q.T), q.T)};
+    acc = ed_add(acc, ed_sel(d == 0, jj_neutral(), s), ed);
+  }
+  return acc;
+}
 // the words of r, most significant first
 constexpr u32 JJ_R_WORDS[8] = {0x73eda753u, 0x299d7d48u, 0x3339d808u, 0x09a1d805u, 0x53bda402u, 0xfffe5bfeu, 0xffffffffu, 0x00000001u};
 PM_DEV bool jj_below_r(const u32x4& lo, const u32x4& hi) {
@@ -236,17 +295,22 @@ PM_DEV bool jj_below_r(const u32x4& lo, const u32x4& hi) {
   }
   return below;
 }
+// the canonical value of v (normalised, below 2 r) is zero
+PM_DEV bool jj_is_zero(const Fr& v) {
+  u32 s[8], any = 0;
+  fe_canon_pack<FrP>(s, v);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) any |= s[j];
+  return any == 0;
+}
 // the point at p (x | y): both coordinates below r and on the curve; x and y in the device form whatever the answer
 PM_DEV bool jj_point_ok(const u32x4* p, const Fr& ed, Fr& x, Fr& y) {
   const bool canonical = jj_below_r(p[0], p[1]) && jj_below_r(p[2], p[3]);
   x = g_to_dev(ld_canon(p, 0)), y = g_to_dev(ld_canon(p, 1));
   const Fr x2 = gmul(x, x), y2 = gmul(y, y);
   const Fr rhs = gadd(fe_one<FrP>(), gmul(gmul(x2, y2), ed));
-  u32 s[8], any = 0;
-  fe_canon_pack<FrP>(s, gsub(gsub(y2, x2), rhs));
-#pragma unroll
-  for (int j = 0; j < 8; ++j) any |= s[j];
-  return canonical && any == 0;
+  const bool on_curve = jj_is_zero(gsub(gsub(y2, x2), rhs));   // not under `canonical &&`: no branch around the test
+  return canonical && on_curve;
 }
 
 // ------------------------------------------------------------------ argument checks
@@ -260,10 +324,26 @@ inline int base_fault(pm_ctx* ctx, const pm_jubjub_base* b) {
   if (b->device != ctx->device) return set_err(ctx, PM_ERR_BAD_ARG, "the base belongs to another device");
   return PM_OK;
 }
-inline bool unaligned(std::initializer_list<const void*> ps) {
-  uintptr_t acc = 0;
-  for (const void* p : ps) acc |= (uintptr_t)p;
-  return (acc & 15u) != 0;
+
+// ------------------------------------------------------------------ a slot per thread in flight
+// The calls whose threads keep a window table in memory (pm_jubjub_mul_dev, pm_schnorr_verify_dev, pm_poseidon_cipher_scan_dev)
+// bound their grid -- eight workgroups of 64 a CU at the most -- and walk n in strides of its threads.
+inline size_t slot_blocks(const pm_ctx* ctx, size_t n) {
+  return std::max<size_t>(std::min<size_t>((n + 63) / 64, (size_t)std::max(ctx->num_cus, 1) * 8), 1);
 }
+// ... and allocate, per call, the slots of that grid ([entry][chunk][thread of the grid]) with a tail of control words behind
+// them.  finish_call (context.h) releases it once the launches are on the stream.
+struct SlotScratch {
+  size_t blocks, stride;    // the grid and its threads
+  size_t slot_bytes = 0;
+  char* base = nullptr;
+  SlotScratch(const pm_ctx* ctx, size_t n) : blocks(slot_blocks(ctx, n)), stride(blocks * 64) {}
+  hipError_t alloc(size_t bytes_per_thread, size_t tail_bytes) {
+    slot_bytes = stride * bytes_per_thread;
+    return hipMalloc((void**)&base, slot_bytes + tail_bytes);
+  }
+  u32x4* slots() const { return (u32x4*)base; }
+  unsigned long long* tail() const { return (unsigned long long*)(base + slot_bytes); }
+};
 
 }  // namespace pm

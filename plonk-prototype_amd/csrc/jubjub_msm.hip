@@ -286,11 +286,6 @@ __global__ void __launch_bounds__(64) jmsm_final_kernel(const JmsmArgs a) {
   jj_store_affine(a.out, b, live, acc);
 }
 
-bool overlaps(const void* p, size_t pb, const void* q, size_t qb) {
-  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
-  return pb && qb && a < b + qb && b < a + pb;
-}
-
 }  // namespace
 
 // context.h: the launches of one MSM on st, arguments already checked; the caller holds the context's mutex and has selected
@@ -345,8 +340,7 @@ extern "C" int pm_jubjub_msm_dev(pm_ctx* ctx, const void* d_points_xy, const voi
                                  uint32_t batch, uint32_t scalar_form, void* d_out_xy, void* hip_stream) {
   if (!ctx) return PM_ERR_BAD_ARG;
   if (int rc = form_fault(ctx, scalar_form)) return rc;
-  if (!d_out_xy || unaligned({d_points_xy, d_scalars, d_out_xy}) || (n != 0 && (!d_points_xy || !d_scalars)))
-    return set_err(ctx, PM_ERR_BAD_ARG, "null or unaligned device pointer");
+  if (int rc = pointer_fault(ctx, {d_out_xy}, unaligned({d_points_xy, d_scalars}) || (n != 0 && (!d_points_xy || !d_scalars)))) return rc;
   if (batch == 0) return set_err(ctx, PM_ERR_BAD_ARG, "pm_jubjub_msm_dev: batch = 0");
   if (scalar_stride < n) return set_err(ctx, PM_ERR_BAD_ARG, "pm_jubjub_msm_dev: scalar_stride < n");
   if (n > 0x7fffffffu || scalar_stride > ((size_t)1 << 40)) return set_err(ctx, PM_ERR_LENGTH, "pm_jubjub_msm_dev: n > 2^31 - 1 or scalar_stride > 2^40");
@@ -355,10 +349,9 @@ extern "C" int pm_jubjub_msm_dev(pm_ctx* ctx, const void* d_points_xy, const voi
   if (jubjub_msm_plan(n, batch, ctx->opt_jubjub_msm_window_bits, &p) == PM_ERR_LENGTH)
     return set_err(ctx, PM_ERR_LENGTH, "pm_jubjub_msm_dev: n x windows x batch exceeds what the plan indexes (jubjub_msm_plan.h)");
   const size_t out_bytes = 64 * (size_t)batch, scalar_bytes = n ? 32 * ((size_t)(batch - 1) * scalar_stride + n) : 0;
-  if (overlaps(d_out_xy, out_bytes, d_points_xy, 64 * n) || overlaps(d_out_xy, out_bytes, d_scalars, scalar_bytes))
+  if (overlap(d_out_xy, out_bytes, d_points_xy, 64 * n) || overlap(d_out_xy, out_bytes, d_scalars, scalar_bytes))   // n = 0: empty ranges
     return set_err(ctx, PM_ERR_BAD_ARG, "pm_jubjub_msm_dev: d_out_xy overlaps an input");
-  PM_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  PM_DEVICE_STREAM(ctx, hip_stream, st);
   return jubjub_msm_enqueue(ctx, d_points_xy, d_scalars, n, scalar_stride, batch, scalar_form == PM_SCALAR_MONTGOMERY, d_out_xy, st);
 }
 
@@ -372,8 +365,7 @@ extern "C" int pm_jubjub_msm_host(const uint64_t* points_xy, const uint64_t* sca
     if (point_fault(points_xy + 8 * i) || !scalar_to_int(scalars + 4 * i, scalar_form, k)) return PM_ERR_BAD_ARG;
     acc = hpoint_add(acc, hpoint_mul(hpoint_load(points_xy + 8 * i), k));
   }
-  memcpy(out_xy, acc.x.l, 32);
-  memcpy(out_xy + 4, acc.y.l, 32);
+  hpoint_store(out_xy, acc);
   return PM_OK;
 }
 

@@ -131,13 +131,6 @@ PM_DEV void st_wide(const WidePtr& w, size_t i, const Fr& v) {
   reinterpret_cast<u32*>(q + 2 * G)[e] = v.l[8];
 }
 
-PM_DEV Fr fr_limbs(const u32* c) {
-  Fr r;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) r.l[i] = c[i];
-  return r;
-}
-
 // w^e from the two-level table: hi[e >> lh] * lo[e & mask]   -> (1, <2)
 PM_DEV Fr two_level(const u32x4* hi, const u32x4* lo, u32 e, u32 lh) {
   return fe_mul<FrP>(ld_tw(hi, e >> lh), ld_tw(lo, e & ((1u << lh) - 1u)));

@@ -40,7 +40,6 @@ using host::HFr;
 constexpr u32 SCH_WINDOWS = 63;                             // signed base-16 digits of a challenge below 2^250 (the top one <= 4)
 constexpr u32 SCH_SLOT_ENTRIES = 9;                         // a thread's scratch: 1 PK .. 8 PK, then u G
 constexpr size_t SCH_SLOT_BYTES = (SCH_SLOT_ENTRIES * (size_t)JJ_POINT_CHUNKS + 3) * 16;   // 1344 per thread in flight
-constexpr size_t SCH_BLOCKS_PER_CU = 8;                     // as pm_jubjub_mul_dev: eight workgroups of 64 a CU at the most
 
 // ------------------------------------------------------------------ the host forms (csrc/host_field.h)
 // the point is not the identity and l times it is
@@ -124,13 +123,6 @@ PM_DEV void sch_challenge(const Fr& h, u64 (&c)[4]) {
   for (int i = 0; i < 4; ++i) c[i] = (u64)w[2 * i] | ((u64)w[2 * i + 1] << 32);
   c[3] &= (1ull << 58) - 1;
 }
-PM_DEV bool sch_is_zero(const Fr& v) {                      // v normalised, below 2 r
-  u32 s[8], any = 0;
-  fe_canon_pack<FrP>(s, v);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) any |= s[j];
-  return any == 0;
-}
 
 __global__ void __launch_bounds__(64) schnorr_sign_kernel(const HadesTab tab, const SchnorrIo a) {
   const size_t g = (size_t)blockIdx.x * 64 + threadIdx.x;
@@ -140,13 +132,7 @@ __global__ void __launch_bounds__(64) schnorr_sign_kernel(const HadesTab tab, co
   // ---- R = k G
   u64 k[4];
   jj_load_scalar(a.nonces + 2 * i, a.montgomery != 0, k);
-  u32 cy = 0;
-  EdPoint acc = jj_neutral();
-#pragma unroll 1
-  for (u32 w = 0; w < JJ_WINDOWS; ++w) {
-    acc = jj_fixed_step(acc, a.tab_g, w, jj_digit((u32)k[0] & 15u, cy), ed);
-    jj_shr4(k);
-  }
+  const EdPoint acc = jj_fixed_walk(a.tab_g, k, ed);
   const Fr zi = fe_inv_dev<FrP>(acc.Z);                     // every lane of the wave is here; nothing below crosses lanes
   Fr s[5];
   {
@@ -189,14 +175,7 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 4)))
   u64 u[4];
   jj_load_scalar(sig, a.montgomery != 0, u);
   const bool u_ok = jj_below_r(sig[0], sig[1]) && scl_below_l(u);
-  u32 cy = 0;
-  EdPoint ug = jj_neutral();
-#pragma unroll 1
-  for (u32 w = 0; w < JJ_WINDOWS; ++w) {
-    ug = jj_fixed_step(ug, a.tab_g, w, jj_digit((u32)u[0] & 15u, cy), ed);
-    jj_shr4(u);
-  }
-  jj_table_store(tbl, T, SCH_SLOT_ENTRIES, ug);
+  jj_table_store(tbl, T, SCH_SLOT_ENTRIES, jj_fixed_walk(a.tab_g, u, ed));
   // ---- the two points, the challenge
   Fr s[5];
   {
@@ -229,38 +208,16 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
     c[0] = (u64)c0.x | ((u64)c0.y << 32), c[1] = (u64)c0.z | ((u64)c0.w << 32);
     c[2] = (u64)c1.x | ((u64)c1.y << 32), c[3] = (u64)c1.z | ((u64)c1.w << 32);
   }
-  // ---- the table of PK: e PK = (e - 1) PK + PK
-  const Fr px = g_to_dev(ld_canon(a.pks, 2 * (size_t)i)), py = g_to_dev(ld_canon(a.pks, 2 * (size_t)i + 1)), pt = gmul(px, py);
-  EdPoint acc{px, py, fe_one<FrP>(), pt};
-  jj_table_store(tbl, T, 1, acc);
-#pragma unroll 1
-  for (u32 e = 2; e <= 8; ++e) {
-    Fr x = px, y = py, t = pt;
-    jj_opaque(x), jj_opaque(y), jj_opaque(t);
-    acc = ed_madd(acc, x, y, t, ed);
-    jj_table_store(tbl, T, e, acc);
-  }
+  // ---- the table of PK
+  jj_table_build(tbl, T, g_to_dev(ld_canon(a.pks, 2 * (size_t)i)), g_to_dev(ld_canon(a.pks, 2 * (size_t)i + 1)), ed);
   // ---- c PK from digit 62 down: digit 63 of c < 2^250 is zero and nothing carries into it
-  u64 carries = jj_carries(c) << 1;
+  const u64 carries = jj_carries(c) << 1;
   jj_shl4(c);
-  acc = jj_neutral();
-#pragma unroll 1
-  for (u32 w = 0; w < SCH_WINDOWS; ++w) {
-#pragma unroll 1
-    for (u32 j = 0; j < 4; ++j) acc = ed_add(acc, acc, ed);
-    u32 cw = (u32)(carries >> 63);
-    const int d = jj_digit((u32)(c[3] >> 60), cw);
-    jj_shl4(c);
-    carries <<= 1;
-    const u32 mag = (u32)(d < 0 ? -d : d), e = mag == 0 ? 1u : (mag > 8u ? 8u : mag);
-    const EdPoint q = jj_table_load(tbl, T, e);
-    const EdPoint s{g_sel(d < 0, gneg(q.X), q.X), q.Y, q.Z, g_sel(d < 0, gneg(q.T), q.T)};
-    acc = ed_add(acc, ed_sel(d == 0, jj_neutral(), s), ed);
-  }
+  EdPoint acc = jj_ladder(tbl, T, c, carries, SCH_WINDOWS, ed);
   // ---- u G + c PK = R: X = R.x Z and Y = R.y Z
   acc = ed_add(acc, jj_table_load(tbl, T, SCH_SLOT_ENTRIES), ed);
   const Fr rx = g_to_dev(ld_canon(a.sigs_in, 3 * (size_t)i + 1)), ry = g_to_dev(ld_canon(a.sigs_in, 3 * (size_t)i + 2));
-  const bool same = sch_is_zero(gsub(acc.X, gmul(rx, acc.Z))) && sch_is_zero(gsub(acc.Y, gmul(ry, acc.Z)));
+  const bool same = jj_is_zero(gsub(acc.X, gmul(rx, acc.Z))) && jj_is_zero(gsub(acc.Y, gmul(ry, acc.Z)));
   size_t at = ((size_t)SCH_SLOT_ENTRIES * JJ_POINT_CHUNKS + 2) * T;
   asm volatile("" : "+s"(at));                               // formed here from tbl: no second address is held across the ladder
   const u32 early = tbl[at].x;
@@ -402,9 +359,6 @@ __global__ void __launch_bounds__(256) schnorr_batch_sum_kernel(const SchnorrBat
 }
 
 // ------------------------------------------------------------------ launches
-size_t verify_blocks(const pm_ctx* ctx, size_t n) {
-  return std::max<size_t>(std::min<size_t>((n + 63) / 64, (size_t)std::max(ctx->num_cus, 1) * SCH_BLOCKS_PER_CU), 1);
-}
 // the base's order, once per handle; the caller holds the context's mutex
 int order_fault(pm_ctx* ctx, const pm_jubjub_base* g, const char* who) {
   if (g->order_state == 0) g->order_state = point_has_order_l(g->xy) ? 1 : -1;
@@ -414,8 +368,7 @@ int order_fault(pm_ctx* ctx, const pm_jubjub_base* g, const char* who) {
 }
 int common_fault(pm_ctx* ctx, const pm_jubjub_base* g, const pm_hades_params* params, uint32_t scalar_form) {
   if (int rc = base_fault(ctx, g)) return rc;
-  if (!params) return set_err(ctx, PM_ERR_BAD_ARG, "null params");
-  if (params->device != ctx->device) return set_err(ctx, PM_ERR_BAD_ARG, "the params belong to another device");
+  if (int rc = params_fault(ctx, params)) return rc;
   return form_fault(ctx, scalar_form);
 }
 
@@ -431,14 +384,12 @@ extern "C" int pm_schnorr_sign_dev(pm_ctx* ctx, const pm_jubjub_base* g, const p
   if (int rc = common_fault(ctx, g, params, scalar_form)) return rc;
   SchnorrIo a{};
   if (int rc = capacity_to_dev(ctx, capacity, a.capacity)) return rc;
-  if (!d_secret_keys || !d_nonces || !d_msgs || !d_sigs || unaligned({d_secret_keys, d_nonces, d_msgs, d_sigs}))
-    return set_err(ctx, PM_ERR_BAD_ARG, "null or unaligned device pointer");
-  if (n > 0x7fffffffu) return set_err(ctx, PM_ERR_LENGTH, "n > 2^31");
+  if (int rc = pointer_fault(ctx, {d_secret_keys, d_nonces, d_msgs, d_sigs})) return rc;
+  if (int rc = count_fault(ctx, n)) return rc;
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (int rc = order_fault(ctx, g, "pm_schnorr_sign_dev")) return rc;
   if (n == 0) return PM_OK;
-  PM_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  PM_DEVICE_STREAM(ctx, hip_stream, st);
   a.tab_g = (const u32x4*)g->d_tab, a.keys = (const u32x4*)d_secret_keys, a.nonces = (const u32x4*)d_nonces;
   a.msgs = (const u32x4*)d_msgs, a.sigs_out = (u32x4*)d_sigs, a.n = n, a.montgomery = scalar_form == PM_SCALAR_MONTGOMERY;
   jubjub_d_limbs(a.edwards_d);
@@ -456,46 +407,35 @@ extern "C" int pm_schnorr_verify_dev(pm_ctx* ctx, const pm_jubjub_base* g, const
   SchnorrIo a{};
   if (int rc = capacity_to_dev(ctx, capacity, a.capacity)) return rc;
   if (!d_reasons && !first_bad) return set_err(ctx, PM_ERR_BAD_ARG, "d_reasons and first_bad are both null");
-  if (!d_pks_xy || !d_msgs || !d_sigs || unaligned({d_pks_xy, d_msgs, d_sigs}) || ((uintptr_t)d_reasons & 3u))
-    return set_err(ctx, PM_ERR_BAD_ARG, "null or unaligned device pointer");
-  if (n > 0x7fffffffu) return set_err(ctx, PM_ERR_LENGTH, "n > 2^31");
+  if (int rc = pointer_fault(ctx, {d_pks_xy, d_msgs, d_sigs}, ((uintptr_t)d_reasons & 3u) != 0)) return rc;
+  if (int rc = count_fault(ctx, n)) return rc;
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (int rc = order_fault(ctx, g, "pm_schnorr_verify_dev")) return rc;
   if (first_bad) *first_bad = n;
   if (n == 0) return PM_OK;
-  PM_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  PM_DEVICE_STREAM(ctx, hip_stream, st);
   // the slots of the threads in flight, and eight bytes for the lowest failing index
-  const size_t blocks = verify_blocks(ctx, n), slot_bytes = blocks * 64 * SCH_SLOT_BYTES;
-  void* scratch = nullptr;
-  PM_HIP(ctx, hipMalloc(&scratch, slot_bytes + 16));
-  unsigned long long* const d_bad = (unsigned long long*)((char*)scratch + slot_bytes);
+  SlotScratch scratch(ctx, n);
+  PM_HIP(ctx, scratch.alloc(SCH_SLOT_BYTES, 16));
+  unsigned long long* const d_bad = scratch.tail();
   unsigned long long bad = n;
-  a.tab_g = (const u32x4*)g->d_tab, a.first_bad = first_bad ? d_bad : nullptr, a.scratch = (u32x4*)scratch;
+  a.tab_g = (const u32x4*)g->d_tab, a.first_bad = first_bad ? d_bad : nullptr, a.scratch = scratch.slots();
   a.montgomery = scalar_form == PM_SCALAR_MONTGOMERY;
   jubjub_d_limbs(a.edwards_d);
   const HadesTab tab = tab_of(params);
   hipError_t e = first_bad ? hipMemcpyAsync(d_bad, &bad, 8, hipMemcpyHostToDevice, st) : hipSuccess;
   if (e == hipSuccess) {
     ProfScope prof(ctx, st, "schnorr_verify");
-    const size_t stride = blocks * 64;
-    for (size_t off = 0; off < n && e == hipSuccess; off += stride) {   // a stride's tail is done before the next head reuses the slots
-      a.n = std::min(stride, n - off), a.base = off;
+    for (size_t off = 0; off < n && e == hipSuccess; off += scratch.stride) {   // a stride's tail is done before the next head reuses the slots
+      a.n = std::min(scratch.stride, n - off), a.base = off;
       a.pks = (const u32x4*)d_pks_xy + 4 * off, a.msgs = (const u32x4*)d_msgs + 2 * off, a.sigs_in = (const u32x4*)d_sigs + 6 * off;
       a.reasons = d_reasons ? (u32*)d_reasons + off : nullptr;
-      hipLaunchKernelGGL(schnorr_verify_head_kernel, dim3((unsigned)blocks), dim3(64), 0, st, tab, a);
-      hipLaunchKernelGGL(schnorr_verify_tail_kernel, dim3((unsigned)blocks), dim3(64), 0, st, a);
+      hipLaunchKernelGGL(schnorr_verify_head_kernel, dim3((unsigned)scratch.blocks), dim3(64), 0, st, tab, a);
+      hipLaunchKernelGGL(schnorr_verify_tail_kernel, dim3((unsigned)scratch.blocks), dim3(64), 0, st, a);
       e = hipGetLastError();
     }
   }
-  if (e == hipSuccess && first_bad) {
-    e = hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-  }
-  // the launch is ordered on the stream like any other; releasing the scratch waits for it (hipFree waits for the device)
-  const hipError_t e2 = hipFree(scratch);
-  if (e == hipSuccess) e = e2;
-  if (e != hipSuccess) return set_err(ctx, PM_ERR_HIP, std::string("pm_schnorr_verify_dev: ") + hipGetErrorString(e));
+  if (int rc = finish_call(ctx, e, st, first_bad ? &bad : nullptr, d_bad, 8, scratch.base, "pm_schnorr_verify_dev")) return rc;
   if (first_bad) *first_bad = (size_t)bad;
   return PM_OK;
 }
@@ -511,8 +451,7 @@ extern "C" int pm_schnorr_sign_host(const uint64_t g_xy[8], uint32_t rounds, uin
   host_challenge(rounds, full_rounds, ark, mds, n_mds, capacity, r, msg, c);
   host::mulsub_l(ki, c, ski, u);
   scalar_from_int(u, scalar_form, sig);
-  memcpy(sig + 4, r.x.l, 32);
-  memcpy(sig + 8, r.y.l, 32);
+  hpoint_store(sig + 4, r);
   return PM_OK;
 }
 
@@ -546,14 +485,14 @@ extern "C" int pm_schnorr_verify_batch_dev(pm_ctx* ctx, const pm_jubjub_base* g,
   SchnorrBatchIo a{};
   if (int rc = capacity_to_dev(ctx, capacity, a.capacity)) return rc;
   if (!result || !first_bad) return set_err(ctx, PM_ERR_BAD_ARG, "null result or first_bad");
-  if (unaligned({d_pks_xy, d_msgs, d_sigs, d_weights, d_sum_xy}) || (n != 0 && (!d_pks_xy || !d_msgs || !d_sigs || !d_weights)))
-    return set_err(ctx, PM_ERR_BAD_ARG, "null or unaligned device pointer");
+  if (int rc = pointer_fault(ctx, {}, unaligned({d_pks_xy, d_msgs, d_sigs, d_weights, d_sum_xy}) ||
+                                          (n != 0 && (!d_pks_xy || !d_msgs || !d_sigs || !d_weights))))
+    return rc;
   if (n > 0x3fffffffu) return set_err(ctx, PM_ERR_LENGTH, "pm_schnorr_verify_batch_dev: n > 2^30 - 1");
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (int rc = order_fault(ctx, g, "pm_schnorr_verify_batch_dev")) return rc;
   *result = PM_SCHNORR_OK, *first_bad = n;
-  PM_HIP(ctx, hipSetDevice(ctx->device));
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+  PM_DEVICE_STREAM(ctx, hip_stream, st);
   if (n == 0) {                                              // the empty sum: accepted, W = (0, 1)
     if (!d_sum_xy) return PM_OK;
     if (int rc = jubjub_msm_enqueue(ctx, nullptr, nullptr, 0, 0, 1, false, d_sum_xy, st)) return rc;
@@ -584,12 +523,9 @@ extern "C" int pm_schnorr_verify_batch_dev(pm_ctx* ctx, const pm_jubjub_base* g,
     if (e == hipSuccess) rc = jubjub_msm_enqueue(ctx, a.points, a.scalars, m, m, 1, false, d_w, st);
   }
   if (e == hipSuccess && rc == PM_OK) e = hipMemcpyAsync(w, d_w, 64, hipMemcpyDeviceToHost, st);
-  if (e == hipSuccess && rc == PM_OK) e = hipMemcpyAsync(ctl, a.ctl, 16, hipMemcpyDeviceToHost, st);
   if (e == hipSuccess && rc == PM_OK && d_sum_xy) e = hipMemcpyAsync(d_sum_xy, d_w, 64, hipMemcpyDeviceToDevice, st);
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  const hipError_t e2 = hipFree(buf);
-  if (e == hipSuccess) e = e2;
-  if (e != hipSuccess) return set_err(ctx, PM_ERR_HIP, std::string("pm_schnorr_verify_batch_dev: ") + hipGetErrorString(e));
+  // the control words last: their way back is the wait for all of it
+  if (int frc = finish_call(ctx, e, st, rc == PM_OK ? ctl : nullptr, a.ctl, 16, buf, "pm_schnorr_verify_batch_dev")) return frc;
   if (rc != PM_OK) return rc;
   if (ctl[1] < n)
     return set_err(ctx, PM_ERR_BAD_ARG, "pm_schnorr_verify_batch_dev: weight " + std::to_string(ctl[1]) + " is zero (it would drop its signature)");
@@ -607,6 +543,6 @@ extern "C" int pm_schnorr_verify_batch_dev(pm_ctx* ctx, const pm_jubjub_base* g,
 
 extern "C" int pm_test_schnorr_stride(pm_ctx* ctx, size_t* stride) {
   if (!ctx || !stride) return PM_ERR_BAD_ARG;
-  *stride = verify_blocks(ctx, ~(size_t)0 >> 1) * 64;
+  *stride = slot_blocks(ctx, ~(size_t)0 >> 1) * 64;
   return PM_OK;
 }

@@ -167,6 +167,31 @@ def test_many_waves(ctx):
         g.free(), h.free()
 
 
+def test_variable_base_walks_n_in_strides(ctx):
+    """more products than the grid holds threads: the kernel's own loop takes a second round, a full wave and a ragged one, in place"""
+    import plonk_prototype_amd as pa
+    stride = C.c_size_t()
+    assert ctx._lib.pm_test_schnorr_stride(ctx._h, C.byref(stride)) == 0     # the one grid of the calls with a slot a thread
+    T = stride.value
+    assert T >= 64 and T % 64 == 0
+    n, period = T + 65, 64
+    rng = random.Random(64)
+    pts = J.edge_points(extra=2)
+    ps = [pts[i % len(pts)] for i in range(period)]
+    sc = [rng.randrange(R) for _ in range(period)]
+    want = J.to_limbs([J.mul(p, s) for p, s in zip(ps, sc)])
+    tile = lambda a: np.tile(a, (n // period + 1,) + (1,) * (a.ndim - 1))[:n]   # noqa: E731
+    dp, ds = pa.DeviceVector.from_host(ctx, tile(J.to_limbs(ps))), pa.DeviceVector.from_host(ctx, tile(_mont(sc)))
+    try:
+        pa.jubjub_mul_dev(ctx, dp.ptr, ds.ptr, n, dp.ptr)                      # out = the points
+        got = dp.to_host().reshape(n, 2, 4)
+    finally:
+        dp.free(), ds.free()
+    if got.tobytes() != tile(want).tobytes():
+        bad = np.flatnonzero((got != tile(want)).any(axis=(1, 2)))
+        raise AssertionError(f"{bad.size} of {n} products differ from 64 of the model's, tiled; first {bad[:8]}, T = {T}")
+
+
 # ---------------------------------------------------------------------------------- 5. the point check
 def test_check(ctx):
     import plonk_prototype_amd as pa
