@@ -1077,6 +1077,65 @@ int pm_poseidon_cipher_encrypt_host(uint32_t rounds, uint32_t full_rounds, const
 int pm_poseidon_cipher_decrypt_host(uint32_t rounds, uint32_t full_rounds, const uint64_t* ark, const uint64_t* mds, uint32_t n_mds,
                                     const uint64_t secret_xy[8], const uint64_t nonce[4], const uint64_t* cipher, uint32_t msg_len,
                                     uint64_t* msg_out, uint32_t* status);
+/* ---- JubJub wire format: batch point decoding with square roots in Fr on the GPU --------------------
+ * A ledger keeps a JubJub point -- the ephemeral key of a note, a public key, the R of a signature -- as 32 bytes: the canonical
+ * y, little-endian, with the least significant bit of the canonical x in bit 7 of byte 31.  This is the SHAPE of
+ * JubJubAffine::to_bytes / from_bytes as remembered -- prior knowledge that nothing in this repository pins, exactly like the
+ * cipher and the Schnorr signature above: it is NOT claimed to accept dusk-jubjub's bytes.  One decision is stricter than the
+ * 2019-era from_bytes as remembered: x = 0 with the sign bit set is REFUSED, so the accepted bytes are exactly the image of the
+ * encoder and decode-then-encode is the identity.
+ *
+ * Square roots.  pm_fr_sqrt_dev: n canonical Montgomery elements at d_in -> n roots at d_out (d_out == d_in is allowed) and n
+ * uint32 flags at d_is_square (may be NULL): 1 and the root whose canonical integer is EVEN (0 for 0) for a square, 0 and root 0
+ * for a non-square or an input that is not below r.  One thread an element, no data-dependent trip count: one fixed
+ * exponentiation, the discrete logarithm in the subgroup of order 2^32 by four 8-bit windows against tables the context builds
+ * once (49 KiB of device memory, released by pm_trim and at shutdown).  n_square may be NULL; with it the call WAITS for the
+ * stream and returns the count of flag 1.  pm_fr_sqrt_host: one element on the CPU, no context, by the plain Tonelli-Shanks
+ * loop: on purpose another algorithm.
+ *
+ * Decoding: clear the sign bit and require y < r; x = sqrt((y^2 - 1) / (1 + d y^2)) (the denominator is never zero: -1 / d is
+ * a non-square), negated when its parity differs from the sign bit.  The status of a point is the LOWEST that applies:
+ *   PM_JUBJUB_OK                   decoded
+ *   PM_JUBJUB_BAD_RANGE            y (bits 0 .. 254) is not below r
+ *   PM_JUBJUB_BAD_NOT_ON_CURVE     (y^2 - 1) / (1 + d y^2) is not a square: no point has this y
+ *   PM_JUBJUB_BAD_SIGN             x = 0 with the sign bit set
+ *   PM_JUBJUB_BAD_NOT_IN_SUBGROUP  only with PM_JUBJUB_CHECK_SUBGROUP: [l] P is not the identity (the identity passes)
+ * A refused point is written as (0, 0), which is off the curve, so every later call refuses it: a scan answers PM_CIPHER_POINT,
+ * a verification its bad-R / bad-PK reason.  A refused point is NOT an error of the call: a ledger holds other people's
+ * garbage, so the verdict is per point, as in the cipher calls.  PM_JUBJUB_CHECK_SUBGROUP is OFF by default because it costs a
+ * whole 256-doubling ladder a point (the wave-uniform ladder of the scan under the digits of l, with a table of 1152 bytes a
+ * thread in flight that the call allocates and releases, which WAITS for the device) where the decoding itself is a few
+ * hundred products.
+ *   pm_jubjub_decompress_dev: record i is the 32 bytes at d_bytes + i in_stride_bytes; point i (x | y, canonical Montgomery)
+ *     goes to d_out_xy + i out_stride_bytes.  A stride of 0 means packed (32 and 64 bytes); otherwise it is a multiple of 16
+ *     that is at least the packed size, anything else is PM_ERR_BAD_ARG, as are unknown flag bits, NULL among the required
+ *     pointers and a pointer that is not 16-byte aligned.  A strided call touches nothing between its records: the R halves
+ *     of n signatures (u | R, 64 bytes) decode with in_stride_bytes = 64, out_stride_bytes = 96 straight into (u, R.x, R.y)
+ *     records.  Input and output must not overlap.  d_status receives n uint32 and may be NULL; n_ok may be NULL, and with it
+ *     the call WAITS for the stream and returns the count of status 0.  n = 0 launches nothing (PM_OK, *n_ok = 0).
+ *   pm_jubjub_compress_dev: n points (64 bytes each, packed) -> n x 32 bytes at d_bytes_out, which must not overlap them.  The
+ *     points are NOT validated (the rule of pm_jubjub_mul_dev): anything that is not a canonical point gives unspecified
+ *     bytes, but the call does not fault.  Asynchronous.
+ *   pm_dev_copy_strided: `rows` runs of width_bytes from d_src + i src_stride_bytes to d_dst + i dst_stride_bytes, device to
+ *     device on hip_stream, asynchronous: how the u halves of byte signatures reach their records.  Strides are at least the
+ *     width; rows = 0 or width_bytes = 0 copies nothing.
+ * The host forms need no context and no GPU (csrc/host_field.h).  pm_jubjub_decompress writes the status; bytes it can judge
+ * are not errors.  pm_jubjub_compress returns PM_ERR_BAD_ARG for a point off the curve or a coordinate that is not below r. */
+#define PM_JUBJUB_CHECK_SUBGROUP 1u
+#define PM_JUBJUB_OK 0u
+#define PM_JUBJUB_BAD_RANGE 1u
+#define PM_JUBJUB_BAD_NOT_ON_CURVE 2u
+#define PM_JUBJUB_BAD_SIGN 3u
+#define PM_JUBJUB_BAD_NOT_IN_SUBGROUP 4u
+int pm_fr_sqrt_dev(pm_ctx* ctx, const void* d_in, size_t n, void* d_out, void* d_is_square, size_t* n_square, void* hip_stream);
+int pm_fr_sqrt_host(const uint64_t a[4], uint64_t out[4], uint32_t* is_square);
+int pm_jubjub_compress(const uint64_t xy[8], uint8_t out[32]);
+int pm_jubjub_decompress(const uint8_t in[32], uint32_t flags, uint64_t xy[8], uint32_t* status);
+int pm_jubjub_compress_dev(pm_ctx* ctx, const void* d_xy, size_t n, void* d_bytes_out, void* hip_stream);
+int pm_jubjub_decompress_dev(pm_ctx* ctx, const void* d_bytes, size_t in_stride_bytes, size_t n, uint32_t flags, void* d_out_xy,
+                             size_t out_stride_bytes, void* d_status, size_t* n_ok, void* hip_stream);
+int pm_dev_copy_strided(pm_ctx* ctx, void* d_dst, size_t dst_stride_bytes, const void* d_src, size_t src_stride_bytes,
+                        size_t width_bytes, size_t rows, void* hip_stream);
 /* Proof::to_bytes: 11 x 48-byte compressed G1, then the 16 scalars of ProofEvaluations::to_bytes. */
 int pm_plonk_proof_to_bytes(const pm_plonk_proof* proof, uint8_t out[PM_PLONK_PROOF_BYTES]);
 /* ---- The prover with coefficient-range ownership end to end (SURVEY.md section 8e row 3 + 8f N5; configs[4]) ----------

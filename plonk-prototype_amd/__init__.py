@@ -14,9 +14,10 @@ from .host import (CommitKey, Context, DeviceVector, Error, EvaluationDomain, La
 from . import cipher, field, jubjub, poseidon, prover, schnorr, srs, synthetic, transcript  # noqa: F401,E402
 from .cipher import (CIPHER_REASONS, PoseidonCipher, poseidon_cipher_decrypt_host,  # noqa: F401,E402
                      poseidon_cipher_encrypt_host)
-from .jubjub import (JUBJUB_GENERATOR, JubJubBase, jubjub_add_host, jubjub_check, jubjub_commit,  # noqa: F401,E402
-                     jubjub_commit_dev, jubjub_msm, jubjub_msm_dev, jubjub_msm_host, jubjub_mul, jubjub_mul_dev,
-                     jubjub_mul_host)
+from .jubjub import (JUBJUB_CODEC_REASONS, JUBJUB_GENERATOR, JubJubBase, fr_sqrt, fr_sqrt_dev, fr_sqrt_host,  # noqa: F401,E402
+                     jubjub_add_host, jubjub_check, jubjub_commit, jubjub_commit_dev, jubjub_compress, jubjub_compress_dev,
+                     jubjub_compress_host, jubjub_decompress, jubjub_decompress_dev, jubjub_decompress_host, jubjub_msm,
+                     jubjub_msm_dev, jubjub_msm_host, jubjub_mul, jubjub_mul_dev, jubjub_mul_host)
 from .poseidon import Hades, MerkleTree, hades_permute_host, poseidon_hash_host  # noqa: F401,E402
 from .prover import (BatchWorkspace, Circuit, Gadget, GadgetInputError, GadgetReport, Proof, ProverKey,  # noqa: F401,E402
                      UnsatisfiedWitness, WitnessReport, preprocess, prove, prove_batch, random_blinders, sigma_from_wires)

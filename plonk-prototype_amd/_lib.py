@@ -240,6 +240,14 @@ SIGNATURES = {
                                                   u64p]),
     "pm_poseidon_cipher_decrypt_host": (C.c_int, [C.c_uint32, C.c_uint32, u64p, u64p, C.c_uint32, u64p, u64p, u64p, C.c_uint32,
                                                   u64p, u32p]),
+    "pm_fr_sqrt_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), C.c_void_p]),
+    "pm_fr_sqrt_host": (C.c_int, [u64p, u64p, u32p]),
+    "pm_jubjub_compress": (C.c_int, [u64p, C.POINTER(C.c_uint8)]),
+    "pm_jubjub_decompress": (C.c_int, [C.POINTER(C.c_uint8), C.c_uint32, u64p, u32p]),
+    "pm_jubjub_compress_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "pm_jubjub_decompress_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t,
+                                           C.c_void_p, C.POINTER(C.c_size_t), C.c_void_p]),
+    "pm_dev_copy_strided": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p]),
     "pm_plonk_proof_to_bytes": (C.c_int, [C.POINTER(PlonkProof), C.POINTER(C.c_uint8)]),
     "pm_plonk_batch_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p)]),
     "pm_plonk_batch_free": (None, [C.c_void_p, C.c_void_p]),
@@ -347,6 +355,10 @@ SCHNORR_REASONS = {1: "u_range", 2: "r_point", 3: "pk_point", 4: "equation"}
 CIPHER_OK, CIPHER_POINT, CIPHER_RANGE, CIPHER_TAG = 0, 1, 2, 3
 CIPHER_REASONS = {1: "point", 2: "range", 3: "tag"}
 CIPHER_MAX_LEN = 4            # message words of a cipher: the rate of the width-5 permutation
+# pm_jubjub_decompress*: the flag, and the status of a point, the lowest that applies
+JUBJUB_CHECK_SUBGROUP = 1
+JUBJUB_OK, JUBJUB_BAD_RANGE, JUBJUB_BAD_NOT_ON_CURVE, JUBJUB_BAD_SIGN, JUBJUB_BAD_NOT_IN_SUBGROUP = 0, 1, 2, 3, 4
+JUBJUB_CODEC_REASONS = {1: "range", 2: "not_on_curve", 3: "sign", 4: "not_in_subgroup"}
 
 # pm_jubjub_msm_dev: the window widths the option "jubjub_msm_window_bits" may force
 JUBJUB_MSM_MIN_WINDOW_BITS, JUBJUB_MSM_MAX_WINDOW_BITS = 4, 16

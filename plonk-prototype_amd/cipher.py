@@ -27,7 +27,7 @@ import numpy as np
 
 from . import _lib
 from .host import DeviceVector, _p
-from .jubjub import JubJubBase, _points, _scalars, jubjub_mul
+from .jubjub import JubJubBase, _encodings, _points, _scalars, jubjub_decompress_dev, jubjub_mul
 from .poseidon import WIDTH, Hades, _elements
 
 CIPHER_REASONS = _lib.CIPHER_REASONS
@@ -181,8 +181,10 @@ class PoseidonCipher:
             for x in (ds, dk, dm, out):
                 x.free()
 
-    def _open(self, first, nonces, ciphers, call):
-        """the common half of decrypt and scan: ``first`` is [n, 2, 4], ``call(d_first, d_nonces, d_ciphers, n, d_msgs, d_status)``"""
+    def _open(self, first, nonces, ciphers, call, decode=None):
+        """the common half of decrypt and scan: ``first`` is [n, 2, 4], ``call(d_first, d_nonces, d_ciphers, n, d_msgs, d_status)``.
+        With ``decode`` (the subgroup flag) ``first`` is ``uint8 [n, 32]`` instead: uploaded as it is and decoded on the device
+        into the buffer ``call`` reads, so the points never visit the host."""
         L = self.msg_len
         k, c = _nonces(nonces), _words(ciphers, L + 1, False, "ciphers")
         n = first.shape[0]
@@ -190,13 +192,19 @@ class PoseidonCipher:
             raise ValueError("one nonce and one cipher per point")
         if n == 0:
             return np.zeros((0, L, 4), np.uint64), np.zeros(0, np.uint32)
-        dp, dk, dc = (DeviceVector.from_host(self.ctx, x.reshape(-1, 4)) for x in (first, k, c))
-        dm, ds = DeviceVector(self.ctx, L * n), DeviceVector(self.ctx, (n + 7) // 8)     # n uint32 in 32-byte elements
+        bufs = [DeviceVector.from_host(self.ctx, x.reshape(-1, 4)) for x in (first if decode is None else first.view(np.uint64), k, c)]
         try:
+            dp, dk, dc = bufs
+            if decode is not None:
+                bufs.append(DeviceVector(self.ctx, 2 * n))
+                jubjub_decompress_dev(self.ctx, dp.ptr, n, bufs[-1].ptr, 0, decode, want_n_ok=False)
+                dp = bufs[-1]
+            dm, ds = DeviceVector(self.ctx, L * n), DeviceVector(self.ctx, (n + 7) // 8)     # n uint32 in 32-byte elements
+            bufs += [dm, ds]
             call(dp.ptr, dk.ptr, dc.ptr, n, dm.ptr, ds.ptr)
             return dm.to_host().reshape(n, L, 4), ds.to_host().view(np.uint32).reshape(-1)[:n].copy()
         finally:
-            for x in (dp, dk, dc, dm, ds):
+            for x in bufs:
                 x.free()
 
     def decrypt(self, secrets, nonces, ciphers):
@@ -213,6 +221,18 @@ class PoseidonCipher:
         form = form if scalar_form is None else scalar_form
         return self._open(_points(ephemeral_keys), nonces, ciphers,
                           lambda *a: self.scan_dev(vk, *a, want_n_ok=False, scalar_form=form))
+
+    def scan_bytes(self, view_key, ephemeral_bytes, nonces, ciphers, check_subgroup: bool = False, scalar_form: int | None = None):
+        """:meth:`scan` for ephemeral keys as a ledger stores them, ``uint8 [n, 32]`` (:func:`~.jubjub.jubjub_compress`): the
+        bytes are uploaded, decoded on the device (:func:`~.jubjub.jubjub_decompress_dev`) and handed to :meth:`scan_dev` without
+        a round trip of the points.  The result is that of :meth:`scan` on the decoded points: a key that does not decode comes
+        back with status 1 (``point``) and zero messages.  Nonces and cipher words stay limbs or integers."""
+        vk, form = _scalars(view_key)
+        if vk.shape[0] != 1:
+            raise ValueError("one viewing key")
+        form = form if scalar_form is None else scalar_form
+        return self._open(_encodings(ephemeral_bytes), nonces, ciphers,
+                          lambda *a: self.scan_dev(vk, *a, want_n_ok=False, scalar_form=form), decode=bool(check_subgroup))
 
     def encrypt_to(self, g: JubJubBase, public_keys, ephemeral_secrets, nonces, messages):
         """The sender's side, composed from ``g.mul``, :func:`~.jubjub.jubjub_mul` and :meth:`encrypt`: note i is encrypted to

@@ -166,7 +166,7 @@ static void release_caches(pm_ctx* ctx, bool all) {
     ctx->domain[d].clear();
   }
   for (DeviceBuffer* b : {&ctx->ntt_tmp[0], &ctx->ntt_tmp[1], &ctx->io_in, &ctx->io_out, &ctx->msm_ws, &ctx->msm_scalars,
-                          &ctx->poly_ws, &ctx->poly_tab, &ctx->jj_msm_ws}) {
+                          &ctx->poly_ws, &ctx->poly_tab, &ctx->jj_msm_ws, &ctx->fr_sqrt_tab}) {
     if (b->ptr) (void)hipFree(b->ptr);
     b->ptr = nullptr;
     b->bytes = 0;

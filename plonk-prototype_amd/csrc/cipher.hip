@@ -53,15 +53,6 @@ void host_init(HFr (&s)[5], const HPoint& secret, const uint64_t* nonce, uint32_
 bool host_consts_fault(uint32_t R, uint32_t F, const uint64_t* ark, const uint64_t* mds, uint32_t n_mds, uint32_t len) {
   return len < 1 || len > CPH_MAX_LEN || !params_fault(R, F, ark, mds, n_mds).empty();
 }
-// vk < r as 64 signed base-16 digits, the top one first: the recoding of jj_digit, once
-void recode_digits(const uint64_t (&vk)[4], signed char (&out)[JJ_WINDOWS]) {
-  uint32_t c = 0;
-  for (u32 w = 0; w < JJ_WINDOWS; ++w) {
-    const uint32_t v = (uint32_t)((vk[w / 16] >> (4 * (w % 16))) & 15u) + c;
-    c = v > 8u ? 1u : 0u;
-    out[JJ_WINDOWS - 1 - w] = (signed char)((int)v - (c ? 16 : 0));
-  }
-}
 
 // ------------------------------------------------------------------ device side
 struct CipherIo {
@@ -82,8 +73,7 @@ struct CipherScanIo {
   u32x4* scratch;           // [entry][chunk][thread of the grid], then a secret (x | y) a thread
   size_t n;
   u32 edwards_d[9];         // device form
-  u32 digits[JJ_WINDOWS / 4];       // of the viewing key, the top one first, four signed bytes a word from the low end: whole
-                                    // words, so that digit w arrives by a scalar load (a byte would take a vector one)
+  u32 digits[JJ_WINDOWS / 4];       // of the viewing key: recode_digit_words (jubjub.hip.h)
 };
 
 // s = init with the keys of round 0 added.  x, y, nonce in the device form, normalised, below 2 r: with the round key a word
@@ -190,21 +180,8 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   const Fr ed = fr_limbs(a.edwards_d);
   // ---- the table of R
   jj_table_build(tbl, T, g_to_dev(ld_canon(a.points, 2 * i)), g_to_dev(ld_canon(a.points, 2 * i + 1)), ed);
-  // ---- the ladder from the top digit down; d is the same in every lane of the grid
-  EdPoint acc = jj_neutral();
-#pragma unroll 1
-  for (u32 w = 0; w < JJ_WINDOWS; ++w) {
-#pragma unroll 1
-    for (u32 j = 0; j < 3; ++j) acc = ed_double<false>(acc);
-    acc = ed_double<true>(acc);                              // the addition reads T
-    const int d = (int)(signed char)(a.digits[w >> 2] >> (8 * (w & 3u)));
-    if (d != 0) {                                            // uniform: a zero digit adds nothing
-      const u32 mag = (u32)(d < 0 ? -d : d), e = mag > 8u ? 8u : mag;
-      EdPoint q = jj_table_load(tbl, T, e);
-      if (d < 0) q.X = gneg(q.X), q.T = gneg(q.T);           // uniform
-      acc = ed_add(acc, q, ed);
-    }
-  }
+  // ---- the ladder from the top digit down; a digit is the same in every lane of the grid
+  const EdPoint acc = jj_ladder_uniform(tbl, T, a.digits, ed);
   // ---- S = (X / Z, Y / Z) into the slot of this thread, live or not: the slots are per thread of the grid
   const Fr zi = g_to_abi(fe_inv_dev<FrP>(acc.Z));           // every lane of the wave is here
   u32x4* const out = a.scratch + (size_t)8 * JJ_POINT_CHUNKS * T + 4 * tid;
@@ -304,9 +281,7 @@ extern "C" int pm_poseidon_cipher_scan_dev(pm_ctx* ctx, const pm_hades_params* p
   CipherScanIo l{};
   l.scratch = scratch.slots();
   jubjub_d_limbs(l.edwards_d);
-  signed char digits[JJ_WINDOWS];
-  recode_digits(vk, digits);
-  for (u32 w = 0; w < JJ_WINDOWS; ++w) l.digits[w >> 2] |= (u32)(unsigned char)digits[w] << (8 * (w & 3u));
+  recode_digit_words(vk, l.digits);
   CipherIo a{};
   a.secrets = l.scratch + (size_t)8 * JJ_POINT_CHUNKS * stride, a.n_ok = n_ok ? d_ok : nullptr;
   io_consts(a, msg_len);

@@ -85,6 +85,7 @@ struct pm_ctx {
   pm::DeviceBuffer msm_scalars;
   pm::DeviceBuffer jj_msm_ws;                           // workspace of pm_jubjub_msm_dev (jubjub_msm_plan.h), under ord_jj_msm
   pm::StreamOrder ord_jj_msm;
+  pm::DeviceBuffer fr_sqrt_tab;                         // tables of the Fr square root (fr_sqrt.hip.h): built at the first call that needs them
   pm::DeviceBuffer poly_ws;                             // scratch of the polynomial helpers
   pm::DeviceBuffer poly_tab;                            // power tables of pm_fr_poly_ruffini_dev
   void* msm_host_pinned = nullptr;

@@ -283,6 +283,44 @@ PM_DEV EdPoint jj_ladder(const u32x4* tbl, size_t T, u64 (&k)[4], u64 carries, u
   }
   return acc;
 }
+// ONE scalar for every thread of the grid (a viewing key in cipher.hip, the order l in jubjub_codec.hip): its 64 signed digits
+// are recoded once on the host -- the recoding of jj_digit, the top digit first -- and travel by value in the kernel's
+// arguments, four signed bytes a word from the low end: whole words, so that digit w arrives by a scalar load (a byte would
+// take a vector one).
+inline void recode_digits(const uint64_t (&k)[4], signed char (&out)[JJ_WINDOWS]) {
+  uint32_t c = 0;
+  for (u32 w = 0; w < JJ_WINDOWS; ++w) {
+    const uint32_t v = (uint32_t)((k[w / 16] >> (4 * (w % 16))) & 15u) + c;
+    c = v > 8u ? 1u : 0u;
+    out[JJ_WINDOWS - 1 - w] = (signed char)((int)v - (c ? 16 : 0));
+  }
+}
+inline void recode_digit_words(const uint64_t (&k)[4], u32 (&words)[JJ_WINDOWS / 4]) {
+  signed char digits[JJ_WINDOWS];
+  recode_digits(k, digits);
+  for (u32 w = 0; w < JJ_WINDOWS / 4; ++w) words[w] = 0;
+  for (u32 w = 0; w < JJ_WINDOWS; ++w) words[w >> 2] |= (u32)(unsigned char)digits[w] << (8 * (w & 3u));
+}
+// k P over the table of jj_table_build under those digits, from the top one down.  Digit w is read at a wave-uniform index, so
+// it lives in a scalar register: its sign and the zero digit are uniform branches, and there is no per-lane recoding, no shift
+// of a per-lane scalar and no word of carries.  The doublings by the dedicated formula, T from the last of four only.
+PM_DEV EdPoint jj_ladder_uniform(const u32x4* tbl, size_t T, const u32 (&digits)[JJ_WINDOWS / 4], const Fr& ed) {
+  EdPoint acc = jj_neutral();
+#pragma unroll 1
+  for (u32 w = 0; w < JJ_WINDOWS; ++w) {
+#pragma unroll 1
+    for (u32 j = 0; j < 3; ++j) acc = ed_double<false>(acc);
+    acc = ed_double<true>(acc);                              // the addition reads T
+    const int d = (int)(signed char)(digits[w >> 2] >> (8 * (w & 3u)));
+    if (d != 0) {                                            // uniform: a zero digit adds nothing
+      const u32 mag = (u32)(d < 0 ? -d : d), e = mag > 8u ? 8u : mag;
+      EdPoint q = jj_table_load(tbl, T, e);
+      if (d < 0) q.X = gneg(q.X), q.T = gneg(q.T);           // uniform
+      acc = ed_add(acc, q, ed);
+    }
+  }
+  return acc;
+}
 // the words of r, most significant first
 constexpr u32 JJ_R_WORDS[8] = {0x73eda753u, 0x299d7d48u, 0x3339d808u, 0x09a1d805u, 0x53bda402u, 0xfffe5bfeu, 0xffffffffu, 0x00000001u};
 PM_DEV bool jj_below_r(const u32x4& lo, const u32x4& hi) {

@@ -875,6 +875,19 @@ extern "C" int pm_dev_download(pm_ctx* ctx, void* dst, const void* d_src, size_t
   return PM_OK;
 }
 
+extern "C" int pm_dev_copy_strided(pm_ctx* ctx, void* d_dst, size_t dst_stride_bytes, const void* d_src, size_t src_stride_bytes,
+                                   size_t width_bytes, size_t rows, void* hip_stream) {
+  if (!ctx) return PM_ERR_BAD_ARG;
+  if (rows == 0 || width_bytes == 0) return PM_OK;
+  if (!d_dst || !d_src || dst_stride_bytes < width_bytes || src_stride_bytes < width_bytes)
+    return set_err(ctx, PM_ERR_BAD_ARG, "null pointer or a stride below the width");
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  PM_HIP(ctx, hipMemcpy2DAsync(d_dst, dst_stride_bytes, d_src, src_stride_bytes, width_bytes, rows, hipMemcpyDeviceToDevice,
+                               hip_stream ? (hipStream_t)hip_stream : ctx->stream));
+  return PM_OK;
+}
+
 extern "C" int pm_fr_vec_op_dev(pm_ctx* ctx, int op, const void* d_a, const void* d_b, size_t b_len, void* d_out,
                                 size_t n, void* hip_stream) {
   if (!ctx) return PM_ERR_BAD_ARG;

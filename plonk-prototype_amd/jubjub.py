@@ -8,6 +8,11 @@ Scalars are Montgomery limb arrays (``uint64``, last axis 4: ``PM_SCALAR_MONTGOM
 the subgroup.  With ``JubJubBase.from_key`` the base is the very point a key's FIXED_BASE gadget multiplies.  None of this is
 hardened against side channels.
 
+The wire format (section 7.2p): a point as 32 bytes, the canonical ``y`` little-endian with the least significant bit of the
+canonical ``x`` in bit 255.  ``jubjub_decompress`` decodes a batch on the GPU with a status per point, ``jubjub_compress``
+encodes, ``fr_sqrt`` is the square root in Fr underneath.  The shape of ``JubJubAffine::to_bytes`` / ``from_bytes`` as
+remembered: prior knowledge that nothing in this repository pins; ``x = 0`` with the sign bit set is refused.
+
 ``JUBJUB_GENERATOR`` is the point with ``y = 0x12``; this repository checks that it lies on the curve and that the subgroup
 order ``JUBJUB_ORDER`` takes it to the identity.  That it is dusk-jubjub's ``GENERATOR`` is prior knowledge, not something this
 repository can verify.  No second generator is shipped: callers pass their own H."""
@@ -238,6 +243,152 @@ def jubjub_msm_host(points, scalars) -> np.ndarray:
     if _lib.load().pm_jubjub_msm_host(_p(p), _p(s), p.shape[0], form, _p(out)) != _lib.PM_OK:
         raise ValueError("pm_jubjub_msm_host refused its arguments")
     return out
+
+
+# ------------------------------------------------------------------------------------------ the wire format (section 7.2p)
+#: why ``jubjub_decompress`` refused a point: the keys are the non-zero statuses, the lowest that applies
+JUBJUB_CODEC_REASONS = _lib.JUBJUB_CODEC_REASONS
+
+
+def _encodings(data, width: int = 32) -> np.ndarray:
+    """``bytes``, a sequence of ``bytes`` or a ``uint8`` array -> ``[n, width]`` ``uint8``"""
+    if isinstance(data, (bytes, bytearray)):
+        a = np.frombuffer(bytes(data), dtype=np.uint8)
+    elif isinstance(data, np.ndarray):
+        if data.dtype != np.uint8:
+            raise ValueError("encodings are uint8")
+        a = data
+    else:
+        a = np.frombuffer(b"".join(bytes(d) for d in data), dtype=np.uint8)
+    if a.size % width:
+        raise ValueError(f"encodings are {width} bytes each")
+    return np.ascontiguousarray(a).reshape(-1, width)
+
+
+def _field_elements(x) -> np.ndarray:
+    """limbs (uint64, [..., 4]) or integers -> [n, 4] Montgomery limbs"""
+    if isinstance(x, np.ndarray) and x.dtype == np.uint64:
+        return np.ascontiguousarray(x).reshape(-1, 4)
+    return fr_vec_to_limbs([int(v) for v in np.asarray(x, dtype=object).reshape(-1)]).reshape(-1, 4)
+
+
+def _words32(v: DeviceVector, n: int) -> np.ndarray:
+    """the first n ``uint32`` of a vector of 32-byte elements"""
+    return v.to_host().view(np.uint32).reshape(-1)[:n].copy()
+
+
+def fr_sqrt_host(value):
+    """``pm_fr_sqrt_host``: one element on the CPU by the plain Tonelli-Shanks loop, no context -> ``(root [4], is_square)``"""
+    a = _field_elements(value)
+    if a.shape[0] != 1:
+        raise ValueError("one element")
+    out, flag = np.zeros(4, np.uint64), C.c_uint32()
+    if _lib.load().pm_fr_sqrt_host(_p(a), _p(out), C.byref(flag)) != _lib.PM_OK:
+        raise ValueError("pm_fr_sqrt_host refused its arguments")
+    return out, int(flag.value)
+
+
+def jubjub_compress_host(point) -> bytes:
+    """``pm_jubjub_compress``: one point on the CPU, no context -> 32 bytes.  A point off the curve or a coordinate that is not
+    below r raises ``ValueError``."""
+    p = _points(point)
+    if p.shape[0] != 1:
+        raise ValueError("one point")
+    out = np.zeros(32, np.uint8)
+    if _lib.load().pm_jubjub_compress(_p(p), out.ctypes.data_as(C.POINTER(C.c_uint8))) != _lib.PM_OK:
+        raise ValueError("pm_jubjub_compress refused its arguments")
+    return out.tobytes()
+
+
+def jubjub_decompress_host(data, check_subgroup: bool = False):
+    """``pm_jubjub_decompress``: 32 bytes on the CPU, no context -> ``(point [2, 4], status)``; a refused point is ``(0, 0)``"""
+    b = _encodings(data)
+    if b.shape[0] != 1:
+        raise ValueError("one encoding")
+    out, status = np.zeros((2, 4), np.uint64), C.c_uint32()
+    rc = _lib.load().pm_jubjub_decompress(b.ctypes.data_as(C.POINTER(C.c_uint8)), _lib.JUBJUB_CHECK_SUBGROUP if check_subgroup else 0,
+                                          _p(out), C.byref(status))
+    if rc != _lib.PM_OK:
+        raise ValueError("pm_jubjub_decompress refused its arguments")
+    return out, int(status.value)
+
+
+def fr_sqrt_dev(ctx: Context, d_in: int, n: int, d_out: int, d_is_square: int = 0, want_count: bool = False, stream: int = 0):
+    """``pm_fr_sqrt_dev``: n roots at ``d_out`` (may be ``d_in``) and n ``uint32`` flags at ``d_is_square`` (0 = not wanted).
+    Returns the count of squares and waits for the stream, or None, asynchronous, when ``want_count`` is false."""
+    cnt = C.c_size_t()
+    ctx._check(ctx._lib.pm_fr_sqrt_dev(ctx._h, C.c_void_p(d_in), n, C.c_void_p(d_out), C.c_void_p(d_is_square) if d_is_square else None,
+                                       C.byref(cnt) if want_count else None, C.c_void_p(stream)))
+    return int(cnt.value) if want_count else None
+
+
+def fr_sqrt(ctx: Context, values):
+    """-> ``(roots [n, 4], is_square [n] uint32)``: the root whose canonical integer is even (0 for 0) and flag 1 for a square,
+    root 0 and flag 0 for a non-square or limbs that are not below r.  ``values``: Montgomery limbs or integers."""
+    a = _field_elements(values)
+    n = a.shape[0]
+    if n == 0:
+        return np.zeros((0, 4), np.uint64), np.zeros(0, np.uint32)
+    d, f = DeviceVector.from_host(ctx, a), DeviceVector(ctx, (n + 7) // 8)
+    try:
+        fr_sqrt_dev(ctx, d.ptr, n, d.ptr, f.ptr)
+        return d.to_host(), _words32(f, n)
+    finally:
+        d.free(), f.free()
+
+
+def jubjub_compress_dev(ctx: Context, d_points: int, n: int, d_bytes: int, stream: int = 0):
+    """``pm_jubjub_compress_dev``: n points (2 elements each) -> n x 32 bytes at ``d_bytes``; asynchronous.  Not validated."""
+    ctx._check(ctx._lib.pm_jubjub_compress_dev(ctx._h, C.c_void_p(d_points), n, C.c_void_p(d_bytes), C.c_void_p(stream)))
+
+
+def jubjub_compress(ctx: Context, points) -> np.ndarray:
+    """-> ``uint8 [n, 32]``: the canonical y, little-endian, with the parity of the canonical x in bit 255.  The points are not
+    validated."""
+    p = _points(points)
+    n = p.shape[0]
+    if n == 0:
+        return np.zeros((0, 32), np.uint8)
+    dp, out = DeviceVector.from_host(ctx, p), DeviceVector(ctx, n)
+    try:
+        jubjub_compress_dev(ctx, dp.ptr, n, out.ptr)
+        return out.to_host().view(np.uint8).reshape(n, 32)
+    finally:
+        dp.free(), out.free()
+
+
+def jubjub_decompress_dev(ctx: Context, d_bytes: int, n: int, d_out: int, d_status: int = 0, check_subgroup: bool = False,
+                          in_stride: int = 0, out_stride: int = 0, want_n_ok: bool = True, stream: int = 0):
+    """``pm_jubjub_decompress_dev``: record i (32 bytes) at ``d_bytes + i * in_stride`` -> point i at ``d_out + i * out_stride``
+    (0 = packed: 32 and 64 bytes), n ``uint32`` at ``d_status`` (0 = not wanted).  A refused point is ``(0, 0)`` and no error.
+    Returns the count of status 0 and waits for the stream, or None when ``want_n_ok`` is false.  The subgroup check is off by
+    default: it costs a whole ladder a point."""
+    ok = C.c_size_t()
+    ctx._check(ctx._lib.pm_jubjub_decompress_dev(ctx._h, C.c_void_p(d_bytes), in_stride, n,
+                                                 _lib.JUBJUB_CHECK_SUBGROUP if check_subgroup else 0, C.c_void_p(d_out), out_stride,
+                                                 C.c_void_p(d_status) if d_status else None, C.byref(ok) if want_n_ok else None,
+                                                 C.c_void_p(stream)))
+    return int(ok.value) if want_n_ok else None
+
+
+def jubjub_decompress(ctx: Context, data, check_subgroup: bool = False, strict: bool = False):
+    """``data``: n x 32 bytes -> ``(points [n, 2, 4], status [n] uint32)``: status 0 = decoded, else a key of
+    ``JUBJUB_CODEC_REASONS``, the lowest that applies; a refused point is ``(0, 0)``, which every later call refuses.  With
+    ``strict`` a refusal raises ``ValueError`` naming the lowest bad index and its reason."""
+    b = _encodings(data)
+    n = b.shape[0]
+    if n == 0:
+        return np.zeros((0, 2, 4), np.uint64), np.zeros(0, np.uint32)
+    db, out, ds = DeviceVector.from_host(ctx, b.view(np.uint64)), DeviceVector(ctx, 2 * n), DeviceVector(ctx, (n + 7) // 8)
+    try:
+        ok = jubjub_decompress_dev(ctx, db.ptr, n, out.ptr, ds.ptr, check_subgroup)
+        status = _words32(ds, n)
+        if strict and ok != n:
+            bad = int(np.flatnonzero(status)[0])
+            raise ValueError(f"encoding {bad} is refused: {JUBJUB_CODEC_REASONS[int(status[bad])]}")
+        return out.to_host().reshape(n, 2, 4), status
+    finally:
+        db.free(), out.free(), ds.free()
 
 
 def jubjub_check(ctx: Context, points):

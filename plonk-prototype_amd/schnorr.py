@@ -26,9 +26,9 @@ import secrets
 import numpy as np
 
 from . import _lib
-from .field import fr_vec_to_limbs
+from .field import fr_vec_from_limbs, fr_vec_to_limbs
 from .host import DeviceVector, _p
-from .jubjub import JUBJUB_ORDER, JubJubBase, _points, _scalars
+from .jubjub import JUBJUB_ORDER, JubJubBase, _encodings, _points, _scalars, jubjub_compress, jubjub_decompress_dev
 from .poseidon import Hades, _capacity, _elements
 
 SCHNORR_REASONS = _lib.SCHNORR_REASONS
@@ -182,6 +182,51 @@ class Schnorr:
             for x in (dp, dm, ds, dr):
                 if x is not None:
                     x.free()
+
+    def signatures_to_bytes(self, signatures, scalar_form: int | None = None) -> np.ndarray:
+        """Signatures as a ledger stores them -> ``uint8 [n, 64]``: the canonical ``u``, little-endian, then the 32-byte encoding
+        of ``R`` (:func:`~.jubjub.jubjub_compress`).  A limb array carries a Montgomery ``u`` unless ``scalar_form`` says
+        otherwise; integer triples a canonical one.  Nothing is validated."""
+        limbs = isinstance(signatures, np.ndarray) and signatures.dtype == np.uint64
+        form = scalar_form if scalar_form is not None else (_lib.SCALAR_MONTGOMERY if limbs else _lib.SCALAR_CANONICAL)
+        sig = _signatures(signatures, form)
+        n = sig.shape[0]
+        out = np.zeros((n, 64), np.uint8)
+        if n == 0:
+            return out
+        u = sig[:, 0, :]
+        if form == _lib.SCALAR_MONTGOMERY:
+            u = _scalars(fr_vec_from_limbs(np.ascontiguousarray(u)))[0]
+        out[:, :32] = np.ascontiguousarray(u).view(np.uint8).reshape(n, 32)
+        out[:, 32:] = jubjub_compress(self.ctx, np.ascontiguousarray(sig[:, 1:, :]))
+        return out
+
+    def verify_bytes(self, public_key_bytes, messages, signature_bytes) -> np.ndarray:
+        """:meth:`verify` for keys and signatures as a ledger stores them: ``public_key_bytes`` ``uint8 [n, 32]``,
+        ``signature_bytes`` ``uint8 [n, 64]`` (:meth:`signatures_to_bytes`) -> [n] ``uint32`` reasons.  Both are uploaded as they
+        are; the ``R`` halves are decoded on the device straight into the ``(u, R.x, R.y)`` records (strides of 64 and 96 bytes),
+        the ``u`` halves are copied beside them and go in canonical.  A key or an ``R`` that does not decode is ``(0, 0)`` and gets
+        the reason :meth:`verify` gives it (``pk_point``, ``r_point``); a ``u`` that is not below ``l`` is ``verify``'s business."""
+        pkb, sgb, msg = _encodings(public_key_bytes), _encodings(signature_bytes, 64), _elements(messages)
+        n = sgb.shape[0]
+        if pkb.shape[0] != n or msg.shape[0] != n:
+            raise ValueError("one public key and one message per signature")
+        if n == 0:
+            return np.zeros(0, np.uint32)
+        c = self.ctx
+        bufs = [DeviceVector.from_host(c, x) for x in (pkb.view(np.uint64), sgb.view(np.uint64), msg)]
+        try:
+            dpb, dsb, dm = bufs
+            dp, ds, dr = DeviceVector(c, 2 * n), DeviceVector(c, 3 * n), DeviceVector(c, (n + 7) // 8)
+            bufs += [dp, ds, dr]
+            jubjub_decompress_dev(c, dpb.ptr, n, dp.ptr, want_n_ok=False)
+            jubjub_decompress_dev(c, dsb.ptr + 32, n, ds.ptr + 32, in_stride=64, out_stride=96, want_n_ok=False)
+            c._check(c._lib.pm_dev_copy_strided(c._h, C.c_void_p(ds.ptr), 96, C.c_void_p(dsb.ptr), 64, 32, n, None))
+            self.verify_dev(dp.ptr, dm.ptr, ds.ptr, n, dr.ptr, False, _lib.SCALAR_CANONICAL)
+            return dr.to_host().view(np.uint32).reshape(-1)[:n].copy()
+        finally:
+            for x in bufs:
+                x.free()
 
     def verify(self, public_keys, messages, signatures, scalar_form: int | None = None) -> np.ndarray:
         """-> [n] ``uint32`` reasons: 0 = valid, else a key of ``SCHNORR_REASONS``.  A limb array of signatures carries a Montgomery
