@@ -1271,7 +1271,9 @@ int pm_test_field_op(pm_ctx* ctx, int op, const uint64_t* a, const uint64_t* b, 
  * fp_is_zero_product, 17 fp_is_zero_lazy (1 -> 1, 0 / 1 in limb 0) (Fp), 18 dft8 (x[0..7], w1, w2, w3: 11 -> 8), 19 dft4
  * (a0..a3, w4: 5 -> 4) (Fr), 20 fe_canon_limbs, 21 fe_inv_int, 22 fe_inv_dev (csrc/field_inv.hip.h; 1 -> 1; cases 64 k ..
  * 64 k + 63 share a wave, whose vote ends the rounds of fe_inv_int), 32 + K fe_sub<K,1> (2 -> 1) for the K the library
- * instantiates (Fr 2, 3, 5, 9; Fp 2, 3, 5, 6, 8, 11).  PM_ERR_BAD_ARG for any other (field, op).  Host pointers, n cases. */
+ * instantiates (Fr 2, 3, 5, 9, 18, 34, 39; Fp 2, 3, 5, 6, 8, 11), 24 fe_reduce_canon_pack (1 -> 1, a wave per 64 cases), the
+ * lazy split products (D = G: limbs normalised, value up to 16.01 r / 37.01 r / 11.01 r) 25 fe_mul_split<3,3> (x, 3 rows:
+ * 4 -> 1), 26 fe_mul_split<1,1> (x, 9 rows: 10 -> 1), 27 fe_mul_split<5,5> (x, 2 rows: 3 -> 1) (Fr).  PM_ERR_BAD_ARG for any other (field, op).  Host pointers, n cases. */
 int pm_test_field_raw_op(pm_ctx* ctx, int field, int op, const uint32_t* in, uint32_t* out, size_t n);
 /* The XYZZ group law of csrc/ec.hip.h on raw limbs.  A point is 57 words: X, Y, ZZ, ZZZ (14 Fp limbs each), infinity flag.
  * op 0 = xyzz_double_affine (X, Y of a), 1 = xyzz_double, 2 = xyzz_madd (X, Y of b: the affine operand), 3 = xyzz_add, 4 =
@@ -1339,6 +1341,12 @@ int pm_test_ntt_plan(uint32_t log_n, uint32_t batch, long tile_log, long max_rad
  * w in the device Montgomery form), then 20 words per step-twiddle entry.  *words = its size in 32-bit words (may be
  * NULL); up to max_words of them are copied to out. */
 int pm_test_ntt_step4_table(pm_ctx* ctx, uint32_t inverse, uint32_t S, uint32_t* out, size_t max_words, size_t* words);
+/* The lazy split table of radix 2^S in form G (G = 1, 2, 3 or 5 data limbs a row; the kernels use 3 and 5) beside it, built on
+ * first use: the head, 84 words (word 9 b + j = limb b of w4 2^(29 (j - 8)) mod r), then per entry of the radix-4 steps
+ * s >= 2 the rows w 2^(29 (j G + G - 9)) mod r, nine words each, zero words up to a multiple of four (28 words for G = 3).
+ * The table of pm_test_ntt_step4_table is not changed by it.  words, max_words and out as there. */
+int pm_test_ntt_step4_lazy_table(pm_ctx* ctx, uint32_t inverse, uint32_t S, uint32_t G, uint32_t* out, size_t max_words,
+                                 size_t* words);
 /* Pure host, no context: thread tid of a radix-4 first or single pass of even radix 2^S (4 <= S <= 10) with 2^LT columns
  * per tile, at its step `step`, in the plane-major exchange of csrc/ntt_kernels4.hip.h (ufast: the pass writes its output
  * u-fast, as a first pass does, which changes the thread order of the last step) -- out[12] = {0 the Stockham butterfly it owns, 1 its column, 2-5 the tile

@@ -291,6 +291,8 @@ SIGNATURES = {
     "pm_test_ntt_plan": (C.c_int, [C.c_uint32, C.c_uint32, C.c_long, C.c_long, C.c_long, C.c_uint32, C.POINTER(C.c_uint32)]),
     "pm_test_ntt_exchange_map": (C.c_int, [C.c_uint32] * 5 + [C.POINTER(C.c_uint32)]),
     "pm_test_ntt_step4_table": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, u32p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "pm_test_ntt_step4_lazy_table": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, u32p, C.c_size_t,
+                                               C.POINTER(C.c_size_t)]),
     "pm_test_wire_sort_plan": (C.c_int, [C.c_size_t, C.c_size_t, u32p, u32p, C.POINTER(C.c_size_t)]),
     "pm_test_host_naf": (C.c_int, [u64p, C.c_uint32, C.POINTER(C.c_int8), C.POINTER(C.c_int)]),
     "pm_test_msm_sizing": (C.c_int, [C.c_size_t, C.c_uint32, C.c_long, C.c_uint32, C.c_uint32, u64p]),

@@ -154,6 +154,7 @@ static void release_caches(pm_ctx* ctx, bool all) {
   for (int d = 0; d < 2; ++d) {
     for (auto& kv : ctx->step_tw[d]) (void)hipFree(kv.second);
     for (auto& kv : ctx->step4_tw[d]) (void)hipFree(kv.second);
+    for (auto& kv : ctx->step4_lazy_tw[d]) (void)hipFree(kv.second);
     for (auto& kv : ctx->domain[d]) {
       (void)hipFree(kv.second.tw_hi);
       (void)hipFree(kv.second.tw_lo);
@@ -163,6 +164,7 @@ static void release_caches(pm_ctx* ctx, bool all) {
     }
     ctx->step_tw[d].clear();
     ctx->step4_tw[d].clear();
+    ctx->step4_lazy_tw[d].clear();
     ctx->domain[d].clear();
   }
   for (DeviceBuffer* b : {&ctx->ntt_tmp[0], &ctx->ntt_tmp[1], &ctx->io_in, &ctx->io_out, &ctx->msm_ws, &ctx->msm_scalars,

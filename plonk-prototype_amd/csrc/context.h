@@ -66,6 +66,7 @@ struct pm_ctx {
   // NTT caches
   std::map<unsigned, void*> step_tw[2];                 // [dir][S] -> device table
   std::map<unsigned, void*> step4_tw[2];                // same for the radix-4 kernels
+  std::map<unsigned, void*> step4_lazy_tw[2];           // [dir][S << 8 | G] -> their lazy table in form G
   std::map<unsigned, pm::NttDomainTables> domain[2];    // [dir][log_n]
   pm::DeviceBuffer ntt_tmp[2];
   pm::DeviceBuffer io_in, io_out;                       // staging for host-pointer calls

@@ -329,13 +329,21 @@ PM_DEV Fe<P> fe_mul(const Fe<P>& a, const Fe<P>& b) {
 // (9 * 6 + 6 = 60 < 63), the bound of fe_mul.  Result: limbs < 2^W, top limb the rest; value < T / 2^(W D) + m
 // < (1 + 2 N Bx 2^-W) m < (1 + 2^-22) m: the class (limbs normalised, value < 2m) of fe_mul.  Needs m = 1 mod 2^W (Fr): the
 // digit is q = -acc and adding 2^W - 1 stands in for q * m_0, exactly as in fe_mont_cols.  One PM_KEEP chain.
+//
+// Lazy form, D = G: one digit fewer, N^2 + (N-1) G limb products (Fr: G = 5 121, G = 3 105, G = 2 97, G = 1 89).  The same
+// residue, T + q m is still a multiple of 2^(W D); only the size changes: (T + q m) / 2^(W G) < ceil(N/G) Bx (1 + 2^(1-W)) m + m,
+// for Fr below 7.01 m (G = 5, Bx = 3), 16.01 m (G = 3, Bx = 5), 26.01 m (G = 2, Bx = 5), 37.01 m (G = 1, Bx = 4).  The limbs
+// come out below 2^W all the same, the top limb included while the value is below 2^(W N): Fr's top limb has six spare
+// bits (top(r) < 2^23), so up to 64 r fits a normalised element.  Column bound N Bx + D < 63 as above.  The caller
+// carries the larger value in its fe_sub<K, 1> constants (ntt_kernels4.hip.h, dft4s_lazy).
 template <class P, int G, int D, class WL>
 PM_DEV Fe<P> fe_mul_split(const Fe<P>& x, WL&& wl) {
   constexpr int N = P::N, W = P::W;
   constexpr u32 MASK = Consts<P>::MASK;
   constexpr Limbs<N> M = Consts<P>::mod_limbs();
   static_assert(M.v[0] == 1u, "fe_mul_split: the modulus must be 1 mod 2^W");
-  static_assert(G >= 1 && G <= N && D == G + 1 && D <= N, "fe_mul_split: one digit more than the longest group");
+  static_assert(G >= 1 && G <= N && (D == G + 1 || D == G) && D <= N,
+                "fe_mul_split: one digit more than the longest group, or as many (lazy: the value stays above 2 m)");
   Fe<P> r;
   u32 q[D];
   u64 acc = 0;

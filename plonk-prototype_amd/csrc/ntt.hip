@@ -57,6 +57,9 @@ int ntt_stamps_arm(pm_ctx* ctx, hipStream_t st, int pass, size_t waves);
 #endif
 int build_step4_table(pm_ctx* ctx, void** out, const NttConsts& c, unsigned S, hipStream_t st);
 size_t step4_table_bytes(unsigned S);
+int pass4_lazy_form(int S, int LT, int role);
+int build_step4_lazy_table(pm_ctx* ctx, void** out, const NttConsts& c, unsigned S, unsigned G, hipStream_t st);
+size_t step4_lazy_table_bytes(unsigned S, unsigned G);
 
 struct Plan {
   int npass = 0;
@@ -182,6 +185,31 @@ static int get_step4_table(pm_ctx* ctx, int dir, unsigned S, void** out, hipStre
   int rc = build_step4_table(ctx, &d, c, S, st);
   if (rc) return rc;
   ctx->step4_tw[dir][S] = d;
+  *out = d;
+  return PM_OK;
+}
+
+// the lazy split table of radix 2^S in form G (ntt_kernels4.hip.h), built once per (S, direction, form) like the table above
+static int get_step4_lazy_table(pm_ctx* ctx, int dir, unsigned S, unsigned G, void** out, hipStream_t st) {
+  const unsigned key = S << 8 | G;
+  auto it = ctx->step4_lazy_tw[dir].find(key);
+  if (it != ctx->step4_lazy_tw[dir].end()) {
+    *out = it->second;
+    return PM_OK;
+  }
+  HFr wR = domain_gen(S);
+  HFr w4 = domain_gen(2);
+  if (dir) wR = host::inv(wR, host::FR());
+  if (dir) w4 = host::inv(w4, host::FR());
+  NttConsts c;
+  memset(&c, 0, sizeof c);
+  to_limbs(c.w8[0], wR);
+  to_limbs(c.w8[1], w4);
+  to_limbs(c.one, host::one(host::FR()));
+  void* d = nullptr;
+  int rc = build_step4_lazy_table(ctx, &d, c, S, G, st);
+  if (rc) return rc;
+  ctx->step4_lazy_tw[dir][key] = d;
   *out = d;
   return PM_OK;
 }
@@ -368,6 +396,13 @@ int ntt_run(pm_ctx* ctx, const void* d_in, size_t in_len, size_t in_stride, void
     a.in = src;
     a.out = dst;
     a.step_tw = (const u32x4*)stw;
+    a.step_tw_lazy = nullptr;
+    if (const int lazy = r4 ? pass4_lazy_form(S, LT, role) : 0) {   // this shape's step products read the lazy table
+      void* ltw = nullptr;
+      rc = get_step4_lazy_table(ctx, dir, (unsigned)S, (unsigned)lazy, &ltw, st);
+      if (rc) return rc;
+      a.step_tw_lazy = (const u32x4*)ltw;
+    }
     a.batch_stride_in = in_stride;
     a.batch_stride_out = (plan.npass == 1 && inplace) ? n : out_stride;
     a.in_len = (u32)in_len;
@@ -653,6 +688,27 @@ extern "C" int pm_test_ntt_step4_table(pm_ctx* ctx, uint32_t inverse, uint32_t S
   return PM_OK;
 }
 
+// test hook: the lazy split table of radix 2^S in form G (1, 2, 3 or 5 data limbs a row) as a kernel of that form reads it:
+// the w4 head, then the entries of the radix-4 steps from the third on.  Built and cached like a transform's; the
+// arguments behind G are those of pm_test_ntt_step4_table.
+extern "C" int pm_test_ntt_step4_lazy_table(pm_ctx* ctx, uint32_t inverse, uint32_t S, uint32_t G, uint32_t* out,
+                                            size_t max_words, size_t* words) {
+  if (!ctx || inverse > 1 || S < 2 || S > 10 || !(G == 1 || G == 2 || G == 3 || G == 5) || (!out && max_words)) return PM_ERR_BAD_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  PM_HIP(ctx, hipSetDevice(ctx->device));
+  OrderScope order_scope(ctx, ctx->ord_ntt, ctx->stream);
+  if (order_scope.rc) return order_scope.rc;
+  void* tab = nullptr;
+  int rc = get_step4_lazy_table(ctx, (int)inverse, S, G, &tab, ctx->stream);
+  if (rc) return rc;
+  const size_t total = step4_lazy_table_bytes(S, G) / 4;
+  if (words) *words = total;
+  const size_t n = std::min(total, max_words);
+  if (n) PM_HIP(ctx, hipMemcpyAsync(out, tab, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return PM_OK;
+}
+
 extern "C" int pm_domain_prepare(pm_ctx* ctx, uint32_t log_n) {
   if (!ctx) return PM_ERR_BAD_ARG;
   std::lock_guard<std::mutex> lk(ctx->mu);
@@ -683,6 +739,10 @@ extern "C" int pm_domain_prepare(pm_ctx* ctx, uint32_t log_n) {
       rc = r4 ? get_step4_table(ctx, dir, (unsigned)plan.S[i], &stw, ctx->stream)
               : get_step_table(ctx, dir, (unsigned)plan.S[i], &stw, ctx->stream);
       if (rc) return rc;
+      if (const int lazy = r4 ? pass4_lazy_form(plan.S[i], plan.LT[i], role) : 0) {
+        rc = get_step4_lazy_table(ctx, dir, (unsigned)plan.S[i], (unsigned)lazy, &stw, ctx->stream);
+        if (rc) return rc;
+      }
       if (i > 0 && log_n <= 26 && ctx->opt_ntt_direct_tw) {
         void* ptw;
         rc = get_pass_tw(ctx, dt, i, last, dir, log_n, log_ns, plan.S[i], wide_glog, kc, ctx->stream, &ptw);

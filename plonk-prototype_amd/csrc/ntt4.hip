@@ -40,6 +40,10 @@ bool pass4_tw_producer(int S, int LT, int role) {
 }
 // does this shape's kernel take wave priorities by step (PASS_STEP_PRIO)
 bool pass4_step_prio(int S, int LT, int role) { return find_pass4(S, LT, role) != nullptr && step4_has_prio(S); }
+// G of the lazy step table this shape's kernel reads through step_tw_lazy, 0: none
+int pass4_lazy_form(int S, int LT, int role) {
+  return find_pass4(S, LT, role) != nullptr ? step4_lazy_form(S, LT, role == 2 || role == 3) : 0;
+}
 size_t pass4_lds(int S, int LT) { return pass4_lds_bytes(S, LT); }
 
 #ifdef PM_DEV_STAMPS
@@ -72,6 +76,19 @@ int build_step4_table(pm_ctx* ctx, void** out, const NttConsts& c, unsigned S, h
   PM_HIP(ctx, hipMalloc(out, step4_table_bytes(S)));
   hipLaunchKernelGGL(step4_tw_kernel, dim3((std::max(total, 9u * STEP4_HEAD_CONSTS) + 255) / 256), dim3(256), 0, st,
                      (u32x4*)*out, c, S);
+  PM_HIP(ctx, hipGetLastError());
+  return PM_OK;
+}
+
+// the w4 head in front, then the entries of the radix-4 steps from the third on in form G
+size_t step4_lazy_table_bytes(unsigned S, unsigned G) {
+  return ((size_t)STEP4_LAZY_HEAD + (size_t)step4_lazy_total((int)S) * step4_lazy_entry((int)G)) * sizeof(u32x4);
+}
+
+int build_step4_lazy_table(pm_ctx* ctx, void** out, const NttConsts& c, unsigned S, unsigned G, hipStream_t st) {
+  const u32 total = (u32)step4_lazy_total((int)S);
+  PM_HIP(ctx, hipMalloc(out, step4_lazy_table_bytes(S, G)));
+  hipLaunchKernelGGL(step4_lazy_tw_kernel, dim3((std::max(total, 9u) + 255) / 256), dim3(256), 0, st, (u32x4*)*out, c, S, G);
   PM_HIP(ctx, hipGetLastError());
   return PM_OK;
 }

@@ -54,6 +54,8 @@ struct NttPassArgs {
   u32 log_ns;             // log2(Ns)
   u32 lh;                 // split point of the two-level tables
   u32 flags;
+  const u32x4* step_tw_lazy;  // radix-4 shapes with lazy split products (step4_lazy_form): their second step table, else null.
+                              // Last, so that every other member keeps its place in the kernels that do not read it.
 };
 enum : u32 {
   PASS_DIRECT_TW = 1u,   // input twiddles come from pass_tw (one load) instead of hi*lo

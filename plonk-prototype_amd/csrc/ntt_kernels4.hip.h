@@ -7,7 +7,8 @@
 // fe_mul_split (fields.hip.h): a step twiddle as two rows (data limbs 0-4 and 5-8, six reduction digits, 129 limb
 // products instead of 153), w4 as nine rows (one per data limb, two digits, 97).  The results are of fe_mul's class,
 // so the bounds written at BFLY / dft4 hold unchanged.  Only the inter-pass twiddles (36 B per element from HBM)
-// keep the plain form.
+// keep the plain form.  The <10, 1> passes go one step further, "lazy split products" below: their table products leave
+// a digit out, return values up to 37 r in normalised limbs and let the butterflies' constants carry the difference.
 #pragma once
 #include "ntt_kernels.hip.h"
 
@@ -196,6 +197,75 @@ PM_DEV Fr mul_tw2(const Fr& x, const FrSplit2& w) {
 __host__ __device__ constexpr bool step4_has_prio(int S) { return S >= 10 && num_steps4(S) >= 2; }
 __host__ __device__ constexpr int step4_prio(int S, int s) { return num_steps4(S) - 1 - s < 3 ? num_steps4(S) - 1 - s : 3; }
 
+// ---- lazy split products (fe_mul_split with D = G, fields.hip.h): one reduction digit fewer per table product ---------------
+// The products above return the class (1, <2) so that dft4's bounds hold as written; that costs one digit column and N - 1
+// limb products each, and the butterflies do not need it.  A lazy product leaves the limbs normalised and the value below
+// V r, V = 16.01 for a step twiddle in three rows (G = D = 3, 105 limb products instead of 129) and 37.01 for w4 in nine rows
+// (G = D = 1, 89 instead of 97); dft4s_lazy carries V in its fe_sub constants, which are compile-time and free.  The weak
+// reduction of x[0] at the top of every step and the products themselves (any value the limbs allow) bring each step's
+// inputs back to the same classes, so nothing grows from step to step; the walk is in tests/test_fe_mul_split_lazy_model.py.
+// The constants come from a table of their own, a.step_tw_lazy (the one above is unchanged and still serves the first-layer
+// head constants, with D = 2):
+//   head, 84 words: w4 for fe_mul_split<1, 1>, transposed as above: word 9 b + j = limb b of row_j = w4 2^(29 (j - 8)) mod r;
+//   entries of the radix-4 steps s >= 2, in the order of the table above: ceil(9 / G) rows, row_j = w 2^(29 (j G + G - 9)) mod r,
+//   canonical limbs, nine words a row, padded with zero words to a multiple of 16 B (G = 3: 27 words in 7 x 16 B).
+// step4_lazy_form() is the G of a shape's step twiddles, 0 for a shape that keeps the code above instruction for
+// instruction.  The <10, 1> passes of the 2^20 transform take it (profiles/lazy_split_headline_ab.txt):
+// three rows where the pass reads the wide form (last and middle, 98 -> 112 VGPRs), two rows (G = D = 5, 121 limb products,
+// value < 11.01 r, the registers of the parent's two rows) in the first pass, which holds the next pass's twiddles beside
+// its own and needs 136 VGPRs with three rows, one wave per SIMD fewer.  Five rows (G = D = 2, 97 limb products, 124 VGPRs)
+// in the last pass measured 2.4 us slower than three over the 2^20 step, with 98 VALU instructions per wave fewer: twelve
+// 16-byte loads a twiddle instead of seven.  The other shapes were not measured with any of it and keep their code.
+// Such a shape's generic steps all have s >= 2 (ntt_step4 asserts it).
+__host__ __device__ constexpr int step4_lazy_form(int S, int LT, bool in_wide) {
+  return S == 10 && LT == 1 ? (in_wide ? 3 : 5) : 0;
+}
+constexpr int STEP4_LAZY_HEAD = STEP4_HEAD_BLOCK / 4;   // u32x4 units in front of the first entry
+__host__ __device__ constexpr int step4_lazy_rows(int G) { return (9 + G - 1) / G; }
+__host__ __device__ constexpr int step4_lazy_entry(int G) { return (9 * step4_lazy_rows(G) + 3) / 4; }   // u32x4 units per entry
+__host__ __device__ constexpr bool step4_lazy_step(int S, int s) { return s >= 2 && s < num_steps4(S) && step4_radix_log(S, s) == 2; }
+__host__ __device__ constexpr int step4_lazy_offset(int S, int s) {   // entries in front of step s
+  int off = 0;
+  for (int i = 2; i < s; ++i) off += step4_lazy_step(S, i) ? 3 << (2 * i) : 0;
+  return off;
+}
+__host__ __device__ constexpr int step4_lazy_total(int S) { return step4_lazy_offset(S, num_steps4(S)); }
+
+template <int G>
+struct FrSplitLazy {
+  u32 l[9 * step4_lazy_rows(G)];
+};
+template <int G>
+PM_DEV FrSplitLazy<G> ld_tw_lazy(const u32x4* ent, size_t idx) {
+  constexpr int WORDS = 9 * step4_lazy_rows(G), UNITS = step4_lazy_entry(G);
+  const u32x4* p = ent + UNITS * idx;
+  FrSplitLazy<G> r;
+#pragma unroll
+  for (int k = 0; k < UNITS; ++k) {
+    if (WORDS - 4 * k == 2) {   // a row pair ends on half a unit
+      const uint2 e = reinterpret_cast<const uint2*>(p + k)[0];
+      r.l[4 * k] = e.x; r.l[4 * k + 1] = e.y;
+    } else {
+      const u32x4 v = p[k];
+      r.l[4 * k] = v.x;
+      if (4 * k + 1 < WORDS) r.l[4 * k + 1] = v.y;
+      if (4 * k + 2 < WORDS) r.l[4 * k + 2] = v.z;
+      if (4 * k + 3 < WORDS) r.l[4 * k + 3] = v.w;
+    }
+  }
+  return r;
+}
+// x * w for a lazy table twiddle: x (B < 6 for G = 5, B <= 5 otherwise, any V the limbs allow) -> limbs < 2^29, value
+// < (ceil(9 / G) B (1 + 2^-28) + 1) r: < 16.01 r for G = 3 and B = 5
+template <int G>
+PM_DEV Fr mul_tw_lazy(const Fr& x, const FrSplitLazy<G>& w) {
+  return fe_mul_split<FrP, G, G>(x, [&](int j, int b) { return w.l[9 * j + b]; });
+}
+// x * w4 through the lazy head: x (B <= 4) -> limbs < 2^29, value < 37.01 r; 89 limb products
+PM_DEV Fr mul_head_lazy(const Fr& x, W4Rows rows) {
+  return fe_mul_split<FrP, 1, 1>(x, [&](int j, int b) { return rows[9 * b + j]; });
+}
+
 // Diagnostic build only (make EXTRA=-DPM_DEV_STAMPS, tools/ntt_phase_timeline.py): lane 0 of every wave leaves shader-clock
 // and wall-clock stamps at its phase boundaries and its hardware placement in a buffer the host sets (ntt_stamps_arm in
 // ntt4.hip), NTT_STAMP_WORDS words per wave: stamp k in words 2 k (s_memtime) and 2 k + 1 (s_memrealtime), k = 0 kernel entry,
@@ -253,6 +323,22 @@ PM_DEV void dft4s(Fr& a0, Fr& a1, Fr& a2, Fr& a3, W4Rows w4) {
   a2 = t;
 }
 
+// dft4s with lazy inputs and a lazy w4 product: a0 (1, <2) (the weakly reduced or untwiddled input), a1..a3 (1, <16.01), what
+// mul_tw_lazy<3> returns; the (1, <2) of step 0, of the first-layer products and of (5, 5) rows is inside it.  Every K is
+// the least that fe_sub<K, 1> admits for its subtrahend, value < (K - 1) r.  Outputs (<5, <60): below the 2^261 = 68.6 r of
+// fe_reduce_weak and fe_reduce_canon_pack, and limbs that fe_mul, fe_mul_split and the stores take.
+PM_DEV void dft4s_lazy(Fr& a0, Fr& a1, Fr& a2, Fr& a3, W4Rows w4) {
+  BFLY(18, a0, a2);  // a0 (2, <18.02)  a2 (4, <20.01)
+  BFLY(18, a1, a3);  // a1 (2, <32.02)  a3 (4, <34.01)
+  a3 = mul_head_lazy(a3, w4);  // (1, <37.01)
+  a2 = fe_norm<FrP>(a2);
+  BFLY(34, a0, a1);  // a0 = X0 (4, <50.04), a1 = X2 (5, <52.02)
+  BFLY(39, a2, a3);  // a2 = X1 (2+, <57.02), a3 = X3 (4+, <59.01)
+  Fr t = a1;
+  a1 = a2;
+  a2 = t;
+}
+
 // element of the output vector (batch offset apart) that the last step of a pass stores its x[m] to
 template <int S, int LT, bool OUT_UFAST>
 PM_DEV size_t pass4_out_index(const NttPassArgs& a, u32 tid, size_t j0, int m) {
@@ -281,7 +367,9 @@ PM_DEV void ntt_step4(Fr (&x)[4], Fr (&ptw)[4], const NttPassArgs& a, const NttC
   constexpr bool PM = step4_plane_major(S, IN_WIDE);            // plane-major exchanges: u below is tau
   constexpr bool L1_CONSUMER = PM && step4_l1_consumer(S, LT, OUT_UFAST);
   constexpr bool TW_PRODUCER = OUT_WIDE && step4_tw_producer(S, LT, OUT_UFAST, IN_WIDE);
+  constexpr int LAZY = step4_lazy_form(S, LT, IN_WIDE);         // G of the lazy step twiddles, 0: the (1, <2) products
   static_assert(!(L1_UNIFORM && STEP == 0 && ufast), "the producer of the first-layer twiddles is in wave order");
+  static_assert(!LAZY || !step4_generic(S, LT, OUT_UFAST, IN_WIDE, STEP) || step4_lazy_step(S, STEP), "the lazy table starts at step 2");
   const u32 c = ufast ? tid / U : tid & (T - 1);
   const u32 u = ufast ? tid % U : tid >> LT;
   constexpr int PRIO = step4_prio(S, STEP);   // PASS_STEP_PRIO: the further a wave has come, the lower (above step4_prio)
@@ -300,6 +388,19 @@ PM_DEV void ntt_step4(Fr (&x)[4], Fr (&ptw)[4], const NttPassArgs& a, const NttC
   }
   NTT_STAMP(2 + 3 * STEP);
   const u32x4* stw = a.step_tw + STEP4_HEAD + STEP4_ENTRY * step4_tw_offset(S, STEP);
+  // the step's twiddles and their product in the shape's form: lazy rows from a.step_tw_lazy, or the two rows of stw
+  const auto ld_step = [&](size_t i) {
+    if constexpr (LAZY != 0)
+      return ld_tw_lazy<LAZY>(a.step_tw_lazy + STEP4_LAZY_HEAD + step4_lazy_entry(LAZY) * step4_lazy_offset(S, STEP), i);
+    else
+      return ld_tw2(stw, i);
+  };
+  const auto mul_step = [](const Fr& v, const auto& w) {
+    if constexpr (LAZY != 0)
+      return mul_tw_lazy<LAZY>(v, w);
+    else
+      return mul_tw2(v, w);
+  };
   if constexpr (LQ == 2) {
     const u32 kp = PM ? step4_pm_digit(S, STEP, u) : u & (nsp - 1);
     if constexpr (L1_CONSUMER && STEP == 1) {
@@ -315,9 +416,9 @@ PM_DEV void ntt_step4(Fr (&x)[4], Fr (&ptw)[4], const NttPassArgs& a, const NttC
       }
     } else if (STEP > 0 && !(L1_UNIFORM && STEP == 1)) {
       x[0] = fe_reduce_weak<FrP>(x[0]);
-      x[1] = mul_tw2(x[1], ld_tw2(stw, 0 * nsp + kp));
-      x[2] = mul_tw2(x[2], ld_tw2(stw, 1 * nsp + kp));
-      const FrSplit2 w3 = ld_tw2(stw, 2 * nsp + kp);
+      x[1] = mul_step(x[1], ld_step(0 * nsp + kp));
+      x[2] = mul_step(x[2], ld_step(1 * nsp + kp));
+      const auto w3 = ld_step(2 * nsp + kp);
       if constexpr (TW_PRODUCER && STEP >= NSTEPS - 2) {
         // the next pass's twiddles of outputs 0, 1 (second-to-last step) and 2, 3 (last step), issued behind the step's
         // own last twiddle load: loads return in order, so nothing this thread needs soon may queue behind them
@@ -330,14 +431,17 @@ PM_DEV void ntt_step4(Fr (&x)[4], Fr (&ptw)[4], const NttPassArgs& a, const NttC
           __builtin_amdgcn_sched_barrier(0);
         }
       }
-      x[3] = mul_tw2(x[3], w3);
+      x[3] = mul_step(x[3], w3);
     }
     // L1_UNIFORM, step 1: step 0 left x[0] at (1, <1.01) and x[1..3] at (1, <2), the classes dft4s takes
     // every step reads the w4 rows anew (scalar loads, a column at a time): an opaque copy of the pointer, or the
     // rows of step 0 stay in 81 SGPRs for the whole kernel and spill
-    W4Rows w4s = w4;
+    W4Rows w4s = LAZY != 0 ? w4_rows(a.step_tw_lazy) : w4;
     asm volatile("" : "+s"(w4s));
-    dft4s(x[0], x[1], x[2], x[3], w4s);  // X[t] in x[t]
+    if constexpr (LAZY != 0)
+      dft4s_lazy(x[0], x[1], x[2], x[3], w4s);  // (<5, <60) where the comments below say (<5, <40)
+    else
+      dft4s(x[0], x[1], x[2], x[3], w4s);  // X[t] in x[t]
     if constexpr (L1_UNIFORM && STEP == 0) {
       // what step 1 owes its inputs, here: X[0] (<5, <40) -> (1, <1.01); X[t] (<5, <40) times w16^(t m) -> (1, <2).  The
       // rows of each product through an opaque pointer of its own, as above.
@@ -533,6 +637,43 @@ static __global__ void step4_tw_kernel(u32x4* out, const NttConsts c, u32 S) {
       p[2] = u32x4{r0.l[8], r1.l[0], r1.l[1], r1.l[2]};
       p[3] = u32x4{r1.l[3], r1.l[4], r1.l[5], r1.l[6]};
       p[4] = u32x4{r1.l[7], r1.l[8], 0u, 0u};
+      return;
+    }
+    off += cnt;
+  }
+}
+
+// the lazy table of radix 2^S in form G (layout above): the first nine threads also write the head, row j of w4 = c.w8[1].
+// 2^(29 e) in Montgomery form is walked up from 2^29 by factors of 2^29 (fe_pow2<261 + 29>), e = j + 1 for the head's
+// row_j and j G + G for an entry's.
+static __global__ void step4_lazy_tw_kernel(u32x4* out, const NttConsts c, u32 S, u32 G) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  const auto pow29 = [](u32 e) {
+    Fr p = fe_pow2<FrP, 29>();
+    for (u32 k = 1; k < e; ++k) p = fe_mul<FrP>(p, fe_pow2<FrP, 261 + 29>());
+    return p;
+  };
+  if (i < 9) {
+    const Fr row = fr_canon(fe_mul<FrP>(fr_limbs(c.w8[1]), pow29(i + 1)));
+    u32* head = reinterpret_cast<u32*>(out);
+    for (u32 b = 0; b < 9; ++b) head[9 * b + i] = row.l[b];
+    if (i < 3) head[81 + i] = 0u;
+  }
+  const u32 rows = (9 + G - 1) / G, units = (9 * rows + 3) / 4;
+  u32 off = 0;
+  for (u32 s = 2; 2 * s + 2 <= S; ++s) {   // the radix-4 steps from the third on
+    const u32 nsp = 1u << (2 * s);
+    const u32 cnt = 3 * nsp;
+    if (i >= off && i < off + cnt) {
+      const u32 t = (i - off) / nsp + 1, kp = (i - off) % nsp;
+      const u32 e = (kp * t) << (S - 2 * s - 2);
+      const Fr w = fr_pow(fr_limbs(c.w8[0]), e, fr_limbs(c.one));
+      u32* p = reinterpret_cast<u32*>(out + STEP4_LAZY_HEAD + (size_t)units * i);
+      for (u32 j = 0; j < rows; ++j) {
+        const Fr row = fr_canon(fe_mul<FrP>(w, pow29(j * G + G)));
+        for (u32 b = 0; b < 9; ++b) p[9 * j + b] = row.l[b];
+      }
+      for (u32 k = 9 * rows; k < 4 * units; ++k) p[k] = 0u;
       return;
     }
     off += cnt;

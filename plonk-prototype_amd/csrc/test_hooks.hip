@@ -23,15 +23,18 @@ namespace pm {
 enum RawOp {
   RAW_ADD = 0, RAW_NORM, RAW_NORM_FULL, RAW_MUL, RAW_SQR, RAW_MUL_LIMB, RAW_MUL2, RAW_MUL3, RAW_MMA2, RAW_SQR2,
   RAW_REDUCE_WEAK, RAW_UNPACK, RAW_CANON_PACK, RAW_POW2, RAW_SPLIT_5_6, RAW_SPLIT_1_2, RAW_ZERO_PRODUCT, RAW_ZERO_LAZY,
-  RAW_DFT8, RAW_DFT4, RAW_CANON_LIMBS, RAW_INV_INT, RAW_INV_DEV, RAW_REDUCE_CANON_PACK = 24, RAW_SUB = 32   // RAW_SUB + K: fe_sub<K, 1>
+  RAW_DFT8, RAW_DFT4, RAW_CANON_LIMBS, RAW_INV_INT, RAW_INV_DEV, RAW_REDUCE_CANON_PACK = 24,
+  RAW_SPLIT_3_3, RAW_SPLIT_1_1, RAW_SPLIT_5_5,   // the lazy forms (D = G) the radix-4 passes use
+  RAW_SUB = 32   // RAW_SUB + K: fe_sub<K, 1>
 };
 
 __host__ __device__ constexpr int raw_in(int op) {
   return op == RAW_ADD || op == RAW_MUL || op == RAW_MUL_LIMB || op == RAW_SQR2 || op >= RAW_SUB ? 2
          : op == RAW_MUL2                                                                         ? 4
          : op == RAW_MUL3 || op == RAW_MMA2                                                       ? 6
-         : op == RAW_SPLIT_5_6                                                                    ? 3
-         : op == RAW_SPLIT_1_2                                                                    ? 10
+         : op == RAW_SPLIT_5_6 || op == RAW_SPLIT_5_5                                             ? 3
+         : op == RAW_SPLIT_3_3                                                                    ? 4
+         : op == RAW_SPLIT_1_2 || op == RAW_SPLIT_1_1                                             ? 10
          : op == RAW_DFT8                                                                         ? 11
          : op == RAW_DFT4                                                                         ? 5
                                                                                                   : 1;
@@ -86,6 +89,9 @@ __global__ void raw_op_kernel(const u32* in, u32* out, size_t n) {
   }
   if constexpr (OP == RAW_SPLIT_5_6) r[0] = fe_mul_split<P, 5, 6>(x[0], [&](int j, int b) { return x[1 + j].l[b]; });
   if constexpr (OP == RAW_SPLIT_1_2) r[0] = fe_mul_split<P, 1, 2>(x[0], [&](int j, int b) { return x[1 + j].l[b]; });
+  if constexpr (OP == RAW_SPLIT_3_3) r[0] = fe_mul_split<P, 3, 3>(x[0], [&](int j, int b) { return x[1 + j].l[b]; });
+  if constexpr (OP == RAW_SPLIT_1_1) r[0] = fe_mul_split<P, 1, 1>(x[0], [&](int j, int b) { return x[1 + j].l[b]; });
+  if constexpr (OP == RAW_SPLIT_5_5) r[0] = fe_mul_split<P, 5, 5>(x[0], [&](int j, int b) { return x[1 + j].l[b]; });
   if constexpr (OP == RAW_ZERO_PRODUCT) r[0].l[0] = fp_is_zero_product(x[0]) ? 1u : 0u;
   if constexpr (OP == RAW_ZERO_LAZY) r[0].l[0] = fp_is_zero_lazy(x[0]) ? 1u : 0u;
   if constexpr (OP == RAW_DFT8) {
@@ -229,7 +235,8 @@ static bool launch_raw(int op, dim3 g, dim3 blk, hipStream_t st, const u32* in, 
     RAW_CASE(RAW_SUB + 2) RAW_CASE(RAW_SUB + 3) RAW_CASE(RAW_SUB + 5)
   }
   if constexpr (FR) {
-    switch (op) { RAW_CASE(RAW_SPLIT_5_6) RAW_CASE(RAW_SPLIT_1_2) RAW_CASE(RAW_DFT8) RAW_CASE(RAW_DFT4) RAW_CASE(RAW_REDUCE_CANON_PACK) RAW_CASE(RAW_SUB + 9) }
+    switch (op) { RAW_CASE(RAW_SPLIT_5_6) RAW_CASE(RAW_SPLIT_1_2) RAW_CASE(RAW_DFT8) RAW_CASE(RAW_DFT4) RAW_CASE(RAW_REDUCE_CANON_PACK) RAW_CASE(RAW_SUB + 9)
+                  RAW_CASE(RAW_SPLIT_3_3) RAW_CASE(RAW_SPLIT_1_1) RAW_CASE(RAW_SPLIT_5_5) RAW_CASE(RAW_SUB + 18) RAW_CASE(RAW_SUB + 34) RAW_CASE(RAW_SUB + 39) }
   } else {
     switch (op) { RAW_CASE(RAW_ZERO_PRODUCT) RAW_CASE(RAW_ZERO_LAZY) RAW_CASE(RAW_SUB + 6) RAW_CASE(RAW_SUB + 8) RAW_CASE(RAW_SUB + 11) }
   }
@@ -246,14 +253,14 @@ static bool launch_raw(int op, dim3 g, dim3 blk, hipStream_t st, const u32* in, 
 using namespace pm;
 
 extern "C" int pm_test_field_raw_op(pm_ctx* ctx, int field, int op, const uint32_t* in, uint32_t* out, size_t n) {
-  if (!ctx || !in || !out || field < 0 || field > 1 || op < 0 || op > RAW_SUB + 11) return PM_ERR_BAD_ARG;
+  if (!ctx || !in || !out || field < 0 || field > 1 || op < 0 || op > RAW_SUB + 39) return PM_ERR_BAD_ARG;
   const bool fr = field == 0;
   {   // the (field, op) pairs that exist: every fe_sub<K, 1> the library instantiates, the split product and the butterflies for Fr, the zero tests for Fp, the inversion routines for both
     const int k = op - RAW_SUB;
-    const bool sub_ok = k == 2 || k == 3 || k == 5 || (fr ? k == 9 : (k == 6 || k == 8 || k == 11));
-    const bool fr_only = op == RAW_SPLIT_5_6 || op == RAW_SPLIT_1_2 || op == RAW_DFT8 || op == RAW_DFT4 || op == RAW_REDUCE_CANON_PACK;
+    const bool sub_ok = k == 2 || k == 3 || k == 5 || (fr ? (k == 9 || k == 18 || k == 34 || k == 39) : (k == 6 || k == 8 || k == 11));
+    const bool fr_only = op == RAW_SPLIT_5_6 || op == RAW_SPLIT_1_2 || op == RAW_DFT8 || op == RAW_DFT4 || op == RAW_REDUCE_CANON_PACK || (op >= RAW_SPLIT_3_3 && op <= RAW_SPLIT_5_5);
     const bool fp_only = op == RAW_ZERO_PRODUCT || op == RAW_ZERO_LAZY;
-    if (op >= RAW_SUB ? !sub_ok : ((op > RAW_INV_DEV && op != RAW_REDUCE_CANON_PACK) || (fr_only && !fr) || (fp_only && fr))) return PM_ERR_BAD_ARG;
+    if (op >= RAW_SUB ? !sub_ok : ((op > RAW_INV_DEV && !(op >= RAW_REDUCE_CANON_PACK && op <= RAW_SPLIT_5_5)) || (fr_only && !fr) || (fp_only && fr))) return PM_ERR_BAD_ARG;
   }
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (n == 0) return PM_OK;
