@@ -1245,7 +1245,10 @@ int pm_ntt_plan(uint32_t log_n, uint32_t radix_log2[4], uint32_t* n_passes);
  * pass's inter-pass twiddle table, so that pass starts on its data alone; 0: every pass multiplies its own inputs.  Same results either way;
  * it needs "ntt_direct_tw" = 1), "ntt_step_prio" (1, the default: the waves of a radix-4 pass of radix 2^10 lower their issue priority step by
  * step, so that the two workgroups of a CU alternate instead of one running ahead; 0: age alone.  Same results either way; any other
- * value is PM_ERR_BAD_ARG), "ntt_pipeline" (0 = no copy / compute overlap in pm_fr_ntt_batch), "poly_lookback" (prefix product in one
+ * value is PM_ERR_BAD_ARG), "ntt_fixed_shape" (1, the default: a pass launch whose size, place in the plan, flags and layout are exactly
+ * those of a fixed-shape kernel takes that kernel, which has the geometry and the flags compiled in, if it measured faster than the generic
+ * one: the first radix-2^10 pass of a plain 2^20 transform, forward or inverse, batched or not; 2: every fixed-shape kernel there is, the last pass
+ * of that transform too; 0: every launch takes the generic kernel.  Same results in all three; any other value is PM_ERR_BAD_ARG), "ntt_pipeline" (0 = no copy / compute overlap in pm_fr_ntt_batch), "poly_lookback" (prefix product in one
  * pass: 0 never, 1 while all tiles are resident -- the default --, 2 always).  PM_ERR_BAD_ARG if unknown. */
 int pm_set_option(pm_ctx* ctx, const char* key, long value);
 /* Opt-in per-kernel timing with hipEvents recorded on the launch stream (bench.py's roofline
@@ -1354,6 +1357,18 @@ int pm_test_ntt_step4_lazy_table(pm_ctx* ctx, uint32_t inverse, uint32_t S, uint
  * (0xFFFFFFFF at step 0), 10 its step-twiddle digit k', 11 whether the step takes its twiddles from the head's scalar
  * rows (step 1 with a wave-uniform digit)}.  PM_ERR_BAD_ARG for a shape that keeps the Stockham exchange. */
 int pm_test_ntt_exchange_map(uint32_t S, uint32_t LT, uint32_t ufast, uint32_t step, uint32_t tid, uint32_t out[12]);
+/* Pure host, no context, no device: 1 if pm_fr_ntt* gives this pass launch its fixed-shape kernel, 0 if the generic one.  The launch: a
+ * radix-4 pass of radix 2^S over 2^LT columns per tile, role 1 (first) or 3 (last; 0 single and 2 middle have no fixed kernel) of a
+ * transform of 2^log_n points of which 2^log_ns are done by the passes before it, intermediate vectors blocked by 2^wide_glog
+ * (out[18] of pm_test_ntt_plan), pass_flags the launch's flags (csrc/ntt_kernels.hip.h: 1 PASS_DIRECT_TW, 2 PASS_PRE_COSET,
+ * 4 PASS_POST_SCALE, 8 PASS_POST_COSET, 16 PASS_XCD_REMAP, 32 PASS_TW_OUT, 64 PASS_TW_APPLIED, 128 PASS_STEP_PRIO), in_len
+ * the elements present in the transform's input, coset whether the transform has PM_NTT_COSET (a transform that is not plain, or
+ * pads its input, keeps the generic kernels in all its passes), fixed_shape the option "ntt_fixed_shape" (0, 1 or 2). */
+int pm_test_ntt_fixed_match(uint32_t S, uint32_t LT, uint32_t role, uint32_t log_n, uint32_t log_ns, uint32_t wide_glog,
+                            uint32_t pass_flags, uint64_t in_len, uint32_t coset, uint32_t fixed_shape);
+/* Which kernel each pass of the context's last transform was launched with -- out[4], a pass each: 0 no such pass (sizes below
+ * 2^3 have no pass kernels), 1 the generic kernel, 2 its fixed-shape variant. */
+int pm_test_ntt_last_variants(pm_ctx* ctx, uint32_t out[4]);
 /* Pure host, no context: the geometry of pm_plonk_sigma_from_wires' sort (csrc/wire_perm.hip) -- passes =
  * max(1, ceil(bits(num_vars - 1) / 8)) 8-bit digit passes, tiles = ceil(4n / 4096) workgroups per pass, scratch_bytes = the
  * transient device memory of the call.  Each out pointer may be NULL.  The errors of pm_plonk_sigma_from_wires for n and

@@ -334,6 +334,11 @@ extern "C" int pm_set_option(pm_ctx* ctx, const char* key, long value) {
     ctx->opt_ntt_step_prio = value;
     return PM_OK;
   }
+  if (!strcmp(key, "ntt_fixed_shape")) {
+    if (value < 0 || value > 2) return set_err(ctx, PM_ERR_BAD_ARG, "ntt_fixed_shape must be 0 (off), 1 or 2 (every variant)");
+    ctx->opt_ntt_fixed_shape = value;
+    return PM_OK;
+  }
   if (!strcmp(key, "ntt_radix")) {
     if (value != 4 && value != 8) return set_err(ctx, PM_ERR_BAD_ARG, "ntt_radix must be 4 or 8");
     ctx->opt_ntt_radix = value;

@@ -58,6 +58,9 @@ int ntt_stamps_arm(pm_ctx* ctx, hipStream_t st, int pass, size_t waves);
 int build_step4_table(pm_ctx* ctx, void** out, const NttConsts& c, unsigned S, hipStream_t st);
 size_t step4_table_bytes(unsigned S);
 int pass4_lazy_form(int S, int LT, int role);
+// fixed-shape variants (ntt4_fixed.hip): the kernel for a launch that equals one exactly, else null
+pass_fn find_pass4_fixed(int S, int LT, int role, unsigned log_n, unsigned log_ns, unsigned wide_glog, unsigned flags,
+                         unsigned long long in_len, bool coset, long mode, int* lazy_form);
 int build_step4_lazy_table(pm_ctx* ctx, void** out, const NttConsts& c, unsigned S, unsigned G, hipStream_t st);
 size_t step4_lazy_table_bytes(unsigned S, unsigned G);
 
@@ -318,6 +321,7 @@ int ntt_run(pm_ctx* ctx, const void* d_in, size_t in_len, size_t in_stride, void
   if (order_scope.rc) return order_scope.rc;
   const int dir = (flags & PM_NTT_INVERSE) ? 1 : 0;
   const bool coset = (flags & PM_NTT_COSET) != 0;
+  memset(ctx->ntt_last_variant, 0, sizeof ctx->ntt_last_variant);   // what pm_test_ntt_last_variants reports: this transform's passes
 
   if (log_n == 0) {  // size-1 domain: identity (w = 1, size_inv = 1, g^0 = 1); zero if in_len == 0
     for (unsigned b = 0; b < batch; ++b) {
@@ -436,6 +440,21 @@ int ntt_run(pm_ctx* ctx, const void* d_in, size_t in_len, size_t in_stride, void
     }
     a.flags = (i == 0 ? pre : 0u) | post_i | tw_flag | (ctx->opt_ntt_xcd ? PASS_XCD_REMAP : 0u);
     if (r4 && ctx->opt_ntt_step_prio && pass4_step_prio(S, LT, role)) a.flags |= PASS_STEP_PRIO;   // wave priorities by step
+    // a launch that is a fixed-shape variant's in every respect takes it: same arguments, grid and LDS, fewer instructions
+    ctx->ntt_last_variant[i] = 1;
+    if (r4 && ctx->opt_ntt_fixed_shape) {
+      int flazy = 0;
+      if (pass_fn ffn = find_pass4_fixed(S, LT, role, log_n, log_ns, a.wide_glog, a.flags, in_len, coset, ctx->opt_ntt_fixed_shape, &flazy)) {
+        if (flazy != pass4_lazy_form(S, LT, role)) {   // the variant reads another form of the lazy table than the generic kernel
+          void* ltw = nullptr;
+          rc = get_step4_lazy_table(ctx, dir, (unsigned)S, (unsigned)flazy, &ltw, st);
+          if (rc) return rc;
+          a.step_tw_lazy = (const u32x4*)ltw;
+        }
+        fn = ffn;
+        ctx->ntt_last_variant[i] = 2;
+      }
+    }
     const unsigned threads = r4 ? pass4_threads(S, LT) : std::max(64u, (1u << (S + LT)) / 8);
     const size_t lds = r4 ? pass4_lds(S, LT) : pass_lds_bytes(S, LT);
     if (lds > 64 * 1024)   // once per kernel and process, not per launch
@@ -665,6 +684,30 @@ extern "C" int pm_test_ntt_plan(uint32_t log_n, uint32_t batch, long tile_log, l
     if ((r4 ? find_pass4(S, LT, role) : find_pass(S, LT, role)) != nullptr) out[17] |= 1u << i;
   }
   out[18] = plan.npass ? plan_wide_glog(plan) : 0u;
+  return PM_OK;
+}
+
+// test hook (pure host): would ntt_run() give this launch its fixed-shape variant: 1, or 0 for the generic kernel.  The launch
+// is a radix-4 pass of radix 2^S over 2^LT columns in `role` (1 first, 3 last) of a 2^log_n transform with log_ns done before
+// it, wide vectors blocked by 2^wide_glog, the pass's PASS_* flags, in_len input elements, coset: the transform has PM_NTT_COSET;
+// fixed_shape is the option's value (0, 1 or 2).
+extern "C" int pm_test_ntt_fixed_match(uint32_t S, uint32_t LT, uint32_t role, uint32_t log_n, uint32_t log_ns,
+                                       uint32_t wide_glog, uint32_t pass_flags, uint64_t in_len, uint32_t coset,
+                                       uint32_t fixed_shape) {
+  if (S > 31 || LT > 31 || role > 3 || fixed_shape > 2) return 0;
+  return fixed_shape && find_pass4((int)S, (int)LT, (int)role) != nullptr &&
+                 find_pass4_fixed((int)S, (int)LT, (int)role, log_n, log_ns, wide_glog, pass_flags, in_len, coset != 0,
+                                  (long)fixed_shape, nullptr) != nullptr
+             ? 1
+             : 0;
+}
+
+// test hook: which kernel each pass of the context's last transform took.  out[4], a pass each: 0 no such pass (or a size
+// without pass kernels), 1 the generic kernel, 2 its fixed-shape variant.
+extern "C" int pm_test_ntt_last_variants(pm_ctx* ctx, uint32_t out[4]) {
+  if (!ctx || !out) return PM_ERR_BAD_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  for (int i = 0; i < 4; ++i) out[i] = ctx->ntt_last_variant[i];
   return PM_OK;
 }
 

@@ -220,6 +220,18 @@ __host__ __device__ constexpr int step4_prio(int S, int s) { return num_steps4(S
 __host__ __device__ constexpr int step4_lazy_form(int S, int LT, bool in_wide) {
   return S == 10 && LT == 1 ? (in_wide ? 3 : 5) : 0;
 }
+// A fixed-shape first pass (FIX != 0, below) has its addresses in 32-bit offsets, not in VGPR pairs, and holds three rows in
+// 117 VGPRs without scratch (two rows: 102): 216 VALU instructions a wave fewer, 1.2 us a launch and 2.8 us of the 2^20 step
+// (profiles/fixed_shape_headline_ab.txt).  PM_NTT_FIXED_FIRST_G is its G; A/B builds set the other one
+// (make EXTRA=-DPM_NTT_FIXED_FIRST_G=5).  It reads the G = 3 table of the last pass, ntt_run() hands it over.  Its inputs and
+// outputs are of the last pass's classes, step for step (tests/test_ntt_fixed_shape_lazy_model.py walks them).
+#ifndef PM_NTT_FIXED_FIRST_G
+#define PM_NTT_FIXED_FIRST_G 3
+#endif
+// G of the kernel ntt_pass4_fixed_kernel<.., FIX> (FIX = 0: of the generic kernel)
+__host__ __device__ constexpr int step4_fixed_lazy_form(int S, int LT, bool in_wide, int FIX) {
+  return FIX != 0 && !in_wide && step4_lazy_form(S, LT, in_wide) != 0 ? PM_NTT_FIXED_FIRST_G : step4_lazy_form(S, LT, in_wide);
+}
 constexpr int STEP4_LAZY_HEAD = STEP4_HEAD_BLOCK / 4;   // u32x4 units in front of the first entry
 __host__ __device__ constexpr int step4_lazy_rows(int G) { return (9 + G - 1) / G; }
 __host__ __device__ constexpr int step4_lazy_entry(int G) { return (9 * step4_lazy_rows(G) + 3) / 4; }   // u32x4 units per entry
@@ -339,6 +351,79 @@ PM_DEV void dft4s_lazy(Fr& a0, Fr& a1, Fr& a2, Fr& a3, W4Rows w4) {
   a2 = t;
 }
 
+// ---- fixed-shape variants (FIX = log_n, 0: the generic kernel; option ntt_fixed_shape) --------------
+// The two <10, 1> passes of a plain 2^20 transform run with one geometry and one set of flags: log_n, log_ns, n_cols and the
+// wide layout's blocking are constants there, the input is whole, nothing is multiplied in at the ends beside the inter-pass
+// twiddles, and the priorities and the XCD tiling are on.  ntt_pass4_fixed_kernel<.., FIX> is that launch and nothing else
+// (ntt_run() takes it only when pass4_fixed_match() holds, everything else launches ntt_pass4_kernel as before): the flag
+// tests are decided at compile time, the other entries and exits do not exist, and every global address is a uniform
+// 64-bit base (batch vector and tile, scalar arithmetic) plus a 32-bit byte offset of the lane (2^FIX x 36 B fits), the form
+// a global load or store takes with its base in SGPRs.  The arithmetic, its order, the placement of the loads, the
+// priorities and the LDS maps are those of the generic kernel, line for line.
+constexpr u32 PASS4_FIX_GLOG = 2;   // blocking of the wide layout in a plan of <10, 1> passes (plan_wide_glog)
+// the flags a launch must carry, all of them and no other: in_wide picks the last pass's set (first: false)
+__host__ __device__ constexpr u32 pass4_fixed_flags(bool in_wide) {
+  return (in_wide ? PASS_TW_APPLIED : PASS_TW_OUT) | PASS_STEP_PRIO | PASS_XCD_REMAP;
+}
+// may this launch take the fixed variant of (S, LT, in_wide) built for log_n = FIX: the geometry and the flags are the variant's,
+// and the transform it belongs to is a plain one on a whole input (coset: PM_NTT_COSET; a coset transform's plain pass and
+// the last pass behind a zero-padded input keep the generic kernel too: the variants were measured in the plain transform)
+__host__ __device__ constexpr bool pass4_fixed_match(int FIX, int S, int LT, bool in_wide, u32 log_n, u32 log_ns, u32 wide_glog,
+                                                     u32 flags, unsigned long long in_len, bool coset) {
+  return FIX != 0 && log_n == (u32)FIX && log_ns == (in_wide ? (u32)(FIX - S) : 0u) && wide_glog == PASS4_FIX_GLOG &&
+         flags == pass4_fixed_flags(in_wide) && in_len == (1ull << FIX) && !coset;
+}
+// A lane's byte offset, opaque to the compiler (no instruction): knowing its range, the compiler takes a constant summand out
+// of it and adds it to the 64-bit address instead, lane by lane in VGPR pairs, which is the arithmetic these offsets replace.
+PM_DEV u32 lane_off(u32 off) {
+  asm("" : "+v"(off));
+  return off;
+}
+// a wide vector seen from a uniform element i0: the lane adds an element offset i with (i0 & 3) + (i & 3) <= 3, so that the
+// block and the place inside it split into a uniform and a lane part (the callers' i0 is a multiple of the tile width T <= 4
+// and their i is a column below T plus a multiple of 4)
+struct WideFix {
+  char* q;    // limbs 0-3 of element i0; limbs 4-7 are 64 B further
+  char* q8;   // limb 8 of element i0
+};
+PM_DEV WideFix wide_fix(const void* base, size_t i0) {
+  char* b = reinterpret_cast<char*>(const_cast<void*>(base)) + 36 * 4 * (i0 >> PASS4_FIX_GLOG);
+  const u32 e = (u32)i0 & 3u;
+  return WideFix{b + 16 * e, b + 128 + 4 * e};
+}
+PM_DEV Fr ld_wide_fix(const WideFix& w, u32 i) {
+  const u32 blk = 144u * (i >> PASS4_FIX_GLOG), e = i & 3u;
+  const u32x4* q = reinterpret_cast<const u32x4*>(w.q + lane_off(blk + 16u * e));
+  u32x4 a = q[0], b = q[4];
+  u32 c = reinterpret_cast<const u32*>(w.q8 + lane_off(blk + 4u * e))[0];
+  Fr r;
+  r.l[0] = a.x; r.l[1] = a.y; r.l[2] = a.z; r.l[3] = a.w;
+  r.l[4] = b.x; r.l[5] = b.y; r.l[6] = b.z; r.l[7] = b.w;
+  r.l[8] = c;
+  return r;
+}
+PM_DEV void st_wide_fix(const WideFix& w, u32 i, const Fr& v) {
+  const u32 blk = 144u * (i >> PASS4_FIX_GLOG), e = i & 3u;
+  u32x4* q = reinterpret_cast<u32x4*>(w.q + lane_off(blk + 16u * e));
+  q[0] = u32x4{v.l[0], v.l[1], v.l[2], v.l[3]};
+  q[4] = u32x4{v.l[4], v.l[5], v.l[6], v.l[7]};
+  reinterpret_cast<u32*>(w.q8 + lane_off(blk + 4u * e))[0] = v.l[8];
+}
+// pass4_out_index of a fixed variant without its tile: the lane's element offset from output j0 R (first pass, log_ns = 0)
+// or j0 (last pass, log_ns = FIX - S, where j < ns and k = j)
+template <int S, int LT, bool OUT_UFAST, bool IN_WIDE, int FIX>
+PM_DEV u32 pass4_fixed_out_lane(u32 tid, int m) {
+  constexpr u32 U = (1u << S) / 4;
+  const u32 c = OUT_UFAST ? tid / U : tid & ((1u << LT) - 1u);
+  const u32 u = OUT_UFAST ? tid % U : tid >> LT;
+  return IN_WIDE ? c + ((u + (u32)m * U) << (FIX - S)) : (c << S) + u + (u32)m * U;
+}
+// ld_tw_lazy with the entry's byte offset in 32 bits (a step's table is a few KB)
+template <int G>
+PM_DEV FrSplitLazy<G> ld_tw_lazy_fix(const u32x4* ent, u32 idx) {
+  return ld_tw_lazy<G>(reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(ent) + lane_off(16u * step4_lazy_entry(G) * idx)), 0);
+}
+
 // element of the output vector (batch offset apart) that the last step of a pass stores its x[m] to
 template <int S, int LT, bool OUT_UFAST>
 PM_DEV size_t pass4_out_index(const NttPassArgs& a, u32 tid, size_t j0, int m) {
@@ -352,7 +437,7 @@ PM_DEV size_t pass4_out_index(const NttPassArgs& a, u32 tid, size_t j0, int m) {
   return (j - k) * R + k + (size_t)(u + m * U) * ns;
 }
 
-template <int S, int LT, int STEP, bool OUT_UFAST, bool IN_WIDE, bool OUT_WIDE>
+template <int S, int LT, int STEP, bool OUT_UFAST, bool IN_WIDE, bool OUT_WIDE, int FIX = 0>
 PM_DEV void ntt_step4(Fr (&x)[4], Fr (&ptw)[4], const NttPassArgs& a, const NttConsts& kc, u32x4* lds0, u32x4* lds1,
                       u32* lds2, W4Rows w4, u32 tid, size_t j0) {
   constexpr int R = 1 << S;
@@ -367,14 +452,17 @@ PM_DEV void ntt_step4(Fr (&x)[4], Fr (&ptw)[4], const NttPassArgs& a, const NttC
   constexpr bool PM = step4_plane_major(S, IN_WIDE);            // plane-major exchanges: u below is tau
   constexpr bool L1_CONSUMER = PM && step4_l1_consumer(S, LT, OUT_UFAST);
   constexpr bool TW_PRODUCER = OUT_WIDE && step4_tw_producer(S, LT, OUT_UFAST, IN_WIDE);
-  constexpr int LAZY = step4_lazy_form(S, LT, IN_WIDE);         // G of the lazy step twiddles, 0: the (1, <2) products
+  constexpr int LAZY = step4_fixed_lazy_form(S, LT, IN_WIDE, FIX);  // G of the lazy step twiddles, 0: the (1, <2) products
   static_assert(!(L1_UNIFORM && STEP == 0 && ufast), "the producer of the first-layer twiddles is in wave order");
   static_assert(!LAZY || !step4_generic(S, LT, OUT_UFAST, IN_WIDE, STEP) || step4_lazy_step(S, STEP), "the lazy table starts at step 2");
   const u32 c = ufast ? tid / U : tid & (T - 1);
   const u32 u = ufast ? tid % U : tid >> LT;
   constexpr int PRIO = step4_prio(S, STEP);   // PASS_STEP_PRIO: the further a wave has come, the lower (above step4_prio)
   if constexpr (step4_has_prio(S) && STEP > 0 && PRIO != step4_prio(S, STEP - 1)) {
-    if (a.flags & PASS_STEP_PRIO) __builtin_amdgcn_s_setprio(PRIO);
+    if constexpr (FIX != 0)
+      __builtin_amdgcn_s_setprio(PRIO);
+    else if (a.flags & PASS_STEP_PRIO)
+      __builtin_amdgcn_s_setprio(PRIO);
   }
   if (STEP > 0) {
 #pragma unroll
@@ -390,7 +478,9 @@ PM_DEV void ntt_step4(Fr (&x)[4], Fr (&ptw)[4], const NttPassArgs& a, const NttC
   const u32x4* stw = a.step_tw + STEP4_HEAD + STEP4_ENTRY * step4_tw_offset(S, STEP);
   // the step's twiddles and their product in the shape's form: lazy rows from a.step_tw_lazy, or the two rows of stw
   const auto ld_step = [&](size_t i) {
-    if constexpr (LAZY != 0)
+    if constexpr (LAZY != 0 && FIX != 0)
+      return ld_tw_lazy_fix<LAZY>(a.step_tw_lazy + STEP4_LAZY_HEAD + step4_lazy_entry(LAZY) * step4_lazy_offset(S, STEP), (u32)i);
+    else if constexpr (LAZY != 0)
       return ld_tw_lazy<LAZY>(a.step_tw_lazy + STEP4_LAZY_HEAD + step4_lazy_entry(LAZY) * step4_lazy_offset(S, STEP), i);
     else
       return ld_tw2(stw, i);
@@ -422,7 +512,14 @@ PM_DEV void ntt_step4(Fr (&x)[4], Fr (&ptw)[4], const NttPassArgs& a, const NttC
       if constexpr (TW_PRODUCER && STEP >= NSTEPS - 2) {
         // the next pass's twiddles of outputs 0, 1 (second-to-last step) and 2, 3 (last step), issued behind the step's
         // own last twiddle load: loads return in order, so nothing this thread needs soon may queue behind them
-        if (a.flags & PASS_TW_OUT) {
+        if constexpr (FIX != 0) {
+          const WideFix wtw = wide_fix(a.pass_tw_out, j0 << S);
+          constexpr int m0 = last ? 2 : 0;
+          __builtin_amdgcn_sched_barrier(0);
+          ptw[m0] = ld_wide_fix(wtw, pass4_fixed_out_lane<S, LT, OUT_UFAST, IN_WIDE, FIX>(tid, m0));
+          ptw[m0 + 1] = ld_wide_fix(wtw, pass4_fixed_out_lane<S, LT, OUT_UFAST, IN_WIDE, FIX>(tid, m0 + 1));
+          __builtin_amdgcn_sched_barrier(0);
+        } else if (a.flags & PASS_TW_OUT) {
           const WidePtr wtw = wide_ptrs(const_cast<void*>(a.pass_tw_out), a.wide_glog);
           constexpr int m0 = last ? 2 : 0;
           __builtin_amdgcn_sched_barrier(0);
@@ -480,7 +577,29 @@ PM_DEV void ntt_step4(Fr (&x)[4], Fr (&ptw)[4], const NttPassArgs& a, const NttC
   }
   if constexpr (last) {
     const size_t n = (size_t)1 << a.log_n;
-    if constexpr (OUT_WIDE) {
+    if constexpr (FIX != 0 && OUT_WIDE) {
+      static_assert(FIX == 0 || (TW_PRODUCER && !IN_WIDE), "the fixed first pass applies the next pass's twiddles");
+      const WideFix wout = wide_fix(a.out, ((size_t)blockIdx.y << FIX) + (j0 << S));
+      // The one flag test a fixed variant keeps (the launch has the flag, pass4_fixed_match): the branch ends the compiler's
+      // scheduling region in front of the four products and behind them, as in the generic kernel.  As one region with the
+      // last butterflies the products are woven into them and the kernel spills (256 VGPRs, 1.6 KB of scratch; fences of
+      // sched_barrier do not end a region); with the branch it holds 102 VGPRs with two lazy rows, 117 with three, and no scratch.
+      if (a.flags & PASS_TW_OUT) {
+#pragma unroll
+        for (int m = 0; m < 4; ++m) x[m] = fe_mul<FrP>(x[m], ptw[m]);  // (<5, <40) * canonical -> (1, <2)
+      }
+#pragma unroll
+      for (int m = 0; m < 4; ++m) st_wide_fix(wout, pass4_fixed_out_lane<S, LT, OUT_UFAST, IN_WIDE, FIX>(tid, m), x[m]);
+    } else if constexpr (FIX != 0) {
+      static_assert(FIX == 0 || IN_WIDE, "the fixed last pass reads the wide form");
+      char* gout = reinterpret_cast<char*>(a.out) + 32 * ((size_t)blockIdx.y * a.batch_stride_out + j0);
+#pragma unroll
+      for (int m = 0; m < 4; ++m) {
+        u32 w[8];   // one pair of stores behind the eight words, as below
+        fe_reduce_canon_pack<FrP>(w, x[m]);  // (<5, <40)
+        fe_store_words<FrP>(gout + lane_off(32u * pass4_fixed_out_lane<S, LT, OUT_UFAST, IN_WIDE, FIX>(tid, m)), w);
+      }
+    } else if constexpr (OUT_WIDE) {
       const WidePtr wout = wide_ptrs(a.out, a.wide_glog);
       const size_t boff = (size_t)blockIdx.y * n;
       if constexpr (TW_PRODUCER) {
@@ -601,6 +720,51 @@ __global__ void __launch_bounds__((1 << (S + LT)) / 4 < 64 ? 64 : (1 << (S + LT)
   if constexpr (NSTEPS > 3) ntt_step4<S, LT, 3, OUT_UFAST, IN_WIDE, OUT_WIDE>(x, ptw, a, kc, lds0, lds1, lds2, w4, tid, j0);
   if constexpr (NSTEPS > 4) ntt_step4<S, LT, 4, OUT_UFAST, IN_WIDE, OUT_WIDE>(x, ptw, a, kc, lds0, lds1, lds2, w4, tid, j0);
   if constexpr (NSTEPS > 5) ntt_step4<S, LT, 5, OUT_UFAST, IN_WIDE, OUT_WIDE>(x, ptw, a, kc, lds0, lds1, lds2, w4, tid, j0);
+}
+
+// The same pass for the one launch of pass4_fixed_match(FIX, ..): same arguments, same grid, same LDS.  A kernel of its own
+// beside the generic one, which keeps its text and its instruction stream.
+template <int S, int LT, bool OUT_UFAST, bool IN_WIDE, bool OUT_WIDE, int FIX>
+__global__ void __launch_bounds__((1 << (S + LT)) / 4 < 64 ? 64 : (1 << (S + LT)) / 4)
+    ntt_pass4_fixed_kernel(const NttPassArgs a, const NttConsts kc) {
+  constexpr int R = 1 << S;
+  constexpr int T = 1 << LT;
+  constexpr int U = R / 4;
+  constexpr int NSTEPS = num_steps4(S);
+  static_assert(FIX > S + LT + 3 && FIX < 26 && T <= (1 << PASS4_FIX_GLOG) && U * T >= 64 && NSTEPS > 1 && NSTEPS <= 6 &&
+                    step4_has_prio(S) && IN_WIDE != OUT_WIDE && OUT_UFAST == OUT_WIDE,
+                "fixed variants: first and last passes with priorities, 36 B x 2^FIX in 32 bits, a tile inside a wide block");
+  extern __shared__ u32x4 lds[];
+  u32x4* lds0 = lds;
+  u32x4* lds1 = lds + R * T;
+  u32* lds2 = reinterpret_cast<u32*>(lds + 2 * R * T);
+
+  const u32 tid = threadIdx.x;
+  __builtin_amdgcn_s_setprio(3);   // the entry loads and step 0 run at 3
+  // 2^(FIX - S - LT) tiles, a multiple of 8, dealt as xcd_tile() deals them under PASS_XCD_REMAP
+  const size_t j0 = (size_t)((blockIdx.x & 7u) * ((1u << (FIX - S - LT)) >> 3) + (blockIdx.x >> 3)) * T;
+  const W4Rows w4 = w4_rows(a.step_tw);
+
+  Fr x[4], ptw[4];  // ptw: the next pass's twiddles, loaded by the last two steps
+  {
+    const u32 c = tid & (T - 1);
+    const u32 u = tid >> LT;
+    if constexpr (IN_WIDE) {   // (1, <2) products of the producing pass (PASS_TW_APPLIED)
+      const WideFix win = wide_fix(a.in, ((size_t)blockIdx.y << FIX) + j0);
+#pragma unroll
+      for (int m = 0; m < 4; ++m) x[m] = ld_wide_fix(win, c + ((u + (u32)m * U) << (FIX - S)));
+    } else {                   // the whole input is there (in_len = n), no coset
+      const char* gin = reinterpret_cast<const char*>(a.in) + 32 * ((size_t)blockIdx.y * a.batch_stride_in + j0);
+#pragma unroll
+      for (int m = 0; m < 4; ++m) x[m] = fe_load<FrP>(gin + lane_off(32u * (c + ((u + (u32)m * U) << (FIX - S)))));
+    }
+  }
+  ntt_step4<S, LT, 0, OUT_UFAST, IN_WIDE, OUT_WIDE, FIX>(x, ptw, a, kc, lds0, lds1, lds2, w4, tid, j0);
+  ntt_step4<S, LT, 1, OUT_UFAST, IN_WIDE, OUT_WIDE, FIX>(x, ptw, a, kc, lds0, lds1, lds2, w4, tid, j0);
+  if constexpr (NSTEPS > 2) ntt_step4<S, LT, 2, OUT_UFAST, IN_WIDE, OUT_WIDE, FIX>(x, ptw, a, kc, lds0, lds1, lds2, w4, tid, j0);
+  if constexpr (NSTEPS > 3) ntt_step4<S, LT, 3, OUT_UFAST, IN_WIDE, OUT_WIDE, FIX>(x, ptw, a, kc, lds0, lds1, lds2, w4, tid, j0);
+  if constexpr (NSTEPS > 4) ntt_step4<S, LT, 4, OUT_UFAST, IN_WIDE, OUT_WIDE, FIX>(x, ptw, a, kc, lds0, lds1, lds2, w4, tid, j0);
+  if constexpr (NSTEPS > 5) ntt_step4<S, LT, 5, OUT_UFAST, IN_WIDE, OUT_WIDE, FIX>(x, ptw, a, kc, lds0, lds1, lds2, w4, tid, j0);
 }
 
 // step twiddles of the radix-4 kernel: block s, entry [(t-1)*Ns' + k'] = wR^(k' t R/(Ns' q)), Ns' = 4^s, both rows
