@@ -1056,6 +1056,26 @@ int pm_schnorr_verify_batch_dev(pm_ctx* ctx, const pm_jubjub_base* g, const pm_h
  *     it must be affine), then the decryption with the curve test of R.  The call allocates the tables of those threads (1216
  *     bytes each) and releases them before it returns, which WAITS for the device, as pm_jubjub_mul_dev does.  R is not
  *     checked to lie in the prime-order subgroup.  NOT hardened against side channels: the table addresses depend on vk.
+ *   pm_poseidon_cipher_scan_keys_dev: the same n notes under n_keys viewing keys, 1 ..
+ *     PM_CIPHER_SCAN_MAX_KEYS of them, in one call.  view_keys: host, n_keys x 4 words in `scalar_form`; duplicates and a key of 0
+ *     are legal.  With st_k[i] and m_k[i] the status and the message pm_poseidon_cipher_scan_dev gives note i under view_keys[k]:
+ *       d_masks[i]    (required, n x uint64) bit k is set exactly when st_k[i] == PM_CIPHER_OK; bits n_keys and above are zero;
+ *       d_status[i]   (n x uint32, 4-byte aligned, may be NULL) PM_CIPHER_POINT or PM_CIPHER_RANGE where the single-key scan
+ *                     reports them -- both depend on the note alone --, else PM_CIPHER_OK when the mask is not zero, else
+ *                     PM_CIPHER_TAG;
+ *       d_msgs_out[i] (n x L elements, may be NULL) m_k[i] for the LOWEST set k, zeros when the mask is zero.  Only the lowest
+ *                     key's message is returned: two keys open one note only when they give the same S (duplicate keys, R the
+ *                     identity, keys that agree modulo the order of R), and then they give the same message;
+ *       *n_hits       (may be NULL) the set bits over all masks; with it the call WAITS for the stream, as n_ok does.
+ *     PM_ERR_BAD_ARG before a byte changes for n_keys outside 1 .. 64, a key not below r, a bad scalar_form or msg_len, a NULL
+ *     or misaligned required pointer.  n = 0 launches nothing: PM_OK, *n_hits = 0.  From "cipher_scan_keys_table_min" keys on
+ *     (pm_set_option) the call builds, once per note, the full window table e 16^w R (w = 0 .. 63, e = 1 .. 8; 73 728 bytes a
+ *     note in flight) and every key then costs at most 64 additions and one inversion, no doubling; below it the single-key
+ *     ladder runs per key.  Either path writes the same bytes, and they depend neither on the scratch budget nor on the stream: S
+ *     is brought to its canonical affine form before it is hashed.  The call allocates pm_poseidon_cipher_scan_keys_work_bytes
+ *     of scratch (PM_ERR_OOM with no output byte written when that fails) and releases them before it returns, which WAITS for
+ *     the device.  The option "cipher_scan_table_mb" caps that scratch: the notes in flight are the largest multiple of 64
+ *     that fits, at least 64; 0 = no cap.  No more hardened against side channels than pm_poseidon_cipher_scan_dev.
  * The two host forms need no context and no GPU (csrc/host_field.h) and take the Hades constants as pm_hades_permute_host does.
  * PM_ERR_BAD_ARG for constants _create refuses, msg_len outside 1 .. 4, NULL, and on encrypt for a secret off the curve or a
  * word that is not below r.  pm_poseidon_cipher_decrypt_host writes the status; inputs it can judge are not errors. */
@@ -1071,6 +1091,13 @@ int pm_poseidon_cipher_decrypt_dev(pm_ctx* ctx, const pm_hades_params* params, c
 int pm_poseidon_cipher_scan_dev(pm_ctx* ctx, const pm_hades_params* params, const uint64_t view_key[4], uint32_t scalar_form,
                                 const void* d_ephemeral_xy, const void* d_nonces, const void* d_ciphers, uint32_t msg_len, size_t n,
                                 void* d_msgs_out, void* d_status, size_t* n_ok, void* hip_stream);
+#define PM_CIPHER_SCAN_MAX_KEYS 64u
+int pm_poseidon_cipher_scan_keys_dev(pm_ctx* ctx, const pm_hades_params* params, const uint64_t* view_keys, uint32_t n_keys,
+                                     uint32_t scalar_form, const void* d_ephemeral_xy, const void* d_nonces, const void* d_ciphers,
+                                     uint32_t msg_len, size_t n, void* d_masks, void* d_msgs_out, void* d_status, size_t* n_hits,
+                                     void* hip_stream);
+/* the scratch that call allocates under the context's options; 0 for arguments it refuses and for n = 0 */
+size_t pm_poseidon_cipher_scan_keys_work_bytes(pm_ctx* ctx, uint32_t n_keys, uint32_t msg_len, size_t n);
 int pm_poseidon_cipher_encrypt_host(uint32_t rounds, uint32_t full_rounds, const uint64_t* ark, const uint64_t* mds, uint32_t n_mds,
                                     const uint64_t secret_xy[8], const uint64_t nonce[4], const uint64_t* msg, uint32_t msg_len,
                                     uint64_t* cipher_out);
@@ -1303,6 +1330,13 @@ int pm_test_cipher_stride(pm_ctx* ctx, size_t* stride);
  * digits with the TOP one first: digits[k] = d_(63 - k), sum d_w 16^w = the integer of the key, every |d_w| <= 8.
  * PM_ERR_BAD_ARG for a key that is not below r, an unknown scalar_form, NULL. */
 int pm_test_cipher_digits(const uint64_t view_key[4], uint32_t scalar_form, int8_t digits[64]);
+/* Pure host, no context: the plan of pm_poseidon_cipher_scan_keys_dev on its full-table path (csrc/cipher_scan_plan.h) for a
+ * GPU of num_cus CUs and the budget table_mb of the option "cipher_scan_table_mb" (0 = no cap): the notes in flight, a multiple
+ * of 64 between 64 and num_cus x 8 x 64 and no more than n rounded up to 64, and the scratch bytes = stride x (73 728 +
+ * n_keys x (64 + 32 msg_len)) + 64 n_keys + 16.  n = 0 gives 0 and 0.  PM_ERR_BAD_ARG for n_keys outside 1 .. 64, msg_len
+ * outside 1 .. 4, a negative budget, NULL. */
+int pm_test_cipher_scan_keys_plan(uint32_t num_cus, uint32_t n_keys, uint32_t msg_len, size_t n, long table_mb, size_t* stride,
+                                  size_t* bytes);
 /* Pure host, no context: the plan of pm_jubjub_msm_dev for n points and `batch` vectors (csrc/jubjub_msm_plan.h); window_bits as
  * the option "jubjub_msm_window_bits" (0 = the rule); num_cus is accepted for symmetry with the other plan hooks and not used:
  * this plan does not depend on the machine.  out[8] = {0 window bits c, 1 windows of a scalar = ceil(257 / c), 2 buckets per

@@ -12,7 +12,7 @@ from .host import (CommitKey, Context, DeviceVector, Error, EvaluationDomain, La
                    msm_variable_base, g1_scalar_mul,
                    g1_fold, g1_to_affine, g1_compress, g1_decompress, domain_info, ntt_plan)
 from . import cipher, field, jubjub, poseidon, prover, schnorr, srs, synthetic, transcript  # noqa: F401,E402
-from .cipher import (CIPHER_REASONS, PoseidonCipher, poseidon_cipher_decrypt_host,  # noqa: F401,E402
+from .cipher import (CIPHER_REASONS, CIPHER_SCAN_MAX_KEYS, PoseidonCipher, poseidon_cipher_decrypt_host,  # noqa: F401,E402
                      poseidon_cipher_encrypt_host)
 from .jubjub import (JUBJUB_CODEC_REASONS, JUBJUB_GENERATOR, JubJubBase, fr_sqrt, fr_sqrt_dev, fr_sqrt_host,  # noqa: F401,E402
                      jubjub_add_host, jubjub_check, jubjub_commit, jubjub_commit_dev, jubjub_compress, jubjub_compress_dev,

@@ -236,6 +236,10 @@ SIGNATURES = {
                                                  C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), C.c_void_p]),
     "pm_poseidon_cipher_scan_dev": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), C.c_void_p]),
+    "pm_poseidon_cipher_scan_keys_dev": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p, C.c_uint32, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.POINTER(C.c_size_t), C.c_void_p]),
+    "pm_poseidon_cipher_scan_keys_work_bytes": (C.c_size_t, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_size_t]),
     "pm_poseidon_cipher_encrypt_host": (C.c_int, [C.c_uint32, C.c_uint32, u64p, u64p, C.c_uint32, u64p, u64p, u64p, C.c_uint32,
                                                   u64p]),
     "pm_poseidon_cipher_decrypt_host": (C.c_int, [C.c_uint32, C.c_uint32, u64p, u64p, C.c_uint32, u64p, u64p, u64p, C.c_uint32,
@@ -286,7 +290,9 @@ SIGNATURES = {
     "pm_test_schnorr_stride": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),
     "pm_test_cipher_stride": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),
     "pm_test_cipher_digits": (C.c_int, [u64p, C.c_uint32, C.POINTER(C.c_int8)]),
-    "pm_test_jubjub_msm_plan": (C.c_int, [C.c_size_t, C.c_uint32, C.c_long, C.c_uint32, u64p]),
+    "pm_test_cipher_scan_keys_plan": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_size_t, C.c_long, C.POINTER(C.c_size_t),
+                                                C.POINTER(C.c_size_t)]),
+    "pm_test_jubjub_msm_plan":(C.c_int, [C.c_size_t, C.c_uint32, C.c_long, C.c_uint32, u64p]),
     "pm_test_jubjub_msm_digits": (C.c_int, [u64p, C.c_uint32, C.POINTER(C.c_int32), u32p]),
     "pm_test_ntt_plan": (C.c_int, [C.c_uint32, C.c_uint32, C.c_long, C.c_long, C.c_long, C.c_uint32, C.POINTER(C.c_uint32)]),
     "pm_test_ntt_exchange_map": (C.c_int, [C.c_uint32] * 5 + [C.POINTER(C.c_uint32)]),
@@ -359,6 +365,7 @@ SCHNORR_REASONS = {1: "u_range", 2: "r_point", 3: "pk_point", 4: "equation"}
 CIPHER_OK, CIPHER_POINT, CIPHER_RANGE, CIPHER_TAG = 0, 1, 2, 3
 CIPHER_REASONS = {1: "point", 2: "range", 3: "tag"}
 CIPHER_MAX_LEN = 4            # message words of a cipher: the rate of the width-5 permutation
+CIPHER_SCAN_MAX_KEYS = 64     # PM_CIPHER_SCAN_MAX_KEYS: viewing keys of one pm_poseidon_cipher_scan_keys_dev, a bit of the mask each
 # pm_jubjub_decompress*: the flag, and the status of a point, the lowest that applies
 JUBJUB_CHECK_SUBGROUP = 1
 JUBJUB_OK, JUBJUB_BAD_RANGE, JUBJUB_BAD_NOT_ON_CURVE, JUBJUB_BAD_SIGN, JUBJUB_BAD_NOT_IN_SUBGROUP = 0, 1, 2, 3, 4

@@ -1,6 +1,6 @@
 """The Poseidon cipher on JubJub keys (``pm_poseidon_cipher_*``): batch encryption and decryption of
 notes on the GPU, and the recipient's side of a private ledger -- :meth:`PoseidonCipher.scan`, the trial decryption of every
-note under one viewing key.
+note under one viewing key, and :meth:`PoseidonCipher.scan_keys`, under up to 64 of them in one call (section 7.2q).
 
 With ``P`` the Hades permutation, ``L`` the message capacity (1 .. 4) and ``S`` a JubJub point, the shared secret::
 
@@ -31,6 +31,7 @@ from .jubjub import JubJubBase, _encodings, _points, _scalars, jubjub_decompress
 from .poseidon import WIDTH, Hades, _elements
 
 CIPHER_REASONS = _lib.CIPHER_REASONS
+CIPHER_SCAN_MAX_KEYS = _lib.CIPHER_SCAN_MAX_KEYS
 
 
 def _check_len(msg_len) -> int:
@@ -74,6 +75,19 @@ def _nonces(x) -> np.ndarray:
     if isinstance(x, np.ndarray) and x.dtype != np.uint64 and x.dtype != object:
         raise ValueError("nonces: limb arrays are uint64")
     return _elements(x)
+
+
+def _view_keys(x):
+    """1 .. 64 viewing keys, integers or ``[K, 4]`` Montgomery limbs (``[4]`` is one key) -> ([K, 4] uint64, scalar_form)"""
+    if isinstance(x, np.ndarray) and x.dtype == np.uint64:
+        if x.ndim not in (1, 2) or x.shape[-1] != 4:
+            raise ValueError("viewing keys: limbs have the shape [K, 4]")
+    elif np.asarray(x, dtype=object).ndim > 1:
+        raise ValueError("viewing keys: integers have the shape [K]")
+    vk, form = _scalars(x)
+    if not 1 <= vk.shape[0] <= CIPHER_SCAN_MAX_KEYS:
+        raise ValueError(f"1 .. {CIPHER_SCAN_MAX_KEYS} viewing keys a call")
+    return vk, form
 
 
 def _host_consts(ark, mds, rounds):
@@ -233,6 +247,62 @@ class PoseidonCipher:
         form = form if scalar_form is None else scalar_form
         return self._open(_encodings(ephemeral_bytes), nonces, ciphers,
                           lambda *a: self.scan_dev(vk, *a, want_n_ok=False, scalar_form=form), decode=bool(check_subgroup))
+
+    # ------------------------------------------------------------------ many viewing keys in one scan
+    def scan_keys_dev(self, view_keys, d_ephemeral: int, d_nonces: int, d_ciphers: int, n: int, d_masks: int, d_msgs: int = 0,
+                      d_status: int = 0, want_n_hits: bool = True, scalar_form: int | None = None, stream: int = 0):
+        """``pm_poseidon_cipher_scan_keys_dev``: the n notes under 1 .. 64 viewing keys in one call.  ``d_masks`` receives n
+        ``uint64``: bit k is set exactly when :meth:`scan_dev` under ``view_keys[k]`` gives note i the status 0.  ``d_msgs``
+        (0 = not wanted) receives the message of the LOWEST key that opens the note, zeros where none does; ``d_status`` (0 =
+        not wanted) 1 or 2 as :meth:`scan_dev` reports them, else 0 where a key opens the note, else 3.  Returns the number of
+        set bits, or None when ``want_n_hits`` is false.  Waits for the device.  Not hardened against side channels."""
+        vk, form = _view_keys(view_keys)
+        c = self.ctx
+        hits = C.c_size_t()
+        c._check(c._lib.pm_poseidon_cipher_scan_keys_dev(c._h, self.hades._h, _p(vk), vk.shape[0], form if scalar_form is None else scalar_form,
+                                                         C.c_void_p(d_ephemeral), C.c_void_p(d_nonces), C.c_void_p(d_ciphers),
+                                                         self.msg_len, n, C.c_void_p(d_masks), C.c_void_p(d_msgs) if d_msgs else None,
+                                                         C.c_void_p(d_status) if d_status else None,
+                                                         C.byref(hits) if want_n_hits else None, C.c_void_p(stream)))
+        return int(hits.value) if want_n_hits else None
+
+    def _scan_keys(self, view_keys, first, nonces, ciphers, scalar_form, decode=None):
+        """:meth:`_open` with the masks in front: -> (masks, messages, status)"""
+        vk, form = _view_keys(view_keys)
+        form = form if scalar_form is None else scalar_form
+        n, masks = first.shape[0], []
+
+        def call(dp, dk, dc, n, dm, ds):
+            d_masks = DeviceVector(self.ctx, (n + 3) // 4)     # n uint64 in 32-byte elements
+            try:
+                self.scan_keys_dev(vk, dp, dk, dc, n, d_masks.ptr, dm, ds, want_n_hits=False, scalar_form=form)
+                masks.append(d_masks.to_host().reshape(-1)[:n].copy())
+            finally:
+                d_masks.free()
+
+        msgs, status = self._open(first, nonces, ciphers, call, decode)
+        return (masks[0] if n else np.zeros(0, np.uint64)), msgs, status
+
+    def scan_keys(self, view_keys, ephemeral_keys, nonces, ciphers, scalar_form: int | None = None):
+        """The notes ``(R_i, nonce_i, c_i)`` under 1 .. 64 viewing keys in one call -> ``(masks [n] uint64, messages [n, L, 4],
+        status [n] uint32)``: bit k of ``masks[i]`` is set exactly when :meth:`scan` under ``view_keys[k]`` gives note i the
+        status 0; the message is that of the LOWEST such key -- two keys open one note only when they give the same secret, and
+        then the same message -- and zero where there is none; the status is 1 or 2 where :meth:`scan` reports them (they depend
+        on the note alone), else 0 where the mask is not zero, else 3.  ``view_keys``: integers or ``[K, 4]`` Montgomery limbs;
+        duplicates and 0 are legal.  :meth:`hits` lists the (note, key) pairs."""
+        return self._scan_keys(view_keys, _points(ephemeral_keys), nonces, ciphers, scalar_form)
+
+    def scan_keys_bytes(self, view_keys, ephemeral_bytes, nonces, ciphers, check_subgroup: bool = False, scalar_form: int | None = None):
+        """:meth:`scan_keys` for ephemeral keys as a ledger stores them, ``uint8 [n, 32]``, decoded on the device as
+        :meth:`scan_bytes` does: a key that does not decode comes back with mask 0, status 1 and zero messages."""
+        return self._scan_keys(view_keys, _encodings(ephemeral_bytes), nonces, ciphers, scalar_form, decode=bool(check_subgroup))
+
+    @staticmethod
+    def hits(masks) -> np.ndarray:
+        """the masks of :meth:`scan_keys` -> ``[h, 2]`` ``int64`` (note, key) pairs, ascending by note, then by key"""
+        m = np.ascontiguousarray(masks, dtype=np.uint64).reshape(-1)
+        bits = (m[:, None] >> np.arange(64, dtype=np.uint64)[None, :]) & np.uint64(1)
+        return np.argwhere(bits != 0).astype(np.int64).reshape(-1, 2)
 
     def encrypt_to(self, g: JubJubBase, public_keys, ephemeral_secrets, nonces, messages):
         """The sender's side, composed from ``g.mul``, :func:`~.jubjub.jubjub_mul` and :meth:`encrypt`: note i is encrypted to

@@ -279,6 +279,17 @@ extern "C" int pm_set_option(pm_ctx* ctx, const char* key, long value) {
     ctx->opt_jubjub_msm_window_bits = value;
     return PM_OK;
   }
+  if (!strcmp(key, "cipher_scan_table_mb")) {
+    if (value < 0 || value > (1L << 20)) return set_err(ctx, PM_ERR_BAD_ARG, "cipher_scan_table_mb must be 0 (no cap) .. 2^20");
+    ctx->opt_cipher_scan_table_mb = value;
+    return PM_OK;
+  }
+  if (!strcmp(key, "cipher_scan_keys_table_min")) {
+    if (value < 0 || value > (long)PM_CIPHER_SCAN_MAX_KEYS + 1)
+      return set_err(ctx, PM_ERR_BAD_ARG, "cipher_scan_keys_table_min must be 0 (the default), 1 (always the table) .. 65 (never)");
+    ctx->opt_cipher_scan_keys_table_min = value;
+    return PM_OK;
+  }
   if (!strcmp(key, "msm_chunk")) {
     if (value < 0 || value > 4096) return set_err(ctx, PM_ERR_BAD_ARG, "msm_chunk out of range");
     ctx->opt_msm_chunk = value;

@@ -13,6 +13,8 @@
 //            only), ONE inversion -- S is hashed, so it has to be affine -- and S into the thread's slot.  Then the decrypt
 //            kernel with S from the slot and its point test on R.  The ladder keeps the register budget jubjub_var_kernel
 //            has (two waves a SIMD) and the permutations their own.
+//   scan under K keys (section 7.2q, further down): the window table e 16^w R of a note built once, a walk of at most 64
+//            additions and one inversion per (note, key), the same decryption, a mask of K bits a note.
 //
 // Every thread of a scan multiplies by the SAME scalar: the 64 signed digits of vk are recoded once on the host and travel by
 // value in the kernel's arguments, top first.  Digit w is read at a wave-uniform index, so it lives in a scalar register: its
@@ -31,6 +33,7 @@
 #include <algorithm>
 #include <string>
 
+#include "cipher_scan_plan.h"
 #include "context.h"
 #include "field_inv.hip.h"
 #include "hades.hip.h"
@@ -70,7 +73,8 @@ struct CipherIo {
 };
 struct CipherScanIo {
   const u32x4* points;      // n x (x | y): the ephemeral keys
-  u32x4* scratch;           // [entry][chunk][thread of the grid], then a secret (x | y) a thread
+  u32x4* scratch;           // the tables: [entry][chunk][thread of the grid]
+  u32x4* secrets;           // a secret (x | y) a thread of the grid: behind the tables, or a key's row of slots (scan_keys)
   size_t n;
   u32 edwards_d[9];         // device form
   u32 digits[JJ_WINDOWS / 4];       // of the viewing key: recode_digit_words (jubjub.hip.h)
@@ -112,31 +116,36 @@ __global__ void __launch_bounds__(64) cipher_encrypt_kernel(const HadesTab tab, 
   if (live) st_canon(a.out, (a.len + 1) * i + a.len, g_to_abi(s[1]));
 }
 
-// SCAN: the secret is what the ladder left in the thread's slot and the point test judges the ephemeral key
+// the nonce and the len + 1 cipher words at ct are below r
+PM_DEV bool cph_range_ok(const u32x4* nonce, const u32x4* ct, u32 len) {
+  bool ok = jj_below_r(nonce[0], nonce[1]);
+#pragma unroll
+  for (u32 j = 0; j <= CPH_MAX_LEN; ++j)
+    if (j <= len) ok = ok && jj_below_r(ct[2 * j], ct[2 * j + 1]);   // uniform
+  return ok;
+}
+// The decryption of note i: the messages, packed, into m -- as computed, whatever the verdict -- and the status returned.
+// SCAN: the secret is the (x | y) at `secret`, what a ladder or a walk left in a slot, and the point test judges the ephemeral
+// key at a.tested; otherwise the secret is that point itself.
 template <bool SCAN>
-__global__ void __launch_bounds__(64) cipher_decrypt_kernel(const HadesTab tab, const CipherIo a) {
-  const size_t g = (size_t)blockIdx.x * 64 + threadIdx.x;
-  const bool live = g < a.n;
-  const size_t i = live ? g : a.n - 1;
+PM_DEV u32 cph_open(const HadesTab& tab, const CipherIo& a, size_t i, const u32x4* secret, u32 (&m)[CPH_MAX_LEN][8]) {
   const Fr zero = fe_zero<FrP>();
   const u32x4* const ct = a.in + 2 * (size_t)(a.len + 1) * i;
   Fr s[5];
-  bool point_ok, range_ok;
+  bool point_ok;
   {
     Fr x, y;
     point_ok = jj_point_ok(a.tested + 4 * i, fr_limbs(a.edwards_d), x, y);
-    if (SCAN) x = g_to_dev(ld_canon(a.secrets, 2 * i)), y = g_to_dev(ld_canon(a.secrets, 2 * i + 1));
-    range_ok = jj_below_r(a.nonces[2 * i], a.nonces[2 * i + 1]);
+    if (SCAN) x = g_to_dev(ld_canon(secret, 0)), y = g_to_dev(ld_canon(secret, 1));
     cph_init(s, x, y, g_to_dev(ld_canon(a.nonces, i)), a, tab);
   }
+  const bool range_ok = cph_range_ok(a.nonces + 2 * i, ct, a.len);
   h_rounds_thread(s, tab);
   // the messages wait, packed, for the verdict of the tag
-  u32 m[CPH_MAX_LEN][8];
   s[0] = h_absorb(s[0], zero, tab.ark);
 #pragma unroll
   for (u32 j = 0; j < CPH_MAX_LEN; ++j) {
     if (j < a.len) {                                         // uniform
-      range_ok = range_ok && jj_below_r(ct[2 * j], ct[2 * j + 1]);
       const Fr c = g_to_dev(ld_canon(ct, j));
       fe_canon_pack<FrP>(m[j], g_to_abi(gsub(c, fe_reduce_weak<FrP>(s[1 + j]))));   // gsub takes a normalised subtrahend
       s[1 + j] = h_absorb(c, zero, tab.ark + 9 * (1 + j));
@@ -148,12 +157,21 @@ __global__ void __launch_bounds__(64) cipher_decrypt_kernel(const HadesTab tab, 
   }
   h_rounds_thread(s, tab);
   const u32x4 t0 = ct[2 * a.len], t1 = ct[2 * a.len + 1];
-  range_ok = range_ok && jj_below_r(t0, t1);
   u32 tag[8];
   fe_canon_pack<FrP>(tag, g_to_abi(s[1]));
   const u32 diff = (tag[0] ^ t0.x) | (tag[1] ^ t0.y) | (tag[2] ^ t0.z) | (tag[3] ^ t0.w) | (tag[4] ^ t1.x) | (tag[5] ^ t1.y) |
                    (tag[6] ^ t1.z) | (tag[7] ^ t1.w);
-  const u32 status = !point_ok ? PM_CIPHER_POINT : !range_ok ? PM_CIPHER_RANGE : diff != 0 ? PM_CIPHER_TAG : PM_CIPHER_OK;
+  return !point_ok ? PM_CIPHER_POINT : !range_ok ? PM_CIPHER_RANGE : diff != 0 ? PM_CIPHER_TAG : PM_CIPHER_OK;
+}
+
+// SCAN: the secret is what the ladder left in the thread's slot and the point test judges the ephemeral key
+template <bool SCAN>
+__global__ void __launch_bounds__(64) cipher_decrypt_kernel(const HadesTab tab, const CipherIo a) {
+  const size_t g = (size_t)blockIdx.x * 64 + threadIdx.x;
+  const bool live = g < a.n;
+  const size_t i = live ? g : a.n - 1;
+  u32 m[CPH_MAX_LEN][8];
+  const u32 status = cph_open<SCAN>(tab, a, i, a.secrets + 4 * i, m);
   const u32 keep = status == PM_CIPHER_OK ? ~0u : 0u;       // a mask, not a select between vectors (that one goes through scratch)
   if (a.n_ok) {
     const unsigned long long hits = __ballot(live && status == PM_CIPHER_OK);
@@ -184,9 +202,100 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2)))
   const EdPoint acc = jj_ladder_uniform(tbl, T, a.digits, ed);
   // ---- S = (X / Z, Y / Z) into the slot of this thread, live or not: the slots are per thread of the grid
   const Fr zi = g_to_abi(fe_inv_dev<FrP>(acc.Z));           // every lane of the wave is here
-  u32x4* const out = a.scratch + (size_t)8 * JJ_POINT_CHUNKS * T + 4 * tid;
+  u32x4* const out = a.secrets + 4 * tid;
   st_canon(out, 0, gmul(acc.X, zi));                         // device x ABI -> ABI
   st_canon(out, 1, gmul(acc.Y, zi));
+}
+
+// ------------------------------------------------------------------ many viewing keys in one scan
+// Per stride of notes in flight: BUILD, a thread a note, writes the window table e 16^w R_i of jj_window_table_build; WALK, the
+// grid over (notes of the stride) x keys with one key a workgroup, adds at most 64 of its entries under the key's digits, inverts
+// once and leaves S = vk_k R_i, canonical, in the slot [key][thread]; OPEN, the same grid, decrypts (note, key) with cph_open
+// and, on a hit, sets bit `key` of the note's mask and leaves the message in the staging slot [key][thread][L]; EMIT, a thread a
+// note, writes the status, the lowest set key's message or zeros, and adds the hits.  Below `cipher_scan_keys_table_min` keys
+// the ladder kernel above fills the slots key by key in place of BUILD and WALK; OPEN and EMIT are the same.
+struct CipherKeysIo {
+  const u32x4* points;      // the stride's ephemeral keys
+  u32x4* table;             // [entry 8 w + e - 1][chunk][thread of the stride]
+  u32x4* secrets;           // [key][thread] x (x | y)
+  u32x4* staging;           // [key][thread][len] messages of the hits
+  const u32* digits;        // [key][JJ_WINDOWS / 4]: recode_digit_words
+  unsigned long long* masks;   // the stride's
+  u32x4* out;               // the stride's messages, or null
+  u32* status;              // the stride's, or null
+  unsigned long long* n_hits;  // or null
+  size_t n, T;              // notes of this stride; the notes in flight, what the scratch is laid out for
+  u32 edwards_d[9];         // device form
+};
+
+// Two waves a SIMD: 512 registers hold B, 2 B, 4 B and the point in the making without scratch
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) cipher_keys_build_kernel(const CipherKeysIo a) {
+  const size_t T = a.T, tid = (size_t)blockIdx.x * 64 + threadIdx.x;
+  const size_t i = tid < a.n ? tid : a.n - 1;
+  jj_window_table_build(a.table + tid, T, g_to_dev(ld_canon(a.points, 2 * i)), g_to_dev(ld_canon(a.points, 2 * i + 1)),
+                        fr_limbs(a.edwards_d));
+}
+
+// blockIdx.y = the key.  Two waves a SIMD: the inversion's register budget, as the ladder.
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 2))) cipher_keys_walk_kernel(const CipherKeysIo a) {
+  const size_t T = a.T, tid = (size_t)blockIdx.x * 64 + threadIdx.x;
+  const u32 key = blockIdx.y;
+  const EdPoint acc = jj_window_walk(a.table + tid, T, a.digits + (size_t)key * (JJ_WINDOWS / 4), fr_limbs(a.edwards_d));
+  const Fr zi = g_to_abi(fe_inv_dev<FrP>(acc.Z));           // every lane of the wave is here
+  u32x4* const out = a.secrets + 4 * ((size_t)key * T + tid);
+  st_canon(out, 0, gmul(acc.X, zi));                         // device x ABI -> ABI
+  st_canon(out, 1, gmul(acc.Y, zi));
+}
+
+// blockIdx.y = the key; c.tested, c.nonces and c.in are the stride's.  A hit sets its bit by an atomic OR, whose result does not
+// depend on the order of the keys, and nothing else is written per key but the message of a hit.
+__global__ void __launch_bounds__(64) cipher_keys_open_kernel(const HadesTab tab, const CipherIo c, const CipherKeysIo a) {
+  const size_t T = a.T, tid = (size_t)blockIdx.x * 64 + threadIdx.x;
+  const u32 key = blockIdx.y;
+  const bool live = tid < a.n;
+  const size_t i = live ? tid : a.n - 1, slot = (size_t)key * T + tid;
+  u32 m[CPH_MAX_LEN][8];
+  const u32 status = cph_open<true>(tab, c, i, a.secrets + 4 * slot, m);
+  if (!live || status != PM_CIPHER_OK) return;
+  atomicOr(a.masks + i, 1ull << key);
+#pragma unroll
+  for (u32 j = 0; j < CPH_MAX_LEN; ++j) {
+    if (j < c.len) {
+      u32x4* const q = a.staging + 2 * (slot * c.len + j);
+      q[0] = u32x4{m[j][0], m[j][1], m[j][2], m[j][3]};
+      q[1] = u32x4{m[j][4], m[j][5], m[j][6], m[j][7]};
+    }
+  }
+}
+
+// a thread a note: what depends on the note alone (the point test of R, the ranges), the mask, the lowest key's message
+__global__ void __launch_bounds__(64) cipher_keys_emit_kernel(const CipherIo c, const CipherKeysIo a) {
+  const size_t T = a.T, tid = (size_t)blockIdx.x * 64 + threadIdx.x;
+  const bool live = tid < a.n;
+  const size_t i = live ? tid : a.n - 1;
+  Fr x, y;
+  const bool point_ok = jj_point_ok(c.tested + 4 * i, fr_limbs(a.edwards_d), x, y);
+  const bool range_ok = cph_range_ok(c.nonces + 2 * i, c.in + 2 * (size_t)(c.len + 1) * i, c.len);
+  const unsigned long long mask = live ? a.masks[i] : 0ull;
+  if (a.n_hits) {
+    u32 hits = (u32)__popcll(mask);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) hits += __shfl_xor(hits, off);
+    if (threadIdx.x == 0 && hits) atomicAdd(a.n_hits, (unsigned long long)hits);
+  }
+  if (!live) return;
+  if (a.status) a.status[i] = !point_ok ? PM_CIPHER_POINT : !range_ok ? PM_CIPHER_RANGE : mask ? PM_CIPHER_OK : PM_CIPHER_TAG;
+  if (!a.out) return;
+  const u32 key = mask ? (u32)__ffsll((long long)mask) - 1 : 0;
+  const u32x4* const from = a.staging + 2 * (((size_t)key * T + tid) * c.len);
+  const u32 keep = mask ? ~0u : 0u;                          // a mask, not a select between vectors, as in the decryption
+#pragma unroll
+  for (u32 j = 0; j < 2 * CPH_MAX_LEN; ++j) {
+    if (j < 2 * c.len) {
+      const u32x4 v = from[j];
+      a.out[2 * (size_t)c.len * i + j] = u32x4{v.x & keep, v.y & keep, v.z & keep, v.w & keep};
+    }
+  }
 }
 
 // ------------------------------------------------------------------ launches
@@ -280,10 +389,11 @@ extern "C" int pm_poseidon_cipher_scan_dev(pm_ctx* ctx, const pm_hades_params* p
   unsigned long long* const d_ok = scratch.tail();
   CipherScanIo l{};
   l.scratch = scratch.slots();
+  l.secrets = l.scratch + (size_t)8 * JJ_POINT_CHUNKS * stride;
   jubjub_d_limbs(l.edwards_d);
   recode_digit_words(vk, l.digits);
   CipherIo a{};
-  a.secrets = l.scratch + (size_t)8 * JJ_POINT_CHUNKS * stride, a.n_ok = n_ok ? d_ok : nullptr;
+  a.secrets = l.secrets, a.n_ok = n_ok ? d_ok : nullptr;
   io_consts(a, msg_len);
   const HadesTab tab = tab_of(params);
   hipError_t e = n_ok ? hipMemsetAsync(d_ok, 0, 16, st) : hipSuccess;
@@ -300,6 +410,107 @@ extern "C" int pm_poseidon_cipher_scan_dev(pm_ctx* ctx, const pm_hades_params* p
     }
   }
   return finish(ctx, e, st, scratch.base, d_ok, n_ok, "pm_poseidon_cipher_scan_dev");
+}
+
+// the plan of a scan under n_keys keys with the context's options: the full table from cipher_scan_keys_table_min keys on
+static int scan_keys_plan(const pm_ctx* ctx, uint32_t n_keys, uint32_t msg_len, size_t n, bool* full_table, CipherScanKeysPlan* p) {
+  const long table_min = ctx->opt_cipher_scan_keys_table_min ? ctx->opt_cipher_scan_keys_table_min : PM_CIPHER_SCAN_KEYS_TABLE_MIN;
+  *full_table = (long)n_keys >= table_min;
+  return cipher_scan_keys_plan(ctx->num_cus, n_keys, msg_len, n, ctx->opt_cipher_scan_table_mb, *full_table, p);
+}
+
+extern "C" size_t pm_poseidon_cipher_scan_keys_work_bytes(pm_ctx* ctx, uint32_t n_keys, uint32_t msg_len, size_t n) {
+  if (!ctx || n > 0x7fffffffu) return 0;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  bool full_table;
+  CipherScanKeysPlan plan{};
+  return scan_keys_plan(ctx, n_keys, msg_len, n, &full_table, &plan) == PM_OK ? plan.bytes : 0;
+}
+
+extern "C" int pm_poseidon_cipher_scan_keys_dev(pm_ctx* ctx, const pm_hades_params* params, const uint64_t* view_keys,
+                                                uint32_t n_keys, uint32_t scalar_form, const void* d_ephemeral_xy,
+                                                const void* d_nonces, const void* d_ciphers, uint32_t msg_len, size_t n,
+                                                void* d_masks, void* d_msgs_out, void* d_status, size_t* n_hits, void* hip_stream) {
+  if (!ctx) return PM_ERR_BAD_ARG;
+  if (int rc = common_fault(ctx, params, msg_len)) return rc;
+  if (int rc = form_fault(ctx, scalar_form)) return rc;
+  if (n_keys < 1 || n_keys > PM_CIPHER_SCAN_MAX_KEYS) return set_err(ctx, PM_ERR_BAD_ARG, "n_keys must be 1 .. 64");
+  if (!view_keys) return set_err(ctx, PM_ERR_BAD_ARG, "the viewing keys are null");
+  u32 digits[PM_CIPHER_SCAN_MAX_KEYS][JJ_WINDOWS / 4];      // lives until finish() has waited for the device
+  for (uint32_t k = 0; k < n_keys; ++k) {
+    uint64_t vk[4];
+    if (!scalar_to_int(view_keys + 4 * k, scalar_form, vk)) return set_err(ctx, PM_ERR_BAD_ARG, "a viewing key is not below r");
+    recode_digit_words(vk, digits[k]);
+  }
+  if (int rc = pointer_fault(ctx, {d_ephemeral_xy, d_nonces, d_ciphers, d_masks}, unaligned({d_msgs_out}) || ((uintptr_t)d_status & 3u) != 0))
+    return rc;
+  if (int rc = count_fault(ctx, n)) return rc;
+  if (n_hits) *n_hits = 0;
+  if (n == 0) return PM_OK;
+  PM_ENTER(ctx, hip_stream, st);
+  bool full_table;
+  CipherScanKeysPlan plan{};
+  if (int rc = scan_keys_plan(ctx, n_keys, msg_len, n, &full_table, &plan)) return set_err(ctx, rc, "pm_poseidon_cipher_scan_keys_dev: no plan");
+  char* base = nullptr;
+  PM_HIP(ctx, hipMalloc((void**)&base, plan.bytes));         // PM_ERR_OOM before an output byte is written
+  const size_t stride = plan.stride;
+  CipherKeysIo k{};
+  k.table = (u32x4*)base, k.secrets = (u32x4*)(base + plan.off_secrets), k.staging = (u32x4*)(base + plan.off_staging);
+  k.digits = (const u32*)(base + plan.off_digits), k.T = stride;
+  unsigned long long* const d_hits = (unsigned long long*)(base + plan.off_count);
+  k.n_hits = n_hits ? d_hits : nullptr;
+  jubjub_d_limbs(k.edwards_d);
+  CipherScanIo l{};                                          // the per-key path: one table 1 R .. 8 R a thread, shared by the keys in turn
+  l.scratch = k.table;
+  jubjub_d_limbs(l.edwards_d);
+  CipherIo a{};
+  io_consts(a, msg_len);
+  const HadesTab tab = tab_of(params);
+  hipError_t e = hipMemcpyAsync(base + plan.off_digits, digits, CSK_DIGIT_BYTES * n_keys, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemsetAsync(d_hits, 0, CSK_COUNT_BYTES, st);
+  if (e == hipSuccess) e = hipMemsetAsync(d_masks, 0, 8 * n, st);
+  for (size_t off = 0; off < n && e == hipSuccess; off += stride) {   // a stride is emitted before the next one reuses the scratch
+    k.n = l.n = a.n = std::min(stride, n - off);
+    const dim3 notes((unsigned)((k.n + 63) / 64)), pairs(notes.x, n_keys);
+    k.points = l.points = a.tested = (const u32x4*)d_ephemeral_xy + 4 * off;
+    a.nonces = (const u32x4*)d_nonces + 2 * off, a.in = (const u32x4*)d_ciphers + 2 * (size_t)(msg_len + 1) * off;
+    k.masks = (unsigned long long*)d_masks + off;
+    k.out = d_msgs_out ? (u32x4*)d_msgs_out + 2 * (size_t)msg_len * off : nullptr;
+    k.status = d_status ? (u32*)d_status + off : nullptr;
+    if (full_table) {
+      {
+        ProfScope prof(ctx, st, "poseidon_cipher_scan_keys_build");
+        hipLaunchKernelGGL(cipher_keys_build_kernel, notes, dim3(64), 0, st, k);
+      }
+      ProfScope prof(ctx, st, "poseidon_cipher_scan_keys_walk");
+      hipLaunchKernelGGL(cipher_keys_walk_kernel, pairs, dim3(64), 0, st, k);
+    } else {
+      ProfScope prof(ctx, st, "poseidon_cipher_scan_keys_ladder");
+      for (uint32_t j = 0; j < n_keys; ++j) {                // the ladder's table layout follows ITS grid: every launch the stride's
+        l.secrets = k.secrets + 4 * (size_t)j * stride;
+        memcpy(l.digits, digits[j], sizeof l.digits);
+        hipLaunchKernelGGL(cipher_scan_ladder_kernel, dim3((unsigned)plan.blocks), dim3(64), 0, st, l);
+      }
+    }
+    {
+      ProfScope prof(ctx, st, "poseidon_cipher_scan_keys_open");
+      hipLaunchKernelGGL(cipher_keys_open_kernel, pairs, dim3(64), 0, st, tab, a, k);
+    }
+    ProfScope prof(ctx, st, "poseidon_cipher_scan_keys_emit");
+    hipLaunchKernelGGL(cipher_keys_emit_kernel, notes, dim3(64), 0, st, a, k);
+    e = hipGetLastError();
+  }
+  return finish(ctx, e, st, base, d_hits, n_hits, "pm_poseidon_cipher_scan_keys_dev");
+}
+
+extern "C" int pm_test_cipher_scan_keys_plan(uint32_t num_cus, uint32_t n_keys, uint32_t msg_len, size_t n, long table_mb,
+                                             size_t* stride, size_t* bytes) {
+  if (!stride || !bytes) return PM_ERR_BAD_ARG;
+  CipherScanKeysPlan plan{};
+  *stride = *bytes = 0;
+  if (int rc = cipher_scan_keys_plan((int)num_cus, n_keys, msg_len, n, table_mb, true, &plan)) return rc;
+  *stride = plan.stride, *bytes = plan.bytes;
+  return PM_OK;
 }
 
 extern "C" int pm_poseidon_cipher_encrypt_host(uint32_t rounds, uint32_t full_rounds, const uint64_t* ark, const uint64_t* mds,

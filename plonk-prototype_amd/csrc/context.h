@@ -20,10 +20,15 @@
 #ifndef PM_NTT_FIXED_SHAPE_DEFAULT
 #define PM_NTT_FIXED_SHAPE_DEFAULT 1
 #endif
+// pm_poseidon_cipher_scan_keys_dev (DESIGN.md section 7.2q has the measurement both rest on): the keys from which the call
+// builds the full window table of a note, below it the single-key ladder runs per key ...
+#define PM_CIPHER_SCAN_KEYS_TABLE_MIN 4
+// ... and the default of the option cipher_scan_table_mb, the cap on its scratch in MiB (0 = none)
+#define PM_CIPHER_SCAN_TABLE_MB_DEFAULT 0
 
 namespace pm {
 
-class ExchangeWatch;                                    // comm.hip
+class ExchangeWatch;                                   // comm.hip
 void exchange_watch_free(ExchangeWatch* w);
 
 struct DeviceBuffer {
@@ -135,7 +140,9 @@ struct pm_ctx {
   long opt_binv_quads = 0;       // batch inversion: quads (4 elements) per thread and inversion; 0 = auto
   long opt_poly_lookback = 1;    // prefix product in one pass (decoupled look-back) instead of totals / scan / replay
   long opt_jubjub_msm_window_bits = 0;   // 0 = the rule of jubjub_msm_plan.h
-  long opt_msm_pipeline = 0;     // 1: a batched MSM runs as up to four pieces on two streams (measured: loses, see msm.hip)
+  long opt_cipher_scan_table_mb = PM_CIPHER_SCAN_TABLE_MB_DEFAULT;   // pm_poseidon_cipher_scan_keys_dev: its scratch in MiB at the most; 0 = no cap
+  long opt_cipher_scan_keys_table_min = 0;   // ... and the keys from which it builds the full window table; 0 = PM_CIPHER_SCAN_KEYS_TABLE_MIN
+  long opt_msm_pipeline = 0;    // 1: a batched MSM runs as up to four pieces on two streams (measured: loses, see msm.hip)
   int num_cus = 256;
 };
 

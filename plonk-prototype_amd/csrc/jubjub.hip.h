@@ -321,6 +321,51 @@ PM_DEV EdPoint jj_ladder_uniform(const u32x4* tbl, size_t T, const u32 (&digits)
   }
   return acc;
 }
+// MANY scalars into the same point (the viewing keys of pm_poseidon_cipher_scan_keys_dev): the window table pm_jubjub_base keeps
+// for a fixed base, built per thread for its own point -- entry 8 w + e - 1 = e 16^w P, w = 0 .. 63, e = 1 .. 8, X Y Z T in the
+// layout of jj_table_store -- so that a scalar costs additions only and the doublings are paid once.  A window by five doublings
+// and three additions: an even entry e B = 2 (e / 2 B) from the entry the thread stored itself, an odd one (e - 1) B + B, then
+// 16 B = 2 (8 B), the next window's B.  The entries are made in a rolled loop, one formula each turn under a uniform branch:
+// written out, the eight of a window are independent enough for the scheduler to hold most of them at once (4628 bytes of
+// scratch a lane).  B is invariant in that loop; it is read back from entry 1 each odd turn, which keeps it out of the
+// registers and, as jj_opaque does for jj_table_build, out of the optimiser's sight.
+PM_DEV void jj_window_table_build(u32x4* tbl, size_t T, const Fr& px, const Fr& py, const Fr& ed) {
+  EdPoint b{px, py, fe_one<FrP>(), gmul(px, py)};
+#pragma unroll 1
+  for (u32 w = 0; w < JJ_WINDOWS; ++w) {
+    u32x4* const win = tbl + (size_t)w * 8 * JJ_POINT_CHUNKS * T;
+    jj_table_store(win, T, 1, b);
+    EdPoint acc = b;
+#pragma unroll 1
+    for (u32 e = 2; e <= 8; ++e) {
+      const EdPoint q = jj_table_load(win, T, (e & 1u) ? 1u : e >> 1);   // B or e / 2 B: no second copy of B in registers
+      if (e & 1u)                                            // uniform
+        acc = ed_add(acc, q, ed);
+      else
+        acc = ed_double<true>(q);
+      jj_table_store(win, T, e, acc);
+    }
+    b = ed_double<true>(acc);
+  }
+}
+// k P over that table: 64 additions at the most, no doubling.  `digits`: the words of recode_digit_words in device memory, read
+// at an address that is the same in every lane of the workgroup, so a digit, its sign and the zero test stay scalar as in
+// jj_ladder_uniform.  The top digit comes first there; the order of a sum is free and the walk goes from window 0 up.
+PM_DEV EdPoint jj_window_walk(const u32x4* tbl, size_t T, const u32* __restrict__ digits, const Fr& ed) {
+  EdPoint acc = jj_neutral();
+#pragma unroll 1
+  for (u32 w = 0; w < JJ_WINDOWS; ++w) {
+    const u32 at = JJ_WINDOWS - 1 - w;
+    const int d = (int)(signed char)(digits[at >> 2] >> (8 * (at & 3u)));
+    if (d != 0) {                                            // uniform: a zero digit adds nothing
+      const u32 mag = (u32)(d < 0 ? -d : d), e = mag > 8u ? 8u : mag;
+      EdPoint q = jj_table_load(tbl + (size_t)w * 8 * JJ_POINT_CHUNKS * T, T, e);
+      if (d < 0) q.X = gneg(q.X), q.T = gneg(q.T);           // uniform
+      acc = ed_add(acc, q, ed);
+    }
+  }
+  return acc;
+}
 // the words of r, most significant first
 constexpr u32 JJ_R_WORDS[8] = {0x73eda753u, 0x299d7d48u, 0x3339d808u, 0x09a1d805u, 0x53bda402u, 0xfffe5bfeu, 0xffffffffu, 0x00000001u};
 PM_DEV bool jj_below_r(const u32x4& lo, const u32x4& hi) {
