@@ -1272,10 +1272,10 @@ int pm_ntt_plan(uint32_t log_n, uint32_t radix_log2[4], uint32_t* n_passes);
  * pass's inter-pass twiddle table, so that pass starts on its data alone; 0: every pass multiplies its own inputs.  Same results either way;
  * it needs "ntt_direct_tw" = 1), "ntt_step_prio" (1, the default: the waves of a radix-4 pass of radix 2^10 lower their issue priority step by
  * step, so that the two workgroups of a CU alternate instead of one running ahead; 0: age alone.  Same results either way; any other
- * value is PM_ERR_BAD_ARG), "ntt_fixed_shape" (1, the default: a pass launch whose size, place in the plan, flags and layout are exactly
- * those of a fixed-shape kernel takes that kernel, which has the geometry and the flags compiled in, if it measured faster than the generic
- * one: the first radix-2^10 pass of a plain 2^20 transform, forward or inverse, batched or not; 2: every fixed-shape kernel there is, the last pass
- * of that transform too; 0: every launch takes the generic kernel.  Same results in all three; any other value is PM_ERR_BAD_ARG), "ntt_pipeline" (0 = no copy / compute overlap in pm_fr_ntt_batch), "poly_lookback" (prefix product in one
+ * value is PM_ERR_BAD_ARG), "ntt_fixed_shape" (2, the default: a pass launch whose size, place in the plan, flags and layout are exactly
+ * those of a fixed-shape kernel takes that kernel, which has the geometry and the flags compiled in: both radix-2^10 passes of a plain 2^20
+ * transform, forward or inverse, batched or not; 1: the first pass of that transform only, the last one takes the generic kernel;
+ * 0: every launch takes the generic kernel.  Same results in all three; any other value is PM_ERR_BAD_ARG), "ntt_pipeline" (0 = no copy / compute overlap in pm_fr_ntt_batch), "poly_lookback" (prefix product in one
  * pass: 0 never, 1 while all tiles are resident -- the default --, 2 always).  PM_ERR_BAD_ARG if unknown. */
 int pm_set_option(pm_ctx* ctx, const char* key, long value);
 /* Opt-in per-kernel timing with hipEvents recorded on the launch stream (bench.py's roofline

@@ -16,9 +16,10 @@
 #ifndef PM_NTT_STEP_PRIO_DEFAULT
 #define PM_NTT_STEP_PRIO_DEFAULT 1
 #endif
-// ... and of the option ntt_fixed_shape
+// ... and of the option ntt_fixed_shape: 2 since the fixed last pass keeps its step twiddles in flight and measured 1.3 - 1.5 us a
+// launch faster than the generic one (PM_NTT_FIXED_TW_PREFETCH, profiles/twiddle_prefetch_kernel_trace.txt)
 #ifndef PM_NTT_FIXED_SHAPE_DEFAULT
-#define PM_NTT_FIXED_SHAPE_DEFAULT 1
+#define PM_NTT_FIXED_SHAPE_DEFAULT 2
 #endif
 // pm_poseidon_cipher_scan_keys_dev (DESIGN.md section 7.2q has the measurement both rest on): the keys from which the call
 // builds the full window table of a note, below it the single-key ladder runs per key ...
@@ -131,7 +132,7 @@ struct pm_ctx {
   long opt_ntt_direct_tw = 1;    // inter-pass twiddles from per-pass N x 36 B tables (1) or from the two-level tables + one product (0)
   long opt_ntt_tw_producer = 1;  // with direct tables: radix-4 passes multiply their outputs by the next pass's table (1) or every pass its own inputs (0)
   long opt_ntt_step_prio = PM_NTT_STEP_PRIO_DEFAULT;  // radix-4 passes of two steps or more: wave priorities by step (1), so that co-resident workgroups alternate, or age alone (0)
-  long opt_ntt_fixed_shape = PM_NTT_FIXED_SHAPE_DEFAULT;  // launches whose geometry and flags equal a fixed-shape variant's take it: the variants that measured faster (1), all of them (2), or every launch the generic kernel (0)
+  long opt_ntt_fixed_shape = PM_NTT_FIXED_SHAPE_DEFAULT;  // launches whose geometry and flags equal a fixed-shape variant's take it: all of them (2, the default), the first pass's only (1), or every launch the generic kernel (0)
   unsigned ntt_last_variant[4] = {0, 0, 0, 0};  // per pass of the last transform ntt_run() launched: 0 none, 1 generic kernel, 2 fixed-shape variant (pm_test_ntt_last_variants)
   long opt_msm_chunk = 0;        // 0 = auto (entries per thread in the level-1 accumulate)
   long opt_msm_max_pairs = 0;    // 0 = 2^31 - 1; a batched MSM with more (digit, point) pairs runs in halves

@@ -424,6 +424,49 @@ PM_DEV FrSplitLazy<G> ld_tw_lazy_fix(const u32x4* ent, u32 idx) {
   return ld_tw_lazy<G>(reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(ent) + lane_off(16u * step4_lazy_entry(G) * idx)), 0);
 }
 
+// Step twiddles kept in flight (PM_NTT_FIXED_TW_PREFETCH).  A lazy step twiddle is seven 16-byte loads
+// that hit L2 (the step-4 table is 86 KB), and as the steps are written each of them is issued only behind the product by the
+// one before it, a few instructions in front of the wait for it: nine round trips a wave that the wave itself covers nothing
+// of.  With the macro at 1 the fixed last pass rotates two buffers: twiddle i + 1 of a step is issued in front of the product by
+// twiddle i, and a step's first twiddle by the step before it, behind its butterflies and in front of the exchange's first
+// barrier (the address is the lane's and the step's, nothing of the data).  Only the order of the loads changes.  0 is the order
+// of the generic kernel (A/B builds: make EXTRA=-DPM_NTT_FIXED_TW_PREFETCH=0).  The first pass keeps the generic order: it
+// stands at 117 VGPRs, a second buffer of 27 words fits only where the next pass's twiddles are not held yet (step 2), and that
+// part with the carried first twiddles measured no faster (profiles/twiddle_prefetch_kernel_trace.txt).  The last pass:
+// 34.2 -> 33.1 us a launch, 107 VGPRs, no scratch.
+#ifndef PM_NTT_FIXED_TW_PREFETCH
+#define PM_NTT_FIXED_TW_PREFETCH 1
+#endif
+__host__ __device__ constexpr bool step4_tw_prefetch(int S, int LT, bool in_wide, int FIX) {
+  return PM_NTT_FIXED_TW_PREFETCH != 0 && FIX != 0 && in_wide && step4_fixed_lazy_form(S, LT, in_wide, FIX) != 0;
+}
+// the first twiddle of the next step on its way from one ntt_step4 to the next; G = 0: nothing is carried
+template <int G>
+struct Step4TwNext {
+  FrSplitLazy<G> w;
+};
+template <>
+struct Step4TwNext<0> {};
+__host__ __device__ constexpr int step4_tw_next_form(int S, int LT, bool in_wide, int FIX) {
+  return step4_tw_prefetch(S, LT, in_wide, FIX) ? step4_fixed_lazy_form(S, LT, in_wide, FIX) : 0;
+}
+// v behind dep for the compiler (no instruction).  With two twiddles loaded, two products of a step are ready at once, and
+// the compiler weaves them into each other: 256 VGPRs and scratch in a kernel that holds 79 with the loads between them.
+PM_DEV void fe_behind(Fr& v, const Fr& dep) {
+  asm("" : "+v"(v.l[0]), "+v"(v.l[1]), "+v"(v.l[2]), "+v"(v.l[3]), "+v"(v.l[4]), "+v"(v.l[5]), "+v"(v.l[6]), "+v"(v.l[7]), "+v"(v.l[8])
+      : "v"(dep.l[8]));
+}
+// twiddle t (0 .. 2, for x[t + 1]) of the lazy step STEP of a fixed variant, for this lane
+template <int S, int LT, int STEP, bool OUT_UFAST, bool IN_WIDE, int FIX>
+PM_DEV auto ld_step_lazy_fix(const NttPassArgs& a, u32 tid, u32 t) {
+  constexpr int G = step4_fixed_lazy_form(S, LT, IN_WIDE, FIX);
+  constexpr u32 U = (1u << S) / 4, nsp = 1u << (2 * STEP);
+  constexpr bool ufast = OUT_UFAST && STEP == num_steps4(S) - 1;
+  const u32 u = ufast ? tid % U : tid >> LT;
+  const u32 kp = step4_plane_major(S, IN_WIDE) ? step4_pm_digit(S, STEP, u) : u & (nsp - 1);
+  return ld_tw_lazy_fix<G>(a.step_tw_lazy + STEP4_LAZY_HEAD + step4_lazy_entry(G) * step4_lazy_offset(S, STEP), t * nsp + kp);
+}
+
 // element of the output vector (batch offset apart) that the last step of a pass stores its x[m] to
 template <int S, int LT, bool OUT_UFAST>
 PM_DEV size_t pass4_out_index(const NttPassArgs& a, u32 tid, size_t j0, int m) {
@@ -439,7 +482,8 @@ PM_DEV size_t pass4_out_index(const NttPassArgs& a, u32 tid, size_t j0, int m) {
 
 template <int S, int LT, int STEP, bool OUT_UFAST, bool IN_WIDE, bool OUT_WIDE, int FIX = 0>
 PM_DEV void ntt_step4(Fr (&x)[4], Fr (&ptw)[4], const NttPassArgs& a, const NttConsts& kc, u32x4* lds0, u32x4* lds1,
-                      u32* lds2, W4Rows w4, u32 tid, size_t j0) {
+                      u32* lds2, W4Rows w4, u32 tid, size_t j0,
+                      Step4TwNext<step4_tw_next_form(S, LT, IN_WIDE, FIX)>* nx = nullptr) {
   constexpr int R = 1 << S;
   constexpr int T = 1 << LT;
   constexpr int U = R / 4;
@@ -453,6 +497,10 @@ PM_DEV void ntt_step4(Fr (&x)[4], Fr (&ptw)[4], const NttPassArgs& a, const NttC
   constexpr bool L1_CONSUMER = PM && step4_l1_consumer(S, LT, OUT_UFAST);
   constexpr bool TW_PRODUCER = OUT_WIDE && step4_tw_producer(S, LT, OUT_UFAST, IN_WIDE);
   constexpr int LAZY = step4_fixed_lazy_form(S, LT, IN_WIDE, FIX);  // G of the lazy step twiddles, 0: the (1, <2) products
+  // step twiddles kept in flight (above): this step takes its first one from nx and leaves the next step's there
+  constexpr bool PREFETCH = step4_tw_prefetch(S, LT, IN_WIDE, FIX);
+  constexpr bool NEXT_PREFETCH = PREFETCH && !last && step4_generic(S, LT, OUT_UFAST, IN_WIDE, STEP + 1);
+  static_assert(!PREFETCH || !TW_PRODUCER, "the next pass's twiddles have no place in the rotated order");
   static_assert(!(L1_UNIFORM && STEP == 0 && ufast), "the producer of the first-layer twiddles is in wave order");
   static_assert(!LAZY || !step4_generic(S, LT, OUT_UFAST, IN_WIDE, STEP) || step4_lazy_step(S, STEP), "the lazy table starts at step 2");
   const u32 c = ufast ? tid / U : tid & (T - 1);
@@ -504,6 +552,20 @@ PM_DEV void ntt_step4(Fr (&x)[4], Fr (&ptw)[4], const NttPassArgs& a, const NttC
         asm volatile("" : "+s"(rows));
         x[m] = mul_head(x[m], rows);
       }
+    } else if constexpr (PREFETCH && STEP > 0 && !(L1_UNIFORM && STEP == 1)) {
+      // twiddle 0 is on its way since the step before; 1 and 2 go out in front of the products by 0 and 1
+      x[0] = fe_reduce_weak<FrP>(x[0]);
+      __builtin_amdgcn_sched_barrier(0);
+      const auto w2 = ld_step_lazy_fix<S, LT, STEP, OUT_UFAST, IN_WIDE, FIX>(a, tid, 1);
+      __builtin_amdgcn_sched_barrier(0);
+      x[1] = mul_step(x[1], nx->w);
+      __builtin_amdgcn_sched_barrier(0);
+      const auto w3 = ld_step_lazy_fix<S, LT, STEP, OUT_UFAST, IN_WIDE, FIX>(a, tid, 2);
+      __builtin_amdgcn_sched_barrier(0);
+      fe_behind(x[2], x[1]);
+      x[2] = mul_step(x[2], w2);
+      fe_behind(x[3], x[2]);
+      x[3] = mul_step(x[3], w3);
     } else if (STEP > 0 && !(L1_UNIFORM && STEP == 1)) {
       x[0] = fe_reduce_weak<FrP>(x[0]);
       x[1] = mul_step(x[1], ld_step(0 * nsp + kp));
@@ -552,6 +614,11 @@ PM_DEV void ntt_step4(Fr (&x)[4], Fr (&ptw)[4], const NttPassArgs& a, const NttC
       }
     }
     NTT_STAMP(2 + 3 * STEP + 1);
+    if constexpr (NEXT_PREFETCH) {   // the next step's first twiddle: the exchange covers its round trip
+      __builtin_amdgcn_sched_barrier(0);
+      nx->w = ld_step_lazy_fix<S, LT, STEP + 1, OUT_UFAST, IN_WIDE, FIX>(a, tid, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    }
     if constexpr (!last) {
       __syncthreads();
       const u32 base = (u - kp) * 4 + kp;
@@ -759,12 +826,13 @@ __global__ void __launch_bounds__((1 << (S + LT)) / 4 < 64 ? 64 : (1 << (S + LT)
       for (int m = 0; m < 4; ++m) x[m] = fe_load<FrP>(gin + lane_off(32u * (c + ((u + (u32)m * U) << (FIX - S)))));
     }
   }
-  ntt_step4<S, LT, 0, OUT_UFAST, IN_WIDE, OUT_WIDE, FIX>(x, ptw, a, kc, lds0, lds1, lds2, w4, tid, j0);
-  ntt_step4<S, LT, 1, OUT_UFAST, IN_WIDE, OUT_WIDE, FIX>(x, ptw, a, kc, lds0, lds1, lds2, w4, tid, j0);
-  if constexpr (NSTEPS > 2) ntt_step4<S, LT, 2, OUT_UFAST, IN_WIDE, OUT_WIDE, FIX>(x, ptw, a, kc, lds0, lds1, lds2, w4, tid, j0);
-  if constexpr (NSTEPS > 3) ntt_step4<S, LT, 3, OUT_UFAST, IN_WIDE, OUT_WIDE, FIX>(x, ptw, a, kc, lds0, lds1, lds2, w4, tid, j0);
-  if constexpr (NSTEPS > 4) ntt_step4<S, LT, 4, OUT_UFAST, IN_WIDE, OUT_WIDE, FIX>(x, ptw, a, kc, lds0, lds1, lds2, w4, tid, j0);
-  if constexpr (NSTEPS > 5) ntt_step4<S, LT, 5, OUT_UFAST, IN_WIDE, OUT_WIDE, FIX>(x, ptw, a, kc, lds0, lds1, lds2, w4, tid, j0);
+  Step4TwNext<step4_tw_next_form(S, LT, IN_WIDE, FIX)> nx;  // a step's first twiddle, issued by the step before it
+  ntt_step4<S, LT, 0, OUT_UFAST, IN_WIDE, OUT_WIDE, FIX>(x, ptw, a, kc, lds0, lds1, lds2, w4, tid, j0, &nx);
+  ntt_step4<S, LT, 1, OUT_UFAST, IN_WIDE, OUT_WIDE, FIX>(x, ptw, a, kc, lds0, lds1, lds2, w4, tid, j0, &nx);
+  if constexpr (NSTEPS > 2) ntt_step4<S, LT, 2, OUT_UFAST, IN_WIDE, OUT_WIDE, FIX>(x, ptw, a, kc, lds0, lds1, lds2, w4, tid, j0, &nx);
+  if constexpr (NSTEPS > 3) ntt_step4<S, LT, 3, OUT_UFAST, IN_WIDE, OUT_WIDE, FIX>(x, ptw, a, kc, lds0, lds1, lds2, w4, tid, j0, &nx);
+  if constexpr (NSTEPS > 4) ntt_step4<S, LT, 4, OUT_UFAST, IN_WIDE, OUT_WIDE, FIX>(x, ptw, a, kc, lds0, lds1, lds2, w4, tid, j0, &nx);
+  if constexpr (NSTEPS > 5) ntt_step4<S, LT, 5, OUT_UFAST, IN_WIDE, OUT_WIDE, FIX>(x, ptw, a, kc, lds0, lds1, lds2, w4, tid, j0, &nx);
 }
 
 // step twiddles of the radix-4 kernel: block s, entry [(t-1)*Ns' + k'] = wR^(k' t R/(Ns' q)), Ns' = 4^s, both rows
