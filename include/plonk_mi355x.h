@@ -860,6 +860,66 @@ int pm_hades_permute_host(uint32_t rounds, uint32_t full_rounds, const uint64_t*
                           uint64_t state[20]);
 int pm_poseidon_hash_host(uint32_t rounds, uint32_t full_rounds, const uint64_t* ark, const uint64_t* mds, uint32_t n_mds,
                           const uint64_t capacity[4], const uint64_t* msg, size_t msg_len, uint64_t out[4]);
+/* ---- The append-only Poseidon tree: a tree of ledger height that stores only what is filled ---------
+ * Arity 4, a fixed height H, 1 <= H <= PM_POSEIDON_LEDGER_MAX_HEIGHT (4^31 = 2^62 positions), the hash of pm_poseidon_merkle_dev.
+ * Leaves are filled from position 0 upward; `count` is their number.  Level 0 is the leaves, level l stores the nodes
+ * [0, ceil(count / 4^l)): those with a filled descendant.  Everything to the right is an empty subtree whose hash is a constant
+ * of its level: Z_0 = empty_leaf, Z_(l+1) = hash(Z_l, Z_l, Z_l, Z_l); a child at or beyond the stored prefix of its level reads
+ * as that level's Z, and the root of an empty tree is Z_H.  A tree whose 4^H positions are all filled holds, level by level, the
+ * bytes pm_poseidon_merkle_dev writes with the same constants and capacity.
+ * The handle, an opaque struct of the name pm_poseidon_ledger, owns one device slab with room for `reserve` leaves and their
+ * ancestors (level l: ceil(reserve / 4^l) elements, the levels one after the other), a device table of Z_0 .. Z_H, a
+ * one-element device root that is current after every call, its own copy of the Hades constants and of the capacity word -- it
+ * does not refer to `params` after _create -- and the host's count and reserve.  One handle must not be used by two calls at a
+ * time, and calls on it that change it must be ordered on one stream.
+ *   _create: the Z_l are computed on the host (pm_hades_permute_host's rounds).  PM_ERR_BAD_ARG for height 0 or above 31, a
+ *     capacity or empty leaf that is not canonical, NULL, reserve_leaves > 4^height.  reserve_leaves = 0 allocates no slab.
+ *   _free waits for the device.  _info: any output may be NULL; device_bytes counts the slab, the Z table, the root and the
+ *     constants.  _bytes is pure host: the slab of a reserve, 32 * sum over l = 0..H of ceil(reserve / 4^l); 0 for arguments
+ *     _create refuses.  _empty_roots writes Z_0 .. Z_H, height + 1 elements, to host memory.
+ *   _append_dev: d_values[0 .. k) become the leaves count .. count + k - 1 (a device copy), then level l = 1..H hashes exactly
+ *     the nodes (count >> 2l) .. ((count + k - 1) >> 2l), one launch a level with the form AUTO picks for that level's exact
+ *     number of nodes, and a copy of the new root to the handle's root element.
+ *     *hashed (may be NULL) = the sum over l of the range sizes, known to the host: the call is asynchronous with no readback.
+ *     If count + k > reserve the slab grows first to max(2 reserve, count + k), at most 4^H: the stored prefixes are copied
+ *     device to device and the call WAITS for the stream.  k = 0: PM_OK, nothing launched.  PM_ERR_LENGTH for count + k > 4^H
+ *     or k > 2^31 - 1; PM_ERR_BAD_ARG for flags above PM_HADES_FORM_WAVE, a NULL or misaligned d_values and one that overlaps
+ *     the handle's device memory (the slab, the Z table, the root).  A refused call changes nothing.
+ *   _truncate_dev, the rollback: new_count > count is PM_ERR_BAD_ARG; new_count = count is PM_OK with *hashed = 0; new_count =
+ *     0 sets the root to Z_H, *hashed = 0; otherwise the H ancestors of leaf new_count - 1 are hashed again, *hashed = H.
+ *     Asynchronous.  Stored bytes beyond the new prefixes are not cleared and are never read as data: an append after a
+ *     truncate gives the bytes of a fresh ledger over the same leaves.
+ *   _root_dev copies the root to d_root (one element) on the stream; _root copies it to the host and WAITS for the stream.
+ *     An output of _root_dev or _paths_dev that overlaps the handle's device memory -- a _level pointer, say -- is
+ *     PM_ERR_BAD_ARG: no call writes tree state through a caller's buffer.
+ *   _level: the stored prefix of level l <= H: its address (valid until the slab next grows; NULL when nothing is stored) and
+ *     its number of nodes.  Bytes beyond `nodes` are unspecified.
+ *   _paths_dev: as pm_poseidon_merkle_paths_dev, [k][H][4] elements; a sibling beyond a stored prefix is its level's Z.  An
+ *     index >= count is PM_ERR_BAD_ARG naming the lowest offending position; nothing is read for it, the other paths are
+ *     written; the call WAITS for the stream.
+ *   _verify_dev: pm_poseidon_merkle_verify_dev -- its kernels, its status words, its refusals -- for 1 <= height <= 31.  It
+ *     needs no handle: the caller holds the constants, the capacity and a root. */
+#define PM_POSEIDON_LEDGER_MAX_HEIGHT 31u
+typedef struct pm_poseidon_ledger pm_poseidon_ledger;
+int pm_poseidon_ledger_create(pm_ctx* ctx, const pm_hades_params* params, const uint64_t capacity[4], uint32_t height,
+                              const uint64_t empty_leaf[4], uint64_t reserve_leaves, pm_poseidon_ledger** out);
+void pm_poseidon_ledger_free(pm_ctx* ctx, pm_poseidon_ledger* ledger);
+int pm_poseidon_ledger_info(const pm_poseidon_ledger* ledger, uint32_t* height, uint64_t* count, uint64_t* reserve_leaves,
+                            size_t* device_bytes);
+size_t pm_poseidon_ledger_bytes(uint32_t height, uint64_t reserve_leaves);
+int pm_poseidon_ledger_empty_roots(const pm_poseidon_ledger* ledger, uint64_t* out);
+int pm_poseidon_ledger_append_dev(pm_ctx* ctx, pm_poseidon_ledger* ledger, const void* d_values, size_t k, uint32_t flags,
+                                  uint64_t* hashed, void* hip_stream);
+int pm_poseidon_ledger_truncate_dev(pm_ctx* ctx, pm_poseidon_ledger* ledger, uint64_t new_count, uint32_t flags, uint64_t* hashed,
+                                    void* hip_stream);
+int pm_poseidon_ledger_root_dev(pm_ctx* ctx, const pm_poseidon_ledger* ledger, void* d_root, void* hip_stream);
+int pm_poseidon_ledger_root(pm_ctx* ctx, const pm_poseidon_ledger* ledger, uint64_t out[4], void* hip_stream);
+int pm_poseidon_ledger_level(const pm_poseidon_ledger* ledger, uint32_t level, void** d_ptr, uint64_t* nodes);
+int pm_poseidon_ledger_paths_dev(pm_ctx* ctx, const pm_poseidon_ledger* ledger, const void* d_indices, size_t k, void* d_out,
+                                 void* hip_stream);
+int pm_poseidon_ledger_verify_dev(pm_ctx* ctx, const pm_hades_params* params, const uint64_t capacity[4], const void* d_paths,
+                                  const void* d_indices, size_t k, uint32_t height, const void* d_root, void* d_status,
+                                  uint32_t flags, void* hip_stream);
 /* ---- Native JubJub: scalar multiplications on the embedded curve outside a circuit ------------------
  * The curve is the one the FIXED_BASE, CURVE_ADD and VAR_BASE gadgets constrain: -x^2 + y^2 = 1 + d x^2 y^2 over Fr with
  * d = -(10240 / 10241), under the law (x1, y1) + (x2, y2) = ((x1 y2 + y1 x2) / (1 + k), (y1 y2 + x1 x2) / (1 - k)),
@@ -1344,6 +1404,14 @@ int pm_test_cipher_scan_keys_plan(uint32_t num_cus, uint32_t n_keys, uint32_t ms
  * 6 segments at most (accumulate threads), 7 buckets per thread of the window kernel}.  Returns what the call would:
  * PM_ERR_BAD_ARG (batch = 0, a width outside 4 .. 16), PM_ERR_LENGTH (the limits of pm_jubjub_msm_dev); out is then zero. */
 int pm_test_jubjub_msm_plan(size_t n, uint32_t batch, long window_bits, uint32_t num_cus, uint64_t out[8]);
+/* Pure host, no context: what pm_poseidon_ledger_append_dev launches when k leaves are appended to a tree of `height` that
+ * holds `count` (the plan the call itself runs from).  For level l = 1..height, at index l - 1 of three arrays of `height`
+ * entries each: first[] = the first node hashed, nodes[] = their number, below[] = the stored width of level l - 1 after the
+ * append.  *chain_from = the first level whose range is one node (every level from there on has one), *hashed = the sum
+ * of nodes[].  k = 0: every entry 0, *chain_from = 0.  Any output may be NULL.  PM_ERR_BAD_ARG for a height outside 1 .. 31 or
+ * count > 4^height, PM_ERR_LENGTH for count + k > 4^height or k > 2^31 - 1. */
+int pm_test_ledger_plan(uint32_t height, uint64_t count, uint64_t k, uint64_t* first, uint64_t* nodes, uint64_t* below,
+                        uint32_t* chain_from, uint64_t* hashed);
 /* Pure host, no context: the signed-window recoding the kernels run, compiled for the host, on ANY 256-bit integer (four words,
  * little end first) at width c in 4 .. 16 (else PM_ERR_BAD_ARG): digits[k], k < *n_digits, with sum digits[k] 2^(c k) = the
  * integer and |digits[k]| <= 2^(c-1).  *n_digits is the plan's window count; a carry out of the top window would show as one

@@ -18,7 +18,7 @@ from .jubjub import (JUBJUB_CODEC_REASONS, JUBJUB_GENERATOR, JubJubBase, fr_sqrt
                      jubjub_add_host, jubjub_check, jubjub_commit, jubjub_commit_dev, jubjub_compress, jubjub_compress_dev,
                      jubjub_compress_host, jubjub_decompress, jubjub_decompress_dev, jubjub_decompress_host, jubjub_msm,
                      jubjub_msm_dev, jubjub_msm_host, jubjub_mul, jubjub_mul_dev, jubjub_mul_host)
-from .poseidon import Hades, MerkleTree, hades_permute_host, poseidon_hash_host  # noqa: F401,E402
+from .poseidon import Hades, LedgerTree, MerkleTree, hades_permute_host, poseidon_hash_host  # noqa: F401,E402
 from .prover import (BatchWorkspace, Circuit, Gadget, GadgetInputError, GadgetReport, Proof, ProverKey,  # noqa: F401,E402
                      UnsatisfiedWitness, WitnessReport, preprocess, prove, prove_batch, random_blinders, sigma_from_wires)
 from .schnorr import SCHNORR_REASONS, Schnorr, schnorr_sign_host, schnorr_verify_host  # noqa: F401,E402

@@ -204,6 +204,19 @@ SIGNATURES = {
                                                 C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, u64p, C.c_void_p]),
     "pm_poseidon_merkle_verify_dev": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32,
                                                 C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "pm_poseidon_ledger_create": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_uint32, u64p, C.c_uint64, C.POINTER(C.c_void_p)]),
+    "pm_poseidon_ledger_free": (None, [C.c_void_p, C.c_void_p]),
+    "pm_poseidon_ledger_info": (C.c_int, [C.c_void_p, u32p, u64p, u64p, C.POINTER(C.c_size_t)]),
+    "pm_poseidon_ledger_bytes": (C.c_size_t, [C.c_uint32, C.c_uint64]),
+    "pm_poseidon_ledger_empty_roots": (C.c_int, [C.c_void_p, u64p]),
+    "pm_poseidon_ledger_append_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, u64p, C.c_void_p]),
+    "pm_poseidon_ledger_truncate_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, u64p, C.c_void_p]),
+    "pm_poseidon_ledger_root_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pm_poseidon_ledger_root": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_void_p]),
+    "pm_poseidon_ledger_level": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), u64p]),
+    "pm_poseidon_ledger_paths_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "pm_poseidon_ledger_verify_dev": (C.c_int, [C.c_void_p, C.c_void_p, u64p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32,
+                                                C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "pm_hades_permute_host": (C.c_int, [C.c_uint32, C.c_uint32, u64p, u64p, C.c_uint32, u64p]),
     "pm_poseidon_hash_host": (C.c_int, [C.c_uint32, C.c_uint32, u64p, u64p, C.c_uint32, u64p, u64p, C.c_size_t, u64p]),
     "pm_jubjub_base_create": (C.c_int, [C.c_void_p, u64p, C.POINTER(C.c_void_p)]),
@@ -294,6 +307,7 @@ SIGNATURES = {
                                                 C.POINTER(C.c_size_t)]),
     "pm_test_jubjub_msm_plan":(C.c_int, [C.c_size_t, C.c_uint32, C.c_long, C.c_uint32, u64p]),
     "pm_test_jubjub_msm_digits": (C.c_int, [u64p, C.c_uint32, C.POINTER(C.c_int32), u32p]),
+    "pm_test_ledger_plan": (C.c_int, [C.c_uint32, C.c_uint64, C.c_uint64, u64p, u64p, u64p, u32p, u64p]),
     "pm_test_ntt_plan": (C.c_int, [C.c_uint32, C.c_uint32, C.c_long, C.c_long, C.c_long, C.c_uint32, C.POINTER(C.c_uint32)]),
     "pm_test_ntt_exchange_map": (C.c_int, [C.c_uint32] * 5 + [C.POINTER(C.c_uint32)]),
     "pm_test_ntt_fixed_match": (C.c_int, [C.c_uint32] * 7 + [C.c_uint64, C.c_uint32, C.c_uint32]),
@@ -356,6 +370,7 @@ PLONK_CHAIN_KINDS = {10: "variable_base"}
 # pm_hades_permute_dev / pm_poseidon_*_dev: which kernel form runs (the bytes do not depend on it)
 HADES_FORM_AUTO, HADES_FORM_THREAD, HADES_FORM_WAVE = 0, 1, 2
 POSEIDON_MERKLE_MAX_HEIGHT = 15
+POSEIDON_LEDGER_MAX_HEIGHT = 31   # pm_poseidon_ledger_*: the append-only tree
 # pm_poseidon_merkle_verify_dev: the status of a path; LINK + l = the hash of level l is not its successor
 MERKLE_PATH_OK, MERKLE_PATH_INDEX, MERKLE_PATH_LINK = 0, 1, 2
 # pm_schnorr_verify_*: why a signature is not valid, the lowest that applies

@@ -20,6 +20,11 @@
 // Section 7.2n adds the tree in place: an update of k leaves that hashes only their ancestors (the two hash kernels again, with
 // an argument block that takes slot i's node from a worklist in device memory; the worklists come from a compaction a level)
 // and the verification of paths, `height` dependent permutations a path from the same rounds.
+//
+// Section 7.2r adds the append-only tree of ledger height (pm_poseidon_ledger): only the filled prefix of a level is stored, what
+// lies to its right is the empty subtree of the level.  An append hashes the contiguous dirty range of every level (the two hash
+// kernels with a third argument block, whose children beyond a stored prefix are that constant), the levels of one node included,
+// up to the root, a launch a level; a truncate is that walk alone.
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -59,6 +64,14 @@ struct HadesNodeIo : HadesIo {
   const MerkleCtl* ctl;
   u32 level;
 };
+// the RANGE hash with defaults (section 7.2r): slot i hashes node first + i of one level of an append-only tree.  Child
+// 4 (first + i) + c is read from the level below (msgs) when it is inside that level's stored prefix of `below` nodes and is
+// the empty subtree of that level, *z, otherwise.  out = the level itself.  Nothing is materialised: what lies beyond a
+// stored prefix is never read.
+struct HadesRangeIo : HadesIo {
+  u64 first, below;
+  const u32x4* z;             // one canonical element: Z of the level below
+};
 PM_DEV size_t h_slots(const HadesIo& io) { return io.n; }
 PM_DEV size_t h_slots(const HadesNodeIo& io) {
   const size_t have = io.ctl->bad == MERKLE_NONE ? io.ctl->cnt[io.level] : 0;
@@ -72,6 +85,17 @@ PM_DEV const u32x4* h_place(const HadesIo& io, size_t slot, size_t& out_at) {
 PM_DEV const u32x4* h_place(const HadesNodeIo& io, size_t slot, size_t& out_at) {
   out_at = io.ids[slot];
   return io.msgs + 8 * out_at;                               // the four children of the node
+}
+PM_DEV const u32x4* h_place(const HadesRangeIo& io, size_t slot, size_t& out_at) {
+  out_at = io.first + slot;
+  return io.msgs;                                            // the level below from its node 0: h_word indexes it by child
+}
+// word t (0..3) of the chunk at element `at` of slot's message (`left` elements to go); node = the slot's out_at
+PM_DEV Fr h_word(const HadesIo&, const u32x4* msg, size_t, size_t at, u32 left, u32 t) { return h_chunk_word(msg, at, left, t); }
+PM_DEV Fr h_word(const HadesRangeIo& io, const u32x4* msg, size_t node, size_t, u32, u32 t) {
+  const u64 child = 4 * (u64)node + t;
+  const bool stored = child < io.below;
+  return h_to_dev(ld_canon(stored ? msg : io.z, stored ? child : 0));
 }
 
 template <bool HASH, class Io = HadesIo>
@@ -97,7 +121,7 @@ __global__ void __launch_bounds__(64) hades_thread_kernel(const HadesTab tab, co
     for (u32 at = 0; at < io.msg_len; at += 4) {
       s[0] = h_absorb(s[0], fe_zero<FrP>(), tab.ark);
 #pragma unroll
-      for (int j = 1; j < 5; ++j) s[j] = h_absorb(s[j], h_chunk_word(msg, at, io.msg_len - at, j - 1), tab.ark + 9 * j);
+      for (int j = 1; j < 5; ++j) s[j] = h_absorb(s[j], h_word(io, msg, out_at, at, io.msg_len - at, j - 1), tab.ark + 9 * j);
       h_rounds_thread(s, tab);
     }
     st_canon(io.out, out_at, h_to_abi(s[1]));
@@ -171,7 +195,7 @@ __global__ void __launch_bounds__(64) hades_wave_kernel(const HadesTab tab, cons
     }
 #pragma unroll 1
     for (u32 at = 0; at < io.msg_len; at += 4) {
-      const Fr add = j == 0 ? fe_zero<FrP>() : h_chunk_word(msg, at, io.msg_len - at, j - 1);
+      const Fr add = j == 0 ? fe_zero<FrP>() : h_word(io, msg, out_at, at, io.msg_len - at, j - 1);
       s = fe_reduce_weak<FrP>(fe_add<FrP>(fe_add<FrP>(s, add), key0));
       s = h_rounds_wave(s, mds, ark, tab, base, i, j);
     }
@@ -363,6 +387,38 @@ __global__ void __launch_bounds__(64) merkle_verify_wave_kernel(const HadesTab t
   if (live && owner && l == 1) io.status[p] = status;
 }
 
+// ---- the append-only tree (section 7.2r).  The slab holds level l at element ledger_offset(reserve, l): the levels one after
+// the other, level q with room for ceil(reserve / 4^q) nodes; level l stores the nodes below ledger_width(count, l).
+__host__ __device__ inline u64 ledger_width(u64 leaves, u32 l) { return (leaves + ((1ull << (2 * l)) - 1)) >> (2 * l); }
+__host__ __device__ inline u64 ledger_offset(u64 reserve, u32 l) {
+  u64 off = 0;
+  for (u32 q = 0; q < l; ++q) off += ledger_width(reserve, q);
+  return off;
+}
+struct LedgerView {
+  const u32x4* slab;
+  const u32x4* z;             // Z_0 .. Z_h, canonical
+  u64 count, reserve;
+  u32 h;
+};
+// merkle_paths_kernel with defaults: a node at or beyond its level's stored prefix is that level's Z
+__global__ void __launch_bounds__(256) ledger_paths_kernel(const LedgerView v, const u64* idx, size_t k, u32x4* out) {
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;   // one thread a node: (j, l, c)
+  if (t >= k * v.h * 4) return;
+  const u32 c = (u32)(t & 3u), l = (u32)((t >> 2) % v.h);
+  const size_t j = (t >> 2) / v.h;
+  const u64 leaf = idx[j];
+  if (leaf >= v.count) return;                               // refused by the host after the call; nothing is read for it
+  const u64 node = ((leaf >> (2 * l)) & ~3ull) + c;
+  const u32x4* const src = node < ledger_width(v.count, l) ? v.slab + 2 * (ledger_offset(v.reserve, l) + node) : v.z + 2 * l;
+  out[2 * t] = src[0];
+  out[2 * t + 1] = src[1];
+}
+__global__ void __launch_bounds__(256) ledger_index_check_kernel(const u64* idx, size_t k, u64 count, unsigned long long* bad) {
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (t < k && idx[t] >= count) atomicMin(bad, (unsigned long long)t);
+}
+
 // ------------------------------------------------------------------ launches
 // AUTO: the WAVE form below this many permutations, the THREAD form from it on.  Measured at (67, 8), DESIGN.md section 7.2j:
 // THREAD takes 0.48 ms for anything up to one wave a SIMD, WAVE grows by 0.054 ms a 1024 permutations and meets it at 8192.
@@ -403,6 +459,7 @@ int params_build(pm_ctx* ctx, uint32_t R, uint32_t F, const uint64_t* ark, const
   }
   pm_hades_params* p = new pm_hades_params();
   p->device = ctx->device, p->rounds = R, p->full = F, p->n_mds = n_mds, p->d_tab = d;
+  p->ark.assign(ark, ark + 20 * (size_t)R), p->mds.assign(mds, mds + 100 * (size_t)n_mds);
   *out = p;
   return PM_OK;
 }
@@ -629,14 +686,15 @@ extern "C" int pm_poseidon_merkle_update_dev(pm_ctx* ctx, const pm_hades_params*
   return PM_OK;
 }
 
-extern "C" int pm_poseidon_merkle_verify_dev(pm_ctx* ctx, const pm_hades_params* params, const uint64_t capacity[4],
-                                             const void* d_paths, const void* d_indices, size_t k, uint32_t height, const void* d_root,
-                                             void* d_status, uint32_t flags, void* hip_stream) {
+namespace {
+// the two verification entries: the dense tree's, which refuses what its tree cannot be (height > 15), and the ledger tree's
+int merkle_verify(pm_ctx* ctx, const pm_hades_params* params, const uint64_t capacity[4], const void* d_paths, const void* d_indices,
+                  size_t k, uint32_t height, uint32_t max_height, const void* d_root, void* d_status, uint32_t flags, void* hip_stream) {
   if (!ctx) return PM_ERR_BAD_ARG;
   if (int rc = common_fault(ctx, params, flags)) return rc;
   MerkleVerifyIo io{};
   if (int rc = capacity_to_dev(ctx, capacity, io.capacity)) return rc;
-  if (height < 1 || height > PM_POSEIDON_MERKLE_MAX_HEIGHT) return set_err(ctx, PM_ERR_BAD_ARG, "height must be in 1 .. 15");
+  if (height < 1 || height > max_height) return set_err(ctx, PM_ERR_BAD_ARG, "height must be in 1 .. " + std::to_string(max_height));
   if (k == 0) return PM_OK;
   if (int rc = pointer_fault(ctx, {d_paths, d_root}, !d_indices || !d_status || ((uintptr_t)d_indices & 7u) || ((uintptr_t)d_status & 3u)))
     return rc;
@@ -654,6 +712,307 @@ extern "C" int pm_poseidon_merkle_verify_dev(pm_ctx* ctx, const pm_hades_params*
   else
     hipLaunchKernelGGL(merkle_verify_thread_kernel, dim3((unsigned)((k + 63) / 64)), dim3(64), 0, st, tab, io);
   PM_HIP(ctx, hipGetLastError());
+  return PM_OK;
+}
+}  // namespace
+
+extern "C" int pm_poseidon_merkle_verify_dev(pm_ctx* ctx, const pm_hades_params* params, const uint64_t capacity[4],
+                                             const void* d_paths, const void* d_indices, size_t k, uint32_t height, const void* d_root,
+                                             void* d_status, uint32_t flags, void* hip_stream) {
+  return merkle_verify(ctx, params, capacity, d_paths, d_indices, k, height, PM_POSEIDON_MERKLE_MAX_HEIGHT, d_root, d_status, flags,
+                       hip_stream);
+}
+
+extern "C" int pm_poseidon_ledger_verify_dev(pm_ctx* ctx, const pm_hades_params* params, const uint64_t capacity[4],
+                                             const void* d_paths, const void* d_indices, size_t k, uint32_t height, const void* d_root,
+                                             void* d_status, uint32_t flags, void* hip_stream) {
+  return merkle_verify(ctx, params, capacity, d_paths, d_indices, k, height, PM_POSEIDON_LEDGER_MAX_HEIGHT, d_root, d_status, flags,
+                       hip_stream);
+}
+
+// ------------------------------------------------------------------ the append-only tree
+struct pm_poseidon_ledger {
+  int device = 0;
+  uint32_t height = 0;
+  uint64_t count = 0, reserve = 0;        // filled leaves; leaves the slab has room for
+  pm_hades_params own;                    // a copy of the constants with its own device table
+  u32 capacity[9] = {};                   // device form
+  std::vector<uint64_t> z;                // Z_0 .. Z_height, canonical: the host's copy of d_z
+  void* d_slab = nullptr;                 // level l at element ledger_offset(reserve, l)
+  void* d_z = nullptr;
+  void* d_root = nullptr;                 // one element, current after every call
+  void* d_bad = nullptr;                  // one u64: the verdict of a paths call's index check
+};
+
+namespace {
+// What an append of k leaves at `count` hashes (the definitions of section 7.2r); index l, 1 <= l <= height.
+struct LedgerPlan {
+  u64 first[PM_POSEIDON_LEDGER_MAX_HEIGHT + 1], nodes[PM_POSEIDON_LEDGER_MAX_HEIGHT + 1], below[PM_POSEIDON_LEDGER_MAX_HEIGHT + 1];
+  u32 chain_from;                         // the first level whose range is one node (one node a level from there on); 0 for k = 0
+  u64 hashed;
+};
+u64 ledger_positions(u32 height) { return 1ull << (2 * height); }
+size_t table_bytes(const pm_hades_params& p) { return (225 * (size_t)p.n_mds + 45 * ((size_t)p.rounds + 1)) * 4; }
+int ledger_plan(u32 height, u64 count, u64 k, LedgerPlan* p) {
+  *p = LedgerPlan{};
+  if (height < 1 || height > PM_POSEIDON_LEDGER_MAX_HEIGHT || count > ledger_positions(height)) return PM_ERR_BAD_ARG;
+  if (k > 0x7fffffffu || k > ledger_positions(height) - count) return PM_ERR_LENGTH;
+  if (k == 0) return PM_OK;
+  const u64 last = count + k - 1;
+  for (u32 l = 1; l <= height; ++l) {
+    p->first[l] = count >> (2 * l);
+    p->nodes[l] = (last >> (2 * l)) - p->first[l] + 1;
+    p->below[l] = ledger_width(count + k, l - 1);
+    p->hashed += p->nodes[l];
+    if (!p->chain_from && p->nodes[l] == 1) p->chain_from = l;
+  }
+  return PM_OK;
+}
+
+int ledger_fault(pm_ctx* ctx, const pm_poseidon_ledger* t) {
+  if (!t) return set_err(ctx, PM_ERR_BAD_ARG, "null ledger");
+  if (t->device != ctx->device) return set_err(ctx, PM_ERR_BAD_ARG, "the ledger belongs to another device");
+  return PM_OK;
+}
+// [p, p + bytes) shares a byte with device memory the handle owns
+bool ledger_owns(const pm_poseidon_ledger* t, const void* p, size_t bytes) {
+  return overlap(p, bytes, t->d_slab, pm_poseidon_ledger_bytes(t->height, t->reserve)) ||
+         overlap(p, bytes, t->d_z, 32 * ((size_t)t->height + 1)) || overlap(p, bytes, t->d_root, 32) || overlap(p, bytes, t->d_bad, 8);
+}
+u32x4* ledger_level_ptr(const pm_poseidon_ledger* t, u32 l) { return (u32x4*)t->d_slab + 2 * ledger_offset(t->reserve, l); }
+
+// The levels of the plan on the stream, a range launch each, and a copy of the root to the handle's own element.  One launch
+// that walks the single-node levels with the hash in registers was built and measured: 1.4 to 1.7 % of a one-leaf append,
+// inside the spread at one of four points, so it was not kept.
+hipError_t ledger_hash(pm_poseidon_ledger* t, const LedgerPlan& plan, uint32_t flags, hipStream_t st) {
+  const u32 H = t->height;
+  HadesRangeIo io{};
+  memcpy(io.capacity, t->capacity, sizeof io.capacity);
+  io.msg_len = 4, io.msg_stride = 4;
+  for (u32 l = 1; l <= H; ++l) {
+    io.n = (size_t)plan.nodes[l], io.first = plan.first[l], io.below = plan.below[l];
+    io.msgs = ledger_level_ptr(t, l - 1), io.out = ledger_level_ptr(t, l), io.z = (const u32x4*)t->d_z + 2 * (l - 1);
+    if (hipError_t e = launch<true>(&t->own, io, flags, st)) return e;
+  }
+  return hipMemcpyAsync(t->d_root, ledger_level_ptr(t, H), 32, hipMemcpyDeviceToDevice, st);
+}
+
+// a slab with room for `reserve` leaves that holds the stored prefixes of the current one; waits for the stream
+int ledger_grow(pm_ctx* ctx, pm_poseidon_ledger* t, u64 reserve, hipStream_t st) {
+  const size_t bytes = pm_poseidon_ledger_bytes(t->height, reserve);
+  void* d = nullptr;
+  PM_HIP(ctx, hipMalloc(&d, bytes));
+  hipError_t e = hipSuccess;
+  for (u32 l = 0; l <= t->height && e == hipSuccess && t->count; ++l)
+    e = hipMemcpyAsync((u32x4*)d + 2 * ledger_offset(reserve, l), ledger_level_ptr(t, l), 32 * (size_t)ledger_width(t->count, l),
+                       hipMemcpyDeviceToDevice, st);
+  const hipError_t waited = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = waited;
+  if (e != hipSuccess) {
+    (void)hipFree(d);
+    return set_err(ctx, PM_ERR_HIP, std::string("pm_poseidon_ledger_append_dev: ") + hipGetErrorString(e));
+  }
+  if (t->d_slab) (void)hipFree(t->d_slab);
+  t->d_slab = d, t->reserve = reserve;
+  return PM_OK;
+}
+
+void ledger_release(pm_poseidon_ledger* t) {
+  for (void* p : {t->d_slab, t->d_z, t->d_root, t->d_bad, t->own.d_tab})
+    if (p) (void)hipFree(p);
+  delete t;
+}
+}  // namespace
+
+extern "C" size_t pm_poseidon_ledger_bytes(uint32_t height, uint64_t reserve_leaves) {
+  if (height < 1 || height > PM_POSEIDON_LEDGER_MAX_HEIGHT || reserve_leaves > ledger_positions(height)) return 0;
+  const u64 elements = ledger_offset(reserve_leaves, height + 1);      // below 2^63
+  return elements > SIZE_MAX / 32 ? SIZE_MAX : 32 * (size_t)elements;  // more than an address space: no allocation succeeds
+}
+
+extern "C" int pm_poseidon_ledger_create(pm_ctx* ctx, const pm_hades_params* params, const uint64_t capacity[4], uint32_t height,
+                                         const uint64_t empty_leaf[4], uint64_t reserve_leaves, pm_poseidon_ledger** out) {
+  if (!ctx || !out) return PM_ERR_BAD_ARG;
+  if (int rc = params_fault(ctx, params)) return rc;
+  u32 cap[9];
+  if (int rc = capacity_to_dev(ctx, capacity, cap)) return rc;
+  if (height < 1 || height > PM_POSEIDON_LEDGER_MAX_HEIGHT) return set_err(ctx, PM_ERR_BAD_ARG, "height must be in 1 .. 31");
+  if (!empty_leaf || !hfr_canonical(empty_leaf)) return set_err(ctx, PM_ERR_BAD_ARG, "empty_leaf is null or not canonical");
+  if (reserve_leaves > ledger_positions(height)) return set_err(ctx, PM_ERR_BAD_ARG, "reserve_leaves exceeds 4^height");
+  pm_poseidon_ledger* t = new pm_poseidon_ledger();
+  t->device = ctx->device, t->height = height, t->reserve = reserve_leaves;
+  t->own.device = params->device, t->own.rounds = params->rounds, t->own.full = params->full, t->own.n_mds = params->n_mds;
+  t->own.ark = params->ark, t->own.mds = params->mds;
+  memcpy(t->capacity, cap, sizeof cap);
+  t->z.assign(4 * ((size_t)height + 1), 0);
+  memcpy(t->z.data(), empty_leaf, 32);
+  for (u32 l = 0; l < height; ++l) {                         // Z_(l+1) = word 1 of the permutation of (capacity, Z_l x 4)
+    const HFr zl = hfr_load(&t->z[4 * l]);
+    HFr s[5] = {hfr_load(capacity), zl, zl, zl, zl};
+    host_permute(params->rounds, params->full, params->ark.data(), params->mds.data(), params->n_mds, s);
+    memcpy(&t->z[4 * (l + 1)], s[1].l, 32);
+  }
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  hipError_t e = hipSetDevice(ctx->device);
+  const size_t slab = pm_poseidon_ledger_bytes(height, reserve_leaves), zb = 32 * ((size_t)height + 1);
+  if (e == hipSuccess) e = hipMalloc(&t->own.d_tab, table_bytes(*params));
+  if (e == hipSuccess) e = hipMalloc(&t->d_z, zb);
+  if (e == hipSuccess) e = hipMalloc(&t->d_root, 32);
+  if (e == hipSuccess) e = hipMalloc(&t->d_bad, 8);
+  if (e == hipSuccess && slab) e = hipMalloc(&t->d_slab, slab);
+  if (e == hipSuccess) e = hipMemcpy(t->own.d_tab, params->d_tab, table_bytes(*params), hipMemcpyDeviceToDevice);
+  if (e == hipSuccess) e = hipMemcpy(t->d_z, t->z.data(), zb, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(t->d_root, &t->z[4 * height], 32, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipDeviceSynchronize();           // the copy of the table: `params` may be freed after this call
+  if (e != hipSuccess) {
+    ledger_release(t);
+    return set_err(ctx, e == hipErrorOutOfMemory ? PM_ERR_OOM : PM_ERR_HIP, std::string("pm_poseidon_ledger_create: ") + hipGetErrorString(e));
+  }
+  *out = t;
+  return PM_OK;
+}
+
+extern "C" void pm_poseidon_ledger_free(pm_ctx* ctx, pm_poseidon_ledger* ledger) {
+  if (!ledger) return;
+  if (ctx) {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    (void)hipSetDevice(ctx->device);
+    (void)hipStreamSynchronize(ctx->stream);
+    ledger_release(ledger);                                  // hipFree waits for the device: launches on caller streams included
+    return;
+  }
+  delete ledger;
+}
+
+extern "C" int pm_poseidon_ledger_info(const pm_poseidon_ledger* ledger, uint32_t* height, uint64_t* count, uint64_t* reserve_leaves,
+                                       size_t* device_bytes) {
+  if (!ledger) return PM_ERR_BAD_ARG;
+  if (height) *height = ledger->height;
+  if (count) *count = ledger->count;
+  if (reserve_leaves) *reserve_leaves = ledger->reserve;
+  if (device_bytes)
+    *device_bytes = pm_poseidon_ledger_bytes(ledger->height, ledger->reserve) + 32 * ((size_t)ledger->height + 2) + table_bytes(ledger->own);
+  return PM_OK;
+}
+
+extern "C" int pm_poseidon_ledger_empty_roots(const pm_poseidon_ledger* ledger, uint64_t* out) {
+  if (!ledger || !out) return PM_ERR_BAD_ARG;
+  memcpy(out, ledger->z.data(), ledger->z.size() * 8);
+  return PM_OK;
+}
+
+extern "C" int pm_poseidon_ledger_level(const pm_poseidon_ledger* ledger, uint32_t level, void** d_ptr, uint64_t* nodes) {
+  if (!ledger || level > ledger->height) return PM_ERR_BAD_ARG;
+  if (d_ptr) *d_ptr = ledger->d_slab ? (void*)ledger_level_ptr(ledger, level) : nullptr;
+  if (nodes) *nodes = ledger_width(ledger->count, level);
+  return PM_OK;
+}
+
+extern "C" int pm_poseidon_ledger_append_dev(pm_ctx* ctx, pm_poseidon_ledger* ledger, const void* d_values, size_t k, uint32_t flags,
+                                             uint64_t* hashed, void* hip_stream) {
+  if (!ctx) return PM_ERR_BAD_ARG;
+  if (int rc = ledger_fault(ctx, ledger)) return rc;
+  if (flags > PM_HADES_FORM_WAVE) return set_err(ctx, PM_ERR_BAD_ARG, "flags must be PM_HADES_FORM_AUTO, _THREAD or _WAVE");
+  if (hashed) *hashed = 0;
+  if (k == 0) return PM_OK;
+  if (int rc = pointer_fault(ctx, {d_values})) return rc;
+  LedgerPlan plan;
+  if (int rc = ledger_plan(ledger->height, ledger->count, k, &plan))
+    return set_err(ctx, rc, "the tree cannot hold count + k leaves, or k > 2^31 - 1");
+  if (ledger_owns(ledger, d_values, k * 32)) return set_err(ctx, PM_ERR_BAD_ARG, "d_values overlaps the ledger's own memory");
+  PM_ENTER(ctx, hip_stream, st);
+  const u64 leaves = ledger->count + k;
+  if (leaves > ledger->reserve) {
+    const u64 twice = 2 * ledger->reserve, most = ledger_positions(ledger->height);
+    const u64 want = twice > leaves ? twice : leaves;
+    if (int rc = ledger_grow(ctx, ledger, want < most ? want : most, st)) return rc;
+  }
+  ProfScope prof(ctx, st, "poseidon_ledger_append");
+  PM_HIP(ctx, hipMemcpyAsync(ledger_level_ptr(ledger, 0) + 2 * ledger->count, d_values, k * 32, hipMemcpyDeviceToDevice, st));
+  PM_HIP(ctx, ledger_hash(ledger, plan, flags, st));
+  ledger->count = leaves;
+  if (hashed) *hashed = plan.hashed;
+  return PM_OK;
+}
+
+extern "C" int pm_poseidon_ledger_truncate_dev(pm_ctx* ctx, pm_poseidon_ledger* ledger, uint64_t new_count, uint32_t flags,
+                                               uint64_t* hashed, void* hip_stream) {
+  if (!ctx) return PM_ERR_BAD_ARG;
+  if (int rc = ledger_fault(ctx, ledger)) return rc;
+  if (flags > PM_HADES_FORM_WAVE) return set_err(ctx, PM_ERR_BAD_ARG, "flags must be PM_HADES_FORM_AUTO, _THREAD or _WAVE");
+  if (new_count > ledger->count) return set_err(ctx, PM_ERR_BAD_ARG, "new_count is above the count: a truncate cannot append");
+  if (hashed) *hashed = 0;
+  if (new_count == ledger->count) return PM_OK;
+  PM_ENTER(ctx, hip_stream, st);
+  ProfScope prof(ctx, st, "poseidon_ledger_truncate");
+  if (new_count == 0) {
+    PM_HIP(ctx, hipMemcpyAsync(ledger->d_root, (const u32x4*)ledger->d_z + 2 * ledger->height, 32, hipMemcpyDeviceToDevice, st));
+  } else {
+    LedgerPlan plan;                                         // the ancestors of leaf new_count - 1: its append to new_count - 1 leaves
+    if (int rc = ledger_plan(ledger->height, new_count - 1, 1, &plan)) return set_err(ctx, rc, "pm_poseidon_ledger_truncate_dev: no plan");
+    PM_HIP(ctx, ledger_hash(ledger, plan, flags, st));
+    if (hashed) *hashed = plan.hashed;
+  }
+  ledger->count = new_count;
+  return PM_OK;
+}
+
+extern "C" int pm_poseidon_ledger_root_dev(pm_ctx* ctx, const pm_poseidon_ledger* ledger, void* d_root, void* hip_stream) {
+  if (!ctx) return PM_ERR_BAD_ARG;
+  if (int rc = ledger_fault(ctx, ledger)) return rc;
+  if (int rc = pointer_fault(ctx, {d_root})) return rc;
+  if (ledger_owns(ledger, d_root, 32)) return set_err(ctx, PM_ERR_BAD_ARG, "d_root overlaps the ledger's own memory");
+  PM_ENTER(ctx, hip_stream, st);
+  PM_HIP(ctx, hipMemcpyAsync(d_root, ledger->d_root, 32, hipMemcpyDeviceToDevice, st));
+  return PM_OK;
+}
+
+extern "C" int pm_poseidon_ledger_root(pm_ctx* ctx, const pm_poseidon_ledger* ledger, uint64_t out[4], void* hip_stream) {
+  if (!ctx) return PM_ERR_BAD_ARG;
+  if (int rc = ledger_fault(ctx, ledger)) return rc;
+  if (!out) return set_err(ctx, PM_ERR_BAD_ARG, "null out");
+  PM_ENTER(ctx, hip_stream, st);
+  return finish_call(ctx, hipSuccess, st, out, ledger->d_root, 32, nullptr, "pm_poseidon_ledger_root");
+}
+
+extern "C" int pm_poseidon_ledger_paths_dev(pm_ctx* ctx, const pm_poseidon_ledger* ledger, const void* d_indices, size_t k, void* d_out,
+                                            void* hip_stream) {
+  if (!ctx) return PM_ERR_BAD_ARG;
+  if (int rc = ledger_fault(ctx, ledger)) return rc;
+  if (k == 0) return PM_OK;
+  if (int rc = pointer_fault(ctx, {d_out}, !d_indices || ((uintptr_t)d_indices & 7u))) return rc;
+  if (k > 0x7fffffffu / (4 * ledger->height)) return set_err(ctx, PM_ERR_LENGTH, "too many paths for one call");
+  if (ledger_owns(ledger, d_out, k * ledger->height * 128)) return set_err(ctx, PM_ERR_BAD_ARG, "d_out overlaps the ledger's own memory");
+  PM_ENTER(ctx, hip_stream, st);
+  unsigned long long* const d_bad = (unsigned long long*)ledger->d_bad;   // the handle's: no allocation a call
+  unsigned long long bad = ~0ull;
+  hipError_t e = hipMemcpyAsync(d_bad, &bad, 8, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    const LedgerView v{(const u32x4*)ledger->d_slab, (const u32x4*)ledger->d_z, ledger->count, ledger->reserve, ledger->height};
+    hipLaunchKernelGGL(ledger_index_check_kernel, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, st, (const u64*)d_indices, k,
+                       ledger->count, d_bad);
+    const size_t nodes = k * ledger->height * 4;
+    hipLaunchKernelGGL(ledger_paths_kernel, dim3((unsigned)((nodes + 255) / 256)), dim3(256), 0, st, v, (const u64*)d_indices, k,
+                       (u32x4*)d_out);
+    e = hipGetLastError();
+  }
+  if (int rc = finish_call(ctx, e, st, &bad, d_bad, 8, nullptr, "pm_poseidon_ledger_paths_dev")) return rc;
+  if (bad != ~0ull) return set_err(ctx, PM_ERR_BAD_ARG, "index " + std::to_string(bad) + " is not below the count");
+  return PM_OK;
+}
+
+extern "C" int pm_test_ledger_plan(uint32_t height, uint64_t count, uint64_t k, uint64_t* first, uint64_t* nodes, uint64_t* below,
+                                   uint32_t* chain_from, uint64_t* hashed) {
+  LedgerPlan plan;
+  const int rc = ledger_plan(height, count, k, &plan);
+  if (rc != PM_OK) return rc;
+  for (u32 l = 1; l <= height; ++l) {
+    if (first) first[l - 1] = plan.first[l];
+    if (nodes) nodes[l - 1] = plan.nodes[l];
+    if (below) below[l - 1] = plan.below[l];
+  }
+  if (chain_from) *chain_from = plan.chain_from;
+  if (hashed) *hashed = plan.hashed;
   return PM_OK;
 }
 

@@ -3,6 +3,7 @@
 // the sponge's absorption.  The forms, their bounds and the kernels are described in hades.hip.
 #pragma once
 #include <string>
+#include <vector>
 
 #include "context.h"
 #include "poly_common.hip.h"
@@ -11,6 +12,7 @@ struct pm_hades_params {
   int device = 0;
   uint32_t rounds = 0, full = 0, n_mds = 0;
   void* d_tab = nullptr;   // u32: mds [n_mds][25][9], then ark [rounds + 1][5][9] (the last row zero), device form
+  std::vector<uint64_t> ark, mds;   // the constants as _create took them, for host_permute: the empty roots of a ledger tree
 };
 
 namespace pm {

@@ -1,6 +1,7 @@
 """Native Poseidon on the GPU (``pm_hades_*`` / ``pm_poseidon_*``): the Hades permutation of width 5
 outside a circuit, the modelled sponge of rate 4 on top of it and an arity-4 Merkle tree with batched sibling paths, in-place
-leaf updates that hash only the changed leaves' ancestors and the bulk verification of paths (section 7.2n).
+leaf updates that hash only the changed leaves' ancestors and the bulk verification of paths (section 7.2n), and the append-only
+tree of ledger height that stores only what is filled (``LedgerTree``, section 7.2r).
 
 Field elements cross this interface as Montgomery limbs, ``uint64`` arrays with a last axis of 4 (``field.fr_vec_to_limbs``);
 constants and the capacity may also be given as Python integers.  With ``Hades.from_key`` the constants are those of a key's own
@@ -13,7 +14,7 @@ import numpy as np
 
 from . import _lib
 from .field import fr_to_limbs, fr_vec_to_limbs
-from .host import Context, DeviceVector, _p
+from .host import Context, DeviceVector, _DeviceView, _p
 
 WIDTH = _lib.PLONK_HADES_WIDTH
 FORMS = {"auto": _lib.HADES_FORM_AUTO, "thread": _lib.HADES_FORM_THREAD, "wave": _lib.HADES_FORM_WAVE}
@@ -177,18 +178,41 @@ class Hades:
         """[k, height, 4, 4] limbs as ``MerkleTree.paths`` gives them, k leaf indices and the root ([4] limbs or an integer)
         -> [k] uint32: 0 = the path folds to the root, 1 = the index is not below 4^height, 2 + l = the hash of level l is
         not the child the next level (the root after the last) holds at the path's position"""
-        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
-        k = idx.shape[0]
-        if k == 0:
-            return np.zeros(0, np.uint32)
-        a = _elements(paths, k * height * 4)
-        d_paths, d_root = DeviceVector.from_host(self.ctx, a), DeviceVector.from_host(self.ctx, _capacity(root).reshape(1, 4))
-        d_idx, d_status = _upload_words(self.ctx, idx), DeviceVector(self.ctx, (k + 7) // 8)
-        try:
-            self.verify_paths_dev(d_paths.ptr, d_idx.ptr, k, height, d_root.ptr, d_status.ptr, capacity, form)
-            return d_status.to_host().view(np.uint32).reshape(-1)[:k].copy()
-        finally:
-            d_paths.free(), d_root.free(), d_idx.free(), d_status.free()
+        return _verify_paths(self.ctx, self.verify_paths_dev, paths, indices, root, height, capacity, form)
+
+    # ------------------------------------------------------------------ the append-only tree (section 7.2r)
+    def ledger(self, height: int, capacity=0, empty_leaf=0, reserve: int = 0) -> "LedgerTree":
+        """``pm_poseidon_ledger_create``: an empty append-only tree of arity 4 and ``height`` (1 .. 31) with room for ``reserve``
+        leaves; ``empty_leaf`` is what an unfilled position holds"""
+        return LedgerTree(self, height, capacity, empty_leaf, reserve)
+
+    def verify_ledger_paths_dev(self, d_paths: int, d_indices: int, k: int, height: int, d_root: int, d_status: int, capacity=0,
+                                form="auto", stream: int = 0):
+        """``pm_poseidon_ledger_verify_dev``: ``verify_paths_dev`` for heights up to 31; asynchronous"""
+        c = self.ctx
+        c._check(c._lib.pm_poseidon_ledger_verify_dev(c._h, self._h, _p(_capacity(capacity)), C.c_void_p(d_paths),
+                                                      C.c_void_p(d_indices), k, height, C.c_void_p(d_root), C.c_void_p(d_status),
+                                                      _form(form), C.c_void_p(stream)))
+
+    def verify_ledger_paths(self, paths, indices, root, height: int, capacity=0, form="auto") -> np.ndarray:
+        """``verify_paths`` for a tree of ledger height (1 .. 31): the same status words"""
+        return _verify_paths(self.ctx, self.verify_ledger_paths_dev, paths, indices, root, height, capacity, form)
+
+
+def _verify_paths(ctx, verify_dev, paths, indices, root, height: int, capacity, form) -> np.ndarray:
+    """host arrays through one of the two verification entries (``verify_dev``: a bound ``*_paths_dev`` method) -> [k] uint32"""
+    idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+    k = idx.shape[0]
+    if k == 0:
+        return np.zeros(0, np.uint32)
+    a = _elements(paths, k * height * 4)
+    d_paths, d_root = DeviceVector.from_host(ctx, a), DeviceVector.from_host(ctx, _capacity(root).reshape(1, 4))
+    d_idx, d_status = _upload_words(ctx, idx), DeviceVector(ctx, (k + 7) // 8)
+    try:
+        verify_dev(d_paths.ptr, d_idx.ptr, k, height, d_root.ptr, d_status.ptr, capacity, form)
+        return d_status.to_host().view(np.uint32).reshape(-1)[:k].copy()
+    finally:
+        d_paths.free(), d_root.free(), d_idx.free(), d_status.free()
 
 
 def _upload_words(ctx, words: np.ndarray) -> DeviceVector:
@@ -282,3 +306,123 @@ class MerkleTree:
 
     def free(self):
         self.leaves.free(), self.nodes.free()
+
+
+class LedgerTree:
+    """An append-only Poseidon tree of arity 4 and a fixed ``height`` up to 31 (``pm_poseidon_ledger``):
+    leaves are filled from position 0 upward, only nodes with a filled descendant are stored, and everything to the right reads
+    as the empty subtree of its level (``empty_roots``).  The device handle keeps its own copy of the constants, so appends,
+    truncates, roots and paths go on after the ``Hades`` it came from is freed; ``verify`` runs through that ``Hades`` and needs
+    it alive.  Not for concurrent use."""
+
+    def __init__(self, hades: Hades, height: int, capacity=0, empty_leaf=0, reserve: int = 0):
+        ctx = hades.ctx
+        self.ctx, self.hades, self.capacity, self._h = ctx, hades, capacity, None
+        h = C.c_void_p()
+        ctx._check(ctx._lib.pm_poseidon_ledger_create(ctx._h, hades._h, _p(_capacity(capacity)), int(height),
+                                                      _p(_capacity(empty_leaf)), int(reserve), C.byref(h)))
+        self._h, self.height = h, int(height)
+
+    def _info(self):
+        count, reserve, nbytes = C.c_uint64(), C.c_uint64(), C.c_size_t()
+        self.ctx._check(self.ctx._lib.pm_poseidon_ledger_info(self._h, None, C.byref(count), C.byref(reserve), C.byref(nbytes)))
+        return count.value, reserve.value, nbytes.value
+
+    @property
+    def count(self) -> int:
+        return self._info()[0]
+
+    @property
+    def reserve(self) -> int:
+        return self._info()[1]
+
+    @property
+    def device_bytes(self) -> int:
+        return self._info()[2]
+
+    @property
+    def empty_roots(self) -> np.ndarray:
+        """[height + 1, 4] limbs: Z_0 = the empty leaf .. Z_height = the root of the empty tree"""
+        out = np.zeros((self.height + 1, 4), np.uint64)
+        self.ctx._check(self.ctx._lib.pm_poseidon_ledger_empty_roots(self._h, _p(out)))
+        return out
+
+    @property
+    def root(self) -> np.ndarray:
+        """``pm_poseidon_ledger_root``: waits for the context's stream"""
+        out = np.zeros(4, np.uint64)
+        self.ctx._check(self.ctx._lib.pm_poseidon_ledger_root(self.ctx._h, self._h, _p(out), None))
+        return out
+
+    def root_dev(self, d_root: int, stream: int = 0):
+        """``pm_poseidon_ledger_root_dev``: one element to ``d_root``, ordered on the stream"""
+        self.ctx._check(self.ctx._lib.pm_poseidon_ledger_root_dev(self.ctx._h, self._h, C.c_void_p(d_root), C.c_void_p(stream)))
+
+    def level(self, l: int) -> DeviceVector:
+        """a view of the stored prefix of level ``l`` (0 = the leaves); valid until the tree next grows"""
+        p, n = C.c_void_p(), C.c_uint64()
+        if not 0 <= l <= self.height:
+            raise ValueError("no such level")
+        self.ctx._check(self.ctx._lib.pm_poseidon_ledger_level(self._h, l, C.byref(p), C.byref(n)))
+        v = object.__new__(_DeviceView)
+        v.ctx, v.n, v._parent, v._p = self.ctx, n.value, self, C.c_void_p(p.value or 0)
+        return v
+
+    def append_dev(self, d_values: int, k: int, form="auto", stream: int = 0) -> int:
+        """``pm_poseidon_ledger_append_dev``: k elements in device memory become the next k leaves -> the permutations run;
+        asynchronous unless the tree has to grow"""
+        hashed = C.c_uint64(0)
+        self.ctx._check(self.ctx._lib.pm_poseidon_ledger_append_dev(self.ctx._h, self._h, C.c_void_p(d_values), k, _form(form),
+                                                                    C.byref(hashed), C.c_void_p(stream)))
+        return hashed.value
+
+    def append(self, values, form="auto") -> int:
+        """[k, 4] limbs or integers -> the permutations run"""
+        vals = _elements(values)
+        if vals.shape[0] == 0:
+            return 0
+        d = DeviceVector.from_host(self.ctx, vals)
+        try:
+            return self.append_dev(d.ptr, vals.shape[0], form)
+        finally:
+            d.free()                                                             # waits for the device
+
+    def truncate(self, count: int, form="auto", stream: int = 0) -> int:
+        """``pm_poseidon_ledger_truncate_dev``, the rollback: keep the first ``count`` leaves -> the permutations run"""
+        hashed = C.c_uint64(0)
+        self.ctx._check(self.ctx._lib.pm_poseidon_ledger_truncate_dev(self.ctx._h, self._h, int(count), _form(form),
+                                                                      C.byref(hashed), C.c_void_p(stream)))
+        return hashed.value
+
+    def paths_dev(self, d_indices: int, k: int, d_out: int, stream: int = 0):
+        """``pm_poseidon_ledger_paths_dev``: k uint64 indices below the count -> k x height x 4 elements; waits for the stream"""
+        self.ctx._check(self.ctx._lib.pm_poseidon_ledger_paths_dev(self.ctx._h, self._h, C.c_void_p(d_indices), k,
+                                                                   C.c_void_p(d_out), C.c_void_p(stream)))
+
+    def paths(self, indices) -> np.ndarray:
+        """-> [k, height, 4, 4] in the layout of ``MerkleTree.paths``; a sibling that is not stored is its level's empty root"""
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        k = idx.shape[0]
+        if k == 0:
+            return np.zeros((0, self.height, 4, 4), np.uint64)
+        d_idx, out = _upload_words(self.ctx, idx), DeviceVector(self.ctx, k * self.height * 4)
+        try:
+            self.paths_dev(d_idx.ptr, k, out.ptr)
+            return out.to_host().reshape(k, self.height, 4, 4)
+        finally:
+            d_idx.free(), out.free()
+
+    def verify(self, paths, indices, root=None, form="auto") -> np.ndarray:
+        """``Hades.verify_ledger_paths`` with this tree's constants, capacity and height; ``root`` defaults to the current root"""
+        return self.hades.verify_ledger_paths(paths, indices, self.root if root is None else root, self.height, self.capacity, form)
+
+    def free(self):
+        if getattr(self, "_h", None) and self.ctx._h:
+            self.ctx._lib.pm_poseidon_ledger_free(self.ctx._h, self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
