@@ -62,8 +62,11 @@ LOG_NON_SQUARES = [1, (1 << 8) + 1, (1 << 32) - 1]
 
 
 def sqrt_edge_inputs(seed: int = 11):
-    """0, 1, 4, r - 1, 7, d, then c^(2^32) g^k for a random c and the logarithms k at which a windowed search goes wrong: zero
-    windows, all-ones windows and carries across every window boundary"""
+    """0, 1, 4, r - 1, 7, d, then c^(2^32) g^k for a random c and the k of LOG_SQUARES + LOG_NON_SQUARES.  The windowed search
+    runs on a^t and t = (r - 1) / 2^32 is -1 mod 2^32, so it meets -k mod 2^32, not k: k = 2 is met as 0xfffffffe, all-ones
+    windows, and k = 2^32 - 2 as 2.  The list still holds zero windows, all-ones windows and carries across window boundaries
+    as MET logarithms only because it is nearly closed under negation (tests/test_fr_sqrt_tables.py checks the sign;
+    tests/fr_sqrt_cases.py has the inputs that are stated as what the search meets, and that reach every table entry)."""
     rng = random.Random(seed)
     out = [0, 1, 4, R - 1, 7, D]
     for k in LOG_SQUARES + LOG_NON_SQUARES:

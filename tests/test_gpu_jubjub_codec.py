@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import fr_sqrt_cases as F  # noqa: E402
 import gadget_model as M  # noqa: E402
 import jubjub_codec_model as CM  # noqa: E402
 import jubjub_model as J  # noqa: E402
@@ -322,3 +323,104 @@ def test_verify_bytes_gives_the_reasons_of_verify(ctx, handles):
     assert got.tolist() == want.tolist()
     assert [int(got[i]) for i in (3, 40, 64)] == [4, 2, 3] and int(np.count_nonzero(got)) == 3
     assert s.verify_bytes(pk_bytes[:0], msgs[:0], sig_bytes[:0]).shape == (0,)
+
+
+# ---------------------------------------------------------------------------------- 6. every table entry and every search digit
+def table_sqrt_case():
+    """the plain set of tests/fr_sqrt_cases.py: (limbs, the CONSTRUCTED roots as limbs, flags, the count of squares)"""
+    if "table_sqrt" not in _CACHE:
+        cases = F.plain_set()
+        flags = np.array([c.flag for c in cases], np.uint32)
+        even = sum(1 for c in cases if c.k is not None and c.k % 2 == 0)
+        assert int(flags.sum()) == even + 1, "the even logarithms and the zero input"
+        _CACHE["table_sqrt"] = (M.to_limbs([c.a for c in cases]), M.to_limbs([c.root for c in cases]), flags, even + 1)
+    return _CACHE["table_sqrt"]
+
+
+def table_decode_case(flag):
+    """the ratio set: (bytes [n, 32], the model's points as limbs, its statuses)"""
+    if ("table_decode", flag) not in _CACHE:
+        want = F.ratio_expected(flag)
+        _CACHE["table_decode", flag] = (_enc(F.ratio_set()), J.to_limbs([p for p, _ in want]), np.array([s for _, s in want], np.uint32))
+    return _CACHE["table_decode", flag]
+
+
+def _rows(got, want):
+    return np.flatnonzero((got.reshape(len(want), -1) != want.reshape(len(want), -1)).any(axis=1))[:8]
+
+
+def test_fr_sqrt_reads_every_reachable_table_entry(ctx):
+    """pm_fr_sqrt_dev on the whole plain set in one call -- 4239 elements whose logarithms carry every digit in every window of
+    the search and of the correction (tests/test_fr_sqrt_tables.py proves it, and that a wrong entry or key changes a root of
+    this set) -- against roots known by construction: out of place, again from the same bytes, and in place."""
+    import plonk_prototype_amd as pa
+    vals, roots, flags, squares = table_sqrt_case()
+    n = len(vals)
+    assert n % 64 != 0 and n > 4096
+    d = pa.DeviceVector.from_host(ctx, vals)
+    out = pa.DeviceVector.from_host(ctx, np.full((n, 4), SENTINEL, np.uint64))
+    f = pa.DeviceVector.from_host(ctx, np.full(((n + 7) // 8, 4), SENTINEL, np.uint64))
+    try:
+        for again in (False, True):
+            assert pa.fr_sqrt_dev(ctx, d.ptr, n, out.ptr, f.ptr, want_count=True) == squares, again
+            got, words = out.to_host(), f.to_host().view(np.uint32).reshape(-1)
+            assert words[:n].tolist() == flags.tolist(), (again, np.flatnonzero(words[:n] != flags)[:8])
+            assert got.tobytes() == roots.tobytes(), (again, _rows(got, roots))
+            assert (words[n:] == 0x77777777).all() and d.to_host().tobytes() == vals.tobytes()
+        assert pa.fr_sqrt_dev(ctx, d.ptr, n, d.ptr, f.ptr, want_count=True) == squares          # in place
+        got = d.to_host()
+        assert got.tobytes() == roots.tobytes(), _rows(got, roots)
+        assert f.to_host().view(np.uint32).reshape(-1)[:n].tolist() == flags.tolist()
+    finally:
+        d.free(), out.free(), f.free()
+
+
+@pytest.mark.parametrize("flag", (False, True), ids=("plain", "subgroup"))
+def test_decompress_reads_every_reachable_table_entry(ctx, flag):
+    """pm_jubjub_decompress_dev on the whole ratio set: 764 seeded y kept out of 3985 drawn, each with both sign bits, and one
+    y that is not below r: 1529 encodings.  Their radicands carry every digit in every window of the search and, on squares,
+    of the correction.  Points and statuses against the model; the count; and the encoder gives the bytes back.  It is the run
+    WITHOUT the flag that covers the tables: with it seven points in eight are refused as not in the subgroup whatever root was
+    found, so a wrong root hides behind the refusal; that run checks the second kernel over the same records."""
+    import plonk_prototype_amd as pa
+    data, points, status = table_decode_case(flag)
+    n = len(data)
+    assert n == 2 * len(F.ratio_ys()[0]) + 1 == 1529 and F.ratio_ys()[1] == 3985
+    good = status == 0
+    db = pa.DeviceVector.from_host(ctx, data.view(np.uint64))
+    out = pa.DeviceVector.from_host(ctx, np.full((2 * n, 4), SENTINEL, np.uint64))
+    ds = pa.DeviceVector.from_host(ctx, np.full(((n + 7) // 8, 4), SENTINEL, np.uint64))
+    back = pa.DeviceVector.from_host(ctx, np.full((n, 4), SENTINEL, np.uint64))
+    try:
+        assert pa.jubjub_decompress_dev(ctx, db.ptr, n, out.ptr, ds.ptr, flag) == int(good.sum())
+        got, words = out.to_host().reshape(n, 2, 4), ds.to_host().view(np.uint32).reshape(-1)
+        assert words[:n].tolist() == status.tolist(), np.flatnonzero(words[:n] != status)[:8]
+        assert got.tobytes() == points.tobytes(), _rows(got, points)
+        assert (words[n:] == 0x77777777).all() and not got[~good].any()
+        # the decoded points, refused ones and all, through the encoder: the rows that decoded are the input bytes
+        pa.jubjub_compress_dev(ctx, out.ptr, n, back.ptr)
+        ctx.sync()
+        again = back.to_host().view(np.uint8).reshape(n, 32)
+        assert again[good].tobytes() == data[good].tobytes(), _rows(again[good], data[good])
+    finally:
+        db.free(), out.free(), ds.free(), back.free()
+
+
+def test_fr_sqrt_slice_on_a_callers_stream_without_flags(ctx):
+    """d_is_square = NULL and no count, asynchronous on a caller's stream: a slice of the plain set that starts inside a wave
+    and ends inside another"""
+    import plonk_prototype_amd as pa
+    import torch
+    vals, roots, _, _ = table_sqrt_case()
+    lo, n = 37, 1000
+    st = torch.cuda.Stream()
+    d = pa.DeviceVector.from_host(ctx, vals)
+    out = pa.DeviceVector.from_host(ctx, np.full((len(vals), 4), SENTINEL, np.uint64))
+    try:
+        assert pa.fr_sqrt_dev(ctx, d.ptr + 32 * lo, n, out.ptr + 32 * lo, 0, stream=st.cuda_stream) is None
+        st.synchronize()
+        got = out.to_host()
+        assert got[lo:lo + n].tobytes() == roots[lo:lo + n].tobytes(), lo + _rows(got[lo:lo + n], roots[lo:lo + n])
+        assert (got[:lo] == SENTINEL).all() and (got[lo + n:] == SENTINEL).all(), "nothing outside the slice is written"
+    finally:
+        d.free(), out.free()
