@@ -126,8 +126,9 @@ int pm_domain_evaluate_all_lagrange_coefficients(uint32_t log_n, const uint64_t 
 int pm_domain_evaluate_all_lagrange_coefficients_dev(pm_ctx* ctx, uint32_t log_n, const uint64_t tau[4], void* d_out,
                                                      void* hip_stream);
 
-/* Build (and cache on the device) the twiddle tables of the 2^log_n domain.  Optional: the
- * first transform of a size does it implicitly. */
+/* Build (and cache on the device) the twiddle tables of the 2^log_n domain: every table that fft, ifft,
+ * coset_fft and coset_ifft of that size read under the options in force, for any input length.  Optional: the
+ * first transform of a size builds what it reads itself. */
 int pm_domain_prepare(pm_ctx* ctx, uint32_t log_n);
 
 /* out[0 .. 2^log_n) = transform of in[0 .. in_len) zero-padded to 2^log_n (the reference's
@@ -1471,6 +1472,22 @@ int pm_test_ntt_fixed_match(uint32_t S, uint32_t LT, uint32_t role, uint32_t log
 /* Which kernel each pass of the context's last transform was launched with -- out[4], a pass each: 0 no such pass (sizes below
  * 2^3 have no pass kernels), 1 the generic kernel, 2 its fixed-shape variant. */
 int pm_test_ntt_last_variants(pm_ctx* ctx, uint32_t out[4]);
+/* Pure host, no context, no device: everything pm_fr_ntt* resolves for a transform before it launches anything -- batch
+ * vectors of 2^log_n points with in_len elements present, flags PM_NTT_INVERSE / PM_NTT_COSET.  opts[8] = the options
+ * ntt_tile_log, ntt_max_radix, ntt_radix (0 = a fresh context's default, as in pm_test_ntt_plan), then the switches
+ * ntt_xcd, ntt_direct_tw, ntt_tw_producer, ntt_step_prio, ntt_fixed_shape (negative = the default: 0 is a value of
+ * theirs); num_cus 0 = 256.  out[60] = {0 passes, 1 log2 group size of the blocked intermediate layout, 2 whether the
+ * tiny kernel (sizes 2 and 4) runs, 3 its PASS_* flags, 4 whether n^-1 of an inverse transform is folded into the last
+ * pass's inter-pass table, 5-7 zero}, then 13 words per pass (up to 4): {log2 radix S, log2 columns per tile LT, role (0
+ * single, 1 first, 2 middle, 3 last), kernel family (4 or 8), variant (1 generic, 2 fixed-shape), threads per workgroup,
+ * LDS bytes, workgroups per vector, the complete PASS_* flags, log_ns (stages done before the pass), form G of the lazy step
+ * table its kernel reads (0: none), the pass whose inter-pass table it reads through pass_tw, the pass whose table it
+ * applies to its outputs through pass_tw_out (-1: none)}.  PM_ERR_BAD_ARG also for a pass shape without a kernel. */
+int pm_test_ntt_launches(uint32_t log_n, uint32_t batch, uint32_t flags, uint64_t in_len, const long opts[8],
+                         uint32_t num_cus, int32_t out[60]);
+/* How many device tables the context caches for the NTT: domain and coset tables (a low and a high one each), step tables,
+ * lazy step tables and inter-pass tables, both directions. */
+int pm_test_ntt_table_count(pm_ctx* ctx, size_t* count);
 /* Pure host, no context: the geometry of pm_plonk_sigma_from_wires' sort (csrc/wire_perm.hip) -- passes =
  * max(1, ceil(bits(num_vars - 1) / 8)) 8-bit digit passes, tiles = ceil(4n / 4096) workgroups per pass, scratch_bytes = the
  * transient device memory of the call.  Each out pointer may be NULL.  The errors of pm_plonk_sigma_from_wires for n and

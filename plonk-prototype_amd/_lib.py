@@ -312,6 +312,9 @@ SIGNATURES = {
     "pm_test_ntt_exchange_map": (C.c_int, [C.c_uint32] * 5 + [C.POINTER(C.c_uint32)]),
     "pm_test_ntt_fixed_match": (C.c_int, [C.c_uint32] * 7 + [C.c_uint64, C.c_uint32, C.c_uint32]),
     "pm_test_ntt_last_variants": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "pm_test_ntt_launches": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.POINTER(C.c_long), C.c_uint32,
+                                       C.POINTER(C.c_int32)]),
+    "pm_test_ntt_table_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),
     "pm_test_ntt_step4_table": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, u32p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "pm_test_ntt_step4_lazy_table": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, u32p, C.c_size_t,
                                                C.POINTER(C.c_size_t)]),

@@ -287,6 +287,19 @@ extern "C" int pm_comm_info(const pm_ctx* ctx, int* rank, int* world) {
   return PM_OK;
 }
 
+extern "C" int pm_comm_stats(pm_ctx* ctx, uint64_t out[4], int reset) {
+  if (!ctx) return PM_ERR_BAD_ARG;
+  std::lock_guard<std::mutex> lk(ctx->mu);
+  if (out) {
+    out[0] = ctx->stat_alltoall_calls;
+    out[1] = ctx->stat_alltoall_bytes;
+    out[2] = ctx->stat_allgather_calls;
+    out[3] = ctx->stat_transpose_steps;
+  }
+  if (reset) ctx->stat_alltoall_calls = ctx->stat_alltoall_bytes = ctx->stat_allgather_calls = ctx->stat_transpose_steps = 0;
+  return PM_OK;
+}
+
 // All-gather of the fixed-size message on the context's communicator: gathered = world x COMM_MSG_WORDS words (host
 // memory).  msg[0] = 0 is the abort marker; a rank that cannot stage its message still enters the collective with it
 // (written by a memset), so that no peer waits in ncclAllGather for ever (it has no timeout).  The caller holds ctx->mu.

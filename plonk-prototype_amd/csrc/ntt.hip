@@ -1,7 +1,9 @@
-// Host side of the Fr NTT: domain tables, pass planning, launches, and the pm_fr_ntt* ABI.
+// Host side of the Fr NTT: the driver -- resolve a transform's passes (ntt_resolve), acquire the tables they name
+// (ntt_acquire), launch (ntt_run) -- and the pm_fr_ntt*, pm_domain_prepare, pm_ntt_plan and NTT test-hook entry points.
 // Mirrors dusk_plonk::fft::EvaluationDomain (dusk-plonk 0.8.2, ref:Cargo.toml:19):
-//   new()      -> domain_constants()  (group_gen = ROOT_OF_UNITY^(2^(32-log_n)), size_inv, ...)
+//   new()      -> domain_gen()  (group_gen = ROOT_OF_UNITY^(2^(32-log_n)); pm_domain_info and the helpers: domain.hip)
 //   fft/ifft/coset_fft/coset_ifft -> ntt_run() with PM_NTT_INVERSE / PM_NTT_COSET
+// The transform split over ranks is ntt_fourstep.hip.
 #include <hip/hip_runtime.h>
 
 #include <condition_variable>
@@ -10,8 +12,7 @@
 #include <algorithm>
 #include <cstring>
 
-#include "context.h"
-#include "host_field.h"
+#include "ntt_internal.h"
 #include "ntt_kernels.hip.h"
 
 namespace pm {
@@ -19,9 +20,6 @@ namespace pm {
 using host::HFr;
 
 // ------------------------------------------------------------------ kernel table
-typedef void (*pass_fn)(const NttPassArgs, const NttConsts);
-enum Role { ROLE_SINGLE = 0, ROLE_FIRST = 1, ROLE_MIDDLE = 2, ROLE_LAST = 3 };
-pass_fn find_pass4(int S, int LT, int role);   // radix-4 kernels (ntt4.hip)
 struct PassEntry {
   int S, LT, role;
   pass_fn fn;
@@ -46,23 +44,6 @@ static pass_fn find_pass(int S, int LT, int role) {
     if (e.S == S && e.LT == LT && e.role == role) return e.fn;
   return nullptr;
 }
-
-// radix-4 kernels (ntt4.hip)
-size_t pass4_lds(int S, int LT);
-unsigned pass4_threads(int S, int LT);
-bool pass4_tw_producer(int S, int LT, int role);
-bool pass4_step_prio(int S, int LT, int role);
-#ifdef PM_DEV_STAMPS
-int ntt_stamps_arm(pm_ctx* ctx, hipStream_t st, int pass, size_t waves);
-#endif
-int build_step4_table(pm_ctx* ctx, void** out, const NttConsts& c, unsigned S, hipStream_t st);
-size_t step4_table_bytes(unsigned S);
-int pass4_lazy_form(int S, int LT, int role);
-// fixed-shape variants (ntt4_fixed.hip): the kernel for a launch that equals one exactly, else null
-pass_fn find_pass4_fixed(int S, int LT, int role, unsigned log_n, unsigned log_ns, unsigned wide_glog, unsigned flags,
-                         unsigned long long in_len, bool coset, long mode, int* lazy_form);
-int build_step4_lazy_table(pm_ctx* ctx, void** out, const NttConsts& c, unsigned S, unsigned G, hipStream_t st);
-size_t step4_lazy_table_bytes(unsigned S, unsigned G);
 
 struct Plan {
   int npass = 0;
@@ -107,13 +88,121 @@ static Plan make_plan(unsigned log_n, int tile_log, int max_radix = 10, int radi
   }
   return p;
 }
+// log2 of the block size of the wide (intermediate) layout: part of the key of the inter-pass tables
+static unsigned plan_wide_glog(const Plan& plan) {
+  int min_lt = 3;
+  for (int i = 0; i < plan.npass; ++i) min_lt = std::min(min_lt, plan.LT[i]);
+  return (unsigned)std::max(min_lt, 2);
+}
+
+// ------------------------------------------------------------------ resolution
+// Everything a transform decides, before anything is allocated or launched: host arithmetic, no HIP call, no context.
+// ntt_run() and pm_domain_prepare() acquire the tables the result names (ntt_acquire) and ntt_run() launches from it;
+// pm_test_ntt_plan / pm_test_ntt_launches show it to the CPU tests.
+struct NttOpts {   // the options "ntt_*" a plan depends on
+  long tile_log, max_radix, radix, xcd, direct_tw, tw_producer, step_prio, fixed_shape;
+};
+static const NttOpts kDefaultOpts = {0, 10, 4, 1, 1, 1, PM_NTT_STEP_PRIO_DEFAULT, PM_NTT_FIXED_SHAPE_DEFAULT};   // a fresh context's (context.h)
+// the fixed-shape variant a launch takes under ntt_fixed_shape = mode, or null: the launch of a radix-4 kernel that equals
+// the variant's in every respect (find_pass4_fixed); *lazy_form (may be null) receives the G of the lazy table it reads
+static pass_fn fixed_variant(int S, int LT, int role, unsigned log_n, unsigned log_ns, unsigned wide_glog, unsigned flags,
+                             unsigned long long in_len, bool coset, long mode, int* lazy_form) {
+  if (!mode || find_pass4(S, LT, role) == nullptr) return nullptr;
+  return find_pass4_fixed(S, LT, role, log_n, log_ns, wide_glog, flags, in_len, coset, mode, lazy_form);
+}
+struct PassLaunch {
+  int S, LT, role;
+  bool r4;                  // a kernel of the radix-4 family (else radix-8)
+  pass_fn fn;               // null: no kernel for this shape
+  int variant;              // 1 the generic kernel, 2 its fixed-shape variant
+  unsigned threads, blocks;
+  size_t lds;
+  u32 flags;                // the complete PASS_* word
+  unsigned log_ns;          // stages done before this pass
+  int lazy;                 // form G of the lazy step table the chosen kernel reads, 0: none
+  int tw_in, tw_out;        // the pass whose inter-pass table this one reads (pass_tw) / applies to its outputs (pass_tw_out); -1: none
+};
+struct NttLaunches {
+  int npass;                // 0: the tiny kernel, or nothing at all (log_n = 0)
+  bool tiny;
+  u32 tiny_flags;
+  bool scale_folded;        // n^-1 of an inverse transform is in the last pass's inter-pass table
+  unsigned wide_glog;
+  PassLaunch pass[4];
+};
+static NttLaunches ntt_resolve(const NttOpts& o, unsigned num_cus, unsigned log_n, unsigned batch, unsigned flags,
+                               unsigned long long in_len) {
+  NttLaunches L;
+  memset(&L, 0, sizeof L);
+  const bool inverse = (flags & PM_NTT_INVERSE) != 0, coset = (flags & PM_NTT_COSET) != 0;
+  const bool direct_tw = log_n <= 26 && o.direct_tw;  // tables of N x 36 B per twiddled pass and direction
+  const Plan plan = make_plan(log_n, (int)o.tile_log, (int)o.max_radix, (int)o.radix, num_cus, batch);
+  L.npass = plan.npass;
+  // n^-1 of an inverse transform: folded into the last pass's twiddle table when there are two
+  // or more passes with direct tables; otherwise multiplied explicitly (PASS_POST_SCALE)
+  L.scale_folded = inverse && plan.npass > 1 && direct_tw;
+  const u32 pre = (coset && !inverse) ? PASS_PRE_COSET : 0u;
+  const u32 post = ((inverse && !L.scale_folded) ? PASS_POST_SCALE : 0u) | ((inverse && coset) ? PASS_POST_COSET : 0u);
+  if (plan.npass == 0) {
+    L.tiny = log_n > 0;   // a size-1 domain is the identity
+    L.tiny_flags = pre | post;
+    return L;
+  }
+  L.wide_glog = plan_wide_glog(plan);
+  auto role_of = [&](int i) {
+    return plan.npass == 1 ? ROLE_SINGLE : (i == 0 ? ROLE_FIRST : (i == plan.npass - 1 ? ROLE_LAST : ROLE_MIDDLE));
+  };
+  unsigned log_ns = 0;
+  for (int i = 0; i < plan.npass; ++i) {
+    PassLaunch& p = L.pass[i];
+    const bool last = (i == plan.npass - 1);
+    const int S = p.S = plan.S[i], LT = p.LT = plan.LT[i], role = p.role = role_of(i);
+    pass_fn fn4 = o.radix == 4 ? find_pass4(S, LT, role) : nullptr;
+    p.r4 = fn4 != nullptr;
+    p.fn = p.r4 ? fn4 : find_pass(S, LT, role);
+    p.variant = 1;
+    p.lazy = p.r4 ? pass4_lazy_form(S, LT, role) : 0;   // this shape's step products read the lazy table
+    p.threads = p.r4 ? pass4_threads(S, LT) : std::max(64u, (1u << (S + LT)) / 8);
+    p.lds = p.r4 ? pass4_lds(S, LT) : pass_lds_bytes(S, LT);
+    p.blocks = (unsigned)(((size_t)1 << log_n) >> (S + LT));
+    p.log_ns = log_ns;
+    p.tw_in = p.tw_out = -1;
+    u32 tw_flag = 0;
+    if (i > 0 && L.pass[i - 1].tw_out == i) {   // the pass before this one multiplied by this pass's table
+      tw_flag = PASS_TW_APPLIED;
+    } else if (i > 0 && direct_tw) {
+      p.tw_in = i;
+      tw_flag = PASS_DIRECT_TW;
+    }
+    // this pass applies the next one's table to its outputs where both are radix-4 kernels and its shape takes the product
+    if (!last && direct_tw && o.tw_producer && p.r4 && pass4_tw_producer(S, LT, role) &&
+        find_pass4(plan.S[i + 1], plan.LT[i + 1], role_of(i + 1)) != nullptr) {
+      p.tw_out = i + 1;
+      tw_flag |= PASS_TW_OUT;
+    }
+    p.flags = (i == 0 ? pre : 0u) | (last ? post : 0u) | tw_flag | (o.xcd ? PASS_XCD_REMAP : 0u);
+    if (p.r4 && o.step_prio && pass4_step_prio(S, LT, role)) p.flags |= PASS_STEP_PRIO;   // wave priorities by step
+    // a launch that is a fixed-shape variant's in every respect takes it: same arguments, grid and LDS, fewer instructions,
+    // and the form of the lazy table that the variant reads
+    if (p.r4) {
+      int flazy = 0;
+      if (pass_fn ffn = fixed_variant(S, LT, role, log_n, log_ns, L.wide_glog, p.flags, in_len, coset, o.fixed_shape, &flazy)) {
+        p.fn = ffn;
+        p.variant = 2;
+        p.lazy = flazy;
+      }
+    }
+    log_ns += (unsigned)S;
+  }
+  return L;
+}
 
 // ------------------------------------------------------------------ host constants
 static HFr fr_pow2k(HFr x, unsigned k) {  // x^(2^k)
   for (unsigned i = 0; i < k; ++i) x = host::mul(x, x, host::FR());
   return x;
 }
-static HFr domain_gen(unsigned log_n) { return fr_pow2k(host::fr_root_of_unity(), 32 - log_n); }
+HFr domain_gen(unsigned log_n) { return fr_pow2k(host::fr_root_of_unity(), 32 - log_n); }
 // ABI Montgomery form (x * 2^256) -> device form (x * 2^261) as 9 x 29-bit limbs
 static void to_limbs(u32* dst, HFr v) {
   for (int i = 0; i < 5; ++i) v = host::add(v, v, host::FR());
@@ -144,81 +233,44 @@ static int build_pow_table(pm_ctx* ctx, void** out, const HFr& base, const HFr& 
   return PM_OK;
 }
 
-static int get_step_table(pm_ctx* ctx, int dir, unsigned S, void** out, hipStream_t st) {
-  auto it = ctx->step_tw[dir].find(S);
-  if (it != ctx->step_tw[dir].end()) {
-    *out = it->second;
-    return PM_OK;
+// One cached device table: the entry of `map` under `key`, built by `build` on first use and published only when it was built.
+template <class Build>
+static int cached_table(std::map<unsigned, void*>& map, unsigned key, void** out, Build build) {
+  auto it = map.find(key);
+  if (it == map.end()) {
+    void* d = nullptr;
+    if (int rc = build(&d)) return rc;
+    it = map.emplace(key, d).first;
   }
-  HFr wR = domain_gen(S);
-  if (dir) wR = host::inv(wR, host::FR());
-  u32 total = (u32)step_tw_total((int)S);
-  void* d = nullptr;
-  PM_HIP(ctx, hipMalloc(&d, (size_t)total * 48));
-  NttConsts c;
-  memset(&c, 0, sizeof c);
-  to_limbs(c.w8[0], wR);
-  to_limbs(c.one, host::one(host::FR()));
-  hipLaunchKernelGGL(step_tw_kernel, dim3((total + 255) / 256), dim3(256), 0, st, (u32x4*)d, c, S);
-  PM_HIP(ctx, hipGetLastError());
-  ctx->step_tw[dir][S] = d;
-  *out = d;
+  *out = it->second;
   return PM_OK;
 }
 
-static int get_step4_table(pm_ctx* ctx, int dir, unsigned S, void** out, hipStream_t st) {
-  auto it = ctx->step4_tw[dir].find(S);
-  if (it != ctx->step4_tw[dir].end()) {
-    *out = it->second;
+// The in-tile step table of radix 2^S and one direction, built once per context.  kind: STEP_R8 the radix-8 family's table,
+// STEP_R4 the radix-4 family's (it starts with the split rows of this direction's w4 and of the powers of its w16), G > 0 the
+// radix-4 family's lazy split table in form G (ntt_kernels4.hip.h).
+enum { STEP_R8 = -1, STEP_R4 = 0 };
+static int get_step_table(pm_ctx* ctx, int dir, unsigned S, int kind, void** out, hipStream_t st) {
+  std::map<unsigned, void*>& map = kind == STEP_R8 ? ctx->step_tw[dir] : kind == STEP_R4 ? ctx->step4_tw[dir] : ctx->step4_lazy_tw[dir];
+  return cached_table(map, kind > 0 ? (S << 8 | (unsigned)kind) : S, out, [&](void** d) -> int {
+    auto root = [&](unsigned lg) { return dir ? host::inv(domain_gen(lg), host::FR()) : domain_gen(lg); };
+    NttConsts c;
+    memset(&c, 0, sizeof c);
+    to_limbs(c.w8[0], root(S));
+    if (kind != STEP_R8) to_limbs(c.w8[1], root(2));
+    if (kind == STEP_R4) to_limbs(c.w8[2], root(4));
+    to_limbs(c.one, host::one(host::FR()));
+    if (kind > 0) return build_step4_lazy_table(ctx, d, c, S, (unsigned)kind, st);
+    if (kind == STEP_R4) return build_step4_table(ctx, d, c, S, st);
+    const u32 total = (u32)step_tw_total((int)S);
+    PM_HIP(ctx, hipMalloc(d, (size_t)total * 48));
+    hipLaunchKernelGGL(step_tw_kernel, dim3((total + 255) / 256), dim3(256), 0, st, (u32x4*)*d, c, S);
+    PM_HIP(ctx, hipGetLastError());
     return PM_OK;
-  }
-  HFr wR = domain_gen(S);
-  if (dir) wR = host::inv(wR, host::FR());
-  HFr w4 = domain_gen(2);   // the table starts with the split rows of this direction's w4 and of the powers of its w16
-  HFr w16 = domain_gen(4);
-  if (dir) w4 = host::inv(w4, host::FR());
-  if (dir) w16 = host::inv(w16, host::FR());
-  NttConsts c;
-  memset(&c, 0, sizeof c);
-  to_limbs(c.w8[0], wR);
-  to_limbs(c.w8[1], w4);
-  to_limbs(c.w8[2], w16);
-  to_limbs(c.one, host::one(host::FR()));
-  void* d = nullptr;
-  int rc = build_step4_table(ctx, &d, c, S, st);
-  if (rc) return rc;
-  ctx->step4_tw[dir][S] = d;
-  *out = d;
-  return PM_OK;
+  });
 }
 
-// the lazy split table of radix 2^S in form G (ntt_kernels4.hip.h), built once per (S, direction, form) like the table above
-static int get_step4_lazy_table(pm_ctx* ctx, int dir, unsigned S, unsigned G, void** out, hipStream_t st) {
-  const unsigned key = S << 8 | G;
-  auto it = ctx->step4_lazy_tw[dir].find(key);
-  if (it != ctx->step4_lazy_tw[dir].end()) {
-    *out = it->second;
-    return PM_OK;
-  }
-  HFr wR = domain_gen(S);
-  HFr w4 = domain_gen(2);
-  if (dir) wR = host::inv(wR, host::FR());
-  if (dir) w4 = host::inv(w4, host::FR());
-  NttConsts c;
-  memset(&c, 0, sizeof c);
-  to_limbs(c.w8[0], wR);
-  to_limbs(c.w8[1], w4);
-  to_limbs(c.one, host::one(host::FR()));
-  void* d = nullptr;
-  int rc = build_step4_lazy_table(ctx, &d, c, S, G, st);
-  if (rc) return rc;
-  ctx->step4_lazy_tw[dir][key] = d;
-  *out = d;
-  return PM_OK;
-}
-
-static int get_domain_tables(pm_ctx* ctx, int dir, unsigned log_n, bool need_coset,
-                             NttDomainTables** out, hipStream_t st) {
+int get_domain_tables(pm_ctx* ctx, int dir, unsigned log_n, bool need_coset, NttDomainTables** out, hipStream_t st) {
   NttDomainTables& t = ctx->domain[dir][log_n];
   const host::Field<4>& F = host::FR();
   t.lh = (log_n + 1) / 2;
@@ -272,11 +324,6 @@ static void fill_consts(NttConsts& c, int dir, unsigned log_n) {
 
 // Inter-pass twiddle table of pass i (N x 36 B, laid out like the wide data): built on first use for
 // the plan in force, rebuilt when the tunables changed the plan.
-static unsigned plan_wide_glog(const Plan& plan) {
-  int min_lt = 3;
-  for (int i = 0; i < plan.npass; ++i) min_lt = std::min(min_lt, plan.LT[i]);
-  return (unsigned)std::max(min_lt, 2);
-}
 static int get_pass_tw(pm_ctx* ctx, NttDomainTables* dt, int i, bool last, int dir, unsigned log_n, unsigned log_ns,
                        int S, unsigned wide_glog, const NttConsts& kc, hipStream_t st, void** out) {
   const size_t n = (size_t)1 << log_n;
@@ -305,22 +352,69 @@ static int get_pass_tw(pm_ctx* ctx, NttDomainTables* dt, int i, bool last, int d
   return PM_OK;
 }
 
+// ------------------------------------------------------------------ acquisition
+// Every table a resolved plan names, present in the context's caches and by pointer: the domain tables (with the coset's for
+// a coset transform), per pass the step table of its family, the lazy table in the form its kernel reads, and the
+// inter-pass tables it reads or applies.  Builds what is missing on st; a second call with the same plan builds nothing.
+struct NttTables {
+  NttDomainTables* dt;
+  NttConsts kc;
+  void *step[4], *lazy[4], *tw_in[4], *tw_out[4];
+};
+static int ntt_acquire(pm_ctx* ctx, const NttLaunches& L, unsigned log_n, unsigned flags, hipStream_t st, NttTables* T) {
+  const int dir = (flags & PM_NTT_INVERSE) ? 1 : 0;
+  memset(T, 0, sizeof *T);
+  int rc = get_domain_tables(ctx, dir, log_n, (flags & PM_NTT_COSET) != 0, &T->dt, st);
+  if (rc) return rc;
+  fill_consts(T->kc, dir, log_n);
+  auto pass_tw = [&](int j, void** out) {   // the inter-pass table of pass j: its consumer and its producer name the same one
+    const PassLaunch& q = L.pass[j];
+    return get_pass_tw(ctx, T->dt, j, q.role == ROLE_LAST, dir, log_n, q.log_ns, q.S, L.wide_glog, T->kc, st, out);
+  };
+  for (int i = 0; i < L.npass; ++i) {
+    const PassLaunch& p = L.pass[i];
+    rc = get_step_table(ctx, dir, (unsigned)p.S, p.r4 ? STEP_R4 : STEP_R8, &T->step[i], st);
+    if (!rc && p.lazy) rc = get_step_table(ctx, dir, (unsigned)p.S, p.lazy, &T->lazy[i], st);
+    if (!rc && p.tw_in >= 0) rc = pass_tw(p.tw_in, &T->tw_in[i]);
+    if (!rc && p.tw_out >= 0) rc = pass_tw(p.tw_out, &T->tw_out[i]);
+    if (rc) return rc;
+  }
+  return PM_OK;
+}
+
 // ------------------------------------------------------------------ execution
-int ntt_run(pm_ctx* ctx, const void* d_in, size_t in_len, size_t in_stride, void* d_out,
-            size_t out_stride, unsigned log_n, unsigned batch, unsigned flags, hipStream_t st) {
+static NttOpts ntt_opts(const pm_ctx* ctx) {
+  return NttOpts{ctx->opt_ntt_tile_log, ctx->opt_ntt_max_radix, ctx->opt_ntt_radix,     ctx->opt_ntt_xcd,
+                 ctx->opt_ntt_direct_tw, ctx->opt_ntt_tw_producer, ctx->opt_ntt_step_prio, ctx->opt_ntt_fixed_shape};
+}
+// the argument checks of pm_fr_ntt_dev and pm_fr_ntt_batch; *empty: a batch of none, nothing to do
+static int ntt_check_args(pm_ctx* ctx, size_t in_len, size_t in_stride, size_t out_stride, unsigned log_n, unsigned batch,
+                          unsigned flags, bool* empty) {
+  *empty = false;
   if (log_n >= host::FR_TWO_ADICITY)
     return set_err(ctx, PM_ERR_DOMAIN_TOO_LARGE, "log_n >= 32 (Fr two-adicity)");
   const size_t n = (size_t)1 << log_n;
   if (in_len > n) return set_err(ctx, PM_ERR_LENGTH, "in_len > 2^log_n");
-  if (batch == 0) return PM_OK;
+  if (batch == 0) {
+    *empty = true;
+    return PM_OK;
+  }
   if (batch > 1 && (in_stride < in_len || out_stride < n))
     return set_err(ctx, PM_ERR_BAD_ARG, "batch strides shorter than the vectors");
   if (flags & ~(PM_NTT_INVERSE | PM_NTT_COSET)) return set_err(ctx, PM_ERR_BAD_ARG, "unknown flags");
+  return PM_OK;
+}
+
+int ntt_run(pm_ctx* ctx, const void* d_in, size_t in_len, size_t in_stride, void* d_out,
+            size_t out_stride, unsigned log_n, unsigned batch, unsigned flags, hipStream_t st) {
+  // validate
+  bool empty = false;
+  if (int rc = ntt_check_args(ctx, in_len, in_stride, out_stride, log_n, batch, flags, &empty)) return rc;
+  if (empty) return PM_OK;
+  const size_t n = (size_t)1 << log_n;
   PM_HIP(ctx, hipSetDevice(ctx->device));
   OrderScope order_scope(ctx, ctx->ord_ntt, st);   // scratch vectors and lazily built tables are shared by all streams
   if (order_scope.rc) return order_scope.rc;
-  const int dir = (flags & PM_NTT_INVERSE) ? 1 : 0;
-  const bool coset = (flags & PM_NTT_COSET) != 0;
   memset(ctx->ntt_last_variant, 0, sizeof ctx->ntt_last_variant);   // what pm_test_ntt_last_variants reports: this transform's passes
 
   if (log_n == 0) {  // size-1 domain: identity (w = 1, size_inv = 1, g^0 = 1); zero if in_len == 0
@@ -336,144 +430,73 @@ int ntt_run(pm_ctx* ctx, const void* d_in, size_t in_len, size_t in_stride, void
     return PM_OK;
   }
 
-  NttDomainTables* dt = nullptr;
-  int rc = get_domain_tables(ctx, dir, log_n, coset, &dt, st);
+  // resolve, acquire, choose buffers
+  const NttLaunches L = ntt_resolve(ntt_opts(ctx), (unsigned)ctx->num_cus, log_n, batch, flags, in_len);
+  for (int i = 0; i < L.npass; ++i)
+    if (!L.pass[i].fn) return set_err(ctx, PM_ERR_BAD_ARG, "no kernel for this pass shape");
+  NttTables T;
+  int rc = ntt_acquire(ctx, L, log_n, flags, st, &T);
   if (rc) return rc;
-  NttConsts kc;
-  fill_consts(kc, dir, log_n);
-
-  NttPassArgs a;
-  memset(&a, 0, sizeof a);
-  a.tw_hi = (const u32x4*)dt->tw_hi;
-  a.tw_lo = (const u32x4*)dt->tw_lo;
-  a.cs_hi = (const u32x4*)dt->cs_hi;
-  a.cs_lo = (const u32x4*)dt->cs_lo;
-  a.log_n = log_n;
-  a.lh = dt->lh;
-
-  const u32 pre = (coset && !dir) ? PASS_PRE_COSET : 0u;
-  // n^-1 of an inverse transform: folded into the last pass's twiddle table when there are two
-  // or more passes with direct tables; otherwise multiplied explicitly (PASS_POST_SCALE)
-  const bool direct_tw = log_n <= 26 && ctx->opt_ntt_direct_tw;  // tables of N x 36 B per twiddled pass and direction
-
-  Plan plan = make_plan(log_n, (int)ctx->opt_ntt_tile_log, (int)ctx->opt_ntt_max_radix, (int)ctx->opt_ntt_radix,
-                        (unsigned)ctx->num_cus, batch);
-  const bool scale_folded = dir && plan.npass > 1 && direct_tw;
-  const u32 post = ((dir && !scale_folded) ? PASS_POST_SCALE : 0u) | ((dir && coset) ? PASS_POST_COSET : 0u);
-  if (plan.npass == 0) {
-    a.in = (const u32x4*)d_in;
-    a.out = (u32x4*)d_out;
-    a.batch_stride_in = in_stride;
-    a.batch_stride_out = out_stride;
-    a.in_len = (u32)in_len;
-    a.flags = pre | post;
-    hipLaunchKernelGGL(ntt_tiny_kernel, dim3(1, batch), dim3(64), 0, st, a, kc);
-    PM_HIP(ctx, hipGetLastError());
-    return PM_OK;
-  }
-
-  // buffers: pass i reads src, writes (last ? out : tmp[i & 1]); a pass never runs in place
-  const bool inplace = (d_in == d_out);
-  const int ntmp = plan.npass - 1 + ((plan.npass == 1 && inplace) ? 1 : 0);
-  for (int i = 0; i < std::min(ntmp, 2); ++i) {
+  // pass i reads what pass i - 1 wrote and writes (last ? out : tmp[i & 1]); a pass never runs in place.  Intermediate
+  // vectors are 9-limb "wide" planes in ntt_tmp[]; only a single-pass in-place transform needs a canonical bounce buffer
+  // (ntt_tmp[0]) plus a copy
+  const bool bounce = L.npass == 1 && d_in == d_out;
+  for (int i = 0; i < std::min(L.npass - 1 + (bounce ? 1 : 0), 2); ++i) {
     rc = ensure_buffer(ctx, ctx->ntt_tmp[i], (size_t)batch * n * 36);
     if (rc) return rc;
   }
-  const void* src = d_in;
-  unsigned log_ns = 0;
+  void* dst[4];
+  for (int i = 0; i < L.npass; ++i) dst[i] = (i == L.npass - 1 && !bounce) ? d_out : ctx->ntt_tmp[i & 1].ptr;
+  for (int i = 0; i < L.npass; ++i)
+    if (L.pass[i].lds > 64 * 1024)   // once per kernel and process, not per launch
+      if (int lrc = raise_lds_limit(ctx, (const void*)L.pass[i].fn, L.pass[i].lds)) return lrc;
+
+  NttPassArgs a;
+  memset(&a, 0, sizeof a);
+  a.tw_hi = (const u32x4*)T.dt->tw_hi;
+  a.tw_lo = (const u32x4*)T.dt->tw_lo;
+  a.cs_hi = (const u32x4*)T.dt->cs_hi;
+  a.cs_lo = (const u32x4*)T.dt->cs_lo;
+  a.log_n = log_n;
+  a.lh = T.dt->lh;
+  a.batch_stride_in = in_stride;
+  a.batch_stride_out = bounce ? n : out_stride;
+  a.in_len = (u32)in_len;
+  if (L.tiny) {
+    a.in = d_in;
+    a.out = d_out;
+    a.flags = L.tiny_flags;
+    hipLaunchKernelGGL(ntt_tiny_kernel, dim3(1, batch), dim3(64), 0, st, a, T.kc);
+    PM_HIP(ctx, hipGetLastError());
+    return PM_OK;
+  }
   a.wide_total = (unsigned long long)batch * n;
-  a.wide_glog = plan_wide_glog(plan);
-  bool tw_applied = false;   // the previous pass ran with PASS_TW_OUT
-  for (int i = 0; i < plan.npass; ++i) {
-    const bool last = (i == plan.npass - 1);
-    const int S = plan.S[i], LT = plan.LT[i];
-    // intermediate vectors are 9-limb "wide" planes in ntt_tmp[]; only a single-pass
-    // in-place transform needs a canonical bounce buffer (ntt_tmp[0]) plus a copy
-    void* dst = (last && !(plan.npass == 1 && inplace)) ? d_out : ctx->ntt_tmp[i & 1].ptr;
-    const int role = plan.npass == 1 ? ROLE_SINGLE : (i == 0 ? ROLE_FIRST : (last ? ROLE_LAST : ROLE_MIDDLE));
-    const bool r4 = ctx->opt_ntt_radix == 4 && find_pass4(S, LT, role) != nullptr;
-    pass_fn fn = r4 ? find_pass4(S, LT, role) : find_pass(S, LT, role);
-    if (!fn) return set_err(ctx, PM_ERR_BAD_ARG, "no kernel for this pass shape");
-    void* stw = nullptr;
-    rc = r4 ? get_step4_table(ctx, dir, (unsigned)S, &stw, st) : get_step_table(ctx, dir, (unsigned)S, &stw, st);
-    if (rc) return rc;
-    a.in = src;
-    a.out = dst;
-    a.step_tw = (const u32x4*)stw;
-    a.step_tw_lazy = nullptr;
-    if (const int lazy = r4 ? pass4_lazy_form(S, LT, role) : 0) {   // this shape's step products read the lazy table
-      void* ltw = nullptr;
-      rc = get_step4_lazy_table(ctx, dir, (unsigned)S, (unsigned)lazy, &ltw, st);
-      if (rc) return rc;
-      a.step_tw_lazy = (const u32x4*)ltw;
-    }
-    a.batch_stride_in = in_stride;
-    a.batch_stride_out = (plan.npass == 1 && inplace) ? n : out_stride;
-    a.in_len = (u32)in_len;
-    a.log_ns = log_ns;
-    u32 post_i = last ? post : 0u;
-    a.pass_tw = nullptr;
-    a.pass_tw_out = nullptr;
-    u32 tw_flag = 0;
-    if (tw_applied) {   // the pass before this one multiplied by this pass's table
-      tw_flag = PASS_TW_APPLIED;
-    } else if (i > 0 && direct_tw) {
-      void* ptw = nullptr;
-      rc = get_pass_tw(ctx, dt, i, last, dir, log_n, log_ns, S, a.wide_glog, kc, st, &ptw);
-      if (rc) return rc;
-      a.pass_tw = ptw;
-      tw_flag = PASS_DIRECT_TW;
-    }
-    // this pass applies the next one's table to its outputs where both are radix-4 kernels and its shape takes the product
-    tw_applied = false;
-    if (!last && direct_tw && ctx->opt_ntt_tw_producer && r4 && pass4_tw_producer(S, LT, role)) {
-      const bool next_last = (i + 1 == plan.npass - 1);
-      const int nS = plan.S[i + 1];
-      if (find_pass4(nS, plan.LT[i + 1], next_last ? ROLE_LAST : ROLE_MIDDLE) != nullptr) {
-        void* ptw = nullptr;
-        rc = get_pass_tw(ctx, dt, i + 1, next_last, dir, log_n, log_ns + (unsigned)S, nS, a.wide_glog, kc, st, &ptw);
-        if (rc) return rc;
-        a.pass_tw_out = ptw;
-        tw_flag |= PASS_TW_OUT;
-        tw_applied = true;
-      }
-    }
-    a.flags = (i == 0 ? pre : 0u) | post_i | tw_flag | (ctx->opt_ntt_xcd ? PASS_XCD_REMAP : 0u);
-    if (r4 && ctx->opt_ntt_step_prio && pass4_step_prio(S, LT, role)) a.flags |= PASS_STEP_PRIO;   // wave priorities by step
-    // a launch that is a fixed-shape variant's in every respect takes it: same arguments, grid and LDS, fewer instructions
-    ctx->ntt_last_variant[i] = 1;
-    if (r4 && ctx->opt_ntt_fixed_shape) {
-      int flazy = 0;
-      if (pass_fn ffn = find_pass4_fixed(S, LT, role, log_n, log_ns, a.wide_glog, a.flags, in_len, coset, ctx->opt_ntt_fixed_shape, &flazy)) {
-        if (flazy != pass4_lazy_form(S, LT, role)) {   // the variant reads another form of the lazy table than the generic kernel
-          void* ltw = nullptr;
-          rc = get_step4_lazy_table(ctx, dir, (unsigned)S, (unsigned)flazy, &ltw, st);
-          if (rc) return rc;
-          a.step_tw_lazy = (const u32x4*)ltw;
-        }
-        fn = ffn;
-        ctx->ntt_last_variant[i] = 2;
-      }
-    }
-    const unsigned threads = r4 ? pass4_threads(S, LT) : std::max(64u, (1u << (S + LT)) / 8);
-    const size_t lds = r4 ? pass4_lds(S, LT) : pass_lds_bytes(S, LT);
-    if (lds > 64 * 1024)   // once per kernel and process, not per launch
-      if (int lrc = raise_lds_limit(ctx, (const void*)fn, lds)) return lrc;
-    const unsigned blocks = (unsigned)(n >> (S + LT));
+  a.wide_glog = L.wide_glog;
+
+  // launch
+  for (int i = 0; i < L.npass; ++i) {
+    const PassLaunch& p = L.pass[i];
+    a.in = i ? dst[i - 1] : d_in;
+    a.out = dst[i];
+    a.step_tw = (const u32x4*)T.step[i];
+    a.step_tw_lazy = (const u32x4*)T.lazy[i];
+    a.pass_tw = T.tw_in[i];
+    a.pass_tw_out = T.tw_out[i];
+    a.log_ns = p.log_ns;
+    a.flags = p.flags;
+    ctx->ntt_last_variant[i] = (unsigned)p.variant;
 #ifdef PM_DEV_STAMPS
-    if (r4)
-      if (int lrc = ntt_stamps_arm(ctx, st, i, (size_t)blocks * batch * ((threads + 63) / 64))) return lrc;
+    if (p.r4)
+      if (int lrc = ntt_stamps_arm(ctx, st, i, (size_t)p.blocks * batch * ((p.threads + 63) / 64))) return lrc;
 #endif
     {
       static const char* kRoleName[4] = {"ntt_pass_single", "ntt_pass_first", "ntt_pass_middle", "ntt_pass_last"};
-      ProfScope prof(ctx, st, kRoleName[role]);
-      hipLaunchKernelGGL(fn, dim3(blocks, batch), dim3(threads), lds, st, a, kc);
+      ProfScope prof(ctx, st, kRoleName[p.role]);
+      hipLaunchKernelGGL(p.fn, dim3(p.blocks, batch), dim3(p.threads), p.lds, st, a, T.kc);
     }
     PM_HIP(ctx, hipGetLastError());
-    src = dst;
-    log_ns += (unsigned)S;
   }
-  if (plan.npass == 1 && inplace) {
+  if (bounce) {
     PM_HIP(ctx, hipMemcpy2DAsync(d_out, out_stride * 32, ctx->ntt_tmp[0].ptr, n * 32, n * 32, batch,
                                  hipMemcpyDeviceToDevice, st));
   }
@@ -493,174 +516,6 @@ extern "C" int pm_ntt_plan(uint32_t log_n, uint32_t radix_log2[4], uint32_t* n_p
   return PM_OK;
 }
 
-extern "C" int pm_domain_info(uint32_t log_n, uint64_t group_gen[4], uint64_t group_gen_inv[4],
-                              uint64_t size_inv[4]) {
-  if (log_n >= host::FR_TWO_ADICITY) return PM_ERR_DOMAIN_TOO_LARGE;
-  const host::Field<4>& F = host::FR();
-  HFr g = domain_gen(log_n);
-  HFr gi = host::inv(g, F);
-  HFr si = host::inv(host::from_u64((u64)1 << log_n, F), F);
-  memcpy(group_gen, g.l, 32);
-  memcpy(group_gen_inv, gi.l, 32);
-  memcpy(size_inv, si.l, 32);
-  return PM_OK;
-}
-
-// ---- the small helpers of dusk_plonk::fft::EvaluationDomain (dusk-plonk 0.8.2, ref:Cargo.toml:19):
-// what a Rust patch at the quotient_poly::compute / linearisation level calls besides the transforms.
-namespace {
-HFr hfr_pow_u64(const HFr& a, host::u64 e) { return host::pow(a, &e, 1, host::FR()); }
-// log of tau to the base w (a generator of the 2^log_n domain), or -1 when tau is not in the domain: Pohlig-Hellman
-// over the 2-group, one bit per step
-long long domain_log(const HFr& tau, unsigned log_n) {
-  const host::Field<4>& F = host::FR();
-  const HFr one = host::one(F), w = domain_gen(log_n), wi = host::inv(w, F);
-  u64 idx = 0;
-  HFr rest = tau;   // tau w^-idx: its order divides 2^(log_n - j) after step j
-  HFr wpow = wi;    // w^-(2^j)
-  for (unsigned j = 0; j < log_n; ++j) {
-    HFr t = rest;
-    for (unsigned s = 0; s + j + 1 < log_n; ++s) t = host::mul(t, t, F);   // rest^(2^(log_n - 1 - j)): 1 or -1
-    if (!host::eq(t, one)) {
-      idx |= (u64)1 << j;
-      rest = host::mul(rest, wpow, F);
-    }
-    wpow = host::mul(wpow, wpow, F);
-  }
-  return host::eq(rest, one) ? (long long)idx : -1;
-}
-}  // namespace
-
-// EvaluationDomain::evaluate_vanishing_polynomial(tau) = tau^size - 1
-extern "C" int pm_domain_evaluate_vanishing_polynomial(uint32_t log_n, const uint64_t tau[4], uint64_t out[4]) {
-  if (!tau || !out) return PM_ERR_BAD_ARG;
-  if (log_n >= host::FR_TWO_ADICITY) return PM_ERR_DOMAIN_TOO_LARGE;
-  const host::Field<4>& F = host::FR();
-  HFr t;
-  memcpy(t.l, tau, 32);
-  const HFr r = host::sub(hfr_pow_u64(t, (u64)1 << log_n), host::one(F), F);
-  memcpy(out, r.l, 32);
-  return PM_OK;
-}
-
-// fft::domain::compute_vanishing_poly_over_coset(domain, poly_degree): Evaluations over the 2^log_n domain of
-// X^poly_degree - 1 on the coset g H:  out[i] = g^d (w^d)^i - 1,  g = GENERATOR = 7.  Upstream asserts size > poly_degree.
-extern "C" int pm_domain_vanishing_poly_over_coset(uint32_t log_n, uint64_t poly_degree, uint64_t* out) {
-  if (!out) return PM_ERR_BAD_ARG;
-  if (log_n >= host::FR_TWO_ADICITY) return PM_ERR_DOMAIN_TOO_LARGE;
-  if (poly_degree >= ((u64)1 << log_n)) return PM_ERR_BAD_ARG;
-  const host::Field<4>& F = host::FR();
-  const HFr one = host::one(F), step = hfr_pow_u64(domain_gen(log_n), poly_degree);
-  HFr cur = hfr_pow_u64(host::from_u64(host::FR_GENERATOR, F), poly_degree);
-  for (size_t i = 0; i < ((size_t)1 << log_n); ++i) {
-    const HFr v = host::sub(cur, one, F);
-    memcpy(out + 4 * i, v.l, 32);
-    cur = host::mul(cur, step, F);
-  }
-  return PM_OK;
-}
-extern "C" int pm_domain_vanishing_poly_over_coset_dev(pm_ctx* ctx, uint32_t log_n, uint64_t poly_degree, void* d_out,
-                                                       void* hip_stream) {
-  if (!ctx || !d_out) return PM_ERR_BAD_ARG;
-  if (log_n >= host::FR_TWO_ADICITY) return PM_ERR_DOMAIN_TOO_LARGE;
-  if (poly_degree >= ((u64)1 << log_n)) return PM_ERR_BAD_ARG;
-  const host::Field<4>& F = host::FR();
-  const HFr one = host::one(F), step = hfr_pow_u64(domain_gen(log_n), poly_degree);
-  const HFr scale = hfr_pow_u64(host::from_u64(host::FR_GENERATOR, F), poly_degree);
-  const size_t n = (size_t)1 << log_n;
-  int rc = pm_fr_powers_dev(ctx, step.l, scale.l, n, d_out, hip_stream);
-  // the scalar operand of the broadcast subtraction lives in the first element's place for one launch: a one-element
-  // device vector of its own, freed after the stream has used it
-  void* d_one = nullptr;
-  if (!rc) rc = pm_dev_alloc(ctx, 32, &d_one);
-  if (!rc) rc = pm_dev_upload(ctx, d_one, one.l, 32);
-  if (!rc) rc = pm_fr_vec_op_dev(ctx, 1 /* sub */, d_out, d_one, 1, d_out, n, hip_stream);
-  if (d_one) {
-    if (hipStreamSynchronize(hip_stream ? (hipStream_t)hip_stream : ctx->stream) != hipSuccess && !rc) rc = PM_ERR_HIP;
-    (void)pm_dev_free(ctx, d_one);
-  }
-  return rc;
-}
-
-// EvaluationDomain::evaluate_all_lagrange_coefficients(tau): out[i] = L_i(tau) = (tau^n - 1) / n * w^i / (tau - w^i);
-// for tau = w^j in the domain the indicator of j.
-extern "C" int pm_domain_evaluate_all_lagrange_coefficients(uint32_t log_n, const uint64_t tau[4], uint64_t* out) {
-  if (!tau || !out) return PM_ERR_BAD_ARG;
-  if (log_n >= host::FR_TWO_ADICITY) return PM_ERR_DOMAIN_TOO_LARGE;
-  const host::Field<4>& F = host::FR();
-  const size_t n = (size_t)1 << log_n;
-  HFr t;
-  memcpy(t.l, tau, 32);
-  const HFr one = host::one(F), w = domain_gen(log_n), tn = hfr_pow_u64(t, (u64)n);
-  if (host::eq(tn, one)) {
-    memset(out, 0, n * 32);
-    const long long j = domain_log(t, log_n);
-    if (j >= 0) memcpy(out + 4 * (size_t)j, one.l, 32);
-    return PM_OK;
-  }
-  // util::batch_inversion (Montgomery's trick) on u[i] = tau - w^i; the running products go to `out`
-  std::vector<HFr> u(n);
-  HFr r = one, acc = one;
-  for (size_t i = 0; i < n; ++i) {
-    u[i] = host::sub(t, r, F);
-    memcpy(out + 4 * i, acc.l, 32);          // product of u[0 .. i)
-    acc = host::mul(acc, u[i], F);
-    r = host::mul(r, w, F);
-  }
-  HFr inv_all = host::inv(acc, F);
-  const HFr l0 = host::mul(host::sub(tn, one, F), host::inv(host::from_u64((u64)n, F), F), F);   // (tau^n - 1) / n
-  const HFr wi = host::inv(w, F);
-  HFr l = host::mul(l0, hfr_pow_u64(w, (u64)(n - 1)), F);   // l0 w^(n-1), walked downwards
-  for (size_t i = n; i-- > 0;) {
-    HFr prefix;
-    memcpy(prefix.l, out + 4 * i, 32);
-    const HFr ui_inv = host::mul(inv_all, prefix, F);
-    inv_all = host::mul(inv_all, u[i], F);
-    const HFr v = host::mul(l, ui_inv, F);
-    memcpy(out + 4 * i, v.l, 32);
-    l = host::mul(l, wi, F);
-  }
-  return PM_OK;
-}
-extern "C" int pm_domain_evaluate_all_lagrange_coefficients_dev(pm_ctx* ctx, uint32_t log_n, const uint64_t tau[4], void* d_out,
-                                                                void* hip_stream) {
-  if (!ctx || !tau || !d_out) return PM_ERR_BAD_ARG;
-  if (log_n >= host::FR_TWO_ADICITY) return PM_ERR_DOMAIN_TOO_LARGE;
-  const host::Field<4>& F = host::FR();
-  const size_t n = (size_t)1 << log_n;
-  hipStream_t st = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
-  HFr t;
-  memcpy(t.l, tau, 32);
-  const HFr one = host::one(F), w = domain_gen(log_n), tn = hfr_pow_u64(t, (u64)n);
-  if (host::eq(tn, one)) {
-    PM_HIP(ctx, hipSetDevice(ctx->device));
-    PM_HIP(ctx, hipMemsetAsync(d_out, 0, n * 32, st));
-    const long long j = domain_log(t, log_n);
-    if (j >= 0) {
-      PM_HIP(ctx, hipMemcpyAsync((char*)d_out + 32 * (size_t)j, one.l, 32, hipMemcpyHostToDevice, st));
-      PM_HIP(ctx, hipStreamSynchronize(st));   // `one` is a stack value
-    }
-    return PM_OK;
-  }
-  // out = w^i;  out -= tau  (= -(tau - w^i));  out = 1 / out;  out *= w^i scaled by -(tau^n - 1) / n
-  void *d_sc = nullptr, *d_roots = nullptr;
-  int rc = pm_dev_alloc(ctx, 32, &d_sc);
-  if (!rc) rc = pm_dev_alloc(ctx, n * 32, &d_roots);
-  const HFr neg_l0 = host::mul(host::sub(one, tn, F), host::inv(host::from_u64((u64)n, F), F), F);
-  if (!rc) rc = pm_fr_powers_dev(ctx, w.l, neg_l0.l, n, d_roots, hip_stream);   // -(tau^n - 1) / n * w^i
-  if (!rc) rc = pm_fr_powers_dev(ctx, w.l, one.l, n, d_out, hip_stream);
-  if (!rc) rc = pm_dev_upload(ctx, d_sc, t.l, 32);
-  if (!rc) rc = pm_fr_vec_op_dev(ctx, 1 /* sub */, d_out, d_sc, 1, d_out, n, hip_stream);
-  if (!rc) rc = pm_fr_batch_inverse_dev(ctx, d_out, n, hip_stream);
-  if (!rc) rc = pm_fr_vec_op_dev(ctx, 2 /* mul */, d_out, d_roots, n, d_out, n, hip_stream);
-  if (d_sc || d_roots) {
-    if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = PM_ERR_HIP;
-    if (d_sc) (void)pm_dev_free(ctx, d_sc);
-    if (d_roots) (void)pm_dev_free(ctx, d_roots);
-  }
-  return rc;
-}
-
 // test hook (pure host): the pass plan ntt_run() follows for this size and these tunables (0 = the defaults of a fresh
 // context).  out[20]: passes, then per pass (up to 4) {log2 radix S, log2 columns per tile LT, threads per workgroup,
 // LDS bytes}, then a bit mask of the passes that have a kernel, then the blocked layout's log2 group size, 0.
@@ -668,22 +523,52 @@ extern "C" int pm_test_ntt_plan(uint32_t log_n, uint32_t batch, long tile_log, l
                                 uint32_t out[20]) {
   if (!out || !batch) return PM_ERR_BAD_ARG;
   if (log_n >= host::FR_TWO_ADICITY) return PM_ERR_DOMAIN_TOO_LARGE;
-  const long rdx = radix ? radix : 4;
-  Plan plan = make_plan(log_n, (int)tile_log, (int)(max_radix ? max_radix : 10), (int)rdx, num_cus ? num_cus : 256u, batch);
+  NttOpts o = kDefaultOpts;
+  o.tile_log = tile_log;
+  if (max_radix) o.max_radix = max_radix;
+  if (radix) o.radix = radix;
+  const NttLaunches L = ntt_resolve(o, num_cus ? num_cus : 256u, log_n, batch, 0, 1ull << log_n);
   memset(out, 0, 20 * sizeof(uint32_t));
-  out[0] = (uint32_t)plan.npass;
-  for (int i = 0; i < plan.npass; ++i) {
-    const bool last = (i == plan.npass - 1);
-    const int role = plan.npass == 1 ? ROLE_SINGLE : (i == 0 ? ROLE_FIRST : (last ? ROLE_LAST : ROLE_MIDDLE));
-    const int S = plan.S[i], LT = plan.LT[i];
-    const bool r4 = rdx == 4 && find_pass4(S, LT, role) != nullptr;
-    out[1 + 4 * i] = (uint32_t)S;
-    out[2 + 4 * i] = (uint32_t)LT;
-    out[3 + 4 * i] = r4 ? pass4_threads(S, LT) : std::max(64u, (1u << (S + LT)) / 8);
-    out[4 + 4 * i] = (uint32_t)(r4 ? pass4_lds(S, LT) : pass_lds_bytes(S, LT));
-    if ((r4 ? find_pass4(S, LT, role) : find_pass(S, LT, role)) != nullptr) out[17] |= 1u << i;
+  out[0] = (uint32_t)L.npass;
+  for (int i = 0; i < L.npass; ++i) {
+    const PassLaunch& p = L.pass[i];
+    out[1 + 4 * i] = (uint32_t)p.S;
+    out[2 + 4 * i] = (uint32_t)p.LT;
+    out[3 + 4 * i] = p.threads;
+    out[4 + 4 * i] = (uint32_t)p.lds;
+    if (p.fn != nullptr) out[17] |= 1u << i;
   }
-  out[18] = plan.npass ? plan_wide_glog(plan) : 0u;
+  out[18] = L.wide_glog;
+  return PM_OK;
+}
+
+// test hook (pure host, no context): everything ntt_run() resolves for a transform before it launches.  opts[8]: the options
+// ntt_tile_log, ntt_max_radix, ntt_radix (0 = the default of a fresh context, as in pm_test_ntt_plan), then the switches
+// ntt_xcd, ntt_direct_tw, ntt_tw_producer, ntt_step_prio and ntt_fixed_shape (a negative value = the default, since 0 is a
+// value of theirs).  out[60]: {passes, log2 group size of the blocked layout, 1 if the tiny kernel runs, its PASS_* flags,
+// 1 if n^-1 is folded into the last pass's table, 0, 0, 0}, then 13 words per pass (up to 4): S, LT, role, family (4 or
+// 8), variant (1 generic, 2 fixed-shape), threads, LDS bytes, workgroups, PASS_* flags, log_ns, lazy-table form G (0
+// none), the pass whose inter-pass table it reads through pass_tw and the pass whose table it applies through pass_tw_out
+// (-1: none).  PM_ERR_BAD_ARG also when a pass has no kernel.
+extern "C" int pm_test_ntt_launches(uint32_t log_n, uint32_t batch, uint32_t flags, uint64_t in_len, const long opts[8],
+                                    uint32_t num_cus, int32_t out[60]) {
+  if (!out || !opts || !batch || (flags & ~(PM_NTT_INVERSE | PM_NTT_COSET))) return PM_ERR_BAD_ARG;
+  if (log_n >= host::FR_TWO_ADICITY) return PM_ERR_DOMAIN_TOO_LARGE;
+  if (in_len > (1ull << log_n)) return PM_ERR_LENGTH;
+  NttOpts o = kDefaultOpts;
+  long* dst[8] = {&o.tile_log, &o.max_radix, &o.radix, &o.xcd, &o.direct_tw, &o.tw_producer, &o.step_prio, &o.fixed_shape};
+  for (int k = 0; k < 8; ++k)
+    if (k < 3 ? opts[k] != 0 : opts[k] >= 0) *dst[k] = opts[k];
+  const NttLaunches L = ntt_resolve(o, num_cus ? num_cus : 256u, log_n, batch, flags, in_len);
+  memset(out, 0, 60 * sizeof(int32_t));
+  out[0] = L.npass, out[1] = (int32_t)L.wide_glog, out[2] = L.tiny, out[3] = (int32_t)L.tiny_flags, out[4] = L.scale_folded;
+  for (int i = 0; i < L.npass; ++i) {
+    const PassLaunch& p = L.pass[i];
+    if (!p.fn) return PM_ERR_BAD_ARG;
+    const int32_t rec[13] = {p.S, p.LT, p.role, p.r4 ? 4 : 8, p.variant, (int32_t)p.threads, (int32_t)p.lds, (int32_t)p.blocks,
+                             (int32_t)p.flags, (int32_t)p.log_ns, p.lazy, p.tw_in, p.tw_out};
+    memcpy(out + 8 + 13 * i, rec, sizeof rec);
+  }
   return PM_OK;
 }
 
@@ -695,9 +580,8 @@ extern "C" int pm_test_ntt_fixed_match(uint32_t S, uint32_t LT, uint32_t role, u
                                        uint32_t wide_glog, uint32_t pass_flags, uint64_t in_len, uint32_t coset,
                                        uint32_t fixed_shape) {
   if (S > 31 || LT > 31 || role > 3 || fixed_shape > 2) return 0;
-  return fixed_shape && find_pass4((int)S, (int)LT, (int)role) != nullptr &&
-                 find_pass4_fixed((int)S, (int)LT, (int)role, log_n, log_ns, wide_glog, pass_flags, in_len, coset != 0,
-                                  (long)fixed_shape, nullptr) != nullptr
+  return fixed_variant((int)S, (int)LT, (int)role, log_n, log_ns, wide_glog, pass_flags, in_len, coset != 0, (long)fixed_shape,
+                       nullptr) != nullptr
              ? 1
              : 0;
 }
@@ -711,44 +595,52 @@ extern "C" int pm_test_ntt_last_variants(pm_ctx* ctx, uint32_t out[4]) {
   return PM_OK;
 }
 
-// test hook: the radix-4 step table of radix 2^S (head, then entries) as the kernels read it, built on first use like
-// any transform's.  *words = its size in 32-bit words; up to max_words of them are copied to out.
-extern "C" int pm_test_ntt_step4_table(pm_ctx* ctx, uint32_t inverse, uint32_t S, uint32_t* out, size_t max_words,
-                                       size_t* words) {
-  if (!ctx || inverse > 1 || S < 2 || S > 10 || (!out && max_words)) return PM_ERR_BAD_ARG;
+// the two table hooks below: the step table of `kind` (get_step_table), `bytes` long, built and cached like a transform's;
+// *words = its size in 32-bit words, up to max_words of them are copied to out
+static int dump_step_table(pm_ctx* ctx, uint32_t inverse, uint32_t S, int kind, size_t bytes, uint32_t* out, size_t max_words,
+                           size_t* words) {
   std::lock_guard<std::mutex> lk(ctx->mu);
   PM_HIP(ctx, hipSetDevice(ctx->device));
   OrderScope order_scope(ctx, ctx->ord_ntt, ctx->stream);
   if (order_scope.rc) return order_scope.rc;
   void* tab = nullptr;
-  int rc = get_step4_table(ctx, (int)inverse, S, &tab, ctx->stream);
+  int rc = get_step_table(ctx, (int)inverse, S, kind, &tab, ctx->stream);
   if (rc) return rc;
-  const size_t total = step4_table_bytes(S) / 4;
+  const size_t total = bytes / 4;
   if (words) *words = total;
   const size_t n = std::min(total, max_words);
   if (n) PM_HIP(ctx, hipMemcpyAsync(out, tab, n * 4, hipMemcpyDeviceToHost, ctx->stream));
   PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return PM_OK;
 }
-
+// test hook: the radix-4 step table of radix 2^S (head, then entries) as the kernels read it
+extern "C" int pm_test_ntt_step4_table(pm_ctx* ctx, uint32_t inverse, uint32_t S, uint32_t* out, size_t max_words,
+                                       size_t* words) {
+  if (!ctx || inverse > 1 || S < 2 || S > 10 || (!out && max_words)) return PM_ERR_BAD_ARG;
+  return dump_step_table(ctx, inverse, S, STEP_R4, step4_table_bytes(S), out, max_words, words);
+}
 // test hook: the lazy split table of radix 2^S in form G (1, 2, 3 or 5 data limbs a row) as a kernel of that form reads it:
-// the w4 head, then the entries of the radix-4 steps from the third on.  Built and cached like a transform's; the
-// arguments behind G are those of pm_test_ntt_step4_table.
+// the w4 head, then the entries of the radix-4 steps from the third on
 extern "C" int pm_test_ntt_step4_lazy_table(pm_ctx* ctx, uint32_t inverse, uint32_t S, uint32_t G, uint32_t* out,
                                             size_t max_words, size_t* words) {
   if (!ctx || inverse > 1 || S < 2 || S > 10 || !(G == 1 || G == 2 || G == 3 || G == 5) || (!out && max_words)) return PM_ERR_BAD_ARG;
+  return dump_step_table(ctx, inverse, S, (int)G, step4_lazy_table_bytes(S, G), out, max_words, words);
+}
+
+// test hook: the device tables the context caches for the NTT -- domain and coset tables (two each), step tables, lazy step
+// tables and inter-pass tables of both directions
+extern "C" int pm_test_ntt_table_count(pm_ctx* ctx, size_t* count) {
+  if (!ctx || !count) return PM_ERR_BAD_ARG;
   std::lock_guard<std::mutex> lk(ctx->mu);
-  PM_HIP(ctx, hipSetDevice(ctx->device));
-  OrderScope order_scope(ctx, ctx->ord_ntt, ctx->stream);
-  if (order_scope.rc) return order_scope.rc;
-  void* tab = nullptr;
-  int rc = get_step4_lazy_table(ctx, (int)inverse, S, G, &tab, ctx->stream);
-  if (rc) return rc;
-  const size_t total = step4_lazy_table_bytes(S, G) / 4;
-  if (words) *words = total;
-  const size_t n = std::min(total, max_words);
-  if (n) PM_HIP(ctx, hipMemcpyAsync(out, tab, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-  PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  size_t c = 0;
+  for (int d = 0; d < 2; ++d) {
+    c += ctx->step_tw[d].size() + ctx->step4_tw[d].size() + ctx->step4_lazy_tw[d].size();
+    for (const auto& kv : ctx->domain[d]) {
+      const NttDomainTables& t = kv.second;
+      for (const void* p : {t.tw_hi, t.tw_lo, t.cs_hi, t.cs_lo, t.pass_tw[0], t.pass_tw[1], t.pass_tw[2], t.pass_tw[3]}) c += p != nullptr;
+    }
+  }
+  *count = c;
   return PM_OK;
 }
 
@@ -761,38 +653,12 @@ extern "C" int pm_domain_prepare(pm_ctx* ctx, uint32_t log_n) {
   if (log_n == 0) return PM_OK;
   OrderScope order_scope(ctx, ctx->ord_ntt, ctx->stream);
   if (order_scope.rc) return order_scope.rc;
-  // exactly the tables ntt_run() would build on the first transform of this size: domain and coset
-  // tables, the step tables of the kernels the plan picks (radix-4 or radix-8 family), and the
-  // inter-pass twiddle tables of both directions
-  Plan plan = make_plan(log_n, (int)ctx->opt_ntt_tile_log, (int)ctx->opt_ntt_max_radix, (int)ctx->opt_ntt_radix,
-                        (unsigned)ctx->num_cus, 1);
-  const unsigned wide_glog = plan_wide_glog(plan);
-  for (int dir = 0; dir < 2; ++dir) {
-    NttDomainTables* dt;
-    int rc = get_domain_tables(ctx, dir, log_n, true, &dt, ctx->stream);
-    if (rc) return rc;
-    NttConsts kc;
-    fill_consts(kc, dir, log_n);
-    unsigned log_ns = 0;
-    for (int i = 0; i < plan.npass; ++i) {
-      const bool last = (i == plan.npass - 1);
-      const int role = plan.npass == 1 ? ROLE_SINGLE : (i == 0 ? ROLE_FIRST : (last ? ROLE_LAST : ROLE_MIDDLE));
-      const bool r4 = ctx->opt_ntt_radix == 4 && find_pass4(plan.S[i], plan.LT[i], role) != nullptr;
-      void* stw;
-      rc = r4 ? get_step4_table(ctx, dir, (unsigned)plan.S[i], &stw, ctx->stream)
-              : get_step_table(ctx, dir, (unsigned)plan.S[i], &stw, ctx->stream);
-      if (rc) return rc;
-      if (const int lazy = r4 ? pass4_lazy_form(plan.S[i], plan.LT[i], role) : 0) {
-        rc = get_step4_lazy_table(ctx, dir, (unsigned)plan.S[i], (unsigned)lazy, &stw, ctx->stream);
-        if (rc) return rc;
-      }
-      if (i > 0 && log_n <= 26 && ctx->opt_ntt_direct_tw) {
-        void* ptw;
-        rc = get_pass_tw(ctx, dt, i, last, dir, log_n, log_ns, plan.S[i], wide_glog, kc, ctx->stream, &ptw);
-        if (rc) return rc;
-      }
-      log_ns += (unsigned)plan.S[i];
-    }
+  // the tables of the transforms of a whole input, one vector at a time, under the options in force: fft, ifft, coset_fft and
+  // coset_ifft.  A batch whose plan takes narrower tiles rebuilds the inter-pass tables it keys differently at its first call.
+  for (unsigned flags : {0u, (unsigned)PM_NTT_COSET, (unsigned)PM_NTT_INVERSE, (unsigned)(PM_NTT_INVERSE | PM_NTT_COSET)}) {
+    const NttLaunches L = ntt_resolve(ntt_opts(ctx), (unsigned)ctx->num_cus, log_n, 1, flags, 1ull << log_n);
+    NttTables T;
+    if (int rc = ntt_acquire(ctx, L, log_n, flags, ctx->stream, &T)) return rc;
   }
   PM_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return PM_OK;
@@ -814,13 +680,10 @@ extern "C" int pm_fr_ntt_batch(pm_ctx* ctx, const uint64_t* in, size_t in_len, s
   if (!ctx) return PM_ERR_BAD_ARG;
   std::lock_guard<std::mutex> lk(ctx->mu);
   if (!out || (!in && in_len)) return set_err(ctx, PM_ERR_BAD_ARG, "null pointer");
-  if (log_n >= host::FR_TWO_ADICITY)
-    return set_err(ctx, PM_ERR_DOMAIN_TOO_LARGE, "log_n >= 32 (Fr two-adicity)");
+  bool empty = false;
+  if (int crc = ntt_check_args(ctx, in_len, in_stride, out_stride, log_n, batch, flags, &empty)) return crc;
+  if (empty) return PM_OK;
   const size_t n = (size_t)1 << log_n;
-  if (in_len > n) return set_err(ctx, PM_ERR_LENGTH, "in_len > 2^log_n");
-  if (batch == 0) return PM_OK;
-  if (batch > 1 && (in_stride < in_len || out_stride < n))
-    return set_err(ctx, PM_ERR_BAD_ARG, "batch strides shorter than the vectors");
   PM_HIP(ctx, hipSetDevice(ctx->device));
   hipStream_t st = ctx->stream;
   const size_t in_elems = std::max<size_t>(in_len, 1);
@@ -911,250 +774,4 @@ extern "C" int pm_fr_ntt(pm_ctx* ctx, const uint64_t* in, size_t in_len, uint64_
                          uint32_t log_n, uint32_t flags) {
   return pm_fr_ntt_batch(ctx, in, in_len, in_len, out, (size_t)1 << (log_n < 32 ? log_n : 0), log_n,
                          1, flags);
-}
-
-// ------------------------------------------------------------------ N5: one transform split over ranks
-// SURVEY.md section 8e row 3 / 8f N5.  The vector of a 2^log_n-point transform is block-distributed in natural
-// order over `world` ranks (one process and one pm_ctx per GPU): rank r holds x[r N/W, (r+1) N/W) and receives the
-// same block of the result.  N = N1 N2 as an N1 x N2 row-major matrix (N1 = 2^(log_n / 2)):
-//     transpose (all-to-all) -> N2/W batched transforms of size N1 -> twiddles w_N^(j k1)
-//     -> transpose -> N1/W batched transforms of size N2 -> transpose (natural order)
-// A transpose is: pack this rank's [R_loc][C] slice into per-peer blocks [peer][C/W][R_loc] (a 32 x 32 tile
-// transpose through LDS; the twiddle / coset factors are folded into this pass), one all-to-all of N/W^2-element
-// blocks (the context's RCCL communicator: grouped ncclSend / ncclRecv, one direct xGMI transfer per peer -- or a
-// caller-supplied callback), and an unpack that interleaves what the peers sent into [C/W][R].  The sub-transforms
-// are the library's own batched passes.  Results are identical to the single-GPU plan bit for bit.
-namespace pm {
-
-struct FsMul {            // factor applied to element (row a, column b) of the slice while it is packed / unpacked
-  u32 mode;               // 0 none, 1 table^((row0 + a) * b)  (twiddle), 2 table^((row0 + a) * C + b)  (coset by index)
-  const u32x4* hi;
-  const u32x4* lo;
-  u32 lh;
-  u32 row0;
-};
-PM_DEV void fs_apply(u32x4& v0, u32x4& v1, const FsMul& m, u32 a, u32 b, u32 C) {
-  if (m.mode == 0) return;
-  const u32 e = m.mode == 1 ? (m.row0 + a) * b : (m.row0 + a) * C + b;
-  u32x4 raw[2] = {v0, v1};
-  Fr x = fe_load<FrP>(raw);
-  x = fe_mul<FrP>(x, two_level(m.hi, m.lo, e, m.lh));
-  fe_store<FrP>(raw, x);
-  v0 = raw[0];
-  v1 = raw[1];
-}
-// A transpose step works on `batch` vectors at once: the per-peer block of the all-to-all holds the batch's blocks one
-// after the other, so ONE exchange carries all of them (message size x batch, call count / batch).
-// send[((s * batch + v) * Cs + bl) * R_loc + a] = f(src_v[a * C + s * Cw + bl]),  s = b / Cw, bl = b % Cw;  Cs = Cw, or Cw + 1
-// with `halo`: the block for rank s then ends with one more column, (s + 1) Cw mod C -- the first column of the NEXT
-// rank's range (the last rank gets column 0) -- which the unpack turns into one extra row.
-__global__ void __launch_bounds__(256) fs_pack_kernel(const u32x4* src, size_t src_stride, u32 batch, u32 R_loc, u32 C, u32 Cw,
-                                                      u32 halo, u32x4* send, const FsMul m) {
-  __shared__ u32x4 t0[32][33], t1[32][33];
-  const u32 v = blockIdx.z;
-  src += 2 * (size_t)v * src_stride;
-  const u32 a0 = blockIdx.y * 32, b0 = blockIdx.x * 32;
-  const u32 tx = threadIdx.x & 31u, ty = threadIdx.x >> 5;   // 32 x 8
-  for (u32 r = ty; r < 32; r += 8) {
-    const u32 a = a0 + r, b = b0 + tx;
-    if (a < R_loc && b < C) {
-      u32x4 v0 = src[2 * ((size_t)a * C + b)], v1 = src[2 * ((size_t)a * C + b) + 1];
-      fs_apply(v0, v1, m, a, b, C);
-      t0[r][tx] = v0;
-      t1[r][tx] = v1;
-    }
-  }
-  __syncthreads();
-  const u32 Cs = Cw + halo, W = C / Cw;
-  for (u32 r = ty; r < 32; r += 8) {
-    const u32 b = b0 + r, a = a0 + tx;
-    if (a < R_loc && b < C) {
-      const u32 s = b / Cw, bl = b % Cw;
-      const size_t o = (((size_t)s * batch + v) * Cs + bl) * R_loc + a;
-      send[2 * o] = t0[tx][r];
-      send[2 * o + 1] = t1[tx][r];
-      if (halo && bl == 0) {   // also the extra column of the rank before s
-        const u32 sp = (s + W - 1) % W;
-        const size_t oh = (((size_t)sp * batch + v) * Cs + Cw) * R_loc + a;
-        send[2 * oh] = t0[tx][r];
-        send[2 * oh + 1] = t1[tx][r];
-      }
-    }
-  }
-}
-// dst_v[bl * R + p * R_loc + a] = g(recv[((p * batch + v) * Cs + bl) * R_loc + a]),  R = W R_loc; g's index: row bl, column
-// p R_loc + a.  With halo the extra row bl == Cw goes to halo_v[p * R_loc + a] instead.
-__global__ void __launch_bounds__(256) fs_unpack_kernel(const u32x4* recv, u32 batch, u32 R_loc, u32 W, u32 Cw, u32 halo,
-                                                        u32x4* dst, size_t dst_stride, u32x4* halo_dst, const FsMul m) {
-  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const u32 v = blockIdx.y;
-  const u32 R = R_loc * W, Cs = Cw + halo;
-  if (t >= (size_t)Cs * R) return;
-  const u32 bl = (u32)(t / R), rr = (u32)(t % R), p = rr / R_loc, a = rr % R_loc;
-  const size_t i = (((size_t)p * batch + v) * Cs + bl) * R_loc + a;
-  u32x4 v0 = recv[2 * i], v1 = recv[2 * i + 1];
-  fs_apply(v0, v1, m, bl, rr, R);
-  u32x4* o = bl < Cw ? dst + 2 * ((size_t)v * dst_stride + t) : halo_dst + 2 * ((size_t)v * R + rr);
-  o[0] = v0;
-  o[1] = v1;
-}
-
-}  // namespace pm
-
-extern "C" int pm_fr_ntt_fourstep_batch_dev(pm_ctx* ctx, void* d_inout, uint32_t batch, void* d_halo, void* d_stage,
-                                            uint32_t log_n, uint32_t world, uint32_t rank, uint32_t flags,
-                                            pm_alltoall_fn exchange, void* user) {
-  if (!ctx || !d_inout || !d_stage || batch == 0) return PM_ERR_BAD_ARG;
-  if (world == 0 || (world & (world - 1)) || rank >= world) return PM_ERR_BAD_ARG;
-  if (flags & ~(PM_NTT_INVERSE | PM_NTT_COSET | PM_NTT_TRANSPOSED)) return PM_ERR_BAD_ARG;
-  if (log_n < 2 || log_n > 26) return PM_ERR_DOMAIN_TOO_LARGE;   // 32-bit exponents of the two-level tables
-  const uint32_t l1 = log_n / 2, l2 = log_n - l1;
-  const uint32_t n1 = 1u << l1, n2 = 1u << l2;
-  if (n1 % world || n2 % world) return PM_ERR_BAD_ARG;            // the ranks must divide both factors
-  const bool inverse = flags & PM_NTT_INVERSE, coset = flags & PM_NTT_COSET;
-  const bool want_halo = d_halo != nullptr;
-  if (want_halo && (inverse || !(flags & PM_NTT_TRANSPOSED))) return PM_ERR_BAD_ARG;   // a row of the block-transposed result
-  const size_t blk = ((size_t)1 << log_n) / world;                // elements per rank and vector
-  if (batch > 65535u) return PM_ERR_BAD_ARG;
-  u32x4* x = (u32x4*)d_inout;
-  u32x4* send = (u32x4*)d_stage;
-  // stage: [send | recv], each batch x (blk, or blk + n2 with a halo row) elements; one rank needs no recv half
-  const size_t stage_half = (size_t)batch * (blk + (want_halo ? n2 : 0));
-  u32x4* recv = world == 1 ? send : send + 2 * stage_half;
-  hipStream_t st;
-  NttDomainTables* dt = nullptr;
-  // the transform holds the NTT resource group from here to its last launch, with the context unlocked in between (the
-  // exchange callback): the scope's closing event is recorded, under the lock, when the function returns
-  struct HeldOrder {
-    pm_ctx* ctx;
-    OrderScope* s;
-    ~HeldOrder() {
-      if (!s) return;
-      std::lock_guard<std::mutex> lk(ctx->mu);
-      delete s;
-      --ctx->calls_holding_tables;
-    }
-  } held{ctx, nullptr};
-  {
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    PM_HIP(ctx, hipSetDevice(ctx->device));
-    st = ctx->stream;
-    if (world > 1 && !exchange && (!ctx->comm || ctx->comm_world != (int)world || ctx->comm_rank != (int)rank))
-      return set_err(ctx, PM_ERR_EXCHANGE, "no exchange callback and no matching communicator (pm_comm_init)");
-    held.s = new OrderScope(ctx, ctx->ord_ntt, st);
-    ++ctx->calls_holding_tables;   // dt and the tables behind it stay in use across the unlocked exchange steps: no pm_trim
-    int rc = held.s->rc;
-    if (!rc) rc = get_domain_tables(ctx, inverse ? 1 : 0, log_n, coset, &dt, st);
-    if (rc) return rc;
-  }
-  const FsMul none{0, nullptr, nullptr, 0, 0};
-  // one transpose of every vector of the batch: slice [R_loc][C] of a row-distributed [R][C] matrix -> slice [C / W][R]
-  // of its transpose (+ one halo row).  The result is in *where: x -- or, with one rank and no factor on the way in, the
-  // stage buffer itself (the unpack would be a plain copy: the next sub-transform reads it from there; `keep_in_x`
-  // forces the copy)
-  auto transpose = [&](const u32x4* from, u32 R_loc, u32 C, const FsMul& on_pack, const FsMul& on_unpack, bool keep_in_x,
-                       bool halo, const u32x4** where) -> int {
-    const u32 Cw = C / world, Cs = Cw + (halo ? 1u : 0u);
-    const size_t peer_bytes = (size_t)batch * Cs * R_loc * 32;
-    {
-      std::lock_guard<std::mutex> lk(ctx->mu);
-      ProfScope prof(ctx, st, "ntt_fourstep_transpose");
-      hipLaunchKernelGGL(fs_pack_kernel, dim3((C + 31) / 32, (R_loc + 31) / 32, batch), dim3(256), 0, st, from, blk, batch, R_loc,
-                         C, Cw, halo ? 1u : 0u, send, on_pack);
-      PM_HIP(ctx, hipGetLastError());
-      ++ctx->stat_transpose_steps;
-      if (world > 1) {
-        ++ctx->stat_alltoall_calls;
-        ctx->stat_alltoall_bytes += peer_bytes * (world - 1);
-      }
-      if (world > 1 && !exchange) {
-        int rc = comm_alltoall(ctx, send, recv, peer_bytes, st);
-        if (rc) return rc;
-      }
-    }
-    if (world == 1 && on_unpack.mode == 0 && !keep_in_x && !halo) {
-      *where = send;
-      return PM_OK;
-    }
-    if (world > 1 && exchange) {   // the callback sees finished data and returns when the peers' blocks are in place
-      {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        PM_HIP(ctx, hipStreamSynchronize(st));
-      }
-      if (exchange(user, send, recv, peer_bytes) != 0) return set_err(ctx, PM_ERR_EXCHANGE, "the all-to-all callback failed");
-    }
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    ProfScope prof(ctx, st, "ntt_fourstep_transpose");
-    const size_t total = (size_t)Cs * R_loc * world;
-    hipLaunchKernelGGL(fs_unpack_kernel, dim3((unsigned)((total + 255) / 256), batch), dim3(256), 0, st, (const u32x4*)recv, batch,
-                       R_loc, world, Cw, halo ? 1u : 0u, x, blk, (u32x4*)d_halo, on_unpack);
-    PM_HIP(ctx, hipGetLastError());
-    *where = x;
-    return PM_OK;
-  };
-  const uint32_t sub = inverse ? PM_NTT_INVERSE : 0;
-  // PM_NTT_TRANSPOSED: a forward transform leaves its result as the [N1 / W][N2] matrix of step 4 -- X[k2 N1 + k1] at
-  // position k1 N2 + k2, rank r holding rows k1 in [r N1 / W, (r + 1) N1 / W) -- and skips the third all-to-all; an
-  // inverse transform TAKES that layout: with the two factors swapped it is exactly the state after step 1.  What sits
-  // between the two in a prover (the pointwise quotient) does not care about the order.
-  const bool transposed = flags & PM_NTT_TRANSPOSED;
-  const uint32_t la = transposed && inverse ? l2 : l1, lb = log_n - la;   // rows x columns of the input matrix
-  const uint32_t na = 1u << la, nb = 1u << lb;
-  const u32x4* cur = x;
-  int rc = PM_OK;
-  if (!(transposed && inverse)) {
-    // 1: [A/W][B] -> [B/W][A]  (coset_fft: x[n] *= g^n on the way out)
-    FsMul pre = none;
-    if (coset && !inverse) pre = FsMul{2, (const u32x4*)dt->cs_hi, (const u32x4*)dt->cs_lo, dt->lh, rank * (na / world)};
-    rc = transpose(x, na / world, nb, pre, none, false, false, &cur);
-    if (rc) return rc;
-  }
-  // `count` contiguous transforms of 2^lg points, in -> out (the batched passes put the batch on gridDim.y: at most 65535 per launch)
-  auto sub_ntts = [&](const void* in, void* out, uint32_t lg, size_t count) -> int {
-    const size_t len = (size_t)1 << lg;
-    for (size_t done = 0; done < count;) {
-      const uint32_t now = (uint32_t)std::min<size_t>(count - done, 32768);
-      int r = pm_fr_ntt_dev(ctx, (const char*)in + done * len * 32, len, len, (char*)out + done * len * 32, len, lg, now, sub, nullptr);
-      if (r) return r;
-      done += now;
-    }
-    return PM_OK;
-  };
-  // 2: B/W transforms of size A over the columns, every vector of the batch (the blocks are contiguous)
-  rc = sub_ntts(cur, x, la, (size_t)batch * (nb / world));
-  if (rc) return rc;
-  // 3: [B/W][A] -> [A/W][B], element (j, k1) times w^(j k1) on the way out; with a halo one more row: the next rank's first
-  const FsMul tw{1, (const u32x4*)dt->tw_hi, (const u32x4*)dt->tw_lo, dt->lh, rank * (nb / world)};
-  rc = transpose(x, nb / world, na, tw, none, false, want_halo, &cur);
-  if (rc) return rc;
-  // 4: A/W transforms of size B over the rows (and over the halo rows: one per vector, contiguous in d_halo)
-  rc = sub_ntts(cur, x, lb, (size_t)batch * (na / world));
-  if (rc) return rc;
-  if (want_halo) {
-    rc = sub_ntts(d_halo, d_halo, lb, batch);
-    if (rc) return rc;
-  }
-  if (transposed && !inverse) return PM_OK;
-  // 5: [A/W][B] (k1, k2) -> [B/W][A] (k2, k1) = natural order  (coset_ifft: X[k] *= g^-k on the way in)
-  FsMul post = none;
-  if (coset && inverse) post = FsMul{2, (const u32x4*)dt->cs_hi, (const u32x4*)dt->cs_lo, dt->lh, rank * (nb / world)};
-  return transpose(x, na / world, nb, none, post, true, false, &cur);
-}
-
-extern "C" int pm_fr_ntt_fourstep_dev(pm_ctx* ctx, void* d_inout, void* d_stage, uint32_t log_n, uint32_t world,
-                                      uint32_t rank, uint32_t flags, pm_alltoall_fn exchange, void* user) {
-  return pm_fr_ntt_fourstep_batch_dev(ctx, d_inout, 1, nullptr, d_stage, log_n, world, rank, flags, exchange, user);
-}
-
-extern "C" int pm_comm_stats(pm_ctx* ctx, uint64_t out[4], int reset) {
-  if (!ctx) return PM_ERR_BAD_ARG;
-  std::lock_guard<std::mutex> lk(ctx->mu);
-  if (out) {
-    out[0] = ctx->stat_alltoall_calls;
-    out[1] = ctx->stat_alltoall_bytes;
-    out[2] = ctx->stat_allgather_calls;
-    out[3] = ctx->stat_transpose_steps;
-  }
-  if (reset) ctx->stat_alltoall_calls = ctx->stat_alltoall_bytes = ctx->stat_allgather_calls = ctx->stat_transpose_steps = 0;
-  return PM_OK;
 }

@@ -4,12 +4,11 @@
 
 #include <algorithm>
 
-#include "context.h"
+#include "ntt_internal.h"
 #include "ntt_kernels4.hip.h"
 
 namespace pm {
 
-typedef void (*pass_fn)(const NttPassArgs, const NttConsts);
 struct Pass4Entry {
   int S, LT, role;  // role: 0 single, 1 first, 2 middle, 3 last
   pass_fn fn;

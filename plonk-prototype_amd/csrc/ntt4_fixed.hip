@@ -2,12 +2,11 @@
 // decides which launches take them.  A translation unit of its own: the two kernels compile beside ntt4.hip, not behind it.
 #include <hip/hip_runtime.h>
 
-#include "context.h"
+#include "ntt_internal.h"
 #include "ntt_kernels4.hip.h"
 
 namespace pm {
 
-typedef void (*pass_fn)(const NttPassArgs, const NttConsts);
 struct Pass4FixedEntry {
   int FIX, S, LT, role;  // FIX: the log_n the variant is built for; role: 1 first, 3 last
   bool by_default;       // taken with ntt_fixed_shape = 1; the others wait for 2, which is the option's default

@@ -736,7 +736,8 @@ __global__ void ruffini_shift_kernel(const u32x4* coeffs, u32x4* out, size_t m) 
 // of the thread's product is moved to ABI form once, after which inverse(ABI) x anything(device) stays in ABI form.
 // The inversion is the binary GCD of field_inv.hip.h: 1291 instructions per round (ISA count, r06), at most 18 rounds,
 // ~13 on random inputs (the wave leaves when every lane's a is zero) -- ~75 products' worth per thread, every lane of
-// the wave inverting its own product; Q amortises it (host side: Q grows with n, as long as every SIMD keeps two waves).
+// the wave inverting its own product; Q amortises it (host side, fr_batch_inverse_mul: Q grows with n at one wave per SIMD
+// up to Q = 16, Q = 32 beyond).
 struct BinvQuad {
   Fr e[4];       // device form, 1 where the element is zero or beyond the end
   bool live[4];  // a non-zero element inside the vector
